@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: denoising steps/sec @256x256 multimodal-cond, batch=32 per GPU, on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N=1)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]          (N=1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one CFG denoising step for a batch of 32 samples (reference loop body
@@ -15,12 +15,15 @@ Matrix-pipe modes (--matmul), all with fp32 accumulation and fp32 results:
   "bf16x3" (default, the headline `value`) every fp32 operand split EXACTLY into three bf16 planes (24 significant bits: the
            operands ARE the fp32 numbers), six product terms, the dropped ones <= 2^-24 relative — the reference's fp32 arithmetic on
            the bf16 matrix pipe (tests/test_gpu_parity.py bf16x3 suites);
-  "f32"    fp32 MFMA everywhere (the round-1 default);  "bf16x3_strict" nine terms.   Both measured in the same run under "alt".
+  "f32"    fp32 MFMA everywhere (the round-1 default);  "bf16x3_strict" nine terms.   With --full both measured in the same run under "alt".
   "f16x2"  every operand held as two scaled fp16 planes — 22-bit operands, NARROWER than the reference's fp32, so never the headline:
-           reported in the same line as "speed_mode" with its measured error (<= the fp32-MFMA path's on every test of
+           reported (--full) in the same line as "speed_mode" with its measured error (<= the fp32-MFMA path's on every test of
            tests/test_gpu_f16x2.py, scales bounded from the weights so fp16 cannot overflow);
   "bf16"   one bf16 plane: reduced precision, BASELINE config C2 — its error is reported, not gated.
-Every fp32-level mode is GATED: one step against the CPU oracle must agree to 1e-4 or the run exits non-zero.
+A plain run sets up, warms up, times --steps steps, writes their outputs when --dump-outputs DIR is given and prints the line.
+Everything else is measured or checked only with --full, after the timed steps: the per-kernel roofline pass, the clock / power pass,
+the CPU baseline, the other matmul modes ("alt", "speed_mode") and the parity gate — every fp32-level mode run must agree with the
+CPU oracle to 1e-4 on one step or the run exits non-zero.
 The f16x2 engine runs the cond / null CFG halves as two kernel chains on two HIP streams by default (bit-identical results,
 --split-streams 0 turns it off); every per-kernel roofline pass runs single-stream, where a kernel's duration is its own.
 """
@@ -273,6 +276,21 @@ def cpu_state(mods):
     return dict(adapt_v=f(av), adapt_a=f(aa), core=f(core), head=f(head))
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_latent(out_dir: str, z: torch.Tensor) -> None:
+    """DIR/latent.npy: the latents one timed step returned, float32.  The inputs are seeded, so two runs with the same arguments
+    can be compared output for output.  At most DUMP_CAP_BYTES are written, the same ones every run: the leading samples of the
+    batch, or the leading values of the first sample when one sample alone is larger."""
+    import numpy as np
+    per_sample = z[0].numel() * 4
+    out = z[:DUMP_CAP_BYTES // per_sample] if per_sample <= DUMP_CAP_BYTES else z.reshape(-1)[:DUMP_CAP_BYTES // 4]
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "latent.npy", out.float().cpu().numpy())
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -288,13 +306,18 @@ def parse_args(argv=None):
     ap.add_argument("--matmul", default="bf16x3", choices=sorted(MODE_TERMS),
                     help="bf16x3 (default): three bf16 planes per operand (exact fp32 operand split), six product terms; f32: fp32 MFMA "
                          "everywhere; bf16x3_strict: all nine product terms; f16x2: two scaled fp16 planes (22-bit operands; reported as "
-                         "speed_mode, never the headline); bf16: plain bf16 operands (reduced precision, reported error)")
+                         "speed_mode with --full, never the headline); bf16: plain bf16 operands (reduced precision, reported error)")
     ap.add_argument("--attn", default="default", choices=["default", "fp8"],
                     help="fp8: e4m3 QK^T / PV in the attention (reduced precision, BASELINE C5; needs a split matmul mode — f16x2, bf16x3 or bf16; never the default)")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra (untimed-region) measurements of the other matmul modes")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--cpu-steps", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel roofline and clock / power passes, the CPU baseline with the "
+                         "parity gate against the CPU oracle, and the other matmul modes (off: a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the latents the last timed step returned as DIR/latent.npy (float32, rank 0)")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip the extra (untimed-region) measurements of the other matmul modes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity gate")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline and clock / power passes")
+    ap.add_argument("--cpu-steps", type=int, default=3, help="with --full: timed steps of the CPU baseline")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for N > 1 (nccl = RCCL over xGMI; gloo only to rehearse N > 1 on a 1-GPU box)")
     ap.add_argument("--share-device", action="store_true",
@@ -387,7 +410,9 @@ def main():
     abar, sched, z_a0, z0 = ctx["abar"], ctx["sched"], ctx["z_a0"], ctx["z0"]
     mods, tdim = build_modules(dev)
     av, aa, core, head = mods
-    peaks_from_device(dev.index if dev.index is not None else 0)
+    roofline = args.full and not args.no_roofline
+    if roofline:
+        peaks_from_device(dev.index if dev.index is not None else 0)
 
     def make_engine(mode, split="arg"):
         if split == "arg":
@@ -444,6 +469,8 @@ def main():
     D.barrier()
     dt = D.max_over_ranks(time.perf_counter() - t0, ctx["comm_dev"])
     assert torch.isfinite(za).all(), "non-finite latent after the timed region"
+    if args.dump_outputs and rank == 0:
+        dump_latent(args.dump_outputs, za)      # before --full's passes step the same buffers again
     verify = None
     if args.verify_ranks:
         verify = {"conditioning_checksum_per_rank": D.gather_scalars(ctx["cond_checksum"], ctx["comm_dev"]),
@@ -513,14 +540,14 @@ def main():
         return roof, kern, single
 
     # ---- roofline of the dominant kernel: per-launch HIP events on the launch stream, separate instrumented pass
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roofline:
         out["roofline"], out["kernels"], single = instrumented(args.matmul, eng)
         if single is not None:
             out["single_stream_steps_per_s"] = single
 
     # ---- clock and socket power the chip holds on this workload: >= 2.5 s of back-to-back steps of the timed engine, sysfs sampled
     # every 50 ms, medians over what was read after the first second (outside the timed region)
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roofline:
         smp = PowerClockSampler(dev.index if dev.index is not None else 0)
         smp.start()
         p0 = time.perf_counter()
@@ -537,7 +564,7 @@ def main():
     # reference's own MMDiT.forward time in the build container: profiles/r03_cpu_port_speed.json)
     tn = tp = cpu_ref = None
     gate = []          # (mode, err) of every fp32-level mode checked against the oracle
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import ref_cpu as R, ref_cpu_fast as RF
         cores = host_cores()
         torch.set_num_threads(cores)
@@ -569,7 +596,7 @@ def main():
         gate.append((args.matmul, err))
 
     # ---- the other matmul modes, measured the same way right after (N=1 only; never part of `value`)
-    if rank == 0 and world == 1 and not args.no_alt:
+    if rank == 0 and world == 1 and args.full and not args.no_alt:
         alts = []
         for other in ("f32", "bf16x3", "bf16x3_strict", "f16x2"):      # each with its engine's default stream layout
             if other == args.matmul:
@@ -595,7 +622,7 @@ def main():
             alt = {"matmul": other, "value": args.steps / adt, "unit": "steps/s", "ms_per_step": 1e3 * adt / args.steps,
                    "algorithmic_tflops": step_flops_per_sample(nv, na) * B * args.steps / adt / 1e12, "dtype": MODE_DTYPE[other],
                    "cfg_halves": "two HIP streams" if eng2._split_streams else "one stacked 2B batch, one stream"}
-            if not args.no_roofline and other != "bf16x3_strict":
+            if roofline and other != "bf16x3_strict":
                 alt["roofline"], _, single = instrumented(other, eng2)
                 if single is not None:
                     alt["single_stream_steps_per_s"] = single

@@ -181,6 +181,28 @@ def test_bench_flop_model_matches_survey():
         assert abs(got - want) / want < 2e-3, (size, got, want)
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path, monkeypatch):
+    """bench.py's arguments: --full is off by default and --dump-outputs takes a directory; dump_latent writes float32, keeps whole
+    leading samples up to the size cap, and only the leading values of the first sample when one sample alone passes it."""
+    import numpy as np
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+    z = torch.randn(5, 8, 12, 2, 2)
+    bench.dump_latent(str(tmp_path / "out"), z)
+    got = np.load(tmp_path / "out" / "latent.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, z.numpy())
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 3 * z[0].numel() * 4 + 100)
+    bench.dump_latent(str(tmp_path / "out"), z.double())
+    got = np.load(tmp_path / "out" / "latent.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, z[:3].numpy())
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 40 * 4)
+    bench.dump_latent(str(tmp_path / "out"), z)
+    assert np.array_equal(np.load(tmp_path / "out" / "latent.npy"), z.reshape(-1)[:40].numpy())
+
+
 def test_checkpoint_interop(tmp_path, small_model):
     """next-4: both checkpoint layouts of the reference load; the trainer layout reports its embedding mode."""
     import multimodal_diffusion_amd as A

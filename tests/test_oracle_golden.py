@@ -1,7 +1,10 @@
 """CPU: pins the oracle (oracle/ref_cpu.py) to golden vectors produced by the reference itself
 (tools/make_golden.py) and to the reference's own value-level test (patch/unpatch round trip,
 reference tests/test_shapes.py:26-36)."""
+import ctypes
 import json
+import math
+import os
 
 import numpy as np
 import pytest
@@ -11,6 +14,32 @@ from conftest import load_golden, rel_err, split_weights
 from oracle import ref_cpu as R
 
 TOL = 1e-4   # max|Δ| <= TOL * max(1, max|ref|)   
+
+
+def _mkl_branch():
+    """The code branch (MKL_CBWR_* value) MKL's vector math runs in this process, or None: torch's CPU exp / sin / cos go through it."""
+    try:
+        lib = ctypes.CDLL(os.path.join(os.path.dirname(torch.__file__), "lib", "libtorch_cpu.so"))
+        forced = int(lib.mkl_serv_cbwr_get(1))              # MKL_CBWR_BRANCH: a branch MKL_CBWR forced, else 1 / 2 (off / auto)
+        return forced if forced > 2 else int(lib.mkl_serv_cbwr_get_auto_branch())
+    except (OSError, AttributeError):
+        return None
+
+
+# The reference's fp32 timestep embedding was recorded on MKL's AVX-512 branch for Intel CPUs (MKL_CBWR_AVX512 = 12, _AVX512_E1 = 14):
+# there the oracle reproduces it bit for bit.  Other branches round a few exp / sin / cos results differently, and t up to 999
+# magnifies a one-ulp change of a frequency a thousandfold in the angle; temb_ulp_bound is what that allows.
+GOLDEN_BRANCH = _mkl_branch() in (12, 14)
+
+
+def temb_ulp_bound(t, dim):
+    """Largest change of R.timestep_embedding(t, dim) when each frequency moves by one ulp, each angle t * f rounds the other way and
+    each cos / sin is one ulp off on both sides: |t| ulp(f) + ulp(t f) + 2 ulp(1), per element (the odd-dim pad column is exact)."""
+    half = dim // 2
+    t = np.abs(np.asarray(t, dtype=np.float64))[:, None]
+    f = np.exp(-math.log(10000) * np.arange(half) / half).astype(np.float32)[None]
+    b = t * np.spacing(f) + np.spacing((t * f).astype(np.float32)) + 2 * np.spacing(np.float32(1))
+    return np.pad(np.concatenate([b, b], 1), ((0, 0), (0, dim % 2)))
 
 
 def T(a):
@@ -36,7 +65,10 @@ def test_g2_timestep_embedding():
     g = load_golden("g2_temb.npz")
     t = T(g["t"])
     for dim, key in ((256, "e256"), (64, "e64"), (7, "e7")):
-        assert np.array_equal(R.timestep_embedding(t, dim).numpy(), g[key]), dim
+        got = R.timestep_embedding(t, dim).numpy()
+        assert (np.abs(got - g[key]) <= temb_ulp_bound(g["t"], dim)).all(), dim
+        if GOLDEN_BRANCH:
+            assert np.array_equal(got, g[key]), dim
     e0 = R.timestep_embedding(torch.zeros(1, dtype=torch.long), 256)[0]
     assert torch.equal(e0[:128], torch.ones(128)) and torch.equal(e0[128:], torch.zeros(128))
 
@@ -200,7 +232,11 @@ def test_g15_add_mode_step(small_model):
     assert rel_err(z, g["z_next"]) < TOL
     tok_v = R.tube_patch(T(g["z_v"]), 2, 4, 4)
     Xv = R.embed_with_time(tok_v, Wa["adapt_v"]["proj.weight"], Wa["adapt_v"]["proj.bias"], T(g["t_now"]), 0, "add")
-    assert rel_err(Xv, g["X"][:, :tok_v.shape[1]]) < 1e-6
+    X = g["X"][:, :tok_v.shape[1]]
+    bound = temb_ulp_bound(g["t_now"], X.shape[-1])[:, None, :] + 1e-6 * max(1.0, float(np.abs(X).max()))
+    assert (np.abs(Xv.numpy() - X) <= bound).all()
+    if GOLDEN_BRANCH:
+        assert rel_err(Xv, X) < 1e-6
 
 
 def g17_inputs():

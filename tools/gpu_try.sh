@@ -13,7 +13,7 @@ AVD_S3_TILE=1 timeout -k 10 300 python3 tools/micro/s3_ksweep.py --iters 10 --on
 AVD_S3_TILE=0 timeout -k 10 300 python3 tools/micro/s3_ksweep.py --iters 10 --only gelu_split > $OUT/ksweep_tile0.txt 2>&1 || { tail $OUT/ksweep_tile0.txt; exit 1; }
 grep -h "N=" $OUT/ksweep.txt $OUT/ksweep_tile1.txt $OUT/ksweep_tile0.txt
 echo "[$(date +%T)] bench"
-timeout -k 10 500 python3 bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
+timeout -k 10 500 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
 python3 - <<PY
 import json
 d=json.load(open("$OUT/bench.json"))

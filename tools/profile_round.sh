@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 step() { echo "[$(date +%T)] $*" | tee -a $OUT/progress.log; }
-B="timeout -k 10 400 python3 bench.py"
+B="timeout -k 10 400 python3 bench.py --full"
 C2="--size 64 --batch 32 --sampler-steps 100 --steps 100 --warmup 10 --no-alt"
 C5="--size 512 --batch 8 --steps 20 --warmup 3 --no-alt"
 
@@ -45,10 +45,10 @@ AVD_ATTN_M16=0 $B $C5 --no-cpu-baseline > $OUT/bench_ab_c5_attn_32x32.json 2>> $
 
 step "rocprofv3 kernel traces"
 prof() { name=$1; shift; (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -o run -- python3 "$@" > $OUT/prof_$name.log 2>&1) || exit 1; step "  traced $name"; }
-prof bf16x3 $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-alt                                  # the default command (headline mode)
-prof f16x2 $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-alt --matmul f16x2                    # speed mode, its two-stream default
-prof f16x2_single $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-alt --matmul f16x2 --split-streams 0
-prof f32 $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-alt --matmul f32
+prof bf16x3 $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-alt                                  # the headline mode
+prof f16x2 $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-alt --matmul f16x2                    # speed mode, its two-stream default
+prof f16x2_single $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-alt --matmul f16x2 --split-streams 0
+prof f32 $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-alt --matmul f32
 prof vae $ROOT/tools/vae_bench.py --iters 5
 prof vae3 $ROOT/tools/vae_bench.py --iters 5 --matmul bf16x3
 prof vae2 $ROOT/tools/vae_bench.py --iters 5 --matmul f16x2
@@ -71,7 +71,7 @@ step "  util f16x2"
 timeout -k 10 600 python3 tools/pmc_util.py --out gpurun_out/$TAG/util_f32.json -- --matmul f32 > $OUT/util_f32.txt 2>&1 || exit 1
 
 step "N=2 rehearsal (gloo, both ranks on this one GPU)"
-timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 10 --warmup 3 \
+timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --full --steps 10 --warmup 3 \
     --backend gloo --share-device --no-alt --verify-ranks > $OUT/bench_n2.out 2> $OUT/bench_n2.err || exit 1
 grep '^{' $OUT/bench_n2.out > $OUT/bench_n2_gloo_rehearsal.json || exit 1
 
