@@ -144,6 +144,29 @@ int avd_ddim_step_f32(const float* x_t, const float* eps_hat, const int64_t* t_n
                       const float* alpha_bar, int T_train, float eta, const float* noise,
                       float* x_prev, int B, int64_t per_sample, avd_stream_t stream);
 
+/* ---- seeded normal stream of the DDIM eta > 0 noise term (a public contract: the values are fixed by what follows).
+ * For sample s = sample_offset + b of a launch, timestep t = t_now[b] and element e of that sample's latent in its natural layout
+ * ([C,T,H,W] for video, [Ca,F] for audio, row-major):
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (e >> 2, (uint32) s, (uint32) t, 0x44444D31)          (the last word tags this use of the generator)
+ *   (x0, x1, x2, x3) = Philox4x32-10(counter, key)                   (Random123: multipliers 0xD2511F53 / 0xCD9E8D57,
+ *                                                                      key increments 0x9E3779B9 / 0xBB67AE85)
+ *   Box-Muller on each pair (xa, xb) = (x0, x1) -> (n0, n1) and (x2, x3) -> (n2, n3), in fp32:
+ *     u = ((xa >> 8) + 1) * 2^-24  in (0, 1],   v = (xb >> 8) * 2^-24,   r = sqrt(-2 ln u)
+ *     n_even = r cos(2 pi v),  n_odd = r sin(2 pi v)
+ *   element e takes n[e & 3].
+ * The normals are a pure function of (seed, global sample index, t, e): the same bits from avd_gaussian_noise_f32 and from the
+ * fused step, at any batch size, rank count, sample_offset split, eager or graph launch, split_streams, matmul mode or DDIM kernel
+ * variant.  A captured graph draws fresh noise every step because t comes from the device-side schedule cursor. */
+typedef struct {
+    uint64_t seed;
+    int64_t sample_offset;   /* global index of sample 0 of the call; sample_offset + B <= 2^32 */
+} avd_noise_key;
+/* out[b, e] = the stream above for sample sample_offset + b at t_now[b], e < per_sample (< 2^34); out: fp32 [B, per_sample].
+ * Its output can be passed as the explicit `noise` of the DDIM entries. */
+int avd_gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int B, int64_t per_sample,
+                           avd_stream_t stream);
+
 /* ---- a8 fused: CFG combine + tube un-patch + DDIM — avdiff/models/infer/sample_clip.py:381-389.
  * eps2: [2B,Nv,C*t*h*w] (cond batch then null batch); eps = null + g*(cond-null); un-patched on the fly.
  * z, z_out: [B,C,T,H,W]. */
@@ -371,6 +394,11 @@ int64_t avd_step_workspace_bytes(const avd_step_desc* s);
 int avd_denoise_step_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_now,
                          const int64_t* t_prev, const float* noise, float* z_out,
                          void* workspace, int64_t workspace_bytes, avd_stream_t stream);
+/* As avd_denoise_step_f32, with the eta > 0 noise drawn inside the fused CFG + DDIM kernel from the seeded stream (avd_noise_key)
+ * for samples key->sample_offset .. + B - 1 at t_now: no noise buffer, graph-capturable.  With s->eta == 0 it is the plain step. */
+int avd_denoise_step_seeded_f32(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp,
+                                const int64_t* t_now, const int64_t* t_prev, float* z_out,
+                                void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 
 /* ---- a9 / next-1: VideoVAE.decode — avdiff/models/encoders/vae_video3d.py:195-214 (decode), :79-84
  * (_conv_block_3d: Conv3d 3x3x3 pad 1 -> GELU(erf) -> GroupNorm(min(8,C), eps 1e-5, affine)), :108-119.

@@ -63,6 +63,11 @@ class StepDesc(C.Structure):
                 ("guidance", C.c_float), ("eta", C.c_float), ("split_streams", C.c_int)]
 
 
+class NoiseKey(C.Structure):
+    """avd_noise_key: the seeded normal stream of the DDIM eta > 0 noise (contract in include/avdiff_hip.h)."""
+    _fields_ = [("seed", C.c_uint64), ("sample_offset", C.c_int64)]
+
+
 class VaeDecodeDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("Cv", C.c_int), ("Tp", C.c_int), ("Hp", C.c_int), ("Wp", C.c_int),
                 ("T", C.c_int), ("H", C.c_int), ("W", C.c_int),
@@ -120,6 +125,8 @@ SIGNATURES = {
     "avd_head_forward_f32": (_I, [C.POINTER(HeadWeights), _P, _L, _L, _L, _L, _P, _P, _L, _P]),
     "avd_step_workspace_bytes": (_L, [C.POINTER(StepDesc)]),
     "avd_denoise_step_f32": (_I, [C.POINTER(StepDesc), _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "avd_denoise_step_seeded_f32": (_I, [C.POINTER(StepDesc), C.POINTER(NoiseKey), _P, _P, _P, _P, _P, _P, _L, _P]),
+    "avd_gaussian_noise_f32": (_I, [C.POINTER(NoiseKey), _P, _P, _I, _L, _P]),
     "avd_sched_advance": (_I, [_P, _I, _P, _P, _P, _I, _P]),
     "avd_split3_bytes": (_L, [_L, _I]),
     "avd_split3_f32": (_I, [_P, _P, _L, _I, _P]),

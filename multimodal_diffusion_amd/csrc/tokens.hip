@@ -224,6 +224,74 @@ __device__ __forceinline__ float cfg_combine(float e_cond, float e_null, float g
     return e_null + guidance * (e_cond - e_null);
 }
 
+// ------------------------------------------------------------------ seeded normal stream (DDIM eta > 0)
+// The public contract is written out in include/avdiff_hip.h (avd_noise_key).  Element e of sample s at timestep t:
+//   (x0, x1, x2, x3) = Philox4x32-10(counter (e >> 2, s, t, 0x44444D31), key (seed lo, seed hi))   (Random123 constants)
+//   Box-Muller on (x0, x1) -> (n0, n1) and on (x2, x3) -> (n2, n3); e takes n[e & 3]
+// The normals are a pure function of (seed, global sample index, t, element): every kernel that draws them must produce the same
+// bits, so the Box-Muller arithmetic runs without fp contraction (see ddim_apply below) and on the accurate logf / sqrtf / sincospif.
+struct NoiseKey {
+    uint32_t k0, k1;   // seed & 0xffffffff, seed >> 32
+    uint32_t s0;       // global index of sample 0 of the launch
+};
+
+__device__ __forceinline__ f32x4 philox_normal4(const NoiseKey& nk, uint32_t e4, uint32_t s, uint32_t t) {
+#pragma clang fp contract(off)
+    uint32_t c0 = e4, c1 = s, c2 = t, c3 = 0x44444D31u, k0 = nk.k0, k1 = nk.k1;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+        const uint32_t lo0 = 0xD2511F53u * c0, hi0 = __umulhi(0xD2511F53u, c0);
+        const uint32_t lo1 = 0xCD9E8D57u * c2, hi1 = __umulhi(0xCD9E8D57u, c2);
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+    }
+    const float u0 = (float)((c0 >> 8) + 1u) * 5.9604644775390625e-8f, v0 = (float)(c1 >> 8) * 5.9604644775390625e-8f;   // 2^-24
+    const float u1 = (float)((c2 >> 8) + 1u) * 5.9604644775390625e-8f, v1 = (float)(c3 >> 8) * 5.9604644775390625e-8f;
+    const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u1));
+    float s0, co0, s1, co1;
+    sincospif(2.0f * v0, &s0, &co0);
+    sincospif(2.0f * v1, &s1, &co1);
+    return f32x4{r0 * co0, r0 * s0, r1 * co1, r1 * s1};
+}
+
+__global__ __launch_bounds__(256) void gaussian_noise_kernel(const int64_t* __restrict__ t_now, float* __restrict__ out, NoiseKey nk,
+                                                             int64_t per, int64_t per4, int64_t total4) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total4) return;
+    const int b = (int)(i / per4);
+    const int64_t q = i % per4;
+    const f32x4 n = philox_normal4(nk, (uint32_t)q, nk.s0 + (uint32_t)b, (uint32_t)t_now[b]);
+    float* o = out + (int64_t)b * per + q * 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (q * 4 + k < per) o[k] = n[k];
+}
+
+static int make_noise_key(const avd_noise_key* key, int B, NoiseKey& nk) {
+    AVD_REQUIRE(key, AVD_EINVAL, "noise key: null pointer");
+    AVD_REQUIRE(B > 0, AVD_EINVAL, "noise key: B must be > 0 (got %d)", B);
+    AVD_REQUIRE(key->sample_offset >= 0 && key->sample_offset + (int64_t)B <= ((int64_t)1 << 32), AVD_EINVAL,
+                "noise key: sample_offset %lld + B %d must lie in [0, 2^32]", (long long)key->sample_offset, B);
+    nk = NoiseKey{(uint32_t)(key->seed & 0xffffffffu), (uint32_t)(key->seed >> 32), (uint32_t)key->sample_offset};
+    return AVD_OK;
+}
+
+int gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int B, int64_t per, hipStream_t st) {
+    NoiseKey nk;
+    if (int rc = make_noise_key(key, B, nk)) return rc;
+    AVD_REQUIRE(t_now && out, AVD_EINVAL, "gaussian_noise: null pointer");
+    AVD_REQUIRE(per > 0 && per < ((int64_t)1 << 34), AVD_EINVAL, "gaussian_noise: per_sample %lld must be in [1, 2^34)", (long long)per);
+    const int64_t per4 = (per + 3) >> 2, total4 = (int64_t)B * per4;
+    AVD_REQUIRE((total4 + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "gaussian_noise: %lld values is too many for one launch",
+                (long long)B * per);
+    hipLaunchKernelGGL(gaussian_noise_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, t_now, out, nk, per, per4, total4);
+    AVD_CHECK_LAUNCH("gaussian_noise");
+    return AVD_OK;
+}
+
 __global__ __launch_bounds__(256) void ddim_kernel(const float* __restrict__ x, const float* __restrict__ eps,
                                                    const int64_t* __restrict__ t_now, const int64_t* __restrict__ t_prev,
                                                    const float* __restrict__ abar, int T_train, float eta,
@@ -251,10 +319,15 @@ int ddim_step_f32(const float* x_t, const float* eps, const int64_t* t_now, cons
 
 // ------------------------------------------------------------------ fused CFG + unpatch + DDIM (video target)
 int g_cfg_rows = getenv("AVD_CFG_ROWS") ? atoi(getenv("AVD_CFG_ROWS")) : 1;      // avd_tune_set "cfg_rows": 0 = the 16-bytes-per-lane gather form
+// SEEDED: zn comes from the seeded normal stream (philox_normal4: one call is exactly this lane's float4) instead of `noise`.  The key
+// rides as a trailing parameter pack that is empty when !SEEDED, so the unseeded instantiations keep the kernel-argument layout (the
+// hidden arguments such as blockDim sit right behind the explicit ones) and compile to the same code as before the stream existed.
+template <bool SEEDED, class... Key>
 __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const float* __restrict__ eps2, const float* __restrict__ z, const int64_t* __restrict__ t_now,
     const int64_t* __restrict__ t_prev, const float* __restrict__ abar, int T_train, float guidance, float eta,
-    const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int64_t total4) {
+    const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int64_t total4, Key... nk) {
+    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0), "the key is passed iff SEEDED");
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total4) return;
     const int64_t per4 = g.per >> 2;
@@ -266,7 +339,10 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const f32x4 en = *reinterpret_cast<const f32x4*>(eps2 + ((int64_t)B + b) * g.per + toff);
     const f32x4 x = *reinterpret_cast<const f32x4*>(z + lat);
     f32x4 zn = {0.f, 0.f, 0.f, 0.f};
-    if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
+    if constexpr (SEEDED) {
+        const NoiseKey k(nk...);
+        zn = philox_normal4(k, (uint32_t)e4, k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
+    } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
     const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, eta, b);
     f32x4 o;
 #pragma unroll
@@ -283,11 +359,12 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
 // = one 128-byte line of latent per (c, t, h) — reads their cond / null rows as whole contiguous rows (GT x D floats each, 16 B per lane),
 // combines (CFG) in registers, parks the combined eps in LDS as [token][feature] and reads it back as [(c, t, h)][GT x w]: eight lanes then
 // cover one full 128-byte line of z / z_out.  Same arithmetic per element, in the same order: bit-identical to the kernel above.
-template <int GT>      // tokens per block
+template <int GT, bool SEEDED, class... Key>      // tokens per block; SEEDED / Key as cfg_unpatch_ddim_kernel
 __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     const float* __restrict__ eps2, const float* __restrict__ z, const int64_t* __restrict__ t_now,
     const int64_t* __restrict__ t_prev, const float* __restrict__ abar, int T_train, float guidance, float eta,
-    const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int groups_per_sample) {
+    const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int groups_per_sample, Key... nk) {
+    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0), "the key is passed iff SEEDED");
     extern __shared__ __attribute__((aligned(16))) float ebuf[];       // [GT][D + 4]: the pad keeps the transposed 16-byte reads off one bank group
     const int LD = g.D + 4;
     const int b = blockIdx.x / groups_per_sample, grp = blockIdx.x % groups_per_sample;
@@ -317,7 +394,10 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         const int64_t lat = (int64_t)b * g.per + (((int64_t)cc * g.T + (tq * g.t + tt)) * g.H + (hq * g.h + hh)) * g.W + (wq + tok) * g.w + wo;
         const f32x4 x = *reinterpret_cast<const f32x4*>(z + lat);
         f32x4 zn = {0.f, 0.f, 0.f, 0.f};
-        if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
+        if constexpr (SEEDED) {
+            const NoiseKey k(nk...);
+            zn = philox_normal4(k, (uint32_t)((lat - (int64_t)b * g.per) >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
+        } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
         f32x4 o;
 #pragma unroll
         for (int k = 0; k < 4; ++k) o[k] = ddim_apply(c, x[k], e[k], zn[k]);
@@ -325,15 +405,22 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     }
 }
 
+// key != nullptr with eta > 0: the noise term is drawn from the seeded stream inside the kernel (`noise` is not read); eta == 0 ignores both
 int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
-                         int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st) {
+                         int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key) {
     AVD_REQUIRE(eps2 && z && t_now && t_prev && abar && z_out, AVD_EINVAL, "cfg_unpatch_ddim: null pointer");
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "cfg_unpatch_ddim: bad dims");
-    AVD_REQUIRE(eta >= 0.f && (eta == 0.f || noise), AVD_EINVAL, "cfg_unpatch_ddim: eta > 0 needs a noise tensor");
+    AVD_REQUIRE(eta >= 0.f && (eta == 0.f || noise || key), AVD_EINVAL, "cfg_unpatch_ddim: eta > 0 needs a noise tensor or a noise key");
     AVD_REQUIRE(z != z_out, AVD_EINVAL, "cfg_unpatch_ddim: z_out must not alias z");
     Tube g;
     if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
+    const bool seeded = key && eta > 0.f;
+    NoiseKey nk{0u, 0u, 0u};
+    if (seeded) {
+        if (int rc = make_noise_key(key, B, nk)) return rc;
+        AVD_REQUIRE(g.per < ((int64_t)1 << 34), AVD_EINVAL, "cfg_unpatch_ddim: a seeded sample must hold < 2^34 values");
+    }
     const int64_t total4 = (int64_t)B * (g.per >> 2);
     static const int tag = prof_tag_id("cfg_unpatch_ddim_kernel");
     ProfScope prof(tag, 16.0 * (double)B * g.per, st);
@@ -342,27 +429,35 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
     if (g_cfg_rows && (gt == 8 || gt == 4) && g.Wt % gt == 0 && g.D % 4 == 0 && (int64_t)gt * (g.D + 4) * 4 <= 64 * 1024) {
         const int groups = (int)(g.per / g.D) / gt;
         const size_t lds = (size_t)gt * (g.D + 4) * 4;
-        if (gt == 8)
-            hipLaunchKernelGGL(cfg_unpatch_ddim_rows_kernel<8>, dim3((unsigned)(B * groups)), dim3(256), lds, st, eps2, z, t_now, t_prev, abar,
-                               T_train, guidance, eta, noise, z_out, g, B, groups);
+        const dim3 grid((unsigned)(B * groups));
+        if (seeded)
+            hipLaunchKernelGGL((gt == 8 ? cfg_unpatch_ddim_rows_kernel<8, true, NoiseKey> : cfg_unpatch_ddim_rows_kernel<4, true, NoiseKey>), grid,
+                               dim3(256), lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, groups, nk);
         else
-            hipLaunchKernelGGL(cfg_unpatch_ddim_rows_kernel<4>, dim3((unsigned)(B * groups)), dim3(256), lds, st, eps2, z, t_now, t_prev, abar,
-                               T_train, guidance, eta, noise, z_out, g, B, groups);
+            hipLaunchKernelGGL((gt == 8 ? cfg_unpatch_ddim_rows_kernel<8, false> : cfg_unpatch_ddim_rows_kernel<4, false>), grid, dim3(256), lds,
+                               st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, groups);
         AVD_CHECK_LAUNCH("cfg_unpatch_ddim (rows)");
         return AVD_OK;
     }
-    hipLaunchKernelGGL(cfg_unpatch_ddim_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, eps2, z, t_now,
-                       t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4);
+    const dim3 grid((unsigned)((total4 + 255) / 256));
+    if (seeded)
+        hipLaunchKernelGGL((cfg_unpatch_ddim_kernel<true, NoiseKey>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train, guidance,
+                           eta, noise, z_out, g, B, total4, nk);
+    else
+        hipLaunchKernelGGL(cfg_unpatch_ddim_kernel<false>, grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta,
+                           noise, z_out, g, B, total4);
     AVD_CHECK_LAUNCH("cfg_unpatch_ddim");
     return AVD_OK;
 }
 
 // ------------------------------------------------------------------ fused CFG + overlap-add + DDIM (audio target)
+template <bool SEEDED, class... Key>      // as cfg_unpatch_ddim_kernel; one generator call per element (e = c F + f of the sample)
 __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, const float* __restrict__ z,
                                               const int64_t* __restrict__ t_now, const int64_t* __restrict__ t_prev,
                                               const float* __restrict__ abar, int T_train, float guidance, float eta,
                                               const float* __restrict__ noise, float* __restrict__ z_out, int B, int Ca,
-                                              int F, int len, int stride, int Na) {
+                                              int F, int len, int stride, int Na, Key... nk) {
+    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0), "the key is passed iff SEEDED");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)B * Ca * F) return;
     const int f = (int)(i % F);
@@ -389,21 +484,38 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
         e = acc / fmaxf(cnt, 1e-8f);
     }
     const Ddim cf = ddim_coef(t_now, t_prev, abar, T_train, eta, b);
-    z_out[i] = ddim_apply(cf, z[i], e, eta > 0.f ? noise[i] : 0.f);
+    if constexpr (SEEDED) {
+        const NoiseKey k(nk...);
+        const int64_t el = i - (int64_t)b * Ca * F;
+        const f32x4 zn = philox_normal4(k, (uint32_t)(el >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
+        z_out[i] = ddim_apply(cf, z[i], e, zn[(int)(el & 3)]);
+    } else {
+        z_out[i] = ddim_apply(cf, z[i], e, eta > 0.f ? noise[i] : 0.f);
+    }
 }
 
+// key: as cfg_unpatch_ddim_f32
 int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
-                               float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st) {
+                               float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st, const avd_noise_key* key) {
     AVD_REQUIRE(eps2 && z && t_now && t_prev && abar && z_out, AVD_EINVAL, "cfg_untoken_ddim_audio: null pointer");
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "cfg_untoken_ddim_audio: bad chunking");
-    AVD_REQUIRE(eta >= 0.f && (eta == 0.f || noise), AVD_EINVAL, "cfg_untoken_ddim_audio: eta > 0 needs noise");
+    AVD_REQUIRE(eta >= 0.f && (eta == 0.f || noise || key), AVD_EINVAL, "cfg_untoken_ddim_audio: eta > 0 needs noise or a noise key");
     AVD_REQUIRE(z != z_out, AVD_EINVAL, "cfg_untoken_ddim_audio: z_out must not alias z");
+    const bool seeded = key && eta > 0.f;
+    NoiseKey nk{0u, 0u, 0u};
+    if (seeded)
+        if (int rc = make_noise_key(key, B, nk)) return rc;
     const int Na = audio_na(F, len, stride);
     const int64_t n = (int64_t)B * Ca * F;
-    hipLaunchKernelGGL(cfg_untoken_ddim_audio_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, eps2, z, t_now,
-                       t_prev, abar, T_train, guidance, eta, noise, z_out, B, Ca, F, len, stride, Na);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (seeded)
+        hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<true, NoiseKey>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train,
+                           guidance, eta, noise, z_out, B, Ca, F, len, stride, Na, nk);
+    else
+        hipLaunchKernelGGL(cfg_untoken_ddim_audio_kernel<false>, grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train, guidance,
+                           eta, noise, z_out, B, Ca, F, len, stride, Na);
     AVD_CHECK_LAUNCH("cfg_untoken_ddim_audio");
     return AVD_OK;
 }
@@ -569,14 +681,18 @@ extern "C" int avd_cfg_unpatch_ddim_f32(const float* eps2, const float* z, const
     AVD_REQUIRE(aligned16(eps2) && aligned16(z) && aligned16(z_out) && (!noise || aligned16(noise)), AVD_EUNSUPPORTED,
                 "cfg_unpatch_ddim: pointers must be 16-byte aligned");
     return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, C, T, H, W, t,
-                                h, w, static_cast<hipStream_t>(stream));
+                                h, w, static_cast<hipStream_t>(stream), nullptr);
 }
 extern "C" int avd_cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now,
                                               const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance,
                                               float eta, const float* noise, float* z_out, int B, int Ca, int F, int len,
                                               int stride, avd_stream_t stream) {
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, Ca, F,
-                                      len, stride, static_cast<hipStream_t>(stream));
+                                      len, stride, static_cast<hipStream_t>(stream), nullptr);
+}
+extern "C" int avd_gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int B, int64_t per_sample,
+                                      avd_stream_t stream) {
+    return gaussian_noise_f32(key, t_now, out, B, per_sample, static_cast<hipStream_t>(stream));
 }
 extern "C" int avd_sched_advance(const int64_t* sched, int n_sched, int32_t* cursor, int64_t* t_now, int64_t* t_prev,
                                  int B, avd_stream_t stream) {

@@ -5,6 +5,7 @@ allocates the output with torch (plumbing) and enqueues the HIP kernel on torch'
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from typing import Optional
 
@@ -194,6 +195,35 @@ def ddim_step(x_t: Tensor, t_now: Tensor, t_prev: Tensor, eps_hat: Tensor, alpha
     out = torch.empty_like(x_t)
     L.check(L.lib().avd_ddim_step_f32(x_t.data_ptr(), eps_hat.data_ptr(), tn.data_ptr(), tp.data_ptr(), ab.data_ptr(),
                                       ab.numel(), float(eta), L.ptr(nz), out.data_ptr(), B, x_t.numel() // B, _st(x_t)))
+    return out
+
+
+def noise_key(seed: int, sample_offset: int = 0) -> "L.NoiseKey":
+    """avd_noise_key after the checks the engine and gaussian_noise share: 0 <= seed < 2**64, sample_offset >= 0."""
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"noise seed must be an int in [0, 2**64), got {seed!r}")
+    if isinstance(sample_offset, bool) or not isinstance(sample_offset, int) or sample_offset < 0:
+        raise ValueError(f"sample_offset must be an int >= 0, got {sample_offset!r}")
+    return L.NoiseKey(seed, sample_offset)
+
+
+def gaussian_noise(seed: int, sample_offset: int, t_now: Tensor, shape) -> Tensor:
+    """The seeded normal stream of the DDIM eta > 0 noise (avd_gaussian_noise_f32; contract in include/avdiff_hip.h): a
+    float32 tensor of ``shape`` = (B, ...) whose row b holds sample ``sample_offset + b``'s normals at timestep ``t_now[b]``,
+    element e of the row in row-major order of shape[1:].  The same values the seeded DenoiseEngine draws inside its step, so the
+    result can be passed as ``noise`` to ``schedule_utils.ddim_step`` / ``DenoiseEngine.step``.  ``t_now``: int [B] (moved to the
+    current ROCm device if it is not on one)."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) < 1 or shape[0] < 1 or any(s < 1 for s in shape):
+        raise ValueError(f"shape must be (B, ...) with positive sizes, got {shape}")
+    key = noise_key(seed, sample_offset)
+    dev = t_now.device if t_now.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    tn = L.dev_i64(t_now, dev)
+    B = shape[0]
+    if tn.numel() != B:
+        raise ValueError(f"t_now has {tn.numel()} entries, shape asks for {B} samples")
+    out = torch.empty(shape, device=dev, dtype=torch.float32)
+    L.check(L.lib().avd_gaussian_noise_f32(C.byref(key), tn.data_ptr(), out.data_ptr(), B, out.numel() // B, _st(out)))
     return out
 
 

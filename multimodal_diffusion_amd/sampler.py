@@ -126,12 +126,19 @@ class DenoiseEngine:
     step(z, t_now, t_prev)   one step, explicit timesteps (int64 [B] on the device) — parity entry point
     run(z, sched)            whole trajectory with the schedule cursor on the device; ``graph=True`` replays a
                              captured HIP graph per step (no per-step host work beyond one graph launch)
+
+    ``noise_seed`` (extension; default None = the reference's ``randn_like`` per step, schedule_utils.py:197): with eta > 0 the
+    step draws its noise inside the fused CFG + DDIM kernel from the seeded normal stream (include/avdiff_hip.h, avd_noise_key),
+    keyed by (noise_seed, sample_offset + b, t_now[b], element) — no noise buffer, and the graph replay of ``run`` applies as at
+    eta == 0.  ``sample_offset`` is the global index of this batch's sample 0 (a batch that is one slice of a larger job draws the
+    same noise as the whole job would).  Both are fixed at construction; a captured graph holds them by value.
     """
 
     def __init__(self, *, adapt_v: LinearAdapter, adapt_a: LinearAdapter, core: MMDiT, head: MultiModalNoiseHead,
                  tstep_dim: int, target: str, latent_shape: Tuple[int, ...], prompt_tokens: int, alpha_bar: torch.Tensor,
                  guidance: float, eta: float = 0.0, tube=(2, 4, 4), chunk=(4, 4), split_streams: Optional[bool] = None,
-                 temb_mode: str = "concat", matmul: Optional[str] = None, attn: Optional[str] = None):
+                 temb_mode: str = "concat", matmul: Optional[str] = None, attn: Optional[str] = None,
+                 noise_seed: Optional[int] = None, sample_offset: int = 0):
         if target not in ("video", "audio"):
             raise ValueError("target must be 'video' or 'audio'")
         if eta < 0:
@@ -152,6 +159,12 @@ class DenoiseEngine:
             raise L.AvdError("DenoiseEngine needs its modules on a ROCm device (no CPU fallback)")
         self.latent_shape = tuple(int(s) for s in latent_shape)      # with batch dim
         B = self.latent_shape[0]
+        self.noise_seed, self.sample_offset = noise_seed, int(sample_offset)
+        self._key = None if noise_seed is None else Fn.noise_key(noise_seed, sample_offset)
+        if self._key is None and sample_offset != 0:
+            raise ValueError("sample_offset keys the seeded noise: it needs noise_seed")
+        if self._key is not None and sample_offset + B > 2 ** 32:
+            raise ValueError(f"sample_offset {sample_offset} + batch {B} exceeds the stream's 2**32 sample indices")
         e = L.EmbedDesc()
         e.B, e.d, e.tdim = B, self.d, self.tdim
         if target == "video":
@@ -329,9 +342,16 @@ class DenoiseEngine:
         tn, tp = L.dev_i64(t_now, self.device), L.dev_i64(t_prev, self.device)
         if not torch.cuda.is_current_stream_capturing():
             self._sync_weights()
+        out = torch.empty_like(z) if out is None else out
+        if self._key is not None:
+            if noise is not None:
+                raise ValueError("this engine draws its noise from noise_seed: do not pass `noise` as well")
+            L.check(L.lib().avd_denoise_step_seeded_f32(C.byref(self.desc), C.byref(self._key), z.data_ptr(), self.Xp.data_ptr(),
+                                                        tn.data_ptr(), tp.data_ptr(), out.data_ptr(), self.workspace.data_ptr(),
+                                                        self.workspace.numel(), L.stream_ptr(self.device)))
+            return out
         if self.eta > 0 and noise is None:
             noise = torch.randn_like(z)
-        out = torch.empty_like(z) if out is None else out
         L.check(L.lib().avd_denoise_step_f32(C.byref(self.desc), z.data_ptr(), self.Xp.data_ptr(), tn.data_ptr(),
                                              tp.data_ptr(), L.ptr(noise), out.data_ptr(), self.workspace.data_ptr(),
                                              self.workspace.numel(), L.stream_ptr(self.device)))
@@ -366,8 +386,8 @@ class DenoiseEngine:
 
     def capture_pair(self, za: torch.Tensor, zb: torch.Tensor) -> "_CapturedPair":
         """Capture two steps (za -> zb -> za) into one HIP graph; replaying it advances the trajectory by two."""
-        if self.eta > 0:
-            raise NotImplementedError("graph replay with eta > 0 would replay the same noise")
+        if self.eta > 0 and self._key is None:
+            raise NotImplementedError("graph replay with eta > 0 would replay the same noise (build the engine with noise_seed)")
         self._sync_weights()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
@@ -379,10 +399,10 @@ class DenoiseEngine:
 
     def run(self, z: torch.Tensor, sched: torch.Tensor, graph: Optional[bool] = None) -> torch.Tensor:
         """Apply len(sched)-1 steps.  ``graph=True`` replays a captured two-step HIP graph; ``None`` (default) does so when the
-        batch is small enough for the step to be launch-bound (2B*N < 6,144 rows, eta == 0) — results are bit-identical either
-        way (tests: test_chained_sampler_golden)."""
+        batch is small enough for the step to be launch-bound (2B*N < 6,144 rows, eta == 0 or a seeded engine) — results are
+        bit-identical either way (tests: test_chained_sampler_golden, test_gpu_seeded_noise)."""
         if graph is None:
-            graph = self.eta == 0 and 2 * self.embed.B * self.N < self.GRAPH_BELOW_ROWS
+            graph = (self.eta == 0 or self._key is not None) and 2 * self.embed.B * self.N < self.GRAPH_BELOW_ROWS
         self.begin(sched)
         za = L.dev_f32(z, "z").clone()
         zb = torch.empty_like(za)
@@ -411,11 +431,15 @@ class DenoiseEngine:
 def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapter, adapt_a: LinearAdapter,
                          core: MMDiT, head: MultiModalNoiseHead, tstep_dim: int, prompt_modality: str,
                          prompt_video: Optional[np.ndarray], prompt_audio: Optional[np.ndarray],
-                         device: torch.device, init_noise: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:
+                         device: torch.device, init_noise: Optional[torch.Tensor] = None,
+                         noise_seed: Optional[int] = None) -> Dict[str, np.ndarray]:
     """sample_clip.py:220-394 with the loop on the HIP engine.  The V->A branch uses the [1,3,T,H,W] layout the
     reference's comment intends (its own permute at :288 is a bug that crashes in conv3d).
     ``init_noise`` (extension; default None = draw it as the reference does, :297 / :304): the target's initial latent, so that a
-    run can be repeated across devices — the reference's only RNG draw comes from the device generator."""
+    run can be repeated across devices — the reference's only RNG draw comes from the device generator.
+    ``noise_seed`` (extension; default None = the reference's per-step ``randn_like``): with ``sampling.ddim_eta`` > 0 the per-step
+    DDIM noise comes from the seeded stream (DenoiseEngine ``noise_seed``), so the whole trajectory repeats from (init_noise,
+    noise_seed)."""
     dcfg, scfg = cfg["diffusion"], cfg["sampling"]
     eta = float(scfg.get("ddim_eta", 0.0))
     t_p, p = int(cfg["tokenizer"]["video"]["tube"]["t"]), int(cfg["tokenizer"]["video"]["tube"]["h"])
@@ -459,7 +483,7 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
     abar, sched = table(target)
     eng = DenoiseEngine(adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, target=target,
                         latent_shape=tuple(z.shape), prompt_tokens=n_prompt, alpha_bar=abar, guidance=guide, eta=eta,
-                        tube=(t_p, p, p), chunk=(l_chunk, s_chunk))
+                        tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed)
     eng.set_prompt(z_p.float())
     z = eng.run(z, sched)
     if target == "audio":

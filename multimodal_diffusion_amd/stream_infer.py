@@ -113,12 +113,16 @@ def crossfade_video(chunks: np.ndarray, hop: int, win: int, fade_f: int, device=
 def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, head, tstep_dim: int, prompt_modality: str,
                     prompt_video: Optional[np.ndarray], prompt_audio: Optional[np.ndarray], device: torch.device,
                     init_noise: Optional[torch.Tensor] = None, max_windows_per_batch: int = 32, shard: bool = False,
-                    seed: Optional[int] = None, comm_device: Optional[torch.device] = None) -> Optional[Dict[str, np.ndarray]]:
+                    seed: Optional[int] = None, comm_device: Optional[torch.device] = None,
+                    noise_seed: Optional[int] = None) -> Optional[Dict[str, np.ndarray]]:
     """The body of the reference's ``main()`` (stream_infer.py:146-225) minus file I/O, with all windows batched.
 
     Returns {"audio": wav, "sr"} for a video prompt or {"video": frames uint8, "fps"} for an audio prompt.
     ``init_noise`` [N_windows, *latent] fixes the initial latents (the reference draws them window by window); ``seed`` draws them
-    from a CPU generator for the WHOLE window list instead (the same numbers whatever the number of ranks).
+    from a CPU generator for the WHOLE window list instead (the same numbers whatever the number of ranks).  ``noise_seed`` does the
+    same for the per-step DDIM noise of ``sampling.ddim_eta`` > 0 (default None: the reference's per-step ``randn_like`` from the device
+    generator): window i draws its noise as sample i of the seeded stream (DenoiseEngine ``noise_seed`` / ``sample_offset``), whatever
+    batch or rank steps it.
 
     ``shard=True`` (every rank of the default process group calls this with the same arguments; one process per GPU): rank 0 encodes
     the prompt windows, ONE broadcast (``dist.broadcast_conditioning``; over ``comm_device``, default: ``device`` for the nccl = RCCL
@@ -129,7 +133,8 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     If rank 0 fails before the broadcast (encode error, a prompt shape the config does not imply), every rank raises.
     Windows never interact inside the loop or the decode, so the stitched output equals the single-process one bit for bit as long as
     both runs take the same kernels (the matrix-pipe mode "auto" switches kernels at 2,048 / 6,144 rows: fix ``core.matmul`` to
-    compare across sizes).
+    compare across sizes).  With ``ddim_eta`` > 0 this holds when ``noise_seed`` is set (then also for any ``max_windows_per_batch``);
+    without it every rank draws from its own device generator.
     """
     st = cfg.get("streaming", {})
     win_s, hop_s = float(st.get("window_seconds", 3.0)), float(st.get("hop_seconds", 1.0))
@@ -212,7 +217,8 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
             hi = min(hi0, lo + max_windows_per_batch)
             eng = DenoiseEngine(adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, target=target,
                                 latent_shape=(hi - lo, *lat), prompt_tokens=n_prompt, alpha_bar=abar, guidance=guide, eta=eta,
-                                tube=(t_p, p, p), chunk=(l_chunk, s_chunk))
+                                tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed,
+                                sample_offset=lo if noise_seed is not None else 0)
             eng.set_prompt(zp_part[lo - lo0:hi - lo0].to(device).float().contiguous())
             outs.append(eng.run(z0[lo:hi].to(device).contiguous(), sched))
         if not outs:

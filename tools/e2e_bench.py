@@ -20,6 +20,14 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=32)
 ap.add_argument("--size", type=int, default=256)
 ap.add_argument("--sampler-steps", type=int, default=50)
+ap.add_argument("--eta", type=float, default=None,
+                help="time only the sampler loop, both directions, at eta = 0 against eta = ETA (DDIM noise per step) instead of the "
+                     "end-to-end runs; the variants run interleaved in one process")
+ap.add_argument("--noise", choices=("both", "seeded", "unseeded"), default="both",
+                help="with --eta: the eta > 0 noise source(s) to time — seeded (the in-kernel stream of DenoiseEngine(noise_seed=...)) "
+                     "and / or unseeded (torch.randn_like per step)")
+ap.add_argument("--matmul", default="bf16x3", help="with --eta: matrix-pipe mode (default: bench.py's headline mode)")
+ap.add_argument("--reps", type=int, default=5, help="with --eta: interleaved rounds; the median per variant is printed")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 B, S, size = args.batch, args.sampler_steps, args.size
@@ -31,6 +39,44 @@ abar = su.alphas_cumprod_from_betas(su.make_beta_schedule(1000, "cosine", 1e-4, 
 sched = su.make_sampling_schedule(1000, S)
 z0 = torch.randn(B, 8, 12, size // 8, size // 8, generator=torch.Generator().manual_seed(1)).to(dev)
 za = torch.randn(B, 8, 150, generator=torch.Generator().manual_seed(2)).to(dev)
+
+if args.eta is not None:
+    # eta > 0 cost: the same trajectory at eta = 0, at eta = ETA with torch.randn_like noise per step (eager: a captured graph would
+    # replay one draw) and at eta = ETA with the seeded in-kernel stream (graph replay where run() takes it, as at eta = 0)
+    import statistics
+    variants = [("eta=0", 0.0, None)]
+    if args.noise in ("both", "unseeded"):
+        variants.append((f"eta={args.eta:g} unseeded", args.eta, None))
+    if args.noise in ("both", "seeded"):
+        variants.append((f"eta={args.eta:g} seeded", args.eta, 1234))
+    zv_prompt = torch.randn(B, 8, 12, size // 8, size // 8, generator=torch.Generator().manual_seed(3)).to(dev)
+    for target, z_init, prompt, n_prompt in (("video", z0, za, 37), ("audio", za, zv_prompt, (12 // 2) * (size // 8 // 4) ** 2)):
+        engs = []
+        for name, eta, seed in variants:
+            eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=tdim, target=target,
+                                  latent_shape=tuple(z_init.shape), prompt_tokens=n_prompt, alpha_bar=abar, guidance=3.5, eta=eta,
+                                  matmul=args.matmul, noise_seed=seed)
+            eng.set_prompt(prompt)
+            eng.run(z_init, sched[:4])                  # warm-up (a graph-replaying variant captures here too)
+            engs.append(eng)
+        times = {name: [] for name, _, _ in variants}
+        for _ in range(args.reps):
+            for (name, _, _), eng in zip(variants, engs):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                eng.run(z_init, sched)
+                torch.cuda.synchronize()
+                times[name].append(1e3 * (time.perf_counter() - t0) / S)
+        base = statistics.median(times["eta=0"])
+        direction = "A->V" if target == "video" else "V->A"
+        rows = 2 * B * (engs[0].N)
+        for (name, _, _), eng in zip(variants, engs):
+            med = statistics.median(times[name])
+            graph = (eng.eta == 0 or eng.noise_seed is not None) and rows < eng.GRAPH_BELOW_ROWS
+            print(f"[{args.matmul}] {direction} B={B} {size}x{size} {name:18s}: {med:7.3f} ms/step (min {min(times[name]):7.3f}, "
+                  f"{args.reps} rounds of {S} steps, {'graph' if graph else 'eager'})  {100 * (med / base - 1):+6.2f} % vs eta=0", flush=True)
+    sys.exit(0)
+
 for mode in ("f32", "bf16x3", "f16x2"):
     vae.matmul = mode
     eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=tdim, target="video", latent_shape=tuple(z0.shape),
