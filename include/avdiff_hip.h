@@ -144,6 +144,28 @@ int avd_ddim_step_f32(const float* x_t, const float* eps_hat, const int64_t* t_n
                       const float* alpha_bar, int T_train, float eta, const float* noise,
                       float* x_prev, int B, int64_t per_sample, avd_stream_t stream);
 
+/* ---- DPM-Solver++(2M) update (multistep, data prediction, eta == 0) — an opt-in alternative to DDIM (a public contract).
+ * For a timestep tau: a(tau) = alpha_bar[clamp(tau, 0, T_train-1)] for tau >= 0 and a(-1) = 1;
+ *   alpha = sqrt(a), sigma = sqrt(1 - a), lambda = log alpha - log sigma.
+ * One step goes from s = t_now to t = t_prev; the step before it came from u = t_last (t_last < 0: no history).  Per element:
+ *   1. eps  = the CFG-combined noise prediction (fused step: exactly as DDIM's);
+ *   2. x0_s = (x_s - sqrt(1 - a_s) eps) / max(sqrt(a_s), 1e-8) in fp32, the same expression and rounding as DDIM's x0
+ *      (t_now < 0 is read as 0, as in DDIM);
+ *   3. per-sample coefficients, computed in fp64 from the fp32 table and rounded once to fp32:
+ *        c_x = sigma_t / sigma_s,  k = alpha_t - c_x alpha_s;
+ *        second order when t_last >= 0, t_prev >= 0, sigma_t > 0 and lambda_u < lambda_s < lambda_t:
+ *          h = lambda_t - lambda_s,  r = (lambda_s - lambda_u) / h,  c_0 = k (1 + 1/(2r)),  c_1 = -k/(2r);
+ *        otherwise first order: c_0 = k, c_1 = 0 (the first step, the final step to t_prev = -1, a non-increasing lambda);
+ *        sigma_s = 0 (a_s == 1.0f): c_x = 0, c_0 = 1, c_1 = 0 (the step returns x0_s);
+ *   4. z_out = (c_x x_s + c_0 x0_s) + c_1 x0_hist in fp32, in that order, without contraction; when c_1 == 0 the last term is
+ *      not added and x0_hist is not read (it may hold anything).  Then x0_hist <- x0_s, each element read before it is written.
+ * A first-order step is DDIM at eta = 0 in exact arithmetic; at t_prev = -1 both return x0_s bit for bit.
+ * x_t, eps_hat, x0_hist, x_out: fp32 [B, per_sample]; t_last, t_now, t_prev: int64 [B].  x0_hist must not overlap x_t, eps_hat or
+ * x_out. */
+int avd_dpmpp_2m_step_f32(const float* x_t, const float* eps_hat, float* x0_hist, const int64_t* t_last, const int64_t* t_now,
+                          const int64_t* t_prev, const float* alpha_bar, int T_train, float* x_out, int B, int64_t per_sample,
+                          avd_stream_t stream);
+
 /* ---- seeded normal stream of the DDIM eta > 0 noise term (a public contract: the values are fixed by what follows).
  * For sample s = sample_offset + b of a launch, timestep t = t_now[b] and element e of that sample's latent in its natural layout
  * ([C,T,H,W] for video, [Ca,F] for audio, row-major):
@@ -399,6 +421,13 @@ int avd_denoise_step_f32(const avd_step_desc* s, const float* z, const float* Xp
 int avd_denoise_step_seeded_f32(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp,
                                 const int64_t* t_now, const int64_t* t_prev, float* z_out,
                                 void* workspace, int64_t workspace_bytes, avd_stream_t stream);
+/* As avd_denoise_step_f32, ending in the DPM-Solver++(2M) update (avd_dpmpp_2m_step_f32) inside the fused CFG kernel instead of DDIM:
+ * t_last: int64 [B] (< 0: first order); x0_hist: fp32 [B, per_sample] in the latent's natural layout, read by second-order steps and
+ * overwritten with this step's x0.  Requires s->eta == 0 (the SDE variant is not implemented); x0_hist must not alias z or z_out.
+ * Graph-capturable: x0_hist stays at its address from step to step. */
+int avd_denoise_step_dpmpp_2m_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_last,
+                                  const int64_t* t_now, const int64_t* t_prev, float* x0_hist, float* z_out,
+                                  void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 
 /* ---- a9 / next-1: VideoVAE.decode — avdiff/models/encoders/vae_video3d.py:195-214 (decode), :79-84
  * (_conv_block_3d: Conv3d 3x3x3 pad 1 -> GELU(erf) -> GroupNorm(min(8,C), eps 1e-5, affine)), :108-119.
@@ -503,6 +532,10 @@ int avd_crossfade_u8(const uint8_t* chunks, const float* w, uint8_t* out, int N,
  * t_now[b] = sched[*cursor], t_prev[b] = sched[*cursor+1] for all b, then (*cursor)++ . */
 int avd_sched_advance(const int64_t* sched, int n_sched, int32_t* cursor, int64_t* t_now, int64_t* t_prev,
                       int B, avd_stream_t stream);
+/* As avd_sched_advance, and t_last[b] = sched[*cursor - 1] when *cursor > 0, else -1 (the multistep solver's history step).
+ * A cursor past the end repeats the last step, with its own t_last. */
+int avd_sched_advance_ms(const int64_t* sched, int n_sched, int32_t* cursor, int64_t* t_last, int64_t* t_now, int64_t* t_prev,
+                         int B, avd_stream_t stream);
 
 /* ---- measurement hooks (bench.py): when enabled, every kernel launch made by this library is bracketed by
  * hipEvents recorded on the launch stream and tagged with its kernel name (template arguments included, so the

@@ -214,15 +214,76 @@ __device__ __forceinline__ Ddim ddim_coef(const int64_t* t_now, const int64_t* t
 // No fp contraction in these two: the reference evaluates them as separate torch ops, one rounding each (schedule_utils.py:186-199,
 // sample_clip.py:381), and hipcc's default -ffp-contract=fast picks its fused multiply-adds per CALL SITE — the same expression came out one
 // ulp apart in two kernels of this file (round 5: the whole-line CFG kernel against the gather form; round 4 met the same in split8).
+// ddim_x0 is also the x0 of the DPM-Solver++(2M) update below: one expression, one rounding, the same bits in both solvers.
+__device__ __forceinline__ float ddim_x0(const Ddim& c, float x, float e) {
+#pragma clang fp contract(off)
+    return (x - c.sqrt_omb_t * e) / c.den;
+}
 __device__ __forceinline__ float ddim_apply(const Ddim& c, float x, float e, float zn) {
 #pragma clang fp contract(off)
-    const float x0 = (x - c.sqrt_omb_t * e) / c.den;
+    const float x0 = ddim_x0(c, x, e);
     return c.sqrt_a_prev * x0 + c.coeff_eps * e + c.sigma * zn;
 }
 __device__ __forceinline__ float cfg_combine(float e_cond, float e_null, float guidance) {
 #pragma clang fp contract(off)
     return e_null + guidance * (e_cond - e_null);
 }
+
+// ------------------------------------------------------------------ DPM-Solver++(2M) (data prediction, multistep, eta == 0)
+// The contract is written out in include/avdiff_hip.h (avd_dpmpp_2m_step_f32).  One step s = t_now -> t = t_prev with the previous
+// step's u = t_last (< 0: no history):  z_out = (c_x x_s + c_0 x0_s) + c_1 x0_hist,  then x0_hist <- x0_s.  The coefficients come
+// from the fp32 table in fp64 and are rounded once to fp32, so every form of the update (the elementwise kernel, the three fused CFG
+// kernels) and the numpy mirror of the tests agree on them bit for bit.
+struct Dpm {
+    float c_x, c_0, c_1;     // c_1 == 0: first order (x0_hist is not read)
+};
+
+// a(tau) of the contract: alpha_bar[clamp(tau, 0, T-1)] for tau >= 0, 1 for tau < 0
+__device__ __forceinline__ float dpm_abar(const float* abar, int T_train, long long tau) {
+    return tau < 0 ? 1.0f : abar[tau > T_train - 1 ? T_train - 1 : tau];
+}
+
+__device__ __forceinline__ Dpm dpm_coef(const int64_t* t_last, const int64_t* t_now, const int64_t* t_prev, const float* abar,
+                                        int T_train, int b) {
+#pragma clang fp contract(off)
+    const long long tu = t_last[b], tp = t_prev[b];
+    long long ts = t_now[b];
+    if (ts < 0) ts = 0;                                  // as ddim_coef: x0_s is DDIM's x0
+    const double as = (double)dpm_abar(abar, T_train, ts), at = (double)dpm_abar(abar, T_train, tp);
+    const double al_s = sqrt(as), sg_s = sqrt(fmax(1.0 - as, 0.0));
+    const double al_t = sqrt(at), sg_t = sqrt(fmax(1.0 - at, 0.0));
+    if (sg_s == 0.0) return Dpm{0.f, 1.f, 0.f};         // a_s == 1: x_s is x0_s, return it
+    const double cx = sg_t / sg_s;
+    const double k = al_t - cx * al_s;
+    double c0 = k, c1 = 0.0;
+    // second order needs a history step, a finite target lambda (sigma_t > 0: not the final step) and lambda_u < lambda_s < lambda_t
+    if (tu >= 0 && tp >= 0 && sg_t > 0.0) {
+        const double au = (double)dpm_abar(abar, T_train, tu);
+        const double al_u = sqrt(au), sg_u = sqrt(fmax(1.0 - au, 0.0));
+        const double lu = log(al_u) - log(sg_u), ls = log(al_s) - log(sg_s), lt = log(al_t) - log(sg_t);
+        if (lu < ls && ls < lt) {
+            const double h = lt - ls, r = (ls - lu) / h;
+            c0 = k * (1.0 + 1.0 / (2.0 * r));
+            c1 = -k / (2.0 * r);
+        }
+    }
+    return Dpm{(float)cx, (float)c0, (float)c1};
+}
+
+__device__ __forceinline__ float dpm_apply(const Dpm& c, float x, float x0, float hist) {
+#pragma clang fp contract(off)
+    const float y = c.c_x * x + c.c_0 * x0;
+    return c.c_1 != 0.f ? y + c.c_1 * hist : y;
+}
+
+// The fused CFG kernels below take the solver's state as their trailing parameter pack: empty (DDIM, the instantiations that
+// existed before the solver, unchanged), NoiseKey (seeded DDIM noise) or DpmState (this solver).
+struct DpmState {
+    const int64_t* t_last;   // int64 [B]
+    float* x0_hist;          // [B, per] in the latent's natural layout: read (second-order steps), then overwritten with x0_s
+};
+template <class... X> struct IsDpm { static constexpr bool value = false; };
+template <> struct IsDpm<DpmState> { static constexpr bool value = true; };
 
 // ------------------------------------------------------------------ seeded normal stream (DDIM eta > 0)
 // The public contract is written out in include/avdiff_hip.h (avd_noise_key).  Element e of sample s at timestep t:
@@ -317,17 +378,52 @@ int ddim_step_f32(const float* x_t, const float* eps, const int64_t* t_now, cons
     return AVD_OK;
 }
 
+// true when [a, a + n) and [b, b + n) overlap (n floats each)
+static bool overlaps(const float* a, const float* b, int64_t n) { return a < b + n && b < a + n; }
+
+__global__ __launch_bounds__(256) void dpmpp_2m_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                                       float* __restrict__ x0_hist, const int64_t* __restrict__ t_last,
+                                                       const int64_t* __restrict__ t_now, const int64_t* __restrict__ t_prev,
+                                                       const float* __restrict__ abar, int T_train, float* __restrict__ out,
+                                                       int64_t per, int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int b = (int)(i / per);
+    const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, 0.f, b);
+    const Dpm d = dpm_coef(t_last, t_now, t_prev, abar, T_train, b);
+    const float x0 = ddim_x0(c, x[i], eps[i]);
+    out[i] = dpm_apply(d, x[i], x0, d.c_1 != 0.f ? x0_hist[i] : 0.f);
+    x0_hist[i] = x0;
+}
+
+int dpmpp_2m_step_f32(const float* x_t, const float* eps, float* x0_hist, const int64_t* t_last, const int64_t* t_now,
+                      const int64_t* t_prev, const float* abar, int T_train, float* x_out, int B, int64_t per, hipStream_t st) {
+    AVD_REQUIRE(x_t && eps && x0_hist && t_last && t_now && t_prev && abar && x_out, AVD_EINVAL, "dpmpp_2m_step: null pointer");
+    AVD_REQUIRE(B > 0 && per > 0 && T_train > 0, AVD_EINVAL, "dpmpp_2m_step: bad dims");
+    const int64_t total = (int64_t)B * per;
+    AVD_REQUIRE(!overlaps(x0_hist, x_t, total) && !overlaps(x0_hist, eps, total) && !overlaps(x0_hist, x_out, total), AVD_EINVAL,
+                "dpmpp_2m_step: x0_hist must not overlap x_t, eps_hat or x_out");
+    AVD_REQUIRE((total + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "dpmpp_2m_step: %lld values is too many for one launch",
+                (long long)total);
+    hipLaunchKernelGGL(dpmpp_2m_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x_t, eps, x0_hist, t_last, t_now,
+                       t_prev, abar, T_train, x_out, per, total);
+    AVD_CHECK_LAUNCH("dpmpp_2m_step");
+    return AVD_OK;
+}
+
 // ------------------------------------------------------------------ fused CFG + unpatch + DDIM (video target)
 int g_cfg_rows = getenv("AVD_CFG_ROWS") ? atoi(getenv("AVD_CFG_ROWS")) : 1;      // avd_tune_set "cfg_rows": 0 = the 16-bytes-per-lane gather form
 // SEEDED: zn comes from the seeded normal stream (philox_normal4: one call is exactly this lane's float4) instead of `noise`.  The key
 // rides as a trailing parameter pack that is empty when !SEEDED, so the unseeded instantiations keep the kernel-argument layout (the
 // hidden arguments such as blockDim sit right behind the explicit ones) and compile to the same code as before the stream existed.
+// A DpmState in the pack (SEEDED false) replaces the DDIM update by the DPM-Solver++(2M) one (dpm_coef / dpm_apply) on the same x0.
 template <bool SEEDED, class... Key>
 __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const float* __restrict__ eps2, const float* __restrict__ z, const int64_t* __restrict__ t_now,
     const int64_t* __restrict__ t_prev, const float* __restrict__ abar, int T_train, float guidance, float eta,
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int64_t total4, Key... nk) {
-    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0), "the key is passed iff SEEDED");
+    constexpr bool DPM = IsDpm<Key...>::value;
+    static_assert(sizeof...(Key) == (SEEDED || DPM ? 1 : 0) && !(SEEDED && DPM), "one key (SEEDED) or one DpmState, or nothing");
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total4) return;
     const int64_t per4 = g.per >> 2;
@@ -345,10 +441,23 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
     const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, eta, b);
     f32x4 o;
+    if constexpr (DPM) {
+        const DpmState ds(nk...);
+        const Dpm d = dpm_coef(ds.t_last, t_now, t_prev, abar, T_train, b);
+        f32x4 hist = {0.f, 0.f, 0.f, 0.f}, x0;
+        if (d.c_1 != 0.f) hist = *reinterpret_cast<const f32x4*>(ds.x0_hist + lat);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float e = cfg_combine(ec[k], en[k], guidance);
-        o[k] = ddim_apply(c, x[k], e, zn[k]);
+        for (int k = 0; k < 4; ++k) {
+            x0[k] = ddim_x0(c, x[k], cfg_combine(ec[k], en[k], guidance));
+            o[k] = dpm_apply(d, x[k], x0[k], hist[k]);
+        }
+        *reinterpret_cast<f32x4*>(ds.x0_hist + lat) = x0;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float e = cfg_combine(ec[k], en[k], guidance);
+            o[k] = ddim_apply(c, x[k], e, zn[k]);
+        }
     }
     *reinterpret_cast<f32x4*>(z_out + lat) = o;
 }
@@ -364,7 +473,8 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     const float* __restrict__ eps2, const float* __restrict__ z, const int64_t* __restrict__ t_now,
     const int64_t* __restrict__ t_prev, const float* __restrict__ abar, int T_train, float guidance, float eta,
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int groups_per_sample, Key... nk) {
-    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0), "the key is passed iff SEEDED");
+    constexpr bool DPM = IsDpm<Key...>::value;
+    static_assert(sizeof...(Key) == (SEEDED || DPM ? 1 : 0) && !(SEEDED && DPM), "one key (SEEDED) or one DpmState, or nothing");
     extern __shared__ __attribute__((aligned(16))) float ebuf[];       // [GT][D + 4]: the pad keeps the transposed 16-byte reads off one bank group
     const int LD = g.D + 4;
     const int b = blockIdx.x / groups_per_sample, grp = blockIdx.x % groups_per_sample;
@@ -382,6 +492,8 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     }
     __syncthreads();
     const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, eta, b);
+    [[maybe_unused]] Dpm d{0.f, 0.f, 0.f};
+    if constexpr (DPM) d = dpm_coef(DpmState(nk...).t_last, t_now, t_prev, abar, T_train, b);
     // token coordinates of the group: n = (t' Ht + h') Wt + w'
     const int wq = n0 % g.Wt, hq = (n0 / g.Wt) % g.Ht, tq = n0 / (g.Wt * g.Ht);
     const int segs = g.D / g.w;                                          // (c, t, h) combinations of a token
@@ -393,28 +505,49 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         const f32x4 e = *reinterpret_cast<const f32x4*>(ebuf + tok * LD + sg * g.w + wo);
         const int64_t lat = (int64_t)b * g.per + (((int64_t)cc * g.T + (tq * g.t + tt)) * g.H + (hq * g.h + hh)) * g.W + (wq + tok) * g.w + wo;
         const f32x4 x = *reinterpret_cast<const f32x4*>(z + lat);
-        f32x4 zn = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (SEEDED) {
-            const NoiseKey k(nk...);
-            zn = philox_normal4(k, (uint32_t)((lat - (int64_t)b * g.per) >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
-        } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
         f32x4 o;
+        if constexpr (DPM) {
+            const DpmState ds(nk...);
+            f32x4 hist = {0.f, 0.f, 0.f, 0.f}, x0;
+            if (d.c_1 != 0.f) hist = *reinterpret_cast<const f32x4*>(ds.x0_hist + lat);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = ddim_apply(c, x[k], e[k], zn[k]);
+            for (int k = 0; k < 4; ++k) {
+                x0[k] = ddim_x0(c, x[k], e[k]);
+                o[k] = dpm_apply(d, x[k], x0[k], hist[k]);
+            }
+            *reinterpret_cast<f32x4*>(ds.x0_hist + lat) = x0;
+        } else {
+            f32x4 zn = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (SEEDED) {
+                const NoiseKey k(nk...);
+                zn = philox_normal4(k, (uint32_t)((lat - (int64_t)b * g.per) >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
+            } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = ddim_apply(c, x[k], e[k], zn[k]);
+        }
         *reinterpret_cast<f32x4*>(z_out + lat) = o;
     }
 }
 
 // key != nullptr with eta > 0: the noise term is drawn from the seeded stream inside the kernel (`noise` is not read); eta == 0 ignores both
+// x0_hist != nullptr: the DPM-Solver++(2M) update (needs eta == 0 and t_last) instead of DDIM; x0_hist must not overlap z or z_out
 int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
-                         int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key) {
+                         int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key,
+                         const int64_t* t_last, float* x0_hist) {
     AVD_REQUIRE(eps2 && z && t_now && t_prev && abar && z_out, AVD_EINVAL, "cfg_unpatch_ddim: null pointer");
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "cfg_unpatch_ddim: bad dims");
     AVD_REQUIRE(eta >= 0.f && (eta == 0.f || noise || key), AVD_EINVAL, "cfg_unpatch_ddim: eta > 0 needs a noise tensor or a noise key");
     AVD_REQUIRE(z != z_out, AVD_EINVAL, "cfg_unpatch_ddim: z_out must not alias z");
     Tube g;
     if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
+    const bool dpm = x0_hist != nullptr;
+    if (dpm) {
+        AVD_REQUIRE(t_last && eta == 0.f, AVD_EINVAL, "cfg_unpatch_dpmpp_2m: needs t_last and eta == 0");
+        AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "cfg_unpatch_dpmpp_2m: x0_hist must be 16-byte aligned");
+        AVD_REQUIRE(!overlaps(x0_hist, z, (int64_t)B * g.per) && !overlaps(x0_hist, z_out, (int64_t)B * g.per), AVD_EINVAL,
+                    "cfg_unpatch_dpmpp_2m: x0_hist must not overlap z or z_out");
+    }
     const bool seeded = key && eta > 0.f;
     NoiseKey nk{0u, 0u, 0u};
     if (seeded) {
@@ -430,7 +563,11 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
         const int groups = (int)(g.per / g.D) / gt;
         const size_t lds = (size_t)gt * (g.D + 4) * 4;
         const dim3 grid((unsigned)(B * groups));
-        if (seeded)
+        if (dpm)
+            hipLaunchKernelGGL((gt == 8 ? cfg_unpatch_ddim_rows_kernel<8, false, DpmState> : cfg_unpatch_ddim_rows_kernel<4, false, DpmState>),
+                               grid, dim3(256), lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, groups,
+                               DpmState{t_last, x0_hist});
+        else if (seeded)
             hipLaunchKernelGGL((gt == 8 ? cfg_unpatch_ddim_rows_kernel<8, true, NoiseKey> : cfg_unpatch_ddim_rows_kernel<4, true, NoiseKey>), grid,
                                dim3(256), lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, groups, nk);
         else
@@ -440,7 +577,10 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
         return AVD_OK;
     }
     const dim3 grid((unsigned)((total4 + 255) / 256));
-    if (seeded)
+    if (dpm)
+        hipLaunchKernelGGL((cfg_unpatch_ddim_kernel<false, DpmState>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train,
+                           guidance, eta, noise, z_out, g, B, total4, DpmState{t_last, x0_hist});
+    else if (seeded)
         hipLaunchKernelGGL((cfg_unpatch_ddim_kernel<true, NoiseKey>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train, guidance,
                            eta, noise, z_out, g, B, total4, nk);
     else
@@ -457,7 +597,8 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
                                               const float* __restrict__ abar, int T_train, float guidance, float eta,
                                               const float* __restrict__ noise, float* __restrict__ z_out, int B, int Ca,
                                               int F, int len, int stride, int Na, Key... nk) {
-    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0), "the key is passed iff SEEDED");
+    constexpr bool DPM = IsDpm<Key...>::value;
+    static_assert(sizeof...(Key) == (SEEDED || DPM ? 1 : 0) && !(SEEDED && DPM), "one key (SEEDED) or one DpmState, or nothing");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)B * Ca * F) return;
     const int f = (int)(i % F);
@@ -484,7 +625,13 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
         e = acc / fmaxf(cnt, 1e-8f);
     }
     const Ddim cf = ddim_coef(t_now, t_prev, abar, T_train, eta, b);
-    if constexpr (SEEDED) {
+    if constexpr (DPM) {
+        const DpmState ds(nk...);
+        const Dpm d = dpm_coef(ds.t_last, t_now, t_prev, abar, T_train, b);
+        const float x = z[i], x0 = ddim_x0(cf, x, e);
+        z_out[i] = dpm_apply(d, x, x0, d.c_1 != 0.f ? ds.x0_hist[i] : 0.f);
+        ds.x0_hist[i] = x0;
+    } else if constexpr (SEEDED) {
         const NoiseKey k(nk...);
         const int64_t el = i - (int64_t)b * Ca * F;
         const f32x4 zn = philox_normal4(k, (uint32_t)(el >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
@@ -494,15 +641,22 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
     }
 }
 
-// key: as cfg_unpatch_ddim_f32
+// key, t_last, x0_hist: as cfg_unpatch_ddim_f32
 int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
-                               float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st, const avd_noise_key* key) {
+                               float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st, const avd_noise_key* key,
+                               const int64_t* t_last, float* x0_hist) {
     AVD_REQUIRE(eps2 && z && t_now && t_prev && abar && z_out, AVD_EINVAL, "cfg_untoken_ddim_audio: null pointer");
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "cfg_untoken_ddim_audio: bad chunking");
     AVD_REQUIRE(eta >= 0.f && (eta == 0.f || noise || key), AVD_EINVAL, "cfg_untoken_ddim_audio: eta > 0 needs noise or a noise key");
     AVD_REQUIRE(z != z_out, AVD_EINVAL, "cfg_untoken_ddim_audio: z_out must not alias z");
+    const bool dpm = x0_hist != nullptr;
+    if (dpm) {
+        AVD_REQUIRE(t_last && eta == 0.f, AVD_EINVAL, "cfg_untoken_dpmpp_2m_audio: needs t_last and eta == 0");
+        AVD_REQUIRE(!overlaps(x0_hist, z, (int64_t)B * Ca * F) && !overlaps(x0_hist, z_out, (int64_t)B * Ca * F), AVD_EINVAL,
+                    "cfg_untoken_dpmpp_2m_audio: x0_hist must not overlap z or z_out");
+    }
     const bool seeded = key && eta > 0.f;
     NoiseKey nk{0u, 0u, 0u};
     if (seeded)
@@ -510,7 +664,10 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
     const int Na = audio_na(F, len, stride);
     const int64_t n = (int64_t)B * Ca * F;
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (seeded)
+    if (dpm)
+        hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<false, DpmState>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train,
+                           guidance, eta, noise, z_out, B, Ca, F, len, stride, Na, DpmState{t_last, x0_hist});
+    else if (seeded)
         hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<true, NoiseKey>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train,
                            guidance, eta, noise, z_out, B, Ca, F, len, stride, Na, nk);
     else
@@ -642,6 +799,25 @@ __global__ void sched_advance_kernel(const int64_t* __restrict__ sched, int n_sc
     if (threadIdx.x == 0) *cursor = cur + 1;
 }
 
+// as sched_advance_kernel, and t_last[b] = the entry before t_now (-1 at the start of the schedule): the multistep solvers' history
+__global__ void sched_advance_ms_kernel(const int64_t* __restrict__ sched, int n_sched, int32_t* cursor, int64_t* __restrict__ t_last,
+                                        int64_t* __restrict__ t_now, int64_t* __restrict__ t_prev, int B) {
+    __shared__ int cur;
+    if (threadIdx.x == 0) cur = *cursor;
+    __syncthreads();
+    int i = cur;
+    if (i < 0) i = 0;
+    if (i > n_sched - 2) i = n_sched - 2;
+    const int64_t l = i > 0 ? sched[i - 1] : -1, a = sched[i], p = sched[i + 1];
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        t_last[b] = l;
+        t_now[b] = a;
+        t_prev[b] = p;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) *cursor = cur + 1;
+}
+
 }  // namespace avd
 
 using namespace avd;
@@ -681,14 +857,14 @@ extern "C" int avd_cfg_unpatch_ddim_f32(const float* eps2, const float* z, const
     AVD_REQUIRE(aligned16(eps2) && aligned16(z) && aligned16(z_out) && (!noise || aligned16(noise)), AVD_EUNSUPPORTED,
                 "cfg_unpatch_ddim: pointers must be 16-byte aligned");
     return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, C, T, H, W, t,
-                                h, w, static_cast<hipStream_t>(stream), nullptr);
+                                h, w, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr);
 }
 extern "C" int avd_cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now,
                                               const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance,
                                               float eta, const float* noise, float* z_out, int B, int Ca, int F, int len,
                                               int stride, avd_stream_t stream) {
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, Ca, F,
-                                      len, stride, static_cast<hipStream_t>(stream), nullptr);
+                                      len, stride, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr);
 }
 extern "C" int avd_gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int B, int64_t per_sample,
                                       avd_stream_t stream) {
@@ -701,4 +877,18 @@ extern "C" int avd_sched_advance(const int64_t* sched, int n_sched, int32_t* cur
                        cursor, t_now, t_prev, B);
     AVD_CHECK_LAUNCH("sched_advance");
     return AVD_OK;
+}
+extern "C" int avd_sched_advance_ms(const int64_t* sched, int n_sched, int32_t* cursor, int64_t* t_last, int64_t* t_now,
+                                    int64_t* t_prev, int B, avd_stream_t stream) {
+    AVD_REQUIRE(sched && cursor && t_last && t_now && t_prev && n_sched >= 2 && B > 0, AVD_EINVAL, "sched_advance_ms: bad arguments");
+    hipLaunchKernelGGL(sched_advance_ms_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), sched, n_sched,
+                       cursor, t_last, t_now, t_prev, B);
+    AVD_CHECK_LAUNCH("sched_advance_ms");
+    return AVD_OK;
+}
+extern "C" int avd_dpmpp_2m_step_f32(const float* x_t, const float* eps_hat, float* x0_hist, const int64_t* t_last,
+                                     const int64_t* t_now, const int64_t* t_prev, const float* alpha_bar, int T_train, float* x_out,
+                                     int B, int64_t per_sample, avd_stream_t stream) {
+    return dpmpp_2m_step_f32(x_t, eps_hat, x0_hist, t_last, t_now, t_prev, alpha_bar, T_train, x_out, B, per_sample,
+                             static_cast<hipStream_t>(stream));
 }

@@ -132,17 +132,29 @@ class DenoiseEngine:
     keyed by (noise_seed, sample_offset + b, t_now[b], element) — no noise buffer, and the graph replay of ``run`` applies as at
     eta == 0.  ``sample_offset`` is the global index of this batch's sample 0 (a batch that is one slice of a larger job draws the
     same noise as the whole job would).  Both are fixed at construction; a captured graph holds them by value.
+
+    ``solver`` (extension; default "ddim" = the reference's sampler): "dpmpp_2m" ends every step in the DPM-Solver++(2M) update
+    (include/avdiff_hip.h, avd_dpmpp_2m_step_f32) inside the same fused CFG kernel — second order, one model call per step, eta == 0
+    only.  The engine owns the solver's history ``x0_hist`` (the previous step's x0, allocated once: a captured graph keeps its
+    address); ``step(..., t_last=None)`` takes a first-order step, and ``run`` starts every trajectory first order.
     """
+
+    SOLVERS = ("ddim", "dpmpp_2m")
 
     def __init__(self, *, adapt_v: LinearAdapter, adapt_a: LinearAdapter, core: MMDiT, head: MultiModalNoiseHead,
                  tstep_dim: int, target: str, latent_shape: Tuple[int, ...], prompt_tokens: int, alpha_bar: torch.Tensor,
                  guidance: float, eta: float = 0.0, tube=(2, 4, 4), chunk=(4, 4), split_streams: Optional[bool] = None,
                  temb_mode: str = "concat", matmul: Optional[str] = None, attn: Optional[str] = None,
-                 noise_seed: Optional[int] = None, sample_offset: int = 0):
+                 noise_seed: Optional[int] = None, sample_offset: int = 0, solver: str = "ddim"):
         if target not in ("video", "audio"):
             raise ValueError("target must be 'video' or 'audio'")
         if eta < 0:
             raise ValueError("eta must be >= 0")
+        if solver not in self.SOLVERS:
+            raise ValueError(f"solver must be one of {self.SOLVERS}, got {solver!r}")
+        if solver == "dpmpp_2m" and eta > 0:
+            raise ValueError("solver 'dpmpp_2m' is the deterministic (ODE) solver: eta must be 0 (the SDE variant is not implemented)")
+        self.solver = solver
         if temb_mode not in ("concat", "add"):
             raise ValueError("temb_mode must be 'concat' (sampler, sample_clip.py:59-70) or 'add' (trainer, trainer.py:45-49)")
         self.temb_mode = temb_mode
@@ -210,6 +222,11 @@ class DenoiseEngine:
         self.workspace: Optional[torch.Tensor] = None
         self.Xp: Optional[torch.Tensor] = None
         self._prompt_latent: Optional[torch.Tensor] = None
+        # DPM-Solver++(2M) history: the previous step's x0, and the all -1 t_last of a first-order step (both at fixed addresses)
+        self.x0_hist: Optional[torch.Tensor] = None
+        if solver == "dpmpp_2m":
+            self.x0_hist = torch.zeros(self.latent_shape, device=self.device, dtype=torch.float32)
+            self._no_hist = torch.full((B,), -1, dtype=torch.long, device=self.device)
         self._bind_weights()
 
     # ---- pointer tables.  They hold derived copies (norm-folded / split3 weights), so they are re-derived whenever a
@@ -333,7 +350,10 @@ class DenoiseEngine:
         return Xp
 
     def step(self, z: torch.Tensor, t_now: torch.Tensor, t_prev: torch.Tensor,
-             noise: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+             noise: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+             t_last: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One step t_now -> t_prev.  ``t_last`` (solver "dpmpp_2m" only): the timesteps the previous step started from, whose x0
+        ``x0_hist`` holds; None (or entries < 0) takes a first-order step.  Either way x0_hist then holds this step's x0."""
         if self.Xp is None:
             raise RuntimeError("call set_prompt() first")
         z = L.dev_f32(z, "z")
@@ -343,6 +363,20 @@ class DenoiseEngine:
         if not torch.cuda.is_current_stream_capturing():
             self._sync_weights()
         out = torch.empty_like(z) if out is None else out
+        if self.solver == "dpmpp_2m":
+            if noise is not None:
+                raise ValueError("solver 'dpmpp_2m' is deterministic: it takes no noise")
+            h = self.x0_hist
+            for name, t in (("z", z), ("out", out)):
+                if t.untyped_storage().data_ptr() == h.untyped_storage().data_ptr():
+                    raise L.AvdError(f"{name} must not alias the engine's x0_hist (the solver history)")
+            tl = self._no_hist if t_last is None else L.dev_i64(t_last, self.device)
+            L.check(L.lib().avd_denoise_step_dpmpp_2m_f32(C.byref(self.desc), z.data_ptr(), self.Xp.data_ptr(), tl.data_ptr(),
+                                                          tn.data_ptr(), tp.data_ptr(), h.data_ptr(), out.data_ptr(),
+                                                          self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device)))
+            return out
+        if t_last is not None:
+            raise ValueError("t_last is the multistep solver's history: this engine runs solver 'ddim'")
         if self._key is not None:
             if noise is not None:
                 raise ValueError("this engine draws its noise from noise_seed: do not pass `noise` as well")
@@ -373,12 +407,20 @@ class DenoiseEngine:
         self._cursor = torch.zeros(1, dtype=torch.int32, device=dev)
         self._tn = torch.empty(B, dtype=torch.long, device=dev)
         self._tp = torch.empty(B, dtype=torch.long, device=dev)
+        self._tl = torch.empty(B, dtype=torch.long, device=dev)
 
     def rewind(self) -> None:
         self._cursor.zero_()
 
     def advance(self, src: torch.Tensor, dst: torch.Tensor) -> None:
-        """dst = one step from src at the cursor's (t_now, t_prev); the cursor moves on, all on the stream."""
+        """dst = one step from src at the cursor's (t_now, t_prev); the cursor moves on, all on the stream.  Solver "dpmpp_2m" also
+        reads t_last off the cursor (-1 at the start of the schedule: every trajectory begins first order)."""
+        if self.solver == "dpmpp_2m":
+            L.check(L.lib().avd_sched_advance_ms(self._sched.data_ptr(), self._sched.numel(), self._cursor.data_ptr(),
+                                                 self._tl.data_ptr(), self._tn.data_ptr(), self._tp.data_ptr(), self.embed.B,
+                                                 L.stream_ptr(self.device)))
+            self.step(src, self._tn, self._tp, out=dst, t_last=self._tl)
+            return
         L.check(L.lib().avd_sched_advance(self._sched.data_ptr(), self._sched.numel(), self._cursor.data_ptr(),
                                           self._tn.data_ptr(), self._tp.data_ptr(), self.embed.B,
                                           L.stream_ptr(self.device)))
@@ -403,6 +445,10 @@ class DenoiseEngine:
         bit-identical either way (tests: test_chained_sampler_golden, test_gpu_seeded_noise)."""
         if graph is None:
             graph = (self.eta == 0 or self._key is not None) and 2 * self.embed.B * self.N < self.GRAPH_BELOW_ROWS
+        if self.solver == "dpmpp_2m":
+            sc = torch.as_tensor(sched).reshape(-1).to("cpu", torch.long)
+            if sc.numel() >= 2 and not bool((sc[1:] < sc[:-1]).all()):
+                raise ValueError("solver 'dpmpp_2m' needs a strictly decreasing schedule (its history step must lie above t_now)")
         self.begin(sched)
         za = L.dev_f32(z, "z").clone()
         zb = torch.empty_like(za)
@@ -439,9 +485,12 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
     run can be repeated across devices — the reference's only RNG draw comes from the device generator.
     ``noise_seed`` (extension; default None = the reference's per-step ``randn_like``): with ``sampling.ddim_eta`` > 0 the per-step
     DDIM noise comes from the seeded stream (DenoiseEngine ``noise_seed``), so the whole trajectory repeats from (init_noise,
-    noise_seed)."""
+    noise_seed).
+    ``sampling.solver`` (extension; default "ddim"): "dpmpp_2m" samples with DPM-Solver++(2M) (DenoiseEngine ``solver``) over the
+    same ``sampler_steps`` schedule."""
     dcfg, scfg = cfg["diffusion"], cfg["sampling"]
     eta = float(scfg.get("ddim_eta", 0.0))
+    solver = str(scfg.get("solver", "ddim"))
     t_p, p = int(cfg["tokenizer"]["video"]["tube"]["t"]), int(cfg["tokenizer"]["video"]["tube"]["h"])
     l_chunk = int(cfg["tokenizer"]["audio"]["chunk"]["length"])
     s_chunk = int(cfg["tokenizer"]["audio"]["chunk"]["stride"])
@@ -483,7 +532,7 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
     abar, sched = table(target)
     eng = DenoiseEngine(adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, target=target,
                         latent_shape=tuple(z.shape), prompt_tokens=n_prompt, alpha_bar=abar, guidance=guide, eta=eta,
-                        tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed)
+                        tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed, solver=solver)
     eng.set_prompt(z_p.float())
     z = eng.run(z, sched)
     if target == "audio":

@@ -20,6 +20,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=32)
 ap.add_argument("--size", type=int, default=256)
 ap.add_argument("--sampler-steps", type=int, default=50)
+ap.add_argument("--solver", choices=("ddim", "dpmpp_2m"), default="ddim",
+                help="sampler of the end-to-end runs (DenoiseEngine solver=): DDIM or DPM-Solver++(2M)")
+ap.add_argument("--modes", default="f32,bf16x3,f16x2", help="comma-separated matrix-pipe modes of the end-to-end runs")
 ap.add_argument("--eta", type=float, default=None,
                 help="time only the sampler loop, both directions, at eta = 0 against eta = ETA (DDIM noise per step) instead of the "
                      "end-to-end runs; the variants run interleaved in one process")
@@ -77,10 +80,11 @@ if args.eta is not None:
                   f"{args.reps} rounds of {S} steps, {'graph' if graph else 'eager'})  {100 * (med / base - 1):+6.2f} % vs eta=0", flush=True)
     sys.exit(0)
 
-for mode in ("f32", "bf16x3", "f16x2"):
+MODES = args.modes.split(",")
+for mode in MODES:
     vae.matmul = mode
     eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=tdim, target="video", latent_shape=tuple(z0.shape),
-                          prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul=mode)
+                          prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul=mode, solver=args.solver)
     eng.set_prompt(za)
     z = eng.run(z0, sched[:3])                      # warm-up
     x = vae.decode(torch.randn_like(z))             # full-batch warm-up: the decoder's workspace (tens of GB) is allocated here
@@ -93,17 +97,18 @@ for mode in ("f32", "bf16x3", "f16x2"):
     x = vae.decode(torch.randn_like(z))
     torch.cuda.synchronize()
     t2 = time.perf_counter()
-    print(f"[{mode:6s}] B={B} {size}x{size}: sampler {S} steps {1e3 * (t1 - t0):7.1f} ms ({1e3 * (t1 - t0) / S:.2f} ms/step)  "
+    print(f"[{mode:6s}] {args.solver} B={B} {size}x{size}: sampler {S} steps {1e3 * (t1 - t0):7.1f} ms ({1e3 * (t1 - t0) / S:.2f} ms/step)  "
           f"VAE decode {1e3 * (t2 - t1):7.1f} ms ({1e3 * (t2 - t1) / B:.2f} ms/sample)  total {1e3 * (t2 - t0):7.1f} ms  "
           f"= {B / (t2 - t0):.1f} clips/s   out {tuple(x.shape)}", flush=True)
 
 # ---- video -> audio: encode the prompt clips, 50 steps on [B, 8, 150] with 384 prompt tokens, codec decode
 codec = A.AudioCodec.from_config({"sr": 16000, "latent": {"channels": 8}, "codec": {"hop_samples": 320}}).eval().to(dev)
 xv = (torch.rand(B, 3, 48, size, size, generator=torch.Generator().manual_seed(3)) * 2 - 1).to(dev)
-for mode in ("f32", "bf16x3", "f16x2"):
+for mode in MODES:
     vae.matmul = mode
     eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=tdim, target="audio", latent_shape=tuple(za.shape),
-                          prompt_tokens=(12 // 2) * (size // 8 // 4) ** 2, alpha_bar=abar, guidance=3.5, matmul=mode)      # tube patches 2 x 4 x 4
+                          prompt_tokens=(12 // 2) * (size // 8 // 4) ** 2, alpha_bar=abar, guidance=3.5, matmul=mode,
+                          solver=args.solver)      # tube patches 2 x 4 x 4
     zp = vae.encode(xv)                              # warm-up (workspace)
     eng.set_prompt(zp)
     eng.run(za, sched[:3])
@@ -121,6 +126,6 @@ for mode in ("f32", "bf16x3", "f16x2"):
         wav = codec.decode(torch.randn_like(z))
         torch.cuda.synchronize()
         t3 = time.perf_counter()
-    print(f"[{mode:6s}] V->A B={B} {size}x{size}: VAE encode {1e3 * (t1 - t0):7.1f} ms ({1e3 * (t1 - t0) / B:.2f} ms/sample)  sampler {S} steps "
+    print(f"[{mode:6s}] {args.solver} V->A B={B} {size}x{size}: VAE encode {1e3 * (t1 - t0):7.1f} ms ({1e3 * (t1 - t0) / B:.2f} ms/sample)  sampler {S} steps "
           f"{1e3 * (t2 - t1):7.1f} ms ({1e3 * (t2 - t1) / S:.2f} ms/step)  codec decode {1e3 * (t3 - t2):6.1f} ms  total {1e3 * (t3 - t0):7.1f} ms  "
           f"= {B / (t3 - t0):.1f} clips/s", flush=True)
