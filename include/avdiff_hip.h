@@ -189,6 +189,31 @@ typedef struct {
 int avd_gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int B, int64_t per_sample,
                            avd_stream_t stream);
 
+/* ---- latent guide: inpainting / outpainting and SDEdit over a known clean latent (a public contract).
+ * Per sample b of a call, with x_k = known[b] and m = the mask, both in the latent's natural layout ([C,T,H,W] video, [Ca,F] audio,
+ * row-major; element e as in avd_noise_key), and a(tau) = alpha_bar[clamp(tau, 0, T_train-1)] for tau >= 0, 1 for tau < 0:
+ *   1. known-noise stream n_k(s, e): the avd_noise_key construction (key.seed) with counter (e >> 2, (uint32) s, 0, 0x4B4E5731)
+ *      and s = key.sample_offset + b.  The counter holds no timestep: each element keeps one normal for the whole trajectory, so
+ *      the known region follows one deterministic forward path.  The last word tags this use of the generator (DDIM's is 0x44444D31);
+ *   2. q(tau) = A x_k + S n_k with A = sqrt(a), S = sqrt(max(1 - a, 0)), in fp32 in that order without contraction;
+ *      q = x_k exactly (no arithmetic) when a == 1.0f, which includes tau < 0;
+ *   3. blend(m, q, z) = z where m == 0, q where m == 1 (both selects), else (1 - m) z + m q in fp32, in that order, without
+ *      contraction: an all-zero mask is bit-identical to no guide, an all-one mask bit-identical to q;
+ *   4. the guided step = the step (DDIM at eta = 0, seeded DDIM at eta > 0 or DPM-Solver++(2M)) producing z_out, then
+ *      z_out <- blend(m, q(t_prev[b]), z_out) in the same kernel.  DPM's x0_hist still receives the model's x0_s, not a blended
+ *      value.  The final step (t_prev = -1) returns x_k bit for bit wherever m == 1. */
+typedef struct {
+    const float* known;          /* fp32 [B, per_sample], 16-byte aligned */
+    const float* mask;           /* fp32, values in [0,1]: [per_sample] (mask_batch_stride 0) or [B, per_sample] (mask_batch_stride
+                                    per_sample), 16-byte aligned; NULL = 1 everywhere */
+    int64_t mask_batch_stride;   /* 0 or per_sample */
+    avd_noise_key key;           /* seed / sample_offset of the known-noise stream */
+} avd_latent_guide;
+/* out[b] = blend(mask, q(tau[b]), z[b]); z == NULL reads as "mask is 1 everywhere" (pure forward noising: out = q).  out may be z;
+ * known / mask must not overlap out.  tau: int64 [B]; z, out: fp32 [B, per_sample]. */
+int avd_latent_guide_f32(const avd_latent_guide* g, const int64_t* tau, const float* alpha_bar, int T_train,
+                         const float* z, float* out, int B, int64_t per_sample, avd_stream_t stream);
+
 /* ---- a8 fused: CFG combine + tube un-patch + DDIM — avdiff/models/infer/sample_clip.py:381-389.
  * eps2: [2B,Nv,C*t*h*w] (cond batch then null batch); eps = null + g*(cond-null); un-patched on the fly.
  * z, z_out: [B,C,T,H,W]. */
@@ -428,6 +453,14 @@ int avd_denoise_step_seeded_f32(const avd_step_desc* s, const avd_noise_key* key
 int avd_denoise_step_dpmpp_2m_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_last,
                                   const int64_t* t_now, const int64_t* t_prev, float* x0_hist, float* z_out,
                                   void* workspace, int64_t workspace_bytes, avd_stream_t stream);
+/* The whole CFG step ending in the guided update (avd_latent_guide): z_out = blend(mask, q(t_prev), step(z)).  key != NULL with
+ * s->eta > 0: seeded DDIM noise (as avd_denoise_step_seeded_f32); eta > 0 without a key is refused.  t_last and x0_hist both
+ * non-NULL: the DPM-Solver++(2M) update (eta == 0, as avd_denoise_step_dpmpp_2m_f32).  known / mask must not overlap z_out or
+ * x0_hist.  Graph-capturable: the guide's buffers are read at their addresses at every launch. */
+int avd_denoise_step_guided_f32(const avd_step_desc* s, const avd_latent_guide* g, const avd_noise_key* key,
+                                const int64_t* t_last, float* x0_hist, const float* z, const float* Xp,
+                                const int64_t* t_now, const int64_t* t_prev, float* z_out,
+                                void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 
 /* ---- a9 / next-1: VideoVAE.decode — avdiff/models/encoders/vae_video3d.py:195-214 (decode), :79-84
  * (_conv_block_3d: Conv3d 3x3x3 pad 1 -> GELU(erf) -> GroupNorm(min(8,C), eps 1e-5, affine)), :108-119.

@@ -68,6 +68,11 @@ class NoiseKey(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("sample_offset", C.c_int64)]
 
 
+class LatentGuide(C.Structure):
+    """avd_latent_guide: a known clean latent, its mask and the key of its known-noise stream (contract in include/avdiff_hip.h)."""
+    _fields_ = [("known", C.c_void_p), ("mask", C.c_void_p), ("mask_batch_stride", C.c_int64), ("key", NoiseKey)]
+
+
 class VaeDecodeDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("Cv", C.c_int), ("Tp", C.c_int), ("Hp", C.c_int), ("Wp", C.c_int),
                 ("T", C.c_int), ("H", C.c_int), ("W", C.c_int),
@@ -131,6 +136,9 @@ SIGNATURES = {
     "avd_sched_advance_ms": (_I, [_P, _I, _P, _P, _P, _P, _I, _P]),
     "avd_dpmpp_2m_step_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _L, _P]),
     "avd_denoise_step_dpmpp_2m_f32": (_I, [C.POINTER(StepDesc), _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "avd_latent_guide_f32": (_I, [C.POINTER(LatentGuide), _P, _P, _I, _P, _P, _I, _L, _P]),
+    "avd_denoise_step_guided_f32": (_I, [C.POINTER(StepDesc), C.POINTER(LatentGuide), C.POINTER(NoiseKey), _P, _P, _P, _P, _P, _P, _P,
+                                         _P, _L, _P]),
     "avd_split3_bytes": (_L, [_L, _I]),
     "avd_split3_f32": (_I, [_P, _P, _L, _I, _P]),
     "avd_rmsnorm_split3_f32": (_I, [_P, _P, _P, _L, _I, _F, _P]),

@@ -11,6 +11,7 @@
 #include "avd_common.h"
 
 #include <stdlib.h>
+#include <type_traits>
 
 namespace avd {
 
@@ -282,8 +283,12 @@ struct DpmState {
     const int64_t* t_last;   // int64 [B]
     float* x0_hist;          // [B, per] in the latent's natural layout: read (second-order steps), then overwritten with x0_s
 };
-template <class... X> struct IsDpm { static constexpr bool value = false; };
-template <> struct IsDpm<DpmState> { static constexpr bool value = true; };
+// the trailing pack holds at most one solver state (NoiseKey or DpmState), then optionally a GuideState (the latent guide below)
+template <class T, class... X> struct PackHas { static constexpr bool value = (std::is_same<T, X>::value || ...); };
+template <class T, class A, class... R> __device__ __forceinline__ T pack_get(const A& a, const R&... r) {
+    if constexpr (std::is_same<T, A>::value) return a;
+    else return pack_get<T>(r...);
+}
 
 // ------------------------------------------------------------------ seeded normal stream (DDIM eta > 0)
 // The public contract is written out in include/avdiff_hip.h (avd_noise_key).  Element e of sample s at timestep t:
@@ -296,9 +301,10 @@ struct NoiseKey {
     uint32_t s0;       // global index of sample 0 of the launch
 };
 
-__device__ __forceinline__ f32x4 philox_normal4(const NoiseKey& nk, uint32_t e4, uint32_t s, uint32_t t) {
+// tag: the counter's domain word (0x44444D31 the DDIM noise, GUIDE_TAG the latent guide's known-region noise)
+__device__ __forceinline__ f32x4 philox_normal4(const NoiseKey& nk, uint32_t e4, uint32_t s, uint32_t t, uint32_t tag = 0x44444D31u) {
 #pragma clang fp contract(off)
-    uint32_t c0 = e4, c1 = s, c2 = t, c3 = 0x44444D31u, k0 = nk.k0, k1 = nk.k1;
+    uint32_t c0 = e4, c1 = s, c2 = t, c3 = tag, k0 = nk.k0, k1 = nk.k1;
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
@@ -411,6 +417,121 @@ int dpmpp_2m_step_f32(const float* x_t, const float* eps, float* x0_hist, const 
     return AVD_OK;
 }
 
+// ------------------------------------------------------------------ latent guide (inpainting / SDEdit)
+// The contract is written out in include/avdiff_hip.h (avd_latent_guide).  Per sample b and element e of the latent's natural layout:
+//   q(tau) = A x_k + S n_k  (A = sqrt(a(tau)), S = sqrt(max(1 - a, 0)); q = x_k when a == 1),  n_k = philox_normal4 at counter
+//   (e >> 2, s, 0, GUIDE_TAG): one fixed normal per element for the whole trajectory;
+//   blend(m, q, z) = z (m == 0), q (m == 1), (1 - m) z + m q otherwise.
+// guide_q / guide_blend are the only places these are written: the elementwise kernel and the three fused CFG kernels call them,
+// without contraction, so every form agrees bit for bit (the lesson of ddim_apply above).
+constexpr uint32_t GUIDE_TAG = 0x4B4E5731u;     // "KNW1"
+
+struct GuideState {
+    const float* known;     // [B, per]
+    const float* mask;      // [per] (mask_bstride 0) or [B, per]; nullptr = 1 everywhere
+    int64_t mask_bstride;
+    NoiseKey nk;            // the known-noise stream's seed and sample offset
+};
+
+struct GuideCoef {
+    float A, S;
+    bool one;               // a == 1.0f: q = x_k, no arithmetic (and no generator call)
+};
+
+__device__ __forceinline__ GuideCoef guide_coef(const float* abar, int T_train, long long tau) {
+    const float a = dpm_abar(abar, T_train, tau);
+    return GuideCoef{sqrtf(a), sqrtf(fmaxf(1.0f - a, 0.f)), a == 1.0f};
+}
+__device__ __forceinline__ float guide_q(const GuideCoef& g, float xk, float n) {
+#pragma clang fp contract(off)
+    return g.one ? xk : g.A * xk + g.S * n;
+}
+__device__ __forceinline__ float guide_blend(float m, float q, float z) {
+#pragma clang fp contract(off)
+    return m == 0.f ? z : (m == 1.f ? q : (1.0f - m) * z + m * q);
+}
+// the four consecutive elements el .. el + 3 (el % 4 == 0) of sample b at lat = b * per + el: known / mask read as f32x4
+__device__ __forceinline__ f32x4 guide_apply4(const GuideState& gs, const GuideCoef& gc, int b, int64_t lat, int64_t el, f32x4 z) {
+    const f32x4 m = gs.mask ? *reinterpret_cast<const f32x4*>(gs.mask + b * gs.mask_bstride + el) : f32x4{1.f, 1.f, 1.f, 1.f};
+    const f32x4 xk = *reinterpret_cast<const f32x4*>(gs.known + lat);
+    f32x4 n = {0.f, 0.f, 0.f, 0.f};
+    if (!gc.one) n = philox_normal4(gs.nk, (uint32_t)(el >> 2), gs.nk.s0 + (uint32_t)b, 0u, GUIDE_TAG);
+    f32x4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = guide_blend(m[k], guide_q(gc, xk[k], n[k]), z[k]);
+    return o;
+}
+// one element el of sample b at i = b * per + el
+__device__ __forceinline__ float guide_apply1(const GuideState& gs, const GuideCoef& gc, int b, int64_t i, int64_t el, float z) {
+    const float m = gs.mask ? gs.mask[b * gs.mask_bstride + el] : 1.f;
+    float n = 0.f;
+    if (!gc.one) n = philox_normal4(gs.nk, (uint32_t)(el >> 2), gs.nk.s0 + (uint32_t)b, 0u, GUIDE_TAG)[(int)(el & 3)];
+    return guide_blend(m, guide_q(gc, gs.known[i], n), z);
+}
+
+// the checks every guided entry makes before any HIP call; out and x0_hist (either may be nullptr) must not overlap known / mask
+int check_latent_guide(const avd_latent_guide* g, int B, int64_t per, const float* out, const float* x0_hist) {
+    AVD_REQUIRE(g, AVD_EINVAL, "latent_guide: null guide");
+    AVD_REQUIRE(g->known, AVD_EINVAL, "latent_guide: null known latent");
+    AVD_REQUIRE(B > 0 && per > 0 && per < ((int64_t)1 << 34), AVD_EINVAL, "latent_guide: bad dims (B %d, per_sample %lld)", B,
+                (long long)per);
+    AVD_REQUIRE(g->mask_batch_stride == 0 || g->mask_batch_stride == per, AVD_EINVAL,
+                "latent_guide: mask_batch_stride %lld must be 0 or per_sample %lld", (long long)g->mask_batch_stride, (long long)per);
+    AVD_REQUIRE(g->key.sample_offset >= 0 && g->key.sample_offset + (int64_t)B <= ((int64_t)1 << 32), AVD_EINVAL,
+                "latent_guide: key sample_offset %lld + B %d must lie in [0, 2^32]", (long long)g->key.sample_offset, B);
+    AVD_REQUIRE(aligned16(g->known) && (!g->mask || aligned16(g->mask)), AVD_EUNSUPPORTED,
+                "latent_guide: known and mask must be 16-byte aligned");
+    const int64_t n = (int64_t)B * per, nm = g->mask_batch_stride ? n : per;
+    for (const float* p : {out, x0_hist}) {
+        if (!p) continue;
+        AVD_REQUIRE(!overlaps(p, g->known, n) && !(g->mask && (p < g->mask + nm && g->mask < p + n)), AVD_EINVAL,
+                    "latent_guide: known / mask must not overlap z_out or x0_hist");
+    }
+    return AVD_OK;
+}
+
+static int make_guide(const avd_latent_guide* g, int B, int64_t per, const float* out, const float* x0_hist, GuideState& gs) {
+    if (int rc = check_latent_guide(g, B, per, out, x0_hist)) return rc;
+    NoiseKey nk;
+    if (int rc = make_noise_key(&g->key, B, nk)) return rc;
+    gs = GuideState{g->known, g->mask, g->mask_batch_stride, nk};
+    return AVD_OK;
+}
+
+__global__ __launch_bounds__(256) void latent_guide_kernel(GuideState gs, const int64_t* __restrict__ tau, const float* __restrict__ abar,
+                                                           int T_train, const float* z, float* out, int64_t per, int64_t per4,
+                                                           int64_t total4) {      // z may be out (in place)
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total4) return;
+    const int b = (int)(i / per4);
+    const int64_t q4 = i % per4;
+    const GuideCoef gc = guide_coef(abar, T_train, tau[b]);
+    f32x4 n = {0.f, 0.f, 0.f, 0.f};
+    if (!gc.one) n = philox_normal4(gs.nk, (uint32_t)q4, gs.nk.s0 + (uint32_t)b, 0u, GUIDE_TAG);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t el = q4 * 4 + k;
+        if (el >= per) break;
+        const int64_t j = (int64_t)b * per + el;
+        const float q = guide_q(gc, gs.known[j], n[k]);
+        out[j] = z ? guide_blend(gs.mask ? gs.mask[b * gs.mask_bstride + el] : 1.f, q, z[j]) : q;
+    }
+}
+
+int latent_guide_f32(const avd_latent_guide* g, const int64_t* tau, const float* abar, int T_train, const float* z, float* out, int B,
+                     int64_t per, hipStream_t st) {
+    GuideState gs;
+    if (int rc = make_guide(g, B, per, out, nullptr, gs)) return rc;
+    AVD_REQUIRE(tau && abar && out && T_train > 0, AVD_EINVAL, "latent_guide: null pointer or bad T_train");
+    const int64_t per4 = (per + 3) >> 2, total4 = (int64_t)B * per4;
+    AVD_REQUIRE((total4 + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "latent_guide: %lld values is too many for one launch",
+                (long long)B * per);
+    hipLaunchKernelGGL(latent_guide_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, gs, tau, abar, T_train, z, out,
+                       per, per4, total4);
+    AVD_CHECK_LAUNCH("latent_guide");
+    return AVD_OK;
+}
+
 // ------------------------------------------------------------------ fused CFG + unpatch + DDIM (video target)
 int g_cfg_rows = getenv("AVD_CFG_ROWS") ? atoi(getenv("AVD_CFG_ROWS")) : 1;      // avd_tune_set "cfg_rows": 0 = the 16-bytes-per-lane gather form
 // SEEDED: zn comes from the seeded normal stream (philox_normal4: one call is exactly this lane's float4) instead of `noise`.  The key
@@ -422,8 +543,9 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const float* __restrict__ eps2, const float* __restrict__ z, const int64_t* __restrict__ t_now,
     const int64_t* __restrict__ t_prev, const float* __restrict__ abar, int T_train, float guidance, float eta,
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int64_t total4, Key... nk) {
-    constexpr bool DPM = IsDpm<Key...>::value;
-    static_assert(sizeof...(Key) == (SEEDED || DPM ? 1 : 0) && !(SEEDED && DPM), "one key (SEEDED) or one DpmState, or nothing");
+    constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
+    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) && !(SEEDED && DPM),
+                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState");
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total4) return;
     const int64_t per4 = g.per >> 2;
@@ -436,13 +558,15 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const f32x4 x = *reinterpret_cast<const f32x4*>(z + lat);
     f32x4 zn = {0.f, 0.f, 0.f, 0.f};
     if constexpr (SEEDED) {
-        const NoiseKey k(nk...);
+        NoiseKey k;      // a one-item pack is copied as before the guide existed: through pack_get its argument loads reorder
+        if constexpr (GUIDED) k = pack_get<NoiseKey>(nk...);
+        else k = NoiseKey(nk...);
         zn = philox_normal4(k, (uint32_t)e4, k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
     } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
     const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, eta, b);
     f32x4 o;
     if constexpr (DPM) {
-        const DpmState ds(nk...);
+        const DpmState ds = pack_get<DpmState>(nk...);
         const Dpm d = dpm_coef(ds.t_last, t_now, t_prev, abar, T_train, b);
         f32x4 hist = {0.f, 0.f, 0.f, 0.f}, x0;
         if (d.c_1 != 0.f) hist = *reinterpret_cast<const f32x4*>(ds.x0_hist + lat);
@@ -459,6 +583,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
             o[k] = ddim_apply(c, x[k], e, zn[k]);
         }
     }
+    if constexpr (GUIDED) o = guide_apply4(pack_get<GuideState>(nk...), guide_coef(abar, T_train, t_prev[b]), b, lat, e4 * 4, o);
     *reinterpret_cast<f32x4*>(z_out + lat) = o;
 }
 
@@ -473,8 +598,9 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     const float* __restrict__ eps2, const float* __restrict__ z, const int64_t* __restrict__ t_now,
     const int64_t* __restrict__ t_prev, const float* __restrict__ abar, int T_train, float guidance, float eta,
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int groups_per_sample, Key... nk) {
-    constexpr bool DPM = IsDpm<Key...>::value;
-    static_assert(sizeof...(Key) == (SEEDED || DPM ? 1 : 0) && !(SEEDED && DPM), "one key (SEEDED) or one DpmState, or nothing");
+    constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
+    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) && !(SEEDED && DPM),
+                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState");
     extern __shared__ __attribute__((aligned(16))) float ebuf[];       // [GT][D + 4]: the pad keeps the transposed 16-byte reads off one bank group
     const int LD = g.D + 4;
     const int b = blockIdx.x / groups_per_sample, grp = blockIdx.x % groups_per_sample;
@@ -493,7 +619,9 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     __syncthreads();
     const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, eta, b);
     [[maybe_unused]] Dpm d{0.f, 0.f, 0.f};
-    if constexpr (DPM) d = dpm_coef(DpmState(nk...).t_last, t_now, t_prev, abar, T_train, b);
+    if constexpr (DPM) d = dpm_coef(pack_get<DpmState>(nk...).t_last, t_now, t_prev, abar, T_train, b);
+    [[maybe_unused]] GuideCoef gc{0.f, 0.f, false};
+    if constexpr (GUIDED) gc = guide_coef(abar, T_train, t_prev[b]);
     // token coordinates of the group: n = (t' Ht + h') Wt + w'
     const int wq = n0 % g.Wt, hq = (n0 / g.Wt) % g.Ht, tq = n0 / (g.Wt * g.Ht);
     const int segs = g.D / g.w;                                          // (c, t, h) combinations of a token
@@ -507,7 +635,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         const f32x4 x = *reinterpret_cast<const f32x4*>(z + lat);
         f32x4 o;
         if constexpr (DPM) {
-            const DpmState ds(nk...);
+            const DpmState ds = pack_get<DpmState>(nk...);
             f32x4 hist = {0.f, 0.f, 0.f, 0.f}, x0;
             if (d.c_1 != 0.f) hist = *reinterpret_cast<const f32x4*>(ds.x0_hist + lat);
 #pragma unroll
@@ -519,22 +647,41 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         } else {
             f32x4 zn = {0.f, 0.f, 0.f, 0.f};
             if constexpr (SEEDED) {
-                const NoiseKey k(nk...);
+                NoiseKey k;      // as in cfg_unpatch_ddim_kernel
+                if constexpr (GUIDED) k = pack_get<NoiseKey>(nk...);
+                else k = NoiseKey(nk...);
                 zn = philox_normal4(k, (uint32_t)((lat - (int64_t)b * g.per) >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
             } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
 #pragma unroll
             for (int k = 0; k < 4; ++k) o[k] = ddim_apply(c, x[k], e[k], zn[k]);
         }
+        if constexpr (GUIDED) o = guide_apply4(pack_get<GuideState>(nk...), gc, b, lat, lat - (int64_t)b * g.per, o);
         *reinterpret_cast<f32x4*>(z_out + lat) = o;
     }
 }
 
+// The guided launches: the solver's state S (nothing, NoiseKey or DpmState) followed by the guide, as the kernels' trailing pack.
+template <class... S>
+static void launch_unpatch_guided(int rows_gt, int groups, dim3 grid, size_t lds, hipStream_t st, const float* eps2, const float* z,
+                                  const int64_t* t_now, const int64_t* t_prev, const float* abar, int T_train, float guidance, float eta,
+                                  const float* noise, float* z_out, const Tube& g, int B, int64_t total4, const GuideState& gs, S... s) {
+    constexpr bool SEEDED = PackHas<NoiseKey, S...>::value;
+    if (rows_gt)
+        hipLaunchKernelGGL((rows_gt == 8 ? cfg_unpatch_ddim_rows_kernel<8, SEEDED, S..., GuideState>
+                                         : cfg_unpatch_ddim_rows_kernel<4, SEEDED, S..., GuideState>),
+                           grid, dim3(256), lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, groups, s..., gs);
+    else
+        hipLaunchKernelGGL((cfg_unpatch_ddim_kernel<SEEDED, S..., GuideState>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train,
+                           guidance, eta, noise, z_out, g, B, total4, s..., gs);
+}
+
 // key != nullptr with eta > 0: the noise term is drawn from the seeded stream inside the kernel (`noise` is not read); eta == 0 ignores both
 // x0_hist != nullptr: the DPM-Solver++(2M) update (needs eta == 0 and t_last) instead of DDIM; x0_hist must not overlap z or z_out
+// guide != nullptr: the latent guide's blend ends the update (after either solver), right before z_out is stored
 int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key,
-                         const int64_t* t_last, float* x0_hist) {
+                         const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide) {
     AVD_REQUIRE(eps2 && z && t_now && t_prev && abar && z_out, AVD_EINVAL, "cfg_unpatch_ddim: null pointer");
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "cfg_unpatch_ddim: bad dims");
     AVD_REQUIRE(eta >= 0.f && (eta == 0.f || noise || key), AVD_EINVAL, "cfg_unpatch_ddim: eta > 0 needs a noise tensor or a noise key");
@@ -554,12 +701,35 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
         if (int rc = make_noise_key(key, B, nk)) return rc;
         AVD_REQUIRE(g.per < ((int64_t)1 << 34), AVD_EINVAL, "cfg_unpatch_ddim: a seeded sample must hold < 2^34 values");
     }
+    GuideState gs{};
+    if (guide) {
+        AVD_REQUIRE(eta == 0.f || seeded, AVD_EINVAL, "cfg_unpatch_ddim: a guided step with eta > 0 needs a noise key");
+        if (int rc = make_guide(guide, B, g.per, z_out, x0_hist, gs)) return rc;
+    }
     const int64_t total4 = (int64_t)B * (g.per >> 2);
     static const int tag = prof_tag_id("cfg_unpatch_ddim_kernel");
     ProfScope prof(tag, 16.0 * (double)B * g.per, st);
     // whole-line form: groups of tokens along w' that make up 128 bytes (or the whole row when W is shorter) of latent per (c, t, h)
     const int gt = (g.W < 32 ? g.W : 32) / g.w;
-    if (g_cfg_rows && (gt == 8 || gt == 4) && g.Wt % gt == 0 && g.D % 4 == 0 && (int64_t)gt * (g.D + 4) * 4 <= 64 * 1024) {
+    const bool rows = g_cfg_rows && (gt == 8 || gt == 4) && g.Wt % gt == 0 && g.D % 4 == 0 && (int64_t)gt * (g.D + 4) * 4 <= 64 * 1024;
+    if (guide) {
+        const int groups = rows ? (int)(g.per / g.D) / gt : 0;
+        const size_t lds = rows ? (size_t)gt * (g.D + 4) * 4 : 0;
+        const dim3 grid(rows ? (unsigned)(B * groups) : (unsigned)((total4 + 255) / 256));
+        const int rgt = rows ? gt : 0;
+        if (dpm)
+            launch_unpatch_guided(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
+                                  gs, DpmState{t_last, x0_hist});
+        else if (seeded)
+            launch_unpatch_guided(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
+                                  gs, nk);
+        else
+            launch_unpatch_guided(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
+                                  gs);
+        AVD_CHECK_LAUNCH("cfg_unpatch_ddim (guided)");
+        return AVD_OK;
+    }
+    if (rows) {
         const int groups = (int)(g.per / g.D) / gt;
         const size_t lds = (size_t)gt * (g.D + 4) * 4;
         const dim3 grid((unsigned)(B * groups));
@@ -597,8 +767,9 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
                                               const float* __restrict__ abar, int T_train, float guidance, float eta,
                                               const float* __restrict__ noise, float* __restrict__ z_out, int B, int Ca,
                                               int F, int len, int stride, int Na, Key... nk) {
-    constexpr bool DPM = IsDpm<Key...>::value;
-    static_assert(sizeof...(Key) == (SEEDED || DPM ? 1 : 0) && !(SEEDED && DPM), "one key (SEEDED) or one DpmState, or nothing");
+    constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
+    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) && !(SEEDED && DPM),
+                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)B * Ca * F) return;
     const int f = (int)(i % F);
@@ -625,27 +796,36 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
         e = acc / fmaxf(cnt, 1e-8f);
     }
     const Ddim cf = ddim_coef(t_now, t_prev, abar, T_train, eta, b);
+    // the guide's epilogue on the value about to be stored (the identity for the unguided instantiations)
+    auto fin = [&](float v) {
+        if constexpr (GUIDED)
+            return guide_apply1(pack_get<GuideState>(nk...), guide_coef(abar, T_train, t_prev[b]), b, i, i - (int64_t)b * Ca * F, v);
+        else
+            return v;
+    };
     if constexpr (DPM) {
-        const DpmState ds(nk...);
+        const DpmState ds = pack_get<DpmState>(nk...);
         const Dpm d = dpm_coef(ds.t_last, t_now, t_prev, abar, T_train, b);
         const float x = z[i], x0 = ddim_x0(cf, x, e);
-        z_out[i] = dpm_apply(d, x, x0, d.c_1 != 0.f ? ds.x0_hist[i] : 0.f);
+        z_out[i] = fin(dpm_apply(d, x, x0, d.c_1 != 0.f ? ds.x0_hist[i] : 0.f));
         ds.x0_hist[i] = x0;
     } else if constexpr (SEEDED) {
-        const NoiseKey k(nk...);
+        NoiseKey k;      // as in cfg_unpatch_ddim_kernel
+        if constexpr (GUIDED) k = pack_get<NoiseKey>(nk...);
+        else k = NoiseKey(nk...);
         const int64_t el = i - (int64_t)b * Ca * F;
         const f32x4 zn = philox_normal4(k, (uint32_t)(el >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
-        z_out[i] = ddim_apply(cf, z[i], e, zn[(int)(el & 3)]);
+        z_out[i] = fin(ddim_apply(cf, z[i], e, zn[(int)(el & 3)]));
     } else {
-        z_out[i] = ddim_apply(cf, z[i], e, eta > 0.f ? noise[i] : 0.f);
+        z_out[i] = fin(ddim_apply(cf, z[i], e, eta > 0.f ? noise[i] : 0.f));
     }
 }
 
-// key, t_last, x0_hist: as cfg_unpatch_ddim_f32
+// key, t_last, x0_hist, guide: as cfg_unpatch_ddim_f32
 int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st, const avd_noise_key* key,
-                               const int64_t* t_last, float* x0_hist) {
+                               const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide) {
     AVD_REQUIRE(eps2 && z && t_now && t_prev && abar && z_out, AVD_EINVAL, "cfg_untoken_ddim_audio: null pointer");
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "cfg_untoken_ddim_audio: bad chunking");
@@ -664,6 +844,22 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
     const int Na = audio_na(F, len, stride);
     const int64_t n = (int64_t)B * Ca * F;
     const dim3 grid((unsigned)((n + 255) / 256));
+    if (guide) {
+        AVD_REQUIRE(eta == 0.f || seeded, AVD_EINVAL, "cfg_untoken_ddim_audio: a guided step with eta > 0 needs a noise key");
+        GuideState gs;
+        if (int rc = make_guide(guide, B, (int64_t)Ca * F, z_out, x0_hist, gs)) return rc;
+        if (dpm)
+            hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<false, DpmState, GuideState>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev,
+                               abar, T_train, guidance, eta, noise, z_out, B, Ca, F, len, stride, Na, DpmState{t_last, x0_hist}, gs);
+        else if (seeded)
+            hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<true, NoiseKey, GuideState>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev,
+                               abar, T_train, guidance, eta, noise, z_out, B, Ca, F, len, stride, Na, nk, gs);
+        else
+            hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<false, GuideState>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar,
+                               T_train, guidance, eta, noise, z_out, B, Ca, F, len, stride, Na, gs);
+        AVD_CHECK_LAUNCH("cfg_untoken_ddim_audio (guided)");
+        return AVD_OK;
+    }
     if (dpm)
         hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<false, DpmState>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train,
                            guidance, eta, noise, z_out, B, Ca, F, len, stride, Na, DpmState{t_last, x0_hist});
@@ -857,14 +1053,14 @@ extern "C" int avd_cfg_unpatch_ddim_f32(const float* eps2, const float* z, const
     AVD_REQUIRE(aligned16(eps2) && aligned16(z) && aligned16(z_out) && (!noise || aligned16(noise)), AVD_EUNSUPPORTED,
                 "cfg_unpatch_ddim: pointers must be 16-byte aligned");
     return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, C, T, H, W, t,
-                                h, w, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr);
+                                h, w, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr);
 }
 extern "C" int avd_cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now,
                                               const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance,
                                               float eta, const float* noise, float* z_out, int B, int Ca, int F, int len,
                                               int stride, avd_stream_t stream) {
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, Ca, F,
-                                      len, stride, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr);
+                                      len, stride, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr);
 }
 extern "C" int avd_gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int B, int64_t per_sample,
                                       avd_stream_t stream) {
@@ -891,4 +1087,8 @@ extern "C" int avd_dpmpp_2m_step_f32(const float* x_t, const float* eps_hat, flo
                                      int B, int64_t per_sample, avd_stream_t stream) {
     return dpmpp_2m_step_f32(x_t, eps_hat, x0_hist, t_last, t_now, t_prev, alpha_bar, T_train, x_out, B, per_sample,
                              static_cast<hipStream_t>(stream));
+}
+extern "C" int avd_latent_guide_f32(const avd_latent_guide* g, const int64_t* tau, const float* alpha_bar, int T_train, const float* z,
+                                    float* out, int B, int64_t per_sample, avd_stream_t stream) {
+    return latent_guide_f32(g, tau, alpha_bar, T_train, z, out, B, per_sample, static_cast<hipStream_t>(stream));
 }

@@ -231,6 +231,51 @@ def noise_key(seed: int, sample_offset: int = 0) -> "L.NoiseKey":
     return L.NoiseKey(seed, sample_offset)
 
 
+def latent_guide_desc(known: Tensor, mask: Optional[Tensor], seed: int, sample_offset: int = 0) -> "L.LatentGuide":
+    """avd_latent_guide over ``known`` (contiguous float32 [B, ...] on the device) and ``mask`` (None = 1 everywhere; contiguous
+    float32 of known.shape[1:] (shared by the batch) or of known.shape).  The struct holds raw pointers: keep both tensors alive."""
+    if not (known.is_cuda and known.dtype == torch.float32 and known.is_contiguous()):
+        raise ValueError("known must be a contiguous float32 device tensor")
+    B = known.shape[0]
+    per = known.numel() // B
+    stride = 0
+    if mask is not None:
+        if not (mask.is_cuda and mask.dtype == torch.float32 and mask.is_contiguous() and mask.device == known.device):
+            raise ValueError("mask must be a contiguous float32 tensor on known's device")
+        if tuple(mask.shape) == tuple(known.shape):
+            stride = per
+        elif tuple(mask.shape) != tuple(known.shape[1:]):
+            raise ValueError(f"mask shape {tuple(mask.shape)} must be {tuple(known.shape[1:])} (one sample, shared) or "
+                             f"{tuple(known.shape)}")
+    return L.LatentGuide(known.data_ptr(), L.ptr(mask), stride, noise_key(seed, sample_offset))
+
+
+def latent_guide(known: Tensor, tau: Tensor, alpha_bar: Tensor, z: Optional[Tensor] = None, mask: Optional[Tensor] = None, *,
+                 seed: int = 0, sample_offset: int = 0) -> Tensor:
+    """The latent guide's blend (avd_latent_guide_f32; contract in include/avdiff_hip.h): out[b] = blend(mask, q(tau[b]), z[b]) with
+    q(tau) = sqrt(a) known + sqrt(1 - a) n_k, n_k the known-noise stream of (seed, sample_offset + b).  ``z`` None: out = q (the known
+    latent forward-noised to tau; tau < 0 returns ``known`` itself).  ``mask``: see latent_guide_desc.  ``tau``: int [B]."""
+    known = L.dev_f32(known, "known").contiguous()
+    dev = known.device
+    B = known.shape[0]
+    m = None if mask is None else L.dev_f32(mask, "mask").contiguous()
+    g = latent_guide_desc(known, m, seed, sample_offset)
+    tn = L.dev_i64(tau, dev)
+    if tn.numel() != B:
+        raise ValueError(f"tau has {tn.numel()} entries, known has {B} samples")
+    zz = None
+    if z is not None:
+        zz = L.dev_f32(z, "z").contiguous()
+        if zz.shape != known.shape:
+            raise ValueError(f"z shape {tuple(zz.shape)} != known shape {tuple(known.shape)}")
+    ab = alpha_bar if (alpha_bar.is_cuda and alpha_bar.dtype == torch.float32) else alpha_bar.to(dev, torch.float32)
+    ab = ab.contiguous()
+    out = torch.empty_like(known)
+    L.check(L.lib().avd_latent_guide_f32(C.byref(g), tn.data_ptr(), ab.data_ptr(), ab.numel(), L.ptr(zz), out.data_ptr(), B,
+                                         known.numel() // B, _st(out)))
+    return out
+
+
 def gaussian_noise(seed: int, sample_offset: int, t_now: Tensor, shape) -> Tensor:
     """The seeded normal stream of the DDIM eta > 0 noise (avd_gaussian_noise_f32; contract in include/avdiff_hip.h): a
     float32 tensor of ``shape`` = (B, ...) whose row b holds sample ``sample_offset + b``'s normals at timestep ``t_now[b]``,

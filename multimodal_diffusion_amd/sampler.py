@@ -137,6 +137,12 @@ class DenoiseEngine:
     (include/avdiff_hip.h, avd_dpmpp_2m_step_f32) inside the same fused CFG kernel — second order, one model call per step, eta == 0
     only.  The engine owns the solver's history ``x0_hist`` (the previous step's x0, allocated once: a captured graph keeps its
     address); ``step(..., t_last=None)`` takes a first-order step, and ``run`` starts every trajectory first order.
+
+    ``set_known(known, mask)`` (extension: latent inpainting / outpainting, SDEdit): while a known clean latent is set, every step
+    ends in the latent guide's blend (include/avdiff_hip.h, avd_latent_guide) inside the same fused kernel — z_out = blend(mask,
+    q(t_prev), step(z)) with q the known latent forward-noised to t_prev along the known-noise stream of (guide_seed,
+    sample_offset + b).  ``start_latent`` builds the trajectory's start for a ``strength``; ``clear_known`` returns to the plain
+    step.  The known latent and the mask live in engine-owned buffers, so a captured graph replays guided steps.
     """
 
     SOLVERS = ("ddim", "dpmpp_2m")
@@ -227,6 +233,11 @@ class DenoiseEngine:
         if solver == "dpmpp_2m":
             self.x0_hist = torch.zeros(self.latent_shape, device=self.device, dtype=torch.float32)
             self._no_hist = torch.full((B,), -1, dtype=torch.long, device=self.device)
+        # latent guide (set_known): the known latent and the mask at fixed addresses, and the avd_latent_guide over them
+        self._known: Optional[torch.Tensor] = None
+        self._mask: Optional[torch.Tensor] = None
+        self._guide: Optional[L.LatentGuide] = None
+        self._guide_sig = None       # what a captured graph holds of the guide by value: pointers, stride, seed
         self._bind_weights()
 
     # ---- pointer tables.  They hold derived copies (norm-folded / split3 weights), so they are re-derived whenever a
@@ -349,6 +360,74 @@ class DenoiseEngine:
         self.Xp = Xp
         return Xp
 
+    # ---- latent guide: a known clean latent the trajectory is held to (inpainting / outpainting) or starts from (SDEdit) ----
+    def set_known(self, known: torch.Tensor, mask: Optional[torch.Tensor] = None, *, guide_seed: int = 0) -> None:
+        """Hold the trajectory to ``known`` (the clean latent, the engine's latent shape) where ``mask`` is 1, blend where it is
+        fractional, leave it free where it is 0.  ``mask``: None = 1 everywhere, else values in [0, 1] broadcastable to one
+        sample's latent shape (shared by the batch) or to the batch's.  ``guide_seed`` keys the known-noise stream with the
+        engine's sample_offset.  Both are copied into engine-owned buffers: a later call with the same shapes, mask presence and
+        seed keeps every captured graph valid."""
+        known = L.dev_f32(known, "known")
+        if tuple(known.shape) != self.latent_shape:
+            raise ValueError(f"known latent shape {tuple(known.shape)} != engine shape {self.latent_shape}")
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask).to(self.device, torch.float32)
+            shape = self.latent_shape[1:] if m.dim() < len(self.latent_shape) else self.latent_shape
+            try:
+                m = m.expand(shape)
+            except RuntimeError:
+                raise ValueError(f"mask shape {tuple(m.shape)} does not broadcast to {self.latent_shape[1:]} or "
+                                 f"{self.latent_shape}") from None
+            if not bool(((m >= 0) & (m <= 1)).all()):
+                raise ValueError("mask values must lie in [0, 1]")
+        Fn.noise_key(guide_seed, self.sample_offset)         # validates the seed
+        if self._known is None:
+            self._known = torch.empty(self.latent_shape, device=self.device, dtype=torch.float32)
+        self._known.copy_(known)
+        if m is not None:
+            if self._mask is None or tuple(self._mask.shape) != tuple(m.shape):
+                self._mask = torch.empty(tuple(m.shape), device=self.device, dtype=torch.float32)
+            self._mask.copy_(m)
+        self._guide = Fn.latent_guide_desc(self._known, self._mask if m is not None else None, guide_seed, self.sample_offset)
+        self._touch_guide()
+
+    def clear_known(self) -> None:
+        """Back to the plain step (the buffers are kept for a later set_known)."""
+        self._guide = None
+        self._touch_guide()
+
+    def _touch_guide(self) -> None:
+        g = self._guide
+        sig = None if g is None else (g.known, g.mask, g.mask_batch_stride, g.key.seed)
+        if sig != self._guide_sig:
+            self._generation += 1
+            self._stale_reason = "the latent guide's buffers, mask presence or seed changed (set_known / clear_known)"
+        self._guide_sig = sig
+
+    def start_latent(self, z_init: torch.Tensor, sched: torch.Tensor, strength: float = 1.0):
+        """(z_start, sched_k): the start of a guided trajectory at ``strength`` (schedule_utils.truncate_schedule: k of the n steps
+        of ``sched`` are run, from t_s = sched_k[0]).  k = n (strength 1): blend(mask, q(t_s), z_init) — the masked region starts on
+        the known clip's forward path, the rest is the caller's noise.  k < n: q(t_s) everywhere (SDEdit: the unmasked region becomes
+        a variation of the known clip); k = 0 returns the known latent itself.  Without a known latent only strength 1 is allowed and
+        z_start is z_init.  Computed on the device (avd_latent_guide_f32)."""
+        sched_k = su.truncate_schedule(sched, strength)
+        n = torch.as_tensor(sched).numel() - 1
+        z_init = L.dev_f32(z_init, "z_init")
+        if tuple(z_init.shape) != self.latent_shape:
+            raise ValueError(f"latent shape {tuple(z_init.shape)} != engine shape {self.latent_shape}")
+        if self._guide is None:
+            if sched_k.numel() - 1 != n:
+                raise ValueError("strength < 1 starts from the known latent: call set_known() first")
+            return z_init, sched_k
+        B = self.embed.B
+        tau = torch.full((B,), int(sched_k[0]), dtype=torch.long, device=self.device)
+        out = torch.empty_like(z_init)
+        z = z_init if sched_k.numel() - 1 == n else None
+        L.check(L.lib().avd_latent_guide_f32(C.byref(self._guide), tau.data_ptr(), self.alpha_bar.data_ptr(), self.alpha_bar.numel(),
+                                             L.ptr(z), out.data_ptr(), B, z_init.numel() // B, L.stream_ptr(self.device)))
+        return out, sched_k
+
     def step(self, z: torch.Tensor, t_now: torch.Tensor, t_prev: torch.Tensor,
              noise: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
              t_last: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -363,6 +442,8 @@ class DenoiseEngine:
         if not torch.cuda.is_current_stream_capturing():
             self._sync_weights()
         out = torch.empty_like(z) if out is None else out
+        if self._guide is not None:
+            return self._step_guided(z, tn, tp, noise, out, t_last)
         if self.solver == "dpmpp_2m":
             if noise is not None:
                 raise ValueError("solver 'dpmpp_2m' is deterministic: it takes no noise")
@@ -389,6 +470,26 @@ class DenoiseEngine:
         L.check(L.lib().avd_denoise_step_f32(C.byref(self.desc), z.data_ptr(), self.Xp.data_ptr(), tn.data_ptr(),
                                              tp.data_ptr(), L.ptr(noise), out.data_ptr(), self.workspace.data_ptr(),
                                              self.workspace.numel(), L.stream_ptr(self.device)))
+        return out
+
+    def _step_guided(self, z, tn, tp, noise, out, t_last) -> torch.Tensor:
+        if noise is not None:
+            raise ValueError("a guided step draws its noise from noise_seed: it takes no `noise`")
+        if self.eta > 0 and self._key is None:
+            raise ValueError("with a known latent, eta > 0 needs noise_seed (unseeded noise is not supported with a guide)")
+        tl = h = None
+        if self.solver == "dpmpp_2m":
+            h = self.x0_hist
+            for name, t in (("z", z), ("out", out)):
+                if t.untyped_storage().data_ptr() == h.untyped_storage().data_ptr():
+                    raise L.AvdError(f"{name} must not alias the engine's x0_hist (the solver history)")
+            tl = self._no_hist if t_last is None else L.dev_i64(t_last, self.device)
+        elif t_last is not None:
+            raise ValueError("t_last is the multistep solver's history: this engine runs solver 'ddim'")
+        L.check(L.lib().avd_denoise_step_guided_f32(C.byref(self.desc), C.byref(self._guide),
+                                                    None if self._key is None else C.byref(self._key), L.ptr(tl), L.ptr(h),
+                                                    z.data_ptr(), self.Xp.data_ptr(), tn.data_ptr(), tp.data_ptr(), out.data_ptr(),
+                                                    self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device)))
         return out
 
     def eps_tokens(self) -> torch.Tensor:
@@ -469,6 +570,27 @@ class DenoiseEngine:
         return za
 
 
+def frame_mask(latent_shape, lo: int, hi: int) -> torch.Tensor:
+    """A latent guide mask (DenoiseEngine.set_known, sample_one_direction ``mask``): float32 ones on latent frames [lo, hi) and zeros
+    elsewhere — the T axis of a video latent ([C,T,H,W] or [B,C,T,H,W]), the F axis of an audio latent ([Ca,F] or [B,Ca,F]).
+    "Keep the first frames and generate what follows" is frame_mask(shape, 0, k).  CPU tensor of ``latent_shape``."""
+    shape = tuple(int(s) for s in latent_shape)
+    if len(shape) in (4, 5):
+        axis = len(shape) - 3
+    elif len(shape) in (2, 3):
+        axis = len(shape) - 1
+    else:
+        raise ValueError(f"latent_shape {shape} is neither a video ([B,]C,T,H,W) nor an audio ([B,]Ca,F) latent")
+    n = shape[axis]
+    if not 0 <= lo <= hi <= n:
+        raise ValueError(f"frames [{lo}, {hi}) must lie within [0, {n}]")
+    m = torch.zeros(shape, dtype=torch.float32)
+    idx = [slice(None)] * len(shape)
+    idx[axis] = slice(lo, hi)
+    m[tuple(idx)] = 1.0
+    return m
+
+
 # ----------------------------------------------------------------------------------------------------------
 # reference-signature entry point (B = 1, codec / VAE supplied by the caller)
 # ----------------------------------------------------------------------------------------------------------
@@ -478,7 +600,9 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
                          core: MMDiT, head: MultiModalNoiseHead, tstep_dim: int, prompt_modality: str,
                          prompt_video: Optional[np.ndarray], prompt_audio: Optional[np.ndarray],
                          device: torch.device, init_noise: Optional[torch.Tensor] = None,
-                         noise_seed: Optional[int] = None) -> Dict[str, np.ndarray]:
+                         noise_seed: Optional[int] = None, init_video: Optional[np.ndarray] = None,
+                         init_audio: Optional[np.ndarray] = None, strength: float = 1.0, mask=None,
+                         guide_seed: Optional[int] = None) -> Dict[str, np.ndarray]:
     """sample_clip.py:220-394 with the loop on the HIP engine.  The V->A branch uses the [1,3,T,H,W] layout the
     reference's comment intends (its own permute at :288 is a bug that crashes in conv3d).
     ``init_noise`` (extension; default None = draw it as the reference does, :297 / :304): the target's initial latent, so that a
@@ -487,7 +611,26 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
     DDIM noise comes from the seeded stream (DenoiseEngine ``noise_seed``), so the whole trajectory repeats from (init_noise,
     noise_seed).
     ``sampling.solver`` (extension; default "ddim"): "dpmpp_2m" samples with DPM-Solver++(2M) (DenoiseEngine ``solver``) over the
-    same ``sampler_steps`` schedule."""
+    same ``sampler_steps`` schedule.
+    ``init_video`` (uint8 [T,H,W,3], audio->video) / ``init_audio`` (float waveform, video->audio), ``strength``, ``mask``,
+    ``guide_seed`` (extensions; the defaults change nothing): start from, or hold on to, an existing clip of the target modality,
+    encoded with the same ``vid_vae`` / ``aud_codec``.  ``strength`` < 1 runs the last part of the schedule from the encoded clip
+    noised to that point (SDEdit, schedule_utils.truncate_schedule; 0 returns the decoded clip).  ``mask`` (latent-shaped for one
+    sample, e.g. ``frame_mask``; 1 = keep) holds the trajectory to the clip there at every step (DenoiseEngine.set_known); without
+    a mask the whole latent is free.  ``guide_seed`` keys the clip's forward noise (default ``noise_seed``, else 0)."""
+    # argument checks that need no device
+    strength = float(strength)
+    if not 0.0 <= strength <= 1.0:
+        raise ValueError(f"strength must lie in [0, 1], got {strength}")
+    init = init_video if init_video is not None else init_audio
+    if init_video is not None and init_audio is not None:
+        raise ValueError("pass init_video or init_audio, not both")
+    if init is None and (mask is not None or strength < 1.0):
+        raise ValueError("a mask or a strength < 1 needs an init clip (init_video for audio->video, init_audio for video->audio)")
+    if init_video is not None and prompt_modality != "audio":
+        raise ValueError("init_video is the target of the audio->video direction (prompt_modality='audio')")
+    if init_audio is not None and prompt_modality != "video":
+        raise ValueError("init_audio is the target of the video->audio direction (prompt_modality='video')")
     dcfg, scfg = cfg["diffusion"], cfg["sampling"]
     eta = float(scfg.get("ddim_eta", 0.0))
     solver = str(scfg.get("solver", "ddim"))
@@ -534,6 +677,30 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
                         latent_shape=tuple(z.shape), prompt_tokens=n_prompt, alpha_bar=abar, guidance=guide, eta=eta,
                         tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed, solver=solver)
     eng.set_prompt(z_p.float())
+    if init is not None:
+        if target == "video":
+            iv = np.asarray(init_video)
+            if iv.ndim != 4 or iv.shape[-1] != 3 or iv.dtype != np.uint8:
+                raise ValueError(f"init_video must be uint8 [T,H,W,3], got {iv.dtype} {iv.shape}")
+            fr = torch.from_numpy(iv).to(device).float() / 255.0
+            known = vid_vae.encode(fr.permute(3, 0, 1, 2).unsqueeze(0).contiguous())
+        else:
+            ia = np.asarray(init_audio)
+            if ia.ndim != 1 or not np.issubdtype(ia.dtype, np.floating):
+                raise ValueError(f"init_audio must be a float waveform [N], got {ia.dtype} {ia.shape}")
+            known = aud_codec.encode(torch.from_numpy(ia).to(device).float().view(1, 1, -1))
+        if tuple(known.shape) != tuple(z.shape):
+            raise ValueError(f"the init clip encodes to a latent of shape {tuple(known.shape)}, the target's is {tuple(z.shape)}")
+        m = torch.zeros(tuple(z.shape[1:])) if mask is None else torch.as_tensor(mask, dtype=torch.float32)
+        if m.dim() == len(z.shape):
+            m = m.squeeze(0)
+        if tuple(m.shape) != tuple(z.shape[1:]):
+            raise ValueError(f"mask has shape {tuple(m.shape)}, expected one sample's latent shape {tuple(z.shape[1:])}")
+        gs = guide_seed if guide_seed is not None else (noise_seed if noise_seed is not None else 0)
+        eng.set_known(known, m, guide_seed=gs)
+        z, sched = eng.start_latent(z, sched, strength)
+        if mask is None:
+            eng.clear_known()          # SDEdit without a mask: the whole latent is free, the plain step runs
     z = eng.run(z, sched)
     if target == "audio":
         return {"audio": aud_codec.decode(z).squeeze(0).squeeze(0).detach().cpu().numpy(), "sr": sr}

@@ -45,6 +45,21 @@ def make_sampling_schedule(T_train: int, T_sample: int) -> torch.Tensor:
     return torch.linspace(T_train - 1, -1, T_sample + 1).round().to(torch.long)
 
 
+def truncate_schedule(sched, strength: float) -> torch.Tensor:
+    """The tail of a sampling schedule that SDEdit / a partial denoise runs: with n = len(sched) - 1 steps, keep
+    k = min(n, floor(strength * n + 1e-9)) steps, i.e. the last k + 1 entries (k = 0: the one entry -1 of a finished trajectory,
+    no steps).  ``strength`` must lie in [0, 1]; 1 returns the whole schedule.  Host-side (int64 CPU tensor)."""
+    strength = float(strength)
+    if not 0.0 <= strength <= 1.0:
+        raise ValueError(f"strength must lie in [0, 1], got {strength}")
+    sc = torch.as_tensor(sched).reshape(-1).to("cpu", torch.long)
+    if sc.numel() < 1:
+        raise ValueError("the schedule is empty")
+    n = sc.numel() - 1
+    k = min(n, math.floor(strength * n + 1e-9))
+    return sc[n - k:].clone()
+
+
 def timestep_embedding(timesteps: torch.Tensor, dim: int, max_period: int = 10000) -> torch.Tensor:
     """[cos | sin] sinusoidal embedding [B, dim] on the device (schedule_utils.py:64-86)."""
     return Fn.timestep_embedding(timesteps, dim, max_period)

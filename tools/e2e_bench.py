@@ -30,7 +30,13 @@ ap.add_argument("--noise", choices=("both", "seeded", "unseeded"), default="both
                 help="with --eta: the eta > 0 noise source(s) to time — seeded (the in-kernel stream of DenoiseEngine(noise_seed=...)) "
                      "and / or unseeded (torch.randn_like per step)")
 ap.add_argument("--matmul", default="bf16x3", help="with --eta: matrix-pipe mode (default: bench.py's headline mode)")
-ap.add_argument("--reps", type=int, default=5, help="with --eta: interleaved rounds; the median per variant is printed")
+ap.add_argument("--reps", type=int, default=5, help="with --eta / --strength / --keep-frames: interleaved rounds; the median per variant "
+                                                   "is printed")
+ap.add_argument("--strength", type=float, default=None,
+                help="time only the A->V sampler loop with a latent guide (DenoiseEngine.set_known / start_latent) at this SDEdit strength "
+                     "beside the unguided loop, interleaved in one process")
+ap.add_argument("--keep-frames", type=int, default=None,
+                help="with or without --strength: hold the first K latent frames to the known clip (frame_mask) at every step")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 B, S, size = args.batch, args.sampler_steps, args.size
@@ -78,6 +84,49 @@ if args.eta is not None:
             graph = (eng.eta == 0 or eng.noise_seed is not None) and rows < eng.GRAPH_BELOW_ROWS
             print(f"[{args.matmul}] {direction} B={B} {size}x{size} {name:18s}: {med:7.3f} ms/step (min {min(times[name]):7.3f}, "
                   f"{args.reps} rounds of {S} steps, {'graph' if graph else 'eager'})  {100 * (med / base - 1):+6.2f} % vs eta=0", flush=True)
+    sys.exit(0)
+
+if args.strength is not None or args.keep_frames is not None:
+    # latent guide cost: the unguided trajectory against the guided one (start_latent at --strength, a frame_mask of --keep-frames
+    # held at every step through the fused guided step); ms/step over the steps each variant runs
+    import statistics
+    strength = 1.0 if args.strength is None else args.strength
+    K = args.keep_frames or 0
+    known = torch.randn(z0.shape, generator=torch.Generator().manual_seed(4)).to(dev)
+    engs = {}
+    for name in ("unguided", "guided"):
+        eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=tdim, target="video", latent_shape=tuple(z0.shape),
+                              prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul=args.matmul, solver=args.solver)
+        eng.set_prompt(za)
+        if name == "guided":
+            eng.set_known(known, A.frame_mask(tuple(z0.shape[1:]), 0, K), guide_seed=5)
+        eng.run(z0, sched[:4])                          # warm-up
+        engs[name] = eng
+    times = {name: [] for name in engs}
+    n_run = {}
+    for _ in range(args.reps):
+        for name, eng in engs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if name == "guided":
+                z, sk = eng.start_latent(z0, sched, strength)
+                if K == 0:
+                    eng.clear_known()                   # SDEdit without a mask: the plain step
+                eng.run(z, sk)
+                if K == 0:
+                    eng.set_known(known, None, guide_seed=5)
+            else:
+                sk = sched
+                eng.run(z0, sched)
+            torch.cuda.synchronize()
+            n_run[name] = sk.numel() - 1
+            times[name].append(1e3 * (time.perf_counter() - t0) / max(n_run[name], 1))
+    base = statistics.median(times["unguided"])
+    for name in engs:
+        med = statistics.median(times[name])
+        print(f"[{args.matmul}] A->V {args.solver} B={B} {size}x{size} {name:8s} strength={strength if name == 'guided' else 1.0:g} "
+              f"keep_frames={K if name == 'guided' else 0}: {med:7.3f} ms/step (min {min(times[name]):7.3f}, {args.reps} rounds of "
+              f"{n_run[name]} steps)  {100 * (med / base - 1):+6.2f} % vs unguided", flush=True)
     sys.exit(0)
 
 MODES = args.modes.split(",")
