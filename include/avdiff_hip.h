@@ -214,6 +214,39 @@ typedef struct {
 int avd_latent_guide_f32(const avd_latent_guide* g, const int64_t* tau, const float* alpha_bar, int T_train,
                          const float* z, float* out, int B, int64_t per_sample, avd_stream_t stream);
 
+/* ---- CFG control: per-sample guidance scales and guidance rescale (Lin et al. 2023, diffusers' rescale_noise_cfg; a public
+ * contract).  For sample b of a call, with n = per_sample (>= 2):
+ *   1. g_b = guidance[b] when that pointer is set, else the scalar guidance (avd_step_desc.guidance); the token-space combine is
+ *      e = null + g_b (cond - null) in fp32 without contraction, as today: an array whose entries all equal g gives the scalar's bits;
+ *   2. U maps tokens to the latent's natural layout: the tube un-patch (a permutation) for video, the overlap-add mean with crop /
+ *      zero-pad (the loop order of the fused audio step) for audio.  c = U(cond tokens), y = U(combined tokens): y is the eps the
+ *      solver consumes without control;
+ *   3. moments in fp64 over the n elements, for v = c and v = y: sigma^2 = (S2 - S1^2 / n) / (n - 1) with S1 = sum v, S2 = sum v^2
+ *      (the unbiased std, as torch.std); s_b = (float)(sigma_c / sigma_y), rounded once; s_b = 1 when sigma_y == 0 or s_b is not
+ *      finite;
+ *   4. r(e) = e where phi_b == 0, e s_b where phi_b == 1 (both selects), else phi_b (e s_b) + (1 - phi_b) e in fp32, in that
+ *      order, without contraction; phi_b = rescale[b], 0 when that pointer is NULL;
+ *   5. the step (DDIM, seeded DDIM or DPM-Solver++(2M)) runs on r(y) in place of y: DPM's x0_hist receives the x0 of r(y); a
+ *      latent guide's blend (avd_latent_guide) still comes last.
+ * s_b is a pure function of sample b's eps tokens, g_b and the geometry: the fp64 sums run over a partition of the sample fixed by
+ * n alone (chunks of 1024 elements in the order of the source layout, tokens for video and the latent for audio), the chunks'
+ * partials are stored with plain stores and summed in index order, no float atomics.  s_b is therefore the same at any B,
+ * sample_offset, split_streams setting, eager or graph launch.  The kernels trust the device values: phi_b outside [0, 1] or NaN is
+ * not detected there (DenoiseEngine / set_cfg / functional.cfg_rescale check them before upload). */
+typedef struct {
+    const float* guidance;     /* fp32 [B] per-sample guidance scales, or NULL (the scalar) */
+    const float* rescale;      /* fp32 [B] per-sample phi in [0, 1], or NULL (phi = 0: no statistics pass, no rescale) */
+    void* stats;               /* caller-owned scratch of >= avd_cfg_stats_bytes(B, per_sample) bytes, 16-byte aligned; needed
+                                  when rescale is set; must not overlap z_out or x0_hist */
+    int64_t stats_bytes;       /* its size */
+} avd_cfg_control;
+/* Bytes of the statistics scratch of B samples of per_sample (>= 2) elements; -1 on bad arguments. */
+int64_t avd_cfg_stats_bytes(int B, int64_t per_sample);
+/* The rescale alone, on latent-layout tensors (steps 3 and 4 with c = e_cond, y = e_cfg): out[b] = r(e_cfg[b]).  e_cond, e_cfg,
+ * out: fp32 [B, per_sample]; phi: fp32 [B] on the device.  out may alias e_cfg. */
+int avd_cfg_rescale_f32(const float* e_cond, const float* e_cfg, const float* phi, void* stats, int64_t stats_bytes, float* out,
+                        int B, int64_t per_sample, avd_stream_t stream);
+
 /* ---- a8 fused: CFG combine + tube un-patch + DDIM — avdiff/models/infer/sample_clip.py:381-389.
  * eps2: [2B,Nv,C*t*h*w] (cond batch then null batch); eps = null + g*(cond-null); un-patched on the fly.
  * z, z_out: [B,C,T,H,W]. */
@@ -461,6 +494,14 @@ int avd_denoise_step_guided_f32(const avd_step_desc* s, const avd_latent_guide* 
                                 const int64_t* t_last, float* x0_hist, const float* z, const float* Xp,
                                 const int64_t* t_now, const int64_t* t_prev, float* z_out,
                                 void* workspace, int64_t workspace_bytes, avd_stream_t stream);
+/* The whole CFG step under a CFG control (avd_cfg_control): per-sample guidance and / or guidance rescale.  With ctl->rescale set, a
+ * statistics pass runs on the stream right before the fused update (after the join of split_streams).  g (the latent guide), key,
+ * t_last and x0_hist are optional and mean what they mean in avd_denoise_step_guided_f32 (eta > 0 needs a key).  Graph-capturable:
+ * the per-sample arrays and the scratch are read at their addresses at every launch. */
+int avd_denoise_step_cfg_f32(const avd_step_desc* s, const avd_cfg_control* ctl, const avd_latent_guide* g,
+                             const avd_noise_key* key, const int64_t* t_last, float* x0_hist, const float* z, const float* Xp,
+                             const int64_t* t_now, const int64_t* t_prev, float* z_out,
+                             void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 
 /* ---- a9 / next-1: VideoVAE.decode — avdiff/models/encoders/vae_video3d.py:195-214 (decode), :79-84
  * (_conv_block_3d: Conv3d 3x3x3 pad 1 -> GELU(erf) -> GroupNorm(min(8,C), eps 1e-5, affine)), :108-119.

@@ -73,6 +73,12 @@ class LatentGuide(C.Structure):
     _fields_ = [("known", C.c_void_p), ("mask", C.c_void_p), ("mask_batch_stride", C.c_int64), ("key", NoiseKey)]
 
 
+class CfgControl(C.Structure):
+    """avd_cfg_control: per-sample guidance scales and guidance rescale phi (device [B] arrays, either may be NULL) and the
+    statistics scratch (contract in include/avdiff_hip.h)."""
+    _fields_ = [("guidance", C.c_void_p), ("rescale", C.c_void_p), ("stats", C.c_void_p), ("stats_bytes", C.c_int64)]
+
+
 class VaeDecodeDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("Cv", C.c_int), ("Tp", C.c_int), ("Hp", C.c_int), ("Wp", C.c_int),
                 ("T", C.c_int), ("H", C.c_int), ("W", C.c_int),
@@ -139,6 +145,10 @@ SIGNATURES = {
     "avd_latent_guide_f32": (_I, [C.POINTER(LatentGuide), _P, _P, _I, _P, _P, _I, _L, _P]),
     "avd_denoise_step_guided_f32": (_I, [C.POINTER(StepDesc), C.POINTER(LatentGuide), C.POINTER(NoiseKey), _P, _P, _P, _P, _P, _P, _P,
                                          _P, _L, _P]),
+    "avd_cfg_stats_bytes": (_L, [_I, _L]),
+    "avd_cfg_rescale_f32": (_I, [_P, _P, _P, _P, _L, _P, _I, _L, _P]),
+    "avd_denoise_step_cfg_f32": (_I, [C.POINTER(StepDesc), C.POINTER(CfgControl), C.POINTER(LatentGuide), C.POINTER(NoiseKey), _P, _P, _P,
+                                      _P, _P, _P, _P, _P, _L, _P]),
     "avd_split3_bytes": (_L, [_L, _I]),
     "avd_split3_f32": (_I, [_P, _P, _L, _I, _P]),
     "avd_rmsnorm_split3_f32": (_I, [_P, _P, _P, _L, _I, _F, _P]),

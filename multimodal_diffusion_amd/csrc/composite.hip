@@ -79,13 +79,15 @@ int assemble_rows_f32(float* X2, const int64_t* t_now, const float* freqs, const
 int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key = nullptr,
-                         const int64_t* t_last = nullptr, float* x0_hist = nullptr, const avd_latent_guide* guide = nullptr);
+                         const int64_t* t_last = nullptr, float* x0_hist = nullptr, const avd_latent_guide* guide = nullptr,
+                         const avd_cfg_control* ctl = nullptr);
 int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st,
                                const avd_noise_key* key = nullptr, const int64_t* t_last = nullptr, float* x0_hist = nullptr,
-                               const avd_latent_guide* guide = nullptr);
+                               const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr);
 int check_latent_guide(const avd_latent_guide* g, int B, int64_t per, const float* out, const float* x0_hist);
+int check_cfg_control(const avd_cfg_control* ctl, int B, int64_t per, const float* out, const float* x0_hist);
 
 static inline int64_t align_up(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
@@ -730,11 +732,12 @@ extern "C" int64_t avd_step_workspace_bytes(const avd_step_desc* s) {
 
 // the body of avd_denoise_step_f32 / avd_denoise_step_seeded_f32 / avd_denoise_step_dpmpp_2m_f32: key != nullptr draws the eta > 0
 // noise from the seeded stream; x0_hist != nullptr ends the step with the DPM-Solver++(2M) update instead of DDIM; guide != nullptr
-// blends the known latent into the update's result (avd_denoise_step_guided_f32)
+// blends the known latent into the update's result (avd_denoise_step_guided_f32); ctl != nullptr applies the CFG control
+// (avd_denoise_step_cfg_f32: its statistics pass runs in the fused update's launcher, on st after the join of the two streams)
 static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp, const int64_t* t_now,
                         const int64_t* t_prev, const float* noise, float* z_out, void* workspace, int64_t workspace_bytes,
                         avd_stream_t stream, const int64_t* t_last = nullptr, float* x0_hist = nullptr,
-                        const avd_latent_guide* guide = nullptr) {
+                        const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr) {
     StepPlan p;
     if (int rc = plan_step(s, p)) return rc;
     AVD_REQUIRE(z && z_out && t_now && t_prev && s->alpha_bar && s->adapt_w, AVD_EINVAL, "step: null pointer");
@@ -787,9 +790,9 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
     }
     if (e.target_kind == 0)
         return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, s->alpha_bar, s->T_train, s->guidance, s->eta, noise, z_out,
-                                    e.B, e.C, e.T, e.H, e.W, e.p0, e.p1, e.p2, st, key, t_last, x0_hist, guide);
+                                    e.B, e.C, e.T, e.H, e.W, e.p0, e.p1, e.p2, st, key, t_last, x0_hist, guide, ctl);
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, s->alpha_bar, s->T_train, s->guidance, s->eta, noise, z_out,
-                                      e.B, e.C, e.T, e.p0, e.p1, st, key, t_last, x0_hist, guide);
+                                      e.B, e.C, e.T, e.p0, e.p1, st, key, t_last, x0_hist, guide, ctl);
 }
 
 extern "C" int avd_denoise_step_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_now,
@@ -840,6 +843,30 @@ extern "C" int avd_denoise_step_guided_f32(const avd_step_desc* s, const avd_lat
         AVD_REQUIRE(key->sample_offset >= 0 && key->sample_offset + (int64_t)s->embed.B <= ((int64_t)1 << 32), AVD_EINVAL,
                     "denoise_step_guided: sample_offset %lld + B %d must lie in [0, 2^32]", (long long)key->sample_offset, s->embed.B);
     return denoise_step(s, key, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, g);
+}
+
+extern "C" int avd_denoise_step_cfg_f32(const avd_step_desc* s, const avd_cfg_control* ctl, const avd_latent_guide* g,
+                                        const avd_noise_key* key, const int64_t* t_last, float* x0_hist, const float* z, const float* Xp,
+                                        const int64_t* t_now, const int64_t* t_prev, float* z_out, void* workspace,
+                                        int64_t workspace_bytes, avd_stream_t stream) {
+    AVD_REQUIRE(s, AVD_EINVAL, "step: null descriptor");
+    // checked here as well as in the fused kernel's launcher: before the model runs, and for both targets
+    const int64_t n = (int64_t)s->embed.B * s->embed.C * s->embed.T * s->embed.H * s->embed.W;
+    const int64_t per = s->embed.B > 0 ? n / s->embed.B : 0;
+    if (int rc = check_cfg_control(ctl, s->embed.B, per, z_out, x0_hist)) return rc;
+    if (g)
+        if (int rc = check_latent_guide(g, s->embed.B, per, z_out, x0_hist)) return rc;
+    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "denoise_step_cfg: t_last and x0_hist go together (the DPM-Solver++(2M) update)");
+    if (x0_hist) {
+        AVD_REQUIRE(s->eta == 0.f, AVD_EINVAL, "denoise_step_cfg: DPM-Solver++(2M) needs eta == 0");
+        AVD_REQUIRE(!(z && x0_hist < z + n && z < x0_hist + n) && !(z_out && x0_hist < z_out + n && z_out < x0_hist + n), AVD_EINVAL,
+                    "denoise_step_cfg: x0_hist must not alias z or z_out");
+    }
+    AVD_REQUIRE(s->eta == 0.f || key, AVD_EINVAL, "denoise_step_cfg: eta > 0 needs a noise key (unseeded noise is not supported here)");
+    if (key)
+        AVD_REQUIRE(key->sample_offset >= 0 && key->sample_offset + (int64_t)s->embed.B <= ((int64_t)1 << 32), AVD_EINVAL,
+                    "denoise_step_cfg: sample_offset %lld + B %d must lie in [0, 2^32]", (long long)key->sample_offset, s->embed.B);
+    return denoise_step(s, key, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, g, ctl);
 }
 
 extern "C" int avd_prof_enable(int on) {

@@ -532,6 +532,220 @@ int latent_guide_f32(const avd_latent_guide* g, const int64_t* tau, const float*
     return AVD_OK;
 }
 
+// ------------------------------------------------------------------ CFG control: per-sample guidance, guidance rescale
+// The contract is written out in include/avdiff_hip.h (avd_cfg_control).  The statistics pass below writes one fp64 partial of
+// (sum c, sum c^2, sum y, sum y^2) per CFG_CHUNK elements of a sample, the finalize pass sums them in index order and stores s_b; the
+// fused kernels then read (g_b, phi_b, s_b) per sample through a CfgState in their trailing pack and step on r(y).
+constexpr int CFG_CHUNK = 1024;          // elements per partial: 256 lanes x 4 consecutive elements; fixed, so s_b depends on n alone
+
+struct CfgState {
+    const float* guidance;   // [B] or nullptr (the scalar)
+    const float* rescale;    // [B] or nullptr (phi = 0)
+    const float* scale;      // [B] s_b, written by cfg_stats_finalize_kernel (read only when rescale is set)
+};
+struct CfgCoef {
+    float g, phi, s;
+};
+__device__ __forceinline__ CfgCoef cfg_coef(const CfgState& cs, float guidance, int b) {
+    CfgCoef c{cs.guidance ? cs.guidance[b] : guidance, 0.f, 1.f};
+    if (cs.rescale) {
+        c.phi = cs.rescale[b];
+        c.s = cs.scale[b];
+    }
+    return c;
+}
+// r(e) of the contract: selects at phi 0 and 1, else diffusers' blend without contraction
+__device__ __forceinline__ float cfg_rescale(float e, float phi, float s) {
+#pragma clang fp contract(off)
+    return phi == 0.f ? e : (phi == 1.f ? e * s : phi * (e * s) + (1.0f - phi) * e);
+}
+// the eps a fused kernel steps on: today's combine (the instantiations without a CfgState), or r(combine with g_b)
+template <bool CTL>
+__device__ __forceinline__ float cfg_eps(float ec, float en, float guidance, const CfgCoef& cc) {
+    if constexpr (CTL) return cfg_rescale(cfg_combine(ec, en, cc.g), cc.phi, cc.s);
+    else return cfg_combine(ec, en, guidance);
+}
+
+static int64_t cfg_chunks(int64_t per) { return (per + CFG_CHUNK - 1) / CFG_CHUNK; }
+static int64_t cfg_scale_off(int B, int64_t per) { return ((int64_t)B * cfg_chunks(per) * 32 + 15) & ~(int64_t)15; }
+int64_t cfg_stats_bytes(int B, int64_t per) {
+    if (B <= 0 || per < 2 || per >= ((int64_t)1 << 34)) return -1;
+    return cfg_scale_off(B, per) + (((int64_t)B * 4 + 15) & ~(int64_t)15);
+}
+
+// Where c and y come from.  PAIR: latent-layout tensors c = a[b], y = y[b] (avd_cfg_rescale_f32).  VIDEO: the cond / null token
+// rows of the fused step, c = cond, y = cfg_combine(cond, null, g_b) (U is a permutation: the moments are those of the tokens).
+// AUDIO: U is the overlap-add mean, computed per element as cfg_untoken_ddim_audio_kernel does.
+enum { CFG_SRC_PAIR = 0, CFG_SRC_VIDEO = 1, CFG_SRC_AUDIO = 2 };
+
+struct AudioGeom {
+    int Ca, F, len, stride, Na;
+};
+
+// grid (chunks, B): block (j, b) writes part[(b * chunks + j) * 4 + {0..3}] = sums over elements [j * 1024, (j + 1) * 1024) of sample b.
+// a / y: sample b's source at a + b * sstride (PAIR, VIDEO: cond tokens; AUDIO: cond tokens) and y + b * sstride (PAIR: y; VIDEO,
+// AUDIO: null tokens).
+template <int SRC>
+__global__ __launch_bounds__(256) void cfg_stats_kernel(const float* __restrict__ a, const float* __restrict__ y, int64_t sstride,
+                                                        const float* __restrict__ gvec, float guidance, double* __restrict__ part,
+                                                        int64_t per, AudioGeom ag) {
+#pragma clang fp contract(off)
+    __shared__ double red[4][4];
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const float gb = gvec ? gvec[b] : guidance;
+    const float* sa = a + (int64_t)b * sstride;
+    const float* sy = y + (int64_t)b * sstride;
+    const int64_t el0 = (int64_t)blockIdx.x * CFG_CHUNK + threadIdx.x * 4;
+    f32x4 cv = {0.f, 0.f, 0.f, 0.f}, yv = {0.f, 0.f, 0.f, 0.f};
+    int nv = 0;                                        // valid elements of this lane (elements >= per add nothing)
+    if (el0 < per) {
+        nv = per - el0 < 4 ? (int)(per - el0) : 4;
+        if constexpr (SRC == CFG_SRC_VIDEO) {          // per % 4 == 0 (w % 4 == 0): a whole float4
+            const f32x4 ec = *reinterpret_cast<const f32x4*>(sa + el0), en = *reinterpret_cast<const f32x4*>(sy + el0);
+            cv = ec;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) yv[k] = cfg_combine(ec[k], en[k], gb);
+        } else {
+            for (int k = 0; k < nv; ++k) {
+                const int64_t el = el0 + k;
+                if constexpr (SRC == CFG_SRC_PAIR) {
+                    cv[k] = sa[el];
+                    yv[k] = sy[el];
+                } else {                                // as cfg_untoken_ddim_audio_kernel: same windows, same order
+                    const int f = (int)(el % ag.F), ch = (int)(el / ag.F);
+                    const int L = (ag.Na - 1) * ag.stride + ag.len, D = ag.Ca * ag.len;
+                    float c = 0.f, e = 0.f;
+                    if (f < L) {
+                        int n_hi = f / ag.stride;
+                        if (n_hi > ag.Na - 1) n_hi = ag.Na - 1;
+                        const int n_lo = (f - ag.len + 1 <= 0) ? 0 : (f - ag.len + ag.stride) / ag.stride;
+                        float acc = 0.f, accc = 0.f, cnt = 0.f;
+                        for (int n = n_lo; n <= n_hi; ++n) {
+                            const int64_t o = (int64_t)n * D + ch * ag.len + (f - n * ag.stride);
+                            acc += cfg_combine(sa[o], sy[o], gb);
+                            accc += sa[o];
+                            cnt += 1.f;
+                        }
+                        e = acc / fmaxf(cnt, 1e-8f);
+                        c = accc / fmaxf(cnt, 1e-8f);
+                    }
+                    cv[k] = c;
+                    yv[k] = e;
+                }
+            }
+        }
+    }
+    double m[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < nv; ++k) {
+        const double c = (double)cv[k], e = (double)yv[k];
+        m[0] += c;
+        m[1] += c * c;
+        m[2] += e;
+        m[3] += e * e;
+    }
+    // fixed-order block sum: a butterfly within each wave (lane 0's result is a fixed function of the inputs), then waves 0..3
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        for (int o = 32; o > 0; o >>= 1) m[q] += __shfl_xor(m[q], o, 64);
+    if (lane == 0)
+        for (int q = 0; q < 4; ++q) red[wv][q] = m[q];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int q = threadIdx.x;
+        part[((int64_t)b * gridDim.x + blockIdx.x) * 4 + q] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
+    }
+}
+
+// one lane per sample: the partials summed in index order, then s_b of the contract
+__global__ void cfg_stats_finalize_kernel(const double* __restrict__ part, float* __restrict__ scale, int B, int chunks, int64_t per) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    const double* p = part + (int64_t)b * chunks * 4;
+    for (int j = 0; j < chunks; ++j)
+        for (int q = 0; q < 4; ++q) s[q] += p[(int64_t)j * 4 + q];
+    const double n = (double)per;
+    const double sig_c = sqrt((s[1] - s[0] * s[0] / n) / (n - 1.0));
+    const double sig_y = sqrt((s[3] - s[2] * s[2] / n) / (n - 1.0));
+    float r = (float)(sig_c / sig_y);
+    if (sig_y == 0.0 || !isfinite(r)) r = 1.f;
+    scale[b] = r;
+}
+
+__global__ __launch_bounds__(256) void cfg_rescale_kernel(const float* e, const float* __restrict__ phi, const float* __restrict__ scale,
+                                                          float* out, int64_t per, int64_t total) {       // e may be out
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int b = (int)(i / per);
+    out[i] = cfg_rescale(e[i], phi[b], scale[b]);
+}
+
+// true when the byte ranges [a, a + na) and [b, b + nb) overlap
+static bool overlaps_bytes(const void* a, int64_t na, const void* b, int64_t nb) {
+    const char *p = static_cast<const char*>(a), *q = static_cast<const char*>(b);
+    return p < q + nb && q < p + na;
+}
+
+// The checks of a CFG control before any launch; with rescale set, the scratch's size / alignment, and no overlap with out / x0_hist
+static int make_cfg(const avd_cfg_control* ctl, int B, int64_t per, const float* out, const float* x0_hist, CfgState& cs) {
+    AVD_REQUIRE(ctl, AVD_EINVAL, "cfg_control: null control");
+    AVD_REQUIRE(B > 0 && B <= 65535 && per >= 2 && per < ((int64_t)1 << 34), AVD_EINVAL,
+                "cfg_control: bad dims (B %d in [1, 65535], per_sample %lld must be >= 2)", B, (long long)per);
+    cs = CfgState{ctl->guidance, ctl->rescale, nullptr};
+    if (!ctl->rescale) return AVD_OK;
+    const int64_t need = cfg_stats_bytes(B, per);
+    AVD_REQUIRE(ctl->stats, AVD_EINVAL, "cfg_control: rescale needs the statistics scratch (stats)");
+    AVD_REQUIRE(aligned16(ctl->stats), AVD_EUNSUPPORTED, "cfg_control: stats must be 16-byte aligned");
+    AVD_REQUIRE(ctl->stats_bytes >= need, AVD_EINVAL, "cfg_control: stats holds %lld bytes, %lld needed", (long long)ctl->stats_bytes,
+                (long long)need);
+    for (const float* p : {out, x0_hist})
+        AVD_REQUIRE(!p || !overlaps_bytes(ctl->stats, need, p, (int64_t)B * per * 4), AVD_EINVAL,
+                    "cfg_control: stats must not overlap z_out or x0_hist");
+    cs.scale = reinterpret_cast<const float*>(static_cast<const char*>(ctl->stats) + cfg_scale_off(B, per));
+    return AVD_OK;
+}
+
+// make_cfg's checks alone: the composite step runs them before the model (as check_latent_guide)
+int check_cfg_control(const avd_cfg_control* ctl, int B, int64_t per, const float* out, const float* x0_hist) {
+    CfgState cs;
+    return make_cfg(ctl, B, per, out, x0_hist, cs);
+}
+
+// the statistics pass: partials, then s_b into the scratch's scale slot
+template <int SRC>
+static int run_cfg_stats(const avd_cfg_control* ctl, const float* a, const float* y, int64_t sstride, float guidance, int B, int64_t per,
+                         AudioGeom ag, hipStream_t st) {
+    const int64_t chunks = cfg_chunks(per);
+    double* part = static_cast<double*>(ctl->stats);
+    static const int tag = prof_tag_id("cfg_stats_kernel");
+    ProfScope prof(tag, 8.0 * (double)B * per, st);
+    hipLaunchKernelGGL(cfg_stats_kernel<SRC>, dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, st, a, y, sstride, ctl->guidance,
+                       guidance, part, per, ag);
+    hipLaunchKernelGGL(cfg_stats_finalize_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, part,
+                       reinterpret_cast<float*>(static_cast<char*>(ctl->stats) + cfg_scale_off(B, per)), B, (int)chunks, per);
+    AVD_CHECK_LAUNCH("cfg_stats");
+    return AVD_OK;
+}
+
+int cfg_rescale_f32(const float* e_cond, const float* e_cfg, const float* phi, void* stats, int64_t stats_bytes, float* out, int B,
+                    int64_t per, hipStream_t st) {
+    AVD_REQUIRE(e_cond && e_cfg && phi && out, AVD_EINVAL, "cfg_rescale: null pointer");
+    const avd_cfg_control ctl{nullptr, phi, stats, stats_bytes};
+    CfgState cs;
+    if (int rc = make_cfg(&ctl, B, per, out, nullptr, cs)) return rc;
+    const int64_t total = (int64_t)B * per;
+    AVD_REQUIRE(!overlaps_bytes(stats, stats_bytes, e_cond, total * 4) && !overlaps_bytes(stats, stats_bytes, e_cfg, total * 4),
+                AVD_EINVAL, "cfg_rescale: stats must not overlap e_cond or e_cfg");
+    AVD_REQUIRE(out == e_cfg || !overlaps(out, e_cfg, total), AVD_EINVAL, "cfg_rescale: out must be e_cfg or not overlap it");
+    AVD_REQUIRE(!overlaps(out, e_cond, total), AVD_EINVAL, "cfg_rescale: out must not overlap e_cond");
+    AVD_REQUIRE((total + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "cfg_rescale: %lld values is too many for one launch", (long long)total);
+    if (int rc = run_cfg_stats<CFG_SRC_PAIR>(&ctl, e_cond, e_cfg, per, 0.f, B, per, AudioGeom{}, st)) return rc;
+    hipLaunchKernelGGL(cfg_rescale_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, e_cfg, phi, cs.scale, out, per, total);
+    AVD_CHECK_LAUNCH("cfg_rescale");
+    return AVD_OK;
+}
+
 // ------------------------------------------------------------------ fused CFG + unpatch + DDIM (video target)
 int g_cfg_rows = getenv("AVD_CFG_ROWS") ? atoi(getenv("AVD_CFG_ROWS")) : 1;      // avd_tune_set "cfg_rows": 0 = the 16-bytes-per-lane gather form
 // SEEDED: zn comes from the seeded normal stream (philox_normal4: one call is exactly this lane's float4) instead of `noise`.  The key
@@ -544,8 +758,9 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const int64_t* __restrict__ t_prev, const float* __restrict__ abar, int T_train, float guidance, float eta,
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int64_t total4, Key... nk) {
     constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
-    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) && !(SEEDED && DPM),
-                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState");
+    constexpr bool CTL = PackHas<CfgState, Key...>::value;
+    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) + (CTL ? 1 : 0) && !(SEEDED && DPM),
+                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState");
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total4) return;
     const int64_t per4 = g.per >> 2;
@@ -556,10 +771,12 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const f32x4 ec = *reinterpret_cast<const f32x4*>(eps2 + (int64_t)b * g.per + toff);
     const f32x4 en = *reinterpret_cast<const f32x4*>(eps2 + ((int64_t)B + b) * g.per + toff);
     const f32x4 x = *reinterpret_cast<const f32x4*>(z + lat);
+    [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
+    if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
     f32x4 zn = {0.f, 0.f, 0.f, 0.f};
     if constexpr (SEEDED) {
         NoiseKey k;      // a one-item pack is copied as before the guide existed: through pack_get its argument loads reorder
-        if constexpr (GUIDED) k = pack_get<NoiseKey>(nk...);
+        if constexpr (GUIDED || CTL) k = pack_get<NoiseKey>(nk...);
         else k = NoiseKey(nk...);
         zn = philox_normal4(k, (uint32_t)e4, k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
     } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
@@ -572,14 +789,14 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
         if (d.c_1 != 0.f) hist = *reinterpret_cast<const f32x4*>(ds.x0_hist + lat);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            x0[k] = ddim_x0(c, x[k], cfg_combine(ec[k], en[k], guidance));
+            x0[k] = ddim_x0(c, x[k], cfg_eps<CTL>(ec[k], en[k], guidance, cc));
             o[k] = dpm_apply(d, x[k], x0[k], hist[k]);
         }
         *reinterpret_cast<f32x4*>(ds.x0_hist + lat) = x0;
     } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float e = cfg_combine(ec[k], en[k], guidance);
+            const float e = cfg_eps<CTL>(ec[k], en[k], guidance, cc);
             o[k] = ddim_apply(c, x[k], e, zn[k]);
         }
     }
@@ -599,8 +816,9 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     const int64_t* __restrict__ t_prev, const float* __restrict__ abar, int T_train, float guidance, float eta,
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int groups_per_sample, Key... nk) {
     constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
-    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) && !(SEEDED && DPM),
-                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState");
+    constexpr bool CTL = PackHas<CfgState, Key...>::value;
+    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) + (CTL ? 1 : 0) && !(SEEDED && DPM),
+                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState");
     extern __shared__ __attribute__((aligned(16))) float ebuf[];       // [GT][D + 4]: the pad keeps the transposed 16-byte reads off one bank group
     const int LD = g.D + 4;
     const int b = blockIdx.x / groups_per_sample, grp = blockIdx.x % groups_per_sample;
@@ -608,11 +826,13 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     const float* tc = eps2 + ((int64_t)b * (g.per / g.D) + n0) * g.D;
     const float* tn = eps2 + (((int64_t)B + b) * (g.per / g.D) + n0) * g.D;
     const int nf4 = GT * g.D / 4;
+    [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
+    if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
     for (int i = threadIdx.x; i < nf4; i += 256) {
         const f32x4 ec = *reinterpret_cast<const f32x4*>(tc + (int64_t)i * 4), en = *reinterpret_cast<const f32x4*>(tn + (int64_t)i * 4);
         f32x4 e;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) e[k] = cfg_combine(ec[k], en[k], guidance);
+        for (int k = 0; k < 4; ++k) e[k] = cfg_eps<CTL>(ec[k], en[k], guidance, cc);
         const int tok = (i * 4) / g.D, k0 = (i * 4) % g.D;
         *reinterpret_cast<f32x4*>(ebuf + tok * LD + k0) = e;
     }
@@ -648,7 +868,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
             f32x4 zn = {0.f, 0.f, 0.f, 0.f};
             if constexpr (SEEDED) {
                 NoiseKey k;      // as in cfg_unpatch_ddim_kernel
-                if constexpr (GUIDED) k = pack_get<NoiseKey>(nk...);
+                if constexpr (GUIDED || CTL) k = pack_get<NoiseKey>(nk...);
                 else k = NoiseKey(nk...);
                 zn = philox_normal4(k, (uint32_t)((lat - (int64_t)b * g.per) >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
             } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
@@ -660,28 +880,29 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     }
 }
 
-// The guided launches: the solver's state S (nothing, NoiseKey or DpmState) followed by the guide, as the kernels' trailing pack.
-template <class... S>
-static void launch_unpatch_guided(int rows_gt, int groups, dim3 grid, size_t lds, hipStream_t st, const float* eps2, const float* z,
-                                  const int64_t* t_now, const int64_t* t_prev, const float* abar, int T_train, float guidance, float eta,
-                                  const float* noise, float* z_out, const Tube& g, int B, int64_t total4, const GuideState& gs, S... s) {
-    constexpr bool SEEDED = PackHas<NoiseKey, S...>::value;
+// The guided and controlled launches: the kernels' whole trailing pack P — the solver's state (nothing, NoiseKey or DpmState), then
+// optionally the guide, then optionally the CFG control.
+template <class... P>
+static void launch_unpatch(int rows_gt, int groups, dim3 grid, size_t lds, hipStream_t st, const float* eps2, const float* z,
+                           const int64_t* t_now, const int64_t* t_prev, const float* abar, int T_train, float guidance, float eta,
+                           const float* noise, float* z_out, const Tube& g, int B, int64_t total4, P... p) {
+    constexpr bool SEEDED = PackHas<NoiseKey, P...>::value;
     if (rows_gt)
-        hipLaunchKernelGGL((rows_gt == 8 ? cfg_unpatch_ddim_rows_kernel<8, SEEDED, S..., GuideState>
-                                         : cfg_unpatch_ddim_rows_kernel<4, SEEDED, S..., GuideState>),
-                           grid, dim3(256), lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, groups, s..., gs);
+        hipLaunchKernelGGL((rows_gt == 8 ? cfg_unpatch_ddim_rows_kernel<8, SEEDED, P...> : cfg_unpatch_ddim_rows_kernel<4, SEEDED, P...>),
+                           grid, dim3(256), lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, groups, p...);
     else
-        hipLaunchKernelGGL((cfg_unpatch_ddim_kernel<SEEDED, S..., GuideState>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train,
-                           guidance, eta, noise, z_out, g, B, total4, s..., gs);
+        hipLaunchKernelGGL((cfg_unpatch_ddim_kernel<SEEDED, P...>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train,
+                           guidance, eta, noise, z_out, g, B, total4, p...);
 }
 
 // key != nullptr with eta > 0: the noise term is drawn from the seeded stream inside the kernel (`noise` is not read); eta == 0 ignores both
 // x0_hist != nullptr: the DPM-Solver++(2M) update (needs eta == 0 and t_last) instead of DDIM; x0_hist must not overlap z or z_out
 // guide != nullptr: the latent guide's blend ends the update (after either solver), right before z_out is stored
+// ctl != nullptr: per-sample guidance and / or rescale (avd_cfg_control); with rescale set the statistics pass runs first on st
 int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key,
-                         const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide) {
+                         const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl) {
     AVD_REQUIRE(eps2 && z && t_now && t_prev && abar && z_out, AVD_EINVAL, "cfg_unpatch_ddim: null pointer");
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "cfg_unpatch_ddim: bad dims");
     AVD_REQUIRE(eta >= 0.f && (eta == 0.f || noise || key), AVD_EINVAL, "cfg_unpatch_ddim: eta > 0 needs a noise tensor or a noise key");
@@ -706,26 +927,58 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
         AVD_REQUIRE(eta == 0.f || seeded, AVD_EINVAL, "cfg_unpatch_ddim: a guided step with eta > 0 needs a noise key");
         if (int rc = make_guide(guide, B, g.per, z_out, x0_hist, gs)) return rc;
     }
+    CfgState cs{};
+    if (ctl) {
+        AVD_REQUIRE(eta == 0.f || seeded, AVD_EINVAL, "cfg_unpatch_ddim: a controlled step with eta > 0 needs a noise key");
+        if (int rc = make_cfg(ctl, B, g.per, z_out, x0_hist, cs)) return rc;
+        AVD_REQUIRE(!ctl->rescale || (aligned16(eps2) && aligned16(eps2 + (int64_t)B * g.per)), AVD_EUNSUPPORTED,
+                    "cfg_unpatch_ddim: the statistics pass reads 16-byte aligned token rows");
+        if (ctl->rescale)
+            if (int rc = run_cfg_stats<CFG_SRC_VIDEO>(ctl, eps2, eps2 + (int64_t)B * g.per, g.per, guidance, B, g.per, AudioGeom{}, st))
+                return rc;
+    }
     const int64_t total4 = (int64_t)B * (g.per >> 2);
     static const int tag = prof_tag_id("cfg_unpatch_ddim_kernel");
     ProfScope prof(tag, 16.0 * (double)B * g.per, st);
     // whole-line form: groups of tokens along w' that make up 128 bytes (or the whole row when W is shorter) of latent per (c, t, h)
     const int gt = (g.W < 32 ? g.W : 32) / g.w;
     const bool rows = g_cfg_rows && (gt == 8 || gt == 4) && g.Wt % gt == 0 && g.D % 4 == 0 && (int64_t)gt * (g.D + 4) * 4 <= 64 * 1024;
+    if (ctl) {
+        const int groups = rows ? (int)(g.per / g.D) / gt : 0;
+        const size_t lds = rows ? (size_t)gt * (g.D + 4) * 4 : 0;
+        const dim3 grid(rows ? (unsigned)(B * groups) : (unsigned)((total4 + 255) / 256));
+        const int rgt = rows ? gt : 0;
+        // the solver's state, then the tail (guide and / or control)
+        auto go = [&](auto... tail) {
+            if (dpm)
+                launch_unpatch(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
+                               DpmState{t_last, x0_hist}, tail...);
+            else if (seeded)
+                launch_unpatch(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
+                               nk, tail...);
+            else
+                launch_unpatch(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
+                               tail...);
+        };
+        if (guide) go(gs, cs);
+        else go(cs);
+        AVD_CHECK_LAUNCH("cfg_unpatch_ddim (controlled)");
+        return AVD_OK;
+    }
     if (guide) {
         const int groups = rows ? (int)(g.per / g.D) / gt : 0;
         const size_t lds = rows ? (size_t)gt * (g.D + 4) * 4 : 0;
         const dim3 grid(rows ? (unsigned)(B * groups) : (unsigned)((total4 + 255) / 256));
         const int rgt = rows ? gt : 0;
         if (dpm)
-            launch_unpatch_guided(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
-                                  gs, DpmState{t_last, x0_hist});
+            launch_unpatch(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
+                           DpmState{t_last, x0_hist}, gs);
         else if (seeded)
-            launch_unpatch_guided(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
-                                  gs, nk);
+            launch_unpatch(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
+                           nk, gs);
         else
-            launch_unpatch_guided(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
-                                  gs);
+            launch_unpatch(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
+                           gs);
         AVD_CHECK_LAUNCH("cfg_unpatch_ddim (guided)");
         return AVD_OK;
     }
@@ -768,8 +1021,9 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
                                               const float* __restrict__ noise, float* __restrict__ z_out, int B, int Ca,
                                               int F, int len, int stride, int Na, Key... nk) {
     constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
-    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) && !(SEEDED && DPM),
-                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState");
+    constexpr bool CTL = PackHas<CfgState, Key...>::value;
+    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) + (CTL ? 1 : 0) && !(SEEDED && DPM),
+                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)B * Ca * F) return;
     const int f = (int)(i % F);
@@ -777,6 +1031,8 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
     const int b = (int)(i / ((int64_t)F * Ca));
     const int L = (Na - 1) * stride + len;
     const int D = Ca * len;
+    [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
+    if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
     float e = 0.f;
     if (f < L) {
         // CFG combine is linear, but the reference combines per token first and overlap-adds after:
@@ -790,11 +1046,12 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
         for (int n = n_lo; n <= n_hi; ++n) {
             const int64_t o = (int64_t)n * D + c * len + (f - n * stride);
             const float vn = tn[o];
-            acc += cfg_combine(tc[o], vn, guidance);
+            acc += cfg_combine(tc[o], vn, CTL ? cc.g : guidance);
             cnt += 1.f;
         }
         e = acc / fmaxf(cnt, 1e-8f);
     }
+    if constexpr (CTL) e = cfg_rescale(e, cc.phi, cc.s);      // r(y) on the whole latent, the zero pad included
     const Ddim cf = ddim_coef(t_now, t_prev, abar, T_train, eta, b);
     // the guide's epilogue on the value about to be stored (the identity for the unguided instantiations)
     auto fin = [&](float v) {
@@ -811,7 +1068,7 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
         ds.x0_hist[i] = x0;
     } else if constexpr (SEEDED) {
         NoiseKey k;      // as in cfg_unpatch_ddim_kernel
-        if constexpr (GUIDED) k = pack_get<NoiseKey>(nk...);
+        if constexpr (GUIDED || CTL) k = pack_get<NoiseKey>(nk...);
         else k = NoiseKey(nk...);
         const int64_t el = i - (int64_t)b * Ca * F;
         const f32x4 zn = philox_normal4(k, (uint32_t)(el >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
@@ -821,11 +1078,11 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
     }
 }
 
-// key, t_last, x0_hist, guide: as cfg_unpatch_ddim_f32
+// key, t_last, x0_hist, guide, ctl: as cfg_unpatch_ddim_f32
 int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st, const avd_noise_key* key,
-                               const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide) {
+                               const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl) {
     AVD_REQUIRE(eps2 && z && t_now && t_prev && abar && z_out, AVD_EINVAL, "cfg_untoken_ddim_audio: null pointer");
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "cfg_untoken_ddim_audio: bad chunking");
@@ -844,6 +1101,32 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
     const int Na = audio_na(F, len, stride);
     const int64_t n = (int64_t)B * Ca * F;
     const dim3 grid((unsigned)((n + 255) / 256));
+    if (ctl) {
+        AVD_REQUIRE(eta == 0.f || seeded, AVD_EINVAL, "cfg_untoken_ddim_audio: a controlled step with eta > 0 needs a noise key");
+        CfgState cs;
+        if (int rc = make_cfg(ctl, B, (int64_t)Ca * F, z_out, x0_hist, cs)) return rc;
+        GuideState gs{};
+        if (guide)
+            if (int rc = make_guide(guide, B, (int64_t)Ca * F, z_out, x0_hist, gs)) return rc;
+        if (ctl->rescale)
+            if (int rc = run_cfg_stats<CFG_SRC_AUDIO>(ctl, eps2, eps2 + (int64_t)B * Na * Ca * len, (int64_t)Na * Ca * len, guidance, B,
+                                                      (int64_t)Ca * F, AudioGeom{Ca, F, len, stride, Na}, st))
+                return rc;
+        auto launch = [&](auto... p) {
+            constexpr bool SEEDED = PackHas<NoiseKey, decltype(p)...>::value;
+            hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<SEEDED, decltype(p)...>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar,
+                               T_train, guidance, eta, noise, z_out, B, Ca, F, len, stride, Na, p...);
+        };
+        auto go = [&](auto... tail) {
+            if (dpm) launch(DpmState{t_last, x0_hist}, tail...);
+            else if (seeded) launch(nk, tail...);
+            else launch(tail...);
+        };
+        if (guide) go(gs, cs);
+        else go(cs);
+        AVD_CHECK_LAUNCH("cfg_untoken_ddim_audio (controlled)");
+        return AVD_OK;
+    }
     if (guide) {
         AVD_REQUIRE(eta == 0.f || seeded, AVD_EINVAL, "cfg_untoken_ddim_audio: a guided step with eta > 0 needs a noise key");
         GuideState gs;
@@ -1053,14 +1336,14 @@ extern "C" int avd_cfg_unpatch_ddim_f32(const float* eps2, const float* z, const
     AVD_REQUIRE(aligned16(eps2) && aligned16(z) && aligned16(z_out) && (!noise || aligned16(noise)), AVD_EUNSUPPORTED,
                 "cfg_unpatch_ddim: pointers must be 16-byte aligned");
     return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, C, T, H, W, t,
-                                h, w, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr);
+                                h, w, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 extern "C" int avd_cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now,
                                               const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance,
                                               float eta, const float* noise, float* z_out, int B, int Ca, int F, int len,
                                               int stride, avd_stream_t stream) {
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, Ca, F,
-                                      len, stride, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr);
+                                      len, stride, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 extern "C" int avd_gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int B, int64_t per_sample,
                                       avd_stream_t stream) {
@@ -1087,6 +1370,11 @@ extern "C" int avd_dpmpp_2m_step_f32(const float* x_t, const float* eps_hat, flo
                                      int B, int64_t per_sample, avd_stream_t stream) {
     return dpmpp_2m_step_f32(x_t, eps_hat, x0_hist, t_last, t_now, t_prev, alpha_bar, T_train, x_out, B, per_sample,
                              static_cast<hipStream_t>(stream));
+}
+extern "C" int64_t avd_cfg_stats_bytes(int B, int64_t per_sample) { return cfg_stats_bytes(B, per_sample); }
+extern "C" int avd_cfg_rescale_f32(const float* e_cond, const float* e_cfg, const float* phi, void* stats, int64_t stats_bytes, float* out,
+                                   int B, int64_t per_sample, avd_stream_t stream) {
+    return cfg_rescale_f32(e_cond, e_cfg, phi, stats, stats_bytes, out, B, per_sample, static_cast<hipStream_t>(stream));
 }
 extern "C" int avd_latent_guide_f32(const avd_latent_guide* g, const int64_t* tau, const float* alpha_bar, int T_train, const float* z,
                                     float* out, int B, int64_t per_sample, avd_stream_t stream) {

@@ -276,6 +276,46 @@ def latent_guide(known: Tensor, tau: Tensor, alpha_bar: Tensor, z: Optional[Tens
     return out
 
 
+def cfg_values(v, B: int, name: str, lo: Optional[float] = None, hi: Optional[float] = None) -> Tensor:
+    """A per-sample CFG value (a number for every sample, or B numbers as a sequence / array / tensor) as a CPU float32 [B] tensor,
+    after the checks DenoiseEngine, set_cfg and cfg_rescale share: finite, and within [lo, hi] where given (the kernels trust the
+    device values of include/avdiff_hip.h, avd_cfg_control)."""
+    t = torch.as_tensor(v.detach().cpu() if isinstance(v, Tensor) else v, dtype=torch.float32).reshape(-1)
+    if t.numel() == 1:
+        t = t.expand(B)
+    if t.numel() != B:
+        raise ValueError(f"{name} has {t.numel()} values, expected 1 or {B} (one per sample)")
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{name} must be finite, got {t.tolist()}")
+    if lo is not None and not bool(((t >= lo) & (t <= hi)).all()):
+        raise ValueError(f"{name} must lie in [{lo:g}, {hi:g}], got {t.tolist()}")
+    return t.contiguous()
+
+
+def cfg_rescale(e_cond: Tensor, e_cfg: Tensor, phi, *, return_scale: bool = False):
+    """Guidance rescale on latent-layout tensors (avd_cfg_rescale_f32; contract in include/avdiff_hip.h, avd_cfg_control): per sample
+    b, s_b = std(e_cond[b]) / std(e_cfg[b]) (unbiased, fp64 moments, rounded once) and out[b] = r(e_cfg[b]) = phi_b (e s_b) +
+    (1 - phi_b) e (e at phi 0, e s_b at phi 1).  ``phi``: a number or B numbers in [0, 1].  ``return_scale``: also return s (float32
+    [B] on the device)."""
+    ec, ey = L.dev_f32(e_cond, "e_cond"), L.dev_f32(e_cfg, "e_cfg")
+    if ec.shape != ey.shape or ec.device != ey.device:
+        raise ValueError(f"e_cond {tuple(ec.shape)} and e_cfg {tuple(ey.shape)} must have one shape on one device")
+    B = ey.shape[0]
+    per = ey.numel() // B
+    ph = cfg_values(phi, B, "phi", 0.0, 1.0).to(ey.device)
+    nb = L.lib().avd_cfg_stats_bytes(B, per)
+    if nb < 0:
+        raise ValueError(f"cfg_rescale needs >= 2 elements per sample (got {per}) and 1 <= B")
+    stats = torch.empty(nb, dtype=torch.uint8, device=ey.device)
+    out = torch.empty_like(ey)
+    L.check(L.lib().avd_cfg_rescale_f32(ec.data_ptr(), ey.data_ptr(), ph.data_ptr(), stats.data_ptr(), nb, out.data_ptr(), B, per,
+                                        _st(out)))
+    if return_scale:
+        off = nb - ((4 * B + 15) // 16) * 16           # the scale slot ends the scratch
+        return out, stats[off:off + 4 * B].view(torch.float32).clone()
+    return out
+
+
 def gaussian_noise(seed: int, sample_offset: int, t_now: Tensor, shape) -> Tensor:
     """The seeded normal stream of the DDIM eta > 0 noise (avd_gaussian_noise_f32; contract in include/avdiff_hip.h): a
     float32 tensor of ``shape`` = (B, ...) whose row b holds sample ``sample_offset + b``'s normals at timestep ``t_now[b]``,

@@ -143,6 +143,13 @@ class DenoiseEngine:
     q(t_prev), step(z)) with q the known latent forward-noised to t_prev along the known-noise stream of (guide_seed,
     sample_offset + b).  ``start_latent`` builds the trajectory's start for a ``strength``; ``clear_known`` returns to the plain
     step.  The known latent and the mask live in engine-owned buffers, so a captured graph replays guided steps.
+
+    ``guidance`` a number (today's scalar CFG) or B per-sample scales, ``guidance_rescale`` phi in [0, 1], a number or B values
+    (extension: per-sample guidance and CFG rescale, include/avdiff_hip.h, avd_cfg_control; diffusers' ``rescale_noise_cfg`` per
+    sample).  With either in use every step runs the controlled fused kernel — after a statistics pass over the eps when any phi is
+    set; a scalar guidance with phi = 0 is the plain step, bit for bit and kernel for kernel.  ``set_cfg`` changes the values in
+    engine-owned buffers (a captured graph follows them); switching between the plain and the controlled step starts a new graph
+    generation.
     """
 
     SOLVERS = ("ddim", "dpmpp_2m")
@@ -151,7 +158,7 @@ class DenoiseEngine:
                  tstep_dim: int, target: str, latent_shape: Tuple[int, ...], prompt_tokens: int, alpha_bar: torch.Tensor,
                  guidance: float, eta: float = 0.0, tube=(2, 4, 4), chunk=(4, 4), split_streams: Optional[bool] = None,
                  temb_mode: str = "concat", matmul: Optional[str] = None, attn: Optional[str] = None,
-                 noise_seed: Optional[int] = None, sample_offset: int = 0, solver: str = "ddim"):
+                 noise_seed: Optional[int] = None, sample_offset: int = 0, solver: str = "ddim", guidance_rescale=0.0):
         if target not in ("video", "audio"):
             raise ValueError("target must be 'video' or 'audio'")
         if eta < 0:
@@ -171,12 +178,19 @@ class DenoiseEngine:
         self.d = core.cfg.d_model
         self.tdim = self.d if temb_mode == "add" else int(tstep_dim)     # the trainer embeds at token width
         self.tube, self.chunk = tuple(tube), tuple(chunk)
-        self.guidance, self.eta = float(guidance), float(eta)
+        self.eta = float(eta)
         self.device = next(core.final_norm.parameters()).device
         if not self.device.type == "cuda":
             raise L.AvdError("DenoiseEngine needs its modules on a ROCm device (no CPU fallback)")
         self.latent_shape = tuple(int(s) for s in latent_shape)      # with batch dim
         B = self.latent_shape[0]
+        # CFG control (set_cfg): the values on the host, and the [B] device buffers + statistics scratch once a step needs them
+        self._g_vals, self._g_per_sample = Fn.cfg_values(guidance, B, "guidance"), not _scalar_like(guidance)
+        self._phi_vals = Fn.cfg_values(guidance_rescale, B, "guidance_rescale", 0.0, 1.0)
+        self.guidance = float(self._g_vals[0])
+        self._cfg_g = self._cfg_phi = self._cfg_stats = None
+        self._ctl: Optional[L.CfgControl] = None
+        self._cfg_sig = None          # what a captured graph holds of the control by value: its pointers
         self.noise_seed, self.sample_offset = noise_seed, int(sample_offset)
         self._key = None if noise_seed is None else Fn.noise_key(noise_seed, sample_offset)
         if self._key is None and sample_offset != 0:
@@ -239,6 +253,7 @@ class DenoiseEngine:
         self._guide: Optional[L.LatentGuide] = None
         self._guide_sig = None       # what a captured graph holds of the guide by value: pointers, stride, seed
         self._bind_weights()
+        self._apply_cfg()
 
     # ---- pointer tables.  They hold derived copies (norm-folded / split3 weights), so they are re-derived whenever a
     # parameter's (address, version) changes: load_state_dict, EMA copy_to, an optimiser step or .to(device) after the
@@ -405,6 +420,52 @@ class DenoiseEngine:
             self._stale_reason = "the latent guide's buffers, mask presence or seed changed (set_known / clear_known)"
         self._guide_sig = sig
 
+    # ---- CFG control: per-sample guidance scales and guidance rescale ----
+    def set_cfg(self, guidance=None, rescale=None) -> None:
+        """New CFG values: ``guidance`` a number (every sample) or B per-sample scales, ``rescale`` phi in [0, 1] (a number or B
+        values); None keeps the current one.  Both are checked before anything changes.  They are copied into engine-owned buffers, so
+        a captured graph replays with the new values — unless the step switches between the plain one (a scalar guidance, phi = 0
+        everywhere) and the controlled one, phi goes from all zero to not (the statistics pass is launched only when some phi is set)
+        or back, or a new scalar reaches the plain step (held by value): that starts a new generation."""
+        B = self.embed.B
+        g = None if guidance is None else Fn.cfg_values(guidance, B, "guidance")
+        phi = None if rescale is None else Fn.cfg_values(rescale, B, "guidance_rescale", 0.0, 1.0)
+        if g is not None:
+            self._g_vals, self._g_per_sample = g, not _scalar_like(guidance)
+        if phi is not None:
+            self._phi_vals = phi
+        self._apply_cfg()
+
+    def _apply_cfg(self) -> None:
+        rescale = bool((self._phi_vals != 0).any())        # phi = 0 everywhere: no statistics pass (rescale pointer NULL)
+        reason = None
+        if self._g_per_sample or rescale:
+            if self._cfg_g is None:
+                B = self.embed.B
+                nb = L.lib().avd_cfg_stats_bytes(B, int(np.prod(self.latent_shape[1:])))
+                if nb < 0:
+                    raise ValueError(f"the CFG control needs >= 2 latent elements per sample and B <= 65535 (latent {self.latent_shape})")
+                self._cfg_g = torch.empty(B, dtype=torch.float32, device=self.device)
+                self._cfg_phi = torch.empty(B, dtype=torch.float32, device=self.device)
+                self._cfg_stats = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            self._cfg_g.copy_(self._g_vals)
+            self._cfg_phi.copy_(self._phi_vals)
+            self._ctl = L.CfgControl(self._cfg_g.data_ptr(), self._cfg_phi.data_ptr() if rescale else None, self._cfg_stats.data_ptr(),
+                                     self._cfg_stats.numel())
+            sig = (self._ctl.guidance, self._ctl.rescale, self._ctl.stats)
+        else:
+            self._ctl, sig = None, None
+            g = float(self._g_vals[0])
+            if g != self.guidance:
+                self.guidance = self.desc.guidance = g
+                reason = "the scalar guidance of the plain step changed (set_cfg)"
+        if sig != self._cfg_sig:
+            reason = "the CFG control was switched on or off, or its rescale (statistics pass) was (set_cfg)"
+        self._cfg_sig = sig
+        if reason:
+            self._generation += 1
+            self._stale_reason = reason
+
     def start_latent(self, z_init: torch.Tensor, sched: torch.Tensor, strength: float = 1.0):
         """(z_start, sched_k): the start of a guided trajectory at ``strength`` (schedule_utils.truncate_schedule: k of the n steps
         of ``sched`` are run, from t_s = sched_k[0]).  k = n (strength 1): blend(mask, q(t_s), z_init) — the masked region starts on
@@ -442,7 +503,7 @@ class DenoiseEngine:
         if not torch.cuda.is_current_stream_capturing():
             self._sync_weights()
         out = torch.empty_like(z) if out is None else out
-        if self._guide is not None:
+        if self._guide is not None or self._ctl is not None:
             return self._step_guided(z, tn, tp, noise, out, t_last)
         if self.solver == "dpmpp_2m":
             if noise is not None:
@@ -473,10 +534,11 @@ class DenoiseEngine:
         return out
 
     def _step_guided(self, z, tn, tp, noise, out, t_last) -> torch.Tensor:
+        """the step with a latent guide and / or a CFG control"""
         if noise is not None:
-            raise ValueError("a guided step draws its noise from noise_seed: it takes no `noise`")
+            raise ValueError("a guided or CFG-controlled step draws its noise from noise_seed: it takes no `noise`")
         if self.eta > 0 and self._key is None:
-            raise ValueError("with a known latent, eta > 0 needs noise_seed (unseeded noise is not supported with a guide)")
+            raise ValueError("with a known latent or a CFG control, eta > 0 needs noise_seed (unseeded noise is not supported there)")
         tl = h = None
         if self.solver == "dpmpp_2m":
             h = self.x0_hist
@@ -486,6 +548,12 @@ class DenoiseEngine:
             tl = self._no_hist if t_last is None else L.dev_i64(t_last, self.device)
         elif t_last is not None:
             raise ValueError("t_last is the multistep solver's history: this engine runs solver 'ddim'")
+        if self._ctl is not None:
+            L.check(L.lib().avd_denoise_step_cfg_f32(C.byref(self.desc), C.byref(self._ctl), None if self._guide is None else C.byref(self._guide),
+                                                     None if self._key is None else C.byref(self._key), L.ptr(tl), L.ptr(h), z.data_ptr(),
+                                                     self.Xp.data_ptr(), tn.data_ptr(), tp.data_ptr(), out.data_ptr(),
+                                                     self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device)))
+            return out
         L.check(L.lib().avd_denoise_step_guided_f32(C.byref(self.desc), C.byref(self._guide),
                                                     None if self._key is None else C.byref(self._key), L.ptr(tl), L.ptr(h),
                                                     z.data_ptr(), self.Xp.data_ptr(), tn.data_ptr(), tp.data_ptr(), out.data_ptr(),
@@ -570,6 +638,11 @@ class DenoiseEngine:
         return za
 
 
+def _scalar_like(v) -> bool:
+    """a single number (not a sequence): the same guidance for every sample, the plain step's scalar"""
+    return isinstance(v, (int, float, np.generic)) or (isinstance(v, (torch.Tensor, np.ndarray)) and v.ndim == 0)
+
+
 def frame_mask(latent_shape, lo: int, hi: int) -> torch.Tensor:
     """A latent guide mask (DenoiseEngine.set_known, sample_one_direction ``mask``): float32 ones on latent frames [lo, hi) and zeros
     elsewhere — the T axis of a video latent ([C,T,H,W] or [B,C,T,H,W]), the F axis of an audio latent ([Ca,F] or [B,Ca,F]).
@@ -617,7 +690,9 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
     encoded with the same ``vid_vae`` / ``aud_codec``.  ``strength`` < 1 runs the last part of the schedule from the encoded clip
     noised to that point (SDEdit, schedule_utils.truncate_schedule; 0 returns the decoded clip).  ``mask`` (latent-shaped for one
     sample, e.g. ``frame_mask``; 1 = keep) holds the trajectory to the clip there at every step (DenoiseEngine.set_known); without
-    a mask the whole latent is free.  ``guide_seed`` keys the clip's forward noise (default ``noise_seed``, else 0)."""
+    a mask the whole latent is free.  ``guide_seed`` keys the clip's forward noise (default ``noise_seed``, else 0).
+    ``sampling.guidance_rescale`` (extension; a per-modality dict like ``guidance_scale``, default 0): CFG rescale phi of the target
+    (DenoiseEngine ``guidance_rescale``); 0 runs the plain step."""
     # argument checks that need no device
     strength = float(strength)
     if not 0.0 <= strength <= 1.0:
@@ -673,9 +748,10 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
         raise ValueError("prompt_modality must be 'video' or 'audio'")
 
     abar, sched = table(target)
+    rescale = float(scfg.get("guidance_rescale", {}).get(target, 0.0))
     eng = DenoiseEngine(adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, target=target,
                         latent_shape=tuple(z.shape), prompt_tokens=n_prompt, alpha_bar=abar, guidance=guide, eta=eta,
-                        tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed, solver=solver)
+                        tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed, solver=solver, guidance_rescale=rescale)
     eng.set_prompt(z_p.float())
     if init is not None:
         if target == "video":

@@ -147,6 +147,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     H, W = int(cfg["video"]["size"][0]), int(cfg["video"]["size"][1])
     eta = float(cfg["sampling"].get("ddim_eta", 0.0))
     solver = str(cfg["sampling"].get("solver", "ddim"))       # "ddim" | "dpmpp_2m" (DenoiseEngine ``solver``)
+    rescale_cfg = cfg["sampling"].get("guidance_rescale", {})  # per modality, like guidance_scale (DenoiseEngine ``guidance_rescale``)
 
     import torch.distributed as tdist
     world = tdist.get_world_size() if (shard and tdist.is_initialized()) else 1
@@ -219,7 +220,8 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
             eng = DenoiseEngine(adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, target=target,
                                 latent_shape=(hi - lo, *lat), prompt_tokens=n_prompt, alpha_bar=abar, guidance=guide, eta=eta,
                                 tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed,
-                                sample_offset=lo if noise_seed is not None else 0, solver=solver)
+                                sample_offset=lo if noise_seed is not None else 0, solver=solver,
+                                guidance_rescale=float(rescale_cfg.get(target, 0.0)))
             eng.set_prompt(zp_part[lo - lo0:hi - lo0].to(device).float().contiguous())
             outs.append(eng.run(z0[lo:hi].to(device).contiguous(), sched))
         if not outs:

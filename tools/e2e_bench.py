@@ -30,13 +30,16 @@ ap.add_argument("--noise", choices=("both", "seeded", "unseeded"), default="both
                 help="with --eta: the eta > 0 noise source(s) to time — seeded (the in-kernel stream of DenoiseEngine(noise_seed=...)) "
                      "and / or unseeded (torch.randn_like per step)")
 ap.add_argument("--matmul", default="bf16x3", help="with --eta: matrix-pipe mode (default: bench.py's headline mode)")
-ap.add_argument("--reps", type=int, default=5, help="with --eta / --strength / --keep-frames: interleaved rounds; the median per variant "
+ap.add_argument("--reps", type=int, default=5, help="with --eta / --strength / --keep-frames / --guidance-rescale: interleaved rounds; the median per variant "
                                                    "is printed")
 ap.add_argument("--strength", type=float, default=None,
                 help="time only the A->V sampler loop with a latent guide (DenoiseEngine.set_known / start_latent) at this SDEdit strength "
                      "beside the unguided loop, interleaved in one process")
 ap.add_argument("--keep-frames", type=int, default=None,
                 help="with or without --strength: hold the first K latent frames to the known clip (frame_mask) at every step")
+ap.add_argument("--guidance-rescale", type=float, default=None,
+                help="time only the sampler loop, both directions, plain CFG against DenoiseEngine(guidance_rescale=PHI) (statistics "
+                     "pass + controlled fused step), interleaved in one process")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 B, S, size = args.batch, args.sampler_steps, args.size
@@ -84,6 +87,36 @@ if args.eta is not None:
             graph = (eng.eta == 0 or eng.noise_seed is not None) and rows < eng.GRAPH_BELOW_ROWS
             print(f"[{args.matmul}] {direction} B={B} {size}x{size} {name:18s}: {med:7.3f} ms/step (min {min(times[name]):7.3f}, "
                   f"{args.reps} rounds of {S} steps, {'graph' if graph else 'eager'})  {100 * (med / base - 1):+6.2f} % vs eta=0", flush=True)
+    sys.exit(0)
+
+if args.guidance_rescale is not None:
+    # CFG rescale cost: the plain engine against one with guidance_rescale = PHI, interleaved; ms/step medians
+    import statistics
+    zv_prompt = torch.randn(B, 8, 12, size // 8, size // 8, generator=torch.Generator().manual_seed(3)).to(dev)
+    variants = (("plain", 0.0), (f"rescale={args.guidance_rescale:g}", args.guidance_rescale))
+    for target, z_init, prompt, n_prompt in (("video", z0, za, 37), ("audio", za, zv_prompt, (12 // 2) * (size // 8 // 4) ** 2)):
+        engs = []
+        for name, phi in variants:
+            eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=tdim, target=target,
+                                  latent_shape=tuple(z_init.shape), prompt_tokens=n_prompt, alpha_bar=abar, guidance=3.5,
+                                  guidance_rescale=phi, matmul=args.matmul, solver=args.solver)
+            eng.set_prompt(prompt)
+            eng.run(z_init, sched[:4])                  # warm-up
+            engs.append(eng)
+        times = {name: [] for name, _ in variants}
+        for _ in range(args.reps):
+            for (name, _), eng in zip(variants, engs):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                eng.run(z_init, sched)
+                torch.cuda.synchronize()
+                times[name].append(1e3 * (time.perf_counter() - t0) / S)
+        base = statistics.median(times["plain"])
+        direction = "A->V" if target == "video" else "V->A"
+        for name, _ in variants:
+            med = statistics.median(times[name])
+            print(f"[{args.matmul}] {direction} {args.solver} B={B} {size}x{size} {name:14s}: {med:7.3f} ms/step (min {min(times[name]):7.3f}, "
+                  f"{args.reps} rounds of {S} steps)  {100 * (med / base - 1):+6.2f} % vs plain", flush=True)
     sys.exit(0)
 
 if args.strength is not None or args.keep_frames is not None:
