@@ -262,6 +262,35 @@ int avd_cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int6
                                    float guidance, float eta, const float* noise, float* z_out,
                                    int B, int Ca, int F, int len, int stride, avd_stream_t stream);
 
+/* ---- guidance interval: cond-only steps (Kynkaanniemi et al. 2024, guidance in a limited interval; a public contract).
+ * A sampler that applies classifier-free guidance on part of the schedule only takes two kinds of step.  A CFG step is every entry
+ * above and avd_denoise_step_*: two branches, eps = null + g (cond - null).  A cond-only step is the single-branch form:
+ *   1. eps = eps_cond exactly — the conditional prediction's bits, not null + 1 (cond - null); the null half is neither assembled, nor
+ *      run through the core and head, nor read;
+ *   2. z_out = update(z, eps): DDIM at eta = 0, DDIM at eta > 0 on explicit or seeded noise, or DPM-Solver++(2M), each the expression of
+ *      its CFG twin; then the latent guide's blend (avd_latent_guide) when a guide is passed;
+ *   3. per-sample guidance scales and guidance rescale (avd_cfg_control) do not apply: with y = c the rescale is the identity, and no
+ *      statistics pass runs;
+ *   4. the seeded noise is keyed as in a CFG step (sample, t_now, element): a trajectory's noise does not depend on which steps are
+ *      cond-only;
+ *   5. DPM-Solver++(2M): x0_hist is read and written as by a CFG step, so the history carries across a boundary between the two kinds
+ *      and the solver does not restart first order there.
+ * Which steps are cond-only is the caller's decision (DenoiseEngine: t_now outside [t_lo, t_hi]).
+ *
+ * The single-branch fused updates alone: eps: [B,Nv,C*t*h*w] resp. [B,Na,Ca*len], the conditional prediction.  Optional, NULL when
+ * unused: key (with eta > 0: seeded noise, `noise` is not read), t_last + x0_hist (both or neither: the DPM-Solver++(2M) update, eta
+ * == 0, x0_hist must not overlap z or z_out), guide (eta > 0 then needs key).  eta > 0 needs noise or key.  Bit-identical to
+ * avd_tube_unpatch_f32 / avd_audio_untokens_f32 (no window) followed by avd_ddim_step_f32 / avd_dpmpp_2m_step_f32 and
+ * avd_latent_guide_f32. */
+int avd_eps_unpatch_ddim_f32(const float* eps, const float* z, const int64_t* t_now, const int64_t* t_prev,
+                             const float* alpha_bar, int T_train, float eta, const float* noise, float* z_out,
+                             int B, int C, int T, int H, int W, int t, int h, int w, const avd_noise_key* key,
+                             const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, avd_stream_t stream);
+int avd_eps_untoken_ddim_audio_f32(const float* eps, const float* z, const int64_t* t_now, const int64_t* t_prev,
+                                   const float* alpha_bar, int T_train, float eta, const float* noise, float* z_out,
+                                   int B, int Ca, int F, int len, int stride, const avd_noise_key* key,
+                                   const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, avd_stream_t stream);
+
 /* ---- a1+a3+a4+a5 fused front end — sample_clip.py:363-371,377 (A->V) / :322-333,338 (V->A).
  * Builds the CFG-stacked sequence X2[2B, Nt+Np, d] in one pass:
  *   target rows : [ adapter(tokens(z_target)) | temb(t_now[b]) ]   (same in both halves)
@@ -287,6 +316,13 @@ int64_t avd_embed_workspace_floats(const avd_embed_desc* desc);
 int avd_embed_cfg_pair_f32(const avd_embed_desc* desc, const float* z_target, const float* Wt, const float* bt,
                            const int64_t* t_now, const float* Xp, float* tok_ws, float* X2,
                            avd_stream_t stream);
+/* The single-branch front end of a cond-only step: X1[B, Nt+Np, d], bit-identical to the cond half of avd_embed_cfg_pair_f32's X2 on
+ * the same inputs; B (Nt+Np) rows are handled, no null rows are written.  ss: NULL, or [B (Nt+Np)] that receives each finished row's
+ * sum of squares in concat mode (the table the core's first folded RMSNorm reads; the bits the two-branch front end leaves for its
+ * cond rows inside avd_denoise_step_f32); not written with temb_add. */
+int avd_embed_cond_f32(const avd_embed_desc* desc, const float* z_target, const float* Wt, const float* bt,
+                       const int64_t* t_now, const float* Xp, float* tok_ws, float* X1, float* ss,
+                       avd_stream_t stream);
 
 /* ---- composites: whole modules / the whole step as one host call (stateless; weights by pointer table).
  * These enqueue exactly the kernels above in order; they exist to keep the per-step host cost at one FFI
@@ -502,6 +538,18 @@ int avd_denoise_step_cfg_f32(const avd_step_desc* s, const avd_cfg_control* ctl,
                              const avd_noise_key* key, const int64_t* t_last, float* x0_hist, const float* z, const float* Xp,
                              const int64_t* t_now, const int64_t* t_prev, float* z_out,
                              void* workspace, int64_t workspace_bytes, avd_stream_t stream);
+/* The whole cond-only step (see "guidance interval" above): the single-branch front end, the core and the head on B (Nt+Np) resp. B Nt
+ * rows — their kernels chosen for those row counts — and the single-branch fused update.  One kernel chain on `stream`: no second
+ * stream, no fork / join, whatever s->split_streams says; s->guidance is not read.  The workspace is the CFG step's
+ * (avd_step_workspace_bytes): the cond half of each region is used, and eps [B,Nt,D] lands where the cond half of eps2 does (the first
+ * B Nt D floats of the trailing eps region).  g, key, t_last and x0_hist are optional and follow avd_denoise_step_guided_f32's rules
+ * (t_last and x0_hist go together and need eta == 0; x0_hist must not alias z or z_out; known / mask must not overlap z_out or
+ * x0_hist).  eta > 0 needs key or, without a guide, an explicit `noise` [B, per_sample]; noise with a key or with a guide is refused.
+ * Graph-capturable as its twins. */
+int avd_denoise_step_cond_f32(const avd_step_desc* s, const avd_latent_guide* g, const avd_noise_key* key,
+                              const int64_t* t_last, float* x0_hist, const float* z, const float* Xp,
+                              const int64_t* t_now, const int64_t* t_prev, const float* noise, float* z_out,
+                              void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 
 /* ---- a9 / next-1: VideoVAE.decode — avdiff/models/encoders/vae_video3d.py:195-214 (decode), :79-84
  * (_conv_block_3d: Conv3d 3x3x3 pad 1 -> GELU(erf) -> GroupNorm(min(8,C), eps 1e-5, affine)), :108-119.

@@ -149,6 +149,12 @@ SIGNATURES = {
     "avd_cfg_rescale_f32": (_I, [_P, _P, _P, _P, _L, _P, _I, _L, _P]),
     "avd_denoise_step_cfg_f32": (_I, [C.POINTER(StepDesc), C.POINTER(CfgControl), C.POINTER(LatentGuide), C.POINTER(NoiseKey), _P, _P, _P,
                                       _P, _P, _P, _P, _P, _L, _P]),
+    "avd_eps_unpatch_ddim_f32": (_I, [_P, _P, _P, _P, _P, _I, _F, _P, _P] + [_I] * 8 + [C.POINTER(NoiseKey), _P, _P, C.POINTER(LatentGuide), _P]),
+    "avd_eps_untoken_ddim_audio_f32": (_I, [_P, _P, _P, _P, _P, _I, _F, _P, _P] + [_I] * 5 + [C.POINTER(NoiseKey), _P, _P,
+                                                                                               C.POINTER(LatentGuide), _P]),
+    "avd_embed_cond_f32": (_I, [C.POINTER(EmbedDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "avd_denoise_step_cond_f32": (_I, [C.POINTER(StepDesc), C.POINTER(LatentGuide), C.POINTER(NoiseKey), _P, _P, _P, _P, _P, _P, _P, _P,
+                                       _P, _L, _P]),
     "avd_split3_bytes": (_L, [_L, _I]),
     "avd_split3_f32": (_I, [_P, _P, _L, _I, _P]),
     "avd_rmsnorm_split3_f32": (_I, [_P, _P, _P, _L, _I, _F, _P]),

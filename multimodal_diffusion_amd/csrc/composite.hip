@@ -86,6 +86,17 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st,
                                const avd_noise_key* key = nullptr, const int64_t* t_last = nullptr, float* x0_hist = nullptr,
                                const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr);
+int assemble_cond_f32(float* X1, const float* temb, const float* Xp, int B, int N, int d, int tdim, int Nt, int Np, int target_first,
+                      hipStream_t st);
+int assemble_rows_cond_f32(float* X1, const int64_t* t_now, const float* freqs, const float* Xp, float* ss, int B, int N, int d,
+                           int tdim, int Nt, int Np, int target_first, float max_period, hipStream_t st);
+int eps_unpatch_ddim_f32(const float* eps1, const float* z, const int64_t* t_now, const int64_t* t_prev, const float* abar, int T_train,
+                         float eta, const float* noise, float* z_out, int B, int C, int T, int H, int W, int t, int h, int w,
+                         hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide);
+int eps_untoken_ddim_audio_f32(const float* eps1, const float* z, const int64_t* t_now, const int64_t* t_prev, const float* abar,
+                               int T_train, float eta, const float* noise, float* z_out, int B, int Ca, int F, int len, int stride,
+                               hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist,
+                               const avd_latent_guide* guide);
 int check_latent_guide(const avd_latent_guide* g, int B, int64_t per, const float* out, const float* x0_hist);
 int check_cfg_control(const avd_cfg_control* ctl, int B, int64_t per, const float* out, const float* x0_hist);
 
@@ -540,8 +551,11 @@ static int64_t embed_ws_floats(const avd_embed_desc* e) {
 }
 
 // ss_out (optional, concat mode): per-row sums of squares of the finished X2, [2B*N] — spares MMDiT's first folded norm its pass
+// cond_only: the single-branch front end of a cond-only step — X2 is [B, N, d] (ss_out [B*N]), the cond half alone, bit-identical to
+// the cond half of the pair; the adapter GEMM is the same launch, only the assembly pass is the B*N-row form
 static int embed_cfg_pair(const avd_embed_desc* e, const float* z, const float* Wt, const float* bt,
-                          const int64_t* t_now, const float* Xp, float* tok_ws, float* X2, hipStream_t st, float* ss_out = nullptr) {
+                          const int64_t* t_now, const float* Xp, float* tok_ws, float* X2, hipStream_t st, float* ss_out = nullptr,
+                          bool cond_only = false) {
     if (int rc = check_embed(e)) return rc;
     AVD_REQUIRE(z && Wt && t_now && tok_ws && X2 && (e->Np == 0 || Xp), AVD_EINVAL, "embed: null pointer");
     const int B = e->B, d = e->d, N = e->Nt + e->Np, D = embed_tok_dim(e);
@@ -565,6 +579,7 @@ static int embed_cfg_pair(const avd_embed_desc* e, const float* z, const float* 
         // the GEMM's residual operand through a row map with zero row stride (one segment of Nt rows per sample).
         const RowMap rm{0, e->Nt, (int64_t)e->tdim};
         if (int rc = gemm_f32(tok, RowMap{D, 0, 0}, Wt, bt, temb, rm, c0, cm, (int64_t)B * e->Nt, d, D, AVD_ACT_NONE, st)) return rc;
+        if (cond_only) return assemble_cond_f32(X2, temb, Xp, B, N, d, 0, e->Nt, e->Np, e->target_first, st);
         return assemble_f32(X2, temb, Xp, B, N, d, 0, e->Nt, e->Np, e->target_first, st);
     }
     if (fuse_patch) {
@@ -574,6 +589,8 @@ static int embed_cfg_pair(const avd_embed_desc* e, const float* z, const float* 
         if (int rc = gemm_f32(tok, RowMap{D, 0, 0}, Wt, bt, nullptr, cm, c0, cm, (int64_t)B * e->Nt, d - e->tdim, D, AVD_ACT_NONE, st)) return rc;
     }
     // timestep columns, null-half copies, prompt rows and the rows' sums of squares in one pass
+    if (cond_only)
+        return assemble_rows_cond_f32(X2, t_now, e->temb_freqs, Xp, ss_out, B, N, d, e->tdim, e->Nt, e->Np, e->target_first, 10000.f, st);
     return assemble_rows_f32(X2, t_now, e->temb_freqs, Xp, ss_out, B, N, d, e->tdim, e->Nt, e->Np, e->target_first, 10000.f, st);
 }
 
@@ -724,6 +741,11 @@ extern "C" int avd_embed_cfg_pair_f32(const avd_embed_desc* desc, const float* z
     return embed_cfg_pair(desc, z_target, Wt, bt, t_now, Xp, tok_ws, X2, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int avd_embed_cond_f32(const avd_embed_desc* desc, const float* z_target, const float* Wt, const float* bt,
+                                  const int64_t* t_now, const float* Xp, float* tok_ws, float* X1, float* ss, avd_stream_t stream) {
+    return embed_cfg_pair(desc, z_target, Wt, bt, t_now, Xp, tok_ws, X1, static_cast<hipStream_t>(stream), ss, true);
+}
+
 extern "C" int64_t avd_step_workspace_bytes(const avd_step_desc* s) {
     StepPlan p;
     if (plan_step(s, p)) return -1;
@@ -793,6 +815,65 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
                                     e.B, e.C, e.T, e.H, e.W, e.p0, e.p1, e.p2, st, key, t_last, x0_hist, guide, ctl);
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, s->alpha_bar, s->T_train, s->guidance, s->eta, noise, z_out,
                                       e.B, e.C, e.T, e.p0, e.p1, st, key, t_last, x0_hist, guide, ctl);
+}
+
+// The cond-only step of a guidance interval: the conditional branch alone, in the cond half of every workspace region of the CFG step's
+// plan (eps lands where the cond half of eps2 does).  One kernel chain on the caller's stream whatever s->split_streams says — there is
+// no second branch to overlap — and core_forward / head_forward choose their kernels for the B * N rows that run (t_step_rows stays 0).
+static int denoise_step_cond(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp, const int64_t* t_now,
+                             const int64_t* t_prev, const float* noise, float* z_out, void* workspace, int64_t workspace_bytes,
+                             avd_stream_t stream, const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide) {
+    StepPlan p;
+    if (int rc = plan_step(s, p)) return rc;
+    AVD_REQUIRE(z && z_out && t_now && t_prev && s->alpha_bar && s->adapt_w, AVD_EINVAL, "step: null pointer");
+    AVD_REQUIRE(z != z_out, AVD_EINVAL, "step: z_out must not alias z");
+    AVD_REQUIRE(workspace && workspace_bytes >= p.total, AVD_EWORKSPACE, "step: workspace %lld < %lld bytes",
+                (long long)workspace_bytes, (long long)p.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const avd_embed_desc& e = s->embed;
+    char* w = static_cast<char*>(workspace);
+    float* X1 = reinterpret_cast<float*>(w);
+    float* tok = reinterpret_cast<float*>(w + p.x2);
+    void* core_ws = w + p.x2 + p.tok;
+    void* head_ws = w + p.x2 + p.tok + p.core;
+    float* ssx = reinterpret_cast<float*>(w + p.x2 + p.tok + p.core + p.head);
+    float* eps1 = reinterpret_cast<float*>(w + p.x2 + p.tok + p.core + p.head + p.ss);
+    const bool have_ss = !e.temb_add;
+
+    if (int rc = embed_cfg_pair(&e, z, s->adapt_w, s->adapt_b, t_now, Xp, tok, X1, st, ssx, true)) return rc;
+    const int row0 = e.target_first ? 0 : e.Np;
+    const RowMap hm{e.d, e.Nt, (int64_t)p.N * e.d};
+    if (int rc = core_forward(s->core, X1, X1, e.B, p.N, row0, e.Nt, nullptr, core_ws, p.core / 2, st, have_ss ? ssx : nullptr)) return rc;
+    if (int rc = head_forward(s->head, X1 + (int64_t)row0 * e.d, hm, p.rows / 2, eps1, head_ws, p.head / 2, st)) return rc;
+    if (e.target_kind == 0)
+        return eps_unpatch_ddim_f32(eps1, z, t_now, t_prev, s->alpha_bar, s->T_train, s->eta, noise, z_out, e.B, e.C, e.T, e.H, e.W, e.p0,
+                                    e.p1, e.p2, st, key, t_last, x0_hist, guide);
+    return eps_untoken_ddim_audio_f32(eps1, z, t_now, t_prev, s->alpha_bar, s->T_train, s->eta, noise, z_out, e.B, e.C, e.T, e.p0, e.p1, st,
+                                      key, t_last, x0_hist, guide);
+}
+
+extern "C" int avd_denoise_step_cond_f32(const avd_step_desc* s, const avd_latent_guide* g, const avd_noise_key* key,
+                                         const int64_t* t_last, float* x0_hist, const float* z, const float* Xp, const int64_t* t_now,
+                                         const int64_t* t_prev, const float* noise, float* z_out, void* workspace,
+                                         int64_t workspace_bytes, avd_stream_t stream) {
+    AVD_REQUIRE(s, AVD_EINVAL, "step: null descriptor");
+    // checked here as well as in the fused kernel's launcher: before the model runs, and for both targets
+    const int64_t n = (int64_t)s->embed.B * s->embed.C * s->embed.T * s->embed.H * s->embed.W;
+    if (g)
+        if (int rc = check_latent_guide(g, s->embed.B, s->embed.B > 0 ? n / s->embed.B : 0, z_out, x0_hist)) return rc;
+    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "denoise_step_cond: t_last and x0_hist go together (the DPM-Solver++(2M) update)");
+    if (x0_hist) {
+        AVD_REQUIRE(s->eta == 0.f, AVD_EINVAL, "denoise_step_cond: DPM-Solver++(2M) needs eta == 0");
+        AVD_REQUIRE(!(z && x0_hist < z + n && z < x0_hist + n) && !(z_out && x0_hist < z_out + n && z_out < x0_hist + n), AVD_EINVAL,
+                    "denoise_step_cond: x0_hist must not alias z or z_out");
+    }
+    AVD_REQUIRE(!(noise && key), AVD_EINVAL, "denoise_step_cond: pass a noise tensor or a noise key, not both");
+    AVD_REQUIRE(!(noise && g), AVD_EINVAL, "denoise_step_cond: unseeded noise is not supported with a latent guide (pass a noise key)");
+    AVD_REQUIRE(s->eta == 0.f || key || noise, AVD_EINVAL, "denoise_step_cond: eta > 0 needs a noise key%s", g ? "" : " or a noise tensor");
+    if (key)
+        AVD_REQUIRE(key->sample_offset >= 0 && key->sample_offset + (int64_t)s->embed.B <= ((int64_t)1 << 32), AVD_EINVAL,
+                    "denoise_step_cond: sample_offset %lld + B %d must lie in [0, 2^32]", (long long)key->sample_offset, s->embed.B);
+    return denoise_step_cond(s, key, z, Xp, t_now, t_prev, noise, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, g);
 }
 
 extern "C" int avd_denoise_step_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_now,

@@ -284,6 +284,10 @@ struct DpmState {
     float* x0_hist;          // [B, per] in the latent's natural layout: read (second-order steps), then overwritten with x0_s
 };
 // the trailing pack holds at most one solver state (NoiseKey or DpmState), then optionally a GuideState (the latent guide below)
+// A CondOnly tag ending the pack selects the single-branch form of the fused kernels (a cond-only step of a guidance interval): eps2 is
+// then eps1 = [B, Nt, D], the conditional prediction alone; the null rows are not loaded, nothing is combined, `guidance` and `B` are
+// not read.  It excludes a CfgState (per-sample guidance and rescale act on the combine: with y = c the rescale is the identity).
+struct CondOnly {};
 template <class T, class... X> struct PackHas { static constexpr bool value = (std::is_same<T, X>::value || ...); };
 template <class T, class A, class... R> __device__ __forceinline__ T pack_get(const A& a, const R&... r) {
     if constexpr (std::is_same<T, A>::value) return a;
@@ -560,9 +564,10 @@ __device__ __forceinline__ float cfg_rescale(float e, float phi, float s) {
     return phi == 0.f ? e : (phi == 1.f ? e * s : phi * (e * s) + (1.0f - phi) * e);
 }
 // the eps a fused kernel steps on: today's combine (the instantiations without a CfgState), or r(combine with g_b)
-template <bool CTL>
+template <bool CTL, bool COND = false>
 __device__ __forceinline__ float cfg_eps(float ec, float en, float guidance, const CfgCoef& cc) {
-    if constexpr (CTL) return cfg_rescale(cfg_combine(ec, en, cc.g), cc.phi, cc.s);
+    if constexpr (COND) return ec;      // the single-branch form: eps = eps_cond exactly
+    else if constexpr (CTL) return cfg_rescale(cfg_combine(ec, en, cc.g), cc.phi, cc.s);
     else return cfg_combine(ec, en, guidance);
 }
 
@@ -758,9 +763,10 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const int64_t* __restrict__ t_prev, const float* __restrict__ abar, int T_train, float guidance, float eta,
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int64_t total4, Key... nk) {
     constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
-    constexpr bool CTL = PackHas<CfgState, Key...>::value;
-    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) + (CTL ? 1 : 0) && !(SEEDED && DPM),
-                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState");
+    constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
+    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) + (CTL ? 1 : 0) + (COND ? 1 : 0) &&
+                      !(SEEDED && DPM) && !(CTL && COND),
+                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState or CondOnly");
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total4) return;
     const int64_t per4 = g.per >> 2;
@@ -769,14 +775,15 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const int64_t lat = (int64_t)b * g.per + e4 * 4;
     const int64_t toff = tube_tok_off(g, e4);
     const f32x4 ec = *reinterpret_cast<const f32x4*>(eps2 + (int64_t)b * g.per + toff);
-    const f32x4 en = *reinterpret_cast<const f32x4*>(eps2 + ((int64_t)B + b) * g.per + toff);
+    [[maybe_unused]] f32x4 en = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (!COND) en = *reinterpret_cast<const f32x4*>(eps2 + ((int64_t)B + b) * g.per + toff);
     const f32x4 x = *reinterpret_cast<const f32x4*>(z + lat);
     [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
     if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
     f32x4 zn = {0.f, 0.f, 0.f, 0.f};
     if constexpr (SEEDED) {
         NoiseKey k;      // a one-item pack is copied as before the guide existed: through pack_get its argument loads reorder
-        if constexpr (GUIDED || CTL) k = pack_get<NoiseKey>(nk...);
+        if constexpr (GUIDED || CTL || COND) k = pack_get<NoiseKey>(nk...);
         else k = NoiseKey(nk...);
         zn = philox_normal4(k, (uint32_t)e4, k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
     } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
@@ -789,14 +796,14 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
         if (d.c_1 != 0.f) hist = *reinterpret_cast<const f32x4*>(ds.x0_hist + lat);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            x0[k] = ddim_x0(c, x[k], cfg_eps<CTL>(ec[k], en[k], guidance, cc));
+            x0[k] = ddim_x0(c, x[k], cfg_eps<CTL, COND>(ec[k], en[k], guidance, cc));
             o[k] = dpm_apply(d, x[k], x0[k], hist[k]);
         }
         *reinterpret_cast<f32x4*>(ds.x0_hist + lat) = x0;
     } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float e = cfg_eps<CTL>(ec[k], en[k], guidance, cc);
+            const float e = cfg_eps<CTL, COND>(ec[k], en[k], guidance, cc);
             o[k] = ddim_apply(c, x[k], e, zn[k]);
         }
     }
@@ -816,23 +823,26 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     const int64_t* __restrict__ t_prev, const float* __restrict__ abar, int T_train, float guidance, float eta,
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int groups_per_sample, Key... nk) {
     constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
-    constexpr bool CTL = PackHas<CfgState, Key...>::value;
-    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) + (CTL ? 1 : 0) && !(SEEDED && DPM),
-                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState");
+    constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
+    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) + (CTL ? 1 : 0) + (COND ? 1 : 0) &&
+                      !(SEEDED && DPM) && !(CTL && COND),
+                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState or CondOnly");
     extern __shared__ __attribute__((aligned(16))) float ebuf[];       // [GT][D + 4]: the pad keeps the transposed 16-byte reads off one bank group
     const int LD = g.D + 4;
     const int b = blockIdx.x / groups_per_sample, grp = blockIdx.x % groups_per_sample;
     const int n0 = grp * GT;                                            // first token of the group (GT divides W / w: one (t', h') row)
     const float* tc = eps2 + ((int64_t)b * (g.per / g.D) + n0) * g.D;
-    const float* tn = eps2 + (((int64_t)B + b) * (g.per / g.D) + n0) * g.D;
+    [[maybe_unused]] const float* tn = eps2 + (((int64_t)B + b) * (g.per / g.D) + n0) * g.D;
     const int nf4 = GT * g.D / 4;
     [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
     if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
     for (int i = threadIdx.x; i < nf4; i += 256) {
-        const f32x4 ec = *reinterpret_cast<const f32x4*>(tc + (int64_t)i * 4), en = *reinterpret_cast<const f32x4*>(tn + (int64_t)i * 4);
+        const f32x4 ec = *reinterpret_cast<const f32x4*>(tc + (int64_t)i * 4);
+        [[maybe_unused]] f32x4 en = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (!COND) en = *reinterpret_cast<const f32x4*>(tn + (int64_t)i * 4);
         f32x4 e;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) e[k] = cfg_eps<CTL>(ec[k], en[k], guidance, cc);
+        for (int k = 0; k < 4; ++k) e[k] = cfg_eps<CTL, COND>(ec[k], en[k], guidance, cc);
         const int tok = (i * 4) / g.D, k0 = (i * 4) % g.D;
         *reinterpret_cast<f32x4*>(ebuf + tok * LD + k0) = e;
     }
@@ -868,7 +878,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
             f32x4 zn = {0.f, 0.f, 0.f, 0.f};
             if constexpr (SEEDED) {
                 NoiseKey k;      // as in cfg_unpatch_ddim_kernel
-                if constexpr (GUIDED || CTL) k = pack_get<NoiseKey>(nk...);
+                if constexpr (GUIDED || CTL || COND) k = pack_get<NoiseKey>(nk...);
                 else k = NoiseKey(nk...);
                 zn = philox_normal4(k, (uint32_t)((lat - (int64_t)b * g.per) >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
             } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
@@ -1013,6 +1023,63 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
     return AVD_OK;
 }
 
+// The single-branch fused update of a cond-only step: eps1 = [B, Nv, D], the conditional prediction alone (12 B per latent element:
+// one eps stream less than the CFG form).  key, t_last / x0_hist and guide as in cfg_unpatch_ddim_f32; the same rows / gather choice.
+int eps_unpatch_ddim_f32(const float* eps1, const float* z, const int64_t* t_now, const int64_t* t_prev, const float* abar, int T_train,
+                         float eta, const float* noise, float* z_out, int B, int C, int T, int H, int W, int t, int h, int w,
+                         hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide) {
+    AVD_REQUIRE(eps1 && z && t_now && t_prev && abar && z_out, AVD_EINVAL, "eps_unpatch_ddim: null pointer");
+    AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "eps_unpatch_ddim: bad dims");
+    AVD_REQUIRE(eta >= 0.f && (eta == 0.f || noise || key), AVD_EINVAL, "eps_unpatch_ddim: eta > 0 needs a noise tensor or a noise key");
+    AVD_REQUIRE(z != z_out, AVD_EINVAL, "eps_unpatch_ddim: z_out must not alias z");
+    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "eps_unpatch_ddim: t_last and x0_hist go together (the DPM-Solver++(2M) update)");
+    Tube g;
+    if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
+    const bool dpm = x0_hist != nullptr;
+    if (dpm) {
+        AVD_REQUIRE(eta == 0.f, AVD_EINVAL, "eps_unpatch_dpmpp_2m: needs eta == 0");
+        AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "eps_unpatch_dpmpp_2m: x0_hist must be 16-byte aligned");
+        AVD_REQUIRE(!overlaps(x0_hist, z, (int64_t)B * g.per) && !overlaps(x0_hist, z_out, (int64_t)B * g.per), AVD_EINVAL,
+                    "eps_unpatch_dpmpp_2m: x0_hist must not overlap z or z_out");
+    }
+    const bool seeded = key && eta > 0.f;
+    NoiseKey nk{0u, 0u, 0u};
+    if (seeded) {
+        if (int rc = make_noise_key(key, B, nk)) return rc;
+        AVD_REQUIRE(g.per < ((int64_t)1 << 34), AVD_EINVAL, "eps_unpatch_ddim: a seeded sample must hold < 2^34 values");
+    }
+    GuideState gs{};
+    if (guide) {
+        AVD_REQUIRE(eta == 0.f || seeded, AVD_EINVAL, "eps_unpatch_ddim: a guided step with eta > 0 needs a noise key");
+        if (int rc = make_guide(guide, B, g.per, z_out, x0_hist, gs)) return rc;
+    }
+    const int64_t total4 = (int64_t)B * (g.per >> 2);
+    static const int tag = prof_tag_id("eps_unpatch_ddim_kernel");
+    ProfScope prof(tag, 12.0 * (double)B * g.per, st);
+    const int gt = (g.W < 32 ? g.W : 32) / g.w;      // as cfg_unpatch_ddim_f32
+    const bool rows = g_cfg_rows && (gt == 8 || gt == 4) && g.Wt % gt == 0 && g.D % 4 == 0 && (int64_t)gt * (g.D + 4) * 4 <= 64 * 1024;
+    const int groups = rows ? (int)(g.per / g.D) / gt : 0;
+    const size_t lds = rows ? (size_t)gt * (g.D + 4) * 4 : 0;
+    const dim3 grid(rows ? (unsigned)(B * groups) : (unsigned)((total4 + 255) / 256));
+    const int rgt = rows ? gt : 0;
+    // the solver's state, then the tail (the guide, if any, and the tag)
+    auto go = [&](auto... tail) {
+        if (dpm)
+            launch_unpatch(rgt, groups, grid, lds, st, eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, g, B, total4,
+                           DpmState{t_last, x0_hist}, tail...);
+        else if (seeded)
+            launch_unpatch(rgt, groups, grid, lds, st, eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, g, B, total4, nk,
+                           tail...);
+        else
+            launch_unpatch(rgt, groups, grid, lds, st, eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, g, B, total4,
+                           tail...);
+    };
+    if (guide) go(gs, CondOnly{});
+    else go(CondOnly{});
+    AVD_CHECK_LAUNCH("eps_unpatch_ddim");
+    return AVD_OK;
+}
+
 // ------------------------------------------------------------------ fused CFG + overlap-add + DDIM (audio target)
 template <bool SEEDED, class... Key>      // as cfg_unpatch_ddim_kernel; one generator call per element (e = c F + f of the sample)
 __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, const float* __restrict__ z,
@@ -1021,9 +1088,10 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
                                               const float* __restrict__ noise, float* __restrict__ z_out, int B, int Ca,
                                               int F, int len, int stride, int Na, Key... nk) {
     constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
-    constexpr bool CTL = PackHas<CfgState, Key...>::value;
-    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) + (CTL ? 1 : 0) && !(SEEDED && DPM),
-                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState");
+    constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
+    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) + (CTL ? 1 : 0) + (COND ? 1 : 0) &&
+                      !(SEEDED && DPM) && !(CTL && COND),
+                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState or CondOnly");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)B * Ca * F) return;
     const int f = (int)(i % F);
@@ -1034,7 +1102,10 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
     [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
     if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
     float e = 0.f;
-    if (f < L) {
+    if constexpr (COND) {
+        // the single-branch form: the overlap-add mean of the cond tokens, the arithmetic of audio_untok_kernel
+        if (f < L) e = ola_gather(eps2 + (int64_t)b * Na * D, D, c, len, stride, Na, f);
+    } else if (f < L) {
         // CFG combine is linear, but the reference combines per token first and overlap-adds after:
         // gather both halves with the same window order, combine per window
         int n_hi = f / stride;
@@ -1068,7 +1139,7 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
         ds.x0_hist[i] = x0;
     } else if constexpr (SEEDED) {
         NoiseKey k;      // as in cfg_unpatch_ddim_kernel
-        if constexpr (GUIDED || CTL) k = pack_get<NoiseKey>(nk...);
+        if constexpr (GUIDED || CTL || COND) k = pack_get<NoiseKey>(nk...);
         else k = NoiseKey(nk...);
         const int64_t el = i - (int64_t)b * Ca * F;
         const f32x4 zn = philox_normal4(k, (uint32_t)(el >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
@@ -1153,6 +1224,51 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
         hipLaunchKernelGGL(cfg_untoken_ddim_audio_kernel<false>, grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train, guidance,
                            eta, noise, z_out, B, Ca, F, len, stride, Na);
     AVD_CHECK_LAUNCH("cfg_untoken_ddim_audio");
+    return AVD_OK;
+}
+
+// the single-branch form (eps1 = [B, Na, Ca * len]): as eps_unpatch_ddim_f32
+int eps_untoken_ddim_audio_f32(const float* eps1, const float* z, const int64_t* t_now, const int64_t* t_prev, const float* abar,
+                               int T_train, float eta, const float* noise, float* z_out, int B, int Ca, int F, int len, int stride,
+                               hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist,
+                               const avd_latent_guide* guide) {
+    AVD_REQUIRE(eps1 && z && t_now && t_prev && abar && z_out, AVD_EINVAL, "eps_untoken_ddim_audio: null pointer");
+    AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "eps_untoken_ddim_audio: bad dims");
+    AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "eps_untoken_ddim_audio: bad chunking");
+    AVD_REQUIRE(eta >= 0.f && (eta == 0.f || noise || key), AVD_EINVAL, "eps_untoken_ddim_audio: eta > 0 needs noise or a noise key");
+    AVD_REQUIRE(z != z_out, AVD_EINVAL, "eps_untoken_ddim_audio: z_out must not alias z");
+    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "eps_untoken_ddim_audio: t_last and x0_hist go together (the DPM-Solver++(2M) update)");
+    const int64_t n = (int64_t)B * Ca * F;
+    const bool dpm = x0_hist != nullptr;
+    if (dpm) {
+        AVD_REQUIRE(eta == 0.f, AVD_EINVAL, "eps_untoken_dpmpp_2m_audio: needs eta == 0");
+        AVD_REQUIRE(!overlaps(x0_hist, z, n) && !overlaps(x0_hist, z_out, n), AVD_EINVAL,
+                    "eps_untoken_dpmpp_2m_audio: x0_hist must not overlap z or z_out");
+    }
+    const bool seeded = key && eta > 0.f;
+    NoiseKey nk{0u, 0u, 0u};
+    if (seeded)
+        if (int rc = make_noise_key(key, B, nk)) return rc;
+    GuideState gs{};
+    if (guide) {
+        AVD_REQUIRE(eta == 0.f || seeded, AVD_EINVAL, "eps_untoken_ddim_audio: a guided step with eta > 0 needs a noise key");
+        if (int rc = make_guide(guide, B, (int64_t)Ca * F, z_out, x0_hist, gs)) return rc;
+    }
+    const int Na = audio_na(F, len, stride);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    auto launch = [&](auto... p) {
+        constexpr bool SEEDED = PackHas<NoiseKey, decltype(p)...>::value;
+        hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<SEEDED, decltype(p)...>), grid, dim3(256), 0, st, eps1, z, t_now, t_prev, abar,
+                           T_train, 0.f, eta, noise, z_out, B, Ca, F, len, stride, Na, p...);
+    };
+    auto go = [&](auto... tail) {
+        if (dpm) launch(DpmState{t_last, x0_hist}, tail...);
+        else if (seeded) launch(nk, tail...);
+        else launch(tail...);
+    };
+    if (guide) go(gs, CondOnly{});
+    else go(CondOnly{});
+    AVD_CHECK_LAUNCH("eps_untoken_ddim_audio");
     return AVD_OK;
 }
 
@@ -1260,6 +1376,101 @@ int assemble_rows_f32(float* X2, const int64_t* t_now, const float* freqs, const
     return AVD_OK;
 }
 
+// ------------------------------------------------------------------ single-branch sequence assembly (cond-only steps)
+// X1[B, N, d]: the cond half of the CFG-stacked sequence alone.  Both kernels write, per cond row, what their two-branch forms above
+// write there — the same value expressions, so X1 and ss are bit-identical to the cond half of X2 and of its ss — and handle B * N
+// rows: no null rows, no copies of the target rows.
+__global__ __launch_bounds__(256) void assemble_cond_kernel(float* __restrict__ X1, const float* __restrict__ temb,
+                                                            const float* __restrict__ Xp, int B, int N, int d, int tdim, int Nt,
+                                                            int Np, int target_first, int64_t total4) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total4) return;
+    const int d4 = d >> 2;
+    const int col = (int)(i % d4) * 4;
+    const int64_t row = i / d4;
+    const int n = (int)(row % N);
+    const int b = (int)(row / N);           // 0..B-1
+    const int t0 = target_first ? 0 : Np;   // first target row
+    const bool is_t = n >= t0 && n < t0 + Nt;
+    f32x4 v;
+    if (is_t) {
+        if (col < d - tdim) return;          // the adapter GEMM's output: already in place
+        v = *reinterpret_cast<const f32x4*>(temb + (int64_t)b * tdim + (col - (d - tdim)));
+    } else {
+        const int np = target_first ? n - Nt : n;
+        v = *reinterpret_cast<const f32x4*>(Xp + ((int64_t)b * Np + np) * d + col);
+    }
+    *reinterpret_cast<f32x4*>(X1 + row * d + col) = v;
+}
+
+int assemble_cond_f32(float* X1, const float* temb, const float* Xp, int B, int N, int d, int tdim, int Nt, int Np, int target_first,
+                      hipStream_t st) {
+    const int64_t total4 = (int64_t)B * N * (d >> 2);
+    static const int tag = prof_tag_id("assemble_cond_kernel");
+    ProfScope prof(tag, 4.0 * 2.0 * ((double)B * Nt * tdim + (double)B * Np * d), st);
+    hipLaunchKernelGGL(assemble_cond_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, X1, temb, Xp, B, N, d, tdim, Nt, Np,
+                       target_first, total4);
+    AVD_CHECK_LAUNCH("assemble_cond");
+    return AVD_OK;
+}
+
+__global__ __launch_bounds__(256) void assemble_rows_cond_kernel(float* __restrict__ X1, const int64_t* __restrict__ t_now,
+                                                                 const float* __restrict__ freqs, const float* __restrict__ Xp,
+                                                                 float* __restrict__ ss, int B, int N, int d, int tdim, int Nt, int Np,
+                                                                 int target_first, float neg_log_mp) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= (int64_t)B * N) return;
+    const int n = (int)(row % N);
+    const int b = (int)(row / N);
+    const int t0 = target_first ? 0 : Np;
+    const bool is_t = n >= t0 && n < t0 + Nt;
+    const int da = d - tdim, th = tdim >> 1;
+    const float tf = is_t ? (float)t_now[b] : 0.f;
+    float acc = 0.f;
+    for (int col = lane * 4; col < d; col += 256) {
+        f32x4 v;
+        bool store = true;
+        if (is_t) {
+            if (col >= da) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int c = col - da + e;
+                    float x = 0.f;
+                    if (c < 2 * th) {
+                        const int k = c < th ? c : c - th;
+                        const float f = freqs ? freqs[k] : expf(neg_log_mp * (float)k / (float)th);
+                        const float a = tf * f;
+                        x = c < th ? cosf(a) : sinf(a);
+                    }
+                    v[e] = x;
+                }
+            } else {
+                v = *reinterpret_cast<const f32x4*>(X1 + row * d + col);      // the adapter GEMM's output, in place
+                store = false;
+            }
+        } else {
+            const int np = target_first ? n - Nt : n;
+            v = *reinterpret_cast<const f32x4*>(Xp + ((int64_t)b * Np + np) * d + col);
+        }
+        if (store) *reinterpret_cast<f32x4*>(X1 + row * d + col) = v;
+        acc += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+    }
+    acc = wave_sum(acc);
+    if (ss && lane == 0) ss[row] = acc;
+}
+
+int assemble_rows_cond_f32(float* X1, const int64_t* t_now, const float* freqs, const float* Xp, float* ss, int B, int N, int d,
+                           int tdim, int Nt, int Np, int target_first, float max_period, hipStream_t st) {
+    const int64_t rows = (int64_t)B * N;
+    static const int tag = prof_tag_id("assemble_rows_cond_kernel");
+    ProfScope prof(tag, 4.0 * ((double)B * N * d + (double)B * Np * d), st);
+    hipLaunchKernelGGL(assemble_rows_cond_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, X1, t_now, freqs, Xp, ss, B, N, d,
+                       tdim, Nt, Np, target_first, -(float)log((double)max_period));
+    AVD_CHECK_LAUNCH("assemble_rows_cond");
+    return AVD_OK;
+}
+
 // ------------------------------------------------------------------ device-side schedule cursor
 __global__ void sched_advance_kernel(const int64_t* __restrict__ sched, int n_sched, int32_t* cursor,
                                      int64_t* __restrict__ t_now, int64_t* __restrict__ t_prev, int B) {
@@ -1344,6 +1555,22 @@ extern "C" int avd_cfg_untoken_ddim_audio_f32(const float* eps2, const float* z,
                                               int stride, avd_stream_t stream) {
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, Ca, F,
                                       len, stride, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+extern "C" int avd_eps_unpatch_ddim_f32(const float* eps, const float* z, const int64_t* t_now, const int64_t* t_prev,
+                                        const float* alpha_bar, int T_train, float eta, const float* noise, float* z_out, int B, int C,
+                                        int T, int H, int W, int t, int h, int w, const avd_noise_key* key, const int64_t* t_last,
+                                        float* x0_hist, const avd_latent_guide* guide, avd_stream_t stream) {
+    AVD_REQUIRE(aligned16(eps) && aligned16(z) && aligned16(z_out) && (!noise || aligned16(noise)), AVD_EUNSUPPORTED,
+                "eps_unpatch_ddim: pointers must be 16-byte aligned");
+    return eps_unpatch_ddim_f32(eps, z, t_now, t_prev, alpha_bar, T_train, eta, noise, z_out, B, C, T, H, W, t, h, w,
+                                static_cast<hipStream_t>(stream), key, t_last, x0_hist, guide);
+}
+extern "C" int avd_eps_untoken_ddim_audio_f32(const float* eps, const float* z, const int64_t* t_now, const int64_t* t_prev,
+                                              const float* alpha_bar, int T_train, float eta, const float* noise, float* z_out, int B,
+                                              int Ca, int F, int len, int stride, const avd_noise_key* key, const int64_t* t_last,
+                                              float* x0_hist, const avd_latent_guide* guide, avd_stream_t stream) {
+    return eps_untoken_ddim_audio_f32(eps, z, t_now, t_prev, alpha_bar, T_train, eta, noise, z_out, B, Ca, F, len, stride,
+                                      static_cast<hipStream_t>(stream), key, t_last, x0_hist, guide);
 }
 extern "C" int avd_gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int B, int64_t per_sample,
                                       avd_stream_t stream) {

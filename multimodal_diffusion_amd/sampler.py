@@ -150,6 +150,14 @@ class DenoiseEngine:
     set; a scalar guidance with phi = 0 is the plain step, bit for bit and kernel for kernel.  ``set_cfg`` changes the values in
     engine-owned buffers (a captured graph follows them); switching between the plain and the controlled step starts a new graph
     generation.
+
+    ``guidance_interval`` (extension: guidance in a limited interval, Kynkaanniemi et al. 2024; default None = every step is a CFG
+    step): (t_lo, t_hi) in training timesteps, both ends inclusive.  ``run`` takes a CFG step — today's step, whichever form the
+    engine runs — where t_lo <= t_now <= t_hi, and a cond-only step elsewhere (include/avdiff_hip.h, "guidance interval"): eps =
+    eps_cond, the null branch is not computed (B*N rows through the model instead of 2B*N), per-sample guidance and rescale do not
+    apply; the seeded noise, the DPM history and the latent guide carry on across the two kinds.  ``step`` / ``advance`` take
+    explicit device timesteps and do not read them: there the caller picks the kind with ``cond_only``.  ``set_guidance_interval``
+    changes the interval for the next ``run``; it is a host-side decision and leaves captured graphs valid.
     """
 
     SOLVERS = ("ddim", "dpmpp_2m")
@@ -158,7 +166,8 @@ class DenoiseEngine:
                  tstep_dim: int, target: str, latent_shape: Tuple[int, ...], prompt_tokens: int, alpha_bar: torch.Tensor,
                  guidance: float, eta: float = 0.0, tube=(2, 4, 4), chunk=(4, 4), split_streams: Optional[bool] = None,
                  temb_mode: str = "concat", matmul: Optional[str] = None, attn: Optional[str] = None,
-                 noise_seed: Optional[int] = None, sample_offset: int = 0, solver: str = "ddim", guidance_rescale=0.0):
+                 noise_seed: Optional[int] = None, sample_offset: int = 0, solver: str = "ddim", guidance_rescale=0.0,
+                 guidance_interval=None):
         if target not in ("video", "audio"):
             raise ValueError("target must be 'video' or 'audio'")
         if eta < 0:
@@ -168,6 +177,8 @@ class DenoiseEngine:
         if solver == "dpmpp_2m" and eta > 0:
             raise ValueError("solver 'dpmpp_2m' is the deterministic (ODE) solver: eta must be 0 (the SDE variant is not implemented)")
         self.solver = solver
+        self.guidance_interval = su.check_guidance_interval(guidance_interval)
+        self._last_cond_only = False      # the kind of the last step: what eps_tokens() finds in the workspace
         if temb_mode not in ("concat", "add"):
             raise ValueError("temb_mode must be 'concat' (sampler, sample_clip.py:59-70) or 'add' (trainer, trainer.py:45-49)")
         self.temb_mode = temb_mode
@@ -466,6 +477,13 @@ class DenoiseEngine:
             self._generation += 1
             self._stale_reason = reason
 
+    # ---- guidance interval ----
+    def set_guidance_interval(self, interval) -> None:
+        """None (every step is a CFG step) or (t_lo, t_hi), ends inclusive: which steps of the next ``run`` apply guidance.  Checked
+        before anything changes.  The two kinds of step are separate launches and ``run`` picks between them on the host, so no
+        captured graph goes stale."""
+        self.guidance_interval = su.check_guidance_interval(interval)
+
     def start_latent(self, z_init: torch.Tensor, sched: torch.Tensor, strength: float = 1.0):
         """(z_start, sched_k): the start of a guided trajectory at ``strength`` (schedule_utils.truncate_schedule: k of the n steps
         of ``sched`` are run, from t_s = sched_k[0]).  k = n (strength 1): blend(mask, q(t_s), z_init) — the masked region starts on
@@ -491,9 +509,12 @@ class DenoiseEngine:
 
     def step(self, z: torch.Tensor, t_now: torch.Tensor, t_prev: torch.Tensor,
              noise: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-             t_last: Optional[torch.Tensor] = None) -> torch.Tensor:
+             t_last: Optional[torch.Tensor] = None, cond_only: bool = False) -> torch.Tensor:
         """One step t_now -> t_prev.  ``t_last`` (solver "dpmpp_2m" only): the timesteps the previous step started from, whose x0
-        ``x0_hist`` holds; None (or entries < 0) takes a first-order step.  Either way x0_hist then holds this step's x0."""
+        ``x0_hist`` holds; None (or entries < 0) takes a first-order step.  Either way x0_hist then holds this step's x0.
+        ``cond_only``: take the single-branch step of a guidance interval (eps = eps_cond, no null branch) instead of the CFG step;
+        the timesteps live on the device and are not read here, so the engine's ``guidance_interval`` does not enter: the caller
+        says which kind it wants (``run`` does, from the host copy of the schedule)."""
         if self.Xp is None:
             raise RuntimeError("call set_prompt() first")
         z = L.dev_f32(z, "z")
@@ -503,6 +524,9 @@ class DenoiseEngine:
         if not torch.cuda.is_current_stream_capturing():
             self._sync_weights()
         out = torch.empty_like(z) if out is None else out
+        self._last_cond_only = bool(cond_only)
+        if cond_only:
+            return self._step_cond(z, tn, tp, noise, out, t_last)
         if self._guide is not None or self._ctl is not None:
             return self._step_guided(z, tn, tp, noise, out, t_last)
         if self.solver == "dpmpp_2m":
@@ -560,12 +584,46 @@ class DenoiseEngine:
                                                     self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device)))
         return out
 
+    def _step_cond(self, z, tn, tp, noise, out, t_last) -> torch.Tensor:
+        """the cond-only step: one entry for every solver state, with or without a latent guide (the CFG control does not apply)"""
+        if self._key is not None and noise is not None:
+            raise ValueError("this engine draws its noise from noise_seed: do not pass `noise` as well")
+        if self._guide is not None:
+            if noise is not None:
+                raise ValueError("a guided step draws its noise from noise_seed: it takes no `noise`")
+            if self.eta > 0 and self._key is None:
+                raise ValueError("with a known latent, eta > 0 needs noise_seed (unseeded noise is not supported there)")
+        tl = h = None
+        if self.solver == "dpmpp_2m":
+            if noise is not None:
+                raise ValueError("solver 'dpmpp_2m' is deterministic: it takes no noise")
+            h = self.x0_hist
+            for name, t in (("z", z), ("out", out)):
+                if t.untyped_storage().data_ptr() == h.untyped_storage().data_ptr():
+                    raise L.AvdError(f"{name} must not alias the engine's x0_hist (the solver history)")
+            tl = self._no_hist if t_last is None else L.dev_i64(t_last, self.device)
+        elif t_last is not None:
+            raise ValueError("t_last is the multistep solver's history: this engine runs solver 'ddim'")
+        if self.eta > 0 and self._key is None and noise is None:
+            noise = torch.randn_like(z)
+        if self.eta == 0:
+            noise = None
+        L.check(L.lib().avd_denoise_step_cond_f32(C.byref(self.desc), None if self._guide is None else C.byref(self._guide),
+                                                  None if self._key is None else C.byref(self._key), L.ptr(tl), L.ptr(h), z.data_ptr(),
+                                                  self.Xp.data_ptr(), tn.data_ptr(), tp.data_ptr(), L.ptr(noise), out.data_ptr(),
+                                                  self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device)))
+        return out
+
     def eps_tokens(self) -> torch.Tensor:
-        """cond/null ε̂ tokens [2B,Nt,D] left in the workspace by the last step (debug / parity only)."""
+        """ε̂ tokens left in the workspace by the last step (debug / parity only): cond / null [2B,Nt,D] after a CFG step; after a
+        cond-only step the conditional prediction alone, [B,Nt,D] — that step computes no null rows, and whatever an earlier CFG
+        step left behind them is not handed out.  Under ``run`` the last step is the schedule's last."""
         e = self.embed
         D = self.head.output_dims[self.target]
         n = 2 * e.B * e.Nt * D
         tail = self.workspace[self.workspace.numel() - ((n * 4 + 255) // 256) * 256:]
+        if self._last_cond_only:
+            return tail[: n * 2].view(torch.float32).view(e.B, e.Nt, D).clone()
         return tail[: n * 4].view(torch.float32).view(2 * e.B, e.Nt, D).clone()
 
     # ---- whole trajectory -------------------------------------------------------------------------------
@@ -581,29 +639,30 @@ class DenoiseEngine:
     def rewind(self) -> None:
         self._cursor.zero_()
 
-    def advance(self, src: torch.Tensor, dst: torch.Tensor) -> None:
+    def advance(self, src: torch.Tensor, dst: torch.Tensor, cond_only: bool = False) -> None:
         """dst = one step from src at the cursor's (t_now, t_prev); the cursor moves on, all on the stream.  Solver "dpmpp_2m" also
-        reads t_last off the cursor (-1 at the start of the schedule: every trajectory begins first order)."""
+        reads t_last off the cursor (-1 at the start of the schedule: every trajectory begins first order).  ``cond_only``: as
+        ``step`` — the cursor's timesteps stay on the device, the caller names the kind of step."""
         if self.solver == "dpmpp_2m":
             L.check(L.lib().avd_sched_advance_ms(self._sched.data_ptr(), self._sched.numel(), self._cursor.data_ptr(),
                                                  self._tl.data_ptr(), self._tn.data_ptr(), self._tp.data_ptr(), self.embed.B,
                                                  L.stream_ptr(self.device)))
-            self.step(src, self._tn, self._tp, out=dst, t_last=self._tl)
+            self.step(src, self._tn, self._tp, out=dst, t_last=self._tl, cond_only=cond_only)
             return
         L.check(L.lib().avd_sched_advance(self._sched.data_ptr(), self._sched.numel(), self._cursor.data_ptr(),
                                           self._tn.data_ptr(), self._tp.data_ptr(), self.embed.B,
                                           L.stream_ptr(self.device)))
-        self.step(src, self._tn, self._tp, out=dst)
+        self.step(src, self._tn, self._tp, out=dst, cond_only=cond_only)
 
-    def capture_pair(self, za: torch.Tensor, zb: torch.Tensor) -> "_CapturedPair":
-        """Capture two steps (za -> zb -> za) into one HIP graph; replaying it advances the trajectory by two."""
+    def capture_pair(self, za: torch.Tensor, zb: torch.Tensor, cond_only: bool = False) -> "_CapturedPair":
+        """Capture two steps (za -> zb -> za) of one kind into one HIP graph; replaying it advances the trajectory by two."""
         if self.eta > 0 and self._key is None:
             raise NotImplementedError("graph replay with eta > 0 would replay the same noise (build the engine with noise_seed)")
         self._sync_weights()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self.advance(za, zb)
-            self.advance(zb, za)
+            self.advance(za, zb, cond_only)
+            self.advance(zb, za, cond_only)
         return _CapturedPair(self, g)
 
     GRAPH_BELOW_ROWS = 6144      # 2B*N under which a step's ~60-95 launches are host-bound: replay them from a HIP graph
@@ -611,13 +670,19 @@ class DenoiseEngine:
     def run(self, z: torch.Tensor, sched: torch.Tensor, graph: Optional[bool] = None) -> torch.Tensor:
         """Apply len(sched)-1 steps.  ``graph=True`` replays a captured two-step HIP graph; ``None`` (default) does so when the
         batch is small enough for the step to be launch-bound (2B*N < 6,144 rows, eta == 0 or a seeded engine) — results are
-        bit-identical either way (tests: test_chained_sampler_golden, test_gpu_seeded_noise)."""
-        if graph is None:
-            graph = (self.eta == 0 or self._key is not None) and 2 * self.embed.B * self.N < self.GRAPH_BELOW_ROWS
+        bit-identical either way (tests: test_chained_sampler_golden, test_gpu_seeded_noise).
+        With a ``guidance_interval`` the schedule is read on the host and split into maximal segments of CFG and of cond-only steps
+        (schedule_utils.guidance_segments); the device cursor runs on across them.  Each kind follows the rule above with its own
+        row count (B*N for cond-only steps), takes its own warm-up step outside capture and keeps its own captured pair for the
+        whole run; capturing one kind leaves the other's pair valid."""
         if self.solver == "dpmpp_2m":
             sc = torch.as_tensor(sched).reshape(-1).to("cpu", torch.long)
             if sc.numel() >= 2 and not bool((sc[1:] < sc[:-1]).all()):
                 raise ValueError("solver 'dpmpp_2m' needs a strictly decreasing schedule (its history step must lie above t_now)")
+        if self.guidance_interval is not None:
+            return self._run_segments(z, sched, graph)
+        if graph is None:
+            graph = (self.eta == 0 or self._key is not None) and 2 * self.embed.B * self.N < self.GRAPH_BELOW_ROWS
         self.begin(sched)
         za = L.dev_f32(z, "z").clone()
         zb = torch.empty_like(za)
@@ -636,6 +701,39 @@ class DenoiseEngine:
             self.advance(za, zb)
             za = zb
         return za
+
+    def _run_segments(self, z: torch.Tensor, sched: torch.Tensor, graph: Optional[bool]) -> torch.Tensor:
+        """``run`` under a guidance interval.  A captured pair steps cur -> other -> cur between the two latent buffers it was
+        captured on, so it is replayed only while the trajectory sits in its source buffer; a single eager step puts it there."""
+        segs = su.guidance_segments(sched, self.guidance_interval)
+        graphable = self.eta == 0 or self._key is not None
+        use_graph = {}
+        for cfg in (True, False):
+            rows = (2 if cfg else 1) * self.embed.B * self.N
+            use_graph[cfg] = (graphable and rows < self.GRAPH_BELOW_ROWS) if graph is None else bool(graph)
+        self.begin(sched)
+        cur = L.dev_f32(z, "z").clone()
+        other = torch.empty_like(cur)
+        warmed, pairs = set(), {}                   # per kind: warm-up step taken; (captured pair, its source buffer)
+        for start, stop, cfg in segs:
+            left, cond = stop - start, not cfg
+            while left:
+                replay = False
+                if use_graph[cfg] and cfg in warmed and left >= 2:
+                    if cfg not in pairs:
+                        pairs[cfg] = (self.capture_pair(cur, other, cond), cur)      # capture enqueues nothing
+                    replay = pairs[cfg][1] is cur
+                if replay:
+                    for _ in range(left // 2):
+                        pairs[cfg][0].replay()
+                    self._last_cond_only = cond
+                    left %= 2
+                else:                               # warm-up, a segment's odd step, or the step that realigns the buffers
+                    self.advance(cur, other, cond)
+                    cur, other = other, cur
+                    warmed.add(cfg)
+                    left -= 1
+        return cur
 
 
 def _scalar_like(v) -> bool:
@@ -675,7 +773,7 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
                          device: torch.device, init_noise: Optional[torch.Tensor] = None,
                          noise_seed: Optional[int] = None, init_video: Optional[np.ndarray] = None,
                          init_audio: Optional[np.ndarray] = None, strength: float = 1.0, mask=None,
-                         guide_seed: Optional[int] = None) -> Dict[str, np.ndarray]:
+                         guide_seed: Optional[int] = None, guidance_interval=None) -> Dict[str, np.ndarray]:
     """sample_clip.py:220-394 with the loop on the HIP engine.  The V->A branch uses the [1,3,T,H,W] layout the
     reference's comment intends (its own permute at :288 is a bug that crashes in conv3d).
     ``init_noise`` (extension; default None = draw it as the reference does, :297 / :304): the target's initial latent, so that a
@@ -692,7 +790,10 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
     sample, e.g. ``frame_mask``; 1 = keep) holds the trajectory to the clip there at every step (DenoiseEngine.set_known); without
     a mask the whole latent is free.  ``guide_seed`` keys the clip's forward noise (default ``noise_seed``, else 0).
     ``sampling.guidance_rescale`` (extension; a per-modality dict like ``guidance_scale``, default 0): CFG rescale phi of the target
-    (DenoiseEngine ``guidance_rescale``); 0 runs the plain step."""
+    (DenoiseEngine ``guidance_rescale``); 0 runs the plain step.
+    ``guidance_interval`` (extension; default None) or ``sampling.guidance_interval`` (a per-modality dict of [t_lo, t_hi] like
+    ``guidance_scale``; the argument wins): apply guidance only on steps with t_lo <= t_now <= t_hi, step on the conditional
+    prediction alone elsewhere (DenoiseEngine ``guidance_interval``)."""
     # argument checks that need no device
     strength = float(strength)
     if not 0.0 <= strength <= 1.0:
@@ -749,9 +850,11 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
 
     abar, sched = table(target)
     rescale = float(scfg.get("guidance_rescale", {}).get(target, 0.0))
+    interval = su.check_guidance_interval(guidance_interval) or su.guidance_interval_from_config(scfg, target)
     eng = DenoiseEngine(adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, target=target,
                         latent_shape=tuple(z.shape), prompt_tokens=n_prompt, alpha_bar=abar, guidance=guide, eta=eta,
-                        tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed, solver=solver, guidance_rescale=rescale)
+                        tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed, solver=solver, guidance_rescale=rescale,
+                        guidance_interval=interval)
     eng.set_prompt(z_p.float())
     if init is not None:
         if target == "video":

@@ -7,7 +7,8 @@ fp32 operation sequence as the reference so the tables are bit-identical, then u
 from __future__ import annotations
 
 import math
-from typing import Optional, Tuple
+import numbers
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -58,6 +59,51 @@ def truncate_schedule(sched, strength: float) -> torch.Tensor:
     n = sc.numel() - 1
     k = min(n, math.floor(strength * n + 1e-9))
     return sc[n - k:].clone()
+
+
+def check_guidance_interval(interval) -> Optional[Tuple[int, int]]:
+    """Validate a guidance interval: None (guidance on every step), or (t_lo, t_hi) — two integers in training timesteps with
+    0 <= t_lo <= t_hi, both ends inclusive.  Returns None or the pair as Python ints.  Host-side."""
+    if interval is None:
+        return None
+    if isinstance(interval, (str, bytes)) or not hasattr(interval, "__len__") or len(interval) != 2:
+        raise ValueError(f"guidance_interval must be None or a pair (t_lo, t_hi), got {interval!r}")
+    out = []
+    for v in interval:
+        if isinstance(v, torch.Tensor) and v.numel() == 1:
+            v = v.item()
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError(f"guidance_interval holds training timesteps (integers), got {v!r}")
+        out.append(int(v))
+    lo, hi = out
+    if lo < 0 or lo > hi:
+        raise ValueError(f"guidance_interval needs 0 <= t_lo <= t_hi, got ({lo}, {hi})")
+    return lo, hi
+
+
+def guidance_segments(sched, interval) -> List[Tuple[int, int, bool]]:
+    """Split the steps of a sampling schedule by kind: step i goes from sched[i] to sched[i + 1] and is a CFG step when
+    t_lo <= sched[i] <= t_hi (``interval`` None: always), else a cond-only step.  Returns the maximal runs of equal kind as
+    [(start, stop, cfg)] with steps start .. stop - 1, in order; together they partition range(len(sched) - 1).  Host-side."""
+    iv = check_guidance_interval(interval)
+    sc = torch.as_tensor(sched).reshape(-1).to("cpu", torch.long).tolist()
+    segs: List[Tuple[int, int, bool]] = []
+    for i, t in enumerate(sc[:-1]):
+        cfg = iv is None or iv[0] <= t <= iv[1]
+        if segs and segs[-1][2] == cfg:
+            segs[-1] = (segs[-1][0], i + 1, cfg)
+        else:
+            segs.append((i, i + 1, cfg))
+    return segs
+
+
+def guidance_interval_from_config(scfg, modality: str) -> Optional[Tuple[int, int]]:
+    """``sampling.guidance_interval`` of a config: a per-modality dict of [t_lo, t_hi] (like ``guidance_scale``); a missing key or
+    modality, or None, means guidance on every step."""
+    table = scfg.get("guidance_interval") or {}
+    if not isinstance(table, dict):
+        raise ValueError(f"sampling.guidance_interval must be a per-modality dict of [t_lo, t_hi], got {table!r}")
+    return check_guidance_interval(table.get(modality))
 
 
 def timestep_embedding(timesteps: torch.Tensor, dim: int, max_period: int = 10000) -> torch.Tensor:

@@ -114,7 +114,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
                     prompt_video: Optional[np.ndarray], prompt_audio: Optional[np.ndarray], device: torch.device,
                     init_noise: Optional[torch.Tensor] = None, max_windows_per_batch: int = 32, shard: bool = False,
                     seed: Optional[int] = None, comm_device: Optional[torch.device] = None,
-                    noise_seed: Optional[int] = None) -> Optional[Dict[str, np.ndarray]]:
+                    noise_seed: Optional[int] = None, guidance_interval=None) -> Optional[Dict[str, np.ndarray]]:
     """The body of the reference's ``main()`` (stream_infer.py:146-225) minus file I/O, with all windows batched.
 
     Returns {"audio": wav, "sr"} for a video prompt or {"video": frames uint8, "fps"} for an audio prompt.
@@ -135,6 +135,8 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     both runs take the same kernels (the matrix-pipe mode "auto" switches kernels at 2,048 / 6,144 rows: fix ``core.matmul`` to
     compare across sizes).  With ``ddim_eta`` > 0 this holds when ``noise_seed`` is set (then also for any ``max_windows_per_batch``);
     without it every rank draws from its own device generator.
+    ``guidance_interval`` (default None) or ``sampling.guidance_interval`` (per modality, [t_lo, t_hi]; the argument wins): guidance
+    on the steps with t_lo <= t_now <= t_hi only, cond-only steps elsewhere (DenoiseEngine ``guidance_interval``).
     """
     st = cfg.get("streaming", {})
     win_s, hop_s = float(st.get("window_seconds", 3.0)), float(st.get("hop_seconds", 1.0))
@@ -197,6 +199,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
             root_error = exc
 
     c = cfg["diffusion"][target]
+    interval = su.check_guidance_interval(guidance_interval) or su.guidance_interval_from_config(cfg["sampling"], target)
     abar = su.alphas_cumprod_from_betas(su.make_beta_schedule(int(c["steps"]), kind=c["schedule"], min_beta=c["min_beta"],
                                                               max_beta=c["max_beta"]))[1]
     sched = su.make_sampling_schedule(int(c["steps"]), int(c["sampler_steps"]))
@@ -221,7 +224,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
                                 latent_shape=(hi - lo, *lat), prompt_tokens=n_prompt, alpha_bar=abar, guidance=guide, eta=eta,
                                 tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed,
                                 sample_offset=lo if noise_seed is not None else 0, solver=solver,
-                                guidance_rescale=float(rescale_cfg.get(target, 0.0)))
+                                guidance_rescale=float(rescale_cfg.get(target, 0.0)), guidance_interval=interval)
             eng.set_prompt(zp_part[lo - lo0:hi - lo0].to(device).float().contiguous())
             outs.append(eng.run(z0[lo:hi].to(device).contiguous(), sched))
         if not outs:

@@ -40,6 +40,9 @@ ap.add_argument("--keep-frames", type=int, default=None,
 ap.add_argument("--guidance-rescale", type=float, default=None,
                 help="time only the sampler loop, both directions, plain CFG against DenoiseEngine(guidance_rescale=PHI) (statistics "
                      "pass + controlled fused step), interleaved in one process")
+ap.add_argument("--guidance-interval", type=int, nargs=2, default=None, metavar=("LO", "HI"),
+                help="time only the sampler loop, both directions, the plain trajectory against DenoiseEngine(guidance_interval=(LO, HI)) "
+                     "(cond-only steps outside the interval), interleaved in one process")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 B, S, size = args.batch, args.sampler_steps, args.size
@@ -87,6 +90,39 @@ if args.eta is not None:
             graph = (eng.eta == 0 or eng.noise_seed is not None) and rows < eng.GRAPH_BELOW_ROWS
             print(f"[{args.matmul}] {direction} B={B} {size}x{size} {name:18s}: {med:7.3f} ms/step (min {min(times[name]):7.3f}, "
                   f"{args.reps} rounds of {S} steps, {'graph' if graph else 'eager'})  {100 * (med / base - 1):+6.2f} % vs eta=0", flush=True)
+    sys.exit(0)
+
+if args.guidance_interval is not None:
+    # guidance interval: the plain engine against one whose steps outside [LO, HI] are cond-only, interleaved; ms/step and clips/s medians
+    import statistics
+    zv_prompt = torch.randn(B, 8, 12, size // 8, size // 8, generator=torch.Generator().manual_seed(3)).to(dev)
+    lo, hi = args.guidance_interval
+    variants = (("plain", None), (f"interval=[{lo},{hi}]", (lo, hi)))
+    for target, z_init, prompt, n_prompt in (("video", z0, za, 37), ("audio", za, zv_prompt, (12 // 2) * (size // 8 // 4) ** 2)):
+        engs = []
+        for name, iv in variants:
+            eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=tdim, target=target,
+                                  latent_shape=tuple(z_init.shape), prompt_tokens=n_prompt, alpha_bar=abar, guidance=3.5,
+                                  guidance_interval=iv, matmul=args.matmul, solver=args.solver)
+            eng.set_prompt(prompt)
+            eng.run(z_init, sched)                      # warm-up: both kinds of step (and their graphs where run() captures)
+            engs.append(eng)
+        n_cfg = sum(b - a for a, b, c in su.guidance_segments(sched, (lo, hi)) if c)
+        times = {name: [] for name, _ in variants}
+        for _ in range(args.reps):
+            for (name, _), eng in zip(variants, engs):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                eng.run(z_init, sched)
+                torch.cuda.synchronize()
+                times[name].append(time.perf_counter() - t0)
+        base = statistics.median(times["plain"])
+        direction = "A->V" if target == "video" else "V->A"
+        for name, iv in variants:
+            med = statistics.median(times[name])
+            print(f"[{args.matmul}] {direction} {args.solver} B={B} {size}x{size} {name:22s}: {1e3 * med / S:7.3f} ms/step (min "
+                  f"{1e3 * min(times[name]) / S:7.3f}, max {1e3 * max(times[name]) / S:7.3f}), {B / med:8.2f} clips/s, {args.reps} rounds of {S} "
+                  f"steps ({n_cfg if iv else S} CFG)  {100 * (med / base - 1):+6.2f} % vs plain", flush=True)
     sys.exit(0)
 
 if args.guidance_rescale is not None:
