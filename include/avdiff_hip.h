@@ -650,6 +650,18 @@ int avd_crossfade_f32(const float* chunks, const float* w, float* out, int N, in
 int avd_crossfade_u8(const uint8_t* chunks, const float* w, uint8_t* out, int N, int L, int hop, int64_t inner,
                      avd_stream_t stream);
 
+/* ---- latent window consensus (extension: MultiDiffusion-style co-denoising, Bar-Tal et al. 2023, for the windows of
+ * stream_generate).  z [N, outer, L, inner] holds N consecutive windows of one canvas of (N-1)*hop + L positions along the sliding
+ * axis, window k at positions k*hop .. k*hop + L - 1 (video latent [N,C,T,H,W]: outer = C, L = T, inner = H*W; audio latent
+ * [N,Ca,F]: outer = Ca, L = F, inner = 1).  In place: every canvas element (o, p, j) that lies under two or more windows k = lo..hi
+ * (the windows the cross-fade gathers for p) becomes
+ *     m = (sum_k w[p - k*hop] * z[k, o, p - k*hop, j]) / (sum_k w[p - k*hop])
+ * in every one of them: sums over k in increasing order from 0, multiply, add and divide rounded separately (no FMA contraction), so
+ * the fp32 result is that of a numpy loop in the same order.  An element under one window is not touched (it keeps its bits).
+ * w[L]: per-position weights on the device, all > 0 (the caller checks: the sum is not clamped).  N == 1 or hop >= L launches
+ * nothing.  One thread owns one canvas element and nobody else reads or writes its z elements, so the pass is race free. */
+int avd_window_consensus_f32(float* z, const float* w, int N, int64_t outer, int L, int hop, int64_t inner, avd_stream_t stream);
+
 /* device-side sampling-schedule cursor so a captured step can be replayed without host writes:
  * t_now[b] = sched[*cursor], t_prev[b] = sched[*cursor+1] for all b, then (*cursor)++ . */
 int avd_sched_advance(const int64_t* sched, int n_sched, int32_t* cursor, int64_t* t_now, int64_t* t_prev,

@@ -183,6 +183,7 @@ SIGNATURES = {
     "avd_avgpool_frames_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "avd_crossfade_f32": (_I, [_P, _P, _P, _I, _I, _I, _L, _P]),
     "avd_crossfade_u8": (_I, [_P, _P, _P, _I, _I, _I, _L, _P]),
+    "avd_window_consensus_f32": (_I, [_P, _P, _I, _L, _I, _I, _L, _P]),
     "avd_prof_enable": (_I, [_I]),
     "avd_prof_num_tags": (_I, []),
     "avd_prof_tag_name": (C.c_char_p, [_I]),

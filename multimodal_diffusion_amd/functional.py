@@ -316,6 +316,51 @@ def cfg_rescale(e_cond: Tensor, e_cfg: Tensor, phi, *, return_scale: bool = Fals
     return out
 
 
+def window_dims(shape) -> tuple:
+    """(outer, L, inner) of a window batch for ``avd_window_consensus_f32``: a video latent [N,C,T,H,W] slides along T, an audio latent
+    [N,Ca,F] along F."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) == 5:
+        return shape[1], shape[2], shape[3] * shape[4]
+    if len(shape) == 3:
+        return shape[1], shape[2], 1
+    raise ValueError(f"a window batch is a video latent [N,C,T,H,W] or an audio latent [N,Ca,F], got shape {shape}")
+
+
+def consensus_weights(weights, L_: int) -> Tensor:
+    """The [L] per-position weight table of ``window_consensus`` as a CPU fp32 tensor: None = uniform; checked to be of shape (L,),
+    finite and > 0 (the kernel divides by their sum unclamped)."""
+    if weights is None:
+        return torch.ones(L_, dtype=torch.float32)
+    w = torch.as_tensor(weights).detach().to("cpu", torch.float32)
+    if tuple(w.shape) != (L_,):
+        raise ValueError(f"consensus weights have shape {tuple(w.shape)}, expected ({L_},): one weight per window position")
+    if not bool((torch.isfinite(w) & (w > 0)).all()):
+        raise ValueError("consensus weights must be finite and > 0")
+    return w.contiguous()
+
+
+def window_consensus(z: Tensor, hop: int, weights: Optional[Tensor] = None) -> Tensor:
+    """Latent window consensus, in place (``avd_window_consensus_f32``, contract in include/avdiff_hip.h): ``z`` is a batch of N
+    consecutive windows of one canvas, window k at canvas positions k*hop .. k*hop + L - 1 of the sliding axis (T of a video latent
+    [N,C,T,H,W], F of an audio latent [N,Ca,F]); every canvas position under several windows is replaced in each of them by their
+    weighted mean, a position under one window keeps its bits.  ``weights`` [L] > 0, None = uniform (MultiDiffusion's choice).
+    Returns ``z``."""
+    if not z.is_cuda:
+        raise L.AvdError(f"z is on {z.device}: the HIP hot path needs ROCm device tensors (no CPU fallback)")
+    if z.dtype != torch.float32 or not z.is_contiguous():
+        raise TypeError("window_consensus works in place: z must be a contiguous float32 tensor")
+    outer, L_, inner = window_dims(z.shape)
+    hop = int(hop)
+    if hop <= 0:
+        raise ValueError(f"hop must be > 0, got {hop}")
+    if z.numel() == 0:
+        raise ValueError(f"empty window batch {tuple(z.shape)}")
+    w = torch.ones(L_, dtype=torch.float32, device=z.device) if weights is None else consensus_weights(weights, L_).to(z.device)
+    L.check(L.lib().avd_window_consensus_f32(z.data_ptr(), w.data_ptr(), z.shape[0], outer, L_, hop, inner, _st(z)))
+    return z
+
+
 def gaussian_noise(seed: int, sample_offset: int, t_now: Tensor, shape) -> Tensor:
     """The seeded normal stream of the DDIM eta > 0 noise (avd_gaussian_noise_f32; contract in include/avdiff_hip.h): a
     float32 tensor of ``shape`` = (B, ...) whose row b holds sample ``sample_offset + b``'s normals at timestep ``t_now[b]``,

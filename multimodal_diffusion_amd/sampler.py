@@ -158,6 +158,16 @@ class DenoiseEngine:
     apply; the seeded noise, the DPM history and the latent guide carry on across the two kinds.  ``step`` / ``advance`` take
     explicit device timesteps and do not read them: there the caller picks the kind with ``cond_only``.  ``set_guidance_interval``
     changes the interval for the next ``run``; it is a host-side decision and leaves captured graphs valid.
+
+    ``set_window_consensus(hop, weights=None)`` (extension: latent window consensus, MultiDiffusion-style co-denoising, Bar-Tal et
+    al. 2023; default off): the batch is N consecutive windows of one latent canvas, window k at positions k*hop .. k*hop + L - 1 of
+    the sliding axis (T of a video latent, F of an audio latent).  While set, every kind of step ends with one more launch on the
+    same stream (include/avdiff_hip.h, avd_window_consensus_f32) that replaces, in ``out``, every canvas position under several
+    windows by their weighted mean, so the windows take the next step from latents that agree wherever they overlap.  It is part
+    of ``step``: ``capture_pair`` captures it and ``run(graph=True)`` replays it.  eta == 0 only (the mean of independent noise
+    draws would shrink their variance).  DPM-Solver++(2M) needs nothing extra: all windows share the timesteps, so the update is the
+    same linear map of (z, x0, x0_hist) for every window and the consensus of the outputs equals the output of the consensed
+    inputs; ``x0_hist`` stays per window.
     """
 
     SOLVERS = ("ddim", "dpmpp_2m")
@@ -263,6 +273,9 @@ class DenoiseEngine:
         self._mask: Optional[torch.Tensor] = None
         self._guide: Optional[L.LatentGuide] = None
         self._guide_sig = None       # what a captured graph holds of the guide by value: pointers, stride, seed
+        # window consensus (set_window_consensus): the hop (None = off) and the [L] weight table at a fixed address
+        self._cons_hop: Optional[int] = None
+        self._cons_w: Optional[torch.Tensor] = None
         self._bind_weights()
         self._apply_cfg()
 
@@ -477,6 +490,35 @@ class DenoiseEngine:
             self._generation += 1
             self._stale_reason = reason
 
+    # ---- window consensus: the batch as N consecutive windows of one latent canvas ----
+    def set_window_consensus(self, hop: int, weights=None) -> None:
+        """This batch is N consecutive windows of one canvas, ``hop`` latent positions apart: every step from now on ends with the
+        consensus launch on its ``out`` (class docstring).  ``weights``: [L] per-position weights > 0, None = uniform.  Checked
+        before anything changes.  The weights are copied into an engine-owned buffer, so new weights reach a captured graph;
+        switching the consensus on, or changing ``hop`` (held by value), starts a new graph generation."""
+        if self.eta > 0:
+            raise ValueError("window consensus needs eta == 0: the mean of the windows' independent noise draws would shrink their "
+                             "variance (a canvas-keyed noise stream is not implemented)")
+        if int(hop) != hop or int(hop) <= 0:
+            raise ValueError(f"hop must be a positive whole number of latent positions, got {hop!r}")
+        L_ = Fn.window_dims(self.latent_shape)[1]
+        w = Fn.consensus_weights(weights, L_)
+        if self._cons_w is None:
+            self._cons_w = torch.empty(L_, dtype=torch.float32, device=self.device)
+        self._cons_w.copy_(w)
+        self._touch_consensus(int(hop))
+
+    def clear_window_consensus(self) -> None:
+        """Back to independent samples (the weight buffer is kept for a later set_window_consensus)."""
+        self._touch_consensus(None)
+
+    def _touch_consensus(self, hop: Optional[int]) -> None:
+        if hop != self._cons_hop:
+            self._generation += 1
+            self._stale_reason = "the window consensus was switched on or off, or its hop changed (set_window_consensus / " \
+                                 "clear_window_consensus)"
+        self._cons_hop = hop
+
     # ---- guidance interval ----
     def set_guidance_interval(self, interval) -> None:
         """None (every step is a CFG step) or (t_lo, t_hi), ends inclusive: which steps of the next ``run`` apply guidance.  Checked
@@ -525,6 +567,15 @@ class DenoiseEngine:
             self._sync_weights()
         out = torch.empty_like(z) if out is None else out
         self._last_cond_only = bool(cond_only)
+        out = self._step_kind(z, tn, tp, noise, out, t_last, cond_only)
+        if self._cons_hop is not None:
+            outer, L_, inner = Fn.window_dims(self.latent_shape)
+            L.check(L.lib().avd_window_consensus_f32(out.data_ptr(), self._cons_w.data_ptr(), self.latent_shape[0], outer, L_,
+                                                     self._cons_hop, inner, L.stream_ptr(self.device)))
+        return out
+
+    def _step_kind(self, z, tn, tp, noise, out, t_last, cond_only) -> torch.Tensor:
+        """the step proper: cond-only, guided / CFG-controlled, DPM-Solver++(2M), seeded or plain DDIM"""
         if cond_only:
             return self._step_cond(z, tn, tp, noise, out, t_last)
         if self._guide is not None or self._ctl is not None:
@@ -667,6 +718,13 @@ class DenoiseEngine:
 
     GRAPH_BELOW_ROWS = 6144      # 2B*N under which a step's ~60-95 launches are host-bound: replay them from a HIP graph
 
+    def check_schedule(self, sched: torch.Tensor) -> None:
+        """what ``run`` asks of a schedule before it steps (a caller that drives ``begin`` / ``advance`` itself asks the same)"""
+        if self.solver == "dpmpp_2m":
+            sc = torch.as_tensor(sched).reshape(-1).to("cpu", torch.long)
+            if sc.numel() >= 2 and not bool((sc[1:] < sc[:-1]).all()):
+                raise ValueError("solver 'dpmpp_2m' needs a strictly decreasing schedule (its history step must lie above t_now)")
+
     def run(self, z: torch.Tensor, sched: torch.Tensor, graph: Optional[bool] = None) -> torch.Tensor:
         """Apply len(sched)-1 steps.  ``graph=True`` replays a captured two-step HIP graph; ``None`` (default) does so when the
         batch is small enough for the step to be launch-bound (2B*N < 6,144 rows, eta == 0 or a seeded engine) — results are
@@ -675,10 +733,7 @@ class DenoiseEngine:
         (schedule_utils.guidance_segments); the device cursor runs on across them.  Each kind follows the rule above with its own
         row count (B*N for cond-only steps), takes its own warm-up step outside capture and keeps its own captured pair for the
         whole run; capturing one kind leaves the other's pair valid."""
-        if self.solver == "dpmpp_2m":
-            sc = torch.as_tensor(sched).reshape(-1).to("cpu", torch.long)
-            if sc.numel() >= 2 and not bool((sc[1:] < sc[:-1]).all()):
-                raise ValueError("solver 'dpmpp_2m' needs a strictly decreasing schedule (its history step must lie above t_now)")
+        self.check_schedule(sched)
         if self.guidance_interval is not None:
             return self._run_segments(z, sched, graph)
         if graph is None:

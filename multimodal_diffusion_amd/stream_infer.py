@@ -12,6 +12,12 @@ further communication (the reference ends every window's call with its own decod
 ``split_*`` are host-side slicing (as in the reference); the fade tables are built on the host with the reference's
 fp32 numpy expressions and uploaded; ``crossfade_*`` keep the reference's numpy-in / numpy-out signatures.
 File I/O and the CLI of the reference script are out of scope.
+
+Extension, opt-in (``stream_generate(consensus=...)``): latent window consensus.  Independent windows make the stitched clip the
+pixel average of up to window / hop unrelated samples.  With consensus the windows are views of ONE latent canvas: after every
+denoising step each canvas position under several windows is replaced in all of them by their weighted mean (MultiDiffusion, Bar-Tal
+et al. 2023; ``avd_window_consensus_f32``), so they stay one batch and finish as one coherent latent clip.  ``latent_hop``,
+``windows_from_canvas`` and ``canvas_from_windows`` are its host-side geometry.
 """
 from __future__ import annotations
 
@@ -22,6 +28,7 @@ import torch
 
 from . import _lib as L
 from . import dist as D
+from . import functional as Fn
 from . import schedule_utils as su
 from .sampler import DenoiseEngine
 
@@ -109,12 +116,62 @@ def crossfade_video(chunks: np.ndarray, hop: int, win: int, fade_f: int, device=
     return out.cpu().numpy()
 
 
+def latent_hop(cfg: Dict, target: str) -> Tuple[int, int]:
+    """(hop, L): the hop and the window length in latent positions of the target's sliding axis, from ``streaming.window_seconds`` /
+    ``hop_seconds``.  Video (axis T): the window's and the hop's frames over ``t_down``; audio (axis F): ``frames_per_clip`` latent
+    frames per window, hop = Fa * hop_s / win_s.  ValueError when the hop is not a whole number of latent positions (windows could not
+    share canvas positions)."""
+    st = cfg.get("streaming", {})
+    win_s, hop_s = float(st.get("window_seconds", 3.0)), float(st.get("hop_seconds", 1.0))
+    if target == "video":
+        fps, t_down = int(cfg["video"]["fps"]), int(cfg["video"]["latent"]["t_down"])
+        win_f, hop_f = int(round(fps * win_s)), int(round(fps * hop_s))
+        if hop_f <= 0 or hop_f % t_down:
+            raise ValueError(f"the hop of {hop_s} s is {hop_f} frames, not a positive multiple of the VAE's t_down = {t_down}: the windows "
+                             "do not share latent frames")
+        return hop_f // t_down, max(1, win_f // t_down)
+    if target == "audio":
+        Fa = int(cfg["audio"]["latent"]["frames_per_clip"])
+        hop = Fa * hop_s / win_s
+        if hop < 0.5 or abs(hop - round(hop)) > 1e-9 * hop:
+            raise ValueError(f"the hop of {hop_s} s is {hop:g} of the window's {Fa} latent frames, not a positive whole number: the windows "
+                             "do not share latent frames")
+        return int(round(hop)), Fa
+    raise ValueError("target must be 'video' or 'audio'")
+
+
+def windows_from_canvas(canvas: torch.Tensor, L_: int, hop: int) -> torch.Tensor:
+    """Latent canvas -> the batch of its windows: video [C, P, H, W] -> [N, C, L, H, W], audio [Ca, P] -> [N, Ca, L], with
+    P = (N-1)*hop + L; window k is canvas positions k*hop .. k*hop + L - 1 (overlapping windows repeat canvas values)."""
+    if canvas.dim() not in (2, 4):
+        raise ValueError(f"a latent canvas is [C, P, H, W] (video) or [Ca, P] (audio), got shape {tuple(canvas.shape)}")
+    P = canvas.shape[1]
+    if L_ <= 0 or hop <= 0 or P < L_ or (P - L_) % hop:
+        raise ValueError(f"a canvas of {P} positions is not (N-1)*{hop} + {L_} for any N >= 1")
+    return torch.stack([canvas[:, k * hop:k * hop + L_] for k in range((P - L_) // hop + 1)], 0).contiguous()
+
+
+def canvas_from_windows(windows: torch.Tensor, hop: int) -> torch.Tensor:
+    """Inverse of ``windows_from_canvas`` for a batch whose windows agree wherever they overlap (what the consensus leaves): [N, C, L,
+    H, W] -> [C, (N-1)*hop + L, H, W], [N, Ca, L] -> [Ca, (N-1)*hop + L].  Where windows disagree the later one wins."""
+    if windows.dim() not in (3, 5):
+        raise ValueError(f"a window batch is [N, C, L, H, W] (video) or [N, Ca, L] (audio), got shape {tuple(windows.shape)}")
+    if hop <= 0:
+        raise ValueError(f"hop must be > 0, got {hop}")
+    N, L_ = windows.shape[0], windows.shape[2]
+    canvas = windows.new_empty((windows.shape[1], (N - 1) * hop + L_) + tuple(windows.shape[3:]))
+    for k in range(N):
+        canvas[:, k * hop:k * hop + L_] = windows[k]
+    return canvas
+
+
 @torch.no_grad()
 def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, head, tstep_dim: int, prompt_modality: str,
                     prompt_video: Optional[np.ndarray], prompt_audio: Optional[np.ndarray], device: torch.device,
                     init_noise: Optional[torch.Tensor] = None, max_windows_per_batch: int = 32, shard: bool = False,
                     seed: Optional[int] = None, comm_device: Optional[torch.device] = None,
-                    noise_seed: Optional[int] = None, guidance_interval=None) -> Optional[Dict[str, np.ndarray]]:
+                    noise_seed: Optional[int] = None, guidance_interval=None, consensus=None,
+                    return_latents: bool = False) -> Optional[Dict[str, np.ndarray]]:
     """The body of the reference's ``main()`` (stream_infer.py:146-225) minus file I/O, with all windows batched.
 
     Returns {"audio": wav, "sr"} for a video prompt or {"video": frames uint8, "fps"} for an audio prompt.
@@ -137,6 +194,18 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     without it every rank draws from its own device generator.
     ``guidance_interval`` (default None) or ``sampling.guidance_interval`` (per modality, [t_lo, t_hi]; the argument wins): guidance
     on the steps with t_lo <= t_now <= t_hi only, cond-only steps elsewhere (DenoiseEngine ``guidance_interval``).
+    ``consensus`` (default None = independent windows, today's output; else ``streaming.latent_consensus``, the argument wins):
+    "uniform" or a table of L weights > 0 (L latent positions per window, ``latent_hop``) switches latent window consensus on: the
+    windows are views of one latent canvas and after every step each canvas position under several windows becomes their weighted
+    mean in all of them (DenoiseEngine ``set_window_consensus``), so the finished latents agree on every overlap.  The initial
+    latents must agree there too (the first mean would shrink the noise otherwise): ``seed`` draws one canvas from the CPU generator
+    and crops it, no seed draws the canvas on the device, and a caller's ``init_noise`` keeps its [N_windows, *latent] shape and must
+    be windows of a canvas (``windows_from_canvas``).  Up to ``max_windows_per_batch`` windows are one engine, run as without
+    consensus; more are several engines stepped in lock-step (eager) with one consensus pass over all windows per step; the latents
+    are the same bits either way where the engines take the same kernels.  Decode and stitching are unchanged: every window is
+    decoded on its own and cross-faded, now over near-identical content.  Needs ``ddim_eta`` == 0 and ``shard=False``: windows on
+    different ranks would need a halo exchange of their overlaps after every step, which is not implemented.
+    ``return_latents`` adds "latents": the finished [N_windows, *latent] float32 latents (single process only).
     """
     st = cfg.get("streaming", {})
     win_s, hop_s = float(st.get("window_seconds", 3.0)), float(st.get("hop_seconds", 1.0))
@@ -150,6 +219,24 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     eta = float(cfg["sampling"].get("ddim_eta", 0.0))
     solver = str(cfg["sampling"].get("solver", "ddim"))       # "ddim" | "dpmpp_2m" (DenoiseEngine ``solver``)
     rescale_cfg = cfg["sampling"].get("guidance_rescale", {})  # per modality, like guidance_scale (DenoiseEngine ``guidance_rescale``)
+
+    if consensus is None:
+        consensus = st.get("latent_consensus")
+    if consensus is not None and consensus is not False:
+        if shard:
+            raise ValueError("consensus with shard=True is not implemented: windows on different ranks would have to exchange their "
+                             "overlapping latent positions (a halo) after every step; run the windows on one device")
+        if eta > 0:
+            raise ValueError("consensus needs sampling.ddim_eta == 0: the mean of the windows' independent noise draws would shrink "
+                             "their variance")
+        cons_hop, cons_L = latent_hop(cfg, "audio" if prompt_modality == "video" else "video")
+        cons_w = None if isinstance(consensus, str) and consensus == "uniform" else consensus
+        if isinstance(cons_w, str):
+            raise ValueError(f"consensus must be None, 'uniform' or a table of {cons_L} weights, got {consensus!r}")
+        cons_w = Fn.consensus_weights(cons_w, cons_L)
+        consensus = True
+    else:
+        consensus = False
 
     import torch.distributed as tdist
     world = tdist.get_world_size() if (shard and tdist.is_initialized()) else 1
@@ -204,7 +291,23 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
                                                               max_beta=c["max_beta"]))[1]
     sched = su.make_sampling_schedule(int(c["steps"]), int(c["sampler_steps"]))
     Nw = zp_shape[0]
-    if init_noise is not None:
+    if return_latents and world > 1:
+        raise ValueError("return_latents needs a single process: a sharded run gathers the decoded windows only")
+    if consensus:
+        if lat[1] != cons_L:
+            raise ValueError(f"consensus: the target latent has {lat[1]} positions along its sliding axis (data.clip_seconds), a window of "
+                             f"streaming.window_seconds has {cons_L}: they must be equal")
+        canvas_shape = (lat[0], (Nw - 1) * cons_hop + cons_L) + tuple(lat[2:])
+    if consensus and init_noise is not None:
+        z0 = init_noise
+        if tuple(z0.shape) == (Nw, *lat) and not torch.equal(windows_from_canvas(canvas_from_windows(z0, cons_hop), cons_L, cons_hop), z0):
+            raise ValueError(f"consensus: init_noise differs between windows where they overlap (hop {cons_hop} of {cons_L} latent "
+                             "positions); build it with windows_from_canvas(canvas, L, hop)")
+    elif consensus and seed is not None:
+        z0 = windows_from_canvas(torch.randn(*canvas_shape, generator=torch.Generator().manual_seed(int(seed))), cons_L, cons_hop)
+    elif consensus:
+        z0 = windows_from_canvas(torch.randn(*canvas_shape, device=device), cons_L, cons_hop)
+    elif init_noise is not None:
         z0 = init_noise
     elif seed is not None:
         z0 = torch.randn(Nw, *lat, generator=torch.Generator().manual_seed(int(seed)))
@@ -215,21 +318,48 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     if tuple(z0.shape) != (Nw, *lat):
         raise ValueError(f"init_noise has shape {tuple(z0.shape)}, expected {(Nw, *lat)}")
 
+    def engine(zp_part: torch.Tensor, lo0: int, lo: int, hi: int) -> DenoiseEngine:
+        """the engine of windows [lo, hi), its prompt rows set from zp_part (which starts at window lo0)"""
+        eng = DenoiseEngine(adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, target=target,
+                            latent_shape=(hi - lo, *lat), prompt_tokens=n_prompt, alpha_bar=abar, guidance=guide, eta=eta,
+                            tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed,
+                            sample_offset=lo if noise_seed is not None else 0, solver=solver,
+                            guidance_rescale=float(rescale_cfg.get(target, 0.0)), guidance_interval=interval)
+        eng.set_prompt(zp_part[lo - lo0:hi - lo0].to(device).float().contiguous())
+        return eng
+
     def denoise(zp_part: torch.Tensor, lo0: int, hi0: int) -> torch.Tensor:
         """the windows [lo0, hi0) of the list, stepped in batches of at most max_windows_per_batch; no communication"""
         outs = []
         for lo in range(lo0, hi0, max_windows_per_batch):
             hi = min(hi0, lo + max_windows_per_batch)
-            eng = DenoiseEngine(adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, target=target,
-                                latent_shape=(hi - lo, *lat), prompt_tokens=n_prompt, alpha_bar=abar, guidance=guide, eta=eta,
-                                tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed,
-                                sample_offset=lo if noise_seed is not None else 0, solver=solver,
-                                guidance_rescale=float(rescale_cfg.get(target, 0.0)), guidance_interval=interval)
-            eng.set_prompt(zp_part[lo - lo0:hi - lo0].to(device).float().contiguous())
-            outs.append(eng.run(z0[lo:hi].to(device).contiguous(), sched))
+            outs.append(engine(zp_part, lo0, lo, hi).run(z0[lo:hi].to(device).contiguous(), sched))
         if not outs:
             return torch.empty(0, *lat, device=device)
         return torch.cat(outs, 0) if len(outs) > 1 else outs[0]
+
+    def denoise_consensus(zp_all: torch.Tensor) -> torch.Tensor:
+        """all windows as views of one latent canvas: one engine with the consensus inside its step, or, above
+        max_windows_per_batch, several engines in lock-step with one consensus pass over all windows after every step"""
+        if Nw <= max_windows_per_batch:
+            eng = engine(zp_all, 0, 0, Nw)
+            eng.set_window_consensus(cons_hop, cons_w)
+            return eng.run(z0.to(device).contiguous(), sched)
+        engs = [(lo, min(Nw, lo + max_windows_per_batch)) for lo in range(0, Nw, max_windows_per_batch)]
+        engs = [(lo, hi, engine(zp_all, 0, lo, hi)) for lo, hi in engs]
+        for _, _, eng in engs:
+            eng.check_schedule(sched)
+            eng.begin(sched)
+        w_dev = cons_w.to(device)
+        za = z0.to(device, torch.float32).contiguous().clone()
+        zb = torch.empty_like(za)
+        for start, stop, cfg_step in su.guidance_segments(sched, interval):     # the kind of every step, read on the host as run() does
+            for _ in range(stop - start):
+                for lo, hi, eng in engs:
+                    eng.advance(za[lo:hi], zb[lo:hi], cond_only=not cfg_step)
+                Fn.window_consensus(zb, cons_hop, w_dev)
+                za, zb = zb, za
+        return za
 
     def decode_windows(z: torch.Tensor) -> torch.Tensor:
         """finished latents of some windows -> what the stitcher takes: waveforms [n, L] float32 or frames [n, T, H, W, 3] uint8"""
@@ -252,10 +382,15 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
             return None
         out = out.to(device)
     else:
-        out = decode_windows(denoise(z_p, 0, Nw))
+        z_fin = denoise_consensus(z_p) if consensus else denoise(z_p, 0, Nw)
+        out = decode_windows(z_fin)
 
     if target == "audio":
         w = torch.from_numpy(audio_fade_window(out.shape[1], int(round(sr * xfade_s))))
-        return {"audio": crossfade_tensor(out, w, int(round(sr * hop_s))).cpu().numpy(), "sr": sr}
-    w = torch.from_numpy(video_fade_window(out.shape[1], int(round(xfade_s * fps))))
-    return {"video": crossfade_tensor(out, w, int(round(fps * hop_s))).cpu().numpy(), "fps": fps}
+        res = {"audio": crossfade_tensor(out, w, int(round(sr * hop_s))).cpu().numpy(), "sr": sr}
+    else:
+        w = torch.from_numpy(video_fade_window(out.shape[1], int(round(xfade_s * fps))))
+        res = {"video": crossfade_tensor(out, w, int(round(fps * hop_s))).cpu().numpy(), "fps": fps}
+    if return_latents:
+        res["latents"] = z_fin.cpu().numpy()
+    return res

@@ -43,6 +43,10 @@ ap.add_argument("--guidance-rescale", type=float, default=None,
 ap.add_argument("--guidance-interval", type=int, nargs=2, default=None, metavar=("LO", "HI"),
                 help="time only the sampler loop, both directions, the plain trajectory against DenoiseEngine(guidance_interval=(LO, HI)) "
                      "(cond-only steps outside the interval), interleaved in one process")
+ap.add_argument("--consensus-hop", type=int, default=None, metavar="HOP",
+                help="time only the sampler loop, the plain trajectory against DenoiseEngine.set_window_consensus(HOP) (the batch as "
+                     "consecutive windows of one latent canvas, HOP latent frames apart; the audio direction takes HOP * 150 / 12 "
+                     "latent frames), interleaved in one process")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 B, S, size = args.batch, args.sampler_steps, args.size
@@ -153,6 +157,37 @@ if args.guidance_rescale is not None:
             med = statistics.median(times[name])
             print(f"[{args.matmul}] {direction} {args.solver} B={B} {size}x{size} {name:14s}: {med:7.3f} ms/step (min {min(times[name]):7.3f}, "
                   f"{args.reps} rounds of {S} steps)  {100 * (med / base - 1):+6.2f} % vs plain", flush=True)
+    sys.exit(0)
+
+if args.consensus_hop is not None:
+    # window consensus cost: the plain engine against one whose every step ends with the consensus pass over its output, interleaved
+    import statistics
+    zv_prompt = torch.randn(B, 8, 12, size // 8, size // 8, generator=torch.Generator().manual_seed(3)).to(dev)
+    for target, z_init, prompt, n_prompt, hop in (("video", z0, za, 37, args.consensus_hop),
+                                                  ("audio", za, zv_prompt, (12 // 2) * (size // 8 // 4) ** 2, args.consensus_hop * 150 // 12)):
+        engs = {}
+        for name in ("plain", f"consensus hop={hop}"):
+            eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=tdim, target=target,
+                                  latent_shape=tuple(z_init.shape), prompt_tokens=n_prompt, alpha_bar=abar, guidance=3.5,
+                                  matmul=args.matmul, solver=args.solver)
+            eng.set_prompt(prompt)
+            if name != "plain":
+                eng.set_window_consensus(hop)
+            eng.run(z_init, sched[:4])                  # warm-up (a graph-replaying variant captures here too)
+            engs[name] = eng
+        times = {name: [] for name in engs}
+        for _ in range(args.reps):
+            for name, eng in engs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                eng.run(z_init, sched)
+                torch.cuda.synchronize()
+                times[name].append(1e3 * (time.perf_counter() - t0) / S)
+        base = statistics.median(times["plain"])
+        for name in engs:
+            med = statistics.median(times[name])
+            print(f"[{args.matmul}] {'A->V' if target == 'video' else 'V->A'} {args.solver} B={B} {size}x{size} {name:18s}: {med:7.3f} ms/step "
+                  f"(min {min(times[name]):7.3f}, {args.reps} rounds of {S} steps)  {100 * (med / base - 1):+6.2f} % vs plain", flush=True)
     sys.exit(0)
 
 if args.strength is not None or args.keep_frames is not None:
