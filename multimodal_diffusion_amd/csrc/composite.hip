@@ -99,6 +99,7 @@ int eps_untoken_ddim_audio_f32(const float* eps1, const float* z, const int64_t*
                                const avd_latent_guide* guide);
 int check_latent_guide(const avd_latent_guide* g, int B, int64_t per, const float* out, const float* x0_hist);
 int check_cfg_control(const avd_cfg_control* ctl, int B, int64_t per, const float* out, const float* x0_hist);
+bool overlaps(const float* a, const float* b, int64_t n);
 
 static inline int64_t align_up(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
@@ -648,6 +649,31 @@ static int plan_step(const avd_step_desc* s, StepPlan& p) {
     return AVD_OK;
 }
 
+// How denoise_step and denoise_step_cond begin: the plan, the argument checks, and the workspace carved into the plan's regions
+struct StepWs {
+    StepPlan p;
+    float *X, *tok;      // X: the [2B, N, d] sequence (the cond-only step fills the cond half)
+    void *core_ws, *head_ws;
+    float *ssx, *eps;
+};
+static int open_step(const avd_step_desc* s, const float* z, const float* z_out, const int64_t* t_now, const int64_t* t_prev,
+                     void* workspace, int64_t workspace_bytes, StepWs& ws) {
+    StepPlan& p = ws.p;
+    if (int rc = plan_step(s, p)) return rc;
+    AVD_REQUIRE(z && z_out && t_now && t_prev && s->alpha_bar && s->adapt_w, AVD_EINVAL, "step: null pointer");
+    AVD_REQUIRE(z != z_out, AVD_EINVAL, "step: z_out must not alias z");
+    AVD_REQUIRE(workspace && workspace_bytes >= p.total, AVD_EWORKSPACE, "step: workspace %lld < %lld bytes",
+                (long long)workspace_bytes, (long long)p.total);
+    char* w = static_cast<char*>(workspace);
+    ws.X = reinterpret_cast<float*>(w);
+    ws.tok = reinterpret_cast<float*>(w + p.x2);
+    ws.core_ws = w + p.x2 + p.tok;
+    ws.head_ws = w + p.x2 + p.tok + p.core;
+    ws.ssx = reinterpret_cast<float*>(w + p.x2 + p.tok + p.core + p.head);
+    ws.eps = reinterpret_cast<float*>(w + p.x2 + p.tok + p.core + p.head + p.ss);
+    return AVD_OK;
+}
+
 }  // namespace avd
 
 using namespace avd;
@@ -760,21 +786,11 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
                         const int64_t* t_prev, const float* noise, float* z_out, void* workspace, int64_t workspace_bytes,
                         avd_stream_t stream, const int64_t* t_last = nullptr, float* x0_hist = nullptr,
                         const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr) {
-    StepPlan p;
-    if (int rc = plan_step(s, p)) return rc;
-    AVD_REQUIRE(z && z_out && t_now && t_prev && s->alpha_bar && s->adapt_w, AVD_EINVAL, "step: null pointer");
-    AVD_REQUIRE(z != z_out, AVD_EINVAL, "step: z_out must not alias z");
-    AVD_REQUIRE(workspace && workspace_bytes >= p.total, AVD_EWORKSPACE, "step: workspace %lld < %lld bytes",
-                (long long)workspace_bytes, (long long)p.total);
+    StepWs ws;
+    if (int rc = open_step(s, z, z_out, t_now, t_prev, workspace, workspace_bytes, ws)) return rc;
+    auto& [p, X2, tok, core_ws, head_ws, ssx, eps2] = ws;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const avd_embed_desc& e = s->embed;
-    char* w = static_cast<char*>(workspace);
-    float* X2 = reinterpret_cast<float*>(w);
-    float* tok = reinterpret_cast<float*>(w + p.x2);
-    void* core_ws = w + p.x2 + p.tok;
-    void* head_ws = w + p.x2 + p.tok + p.core;
-    float* ssx = reinterpret_cast<float*>(w + p.x2 + p.tok + p.core + p.head);
-    float* eps2 = reinterpret_cast<float*>(w + p.x2 + p.tok + p.core + p.head + p.ss);
     const bool have_ss = !e.temb_add;      // the fused concat front end leaves the rows' sums of squares behind
 
     if (int rc = embed_cfg_pair(&e, z, s->adapt_w, s->adapt_b, t_now, Xp, tok, X2, st, ssx)) return rc;
@@ -823,21 +839,11 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
 static int denoise_step_cond(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp, const int64_t* t_now,
                              const int64_t* t_prev, const float* noise, float* z_out, void* workspace, int64_t workspace_bytes,
                              avd_stream_t stream, const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide) {
-    StepPlan p;
-    if (int rc = plan_step(s, p)) return rc;
-    AVD_REQUIRE(z && z_out && t_now && t_prev && s->alpha_bar && s->adapt_w, AVD_EINVAL, "step: null pointer");
-    AVD_REQUIRE(z != z_out, AVD_EINVAL, "step: z_out must not alias z");
-    AVD_REQUIRE(workspace && workspace_bytes >= p.total, AVD_EWORKSPACE, "step: workspace %lld < %lld bytes",
-                (long long)workspace_bytes, (long long)p.total);
+    StepWs ws;
+    if (int rc = open_step(s, z, z_out, t_now, t_prev, workspace, workspace_bytes, ws)) return rc;
+    auto& [p, X1, tok, core_ws, head_ws, ssx, eps1] = ws;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const avd_embed_desc& e = s->embed;
-    char* w = static_cast<char*>(workspace);
-    float* X1 = reinterpret_cast<float*>(w);
-    float* tok = reinterpret_cast<float*>(w + p.x2);
-    void* core_ws = w + p.x2 + p.tok;
-    void* head_ws = w + p.x2 + p.tok + p.core;
-    float* ssx = reinterpret_cast<float*>(w + p.x2 + p.tok + p.core + p.head);
-    float* eps1 = reinterpret_cast<float*>(w + p.x2 + p.tok + p.core + p.head + p.ss);
     const bool have_ss = !e.temb_add;
 
     if (int rc = embed_cfg_pair(&e, z, s->adapt_w, s->adapt_b, t_now, Xp, tok, X1, st, ssx, true)) return rc;
@@ -852,27 +858,43 @@ static int denoise_step_cond(const avd_step_desc* s, const avd_noise_key* key, c
                                       key, t_last, x0_hist, guide);
 }
 
+// The option checks the step entries share, made here as well as in the fused update's launcher: before the model runs, and for both
+// targets.  need: what this entry cannot do without; a guide, a control or a key it merely accepts is checked when present.  `noise`
+// is the unseeded noise tensor of the one entry that takes one (avd_denoise_step_cond_f32), nullptr from the others.
+enum { NEED_KEY = 1, NEED_HIST = 2, NEED_GUIDE = 4, NEED_CTL = 8 };
+static int check_step_options(const char* what, int need, const avd_step_desc* s, const avd_noise_key* key, const int64_t* t_last,
+                              const float* x0_hist, const float* z, const float* z_out, const avd_latent_guide* g,
+                              const avd_cfg_control* ctl, const float* noise, bool takes_noise = false) {
+    AVD_REQUIRE(s, AVD_EINVAL, "step: null descriptor");
+    const int B = s->embed.B;
+    const int64_t n = (int64_t)B * s->embed.C * s->embed.T * s->embed.H * s->embed.W, per = B > 0 ? n / B : 0;
+    if (ctl || (need & NEED_CTL))
+        if (int rc = check_cfg_control(ctl, B, per, z_out, x0_hist)) return rc;
+    if (g || (need & NEED_GUIDE))
+        if (int rc = check_latent_guide(g, B, per, z_out, x0_hist)) return rc;
+    AVD_REQUIRE(!(need & NEED_HIST) || (t_last && x0_hist), AVD_EINVAL, "%s: null t_last or x0_hist", what);
+    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "%s: t_last and x0_hist go together (the DPM-Solver++(2M) update)", what);
+    if (x0_hist) {
+        AVD_REQUIRE(s->eta == 0.f, AVD_EINVAL, "%s: DPM-Solver++(2M) needs eta == 0 (the SDE variant is not implemented)", what);
+        AVD_REQUIRE(!(z && overlaps(x0_hist, z, n)) && !(z_out && overlaps(x0_hist, z_out, n)), AVD_EINVAL,
+                    "%s: x0_hist must not alias z or z_out", what);
+    }
+    AVD_REQUIRE(key || !(need & NEED_KEY), AVD_EINVAL, "%s: null noise key", what);
+    AVD_REQUIRE(!(noise && key), AVD_EINVAL, "%s: pass a noise tensor or a noise key, not both", what);
+    AVD_REQUIRE(!(noise && g), AVD_EINVAL, "%s: unseeded noise is not supported with a latent guide (pass a noise key)", what);
+    AVD_REQUIRE(s->eta == 0.f || key || noise, AVD_EINVAL, "%s: eta > 0 needs a noise key%s", what,
+                takes_noise && !g ? " or a noise tensor" : " (unseeded noise is not supported here)");
+    if (key)
+        AVD_REQUIRE(key->sample_offset >= 0 && key->sample_offset + (int64_t)B <= ((int64_t)1 << 32), AVD_EINVAL,
+                    "%s: sample_offset %lld + B %d must lie in [0, 2^32]", what, (long long)key->sample_offset, B);
+    return AVD_OK;
+}
+
 extern "C" int avd_denoise_step_cond_f32(const avd_step_desc* s, const avd_latent_guide* g, const avd_noise_key* key,
                                          const int64_t* t_last, float* x0_hist, const float* z, const float* Xp, const int64_t* t_now,
                                          const int64_t* t_prev, const float* noise, float* z_out, void* workspace,
                                          int64_t workspace_bytes, avd_stream_t stream) {
-    AVD_REQUIRE(s, AVD_EINVAL, "step: null descriptor");
-    // checked here as well as in the fused kernel's launcher: before the model runs, and for both targets
-    const int64_t n = (int64_t)s->embed.B * s->embed.C * s->embed.T * s->embed.H * s->embed.W;
-    if (g)
-        if (int rc = check_latent_guide(g, s->embed.B, s->embed.B > 0 ? n / s->embed.B : 0, z_out, x0_hist)) return rc;
-    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "denoise_step_cond: t_last and x0_hist go together (the DPM-Solver++(2M) update)");
-    if (x0_hist) {
-        AVD_REQUIRE(s->eta == 0.f, AVD_EINVAL, "denoise_step_cond: DPM-Solver++(2M) needs eta == 0");
-        AVD_REQUIRE(!(z && x0_hist < z + n && z < x0_hist + n) && !(z_out && x0_hist < z_out + n && z_out < x0_hist + n), AVD_EINVAL,
-                    "denoise_step_cond: x0_hist must not alias z or z_out");
-    }
-    AVD_REQUIRE(!(noise && key), AVD_EINVAL, "denoise_step_cond: pass a noise tensor or a noise key, not both");
-    AVD_REQUIRE(!(noise && g), AVD_EINVAL, "denoise_step_cond: unseeded noise is not supported with a latent guide (pass a noise key)");
-    AVD_REQUIRE(s->eta == 0.f || key || noise, AVD_EINVAL, "denoise_step_cond: eta > 0 needs a noise key%s", g ? "" : " or a noise tensor");
-    if (key)
-        AVD_REQUIRE(key->sample_offset >= 0 && key->sample_offset + (int64_t)s->embed.B <= ((int64_t)1 << 32), AVD_EINVAL,
-                    "denoise_step_cond: sample_offset %lld + B %d must lie in [0, 2^32]", (long long)key->sample_offset, s->embed.B);
+    if (int rc = check_step_options("denoise_step_cond", 0, s, key, t_last, x0_hist, z, z_out, g, nullptr, noise, true)) return rc;
     return denoise_step_cond(s, key, z, Xp, t_now, t_prev, noise, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, g);
 }
 
@@ -885,23 +907,15 @@ extern "C" int avd_denoise_step_f32(const avd_step_desc* s, const float* z, cons
 extern "C" int avd_denoise_step_seeded_f32(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp,
                                            const int64_t* t_now, const int64_t* t_prev, float* z_out, void* workspace,
                                            int64_t workspace_bytes, avd_stream_t stream) {
-    AVD_REQUIRE(s, AVD_EINVAL, "step: null descriptor");
-    AVD_REQUIRE(key, AVD_EINVAL, "denoise_step_seeded: null noise key");
-    AVD_REQUIRE(key->sample_offset >= 0 && key->sample_offset + (int64_t)s->embed.B <= ((int64_t)1 << 32), AVD_EINVAL,
-                "denoise_step_seeded: sample_offset %lld + B %d must lie in [0, 2^32]", (long long)key->sample_offset, s->embed.B);
+    if (int rc = check_step_options("denoise_step_seeded", NEED_KEY, s, key, nullptr, nullptr, z, z_out, nullptr, nullptr, nullptr)) return rc;
     return denoise_step(s, key, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int avd_denoise_step_dpmpp_2m_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_last,
                                              const int64_t* t_now, const int64_t* t_prev, float* x0_hist, float* z_out, void* workspace,
                                              int64_t workspace_bytes, avd_stream_t stream) {
-    AVD_REQUIRE(s, AVD_EINVAL, "step: null descriptor");
-    AVD_REQUIRE(t_last && x0_hist, AVD_EINVAL, "denoise_step_dpmpp_2m: null t_last or x0_hist");
-    AVD_REQUIRE(s->eta == 0.f, AVD_EINVAL, "denoise_step_dpmpp_2m: eta must be 0 (the SDE variant is not implemented)");
-    // checked here as well as in the fused kernel's launcher: before the model runs, and for both targets
-    const int64_t n = (int64_t)s->embed.B * s->embed.C * s->embed.T * s->embed.H * s->embed.W;
-    AVD_REQUIRE(!(z && x0_hist < z + n && z < x0_hist + n) && !(z_out && x0_hist < z_out + n && z_out < x0_hist + n), AVD_EINVAL,
-                "denoise_step_dpmpp_2m: x0_hist must not alias z or z_out");
+    if (int rc = check_step_options("denoise_step_dpmpp_2m", NEED_HIST, s, nullptr, t_last, x0_hist, z, z_out, nullptr, nullptr, nullptr))
+        return rc;
     return denoise_step(s, nullptr, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist);
 }
 
@@ -909,20 +923,7 @@ extern "C" int avd_denoise_step_guided_f32(const avd_step_desc* s, const avd_lat
                                            const int64_t* t_last, float* x0_hist, const float* z, const float* Xp, const int64_t* t_now,
                                            const int64_t* t_prev, float* z_out, void* workspace, int64_t workspace_bytes,
                                            avd_stream_t stream) {
-    AVD_REQUIRE(s, AVD_EINVAL, "step: null descriptor");
-    // checked here as well as in the fused kernel's launcher: before the model runs, and for both targets
-    const int64_t n = (int64_t)s->embed.B * s->embed.C * s->embed.T * s->embed.H * s->embed.W;
-    if (int rc = check_latent_guide(g, s->embed.B, s->embed.B > 0 ? n / s->embed.B : 0, z_out, x0_hist)) return rc;
-    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "denoise_step_guided: t_last and x0_hist go together (the DPM-Solver++(2M) update)");
-    if (x0_hist) {
-        AVD_REQUIRE(s->eta == 0.f, AVD_EINVAL, "denoise_step_guided: DPM-Solver++(2M) needs eta == 0");
-        AVD_REQUIRE(!(z && x0_hist < z + n && z < x0_hist + n) && !(z_out && x0_hist < z_out + n && z_out < x0_hist + n), AVD_EINVAL,
-                    "denoise_step_guided: x0_hist must not alias z or z_out");
-    }
-    AVD_REQUIRE(s->eta == 0.f || key, AVD_EINVAL, "denoise_step_guided: eta > 0 needs a noise key (unseeded noise is not supported with a guide)");
-    if (key)
-        AVD_REQUIRE(key->sample_offset >= 0 && key->sample_offset + (int64_t)s->embed.B <= ((int64_t)1 << 32), AVD_EINVAL,
-                    "denoise_step_guided: sample_offset %lld + B %d must lie in [0, 2^32]", (long long)key->sample_offset, s->embed.B);
+    if (int rc = check_step_options("denoise_step_guided", NEED_GUIDE, s, key, t_last, x0_hist, z, z_out, g, nullptr, nullptr)) return rc;
     return denoise_step(s, key, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, g);
 }
 
@@ -930,23 +931,7 @@ extern "C" int avd_denoise_step_cfg_f32(const avd_step_desc* s, const avd_cfg_co
                                         const avd_noise_key* key, const int64_t* t_last, float* x0_hist, const float* z, const float* Xp,
                                         const int64_t* t_now, const int64_t* t_prev, float* z_out, void* workspace,
                                         int64_t workspace_bytes, avd_stream_t stream) {
-    AVD_REQUIRE(s, AVD_EINVAL, "step: null descriptor");
-    // checked here as well as in the fused kernel's launcher: before the model runs, and for both targets
-    const int64_t n = (int64_t)s->embed.B * s->embed.C * s->embed.T * s->embed.H * s->embed.W;
-    const int64_t per = s->embed.B > 0 ? n / s->embed.B : 0;
-    if (int rc = check_cfg_control(ctl, s->embed.B, per, z_out, x0_hist)) return rc;
-    if (g)
-        if (int rc = check_latent_guide(g, s->embed.B, per, z_out, x0_hist)) return rc;
-    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "denoise_step_cfg: t_last and x0_hist go together (the DPM-Solver++(2M) update)");
-    if (x0_hist) {
-        AVD_REQUIRE(s->eta == 0.f, AVD_EINVAL, "denoise_step_cfg: DPM-Solver++(2M) needs eta == 0");
-        AVD_REQUIRE(!(z && x0_hist < z + n && z < x0_hist + n) && !(z_out && x0_hist < z_out + n && z_out < x0_hist + n), AVD_EINVAL,
-                    "denoise_step_cfg: x0_hist must not alias z or z_out");
-    }
-    AVD_REQUIRE(s->eta == 0.f || key, AVD_EINVAL, "denoise_step_cfg: eta > 0 needs a noise key (unseeded noise is not supported here)");
-    if (key)
-        AVD_REQUIRE(key->sample_offset >= 0 && key->sample_offset + (int64_t)s->embed.B <= ((int64_t)1 << 32), AVD_EINVAL,
-                    "denoise_step_cfg: sample_offset %lld + B %d must lie in [0, 2^32]", (long long)key->sample_offset, s->embed.B);
+    if (int rc = check_step_options("denoise_step_cfg", NEED_CTL, s, key, t_last, x0_hist, z, z_out, g, ctl, nullptr)) return rc;
     return denoise_step(s, key, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, g, ctl);
 }
 

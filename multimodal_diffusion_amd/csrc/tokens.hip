@@ -289,6 +289,14 @@ struct DpmState {
 // not read.  It excludes a CfgState (per-sample guidance and rescale act on the combine: with y = c the rescale is the identity).
 struct CondOnly {};
 template <class T, class... X> struct PackHas { static constexpr bool value = (std::is_same<T, X>::value || ...); };
+struct GuideState;
+struct CfgState;
+// a well-formed pack: one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState or CondOnly
+template <bool SEEDED, class... X> struct PackOk {
+    template <class T> static constexpr int n = PackHas<T, X...>::value ? 1 : 0;
+    static constexpr bool value = sizeof...(X) == (SEEDED ? 1 : 0) + n<DpmState> + n<GuideState> + n<CfgState> + n<CondOnly> &&
+                                  !(SEEDED && n<DpmState>) && !(n<CfgState> && n<CondOnly>);
+};
 template <class T, class A, class... R> __device__ __forceinline__ T pack_get(const A& a, const R&... r) {
     if constexpr (std::is_same<T, A>::value) return a;
     else return pack_get<T>(r...);
@@ -389,7 +397,7 @@ int ddim_step_f32(const float* x_t, const float* eps, const int64_t* t_now, cons
 }
 
 // true when [a, a + n) and [b, b + n) overlap (n floats each)
-static bool overlaps(const float* a, const float* b, int64_t n) { return a < b + n && b < a + n; }
+bool overlaps(const float* a, const float* b, int64_t n) { return a < b + n && b < a + n; }
 
 __global__ __launch_bounds__(256) void dpmpp_2m_kernel(const float* __restrict__ x, const float* __restrict__ eps,
                                                        float* __restrict__ x0_hist, const int64_t* __restrict__ t_last,
@@ -764,9 +772,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int64_t total4, Key... nk) {
     constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
     constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
-    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) + (CTL ? 1 : 0) + (COND ? 1 : 0) &&
-                      !(SEEDED && DPM) && !(CTL && COND),
-                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState or CondOnly");
+    static_assert(PackOk<SEEDED, Key...>::value, "not a pack of the fused update kernels (see PackOk)");
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total4) return;
     const int64_t per4 = g.per >> 2;
@@ -824,9 +830,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int groups_per_sample, Key... nk) {
     constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
     constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
-    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) + (CTL ? 1 : 0) + (COND ? 1 : 0) &&
-                      !(SEEDED && DPM) && !(CTL && COND),
-                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState or CondOnly");
+    static_assert(PackOk<SEEDED, Key...>::value, "not a pack of the fused update kernels (see PackOk)");
     extern __shared__ __attribute__((aligned(16))) float ebuf[];       // [GT][D + 4]: the pad keeps the transposed 16-byte reads off one bank group
     const int LD = g.D + 4;
     const int b = blockIdx.x / groups_per_sample, grp = blockIdx.x % groups_per_sample;
@@ -890,135 +894,117 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     }
 }
 
-// The guided and controlled launches: the kernels' whole trailing pack P — the solver's state (nothing, NoiseKey or DpmState), then
-// optionally the guide, then optionally the CFG control.
-template <class... P>
-static void launch_unpatch(int rows_gt, int groups, dim3 grid, size_t lds, hipStream_t st, const float* eps2, const float* z,
-                           const int64_t* t_now, const int64_t* t_prev, const float* abar, int T_train, float guidance, float eta,
-                           const float* noise, float* z_out, const Tube& g, int B, int64_t total4, P... p) {
-    constexpr bool SEEDED = PackHas<NoiseKey, P...>::value;
-    if (rows_gt)
-        hipLaunchKernelGGL((rows_gt == 8 ? cfg_unpatch_ddim_rows_kernel<8, SEEDED, P...> : cfg_unpatch_ddim_rows_kernel<4, SEEDED, P...>),
-                           grid, dim3(256), lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, groups, p...);
-    else
-        hipLaunchKernelGGL((cfg_unpatch_ddim_kernel<SEEDED, P...>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train,
-                           guidance, eta, noise, z_out, g, B, total4, p...);
-}
+// ---- the host side of the fused updates, both targets
+// the arguments every fused update kernel starts with
+struct UpdateArgs {
+    const float *eps, *z;      // eps: cond / null [2B, Nt, D], or the cond rows alone [B, Nt, D] (the single-branch form)
+    const int64_t *t_now, *t_prev;
+    const float* abar;
+    int T_train;
+    float guidance, eta;       // guidance: not read by the single-branch form
+    const float* noise;
+    float* z_out;
+    int B;
+};
+// what the kernels' trailing pack is made of: filled by check_fused_update, read by with_update_pack
+struct UpdateKeys {
+    bool dpm, seeded, guide, ctl;
+    DpmState ds;
+    NoiseKey nk;
+    GuideState gs;
+    CfgState cs;
+};
 
+// The checks the four launchers share, all before any HIP call.  per: the values of one sample's latent.
 // key != nullptr with eta > 0: the noise term is drawn from the seeded stream inside the kernel (`noise` is not read); eta == 0 ignores both
 // x0_hist != nullptr: the DPM-Solver++(2M) update (needs eta == 0 and t_last) instead of DDIM; x0_hist must not overlap z or z_out
 // guide != nullptr: the latent guide's blend ends the update (after either solver), right before z_out is stored
-// ctl != nullptr: per-sample guidance and / or rescale (avd_cfg_control); with rescale set the statistics pass runs first on st
+// ctl != nullptr: per-sample guidance and / or rescale (avd_cfg_control); with rescale set the launcher runs the statistics pass first
+static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per, const avd_noise_key* key, const int64_t* t_last,
+                              float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl, UpdateKeys& k) {
+    AVD_REQUIRE(a.eps && a.z && a.t_now && a.t_prev && a.abar && a.z_out, AVD_EINVAL, "%s: null pointer", what);
+    AVD_REQUIRE(a.eta >= 0.f && (a.eta == 0.f || a.noise || key), AVD_EINVAL, "%s: eta > 0 needs a noise tensor or a noise key", what);
+    AVD_REQUIRE(a.z != a.z_out, AVD_EINVAL, "%s: z_out must not alias z", what);
+    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "%s: t_last and x0_hist go together (the DPM-Solver++(2M) update)", what);
+    k = UpdateKeys{};
+    k.dpm = x0_hist != nullptr;
+    k.ds = DpmState{t_last, x0_hist};
+    if (k.dpm) {
+        AVD_REQUIRE(a.eta == 0.f, AVD_EINVAL, "%s: the DPM-Solver++(2M) update needs eta == 0", what);
+        AVD_REQUIRE(!overlaps(x0_hist, a.z, a.B * per) && !overlaps(x0_hist, a.z_out, a.B * per), AVD_EINVAL,
+                    "%s: x0_hist must not overlap z or z_out", what);
+    }
+    k.seeded = key && a.eta > 0.f;
+    if (k.seeded) {
+        if (int rc = make_noise_key(key, a.B, k.nk)) return rc;
+        AVD_REQUIRE(per < ((int64_t)1 << 34), AVD_EINVAL, "%s: a seeded sample must hold < 2^34 values", what);
+    }
+    k.guide = guide != nullptr;
+    k.ctl = ctl != nullptr;
+    if (guide || ctl)
+        AVD_REQUIRE(a.eta == 0.f || k.seeded, AVD_EINVAL, "%s: a guided or controlled step with eta > 0 needs a noise key", what);
+    if (guide)
+        if (int rc = make_guide(guide, a.B, per, a.z_out, x0_hist, k.gs)) return rc;
+    if (ctl)
+        if (int rc = make_cfg(ctl, a.B, per, a.z_out, x0_hist, k.cs)) return rc;
+    return AVD_OK;
+}
+
+// Calls launch(pack...) with the kernels' whole trailing pack: the solver's state (DpmState, the NoiseKey of a seeded eta > 0 step, or
+// nothing), then the guide if there is one, then the CFG control if there is one or, for the single-branch form, the CondOnly tag.
+template <class F>
+static void with_update_pack(const UpdateKeys& k, bool cond_only, F launch) {
+    auto tail = [&](auto... state) {
+        if (cond_only && k.guide) launch(state..., k.gs, CondOnly{});
+        else if (cond_only) launch(state..., CondOnly{});
+        else if (k.guide && k.ctl) launch(state..., k.gs, k.cs);
+        else if (k.guide) launch(state..., k.gs);
+        else if (k.ctl) launch(state..., k.cs);
+        else launch(state...);
+    };
+    if (k.dpm) tail(k.ds);
+    else if (k.seeded) tail(k.nk);
+    else tail();
+}
+
+// the video launch for one pack: the whole-line kernel where the geometry allows it, the gather form otherwise
+template <class... P>
+static void launch_unpatch(const UpdateArgs& a, const Tube& g, hipStream_t st, P... p) {
+    constexpr bool SEEDED = PackHas<NoiseKey, P...>::value;
+    // whole-line form: groups of tokens along w' that make up 128 bytes (or the whole row when W is shorter) of latent per (c, t, h)
+    const int gt = (g.W < 32 ? g.W : 32) / g.w;
+    if (g_cfg_rows && (gt == 8 || gt == 4) && g.Wt % gt == 0 && g.D % 4 == 0 && (int64_t)gt * (g.D + 4) * 4 <= 64 * 1024) {
+        const int groups = (int)(g.per / g.D) / gt;
+        hipLaunchKernelGGL((gt == 8 ? cfg_unpatch_ddim_rows_kernel<8, SEEDED, P...> : cfg_unpatch_ddim_rows_kernel<4, SEEDED, P...>),
+                           dim3((unsigned)(a.B * groups)), dim3(256), (size_t)gt * (g.D + 4) * 4, st, a.eps, a.z, a.t_now, a.t_prev, a.abar,
+                           a.T_train, a.guidance, a.eta, a.noise, a.z_out, g, a.B, groups, p...);
+    } else {
+        const int64_t total4 = (int64_t)a.B * (g.per >> 2);
+        hipLaunchKernelGGL((cfg_unpatch_ddim_kernel<SEEDED, P...>), dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, a.eps, a.z,
+                           a.t_now, a.t_prev, a.abar, a.T_train, a.guidance, a.eta, a.noise, a.z_out, g, a.B, total4, p...);
+    }
+}
+
+// key, t_last / x0_hist, guide, ctl: see check_fused_update; with ctl->rescale set the statistics pass runs first, on st
 int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key,
                          const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl) {
-    AVD_REQUIRE(eps2 && z && t_now && t_prev && abar && z_out, AVD_EINVAL, "cfg_unpatch_ddim: null pointer");
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "cfg_unpatch_ddim: bad dims");
-    AVD_REQUIRE(eta >= 0.f && (eta == 0.f || noise || key), AVD_EINVAL, "cfg_unpatch_ddim: eta > 0 needs a noise tensor or a noise key");
-    AVD_REQUIRE(z != z_out, AVD_EINVAL, "cfg_unpatch_ddim: z_out must not alias z");
     Tube g;
     if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
-    const bool dpm = x0_hist != nullptr;
-    if (dpm) {
-        AVD_REQUIRE(t_last && eta == 0.f, AVD_EINVAL, "cfg_unpatch_dpmpp_2m: needs t_last and eta == 0");
-        AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "cfg_unpatch_dpmpp_2m: x0_hist must be 16-byte aligned");
-        AVD_REQUIRE(!overlaps(x0_hist, z, (int64_t)B * g.per) && !overlaps(x0_hist, z_out, (int64_t)B * g.per), AVD_EINVAL,
-                    "cfg_unpatch_dpmpp_2m: x0_hist must not overlap z or z_out");
-    }
-    const bool seeded = key && eta > 0.f;
-    NoiseKey nk{0u, 0u, 0u};
-    if (seeded) {
-        if (int rc = make_noise_key(key, B, nk)) return rc;
-        AVD_REQUIRE(g.per < ((int64_t)1 << 34), AVD_EINVAL, "cfg_unpatch_ddim: a seeded sample must hold < 2^34 values");
-    }
-    GuideState gs{};
-    if (guide) {
-        AVD_REQUIRE(eta == 0.f || seeded, AVD_EINVAL, "cfg_unpatch_ddim: a guided step with eta > 0 needs a noise key");
-        if (int rc = make_guide(guide, B, g.per, z_out, x0_hist, gs)) return rc;
-    }
-    CfgState cs{};
-    if (ctl) {
-        AVD_REQUIRE(eta == 0.f || seeded, AVD_EINVAL, "cfg_unpatch_ddim: a controlled step with eta > 0 needs a noise key");
-        if (int rc = make_cfg(ctl, B, g.per, z_out, x0_hist, cs)) return rc;
-        AVD_REQUIRE(!ctl->rescale || (aligned16(eps2) && aligned16(eps2 + (int64_t)B * g.per)), AVD_EUNSUPPORTED,
+    AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "cfg_unpatch_ddim: x0_hist must be 16-byte aligned");
+    const UpdateArgs a{eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, B};
+    UpdateKeys k;
+    if (int rc = check_fused_update("cfg_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, ctl, k)) return rc;
+    if (ctl && ctl->rescale) {
+        AVD_REQUIRE(aligned16(eps2) && aligned16(eps2 + (int64_t)B * g.per), AVD_EUNSUPPORTED,
                     "cfg_unpatch_ddim: the statistics pass reads 16-byte aligned token rows");
-        if (ctl->rescale)
-            if (int rc = run_cfg_stats<CFG_SRC_VIDEO>(ctl, eps2, eps2 + (int64_t)B * g.per, g.per, guidance, B, g.per, AudioGeom{}, st))
-                return rc;
+        if (int rc = run_cfg_stats<CFG_SRC_VIDEO>(ctl, eps2, eps2 + (int64_t)B * g.per, g.per, guidance, B, g.per, AudioGeom{}, st)) return rc;
     }
-    const int64_t total4 = (int64_t)B * (g.per >> 2);
     static const int tag = prof_tag_id("cfg_unpatch_ddim_kernel");
     ProfScope prof(tag, 16.0 * (double)B * g.per, st);
-    // whole-line form: groups of tokens along w' that make up 128 bytes (or the whole row when W is shorter) of latent per (c, t, h)
-    const int gt = (g.W < 32 ? g.W : 32) / g.w;
-    const bool rows = g_cfg_rows && (gt == 8 || gt == 4) && g.Wt % gt == 0 && g.D % 4 == 0 && (int64_t)gt * (g.D + 4) * 4 <= 64 * 1024;
-    if (ctl) {
-        const int groups = rows ? (int)(g.per / g.D) / gt : 0;
-        const size_t lds = rows ? (size_t)gt * (g.D + 4) * 4 : 0;
-        const dim3 grid(rows ? (unsigned)(B * groups) : (unsigned)((total4 + 255) / 256));
-        const int rgt = rows ? gt : 0;
-        // the solver's state, then the tail (guide and / or control)
-        auto go = [&](auto... tail) {
-            if (dpm)
-                launch_unpatch(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
-                               DpmState{t_last, x0_hist}, tail...);
-            else if (seeded)
-                launch_unpatch(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
-                               nk, tail...);
-            else
-                launch_unpatch(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
-                               tail...);
-        };
-        if (guide) go(gs, cs);
-        else go(cs);
-        AVD_CHECK_LAUNCH("cfg_unpatch_ddim (controlled)");
-        return AVD_OK;
-    }
-    if (guide) {
-        const int groups = rows ? (int)(g.per / g.D) / gt : 0;
-        const size_t lds = rows ? (size_t)gt * (g.D + 4) * 4 : 0;
-        const dim3 grid(rows ? (unsigned)(B * groups) : (unsigned)((total4 + 255) / 256));
-        const int rgt = rows ? gt : 0;
-        if (dpm)
-            launch_unpatch(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
-                           DpmState{t_last, x0_hist}, gs);
-        else if (seeded)
-            launch_unpatch(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
-                           nk, gs);
-        else
-            launch_unpatch(rgt, groups, grid, lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, total4,
-                           gs);
-        AVD_CHECK_LAUNCH("cfg_unpatch_ddim (guided)");
-        return AVD_OK;
-    }
-    if (rows) {
-        const int groups = (int)(g.per / g.D) / gt;
-        const size_t lds = (size_t)gt * (g.D + 4) * 4;
-        const dim3 grid((unsigned)(B * groups));
-        if (dpm)
-            hipLaunchKernelGGL((gt == 8 ? cfg_unpatch_ddim_rows_kernel<8, false, DpmState> : cfg_unpatch_ddim_rows_kernel<4, false, DpmState>),
-                               grid, dim3(256), lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, groups,
-                               DpmState{t_last, x0_hist});
-        else if (seeded)
-            hipLaunchKernelGGL((gt == 8 ? cfg_unpatch_ddim_rows_kernel<8, true, NoiseKey> : cfg_unpatch_ddim_rows_kernel<4, true, NoiseKey>), grid,
-                               dim3(256), lds, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, groups, nk);
-        else
-            hipLaunchKernelGGL((gt == 8 ? cfg_unpatch_ddim_rows_kernel<8, false> : cfg_unpatch_ddim_rows_kernel<4, false>), grid, dim3(256), lds,
-                               st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, g, B, groups);
-        AVD_CHECK_LAUNCH("cfg_unpatch_ddim (rows)");
-        return AVD_OK;
-    }
-    const dim3 grid((unsigned)((total4 + 255) / 256));
-    if (dpm)
-        hipLaunchKernelGGL((cfg_unpatch_ddim_kernel<false, DpmState>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train,
-                           guidance, eta, noise, z_out, g, B, total4, DpmState{t_last, x0_hist});
-    else if (seeded)
-        hipLaunchKernelGGL((cfg_unpatch_ddim_kernel<true, NoiseKey>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train, guidance,
-                           eta, noise, z_out, g, B, total4, nk);
-    else
-        hipLaunchKernelGGL(cfg_unpatch_ddim_kernel<false>, grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train, guidance, eta,
-                           noise, z_out, g, B, total4);
+    with_update_pack(k, false, [&](auto... p) { launch_unpatch(a, g, st, p...); });
     AVD_CHECK_LAUNCH("cfg_unpatch_ddim");
     return AVD_OK;
 }
@@ -1028,54 +1014,16 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
 int eps_unpatch_ddim_f32(const float* eps1, const float* z, const int64_t* t_now, const int64_t* t_prev, const float* abar, int T_train,
                          float eta, const float* noise, float* z_out, int B, int C, int T, int H, int W, int t, int h, int w,
                          hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide) {
-    AVD_REQUIRE(eps1 && z && t_now && t_prev && abar && z_out, AVD_EINVAL, "eps_unpatch_ddim: null pointer");
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "eps_unpatch_ddim: bad dims");
-    AVD_REQUIRE(eta >= 0.f && (eta == 0.f || noise || key), AVD_EINVAL, "eps_unpatch_ddim: eta > 0 needs a noise tensor or a noise key");
-    AVD_REQUIRE(z != z_out, AVD_EINVAL, "eps_unpatch_ddim: z_out must not alias z");
-    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "eps_unpatch_ddim: t_last and x0_hist go together (the DPM-Solver++(2M) update)");
     Tube g;
     if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
-    const bool dpm = x0_hist != nullptr;
-    if (dpm) {
-        AVD_REQUIRE(eta == 0.f, AVD_EINVAL, "eps_unpatch_dpmpp_2m: needs eta == 0");
-        AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "eps_unpatch_dpmpp_2m: x0_hist must be 16-byte aligned");
-        AVD_REQUIRE(!overlaps(x0_hist, z, (int64_t)B * g.per) && !overlaps(x0_hist, z_out, (int64_t)B * g.per), AVD_EINVAL,
-                    "eps_unpatch_dpmpp_2m: x0_hist must not overlap z or z_out");
-    }
-    const bool seeded = key && eta > 0.f;
-    NoiseKey nk{0u, 0u, 0u};
-    if (seeded) {
-        if (int rc = make_noise_key(key, B, nk)) return rc;
-        AVD_REQUIRE(g.per < ((int64_t)1 << 34), AVD_EINVAL, "eps_unpatch_ddim: a seeded sample must hold < 2^34 values");
-    }
-    GuideState gs{};
-    if (guide) {
-        AVD_REQUIRE(eta == 0.f || seeded, AVD_EINVAL, "eps_unpatch_ddim: a guided step with eta > 0 needs a noise key");
-        if (int rc = make_guide(guide, B, g.per, z_out, x0_hist, gs)) return rc;
-    }
-    const int64_t total4 = (int64_t)B * (g.per >> 2);
+    AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "eps_unpatch_ddim: x0_hist must be 16-byte aligned");
+    const UpdateArgs a{eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, B};
+    UpdateKeys k;
+    if (int rc = check_fused_update("eps_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, nullptr, k)) return rc;
     static const int tag = prof_tag_id("eps_unpatch_ddim_kernel");
     ProfScope prof(tag, 12.0 * (double)B * g.per, st);
-    const int gt = (g.W < 32 ? g.W : 32) / g.w;      // as cfg_unpatch_ddim_f32
-    const bool rows = g_cfg_rows && (gt == 8 || gt == 4) && g.Wt % gt == 0 && g.D % 4 == 0 && (int64_t)gt * (g.D + 4) * 4 <= 64 * 1024;
-    const int groups = rows ? (int)(g.per / g.D) / gt : 0;
-    const size_t lds = rows ? (size_t)gt * (g.D + 4) * 4 : 0;
-    const dim3 grid(rows ? (unsigned)(B * groups) : (unsigned)((total4 + 255) / 256));
-    const int rgt = rows ? gt : 0;
-    // the solver's state, then the tail (the guide, if any, and the tag)
-    auto go = [&](auto... tail) {
-        if (dpm)
-            launch_unpatch(rgt, groups, grid, lds, st, eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, g, B, total4,
-                           DpmState{t_last, x0_hist}, tail...);
-        else if (seeded)
-            launch_unpatch(rgt, groups, grid, lds, st, eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, g, B, total4, nk,
-                           tail...);
-        else
-            launch_unpatch(rgt, groups, grid, lds, st, eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, g, B, total4,
-                           tail...);
-    };
-    if (guide) go(gs, CondOnly{});
-    else go(CondOnly{});
+    with_update_pack(k, true, [&](auto... p) { launch_unpatch(a, g, st, p...); });
     AVD_CHECK_LAUNCH("eps_unpatch_ddim");
     return AVD_OK;
 }
@@ -1089,9 +1037,7 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
                                               int F, int len, int stride, int Na, Key... nk) {
     constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
     constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
-    static_assert(sizeof...(Key) == (SEEDED ? 1 : 0) + (DPM ? 1 : 0) + (GUIDED ? 1 : 0) + (CTL ? 1 : 0) + (COND ? 1 : 0) &&
-                      !(SEEDED && DPM) && !(CTL && COND),
-                  "one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState or CondOnly");
+    static_assert(PackOk<SEEDED, Key...>::value, "not a pack of the fused update kernels (see PackOk)");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)B * Ca * F) return;
     const int f = (int)(i % F);
@@ -1149,80 +1095,32 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
     }
 }
 
+template <class... P>
+static void launch_untoken(const UpdateArgs& a, const AudioGeom& ag, hipStream_t st, P... p) {
+    constexpr bool SEEDED = PackHas<NoiseKey, P...>::value;
+    const int64_t n = (int64_t)a.B * ag.Ca * ag.F;
+    hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<SEEDED, P...>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.eps, a.z,
+                       a.t_now, a.t_prev, a.abar, a.T_train, a.guidance, a.eta, a.noise, a.z_out, a.B, ag.Ca, ag.F, ag.len, ag.stride,
+                       ag.Na, p...);
+}
+
 // key, t_last, x0_hist, guide, ctl: as cfg_unpatch_ddim_f32
 int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st, const avd_noise_key* key,
                                const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl) {
-    AVD_REQUIRE(eps2 && z && t_now && t_prev && abar && z_out, AVD_EINVAL, "cfg_untoken_ddim_audio: null pointer");
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "cfg_untoken_ddim_audio: bad chunking");
-    AVD_REQUIRE(eta >= 0.f && (eta == 0.f || noise || key), AVD_EINVAL, "cfg_untoken_ddim_audio: eta > 0 needs noise or a noise key");
-    AVD_REQUIRE(z != z_out, AVD_EINVAL, "cfg_untoken_ddim_audio: z_out must not alias z");
-    const bool dpm = x0_hist != nullptr;
-    if (dpm) {
-        AVD_REQUIRE(t_last && eta == 0.f, AVD_EINVAL, "cfg_untoken_dpmpp_2m_audio: needs t_last and eta == 0");
-        AVD_REQUIRE(!overlaps(x0_hist, z, (int64_t)B * Ca * F) && !overlaps(x0_hist, z_out, (int64_t)B * Ca * F), AVD_EINVAL,
-                    "cfg_untoken_dpmpp_2m_audio: x0_hist must not overlap z or z_out");
+    const UpdateArgs a{eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, B};
+    const int64_t per = (int64_t)Ca * F;
+    UpdateKeys k;
+    if (int rc = check_fused_update("cfg_untoken_ddim_audio", a, per, key, t_last, x0_hist, guide, ctl, k)) return rc;
+    const AudioGeom ag{Ca, F, len, stride, audio_na(F, len, stride)};
+    if (ctl && ctl->rescale) {
+        const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
+        if (int rc = run_cfg_stats<CFG_SRC_AUDIO>(ctl, eps2, eps2 + B * half, half, guidance, B, per, ag, st)) return rc;
     }
-    const bool seeded = key && eta > 0.f;
-    NoiseKey nk{0u, 0u, 0u};
-    if (seeded)
-        if (int rc = make_noise_key(key, B, nk)) return rc;
-    const int Na = audio_na(F, len, stride);
-    const int64_t n = (int64_t)B * Ca * F;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (ctl) {
-        AVD_REQUIRE(eta == 0.f || seeded, AVD_EINVAL, "cfg_untoken_ddim_audio: a controlled step with eta > 0 needs a noise key");
-        CfgState cs;
-        if (int rc = make_cfg(ctl, B, (int64_t)Ca * F, z_out, x0_hist, cs)) return rc;
-        GuideState gs{};
-        if (guide)
-            if (int rc = make_guide(guide, B, (int64_t)Ca * F, z_out, x0_hist, gs)) return rc;
-        if (ctl->rescale)
-            if (int rc = run_cfg_stats<CFG_SRC_AUDIO>(ctl, eps2, eps2 + (int64_t)B * Na * Ca * len, (int64_t)Na * Ca * len, guidance, B,
-                                                      (int64_t)Ca * F, AudioGeom{Ca, F, len, stride, Na}, st))
-                return rc;
-        auto launch = [&](auto... p) {
-            constexpr bool SEEDED = PackHas<NoiseKey, decltype(p)...>::value;
-            hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<SEEDED, decltype(p)...>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar,
-                               T_train, guidance, eta, noise, z_out, B, Ca, F, len, stride, Na, p...);
-        };
-        auto go = [&](auto... tail) {
-            if (dpm) launch(DpmState{t_last, x0_hist}, tail...);
-            else if (seeded) launch(nk, tail...);
-            else launch(tail...);
-        };
-        if (guide) go(gs, cs);
-        else go(cs);
-        AVD_CHECK_LAUNCH("cfg_untoken_ddim_audio (controlled)");
-        return AVD_OK;
-    }
-    if (guide) {
-        AVD_REQUIRE(eta == 0.f || seeded, AVD_EINVAL, "cfg_untoken_ddim_audio: a guided step with eta > 0 needs a noise key");
-        GuideState gs;
-        if (int rc = make_guide(guide, B, (int64_t)Ca * F, z_out, x0_hist, gs)) return rc;
-        if (dpm)
-            hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<false, DpmState, GuideState>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev,
-                               abar, T_train, guidance, eta, noise, z_out, B, Ca, F, len, stride, Na, DpmState{t_last, x0_hist}, gs);
-        else if (seeded)
-            hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<true, NoiseKey, GuideState>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev,
-                               abar, T_train, guidance, eta, noise, z_out, B, Ca, F, len, stride, Na, nk, gs);
-        else
-            hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<false, GuideState>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar,
-                               T_train, guidance, eta, noise, z_out, B, Ca, F, len, stride, Na, gs);
-        AVD_CHECK_LAUNCH("cfg_untoken_ddim_audio (guided)");
-        return AVD_OK;
-    }
-    if (dpm)
-        hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<false, DpmState>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train,
-                           guidance, eta, noise, z_out, B, Ca, F, len, stride, Na, DpmState{t_last, x0_hist});
-    else if (seeded)
-        hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<true, NoiseKey>), grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train,
-                           guidance, eta, noise, z_out, B, Ca, F, len, stride, Na, nk);
-    else
-        hipLaunchKernelGGL(cfg_untoken_ddim_audio_kernel<false>, grid, dim3(256), 0, st, eps2, z, t_now, t_prev, abar, T_train, guidance,
-                           eta, noise, z_out, B, Ca, F, len, stride, Na);
+    with_update_pack(k, false, [&](auto... p) { launch_untoken(a, ag, st, p...); });
     AVD_CHECK_LAUNCH("cfg_untoken_ddim_audio");
     return AVD_OK;
 }
@@ -1232,42 +1130,13 @@ int eps_untoken_ddim_audio_f32(const float* eps1, const float* z, const int64_t*
                                int T_train, float eta, const float* noise, float* z_out, int B, int Ca, int F, int len, int stride,
                                hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist,
                                const avd_latent_guide* guide) {
-    AVD_REQUIRE(eps1 && z && t_now && t_prev && abar && z_out, AVD_EINVAL, "eps_untoken_ddim_audio: null pointer");
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "eps_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "eps_untoken_ddim_audio: bad chunking");
-    AVD_REQUIRE(eta >= 0.f && (eta == 0.f || noise || key), AVD_EINVAL, "eps_untoken_ddim_audio: eta > 0 needs noise or a noise key");
-    AVD_REQUIRE(z != z_out, AVD_EINVAL, "eps_untoken_ddim_audio: z_out must not alias z");
-    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "eps_untoken_ddim_audio: t_last and x0_hist go together (the DPM-Solver++(2M) update)");
-    const int64_t n = (int64_t)B * Ca * F;
-    const bool dpm = x0_hist != nullptr;
-    if (dpm) {
-        AVD_REQUIRE(eta == 0.f, AVD_EINVAL, "eps_untoken_dpmpp_2m_audio: needs eta == 0");
-        AVD_REQUIRE(!overlaps(x0_hist, z, n) && !overlaps(x0_hist, z_out, n), AVD_EINVAL,
-                    "eps_untoken_dpmpp_2m_audio: x0_hist must not overlap z or z_out");
-    }
-    const bool seeded = key && eta > 0.f;
-    NoiseKey nk{0u, 0u, 0u};
-    if (seeded)
-        if (int rc = make_noise_key(key, B, nk)) return rc;
-    GuideState gs{};
-    if (guide) {
-        AVD_REQUIRE(eta == 0.f || seeded, AVD_EINVAL, "eps_untoken_ddim_audio: a guided step with eta > 0 needs a noise key");
-        if (int rc = make_guide(guide, B, (int64_t)Ca * F, z_out, x0_hist, gs)) return rc;
-    }
-    const int Na = audio_na(F, len, stride);
-    const dim3 grid((unsigned)((n + 255) / 256));
-    auto launch = [&](auto... p) {
-        constexpr bool SEEDED = PackHas<NoiseKey, decltype(p)...>::value;
-        hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<SEEDED, decltype(p)...>), grid, dim3(256), 0, st, eps1, z, t_now, t_prev, abar,
-                           T_train, 0.f, eta, noise, z_out, B, Ca, F, len, stride, Na, p...);
-    };
-    auto go = [&](auto... tail) {
-        if (dpm) launch(DpmState{t_last, x0_hist}, tail...);
-        else if (seeded) launch(nk, tail...);
-        else launch(tail...);
-    };
-    if (guide) go(gs, CondOnly{});
-    else go(CondOnly{});
+    const UpdateArgs a{eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, B};
+    UpdateKeys k;
+    if (int rc = check_fused_update("eps_untoken_ddim_audio", a, (int64_t)Ca * F, key, t_last, x0_hist, guide, nullptr, k)) return rc;
+    const AudioGeom ag{Ca, F, len, stride, audio_na(F, len, stride)};
+    with_update_pack(k, true, [&](auto... p) { launch_untoken(a, ag, st, p...); });
     AVD_CHECK_LAUNCH("eps_untoken_ddim_audio");
     return AVD_OK;
 }

@@ -574,45 +574,17 @@ class DenoiseEngine:
                                                      self._cons_hop, inner, L.stream_ptr(self.device)))
         return out
 
-    def _step_kind(self, z, tn, tp, noise, out, t_last, cond_only) -> torch.Tensor:
-        """the step proper: cond-only, guided / CFG-controlled, DPM-Solver++(2M), seeded or plain DDIM"""
-        if cond_only:
-            return self._step_cond(z, tn, tp, noise, out, t_last)
-        if self._guide is not None or self._ctl is not None:
-            return self._step_guided(z, tn, tp, noise, out, t_last)
-        if self.solver == "dpmpp_2m":
-            if noise is not None:
-                raise ValueError("solver 'dpmpp_2m' is deterministic: it takes no noise")
-            h = self.x0_hist
-            for name, t in (("z", z), ("out", out)):
-                if t.untyped_storage().data_ptr() == h.untyped_storage().data_ptr():
-                    raise L.AvdError(f"{name} must not alias the engine's x0_hist (the solver history)")
-            tl = self._no_hist if t_last is None else L.dev_i64(t_last, self.device)
-            L.check(L.lib().avd_denoise_step_dpmpp_2m_f32(C.byref(self.desc), z.data_ptr(), self.Xp.data_ptr(), tl.data_ptr(),
-                                                          tn.data_ptr(), tp.data_ptr(), h.data_ptr(), out.data_ptr(),
-                                                          self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device)))
-            return out
-        if t_last is not None:
-            raise ValueError("t_last is the multistep solver's history: this engine runs solver 'ddim'")
-        if self._key is not None:
-            if noise is not None:
-                raise ValueError("this engine draws its noise from noise_seed: do not pass `noise` as well")
-            L.check(L.lib().avd_denoise_step_seeded_f32(C.byref(self.desc), C.byref(self._key), z.data_ptr(), self.Xp.data_ptr(),
-                                                        tn.data_ptr(), tp.data_ptr(), out.data_ptr(), self.workspace.data_ptr(),
-                                                        self.workspace.numel(), L.stream_ptr(self.device)))
-            return out
-        if self.eta > 0 and noise is None:
-            noise = torch.randn_like(z)
-        L.check(L.lib().avd_denoise_step_f32(C.byref(self.desc), z.data_ptr(), self.Xp.data_ptr(), tn.data_ptr(),
-                                             tp.data_ptr(), L.ptr(noise), out.data_ptr(), self.workspace.data_ptr(),
-                                             self.workspace.numel(), L.stream_ptr(self.device)))
-        return out
-
-    def _step_guided(self, z, tn, tp, noise, out, t_last) -> torch.Tensor:
-        """the step with a latent guide and / or a CFG control"""
+    def _step_args(self, z, out, noise, t_last, guided):
+        """(t_last, x0_hist, noise) as the step entries take them.  ``guided``: the step ends in the latent guide's blend or the CFG
+        control, which draw eta > 0 noise from noise_seed only."""
         if noise is not None:
-            raise ValueError("a guided or CFG-controlled step draws its noise from noise_seed: it takes no `noise`")
-        if self.eta > 0 and self._key is None:
+            if self._key is not None:
+                raise ValueError("this engine draws its noise from noise_seed: do not pass `noise` as well")
+            if guided:
+                raise ValueError("a guided or CFG-controlled step draws its noise from noise_seed: it takes no `noise`")
+            if self.solver == "dpmpp_2m":
+                raise ValueError("solver 'dpmpp_2m' is deterministic: it takes no noise")
+        if guided and self.eta > 0 and self._key is None:
             raise ValueError("with a known latent or a CFG control, eta > 0 needs noise_seed (unseeded noise is not supported there)")
         tl = h = None
         if self.solver == "dpmpp_2m":
@@ -623,46 +595,35 @@ class DenoiseEngine:
             tl = self._no_hist if t_last is None else L.dev_i64(t_last, self.device)
         elif t_last is not None:
             raise ValueError("t_last is the multistep solver's history: this engine runs solver 'ddim'")
-        if self._ctl is not None:
-            L.check(L.lib().avd_denoise_step_cfg_f32(C.byref(self.desc), C.byref(self._ctl), None if self._guide is None else C.byref(self._guide),
-                                                     None if self._key is None else C.byref(self._key), L.ptr(tl), L.ptr(h), z.data_ptr(),
-                                                     self.Xp.data_ptr(), tn.data_ptr(), tp.data_ptr(), out.data_ptr(),
-                                                     self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device)))
-            return out
-        L.check(L.lib().avd_denoise_step_guided_f32(C.byref(self.desc), C.byref(self._guide),
-                                                    None if self._key is None else C.byref(self._key), L.ptr(tl), L.ptr(h),
-                                                    z.data_ptr(), self.Xp.data_ptr(), tn.data_ptr(), tp.data_ptr(), out.data_ptr(),
-                                                    self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device)))
-        return out
-
-    def _step_cond(self, z, tn, tp, noise, out, t_last) -> torch.Tensor:
-        """the cond-only step: one entry for every solver state, with or without a latent guide (the CFG control does not apply)"""
-        if self._key is not None and noise is not None:
-            raise ValueError("this engine draws its noise from noise_seed: do not pass `noise` as well")
-        if self._guide is not None:
-            if noise is not None:
-                raise ValueError("a guided step draws its noise from noise_seed: it takes no `noise`")
-            if self.eta > 0 and self._key is None:
-                raise ValueError("with a known latent, eta > 0 needs noise_seed (unseeded noise is not supported there)")
-        tl = h = None
-        if self.solver == "dpmpp_2m":
-            if noise is not None:
-                raise ValueError("solver 'dpmpp_2m' is deterministic: it takes no noise")
-            h = self.x0_hist
-            for name, t in (("z", z), ("out", out)):
-                if t.untyped_storage().data_ptr() == h.untyped_storage().data_ptr():
-                    raise L.AvdError(f"{name} must not alias the engine's x0_hist (the solver history)")
-            tl = self._no_hist if t_last is None else L.dev_i64(t_last, self.device)
-        elif t_last is not None:
-            raise ValueError("t_last is the multistep solver's history: this engine runs solver 'ddim'")
-        if self.eta > 0 and self._key is None and noise is None:
-            noise = torch.randn_like(z)
         if self.eta == 0:
             noise = None
-        L.check(L.lib().avd_denoise_step_cond_f32(C.byref(self.desc), None if self._guide is None else C.byref(self._guide),
-                                                  None if self._key is None else C.byref(self._key), L.ptr(tl), L.ptr(h), z.data_ptr(),
-                                                  self.Xp.data_ptr(), tn.data_ptr(), tp.data_ptr(), L.ptr(noise), out.data_ptr(),
-                                                  self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device)))
+        elif self._key is None and noise is None:
+            noise = torch.randn_like(z)
+        return tl, h, noise
+
+    def _step_kind(self, z, tn, tp, noise, out, t_last, cond_only) -> torch.Tensor:
+        """the step proper: cond-only (one entry for every solver state, with or without a latent guide; the CFG control does not
+        apply there), CFG-controlled, guided, DPM-Solver++(2M), seeded or plain DDIM"""
+        guided = self._guide is not None or (self._ctl is not None and not cond_only)
+        tl, h, noise = self._step_args(z, out, noise, t_last, guided)
+        lib, desc = L.lib(), C.byref(self.desc)
+        key = None if self._key is None else C.byref(self._key)
+        guide = None if self._guide is None else C.byref(self._guide)
+        zx, ts = (z.data_ptr(), self.Xp.data_ptr()), (tn.data_ptr(), tp.data_ptr())
+        tail = (out.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device))
+        if cond_only:
+            rc = lib.avd_denoise_step_cond_f32(desc, guide, key, L.ptr(tl), L.ptr(h), *zx, *ts, L.ptr(noise), *tail)
+        elif self._ctl is not None:
+            rc = lib.avd_denoise_step_cfg_f32(desc, C.byref(self._ctl), guide, key, L.ptr(tl), L.ptr(h), *zx, *ts, *tail)
+        elif guided:
+            rc = lib.avd_denoise_step_guided_f32(desc, guide, key, L.ptr(tl), L.ptr(h), *zx, *ts, *tail)
+        elif h is not None:
+            rc = lib.avd_denoise_step_dpmpp_2m_f32(desc, *zx, tl.data_ptr(), *ts, h.data_ptr(), *tail)
+        elif key is not None:
+            rc = lib.avd_denoise_step_seeded_f32(desc, key, *zx, *ts, *tail)
+        else:
+            rc = lib.avd_denoise_step_f32(desc, *zx, *ts, L.ptr(noise), *tail)
+        L.check(rc)
         return out
 
     def eps_tokens(self) -> torch.Tensor:
