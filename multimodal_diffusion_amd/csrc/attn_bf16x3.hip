@@ -289,7 +289,7 @@ __global__ __launch_bounds__(A3_NW * 64, 2) void attn_bf16x3_kernel(const unsign
 // with the VALU work cut into items that are dealt out behind every MFMA pair in program order (a sched_barrier pins each slot).
 // K(kt+2) is fetched while phase B runs, V(kt+1) while phase A runs: the same two LDS tiles and two barriers per tile as before.
 // The O rescale is unconditional here (alpha = 1 when no maximum moved): a wave-uniform branch would cut the schedule in two.
-int g_attn_pipe = getenv("AVD_ATTN_PIPE") ? atoi(getenv("AVD_ATTN_PIPE")) : 1;
+int g_attn_pipe = 1;
 
 // Round 5: the tile loop is PEELED.  The instruction mix of round 4's loop body (867 instructions per 64-key tile, 96 of them MFMAs) held ~250
 // vector instructions that do no arithmetic of the algorithm: the ragged-tail mask (32 compares + 32 selects, executed by EVERY tile because a
@@ -672,7 +672,7 @@ __device__ __forceinline__ f32x4t mma16s(bf16x8 a, bf16x8 b, f32x4t c) {
 }
 // Measured (profiles/r05_attn_m16.txt): C3 151.8 -> 146.2 us per launch alone (shader clock 2,140 -> 2,254 MHz at the same ~1,355 W), 157.4 -> 152.3 us inside
 // the step, C5 geometry 415.6 -> 400.8 us: default 1 for the three-plane modes (2: every split mode, 0: the 32x32x16 kernels).
-int g_attn_m16 = getenv("AVD_ATTN_M16") ? atoi(getenv("AVD_ATTN_M16")) : 1;
+int g_attn_m16 = 1;
 
 struct S16 { f32x4t t[4][2]; };       // scores / probabilities of one 64-key tile: [key tile][query tile]
 

@@ -154,7 +154,7 @@ __global__ void avgpool_frames_kernel(const float* __restrict__ x, float* __rest
 }
 
 // avd_tune_set "codec_mfma" (AVD_CODEC_MFMA): 1 (default) = 64 -> 64 layers with k = 7 / 9 on the fp32 matrix pipe; 0 = the vector kernel
-int g_codec_mfma = getenv("AVD_CODEC_MFMA") ? atoi(getenv("AVD_CODEC_MFMA")) : 1;
+int g_codec_mfma = 1;
 int conv1d_f32(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int Lin, int up,
                int k, int act, hipStream_t st) {
     AVD_REQUIRE(x && w && out, AVD_EINVAL, "conv1d: null pointer");

@@ -3,6 +3,7 @@
 // order, on the caller's stream — one FFI call per module / per step, hipGraph-capturable.
 #include "avd_common.h"
 
+#include <limits.h>
 #include <stdlib.h>
 
 #include <string.h>
@@ -122,8 +123,8 @@ constexpr int64_t kSplitMinRows = 6144;    // 128x128 geometry at B=32 (8,512 ro
 // the six-term mode on the 16x16x32 kernels has 64 .. 224-row blocks for its residual launches (round 4): it passes the fp32 MFMA path
 // between 1,684 rows (606 against 680 steps/s) and 2,128 rows (631 against 516); 3,904 rows (C2): 549 against 462
 constexpr int64_t kSplitMinRowsM16 = 2048;
-static int64_t g_s3_min_rows = [] { const char* e = getenv("AVD_S3_MIN_ROWS"); return e ? (int64_t)atoll(e) : (int64_t)-1; }();
-static bool g_no_fold = getenv("AVD_NO_FOLD") != nullptr;
+static int g_s3_min_rows = -1;
+static int g_no_fold = 0;
 // avd_tune_set "s3_min_rows" (measurement aid): -1 = the per-mode defaults above, >= 0 = that many rows in every mode
 static int64_t split_min_rows(int terms = 3) {
     if (g_s3_min_rows >= 0) return g_s3_min_rows;
@@ -180,7 +181,7 @@ static bool core_use_fold(const avd_core_weights* w) {
 }
 
 // last-block dead-row elimination (avd_tune_set "core_trim" 0 switches it off: measurement aid / A-B in tests)
-static bool g_core_trim = getenv("AVD_CORE_TRIM") ? atoi(getenv("AVD_CORE_TRIM")) != 0 : true;
+static int g_core_trim = 1;
 static int64_t core_trim_floats(const avd_core_weights* w, int B, int N) { return (int64_t)B * N * w->d; }
 
 // the wide scratch of the bf16x3 path holds the qkv3 image, then the fc1 image
@@ -681,44 +682,57 @@ using namespace avd;
 extern "C" int avd_abi_version(void) { return AVD_ABI_VERSION; }
 extern "C" const char* avd_last_error(void) { return g_err; }
 
+// The tune keys: avd_tune_set key, environment variable read when the library loads, the variable (defined with its default, as a
+// constant, in the file that reads it), the accepted range, whether the value is stored as 0 / 1, and one value inside the range
+// that avd_tune_set refuses as well (kNoExcept: none).
+constexpr int kNoExcept = INT_MIN;
+struct TuneKey { const char* key; const char* env; int* var; int lo, hi; bool boolean; int except = kNoExcept; };
+static const TuneKey kTuneKeys[] = {
+    {"s3_tile", "AVD_S3_TILE", &g_s3_tile, INT_MIN, INT_MAX, false},
+    {"s3_m16", "AVD_S3_M16", &g_s3_m16, INT_MIN, INT_MAX, false},
+    {"s3_rt", "AVD_S3_RT", &g_s3_rt, INT_MIN, INT_MAX, false},
+    {"s3_rt4", "AVD_S3_RT4", &g_s3_rt4, 0, 8, false, 1},               // 0 automatic, 2 .. 8 row tiles
+    {"s3_deep4", "AVD_S3_DEEP4", &g_s3_deep4, INT_MIN, INT_MAX, true},
+    {"s3_w128", "AVD_S3_W128", &g_s3_w128, INT_MIN, INT_MAX, false},
+    {"s3_splitk", "AVD_S3_SPLITK", &g_s3_splitk, 0, kS3SplitKMax, false},
+    {"s3_stagger", "AVD_S3_STAGGER", &g_s3_stagger, INT_MIN, INT_MAX, false},
+    {"cfg_rows", "AVD_CFG_ROWS", &g_cfg_rows, INT_MIN, INT_MAX, true},
+    {"vae_lat", "AVD_VAE_LAT", &g_vae_lat, INT_MIN, INT_MAX, true},
+    {"vae_fold", "AVD_VAE_FOLD", &g_vae_fold, INT_MIN, INT_MAX, true},
+    {"codec_mfma", "AVD_CODEC_MFMA", &g_codec_mfma, INT_MIN, INT_MAX, true},
+    {"s3_sn", "AVD_S3_SN", &g_s3_sn, INT_MIN, INT_MAX, false},
+    {"s3_super4", "AVD_S3_SUPER4", &g_s3_super4, INT_MIN, INT_MAX, false},
+    {"s3_super8", "AVD_S3_SUPER8", &g_s3_super8, INT_MIN, INT_MAX, false},
+    {"attn_pipe", "AVD_ATTN_PIPE", &g_attn_pipe, INT_MIN, INT_MAX, false},
+    {"attn_m16", "AVD_ATTN_M16", &g_attn_m16, INT_MIN, INT_MAX, false},
+    {"core_trim", "AVD_CORE_TRIM", &g_core_trim, INT_MIN, INT_MAX, true},
+    {"mlp_fused", "AVD_MLP_FUSED", &g_mlp_fused, INT_MIN, INT_MAX, false},
+    {"gemm_tile", "AVD_GEMM_TILE", &g_gemm_force_tile, INT_MIN, INT_MAX, false},
+    {"gemm_stages", "AVD_GEMM_STAGES", &g_gemm_stages, INT_MIN, INT_MAX, false},
+    {"gemm_splitk", "AVD_GEMM_SPLITK", &g_gemm_splitk, 0, kGemmSplitKMax, false},
+    {"s3_min_rows", "AVD_S3_MIN_ROWS", &g_s3_min_rows, INT_MIN, INT_MAX, false},
+    {"no_fold", "AVD_NO_FOLD", &g_no_fold, INT_MIN, INT_MAX, true},
+};
+static void tune_store(const TuneKey& t, int64_t value) { *t.var = t.boolean ? value != 0 : (int)value; }
+// Environment overrides, applied once when the library loads (the variables are constant-initialised, so they hold their defaults before
+// any dynamic initialiser runs).  A process cannot refuse here: an out-of-range value is clamped.
+[[maybe_unused]] static const bool g_tune_env_applied = [] {
+    for (const TuneKey& t : kTuneKeys)
+        if (const char* e = getenv(t.env)) {
+            const long long v = atoll(e);
+            tune_store(t, v < t.lo ? t.lo : v > t.hi ? t.hi : v);
+        }
+    return true;
+}();
+
 extern "C" int avd_tune_set(const char* key, int64_t value) {
     AVD_REQUIRE(key, AVD_EINVAL, "tune_set: null key");
-    if (!strcmp(key, "s3_tile")) { g_s3_tile = (int)value; return AVD_OK; }
-    if (!strcmp(key, "s3_m16")) { g_s3_m16 = (int)value; return AVD_OK; }
-    if (!strcmp(key, "s3_rt")) { g_s3_rt = (int)value; return AVD_OK; }
-    if (!strcmp(key, "s3_rt4")) {
-        AVD_REQUIRE(value == 0 || (value >= 2 && value <= 8), AVD_EINVAL, "tune_set: s3_rt4 must be 0 (automatic) or 2 .. 8");
-        g_s3_rt4 = (int)value;
+    for (const TuneKey& t : kTuneKeys) {
+        if (strcmp(key, t.key)) continue;
+        AVD_REQUIRE(value >= t.lo && value <= t.hi && value != t.except, AVD_EINVAL, "tune_set: %s does not take %lld", key, (long long)value);
+        tune_store(t, value);
         return AVD_OK;
     }
-    if (!strcmp(key, "s3_deep4")) { g_s3_deep4 = value != 0; return AVD_OK; }
-    if (!strcmp(key, "s3_w128")) { g_s3_w128 = (int)value; return AVD_OK; }
-    if (!strcmp(key, "s3_splitk")) {
-        AVD_REQUIRE(value >= 0 && value <= kS3SplitKMax, AVD_EINVAL, "tune_set: s3_splitk must be in [0, %d]", kS3SplitKMax);
-        g_s3_splitk = (int)value;
-        return AVD_OK;
-    }
-    if (!strcmp(key, "s3_stagger")) { g_s3_stagger = (int)value; return AVD_OK; }
-    if (!strcmp(key, "cfg_rows")) { g_cfg_rows = value != 0; return AVD_OK; }
-    if (!strcmp(key, "vae_lat")) { g_vae_lat = value != 0; return AVD_OK; }
-    if (!strcmp(key, "vae_fold")) { g_vae_fold = value != 0; return AVD_OK; }
-    if (!strcmp(key, "codec_mfma")) { g_codec_mfma = value != 0; return AVD_OK; }
-    if (!strcmp(key, "s3_sn")) { g_s3_sn = (int)value; return AVD_OK; }
-    if (!strcmp(key, "s3_super4")) { g_s3_super4 = (int)value; return AVD_OK; }
-    if (!strcmp(key, "s3_super8")) { g_s3_super8 = (int)value; return AVD_OK; }
-    if (!strcmp(key, "attn_pipe")) { g_attn_pipe = (int)value; return AVD_OK; }
-    if (!strcmp(key, "attn_m16")) { g_attn_m16 = (int)value; return AVD_OK; }
-    if (!strcmp(key, "core_trim")) { g_core_trim = value != 0; return AVD_OK; }
-    if (!strcmp(key, "mlp_fused")) { g_mlp_fused = (int)value; return AVD_OK; }
-    if (!strcmp(key, "gemm_tile")) { g_gemm_force_tile = (int)value; return AVD_OK; }
-    if (!strcmp(key, "gemm_stages")) { g_gemm_stages = (int)value; return AVD_OK; }
-    if (!strcmp(key, "gemm_splitk")) {
-        AVD_REQUIRE(value >= 0 && value <= kGemmSplitKMax, AVD_EINVAL, "tune_set: gemm_splitk must be in [0, %d]", kGemmSplitKMax);
-        g_gemm_splitk = (int)value;
-        return AVD_OK;
-    }
-    if (!strcmp(key, "s3_min_rows")) { g_s3_min_rows = value; return AVD_OK; }
-    if (!strcmp(key, "no_fold")) { g_no_fold = value != 0; return AVD_OK; }
     return set_error(AVD_EINVAL, "tune_set: unknown key '%s'", key);
 }
 

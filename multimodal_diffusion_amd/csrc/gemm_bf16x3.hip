@@ -35,6 +35,7 @@
 #include "s3_common.h"
 
 #include <stdlib.h>
+#include <optional>
 #include <type_traits>
 
 namespace avd {
@@ -1391,6 +1392,10 @@ int64_t split3_bytes(int64_t rows, int K) { return ((rows + 255) / 256 * 256) * 
 // algorithmic bytes per element of a producer that reads fp32 and writes an operand image: 4 + three bf16 planes, or 4 + the two
 // fp16 planes of an f16x2 image (the third plane is never written)
 static double image_rw_bytes(float h2_scale) { return h2_scale > 0.f ? 8.0 : 10.0; }
+static bool scale_ok(float s) { return s > 0.f && s < __builtin_inff(); }      // an image scale: positive and finite
+// f(std::true_type{}) / f(std::false_type{}): a runtime yes / no as a template argument (f16x2 image or bf16 planes, image or none)
+template <class F>
+static void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
 
 int split3_f32(const float* x, int64_t ld, void* out, int64_t rows, int K, hipStream_t st, float h2_scale) {
     return split3_rows_f32(x, RowMap{ld, 0, 0}, out, rows, K, st, h2_scale);
@@ -1407,14 +1412,12 @@ int split3_rows_f32(const float* x, RowMap xm, void* out, int64_t rows, int K, h
     const int64_t n = rows_pad * (K / 8);
     AVD_REQUIRE((n + 255) / 256 < (1ll << 31), AVD_EUNSUPPORTED, "split3: grid too large");
     static const int tag = prof_tag_id("split3_kernel");
-    AVD_REQUIRE(h2_scale >= 0.f && h2_scale < __builtin_inff(), AVD_EINVAL, "split3: f16x2 image scale must be positive and finite");
+    AVD_REQUIRE(h2_scale == 0.f || scale_ok(h2_scale), AVD_EINVAL, "split3: f16x2 image scale must be positive and finite");
     ProfScope prof(tag, (double)rows * K * image_rw_bytes(h2_scale), st);
-    if (h2_scale > 0.f)
-        hipLaunchKernelGGL(split3_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, xm,
-                           static_cast<unsigned char*>(out), rows, rows_pad, K, h2_scale, ss);
-    else
-        hipLaunchKernelGGL(split3_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, xm,
-                           static_cast<unsigned char*>(out), rows, rows_pad, K, 0.f, ss);
+    with_bool(h2_scale > 0.f, [&](auto f16) {
+        hipLaunchKernelGGL(split3_kernel<f16()>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, xm,
+                           static_cast<unsigned char*>(out), rows, rows_pad, K, f16() ? h2_scale : 0.f, ss);
+    });
     AVD_CHECK_LAUNCH("split3");
     return AVD_OK;
 }
@@ -1428,10 +1431,11 @@ int rmsnorm_split3_f32(const float* x, const float* scale, void* out, int64_t ro
     const unsigned grid = (unsigned)((rows + 3) / 4);
     const float isd = (float)sqrt((double)d);
     unsigned char* o = static_cast<unsigned char*>(out);
-    AVD_REQUIRE(h2_scale >= 0.f && h2_scale < __builtin_inff(), AVD_EINVAL, "rmsnorm_split3: f16x2 image scale must be positive and finite");
+    AVD_REQUIRE(h2_scale == 0.f || scale_ok(h2_scale), AVD_EINVAL, "rmsnorm_split3: f16x2 image scale must be positive and finite");
 #define AVD_RMS3(NC)                                                                                                                  \
-    if (h2_scale > 0.f) hipLaunchKernelGGL((rmsnorm_split3_kernel<NC, true>), dim3(grid), dim3(256), 0, st, x, scale, o, rows, d, eps, isd, h2_scale); \
-    else hipLaunchKernelGGL((rmsnorm_split3_kernel<NC, false>), dim3(grid), dim3(256), 0, st, x, scale, o, rows, d, eps, isd, 0.f)
+    with_bool(h2_scale > 0.f, [&](auto f16) {                                                                                         \
+        hipLaunchKernelGGL((rmsnorm_split3_kernel<NC, f16()>), dim3(grid), dim3(256), 0, st, x, scale, o, rows, d, eps, isd, f16() ? h2_scale : 0.f); \
+    })
     switch ((d + 511) / 512) {
         case 1: AVD_RMS3(1); break;
         case 2: AVD_RMS3(2); break;
@@ -1448,15 +1452,15 @@ int layernorm_act_split3_f32(const float* x, const float* gamma, const float* be
     AVD_REQUIRE(x && gamma && beta && out, AVD_EINVAL, "layernorm_split3: null pointer");
     AVD_REQUIRE(rows > 0 && d > 0 && d % 16 == 0 && d <= 2048, AVD_EUNSUPPORTED, "layernorm_split3: d=%d must be a multiple of 16, <= 2048", d);
     AVD_REQUIRE(aligned16(x) && aligned16(out) && aligned16(gamma) && aligned16(beta), AVD_EUNSUPPORTED, "layernorm_split3: pointers must be 16-byte aligned");
-    AVD_REQUIRE(h2_scale >= 0.f && h2_scale < __builtin_inff(), AVD_EINVAL, "layernorm_split3: f16x2 image scale must be positive and finite");
+    AVD_REQUIRE(h2_scale == 0.f || scale_ok(h2_scale), AVD_EINVAL, "layernorm_split3: f16x2 image scale must be positive and finite");
     static const int tag = prof_tag_id("layernorm_act_split3_kernel");
     ProfScope prof(tag, image_rw_bytes(h2_scale) * (double)rows * d, st);
     const unsigned grid = (unsigned)((rows + 3) / 4);
     unsigned char* o = static_cast<unsigned char*>(out);
-#define AVD_LN3K(NC, F16, G) hipLaunchKernelGGL((layernorm_act_split3_kernel<NC, F16, G>), dim3(grid), dim3(256), 0, st, x, gamma, beta, o, rows, d, eps, act, h2_scale)
-#define AVD_LN3(NC)                                                                            \
-    if (h2_scale > 0.f) { if (act == AVD_ACT_GELU) AVD_LN3K(NC, true, true); else AVD_LN3K(NC, true, false); } \
-    else { if (act == AVD_ACT_GELU) AVD_LN3K(NC, false, true); else AVD_LN3K(NC, false, false); }
+#define AVD_LN3(NC)                                                                                                                   \
+    with_bool(h2_scale > 0.f, [&](auto f16) { with_bool(act == AVD_ACT_GELU, [&](auto gelu) {                                         \
+        hipLaunchKernelGGL((layernorm_act_split3_kernel<NC, f16(), gelu()>), dim3(grid), dim3(256), 0, st, x, gamma, beta, o, rows, d, eps, act, h2_scale); \
+    }); })
     switch ((d + 511) / 512) {
         case 1: AVD_LN3(1); break;
         case 2: AVD_LN3(2); break;
@@ -1464,7 +1468,6 @@ int layernorm_act_split3_f32(const float* x, const float* gamma, const float* be
         default: AVD_LN3(4); break;
     }
 #undef AVD_LN3
-#undef AVD_LN3K
     AVD_CHECK_LAUNCH("layernorm_split3");
     return AVD_OK;
 }
@@ -1475,7 +1478,7 @@ bool gemm_bf16x3_rownorm_supported(int N, int terms) { return N == 512 && terms 
 
 // tile configuration: 0 = 256x256, 8 waves, one block per CU; 1 = 256x128, 4 waves, two blocks per CU.
 // AVD_S3_TILE=0|1 forces one (measurement aid, also avd_tune_set "s3_tile"); default: per epilogue, what measured faster in the C3 pipeline.
-int g_s3_tile = getenv("AVD_S3_TILE") ? atoi(getenv("AVD_S3_TILE")) : -1;
+int g_s3_tile = -1;
 static int s3_tile_for(int epi, int64_t M, int N) {
     if (g_s3_tile == 0 || g_s3_tile == 1) return g_s3_tile;
     if (epi == S3_EPI_GELU_SPLIT || epi == S3_EPI_QKV3 || epi == S3_EPI_SPLIT) return 1;
@@ -1487,7 +1490,7 @@ static int s3_tile_for(int epi, int64_t M, int N) {
 // Stagger of the two co-resident blocks of the 4-wave kernel, x 1024 cycles; -1 = automatic: about a third of a tile's life when
 // the launch has at least two generations of blocks and the caller is not already running two kernel chains on two streams (those
 // drift apart by themselves; there the start-up delay only costs).  avd_tune_set "s3_stagger".
-int g_s3_stagger = getenv("AVD_S3_STAGGER") ? atoi(getenv("AVD_S3_STAGGER")) : -1;
+int g_s3_stagger = -1;
 thread_local bool t_s3_two_streams = false;      // set by avd_denoise_step_f32 around its two-stream section
 #ifdef AVD_S3_STAMPS
 unsigned long long* g_s3_dbg = nullptr;
@@ -1507,15 +1510,16 @@ static int s3_cu_count() {                 // CUs of the current device (looked 
     }
     return n;
 }
+static int64_t s3_cu_or_256() { const int n = s3_cu_count(); return n > 0 ? n : 256; }      // for the block-count rules below
 
 // Super-tiles: the blocks an XCD runs together (consecutive ids after the XCD remap) form sm x sn blocks that share sm A panels and sn W
 // panels.  256x128 tiles (tile = true, two blocks per CU): rounds 2-4 ran whole block rows per super-tile (the 12-16 column blocks that
 // share an A panel together, 2 rows x all columns); 16 blocks per super-tile for the one-block-per-CU tiles.
 // AVD_S3_SN / AVD_S3_SUPER4 / AVD_S3_SUPER8 (avd_tune_set "s3_sn" / "s3_super4" / "s3_super8"): measurement aids — super-tile width in blocks /
 // blocks per super-tile of the two-per-CU and one-per-CU kernels; profiles/r05_fetch_ab.txt holds the FETCH_SIZE of fc1 / in_proj across them.
-int g_s3_sn = getenv("AVD_S3_SN") ? atoi(getenv("AVD_S3_SN")) : 0;                  // avd_tune_set "s3_sn": 0 = the rule below
-int g_s3_super4 = getenv("AVD_S3_SUPER4") ? atoi(getenv("AVD_S3_SUPER4")) : 0;      // avd_tune_set "s3_super4" / "s3_super8": 0 = 32 / 16 blocks
-int g_s3_super8 = getenv("AVD_S3_SUPER8") ? atoi(getenv("AVD_S3_SUPER8")) : 0;
+int g_s3_sn = 0;                  // avd_tune_set "s3_sn": 0 = the rule below
+int g_s3_super4 = 0;      // avd_tune_set "s3_super4" / "s3_super8": 0 = 32 / 16 blocks
+int g_s3_super8 = 0;
 static void s3_supertile(bool tile, int nbn, int& sn_out, int& sm_out) {
     int sn = 8;
     while (nbn % sn) sn >>= 1;
@@ -1531,92 +1535,66 @@ static void s3_supertile(bool tile, int nbn, int& sn_out, int& sm_out) {
     sm_out = total / sn > 0 ? total / sn : 1;
 }
 
-template <int EPI, int TERMS, int WAVES>
-static int launch_s3w(S3Args g, hipStream_t st, int nz = 1) {
-    using Cf = S3Cfg<TERMS, WAVES, EPI == S3_EPI_RES_NORM>;
-    constexpr bool tile = WAVES == 4;
-    static LdsAttr attr;
-    auto kern = gemm_bf16x3_kernel<EPI, TERMS, WAVES>;
-    if (int rc = attr.ensure(reinterpret_cast<const void*>(kern), Cf::LDS, "gemm_bf16x3")) return rc;
+// What the three launchers below share.  Block geometry: rows and columns per block, dynamic LDS bytes, threads, two blocks per CU
+// (the 4-wave kernels: wide super-tiles, staggered start) or one, and the stagger base in 1024-cycle units at K < 1024 (twice that from
+// K = 1024 on); stagger < 0: the kernel knows no stagger and no first generation.
+struct S3Geom { int bm, bn, lds, threads; bool two_per_cu; int stagger; };
+template <class Kern>
+static int s3_launch(Kern kern, LdsAttr& attr, const S3Geom& ge, int tag, const char* what, S3Args g, hipStream_t st, int nz = 1) {
+    if (int rc = attr.ensure(reinterpret_cast<const void*>(kern), ge.lds, what)) return rc;
 #ifdef AVD_S3_STAMPS
     g.dbg = g_s3_dbg;
 #endif
-    g.nbn = g.N / Cf::BN;
-    s3_supertile(tile, g.nbn, g.sn, g.sm);
-    const int64_t nbm = (g.M + Cf::BM - 1) / Cf::BM;
+    g.nbn = g.N / ge.bn;
+    s3_supertile(ge.two_per_cu, g.nbn, g.sn, g.sm);
+    const int64_t nbm = (g.M + ge.bm - 1) / ge.bm;
     const int64_t nwg = nbm * g.nbn;
     AVD_REQUIRE(nwg < (1ll << 31), AVD_EUNSUPPORTED, "gemm_bf16x3 grid too large");
     g.stagger = 0;
-    g.first_gen = 2 * s3_cu_count();
-    if (tile && g.first_gen > 0 && nbm * g.nbn >= 2 * g.first_gen)
-        g.stagger = g_s3_stagger >= 0 ? g_s3_stagger : t_s3_two_streams ? 0 : (TERMS == 3 ? 24 : TERMS == 1 ? 12 : 48) * (g.K >= 1024 ? 2 : 1);
-    // tag = the kernel name as rocprofv3 prints its template arguments (EPI, TERMS, WAVES)
-    static const int tag = prof_tag_id("gemm_bf16x3_kernel<%d, %d, %d>", EPI, TERMS, WAVES);
+    g.first_gen = ge.stagger < 0 ? 0 : 2 * s3_cu_count();
+    if (ge.two_per_cu && g.first_gen > 0 && nwg >= 2 * g.first_gen)
+        g.stagger = g_s3_stagger >= 0 ? g_s3_stagger : t_s3_two_streams ? 0 : ge.stagger * (g.K >= 1024 ? 2 : 1);
     ProfScope prof(tag, 2.0 * (double)g.M * g.N * g.K * nz, st);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg, (unsigned)nz), dim3(WAVES * 64), Cf::LDS, st, g);
-    AVD_CHECK_LAUNCH("gemm_bf16x3");
+    hipLaunchKernelGGL(kern, dim3((unsigned)nwg, (unsigned)nz), dim3(ge.threads), ge.lds, st, g);
+    AVD_CHECK_LAUNCH(what);
     return AVD_OK;
 }
 
+template <int EPI, int TERMS, int WAVES>
+static int launch_s3w(const S3Args& g, hipStream_t st, int nz = 1) {
+    using Cf = S3Cfg<TERMS, WAVES, EPI == S3_EPI_RES_NORM>;
+    constexpr S3Geom ge{Cf::BM, Cf::BN, Cf::LDS, WAVES * 64, WAVES == 4, TERMS == 3 ? 24 : TERMS == 1 ? 12 : 48};
+    static LdsAttr attr;
+    // tag = the kernel name as rocprofv3 prints its template arguments (EPI, TERMS, WAVES)
+    static const int tag = prof_tag_id("gemm_bf16x3_kernel<%d, %d, %d>", EPI, TERMS, WAVES);
+    return s3_launch(gemm_bf16x3_kernel<EPI, TERMS, WAVES>, attr, ge, tag, "gemm_bf16x3", g, st, nz);
+}
+
 // bf16x3 (six terms) on the 16x16x32 MFMA with two terms per instruction; avd_tune_set "s3_m16" 0 takes the 32x32x16 kernel instead
-int g_s3_m16 = getenv("AVD_S3_M16") ? atoi(getenv("AVD_S3_M16")) : 1;
+int g_s3_m16 = 1;
 // rows per 8-wave block of the residual + image epilogue: 0 = automatic (224 when that saves a generation of blocks), 7 / 8 forced
 // (avd_tune_set "s3_rt", AVD_S3_RT)
-int g_s3_rt = getenv("AVD_S3_RT") ? atoi(getenv("AVD_S3_RT")) : 0;
+int g_s3_rt = 0;
 template <int EPI, int WAVES, int RT = 8, int NSTK = 0>
-static int launch_s3w16(S3Args g, hipStream_t st) {
+static int launch_s3w16(const S3Args& g, hipStream_t st) {
     using Cf = S3Cfg<6, WAVES>;
-    constexpr bool tile = WAVES == 4;
-    constexpr int BM = WAVES == 8 || RT < 8 ? 32 * RT : Cf::BM;
-    constexpr int LDS = NSTK ? NSTK * Cf::STAGE : Cf::LDS;
+    constexpr S3Geom ge{WAVES == 8 || RT < 8 ? 32 * RT : Cf::BM, Cf::BN, NSTK ? NSTK * Cf::STAGE : Cf::LDS, WAVES * 64, WAVES == 4, 48};
     static LdsAttr attr;
-    auto kern = gemm_bf16x3_m16_kernel<EPI, WAVES, RT, NSTK>;
-    if (int rc = attr.ensure(reinterpret_cast<const void*>(kern), LDS, "gemm_bf16x3 (16x16x32)")) return rc;
-#ifdef AVD_S3_STAMPS
-    g.dbg = g_s3_dbg;
-#endif
-    g.nbn = g.N / Cf::BN;
-    s3_supertile(tile, g.nbn, g.sn, g.sm);
-    const int64_t nbm = (g.M + BM - 1) / BM;
-    const int64_t nwg = nbm * g.nbn;
-    AVD_REQUIRE(nwg < (1ll << 31), AVD_EUNSUPPORTED, "gemm_bf16x3 grid too large");
-    g.stagger = 0;
-    g.first_gen = 2 * s3_cu_count();
-    if (tile && g.first_gen > 0 && nbm * g.nbn >= 2 * g.first_gen)
-        g.stagger = g_s3_stagger >= 0 ? g_s3_stagger : t_s3_two_streams ? 0 : 48 * (g.K >= 1024 ? 2 : 1);
     // tag = the kernel name as rocprofv3 prints it (a defaulted NSTK = 0 is printed too)
     static const int tag = prof_tag_id("gemm_bf16x3_m16_kernel<%d, %d, %d, %d>", EPI, WAVES, RT, NSTK);
-    ProfScope prof(tag, 2.0 * (double)g.M * g.N * g.K, st);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(WAVES * 64), LDS, st, g);
-    AVD_CHECK_LAUNCH("gemm_bf16x3 (16x16x32)");
-    return AVD_OK;
+    return s3_launch(gemm_bf16x3_m16_kernel<EPI, WAVES, RT, NSTK>, attr, ge, tag, "gemm_bf16x3 (16x16x32)", g, st);
 }
 
 // 4 waves with a 128 x 128 wave tile (gemm_bf16x3_w128_kernel) in place of the 8-wave blocks of the image epilogues (by default that is the
 // residual + image epilogue of out_proj / fc2: 190 -> 180 us per launch at C3; fc1 / in_proj keep two 4-wave blocks per CU — with one
 // wave per SIMD nothing runs beside their GELU / split epilogue: 389 against 292 us).  avd_tune_set "s3_w128" 0 takes the 8-wave kernel.
-int g_s3_w128 = getenv("AVD_S3_W128") ? atoi(getenv("AVD_S3_W128")) : 1;
+int g_s3_w128 = 1;
 template <int EPI, int RT>
-static int launch_s3w128(S3Args g, hipStream_t st) {
-    constexpr int BM = 32 * RT, LDS = 3 * 6 * 256 * 32;
+static int launch_s3w128(const S3Args& g, hipStream_t st) {
+    constexpr S3Geom ge{32 * RT, 256, 3 * 6 * 256 * 32, 256, false, -1};
     static LdsAttr attr;
-    auto kern = gemm_bf16x3_w128_kernel<EPI, RT>;
-    if (int rc = attr.ensure(reinterpret_cast<const void*>(kern), LDS, "gemm_bf16x3 (128x128 wave tile)")) return rc;
-#ifdef AVD_S3_STAMPS
-    g.dbg = g_s3_dbg;
-#endif
-    g.nbn = g.N / 256;
-    s3_supertile(false, g.nbn, g.sn, g.sm);
-    const int64_t nbm = (g.M + BM - 1) / BM;
-    const int64_t nwg = nbm * g.nbn;
-    AVD_REQUIRE(nwg < (1ll << 31), AVD_EUNSUPPORTED, "gemm_bf16x3 grid too large");
-    g.stagger = 0;
-    g.first_gen = 0;
     static const int tag = prof_tag_id("gemm_bf16x3_w128_kernel<%d, %d>", EPI, RT);
-    ProfScope prof(tag, 2.0 * (double)g.M * g.N * g.K, st);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), LDS, st, g);
-    AVD_CHECK_LAUNCH("gemm_bf16x3 (128x128 wave tile)");
-    return AVD_OK;
+    return s3_launch(gemm_bf16x3_w128_kernel<EPI, RT>, attr, ge, tag, "gemm_bf16x3 (128x128 wave tile)", g, st);
 }
 
 // Rows per 4-wave block (32 RT) of the image epilogues: 0 = automatic, 2 .. 8 forced (avd_tune_set "s3_rt4", AVD_S3_RT4; in_proj / fc1
@@ -1626,10 +1604,10 @@ static int launch_s3w128(S3Args g, hipStream_t st) {
 // residual launches at 3,904 rows: 71.4 / 60.8 / 56.7 / 45.1 us for RT = 5 / 4 / 3 / 2): RT minimises ceil(blocks / CUs) x (RT + 3),
 // and 8 stays unless a shorter block models at least 6 % better — many generations of blocks
 // (C3: 26,944 rows) keep 256-row blocks, whose W traffic and fragment reads per MFMA are the lowest.
-int g_s3_rt4 = getenv("AVD_S3_RT4") ? atoi(getenv("AVD_S3_RT4")) : 0;
+int g_s3_rt4 = 0;
 static int s3_rt4_for(int64_t M, int N, int rt_min) {
     if (g_s3_rt4 >= 2 && g_s3_rt4 <= 8) return g_s3_rt4 > rt_min ? g_s3_rt4 : rt_min;
-    const int64_t cu = s3_cu_count() > 0 ? s3_cu_count() : 256, nbn = N / 128;
+    const int64_t cu = s3_cu_or_256(), nbn = N / 128;
     int best = 8;
     int64_t cost8 = 0, cbest = 0;
     for (int rt = 8; rt >= rt_min; --rt) {
@@ -1639,12 +1617,29 @@ static int s3_rt4_for(int64_t M, int N, int rt_min) {
     }
     return cbest * 100 <= cost8 * 94 ? best : 8;
 }
+// Row tiles (6 / 7 / 8) of the one-block-per-CU kernels of the residual + image epilogue: 224-row (192-row) blocks when they need fewer
+// generations of blocks x rows than 256-row blocks; "s3_rt" 6 / 7 / 8 forces one (192 rows: the four-wave "s3_w128" kernel only)
+static int s3_rt8_for(int64_t M, int N) {
+    const int64_t cu = s3_cu_or_256(), nbn = N / 256;
+    const int64_t g8 = ((M + 255) / 256 * nbn + cu - 1) / cu * 8, g7 = ((M + 223) / 224 * nbn + cu - 1) / cu * 7;
+    const int64_t g6 = ((M + 191) / 192 * nbn + cu - 1) / cu * 6;
+    if (g_s3_w128 && (g_s3_rt == 6 || (g_s3_rt == 0 && g6 < g7 && g6 < g8))) return 6;
+    return g_s3_rt == 7 || (g_s3_rt != 8 && g7 < g8) ? 7 : 8;
+}
 // The four-stage ring (one block per CU) of the residual + image launches: 1 (default) when the launch's blocks fit the CUs once,
 // 0 never (avd_tune_set "s3_deep4", AVD_S3_DEEP4)
-int g_s3_deep4 = getenv("AVD_S3_DEEP4") ? atoi(getenv("AVD_S3_DEEP4")) : 1;
+int g_s3_deep4 = 1;
 static bool s3_deep4_for(int64_t M, int N, int rt) {
-    const int64_t cu = s3_cu_count() > 0 ? s3_cu_count() : 256;
-    return g_s3_deep4 != 0 && (M + 32 * rt - 1) / (32 * rt) * (N / 128) <= cu;
+    return g_s3_deep4 != 0 && (M + 32 * rt - 1) / (32 * rt) * (N / 128) <= s3_cu_or_256();
+}
+
+// A runtime row-tile count as a template argument: the status of f(std::integral_constant<int, rt>{}) for rt in [LO, HI].  Any other rt
+// takes HI when hi_is_default, and else launches nothing and returns no status (the caller goes on to its next rule).
+template <int LO, int HI, class F>
+static std::optional<int> s3_with_rt(int rt, bool hi_is_default, F&& f) {
+    if (rt == LO || (LO == HI && hi_is_default)) return f(std::integral_constant<int, LO>{});
+    if constexpr (LO < HI) return s3_with_rt<LO + 1, HI>(rt, hi_is_default, f);
+    else return std::nullopt;
 }
 
 template <int EPI, int TERMS>
@@ -1654,75 +1649,32 @@ static int launch_s3t(const S3Args& a, hipStream_t st) {
             if (s3_tile_for(EPI, a.M, a.N)) {
                 // the noise head's launches (fp32 out with a bias: shared Linears, out_proj; image out: input_proj) when their blocks fit the
                 // CUs once — short blocks, one per CU, on the four-stage ring; EPI_BIAS then runs from the registers (S3_EPI_BIAS_REG)
-                if constexpr (EPI == S3_EPI_BIAS || EPI == S3_EPI_SPLIT) {
-                    constexpr int E2 = EPI == S3_EPI_BIAS ? (int)S3_EPI_BIAS_REG : (int)S3_EPI_SPLIT;
+                if constexpr (EPI == S3_EPI_BIAS || EPI == S3_EPI_SPLIT || EPI == S3_EPI_RES_IMG) {
+                    constexpr int E2 = EPI == S3_EPI_BIAS ? (int)S3_EPI_BIAS_REG : (int)EPI;
                     const int rt = s3_rt4_for(a.M, a.N, 2);
-                    if (a.bias && a.N % 128 == 0 && s3_deep4_for(a.M, a.N, rt)) {
-                        switch (rt) {
-                            case 2: return launch_s3w16<E2, 4, 2, 4>(a, st);
-                            case 3: return launch_s3w16<E2, 4, 3, 4>(a, st);
-                            case 4: return launch_s3w16<E2, 4, 4, 4>(a, st);
-                            case 5: return launch_s3w16<E2, 4, 5, 4>(a, st);
-                            case 6: return launch_s3w16<E2, 4, 6, 4>(a, st);
-                            case 7: return launch_s3w16<E2, 4, 7, 4>(a, st);
-                            default: return launch_s3w16<E2, 4, 8, 4>(a, st);
-                        }
-                    }
-                }
-                if constexpr (EPI == S3_EPI_RES_IMG) {
-                    const int rt = s3_rt4_for(a.M, a.N, 2);
-                    if (s3_deep4_for(a.M, a.N, rt)) {
-                        switch (rt) {
-                            case 2: return launch_s3w16<EPI, 4, 2, 4>(a, st);
-                            case 3: return launch_s3w16<EPI, 4, 3, 4>(a, st);
-                            case 4: return launch_s3w16<EPI, 4, 4, 4>(a, st);
-                            case 5: return launch_s3w16<EPI, 4, 5, 4>(a, st);
-                            case 6: return launch_s3w16<EPI, 4, 6, 4>(a, st);
-                            case 7: return launch_s3w16<EPI, 4, 7, 4>(a, st);
-                            default: return launch_s3w16<EPI, 4, 8, 4>(a, st);
-                        }
-                    }
-                }
-                // (in_proj / fc1 on the four-stage ring when their blocks fit the CUs once: measured, no gain — K = 512 is 32 steps, and at
-                // 3,904 rows in_proj's 252 blocks run 62 us two to a CU and 79 us one to a CU; they keep the two-stage ring)
-                if constexpr (EPI == S3_EPI_RES_IMG) {
-                    switch (s3_rt4_for(a.M, a.N, 2)) {
-                        case 2: return launch_s3w16<EPI, 4, 2>(a, st);
-                        case 3: return launch_s3w16<EPI, 4, 3>(a, st);
-                        case 4: return launch_s3w16<EPI, 4, 4>(a, st);
-                        default: break;
+                    if ((EPI == S3_EPI_RES_IMG || (a.bias && a.N % 128 == 0)) && s3_deep4_for(a.M, a.N, rt))
+                        return *s3_with_rt<2, 8>(rt, true, [&](auto r) { return launch_s3w16<E2, 4, r(), 4>(a, st); });
+                    // (in_proj / fc1 on the four-stage ring when their blocks fit the CUs once: measured, no gain — K = 512 is 32 steps, and at
+                    // 3,904 rows in_proj's 252 blocks run 62 us two to a CU and 79 us one to a CU; they keep the two-stage ring)
+                    if constexpr (EPI == S3_EPI_RES_IMG) {
+                        if (const auto rc = s3_with_rt<2, 4>(rt, false, [&](auto r) { return launch_s3w16<EPI, 4, r()>(a, st); })) return *rc;
                     }
                 }
                 if constexpr (EPI == S3_EPI_GELU_SPLIT || EPI == S3_EPI_QKV3 || EPI == S3_EPI_RES_IMG) {
-                    switch (s3_rt4_for(a.M, a.N, 5)) {
-                        case 5: return launch_s3w16<EPI, 4, 5>(a, st);
-                        case 6: return launch_s3w16<EPI, 4, 6>(a, st);
-                        case 7: return launch_s3w16<EPI, 4, 7>(a, st);
-                        default: break;
-                    }
+                    const int rt = s3_rt4_for(a.M, a.N, 5);
+                    if (const auto rc = s3_with_rt<5, 7>(rt, false, [&](auto r) { return launch_s3w16<EPI, 4, r()>(a, st); })) return *rc;
                 }
                 return launch_s3w16<EPI, 4>(a, st);
             }
-            constexpr bool TR = EPI == S3_EPI_GELU_SPLIT || EPI == S3_EPI_SPLIT || EPI == S3_EPI_QKV3 || EPI == S3_EPI_RES_IMG;
-            bool rt7 = false, rt6 = false;
-            if constexpr (EPI == S3_EPI_RES_IMG) {
-                // 224-row (192-row) blocks when they need fewer generations of blocks x rows than 256-row blocks (one block per CU)
-                const int64_t cu = s3_cu_count() > 0 ? s3_cu_count() : 256, nbn = a.N / 256;
-                const int64_t g8 = ((a.M + 255) / 256 * nbn + cu - 1) / cu * 8, g7 = ((a.M + 223) / 224 * nbn + cu - 1) / cu * 7;
-                const int64_t g6 = ((a.M + 191) / 192 * nbn + cu - 1) / cu * 6;
-                rt6 = g_s3_w128 && (g_s3_rt == 6 || (g_s3_rt == 0 && g6 < g7 && g6 < g8));       // 192 rows: the four-wave kernel only
-                rt7 = !rt6 && (g_s3_rt == 7 || (g_s3_rt != 8 && g7 < g8));
+            // one block per CU: the 128 x 128 wave tile for the image epilogues ("s3_w128"), else 8 waves; 192 / 224-row blocks for the
+            // residual + image epilogue (s3_rt8_for; 192 rows exist on the 128 x 128 wave tile only)
+            constexpr bool RI = EPI == S3_EPI_RES_IMG;
+            const int rt = RI ? s3_rt8_for(a.M, a.N) : 8;
+            if constexpr (RI || EPI == S3_EPI_GELU_SPLIT || EPI == S3_EPI_SPLIT || EPI == S3_EPI_QKV3) {
+                if (g_s3_w128) return *s3_with_rt<RI ? 6 : 7, 8>(rt, true, [&](auto r) { return launch_s3w128<EPI, r()>(a, st); });
             }
-            if constexpr (TR) {
-                if (g_s3_w128) {
-                    if constexpr (EPI == S3_EPI_RES_IMG) {
-                        if (rt6) return launch_s3w128<EPI, 6>(a, st);
-                    }
-                    return rt7 ? launch_s3w128<EPI, 7>(a, st) : launch_s3w128<EPI, 8>(a, st);
-                }
-            }
-            if constexpr (EPI == S3_EPI_RES_IMG) {
-                if (rt7) return launch_s3w16<EPI, 8, 7>(a, st);
+            if constexpr (RI) {
+                if (rt == 7) return launch_s3w16<EPI, 8, 7>(a, st);
             }
             return launch_s3w16<EPI, 8>(a, st);
         }
@@ -1752,6 +1704,16 @@ static int launch_s3(const S3Args& a, hipStream_t st) {
 // C, C3, R and ss_out all given -> the new residual stream as fp32, as an image and as sums of squares in one epilogue.
 bool gemm_bf16x3_resmap_supported(int terms) { return (terms == 0 || terms == 6) && g_s3_m16 != 0; }
 
+// the fields every launch has; the rest null / 0 (the launcher fills nbn, sm, sn, stagger, first_gen), scales 1
+static S3Args s3_args(const void* A3, const void* W3, int64_t M, int N, int K, int terms) {
+    S3Args a{};
+    a.A = static_cast<const unsigned char*>(A3);
+    a.W = static_cast<const unsigned char*>(W3);
+    a.M = M, a.N = N, a.K = K, a.terms = terms;
+    a.ab_inv = a.c_scale = a.ss_sqrt_d = 1.0f;
+    return a;
+}
+
 int gemm_bf16x3(const void* A3, const void* W3, const float* bias, const float* R, float* C, void* C3, int64_t M, int N, int K,
                 int act, int terms, hipStream_t st, float ab_scale, float c_scale, const float* ss_in, float eps, float* ss_out,
                 const float* gamma, int r_seg, int r_stride) {
@@ -1763,15 +1725,16 @@ int gemm_bf16x3(const void* A3, const void* W3, const float* bias, const float* 
     AVD_REQUIRE(!ss_in || (C3 && !C && K % 64 == 0), AVD_EUNSUPPORTED, "gemm_bf16x3: a folded norm needs an image output and K %% 64 == 0");
     AVD_REQUIRE(!ss_out || (C && C3 && R && bias && N % 64 == 0 && act == AVD_ACT_NONE && terms != 3), AVD_EUNSUPPORTED,
                 "gemm_bf16x3: sums of squares are written by the fp32 + image residual epilogue only (bf16 planes)");
-    AVD_REQUIRE(ab_scale > 0.f && ab_scale < __builtin_inff() && c_scale > 0.f && c_scale < __builtin_inff(), AVD_EINVAL,
-                "gemm_bf16x3: image scales must be positive and finite");
+    AVD_REQUIRE(scale_ok(ab_scale) && scale_ok(c_scale), AVD_EINVAL, "gemm_bf16x3: image scales must be positive and finite");
     AVD_REQUIRE(gemm_bf16x3_supported(M, N, K), AVD_EUNSUPPORTED, "gemm_bf16x3: need N %% 256 == 0 and K %% 16 == 0 (M=%lld N=%d K=%d)",
                 (long long)M, N, K);
     AVD_REQUIRE(aligned16(A3) && aligned16(W3) && aligned16(C) && aligned16(C3) && aligned16(bias) && aligned16(R), AVD_EUNSUPPORTED,
                 "gemm_bf16x3: pointers must be 16-byte aligned");
-    S3Args a{static_cast<const unsigned char*>(A3), static_cast<const unsigned char*>(W3), bias, R, C,
-             static_cast<unsigned char*>(C3), M, N, K, 0, 0, 0, 0, 0, 0, 0.f, 0, 0, terms, 1.0f / ab_scale, c_scale,
-             ss_in, ss_out, (float)sqrt((double)K), eps, gamma, r_seg, r_stride};
+    S3Args a = s3_args(A3, W3, M, N, K, terms);
+    a.bias = bias, a.R = R, a.C = C, a.C3 = static_cast<unsigned char*>(C3);
+    a.ab_inv = 1.0f / ab_scale, a.c_scale = c_scale;
+    a.ss_in = ss_in, a.ss_out = ss_out, a.ss_sqrt_d = (float)sqrt((double)K), a.ss_eps = eps;
+    a.gamma = gamma, a.r_seg = r_seg, a.r_stride = r_stride;
     if (gamma) {
         a.ss_sqrt_d = (float)sqrt((double)N);
         return launch_s3<S3_EPI_RES_NORM>(a, st);
@@ -1842,7 +1805,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 // well — 8,512 rows, 136 blocks x 2 slices = 272 blocks: the 16 CUs that get two blocks set the launch time, 130 + 21 us against 150 us
 // unsplit, profiles/r04_bench_128_splitk.txt — so a CU never gets more than one.)  The slices run on the 32x32x16 kernel (one-term and
 // nine-term modes, and the six-term mode when "s3_m16" is 0).  avd_tune_set "s3_splitk" (AVD_S3_SPLITK): 0 off, else the largest slice count tried.
-int g_s3_splitk = [] { const int v = getenv("AVD_S3_SPLITK") ? atoi(getenv("AVD_S3_SPLITK")) : 4; return v < 0 ? 0 : v > kS3SplitKMax ? kS3SplitKMax : v; }();
+int g_s3_splitk = 4;
 static bool splitk_shape_ok(int64_t M, int N, int K) {
     if (N % 128 || K % 32 || K / 2 < 512) return false;
     return (M + 255) / 256 * (N / 128) * 2 <= (int64_t)s3_cu_count();
@@ -1871,8 +1834,8 @@ int gemm_bf16x3_splitk(const void* A3, const void* W3, const float* bias, const 
                 "gemm_bf16x3_splitk: shape (M=%lld N=%d K=%d slices=%d)", (long long)M, N, K, ns);
     AVD_REQUIRE(aligned16(A3) && aligned16(W3) && aligned16(C) && aligned16(C3) && aligned16(bias) && aligned16(R) && aligned16(part),
                 AVD_EUNSUPPORTED, "gemm_bf16x3_splitk: pointers must be 16-byte aligned");
-    S3Args a{static_cast<const unsigned char*>(A3), static_cast<const unsigned char*>(W3), nullptr, nullptr, part, nullptr, M, N, K / ns,
-             0, 0, 0, 0, 0, 0, 0.f, 0, 0, terms, 1.0f, 1.0f, nullptr, nullptr, 1.0f, 0.f, nullptr, 0, 0};
+    S3Args a = s3_args(A3, W3, M, N, K / ns, terms);
+    a.C = part;
     int rc;
     switch (terms) {
         case 1: rc = launch_s3w<S3_EPI_BIAS, 1, 4>(a, st, ns); break;
@@ -1884,12 +1847,10 @@ int gemm_bf16x3_splitk(const void* A3, const void* W3, const float* bias, const 
     const int64_t threads = M * (N >> 3);
     static const int tag = prof_tag_id("splitk_reduce_kernel");
     ProfScope prof(tag, (double)M * N * 4.0 * (ns + 2) + (C3 ? (double)M * N * 6.0 : 0.0), st);
-    if (C3)
-        hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, part, ns, bias, R, C,
+    with_bool(C3 != nullptr, [&](auto img) {      // (ss comes with C3: both null without an image)
+        hipLaunchKernelGGL(splitk_reduce_kernel<img()>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, part, ns, bias, R, C,
                            static_cast<unsigned char*>(C3), ss, M, N);
-    else
-        hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, part, ns, bias, R, C,
-                           nullptr, nullptr, M, N);
+    });
     AVD_CHECK_LAUNCH("splitk_reduce");
     return AVD_OK;
 }
@@ -1899,17 +1860,18 @@ int gemm_bf16x3_qkv3(const void* A3, const void* W3, const float* bias, void* im
                      int terms, hipStream_t st, float ab_scale, float c_scale, const float* ss_in, float eps) {
     AVD_REQUIRE(!ss_in || K % 64 == 0, AVD_EUNSUPPORTED, "gemm_bf16x3_qkv3: a folded norm needs K %% 64 == 0");
     AVD_REQUIRE(A3 && W3 && bias && img, AVD_EINVAL, "gemm_bf16x3_qkv3: null pointer");
-    AVD_REQUIRE(ab_scale > 0.f && ab_scale < __builtin_inff() && c_scale > 0.f && c_scale < __builtin_inff(), AVD_EINVAL,
-                "gemm_bf16x3_qkv3: image scales must be positive and finite");
+    AVD_REQUIRE(scale_ok(ab_scale) && scale_ok(c_scale), AVD_EINVAL, "gemm_bf16x3_qkv3: image scales must be positive and finite");
     const int N = 3 * heads * 64;
     AVD_REQUIRE(tokens > 0 && heads > 0 && M > 0 && M % tokens == 0, AVD_EINVAL, "gemm_bf16x3_qkv3: rows %lld not a multiple of tokens %d",
                 (long long)M, tokens);
     AVD_REQUIRE(M < (1ll << 31) - 256, AVD_EUNSUPPORTED, "gemm_bf16x3_qkv3: more than 2^31 rows");
     AVD_REQUIRE(gemm_bf16x3_supported(M, N, K), AVD_EUNSUPPORTED, "gemm_bf16x3_qkv3: need 3*heads*64 %% 256 == 0 and K %% 16 == 0");
     AVD_REQUIRE(aligned16(A3) && aligned16(W3) && aligned16(bias) && aligned16(img), AVD_EUNSUPPORTED, "gemm_bf16x3_qkv3: alignment");
-    S3Args a{static_cast<const unsigned char*>(A3), static_cast<const unsigned char*>(W3), bias, nullptr, nullptr,
-             static_cast<unsigned char*>(img), M, N, K, 0, 0, 0, tokens, qkv3_npad(tokens), heads, qscale, 0, 0, terms, 1.0f / ab_scale, c_scale,
-             ss_in, nullptr, (float)sqrt((double)K), eps, nullptr, 0, 0};
+    S3Args a = s3_args(A3, W3, M, N, K, terms);
+    a.bias = bias, a.C3 = static_cast<unsigned char*>(img);
+    a.tokN = tokens, a.tokNpad = qkv3_npad(tokens), a.heads = heads, a.qscale = qscale;
+    a.ab_inv = 1.0f / ab_scale, a.c_scale = c_scale;
+    a.ss_in = ss_in, a.ss_sqrt_d = (float)sqrt((double)K), a.ss_eps = eps;
     return launch_s3<S3_EPI_QKV3>(a, st);
 }
 

@@ -555,8 +555,8 @@ unsigned long long* g_gemm_dbg = nullptr;
 extern "C" void lab_set_dbg(unsigned long long* p) { g_gemm_dbg = p; }
 extern "C" void lab_set_tile(int t);
 #endif
-int g_gemm_stages = getenv("AVD_GEMM_STAGES") ? atoi(getenv("AVD_GEMM_STAGES")) : 0;      // LDS ring depth of the 128x64 / 64x64 tiles: 0 = by size
-int g_gemm_force_tile = getenv("AVD_GEMM_TILE") ? atoi(getenv("AVD_GEMM_TILE")) : -1;
+int g_gemm_stages = 0;      // LDS ring depth of the 128x64 / 64x64 tiles: 0 = by size
+int g_gemm_force_tile = -1;
 
 #ifdef AVD_GEMM_STAMPS
 extern "C" void lab_set_tile(int t) { g_gemm_force_tile = t; }
@@ -642,7 +642,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_f32_kernel(const float* __r
     }
 }
 
-int g_gemm_splitk = getenv("AVD_GEMM_SPLITK") ? atoi(getenv("AVD_GEMM_SPLITK")) : 4;     // largest slice count tried (0 off); avd_tune_set "gemm_splitk"
+int g_gemm_splitk = 4;     // largest slice count tried (0 off); avd_tune_set "gemm_splitk"
 static int gemm_cu_count() {
     static std::atomic<int> cache[64];
     int dev = 0;

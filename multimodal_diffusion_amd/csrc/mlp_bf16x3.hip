@@ -249,7 +249,7 @@ __global__ __launch_bounds__(256, 1) void mlp_bf16x3_kernel(MlpArgs g) {
     s3_epilogue_img16<S3_EPI_RES_IMG, 8>(g.epi, acc2[1], m0, wave * 128 + 64, lane_e);
 }
 
-int g_mlp_fused = getenv("AVD_MLP_FUSED") ? atoi(getenv("AVD_MLP_FUSED")) : 0;
+int g_mlp_fused = 0;
 
 bool mlp_bf16x3_supported(int d, int hidden, int terms) { return d == ML_D && hidden > 0 && hidden % 128 == 0 && (terms == 0 || terms == 6); }
 

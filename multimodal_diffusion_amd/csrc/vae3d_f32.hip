@@ -1422,12 +1422,12 @@ template <int TERMS> static int conv3_blocks(int T, int H, int W) {
 static int conv3_tiles(int terms, int T, int H, int W) {
     return terms == 3 ? conv3_blocks<3>(T, H, W) * (HaloCfg<3>::VOX / 128) : conv3_blocks<6>(T, H, W) * (HaloCfg<6>::VOX / 128);
 }
-int g_vae_lat = getenv("AVD_VAE_LAT") ? atoi(getenv("AVD_VAE_LAT")) : 1;      // avd_tune_set "vae_lat": 0 = from_lat -> upsample -> 64-channel first conv
+int g_vae_lat = 1;      // avd_tune_set "vae_lat": 0 = from_lat -> upsample -> 64-channel first conv
 static LdsAttr g_conv3_lat_attr[2];
 // avd_tune_set "vae_fold" (AVD_VAE_FOLD): 1 (default) = the three-plane decoder with two conv blocks and a latent-composed first conv writes
 // conv 0's output straight into conv 1's operand image, folds the GroupNorm between them into conv 1's per-sample weights, and finishes
 // to_img from per-group partial sums of conv 1's epilogue; 0 = fp32 activations between the kernels (rounds 1-4)
-int g_vae_fold = getenv("AVD_VAE_FOLD") ? atoi(getenv("AVD_VAE_FOLD")) : 1;
+int g_vae_fold = 1;
 static LdsAttr g_conv3_fold_attr[3];
 template <int TERMS, int NSLAB, int OUT>
 static int conv3_launch_as(const Conv3Args& a3, int B, double flops, hipStream_t st, LdsAttr& attr, const char* what) {

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import _dpm_ref as D
+from _tune import cfg_rows  # noqa: F401  (fixture)
 from conftest import rel_err
 from oracle import ref_cpu as R
 
@@ -33,19 +34,6 @@ def model(dev):
     av.load_state_dict(ws["adapt_v"])
     aa.load_state_dict(ws["adapt_a"])
     return ws, tuple(m.to(dev) for m in (core, head, av, aa))
-
-
-@pytest.fixture
-def cfg_rows():
-    """sets the avd_tune_set "cfg_rows" key for one test and restores the library default (1) afterwards"""
-    from multimodal_diffusion_amd import _lib as L
-
-    def set_(v):
-        L.check(L.lib().avd_tune_set(b"cfg_rows", v))
-    try:
-        yield set_
-    finally:
-        set_(1)
 
 
 def _engine(model, target, shape, n_prompt, **kw):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from _tune import tuned
 from conftest import rel_err
 from oracle import ref_cpu as R
 from test_gpu_parity import TOL, _full_modules, dev, full  # noqa: F401  (dev / full are fixtures)
@@ -667,11 +668,8 @@ def test_block_stagger_changes_timing_only(dev, full):
     x = torch.randn(64, 421, 512, generator=torch.Generator().manual_seed(21)).to(dev)      # 26,944 rows: two generations of blocks
     outs = []
     for v in (0, -1, 40):
-        L.check(L.lib().avd_tune_set(b"s3_stagger", v))
-        try:
+        with tuned(s3_stagger=v):
             outs.append(core(x))
-        finally:
-            L.check(L.lib().avd_tune_set(b"s3_stagger", -1))
     assert torch.isfinite(outs[0]).all() and torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
 
 

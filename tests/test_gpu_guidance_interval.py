@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import _interval_ref as IR
+from _tune import cfg_rows, tune, tuned  # noqa: F401  (cfg_rows is a fixture)
 from conftest import rel_err
 from oracle import ref_cpu as R
 
@@ -47,19 +48,6 @@ def model(dev):
 def full(dev):
     ws = R.synth_weights(seed=0)
     return ws, _modules(dev, ws, 8)
-
-
-def _tune(key, v):
-    from multimodal_diffusion_amd import _lib as L
-    L.check(L.lib().avd_tune_set(key.encode(), v))
-
-
-@pytest.fixture
-def cfg_rows():
-    try:
-        yield lambda v: _tune("cfg_rows", v)
-    finally:
-        _tune("cfg_rows", 1)
 
 
 def _engine(model, target, shape, n_prompt, guidance=GS, **kw):
@@ -239,9 +227,9 @@ def _check_cond_step(dev, model, n_layers, target, mode, z, zp, npr):
     ws = model[0]
     B = z.shape[0]
     tn, tp = _t([982, 500, 16, 999][:B], dev), _t([966, 480, -1, 979][:B], dev)
-    try:
+    with tuned("s3_min_rows"):
         if mode != "f32":
-            _tune("s3_min_rows", 0)             # let the split-operand kernels engage at these row counts
+            tune("s3_min_rows", 0)             # let the split-operand kernels engage at these row counts
         eng = _engine(model, target, tuple(z.shape), npr, matmul=mode)
         eng.set_prompt(zp)
         out = eng.step(z, tn, tp, cond_only=True)
@@ -260,8 +248,6 @@ def _check_cond_step(dev, model, n_layers, target, mode, z, zp, npr):
         assert torch.equal(eng2.step(z, tn, tp), cfg)
         assert torch.equal(eng2.step(z, tn, tp, cond_only=True), out)
         assert not torch.equal(out, cfg)
-    finally:
-        _tune("s3_min_rows", -1)
 
 
 @pytest.mark.parametrize("mode", ["f32", "bf16x3", "f16x2"])

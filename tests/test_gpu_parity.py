@@ -9,12 +9,12 @@ import numpy as np
 import pytest
 import torch
 
+from _tune import tune, tuned
 from conftest import load_golden, rel_err, split_weights
 from oracle import ref_cpu as R
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
-W128_DEFAULT = 1      # library default of the "s3_w128" tune key
 
 
 @pytest.fixture(scope="module")
@@ -530,21 +530,51 @@ def test_audio_codec_golden(dev):
     torch.cuda.synchronize()
     L.prof_enable(False)
     assert L.prof_report()["conv1d_mfma_kernel"][0] == 2
-    try:
-        _tune("codec_mfma", 0)
+    with tuned(codec_mfma=0):
         z0, w0 = codec.encode(G(g["wav"], dev)).cpu(), codec.decode(G(g["z_in"], dev)).cpu()
-    finally:
-        _tune("codec_mfma", 1)
     L.prof_enable(True)
     try:
-        _tune("codec_mfma", 0)
-        codec.decode(G(g["z_in"], dev))
-        torch.cuda.synchronize()
+        with tuned(codec_mfma=0):
+            codec.decode(G(g["z_in"], dev))
+            torch.cuda.synchronize()
     finally:
-        _tune("codec_mfma", 1)
         L.prof_enable(False)
     assert L.prof_report()["conv1d_mfma_kernel"][0] == 0 and L.prof_report()["conv1d_ncl_kernel"][0] == 4
     assert torch.equal(z, z0) and torch.equal(w, w0)
+
+
+_CODEC_ENV_CHILD = """
+import json, sys, torch
+from conftest import load_golden, split_weights
+from multimodal_diffusion_amd import _lib as L
+from multimodal_diffusion_amd.audio_codec import AudioCodec
+g = load_golden("g13_audio_codec.npz")
+codec = AudioCodec.from_config({"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150},
+                                "codec": {"hop_samples": 320, "hidden": 64, "smooth_kernel": 7}}).eval()
+codec.load_state_dict(split_weights(g)["w"], strict=True)
+codec = codec.to("cuda:0")
+L.prof_enable(True)
+codec.decode(torch.from_numpy(g["z_in"]).to("cuda:0"))
+torch.cuda.synchronize()
+L.prof_enable(False)
+print(json.dumps({k: v[0] for k, v in L.prof_report().items() if k.startswith("conv1d")}))
+"""
+
+
+@pytest.mark.gpu_first
+def test_tune_key_from_the_environment():
+    """The environment path of the tune-key table (csrc/composite.hip): a fresh process started with AVD_CODEC_MFMA=0 decodes the
+    golden codec input on the vector kernel only — what avd_tune_set "codec_mfma" 0 selects in test_audio_codec_golden."""
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    path = [str(ROOT), str(ROOT / "tests")] + [p for p in os.environ.get("PYTHONPATH", "").split(os.pathsep) if p]
+    env = dict(os.environ, AVD_CODEC_MFMA="0", PYTHONPATH=os.pathsep.join(path))
+    r = subprocess.run([sys.executable, "-c", _CODEC_ENV_CHILD], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+    used = json.loads(r.stdout.strip().splitlines()[-1])
+    assert used.get("conv1d_ncl_kernel", 0) > 0 and used.get("conv1d_mfma_kernel", 0) == 0, used
 
 
 def test_sample_one_direction_end_to_end(dev, full):
@@ -621,13 +651,11 @@ def test_sample_one_direction_shipped_config_golden(dev, mode):
     rec = {}
     dec0 = vae.decode
     vae.decode = lambda z, *a, **k: (rec.__setitem__("z", z.clone()), dec0(z, *a, **k))[1]
-    try:
+    with tuned("s3_min_rows"):
         if mode == "bf16x3":
-            _tune("s3_min_rows", 0)
+            tune("s3_min_rows", 0)
         res = A.sample_one_direction(cfg=cfg, vid_vae=vae, aud_codec=codec, adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=tdim,
                                      prompt_modality="audio", prompt_video=None, prompt_audio=wav, device=dev, init_noise=T(g["z_init"]))
-    finally:
-        _tune("s3_min_rows", -1)
     ref = T(g["z_final"]).double()
     l2 = float((rec["z"].cpu().double() - ref).norm() / ref.norm())
     assert l2 < 1e-3, (mode, l2)              # chained tolerance
@@ -653,15 +681,13 @@ def test_chain_full_width_vs_oracle(dev, full, mode):
     ref = R.sample_a2v(z, za, R.sampling_schedule(1000, 10), abar, adapt_v=ws["adapt_v"], adapt_a=ws["adapt_a"], core=ws["core"],
                        head=ws["head"], n_layers=8, n_heads=8, guidance=3.5).double()
     core, head, av, aa = _full_modules(dev, ws)
-    try:
+    with tuned("s3_min_rows"):
         if mode == "f16x2":
-            _tune("s3_min_rows", 0)
+            tune("s3_min_rows", 0)
         eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video", latent_shape=tuple(z.shape),
                               prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul=mode)
         eng.set_prompt(za.to(dev))
         out = eng.run(z.to(dev), sched)
-    finally:
-        _tune("s3_min_rows", -1)
     l2 = float((out.cpu().double() - ref).norm() / ref.norm())
     assert torch.isfinite(out).all() and l2 < 1e-3, (mode, l2)       # chained tolerance; final |z| ~ 1e4
 
@@ -975,16 +1001,14 @@ def test_attention_m16_shape(dev, B, N, H, nq, terms):
     q, k, v = (full[:, :, i].transpose(1, 2) for i in range(3))
     ref = (torch.softmax(q @ k.transpose(-1, -2) / 8.0, dim=-1) @ v).transpose(1, 2).reshape(B, N, d)
     outs = {}
-    try:
+    with tuned("attn_m16"):
         for m16 in (0, 2):
-            _tune("attn_m16", m16)
+            tune("attn_m16", m16)
             out = torch.full((B, N, d), 7.0, device=dev)
             L.check(lib.avd_attn_fwd_qkv3_f32(img.data_ptr(), out.data_ptr(), None, B, N, H, nq, terms, L.stream_ptr(dev)))
             outs[m16] = out.cpu()
         o3 = torch.zeros(lib.avd_split3_bytes(B * N, d), dtype=torch.uint8, device=dev)
         L.check(lib.avd_attn_fwd_qkv3_f32(img.data_ptr(), None, o3.data_ptr(), B, N, H, nq, terms, L.stream_ptr(dev)))
-    finally:
-        _tune("attn_m16", 0)
     tol = 2e-6 if terms != 1 else 2e-2          # (one plane: plain bf16 operands, reduced precision)
     e16, e32 = rel_err(outs[2][:, :nq], ref[:, :nq]), rel_err(outs[0][:, :nq], ref[:, :nq])
     assert e16 < tol and e16 < 2.0 * e32 + 2e-7, (e16, e32)
@@ -1069,9 +1093,9 @@ def test_vae_decode_folded_route(dev, mode):
     from multimodal_diffusion_amd import _lib as L
     g = load_golden("g11_vae_decode.npz")
     outs = {}
-    try:
+    with tuned("vae_fold"):
         for fold in (0, 1):
-            _tune("vae_fold", fold)
+            tune("vae_fold", fold)
             vae = _vae_from(split_weights(g)["w"], dev)
             vae.matmul = mode
             L.prof_enable(True)
@@ -1096,14 +1120,12 @@ def test_vae_decode_folded_route(dev, mode):
         ref = R.vae_decode(z.double(), {k: v.double() for k, v in W.items()}, n_blocks=2)
         errs = {}
         for fold in (0, 1):
-            _tune("vae_fold", fold)
+            tune("vae_fold", fold)
             v = A.VideoVAE(A.VideoVAEConfig(dec_blocks=2)).eval()
             v.load_state_dict(W, strict=False)
             v.matmul = mode
             errs[fold] = rel_err(v.to(dev).decode(z.to(dev)).cpu(), ref)
         assert errs[1] < TOL and errs[1] < 3.0 * errs[0] + 1e-6, errs
-    finally:
-        _tune("vae_fold", 1)
 
 
 def test_vae_encode_bf16x3(dev):
@@ -1137,9 +1159,9 @@ def test_vae_encode_folded_route(dev):
     g = load_golden("g12_vae_encode.npz")
     for mode in ("bf16x3", "f16x2"):
         outs = {}
-        try:
+        with tuned("vae_fold"):
             for fold in (0, 1):
-                _tune("vae_fold", fold)
+                tune("vae_fold", fold)
                 vae = A.VideoVAE.from_config({"latent": {"channels": 8, "t_down": 4, "s_down": 8}}).eval()
                 vae.load_state_dict(split_weights(g)["w"], strict=False)
                 vae = vae.to(dev)
@@ -1158,8 +1180,6 @@ def test_vae_encode_folded_route(dev):
                     outs[fold] = (z, vae.encode(G(g["x_crop"], dev)).cpu())
             assert rel_err(outs[1][0], g["z"]) < TOL and rel_err(outs[1][1], g["z_crop"]) < TOL
             assert rel_err(outs[1][0], outs[0][0]) < 2e-5 and rel_err(outs[1][1], outs[0][1]) < 2e-5
-        finally:
-            _tune("vae_fold", 1)
 
 
 def test_full_step_v2a_bf16x3(dev, full):
@@ -1208,15 +1228,12 @@ def test_cfg_unpatch_ddim_row_form_is_bit_identical(dev, B, C, T, H, W, eta):
     d_eps, d_z, d_tn, d_tp, d_ab = eps2.to(dev), z.to(dev), tn.to(dev), tp.to(dev), abar.to(dev)     # (kept alive across the launches)
     d_noise = None if noise is None else noise.to(dev)
     for rows in (0, 1):
-        _tune("cfg_rows", rows)
-        try:
+        with tuned(cfg_rows=rows):
             out = torch.empty(B, C, T, H, W, device=dev)
             L.check(L.lib().avd_cfg_unpatch_ddim_f32(d_eps.data_ptr(), d_z.data_ptr(), d_tn.data_ptr(), d_tp.data_ptr(), d_ab.data_ptr(), 1000, 3.5,
                                                      eta, L.ptr(d_noise), out.data_ptr(), B, C, T, H, W, 2, 4, 4, L.stream_ptr(dev)))
             torch.cuda.synchronize()
             outs[rows] = out.cpu()
-        finally:
-            _tune("cfg_rows", 1)
     assert torch.equal(outs[0], outs[1])
     e = eps2[B:] + 3.5 * (eps2[:B] - eps2[B:])
     if eta == 0:
@@ -1225,11 +1242,6 @@ def test_cfg_unpatch_ddim_row_form_is_bit_identical(dev, B, C, T, H, W, eta):
 
 
 # ------------------------------------------------------------------------------------------------- round-2 coverage
-def _tune(key, value):
-    from multimodal_diffusion_amd import _lib as L
-    L.check(L.lib().avd_tune_set(key.encode(), value))
-
-
 def _sample_rows(M, g):
     idx = torch.cat([torch.arange(0, min(M, 192)), torch.arange(max(0, M - 192), M),
                      torch.randint(0, M, (384,), generator=g)]).unique()
@@ -1254,12 +1266,9 @@ def test_gemm_dma_templates_direct(dev, tile, M, N, K, mode):
         ref = R.gelu_erf(ref)
     if mode == "res":
         ref = ref + r[idx].double()
-    _tune("gemm_tile", tile)
-    try:
+    with tuned(gemm_tile=tile):
         y = Fn.linear(x.to(dev), w.to(dev), b.to(dev), act=L.ACT_GELU if mode == "gelu" else L.ACT_NONE,
                       residual=r.to(dev) if mode == "res" else None)
-    finally:
-        _tune("gemm_tile", -1)
     assert torch.isfinite(y).all()
     assert rel_err(y.cpu()[idx], ref) < 2e-5
 
@@ -1281,15 +1290,12 @@ def test_gemm_rmsfold_epilogue_direct(dev, tile, M):
     w1 = torch.randn(hid, d, generator=g) / math.sqrt(d)
     b1 = torch.randn(hid, generator=g) * 0.1
     idx = _sample_rows(M, g)
-    _tune("gemm_tile", tile)
-    try:
+    with tuned(gemm_tile=tile):
         x1, ss = Fn.linear_rmsfold(a.to(dev), w0.to(dev), b0.to(dev), residual=x0.to(dev), want_ss=True)
         y, _ = Fn.linear_rmsfold(x1, (w1 * scale[None, :]).to(dev), b1.to(dev), act=L.ACT_GELU, ss_in=ss, eps=1e-6)
         # the one-column table form (first block: rowss kernel)
         ss1 = (x1 * x1).sum(-1, keepdim=True).contiguous()
         y1, _ = Fn.linear_rmsfold(x1, (w1 * scale[None, :]).to(dev), b1.to(dev), act=L.ACT_GELU, ss_in=ss1, eps=1e-6)
-    finally:
-        _tune("gemm_tile", -1)
     x1_ref = x0[idx].double() + R.linear(a[idx].double(), w0.double(), b0.double())
     assert rel_err(x1.cpu()[idx], x1_ref) < 2e-5
     chunks = x1.cpu().double().view(M, d // 32, 32).pow(2).sum(-1)
@@ -1396,16 +1402,14 @@ def test_vae_decode_512_routes_agree(dev):
     W = R.synth_vae_decoder(seed=9, n_blocks=2)
     z = torch.randn(1, 8, 12, 64, 64, generator=torch.Generator().manual_seed(10)).to(dev)
     outs = {}
-    try:
+    with tuned("vae_fold"):
         for route in ("default", "three passes"):
-            _tune("vae_fold", 1 if route == "default" else 0)
+            tune("vae_fold", 1 if route == "default" else 0)
             vae = A.VideoVAE(A.VideoVAEConfig()).eval()
             vae.load_state_dict(W, strict=False)
             vae.matmul, vae.lat_composed = "bf16x3", route == "default"
             outs[route] = vae.to(dev).decode(z)
             del vae
-    finally:
-        _tune("vae_fold", 1)
     assert outs["default"].shape == (1, 3, 48, 512, 512) and bool(torch.isfinite(outs["default"]).all())
     assert float((outs["default"] - outs["three passes"]).abs().max()) < 2e-5
 
@@ -1572,15 +1576,12 @@ def test_last_block_runs_on_the_output_window_only(dev, full, B, N, nq):
         wsb = torch.empty(L.lib().avd_core_workspace_bytes(C.byref(cw), B, N), dtype=torch.uint8, device=dev)
 
         def fwd(rows, trim):
-            _tune("core_trim", trim)
-            try:
+            with tuned(core_trim=trim):
                 y = torch.zeros_like(x)
                 L.check(L.lib().avd_core_forward_f32(C.byref(cw), x.data_ptr(), y.data_ptr(), B, N, 0, rows, None, wsb.data_ptr(), wsb.numel(),
                                                      L.stream_ptr(dev)))
                 torch.cuda.synchronize()
                 return y
-            finally:
-                _tune("core_trim", 1)
         whole = fwd(N, 1)
         assert torch.isfinite(whole).all()
         assert rel_err(whole[:1].cpu(), R.mmdit_forward(x[:1].cpu(), ws["core"], 8, 8)) < TOL
@@ -1610,11 +1611,10 @@ def test_fused_mlp_matches_two_launches(dev, full, B):
     tn = torch.tensor(([982, 500, 16, 999] * B)[:B])
     tp = torch.tensor(([966, 480, -1, 979] * B)[:B])
     outs = {}
-    try:
-        _tune("s3_splitk", 0)                # (split-K of fc2 and the fused launch exclude each other: keep both arms on whole-K sums)
+    with tuned("mlp_fused", "core_trim", s3_splitk=0):        # (split-K of fc2 and the fused launch exclude each other: keep both arms on whole-K sums)
         for fused, trim in ((0, 1), (1, 1), (1, 0)):
-            _tune("mlp_fused", fused)
-            _tune("core_trim", trim)
+            tune("mlp_fused", fused)
+            tune("core_trim", trim)
             eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video", latent_shape=tuple(z_v.shape),
                                   prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul="bf16x3")
             eng.set_prompt(z_a.to(dev))
@@ -1627,10 +1627,6 @@ def test_fused_mlp_matches_two_launches(dev, full, B):
             assert (rep.get("mlp_bf16x3_kernel", (0,))[0] > 0) == bool(fused), rep.keys()
             if fused:
                 print(f"fused MLP, B={B}, trim={trim}: {1e3 * rep['mlp_bf16x3_kernel'][1] / rep['mlp_bf16x3_kernel'][0]:.1f} us per launch")
-    finally:
-        _tune("mlp_fused", 0)
-        _tune("core_trim", 1)
-        _tune("s3_splitk", 4)
     assert torch.isfinite(outs[0, 1]).all() and torch.isfinite(outs[1, 1]).all()
     d1, d0 = rel_err(outs[1, 1], outs[0, 1]), rel_err(outs[1, 0], outs[0, 1])
     assert torch.equal(outs[1, 0], outs[1, 1])                 # the fused path with and without the trimmed last block: bit-identical
@@ -1651,9 +1647,9 @@ def test_f32_splitk_tiny_batch(dev, full):
     from multimodal_diffusion_amd import _lib as L
     ws, mods = full
     outs = []
-    try:
+    with tuned("gemm_splitk"):
         for ns in (4, 0, 4):
-            _tune("gemm_splitk", ns)
+            tune("gemm_splitk", ns)
             L.prof_enable(True)
             out, ref = _one_step(dev, mods, ws, 32, 4, 4, matmul="f32")
             torch.cuda.synchronize()
@@ -1661,8 +1657,6 @@ def test_f32_splitk_tiny_batch(dev, full):
             ran = L.prof_report().get("splitk_reduce_f32_kernel", (0,))[0] > 0
             assert ran == (ns > 0), (ns, ran)
             outs.append(out)
-    finally:
-        _tune("gemm_splitk", 4)
     assert torch.equal(outs[0], outs[2]) and not torch.equal(outs[0], outs[1])
     d, e4, e0 = rel_err(outs[0], outs[1]), rel_err(outs[0], ref), rel_err(outs[1], ref)
     print(f"fp32 split-K fc2 at C1: vs one launch {d:.2e}; vs CPU oracle {e4:.3e} (one launch {e0:.3e})")
@@ -1733,18 +1727,14 @@ def test_split_gemm_short_blocks_ragged_rows(dev, N, K):
         x3 = Fn.split3(x.to(dev))
         ref = x.double() @ w.double().t() + b.double()
         outs = {}
-        try:
+        with tuned("s3_rt4", "s3_deep4", "s3_tile"):
             for rt, deep in ((8, 0), (8, 1), (7, 1), (6, 0), (5, 1), (4, 0), (3, 1), (2, 0), (2, 1), (0, 1)):
-                _tune("s3_rt4", rt)
-                _tune("s3_deep4", deep)
-                _tune("s3_tile", 1)
+                tune("s3_rt4", rt)
+                tune("s3_deep4", deep)
+                tune("s3_tile", 1)
                 outs[rt, deep] = (Fn.linear_bf16x3(x3, M, w3, N, K, bias=b.to(dev)).cpu(),
                                   Fn.linear_bf16x3(x3, M, w3, N, K, bias=b.to(dev), residual=r.to(dev)).cpu(),
                                   Fn.linear_bf16x3(x3, M, w3, N, K, bias=b.to(dev), act=L.ACT_GELU, out_split3=True).cpu())
-        finally:
-            _tune("s3_rt4", 0)
-            _tune("s3_deep4", 1)
-            _tune("s3_tile", -1)
         base = outs[8, 0]
         bound = 2.0 * K * 2.0 ** -24 * (x.double().abs() @ w.double().abs().t() + b.double().abs()) + 1e-30
         assert ((base[0].double() - ref).abs() <= bound).all(), (M, float(((base[0].double() - ref).abs() / bound).max()))
@@ -1950,11 +1940,7 @@ def test_split_gemm_short_four_wave_blocks_agree(dev, full, size, B):
     tp = torch.tensor(([966, 480, -1, 979] * B)[:B])
     outs, names = {}, {}
     for rt, deep in ((8, 0), (8, 1), (7, 0), (6, 0), (5, 0), (5, 1), (6, 1), (4, 0), (4, 1), (3, 0), (3, 1), (2, 0), (2, 1), (0, 1)):
-        _tune("s3_rt4", rt)
-        _tune("s3_deep4", deep)
-        _tune("s3_min_rows", 1)
-        _tune("s3_tile", 1)
-        try:
+        with tuned(s3_rt4=rt, s3_deep4=deep, s3_min_rows=1, s3_tile=1):
             eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video", latent_shape=tuple(z_v.shape),
                                   prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul="bf16x3")
             eng.set_prompt(z_a.to(dev))
@@ -1963,11 +1949,6 @@ def test_split_gemm_short_four_wave_blocks_agree(dev, full, size, B):
             torch.cuda.synchronize()
             L.prof_enable(False)
             names[rt, deep] = sorted(k[len("gemm_bf16x3_m16_kernel"):] for k, v in L.prof_report().items() if k.startswith("gemm_bf16x3_m16_kernel") and v[0] > 0)
-        finally:
-            _tune("s3_rt4", 0)
-            _tune("s3_deep4", 1)
-            _tune("s3_min_rows", -1)
-            _tune("s3_tile", -1)
     base = outs[8, 0]
     assert torch.isfinite(base).all()
     for key, out in outs.items():
@@ -2003,18 +1984,11 @@ def test_split_gemm_block_rows_agree(dev, full, size, B):
     tp = torch.tensor(([966, 480, -1, 979] * B)[:B])
     outs = {}
     for rt, w128 in ((7, 0), (8, 0), (0, 0), (7, 1), (8, 1), (6, 1), (0, 1)):
-        _tune("s3_rt", rt)
-        _tune("s3_w128", w128)
-        _tune("s3_tile", 0 if B == 5 else -1)
-        try:
+        with tuned(s3_rt=rt, s3_w128=w128, s3_tile=0 if B == 5 else -1):
             eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video", latent_shape=tuple(z_v.shape),
                                   prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul="bf16x3")
             eng.set_prompt(z_a.to(dev))
             outs[rt, w128] = eng.step(z_v.to(dev), tn.to(dev), tp.to(dev)).cpu()
-        finally:
-            _tune("s3_rt", 0)
-            _tune("s3_w128", W128_DEFAULT)
-            _tune("s3_tile", -1)
     assert torch.isfinite(outs[7, 0]).all()
     assert torch.equal(outs[7, 0], outs[8, 0])
     assert torch.equal(outs[0, 0], outs[8, 0])
@@ -2047,14 +2021,11 @@ def test_f16x2_rownorm_epilogue_matches_norm_kernel(dev, full, B):
     tp = torch.tensor(([966, 480, -1, 979] * B)[:B])
     outs = []
     for no_fold in (0, 1):
-        _tune("no_fold", no_fold)
-        try:
+        with tuned(no_fold=no_fold):
             eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video", latent_shape=tuple(z_v.shape),
                                   prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul="f16x2")
             eng.set_prompt(z_a.to(dev))
             outs.append(eng.step(z_v.to(dev), tn.to(dev), tp.to(dev)).cpu())
-        finally:
-            _tune("no_fold", 0)
     assert torch.isfinite(outs[0]).all()
     d = rel_err(outs[0], outs[1])
     print(f"f16x2 row-norm epilogue vs norm kernel, B={B}: {d:.3e}")
@@ -2076,15 +2047,11 @@ def test_splitk_small_batch_fc2(dev, full, matmul):
     forced onto the split kernels at this size) is held to the parity tolerance against the CPU oracle."""
     ws, mods = full
     outs = []
-    try:
-        _tune("s3_min_rows", 0)
+    with tuned("s3_splitk", s3_min_rows=0):
         for ns in (4, 0, 4):
-            _tune("s3_splitk", ns)
+            tune("s3_splitk", ns)
             out, ref = _one_step(dev, mods, ws, 64, 32, 2, matmul=matmul)
             outs.append(out)
-    finally:
-        _tune("s3_splitk", 4)
-        _tune("s3_min_rows", -1)
     assert torch.isfinite(outs[0]).all()
     assert torch.equal(outs[0], outs[2])
     d = rel_err(outs[0], outs[1])
@@ -2116,8 +2083,7 @@ def test_split_gemm_tile_configurations_agree(dev):
         for mode in ("bf16x3", "bf16x3_strict", "bf16", "f16x2"):
             outs = []
             for tile in (0, 1):
-                _tune("s3_tile", tile)
-                try:
+                with tuned(s3_tile=tile):
                     if mode == "f16x2":
                         x2, sx = Fn.split_f16x2(x)
                         w2, sw = Fn.split_f16x2(w)
@@ -2128,8 +2094,6 @@ def test_split_gemm_tile_configurations_agree(dev):
                         x3, w3 = Fn.split3(x), Fn.split3(w)
                         y = Fn.linear_bf16x3(x3, M, w3, N, K, bias=b, residual=r, terms=terms)
                         img = Fn.linear_bf16x3(x3, M, w3, N, K, bias=b, act=L.ACT_GELU, out_split3=True, terms=terms)
-                finally:
-                    _tune("s3_tile", -1)
                 outs.append((y, img))
             assert torch.equal(outs[0][0], outs[1][0]), (mode, M, N, K)
             if M % 256 == 0:          # whole image defined (rows past M inside the last 256-row tile are never written)

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from _noise_ref import normals
+from _tune import cfg_rows  # noqa: F401  (fixture)
 from oracle import ref_cpu as R
 
 pytestmark = pytest.mark.gpu
@@ -39,19 +40,6 @@ def model(dev):
     av.load_state_dict(ws["adapt_v"])
     aa.load_state_dict(ws["adapt_a"])
     return ws, tuple(m.to(dev) for m in (core, head, av, aa))
-
-
-@pytest.fixture
-def cfg_rows():
-    """sets the avd_tune_set "cfg_rows" key for one test and restores the library default (1) afterwards"""
-    from multimodal_diffusion_amd import _lib as L
-
-    def set_(v):
-        L.check(L.lib().avd_tune_set(b"cfg_rows", v))
-    try:
-        yield set_
-    finally:
-        set_(1)
 
 
 ABAR = R.alpha_bar_table(R.beta_table(1000))
