@@ -15,6 +15,7 @@
 #include "avd_common.h"
 
 #include <stdlib.h>
+#include <string>
 #include <type_traits>
 #include <utility>
 
@@ -1411,8 +1412,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_bf16x3_kernel(Conv3Args g) {
     }
 }
 
-// launch of one 64 -> 64 convolution on the 16-bit matrix pipe (terms 0 / 6: bf16x3, 3: f16x2)
-static LdsAttr g_conv3_attr[2];      // dynamic-LDS limit of conv3d_k3_bf16x3_kernel<6> / <3> (per device)
+// ---- host side: one launch path for the halo-tile convolution, the steps the two directions share, one workspace layout and one route
+// decision per direction (vae_dec_route / vae_enc_route), one function per route ----
 // blocks per sample of the halo-tile kernel, and the number of 128-voxel "tiles" its GroupNorm partials amount to (one partials
 // entry per 64 voxels of every block, whether the tile is ragged or not): what gn_finalize_kernel sums over for this conv
 template <int TERMS> static int conv3_blocks(int T, int H, int W) {
@@ -1423,88 +1424,71 @@ static int conv3_tiles(int terms, int T, int H, int W) {
     return terms == 3 ? conv3_blocks<3>(T, H, W) * (HaloCfg<3>::VOX / 128) : conv3_blocks<6>(T, H, W) * (HaloCfg<6>::VOX / 128);
 }
 int g_vae_lat = 1;      // avd_tune_set "vae_lat": 0 = from_lat -> upsample -> 64-channel first conv
-static LdsAttr g_conv3_lat_attr[2];
 // avd_tune_set "vae_fold" (AVD_VAE_FOLD): 1 (default) = the three-plane decoder with two conv blocks and a latent-composed first conv writes
 // conv 0's output straight into conv 1's operand image, folds the GroupNorm between them into conv 1's per-sample weights, and finishes
 // to_img from per-group partial sums of conv 1's epilogue; 0 = fp32 activations between the kernels (rounds 1-4)
 int g_vae_fold = 1;
-static LdsAttr g_conv3_fold_attr[3];
+
+// the kernels that exist in a <true> and a <false> form (F16: two scaled fp16 planes): f receives the flag as an integral_constant
+template <typename F> static void with_f16(bool f16, F&& f) { f16 ? f(std::true_type{}) : f(std::false_type{}); }
+
+// What one halo-tile convolution reads and writes = the NSLAB and OUT arguments of conv3d_k3_bf16x3_kernel.
+enum class ConvIn { Full64, Lat, LatPacked };       // 64 channels in four slab images | the 96-byte latent image | that image, two taps per k-step
+enum class ConvOut { Act, Image, ToImgP, PoolP };   // fp32 activations | the next conv's operand image | to_img partial sums | pooling partial sums
+
+static std::string conv3_what(int terms, int nslab, int out) {
+    const char* const in_s = nslab == 4 ? "" : nslab == 1 ? "latent" : "latent, packed taps";
+    const char* const out_s = out == 0 ? "" : out == 1 ? "image out" : out == 2 ? "to_img partials out" : "pooling partials out";
+    std::string s = terms == 3 ? "conv3d f16x2" : "conv3d bf16x3";
+    if (*in_s || *out_s) s += std::string(" (") + in_s + (*in_s && *out_s ? ", " : "") + out_s + ")";
+    return s;
+}
 template <int TERMS, int NSLAB, int OUT>
-static int conv3_launch_as(const Conv3Args& a3, int B, double flops, hipStream_t st, LdsAttr& attr, const char* what) {
+static int conv3_launch_as(const Conv3Args& a3, int B, double flops, hipStream_t st) {
     auto kern = conv3d_k3_bf16x3_kernel<TERMS, NSLAB, OUT>;
-    if (int rc = attr.ensure(reinterpret_cast<const void*>(kern), HaloCfg<TERMS>::LDS, what)) return rc;
+    static LdsAttr attr;        // dynamic-LDS limit of this instantiation (per device)
+    static const std::string what = conv3_what(TERMS, NSLAB, OUT);
+    if (int rc = attr.ensure(reinterpret_cast<const void*>(kern), HaloCfg<TERMS>::LDS, what.c_str())) return rc;
     static const int tag = prof_tag_id("conv3d_k3_bf16x3_kernel<%d, %d, %d>", TERMS, NSLAB, OUT);
     ProfScope prof(tag, flops, st);
     hipLaunchKernelGGL(kern, dim3((unsigned)(B * conv3_blocks<TERMS>(a3.T, a3.H, a3.W))), dim3(256), HaloCfg<TERMS>::LDS, st, a3);
-    AVD_CHECK_LAUNCH(what);
+    AVD_CHECK_LAUNCH(what.c_str());
     return AVD_OK;
 }
-static LdsAttr g_conv3_pk_attr[3];
-static int conv3_launch(Conv3Args a3, int terms, int B, double flops, hipStream_t st, bool lat = false, int out_mode = 0, bool packed = false) {
+template <int NSLAB, int OUT>
+static int conv3_launch_terms(int terms, const Conv3Args& a3, int B, double flops, hipStream_t st) {
+    return terms == 3 ? conv3_launch_as<3, NSLAB, OUT>(a3, B, flops, st) : conv3_launch_as<6, NSLAB, OUT>(a3, B, flops, st);
+}
+// The one place that says which (input, output) kinds exist, what each needs, and which instantiation runs it.  The next conv's image
+// (ConvOut::Image) is written by the three-plane latent-composed forms only; the partial sums by the 64-channel form only.
+static int conv3_launch(Conv3Args a3, int terms, ConvIn in, ConvOut out, int B, hipStream_t st) {
     a3.tiles = conv3_tiles(terms, a3.T, a3.H, a3.W);
-    if (lat && packed) {       // two taps per k-step (conv3d_k3_bf16x3_kernel<.., 0, ..>): 14 / 27 of the MFMA work
-        AVD_REQUIRE((a3.btab || out_mode == 1) && out_mode != 2 && (out_mode == 0 || (terms != 3 && a3.X3out)), AVD_EINVAL,
-                    "conv3d (latent-composed, packed taps): bad arguments");
-        if (terms == 3) return conv3_launch_as<3, 0, 0>(a3, B, flops * 14.0 / 27.0, st, g_conv3_pk_attr[0], "conv3d f16x2 (latent, packed taps)");
-        if (out_mode == 1) return conv3_launch_as<6, 0, 1>(a3, B, flops * 14.0 / 27.0, st, g_conv3_pk_attr[1], "conv3d bf16x3 (latent, packed taps, image out)");
-        return conv3_launch_as<6, 0, 0>(a3, B, flops * 14.0 / 27.0, st, g_conv3_pk_attr[2], "conv3d bf16x3 (latent, packed taps)");
-    }
-    if (out_mode == 3) {       // the encoder's last conv: pooling partial sums instead of fp32 activations
+    const bool lat = in != ConvIn::Full64, image_ok = out == ConvOut::Image && terms != 3 && a3.X3out;
+    if (in == ConvIn::LatPacked)
+        AVD_REQUIRE(out == ConvOut::Act ? a3.btab != nullptr : image_ok, AVD_EINVAL, "conv3d (latent-composed, packed taps): bad arguments");
+    else if (out == ConvOut::PoolP)
         AVD_REQUIRE(!lat && a3.P, AVD_EINVAL, "conv3d (pooling partials): bad arguments");
-        static LdsAttr attr[2];
-        if (terms == 3) return conv3_launch_as<3, 4, 3>(a3, B, flops, st, attr[0], "conv3d f16x2 (pooling partials out)");
-        return conv3_launch_as<6, 4, 3>(a3, B, flops, st, attr[1], "conv3d bf16x3 (pooling partials out)");
-    }
-    if (out_mode != 0) {
-        AVD_REQUIRE((out_mode == 1 && terms != 3 && lat && a3.X3out) || (out_mode == 2 && !lat && a3.P && a3.wimg_g), AVD_EINVAL, "conv3d (folded route): bad arguments");
-        if (out_mode == 2 && terms == 3) {
-            if (int rc = g_conv3_fold_attr[2].ensure(reinterpret_cast<const void*>(conv3d_k3_bf16x3_kernel<3, 4, 2>), HaloCfg<3>::LDS, "conv3d f16x2 (to_img partials out)")) return rc;
-            static const int tag = prof_tag_id("conv3d_k3_bf16x3_kernel<3, 4, 2>");
-            ProfScope prof(tag, flops, st);
-            hipLaunchKernelGGL((conv3d_k3_bf16x3_kernel<3, 4, 2>), dim3((unsigned)(B * conv3_blocks<3>(a3.T, a3.H, a3.W))), dim3(256), HaloCfg<3>::LDS, st, a3);
-        } else if (out_mode == 1) {
-            if (int rc = g_conv3_fold_attr[0].ensure(reinterpret_cast<const void*>(conv3d_k3_bf16x3_kernel<6, 1, 1>), HaloCfg<6>::LDS, "conv3d bf16x3 (latent, image out)")) return rc;
-            static const int tag = prof_tag_id("conv3d_k3_bf16x3_kernel<6, 1, 1>");
-            ProfScope prof(tag, flops, st);
-            hipLaunchKernelGGL((conv3d_k3_bf16x3_kernel<6, 1, 1>), dim3((unsigned)(B * conv3_blocks<6>(a3.T, a3.H, a3.W))), dim3(256), HaloCfg<6>::LDS, st, a3);
-        } else {
-            if (int rc = g_conv3_fold_attr[1].ensure(reinterpret_cast<const void*>(conv3d_k3_bf16x3_kernel<6, 4, 2>), HaloCfg<6>::LDS, "conv3d bf16x3 (to_img partials out)")) return rc;
-            static const int tag = prof_tag_id("conv3d_k3_bf16x3_kernel<6, 4, 2>");
-            ProfScope prof(tag, flops, st);
-            hipLaunchKernelGGL((conv3d_k3_bf16x3_kernel<6, 4, 2>), dim3((unsigned)(B * conv3_blocks<6>(a3.T, a3.H, a3.W))), dim3(256), HaloCfg<6>::LDS, st, a3);
-        }
-        AVD_CHECK_LAUNCH("conv3d (folded route)");
-        return AVD_OK;
-    }
-    if (lat) {
-        AVD_REQUIRE(a3.btab, AVD_EINVAL, "conv3d (latent-composed): null bias table");
-        if (terms == 3) {
-            if (int rc = g_conv3_lat_attr[1].ensure(reinterpret_cast<const void*>(conv3d_k3_bf16x3_kernel<3, 1>), HaloCfg<3>::LDS, "conv3d f16x2 (latent)")) return rc;
-            static const int tag = prof_tag_id("conv3d_k3_bf16x3_kernel<3, 1, 0>");
-            ProfScope prof(tag, flops, st);
-            hipLaunchKernelGGL((conv3d_k3_bf16x3_kernel<3, 1>), dim3((unsigned)(B * conv3_blocks<3>(a3.T, a3.H, a3.W))), dim3(256), HaloCfg<3>::LDS, st, a3);
-        } else {
-            if (int rc = g_conv3_lat_attr[0].ensure(reinterpret_cast<const void*>(conv3d_k3_bf16x3_kernel<6, 1>), HaloCfg<6>::LDS, "conv3d bf16x3 (latent)")) return rc;
-            static const int tag = prof_tag_id("conv3d_k3_bf16x3_kernel<6, 1, 0>");
-            ProfScope prof(tag, flops, st);
-            hipLaunchKernelGGL((conv3d_k3_bf16x3_kernel<6, 1>), dim3((unsigned)(B * conv3_blocks<6>(a3.T, a3.H, a3.W))), dim3(256), HaloCfg<6>::LDS, st, a3);
-        }
-        AVD_CHECK_LAUNCH("conv3d (latent-composed)");
-        return AVD_OK;
-    }
-    if (terms == 3) {
-        if (int rc = g_conv3_attr[1].ensure(reinterpret_cast<const void*>(conv3d_k3_bf16x3_kernel<3, 4>), HaloCfg<3>::LDS, "conv3d f16x2")) return rc;
-        static const int tag = prof_tag_id("conv3d_k3_bf16x3_kernel<3, 4, 0>");
-        ProfScope prof(tag, flops, st);
-        hipLaunchKernelGGL((conv3d_k3_bf16x3_kernel<3, 4>), dim3((unsigned)(B * conv3_blocks<3>(a3.T, a3.H, a3.W))), dim3(256), HaloCfg<3>::LDS, st, a3);
-    } else {
-        if (int rc = g_conv3_attr[0].ensure(reinterpret_cast<const void*>(conv3d_k3_bf16x3_kernel<6, 4>), HaloCfg<6>::LDS, "conv3d bf16x3")) return rc;
-        static const int tag = prof_tag_id("conv3d_k3_bf16x3_kernel<6, 4, 0>");
-        ProfScope prof(tag, flops, st);
-        hipLaunchKernelGGL((conv3d_k3_bf16x3_kernel<6, 4>), dim3((unsigned)(B * conv3_blocks<6>(a3.T, a3.H, a3.W))), dim3(256), HaloCfg<6>::LDS, st, a3);
-    }
-    AVD_CHECK_LAUNCH("conv3d (split operands)");
-    return AVD_OK;
+    else if (out != ConvOut::Act)
+        AVD_REQUIRE(lat ? image_ok : out == ConvOut::ToImgP && a3.P && a3.wimg_g, AVD_EINVAL, "conv3d (folded route): bad arguments");
+    else
+        AVD_REQUIRE(!lat || a3.btab, AVD_EINVAL, "conv3d (latent-composed): null bias table");
+    // profiled work: 27 taps x (16 | 64) input channels; two taps per k-step (14 steps for 27 taps) is 14 / 27 of the MFMA work
+    double flops = 2.0 * (double)B * ((int64_t)a3.T * a3.H * a3.W) * VC * 27.0 * (lat ? 16 : VC);
+    if (in == ConvIn::LatPacked) flops = flops * 14.0 / 27.0;
+    if (in == ConvIn::Full64)
+        return out == ConvOut::Act      ? conv3_launch_terms<4, 0>(terms, a3, B, flops, st)
+               : out == ConvOut::ToImgP ? conv3_launch_terms<4, 2>(terms, a3, B, flops, st)
+                                        : conv3_launch_terms<4, 3>(terms, a3, B, flops, st);
+    if (out == ConvOut::Image)
+        return in == ConvIn::Lat ? conv3_launch_as<6, 1, 1>(a3, B, flops, st) : conv3_launch_as<6, 0, 1>(a3, B, flops, st);
+    return in == ConvIn::Lat ? conv3_launch_terms<1, 0>(terms, a3, B, flops, st) : conv3_launch_terms<0, 0>(terms, a3, B, flops, st);
+}
+// the fields every halo-tile conv launch sets (tiles: conv3_launch); the others are named where a launch needs them
+static Conv3Args conv3_args(const unsigned char* X3, const void* W3, const float* bias, float* part, int T, int H, int W) {
+    Conv3Args a{};
+    a.X3 = X3; a.W3 = static_cast<const unsigned char*>(W3); a.bias = bias; a.part = part;
+    a.T = T; a.H = H; a.W = W; a.ab_inv = 1.f;
+    return a;
 }
 static int check_conv_terms(int terms, const float* w_scale, const float* a_scale, int n_blocks, int first, bool first_runtime) {
     AVD_REQUIRE(terms == 0 || terms == 6 || terms == 3, AVD_EINVAL, "vae: conv_terms must be 0 / 6 (bf16x3) or 3 (f16x2), got %d", terms);
@@ -1518,39 +1502,97 @@ static int check_conv_terms(int terms, const float* w_scale, const float* a_scal
     return AVD_OK;
 }
 
-static inline int64_t a256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
-// upsample(z) -> the latent-composed conv's input image: from a channel-last copy of the latent when lat_ch <= 8 (zt = scratch of B x vol x 8 floats)
-static int upsample_lat16(const float* z, float* zt, unsigned char* X16, int B, int Cv, int Tp, int Hp, int Wp, int T, int H, int W, bool f16,
-                          const float* sc_dev, hipStream_t st) {
-    const int64_t nvox = (int64_t)B * T * H * W;
-    const float fst = (float)Tp / (float)T, fsh = (float)Hp / (float)H, fsw = (float)Wp / (float)W;
-    if (Cv <= 8 && zt) {
-        const int vol = Tp * Hp * Wp;
-        const int64_t total = (int64_t)B * vol;
-        hipLaunchKernelGGL(lat_cl8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, z, zt, Cv, vol, total);
-        AVD_CHECK_LAUNCH("lat_cl8");
-        static const int tag = prof_tag_id("upsample_lat8_kernel");
-        ProfScope prof(tag, (double)nvox * L16_ROWB, st);
-        if (f16) hipLaunchKernelGGL(upsample_lat8_kernel<true>, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, st, zt, X16, Tp, Hp, Wp, T, H, W, fst, fsh, fsw, nvox, sc_dev);
-        else hipLaunchKernelGGL(upsample_lat8_kernel<false>, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, st, zt, X16, Tp, Hp, Wp, T, H, W, fst, fsh, fsw, nvox, nullptr);
-        AVD_CHECK_LAUNCH("upsample_lat8");
-        return AVD_OK;
-    }
-    static const int tag = prof_tag_id("upsample_lat16_kernel");
-    ProfScope prof(tag, (double)nvox * L16_ROWB, st);
-    if (f16) hipLaunchKernelGGL(upsample_lat16_kernel<true>, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, st, z, X16, Cv, Tp, Hp, Wp, T, H, W, fst, fsh, fsw, nvox, sc_dev);
-    else hipLaunchKernelGGL(upsample_lat16_kernel<false>, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, st, z, X16, Cv, Tp, Hp, Wp, T, H, W, fst, fsh, fsw, nvox, nullptr);
-    AVD_CHECK_LAUNCH("upsample_lat16");
+// ---- steps both directions run ----
+// one 64-output convolution on the fp32 kernel (CIN 64, or 4 = the encoder's first conv; cin: the channels that count as work)
+template <int CIN>
+static int conv_f32_launch(const float* X, const float* Wt, const float* bias, float* Y, float* part, int B, int T, int H, int W, int cin,
+                           const char* what, hipStream_t st) {
+    constexpr int stage_lds = 2 * (VBM + VC) * VBK * 4, epi_lds = 4 * 64 * 36 * 4;
+    constexpr int lds = stage_lds > epi_lds ? stage_lds : epi_lds;
+    const int64_t THW = (int64_t)T * H * W;
+    const ConvArgs a{X, Wt, bias, Y, part, T, H, W, (int)((THW + VBM - 1) / VBM)};
+    static const int tag = prof_tag_id("conv3d_k3_gelu_stats_kernel<%d>", CIN);
+    ProfScope prof(tag, 2.0 * (double)B * THW * VC * 27.0 * cin, st);
+    hipLaunchKernelGGL(conv3d_k3_gelu_stats_kernel<CIN>, dim3((unsigned)(B * a.tiles)), dim3(256), lds, st, a);
+    AVD_CHECK_LAUNCH(what);
     return AVD_OK;
 }
+// GroupNorm(Y) into the next conv's padded input: the slab-major operand image X of the split-operand convs (f16 with its scale), or fp32
+static int gn_apply_next(bool split, bool f16, const float* Y, const float* stats, const float* gamma, const float* beta, void* X, int B, int T,
+                         int H, int W, float a_scale, int64_t act_slab, hipStream_t st) {
+    const int64_t nvox = (int64_t)B * T * H * W;
+    if (split) {
+        const int64_t total = nvox * 4;       // threads: (voxel, 16-channel slab)
+        static const int tag = prof_tag_id("gn_apply_pad3_kernel");
+        ProfScope prof(tag, 10.0 * (double)nvox * VC, st);
+        with_f16(f16, [&](auto F) {
+            hipLaunchKernelGGL(gn_apply_pad3_kernel<F()>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, Y, stats, gamma, beta,
+                               static_cast<unsigned char*>(X), T, H, W, nvox, a_scale, act_slab);
+        });
+        AVD_CHECK_LAUNCH("gn_apply_pad3");
+    } else {
+        const int64_t total4 = nvox * (VC / 4);
+        static const int tag = prof_tag_id("gn_apply_pad_kernel");
+        ProfScope prof(tag, 8.0 * (double)nvox * VC, st);
+        hipLaunchKernelGGL(gn_apply_pad_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, Y, stats, gamma, beta,
+                           static_cast<float*>(X), T, H, W, total4);
+        AVD_CHECK_LAUNCH("gn_apply_pad");
+    }
+    return AVD_OK;
+}
+// Folded routes: GroupNorm 0 goes into conv 1's per-sample weight image and bias table (from the statistics of conv 0's output), and conv 1
+// runs on them from the operand image conv 0 wrote, its epilogue writing partial sums P (decoder: to_img with wimg_g; encoder: pooling)
+// (a3: conv 1's launch but for the weights; w1: its tap-major fp32 weights; wimg, btab1: B images and B tables, written here)
+static int conv1_gn_folded(Conv3Args a3, ConvOut out, const float* w1, const float* gamma0, const float* beta0, const float* stats, unsigned char* wimg,
+                           float* btab1, int B, hipStream_t st) {
+    {
+        static const int tag = prof_tag_id("conv3_weight_gn_kernel");
+        ProfScope prof(tag, (double)B * (W3_BYTES + 27.0 * VC * VC * 4), st);
+        hipLaunchKernelGGL(conv3_weight_gn_kernel, dim3(54, B), dim3(256), 0, st, w1, stats, gamma0, wimg);
+        AVD_CHECK_LAUNCH("conv3_weight_gn");
+        hipLaunchKernelGGL(conv3_gn_btab_kernel, dim3(B, VC / 8), dim3(256), 0, st, w1, stats, gamma0, beta0, btab1);
+        AVD_CHECK_LAUNCH("conv3_gn_btab");
+    }
+    a3.W3 = wimg; a3.w3_stride = W3_BYTES;
+    a3.btab = btab1; a3.btab_stride = 64 * VC;
+    return conv3_launch(a3, 6, ConvIn::Full64, out, B, st);
+}
 
+static inline int64_t a256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+// a workspace as consecutive regions: take() returns the offset of the next one
+struct Carve { int64_t end = 0; int64_t take(int64_t bytes) { end += bytes; return end - bytes; } };
+// one decode / encode call: the descriptor, its plan (workspace offsets), the workspace, input and output, the stream
+template <typename Desc, typename Plan> struct VaeRun {
+    const Desc* d;
+    const Plan& p;
+    void* ws;
+    const float* in;
+    float* out;
+    hipStream_t st;
+    template <typename T> T* at(int64_t offset) const { return reinterpret_cast<T*>(static_cast<char*>(ws) + offset); }
+    int gn_finalize_for(int tiles) const {
+        return gn_finalize(at<float>(p.part), at<double>(p.fin), at<float>(p.stats), d->B, tiles, (double)p.THW * (VC / VG), d->gn_eps, st);
+    }
+};
+// floats of the GroupNorm partials region: sized for whichever conv kernel writes the most entries (fp32: one per 128 voxels)
+static int64_t gn_part_floats(int B, int T, int H, int W) {
+    const int t1 = (int)(((int64_t)T * H * W + VBM - 1) / VBM), t3 = conv3_tiles(3, T, H, W), t6 = conv3_tiles(6, T, H, W);
+    const int tmax = t1 > t3 ? (t1 > t6 ? t1 : t6) : (t3 > t6 ? t3 : t6);
+    return (int64_t)B * tmax * 2 * VG * 2;
+}
 
-
+// ---- VideoVAE.decode ----
+// The decoder's plan: its workspace as byte offsets, regions in this order and 256-byte aligned; an alias names a region's second use
 struct VaePlan {
-    int T, H, W, tiles;
+    int T, H, W;
     bool fold_img;
-    int64_t THW, pad_b, y_b, hlow_b, part_b, part_n, fold_b, stats_b, total;
+    int64_t THW, padvox, y_b;
+    int64_t x;                      // padded conv input: fp32 NDHWC | slab-major act3 image (4 B "samples" of halo) | SplitLat: first the latent image
+    int64_t y, lat, p;              // fp32 activations | folded route: the latent image | the last conv's to_img partial sums
+    int64_t hlow;                   // from_lat(z) on the latent grid | the channel-last copy of z
+    int64_t part, fin;              // GroupNorm partials, then gn_finalize's per-chunk fp64 sums
+    int64_t consts, wg, wimg, btab1;// {rstd[8], K[4]} per sample, to_img_w . gamma [4][64], folded route: conv 1's per-sample images and bias tables
+    int64_t stats, scale, total;    // GroupNorm mean / rstd, then {max |x|, -, s, 1 / s} of the f16x2 decoder's first image
 };
 
 static int vae_plan(const avd_vae_decode_desc* d, VaePlan& p) {
@@ -1564,23 +1606,242 @@ static int vae_plan(const avd_vae_decode_desc* d, VaePlan& p) {
     p.THW = (int64_t)d->T * d->H * d->W;
     AVD_REQUIRE(p.THW * VC < (1ll << 31) && (int64_t)(d->T + 2) * (d->H + 2) * (d->W + 2) * VC < (1ll << 31), AVD_EUNSUPPORTED,
                 "vae_decode: one sample's activation exceeds 2^31 elements");
-    p.tiles = (int)((p.THW + VBM - 1) / VBM);
-    p.pad_b = a256((int64_t)d->B * (d->T + 2) * (d->H + 2) * (d->W + 2) * (d->conv_w3 ? A3_ROWB : VC * 4));
+    p.padvox = (int64_t)d->B * (d->T + 2) * (d->H + 2) * (d->W + 2);
     p.y_b = a256((int64_t)d->B * p.THW * VC * 4);
-    p.hlow_b = a256((int64_t)d->B * d->Tp * d->Hp * d->Wp * VC * 4);
-    {
-        const int t3 = conv3_tiles(3, d->T, d->H, d->W), t6 = conv3_tiles(6, d->T, d->H, d->W);
-        const int tmax = p.tiles > t3 ? (p.tiles > t6 ? p.tiles : t6) : (t3 > t6 ? t3 : t6);
-        p.part_n = (int64_t)d->B * tmax * 2 * VG * 2;
-        p.part_b = a256(p.part_n * 4 + gn_fin_bytes(d->B));       // + gn_finalize's per-chunk fp64 sums
-    }
-    p.stats_b = a256((int64_t)d->B * VG * 2 * 4) + 256;       // + the scale slot of the f16x2 decoder (4 floats)
-    // folded route (three planes, two blocks): per-sample weight image + bias table of conv 1, to_img constants, to_img_w . gamma
-    // (to_img constants and to_img_w . gamma: every split-operand decoder; the per-sample image and table: three planes, two blocks)
+    // the per-sample weight image and bias table of conv 1: three planes, two blocks
     p.fold_img = d->conv_w3 && d->conv_terms != 3 && d->n_blocks == 2;
-    p.fold_b = d->conv_w3 ? a256((int64_t)d->B * 64 + 4 * VC * 4 + (p.fold_img ? (int64_t)d->B * (W3_BYTES + 64 * VC * 4) : 0)) : 0;
-    p.total = p.pad_b + p.y_b + p.hlow_b + p.part_b + p.fold_b + p.stats_b;
+    const int64_t part_n = gn_part_floats(d->B, d->T, d->H, d->W);
+    Carve c;
+    p.x = c.take(a256(p.padvox * (d->conv_w3 ? A3_ROWB : VC * 4)));
+    p.y = p.lat = p.p = c.take(p.y_b);
+    p.hlow = c.take(a256((int64_t)d->B * d->Tp * d->Hp * d->Wp * VC * 4));
+    p.part = c.take(a256(part_n * 4 + gn_fin_bytes(d->B)));
+    p.fin = p.part + part_n * 4;
+    // to_img constants and to_img_w . gamma: every split-operand decoder
+    p.consts = c.take(d->conv_w3 ? a256((int64_t)d->B * 64 + 4 * VC * 4 + (p.fold_img ? (int64_t)d->B * (W3_BYTES + 64 * VC * 4) : 0)) : 0);
+    p.wg = p.consts + (int64_t)d->B * 16 * 4;
+    p.wimg = p.wg + 4 * VC * 4;
+    p.btab1 = p.wimg + (int64_t)d->B * W3_BYTES;
+    p.stats = c.take(a256((int64_t)d->B * VG * 2 * 4));
+    p.scale = c.take(256);
+    p.total = c.end;
     return AVD_OK;
+}
+
+// Which way a descriptor runs.  fp32: every conv on the fp32 kernel.  Split: every conv on the halo-tile kernel from act3 images.
+// SplitLat: Split with the first conv composed with from_lat and the upsample (its input is upsample(z), 16 channels).  Folded: SplitLat
+// for three planes and two blocks with no fp32 activation in between.  A descriptor that asks for the composed conv but cannot take the
+// folded route (no bias table, Cv too large for the image, the latent image larger than the activations' region) falls through to
+// SplitLat, whose own checks refuse what it cannot run.
+enum class DecKind { F32, Split, SplitLat, Folded };
+struct DecRoute {
+    DecKind kind;
+    bool p_out;         // the last conv writes to_img's partial sums, toimg_from_p finishes ("vae_fold"; not a latent-composed last conv)
+};
+static DecRoute vae_dec_route(const avd_vae_decode_desc* d, const VaePlan& p, int vae_lat, int vae_fold) {
+    if (!d->conv_w3) return {DecKind::F32, false};
+    if (!(d->conv0_lat_w3 && vae_lat)) return {DecKind::Split, vae_fold != 0};
+    if (d->conv_terms != 3 && vae_fold && p.fold_img && d->conv0_lat_btab && d->Cv <= (d->conv0_lat_packed ? 8 : 16) && p.padvox * L16_ROWB <= p.y_b)
+        return {DecKind::Folded, true};
+    return {DecKind::SplitLat, vae_fold && d->n_blocks > 1};
+}
+
+using VaeDec = VaeRun<avd_vae_decode_desc, VaePlan>;
+
+// upsample(z) -> the latent-composed conv's input image: from a channel-last copy of the latent when lat_ch <= 8 (zt = scratch of B x vol x 8 floats)
+static int upsample_lat16(const float* z, float* zt, unsigned char* X16, int B, int Cv, int Tp, int Hp, int Wp, int T, int H, int W, bool f16,
+                          const float* sc_dev, hipStream_t st) {
+    const int64_t nvox = (int64_t)B * T * H * W;
+    const float fst = (float)Tp / (float)T, fsh = (float)Hp / (float)H, fsw = (float)Wp / (float)W;
+    const dim3 grid((unsigned)((nvox + 255) / 256));
+    if (Cv <= 8 && zt) {
+        const int vol = Tp * Hp * Wp;
+        const int64_t total = (int64_t)B * vol;
+        hipLaunchKernelGGL(lat_cl8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, z, zt, Cv, vol, total);
+        AVD_CHECK_LAUNCH("lat_cl8");
+        static const int tag = prof_tag_id("upsample_lat8_kernel");
+        ProfScope prof(tag, (double)nvox * L16_ROWB, st);
+        with_f16(f16, [&](auto F) {
+            hipLaunchKernelGGL(upsample_lat8_kernel<F()>, grid, dim3(256), 0, st, zt, X16, Tp, Hp, Wp, T, H, W, fst, fsh, fsw, nvox, F() ? sc_dev : nullptr);
+        });
+        AVD_CHECK_LAUNCH("upsample_lat8");
+        return AVD_OK;
+    }
+    static const int tag = prof_tag_id("upsample_lat16_kernel");
+    ProfScope prof(tag, (double)nvox * L16_ROWB, st);
+    with_f16(f16, [&](auto F) {
+        hipLaunchKernelGGL(upsample_lat16_kernel<F()>, grid, dim3(256), 0, st, z, X16, Cv, Tp, Hp, Wp, T, H, W, fst, fsh, fsw, nvox, F() ? sc_dev : nullptr);
+    });
+    AVD_CHECK_LAUNCH("upsample_lat16");
+    return AVD_OK;
+}
+static int dec_upsample_lat(const VaeDec& r, unsigned char* image, bool f16) {
+    const auto* d = r.d;
+    return upsample_lat16(r.in, r.at<float>(r.p.hlow), image, d->B, d->Cv, d->Tp, d->Hp, d->Wp, r.p.T, r.p.H, r.p.W, f16, r.at<float>(r.p.scale) + 2, r.st);
+}
+// from_lat on the latent grid
+static int dec_fromlat(const VaeDec& r) {
+    const auto* d = r.d;
+    const int vol = d->Tp * d->Hp * d->Wp;
+    const int64_t total = (int64_t)d->B * vol * VC;
+    static const int tag = prof_tag_id("fromlat_kernel");
+    ProfScope prof(tag, 4.0 * ((double)d->B * vol * d->Cv + (double)total), r.st);
+    hipLaunchKernelGGL(fromlat_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, r.st, r.in, d->from_lat_w, d->from_lat_b, r.at<float>(r.p.hlow),
+                       d->Cv, vol, total);
+    AVD_CHECK_LAUNCH("fromlat");
+    return AVD_OK;
+}
+// the f16x2 decoder's first image is an interpolation (a convex combination) of x: its magnitude is bounded by max |x|, which depends on
+// the data — the power-of-two image scale is derived from it on the device
+static int dec_first_scale(const VaeDec& r, const float* x, int64_t rows, int cols) {
+    if (int rc = weight_bounds_f32(x, rows, cols, r.at<float>(r.p.scale), r.st)) return rc;
+    hipLaunchKernelGGL(pow2_scale_kernel, dim3(1), dim3(1), 0, r.st, r.at<float>(r.p.scale));
+    AVD_CHECK_LAUNCH("pow2_scale");
+    return AVD_OK;
+}
+// GroupNorm + to_img + output activation from the last conv's fp32 activations
+static int dec_gn_toimg(const VaeDec& r, int blk) {
+    const auto* d = r.d;
+    const int64_t nvox = (int64_t)d->B * r.p.THW;
+    static const int tag = prof_tag_id("gn_apply_toimg_kernel");
+    ProfScope prof(tag, 4.0 * ((double)nvox * VC + (double)nvox * d->out_ch), r.st);
+    hipLaunchKernelGGL(gn_apply_toimg_kernel, dim3((unsigned)((nvox + TOIMG_VOX - 1) / TOIMG_VOX)), dim3(256), 0, r.st, r.at<float>(r.p.y),
+                       r.at<float>(r.p.stats), d->gn_w[blk], d->gn_b[blk], d->to_img_w, d->to_img_b, r.out, (int)r.p.THW, d->out_ch, d->out_tanh, nvox);
+    AVD_CHECK_LAUNCH("gn_apply_toimg");
+    return AVD_OK;
+}
+// to_img from the last conv's per-group partial sums: to_img_w . gamma before that conv, the rest after its GroupNorm statistics
+static int dec_toimg_wg(const VaeDec& r, int blk) {
+    hipLaunchKernelGGL(toimg_wg_kernel, dim3(1), dim3(256), 0, r.st, r.d->to_img_w, r.d->gn_w[blk], r.at<float>(r.p.wg), r.d->out_ch);
+    AVD_CHECK_LAUNCH("toimg_wg");
+    return AVD_OK;
+}
+static int dec_toimg_from_p(const VaeDec& r, int blk) {
+    const auto* d = r.d;
+    const int64_t nvox = (int64_t)d->B * r.p.THW;
+    float* consts = r.at<float>(r.p.consts);
+    hipLaunchKernelGGL(toimg_consts_kernel, dim3(d->B), dim3(64), 0, r.st, r.at<float>(r.p.stats), d->gn_w[blk], d->gn_b[blk], d->to_img_w, d->to_img_b,
+                       consts, d->out_ch);
+    AVD_CHECK_LAUNCH("toimg_consts");
+    static const int tag = prof_tag_id("toimg_from_p_kernel");
+    ProfScope prof(tag, 4.0 * ((double)nvox * VG * 4 + (double)nvox * d->out_ch), r.st);
+    hipLaunchKernelGGL(toimg_from_p_kernel, dim3((unsigned)((nvox + TOIMG_P_VOX - 1) / TOIMG_P_VOX)), dim3(256), 0, r.st, r.at<float>(r.p.p), consts, r.out,
+                       (int)r.p.THW, d->out_ch, d->out_tanh, nvox);
+    AVD_CHECK_LAUNCH("toimg_from_p");
+    return AVD_OK;
+}
+
+// ---- fp32 route: from_lat -> upsample -> [conv | GroupNorm statistics | normalise into the next input] ... -> GroupNorm + to_img
+static int vae_dec_f32(const VaeDec& r) {
+    const auto* d = r.d;
+    const VaePlan& p = r.p;
+    const int B = d->B;
+    float *Xp = r.at<float>(p.x), *Y = r.at<float>(p.y), *hlow = r.at<float>(p.hlow);
+    // zero halo: interiors are overwritten by the upsample / GroupNorm-apply passes, the halo stays zero for every conv
+    if (int rc = zero_halo(Xp, B, p.T, p.H, p.W, VC * 4, r.st)) return rc;
+    if (int rc = dec_fromlat(r)) return rc;
+    {
+        const int64_t total4 = (int64_t)B * p.THW * (VC / 4);
+        static const int tag = prof_tag_id("upsample_pad_kernel");
+        ProfScope prof(tag, 4.0 * (double)B * p.THW * VC, r.st);
+        hipLaunchKernelGGL(upsample_pad_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, r.st, hlow, Xp, d->Tp, d->Hp, d->Wp, p.T, p.H, p.W,
+                           (float)d->Tp / (float)p.T, (float)d->Hp / (float)p.H, (float)d->Wp / (float)p.W, total4);
+        AVD_CHECK_LAUNCH("upsample_pad");
+    }
+    for (int blk = 0; blk < d->n_blocks; ++blk) {
+        if (int rc = conv_f32_launch<64>(Xp, d->conv_w[blk], d->conv_b[blk], Y, r.at<float>(p.part), B, p.T, p.H, p.W, VC, "conv3d", r.st)) return rc;
+        if (int rc = r.gn_finalize_for((int)((p.THW + VBM - 1) / VBM))) return rc;
+        if (blk + 1 == d->n_blocks) return dec_gn_toimg(r, blk);
+        if (int rc = gn_apply_next(false, false, Y, r.at<float>(p.stats), d->gn_w[blk], d->gn_b[blk], Xp, B, p.T, p.H, p.W, 0.f, 0, r.st)) return rc;
+    }
+    return AVD_OK;
+}
+
+// ---- split-operand routes (Split, SplitLat): the first image from from_lat -> upsample, or upsample(z) for the latent-composed first conv;
+// then [conv | statistics | normalise into the next image] ..., the last conv's output as the route says
+static int vae_dec_split(const VaeDec& r, DecRoute route) {
+    const auto* d = r.d;
+    const VaePlan& p = r.p;
+    const bool h2 = d->conv_terms == 3, lat = route.kind == DecKind::SplitLat;
+    const int B = d->B, terms = h2 ? 3 : 6, act_rowb = h2 ? 64 : L16_ROWB;       // act_rowb: bytes per voxel of one slab image, planes x 32
+    const int64_t act_slab = p.padvox * act_rowb;            // bytes between the four slab images of a conv's input
+    unsigned char* X3 = r.at<unsigned char>(p.x);
+    float *Y = r.at<float>(p.y), *hlow = r.at<float>(p.hlow), *scale = r.at<float>(p.scale);
+    if (lat) {
+        AVD_REQUIRE(d->conv0_lat_btab && d->Cv <= 16, AVD_EINVAL, "vae_decode: the latent-composed first conv needs its bias table and Cv <= 16");
+        AVD_REQUIRE(!d->conv0_lat_packed || d->Cv <= 8, AVD_EINVAL, "vae_decode: conv0_lat_packed needs Cv <= 8");
+        AVD_REQUIRE(!h2 || (d->conv0_lat_w_scale > 0.f && d->conv0_lat_w_scale < __builtin_inff()), AVD_EINVAL,
+                    "vae_decode: conv0_lat_w_scale must be positive and finite");
+        if (int rc = zero_halo(X3, B, p.T, p.H, p.W, L16_ROWB, r.st)) return rc;
+        if (h2)         // |upsample(z)| <= max |z|
+            if (int rc = dec_first_scale(r, r.in, (int64_t)B * d->Cv, d->Tp * d->Hp * d->Wp)) return rc;
+        if (int rc = dec_upsample_lat(r, X3, h2)) return rc;
+    } else {
+        if (int rc = zero_halo(X3, 4 * B, p.T, p.H, p.W, act_rowb, r.st)) return rc;
+        if (int rc = dec_fromlat(r)) return rc;
+        if (h2)
+            if (int rc = dec_first_scale(r, hlow, (int64_t)B * d->Tp * d->Hp * d->Wp, VC)) return rc;
+        const int64_t total8 = (int64_t)B * p.THW * 8;
+        static const int tag = prof_tag_id("upsample_pad3_kernel");
+        ProfScope prof(tag, 6.0 * (double)B * p.THW * VC, r.st);
+        with_f16(h2, [&](auto F) {
+            hipLaunchKernelGGL(upsample_pad3_kernel<F()>, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, r.st, hlow, X3, d->Tp, d->Hp, d->Wp, p.T, p.H,
+                               p.W, (float)d->Tp / (float)p.T, (float)d->Hp / (float)p.H, (float)d->Wp / (float)p.W, total8, F() ? scale + 2 : nullptr, act_slab);
+        });
+        AVD_CHECK_LAUNCH("upsample_pad3");
+    }
+    for (int blk = 0; blk < d->n_blocks; ++blk) {
+        const bool lat0 = lat && blk == 0, last = blk + 1 == d->n_blocks, p_out = last && route.p_out;
+        Conv3Args a3 = conv3_args(X3, lat0 ? d->conv0_lat_w3 : d->conv_w3[blk], d->conv_b[blk], r.at<float>(p.part), p.T, p.H, p.W);
+        if (lat0) a3.btab = d->conv0_lat_btab;
+        else a3.x_slab_stride = act_slab;
+        if (h2) {       // block 0: the activation scale was derived on the device
+            a3.ab_inv = blk == 0 ? 1.0f / (lat0 ? d->conv0_lat_w_scale : d->conv_w_scale[0]) : 1.0f / (d->conv_w_scale[blk] * d->conv_a_scale[blk]);
+            a3.a_inv_dev = blk == 0 ? scale + 3 : nullptr;
+        }
+        if (!p_out) a3.Y = Y;
+        else if (int rc = dec_toimg_wg(r, blk)) return rc;
+        else { a3.P = r.at<float>(p.p); a3.wimg_g = r.at<float>(p.wg); }
+        const ConvIn in = !lat0 ? ConvIn::Full64 : d->conv0_lat_packed ? ConvIn::LatPacked : ConvIn::Lat;
+        if (int rc = conv3_launch(a3, terms, in, p_out ? ConvOut::ToImgP : ConvOut::Act, B, r.st)) return rc;
+        // the act3 buffer of the next conv overlays the latent image: its halo is zeroed now that conv 0 has read the latent image
+        if (lat0 && !last)
+            if (int rc = zero_halo(X3, 4 * B, p.T, p.H, p.W, act_rowb, r.st)) return rc;
+        if (int rc = r.gn_finalize_for(conv3_tiles(terms, p.T, p.H, p.W))) return rc;
+        if (last) return p_out ? dec_toimg_from_p(r, blk) : dec_gn_toimg(r, blk);
+        if (int rc = gn_apply_next(true, h2, Y, r.at<float>(p.stats), d->gn_w[blk], d->gn_b[blk], X3, B, p.T, p.H, p.W, h2 ? d->conv_a_scale[blk + 1] : 0.f,
+                                   act_slab, r.st)) return rc;
+    }
+    return AVD_OK;
+}
+
+// ---- folded route: upsample(z) -> L | conv 0 (L -> act3 image of GELU) | stats | conv 1 with GN 0 folded in (-> to_img partials) | stats | to_img.
+// L and the partials P share the region the fp32 activations have on the other routes.
+static int vae_dec_folded(const VaeDec& r) {
+    const auto* d = r.d;
+    const VaePlan& p = r.p;
+    const int B = d->B, gn_tiles = conv3_tiles(6, p.T, p.H, p.W);
+    unsigned char *Lm = r.at<unsigned char>(p.lat), *X3 = r.at<unsigned char>(p.x);
+    if (int rc = zero_halo(Lm, B, p.T, p.H, p.W, L16_ROWB, r.st)) return rc;
+    if (int rc = dec_upsample_lat(r, Lm, false)) return rc;
+    // conv 1's operand image is slab-major (four 96-byte-per-voxel images, one per 16 channels) = 4 B "samples" of halo
+    const int64_t slab_stride = p.padvox * L16_ROWB;
+    if (int rc = zero_halo(X3, 4 * B, p.T, p.H, p.W, L16_ROWB, r.st)) return rc;
+    Conv3Args a3 = conv3_args(Lm, d->conv0_lat_w3, d->conv_b[0], r.at<float>(p.part), p.T, p.H, p.W);
+    a3.btab = d->conv0_lat_btab;
+    a3.X3out = X3;
+    a3.out_slab_stride = slab_stride;
+    if (int rc = conv3_launch(a3, 6, d->conv0_lat_packed ? ConvIn::LatPacked : ConvIn::Lat, ConvOut::Image, B, r.st)) return rc;
+    if (int rc = r.gn_finalize_for(gn_tiles)) return rc;
+    if (int rc = dec_toimg_wg(r, 1)) return rc;
+    a3 = conv3_args(X3, nullptr, d->conv_b[1], r.at<float>(p.part), p.T, p.H, p.W);
+    a3.x_slab_stride = slab_stride;
+    a3.P = r.at<float>(p.p);
+    a3.wimg_g = r.at<float>(p.wg);
+    if (int rc = conv1_gn_folded(a3, ConvOut::ToImgP, d->conv_w[1], d->gn_w[0], d->gn_b[0], r.at<float>(p.stats), r.at<unsigned char>(p.wimg),
+                                 r.at<float>(p.btab1), B, r.st)) return rc;
+    if (int rc = r.gn_finalize_for(gn_tiles)) return rc;
+    return dec_toimg_from_p(r, 1);
 }
 
 }  // namespace avd
@@ -1618,213 +1879,24 @@ extern "C" int avd_vae_decode_f32(const avd_vae_decode_desc* d, const float* z, 
                 d->to_img_b, AVD_EINVAL, "vae_decode: null pointer");
     AVD_REQUIRE(workspace && workspace_bytes >= p.total, AVD_EWORKSPACE, "vae_decode: workspace %lld < %lld bytes",
                 (long long)workspace_bytes, (long long)p.total);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* w = static_cast<char*>(workspace);
-    float* Xp = reinterpret_cast<float*>(w);
-    float* Y = reinterpret_cast<float*>(w + p.pad_b);
-    float* hlow = reinterpret_cast<float*>(w + p.pad_b + p.y_b);
-    float* part = reinterpret_cast<float*>(w + p.pad_b + p.y_b + p.hlow_b);
-    double* fin = reinterpret_cast<double*>(part + p.part_n);
-    char* foldw = w + p.pad_b + p.y_b + p.hlow_b + p.part_b;
-    float* stats = reinterpret_cast<float*>(foldw + p.fold_b);
-    const int B = d->B;
-
-    const bool s3 = d->conv_w3 != nullptr;                  // split-operand convolutions: Xp is the act3 buffer (384 B per voxel)
-    const bool h2 = s3 && d->conv_terms == 3;               // f16x2: two fp16 planes of that buffer, scaled
-    unsigned char* X3 = reinterpret_cast<unsigned char*>(w);
-    float* scale_ws = reinterpret_cast<float*>(w + p.total - 256);     // {max |from_lat(z)|, -, s, 1 / s} of the f16x2 decoder's first image
-    if (s3) {
+    if (d->conv_w3) {
         for (int blk = 0; blk < d->n_blocks; ++blk) AVD_REQUIRE(d->conv_w3[blk], AVD_EINVAL, "vae_decode: null conv_w3[%d]", blk);
         if (int rc = check_conv_terms(d->conv_terms, d->conv_w_scale, d->conv_a_scale, d->n_blocks, 0, true)) return rc;
     }
-    // latent-composed first convolution (conv3d_k3_bf16x3_kernel<.., 1>): its input image is upsample(z), 96 B per voxel
-    const bool lat = s3 && d->conv0_lat_w3 != nullptr && g_vae_lat;
-    const int64_t padvox = (int64_t)B * (p.T + 2) * (p.H + 2) * (p.W + 2);
-    const int act_rowb = d->conv_w3 && d->conv_terms == 3 ? 64 : L16_ROWB;      // bytes per voxel of one slab image: planes x 32
-    const int64_t act_slab = padvox * act_rowb;       // bytes between the four slab images of a split-operand conv's input (slab-major act3)
-    const int64_t nvox = (int64_t)B * p.THW;
-    float* consts = reinterpret_cast<float*>(foldw);            // {rstd[8], K[4]} per sample (16 floats each), then to_img_w . gamma [4][64]
-    float* wg = consts + (int64_t)B * 16;
-    float* Pp = Y;                                              // the last conv's to_img partial sums live where the fp32 activations do otherwise
-    // to_img from the last conv's per-group partial sums (every split-operand decoder; "vae_fold" 0 restores gn_apply_toimg)
-    auto toimg_from_p = [&](int blk) -> int {
-        hipLaunchKernelGGL(toimg_consts_kernel, dim3(B), dim3(64), 0, st, stats, d->gn_w[blk], d->gn_b[blk], d->to_img_w, d->to_img_b, consts, d->out_ch);
-        AVD_CHECK_LAUNCH("toimg_consts");
-        static const int tag = prof_tag_id("toimg_from_p_kernel");
-        ProfScope prof(tag, 4.0 * ((double)nvox * VG * 4 + (double)nvox * d->out_ch), st);
-        hipLaunchKernelGGL(toimg_from_p_kernel, dim3((unsigned)((nvox + TOIMG_P_VOX - 1) / TOIMG_P_VOX)), dim3(256), 0, st, Pp, consts, out, (int)p.THW,
-                           d->out_ch, d->out_tanh, nvox);
-        AVD_CHECK_LAUNCH("toimg_from_p");
-        return AVD_OK;
-    };
-    if (lat && !h2 && g_vae_fold && p.fold_img && d->conv0_lat_btab && d->Cv <= (d->conv0_lat_packed ? 8 : 16) && padvox * L16_ROWB <= p.y_b) {
-        // ---- folded route: upsample(z) -> L | conv 0 (L -> act3 image of GELU) | stats | conv 1 with GN 0 folded in (-> to_img partials) |
-        // stats | to_img.  L and the partials P share the region the fp32 activations Y have on the other routes.
-        unsigned char* Lm = reinterpret_cast<unsigned char*>(Y);
-        unsigned char* wimg = reinterpret_cast<unsigned char*>(wg + 4 * VC);
-        float* btab1 = reinterpret_cast<float*>(wimg + (int64_t)B * W3_BYTES);
-        if (int rc = zero_halo(reinterpret_cast<float*>(Lm), B, p.T, p.H, p.W, L16_ROWB, st)) return rc;
-        if (int rc = upsample_lat16(z, hlow, Lm, B, d->Cv, d->Tp, d->Hp, d->Wp, p.T, p.H, p.W, false, nullptr, st)) return rc;
-        // conv 1's operand image is SLAB-major (four 96-byte-per-voxel images, one per 16 channels: conv3d_k3_bf16x3_kernel) = 4 B "samples" of halo
-        const int64_t slab_stride = act_slab;
-        if (int rc = zero_halo(Xp, 4 * B, p.T, p.H, p.W, L16_ROWB, st)) return rc;
-        const int gn_tiles = conv3_tiles(6, p.T, p.H, p.W);
-        {
-            Conv3Args a3{Lm, static_cast<const unsigned char*>(d->conv0_lat_w3), d->conv_b[0], nullptr, part, p.T, p.H, p.W, p.tiles, 1.f, nullptr,
-                         d->conv0_lat_btab, X3, nullptr, nullptr, 0, 0, 0, slab_stride};
-            if (int rc = conv3_launch(a3, 6, B, 2.0 * (double)B * p.THW * VC * 27.0 * 16, st, true, 1, d->conv0_lat_packed != 0)) return rc;
-        }
-        if (int rc = gn_finalize(part, fin, stats, B, gn_tiles, (double)p.THW * (VC / VG), d->gn_eps, st)) return rc;
-        {
-            static const int tag = prof_tag_id("conv3_weight_gn_kernel");
-            ProfScope prof(tag, (double)B * (W3_BYTES + 27.0 * VC * VC * 4), st);
-            hipLaunchKernelGGL(conv3_weight_gn_kernel, dim3(54, B), dim3(256), 0, st, d->conv_w[1], stats, d->gn_w[0], wimg);
-            AVD_CHECK_LAUNCH("conv3_weight_gn");
-            hipLaunchKernelGGL(conv3_gn_btab_kernel, dim3(B, VC / 8), dim3(256), 0, st, d->conv_w[1], stats, d->gn_w[0], d->gn_b[0], btab1);
-            AVD_CHECK_LAUNCH("conv3_gn_btab");
-            hipLaunchKernelGGL(toimg_wg_kernel, dim3(1), dim3(256), 0, st, d->to_img_w, d->gn_w[1], wg, d->out_ch);
-            AVD_CHECK_LAUNCH("toimg_wg");
-        }
-        {
-            Conv3Args a3{X3, wimg, d->conv_b[1], nullptr, part, p.T, p.H, p.W, p.tiles, 1.f, nullptr, btab1, nullptr, Pp, wg, W3_BYTES, 64 * VC, slab_stride, 0};
-            if (int rc = conv3_launch(a3, 6, B, 2.0 * (double)B * p.THW * VC * 27.0 * VC, st, false, 2)) return rc;
-        }
-        if (int rc = gn_finalize(part, fin, stats, B, gn_tiles, (double)p.THW * (VC / VG), d->gn_eps, st)) return rc;
-        return toimg_from_p(1);
-    }
-    if (lat) {
-        AVD_REQUIRE(d->conv0_lat_btab && d->Cv <= 16, AVD_EINVAL, "vae_decode: the latent-composed first conv needs its bias table and Cv <= 16");
-        AVD_REQUIRE(!d->conv0_lat_packed || d->Cv <= 8, AVD_EINVAL, "vae_decode: conv0_lat_packed needs Cv <= 8");
-        AVD_REQUIRE(!h2 || (d->conv0_lat_w_scale > 0.f && d->conv0_lat_w_scale < __builtin_inff()), AVD_EINVAL,
-                    "vae_decode: conv0_lat_w_scale must be positive and finite");
-        if (int rc = zero_halo(Xp, B, p.T, p.H, p.W, L16_ROWB, st)) return rc;
-        if (h2) {   // |upsample(z)| <= max |z| (a convex combination): the image scale is derived from the data on the device
-            if (int rc = weight_bounds_f32(z, (int64_t)B * d->Cv, d->Tp * d->Hp * d->Wp, scale_ws, st)) return rc;
-            hipLaunchKernelGGL(pow2_scale_kernel, dim3(1), dim3(1), 0, st, scale_ws);
-            AVD_CHECK_LAUNCH("pow2_scale");
-        }
-        if (int rc = upsample_lat16(z, hlow, X3, B, d->Cv, d->Tp, d->Hp, d->Wp, p.T, p.H, p.W, h2, scale_ws + 2, st)) return rc;
-    } else {
-    // zero halo (interiors are overwritten below by the upsample / GroupNorm-apply passes, the halo stays zero for every conv); the operand
-    // image of the split-operand convs is slab-major: 4 B "samples" of 96-byte rows
-    if (int rc = s3 ? zero_halo(Xp, 4 * B, p.T, p.H, p.W, act_rowb, st) : zero_halo(Xp, B, p.T, p.H, p.W, VC * 4, st)) return rc;
-    {   // from_lat on the latent grid, then trilinear upsample into the padded conv input
-        const int vol = d->Tp * d->Hp * d->Wp;
-        const int64_t total = (int64_t)B * vol * VC;
-        static const int tag = prof_tag_id("fromlat_kernel");
-        ProfScope prof(tag, 4.0 * ((double)B * vol * d->Cv + (double)total), st);
-        hipLaunchKernelGGL(fromlat_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, z, d->from_lat_w,
-                           d->from_lat_b, hlow, d->Cv, vol, total);
-        AVD_CHECK_LAUNCH("fromlat");
-    }
-    if (s3) {
-        if (h2) {
-            // The first conv's input is a trilinear interpolation (a convex combination) of from_lat(z): its magnitude is bounded by
-            // max |from_lat(z)|, which depends on the data — the power-of-two image scale is derived from it on the device
-            if (int rc = weight_bounds_f32(hlow, (int64_t)B * d->Tp * d->Hp * d->Wp, VC, scale_ws, st)) return rc;
-            hipLaunchKernelGGL(pow2_scale_kernel, dim3(1), dim3(1), 0, st, scale_ws);
-            AVD_CHECK_LAUNCH("pow2_scale");
-        }
-        const int64_t total8 = (int64_t)B * p.THW * 8;
-        static const int tag = prof_tag_id("upsample_pad3_kernel");
-        ProfScope prof(tag, 6.0 * (double)B * p.THW * VC, st);
-        if (h2)
-            hipLaunchKernelGGL(upsample_pad3_kernel<true>, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, st, hlow, X3, d->Tp, d->Hp,
-                               d->Wp, p.T, p.H, p.W, (float)d->Tp / (float)p.T, (float)d->Hp / (float)p.H, (float)d->Wp / (float)p.W, total8,
-                               scale_ws + 2, act_slab);
-        else
-            hipLaunchKernelGGL(upsample_pad3_kernel<false>, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, st, hlow, X3, d->Tp, d->Hp,
-                               d->Wp, p.T, p.H, p.W, (float)d->Tp / (float)p.T, (float)d->Hp / (float)p.H, (float)d->Wp / (float)p.W, total8,
-                               nullptr, act_slab);
-        AVD_CHECK_LAUNCH("upsample_pad3");
-    } else {
-        const int64_t total4 = (int64_t)B * p.THW * (VC / 4);
-        static const int tag = prof_tag_id("upsample_pad_kernel");
-        ProfScope prof(tag, 4.0 * (double)B * p.THW * VC, st);
-        hipLaunchKernelGGL(upsample_pad_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, hlow, Xp, d->Tp,
-                           d->Hp, d->Wp, p.T, p.H, p.W, (float)d->Tp / (float)p.T, (float)d->Hp / (float)p.H,
-                           (float)d->Wp / (float)p.W, total4);
-        AVD_CHECK_LAUNCH("upsample_pad");
-    }
-    }       // (!lat)
-    constexpr int stage_lds = 2 * (VBM + VC) * VBK * 4, epi_lds = 4 * 64 * 36 * 4;
-    constexpr int lds = stage_lds > epi_lds ? stage_lds : epi_lds;
-    for (int blk = 0; blk < d->n_blocks; ++blk) {
-        ConvArgs a{Xp, d->conv_w[blk], d->conv_b[blk], Y, part, p.T, p.H, p.W, p.tiles};
-        int gn_tiles = p.tiles;           // partials entries / 2 the conv of this block writes (the halo-tile kernel has its own tiling)
-        if (s3) {
-            const bool lat0 = lat && blk == 0;
-            Conv3Args a3{X3, static_cast<const unsigned char*>(lat0 ? d->conv0_lat_w3 : d->conv_w3[blk]), d->conv_b[blk], Y, part, p.T, p.H, p.W, p.tiles,
-                         1.f, nullptr, lat0 ? d->conv0_lat_btab : nullptr};
-            if (!lat0) a3.x_slab_stride = act_slab;
-            if (h2) {
-                a3.ab_inv = blk == 0 ? 1.0f / (lat0 ? d->conv0_lat_w_scale : d->conv_w_scale[0]) : 1.0f / (d->conv_w_scale[blk] * d->conv_a_scale[blk]);
-                a3.a_inv_dev = blk == 0 ? scale_ws + 3 : nullptr;
-            }
-            // last conv: to_img's per-group partial sums instead of fp32 activations (toimg_from_p below)
-            const bool p_out = g_vae_fold && blk + 1 == d->n_blocks && !lat0;
-            if (p_out) {
-                hipLaunchKernelGGL(toimg_wg_kernel, dim3(1), dim3(256), 0, st, d->to_img_w, d->gn_w[blk], wg, d->out_ch);
-                AVD_CHECK_LAUNCH("toimg_wg");
-                a3.Y = nullptr;
-                a3.P = Pp;
-                a3.wimg_g = wg;
-            }
-            if (int rc = conv3_launch(a3, h2 ? 3 : 6, B, 2.0 * (double)B * p.THW * VC * 27.0 * (lat0 ? 16 : VC), st, lat0, p_out ? 2 : 0,
-                                      lat0 && d->conv0_lat_packed != 0)) return rc;
-            gn_tiles = conv3_tiles(h2 ? 3 : 6, p.T, p.H, p.W);
-            // the act3 buffer of the next conv overlays the latent image: its halo is zeroed now that conv 0 has read the latent image
-            if (lat0 && blk + 1 < d->n_blocks)
-                if (int rc = zero_halo(Xp, 4 * B, p.T, p.H, p.W, act_rowb, st)) return rc;
-            if (p_out) {
-                if (int rc = gn_finalize(part, fin, stats, B, gn_tiles, (double)p.THW * (VC / VG), d->gn_eps, st)) return rc;
-                return toimg_from_p(blk);
-            }
-        } else {
-            static const int tag = prof_tag_id("conv3d_k3_gelu_stats_kernel<64>");
-            ProfScope prof(tag, 2.0 * (double)B * p.THW * VC * 27.0 * VC, st);
-            hipLaunchKernelGGL(conv3d_k3_gelu_stats_kernel<64>, dim3((unsigned)(B * p.tiles)), dim3(256), lds, st, a);
-            AVD_CHECK_LAUNCH("conv3d");
-        }
-        if (int rc = gn_finalize(part, fin, stats, B, gn_tiles, (double)p.THW * (VC / VG), d->gn_eps, st)) return rc;
-        if (blk + 1 < d->n_blocks && s3) {
-            const int64_t total8 = (int64_t)B * p.THW * 4;       // threads: (voxel, 16-channel slab)
-            static const int tag = prof_tag_id("gn_apply_pad3_kernel");
-            ProfScope prof(tag, 10.0 * (double)B * p.THW * VC, st);
-            if (h2)
-                hipLaunchKernelGGL(gn_apply_pad3_kernel<true>, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, st, Y, stats, d->gn_w[blk],
-                                   d->gn_b[blk], X3, p.T, p.H, p.W, total8 / 4, d->conv_a_scale[blk + 1], act_slab);
-            else
-                hipLaunchKernelGGL(gn_apply_pad3_kernel<false>, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, st, Y, stats, d->gn_w[blk],
-                                   d->gn_b[blk], X3, p.T, p.H, p.W, total8 / 4, 0.f, act_slab);
-            AVD_CHECK_LAUNCH("gn_apply_pad3");
-        } else if (blk + 1 < d->n_blocks) {
-            const int64_t total4 = (int64_t)B * p.THW * (VC / 4);
-            static const int tag = prof_tag_id("gn_apply_pad_kernel");
-            ProfScope prof(tag, 8.0 * (double)B * p.THW * VC, st);
-            hipLaunchKernelGGL(gn_apply_pad_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, Y, stats,
-                               d->gn_w[blk], d->gn_b[blk], Xp, p.T, p.H, p.W, total4);
-            AVD_CHECK_LAUNCH("gn_apply_pad");
-        } else {
-            const int64_t nvox = (int64_t)B * p.THW;
-            static const int tag = prof_tag_id("gn_apply_toimg_kernel");
-            ProfScope prof(tag, 4.0 * ((double)nvox * VC + (double)nvox * d->out_ch), st);
-            hipLaunchKernelGGL(gn_apply_toimg_kernel, dim3((unsigned)((nvox + TOIMG_VOX - 1) / TOIMG_VOX)), dim3(256), 0, st, Y, stats,
-                               d->gn_w[blk], d->gn_b[blk], d->to_img_w, d->to_img_b, out, (int)p.THW, d->out_ch,
-                               d->out_tanh, nvox);
-            AVD_CHECK_LAUNCH("gn_apply_toimg");
-        }
-    }
-    return AVD_OK;
+    const VaeDec r{d, p, workspace, z, out, static_cast<hipStream_t>(stream)};
+    const DecRoute route = vae_dec_route(d, p, g_vae_lat, g_vae_fold);
+    return route.kind == DecKind::F32 ? vae_dec_f32(r) : route.kind == DecKind::Folded ? vae_dec_folded(r) : vae_dec_split(r, route);
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // VideoVAE.encode — vae_video3d.py:164-189 (deterministic path): enc_net -> AvgPool3d(t_down,s_down,s_down) -> to_lat
 // ---------------------------------------------------------------------------------------------------------
 namespace avd {
+// The encoder's plan, as the decoder's: x4 = the padded RGB + zero channel input, x = the padded input of the 64 -> 64 convs (fp32 | act3 image),
+// y = fp32 activations = lat (folded route: the 96-byte input image) = p (the last conv's pooling partial sums), wimg / btab1 = folded route
 struct VaeEncPlan {
-    int tiles;
-    int64_t THW, pad4_b, pad_b, y_b, part_b, part_n, fold_b, stats_b, total;
+    int64_t THW, padvox, y_b, fold_b;
+    int64_t x4, x, y, lat, p, part, fin, wimg, btab1, stats, total;
 };
 static int vae_enc_plan(const avd_vae_encode_desc* d, VaeEncPlan& p) {
     AVD_REQUIRE(d, AVD_EINVAL, "vae_encode: null descriptor");
@@ -1838,22 +1910,137 @@ static int vae_enc_plan(const avd_vae_encode_desc* d, VaeEncPlan& p) {
     p.THW = (int64_t)d->T * d->H * d->W;
     AVD_REQUIRE((int64_t)(d->T + 2) * (d->H + 2) * (d->W + 2) * VC < (1ll << 31), AVD_EUNSUPPORTED,
                 "vae_encode: one sample's activation exceeds 2^31 elements");
-    p.tiles = (int)((p.THW + VBM - 1) / VBM);
-    const int64_t padvox = (int64_t)d->B * (d->T + 2) * (d->H + 2) * (d->W + 2);
-    p.pad4_b = a256(padvox * 4 * 4);
-    p.pad_b = d->n_blocks > 1 ? a256(padvox * (d->conv_w3 ? A3_ROWB : VC * 4)) : 0;
+    p.padvox = (int64_t)d->B * (d->T + 2) * (d->H + 2) * (d->W + 2);
     p.y_b = a256((int64_t)d->B * p.THW * VC * 4);
-    {
-        const int t3 = conv3_tiles(3, d->T, d->H, d->W), t6 = conv3_tiles(6, d->T, d->H, d->W);
-        const int tmax = p.tiles > t3 ? (p.tiles > t6 ? p.tiles : t6) : (t3 > t6 ? t3 : t6);
-        p.part_n = (int64_t)d->B * tmax * 2 * VG * 2;
-        p.part_b = a256(p.part_n * 4 + gn_fin_bytes(d->B));
-    }
-    p.stats_b = a256((int64_t)d->B * VG * 2 * 4);
     // folded route (three planes, two blocks, packed first conv): per-sample weight image + bias table of conv 1
     p.fold_b = d->conv_w3 && d->conv_terms != 3 && d->n_blocks == 2 && d->conv0_pk_w3 ? a256((int64_t)d->B * (W3_BYTES + 64 * VC * 4)) : 0;
-    p.total = p.pad4_b + p.pad_b + p.y_b + p.part_b + p.fold_b + p.stats_b;
+    const int64_t part_n = gn_part_floats(d->B, d->T, d->H, d->W);
+    Carve c;
+    p.x4 = c.take(a256(p.padvox * 4 * 4));
+    p.x = c.take(d->n_blocks > 1 ? a256(p.padvox * (d->conv_w3 ? A3_ROWB : VC * 4)) : 0);
+    p.y = p.lat = p.p = c.take(p.y_b);
+    p.part = c.take(a256(part_n * 4 + gn_fin_bytes(d->B)));
+    p.fin = p.part + part_n * 4;
+    p.wimg = c.take(p.fold_b);
+    p.btab1 = p.wimg + (int64_t)d->B * W3_BYTES;
+    p.stats = c.take(a256((int64_t)d->B * VG * 2 * 4));
+    p.total = c.end;
     return AVD_OK;
+}
+
+// Which way a descriptor runs.  Block 0 (4 -> 64) is fp32 on the fp32 and Split routes; Split runs the 64 -> 64 convs on the halo-tile kernel.
+// Folded (three planes, two blocks, pooling (4, 8, 8), the packed first-conv image): both convs on the halo-tile kernel, no fp32 activation;
+// a descriptor that misses one of its conditions falls through to Split.
+enum class EncKind { F32, Split, Folded };
+struct EncRoute {
+    EncKind kind;
+    bool pool_out;      // the last conv writes pooling partial sums ("vae_fold", the shipped pooling (4, 8, 8))
+};
+static EncRoute vae_enc_route(const avd_vae_encode_desc* d, const VaeEncPlan& p, int vae_fold) {
+    if (!(d->conv_w3 && d->n_blocks > 1)) return {EncKind::F32, false};
+    const bool pool488 = d->t_down == 4 && d->s_down == 8;
+    if (d->conv_terms != 3 && vae_fold && p.fold_b > 0 && d->in_ch <= 8 && pool488 && p.padvox * L16_ROWB <= p.y_b) return {EncKind::Folded, true};
+    return {EncKind::Split, vae_fold && pool488};
+}
+
+using VaeEnc = VaeRun<avd_vae_encode_desc, VaeEncPlan>;
+
+// GroupNorm + AvgPool + to_lat: from the last conv's fp32 activations, or from its pooling partial sums (tile height by the term count)
+static int enc_gn_pool_tolat(const VaeEnc& r, int blk) {
+    const auto* d = r.d;
+    const int64_t nlat = (int64_t)d->B * (d->T / d->t_down) * (d->H / d->s_down) * (d->W / d->s_down);
+    static const int tag = prof_tag_id("gn_pool_tolat_kernel");
+    ProfScope prof(tag, 4.0 * (double)d->B * r.p.THW * VC, r.st);
+    hipLaunchKernelGGL(gn_pool_tolat_kernel, dim3((unsigned)((nlat + 3) / 4)), dim3(256), 0, r.st, r.at<float>(r.p.y), r.at<float>(r.p.stats), d->gn_w[blk],
+                       d->gn_b[blk], d->to_lat_w, d->to_lat_b, r.out, d->T, d->H, d->W, d->t_down, d->s_down, d->lat_ch, nlat);
+    AVD_CHECK_LAUNCH("gn_pool_tolat");
+    return AVD_OK;
+}
+static int enc_pool_tolat_from_p(const VaeEnc& r, int blk, int terms) {
+    const auto* d = r.d;
+    const int64_t nlat = (int64_t)d->B * (d->T / 4) * (d->H / 8) * (d->W / 8);
+    const int entries = conv3_tiles(terms, d->T, d->H, d->W) * 2;
+    static const int tag = prof_tag_id("pool_tolat_from_partials_kernel");
+    ProfScope prof(tag, 4.0 * (double)nlat * 8 * VC, r.st);
+    with_f16(terms == 3, [&](auto F) {
+        hipLaunchKernelGGL(pool_tolat_from_partials_kernel<HaloCfg<F() ? 3 : 6>::TH>, dim3((unsigned)((nlat + 3) / 4)), dim3(256), 0, r.st, r.at<float>(r.p.p),
+                           r.at<float>(r.p.stats), d->gn_w[blk], d->gn_b[blk], d->to_lat_w, d->to_lat_b, r.out, d->T, d->H, d->W, entries, d->lat_ch, nlat);
+    });
+    AVD_CHECK_LAUNCH("pool_tolat_from_partials");
+    return AVD_OK;
+}
+
+// ---- fp32 and Split routes: block 0 on the fp32 kernel from the 4-channel image, the 64 -> 64 convs on the fp32 (F32) or halo-tile (Split) kernel
+static int vae_enc_blocks(const VaeEnc& r, EncRoute route) {
+    const auto* d = r.d;
+    const VaeEncPlan& p = r.p;
+    const int B = d->B, T = d->T, H = d->H, W = d->W;
+    const bool split = route.kind == EncKind::Split, h2 = split && d->conv_terms == 3;
+    const int terms = h2 ? 3 : 6, act_rowb = h2 ? 64 : L16_ROWB;
+    const int64_t act_slab = p.padvox * act_rowb;            // slab-major operand image of the split-operand convs
+    float *Xp4 = r.at<float>(p.x4), *Xp = r.at<float>(p.x), *Y = r.at<float>(p.y), *part = r.at<float>(p.part), *stats = r.at<float>(p.stats);
+    if (int rc = zero_halo(Xp4, B, T, H, W, 16, r.st)) return rc;
+    if (d->n_blocks > 1)
+        if (int rc = split ? zero_halo(Xp, 4 * B, T, H, W, act_rowb, r.st) : zero_halo(Xp, B, T, H, W, VC * 4, r.st)) return rc;
+    {
+        const int64_t nvox = (int64_t)B * p.THW;
+        hipLaunchKernelGGL(rgb_to_ndhwc4_pad_kernel, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, r.st, r.in, Xp4, d->in_ch, T, H, W, nvox);
+        AVD_CHECK_LAUNCH("rgb_to_ndhwc4_pad");
+    }
+    for (int blk = 0; blk < d->n_blocks; ++blk) {
+        const bool last = blk + 1 == d->n_blocks, pool_out = last && route.pool_out;
+        int gn_tiles = (int)((p.THW + VBM - 1) / VBM);
+        if (blk == 0) {
+            if (int rc = conv_f32_launch<4>(Xp4, d->conv_w[0], d->conv_b[0], Y, part, B, T, H, W, d->in_ch, "conv3d(enc)", r.st)) return rc;
+        } else if (!split) {
+            if (int rc = conv_f32_launch<64>(Xp, d->conv_w[blk], d->conv_b[blk], Y, part, B, T, H, W, VC, "conv3d(enc)", r.st)) return rc;
+        } else {
+            Conv3Args a3 = conv3_args(r.at<unsigned char>(p.x), d->conv_w3[blk], d->conv_b[blk], part, T, H, W);
+            if (h2) a3.ab_inv = 1.0f / (d->conv_w_scale[blk] * d->conv_a_scale[blk]);
+            a3.x_slab_stride = act_slab;
+            if (pool_out) a3.P = r.at<float>(p.p);
+            else a3.Y = Y;
+            if (int rc = conv3_launch(a3, terms, ConvIn::Full64, pool_out ? ConvOut::PoolP : ConvOut::Act, B, r.st)) return rc;
+            gn_tiles = conv3_tiles(terms, T, H, W);
+        }
+        if (int rc = r.gn_finalize_for(gn_tiles)) return rc;
+        if (last) return pool_out ? enc_pool_tolat_from_p(r, blk, terms) : enc_gn_pool_tolat(r, blk);
+        if (int rc = gn_apply_next(split, h2, Y, stats, d->gn_w[blk], d->gn_b[blk], Xp, B, T, H, W, h2 ? d->conv_a_scale[blk + 1] : 0.f, act_slab, r.st))
+            return rc;
+    }
+    return AVD_OK;
+}
+
+// ---- folded route (round 5): the first conv on the halo-tile kernel with two taps per k-step from a 96-byte image of the input, its output
+// straight into conv 1's operand image, GroupNorm 0 folded into conv 1's per-sample weights, conv 1's epilogue -> pooling partial sums ->
+// GroupNorm 1 + AvgPool + to_lat.  No fp32 activation is written.
+static int vae_enc_folded(const VaeEnc& r) {
+    const auto* d = r.d;
+    const VaeEncPlan& p = r.p;
+    const int B = d->B, T = d->T, H = d->H, W = d->W, gn_tiles = conv3_tiles(6, T, H, W);
+    unsigned char *Lm = r.at<unsigned char>(p.lat), *X3 = r.at<unsigned char>(p.x);
+    const int64_t nvox = (int64_t)B * p.THW;
+    if (int rc = zero_halo(Lm, B, T, H, W, L16_ROWB, r.st)) return rc;
+    {
+        static const int tag = prof_tag_id("rgb_lat16_kernel");
+        ProfScope prof(tag, (double)nvox * (L16_ROWB + 4.0 * d->in_ch), r.st);
+        hipLaunchKernelGGL(rgb_lat16_kernel, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, r.st, r.in, Lm, d->in_ch, T, H, W, nvox);
+        AVD_CHECK_LAUNCH("rgb_lat16");
+    }
+    const int64_t slab_stride = p.padvox * L16_ROWB;       // conv 1's operand image: slab-major
+    if (int rc = zero_halo(X3, 4 * B, T, H, W, L16_ROWB, r.st)) return rc;
+    Conv3Args a3 = conv3_args(Lm, d->conv0_pk_w3, d->conv_b[0], r.at<float>(p.part), T, H, W);
+    a3.X3out = X3;
+    a3.out_slab_stride = slab_stride;
+    if (int rc = conv3_launch(a3, 6, ConvIn::LatPacked, ConvOut::Image, B, r.st)) return rc;
+    if (int rc = r.gn_finalize_for(gn_tiles)) return rc;
+    a3 = conv3_args(X3, nullptr, d->conv_b[1], r.at<float>(p.part), T, H, W);
+    a3.x_slab_stride = slab_stride;
+    a3.P = r.at<float>(p.p);
+    if (int rc = conv1_gn_folded(a3, ConvOut::PoolP, d->conv_w[1], d->gn_w[0], d->gn_b[0], r.at<float>(p.stats), r.at<unsigned char>(p.wimg),
+                                 r.at<float>(p.btab1), B, r.st)) return rc;
+    if (int rc = r.gn_finalize_for(gn_tiles)) return rc;
+    return enc_pool_tolat_from_p(r, 1, 6);
 }
 }  // namespace avd
 
@@ -1871,145 +2058,11 @@ extern "C" int avd_vae_encode_f32(const avd_vae_encode_desc* d, const float* x, 
                 "vae_encode: null pointer");
     AVD_REQUIRE(workspace && workspace_bytes >= p.total, AVD_EWORKSPACE, "vae_encode: workspace %lld < %lld bytes",
                 (long long)workspace_bytes, (long long)p.total);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* w = static_cast<char*>(workspace);
-    float* Xp4 = reinterpret_cast<float*>(w);
-    float* Xp = reinterpret_cast<float*>(w + p.pad4_b);
-    float* Y = reinterpret_cast<float*>(w + p.pad4_b + p.pad_b);
-    float* part = reinterpret_cast<float*>(w + p.pad4_b + p.pad_b + p.y_b);
-    double* fin = reinterpret_cast<double*>(part + p.part_n);
-    char* foldw = w + p.pad4_b + p.pad_b + p.y_b + p.part_b;
-    float* stats = reinterpret_cast<float*>(foldw + p.fold_b);
-    const int B = d->B, T = d->T, H = d->H, W = d->W;
-
-    const bool s3 = d->conv_w3 != nullptr && d->n_blocks > 1;     // split operands for the 64 -> 64 convolutions (block 0 is 4 -> 64, fp32)
-    const bool h2 = s3 && d->conv_terms == 3;
-    unsigned char* X3 = reinterpret_cast<unsigned char*>(Xp);
-    if (s3) {
+    if (d->conv_w3 && d->n_blocks > 1) {        // split operands for the 64 -> 64 convolutions
         for (int blk = 1; blk < d->n_blocks; ++blk) AVD_REQUIRE(d->conv_w3[blk], AVD_EINVAL, "vae_encode: null conv_w3[%d]", blk);
         if (int rc = check_conv_terms(d->conv_terms, d->conv_w_scale, d->conv_a_scale, d->n_blocks, 1, false)) return rc;
     }
-    {
-        // ---- folded route (round 5; three planes, two blocks, pooling (4, 8, 8), in_ch <= 8): the first conv on the halo-tile kernel with two taps
-        // per k-step from a 96-byte image of the input, its output straight into conv 1's operand image, GroupNorm 0 folded into conv 1's
-        // per-sample weights, conv 1's epilogue -> pooling partial sums -> GroupNorm 1 + AvgPool + to_lat.  No fp32 activation is written.
-        const int64_t padvox = (int64_t)B * (T + 2) * (H + 2) * (W + 2);
-        if (s3 && !h2 && g_vae_fold && p.fold_b > 0 && d->in_ch <= 8 && d->t_down == 4 && d->s_down == 8 && padvox * L16_ROWB <= p.y_b) {
-            unsigned char* Lm = reinterpret_cast<unsigned char*>(Y);
-            unsigned char* wimg = reinterpret_cast<unsigned char*>(foldw);
-            float* btab1 = reinterpret_cast<float*>(wimg + (int64_t)B * W3_BYTES);
-            const int64_t nvox = (int64_t)B * p.THW;
-            if (int rc = zero_halo(Lm, B, T, H, W, L16_ROWB, st)) return rc;
-            {
-                static const int tag = prof_tag_id("rgb_lat16_kernel");
-                ProfScope prof(tag, (double)nvox * (L16_ROWB + 4.0 * d->in_ch), st);
-                hipLaunchKernelGGL(rgb_lat16_kernel, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, st, x, Lm, d->in_ch, T, H, W, nvox);
-                AVD_CHECK_LAUNCH("rgb_lat16");
-            }
-            const int64_t slab_stride = padvox * L16_ROWB;       // conv 1's operand image: slab-major (conv3d_k3_bf16x3_kernel)
-            if (int rc = zero_halo(Xp, 4 * B, T, H, W, L16_ROWB, st)) return rc;
-            const int gn_tiles = conv3_tiles(6, T, H, W);
-            {
-                Conv3Args a3{Lm, static_cast<const unsigned char*>(d->conv0_pk_w3), d->conv_b[0], nullptr, part, T, H, W, p.tiles, 1.f, nullptr, nullptr, X3,
-                             nullptr, nullptr, 0, 0, 0, slab_stride};
-                if (int rc = conv3_launch(a3, 6, B, 2.0 * (double)B * p.THW * VC * 27.0 * 16, st, true, 1, true)) return rc;
-            }
-            if (int rc = gn_finalize(part, fin, stats, B, gn_tiles, (double)p.THW * (VC / VG), d->gn_eps, st)) return rc;
-            {
-                static const int tag = prof_tag_id("conv3_weight_gn_kernel");
-                ProfScope prof(tag, (double)B * (W3_BYTES + 27.0 * VC * VC * 4), st);
-                hipLaunchKernelGGL(conv3_weight_gn_kernel, dim3(54, B), dim3(256), 0, st, d->conv_w[1], stats, d->gn_w[0], wimg);
-                AVD_CHECK_LAUNCH("conv3_weight_gn");
-                hipLaunchKernelGGL(conv3_gn_btab_kernel, dim3(B, VC / 8), dim3(256), 0, st, d->conv_w[1], stats, d->gn_w[0], d->gn_b[0], btab1);
-                AVD_CHECK_LAUNCH("conv3_gn_btab");
-            }
-            {
-                Conv3Args a3{X3, wimg, d->conv_b[1], nullptr, part, T, H, W, p.tiles, 1.f, nullptr, btab1, nullptr, Y, nullptr, W3_BYTES, 64 * VC, slab_stride, 0};
-                if (int rc = conv3_launch(a3, 6, B, 2.0 * (double)B * p.THW * VC * 27.0 * VC, st, false, 3)) return rc;
-            }
-            if (int rc = gn_finalize(part, fin, stats, B, gn_tiles, (double)p.THW * (VC / VG), d->gn_eps, st)) return rc;
-            const int64_t nlat = (int64_t)B * (T / 4) * (H / 8) * (W / 8);
-            static const int tag = prof_tag_id("pool_tolat_from_partials_kernel");
-            ProfScope prof(tag, 4.0 * (double)nlat * 8 * VC, st);
-            hipLaunchKernelGGL(pool_tolat_from_partials_kernel<HaloCfg<6>::TH>, dim3((unsigned)((nlat + 3) / 4)), dim3(256), 0, st, Y, stats, d->gn_w[1],
-                               d->gn_b[1], d->to_lat_w, d->to_lat_b, z, T, H, W, gn_tiles * 2, d->lat_ch, nlat);
-            AVD_CHECK_LAUNCH("pool_tolat_from_partials");
-            return AVD_OK;
-        }
-    }
-    const int act_rowb = h2 ? 64 : L16_ROWB;
-    const int64_t act_slab = (int64_t)B * (T + 2) * (H + 2) * (W + 2) * act_rowb;      // slab-major operand image of the split-operand convs
-    if (int rc = zero_halo(Xp4, B, T, H, W, 16, st)) return rc;
-    if (d->n_blocks > 1)
-        if (int rc = s3 ? zero_halo(Xp, 4 * B, T, H, W, act_rowb, st) : zero_halo(Xp, B, T, H, W, VC * 4, st)) return rc;
-    {
-        const int64_t nvox = (int64_t)B * p.THW;
-        hipLaunchKernelGGL(rgb_to_ndhwc4_pad_kernel, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, st, x, Xp4, d->in_ch,
-                           T, H, W, nvox);
-        AVD_CHECK_LAUNCH("rgb_to_ndhwc4_pad");
-    }
-    constexpr int stage_lds = 2 * (VBM + VC) * VBK * 4, epi_lds = 4 * 64 * 36 * 4;
-    constexpr int lds = stage_lds > epi_lds ? stage_lds : epi_lds;
-    for (int blk = 0; blk < d->n_blocks; ++blk) {
-        ConvArgs a{blk == 0 ? Xp4 : Xp, d->conv_w[blk], d->conv_b[blk], Y, part, T, H, W, p.tiles};
-        int gn_tiles = p.tiles;
-        // last conv on the halo-tile kernel with the shipped pooling (4, 8, 8): pooling partial sums instead of fp32 activations ("vae_fold")
-        const bool pool_out = blk > 0 && s3 && blk + 1 == d->n_blocks && g_vae_fold && d->t_down == 4 && d->s_down == 8;
-        if (blk > 0 && s3) {
-            Conv3Args a3{X3, static_cast<const unsigned char*>(d->conv_w3[blk]), d->conv_b[blk], Y, part, T, H, W, p.tiles,
-                         h2 ? 1.0f / (d->conv_w_scale[blk] * d->conv_a_scale[blk]) : 1.f, nullptr};
-            a3.x_slab_stride = act_slab;
-            if (pool_out) { a3.Y = nullptr; a3.P = Y; }
-            if (int rc = conv3_launch(a3, h2 ? 3 : 6, B, 2.0 * (double)B * p.THW * VC * 27.0 * VC, st, false, pool_out ? 3 : 0)) return rc;
-            gn_tiles = conv3_tiles(h2 ? 3 : 6, T, H, W);
-        } else if (blk == 0) {
-            static const int tag = prof_tag_id("conv3d_k3_gelu_stats_kernel<4>");
-            ProfScope prof(tag, 2.0 * (double)B * p.THW * VC * 27.0 * d->in_ch, st);
-            hipLaunchKernelGGL(conv3d_k3_gelu_stats_kernel<4>, dim3((unsigned)(B * p.tiles)), dim3(256), lds, st, a);
-        } else {
-            static const int tag = prof_tag_id("conv3d_k3_gelu_stats_kernel<64>");
-            ProfScope prof(tag, 2.0 * (double)B * p.THW * VC * 27.0 * VC, st);
-            hipLaunchKernelGGL(conv3d_k3_gelu_stats_kernel<64>, dim3((unsigned)(B * p.tiles)), dim3(256), lds, st, a);
-        }
-        AVD_CHECK_LAUNCH("conv3d(enc)");
-        if (int rc = gn_finalize(part, fin, stats, B, gn_tiles, (double)p.THW * (VC / VG), d->gn_eps, st)) return rc;
-        if (blk + 1 < d->n_blocks && s3) {
-            const int64_t total8 = (int64_t)B * p.THW * 4;       // threads: (voxel, 16-channel slab)
-            static const int tag = prof_tag_id("gn_apply_pad3_kernel");
-            ProfScope prof(tag, 10.0 * (double)B * p.THW * VC, st);
-            if (h2)
-                hipLaunchKernelGGL(gn_apply_pad3_kernel<true>, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, st, Y, stats, d->gn_w[blk],
-                                   d->gn_b[blk], X3, T, H, W, total8 / 4, d->conv_a_scale[blk + 1], act_slab);
-            else
-                hipLaunchKernelGGL(gn_apply_pad3_kernel<false>, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, st, Y, stats, d->gn_w[blk],
-                                   d->gn_b[blk], X3, T, H, W, total8 / 4, 0.f, act_slab);
-            AVD_CHECK_LAUNCH("gn_apply_pad3");
-        } else if (blk + 1 < d->n_blocks) {
-            const int64_t total4 = (int64_t)B * p.THW * (VC / 4);
-            static const int tag = prof_tag_id("gn_apply_pad_kernel");
-            ProfScope prof(tag, 8.0 * (double)B * p.THW * VC, st);
-            hipLaunchKernelGGL(gn_apply_pad_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, Y, stats,
-                               d->gn_w[blk], d->gn_b[blk], Xp, T, H, W, total4);
-            AVD_CHECK_LAUNCH("gn_apply_pad");
-        } else if (pool_out) {
-            const int64_t nlat = (int64_t)B * (T / 4) * (H / 8) * (W / 8);
-            static const int tag = prof_tag_id("pool_tolat_from_partials_kernel");
-            ProfScope prof(tag, 4.0 * (double)nlat * 8 * VC, st);
-            if (h2)
-                hipLaunchKernelGGL(pool_tolat_from_partials_kernel<HaloCfg<3>::TH>, dim3((unsigned)((nlat + 3) / 4)), dim3(256), 0, st, Y, stats, d->gn_w[blk],
-                                   d->gn_b[blk], d->to_lat_w, d->to_lat_b, z, T, H, W, gn_tiles * 2, d->lat_ch, nlat);
-            else
-                hipLaunchKernelGGL(pool_tolat_from_partials_kernel<HaloCfg<6>::TH>, dim3((unsigned)((nlat + 3) / 4)), dim3(256), 0, st, Y, stats, d->gn_w[blk],
-                                   d->gn_b[blk], d->to_lat_w, d->to_lat_b, z, T, H, W, gn_tiles * 2, d->lat_ch, nlat);
-            AVD_CHECK_LAUNCH("pool_tolat_from_partials");
-        } else {
-            const int64_t nlat = (int64_t)B * (T / d->t_down) * (H / d->s_down) * (W / d->s_down);
-            static const int tag = prof_tag_id("gn_pool_tolat_kernel");
-            ProfScope prof(tag, 4.0 * (double)B * p.THW * VC, st);
-            hipLaunchKernelGGL(gn_pool_tolat_kernel, dim3((unsigned)((nlat + 3) / 4)), dim3(256), 0, st, Y, stats, d->gn_w[blk],
-                               d->gn_b[blk], d->to_lat_w, d->to_lat_b, z, T, H, W, d->t_down, d->s_down, d->lat_ch, nlat);
-            AVD_CHECK_LAUNCH("gn_pool_tolat");
-        }
-    }
-    return AVD_OK;
+    const VaeEnc r{d, p, workspace, x, z, static_cast<hipStream_t>(stream)};
+    const EncRoute route = vae_enc_route(d, p, g_vae_fold);
+    return route.kind == EncKind::Folded ? vae_enc_folded(r) : vae_enc_blocks(r, route);
 }
