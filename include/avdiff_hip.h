@@ -189,6 +189,29 @@ typedef struct {
 int avd_gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int B, int64_t per_sample,
                            avd_stream_t stream);
 
+/* ---- canvas-keyed noise: a second keying of the seeded stream above, for windows of one canvas (a public contract).
+ * A batch is N consecutive windows of one canvas, `hop` positions apart along the sliding axis, with (outer, L, inner) as in
+ * avd_window_consensus_f32: video latent [N,C,T,H,W]: outer = C, L = T, inner = H*W; audio latent [N,Ca,F]: outer = Ca, L = F,
+ * inner = 1.  Window b of a call has the global window index w = key.sample_offset + b; its element (o, l, i) sits on canvas position
+ *     p = w*hop + l                                                  (computed in 64 bits)
+ * and its normal is the value the per-sample stream (avd_noise_key) gives for sample s = p, timestep t = t_now[b] and element
+ * e' = o*inner + i: counter (e' >> 2, (uint32) p, (uint32) t, 0x44444D31), the element takes n[e' & 3].  In other words the canvas
+ * noise at [b, o, l, i] has the bits of avd_gaussian_noise_f32(key {seed, 0}, t, B = P, per_sample = outer*inner) at [p, e'].
+ * Every window that covers a canvas position draws the same bits there, so with z_out_k = det_k + sigma n(p) any weighted mean over
+ * the windows under p is mean_w(det_k) + sigma n(p): the noise term passes through avd_window_consensus_f32 for any weights, and
+ * consensus sampling at eta > 0 is as well defined as at eta = 0.  The definition does not contain the canvas length: extending a
+ * canvas leaves the noise of the positions already there unchanged.  Windows that share a canvas share their timesteps.
+ * Arguments, checked before any launch (AVD_EINVAL): hop >= 1; (sample_offset + N - 1)*hop + L <= 2^32; outer*inner < 2^34.
+ * Philox, Box-Muller and rounding are those of the per-sample stream (one implementation).  When inner % 4 == 0 and the base is
+ * 16-byte aligned a lane's four values lie inside one (o, l) slice and come from one Philox call; otherwise (every audio latent:
+ * inner = 1) one call per element.  Same bits either way, and the same bits from avd_canvas_noise_f32 and from the fused step.
+ * A latent guide's known-noise stream (avd_latent_guide) keeps its per-sample keying (sample = key.sample_offset + b) under canvas
+ * keying: canvas-keyed known noise is not implemented.  DPM-Solver++(2M) is eta == 0 only and has no canvas form. */
+/* out[b, o, l, i] = the canvas-keyed normal above; out: fp32 [N, outer, L, inner]; t_now: int64 [N].  Argument order as
+ * avd_window_consensus_f32.  Its output can be passed as the explicit `noise` of the DDIM entries. */
+int avd_canvas_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int N, int64_t outer, int L, int hop,
+                         int64_t inner, avd_stream_t stream);
+
 /* ---- latent guide: inpainting / outpainting and SDEdit over a known clean latent (a public contract).
  * Per sample b of a call, with x_k = known[b] and m = the mask, both in the latent's natural layout ([C,T,H,W] video, [Ca,F] audio,
  * row-major; element e as in avd_noise_key), and a(tau) = alpha_bar[clamp(tau, 0, T_train-1)] for tau >= 0, 1 for tau < 0:
@@ -550,6 +573,19 @@ int avd_denoise_step_cond_f32(const avd_step_desc* s, const avd_latent_guide* g,
                               const int64_t* t_last, float* x0_hist, const float* z, const float* Xp,
                               const int64_t* t_now, const int64_t* t_prev, const float* noise, float* z_out,
                               void* workspace, int64_t workspace_bytes, avd_stream_t stream);
+
+/* The whole seeded eta > 0 DDIM step with canvas-keyed noise (see "canvas-keyed noise"): the B samples of s->embed are consecutive
+ * windows of one canvas, `hop` positions apart along T (video) or F (audio), window 0 at global index key->sample_offset.  Requires
+ * s->eta > 0 and key; the canvas-keying limits are checked before the model runs.  cond_only == 0: the CFG step, with ctl (NULL or an
+ * avd_cfg_control, as avd_denoise_step_cfg_f32) and g (NULL or a latent guide, as avd_denoise_step_guided_f32; its known-noise stream
+ * stays keyed per sample).  cond_only != 0: the cond-only step (as avd_denoise_step_cond_f32 with a key; ctl must be NULL).  Only the
+ * draw inside the fused update differs from those entries: fed avd_canvas_noise_f32's output as explicit noise, avd_denoise_step_f32
+ * returns the same bits.  No DPM-Solver++(2M) form (that solver is eta == 0 only), so no t_last / x0_hist.  Graph-capturable: seed,
+ * sample_offset and hop are held by value. */
+int avd_denoise_step_canvas_f32(const avd_step_desc* s, const avd_noise_key* key, int hop, const avd_cfg_control* ctl,
+                                const avd_latent_guide* g, int cond_only, const float* z, const float* Xp,
+                                const int64_t* t_now, const int64_t* t_prev, float* z_out,
+                                void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 
 /* ---- a9 / next-1: VideoVAE.decode — avdiff/models/encoders/vae_video3d.py:195-214 (decode), :79-84
  * (_conv_block_3d: Conv3d 3x3x3 pad 1 -> GELU(erf) -> GroupNorm(min(8,C), eps 1e-5, affine)), :108-119.

@@ -138,6 +138,9 @@ SIGNATURES = {
     "avd_denoise_step_f32": (_I, [C.POINTER(StepDesc), _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "avd_denoise_step_seeded_f32": (_I, [C.POINTER(StepDesc), C.POINTER(NoiseKey), _P, _P, _P, _P, _P, _P, _L, _P]),
     "avd_gaussian_noise_f32": (_I, [C.POINTER(NoiseKey), _P, _P, _I, _L, _P]),
+    "avd_canvas_noise_f32": (_I, [C.POINTER(NoiseKey), _P, _P, _I, _L, _I, _I, _L, _P]),
+    "avd_denoise_step_canvas_f32": (_I, [C.POINTER(StepDesc), C.POINTER(NoiseKey), _I, C.POINTER(CfgControl), C.POINTER(LatentGuide), _I,
+                                         _P, _P, _P, _P, _P, _P, _L, _P]),
     "avd_sched_advance": (_I, [_P, _I, _P, _P, _P, _I, _P]),
     "avd_sched_advance_ms": (_I, [_P, _I, _P, _P, _P, _P, _I, _P]),
     "avd_dpmpp_2m_step_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _L, _P]),

@@ -291,11 +291,14 @@ struct CondOnly {};
 template <class T, class... X> struct PackHas { static constexpr bool value = (std::is_same<T, X>::value || ...); };
 struct GuideState;
 struct CfgState;
-// a well-formed pack: one key (SEEDED) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState or CondOnly
+// a well-formed pack: one key (SEEDED: a NoiseKey, or a CanvasKey for the canvas-keyed draw) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState or CondOnly
+struct NoiseKey;
+struct CanvasKey;
 template <bool SEEDED, class... X> struct PackOk {
     template <class T> static constexpr int n = PackHas<T, X...>::value ? 1 : 0;
     static constexpr bool value = sizeof...(X) == (SEEDED ? 1 : 0) + n<DpmState> + n<GuideState> + n<CfgState> + n<CondOnly> &&
-                                  !(SEEDED && n<DpmState>) && !(n<CfgState> && n<CondOnly>);
+                                  !(SEEDED && n<DpmState>) && !(n<CfgState> && n<CondOnly>) &&
+                                  n<NoiseKey> + n<CanvasKey> == (SEEDED ? 1 : 0);
 };
 template <class T, class A, class... R> __device__ __forceinline__ T pack_get(const A& a, const R&... r) {
     if constexpr (std::is_same<T, A>::value) return a;
@@ -368,6 +371,81 @@ int gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* ou
                 (long long)B * per);
     hipLaunchKernelGGL(gaussian_noise_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, t_now, out, nk, per, per4, total4);
     AVD_CHECK_LAUNCH("gaussian_noise");
+    return AVD_OK;
+}
+
+// ------------------------------------------------------------------ canvas keying of the seeded stream (window consensus at eta > 0)
+// The contract is written out in include/avdiff_hip.h ("canvas-keyed noise").  A batch is N consecutive windows [N, outer, L, inner] of
+// one canvas; element (o, l, i) of window b sits on canvas position p = (w0 + b) * hop + l and takes the per-sample stream's value for
+// sample p, timestep t_now[b], element e' = o * inner + i: every window that covers p draws the same bits there.
+struct CanvasKey {
+    uint32_t k0, k1;   // seed & 0xffffffff, seed >> 32
+    uint32_t w0;       // global index of window 0 of the launch
+    uint32_t hop;      // canvas positions from one window to the next
+};
+
+// the Philox call that holds element e' = o * inner + i of canvas position p (window b, position l): e' takes n[e' & 3]; with
+// inner % 4 == 0 and i % 4 == 0 the four values are elements i .. i + 3 of the (o, l) slice
+__device__ __forceinline__ f32x4 canvas_normal4(const CanvasKey& ck, int b, int64_t o, int l, int64_t i, int64_t inner, uint32_t t) {
+    const uint64_t p = ((uint64_t)ck.w0 + (uint32_t)b) * ck.hop + (uint32_t)l;
+    return philox_normal4(NoiseKey{ck.k0, ck.k1, 0u}, (uint32_t)((o * inner + i) >> 2), (uint32_t)p, t);
+}
+
+// V == 4: inner % 4 == 0 and out 16-byte aligned, a lane's float4 lies inside one (o, l) slice: one Philox call per four values.
+// V == 1: one Philox call per element (every audio latent: inner == 1).  n: N * outer * L * inner / V lanes.
+template <int V>
+__global__ __launch_bounds__(256) void canvas_noise_kernel(const int64_t* __restrict__ t_now, float* __restrict__ out, CanvasKey ck,
+                                                           int64_t outer, int L, int64_t inner, int64_t n) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const int64_t iv = inner / V;
+    const int64_t i = (idx % iv) * V;
+    int64_t r = idx / iv;
+    const int l = (int)(r % L);
+    r /= L;
+    const int64_t o = r % outer;
+    const int b = (int)(r / outer);
+    const f32x4 v = canvas_normal4(ck, b, o, l, i, inner, (uint32_t)t_now[b]);
+    if constexpr (V == 4) *reinterpret_cast<f32x4*>(out + idx * 4) = v;
+    else out[idx] = v[(int)((o * inner + i) & 3)];
+}
+
+// the checks of the canvas keying, all before any HIP call: hop >= 1, every canvas position of the batch below 2^32, and one position's
+// slice outer * inner below 2^34 elements
+int make_canvas_key(const avd_noise_key* key, int N, int64_t outer, int L, int hop, int64_t inner, CanvasKey& ck) {
+    AVD_REQUIRE(key, AVD_EINVAL, "canvas noise: null noise key");
+    AVD_REQUIRE(N > 0 && outer > 0 && L > 0 && inner > 0, AVD_EINVAL, "canvas noise: bad dims (N %d, outer %lld, L %d, inner %lld)", N,
+                (long long)outer, L, (long long)inner);
+    AVD_REQUIRE(hop >= 1, AVD_EINVAL, "canvas noise: hop must be >= 1 (got %d)", hop);
+    const int64_t lim = (int64_t)1 << 32;
+    AVD_REQUIRE(key->sample_offset >= 0 && key->sample_offset < lim && key->sample_offset + N - 1 <= (lim - L) / hop, AVD_EINVAL,
+                "canvas noise: (sample_offset %lld + N %d - 1) * hop %d + L %d must lie in [1, 2^32]", (long long)key->sample_offset, N,
+                hop, L);
+    AVD_REQUIRE(outer <= (((int64_t)1 << 34) - 1) / inner, AVD_EINVAL, "canvas noise: outer %lld * inner %lld must be < 2^34",
+                (long long)outer, (long long)inner);
+    ck = CanvasKey{(uint32_t)(key->seed & 0xffffffffu), (uint32_t)(key->seed >> 32), (uint32_t)key->sample_offset, (uint32_t)hop};
+    return AVD_OK;
+}
+
+int check_canvas_key(const avd_noise_key* key, int N, int64_t outer, int L, int hop, int64_t inner) {
+    CanvasKey ck;
+    return make_canvas_key(key, N, outer, L, hop, inner, ck);
+}
+
+int canvas_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int N, int64_t outer, int L, int hop, int64_t inner,
+                     hipStream_t st) {
+    CanvasKey ck;
+    if (int rc = make_canvas_key(key, N, outer, L, hop, inner, ck)) return rc;
+    AVD_REQUIRE(t_now && out, AVD_EINVAL, "canvas_noise: null pointer");
+    const bool vec = inner % 4 == 0 && aligned16(out);
+    AVD_REQUIRE((double)N * (double)outer * (double)L * (double)inner < 9.0e18, AVD_EUNSUPPORTED, "canvas_noise: too many values");
+    const int64_t n = (int64_t)N * outer * L * inner / (vec ? 4 : 1);
+    AVD_REQUIRE((n + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "canvas_noise: %lld lanes are too many for one launch", (long long)n);
+    if (vec)
+        hipLaunchKernelGGL(canvas_noise_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t_now, out, ck, outer, L, inner, n);
+    else
+        hipLaunchKernelGGL(canvas_noise_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t_now, out, ck, outer, L, inner, n);
+    AVD_CHECK_LAUNCH("canvas_noise");
     return AVD_OK;
 }
 
@@ -764,6 +842,8 @@ int g_cfg_rows = 1;      // avd_tune_set "cfg_rows": 0 = the 16-bytes-per-lane g
 // SEEDED: zn comes from the seeded normal stream (philox_normal4: one call is exactly this lane's float4) instead of `noise`.  The key
 // rides as a trailing parameter pack that is empty when !SEEDED, so the unseeded instantiations keep the kernel-argument layout (the
 // hidden arguments such as blockDim sit right behind the explicit ones) and compile to the same code as before the stream existed.
+// A CanvasKey in the key's place (SEEDED true) draws zn by canvas position instead (canvas_normal4): one more compile-time case, the
+// instantiations with a NoiseKey are untouched.
 // A DpmState in the pack (SEEDED false) replaces the DDIM update by the DPM-Solver++(2M) one (dpm_coef / dpm_apply) on the same x0.
 template <bool SEEDED, class... Key>
 __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
@@ -772,6 +852,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int64_t total4, Key... nk) {
     constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
     constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
+    constexpr bool CANVAS = PackHas<CanvasKey, Key...>::value;
     static_assert(PackOk<SEEDED, Key...>::value, "not a pack of the fused update kernels (see PackOk)");
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total4) return;
@@ -787,7 +868,10 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
     if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
     f32x4 zn = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (SEEDED) {
+    if constexpr (CANVAS) {      // the canvas-keyed draw: this lane's float4 lies inside one (c, t) slice (W % 4 == 0)
+        const int64_t hw4 = ((int64_t)g.H * g.W) >> 2, r = e4 / hw4;
+        zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, r / g.T, (int)(r % g.T), (e4 % hw4) * 4, hw4 * 4, (uint32_t)t_now[b]);
+    } else if constexpr (SEEDED) {
         NoiseKey k;      // a one-item pack is copied as before the guide existed: through pack_get its argument loads reorder
         if constexpr (GUIDED || CTL || COND) k = pack_get<NoiseKey>(nk...);
         else k = NoiseKey(nk...);
@@ -830,6 +914,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int groups_per_sample, Key... nk) {
     constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
     constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
+    constexpr bool CANVAS = PackHas<CanvasKey, Key...>::value;
     static_assert(PackOk<SEEDED, Key...>::value, "not a pack of the fused update kernels (see PackOk)");
     extern __shared__ __attribute__((aligned(16))) float ebuf[];       // [GT][D + 4]: the pad keeps the transposed 16-byte reads off one bank group
     const int LD = g.D + 4;
@@ -880,7 +965,10 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
             *reinterpret_cast<f32x4*>(ds.x0_hist + lat) = x0;
         } else {
             f32x4 zn = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (SEEDED) {
+            if constexpr (CANVAS) {      // element (c, t, h, w) of window b: canvas position from t, element (c, h W + w) of its slice
+                zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, cc, tq * g.t + tt, (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo,
+                                    (int64_t)g.H * g.W, (uint32_t)t_now[b]);
+            } else if constexpr (SEEDED) {
                 NoiseKey k;      // as in cfg_unpatch_ddim_kernel
                 if constexpr (GUIDED || CTL || COND) k = pack_get<NoiseKey>(nk...);
                 else k = NoiseKey(nk...);
@@ -908,9 +996,10 @@ struct UpdateArgs {
 };
 // what the kernels' trailing pack is made of: filled by check_fused_update, read by with_update_pack
 struct UpdateKeys {
-    bool dpm, seeded, guide, ctl;
+    bool dpm, seeded, canvas, guide, ctl;
     DpmState ds;
     NoiseKey nk;
+    CanvasKey ck;      // canvas: the seeded draw is keyed by canvas position (ck replaces nk in the pack)
     GuideState gs;
     CfgState cs;
 };
@@ -920,8 +1009,15 @@ struct UpdateKeys {
 // x0_hist != nullptr: the DPM-Solver++(2M) update (needs eta == 0 and t_last) instead of DDIM; x0_hist must not overlap z or z_out
 // guide != nullptr: the latent guide's blend ends the update (after either solver), right before z_out is stored
 // ctl != nullptr: per-sample guidance and / or rescale (avd_cfg_control); with rescale set the launcher runs the statistics pass first
+// cv != nullptr: the batch is windows of one canvas and the seeded draw is keyed by canvas position (needs key and eta > 0, no DPM)
+struct CanvasDims {
+    int64_t outer;
+    int L, hop;
+    int64_t inner;
+};
 static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per, const avd_noise_key* key, const int64_t* t_last,
-                              float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl, UpdateKeys& k) {
+                              float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl, UpdateKeys& k,
+                              const CanvasDims* cv = nullptr) {
     AVD_REQUIRE(a.eps && a.z && a.t_now && a.t_prev && a.abar && a.z_out, AVD_EINVAL, "%s: null pointer", what);
     AVD_REQUIRE(a.eta >= 0.f && (a.eta == 0.f || a.noise || key), AVD_EINVAL, "%s: eta > 0 needs a noise tensor or a noise key", what);
     AVD_REQUIRE(a.z != a.z_out, AVD_EINVAL, "%s: z_out must not alias z", what);
@@ -935,7 +1031,11 @@ static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per
                     "%s: x0_hist must not overlap z or z_out", what);
     }
     k.seeded = key && a.eta > 0.f;
-    if (k.seeded) {
+    k.canvas = cv != nullptr;
+    if (cv) {
+        AVD_REQUIRE(k.seeded && !k.dpm, AVD_EINVAL, "%s: the canvas-keyed draw is the seeded eta > 0 DDIM step (needs a noise key and eta > 0)", what);
+        if (int rc = make_canvas_key(key, a.B, cv->outer, cv->L, cv->hop, cv->inner, k.ck)) return rc;
+    } else if (k.seeded) {
         if (int rc = make_noise_key(key, a.B, k.nk)) return rc;
         AVD_REQUIRE(per < ((int64_t)1 << 34), AVD_EINVAL, "%s: a seeded sample must hold < 2^34 values", what);
     }
@@ -950,8 +1050,8 @@ static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per
     return AVD_OK;
 }
 
-// Calls launch(pack...) with the kernels' whole trailing pack: the solver's state (DpmState, the NoiseKey of a seeded eta > 0 step, or
-// nothing), then the guide if there is one, then the CFG control if there is one or, for the single-branch form, the CondOnly tag.
+// Calls launch(pack...) with the kernels' whole trailing pack: the solver's state (DpmState, the NoiseKey of a seeded eta > 0 step or
+// the CanvasKey of a canvas-keyed one, or nothing), then the guide if there is one, then the CFG control if there is one or, for the single-branch form, the CondOnly tag.
 template <class F>
 static void with_update_pack(const UpdateKeys& k, bool cond_only, F launch) {
     auto tail = [&](auto... state) {
@@ -963,6 +1063,7 @@ static void with_update_pack(const UpdateKeys& k, bool cond_only, F launch) {
         else launch(state...);
     };
     if (k.dpm) tail(k.ds);
+    else if (k.seeded && k.canvas) tail(k.ck);
     else if (k.seeded) tail(k.nk);
     else tail();
 }
@@ -970,7 +1071,7 @@ static void with_update_pack(const UpdateKeys& k, bool cond_only, F launch) {
 // the video launch for one pack: the whole-line kernel where the geometry allows it, the gather form otherwise
 template <class... P>
 static void launch_unpatch(const UpdateArgs& a, const Tube& g, hipStream_t st, P... p) {
-    constexpr bool SEEDED = PackHas<NoiseKey, P...>::value;
+    constexpr bool SEEDED = PackHas<NoiseKey, P...>::value || PackHas<CanvasKey, P...>::value;
     // whole-line form: groups of tokens along w' that make up 128 bytes (or the whole row when W is shorter) of latent per (c, t, h)
     const int gt = (g.W < 32 ? g.W : 32) / g.w;
     if (g_cfg_rows && (gt == 8 || gt == 4) && g.Wt % gt == 0 && g.D % 4 == 0 && (int64_t)gt * (g.D + 4) * 4 <= 64 * 1024) {
@@ -986,17 +1087,21 @@ static void launch_unpatch(const UpdateArgs& a, const Tube& g, hipStream_t st, P
 }
 
 // key, t_last / x0_hist, guide, ctl: see check_fused_update; with ctl->rescale set the statistics pass runs first, on st
+// canvas_hop != 0: the B samples are consecutive windows of one canvas, canvas_hop positions apart along T (F for audio), and the seeded
+// draw is keyed by canvas position (CanvasDims); 0: per-sample keying
 int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key,
-                         const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl) {
+                         const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
+                         int canvas_hop) {
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "cfg_unpatch_ddim: bad dims");
     Tube g;
     if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
     AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "cfg_unpatch_ddim: x0_hist must be 16-byte aligned");
     const UpdateArgs a{eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, B};
     UpdateKeys k;
-    if (int rc = check_fused_update("cfg_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, ctl, k)) return rc;
+    const CanvasDims cv{C, T, canvas_hop, (int64_t)H * W};
+    if (int rc = check_fused_update("cfg_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr)) return rc;
     if (ctl && ctl->rescale) {
         AVD_REQUIRE(aligned16(eps2) && aligned16(eps2 + (int64_t)B * g.per), AVD_EUNSUPPORTED,
                     "cfg_unpatch_ddim: the statistics pass reads 16-byte aligned token rows");
@@ -1013,14 +1118,16 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
 // one eps stream less than the CFG form).  key, t_last / x0_hist and guide as in cfg_unpatch_ddim_f32; the same rows / gather choice.
 int eps_unpatch_ddim_f32(const float* eps1, const float* z, const int64_t* t_now, const int64_t* t_prev, const float* abar, int T_train,
                          float eta, const float* noise, float* z_out, int B, int C, int T, int H, int W, int t, int h, int w,
-                         hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide) {
+                         hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide,
+                         int canvas_hop) {
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "eps_unpatch_ddim: bad dims");
     Tube g;
     if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
     AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "eps_unpatch_ddim: x0_hist must be 16-byte aligned");
     const UpdateArgs a{eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, B};
     UpdateKeys k;
-    if (int rc = check_fused_update("eps_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, nullptr, k)) return rc;
+    const CanvasDims cv{C, T, canvas_hop, (int64_t)H * W};
+    if (int rc = check_fused_update("eps_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, nullptr, k, canvas_hop ? &cv : nullptr)) return rc;
     static const int tag = prof_tag_id("eps_unpatch_ddim_kernel");
     ProfScope prof(tag, 12.0 * (double)B * g.per, st);
     with_update_pack(k, true, [&](auto... p) { launch_unpatch(a, g, st, p...); });
@@ -1037,6 +1144,7 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
                                               int F, int len, int stride, int Na, Key... nk) {
     constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
     constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
+    constexpr bool CANVAS = PackHas<CanvasKey, Key...>::value;
     static_assert(PackOk<SEEDED, Key...>::value, "not a pack of the fused update kernels (see PackOk)");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)B * Ca * F) return;
@@ -1083,6 +1191,9 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
         const float x = z[i], x0 = ddim_x0(cf, x, e);
         z_out[i] = fin(dpm_apply(d, x, x0, d.c_1 != 0.f ? ds.x0_hist[i] : 0.f));
         ds.x0_hist[i] = x0;
+    } else if constexpr (CANVAS) {      // element (c, f) of window b: canvas position from f, element c of its slice (inner == 1)
+        const f32x4 zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, c, f, 0, 1, (uint32_t)t_now[b]);
+        z_out[i] = fin(ddim_apply(cf, z[i], e, zn[c & 3]));
     } else if constexpr (SEEDED) {
         NoiseKey k;      // as in cfg_unpatch_ddim_kernel
         if constexpr (GUIDED || CTL || COND) k = pack_get<NoiseKey>(nk...);
@@ -1097,7 +1208,7 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
 
 template <class... P>
 static void launch_untoken(const UpdateArgs& a, const AudioGeom& ag, hipStream_t st, P... p) {
-    constexpr bool SEEDED = PackHas<NoiseKey, P...>::value;
+    constexpr bool SEEDED = PackHas<NoiseKey, P...>::value || PackHas<CanvasKey, P...>::value;
     const int64_t n = (int64_t)a.B * ag.Ca * ag.F;
     hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<SEEDED, P...>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.eps, a.z,
                        a.t_now, a.t_prev, a.abar, a.T_train, a.guidance, a.eta, a.noise, a.z_out, a.B, ag.Ca, ag.F, ag.len, ag.stride,
@@ -1108,13 +1219,15 @@ static void launch_untoken(const UpdateArgs& a, const AudioGeom& ag, hipStream_t
 int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st, const avd_noise_key* key,
-                               const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl) {
+                               const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
+                               int canvas_hop) {
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "cfg_untoken_ddim_audio: bad chunking");
     const UpdateArgs a{eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, B};
     const int64_t per = (int64_t)Ca * F;
     UpdateKeys k;
-    if (int rc = check_fused_update("cfg_untoken_ddim_audio", a, per, key, t_last, x0_hist, guide, ctl, k)) return rc;
+    const CanvasDims cv{Ca, F, canvas_hop, 1};
+    if (int rc = check_fused_update("cfg_untoken_ddim_audio", a, per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr)) return rc;
     const AudioGeom ag{Ca, F, len, stride, audio_na(F, len, stride)};
     if (ctl && ctl->rescale) {
         const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
@@ -1129,12 +1242,14 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
 int eps_untoken_ddim_audio_f32(const float* eps1, const float* z, const int64_t* t_now, const int64_t* t_prev, const float* abar,
                                int T_train, float eta, const float* noise, float* z_out, int B, int Ca, int F, int len, int stride,
                                hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist,
-                               const avd_latent_guide* guide) {
+                               const avd_latent_guide* guide, int canvas_hop) {
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "eps_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "eps_untoken_ddim_audio: bad chunking");
     const UpdateArgs a{eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, B};
     UpdateKeys k;
-    if (int rc = check_fused_update("eps_untoken_ddim_audio", a, (int64_t)Ca * F, key, t_last, x0_hist, guide, nullptr, k)) return rc;
+    const CanvasDims cv{Ca, F, canvas_hop, 1};
+    if (int rc = check_fused_update("eps_untoken_ddim_audio", a, (int64_t)Ca * F, key, t_last, x0_hist, guide, nullptr, k,
+                                    canvas_hop ? &cv : nullptr)) return rc;
     const AudioGeom ag{Ca, F, len, stride, audio_na(F, len, stride)};
     with_update_pack(k, true, [&](auto... p) { launch_untoken(a, ag, st, p...); });
     AVD_CHECK_LAUNCH("eps_untoken_ddim_audio");
@@ -1416,14 +1531,14 @@ extern "C" int avd_cfg_unpatch_ddim_f32(const float* eps2, const float* z, const
     AVD_REQUIRE(aligned16(eps2) && aligned16(z) && aligned16(z_out) && (!noise || aligned16(noise)), AVD_EUNSUPPORTED,
                 "cfg_unpatch_ddim: pointers must be 16-byte aligned");
     return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, C, T, H, W, t,
-                                h, w, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr);
+                                h, w, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0);
 }
 extern "C" int avd_cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now,
                                               const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance,
                                               float eta, const float* noise, float* z_out, int B, int Ca, int F, int len,
                                               int stride, avd_stream_t stream) {
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, Ca, F,
-                                      len, stride, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr);
+                                      len, stride, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0);
 }
 extern "C" int avd_eps_unpatch_ddim_f32(const float* eps, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                         const float* alpha_bar, int T_train, float eta, const float* noise, float* z_out, int B, int C,
@@ -1432,18 +1547,22 @@ extern "C" int avd_eps_unpatch_ddim_f32(const float* eps, const float* z, const 
     AVD_REQUIRE(aligned16(eps) && aligned16(z) && aligned16(z_out) && (!noise || aligned16(noise)), AVD_EUNSUPPORTED,
                 "eps_unpatch_ddim: pointers must be 16-byte aligned");
     return eps_unpatch_ddim_f32(eps, z, t_now, t_prev, alpha_bar, T_train, eta, noise, z_out, B, C, T, H, W, t, h, w,
-                                static_cast<hipStream_t>(stream), key, t_last, x0_hist, guide);
+                                static_cast<hipStream_t>(stream), key, t_last, x0_hist, guide, 0);
 }
 extern "C" int avd_eps_untoken_ddim_audio_f32(const float* eps, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                               const float* alpha_bar, int T_train, float eta, const float* noise, float* z_out, int B,
                                               int Ca, int F, int len, int stride, const avd_noise_key* key, const int64_t* t_last,
                                               float* x0_hist, const avd_latent_guide* guide, avd_stream_t stream) {
     return eps_untoken_ddim_audio_f32(eps, z, t_now, t_prev, alpha_bar, T_train, eta, noise, z_out, B, Ca, F, len, stride,
-                                      static_cast<hipStream_t>(stream), key, t_last, x0_hist, guide);
+                                      static_cast<hipStream_t>(stream), key, t_last, x0_hist, guide, 0);
 }
 extern "C" int avd_gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int B, int64_t per_sample,
                                       avd_stream_t stream) {
     return gaussian_noise_f32(key, t_now, out, B, per_sample, static_cast<hipStream_t>(stream));
+}
+extern "C" int avd_canvas_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int N, int64_t outer, int L, int hop,
+                                    int64_t inner, avd_stream_t stream) {
+    return canvas_noise_f32(key, t_now, out, N, outer, L, hop, inner, static_cast<hipStream_t>(stream));
 }
 extern "C" int avd_sched_advance(const int64_t* sched, int n_sched, int32_t* cursor, int64_t* t_now, int64_t* t_prev,
                                  int B, avd_stream_t stream) {

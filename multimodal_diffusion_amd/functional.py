@@ -381,6 +381,49 @@ def gaussian_noise(seed: int, sample_offset: int, t_now: Tensor, shape) -> Tenso
     return out
 
 
+def check_canvas_keying(shape, hop, window_offset: int = 0) -> int:
+    """The limits of the canvas-keyed noise stream (include/avdiff_hip.h, "canvas-keyed noise") for a window batch ``shape`` whose
+    window 0 has the global index ``window_offset``: an integer hop >= 1, every canvas position below 2**32 and one position's slice
+    below 2**34 elements.  Returns hop as an int."""
+    outer, L_, inner = window_dims(shape)
+    if isinstance(hop, bool) or not isinstance(hop, int) or hop < 1:
+        raise ValueError(f"canvas_hop must be an int >= 1 (latent positions from one window to the next), got {hop!r}")
+    if hop >= 2 ** 31:
+        raise ValueError(f"canvas_hop {hop} does not fit the C ABI's int")
+    N = int(shape[0])
+    if N < 1 or (window_offset + N - 1) * hop + L_ > 2 ** 32:
+        raise ValueError(f"(window_offset {window_offset} + N {N} - 1) * hop {hop} + L {L_} exceeds the stream's 2**32 canvas positions")
+    if outer * inner >= 2 ** 34:
+        raise ValueError(f"one canvas position holds outer * inner = {outer * inner} elements, the stream keys < 2**34")
+    return hop
+
+
+def canvas_noise(seed: int, t_now: Tensor, shape, hop: int, window_offset: int = 0, out: Optional[Tensor] = None) -> Tensor:
+    """The canvas-keyed form of the seeded normal stream (avd_canvas_noise_f32; contract in include/avdiff_hip.h, "canvas-keyed
+    noise"): a float32 tensor of ``shape``, a batch of N consecutive windows of one canvas ([N,C,T,H,W] video, [N,Ca,F] audio), ``hop``
+    positions apart along the sliding axis, window 0 at global window index ``window_offset``.  Element (o, l, i) of window b holds
+    the normal of canvas position p = (window_offset + b)*hop + l: the value ``gaussian_noise(seed, 0, t, (P, outer, inner))`` has at
+    [p, o, i] — every window covering p gets the same bits.  The values a canvas-keyed DenoiseEngine draws inside its step, so the
+    result can be passed as ``noise`` to an unseeded engine's ``step``.  ``t_now``: int [N] (moved to the current ROCm device if it
+    is not on one).  ``out``: a contiguous float32 device tensor of ``shape`` to fill instead of a new one."""
+    shape = tuple(int(s) for s in shape)
+    outer, L_, inner = window_dims(shape)
+    if any(s < 1 for s in shape):
+        raise ValueError(f"shape must have positive sizes, got {shape}")
+    key = noise_key(seed, window_offset)
+    hop = check_canvas_keying(shape, hop, window_offset)
+    if out is not None and not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+        raise ValueError(f"out must be a contiguous float32 device tensor of shape {shape}")
+    dev = out.device if out is not None else (t_now.device if t_now.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    tn = L.dev_i64(t_now, dev)
+    if tn.numel() != shape[0]:
+        raise ValueError(f"t_now has {tn.numel()} entries, shape asks for {shape[0]} windows")
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=torch.float32)
+    L.check(L.lib().avd_canvas_noise_f32(C.byref(key), tn.data_ptr(), out.data_ptr(), shape[0], outer, L_, hop, inner, _st(out)))
+    return out
+
+
 # ---- "bf16x3": fp32-accurate Linear on the bf16 matrix pipe (csrc/gemm_bf16x3.hip) ----
 def split3(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """fp32 [rows, K] -> its split3 image (uint8; three bf16 planes, tiled).  K must be a multiple of 16.

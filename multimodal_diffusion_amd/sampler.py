@@ -164,20 +164,32 @@ class DenoiseEngine:
     the sliding axis (T of a video latent, F of an audio latent).  While set, every kind of step ends with one more launch on the
     same stream (include/avdiff_hip.h, avd_window_consensus_f32) that replaces, in ``out``, every canvas position under several
     windows by their weighted mean, so the windows take the next step from latents that agree wherever they overlap.  It is part
-    of ``step``: ``capture_pair`` captures it and ``run(graph=True)`` replays it.  eta == 0 only (the mean of independent noise
-    draws would shrink their variance).  DPM-Solver++(2M) needs nothing extra: all windows share the timesteps, so the update is the
+    of ``step``: ``capture_pair`` captures it and ``run(graph=True)`` replays it.  With the default per-sample noise stream it is
+    eta == 0 only (the mean of independent noise draws would shrink their variance); a canvas-keyed engine (below) lifts that for
+    hop == canvas_hop.  DPM-Solver++(2M) needs nothing extra: all windows share the timesteps, so the update is the
     same linear map of (z, x0, x0_hist) for every window and the consensus of the outputs equals the output of the consensed
     inputs; ``x0_hist`` stays per window.
+
+    ``noise_keying`` (extension; default "sample" = the stream above): "canvas" needs ``noise_seed`` and an integer ``canvas_hop`` >=
+    1 and reads the batch as N consecutive windows of one canvas, ``canvas_hop`` latent positions apart, window 0 at global window
+    index ``sample_offset``.  At eta > 0 every CFG, CFG-controlled, guided and cond-only step then draws its noise keyed by
+    (noise_seed, canvas position, t_now, element of that position's slice) (include/avdiff_hip.h, "canvas-keyed noise";
+    avd_denoise_step_canvas_f32): all windows over a canvas position draw the same normal there, so the noise term passes through
+    the consensus mean unchanged for any weights, and ``set_window_consensus(hop)`` is allowed at eta > 0 when hop == canvas_hop.
+    (sample_offset + N - 1) * canvas_hop + L <= 2**32 replaces the per-sample range check.  Both values are fixed at construction; a
+    captured graph holds them by value.  ``noise=`` is refused as on any seeded engine.  A latent guide's known-noise stream stays
+    keyed per sample; at eta == 0 (which includes solver "dpmpp_2m", an ODE solver) no noise is drawn and the keying changes nothing.
     """
 
     SOLVERS = ("ddim", "dpmpp_2m")
+    NOISE_KEYINGS = ("sample", "canvas")
 
     def __init__(self, *, adapt_v: LinearAdapter, adapt_a: LinearAdapter, core: MMDiT, head: MultiModalNoiseHead,
                  tstep_dim: int, target: str, latent_shape: Tuple[int, ...], prompt_tokens: int, alpha_bar: torch.Tensor,
                  guidance: float, eta: float = 0.0, tube=(2, 4, 4), chunk=(4, 4), split_streams: Optional[bool] = None,
                  temb_mode: str = "concat", matmul: Optional[str] = None, attn: Optional[str] = None,
                  noise_seed: Optional[int] = None, sample_offset: int = 0, solver: str = "ddim", guidance_rescale=0.0,
-                 guidance_interval=None):
+                 guidance_interval=None, noise_keying: str = "sample", canvas_hop: Optional[int] = None):
         if target not in ("video", "audio"):
             raise ValueError("target must be 'video' or 'audio'")
         if eta < 0:
@@ -216,7 +228,18 @@ class DenoiseEngine:
         self._key = None if noise_seed is None else Fn.noise_key(noise_seed, sample_offset)
         if self._key is None and sample_offset != 0:
             raise ValueError("sample_offset keys the seeded noise: it needs noise_seed")
-        if self._key is not None and sample_offset + B > 2 ** 32:
+        if noise_keying not in self.NOISE_KEYINGS:
+            raise ValueError(f"noise_keying must be one of {self.NOISE_KEYINGS}, got {noise_keying!r}")
+        self.noise_keying, self.canvas_hop = noise_keying, None
+        if noise_keying == "canvas":
+            if self._key is None:
+                raise ValueError("noise_keying='canvas' keys the seeded noise stream by canvas position: it needs noise_seed")
+            if canvas_hop is None:
+                raise ValueError("noise_keying='canvas' needs canvas_hop: the latent positions from one window of the batch to the next")
+            self.canvas_hop = Fn.check_canvas_keying(self.latent_shape, canvas_hop, self.sample_offset)
+        elif canvas_hop is not None:
+            raise ValueError("canvas_hop belongs to noise_keying='canvas'")
+        elif self._key is not None and sample_offset + B > 2 ** 32:
             raise ValueError(f"sample_offset {sample_offset} + batch {B} exceeds the stream's 2**32 sample indices")
         e = L.EmbedDesc()
         e.B, e.d, e.tdim = B, self.d, self.tdim
@@ -496,11 +519,15 @@ class DenoiseEngine:
         consensus launch on its ``out`` (class docstring).  ``weights``: [L] per-position weights > 0, None = uniform.  Checked
         before anything changes.  The weights are copied into an engine-owned buffer, so new weights reach a captured graph;
         switching the consensus on, or changing ``hop`` (held by value), starts a new graph generation."""
-        if self.eta > 0:
-            raise ValueError("window consensus needs eta == 0: the mean of the windows' independent noise draws would shrink their "
-                             "variance (a canvas-keyed noise stream is not implemented)")
+        if self.eta > 0 and self.noise_keying != "canvas":
+            raise ValueError("window consensus needs eta == 0 with the per-sample noise stream: the mean of the windows' independent "
+                             "noise draws would shrink their variance (build the engine with noise_keying='canvas', canvas_hop=hop "
+                             "to key the noise by canvas position)")
         if int(hop) != hop or int(hop) <= 0:
             raise ValueError(f"hop must be a positive whole number of latent positions, got {hop!r}")
+        if self.eta > 0 and int(hop) != self.canvas_hop:
+            raise ValueError(f"window consensus at eta > 0 needs hop == canvas_hop (the noise is keyed for windows {self.canvas_hop} "
+                             f"positions apart), got hop {hop}")
         L_ = Fn.window_dims(self.latent_shape)[1]
         w = Fn.consensus_weights(weights, L_)
         if self._cons_w is None:
@@ -602,8 +629,9 @@ class DenoiseEngine:
         return tl, h, noise
 
     def _step_kind(self, z, tn, tp, noise, out, t_last, cond_only) -> torch.Tensor:
-        """the step proper: cond-only (one entry for every solver state, with or without a latent guide; the CFG control does not
-        apply there), CFG-controlled, guided, DPM-Solver++(2M), seeded or plain DDIM"""
+        """the step proper: canvas-keyed (one entry for every kind of eta > 0 step of a canvas-keyed engine), cond-only (one entry for
+        every solver state, with or without a latent guide; the CFG control does not apply there), CFG-controlled, guided,
+        DPM-Solver++(2M), seeded or plain DDIM"""
         guided = self._guide is not None or (self._ctl is not None and not cond_only)
         tl, h, noise = self._step_args(z, out, noise, t_last, guided)
         lib, desc = L.lib(), C.byref(self.desc)
@@ -611,7 +639,10 @@ class DenoiseEngine:
         guide = None if self._guide is None else C.byref(self._guide)
         zx, ts = (z.data_ptr(), self.Xp.data_ptr()), (tn.data_ptr(), tp.data_ptr())
         tail = (out.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device))
-        if cond_only:
+        if self.canvas_hop is not None and self.eta > 0:
+            ctl = None if self._ctl is None or cond_only else C.byref(self._ctl)
+            rc = lib.avd_denoise_step_canvas_f32(desc, key, self.canvas_hop, ctl, guide, 1 if cond_only else 0, *zx, *ts, *tail)
+        elif cond_only:
             rc = lib.avd_denoise_step_cond_f32(desc, guide, key, L.ptr(tl), L.ptr(h), *zx, *ts, L.ptr(noise), *tail)
         elif self._ctl is not None:
             rc = lib.avd_denoise_step_cfg_f32(desc, C.byref(self._ctl), guide, key, L.ptr(tl), L.ptr(h), *zx, *ts, *tail)

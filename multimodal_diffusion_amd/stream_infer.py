@@ -171,7 +171,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
                     init_noise: Optional[torch.Tensor] = None, max_windows_per_batch: int = 32, shard: bool = False,
                     seed: Optional[int] = None, comm_device: Optional[torch.device] = None,
                     noise_seed: Optional[int] = None, guidance_interval=None, consensus=None,
-                    return_latents: bool = False) -> Optional[Dict[str, np.ndarray]]:
+                    return_latents: bool = False, noise_keying: Optional[str] = None) -> Optional[Dict[str, np.ndarray]]:
     """The body of the reference's ``main()`` (stream_infer.py:146-225) minus file I/O, with all windows batched.
 
     Returns {"audio": wav, "sr"} for a video prompt or {"video": frames uint8, "fps"} for an audio prompt.
@@ -203,8 +203,15 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     be windows of a canvas (``windows_from_canvas``).  Up to ``max_windows_per_batch`` windows are one engine, run as without
     consensus; more are several engines stepped in lock-step (eager) with one consensus pass over all windows per step; the latents
     are the same bits either way where the engines take the same kernels.  Decode and stitching are unchanged: every window is
-    decoded on its own and cross-faded, now over near-identical content.  Needs ``ddim_eta`` == 0 and ``shard=False``: windows on
-    different ranks would need a halo exchange of their overlaps after every step, which is not implemented.
+    decoded on its own and cross-faded, now over near-identical content.  Needs ``shard=False``: windows on different ranks would need
+    a halo exchange of their overlaps after every step, which is not implemented.  With the default noise keying it also needs
+    ``ddim_eta`` == 0: windows draw independent noise, and the mean over an overlap would shrink its variance.
+    ``noise_keying`` (default None = ``streaming.noise_keying``, else "sample"; the argument wins): "canvas" keys the per-step DDIM
+    noise by canvas position instead of by window (DenoiseEngine ``noise_keying``; include/avdiff_hip.h, "canvas-keyed noise"), so
+    every window draws the same normal at a shared position and the consensus leaves the noise term intact: stochastic sampling
+    (``ddim_eta`` > 0) under consensus.  It needs consensus on and ``noise_seed``; the engines are built with ``canvas_hop`` =
+    ``latent_hop`` and ``sample_offset`` = their first window, so the latents are the same bits for any ``max_windows_per_batch``
+    where the engines take the same kernels.  ``shard=True`` stays refused.
     ``return_latents`` adds "latents": the finished [N_windows, *latent] float32 latents (single process only).
     """
     st = cfg.get("streaming", {})
@@ -222,13 +229,24 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
 
     if consensus is None:
         consensus = st.get("latent_consensus")
+    if noise_keying is None:
+        noise_keying = st.get("noise_keying", "sample")
+    if noise_keying not in DenoiseEngine.NOISE_KEYINGS:
+        raise ValueError(f"noise_keying must be one of {DenoiseEngine.NOISE_KEYINGS}, got {noise_keying!r}")
+    canvas_keyed = noise_keying == "canvas"
+    if canvas_keyed and (consensus is None or consensus is False):
+        raise ValueError("noise_keying='canvas' keys the DDIM noise by the position on the windows' shared latent canvas: it needs "
+                         "consensus (or streaming.latent_consensus)")
+    if canvas_keyed and noise_seed is None:
+        raise ValueError("noise_keying='canvas' is a keying of the seeded noise stream: it needs noise_seed")
     if consensus is not None and consensus is not False:
         if shard:
             raise ValueError("consensus with shard=True is not implemented: windows on different ranks would have to exchange their "
                              "overlapping latent positions (a halo) after every step; run the windows on one device")
-        if eta > 0:
-            raise ValueError("consensus needs sampling.ddim_eta == 0: the mean of the windows' independent noise draws would shrink "
-                             "their variance")
+        if eta > 0 and not canvas_keyed:
+            raise ValueError("consensus needs sampling.ddim_eta == 0 with the per-window noise stream: the mean of the windows' "
+                             "independent noise draws would shrink their variance (noise_keying='canvas' with noise_seed keys the "
+                             "noise by canvas position instead)")
         cons_hop, cons_L = latent_hop(cfg, "audio" if prompt_modality == "video" else "video")
         cons_w = None if isinstance(consensus, str) and consensus == "uniform" else consensus
         if isinstance(cons_w, str):
@@ -324,7 +342,8 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
                             latent_shape=(hi - lo, *lat), prompt_tokens=n_prompt, alpha_bar=abar, guidance=guide, eta=eta,
                             tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed,
                             sample_offset=lo if noise_seed is not None else 0, solver=solver,
-                            guidance_rescale=float(rescale_cfg.get(target, 0.0)), guidance_interval=interval)
+                            guidance_rescale=float(rescale_cfg.get(target, 0.0)), guidance_interval=interval,
+                            noise_keying=noise_keying, canvas_hop=cons_hop if canvas_keyed else None)
         eng.set_prompt(zp_part[lo - lo0:hi - lo0].to(device).float().contiguous())
         return eng
 
