@@ -12,6 +12,7 @@ import torch
 
 import _canvas_noise_ref as CN
 import _consensus_ref as W
+from _kit import STREAM_HALF_SECOND, pipeline_cfg
 from conftest import ROOT
 
 SEED = 0xDEADBEEF12345678
@@ -149,23 +150,13 @@ def test_canvas_noise_python_checks_need_no_device():
         Fn.check_canvas_keying((1, 8, 3), 1, 2 ** 32 - 2)
 
 
-def _stream_cfg(**sampling):
-    return {"tokenizer": {"width": 512, "video": {"tube": {"t": 2, "h": 4, "w": 4}}, "audio": {"chunk": {"length": 4, "stride": 4}}},
-            "video": {"fps": 16, "size": [32, 32], "latent": {"channels": 8, "t_down": 4, "s_down": 8}},
-            "audio": {"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150}},
-            "data": {"clip_seconds": 0.5}, "streaming": {"window_seconds": 0.5, "hop_seconds": 0.25, "crossfade_seconds": 0.125},
-            "diffusion": {m: {"steps": 1000, "sampler_steps": 4, "schedule": "cosine", "min_beta": 1e-4, "max_beta": 0.02}
-                          for m in ("video", "audio")},
-            "sampling": dict({"guidance_scale": {"video": 2.0, "audio": 2.0}}, **sampling)}
-
-
 def test_stream_generate_refuses_canvas_keying_without_consensus_or_seed():
     """raised at the top of the function, before any device work: no module and no device is touched"""
     from multimodal_diffusion_amd import stream_infer as S
     assert inspect.signature(S.stream_generate).parameters["noise_keying"].default is None
     kw = dict(vid_vae=None, aud_codec=None, adapt_v=None, adapt_a=None, core=None, head=None, tstep_dim=256, prompt_modality="audio",
               prompt_video=None, prompt_audio=np.zeros(18000, dtype=np.float32), device=torch.device("cpu"))
-    cfg = _stream_cfg(ddim_eta=0.5)
+    cfg = pipeline_cfg(clip_seconds=0.5, sampler_steps=4, streaming=STREAM_HALF_SECOND, sampling={"ddim_eta": 0.5})
     with pytest.raises(ValueError, match="consensus"):
         S.stream_generate(cfg=cfg, noise_keying="canvas", noise_seed=3, **kw)
     with pytest.raises(ValueError, match="noise_seed"):

@@ -2,20 +2,13 @@
 contiguous batch shards, max-over-ranks timing.  The per-rank compute itself is covered by the GPU tests; here the
 'step' is a stand-in so the test exercises exactly the collective layout bench.py uses."""
 import os
-import socket
 
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from _kit import free_port
 
 
 def _worker(rank, world, port, out):
@@ -45,7 +38,7 @@ def _worker(rank, world, port, out):
 def test_broadcast_and_shard_world2():
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -115,7 +108,7 @@ def test_run_sharded_world2():
     World size 2 over gloo on CPU with a stand-in step."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_shard_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -152,7 +145,7 @@ def test_bench_setup_under_torchrun(tmp_path):
     out = tmp_path / "res"
     env = dict(os.environ, AVD_TEST_OUT=str(out), MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), str(root / "tests" / "_bench_setup_worker.py")]
+           "--master-port", str(free_port()), str(root / "tests" / "_bench_setup_worker.py")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     res = [json.loads(Path(f"{out}.{k}").read_text()) for k in range(2)]
@@ -180,7 +173,7 @@ def test_bench_two_ranks_share_device():
     root = Path(__file__).resolve().parent.parent
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), str(root / "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--backend", "gloo",
+           "--master-port", str(free_port()), str(root / "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--backend", "gloo",
            "--share-device", "--no-alt", "--no-cpu-baseline", "--no-roofline", "--verify-ranks"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
@@ -215,7 +208,7 @@ def test_stream_generate_sharded_two_ranks_share_device(tmp_path):
     out = tmp_path / "shard.json"
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", AVD_TEST_OUT=str(out))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), str(root / "tests" / "_stream_shard_worker.py")]
+           "--master-port", str(free_port()), str(root / "tests" / "_stream_shard_worker.py")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     d = json.loads(out.read_text())

@@ -3,68 +3,27 @@ per-sample stream bit for bit and against the numpy mirror, the fused canvas-key
 explicitly (both targets, both video kernel forms, cond-only, CFG control, latent guide), the step under window consensus, graph replay
 against eager launches, an eta > 0 consensus trajectory against the CPU oracle, stream_generate at ddim_eta > 0 under consensus for any
 batching, and the refusals."""
+from functools import partial
+
 import numpy as np
 import pytest
 import torch
 
 import _canvas_noise_ref as CN
 import _consensus_ref as W
+from _kit import (ABAR, STREAM_HALF_SECOND, audio_case, audio_prompt, components, dev, engine, matmul_f32, model,  # noqa: F401  (dev / model are fixtures)
+                  pipeline, ts, video_case, video_prompt)
 from _tune import cfg_rows  # noqa: F401  (fixture)
 from oracle import ref_cpu as R
 
 pytestmark = pytest.mark.gpu
-ABAR = R.alpha_bar_table(R.beta_table(1000))
 SEED = 0xDEADBEEF12345678           # both key words non-zero
 ETA, G = 0.5, 3.0
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def model(dev):
-    import multimodal_diffusion_amd as A
-    ws = R.synth_weights(seed=0, n_layers=2)
-    core = A.MMDiT(d_model=512, n_layers=2, n_heads=8, mlp_ratio=4.0).eval()
-    core.load_state_dict(ws["core"], strict=True)
-    head = A.MultiModalNoiseHead({"video": 512, "audio": 512}, {"video": 256, "audio": 32}, hidden_dim=512).eval()
-    head.load_state_dict(ws["head"], strict=True)
-    av, aa = A.LinearAdapter(256, 256), A.LinearAdapter(32, 256)
-    av.load_state_dict(ws["adapt_v"])
-    aa.load_state_dict(ws["adapt_a"])
-    return ws, tuple(m.to(dev) for m in (core, head, av, aa))
-
-
-def _engine(model, target, shape, n_prompt, guidance=G, **kw):
-    import multimodal_diffusion_amd as A
-    _, (core, head, av, aa) = model
-    return A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target=target, latent_shape=shape,
-                           prompt_tokens=n_prompt, alpha_bar=ABAR, guidance=guidance, **kw)
+_engine = partial(engine, guidance=G)        # engine(mods, target, shape, n_prompt, **kw) at this file's guidance
 
 
 def _canvas_engine(model, target, shape, n_prompt, hop, **kw):
-    return _engine(model, target, shape, n_prompt, eta=ETA, noise_seed=SEED, noise_keying="canvas", canvas_hop=hop, **kw)
-
-
-def _video_case(dev, B=3, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    z = torch.randn(B, 8, 4, 16, 16, generator=g).to(dev)
-    za = torch.randn(B, 8, 40, generator=g).to(dev)           # 10 prompt tokens (chunk 4, stride 4)
-    return z, za, 10
-
-
-def _audio_case(dev, B=3, seed=1):
-    g = torch.Generator().manual_seed(seed)
-    z = torch.randn(B, 8, 150, generator=g).to(dev)
-    zv = torch.randn(B, 8, 4, 8, 8, generator=g).to(dev)      # 8 prompt tokens (tube 2 x 4 x 4)
-    return z, zv, 8
-
-
-def _t(v, dev):
-    return torch.tensor(v, dtype=torch.long, device=dev)
+    return _engine(model[1], target, shape, n_prompt, eta=ETA, noise_seed=SEED, noise_keying="canvas", canvas_hop=hop, **kw)
 
 
 # ------------------------------------------------------------------------------------------------- the noise kernel
@@ -88,9 +47,9 @@ def test_kernel_is_the_gather_of_the_per_sample_stream(dev, name, shape, hop):
     outer, L_, inner = W.dims(shape)
     P = (N - 1) * hop + L_
     t = 731
-    got = Fn.canvas_noise(SEED, _t([t] * N, dev), shape, hop)
+    got = Fn.canvas_noise(SEED, ts([t] * N, dev), shape, hop)
     assert tuple(got.shape) == shape and got.dtype == torch.float32
-    draw = Fn.gaussian_noise(SEED, 0, _t([t] * P, dev), (P, outer, inner)).cpu().numpy().reshape(P, outer * inner)
+    draw = Fn.gaussian_noise(SEED, 0, ts([t] * P, dev), (P, outer, inner)).cpu().numpy().reshape(P, outer * inner)
     ref = CN.gather_windows(draw, shape, hop)
     gn = got.cpu().numpy()
     assert np.array_equal(gn, ref)                                           # bit for bit
@@ -103,17 +62,17 @@ def test_kernel_is_the_gather_of_the_per_sample_stream(dev, name, shape, hop):
     buf = torch.empty(int(np.prod(shape)) + 1, device=dev)
     zu = buf[1:].view(shape)
     assert zu.data_ptr() % 16 != 0
-    assert Fn.canvas_noise(SEED, _t([t] * N, dev), shape, hop, out=zu) is zu
+    assert Fn.canvas_noise(SEED, ts([t] * N, dev), shape, hop, out=zu) is zu
     assert np.array_equal(zu.cpu().numpy(), ref)
     # windows [lo, N) with window_offset = lo are that slice of the full batch
     for lo in {N // 2, N - 1}:
-        part = Fn.canvas_noise(SEED, _t([t] * (N - lo), dev), (N - lo,) + shape[1:], hop, window_offset=lo)
+        part = Fn.canvas_noise(SEED, ts([t] * (N - lo), dev), (N - lo,) + shape[1:], hop, window_offset=lo)
         assert np.array_equal(part.cpu().numpy(), ref[lo:])
     # per-window timesteps that differ: window b is rows (b*hop .. b*hop + L - 1) of the per-sample stream at t_now[b]
     tn = [999 - 37 * b for b in range(N)]
-    per_t = Fn.canvas_noise(SEED, _t(tn, dev), shape, hop).cpu().numpy()
+    per_t = Fn.canvas_noise(SEED, ts(tn, dev), shape, hop).cpu().numpy()
     for b in range(N):
-        rows = Fn.gaussian_noise(SEED, b * hop, _t([tn[b]] * L_, dev), (L_, outer, inner)).cpu().numpy().reshape(L_, outer * inner)
+        rows = Fn.gaussian_noise(SEED, b * hop, ts([tn[b]] * L_, dev), (L_, outer, inner)).cpu().numpy().reshape(L_, outer * inner)
         assert np.array_equal(per_t[b:b + 1], CN.gather_windows(rows, (1,) + shape[1:], hop))
     assert np.abs(per_t.astype(np.float64) - CN.canvas_normals(SEED, tn, shape, hop)).max() < 1e-5
     if N > 1:
@@ -125,11 +84,11 @@ def test_kernel_far_window_offset(dev):
     from multimodal_diffusion_amd import functional as Fn
     shape, hop = (2, 8, 6, 4, 4), 3
     off = (2 ** 32 - 6 - hop) // hop                                         # the last position is <= 2^32 - 1
-    got = Fn.canvas_noise(7, _t([5, 5], dev), shape, hop, window_offset=off).cpu().numpy()
-    rows = Fn.gaussian_noise(7, off * hop, _t([5] * 9, dev), (9, 8, 16)).cpu().numpy().reshape(9, 128)
+    got = Fn.canvas_noise(7, ts([5, 5], dev), shape, hop, window_offset=off).cpu().numpy()
+    rows = Fn.gaussian_noise(7, off * hop, ts([5] * 9, dev), (9, 8, 16)).cpu().numpy().reshape(9, 128)
     assert np.array_equal(got, CN.gather_windows(rows, shape, hop))
     with pytest.raises(ValueError):
-        Fn.canvas_noise(7, _t([5, 5], dev), shape, hop, window_offset=off + 2)
+        Fn.canvas_noise(7, ts([5, 5], dev), shape, hop, window_offset=off + 2)
 
 
 # ------------------------------------------------------------------------------------------------- fused step = explicit noise
@@ -138,11 +97,11 @@ def test_kernel_far_window_offset(dev):
 def test_fused_step_equals_explicit_noise_video(dev, model, cfg_rows, rows, cond_only):
     from multimodal_diffusion_amd import functional as Fn
     cfg_rows(rows)
-    z, za, npr = _video_case(dev)
-    tn, tp = _t([981, 402, 40], dev), _t([961, 382, -1], dev)
+    z, za, npr = video_case(dev, B=3, W=16)
+    tn, tp = ts([981, 402, 40], dev), ts([961, 382, -1], dev)
     hop, off = 2, 5
     canvas = _canvas_engine(model, "video", tuple(z.shape), npr, hop, sample_offset=off)
-    plain = _engine(model, "video", tuple(z.shape), npr, eta=ETA)
+    plain = _engine(model[1], "video", tuple(z.shape), npr, eta=ETA)
     for e in (canvas, plain):
         e.set_prompt(za)
     a = canvas.step(z, tn, tp, cond_only=cond_only)
@@ -157,9 +116,9 @@ def test_fused_step_equals_explicit_noise_video_wide_rows(dev, model):
     from multimodal_diffusion_amd import functional as Fn
     g = torch.Generator().manual_seed(2)
     z, za = torch.randn(2, 8, 4, 16, 32, generator=g).to(dev), torch.randn(2, 8, 40, generator=g).to(dev)
-    tn, tp = _t([700, 300], dev), _t([680, 280], dev)
+    tn, tp = ts([700, 300], dev), ts([680, 280], dev)
     canvas = _canvas_engine(model, "video", tuple(z.shape), 10, 3, sample_offset=1)
-    plain = _engine(model, "video", tuple(z.shape), 10, eta=ETA)
+    plain = _engine(model[1], "video", tuple(z.shape), 10, eta=ETA)
     for e in (canvas, plain):
         e.set_prompt(za)
     noise = Fn.canvas_noise(SEED, tn, tuple(z.shape), 3, window_offset=1)
@@ -169,11 +128,11 @@ def test_fused_step_equals_explicit_noise_video_wide_rows(dev, model):
 @pytest.mark.parametrize("cond_only", [False, True])
 def test_fused_step_equals_explicit_noise_audio(dev, model, cond_only):
     from multimodal_diffusion_amd import functional as Fn
-    z, zv, npr = _audio_case(dev)
-    tn, tp = _t([981, 402, 40], dev), _t([961, 382, -1], dev)
+    z, zv, npr = audio_case(dev, B=3, L=150)
+    tn, tp = ts([981, 402, 40], dev), ts([961, 382, -1], dev)
     hop, off = 75, 11
     canvas = _canvas_engine(model, "audio", tuple(z.shape), npr, hop, sample_offset=off)
-    plain = _engine(model, "audio", tuple(z.shape), npr, eta=ETA)
+    plain = _engine(model[1], "audio", tuple(z.shape), npr, eta=ETA)
     for e in (canvas, plain):
         e.set_prompt(zv)
     a = canvas.step(z, tn, tp, cond_only=cond_only)
@@ -188,10 +147,10 @@ def test_fused_controlled_step_equals_composed(dev, model, cfg_rows, rows):
     is a permutation for video, r is elementwise), un-patch, then avd_ddim_step_f32 on the explicit canvas noise.  Bit for bit."""
     from multimodal_diffusion_amd import functional as Fn
     cfg_rows(rows)
-    z, za, npr = _video_case(dev)
+    z, za, npr = video_case(dev, B=3, W=16)
     B = z.shape[0]
     g, phi = [2.0, 3.5, 5.0], [0.7, 0.3, 1.0]
-    tn, tp = _t([981, 402, 40], dev), _t([961, 382, 20], dev)
+    tn, tp = ts([981, 402, 40], dev), ts([961, 382, 20], dev)
     hop = 2
     eng = _canvas_engine(model, "video", tuple(z.shape), npr, hop, guidance=g, guidance_rescale=phi)
     eng.set_prompt(za)
@@ -211,7 +170,7 @@ def test_fused_controlled_step_equals_composed(dev, model, cfg_rows, rows):
     plain = _canvas_engine(model, "video", tuple(z.shape), npr, hop)
     plain.set_prompt(za)
     assert not torch.equal(plain.step(z, tn, tp), out)
-    sample = _engine(model, "video", tuple(z.shape), npr, guidance=g, guidance_rescale=phi, eta=ETA, noise_seed=SEED)
+    sample = _engine(model[1], "video", tuple(z.shape), npr, guidance=g, guidance_rescale=phi, eta=ETA, noise_seed=SEED)
     sample.set_prompt(za)
     assert not torch.equal(sample.step(z, tn, tp), out)
 
@@ -223,11 +182,11 @@ def test_fused_guided_step_equals_composed(dev, model, cond_only):
     from multimodal_diffusion_amd import _lib as L
     from multimodal_diffusion_amd import functional as Fn
     from multimodal_diffusion_amd.sampler import frame_mask
-    z, za, npr = _video_case(dev)
+    z, za, npr = video_case(dev, B=3, W=16)
     B = z.shape[0]
     known = torch.randn(z.shape, generator=torch.Generator().manual_seed(4)).to(dev)
     mask = frame_mask(tuple(z.shape[1:]), 0, 2).to(dev)
-    tn, tp = _t([981, 402, 40], dev), _t([961, 382, -1], dev)
+    tn, tp = ts([981, 402, 40], dev), ts([961, 382, -1], dev)
     hop, off, gseed = 2, 3, 77
     eng = _canvas_engine(model, "video", tuple(z.shape), npr, hop, sample_offset=off)
     eng.set_prompt(za)
@@ -250,13 +209,13 @@ def test_fused_guided_step_equals_composed(dev, model, cond_only):
 def test_step_with_consensus_is_consensus_of_step(dev, model, target):
     from multimodal_diffusion_amd import functional as Fn
     if target == "video":
-        z, zp, npr = _video_case(dev)
+        z, zp, npr = video_case(dev, B=3, W=16)
         hop = 2
     else:
-        z, zp, npr = _audio_case(dev)
+        z, zp, npr = audio_case(dev, B=3, L=150)
         hop = 50
     L_ = W.dims(tuple(z.shape))[1]
-    tn, tp = _t([900] * 3, dev), _t([700] * 3, dev)
+    tn, tp = ts([900] * 3, dev), ts([700] * 3, dev)
     eng = _canvas_engine(model, target, tuple(z.shape), npr, hop)
     eng.set_prompt(zp)
     free = eng.step(z, tn, tp)
@@ -272,7 +231,7 @@ def test_step_with_consensus_is_consensus_of_step(dev, model, target):
 # ------------------------------------------------------------------------------------------------- graph = eager
 @pytest.mark.parametrize("interval", [None, "split"])
 def test_graph_equals_eager(dev, model, interval):
-    z, za, npr = _video_case(dev)
+    z, za, npr = video_case(dev, B=3, W=16)
     sched = R.sampling_schedule(1000, 6)
     iv = None if interval is None else (int(sched[4]), int(sched[1]))          # steps 1 .. 4 are CFG steps, 0 and 5 cond-only
     hop = 2
@@ -295,7 +254,7 @@ def test_consensus_trajectory_vs_oracle(dev, model):
     ws, _ = model
     n_steps, hop, off = 5, 2, 3
     sched = R.sampling_schedule(1000, n_steps)
-    z, zp, npr = _video_case(dev)
+    z, zp, npr = video_case(dev, B=3, W=16)
     wts = np.linspace(0.5, 2.0, 4).astype(np.float32)
     eng = _canvas_engine(model, "video", tuple(z.shape), npr, hop, sample_offset=off)
     eng.set_prompt(zp)
@@ -322,43 +281,15 @@ def test_consensus_trajectory_vs_oracle(dev, model):
 def stream(dev, model):
     """(kw, cfg): the geometry of test_gpu_window_consensus.py's stream tests (0.5 s windows every 0.25 s, 32 x 32 frames, a 4-step
     schedule) with ddim_eta = 0.5; the fp32 kernel family whatever the batch, so that batch sizes can be compared"""
-    import multimodal_diffusion_amd as A
-    _, (core, head, av, aa) = model
-    prev = core.matmul, head.matmul
-    core.matmul = head.matmul = "f32"
-    try:
-        torch.manual_seed(8)
-        vae = A.VideoVAE.from_config({"latent": {"channels": 8, "t_down": 4, "s_down": 8}}).eval().to(dev)
-        codec = A.AudioCodec.from_config({"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150},
-                                          "codec": {"hop_samples": 320}}).eval().to(dev)
-        cfg = {"tokenizer": {"width": 512, "video": {"tube": {"t": 2, "h": 4, "w": 4}}, "audio": {"chunk": {"length": 4, "stride": 4}}},
-               "video": {"fps": 16, "size": [32, 32], "latent": {"channels": 8, "t_down": 4, "s_down": 8}},
-               "audio": {"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150}},
-               "data": {"clip_seconds": 0.5}, "streaming": {"window_seconds": 0.5, "hop_seconds": 0.25, "crossfade_seconds": 0.125},
-               "diffusion": {m: {"steps": 1000, "sampler_steps": 4, "schedule": "cosine", "min_beta": 1e-4, "max_beta": 0.02}
-                             for m in ("video", "audio")},
-               "sampling": {"guidance_scale": {"video": 2.0, "audio": 2.0}, "ddim_eta": 0.5}}
-        kw = dict(cfg=cfg, vid_vae=vae, aud_codec=codec, adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, device=dev,
-                  shard=False)
-        yield kw, cfg
-    finally:
-        core.matmul, head.matmul = prev
-
-
-def _audio_prompt(n=18000):
-    wav = (0.1 * torch.randn(n, generator=torch.Generator().manual_seed(9))).numpy()      # 18000 samples: 4 windows
-    return dict(prompt_modality="audio", prompt_video=None, prompt_audio=wav, seed=10)
-
-
-def _video_prompt():
-    vid = torch.randint(0, 256, (20, 32, 32, 3), generator=torch.Generator().manual_seed(11), dtype=torch.uint8).numpy()
-    return dict(prompt_modality="video", prompt_video=vid, prompt_audio=None, seed=12)          # 20 frames: 4 windows
+    with matmul_f32(model[1]):
+        vae, codec, cfg = pipeline(dev, seed=8, clip_seconds=0.5, sampler_steps=4, streaming=STREAM_HALF_SECOND, sampling={"ddim_eta": 0.5})
+        yield dict(components(model[1], vae, codec, dev), cfg=cfg, shard=False), cfg
 
 
 def test_stream_generate_stochastic_consensus(dev, stream):
     from multimodal_diffusion_amd import stream_infer as S
     kw, cfg = stream
-    kws = dict(kw, consensus="uniform", noise_seed=3, noise_keying="canvas", return_latents=True, **_audio_prompt())
+    kws = dict(kw, consensus="uniform", noise_seed=3, noise_keying="canvas", return_latents=True, **audio_prompt())
     hop, L_ = S.latent_hop(cfg, "video")
     assert (hop, L_) == (1, 2)
     whole = S.stream_generate(**kws)
@@ -388,7 +319,7 @@ def test_stream_generate_stochastic_consensus(dev, stream):
 def test_stream_generate_video_prompt_direction(dev, stream):
     from multimodal_diffusion_amd import stream_infer as S
     kw, cfg = stream
-    kws = dict(kw, consensus="uniform", noise_seed=3, noise_keying="canvas", return_latents=True, **_video_prompt())
+    kws = dict(kw, consensus="uniform", noise_seed=3, noise_keying="canvas", return_latents=True, **video_prompt())
     assert S.latent_hop(cfg, "audio") == (75, 150)
     whole = S.stream_generate(**kws)
     assert whole["latents"].shape == (4, 8, 150) and W.overlaps_agree(whole["latents"], 75)
@@ -398,46 +329,46 @@ def test_stream_generate_video_prompt_direction(dev, stream):
 
 # ------------------------------------------------------------------------------------------------- misuse, and nothing else moved
 def test_engine_misuse(dev, model):
-    z, za, npr = _video_case(dev)
+    z, za, npr = video_case(dev, B=3, W=16)
     shape = tuple(z.shape)
     with pytest.raises(ValueError, match="noise_seed"):
-        _engine(model, "video", shape, npr, eta=ETA, noise_keying="canvas", canvas_hop=2)
+        _engine(model[1], "video", shape, npr, eta=ETA, noise_keying="canvas", canvas_hop=2)
     with pytest.raises(ValueError, match="canvas_hop"):
-        _engine(model, "video", shape, npr, eta=ETA, noise_seed=1, noise_keying="canvas")
+        _engine(model[1], "video", shape, npr, eta=ETA, noise_seed=1, noise_keying="canvas")
     for bad in (0, -1, 1.5, True):
         with pytest.raises(ValueError):
-            _engine(model, "video", shape, npr, eta=ETA, noise_seed=1, noise_keying="canvas", canvas_hop=bad)
+            _engine(model[1], "video", shape, npr, eta=ETA, noise_seed=1, noise_keying="canvas", canvas_hop=bad)
     with pytest.raises(ValueError):
-        _engine(model, "video", shape, npr, eta=ETA, noise_seed=1, noise_keying="position", canvas_hop=2)
+        _engine(model[1], "video", shape, npr, eta=ETA, noise_seed=1, noise_keying="position", canvas_hop=2)
     with pytest.raises(ValueError):
-        _engine(model, "video", shape, npr, eta=ETA, noise_seed=1, canvas_hop=2)                  # canvas_hop without the keying
+        _engine(model[1], "video", shape, npr, eta=ETA, noise_seed=1, canvas_hop=2)                  # canvas_hop without the keying
     with pytest.raises(ValueError):                                                                 # (2^32 - 2 + 2)*2 + 4 > 2^32
-        _engine(model, "video", shape, npr, eta=ETA, noise_seed=1, noise_keying="canvas", canvas_hop=2, sample_offset=2 ** 32 - 2)
+        _engine(model[1], "video", shape, npr, eta=ETA, noise_seed=1, noise_keying="canvas", canvas_hop=2, sample_offset=2 ** 32 - 2)
     eng = _canvas_engine(model, "video", shape, npr, 2)
     eng.set_prompt(za)
     gen = eng._generation
     with pytest.raises(ValueError, match="canvas_hop"):
         eng.set_window_consensus(3)
     assert eng._cons_hop is None and eng._generation == gen
-    tn, tp = _t([900] * 3, dev), _t([700] * 3, dev)
+    tn, tp = ts([900] * 3, dev), ts([700] * 3, dev)
     with pytest.raises(ValueError):
         eng.step(z, tn, tp, noise=torch.randn_like(z))
     # the sample-keyed engine keeps today's refusal, naming the option
     with pytest.raises(ValueError, match="eta.*noise_keying='canvas'"):
-        _engine(model, "video", shape, npr, eta=ETA, noise_seed=1).set_window_consensus(2)
+        _engine(model[1], "video", shape, npr, eta=ETA, noise_seed=1).set_window_consensus(2)
 
 
 def test_default_engines_keep_their_bits(dev, model):
     """Nothing else moved: at eta == 0 a canvas-keyed engine is the plain engine, and a default (sample-keyed) seeded engine at eta > 0
     still draws the per-sample stream — each compared through the pre-existing entries."""
     from multimodal_diffusion_amd import functional as Fn
-    z, za, npr = _video_case(dev)
+    z, za, npr = video_case(dev, B=3, W=16)
     shape = tuple(z.shape)
-    tn, tp = _t([900, 100, 500], dev), _t([880, 80, 480], dev)
-    canvas0 = _engine(model, "video", shape, npr, eta=0.0, noise_seed=SEED, noise_keying="canvas", canvas_hop=2)
-    plain0 = _engine(model, "video", shape, npr, eta=0.0)
-    seeded = _engine(model, "video", shape, npr, eta=ETA, noise_seed=SEED, sample_offset=5)
-    plain = _engine(model, "video", shape, npr, eta=ETA)
+    tn, tp = ts([900, 100, 500], dev), ts([880, 80, 480], dev)
+    canvas0 = _engine(model[1], "video", shape, npr, eta=0.0, noise_seed=SEED, noise_keying="canvas", canvas_hop=2)
+    plain0 = _engine(model[1], "video", shape, npr, eta=0.0)
+    seeded = _engine(model[1], "video", shape, npr, eta=ETA, noise_seed=SEED, sample_offset=5)
+    plain = _engine(model[1], "video", shape, npr, eta=ETA)
     for e in (canvas0, plain0, seeded, plain):
         e.set_prompt(za)
     assert torch.equal(canvas0.step(z, tn, tp), plain0.step(z, tn, tp))

@@ -4,62 +4,21 @@ and with / without a latent guide, bit-identity of rows / gather forms, graph re
 batch splits, all-equal arrays against the scalar and phi = 0 against the plain engine, trajectories against the CPU oracle, the
 phi = 1 property, sample_one_direction's sampling.guidance_rescale, and misuse."""
 import ctypes as C
+from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
 import _cfg_ref as CR
+from _kit import ABAR, Recorder, case, components, dev, engine, model, pipeline, ts  # noqa: F401  (dev / model are fixtures)
 from _tune import cfg_rows  # noqa: F401  (fixture)
 from oracle import ref_cpu as R
 
 pytestmark = pytest.mark.gpu
-ABAR = R.alpha_bar_table(R.beta_table(1000))
 GS = 3.0
 GSEED = 77
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def model(dev):
-    import multimodal_diffusion_amd as A
-    ws = R.synth_weights(seed=0, n_layers=2)
-    core = A.MMDiT(d_model=512, n_layers=2, n_heads=8, mlp_ratio=4.0).eval()
-    core.load_state_dict(ws["core"], strict=True)
-    head = A.MultiModalNoiseHead({"video": 512, "audio": 512}, {"video": 256, "audio": 32}, hidden_dim=512).eval()
-    head.load_state_dict(ws["head"], strict=True)
-    av, aa = A.LinearAdapter(256, 256), A.LinearAdapter(32, 256)
-    av.load_state_dict(ws["adapt_v"])
-    aa.load_state_dict(ws["adapt_a"])
-    return ws, tuple(m.to(dev) for m in (core, head, av, aa))
-
-
-def _engine(model, target, shape, n_prompt, guidance=GS, **kw):
-    import multimodal_diffusion_amd as A
-    _, (core, head, av, aa) = model
-    return A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target=target, latent_shape=shape,
-                           prompt_tokens=n_prompt, alpha_bar=ABAR, guidance=guidance, **kw)
-
-
-def _case(dev, target, B=2, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    if target == "video":
-        z = torch.randn(B, 8, 4, 16, 32, generator=g)
-        zp, npr = torch.randn(B, 8, 40, generator=g), 10
-    else:
-        z = torch.randn(B, 8, 40, generator=g)
-        zp, npr = torch.randn(B, 8, 4, 8, 8, generator=g), 8
-    known = torch.randn(z.shape, generator=g)
-    return z.to(dev), zp.to(dev), npr, known.to(dev)
-
-
-def _t(v, dev):
-    return torch.tensor(v, dtype=torch.long, device=dev)
+_engine = partial(engine, guidance=GS)        # engine(mods, target, shape, n_prompt, **kw) at this file's guidance
 
 
 def _ulps(a, b):
@@ -128,9 +87,9 @@ G2, PHI2 = [2.0, 5.0], [0.7, 0.3]
 @pytest.mark.parametrize("target", ["video", "audio"])
 def test_fused_equals_composed(dev, model, cfg_rows, target, kw, guided):
     from multimodal_diffusion_amd import functional as Fn
-    z, zp, npr, known = _case(dev, target)
+    z, zp, npr, known = case(dev, target)
     B = z.shape[0]
-    eng = _engine(model, target, tuple(z.shape), npr, guidance=G2, guidance_rescale=PHI2, **kw)
+    eng = _engine(model[1], target, tuple(z.shape), npr, guidance=G2, guidance_rescale=PHI2, **kw)
     eng.set_prompt(zp)
     dpm = kw.get("solver") == "dpmpp_2m"
     mask = None
@@ -140,8 +99,8 @@ def test_fused_equals_composed(dev, model, cfg_rows, target, kw, guided):
         mask = mask.to(dev)
         eng.set_known(known, mask, guide_seed=GSEED)
     h0 = torch.randn(z.shape, generator=torch.Generator().manual_seed(7)).to(dev)
-    tn, tp = _t([981, 402], dev), _t([961, 382], dev)
-    tl = _t([999, 700], dev) if dpm else None
+    tn, tp = ts([981, 402], dev), ts([961, 382], dev)
+    tl = ts([999, 700], dev) if dpm else None
 
     def fused():
         if dpm:
@@ -184,11 +143,11 @@ def test_fused_equals_composed(dev, model, cfg_rows, target, kw, guided):
 # ------------------------------------------------------------------------------------------------- bit-identities
 def test_graph_replay_follows_set_cfg(dev, model):
     from multimodal_diffusion_amd import _lib as L
-    z, zp, npr, _ = _case(dev, "video")
+    z, zp, npr, _ = case(dev, "video")
     B = z.shape[0]
     sched = R.sampling_schedule(1000, 5)
     A_, B_ = dict(guidance=[2.0, 5.0], rescale=[0.7, 0.0]), dict(guidance=[4.0, 1.5], rescale=[0.2, 1.0])
-    eng = _engine(model, "video", tuple(z.shape), npr, guidance=A_["guidance"], guidance_rescale=A_["rescale"])
+    eng = _engine(model[1], "video", tuple(z.shape), npr, guidance=A_["guidance"], guidance_rescale=A_["rescale"])
     eng.set_prompt(zp)
     # eager: values A for steps 0..2, B for steps 3..4
     x = z.clone()
@@ -220,11 +179,11 @@ def test_graph_replay_follows_set_cfg(dev, model):
 
 @pytest.mark.parametrize("target", ["video", "audio"])
 def test_split_streams_and_defaults(dev, model, target):
-    z, zp, npr, _ = _case(dev, target)
-    tn, tp = _t([981, 402], dev), _t([961, 382], dev)
+    z, zp, npr, _ = case(dev, target)
+    tn, tp = ts([981, 402], dev), ts([961, 382], dev)
 
     def step(**kw):
-        eng = _engine(model, target, tuple(z.shape), npr, **kw)
+        eng = _engine(model[1], target, tuple(z.shape), npr, **kw)
         eng.set_prompt(zp)
         return eng, eng.step(z, tn, tp)
 
@@ -246,12 +205,12 @@ def test_split_streams_and_defaults(dev, model, target):
 
 
 def test_batch_split(dev, model):
-    z, zp, npr, _ = _case(dev, "video", B=4)
+    z, zp, npr, _ = case(dev, "video", B=4)
     g4, p4 = [2.0, 5.0, 3.0, 1.5], [0.7, 0.0, 1.0, 0.3]
     sched = R.sampling_schedule(1000, 4)
 
     def run(sl, **kw):
-        eng = _engine(model, "video", (sl.stop - sl.start,) + tuple(z.shape[1:]), npr, matmul="f32", **kw)
+        eng = _engine(model[1], "video", (sl.stop - sl.start,) + tuple(z.shape[1:]), npr, matmul="f32", **kw)
         eng.set_prompt(zp[sl].contiguous())
         return eng.run(z[sl].contiguous(), sched)
 
@@ -299,7 +258,7 @@ def test_trajectory_vs_oracle(dev, model, target):
         z, zp, npr = torch.randn(2, 8, 4, 16, 16, generator=gen), torch.randn(2, 8, 40, generator=gen), 10
     else:
         z, zp, npr = torch.randn(2, 8, 40, generator=gen), torch.randn(2, 8, 4, 8, 8, generator=gen), 8
-    eng = _engine(model, target, tuple(z.shape), npr, guidance=g, guidance_rescale=phi, matmul="f32")
+    eng = _engine(model[1], target, tuple(z.shape), npr, guidance=g, guidance_rescale=phi, matmul="f32")
     eng.set_prompt(zp.to(dev))
     out = eng.run(z.to(dev), sched).cpu().double()
     x = z.clone()
@@ -310,37 +269,13 @@ def test_trajectory_vs_oracle(dev, model, target):
 
 
 # ------------------------------------------------------------------------------------------------- sample_one_direction
-class _Recorder:
-    """wraps a VAE and keeps the latent it last decoded"""
-
-    def __init__(self, inner):
-        self.inner, self.last = inner, None
-
-    def encode(self, x):
-        return self.inner.encode(x)
-
-    def decode(self, z):
-        self.last = z.clone()
-        return self.inner.decode(z)
-
-
 def test_sample_one_direction_guidance_rescale(dev, model):
     import multimodal_diffusion_amd as A
-    _, (core, head, av, aa) = model
-    torch.manual_seed(8)
-    vae = _Recorder(A.VideoVAE.from_config({"latent": {"channels": 8, "t_down": 4, "s_down": 8}}).eval().to(dev))
-    codec = A.AudioCodec.from_config({"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150},
-                                      "codec": {"hop_samples": 320}}).eval().to(dev)
-    cfg = {"tokenizer": {"width": 512, "video": {"tube": {"t": 2, "h": 4, "w": 4}}, "audio": {"chunk": {"length": 4, "stride": 4}}},
-           "video": {"fps": 16, "size": [32, 32], "latent": {"channels": 8, "t_down": 4, "s_down": 8}},
-           "audio": {"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150}},
-           "data": {"clip_seconds": 1.0},
-           "diffusion": {m: {"steps": 1000, "sampler_steps": 5, "schedule": "cosine", "min_beta": 1e-4, "max_beta": 0.02}
-                         for m in ("video", "audio")},
-           "sampling": {"guidance_scale": {"video": 4.0, "audio": 4.0}}}
+    vae, codec, cfg = pipeline(dev, seed=8, clip_seconds=1.0, sampler_steps=5,
+                               sampling={"guidance_scale": {"video": 4.0, "audio": 4.0}})
+    vae = Recorder(vae)
     wav = (0.1 * torch.randn(16000, generator=torch.Generator().manual_seed(9))).numpy()
-    kw = dict(vid_vae=vae, aud_codec=codec, adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, device=dev,
-              prompt_modality="audio", prompt_video=None, prompt_audio=wav)
+    kw = dict(components(model[1], vae, codec, dev), prompt_modality="audio", prompt_video=None, prompt_audio=wav)
     noise = torch.randn(1, 8, 4, 4, 4, generator=torch.Generator().manual_seed(4))
     a = A.sample_one_direction(cfg=cfg, init_noise=noise, **kw)
     za = vae.last
@@ -357,12 +292,12 @@ def test_sample_one_direction_guidance_rescale(dev, model):
 def test_misuse(dev, model):
     from multimodal_diffusion_amd import _lib as L
     from multimodal_diffusion_amd import functional as Fn
-    z, zp, npr, _ = _case(dev, "video")
+    z, zp, npr, _ = case(dev, "video")
     for bad in (dict(guidance_rescale=1.5), dict(guidance_rescale=float("nan")), dict(guidance_rescale=[0.2, -0.1]),
                 dict(guidance=[1.0, 2.0, 3.0]), dict(guidance=[1.0, float("inf")])):
         with pytest.raises(ValueError):
-            _engine(model, "video", tuple(z.shape), npr, **bad)
-    eng = _engine(model, "video", tuple(z.shape), npr, solver="dpmpp_2m", guidance_rescale=0.5)
+            _engine(model[1], "video", tuple(z.shape), npr, **bad)
+    eng = _engine(model[1], "video", tuple(z.shape), npr, solver="dpmpp_2m", guidance_rescale=0.5)
     eng.set_prompt(zp)
     gen = eng._generation
     with pytest.raises(ValueError, match="guidance_rescale"):
@@ -373,9 +308,9 @@ def test_misuse(dev, model):
     with pytest.raises(ValueError):
         Fn.cfg_rescale(z[:, :1, :1, :1, :1].contiguous(), z[:, :1, :1, :1, :1].contiguous(), 0.5)    # one element per sample
     # unseeded eta > 0 with a control
-    ddim = _engine(model, "video", tuple(z.shape), npr, eta=0.5, guidance=[2.0, 3.0])
+    ddim = _engine(model[1], "video", tuple(z.shape), npr, eta=0.5, guidance=[2.0, 3.0])
     ddim.set_prompt(zp)
-    tn, tp = _t([900, 900], dev), _t([800, 800], dev)
+    tn, tp = ts([900, 900], dev), ts([800, 800], dev)
     with pytest.raises(ValueError, match="noise_seed"):
         ddim.step(z, tn, tp)
     # the stats scratch overlapping z_out / x0_hist, or too small, at the C entry: refused before any launch

@@ -2,63 +2,22 @@
 (edge cases included), the fused CFG + un-patch / overlap-add + DPM kernels against explicit computation from the step's own eps
 tokens (both video kernel forms, audio, split streams), the first-order step against DDIM, graph replay against eager launches,
 trajectories against the CPU oracle driven by the fp64 reference, batch invariance of stream_generate, and misuse."""
+from functools import partial
+
 import numpy as np
 import pytest
 import torch
 
 import _dpm_ref as D
+from _kit import (ABAR, STREAM_HALF_SECOND, audio_case, audio_prompt, components, dev, engine, matmul_f32, model,  # noqa: F401  (dev / model are fixtures)
+                  pipeline, ts, video_case)
 from _tune import cfg_rows  # noqa: F401  (fixture)
 from conftest import rel_err
 from oracle import ref_cpu as R
 
 pytestmark = pytest.mark.gpu
-ABAR = R.alpha_bar_table(R.beta_table(1000))
 G = 3.0
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def model(dev):
-    import multimodal_diffusion_amd as A
-    ws = R.synth_weights(seed=0, n_layers=2)
-    core = A.MMDiT(d_model=512, n_layers=2, n_heads=8, mlp_ratio=4.0).eval()
-    core.load_state_dict(ws["core"], strict=True)
-    head = A.MultiModalNoiseHead({"video": 512, "audio": 512}, {"video": 256, "audio": 32}, hidden_dim=512).eval()
-    head.load_state_dict(ws["head"], strict=True)
-    av, aa = A.LinearAdapter(256, 256), A.LinearAdapter(32, 256)
-    av.load_state_dict(ws["adapt_v"])
-    aa.load_state_dict(ws["adapt_a"])
-    return ws, tuple(m.to(dev) for m in (core, head, av, aa))
-
-
-def _engine(model, target, shape, n_prompt, **kw):
-    import multimodal_diffusion_amd as A
-    _, (core, head, av, aa) = model
-    return A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target=target, latent_shape=shape,
-                           prompt_tokens=n_prompt, alpha_bar=ABAR, guidance=G, **kw)
-
-
-def _video_case(dev, B=2, W=32, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    z = torch.randn(B, 8, 4, 16, W, generator=g).to(dev)
-    za = torch.randn(B, 8, 40, generator=g).to(dev)           # 10 prompt tokens (chunk 4, stride 4)
-    return z, za, 10
-
-
-def _audio_case(dev, B=2, seed=1):
-    g = torch.Generator().manual_seed(seed)
-    z = torch.randn(B, 8, 40, generator=g).to(dev)
-    zv = torch.randn(B, 8, 4, 8, 8, generator=g).to(dev)      # 8 prompt tokens (tube 2 x 4 x 4)
-    return z, zv, 8
-
-
-def _t(v, dev):
-    return torch.tensor(v, dtype=torch.long, device=dev)
+_engine = partial(engine, guidance=G)        # engine(mods, target, shape, n_prompt, **kw) at this file's guidance
 
 
 # ------------------------------------------------------------------------------------------------- elementwise update = fp32 mirror
@@ -82,7 +41,7 @@ def test_elementwise_step_matches_fp32_mirror(dev):
     h[first] = float("nan")                                   # a first-order step never reads its history
     assert (~first).sum() >= 3 and first.sum() >= 6
     hd = h.to(dev)
-    out = Fn.dpmpp_2m_step(x.to(dev), e.to(dev), hd, _t(tl, dev), _t(tn, dev), _t(tp, dev), abar)
+    out = Fn.dpmpp_2m_step(x.to(dev), e.to(dev), hd, ts(tl, dev), ts(tn, dev), ts(tp, dev), abar)
     ref, x0 = D.step_f32(x.numpy(), e.numpy(), h.numpy(), abar.numpy(), tl, tn, tp)
     out = out.cpu()
     assert torch.isfinite(out).all() and torch.isfinite(hd).all()
@@ -111,15 +70,15 @@ TL, TN, TP = [-1, 981, 700], [981, 402, 40], [961, 382, -1]      # first order, 
 
 
 def test_fused_step_video_both_forms(dev, model, cfg_rows):
-    z, za, npr = _video_case(dev, B=3)
+    z, za, npr = video_case(dev, B=3)
     h0 = torch.randn(z.shape, generator=torch.Generator().manual_seed(7)).to(dev)
     outs = []
     for rows in (1, 0):
         cfg_rows(rows)
-        eng = _engine(model, "video", tuple(z.shape), npr, solver="dpmpp_2m")
+        eng = _engine(model[1], "video", tuple(z.shape), npr, solver="dpmpp_2m")
         eng.set_prompt(za)
         eng.x0_hist.copy_(h0)
-        out = eng.step(z, _t(TN, dev), _t(TP, dev), t_last=_t(TL, dev))
+        out = eng.step(z, ts(TN, dev), ts(TP, dev), t_last=ts(TL, dev))
         ref, x0 = _explicit(eng, z, h0, TL, TN, TP, "video")
         assert rel_err(out.cpu(), torch.from_numpy(ref)) <= 1e-6
         assert rel_err(eng.x0_hist.cpu(), torch.from_numpy(x0)) <= 1e-6
@@ -129,25 +88,25 @@ def test_fused_step_video_both_forms(dev, model, cfg_rows):
 
 
 def test_fused_step_audio(dev, model):
-    z, zv, npr = _audio_case(dev, B=3)
+    z, zv, npr = audio_case(dev, B=3)
     h0 = torch.randn(z.shape, generator=torch.Generator().manual_seed(8)).to(dev)
-    eng = _engine(model, "audio", tuple(z.shape), npr, solver="dpmpp_2m")
+    eng = _engine(model[1], "audio", tuple(z.shape), npr, solver="dpmpp_2m")
     eng.set_prompt(zv)
     eng.x0_hist.copy_(h0)
-    out = eng.step(z, _t(TN, dev), _t(TP, dev), t_last=_t(TL, dev))
+    out = eng.step(z, ts(TN, dev), ts(TP, dev), t_last=ts(TL, dev))
     ref, x0 = _explicit(eng, z, h0, TL, TN, TP, "audio")
     assert rel_err(out.cpu(), torch.from_numpy(ref)) <= 1e-6
     assert rel_err(eng.x0_hist.cpu(), torch.from_numpy(x0)) <= 1e-6
 
 
 def test_fused_step_split_streams_f16x2(dev, model):
-    z, za, npr = _video_case(dev, B=2)
+    z, za, npr = video_case(dev, B=2)
     tl, tn, tp = [999, 720], [700, 300], [680, 280]
     h0 = torch.randn(z.shape, generator=torch.Generator().manual_seed(9)).to(dev)
-    eng = _engine(model, "video", tuple(z.shape), npr, solver="dpmpp_2m", matmul="f16x2", split_streams=True)
+    eng = _engine(model[1], "video", tuple(z.shape), npr, solver="dpmpp_2m", matmul="f16x2", split_streams=True)
     eng.set_prompt(za)
     eng.x0_hist.copy_(h0)
-    out = eng.step(z, _t(tn, dev), _t(tp, dev), t_last=_t(tl, dev))
+    out = eng.step(z, ts(tn, dev), ts(tp, dev), t_last=ts(tl, dev))
     ref, _ = _explicit(eng, z, h0, tl, tn, tp, "video")
     assert rel_err(out.cpu(), torch.from_numpy(ref)) <= 1e-6
 
@@ -155,12 +114,12 @@ def test_fused_step_split_streams_f16x2(dev, model):
 # ------------------------------------------------------------------------------------------------- against DDIM
 @pytest.mark.parametrize("target", ["video", "audio"])
 def test_first_order_step_and_one_step_trajectory_match_ddim(dev, model, target):
-    z, zp, npr = _video_case(dev, B=2) if target == "video" else _audio_case(dev, B=2)
-    dpm = _engine(model, target, tuple(z.shape), npr, solver="dpmpp_2m")
-    ddim = _engine(model, target, tuple(z.shape), npr)
+    z, zp, npr = video_case(dev, B=2) if target == "video" else audio_case(dev, B=2)
+    dpm = _engine(model[1], target, tuple(z.shape), npr, solver="dpmpp_2m")
+    ddim = _engine(model[1], target, tuple(z.shape), npr)
     for e in (dpm, ddim):
         e.set_prompt(zp)
-    tn, tp = _t([999, 500], dev), _t([950, 450], dev)
+    tn, tp = ts([999, 500], dev), ts([950, 450], dev)
     a = dpm.step(z, tn, tp)                                   # t_last = None: first order
     b = ddim.step(z, tn, tp)
     assert rel_err(a.cpu(), b.cpu()) <= 2e-6
@@ -171,23 +130,23 @@ def test_first_order_step_and_one_step_trajectory_match_ddim(dev, model, target)
 # ------------------------------------------------------------------------------------------------- graph = eager
 @pytest.mark.parametrize("n_steps", [5, 6])
 def test_graph_equals_eager(dev, model, n_steps):
-    z, za, npr = _video_case(dev, B=2)
+    z, za, npr = video_case(dev, B=2)
     sched = R.sampling_schedule(1000, n_steps)
-    eng = _engine(model, "video", tuple(z.shape), npr, solver="dpmpp_2m")
+    eng = _engine(model[1], "video", tuple(z.shape), npr, solver="dpmpp_2m")
     eng.set_prompt(za)
     zg = eng.run(z, sched, graph=True)
     ze = eng.run(z, sched, graph=False)
     assert torch.equal(zg, ze)
     assert torch.equal(eng.run(z, sched, graph=True), zg)     # a second run starts first order again: no stale history
     # explicit steps with the history passed by hand land on the same bits
-    eng2 = _engine(model, "video", tuple(z.shape), npr, solver="dpmpp_2m")
+    eng2 = _engine(model[1], "video", tuple(z.shape), npr, solver="dpmpp_2m")
     eng2.set_prompt(za)
     x = z.clone()
     for i in range(n_steps):
-        tl = None if i == 0 else _t([int(sched[i - 1])] * 2, dev)
-        x = eng2.step(x, _t([int(sched[i])] * 2, dev), _t([int(sched[i + 1])] * 2, dev), t_last=tl)
+        tl = None if i == 0 else ts([int(sched[i - 1])] * 2, dev)
+        x = eng2.step(x, ts([int(sched[i])] * 2, dev), ts([int(sched[i + 1])] * 2, dev), t_last=tl)
     assert torch.equal(x, zg)
-    ddim = _engine(model, "video", tuple(z.shape), npr)
+    ddim = _engine(model[1], "video", tuple(z.shape), npr)
     ddim.set_prompt(za)
     assert not torch.equal(ddim.run(z, sched), zg)             # the second-order steps are live
 
@@ -200,10 +159,10 @@ def test_trajectory_vs_oracle(dev, model, target, mode):
     n_steps = 8
     sched = R.sampling_schedule(1000, n_steps)
     if target == "video":
-        z, zp, npr = _video_case(dev, B=2, W=16)
+        z, zp, npr = video_case(dev, B=2, W=16)
     else:
-        z, zp, npr = _audio_case(dev, B=2)
-    eng = _engine(model, target, tuple(z.shape), npr, solver="dpmpp_2m", matmul=mode)
+        z, zp, npr = audio_case(dev, B=2)
+    eng = _engine(model[1], target, tuple(z.shape), npr, solver="dpmpp_2m", matmul=mode)
     eng.set_prompt(zp)
     out = eng.run(z, sched).cpu().double()
     x, p = z.cpu(), zp.cpu()
@@ -226,33 +185,16 @@ def test_trajectory_vs_oracle(dev, model, target, mode):
 
 # ------------------------------------------------------------------------------------------------- batch invariance
 def test_stream_generate_batch_invariance(dev, model):
-    import multimodal_diffusion_amd as A
     from multimodal_diffusion_amd import stream_infer as S
-    _, (core, head, av, aa) = model
-    prev = core.matmul, head.matmul
-    core.matmul = head.matmul = "f32"     # one kernel family whatever the batch (the "auto" rule switches at 2,048 / 6,144 rows)
-    try:
-        torch.manual_seed(8)
-        vae = A.VideoVAE.from_config({"latent": {"channels": 8, "t_down": 4, "s_down": 8}}).eval().to(dev)
-        codec = A.AudioCodec.from_config({"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150},
-                                          "codec": {"hop_samples": 320}}).eval().to(dev)
-        cfg = {"tokenizer": {"width": 512, "video": {"tube": {"t": 2, "h": 4, "w": 4}}, "audio": {"chunk": {"length": 4, "stride": 4}}},
-               "video": {"fps": 16, "size": [32, 32], "latent": {"channels": 8, "t_down": 4, "s_down": 8}},
-               "audio": {"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150}},
-               "data": {"clip_seconds": 0.5}, "streaming": {"window_seconds": 0.5, "hop_seconds": 0.25, "crossfade_seconds": 0.125},
-               "diffusion": {m: {"steps": 1000, "sampler_steps": 4, "schedule": "cosine", "min_beta": 1e-4, "max_beta": 0.02}
-                             for m in ("video", "audio")},
-               "sampling": {"solver": "dpmpp_2m", "guidance_scale": {"video": 2.0, "audio": 2.0}}}
-        wav = (0.1 * torch.randn(18000, generator=torch.Generator().manual_seed(9))).numpy()      # 4 windows
-        kw = dict(cfg=cfg, vid_vae=vae, aud_codec=codec, adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, device=dev,
-                  prompt_modality="audio", prompt_video=None, prompt_audio=wav, seed=10)
+    with matmul_f32(model[1]):            # one kernel family whatever the batch (the "auto" rule switches at 2,048 / 6,144 rows)
+        vae, codec, cfg = pipeline(dev, seed=8, clip_seconds=0.5, sampler_steps=4, streaming=STREAM_HALF_SECOND,
+                                   sampling={"solver": "dpmpp_2m"})
+        kw = dict(components(model[1], vae, codec, dev), cfg=cfg, **audio_prompt())                # 4 windows
         whole = S.stream_generate(shard=False, **kw)
         per_window = S.stream_generate(shard=False, max_windows_per_batch=1, **kw)
         assert np.array_equal(whole["video"], per_window["video"])
         ddim = S.stream_generate(shard=False, **dict(kw, cfg=dict(cfg, sampling={"guidance_scale": cfg["sampling"]["guidance_scale"]})))
         assert not np.array_equal(ddim["video"], whole["video"])       # the config key selects the solver
-    finally:
-        core.matmul, head.matmul = prev
 
 
 # ------------------------------------------------------------------------------------------------- misuse
@@ -260,10 +202,10 @@ def test_misuse(dev, model):
     import multimodal_diffusion_amd as A
     from multimodal_diffusion_amd import functional as Fn
     from multimodal_diffusion_amd import _lib as L
-    z, za, npr = _video_case(dev, B=2)
-    eng = _engine(model, "video", tuple(z.shape), npr, solver="dpmpp_2m")
+    z, za, npr = video_case(dev, B=2)
+    eng = _engine(model[1], "video", tuple(z.shape), npr, solver="dpmpp_2m")
     eng.set_prompt(za)
-    tn, tp = _t([900, 900], dev), _t([800, 800], dev)
+    tn, tp = ts([900, 900], dev), ts([800, 800], dev)
     eng.x0_hist.copy_(z)
     with pytest.raises(L.AvdError):
         eng.step(eng.x0_hist, tn, tp)
@@ -278,8 +220,8 @@ def test_misuse(dev, model):
     with pytest.raises(ValueError, match="x0_hist"):
         Fn.dpmpp_2m_step(x, torch.randn_like(x), x, tn, tn, tp, ABAR)
     with pytest.raises(ValueError):
-        _engine(model, "video", tuple(z.shape), npr, solver="dpmpp_2m", eta=0.5)
-    ddim = _engine(model, "video", tuple(z.shape), npr)
+        _engine(model[1], "video", tuple(z.shape), npr, solver="dpmpp_2m", eta=0.5)
+    ddim = _engine(model[1], "video", tuple(z.shape), npr)
     ddim.set_prompt(za)
     with pytest.raises(ValueError):
         ddim.step(z, tn, tp, t_last=tn)

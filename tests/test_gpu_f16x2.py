@@ -7,10 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+from _kit import components, dev, engine, full, modules, pipeline  # noqa: F401  (dev / full are fixtures)
 from _tune import tuned
 from conftest import rel_err
 from oracle import ref_cpu as R
-from test_gpu_parity import TOL, _full_modules, dev, full  # noqa: F401  (dev / full are fixtures)
+from test_gpu_parity import TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -135,8 +136,8 @@ def test_core_f16x2_vs_oracle_and_f32(dev, full):
     """MMDiT.forward at 16,840 rows: inside the fp32 parity tolerance, and within a small multiple of the fp32-MFMA path's own
     distance from the fp64 oracle."""
     ws, _ = full
-    core2, _, _, _ = _full_modules(dev, ws)
-    core32, _, _, _ = _full_modules(dev, ws)
+    core2, _, _, _ = modules(dev, ws, 8)
+    core32, _, _, _ = modules(dev, ws, 8)
     core2.matmul, core32.matmul = "f16x2", "f32"
     x = torch.randn(40, 421, 512, generator=torch.Generator().manual_seed(12))
     y2 = core2(x.to(dev)).cpu()
@@ -154,9 +155,8 @@ def test_core_f16x2_vs_oracle_and_f32(dev, full):
 
 def test_full_step_f16x2_vs_oracle(dev, full):
     """BASELINE C3 shape, B=20 (16,840 rows), one CFG step against the CPU oracle; deterministic."""
-    import multimodal_diffusion_amd as A
     ws, _ = full
-    core, head, av, aa = _full_modules(dev, ws)
+    core, head, av, aa = modules(dev, ws, 8)
     B = 20
     g = torch.Generator().manual_seed(256)
     z_v = torch.randn(B, 8, 12, 32, 32, generator=g)
@@ -169,8 +169,7 @@ def test_full_step_f16x2_vs_oracle(dev, full):
                              core=ws["core"], head=ws["head"], n_layers=8, n_heads=8, guidance=3.5)
     outs = {}
     for mode in ("f16x2", "f32"):
-        eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video",
-                              latent_shape=tuple(z_v.shape), prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul=mode)
+        eng = engine((core, head, av, aa), "video", tuple(z_v.shape), 37, alpha_bar=abar, guidance=3.5, matmul=mode)
         eng.set_prompt(z_a.to(dev))
         outs[mode] = eng.step(z_v.to(dev), tn.to(dev), tp.to(dev))
         assert torch.equal(outs[mode], eng.step(z_v.to(dev), tn.to(dev), tp.to(dev)))
@@ -182,7 +181,6 @@ def test_full_step_f16x2_vs_oracle(dev, full):
 def test_chain_f16x2_tracks_f32(dev, full):
     """A 10-step DDIM + CFG trajectory at the C3 shape (B=20): within the chained tolerance of the fp32-MFMA mode (rel L2 <= 1e-3,
     SURVEY 8c), eager and as a replayed HIP graph — late steps carry |x| ~ 1e4..1e5 in the residual stream."""
-    import multimodal_diffusion_amd as A
     from multimodal_diffusion_amd import schedule_utils as su
     ws, _ = full
     B = 20
@@ -193,9 +191,8 @@ def test_chain_f16x2_tracks_f32(dev, full):
     sched = su.make_sampling_schedule(1000, 10)
     outs = {}
     for mode in ("f32", "bf16x3", "f16x2"):
-        core, head, av, aa = _full_modules(dev, ws)
-        eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video",
-                              latent_shape=tuple(z.shape), prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul=mode)
+        core, head, av, aa = modules(dev, ws, 8)
+        eng = engine((core, head, av, aa), "video", tuple(z.shape), 37, alpha_bar=abar, guidance=3.5, matmul=mode)
         eng.set_prompt(za)
         outs[mode] = eng.run(z, sched)
         if mode == "f16x2":
@@ -287,7 +284,7 @@ def test_f16x2_scales_hold_for_adversarial_weights(dev, full):
     ws, _ = full
     cores = []
     for mode in ("f16x2", "f32"):
-        core, _, _, _ = _full_modules(dev, ws)
+        core, _, _, _ = modules(dev, ws, 8)
         g = torch.Generator().manual_seed(5)
         with torch.no_grad():
             for i, b in enumerate(core.blocks):
@@ -318,8 +315,8 @@ def test_f16x2_engine_follows_weight_updates(dev, full):
     """The scales are cached per parameter version: an in-place weight update (x64 on a norm gain with in_proj / 64, so the
     attention logits keep their conditioning; x32 on fc1 with fc2 / 32) is picked up — a stale scale would overflow fp16."""
     ws, _ = full
-    core, _, _, _ = _full_modules(dev, ws)
-    ref_core, _, _, _ = _full_modules(dev, ws)
+    core, _, _, _ = modules(dev, ws, 8)
+    ref_core, _, _, _ = modules(dev, ws, 8)
     core.matmul, ref_core.matmul = "f16x2", "f32"
     x = torch.randn(16, 421, 512, generator=torch.Generator().manual_seed(8)).to(dev)
     y0 = core(x)
@@ -367,7 +364,6 @@ def test_two_stream_cfg_halves_are_bit_identical(dev, full, mode):
     """split_streams runs the cond / null halves as two kernel chains on two HIP streams: every output element is the same sum in
     the same order, so a step, a trajectory and a replayed graph must equal the single-stream results bit for bit.  (The f16x2
     engine turns the two-stream layout on by itself at >= 6144 rows per half.)"""
-    import multimodal_diffusion_amd as A
     from multimodal_diffusion_amd import schedule_utils as su
     ws, _ = full
     B = 16
@@ -378,9 +374,8 @@ def test_two_stream_cfg_halves_are_bit_identical(dev, full, mode):
     sched = su.make_sampling_schedule(1000, 4)
     outs = {}
     for split in (False, True):
-        core, head, av, aa = _full_modules(dev, ws)
-        eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video", latent_shape=tuple(z.shape),
-                              prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul=mode, split_streams=split)
+        core, head, av, aa = modules(dev, ws, 8)
+        eng = engine((core, head, av, aa), "video", tuple(z.shape), 37, alpha_bar=abar, guidance=3.5, matmul=mode, split_streams=split)
         eng.set_prompt(za)
         outs[split] = (eng.run(z, sched, graph=False), eng.run(z, sched, graph=True))
     assert torch.isfinite(outs[True][0]).all()
@@ -393,9 +388,8 @@ def test_two_stream_cfg_halves_are_bit_identical(dev, full, mode):
     same(outs[False][0], outs[True][0], "two streams vs one, eager")
     same(outs[False][1], outs[True][1], "two streams vs one, graph replay")
     same(outs[True][0], outs[True][1], "two streams: eager vs graph replay")
-    core, head, av, aa = _full_modules(dev, ws)
-    auto = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video", latent_shape=tuple(z.shape),
-                           prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul=mode)
+    core, head, av, aa = modules(dev, ws, 8)
+    auto = engine((core, head, av, aa), "video", tuple(z.shape), 37, alpha_bar=abar, guidance=3.5, matmul=mode)
     assert auto._split_streams == (mode == "f16x2")          # 16 x 421 = 6736 rows per half
 
 
@@ -404,7 +398,6 @@ def test_two_stream_halves_take_the_step_kernel_family(dev, full, mode):
     """in the six-term mode the split kernels engage at 2,048 rows of the stacked 2B x N batch.  At B = 3 (2,526 rows; one CFG
     half alone: 1,263) a forced two-stream step must take the SAME kernels as the one-stream layout — the family is chosen once per step —
     so the two layouts stay bit-identical in that band too (and the step really runs on the split kernels: kernel tags)."""
-    import multimodal_diffusion_amd as A
     from multimodal_diffusion_amd import _lib as L
     ws, _ = full
     B = 3
@@ -415,9 +408,8 @@ def test_two_stream_halves_take_the_step_kernel_family(dev, full, mode):
     tn, tp = torch.tensor([982, 500, 16]).to(dev), torch.tensor([966, 480, -1]).to(dev)
     outs, tags = {}, {}
     for split in (False, True):
-        core, head, av, aa = _full_modules(dev, ws)
-        eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video", latent_shape=tuple(z.shape),
-                              prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul=mode, split_streams=split)
+        core, head, av, aa = modules(dev, ws, 8)
+        eng = engine((core, head, av, aa), "video", tuple(z.shape), 37, alpha_bar=abar, guidance=3.5, matmul=mode, split_streams=split)
         eng.set_prompt(za)
         eng.step(z, tn, tp)
         L.check(L.lib().avd_prof_enable(1))
@@ -439,7 +431,6 @@ def test_f16x2_below_and_at_the_row_threshold(dev, full):
     """Below 6144 rows the f16x2 request keeps the fp32-MFMA kernels (the 256-row tiles would not fill the chip); at the threshold
     (128x128 at B=32: 8512 core rows, exactly 6144 head rows) the split kernels take over — the step workspace is sized for
     whichever path runs, and both agree with the f32 mode."""
-    import multimodal_diffusion_amd as A
     ws, _ = full
     abar = R.alpha_bar_table(R.beta_table(1000))
     for B, hw in ((4, 32), (32, 16)):
@@ -449,9 +440,8 @@ def test_f16x2_below_and_at_the_row_threshold(dev, full):
         tn, tp = torch.full((B,), 500, device=dev), torch.full((B,), 480, device=dev)
         outs = {}
         for mode in ("f32", "f16x2"):
-            core, head, av, aa = _full_modules(dev, ws)
-            eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video", latent_shape=tuple(z.shape),
-                                  prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul=mode)
+            core, head, av, aa = modules(dev, ws, 8)
+            eng = engine((core, head, av, aa), "video", tuple(z.shape), 37, alpha_bar=abar, guidance=3.5, matmul=mode)
             eng.set_prompt(za)
             outs[mode] = eng.step(z, tn, tp)
         assert torch.isfinite(outs["f16x2"]).all()
@@ -463,16 +453,14 @@ def test_f16x2_below_and_at_the_row_threshold(dev, full):
 def test_full_width_step_vs_reference_golden(dev, full, mode):
     """Fixture g17: one CFG step at the bench's full model width, batch 8 (6,736 rows — every matrix-pipe mode engages, the head's
     split path too), computed by the reference's own modules.  Every mode must reproduce the reference's next latents."""
-    import multimodal_diffusion_amd as A
     from conftest import load_golden
     from test_oracle_golden import g17_inputs
     ws, _ = full
     g = load_golden("g17_full_step_c3.npz")
     z_v, z_a = g17_inputs()
     abar = R.alpha_bar_table(R.beta_table(1000))
-    core, head, av, aa = _full_modules(dev, ws)
-    eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video", latent_shape=tuple(z_v.shape),
-                          prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul=mode)
+    core, head, av, aa = modules(dev, ws, 8)
+    eng = engine((core, head, av, aa), "video", tuple(z_v.shape), 37, alpha_bar=abar, guidance=3.5, matmul=mode)
     eng.set_prompt(z_a.to(dev))
     out = eng.step(z_v.to(dev), torch.from_numpy(g["t_now"]).to(dev), torch.from_numpy(g["t_prev"]).to(dev)).cpu()
     e = rel_err(out[:2], g["z_next01"])
@@ -483,9 +471,8 @@ def test_full_width_step_vs_reference_golden(dev, full, mode):
 def test_full_step_v2a_f16x2(dev, full):
     """Video -> audio direction in f16x2: 37 target + 384 prompt tokens at 256x256 (target rows first, the 32-wide audio head stays
     on fp32 MFMA), B=10 -> 8,420 rows; oracle on the first two samples; two streams off (4,210 rows per half)."""
-    import multimodal_diffusion_amd as A
     ws, _ = full
-    core, head, av, aa = _full_modules(dev, ws)
+    core, head, av, aa = modules(dev, ws, 8)
     g = torch.Generator().manual_seed(78)
     B = 10
     z_v = torch.randn(B, 8, 12, 32, 32, generator=g)
@@ -497,8 +484,7 @@ def test_full_step_v2a_f16x2(dev, full):
                              head=ws["head"], n_layers=8, n_heads=8, guidance=3.0)
     outs = {}
     for mode in ("f16x2", "f32"):
-        eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=_full_modules(dev, ws)[0], head=head, tstep_dim=256, target="audio",
-                              latent_shape=tuple(z_a.shape), prompt_tokens=384, alpha_bar=abar, guidance=3.0, matmul=mode)
+        eng = engine((modules(dev, ws, 8)[0], head, av, aa), "audio", tuple(z_a.shape), 384, alpha_bar=abar, guidance=3.0, matmul=mode)
         eng.set_prompt(z_v.to(dev))
         outs[mode] = eng.step(z_a.to(dev), tn.to(dev), tp.to(dev))
         assert not eng._split_streams
@@ -510,9 +496,8 @@ def test_full_step_v2a_f16x2(dev, full):
 def test_full_step_f16x2_512(dev, full):
     """BASELINE C5 geometry (512x512: 1536+37 tokens, ragged 1573 -> 1600 padded keys), B=8 -> 25,168 rows, the f16x2 engine's default
     layout (two streams, 12,584 rows per half); sample 0 against the CPU oracle."""
-    import multimodal_diffusion_amd as A
     ws, _ = full
-    core, head, av, aa = _full_modules(dev, ws)
+    core, head, av, aa = modules(dev, ws, 8)
     B = 8
     g = torch.Generator().manual_seed(512)
     z_v = torch.randn(B, 8, 12, 64, 64, generator=g)
@@ -522,8 +507,7 @@ def test_full_step_f16x2_512(dev, full):
     tp = torch.tensor([966, 480, -1, 979, 680, 280, 48, -1])
     ref = R.denoise_step_a2v(z_v[:1], z_a[:1], tn[:1], tp[:1], abar, adapt_v=ws["adapt_v"], adapt_a=ws["adapt_a"],
                              core=ws["core"], head=ws["head"], n_layers=8, n_heads=8, guidance=3.5)
-    eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video",
-                          latent_shape=tuple(z_v.shape), prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul="f16x2")
+    eng = engine((core, head, av, aa), "video", tuple(z_v.shape), 37, alpha_bar=abar, guidance=3.5, matmul="f16x2")
     assert eng._split_streams
     eng.set_prompt(z_a.to(dev))
     out = eng.step(z_v.to(dev), tn.to(dev), tp.to(dev))
@@ -536,27 +520,16 @@ def test_sample_one_direction_with_f16x2_modules(dev, full):
     """The reference-signature sampler with the core / head switched to "f16x2" on a small clip (B=1: far below 6144 rows, so the
     request must be harmless — the fp32 kernels run) produces the frames of the f32 run to within 1 LSB."""
     import multimodal_diffusion_amd as A
-    from multimodal_diffusion_amd.audio_codec import AudioCodec
     ws, _ = full
-    torch.manual_seed(3)
-    vae = A.VideoVAE.from_config({"latent": {"channels": 8, "t_down": 4, "s_down": 8}}).eval().to(dev)
-    codec = AudioCodec.from_config({"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150},
-                                    "codec": {"hop_samples": 320}}).eval().to(dev)
-    cfg = {"tokenizer": {"width": 512, "video": {"tube": {"t": 2, "h": 4, "w": 4}}, "audio": {"chunk": {"length": 4, "stride": 4}}},
-           "video": {"fps": 16, "size": [32, 32], "latent": {"channels": 8, "t_down": 4, "s_down": 8}},
-           "audio": {"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150}},
-           "data": {"clip_seconds": 0.5},
-           "diffusion": {m: {"steps": 1000, "sampler_steps": 3, "schedule": "cosine", "min_beta": 1e-4, "max_beta": 0.02}
-                         for m in ("video", "audio")},
-           "sampling": {"ddim_eta": 0.0, "guidance_scale": {"video": 2.0, "audio": 2.0}}}
+    vae, codec, cfg = pipeline(dev, seed=3, clip_seconds=0.5, sampler_steps=3, sampling={"ddim_eta": 0.0})
     wav = (0.1 * torch.randn(48000, generator=torch.Generator().manual_seed(5))).numpy()
     frames = {}
     for mode in ("f32", "f16x2"):
-        core, head, av, aa = _full_modules(dev, ws)
-        core.matmul = head.matmul = mode
+        mods = modules(dev, ws, 8)
+        mods[0].matmul = mods[1].matmul = mode
         torch.manual_seed(77)
-        res = A.sample_one_direction(cfg=cfg, vid_vae=vae, aud_codec=codec, adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256,
-                                     device=dev, prompt_modality="audio", prompt_video=None, prompt_audio=wav)
+        res = A.sample_one_direction(cfg=cfg, prompt_modality="audio", prompt_video=None, prompt_audio=wav,
+                                     **components(mods, vae, codec, dev))
         frames[mode] = res["video"].astype(np.int32)
     assert np.abs(frames["f32"] - frames["f16x2"]).max() <= 1
 
@@ -663,7 +636,7 @@ def test_block_stagger_changes_timing_only(dev, full):
     forces it) is a scheduling device: results are bit-identical with it off, automatic and forced large."""
     from multimodal_diffusion_amd import _lib as L
     ws, _ = full
-    core, _, _, _ = _full_modules(dev, ws)
+    core, _, _, _ = modules(dev, ws, 8)
     core.matmul = "f16x2"
     x = torch.randn(64, 421, 512, generator=torch.Generator().manual_seed(21)).to(dev)      # 26,944 rows: two generations of blocks
     outs = []
@@ -677,7 +650,6 @@ def test_fp8_attention_on_f16x2_images(dev, full):
     """BASELINE C5 as named (512x512, "fp8 MFMA attention"), with f16x2 projections: the e4m3 attention reads the f16x2 q|k|v image
     and writes its result as an f16x2 image.  Reduced precision — the error against the fp32 oracle is reported and bounded at 2.2x the
     measured 1.5e-3 of max|z|, and must be of the size the bf16x3 + fp8 combination has."""
-    import multimodal_diffusion_amd as A
     ws, mods = full
     core, head, av, aa = mods
     g = torch.Generator().manual_seed(512)
@@ -691,8 +663,7 @@ def test_fp8_attention_on_f16x2_images(dev, full):
                              head=ws["head"], n_layers=8, n_heads=8, guidance=3.5)
     errs = {}
     for matmul, attn in (("f16x2", "default"), ("f16x2", "fp8"), ("bf16x3", "fp8")):
-        eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video", latent_shape=tuple(z_v.shape),
-                              prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul=matmul, attn=attn)
+        eng = engine((core, head, av, aa), "video", tuple(z_v.shape), 37, alpha_bar=abar, guidance=3.5, matmul=matmul, attn=attn)
         eng.set_prompt(z_a.to(dev))
         out = eng.step(z_v.to(dev), tn.to(dev), tp.to(dev)).cpu()
         assert torch.isfinite(out).all()
@@ -735,7 +706,6 @@ def test_captured_graph_refuses_stale_scales(dev, full):
     """a captured f16x2 step holds the image scales BY VALUE (kernel arguments).  An in-place update that moves max|w|
     across a power of two (here a norm gain x64 with in_proj / 64) leaves every pointer unchanged — the replay must raise instead
     of dividing by the old scales; an update that keeps the scales replays and follows the new weights; capturing again works."""
-    import multimodal_diffusion_amd as A
     from multimodal_diffusion_amd import schedule_utils as su, _lib as L
     ws, _ = full
     B = 4
@@ -744,9 +714,8 @@ def test_captured_graph_refuses_stale_scales(dev, full):
     za = torch.randn(B, 8, 150, generator=g).to(dev)
     abar = R.alpha_bar_table(R.beta_table(1000))
     sched = su.make_sampling_schedule(1000, 6)
-    core, head, av, aa = _full_modules(dev, ws)
-    eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video", latent_shape=tuple(z.shape),
-                          prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul="f16x2")
+    core, head, av, aa = modules(dev, ws, 8)
+    eng = engine((core, head, av, aa), "video", tuple(z.shape), 37, alpha_bar=abar, guidance=3.5, matmul="f16x2")
     eng.set_prompt(za)
     eng.begin(sched)
     a, b = z.clone(), torch.empty_like(z)
@@ -780,8 +749,7 @@ def test_captured_graph_refuses_stale_scales(dev, full):
     a.copy_(z)
     graph2.replay()
     torch.cuda.synchronize()
-    ref_eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video", latent_shape=tuple(z.shape),
-                              prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul="f16x2")
+    ref_eng = engine((core, head, av, aa), "video", tuple(z.shape), 37, alpha_bar=abar, guidance=3.5, matmul="f16x2")
     ref_eng.set_prompt(za)
     ref_eng.begin(sched)
     c, d = z.clone(), torch.empty_like(z)

@@ -3,82 +3,24 @@ functional ops (bit for bit, every solver state, rows / gather / audio forms), t
 two-branch one, the cond-only step against the oracle's conditional prediction, trajectories under an interval against the oracle
 stepped at guidance g inside and 1.0 outside, graph replay against eager launches, invariances, the entry points and misuse."""
 import ctypes as C
+from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
 import _interval_ref as IR
+from _kit import (ABAR, Recorder, case, components, dev, engine, full, model, pipeline, soft_mask,  # noqa: F401  (dev / model / full are fixtures)
+                  ts)
 from _tune import cfg_rows, tune, tuned  # noqa: F401  (cfg_rows is a fixture)
 from conftest import rel_err
 from oracle import ref_cpu as R
 
 pytestmark = pytest.mark.gpu
-ABAR = R.alpha_bar_table(R.beta_table(1000))
 TOL = 1e-4                      # the project's one-step tolerance (test_gpu_parity.TOL)
 GS = 3.0
 GSEED, NSEED = 77, 5
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-def _modules(dev, ws, n_layers):
-    import multimodal_diffusion_amd as A
-    core = A.MMDiT(d_model=512, n_layers=n_layers, n_heads=8, mlp_ratio=4.0).eval()
-    core.load_state_dict(ws["core"], strict=True)
-    head = A.MultiModalNoiseHead({"video": 512, "audio": 512}, {"video": 256, "audio": 32}, hidden_dim=512).eval()
-    head.load_state_dict(ws["head"], strict=True)
-    av, aa = A.LinearAdapter(256, 256), A.LinearAdapter(32, 256)
-    av.load_state_dict(ws["adapt_v"])
-    aa.load_state_dict(ws["adapt_a"])
-    return tuple(m.to(dev) for m in (core, head, av, aa))
-
-
-@pytest.fixture(scope="module")
-def model(dev):
-    ws = R.synth_weights(seed=0, n_layers=2)
-    return ws, _modules(dev, ws, 2)
-
-
-@pytest.fixture(scope="module")
-def full(dev):
-    ws = R.synth_weights(seed=0)
-    return ws, _modules(dev, ws, 8)
-
-
-def _engine(model, target, shape, n_prompt, guidance=GS, **kw):
-    import multimodal_diffusion_amd as A
-    _, (core, head, av, aa) = model
-    return A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target=target, latent_shape=shape,
-                           prompt_tokens=n_prompt, alpha_bar=ABAR, guidance=guidance, **kw)
-
-
-def _case(dev, target, B=2, seed=0, W=32):
-    g = torch.Generator().manual_seed(seed)
-    if target == "video":
-        z = torch.randn(B, 8, 4, 16, W, generator=g)
-        zp, npr = torch.randn(B, 8, 40, generator=g), 10
-    else:
-        z = torch.randn(B, 8, 40, generator=g)
-        zp, npr = torch.randn(B, 8, 4, 8, 8, generator=g), 8
-    known = torch.randn(z.shape, generator=g)
-    return z.to(dev), zp.to(dev), npr, known.to(dev)
-
-
-def _soft_mask(shape, seed=3):
-    g = torch.Generator().manual_seed(seed)
-    m = torch.rand(shape, generator=g)
-    m[m < 0.35] = 0.0
-    m[m > 0.7] = 1.0
-    return m
-
-
-def _t(v, dev):
-    return torch.tensor(v, dtype=torch.long, device=dev)
+_engine = partial(engine, guidance=GS)        # engine(mods, target, shape, n_prompt, **kw) at this file's guidance
 
 
 # ------------------------------------------------------------------------------------------------- 1. kernels = composed ops
@@ -92,7 +34,7 @@ def _fused(dev, target, eps, z, tn, tp, state, guide, h):
     eta = 0.7 if state in ("noise", "seeded") else 0.0
     noise = Fn.gaussian_noise(NSEED, 4, tn, tuple(z.shape)) if state == "noise" else None
     key = Fn.noise_key(NSEED, 4) if state == "seeded" else None
-    tl = {"dpm1": _t([-1] * B, dev), "dpm2": _t([999, 700, 850][:B], dev)}.get(state)
+    tl = {"dpm1": ts([-1] * B, dev), "dpm2": ts([999, 700, 850][:B], dev)}.get(state)
     hist = h.clone() if tl is not None else None
     out = torch.empty_like(z)
     ab = ABAR.to(dev)
@@ -113,7 +55,7 @@ def _composed(dev, target, eps, z, tn, tp, state, known, mask, h):
     hist = None
     if state in ("dpm1", "dpm2"):
         hist = h.clone()
-        tl = _t([-1] * B, dev) if state == "dpm1" else _t([999, 700, 850][:B], dev)
+        tl = ts([-1] * B, dev) if state == "dpm1" else ts([999, 700, 850][:B], dev)
         out = Fn.dpmpp_2m_step(z, lat, hist, tl, tn, tp, ABAR)
     elif state == "plain":
         out = Fn.ddim_step(z, tn, tp, lat, ABAR)
@@ -143,8 +85,8 @@ def test_kernels_equal_composed_ops(dev, cfg_rows, target, lat, state, guided):
     else:
         eps = torch.randn(B, (lat[1] - 4) // 4 + 1, lat[0] * 4, generator=g).to(dev)
     known, h = torch.randn(z.shape, generator=g).to(dev), torch.randn(z.shape, generator=g).to(dev)
-    mask = _soft_mask(tuple(z.shape[1:])).to(dev)
-    tn, tp = _t([981, 402, 40], dev), _t([961, 382, -1], dev)
+    mask = soft_mask(tuple(z.shape[1:])).to(dev)
+    tn, tp = ts([981, 402, 40], dev), ts([961, 382, -1], dev)
     guide = Fn.latent_guide_desc(known, mask, GSEED, 4) if guided else None
     ref, href = _composed(dev, target, eps, z, tn, tp, state, known if guided else None, mask, h)
     outs = []
@@ -167,7 +109,7 @@ def test_front_end_equals_cond_half(dev, model, target, temb_mode):
     import multimodal_diffusion_amd as A
     from multimodal_diffusion_amd import _lib as L
     _, (core, head, av, aa) = model
-    z, zp, npr, _ = _case(dev, target, B=3)
+    z, zp, npr, _ = case(dev, target, B=3)
     adapters = dict(adapt_v=av, adapt_a=aa)
     if temb_mode == "add":      # the trainer's embedding needs d-wide adapters
         torch.manual_seed(1)
@@ -176,7 +118,7 @@ def test_front_end_equals_cond_half(dev, model, target, temb_mode):
                           alpha_bar=ABAR, guidance=GS, temb_mode=temb_mode, **adapters)
     Xp = eng.set_prompt(zp)
     e, B, N, d = eng.embed, 3, eng.N, eng.d
-    tn = _t([981, 402, 0], dev)
+    tn = ts([981, 402, 0], dev)
     nws = L.lib().avd_embed_workspace_floats(C.byref(e))
     tok = torch.empty(nws, device=dev)
     X2 = torch.full((2 * B, N, d), float("nan"), device=dev)
@@ -193,7 +135,7 @@ def test_front_end_equals_cond_half(dev, model, target, temb_mode):
     D_ = eng.head.output_dims[target]
     eps_b = ((2 * B * e.Nt * D_ * 4 + 255) // 256) * 256
     ss_b = ((2 * B * N * 4 + 255) // 256) * 256
-    out = eng.step(z, tn, _t([961, 382, -1], dev))
+    out = eng.step(z, tn, ts([961, 382, -1], dev))
     end = eng.workspace.numel() - eps_b
     ss2 = eng.workspace[end - ss_b:end][: 2 * B * N * 4].view(torch.float32).clone()
     if temb_mode == "concat":
@@ -226,11 +168,11 @@ def _composed_from_tokens(dev, eng, target, eps, z, tn, tp):
 def _check_cond_step(dev, model, n_layers, target, mode, z, zp, npr):
     ws = model[0]
     B = z.shape[0]
-    tn, tp = _t([982, 500, 16, 999][:B], dev), _t([966, 480, -1, 979][:B], dev)
+    tn, tp = ts([982, 500, 16, 999][:B], dev), ts([966, 480, -1, 979][:B], dev)
     with tuned("s3_min_rows"):
         if mode != "f32":
             tune("s3_min_rows", 0)             # let the split-operand kernels engage at these row counts
-        eng = _engine(model, target, tuple(z.shape), npr, matmul=mode)
+        eng = _engine(model[1], target, tuple(z.shape), npr, matmul=mode)
         eng.set_prompt(zp)
         out = eng.step(z, tn, tp, cond_only=True)
         eps = eng.eps_tokens()
@@ -243,7 +185,7 @@ def _check_cond_step(dev, model, n_layers, target, mode, z, zp, npr):
         # without the flag an engine that has an interval steps exactly as one that has none
         cfg = eng.step(z, tn, tp).clone()
         assert tuple(eng.eps_tokens().shape)[0] == 2 * B
-        eng2 = _engine(model, target, tuple(z.shape), npr, matmul=mode, guidance_interval=(300, 700))
+        eng2 = _engine(model[1], target, tuple(z.shape), npr, matmul=mode, guidance_interval=(300, 700))
         eng2.set_prompt(zp)
         assert torch.equal(eng2.step(z, tn, tp), cfg)
         assert torch.equal(eng2.step(z, tn, tp, cond_only=True), out)
@@ -253,7 +195,7 @@ def _check_cond_step(dev, model, n_layers, target, mode, z, zp, npr):
 @pytest.mark.parametrize("mode", ["f32", "bf16x3", "f16x2"])
 @pytest.mark.parametrize("target", ["video", "audio"])
 def test_cond_step_small(dev, model, target, mode):
-    z, zp, npr, _ = _case(dev, target, B=2)
+    z, zp, npr, _ = case(dev, target, B=2)
     _check_cond_step(dev, model, 2, target, mode, z, zp, npr)
 
 
@@ -303,7 +245,7 @@ def test_trajectory_vs_oracle(dev, model, target, kind, eta):
     ws, _ = model
     n_steps = 8
     sched = R.sampling_schedule(1000, n_steps)                 # 999, 874, 749, 624, 499, 374, 249, 124, -1
-    z, zp, npr, _ = _case(dev, target, B=2, seed=2, W=16)
+    z, zp, npr, _ = case(dev, target, B=2, seed=2, W=16)
     kw = dict(matmul="f32")
     if kind == "seeded":
         kw.update(eta=eta, noise_seed=NSEED, sample_offset=3)
@@ -311,12 +253,12 @@ def test_trajectory_vs_oracle(dev, model, target, kind, eta):
         kw.update(solver="dpmpp_2m")
     noise = (lambda tn: Fn.gaussian_noise(NSEED, 3, tn.to(dev), tuple(z.shape)).cpu()) if kind == "seeded" else None
     solver = "dpmpp_2m" if kind == "dpmpp_2m" else "ddim"
-    plain = _engine(model, target, tuple(z.shape), npr, **kw)
+    plain = _engine(model[1], target, tuple(z.shape), npr, **kw)
     plain.set_prompt(zp)
     base = plain.run(z, sched)
     outs = {}
     for name, iv in (("middle", (300, 700)), ("all", (0, 999)), ("empty", (1000, 2000))):
-        eng = _engine(model, target, tuple(z.shape), npr, guidance_interval=iv, **kw)
+        eng = _engine(model[1], target, tuple(z.shape), npr, guidance_interval=iv, **kw)
         eng.set_prompt(zp)
         out = eng.run(z, sched)
         outs[name] = out
@@ -337,18 +279,18 @@ def test_trajectory_vs_oracle(dev, model, target, kind, eta):
 def test_graph_equals_eager(dev, model, solver):
     """segments of lengths 1, 2, an odd and an even number >= 3; plain, with a latent guide, with rescale active on the CFG steps"""
     from multimodal_diffusion_amd import schedule_utils as su
-    z, zp, npr, known = _case(dev, "video")
+    z, zp, npr, known = case(dev, "video")
     if solver == "ddim":        # one run with four segments (DDIM takes any schedule)
         runs = [(torch.tensor([990, 900, 880, 400, 390, 380, 370, 360, 700, 650, 600, 550, -1]), (500, 950), [1, 2, 5, 4])]
     else:                       # a decreasing schedule has at most three segments: two intervals
         sched = torch.tensor([990, 900, 880, 840, 830, 820, 810, 800, -1])
         runs = [(sched, (860, 950), [1, 2, 5]), (sched, (0, 835), [4, 4])]
-    eng = _engine(model, "video", tuple(z.shape), npr, solver=solver)
+    eng = _engine(model[1], "video", tuple(z.shape), npr, solver=solver)
     eng.set_prompt(zp)
     last = None
     for setup in ("plain", "guide", "rescale"):
         if setup == "guide":
-            eng.set_known(known, _soft_mask(tuple(z.shape[1:])), guide_seed=GSEED)
+            eng.set_known(known, soft_mask(tuple(z.shape[1:])), guide_seed=GSEED)
         if setup == "rescale":
             eng.set_cfg(rescale=0.7)                            # acts on the CFG steps only
         for sched, iv, lens in runs:
@@ -364,9 +306,9 @@ def test_graph_equals_eager(dev, model, solver):
     # back to no interval: today's run, bit for bit
     sched = runs[0][0]
     eng.set_guidance_interval(None)
-    ref = _engine(model, "video", tuple(z.shape), npr, solver=solver, guidance_rescale=0.7)
+    ref = _engine(model[1], "video", tuple(z.shape), npr, solver=solver, guidance_rescale=0.7)
     ref.set_prompt(zp)
-    ref.set_known(known, _soft_mask(tuple(z.shape[1:])), guide_seed=GSEED)
+    ref.set_known(known, soft_mask(tuple(z.shape[1:])), guide_seed=GSEED)
     assert torch.equal(eng.run(z, sched, graph=True), ref.run(z, sched, graph=True))
 
 
@@ -374,10 +316,10 @@ def test_graph_equals_eager(dev, model, solver):
 @pytest.mark.parametrize("kw", [{}, dict(eta=0.7, noise_seed=NSEED), dict(solver="dpmpp_2m")])
 @pytest.mark.parametrize("target", ["video", "audio"])
 def test_zero_mask_guide_is_no_guide(dev, model, target, kw):
-    z, zp, npr, known = _case(dev, target)
-    eng = _engine(model, target, tuple(z.shape), npr, **kw)
+    z, zp, npr, known = case(dev, target)
+    eng = _engine(model[1], target, tuple(z.shape), npr, **kw)
     eng.set_prompt(zp)
-    tn, tp = _t([981, 402], dev), _t([961, 382], dev)
+    tn, tp = ts([981, 402], dev), ts([961, 382], dev)
     base = eng.step(z, tn, tp, cond_only=True).clone()
     eng.set_known(known, torch.zeros(tuple(z.shape[1:])), guide_seed=GSEED)
     assert torch.equal(eng.step(z, tn, tp, cond_only=True), base)
@@ -388,12 +330,12 @@ def test_zero_mask_guide_is_no_guide(dev, model, target, kw):
 
 def test_batch_offset_invariance(dev, model):
     """as test_gpu_latent_guide / test_gpu_seeded_noise: a batch of 4 is two batches of 2 at sample_offset 0 and 2"""
-    z, zp, npr, known = _case(dev, "video", B=4)
-    m = _soft_mask(tuple(z.shape), seed=8).to(dev)
+    z, zp, npr, known = case(dev, "video", B=4)
+    m = soft_mask(tuple(z.shape), seed=8).to(dev)
     sched = R.sampling_schedule(1000, 4)
 
     def run(sl, off):
-        eng = _engine(model, "video", (sl.stop - sl.start,) + tuple(z.shape[1:]), npr, matmul="f32", eta=0.5, noise_seed=1,
+        eng = _engine(model[1], "video", (sl.stop - sl.start,) + tuple(z.shape[1:]), npr, matmul="f32", eta=0.5, noise_seed=1,
                       sample_offset=off, guidance_interval=(400, 800))
         eng.set_prompt(zp[sl].contiguous())
         eng.set_known(known[sl].contiguous(), m[sl].contiguous(), guide_seed=GSEED)
@@ -407,9 +349,9 @@ def test_batch_offset_invariance(dev, model):
     assert torch.equal(o4[keep], known[keep]) and torch.equal(o2[keep], known[keep])
     # the noise of a trajectory does not depend on the interval: a cond-only step draws what the CFG step would
     from multimodal_diffusion_amd import functional as Fn
-    eng = _engine(model, "video", tuple(z.shape), npr, eta=0.5, noise_seed=1, sample_offset=6)
+    eng = _engine(model[1], "video", tuple(z.shape), npr, eta=0.5, noise_seed=1, sample_offset=6)
     eng.set_prompt(zp)
-    tn, tp = _t([981, 402, 40, 700], dev), _t([961, 382, -1, 650], dev)
+    tn, tp = ts([981, 402, 40, 700], dev), ts([961, 382, -1, 650], dev)
     out = eng.step(z, tn, tp, cond_only=True)
     lat = Fn.tube_unpatch(eng.eps_tokens(), *z.shape[1:], 2, 4, 4)
     assert torch.equal(out, Fn.ddim_step(z, tn, tp, lat, ABAR, 0.5, Fn.gaussian_noise(1, 6, tn, tuple(z.shape))))
@@ -417,47 +359,24 @@ def test_batch_offset_invariance(dev, model):
 
 @pytest.mark.parametrize("mode", ["f32", "f16x2"])
 def test_split_streams_is_one_chain(dev, model, mode):
-    z, zp, npr, _ = _case(dev, "video")
-    tn, tp = _t([981, 402], dev), _t([961, 382], dev)
+    z, zp, npr, _ = case(dev, "video")
+    tn, tp = ts([981, 402], dev), ts([961, 382], dev)
     outs = []
     for split in (False, True):
-        eng = _engine(model, "video", tuple(z.shape), npr, matmul=mode, split_streams=split)
+        eng = _engine(model[1], "video", tuple(z.shape), npr, matmul=mode, split_streams=split)
         eng.set_prompt(zp)
         outs.append((eng.step(z, tn, tp, cond_only=True).clone(), eng.eps_tokens()))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
 
 
 # ------------------------------------------------------------------------------------------------- 7. entry points, misuse
-class _Recorder:
-    def __init__(self, inner):
-        self.inner, self.last = inner, None
-
-    def encode(self, x):
-        return self.inner.encode(x)
-
-    def decode(self, z):
-        self.last = z.clone()
-        return self.inner.decode(z)
-
-
 @pytest.fixture(scope="module")
 def a2v_setup(dev, model):
-    import multimodal_diffusion_amd as A
-    _, (core, head, av, aa) = model
-    torch.manual_seed(8)
-    vae = A.VideoVAE.from_config({"latent": {"channels": 8, "t_down": 4, "s_down": 8}}).eval().to(dev)
-    codec = A.AudioCodec.from_config({"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150},
-                                      "codec": {"hop_samples": 320}}).eval().to(dev)
-    cfg = {"tokenizer": {"width": 512, "video": {"tube": {"t": 2, "h": 4, "w": 4}}, "audio": {"chunk": {"length": 4, "stride": 4}}},
-           "video": {"fps": 16, "size": [32, 32], "latent": {"channels": 8, "t_down": 4, "s_down": 8}},
-           "audio": {"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150}},
-           "data": {"clip_seconds": 1.0}, "streaming": {"window_seconds": 1.0, "hop_seconds": 0.5, "crossfade_seconds": 0.25},
-           "diffusion": {m: {"steps": 1000, "sampler_steps": 6, "schedule": "cosine", "min_beta": 1e-4, "max_beta": 0.02}
-                         for m in ("video", "audio")},
-           "sampling": {"guidance_scale": {"video": 2.0, "audio": 2.0}, "guidance_interval": {"video": [300, 700]}}}
+    vae, codec, cfg = pipeline(dev, seed=8, clip_seconds=1.0, sampler_steps=6,
+                               streaming={"window_seconds": 1.0, "hop_seconds": 0.5, "crossfade_seconds": 0.25},
+                               sampling={"guidance_interval": {"video": [300, 700]}})
     wav = (0.1 * torch.randn(16000, generator=torch.Generator().manual_seed(9))).numpy()
-    kw = dict(cfg=cfg, vid_vae=_Recorder(vae), aud_codec=codec, adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, device=dev,
-              prompt_modality="audio", prompt_video=None, prompt_audio=wav)
+    kw = dict(components(model[1], Recorder(vae), codec, dev), cfg=cfg, prompt_modality="audio", prompt_video=None, prompt_audio=wav)
     return kw, codec
 
 
@@ -474,7 +393,7 @@ def test_entry_points_follow_the_config_key(dev, model, a2v_setup):
     with torch.no_grad():
         z_p = codec.encode(torch.from_numpy(kw["prompt_audio"]).to(dev).view(1, 1, -1)).float()
     sched = A.schedule_utils.make_sampling_schedule(1000, 6)
-    eng = _engine(model, "video", lat, (z_p.shape[-1] - 4) // 4 + 1, guidance=2.0, guidance_interval=(300, 700))
+    eng = _engine(model[1], "video", lat, (z_p.shape[-1] - 4) // 4 + 1, guidance=2.0, guidance_interval=(300, 700))
     eng.set_prompt(z_p)
     hand = eng.run(noise.to(dev), sched)
     assert torch.equal(got, hand)
@@ -496,15 +415,15 @@ def test_entry_points_follow_the_config_key(dev, model, a2v_setup):
 def test_misuse(dev, model):
     import multimodal_diffusion_amd as A
     from multimodal_diffusion_amd import _lib as L, functional as Fn
-    z, zp, npr, known = _case(dev, "video")
+    z, zp, npr, known = case(dev, "video")
     with pytest.raises(ValueError, match="guidance_interval"):
-        _engine(model, "video", tuple(z.shape), npr, guidance_interval=(700, 300))
-    eng = _engine(model, "video", tuple(z.shape), npr, solver="dpmpp_2m")
+        _engine(model[1], "video", tuple(z.shape), npr, guidance_interval=(700, 300))
+    eng = _engine(model[1], "video", tuple(z.shape), npr, solver="dpmpp_2m")
     eng.set_prompt(zp)
     with pytest.raises(ValueError, match="guidance_interval"):
         eng.set_guidance_interval((-3, 10))
     assert eng.guidance_interval is None
-    tn, tp = _t([900, 900], dev), _t([800, 800], dev)
+    tn, tp = ts([900, 900], dev), ts([800, 800], dev)
     out = torch.full_like(z, float("nan"))
 
     def cond(e, *, g=None, key=None, tl=None, h=None, noise=None, z_=None, out_=None):
@@ -523,7 +442,7 @@ def test_misuse(dev, model):
     with pytest.raises(L.AvdError, match="x0_hist"):
         eng.step(z, tn, tp, out=eng.x0_hist, cond_only=True)
     # eta > 0: no noise and no key; a guide without a key; noise together with a key or a guide
-    ddim = _engine(model, "video", tuple(z.shape), npr, eta=0.5)
+    ddim = _engine(model[1], "video", tuple(z.shape), npr, eta=0.5)
     ddim.set_prompt(zp)
     nz, key = torch.randn_like(z), Fn.noise_key(3, 0)
     gd = Fn.latent_guide_desc(known, None, GSEED, 0)

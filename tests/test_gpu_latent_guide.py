@@ -3,72 +3,21 @@ guided step against the unguided step followed by the elementwise blend (bit for
 select cases, graph replay against eager launches, guided trajectories against the CPU oracle, batch / sample_offset invariance,
 sample_one_direction's init / strength / mask arguments, and misuse."""
 import ctypes as C
+from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
 import _guide_ref as G
+from _kit import ABAR, Recorder, case, components, dev, engine, model, pipeline, soft_mask, ts  # noqa: F401  (dev / model are fixtures)
 from _tune import cfg_rows  # noqa: F401  (fixture)
 from oracle import ref_cpu as R
 
 pytestmark = pytest.mark.gpu
-ABAR = R.alpha_bar_table(R.beta_table(1000))
 GS = 3.0
 GSEED = 77
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def model(dev):
-    import multimodal_diffusion_amd as A
-    ws = R.synth_weights(seed=0, n_layers=2)
-    core = A.MMDiT(d_model=512, n_layers=2, n_heads=8, mlp_ratio=4.0).eval()
-    core.load_state_dict(ws["core"], strict=True)
-    head = A.MultiModalNoiseHead({"video": 512, "audio": 512}, {"video": 256, "audio": 32}, hidden_dim=512).eval()
-    head.load_state_dict(ws["head"], strict=True)
-    av, aa = A.LinearAdapter(256, 256), A.LinearAdapter(32, 256)
-    av.load_state_dict(ws["adapt_v"])
-    aa.load_state_dict(ws["adapt_a"])
-    return ws, tuple(m.to(dev) for m in (core, head, av, aa))
-
-
-def _engine(model, target, shape, n_prompt, **kw):
-    import multimodal_diffusion_amd as A
-    _, (core, head, av, aa) = model
-    return A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target=target, latent_shape=shape,
-                           prompt_tokens=n_prompt, alpha_bar=ABAR, guidance=GS, **kw)
-
-
-def _case(dev, target, B=2, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    if target == "video":
-        z = torch.randn(B, 8, 4, 16, 32, generator=g)
-        zp, npr = torch.randn(B, 8, 40, generator=g), 10
-    else:
-        z = torch.randn(B, 8, 40, generator=g)
-        zp, npr = torch.randn(B, 8, 4, 8, 8, generator=g), 8
-    known = torch.randn(z.shape, generator=g)
-    return z.to(dev), zp.to(dev), npr, known.to(dev)
-
-
-def _soft_mask(shape, seed=3):
-    """per-sample mask with exact 0 and 1 entries and fractional ones"""
-    g = torch.Generator().manual_seed(seed)
-    m = torch.rand(shape, generator=g)
-    m[m < 0.35] = 0.0
-    m[m > 0.7] = 1.0
-    assert (m == 0).any() and (m == 1).any() and ((m > 0) & (m < 1)).any()
-    return m
-
-
-def _t(v, dev):
-    return torch.tensor(v, dtype=torch.long, device=dev)
+_engine = partial(engine, guidance=GS)        # engine(mods, target, shape, n_prompt, **kw) at this file's guidance
 
 
 # ------------------------------------------------------------------------------------------------- elementwise = numpy mirror
@@ -77,20 +26,20 @@ def test_elementwise_matches_reference(dev):
     B, per = 6, 65_539                                        # not a multiple of 4
     g = torch.Generator().manual_seed(1)
     known, z = torch.randn(B, per, generator=g), torch.randn(B, per, generator=g)
-    m = _soft_mask((per,))
+    m = soft_mask((per,))
     tau = [999, 500, 17, 0, -1, 1500]
-    got = Fn.latent_guide(known.to(dev), _t(tau, dev), ABAR, z=z.to(dev), mask=m.to(dev), seed=GSEED, sample_offset=9).cpu()
+    got = Fn.latent_guide(known.to(dev), ts(tau, dev), ABAR, z=z.to(dev), mask=m.to(dev), seed=GSEED, sample_offset=9).cpu()
     q = G.q_f64(known.numpy(), tau, ABAR.numpy(), GSEED, 9)
     ref = G.blend_f64(m.numpy(), q, z.numpy())
     assert np.abs(got.double().numpy() - ref).max() < 2e-5
     keep, free = (m == 1).expand(B, per), (m == 0).expand(B, per)
     assert torch.equal(got[free], z[free])
     assert torch.equal(got[4][keep[4]], known[4][keep[4]])    # tau < 0: known bit for bit
-    pure = Fn.latent_guide(known.to(dev), _t(tau, dev), ABAR, seed=GSEED, sample_offset=9).cpu()
+    pure = Fn.latent_guide(known.to(dev), ts(tau, dev), ABAR, seed=GSEED, sample_offset=9).cpu()
     assert np.abs(pure.double().numpy() - q).max() < 2e-5
     assert torch.equal(pure[4], known[4])
-    per_sample = _soft_mask((B, per), seed=4)
-    got2 = Fn.latent_guide(known.to(dev), _t(tau, dev), ABAR, z=z.to(dev), mask=per_sample.to(dev), seed=GSEED, sample_offset=9).cpu()
+    per_sample = soft_mask((B, per), seed=4)
+    got2 = Fn.latent_guide(known.to(dev), ts(tau, dev), ABAR, z=z.to(dev), mask=per_sample.to(dev), seed=GSEED, sample_offset=9).cpu()
     assert np.abs(got2.double().numpy() - G.blend_f64(per_sample.numpy(), q, z.numpy())).max() < 2e-5
 
 
@@ -105,14 +54,14 @@ VARIANTS = [("video", 1, {}), ("video", 0, {}), ("audio", 1, {}),
 def test_fused_equals_composed(dev, model, cfg_rows, target, rows, kw):
     from multimodal_diffusion_amd import functional as Fn
     cfg_rows(rows)
-    z, zp, npr, known = _case(dev, target)
-    eng = _engine(model, target, tuple(z.shape), npr, **kw)
+    z, zp, npr, known = case(dev, target)
+    eng = _engine(model[1], target, tuple(z.shape), npr, **kw)
     eng.set_prompt(zp)
     dpm = kw.get("solver") == "dpmpp_2m"
     h0 = torch.randn(z.shape, generator=torch.Generator().manual_seed(7)).to(dev)
-    tn, tp = _t([981, 402], dev), _t([961, 382], dev)
-    tls = [None, _t([999, 700], dev)] if dpm else [None]       # DPM: first and second order
-    soft = _soft_mask(tuple(z.shape[1:])).to(dev)
+    tn, tp = ts([981, 402], dev), ts([961, 382], dev)
+    tls = [None, ts([999, 700], dev)] if dpm else [None]       # DPM: first and second order
+    soft = soft_mask(tuple(z.shape[1:])).to(dev)
     for tl in tls:
         def plain():
             eng.clear_known()
@@ -144,8 +93,8 @@ def test_fused_equals_composed(dev, model, cfg_rows, target, rows, kw):
 def test_full_run_keeps_known_frames(dev, model):
     import multimodal_diffusion_amd as A
     for target, kw in (("video", {}), ("video", dict(solver="dpmpp_2m")), ("audio", dict(eta=0.5, noise_seed=3))):
-        z, zp, npr, known = _case(dev, target)
-        eng = _engine(model, target, tuple(z.shape), npr, **kw)
+        z, zp, npr, known = case(dev, target)
+        eng = _engine(model[1], target, tuple(z.shape), npr, **kw)
         eng.set_prompt(zp)
         m = A.frame_mask(tuple(z.shape[1:]), 0, 2)
         eng.set_known(known, m, guide_seed=GSEED)
@@ -162,17 +111,17 @@ def test_full_run_keeps_known_frames(dev, model):
 @pytest.mark.parametrize("solver", ["ddim", "dpmpp_2m"])
 @pytest.mark.parametrize("n_steps", [5, 6])
 def test_graph_equals_eager(dev, model, solver, n_steps):
-    z, zp, npr, known = _case(dev, "video")
+    z, zp, npr, known = case(dev, "video")
     sched = R.sampling_schedule(1000, n_steps)
-    eng = _engine(model, "video", tuple(z.shape), npr, solver=solver)
+    eng = _engine(model[1], "video", tuple(z.shape), npr, solver=solver)
     eng.set_prompt(zp)
-    eng.set_known(known, _soft_mask(tuple(z.shape[1:])), guide_seed=GSEED)
+    eng.set_known(known, soft_mask(tuple(z.shape[1:])), guide_seed=GSEED)
     zg = eng.run(z, sched, graph=True)
     ze = eng.run(z, sched, graph=False)
     assert torch.equal(zg, ze)
     # new values behind the same buffers: no reallocation, the graph path follows them
     gen = eng._generation
-    eng.set_known(known.flip(0), _soft_mask(tuple(z.shape[1:]), seed=5), guide_seed=GSEED)
+    eng.set_known(known.flip(0), soft_mask(tuple(z.shape[1:]), seed=5), guide_seed=GSEED)
     assert eng._generation == gen
     assert torch.equal(eng.run(z, sched, graph=True), eng.run(z, sched, graph=False))
     eng.clear_known()
@@ -192,8 +141,8 @@ def test_trajectory_vs_oracle(dev, model, target):
     else:
         z, zp, npr = torch.randn(2, 8, 40, generator=g), torch.randn(2, 8, 4, 8, 8, generator=g), 8
     known = torch.randn(z.shape, generator=g)
-    m = _soft_mask(tuple(z.shape[1:]), seed=6)
-    eng = _engine(model, target, tuple(z.shape), npr, matmul="f32")
+    m = soft_mask(tuple(z.shape[1:]), seed=6)
+    eng = _engine(model[1], target, tuple(z.shape), npr, matmul="f32")
     eng.set_prompt(zp.to(dev))
     eng.set_known(known.to(dev), m, guide_seed=GSEED)
     out = eng.run(z.to(dev), sched).cpu().double()
@@ -212,10 +161,10 @@ def test_trajectory_vs_oracle(dev, model, target):
 # ------------------------------------------------------------------------------------------------- batch / offset invariance
 def test_batch_offset_invariance(dev, model):
     from multimodal_diffusion_amd import functional as Fn
-    z, zp, npr, known = _case(dev, "video", B=4)
-    m = _soft_mask(tuple(z.shape), seed=8).to(dev)             # one mask per sample
+    z, zp, npr, known = case(dev, "video", B=4)
+    m = soft_mask(tuple(z.shape), seed=8).to(dev)             # one mask per sample
     sched = R.sampling_schedule(1000, 4)
-    tau = _t([961, 382, 17, -1], dev)
+    tau = ts([961, 382, 17, -1], dev)
     # the guide itself: a batch of 4 is two batches of 2 at sample_offset 0 and 2, bit for bit
     whole = Fn.latent_guide(known, tau, ABAR, z=z, mask=m, seed=GSEED)
     halves = torch.cat([Fn.latent_guide(known[s], tau[s], ABAR, z=z[s], mask=m[s], seed=GSEED, sample_offset=o)
@@ -223,7 +172,7 @@ def test_batch_offset_invariance(dev, model):
     assert torch.equal(whole, halves)
 
     def run(sl, off):
-        eng = _engine(model, "video", (sl.stop - sl.start,) + tuple(z.shape[1:]), npr, matmul="f32", noise_seed=1, sample_offset=off)
+        eng = _engine(model[1], "video", (sl.stop - sl.start,) + tuple(z.shape[1:]), npr, matmul="f32", noise_seed=1, sample_offset=off)
         eng.set_prompt(zp[sl].contiguous())
         eng.set_known(known[sl].contiguous(), m[sl].contiguous(), guide_seed=GSEED)
         z0, sk = eng.start_latent(z[sl].contiguous(), sched, 0.75)
@@ -239,39 +188,12 @@ def test_batch_offset_invariance(dev, model):
 
 
 # ------------------------------------------------------------------------------------------------- sample_one_direction
-class _Recorder:
-    """wraps a VAE / codec and keeps the latent it last decoded"""
-
-    def __init__(self, inner):
-        self.inner, self.last = inner, None
-
-    def encode(self, x):
-        return self.inner.encode(x)
-
-    def decode(self, z):
-        self.last = z.clone()
-        return self.inner.decode(z)
-
-
 @pytest.fixture(scope="module")
 def a2v_setup(dev, model):
-    import multimodal_diffusion_amd as A
-    _, (core, head, av, aa) = model
-    torch.manual_seed(8)
-    vae = A.VideoVAE.from_config({"latent": {"channels": 8, "t_down": 4, "s_down": 8}}).eval().to(dev)
-    codec = A.AudioCodec.from_config({"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150},
-                                      "codec": {"hop_samples": 320}}).eval().to(dev)
-    cfg = {"tokenizer": {"width": 512, "video": {"tube": {"t": 2, "h": 4, "w": 4}}, "audio": {"chunk": {"length": 4, "stride": 4}}},
-           "video": {"fps": 16, "size": [32, 32], "latent": {"channels": 8, "t_down": 4, "s_down": 8}},
-           "audio": {"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150}},
-           "data": {"clip_seconds": 1.0},
-           "diffusion": {m: {"steps": 1000, "sampler_steps": 5, "schedule": "cosine", "min_beta": 1e-4, "max_beta": 0.02}
-                         for m in ("video", "audio")},
-           "sampling": {"guidance_scale": {"video": 2.0, "audio": 2.0}}}
+    vae, codec, cfg = pipeline(dev, seed=8, clip_seconds=1.0, sampler_steps=5)
     wav = (0.1 * torch.randn(16000, generator=torch.Generator().manual_seed(9))).numpy()
     clip = np.random.default_rng(3).integers(0, 256, size=(16, 32, 32, 3), dtype=np.uint8)
-    kw = dict(cfg=cfg, vid_vae=_Recorder(vae), aud_codec=codec, adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, device=dev,
-              prompt_modality="audio", prompt_video=None, prompt_audio=wav)
+    kw = dict(components(model[1], Recorder(vae), codec, dev), cfg=cfg, prompt_modality="audio", prompt_video=None, prompt_audio=wav)
     return kw, clip, vae
 
 
@@ -307,8 +229,8 @@ def test_sample_one_direction_init_strength_mask(dev, a2v_setup):
 def test_misuse(dev, model, a2v_setup):
     import multimodal_diffusion_amd as A
     from multimodal_diffusion_amd import _lib as L
-    z, zp, npr, known = _case(dev, "video")
-    eng = _engine(model, "video", tuple(z.shape), npr, solver="dpmpp_2m")
+    z, zp, npr, known = case(dev, "video")
+    eng = _engine(model[1], "video", tuple(z.shape), npr, solver="dpmpp_2m")
     eng.set_prompt(zp)
     with pytest.raises(ValueError, match="mask"):
         eng.set_known(known, torch.ones(3, 3))
@@ -317,7 +239,7 @@ def test_misuse(dev, model, a2v_setup):
     with pytest.raises(ValueError, match="shape"):
         eng.set_known(known[:1])
     eng.set_known(known, None, guide_seed=GSEED)
-    tn, tp = _t([900, 900], dev), _t([800, 800], dev)
+    tn, tp = ts([900, 900], dev), ts([800, 800], dev)
     with pytest.raises(ValueError, match="overlap"):
         eng.step(z, tn, tp, out=eng._known)                   # known aliases z_out
     # known aliasing x0_hist, at the C entry
@@ -328,7 +250,7 @@ def test_misuse(dev, model, a2v_setup):
                                              eng.workspace.data_ptr(), eng.workspace.numel(), L.stream_ptr(dev))
     assert rc == L.EINVAL
     # unseeded eta > 0 with a guide
-    ddim = _engine(model, "video", tuple(z.shape), npr, eta=0.5)
+    ddim = _engine(model[1], "video", tuple(z.shape), npr, eta=0.5)
     ddim.set_prompt(zp)
     ddim.set_known(known, None)
     with pytest.raises(ValueError, match="noise_seed"):

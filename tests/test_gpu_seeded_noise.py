@@ -6,12 +6,14 @@ import json
 import os
 import subprocess
 import sys
+from functools import partial
 from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
 
+from _kit import ABAR, audio_case, dev, engine, free_port, model, video_case  # noqa: F401  (dev / model are fixtures)
 from _noise_ref import normals
 from _tune import cfg_rows  # noqa: F401  (fixture)
 from oracle import ref_cpu as R
@@ -20,50 +22,7 @@ pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 SEED = 0xDEADBEEF12345678           # both key words non-zero
 ETA = 0.5
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def model(dev):
-    import multimodal_diffusion_amd as A
-    ws = R.synth_weights(seed=0, n_layers=2)
-    core = A.MMDiT(d_model=512, n_layers=2, n_heads=8, mlp_ratio=4.0).eval()
-    core.load_state_dict(ws["core"], strict=True)
-    head = A.MultiModalNoiseHead({"video": 512, "audio": 512}, {"video": 256, "audio": 32}, hidden_dim=512).eval()
-    head.load_state_dict(ws["head"], strict=True)
-    av, aa = A.LinearAdapter(256, 256), A.LinearAdapter(32, 256)
-    av.load_state_dict(ws["adapt_v"])
-    aa.load_state_dict(ws["adapt_a"])
-    return ws, tuple(m.to(dev) for m in (core, head, av, aa))
-
-
-ABAR = R.alpha_bar_table(R.beta_table(1000))
-
-
-def _engine(model, target, shape, n_prompt, **kw):
-    import multimodal_diffusion_amd as A
-    _, (core, head, av, aa) = model
-    return A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target=target, latent_shape=shape,
-                           prompt_tokens=n_prompt, alpha_bar=ABAR, guidance=3.0, **kw)
-
-
-def _video_case(dev, B=2, W=32, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    z = torch.randn(B, 8, 4, 16, W, generator=g).to(dev)
-    za = torch.randn(B, 8, 40, generator=g).to(dev)           # 10 prompt tokens (chunk 4, stride 4)
-    return z, za, 10
-
-
-def _audio_case(dev, B=2, seed=1):
-    g = torch.Generator().manual_seed(seed)
-    z = torch.randn(B, 8, 40, generator=g).to(dev)
-    zv = torch.randn(B, 8, 4, 8, 8, generator=g).to(dev)      # 8 prompt tokens (tube 2 x 4 x 4)
-    return z, zv, 8
+_engine = partial(engine, guidance=3.0)        # engine(mods, target, shape, n_prompt, **kw) at this file's guidance
 
 
 # ------------------------------------------------------------------------------------------------- the generator
@@ -113,11 +72,11 @@ def test_stream_batch_and_offset_invariance(dev, model):
     for k in range(4):
         assert torch.equal(Fn.gaussian_noise(SEED, k, tn[k:k + 1], (1,) + shape[1:]), whole[k:k + 1])
     # a seeded engine at sample_offset = k uses row k of the stream
-    z, za, npr = _video_case(dev, B=1)
+    z, za, npr = video_case(dev, B=1)
     tp = tn - 20
     k = 2
-    seeded = _engine(model, "video", tuple(z.shape), npr, eta=ETA, noise_seed=SEED, sample_offset=k)
-    plain = _engine(model, "video", tuple(z.shape), npr, eta=ETA)
+    seeded = _engine(model[1], "video", tuple(z.shape), npr, eta=ETA, noise_seed=SEED, sample_offset=k)
+    plain = _engine(model[1], "video", tuple(z.shape), npr, eta=ETA)
     for e in (seeded, plain):
         e.set_prompt(za)
     a = seeded.step(z, tn[k:k + 1], tp[k:k + 1])
@@ -130,11 +89,11 @@ def test_stream_batch_and_offset_invariance(dev, model):
 def test_fused_step_equals_explicit_noise_video(dev, model, cfg_rows, rows):
     from multimodal_diffusion_amd import functional as Fn
     cfg_rows(rows)
-    z, za, npr = _video_case(dev, B=3)
+    z, za, npr = video_case(dev, B=3)
     tn = torch.tensor([981, 402, 40], dtype=torch.long, device=dev)
     tp = torch.tensor([961, 382, -1], dtype=torch.long, device=dev)
-    seeded = _engine(model, "video", tuple(z.shape), npr, eta=ETA, noise_seed=SEED, sample_offset=5)
-    plain = _engine(model, "video", tuple(z.shape), npr, eta=ETA)
+    seeded = _engine(model[1], "video", tuple(z.shape), npr, eta=ETA, noise_seed=SEED, sample_offset=5)
+    plain = _engine(model[1], "video", tuple(z.shape), npr, eta=ETA)
     for e in (seeded, plain):
         e.set_prompt(za)
     a = seeded.step(z, tn, tp)
@@ -146,11 +105,11 @@ def test_fused_step_equals_explicit_noise_video(dev, model, cfg_rows, rows):
 
 def test_fused_step_equals_explicit_noise_audio(dev, model):
     from multimodal_diffusion_amd import functional as Fn
-    z, zv, npr = _audio_case(dev, B=3)
+    z, zv, npr = audio_case(dev, B=3)
     tn = torch.tensor([981, 402, 40], dtype=torch.long, device=dev)
     tp = torch.tensor([961, 382, -1], dtype=torch.long, device=dev)
-    seeded = _engine(model, "audio", tuple(z.shape), npr, eta=ETA, noise_seed=SEED, sample_offset=11)
-    plain = _engine(model, "audio", tuple(z.shape), npr, eta=ETA)
+    seeded = _engine(model[1], "audio", tuple(z.shape), npr, eta=ETA, noise_seed=SEED, sample_offset=11)
+    plain = _engine(model[1], "audio", tuple(z.shape), npr, eta=ETA)
     for e in (seeded, plain):
         e.set_prompt(zv)
     a = seeded.step(z, tn, tp)
@@ -159,12 +118,12 @@ def test_fused_step_equals_explicit_noise_audio(dev, model):
 
 def test_fused_step_equals_explicit_noise_split_streams_f16x2(dev, model):
     from multimodal_diffusion_amd import functional as Fn
-    z, za, npr = _video_case(dev, B=2)
+    z, za, npr = video_case(dev, B=2)
     tn = torch.tensor([700, 300], dtype=torch.long, device=dev)
     tp = torch.tensor([680, 280], dtype=torch.long, device=dev)
     kw = dict(eta=ETA, matmul="f16x2", split_streams=True)
-    seeded = _engine(model, "video", tuple(z.shape), npr, noise_seed=SEED, **kw)
-    plain = _engine(model, "video", tuple(z.shape), npr, **kw)
+    seeded = _engine(model[1], "video", tuple(z.shape), npr, noise_seed=SEED, **kw)
+    plain = _engine(model[1], "video", tuple(z.shape), npr, **kw)
     for e in (seeded, plain):
         e.set_prompt(za)
     assert torch.equal(seeded.step(z, tn, tp), plain.step(z, tn, tp, noise=Fn.gaussian_noise(SEED, 0, tn, tuple(z.shape))))
@@ -174,17 +133,17 @@ def test_fused_step_equals_explicit_noise_split_streams_f16x2(dev, model):
 @pytest.mark.parametrize("n_steps", [5, 6])
 def test_seeded_graph_equals_eager(dev, model, n_steps):
     from multimodal_diffusion_amd import functional as Fn
-    z, za, npr = _video_case(dev, B=2)
+    z, za, npr = video_case(dev, B=2)
     sched = torch.linspace(999, 0, n_steps + 1).round().long()
     sched[-1] = -1
-    seeded = _engine(model, "video", tuple(z.shape), npr, eta=ETA, noise_seed=SEED)
+    seeded = _engine(model[1], "video", tuple(z.shape), npr, eta=ETA, noise_seed=SEED)
     seeded.set_prompt(za)
     zg = seeded.run(z, sched, graph=True)
     ze = seeded.run(z, sched, graph=False)
     assert torch.equal(zg, ze)
     assert torch.equal(seeded.run(z, sched), zg)             # graph=None takes the graph here (2B*N < 6,144 rows)
     # every step drew the noise of its own t_now: the unseeded engine fed the stream step by step lands on the same bits
-    plain = _engine(model, "video", tuple(z.shape), npr, eta=ETA)
+    plain = _engine(model[1], "video", tuple(z.shape), npr, eta=ETA)
     plain.set_prompt(za)
     x = z.clone()
     for i in range(n_steps):
@@ -205,10 +164,10 @@ def test_seeded_trajectory_vs_oracle(dev, model, target):
     n_steps = 8
     sched = R.sampling_schedule(1000, n_steps)
     if target == "video":
-        z, zp, npr = _video_case(dev, B=2, W=16)
+        z, zp, npr = video_case(dev, B=2, W=16)
     else:
-        z, zp, npr = _audio_case(dev, B=2)
-    eng = _engine(model, target, tuple(z.shape), npr, eta=ETA, noise_seed=SEED, sample_offset=3)
+        z, zp, npr = audio_case(dev, B=2)
+    eng = _engine(model[1], target, tuple(z.shape), npr, eta=ETA, noise_seed=SEED, sample_offset=3)
     eng.set_prompt(zp)
     out = eng.run(z, sched).cpu().double()
     x, p = z.cpu(), zp.cpu()
@@ -230,36 +189,29 @@ def test_seeded_trajectory_vs_oracle(dev, model, target):
 
 # ------------------------------------------------------------------------------------------------- no behaviour change
 def test_no_behaviour_change_without_eta_or_seed(dev, model):
-    z, za, npr = _video_case(dev, B=2)
+    z, za, npr = video_case(dev, B=2)
     tn = torch.tensor([900, 100], dtype=torch.long, device=dev)
     tp = torch.tensor([880, 80], dtype=torch.long, device=dev)
-    seeded0 = _engine(model, "video", tuple(z.shape), npr, eta=0.0, noise_seed=SEED)
-    plain0 = _engine(model, "video", tuple(z.shape), npr, eta=0.0)
+    seeded0 = _engine(model[1], "video", tuple(z.shape), npr, eta=0.0, noise_seed=SEED)
+    plain0 = _engine(model[1], "video", tuple(z.shape), npr, eta=0.0)
     for e in (seeded0, plain0):
         e.set_prompt(za)
     assert torch.equal(seeded0.step(z, tn, tp), plain0.step(z, tn, tp))
-    unseeded = _engine(model, "video", tuple(z.shape), npr, eta=ETA)
+    unseeded = _engine(model[1], "video", tuple(z.shape), npr, eta=ETA)
     unseeded.set_prompt(za)
     unseeded.begin(torch.tensor([999, 500, -1]))
     with pytest.raises(NotImplementedError):
         unseeded.capture_pair(z.clone(), torch.empty_like(z))
-    seeded = _engine(model, "video", tuple(z.shape), npr, eta=ETA, noise_seed=SEED)
+    seeded = _engine(model[1], "video", tuple(z.shape), npr, eta=ETA, noise_seed=SEED)
     seeded.set_prompt(za)
     with pytest.raises(ValueError):
         seeded.step(z, tn, tp, noise=torch.randn_like(z))
     for bad in (dict(noise_seed=-1), dict(noise_seed=2 ** 64), dict(noise_seed=1, sample_offset=-1), dict(sample_offset=3)):
         with pytest.raises(ValueError):
-            _engine(model, "video", tuple(z.shape), npr, eta=ETA, **bad)
+            _engine(model[1], "video", tuple(z.shape), npr, eta=ETA, **bad)
 
 
 # ------------------------------------------------------------------------------------------------- sharded = single process
-def _free_port():
-    import socket
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 @pytest.mark.gpu_first
 def test_stream_generate_seeded_eta_sharded_two_ranks_share_device(tmp_path):
     """stream_generate(shard=True) with ddim_eta 0.5 and noise_seed, as two fresh ranks under torch.distributed.run (gloo, both on
@@ -272,7 +224,7 @@ def test_stream_generate_seeded_eta_sharded_two_ranks_share_device(tmp_path):
     out = tmp_path / "shard.json"
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", AVD_TEST_OUT=str(out))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), str(ROOT / "tests" / "_stream_shard_seeded_worker.py")]
+           "--master-port", str(free_port()), str(ROOT / "tests" / "_stream_shard_seeded_worker.py")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     d = json.loads(out.read_text())

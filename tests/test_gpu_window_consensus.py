@@ -1,54 +1,20 @@
 """Latent window consensus on the MI355X (include/avdiff_hip.h, avd_window_consensus_f32): the kernel against the numpy mirror bit for
 bit, the engine's consensus step against the plain step followed by the functional call, graph replay against eager launches, and
 stream_generate: the finished latents agree on every overlap, whatever the batching, and equal a hand-written loop; off by default."""
+from functools import partial
+
 import numpy as np
 import pytest
 import torch
 
 import _consensus_ref as W
+from _kit import (STREAM_HALF_SECOND, audio_prompt, components, dev, engine, matmul_f32, model,  # noqa: F401  (dev / model are fixtures)
+                  pipeline, ts, video_case, video_prompt, with_sampling)
 from oracle import ref_cpu as R
 
 pytestmark = pytest.mark.gpu
-ABAR = R.alpha_bar_table(R.beta_table(1000))
 G = 3.0
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def model(dev):
-    import multimodal_diffusion_amd as A
-    ws = R.synth_weights(seed=0, n_layers=2)
-    core = A.MMDiT(d_model=512, n_layers=2, n_heads=8, mlp_ratio=4.0).eval()
-    core.load_state_dict(ws["core"], strict=True)
-    head = A.MultiModalNoiseHead({"video": 512, "audio": 512}, {"video": 256, "audio": 32}, hidden_dim=512).eval()
-    head.load_state_dict(ws["head"], strict=True)
-    av, aa = A.LinearAdapter(256, 256), A.LinearAdapter(32, 256)
-    av.load_state_dict(ws["adapt_v"])
-    aa.load_state_dict(ws["adapt_a"])
-    return ws, tuple(m.to(dev) for m in (core, head, av, aa))
-
-
-def _engine(model, target, shape, n_prompt, **kw):
-    import multimodal_diffusion_amd as A
-    _, (core, head, av, aa) = model
-    return A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target=target, latent_shape=shape,
-                           prompt_tokens=n_prompt, alpha_bar=ABAR, guidance=G, **kw)
-
-
-def _video_case(dev, B=3, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    z = torch.randn(B, 8, 4, 16, 16, generator=g).to(dev)
-    za = torch.randn(B, 8, 40, generator=g).to(dev)           # 10 prompt tokens (chunk 4, stride 4)
-    return z, za, 10
-
-
-def _t(v, dev):
-    return torch.tensor(v, dtype=torch.long, device=dev)
+_engine = partial(engine, guidance=G)        # engine(mods, target, shape, n_prompt, **kw) at this file's guidance
 
 
 # ------------------------------------------------------------------------------------------------- kernel = mirror, bit for bit
@@ -111,10 +77,10 @@ def test_functional_misuse(dev):
 @pytest.mark.parametrize("solver,cond_only", [("ddim", False), ("dpmpp_2m", False), ("ddim", True), ("dpmpp_2m", True)])
 def test_engine_step_is_step_then_consensus(dev, model, solver, cond_only):
     from multimodal_diffusion_amd import functional as Fn
-    z, za, npr = _video_case(dev)
+    z, za, npr = video_case(dev, B=3, W=16)
     w = torch.linspace(0.5, 2.0, 4)
-    tn, tp, tl = _t([900] * 3, dev), _t([700] * 3, dev), _t([950] * 3, dev)
-    eng = _engine(model, "video", tuple(z.shape), npr, solver=solver)
+    tn, tp, tl = ts([900] * 3, dev), ts([700] * 3, dev), ts([950] * 3, dev)
+    eng = _engine(model[1], "video", tuple(z.shape), npr, solver=solver)
     eng.set_prompt(za)
     hist = torch.randn(z.shape, generator=torch.Generator().manual_seed(3)).to(dev)
 
@@ -141,9 +107,9 @@ def test_engine_step_is_step_then_consensus(dev, model, solver, cond_only):
 @pytest.mark.parametrize("solver", ["ddim", "dpmpp_2m"])
 def test_graph_equals_eager_and_stale_pairs_are_refused(dev, model, solver):
     from multimodal_diffusion_amd import _lib as L
-    z, za, npr = _video_case(dev)
+    z, za, npr = video_case(dev, B=3, W=16)
     sched = R.sampling_schedule(1000, 5)
-    eng = _engine(model, "video", tuple(z.shape), npr, solver=solver)
+    eng = _engine(model[1], "video", tuple(z.shape), npr, solver=solver)
     eng.set_prompt(za)
     free = eng.run(z, sched, graph=False)
     # a pair captured before the consensus is switched on holds no consensus launch: it refuses to replay afterwards
@@ -172,11 +138,11 @@ def test_graph_equals_eager_and_stale_pairs_are_refused(dev, model, solver):
 
 
 def test_engine_misuse(dev, model):
-    z, za, npr = _video_case(dev)
-    noisy = _engine(model, "video", tuple(z.shape), npr, eta=0.5, noise_seed=1)
+    z, za, npr = video_case(dev, B=3, W=16)
+    noisy = _engine(model[1], "video", tuple(z.shape), npr, eta=0.5, noise_seed=1)
     with pytest.raises(ValueError, match="eta"):
         noisy.set_window_consensus(2)
-    eng = _engine(model, "video", tuple(z.shape), npr)
+    eng = _engine(model[1], "video", tuple(z.shape), npr)
     for hop in (0, -2, 1.5):
         with pytest.raises(ValueError):
             eng.set_window_consensus(hop)
@@ -184,7 +150,7 @@ def test_engine_misuse(dev, model):
         eng.set_window_consensus(2, torch.ones(3))             # L is 4
     with pytest.raises(ValueError):
         eng.set_window_consensus(2, torch.tensor([1.0, 0.0, 1.0, 1.0]))
-    assert eng._cons_hop is None and eng._generation == _engine(model, "video", tuple(z.shape), npr)._generation
+    assert eng._cons_hop is None and eng._generation == _engine(model[1], "video", tuple(z.shape), npr)._generation
 
 
 # ------------------------------------------------------------------------------------------------- stream_generate
@@ -192,48 +158,16 @@ def test_engine_misuse(dev, model):
 def stream(dev, model):
     """(kw, cfg) for stream_generate at the geometry of test_gpu_dpm_solver.py::test_stream_generate_batch_invariance: 0.5 s windows
     every 0.25 s, 32 x 32 frames, a 4-step schedule; the fp32 kernel family whatever the batch, so that batch sizes can be compared"""
-    import multimodal_diffusion_amd as A
-    _, (core, head, av, aa) = model
-    prev = core.matmul, head.matmul
-    core.matmul = head.matmul = "f32"
-    try:
-        torch.manual_seed(8)
-        vae = A.VideoVAE.from_config({"latent": {"channels": 8, "t_down": 4, "s_down": 8}}).eval().to(dev)
-        codec = A.AudioCodec.from_config({"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150},
-                                          "codec": {"hop_samples": 320}}).eval().to(dev)
-        cfg = {"tokenizer": {"width": 512, "video": {"tube": {"t": 2, "h": 4, "w": 4}}, "audio": {"chunk": {"length": 4, "stride": 4}}},
-               "video": {"fps": 16, "size": [32, 32], "latent": {"channels": 8, "t_down": 4, "s_down": 8}},
-               "audio": {"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150}},
-               "data": {"clip_seconds": 0.5}, "streaming": {"window_seconds": 0.5, "hop_seconds": 0.25, "crossfade_seconds": 0.125},
-               "diffusion": {m: {"steps": 1000, "sampler_steps": 4, "schedule": "cosine", "min_beta": 1e-4, "max_beta": 0.02}
-                             for m in ("video", "audio")},
-               "sampling": {"guidance_scale": {"video": 2.0, "audio": 2.0}}}
-        kw = dict(cfg=cfg, vid_vae=vae, aud_codec=codec, adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, device=dev,
-                  shard=False)
-        yield kw, cfg
-    finally:
-        core.matmul, head.matmul = prev
-
-
-def _with_solver(cfg, solver, **sampling):
-    return dict(cfg, sampling=dict(cfg["sampling"], solver=solver, **sampling))
-
-
-def _audio_prompt(n=18000):
-    wav = (0.1 * torch.randn(n, generator=torch.Generator().manual_seed(9))).numpy()      # 18000 samples: 4 windows
-    return dict(prompt_modality="audio", prompt_video=None, prompt_audio=wav, seed=10)
-
-
-def _video_prompt():
-    vid = torch.randint(0, 256, (20, 32, 32, 3), generator=torch.Generator().manual_seed(11), dtype=torch.uint8).numpy()
-    return dict(prompt_modality="video", prompt_video=vid, prompt_audio=None, seed=12)          # 20 frames: 4 windows
+    with matmul_f32(model[1]):
+        vae, codec, cfg = pipeline(dev, seed=8, clip_seconds=0.5, sampler_steps=4, streaming=STREAM_HALF_SECOND)
+        yield dict(components(model[1], vae, codec, dev), cfg=cfg, shard=False), cfg
 
 
 @pytest.mark.parametrize("solver", ["ddim", "dpmpp_2m"])
 def test_stream_latents_agree_on_overlaps_for_any_batching(dev, stream, solver):
     from multimodal_diffusion_amd import stream_infer as S
     kw, cfg = stream
-    kw = dict(kw, cfg=_with_solver(cfg, solver), **_audio_prompt())
+    kw = dict(kw, cfg=with_sampling(cfg, solver=solver), **audio_prompt())
     hop, L_ = S.latent_hop(kw["cfg"], "video")
     assert (hop, L_) == (1, 2)
     whole = S.stream_generate(consensus="uniform", return_latents=True, **kw)
@@ -259,16 +193,14 @@ def test_stream_latents_agree_on_overlaps_for_any_batching(dev, stream, solver):
 
 @pytest.mark.parametrize("solver", ["ddim", "dpmpp_2m"])
 def test_stream_equals_hand_written_loop(dev, model, stream, solver):
-    import multimodal_diffusion_amd as A
     from multimodal_diffusion_amd import functional as Fn
     from multimodal_diffusion_amd import schedule_utils as su
     from multimodal_diffusion_amd import stream_infer as S
     kw, cfg = stream
-    kw = dict(kw, cfg=_with_solver(cfg, solver), **_audio_prompt())
+    kw = dict(kw, cfg=with_sampling(cfg, solver=solver), **audio_prompt())
     got = S.stream_generate(consensus="uniform", return_latents=True, **kw)["latents"]
     # the same trajectory by hand: the prompt windows, the seeded canvas cropped into windows, one engine, and after every step the
     # functional consensus
-    _, (core, head, av, aa) = model
     chunks, _, _ = S.split_audio_into_windows(kw["prompt_audio"], sr=16000, win_s=0.5, hop_s=0.25)
     z_p = kw["aud_codec"].encode(torch.from_numpy(np.ascontiguousarray(chunks, dtype=np.float32)).to(dev)[:, None, :])
     canvas = torch.randn(8, 5, 4, 4, generator=torch.Generator().manual_seed(10))
@@ -276,14 +208,13 @@ def test_stream_equals_hand_written_loop(dev, model, stream, solver):
     c = cfg["diffusion"]["video"]
     abar = su.alphas_cumprod_from_betas(su.make_beta_schedule(1000, kind=c["schedule"], min_beta=c["min_beta"], max_beta=c["max_beta"]))[1]
     sched = su.make_sampling_schedule(1000, 4)
-    eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target="video", latent_shape=tuple(z.shape),
-                          prompt_tokens=(150 - 4) // 4 + 1, alpha_bar=abar, guidance=2.0, solver=solver)
+    eng = engine(model[1], "video", tuple(z.shape), (150 - 4) // 4 + 1, alpha_bar=abar, guidance=2.0, solver=solver)
     eng.set_prompt(z_p.float().contiguous())
     for i in range(sched.numel() - 1):
         kws = {}
         if solver == "dpmpp_2m" and i > 0:
-            kws["t_last"] = _t([int(sched[i - 1])] * 4, dev)
-        z = eng.step(z, _t([int(sched[i])] * 4, dev), _t([int(sched[i + 1])] * 4, dev), **kws)
+            kws["t_last"] = ts([int(sched[i - 1])] * 4, dev)
+        z = eng.step(z, ts([int(sched[i])] * 4, dev), ts([int(sched[i + 1])] * 4, dev), **kws)
         Fn.window_consensus(z, 1)
     assert np.array_equal(z.cpu().numpy(), got)
 
@@ -297,8 +228,8 @@ def test_stream_guidance_interval_keeps_batch_invariance(dev, stream):
     kinds = [c for _, _, c in su.guidance_segments(sched, interval)]
     assert kinds == [False, True, False]
     for solver in ("ddim", "dpmpp_2m"):
-        kws = dict(kw, cfg=_with_solver(cfg, solver), guidance_interval=interval, consensus="uniform", return_latents=True,
-                   **_audio_prompt())
+        kws = dict(kw, cfg=with_sampling(cfg, solver=solver), guidance_interval=interval, consensus="uniform", return_latents=True,
+                   **audio_prompt())
         whole = S.stream_generate(**kws)
         assert W.overlaps_agree(whole["latents"], 1)
         for mw in (2, 1):
@@ -312,7 +243,7 @@ def test_stream_video_prompt_direction(dev, stream):
     from multimodal_diffusion_amd import stream_infer as S
     kw, cfg = stream
     for solver in ("ddim", "dpmpp_2m"):
-        kws = dict(kw, cfg=_with_solver(cfg, solver), **_video_prompt())
+        kws = dict(kw, cfg=with_sampling(cfg, solver=solver), **video_prompt())
         assert S.latent_hop(kws["cfg"], "audio") == (75, 150)
         whole = S.stream_generate(consensus="uniform", return_latents=True, **kws)
         assert whole["latents"].shape == (4, 8, 150) and W.overlaps_agree(whole["latents"], 75)
@@ -325,13 +256,13 @@ def test_stream_video_prompt_direction(dev, stream):
 def test_stream_off_by_default_and_single_window(dev, stream):
     from multimodal_diffusion_amd import stream_infer as S
     kw, cfg = stream
-    kws = dict(kw, **_audio_prompt())
+    kws = dict(kw, **audio_prompt())
     today = S.stream_generate(**kws)
     assert set(today) == {"video", "fps"}
     off = S.stream_generate(consensus=None, return_latents=True, **kws)
     assert np.array_equal(off["video"], today["video"])
     # one window has nothing to agree with: the same output with and without
-    one = dict(kw, **_audio_prompt(8000))
+    one = dict(kw, **audio_prompt(8000))
     a = S.stream_generate(return_latents=True, **one)
     b = S.stream_generate(consensus="uniform", return_latents=True, **one)
     assert a["latents"].shape == (1, 8, 2, 4, 4)
@@ -341,11 +272,11 @@ def test_stream_off_by_default_and_single_window(dev, stream):
 def test_stream_misuse(dev, stream):
     from multimodal_diffusion_amd import stream_infer as S
     kw, cfg = stream
-    kws = dict(kw, **_audio_prompt())
+    kws = dict(kw, **audio_prompt())
     with pytest.raises(ValueError, match="halo"):
         S.stream_generate(consensus="uniform", **dict(kws, shard=True))
     with pytest.raises(ValueError, match="ddim_eta"):
-        S.stream_generate(consensus="uniform", noise_seed=3, **dict(kws, cfg=_with_solver(cfg, "ddim", ddim_eta=0.5)))
+        S.stream_generate(consensus="uniform", noise_seed=3, **dict(kws, cfg=with_sampling(cfg, solver="ddim", ddim_eta=0.5)))
     misaligned = dict(cfg, streaming=dict(cfg["streaming"], hop_seconds=0.125))              # 2 frames per hop, t_down 4
     with pytest.raises(ValueError, match="t_down"):
         S.stream_generate(consensus="uniform", **dict(kws, cfg=misaligned))

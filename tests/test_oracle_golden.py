@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from _kit import grp
 from conftest import load_golden, rel_err, split_weights
 from oracle import ref_cpu as R
 
@@ -325,10 +326,6 @@ def test_g19_shipped_config_through_reference_sampler():
     assert mx <= 1 and frac < 1e-3, (mx, frac)
 
 
-def _grp(g, prefix):
-    return {k[len(prefix) + 1:]: torch.from_numpy(v) for k, v in g.items() if k.startswith(prefix + "/")}
-
-
 def test_g16_dropin_corners(small_model):
     """Options of the reference API the shipped sampler never uses: key_padding_mask, norm="layernorm", relu / leaky_relu heads,
     variational eval encode, Hann-window overlap-add (tools/make_golden.py G16)."""
@@ -336,11 +333,11 @@ def test_g16_dropin_corners(small_model):
     g = load_golden("g16_dropin_corners.npz")
     y = R.mmdit_forward(T(g["mask/x"]), W["core"], meta["n_layers"], meta["n_heads"], key_padding_mask=T(g["mask/kpm"]))
     assert rel_err(y, g["mask/y"]) < TOL
-    assert rel_err(R.mmdit_forward(T(g["ln/x"]), _grp(g, "ln_core"), 2, 2), g["ln/y"]) < TOL
+    assert rel_err(R.mmdit_forward(T(g["ln/x"]), grp(g, "ln_core"), 2, 2), g["ln/y"]) < TOL
     for act in ("relu", "leaky_relu"):
-        out = R.noise_head(T(g[f"head_{act}/hv"]), _grp(g, f"head_{act}_w"), "video", activation=act)
+        out = R.noise_head(T(g[f"head_{act}/hv"]), grp(g, f"head_{act}_w"), "video", activation=act)
         assert rel_err(out, g[f"head_{act}/out_v"]) < TOL
-    z, kld = R.vae_encode(T(g["vvae/x"]), _grp(g, "vvae_w"), variational=True)
+    z, kld = R.vae_encode(T(g["vvae/x"]), grp(g, "vvae_w"), variational=True)
     assert rel_err(z, g["vvae/z"]) < TOL and abs(float(kld) - float(g["vvae/kld"])) < 1e-5
     wnd = T(g["hann/windows"])                                         # [2,3,5,8] -> one "channel" per prefix row
     flat = wnd.reshape(6, 5, 8)
