@@ -156,6 +156,8 @@ def tube_unpatch(tokens: Tensor, C_: int, T: int, H: int, W: int, t: int, h: int
 def audio_tokens(z_a: Tensor, length: int, stride: int) -> Tensor:
     z_a = L.dev_f32(z_a, "z_a")
     B, Ca, F = z_a.shape
+    if length <= 0 or stride <= 0 or F < length:      # no token to allocate: refused here, in the words of audio_tokens_f32 (csrc/tokens.hip)
+        raise L.AvdError(f"audio_tokens: need 0 < len <= F and stride > 0 (got F={F} len={length} stride={stride})")
     na = (F - length) // stride + 1
     tok = torch.empty(B, na, Ca * length, device=z_a.device, dtype=torch.float32)
     L.check(L.lib().avd_audio_tokens_f32(z_a.data_ptr(), tok.data_ptr(), B, Ca, F, length, stride, _st(z_a)))

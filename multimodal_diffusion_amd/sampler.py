@@ -89,6 +89,12 @@ def latents_to_tokens_video(z_v: torch.Tensor, t_p: int, p: int) -> torch.Tensor
     return ops.tube_patch_video(z_v, t=t_p, h=p, w=p)
 
 
+def tube_from_config(cfg: Dict) -> Tuple[int, int, int]:
+    """tokenizer.video.tube as (t, h, w); a config without "w" has the reference's square tube (w = h)"""
+    tube = cfg["tokenizer"]["video"]["tube"]
+    return int(tube["t"]), int(tube["h"]), int(tube.get("w", tube["h"]))
+
+
 def latents_to_tokens_audio(z_a: torch.Tensor, l_chunk: int, s_chunk: int) -> torch.Tensor:
     return Fn.audio_tokens(z_a, l_chunk, s_chunk)
 
@@ -393,7 +399,7 @@ class DenoiseEngine:
         if z.shape[0] != B:
             raise ValueError("prompt batch size must match the engine's")
         tok = latents_to_tokens_audio(z, *self.chunk) if self.target == "video" else \
-            latents_to_tokens_video(z, self.tube[0], self.tube[1])
+            ops.tube_patch_video(z, *self.tube)
         if tok.shape[1] != self.embed.Np:
             raise ValueError(f"prompt yields {tok.shape[1]} tokens, engine was built for {self.embed.Np}")
         d, td = self.d, self.tdim
@@ -857,7 +863,7 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
     dcfg, scfg = cfg["diffusion"], cfg["sampling"]
     eta = float(scfg.get("ddim_eta", 0.0))
     solver = str(scfg.get("solver", "ddim"))
-    t_p, p = int(cfg["tokenizer"]["video"]["tube"]["t"]), int(cfg["tokenizer"]["video"]["tube"]["h"])
+    t_p, p, p_w = tube_from_config(cfg)
     l_chunk = int(cfg["tokenizer"]["audio"]["chunk"]["length"])
     s_chunk = int(cfg["tokenizer"]["audio"]["chunk"]["stride"])
     Cv, t_down, s_down = (int(cfg["video"]["latent"][k]) for k in ("channels", "t_down", "s_down"))
@@ -879,7 +885,7 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
         if tuple(z.shape) != (1, Ca, Fa):
             raise ValueError(f"init_noise has shape {tuple(z.shape)}, expected {(1, Ca, Fa)}")
         target, guide = "audio", float(scfg["guidance_scale"].get("audio", 3.0))
-        n_prompt = (z_p.shape[2] // t_p) * (z_p.shape[3] // p) * (z_p.shape[4] // p)
+        n_prompt = (z_p.shape[2] // t_p) * (z_p.shape[3] // p) * (z_p.shape[4] // p_w)
     elif prompt_modality == "audio":
         if prompt_audio is None:
             raise ValueError("prompt_audio required for prompt_modality=audio")
@@ -900,7 +906,7 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
     interval = su.check_guidance_interval(guidance_interval) or su.guidance_interval_from_config(scfg, target)
     eng = DenoiseEngine(adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, target=target,
                         latent_shape=tuple(z.shape), prompt_tokens=n_prompt, alpha_bar=abar, guidance=guide, eta=eta,
-                        tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed, solver=solver, guidance_rescale=rescale,
+                        tube=(t_p, p, p_w), chunk=(l_chunk, s_chunk), noise_seed=noise_seed, solver=solver, guidance_rescale=rescale,
                         guidance_interval=interval)
     eng.set_prompt(z_p.float())
     if init is not None:

@@ -30,7 +30,7 @@ from . import _lib as L
 from . import dist as D
 from . import functional as Fn
 from . import schedule_utils as su
-from .sampler import DenoiseEngine
+from .sampler import DenoiseEngine, tube_from_config
 
 
 def split_audio_into_windows(y: np.ndarray, sr: int, win_s: float, hop_s: float) -> Tuple[np.ndarray, int, int]:
@@ -218,7 +218,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     win_s, hop_s = float(st.get("window_seconds", 3.0)), float(st.get("hop_seconds", 1.0))
     xfade_s = float(st.get("crossfade_seconds", 0.25))
     fps, sr = int(cfg["video"]["fps"]), int(cfg["audio"]["sr"])
-    t_p, p = int(cfg["tokenizer"]["video"]["tube"]["t"]), int(cfg["tokenizer"]["video"]["tube"]["h"])
+    t_p, p, p_w = tube_from_config(cfg)
     l_chunk, s_chunk = int(cfg["tokenizer"]["audio"]["chunk"]["length"]), int(cfg["tokenizer"]["audio"]["chunk"]["stride"])
     Cv, t_down, s_down = (int(cfg["video"]["latent"][k]) for k in ("channels", "t_down", "s_down"))
     Ca, Fa = int(cfg["audio"]["latent"]["channels"]), int(cfg["audio"]["latent"]["frames_per_clip"])
@@ -268,7 +268,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         chunks, win, hop = split_frames_into_windows(prompt_video, fps=fps, win_s=win_s, hop_s=hop_s)
         zp_shape = (chunks.shape[0], Cv, chunks.shape[1] // t_down, chunks.shape[2] // s_down, chunks.shape[3] // s_down)
         target, lat = "audio", (Ca, Fa)
-        n_prompt = (zp_shape[2] // t_p) * (zp_shape[3] // p) * (zp_shape[4] // p)
+        n_prompt = (zp_shape[2] // t_p) * (zp_shape[3] // p) * (zp_shape[4] // p_w)
         guide = float(cfg["sampling"]["guidance_scale"].get("audio", 3.0))
     elif prompt_modality == "audio":
         if prompt_audio is None:
@@ -295,7 +295,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
                 # single process (e.g. a caller-supplied encoder): the encoder's own output decides, as in the reference
                 zp_shape = tuple(z_p.shape)
                 if prompt_modality == "video":
-                    n_prompt = (zp_shape[2] // t_p) * (zp_shape[3] // p) * (zp_shape[4] // p)
+                    n_prompt = (zp_shape[2] // t_p) * (zp_shape[3] // p) * (zp_shape[4] // p_w)
                 else:
                     n_prompt = (zp_shape[-1] - l_chunk) // s_chunk + 1
         except Exception as exc:            # noqa: BLE001 — re-raised below; a sharded run first tells the other ranks
@@ -340,7 +340,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         """the engine of windows [lo, hi), its prompt rows set from zp_part (which starts at window lo0)"""
         eng = DenoiseEngine(adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, target=target,
                             latent_shape=(hi - lo, *lat), prompt_tokens=n_prompt, alpha_bar=abar, guidance=guide, eta=eta,
-                            tube=(t_p, p, p), chunk=(l_chunk, s_chunk), noise_seed=noise_seed,
+                            tube=(t_p, p, p_w), chunk=(l_chunk, s_chunk), noise_seed=noise_seed,
                             sample_offset=lo if noise_seed is not None else 0, solver=solver,
                             guidance_rescale=float(rescale_cfg.get(target, 0.0)), guidance_interval=interval,
                             noise_keying=noise_keying, canvas_hop=cons_hop if canvas_keyed else None)

@@ -43,3 +43,10 @@ def rescale_f32(e, phi, s):
 def cfg_rescale(c, y, phi):
     """r(y) with s_b from (c, y): what functional.cfg_rescale computes on latent-layout tensors."""
     return rescale_f32(y, phi, scale(c, y))
+
+
+def ulps(a, b):
+    """fp32 ulp distance, elementwise (same-sign finite values)"""
+    ia = np.asarray(a, np.float32).view(np.int32).astype(np.int64)
+    ib = np.asarray(b, np.float32).view(np.int32).astype(np.int64)
+    return np.abs(ia - ib)

@@ -120,9 +120,10 @@ def grp(g, prefix):
 
 
 # ------------------------------------------------------------------------------------------------- the reduced pipeline
-def pipeline_cfg(*, clip_seconds, sampler_steps, size=(32, 32), streaming=None, sampling=None):
+def pipeline_cfg(*, clip_seconds, sampler_steps, size=(32, 32), streaming=None, sampling=None, tokenizer=None):
     """the config of the reduced pipeline: tube 2 x 4 x 4, chunk 4 / 4, 16 fps, a cosine schedule of 1000 steps; `sampling` adds to
-    (or overrides) guidance 2.0 for both targets"""
+    (or overrides) guidance 2.0 for both targets; `tokenizer` = {"video": {"tube": ...}, "audio": {"chunk": ...}} replaces the
+    tokenizer sub-dicts it names"""
     cfg = {"tokenizer": {"width": 512, "video": {"tube": {"t": 2, "h": 4, "w": 4}}, "audio": {"chunk": {"length": 4, "stride": 4}}},
            "video": {"fps": 16, "size": list(size), "latent": {"channels": 8, "t_down": 4, "s_down": 8}},
            "audio": {"sr": 16000, "latent": {"channels": 8, "frames_per_clip": 150}},
@@ -132,6 +133,9 @@ def pipeline_cfg(*, clip_seconds, sampler_steps, size=(32, 32), streaming=None, 
            "sampling": dict({"guidance_scale": {"video": 2.0, "audio": 2.0}}, **(sampling or {}))}
     if streaming is not None:
         cfg["streaming"] = dict(streaming)
+    for k in ("video", "audio"):
+        if tokenizer is not None and k in tokenizer:
+            cfg["tokenizer"][k] = dict(tokenizer[k])
     return cfg
 
 

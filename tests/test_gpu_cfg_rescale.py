@@ -21,13 +21,6 @@ GSEED = 77
 _engine = partial(engine, guidance=GS)        # engine(mods, target, shape, n_prompt, **kw) at this file's guidance
 
 
-def _ulps(a, b):
-    """fp32 ulp distance, elementwise (same-sign finite values)"""
-    ia = np.asarray(a, np.float32).view(np.int32).astype(np.int64)
-    ib = np.asarray(b, np.float32).view(np.int32).astype(np.int64)
-    return np.abs(ia - ib)
-
-
 def _untok(eng, tok):
     """U: tokens [B, N, D] -> the latent's natural layout (tube un-patch / overlap-add mean)"""
     from multimodal_diffusion_amd import functional as Fn
@@ -50,7 +43,7 @@ def test_functional_matches_mirror(dev):
     for phi in (0.0, 0.3, 0.7, 1.0, [0.0, 0.3, 0.7, 1.0, 0.5]):
         out, s = Fn.cfg_rescale(c.to(dev), y.to(dev), phi, return_scale=True)
         s = s.cpu().numpy()
-        assert _ulps(s, s_ref).max() <= 2, (s, s_ref)
+        assert CR.ulps(s, s_ref).max() <= 2, (s, s_ref)
         assert np.array_equal(out.cpu().numpy(), CR.rescale_f32(y.numpy(), phi, s))     # r(e) is elementwise: exact given s
         if phi == 0.0:
             assert torch.equal(out.cpu(), y)
@@ -82,21 +75,14 @@ SOLVERS = [{}, dict(eta=0.7, noise_seed=5), dict(solver="dpmpp_2m")]
 G2, PHI2 = [2.0, 5.0], [0.7, 0.3]
 
 
-@pytest.mark.parametrize("guided", [False, True])
-@pytest.mark.parametrize("kw", SOLVERS, ids=["ddim", "seeded", "dpmpp_2m"])
-@pytest.mark.parametrize("target", ["video", "audio"])
-def test_fused_equals_composed(dev, model, cfg_rows, target, kw, guided):
+def _check_fused_equals_composed(dev, eng, cfg_rows, z, known, mask, kw, check_scale=False):
+    """the body of test_fused_equals_composed for an engine built with guidance G2, rescale PHI2 and the solver keywords kw, its
+    prompt set: B = 2; mask None = no guide.  check_scale: s_b of the composed path also against the numpy mirror, within the 2 ulp
+    of test_functional_matches_mirror.  test_gpu_token_geometry runs it at the other geometries."""
     from multimodal_diffusion_amd import functional as Fn
-    z, zp, npr, known = case(dev, target)
-    B = z.shape[0]
-    eng = _engine(model[1], target, tuple(z.shape), npr, guidance=G2, guidance_rescale=PHI2, **kw)
-    eng.set_prompt(zp)
+    B, target = z.shape[0], eng.target
     dpm = kw.get("solver") == "dpmpp_2m"
-    mask = None
-    if guided:
-        mask = torch.rand(tuple(z.shape[1:]), generator=torch.Generator().manual_seed(3))
-        mask[mask < 0.35] = 0.0
-        mask = mask.to(dev)
+    if mask is not None:
         eng.set_known(known, mask, guide_seed=GSEED)
     h0 = torch.randn(z.shape, generator=torch.Generator().manual_seed(7)).to(dev)
     tn, tp = ts([981, 402], dev), ts([961, 382], dev)
@@ -119,8 +105,11 @@ def test_fused_equals_composed(dev, model, cfg_rows, target, kw, guided):
     ep = eng.eps_tokens()
     ec, en = ep[:B], ep[B:]
     gt = torch.tensor(G2, device=dev).view(B, 1, 1)
-    y = _untok(eng, en + gt * (ec - en))
-    r = Fn.cfg_rescale(_untok(eng, ec), y, PHI2)
+    c, y = _untok(eng, ec), _untok(eng, en + gt * (ec - en))
+    r, s = Fn.cfg_rescale(c, y, PHI2, return_scale=True)
+    if check_scale:
+        s_ref = CR.scale(c.cpu().numpy(), y.cpu().numpy())
+        assert CR.ulps(s.cpu().numpy(), s_ref).max() <= 2, (s, s_ref)
     if dpm:
         h = h0.clone()
         ref = Fn.dpmpp_2m_step(z, r, h, tl, tn, tp, ABAR)
@@ -129,7 +118,7 @@ def test_fused_equals_composed(dev, model, cfg_rows, target, kw, guided):
         ref = Fn.ddim_step(z, tn, tp, r, ABAR, eta=0.7, noise=Fn.gaussian_noise(5, 0, tn, tuple(z.shape)))
     else:
         ref = Fn.ddim_step(z, tn, tp, r, ABAR)
-    if guided:
+    if mask is not None:
         ref = Fn.latent_guide(known, tp, ABAR, z=ref, mask=mask, seed=GSEED)
     assert torch.isfinite(out).all()
     assert float((out - ref).norm() / ref.norm()) <= 1e-6
@@ -138,6 +127,21 @@ def test_fused_equals_composed(dev, model, cfg_rows, target, kw, guided):
     if dpm:
         eng.x0_hist.copy_(h0)
     assert not torch.equal(eng.step(z, tn, tp, t_last=tl), out)
+
+
+@pytest.mark.parametrize("guided", [False, True])
+@pytest.mark.parametrize("kw", SOLVERS, ids=["ddim", "seeded", "dpmpp_2m"])
+@pytest.mark.parametrize("target", ["video", "audio"])
+def test_fused_equals_composed(dev, model, cfg_rows, target, kw, guided):
+    z, zp, npr, known = case(dev, target)
+    eng = _engine(model[1], target, tuple(z.shape), npr, guidance=G2, guidance_rescale=PHI2, **kw)
+    eng.set_prompt(zp)
+    mask = None
+    if guided:
+        mask = torch.rand(tuple(z.shape[1:]), generator=torch.Generator().manual_seed(3))
+        mask[mask < 0.35] = 0.0
+        mask = mask.to(dev)
+    _check_fused_equals_composed(dev, eng, cfg_rows, z, known, mask, kw)
 
 
 # ------------------------------------------------------------------------------------------------- bit-identities

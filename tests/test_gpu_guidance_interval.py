@@ -27,8 +27,9 @@ _engine = partial(engine, guidance=GS)        # engine(mods, target, shape, n_pr
 STATES = ["plain", "noise", "seeded", "dpm1", "dpm2"]
 
 
-def _fused(dev, target, eps, z, tn, tp, state, guide, h):
-    """avd_eps_unpatch_ddim_f32 / avd_eps_untoken_ddim_audio_f32 -> (z_out, x0_hist)"""
+def _fused(dev, target, eps, z, tn, tp, state, guide, h, geom=None):
+    """avd_eps_unpatch_ddim_f32 / avd_eps_untoken_ddim_audio_f32 -> (z_out, x0_hist); geom: the tube (t, h, w) resp. the chunk
+    (len, stride), None = 2 x 4 x 4 resp. 4 / 4 (test_gpu_token_geometry passes the others)"""
     from multimodal_diffusion_amd import _lib as L, functional as Fn
     B = z.shape[0]
     eta = 0.7 if state in ("noise", "seeded") else 0.0
@@ -41,17 +42,21 @@ def _fused(dev, target, eps, z, tn, tp, state, guide, h):
     head = (eps.data_ptr(), z.data_ptr(), tn.data_ptr(), tp.data_ptr(), ab.data_ptr(), ab.numel(), eta, L.ptr(noise), out.data_ptr(), B)
     tail = (None if key is None else C.byref(key), L.ptr(tl), L.ptr(hist), None if guide is None else C.byref(guide), L.stream_ptr(dev))
     if target == "video":
-        L.check(L.lib().avd_eps_unpatch_ddim_f32(*head, *z.shape[1:], 2, 4, 4, *tail))
+        L.check(L.lib().avd_eps_unpatch_ddim_f32(*head, *z.shape[1:], *(geom or (2, 4, 4)), *tail))
     else:
-        L.check(L.lib().avd_eps_untoken_ddim_audio_f32(*head, z.shape[1], z.shape[2], 4, 4, *tail))
+        L.check(L.lib().avd_eps_untoken_ddim_audio_f32(*head, z.shape[1], z.shape[2], *(geom or (4, 4)), *tail))
     return out, hist
 
 
-def _composed(dev, target, eps, z, tn, tp, state, known, mask, h):
-    """tube_unpatch / audio_untokens, then ddim_step / dpmpp_2m_step, then latent_guide: the existing functional ops"""
+def _composed(dev, target, eps, z, tn, tp, state, known, mask, h, geom=None):
+    """tube_unpatch / audio_untokens, then ddim_step / dpmpp_2m_step, then latent_guide: the existing functional ops; geom as _fused"""
     from multimodal_diffusion_amd import functional as Fn
     B = z.shape[0]
-    lat = Fn.tube_unpatch(eps, *z.shape[1:], 2, 4, 4) if target == "video" else Fn.audio_untokens(eps, z.shape[1], 4, z.shape[2], 4)
+    if target == "video":
+        lat = Fn.tube_unpatch(eps, *z.shape[1:], *(geom or (2, 4, 4)))
+    else:
+        ln, st = geom or (4, 4)
+        lat = Fn.audio_untokens(eps, z.shape[1], ln, z.shape[2], st)
     hist = None
     if state in ("dpm1", "dpm2"):
         hist = h.clone()
@@ -74,25 +79,23 @@ GEOMS = [("video", (8, 4, 16, 32)), ("video", (8, 4, 16, 16)), ("video", (8, 4, 
 KCASES = [(t, lat, st, gd) for t, lat in GEOMS for st in STATES for gd in (False, True) if not (gd and st == "noise")]
 
 
-@pytest.mark.parametrize("target,lat,state,guided", KCASES)
-def test_kernels_equal_composed_ops(dev, cfg_rows, target, lat, state, guided):
+def _check_kernels_equal_composed(dev, cfg_rows, target, lat, state, guided, seed, n_tok, geom=None):
+    """the body of test_kernels_equal_composed_ops for one latent (lat, without the batch), its token count and its geometry (as
+    _fused); test_gpu_token_geometry runs it at the other geometries"""
     from multimodal_diffusion_amd import functional as Fn
     B = 3
-    g = torch.Generator().manual_seed(len(lat) * 100 + lat[-1])
+    g = torch.Generator().manual_seed(seed)
     z = torch.randn(B, *lat, generator=g).to(dev)
-    if target == "video":
-        eps = torch.randn(B, (lat[1] // 2) * (lat[2] // 4) * (lat[3] // 4), lat[0] * 32, generator=g).to(dev)
-    else:
-        eps = torch.randn(B, (lat[1] - 4) // 4 + 1, lat[0] * 4, generator=g).to(dev)
+    eps = torch.randn(B, *n_tok, generator=g).to(dev)
     known, h = torch.randn(z.shape, generator=g).to(dev), torch.randn(z.shape, generator=g).to(dev)
     mask = soft_mask(tuple(z.shape[1:])).to(dev)
     tn, tp = ts([981, 402, 40], dev), ts([961, 382, -1], dev)
     guide = Fn.latent_guide_desc(known, mask, GSEED, 4) if guided else None
-    ref, href = _composed(dev, target, eps, z, tn, tp, state, known if guided else None, mask, h)
+    ref, href = _composed(dev, target, eps, z, tn, tp, state, known if guided else None, mask, h, geom)
     outs = []
     for rows in ((1, 0) if target == "video" else (1,)):
         cfg_rows(rows)
-        out, hist = _fused(dev, target, eps, z, tn, tp, state, guide, h)
+        out, hist = _fused(dev, target, eps, z, tn, tp, state, guide, h, geom)
         assert torch.isfinite(out).all()
         assert torch.equal(out, ref), (rows, float((out - ref).abs().max()))
         if hist is not None:
@@ -100,6 +103,12 @@ def test_kernels_equal_composed_ops(dev, cfg_rows, target, lat, state, guided):
         outs.append(out)
     if len(outs) == 2:
         assert torch.equal(outs[0], outs[1])                   # rows form == gather form
+
+
+@pytest.mark.parametrize("target,lat,state,guided", KCASES)
+def test_kernels_equal_composed_ops(dev, cfg_rows, target, lat, state, guided):
+    n_tok = ((lat[1] // 2) * (lat[2] // 4) * (lat[3] // 4), lat[0] * 32) if target == "video" else ((lat[1] - 4) // 4 + 1, lat[0] * 4)
+    _check_kernels_equal_composed(dev, cfg_rows, target, lat, state, guided, len(lat) * 100 + lat[-1], n_tok)
 
 
 # ------------------------------------------------------------------------------------------------- 2. front end
