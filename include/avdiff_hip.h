@@ -144,7 +144,8 @@ int avd_ddim_step_f32(const float* x_t, const float* eps_hat, const int64_t* t_n
                       const float* alpha_bar, int T_train, float eta, const float* noise,
                       float* x_prev, int B, int64_t per_sample, avd_stream_t stream);
 
-/* ---- DPM-Solver++(2M) update (multistep, data prediction, eta == 0) — an opt-in alternative to DDIM (a public contract).
+/* ---- DPM-Solver++(2M) update (multistep, data prediction; this entry: eta == 0, the ODE solver; eta > 0: the SDE form below) — an
+ * opt-in alternative to DDIM (a public contract).
  * For a timestep tau: a(tau) = alpha_bar[clamp(tau, 0, T_train-1)] for tau >= 0 and a(-1) = 1;
  *   alpha = sqrt(a), sigma = sqrt(1 - a), lambda = log alpha - log sigma.
  * One step goes from s = t_now to t = t_prev; the step before it came from u = t_last (t_last < 0: no history).  Per element:
@@ -165,6 +166,33 @@ int avd_ddim_step_f32(const float* x_t, const float* eps_hat, const int64_t* t_n
 int avd_dpmpp_2m_step_f32(const float* x_t, const float* eps_hat, float* x0_hist, const int64_t* t_last, const int64_t* t_now,
                           const int64_t* t_prev, const float* alpha_bar, int T_train, float* x_out, int B, int64_t per_sample,
                           avd_stream_t stream);
+
+/* ---- SDE-DPM-Solver++(2M): the update above at eta > 0 (a public contract).  k-diffusion's "DPM++ 2M SDE" (midpoint) in VP form; at
+ * eta = 1 Lu et al.'s SDE-DPM-Solver++(2M).  Notation (a, alpha, sigma, lambda; s = t_now, t = t_prev, u = t_last) and x0_s (DDIM's
+ * fp32 x0) as above.  For eta > 0 the per-sample coefficients, in fp64 from the fp32 table and rounded once to fp32:
+ *        h   = lambda_t - lambda_s                         (+inf when sigma_t = 0)
+ *        c_x = (sigma_t / sigma_s) exp(-eta h)
+ *        k   = alpha_t (-expm1(-(1 + eta) h))
+ *        c_n = sigma_t sqrt(max(-expm1(-2 eta h), 0))
+ *        second order under exactly the ODE conditions (t_last >= 0, t_prev >= 0, sigma_t > 0, lambda_u < lambda_s < lambda_t):
+ *          r = (lambda_s - lambda_u) / h,  c_0 = k (1 + 1/(2r)),  c_1 = -k/(2r);   otherwise first order: c_0 = k, c_1 = 0;
+ *        sigma_s = 0: (c_x, c_0, c_1, c_n) = (0, 1, 0, 0);
+ *        sigma_t = 0 (the final step, or a_t == 1.0f): c_x = 0, c_0 = alpha_t, c_1 = 0, c_n = 0 — no exp(-inf), no 0 * inf: the step
+ *        returns x0_s bit for bit, as the ODE step does.
+ *   z_out = ((c_x x_s + c_0 x0_s) [+ c_1 x0_hist]) + c_n n in fp32, in that order, without contraction; the c_1 term is added, and
+ *   x0_hist read, only when c_1 != 0; the noise term is added only when eta > 0.  Then x0_hist <- x0_s.
+ * Its first-order step is DDIM at eta = 1 in exact arithmetic; at eta -> 0 the formulas reduce to the ODE ones, and eta == 0 itself
+ * evaluates the ODE expressions above (the same bits as avd_dpmpp_2m_step_f32; `noise` is not read).
+ * The noise n of the fused step is the DDIM stream below, with no tag of its own: key (seed, sample_offset + b, t_now[b], element)
+ * with tag 0x44444D31, or its canvas keying — a DDIM eta > 0 step and an SDE step with the same seed draw the same normals at the same
+ * (sample, t, element).  This entry takes n as an explicit tensor (what avd_gaussian_noise_f32 or avd_canvas_noise_f32 wrote, for
+ * instance): `noise` fp32 [B, per_sample], required when eta > 0.  Overlap rules as avd_dpmpp_2m_step_f32, and `noise` must not
+ * overlap x0_hist or x_out.
+ * Limits: the fused steps draw seeded noise only (no unseeded or explicit noise there); a latent guide's known noise stays keyed per
+ * sample under canvas keying. */
+int avd_dpmpp_2m_sde_step_f32(const float* x_t, const float* eps_hat, float* x0_hist, const int64_t* t_last, const int64_t* t_now,
+                              const int64_t* t_prev, const float* alpha_bar, int T_train, float eta, const float* noise, float* x_out,
+                              int B, int64_t per_sample, avd_stream_t stream);
 
 /* ---- seeded normal stream of the DDIM eta > 0 noise term (a public contract: the values are fixed by what follows).
  * For sample s = sample_offset + b of a launch, timestep t = t_now[b] and element e of that sample's latent in its natural layout
@@ -206,7 +234,8 @@ int avd_gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float
  * 16-byte aligned a lane's four values lie inside one (o, l) slice and come from one Philox call; otherwise (every audio latent:
  * inner = 1) one call per element.  Same bits either way, and the same bits from avd_canvas_noise_f32 and from the fused step.
  * A latent guide's known-noise stream (avd_latent_guide) keeps its per-sample keying (sample = key.sample_offset + b) under canvas
- * keying: canvas-keyed known noise is not implemented.  DPM-Solver++(2M) is eta == 0 only and has no canvas form. */
+ * keying: canvas-keyed known noise is not implemented.  DPM-Solver++(2M) at eta > 0 (avd_denoise_step_dpmpp_2m_sde_f32) draws the
+ * same canvas-keyed normals as the DDIM step; at eta == 0 it draws nothing. */
 /* out[b, o, l, i] = the canvas-keyed normal above; out: fp32 [N, outer, L, inner]; t_now: int64 [N].  Argument order as
  * avd_window_consensus_f32.  Its output can be passed as the explicit `noise` of the DDIM entries. */
 int avd_canvas_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int N, int64_t outer, int L, int hop,
@@ -540,7 +569,7 @@ int avd_denoise_step_seeded_f32(const avd_step_desc* s, const avd_noise_key* key
                                 void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 /* As avd_denoise_step_f32, ending in the DPM-Solver++(2M) update (avd_dpmpp_2m_step_f32) inside the fused CFG kernel instead of DDIM:
  * t_last: int64 [B] (< 0: first order); x0_hist: fp32 [B, per_sample] in the latent's natural layout, read by second-order steps and
- * overwritten with this step's x0.  Requires s->eta == 0 (the SDE variant is not implemented); x0_hist must not alias z or z_out.
+ * overwritten with this step's x0.  Requires s->eta == 0 (eta > 0: avd_denoise_step_dpmpp_2m_sde_f32); x0_hist must not alias z or z_out.
  * Graph-capturable: x0_hist stays at its address from step to step. */
 int avd_denoise_step_dpmpp_2m_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_last,
                                   const int64_t* t_now, const int64_t* t_prev, float* x0_hist, float* z_out,
@@ -580,12 +609,25 @@ int avd_denoise_step_cond_f32(const avd_step_desc* s, const avd_latent_guide* g,
  * avd_cfg_control, as avd_denoise_step_cfg_f32) and g (NULL or a latent guide, as avd_denoise_step_guided_f32; its known-noise stream
  * stays keyed per sample).  cond_only != 0: the cond-only step (as avd_denoise_step_cond_f32 with a key; ctl must be NULL).  Only the
  * draw inside the fused update differs from those entries: fed avd_canvas_noise_f32's output as explicit noise, avd_denoise_step_f32
- * returns the same bits.  No DPM-Solver++(2M) form (that solver is eta == 0 only), so no t_last / x0_hist.  Graph-capturable: seed,
- * sample_offset and hop are held by value. */
+ * returns the same bits.  This entry is the DDIM step: the canvas-keyed DPM-Solver++(2M) step is avd_denoise_step_dpmpp_2m_sde_f32 with
+ * canvas_hop != 0.  Graph-capturable: seed, sample_offset and hop are held by value. */
 int avd_denoise_step_canvas_f32(const avd_step_desc* s, const avd_noise_key* key, int hop, const avd_cfg_control* ctl,
                                 const avd_latent_guide* g, int cond_only, const float* z, const float* Xp,
                                 const int64_t* t_now, const int64_t* t_prev, float* z_out,
                                 void* workspace, int64_t workspace_bytes, avd_stream_t stream);
+
+/* The whole step ending in the SDE form of the DPM-Solver++(2M) update (avd_dpmpp_2m_sde_step_f32) inside the fused kernel, its noise
+ * drawn from the seeded stream: one entry for every kind of SDE step.  Requires s->eta > 0, key, t_last and x0_hist (as
+ * avd_denoise_step_dpmpp_2m_f32).  canvas_hop == 0: per-sample keying (as avd_denoise_step_seeded_f32); canvas_hop >= 1: the B samples
+ * are consecutive windows of one canvas and the draw is keyed by canvas position (as avd_denoise_step_canvas_f32, same range checks).
+ * cond_only == 0: the CFG step, with ctl (NULL or an avd_cfg_control) and g (NULL or a latent guide; its known-noise stream stays
+ * keyed per sample).  cond_only != 0: the cond-only step (ctl must be NULL).  All argument checks run before the model.  The
+ * workspace is the CFG step's (avd_step_workspace_bytes).  Unseeded or explicit noise is not supported here.  Graph-capturable: the
+ * key and canvas_hop are held by value, x0_hist stays at its address. */
+int avd_denoise_step_dpmpp_2m_sde_f32(const avd_step_desc* s, const avd_noise_key* key, int canvas_hop, const avd_cfg_control* ctl,
+                                      const avd_latent_guide* g, int cond_only, const int64_t* t_last, float* x0_hist,
+                                      const float* z, const float* Xp, const int64_t* t_now, const int64_t* t_prev, float* z_out,
+                                      void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 
 /* ---- a9 / next-1: VideoVAE.decode — avdiff/models/encoders/vae_video3d.py:195-214 (decode), :79-84
  * (_conv_block_3d: Conv3d 3x3x3 pad 1 -> GELU(erf) -> GroupNorm(min(8,C), eps 1e-5, affine)), :108-119.

@@ -145,6 +145,9 @@ SIGNATURES = {
     "avd_sched_advance_ms": (_I, [_P, _I, _P, _P, _P, _P, _I, _P]),
     "avd_dpmpp_2m_step_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _L, _P]),
     "avd_denoise_step_dpmpp_2m_f32": (_I, [C.POINTER(StepDesc), _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "avd_dpmpp_2m_sde_step_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _F, _P, _P, _I, _L, _P]),
+    "avd_denoise_step_dpmpp_2m_sde_f32": (_I, [C.POINTER(StepDesc), C.POINTER(NoiseKey), _I, C.POINTER(CfgControl), C.POINTER(LatentGuide),
+                                               _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "avd_latent_guide_f32": (_I, [C.POINTER(LatentGuide), _P, _P, _I, _P, _P, _I, _L, _P]),
     "avd_denoise_step_guided_f32": (_I, [C.POINTER(StepDesc), C.POINTER(LatentGuide), C.POINTER(NoiseKey), _P, _P, _P, _P, _P, _P, _P,
                                          _P, _L, _P]),

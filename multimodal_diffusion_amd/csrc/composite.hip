@@ -798,7 +798,8 @@ extern "C" int64_t avd_step_workspace_bytes(const avd_step_desc* s) {
 // noise from the seeded stream; x0_hist != nullptr ends the step with the DPM-Solver++(2M) update instead of DDIM; guide != nullptr
 // blends the known latent into the update's result (avd_denoise_step_guided_f32); ctl != nullptr applies the CFG control
 // (avd_denoise_step_cfg_f32: its statistics pass runs in the fused update's launcher, on st after the join of the two streams);
-// canvas_hop != 0 keys the seeded draw by canvas position (avd_denoise_step_canvas_f32)
+// canvas_hop != 0 keys the seeded draw by canvas position (avd_denoise_step_canvas_f32); key and x0_hist together at eta > 0 end the
+// step with the solver's SDE form (avd_denoise_step_dpmpp_2m_sde_f32)
 static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp, const int64_t* t_now,
                         const int64_t* t_prev, const float* noise, float* z_out, void* workspace, int64_t workspace_bytes,
                         avd_stream_t stream, const int64_t* t_last = nullptr, float* x0_hist = nullptr,
@@ -879,7 +880,8 @@ static int denoise_step_cond(const avd_step_desc* s, const avd_noise_key* key, c
 // The option checks the step entries share, made here as well as in the fused update's launcher: before the model runs, and for both
 // targets.  need: what this entry cannot do without; a guide, a control or a key it merely accepts is checked when present.  `noise`
 // is the unseeded noise tensor of the one entry that takes one (avd_denoise_step_cond_f32), nullptr from the others.
-enum { NEED_KEY = 1, NEED_HIST = 2, NEED_GUIDE = 4, NEED_CTL = 8 };
+// TAKES_SDE: the entry runs the DPM-Solver++(2M) update at eta > 0 (its SDE form); every other entry refuses x0_hist with eta > 0.
+enum { NEED_KEY = 1, NEED_HIST = 2, NEED_GUIDE = 4, NEED_CTL = 8, TAKES_SDE = 16 };
 static int check_step_options(const char* what, int need, const avd_step_desc* s, const avd_noise_key* key, const int64_t* t_last,
                               const float* x0_hist, const float* z, const float* z_out, const avd_latent_guide* g,
                               const avd_cfg_control* ctl, const float* noise, bool takes_noise = false) {
@@ -893,7 +895,8 @@ static int check_step_options(const char* what, int need, const avd_step_desc* s
     AVD_REQUIRE(!(need & NEED_HIST) || (t_last && x0_hist), AVD_EINVAL, "%s: null t_last or x0_hist", what);
     AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "%s: t_last and x0_hist go together (the DPM-Solver++(2M) update)", what);
     if (x0_hist) {
-        AVD_REQUIRE(s->eta == 0.f, AVD_EINVAL, "%s: DPM-Solver++(2M) needs eta == 0 (the SDE variant is not implemented)", what);
+        AVD_REQUIRE(s->eta == 0.f || (need & TAKES_SDE), AVD_EINVAL,
+                    "%s: DPM-Solver++(2M) needs eta == 0 here (eta > 0 is avd_denoise_step_dpmpp_2m_sde_f32)", what);
         AVD_REQUIRE(!(z && overlaps(x0_hist, z, n)) && !(z_out && overlaps(x0_hist, z_out, n)), AVD_EINVAL,
                     "%s: x0_hist must not alias z or z_out", what);
     }
@@ -969,6 +972,31 @@ extern "C" int avd_denoise_step_canvas_f32(const avd_step_desc* s, const avd_noi
     if (cond_only)
         return denoise_step_cond(s, key, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, nullptr, nullptr, g, hop);
     return denoise_step(s, key, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, nullptr, nullptr, g, ctl, hop);
+}
+
+// The SDE form of the DPM-Solver++(2M) step (eta > 0, seeded noise only): the CFG step (with an optional control and guide) or, with
+// cond_only, the single-branch step; canvas_hop != 0 keys the noise by canvas position.  Only the fused update differs from the ODE step.
+extern "C" int avd_denoise_step_dpmpp_2m_sde_f32(const avd_step_desc* s, const avd_noise_key* key, int canvas_hop,
+                                                 const avd_cfg_control* ctl, const avd_latent_guide* g, int cond_only,
+                                                 const int64_t* t_last, float* x0_hist, const float* z, const float* Xp,
+                                                 const int64_t* t_now, const int64_t* t_prev, float* z_out, void* workspace,
+                                                 int64_t workspace_bytes, avd_stream_t stream) {
+    AVD_REQUIRE(s, AVD_EINVAL, "denoise_step_dpmpp_2m_sde: null descriptor");
+    AVD_REQUIRE(s->eta > 0.f, AVD_EINVAL, "denoise_step_dpmpp_2m_sde: the SDE form needs eta > 0 (eta is %g: avd_denoise_step_dpmpp_2m_f32)",
+                (double)s->eta);
+    AVD_REQUIRE(key, AVD_EINVAL, "denoise_step_dpmpp_2m_sde: null noise key (the SDE form draws seeded noise only)");
+    AVD_REQUIRE(t_last && x0_hist, AVD_EINVAL, "denoise_step_dpmpp_2m_sde: null t_last or x0_hist");
+    AVD_REQUIRE(!(cond_only && ctl), AVD_EINVAL, "denoise_step_dpmpp_2m_sde: a cond-only step takes no CFG control");
+    AVD_REQUIRE(canvas_hop >= 0, AVD_EINVAL, "denoise_step_dpmpp_2m_sde: canvas_hop must be >= 0 (0: per-sample keying), got %d", canvas_hop);
+    const avd_embed_desc& e = s->embed;
+    if (canvas_hop)
+        if (int rc = check_canvas_key(key, e.B, e.C, e.T, canvas_hop, (int64_t)e.H * e.W)) return rc;
+    if (int rc = check_step_options("denoise_step_dpmpp_2m_sde", NEED_KEY | NEED_HIST | TAKES_SDE, s, key, t_last, x0_hist, z, z_out, g, ctl,
+                                    nullptr)) return rc;
+    if (cond_only)
+        return denoise_step_cond(s, key, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, g,
+                                 canvas_hop);
+    return denoise_step(s, key, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, g, ctl, canvas_hop);
 }
 
 extern "C" int avd_prof_enable(int on) {

@@ -216,6 +216,8 @@ __device__ __forceinline__ Ddim ddim_coef(const int64_t* t_now, const int64_t* t
 // sample_clip.py:381), and hipcc's default -ffp-contract=fast picks its fused multiply-adds per CALL SITE — the same expression came out one
 // ulp apart in two kernels of this file (round 5: the whole-line CFG kernel against the gather form; round 4 met the same in split8).
 // ddim_x0 is also the x0 of the DPM-Solver++(2M) update below: one expression, one rounding, the same bits in both solvers.
+// It reads sqrt_omb_t and den alone, which do not depend on eta: the fused SDE kernels take them from ddim_coef(..., eta, b), the
+// elementwise DPM kernels from ddim_coef(..., 0.f, b), and both get the same x0.  A Ddim member that ddim_x0 reads must stay free of eta.
 __device__ __forceinline__ float ddim_x0(const Ddim& c, float x, float e) {
 #pragma clang fp contract(off)
     return (x - c.sqrt_omb_t * e) / c.den;
@@ -230,13 +232,15 @@ __device__ __forceinline__ float cfg_combine(float e_cond, float e_null, float g
     return e_null + guidance * (e_cond - e_null);
 }
 
-// ------------------------------------------------------------------ DPM-Solver++(2M) (data prediction, multistep, eta == 0)
-// The contract is written out in include/avdiff_hip.h (avd_dpmpp_2m_step_f32).  One step s = t_now -> t = t_prev with the previous
-// step's u = t_last (< 0: no history):  z_out = (c_x x_s + c_0 x0_s) + c_1 x0_hist,  then x0_hist <- x0_s.  The coefficients come
-// from the fp32 table in fp64 and are rounded once to fp32, so every form of the update (the elementwise kernel, the three fused CFG
-// kernels) and the numpy mirror of the tests agree on them bit for bit.
+// ------------------------------------------------------------------ DPM-Solver++(2M) (data prediction, multistep; eta > 0: its SDE form)
+// The contract is written out in include/avdiff_hip.h (avd_dpmpp_2m_step_f32, avd_dpmpp_2m_sde_step_f32).  One step s = t_now -> t =
+// t_prev with the previous step's u = t_last (< 0: no history):  z_out = ((c_x x_s + c_0 x0_s) + c_1 x0_hist) + c_n n,  then
+// x0_hist <- x0_s; the noise term exists at eta > 0 only.  The coefficients come from the fp32 table in fp64 and are rounded once to
+// fp32, so every form of the update (the elementwise kernels, the three fused CFG kernels) and the numpy mirror of the tests agree
+// on them bit for bit.
 struct Dpm {
     float c_x, c_0, c_1;     // c_1 == 0: first order (x0_hist is not read)
+    float c_n;               // the noise term's weight (eta > 0; 0 at eta == 0, on the final step and at equal lambdas)
 };
 
 // a(tau) of the contract: alpha_bar[clamp(tau, 0, T-1)] for tau >= 0, 1 for tau < 0
@@ -244,8 +248,9 @@ __device__ __forceinline__ float dpm_abar(const float* abar, int T_train, long l
     return tau < 0 ? 1.0f : abar[tau > T_train - 1 ? T_train - 1 : tau];
 }
 
+// eta == 0 keeps the ODE expressions (and their bits); eta > 0 takes the exponential forms of the SDE contract
 __device__ __forceinline__ Dpm dpm_coef(const int64_t* t_last, const int64_t* t_now, const int64_t* t_prev, const float* abar,
-                                        int T_train, int b) {
+                                        int T_train, float eta, int b) {
 #pragma clang fp contract(off)
     const long long tu = t_last[b], tp = t_prev[b];
     long long ts = t_now[b];
@@ -253,7 +258,26 @@ __device__ __forceinline__ Dpm dpm_coef(const int64_t* t_last, const int64_t* t_
     const double as = (double)dpm_abar(abar, T_train, ts), at = (double)dpm_abar(abar, T_train, tp);
     const double al_s = sqrt(as), sg_s = sqrt(fmax(1.0 - as, 0.0));
     const double al_t = sqrt(at), sg_t = sqrt(fmax(1.0 - at, 0.0));
-    if (sg_s == 0.0) return Dpm{0.f, 1.f, 0.f};         // a_s == 1: x_s is x0_s, return it
+    if (sg_s == 0.0) return Dpm{0.f, 1.f, 0.f, 0.f};    // a_s == 1: x_s is x0_s, return it
+    if (eta > 0.f) {
+        if (sg_t == 0.0) return Dpm{0.f, (float)al_t, 0.f, 0.f};      // h = +inf (the final step, or a_t == 1): x0_s, no noise
+        const double et = (double)eta;
+        const double ls = log(al_s) - log(sg_s), lt = log(al_t) - log(sg_t), h = lt - ls;
+        const double cx = (sg_t / sg_s) * exp(-et * h);
+        const double k = al_t * (-expm1(-(1.0 + et) * h));
+        const double cn = sg_t * sqrt(fmax(-expm1(-2.0 * et * h), 0.0));
+        double c0 = k, c1 = 0.0;
+        if (tu >= 0 && tp >= 0) {                        // second order: the conditions of the ODE form below
+            const double au = (double)dpm_abar(abar, T_train, tu);
+            const double lu = log(sqrt(au)) - log(sqrt(fmax(1.0 - au, 0.0)));
+            if (lu < ls && ls < lt) {
+                const double r = (ls - lu) / h;
+                c0 = k * (1.0 + 1.0 / (2.0 * r));
+                c1 = -k / (2.0 * r);
+            }
+        }
+        return Dpm{(float)cx, (float)c0, (float)c1, (float)cn};
+    }
     const double cx = sg_t / sg_s;
     const double k = al_t - cx * al_s;
     double c0 = k, c1 = 0.0;
@@ -268,22 +292,24 @@ __device__ __forceinline__ Dpm dpm_coef(const int64_t* t_last, const int64_t* t_
             c1 = -k / (2.0 * r);
         }
     }
-    return Dpm{(float)cx, (float)c0, (float)c1};
+    return Dpm{(float)cx, (float)c0, (float)c1, 0.f};
 }
 
-__device__ __forceinline__ float dpm_apply(const Dpm& c, float x, float x0, float hist) {
+// noisy: eta > 0, the noise term c_n zn ends the update (false: zn is not read, the ODE update as it was)
+__device__ __forceinline__ float dpm_apply(const Dpm& c, float x, float x0, float hist, float zn, bool noisy) {
 #pragma clang fp contract(off)
     const float y = c.c_x * x + c.c_0 * x0;
-    return c.c_1 != 0.f ? y + c.c_1 * hist : y;
+    const float y2 = c.c_1 != 0.f ? y + c.c_1 * hist : y;
+    return noisy ? y2 + c.c_n * zn : y2;
 }
 
 // The fused CFG kernels below take the solver's state as their trailing parameter pack: empty (DDIM, the instantiations that
-// existed before the solver, unchanged), NoiseKey (seeded DDIM noise) or DpmState (this solver).
+// existed before the solver, unchanged), NoiseKey (seeded DDIM noise), DpmState (this solver) or DpmState with a key (its SDE form).
 struct DpmState {
     const int64_t* t_last;   // int64 [B]
     float* x0_hist;          // [B, per] in the latent's natural layout: read (second-order steps), then overwritten with x0_s
 };
-// the trailing pack holds at most one solver state (NoiseKey or DpmState), then optionally a GuideState (the latent guide below)
+// the trailing pack holds the solver state (a DpmState, a key, or a DpmState then a key), then optionally a GuideState (the latent guide below)
 // A CondOnly tag ending the pack selects the single-branch form of the fused kernels (a cond-only step of a guidance interval): eps2 is
 // then eps1 = [B, Nt, D], the conditional prediction alone; the null rows are not loaded, nothing is combined, `guidance` and `B` are
 // not read.  It excludes a CfgState (per-sample guidance and rescale act on the combine: with y = c the rescale is the identity).
@@ -291,13 +317,14 @@ struct CondOnly {};
 template <class T, class... X> struct PackHas { static constexpr bool value = (std::is_same<T, X>::value || ...); };
 struct GuideState;
 struct CfgState;
-// a well-formed pack: one key (SEEDED: a NoiseKey, or a CanvasKey for the canvas-keyed draw) or one DpmState, or nothing; then optionally one GuideState, then optionally one CfgState or CondOnly
+// a well-formed pack: optionally one DpmState; one key exactly when SEEDED (a NoiseKey, or a CanvasKey for the canvas-keyed draw: seeded
+// DDIM noise, or with the DpmState the SDE form's noise); then optionally one GuideState, then optionally one CfgState or CondOnly
 struct NoiseKey;
 struct CanvasKey;
 template <bool SEEDED, class... X> struct PackOk {
     template <class T> static constexpr int n = PackHas<T, X...>::value ? 1 : 0;
     static constexpr bool value = sizeof...(X) == (SEEDED ? 1 : 0) + n<DpmState> + n<GuideState> + n<CfgState> + n<CondOnly> &&
-                                  !(SEEDED && n<DpmState>) && !(n<CfgState> && n<CondOnly>) &&
+                                  !(n<CfgState> && n<CondOnly>) &&
                                   n<NoiseKey> + n<CanvasKey> == (SEEDED ? 1 : 0);
 };
 template <class T, class A, class... R> __device__ __forceinline__ T pack_get(const A& a, const R&... r) {
@@ -486,9 +513,27 @@ __global__ __launch_bounds__(256) void dpmpp_2m_kernel(const float* __restrict__
     if (i >= total) return;
     const int b = (int)(i / per);
     const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, 0.f, b);
-    const Dpm d = dpm_coef(t_last, t_now, t_prev, abar, T_train, b);
+    const Dpm d = dpm_coef(t_last, t_now, t_prev, abar, T_train, 0.f, b);
     const float x0 = ddim_x0(c, x[i], eps[i]);
-    out[i] = dpm_apply(d, x[i], x0, d.c_1 != 0.f ? x0_hist[i] : 0.f);
+    out[i] = dpm_apply(d, x[i], x0, d.c_1 != 0.f ? x0_hist[i] : 0.f, 0.f, false);
+    x0_hist[i] = x0;
+}
+
+// the SDE form on explicit noise (read at eta > 0 only); at eta == 0 the arithmetic of dpmpp_2m_kernel
+__global__ __launch_bounds__(256) void dpmpp_2m_sde_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                                           float* __restrict__ x0_hist, const int64_t* __restrict__ t_last,
+                                                           const int64_t* __restrict__ t_now, const int64_t* __restrict__ t_prev,
+                                                           const float* __restrict__ abar, int T_train, float eta,
+                                                           const float* __restrict__ noise, float* __restrict__ out, int64_t per,
+                                                           int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int b = (int)(i / per);
+    const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, 0.f, b);
+    const Dpm d = dpm_coef(t_last, t_now, t_prev, abar, T_train, eta, b);
+    const float x0 = ddim_x0(c, x[i], eps[i]);
+    const bool noisy = eta > 0.f;
+    out[i] = dpm_apply(d, x[i], x0, d.c_1 != 0.f ? x0_hist[i] : 0.f, noisy ? noise[i] : 0.f, noisy);
     x0_hist[i] = x0;
 }
 
@@ -504,6 +549,26 @@ int dpmpp_2m_step_f32(const float* x_t, const float* eps, float* x0_hist, const 
     hipLaunchKernelGGL(dpmpp_2m_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x_t, eps, x0_hist, t_last, t_now,
                        t_prev, abar, T_train, x_out, per, total);
     AVD_CHECK_LAUNCH("dpmpp_2m_step");
+    return AVD_OK;
+}
+
+int dpmpp_2m_sde_step_f32(const float* x_t, const float* eps, float* x0_hist, const int64_t* t_last, const int64_t* t_now,
+                          const int64_t* t_prev, const float* abar, int T_train, float eta, const float* noise, float* x_out, int B,
+                          int64_t per, hipStream_t st) {
+    AVD_REQUIRE(x_t && eps && x0_hist && t_last && t_now && t_prev && abar && x_out, AVD_EINVAL, "dpmpp_2m_sde_step: null pointer");
+    AVD_REQUIRE(B > 0 && per > 0 && T_train > 0, AVD_EINVAL, "dpmpp_2m_sde_step: bad dims");
+    AVD_REQUIRE(eta >= 0.f, AVD_EINVAL, "dpmpp_2m_sde_step: eta must be >= 0");
+    AVD_REQUIRE(eta == 0.f || noise != nullptr, AVD_EINVAL, "dpmpp_2m_sde_step: eta > 0 needs a noise tensor");
+    const int64_t total = (int64_t)B * per;
+    AVD_REQUIRE(!overlaps(x0_hist, x_t, total) && !overlaps(x0_hist, eps, total) && !overlaps(x0_hist, x_out, total), AVD_EINVAL,
+                "dpmpp_2m_sde_step: x0_hist must not overlap x_t, eps_hat or x_out");
+    AVD_REQUIRE(eta == 0.f || (!overlaps(noise, x0_hist, total) && !overlaps(noise, x_out, total)), AVD_EINVAL,
+                "dpmpp_2m_sde_step: noise must not overlap x0_hist or x_out");
+    AVD_REQUIRE((total + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "dpmpp_2m_sde_step: %lld values is too many for one launch",
+                (long long)total);
+    hipLaunchKernelGGL(dpmpp_2m_sde_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x_t, eps, x0_hist, t_last, t_now,
+                       t_prev, abar, T_train, eta, noise, x_out, per, total);
+    AVD_CHECK_LAUNCH("dpmpp_2m_sde_step");
     return AVD_OK;
 }
 
@@ -844,7 +909,8 @@ int g_cfg_rows = 1;      // avd_tune_set "cfg_rows": 0 = the 16-bytes-per-lane g
 // hidden arguments such as blockDim sit right behind the explicit ones) and compile to the same code as before the stream existed.
 // A CanvasKey in the key's place (SEEDED true) draws zn by canvas position instead (canvas_normal4): one more compile-time case, the
 // instantiations with a NoiseKey are untouched.
-// A DpmState in the pack (SEEDED false) replaces the DDIM update by the DPM-Solver++(2M) one (dpm_coef / dpm_apply) on the same x0.
+// A DpmState in the pack replaces the DDIM update by the DPM-Solver++(2M) one (dpm_coef / dpm_apply) on the same x0: alone (SEEDED false)
+// the ODE update; followed by a key (SEEDED true, eta > 0) the SDE form, whose noise term is the same zn the DDIM step would draw.
 template <bool SEEDED, class... Key>
 __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const float* __restrict__ eps2, const float* __restrict__ z, const int64_t* __restrict__ t_now,
@@ -873,7 +939,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
         zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, r / g.T, (int)(r % g.T), (e4 % hw4) * 4, hw4 * 4, (uint32_t)t_now[b]);
     } else if constexpr (SEEDED) {
         NoiseKey k;      // a one-item pack is copied as before the guide existed: through pack_get its argument loads reorder
-        if constexpr (GUIDED || CTL || COND) k = pack_get<NoiseKey>(nk...);
+        if constexpr (GUIDED || CTL || COND || DPM) k = pack_get<NoiseKey>(nk...);
         else k = NoiseKey(nk...);
         zn = philox_normal4(k, (uint32_t)e4, k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
     } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
@@ -881,13 +947,13 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     f32x4 o;
     if constexpr (DPM) {
         const DpmState ds = pack_get<DpmState>(nk...);
-        const Dpm d = dpm_coef(ds.t_last, t_now, t_prev, abar, T_train, b);
+        const Dpm d = dpm_coef(ds.t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, b);
         f32x4 hist = {0.f, 0.f, 0.f, 0.f}, x0;
         if (d.c_1 != 0.f) hist = *reinterpret_cast<const f32x4*>(ds.x0_hist + lat);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             x0[k] = ddim_x0(c, x[k], cfg_eps<CTL, COND>(ec[k], en[k], guidance, cc));
-            o[k] = dpm_apply(d, x[k], x0[k], hist[k]);
+            o[k] = dpm_apply(d, x[k], x0[k], hist[k], zn[k], SEEDED);
         }
         *reinterpret_cast<f32x4*>(ds.x0_hist + lat) = x0;
     } else {
@@ -937,8 +1003,8 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     }
     __syncthreads();
     const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, eta, b);
-    [[maybe_unused]] Dpm d{0.f, 0.f, 0.f};
-    if constexpr (DPM) d = dpm_coef(pack_get<DpmState>(nk...).t_last, t_now, t_prev, abar, T_train, b);
+    [[maybe_unused]] Dpm d{0.f, 0.f, 0.f, 0.f};
+    if constexpr (DPM) d = dpm_coef(pack_get<DpmState>(nk...).t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, b);
     [[maybe_unused]] GuideCoef gc{0.f, 0.f, false};
     if constexpr (GUIDED) gc = guide_coef(abar, T_train, t_prev[b]);
     // token coordinates of the group: n = (t' Ht + h') Wt + w'
@@ -953,6 +1019,18 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         const int64_t lat = (int64_t)b * g.per + (((int64_t)cc * g.T + (tq * g.t + tt)) * g.H + (hq * g.h + hh)) * g.W + (wq + tok) * g.w + wo;
         const f32x4 x = *reinterpret_cast<const f32x4*>(z + lat);
         f32x4 o;
+        [[maybe_unused]] f32x4 zn = {0.f, 0.f, 0.f, 0.f};      // the unkeyed DPM update (eta == 0) draws nothing
+        if constexpr (CANVAS) {      // element (c, t, h, w) of window b: canvas position from t, element (c, h W + w) of its slice
+            zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, cc, tq * g.t + tt, (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo,
+                                (int64_t)g.H * g.W, (uint32_t)t_now[b]);
+        } else if constexpr (SEEDED) {
+            NoiseKey k;      // as in cfg_unpatch_ddim_kernel
+            if constexpr (GUIDED || CTL || COND || DPM) k = pack_get<NoiseKey>(nk...);
+            else k = NoiseKey(nk...);
+            zn = philox_normal4(k, (uint32_t)((lat - (int64_t)b * g.per) >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
+        } else if constexpr (!DPM) {
+            if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
+        }
         if constexpr (DPM) {
             const DpmState ds = pack_get<DpmState>(nk...);
             f32x4 hist = {0.f, 0.f, 0.f, 0.f}, x0;
@@ -960,20 +1038,10 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 x0[k] = ddim_x0(c, x[k], e[k]);
-                o[k] = dpm_apply(d, x[k], x0[k], hist[k]);
+                o[k] = dpm_apply(d, x[k], x0[k], hist[k], zn[k], SEEDED);
             }
             *reinterpret_cast<f32x4*>(ds.x0_hist + lat) = x0;
         } else {
-            f32x4 zn = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (CANVAS) {      // element (c, t, h, w) of window b: canvas position from t, element (c, h W + w) of its slice
-                zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, cc, tq * g.t + tt, (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo,
-                                    (int64_t)g.H * g.W, (uint32_t)t_now[b]);
-            } else if constexpr (SEEDED) {
-                NoiseKey k;      // as in cfg_unpatch_ddim_kernel
-                if constexpr (GUIDED || CTL || COND) k = pack_get<NoiseKey>(nk...);
-                else k = NoiseKey(nk...);
-                zn = philox_normal4(k, (uint32_t)((lat - (int64_t)b * g.per) >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
-            } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
 #pragma unroll
             for (int k = 0; k < 4; ++k) o[k] = ddim_apply(c, x[k], e[k], zn[k]);
         }
@@ -1006,10 +1074,11 @@ struct UpdateKeys {
 
 // The checks the four launchers share, all before any HIP call.  per: the values of one sample's latent.
 // key != nullptr with eta > 0: the noise term is drawn from the seeded stream inside the kernel (`noise` is not read); eta == 0 ignores both
-// x0_hist != nullptr: the DPM-Solver++(2M) update (needs eta == 0 and t_last) instead of DDIM; x0_hist must not overlap z or z_out
+// x0_hist != nullptr: the DPM-Solver++(2M) update (needs t_last; at eta > 0 its SDE form, which needs key) instead of DDIM; x0_hist must
+// not overlap z or z_out
 // guide != nullptr: the latent guide's blend ends the update (after either solver), right before z_out is stored
 // ctl != nullptr: per-sample guidance and / or rescale (avd_cfg_control); with rescale set the launcher runs the statistics pass first
-// cv != nullptr: the batch is windows of one canvas and the seeded draw is keyed by canvas position (needs key and eta > 0, no DPM)
+// cv != nullptr: the batch is windows of one canvas and the seeded draw is keyed by canvas position (needs key and eta > 0)
 struct CanvasDims {
     int64_t outer;
     int L, hop;
@@ -1026,14 +1095,15 @@ static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per
     k.dpm = x0_hist != nullptr;
     k.ds = DpmState{t_last, x0_hist};
     if (k.dpm) {
-        AVD_REQUIRE(a.eta == 0.f, AVD_EINVAL, "%s: the DPM-Solver++(2M) update needs eta == 0", what);
+        AVD_REQUIRE(a.eta == 0.f || (key && !a.noise), AVD_EINVAL,
+                    "%s: the DPM-Solver++(2M) update with eta > 0 draws its noise from a noise key (no unseeded or explicit noise)", what);
         AVD_REQUIRE(!overlaps(x0_hist, a.z, a.B * per) && !overlaps(x0_hist, a.z_out, a.B * per), AVD_EINVAL,
                     "%s: x0_hist must not overlap z or z_out", what);
     }
     k.seeded = key && a.eta > 0.f;
     k.canvas = cv != nullptr;
     if (cv) {
-        AVD_REQUIRE(k.seeded && !k.dpm, AVD_EINVAL, "%s: the canvas-keyed draw is the seeded eta > 0 DDIM step (needs a noise key and eta > 0)", what);
+        AVD_REQUIRE(k.seeded, AVD_EINVAL, "%s: the canvas-keyed draw is a seeded eta > 0 step (needs a noise key and eta > 0)", what);
         if (int rc = make_canvas_key(key, a.B, cv->outer, cv->L, cv->hop, cv->inner, k.ck)) return rc;
     } else if (k.seeded) {
         if (int rc = make_noise_key(key, a.B, k.nk)) return rc;
@@ -1051,7 +1121,8 @@ static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per
 }
 
 // Calls launch(pack...) with the kernels' whole trailing pack: the solver's state (DpmState, the NoiseKey of a seeded eta > 0 step or
-// the CanvasKey of a canvas-keyed one, or nothing), then the guide if there is one, then the CFG control if there is one or, for the single-branch form, the CondOnly tag.
+// the CanvasKey of a canvas-keyed one, DpmState then that key for the SDE form, or nothing), then the guide if there is one, then the
+// CFG control if there is one or, for the single-branch form, the CondOnly tag.
 template <class F>
 static void with_update_pack(const UpdateKeys& k, bool cond_only, F launch) {
     auto tail = [&](auto... state) {
@@ -1062,7 +1133,9 @@ static void with_update_pack(const UpdateKeys& k, bool cond_only, F launch) {
         else if (k.ctl) launch(state..., k.cs);
         else launch(state...);
     };
-    if (k.dpm) tail(k.ds);
+    if (k.dpm && k.seeded && k.canvas) tail(k.ds, k.ck);
+    else if (k.dpm && k.seeded) tail(k.ds, k.nk);
+    else if (k.dpm) tail(k.ds);
     else if (k.seeded && k.canvas) tail(k.ck);
     else if (k.seeded) tail(k.nk);
     else tail();
@@ -1185,22 +1258,24 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
         else
             return v;
     };
-    if constexpr (DPM) {
-        const DpmState ds = pack_get<DpmState>(nk...);
-        const Dpm d = dpm_coef(ds.t_last, t_now, t_prev, abar, T_train, b);
-        const float x = z[i], x0 = ddim_x0(cf, x, e);
-        z_out[i] = fin(dpm_apply(d, x, x0, d.c_1 != 0.f ? ds.x0_hist[i] : 0.f));
-        ds.x0_hist[i] = x0;
-    } else if constexpr (CANVAS) {      // element (c, f) of window b: canvas position from f, element c of its slice (inner == 1)
-        const f32x4 zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, c, f, 0, 1, (uint32_t)t_now[b]);
-        z_out[i] = fin(ddim_apply(cf, z[i], e, zn[c & 3]));
+    [[maybe_unused]] float zn = 0.f;      // the unkeyed DPM update (eta == 0) draws nothing
+    if constexpr (CANVAS) {      // element (c, f) of window b: canvas position from f, element c of its slice (inner == 1)
+        zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, c, f, 0, 1, (uint32_t)t_now[b])[c & 3];
     } else if constexpr (SEEDED) {
         NoiseKey k;      // as in cfg_unpatch_ddim_kernel
-        if constexpr (GUIDED || CTL || COND) k = pack_get<NoiseKey>(nk...);
+        if constexpr (GUIDED || CTL || COND || DPM) k = pack_get<NoiseKey>(nk...);
         else k = NoiseKey(nk...);
         const int64_t el = i - (int64_t)b * Ca * F;
-        const f32x4 zn = philox_normal4(k, (uint32_t)(el >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
-        z_out[i] = fin(ddim_apply(cf, z[i], e, zn[(int)(el & 3)]));
+        zn = philox_normal4(k, (uint32_t)(el >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b])[(int)(el & 3)];
+    }
+    if constexpr (DPM) {
+        const DpmState ds = pack_get<DpmState>(nk...);
+        const Dpm d = dpm_coef(ds.t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, b);
+        const float x = z[i], x0 = ddim_x0(cf, x, e);
+        z_out[i] = fin(dpm_apply(d, x, x0, d.c_1 != 0.f ? ds.x0_hist[i] : 0.f, zn, SEEDED));
+        ds.x0_hist[i] = x0;
+    } else if constexpr (SEEDED) {
+        z_out[i] = fin(ddim_apply(cf, z[i], e, zn));
     } else {
         z_out[i] = fin(ddim_apply(cf, z[i], e, eta > 0.f ? noise[i] : 0.f));
     }
@@ -1585,6 +1660,12 @@ extern "C" int avd_dpmpp_2m_step_f32(const float* x_t, const float* eps_hat, flo
                                      int B, int64_t per_sample, avd_stream_t stream) {
     return dpmpp_2m_step_f32(x_t, eps_hat, x0_hist, t_last, t_now, t_prev, alpha_bar, T_train, x_out, B, per_sample,
                              static_cast<hipStream_t>(stream));
+}
+extern "C" int avd_dpmpp_2m_sde_step_f32(const float* x_t, const float* eps_hat, float* x0_hist, const int64_t* t_last,
+                                         const int64_t* t_now, const int64_t* t_prev, const float* alpha_bar, int T_train, float eta,
+                                         const float* noise, float* x_out, int B, int64_t per_sample, avd_stream_t stream) {
+    return dpmpp_2m_sde_step_f32(x_t, eps_hat, x0_hist, t_last, t_now, t_prev, alpha_bar, T_train, eta, noise, x_out, B, per_sample,
+                                 static_cast<hipStream_t>(stream));
 }
 extern "C" int64_t avd_cfg_stats_bytes(int B, int64_t per_sample) { return cfg_stats_bytes(B, per_sample); }
 extern "C" int avd_cfg_rescale_f32(const float* e_cond, const float* e_cfg, const float* phi, void* stats, int64_t stats_bytes, float* out,

@@ -224,6 +224,37 @@ def dpmpp_2m_step(x_t: Tensor, eps_hat: Tensor, x0_hist: Tensor, t_last: Tensor,
     return out
 
 
+def dpmpp_2m_sde_step(x_t: Tensor, eps_hat: Tensor, x0_hist: Tensor, t_last: Tensor, t_now: Tensor, t_prev: Tensor,
+                      alpha_bar: Tensor, eta: float, noise: Optional[Tensor] = None) -> Tensor:
+    """One SDE-DPM-Solver++(2M) update (avd_dpmpp_2m_sde_step_f32; contract in include/avdiff_hip.h): ``dpmpp_2m_step`` with the
+    exponential coefficients of ``eta`` > 0 and the noise term c_n * ``noise``.  ``noise`` (float32, the shape of x_t, not overlapping
+    x0_hist) is explicit and required when eta > 0 — ``gaussian_noise`` / ``canvas_noise`` give the normals the fused step draws; at
+    eta == 0 it is not read and the result has the bits of ``dpmpp_2m_step``."""
+    x_t = L.dev_f32(x_t, "x_t")
+    eps_hat = L.dev_f32(eps_hat, "eps_hat")
+    if eps_hat.shape != x_t.shape:
+        raise RuntimeError("eps_hat must have the shape of x_t")
+    if not (x0_hist.is_cuda and x0_hist.dtype == torch.float32 and x0_hist.is_contiguous() and x0_hist.shape == x_t.shape):
+        raise RuntimeError("x0_hist must be a contiguous float32 device tensor of x_t's shape (it is updated in place)")
+    if eta > 0.0 and noise is None:
+        raise ValueError("dpmpp_2m_sde_step: eta > 0 needs `noise` (gaussian_noise / canvas_noise give the seeded stream's normals)")
+    nz = None if noise is None else L.dev_f32(noise, "noise")
+    if nz is not None and nz.shape != x_t.shape:
+        raise RuntimeError("noise must have the shape of x_t")
+    dev = x_t.device
+    ab = alpha_bar if (alpha_bar.is_cuda and alpha_bar.dtype == torch.float32) else alpha_bar.to(dev, torch.float32)
+    ab = ab.contiguous()
+    tl, tn, tp = L.dev_i64(t_last, dev), L.dev_i64(t_now, dev), L.dev_i64(t_prev, dev)
+    B = x_t.shape[0]
+    if tl.numel() != B or tn.numel() != B or tp.numel() != B:
+        raise RuntimeError("t_last / t_now / t_prev must have one entry per sample")
+    out = torch.empty_like(x_t)
+    L.check(L.lib().avd_dpmpp_2m_sde_step_f32(x_t.data_ptr(), eps_hat.data_ptr(), x0_hist.data_ptr(), tl.data_ptr(), tn.data_ptr(),
+                                              tp.data_ptr(), ab.data_ptr(), ab.numel(), float(eta), L.ptr(nz), out.data_ptr(), B,
+                                              x_t.numel() // B, _st(x_t)))
+    return out
+
+
 def noise_key(seed: int, sample_offset: int = 0) -> "L.NoiseKey":
     """avd_noise_key after the checks the engine and gaussian_noise share: 0 <= seed < 2**64, sample_offset >= 0."""
     if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:

@@ -140,8 +140,11 @@ class DenoiseEngine:
     same noise as the whole job would).  Both are fixed at construction; a captured graph holds them by value.
 
     ``solver`` (extension; default "ddim" = the reference's sampler): "dpmpp_2m" ends every step in the DPM-Solver++(2M) update
-    (include/avdiff_hip.h, avd_dpmpp_2m_step_f32) inside the same fused CFG kernel — second order, one model call per step, eta == 0
-    only.  The engine owns the solver's history ``x0_hist`` (the previous step's x0, allocated once: a captured graph keeps its
+    (include/avdiff_hip.h, avd_dpmpp_2m_step_f32) inside the same fused CFG kernel — second order, one model call per step.  With
+    eta > 0 it is the solver's SDE form (SDE-DPM-Solver++(2M), avd_dpmpp_2m_sde_step_f32; k-diffusion's "DPM++ 2M SDE"): it needs
+    ``noise_seed`` (seeded noise only — the stream the DDIM step draws, so both solvers see the same normals at a (sample, t,
+    element)), and every kind of step — CFG, CFG-controlled, guided, cond-only, canvas-keyed — goes through one entry
+    (avd_denoise_step_dpmpp_2m_sde_f32).  The engine owns the solver's history ``x0_hist`` (the previous step's x0, allocated once: a captured graph keeps its
     address); ``step(..., t_last=None)`` takes a first-order step, and ``run`` starts every trajectory first order.
 
     ``set_known(known, mask)`` (extension: latent inpainting / outpainting, SDEdit): while a known clean latent is set, every step
@@ -173,18 +176,18 @@ class DenoiseEngine:
     of ``step``: ``capture_pair`` captures it and ``run(graph=True)`` replays it.  With the default per-sample noise stream it is
     eta == 0 only (the mean of independent noise draws would shrink their variance); a canvas-keyed engine (below) lifts that for
     hop == canvas_hop.  DPM-Solver++(2M) needs nothing extra: all windows share the timesteps, so the update is the
-    same linear map of (z, x0, x0_hist) for every window and the consensus of the outputs equals the output of the consensed
-    inputs; ``x0_hist`` stays per window.
+    same linear map of (z, x0, x0_hist) for every window — at eta > 0 plus the canvas-keyed noise term the windows share — and the
+    consensus of the outputs equals the output of the consensed inputs; ``x0_hist`` stays per window.
 
     ``noise_keying`` (extension; default "sample" = the stream above): "canvas" needs ``noise_seed`` and an integer ``canvas_hop`` >=
     1 and reads the batch as N consecutive windows of one canvas, ``canvas_hop`` latent positions apart, window 0 at global window
-    index ``sample_offset``.  At eta > 0 every CFG, CFG-controlled, guided and cond-only step then draws its noise keyed by
+    index ``sample_offset``.  At eta > 0 every CFG, CFG-controlled, guided and cond-only step of either solver then draws its noise keyed by
     (noise_seed, canvas position, t_now, element of that position's slice) (include/avdiff_hip.h, "canvas-keyed noise";
     avd_denoise_step_canvas_f32): all windows over a canvas position draw the same normal there, so the noise term passes through
     the consensus mean unchanged for any weights, and ``set_window_consensus(hop)`` is allowed at eta > 0 when hop == canvas_hop.
     (sample_offset + N - 1) * canvas_hop + L <= 2**32 replaces the per-sample range check.  Both values are fixed at construction; a
     captured graph holds them by value.  ``noise=`` is refused as on any seeded engine.  A latent guide's known-noise stream stays
-    keyed per sample; at eta == 0 (which includes solver "dpmpp_2m", an ODE solver) no noise is drawn and the keying changes nothing.
+    keyed per sample; at eta == 0 no noise is drawn and the keying changes nothing.
     """
 
     SOLVERS = ("ddim", "dpmpp_2m")
@@ -202,8 +205,9 @@ class DenoiseEngine:
             raise ValueError("eta must be >= 0")
         if solver not in self.SOLVERS:
             raise ValueError(f"solver must be one of {self.SOLVERS}, got {solver!r}")
-        if solver == "dpmpp_2m" and eta > 0:
-            raise ValueError("solver 'dpmpp_2m' is the deterministic (ODE) solver: eta must be 0 (the SDE variant is not implemented)")
+        if solver == "dpmpp_2m" and eta > 0 and noise_seed is None:
+            raise ValueError("solver 'dpmpp_2m' with eta > 0 (its SDE form) draws seeded noise only: pass noise_seed, or eta = 0 for the "
+                             "deterministic (ODE) solver")
         self.solver = solver
         self.guidance_interval = su.check_guidance_interval(guidance_interval)
         self._last_cond_only = False      # the kind of the last step: what eps_tokens() finds in the workspace
@@ -616,7 +620,7 @@ class DenoiseEngine:
             if guided:
                 raise ValueError("a guided or CFG-controlled step draws its noise from noise_seed: it takes no `noise`")
             if self.solver == "dpmpp_2m":
-                raise ValueError("solver 'dpmpp_2m' is deterministic: it takes no noise")
+                raise ValueError("solver 'dpmpp_2m' takes no noise: it is deterministic at eta == 0 and draws from noise_seed at eta > 0")
         if guided and self.eta > 0 and self._key is None:
             raise ValueError("with a known latent or a CFG control, eta > 0 needs noise_seed (unseeded noise is not supported there)")
         tl = h = None
@@ -635,9 +639,10 @@ class DenoiseEngine:
         return tl, h, noise
 
     def _step_kind(self, z, tn, tp, noise, out, t_last, cond_only) -> torch.Tensor:
-        """the step proper: canvas-keyed (one entry for every kind of eta > 0 step of a canvas-keyed engine), cond-only (one entry for
-        every solver state, with or without a latent guide; the CFG control does not apply there), CFG-controlled, guided,
-        DPM-Solver++(2M), seeded or plain DDIM"""
+        """the step proper: the SDE form of DPM-Solver++(2M) (one entry for every kind of eta > 0 step of that solver), canvas-keyed
+        (one entry for every kind of eta > 0 DDIM step of a canvas-keyed engine), cond-only (one entry for every solver state, with
+        or without a latent guide; the CFG control does not apply there), CFG-controlled, guided, DPM-Solver++(2M), seeded or plain
+        DDIM"""
         guided = self._guide is not None or (self._ctl is not None and not cond_only)
         tl, h, noise = self._step_args(z, out, noise, t_last, guided)
         lib, desc = L.lib(), C.byref(self.desc)
@@ -645,7 +650,11 @@ class DenoiseEngine:
         guide = None if self._guide is None else C.byref(self._guide)
         zx, ts = (z.data_ptr(), self.Xp.data_ptr()), (tn.data_ptr(), tp.data_ptr())
         tail = (out.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device))
-        if self.canvas_hop is not None and self.eta > 0:
+        if self.solver == "dpmpp_2m" and self.eta > 0:
+            ctl = None if self._ctl is None or cond_only else C.byref(self._ctl)
+            rc = lib.avd_denoise_step_dpmpp_2m_sde_f32(desc, key, self.canvas_hop or 0, ctl, guide, 1 if cond_only else 0, tl.data_ptr(),
+                                                       h.data_ptr(), *zx, *ts, *tail)
+        elif self.canvas_hop is not None and self.eta > 0:
             ctl = None if self._ctl is None or cond_only else C.byref(self._ctl)
             rc = lib.avd_denoise_step_canvas_f32(desc, key, self.canvas_hop, ctl, guide, 1 if cond_only else 0, *zx, *ts, *tail)
         elif cond_only:
@@ -835,7 +844,7 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
     DDIM noise comes from the seeded stream (DenoiseEngine ``noise_seed``), so the whole trajectory repeats from (init_noise,
     noise_seed).
     ``sampling.solver`` (extension; default "ddim"): "dpmpp_2m" samples with DPM-Solver++(2M) (DenoiseEngine ``solver``) over the
-    same ``sampler_steps`` schedule.
+    same ``sampler_steps`` schedule; with ``sampling.ddim_eta`` > 0 it runs the solver's SDE form, which needs ``noise_seed``.
     ``init_video`` (uint8 [T,H,W,3], audio->video) / ``init_audio`` (float waveform, video->audio), ``strength``, ``mask``,
     ``guide_seed`` (extensions; the defaults change nothing): start from, or hold on to, an existing clip of the target modality,
     encoded with the same ``vid_vae`` / ``aud_codec``.  ``strength`` < 1 runs the last part of the schedule from the encoded clip

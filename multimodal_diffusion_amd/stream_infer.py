@@ -179,7 +179,8 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     from a CPU generator for the WHOLE window list instead (the same numbers whatever the number of ranks).  ``noise_seed`` does the
     same for the per-step DDIM noise of ``sampling.ddim_eta`` > 0 (default None: the reference's per-step ``randn_like`` from the device
     generator): window i draws its noise as sample i of the seeded stream (DenoiseEngine ``noise_seed`` / ``sample_offset``), whatever
-    batch or rank steps it.
+    batch or rank steps it.  ``sampling.solver: dpmpp_2m`` with ``ddim_eta`` > 0 runs the solver's SDE form (SDE-DPM-Solver++(2M)) on
+    the same stream; it draws seeded noise only, so it needs ``noise_seed``.
 
     ``shard=True`` (every rank of the default process group calls this with the same arguments; one process per GPU): rank 0 encodes
     the prompt windows, ONE broadcast (``dist.broadcast_conditioning``; over ``comm_device``, default: ``device`` for the nccl = RCCL
@@ -206,8 +207,8 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     decoded on its own and cross-faded, now over near-identical content.  Needs ``shard=False``: windows on different ranks would need
     a halo exchange of their overlaps after every step, which is not implemented.  With the default noise keying it also needs
     ``ddim_eta`` == 0: windows draw independent noise, and the mean over an overlap would shrink its variance.
-    ``noise_keying`` (default None = ``streaming.noise_keying``, else "sample"; the argument wins): "canvas" keys the per-step DDIM
-    noise by canvas position instead of by window (DenoiseEngine ``noise_keying``; include/avdiff_hip.h, "canvas-keyed noise"), so
+    ``noise_keying`` (default None = ``streaming.noise_keying``, else "sample"; the argument wins): "canvas" keys the per-step noise
+    (DDIM's, or that of solver "dpmpp_2m" at ``ddim_eta`` > 0) by canvas position instead of by window (DenoiseEngine ``noise_keying``; include/avdiff_hip.h, "canvas-keyed noise"), so
     every window draws the same normal at a shared position and the consensus leaves the noise term intact: stochastic sampling
     (``ddim_eta`` > 0) under consensus.  It needs consensus on and ``noise_seed``; the engines are built with ``canvas_hop`` =
     ``latent_hop`` and ``sample_offset`` = their first window, so the latents are the same bits for any ``max_windows_per_batch``
