@@ -188,8 +188,8 @@ int avd_dpmpp_2m_step_f32(const float* x_t, const float* eps_hat, float* x0_hist
  * (sample, t, element).  This entry takes n as an explicit tensor (what avd_gaussian_noise_f32 or avd_canvas_noise_f32 wrote, for
  * instance): `noise` fp32 [B, per_sample], required when eta > 0.  Overlap rules as avd_dpmpp_2m_step_f32, and `noise` must not
  * overlap x0_hist or x_out.
- * Limits: the fused steps draw seeded noise only (no unseeded or explicit noise there); a latent guide's known noise stays keyed per
- * sample under canvas keying. */
+ * Limits: the fused steps draw seeded noise only (no unseeded or explicit noise there).  A latent guide's known noise is keyed per
+ * sample by this entry's fused twin (avd_denoise_step_dpmpp_2m_sde_f32) and by canvas position by avd_denoise_step_canvas_guided_f32. */
 int avd_dpmpp_2m_sde_step_f32(const float* x_t, const float* eps_hat, float* x0_hist, const int64_t* t_last, const int64_t* t_now,
                               const int64_t* t_prev, const float* alpha_bar, int T_train, float eta, const float* noise, float* x_out,
                               int B, int64_t per_sample, avd_stream_t stream);
@@ -233,8 +233,9 @@ int avd_gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float
  * Philox, Box-Muller and rounding are those of the per-sample stream (one implementation).  When inner % 4 == 0 and the base is
  * 16-byte aligned a lane's four values lie inside one (o, l) slice and come from one Philox call; otherwise (every audio latent:
  * inner = 1) one call per element.  Same bits either way, and the same bits from avd_canvas_noise_f32 and from the fused step.
- * A latent guide's known-noise stream (avd_latent_guide) keeps its per-sample keying (sample = key.sample_offset + b) under canvas
- * keying: canvas-keyed known noise is not implemented.  DPM-Solver++(2M) at eta > 0 (avd_denoise_step_dpmpp_2m_sde_f32) draws the
+ * A latent guide's known-noise stream (avd_latent_guide) has the same two keyings: per sample (sample = key.sample_offset + b; what
+ * avd_denoise_step_canvas_f32 and avd_denoise_step_dpmpp_2m_sde_f32 keep when handed a guide) and by canvas position ("canvas-keyed
+ * known noise" below; avd_denoise_step_canvas_guided_f32).  DPM-Solver++(2M) at eta > 0 (avd_denoise_step_dpmpp_2m_sde_f32) draws the
  * same canvas-keyed normals as the DDIM step; at eta == 0 it draws nothing. */
 /* out[b, o, l, i] = the canvas-keyed normal above; out: fp32 [N, outer, L, inner]; t_now: int64 [N].  Argument order as
  * avd_window_consensus_f32.  Its output can be passed as the explicit `noise` of the DDIM entries. */
@@ -265,6 +266,28 @@ typedef struct {
  * known / mask must not overlap out.  tau: int64 [B]; z, out: fp32 [B, per_sample]. */
 int avd_latent_guide_f32(const avd_latent_guide* g, const int64_t* tau, const float* alpha_bar, int T_train,
                          const float* z, float* out, int B, int64_t per_sample, avd_stream_t stream);
+
+/* ---- canvas-keyed known noise: the second keying of the guide's stream, for windows of one canvas (a public contract; the
+ * construction of "canvas-keyed noise" applied to n_k).  A batch is N consecutive windows [N, outer, L, inner] of one canvas, `hop`
+ * positions apart ((outer, L, inner) as in avd_window_consensus_f32).  Window b has the global index w = guide.key.sample_offset + b;
+ * its element (o, l, i) sits on canvas position
+ *     p = w*hop + l                                                  (computed in 64 bits)
+ * and takes the known-noise value the per-sample guide stream (step 1 of avd_latent_guide) gives for sample s = p and element
+ * e' = o*inner + i: counter (e' >> 2, (uint32) p, 0, 0x4B4E5731), the element takes n[e' & 3].  In other words n_k at [b, o, l, i] has
+ * the bits of the per-sample stream of key {seed, 0} over B = P samples of outer*inner elements at [p, e'].  q, blend, the a == 1
+ * shortcut (no arithmetic, no generator call) and "no contraction" are exactly those of avd_latent_guide: one implementation.
+ * Every window over a canvas position holds q = A x_k + S n_k(p) with the same normal there, so when the windows' known latents agree
+ * on their overlaps (one canvas: avd_window_consensus_f32 of the encoded windows, once) a held region passes through the consensus
+ * mean as it is, for any weights: it stays on its forward path.  Keyed per sample the mean would shrink the noise term (by 1/sqrt(k)
+ * under uniform weights).  The definition does not contain the canvas length.
+ * Arguments, checked before any launch (AVD_EINVAL): hop >= 1; (sample_offset + N - 1)*hop + L <= 2^32; outer*inner < 2^34; and
+ * avd_latent_guide's own (per_sample = outer*L*inner).  avd_latent_guide keeps its layout: the keying is chosen by the entry. */
+/* out[b] = blend(mask, q(tau[b]), z[b]) with the canvas-keyed n_k; argument order as avd_canvas_noise_f32; z == NULL reads as "mask is
+ * 1 everywhere"; out may be z; known / mask must not overlap out.  When inner % 4 == 0 and z / out are 16-byte aligned a lane's four
+ * values lie inside one (o, l) slice and come from one Philox call; otherwise (every audio latent) one call per element.  Same bits
+ * either way, and the same bits from the fused step. */
+int avd_latent_guide_canvas_f32(const avd_latent_guide* g, const int64_t* tau, const float* alpha_bar, int T_train,
+                                const float* z, float* out, int N, int64_t outer, int L, int hop, int64_t inner, avd_stream_t stream);
 
 /* ---- CFG control: per-sample guidance scales and guidance rescale (Lin et al. 2023, diffusers' rescale_noise_cfg; a public
  * contract).  For sample b of a call, with n = per_sample (>= 2):
@@ -603,14 +626,14 @@ int avd_denoise_step_cond_f32(const avd_step_desc* s, const avd_latent_guide* g,
                               const int64_t* t_now, const int64_t* t_prev, const float* noise, float* z_out,
                               void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 
-/* The whole seeded eta > 0 DDIM step with canvas-keyed noise (see "canvas-keyed noise"): the B samples of s->embed are consecutive
- * windows of one canvas, `hop` positions apart along T (video) or F (audio), window 0 at global index key->sample_offset.  Requires
- * s->eta > 0 and key; the canvas-keying limits are checked before the model runs.  cond_only == 0: the CFG step, with ctl (NULL or an
- * avd_cfg_control, as avd_denoise_step_cfg_f32) and g (NULL or a latent guide, as avd_denoise_step_guided_f32; its known-noise stream
- * stays keyed per sample).  cond_only != 0: the cond-only step (as avd_denoise_step_cond_f32 with a key; ctl must be NULL).  Only the
- * draw inside the fused update differs from those entries: fed avd_canvas_noise_f32's output as explicit noise, avd_denoise_step_f32
- * returns the same bits.  This entry is the DDIM step: the canvas-keyed DPM-Solver++(2M) step is avd_denoise_step_dpmpp_2m_sde_f32 with
- * canvas_hop != 0.  Graph-capturable: seed, sample_offset and hop are held by value. */
+/* The whole seeded eta > 0 DDIM step with canvas-keyed noise (see "canvas-keyed noise"): the B samples of s->embed are consecutive windows
+ * of one canvas, `hop` positions apart along T (video) or F (audio), window 0 at global index key->sample_offset.  Requires s->eta > 0 and
+ * key; the canvas-keying limits are checked before the model runs.  cond_only == 0: the CFG step, with ctl (NULL or an avd_cfg_control, as
+ * avd_denoise_step_cfg_f32) and g (NULL or a latent guide, as avd_denoise_step_guided_f32; its known-noise stream stays keyed per sample:
+ * the canvas keying of the guide is avd_denoise_step_canvas_guided_f32).  cond_only != 0: the cond-only step (as avd_denoise_step_cond_f32
+ * with a key; ctl must be NULL).  Only the draw inside the fused update differs from those entries: fed avd_canvas_noise_f32's output as
+ * explicit noise, avd_denoise_step_f32 returns the same bits.  This entry is the DDIM step: the canvas-keyed DPM-Solver++(2M) step is
+ * avd_denoise_step_dpmpp_2m_sde_f32 with canvas_hop != 0.  Graph-capturable: seed, sample_offset and hop are held by value. */
 int avd_denoise_step_canvas_f32(const avd_step_desc* s, const avd_noise_key* key, int hop, const avd_cfg_control* ctl,
                                 const avd_latent_guide* g, int cond_only, const float* z, const float* Xp,
                                 const int64_t* t_now, const int64_t* t_prev, float* z_out,
@@ -628,6 +651,21 @@ int avd_denoise_step_dpmpp_2m_sde_f32(const avd_step_desc* s, const avd_noise_ke
                                       const avd_latent_guide* g, int cond_only, const int64_t* t_last, float* x0_hist,
                                       const float* z, const float* Xp, const int64_t* t_now, const int64_t* t_prev, float* z_out,
                                       void* workspace, int64_t workspace_bytes, avd_stream_t stream);
+
+/* The whole step ending in the canvas-keyed guided update ("canvas-keyed known noise"): one entry for every kind of step.  The B samples
+ * of s->embed are consecutive windows of one canvas, `hop` positions apart along T (video) or F (audio), window 0 at global index
+ * g->key.sample_offset; z_out = blend(mask, q(t_prev), step(z)) with n_k keyed by canvas position.  The step: DDIM at s->eta == 0 (key is
+ * not read: pass NULL), seeded DDIM at eta > 0, or with t_last and x0_hist (both or neither) DPM-Solver++(2M) in its ODE (eta == 0) or
+ * SDE (eta > 0) form; x0_hist receives the model's x0, not the blended value.  At eta > 0 the step's own noise is canvas-keyed with the
+ * same hop from `key` (as avd_denoise_step_canvas_f32; key->sample_offset is the first window's global index for that stream): a
+ * canvas-keyed guide with per-sample, unseeded or explicit step noise is refused (AVD_EINVAL), as is eta > 0 without a key.
+ * cond_only == 0: the CFG step, with ctl NULL or an avd_cfg_control; cond_only != 0: the cond-only step (ctl must be NULL).  All
+ * argument checks run before the model.  The workspace is the CFG step's.  Graph-capturable: seeds, offsets and hop are held by
+ * value, the guide's buffers and x0_hist are read at their addresses at every launch. */
+int avd_denoise_step_canvas_guided_f32(const avd_step_desc* s, const avd_latent_guide* g, int hop, const avd_noise_key* key,
+                                       const avd_cfg_control* ctl, int cond_only, const int64_t* t_last, float* x0_hist,
+                                       const float* z, const float* Xp, const int64_t* t_now, const int64_t* t_prev, float* z_out,
+                                       void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 
 /* ---- a9 / next-1: VideoVAE.decode — avdiff/models/encoders/vae_video3d.py:195-214 (decode), :79-84
  * (_conv_block_3d: Conv3d 3x3x3 pad 1 -> GELU(erf) -> GroupNorm(min(8,C), eps 1e-5, affine)), :108-119.

@@ -9,7 +9,7 @@ from .adapters import TimestepCfg, TimestepEmbedder      # noqa: F401
 from .mmdt import MMDiT, Block, MHA, MLP, RMSNorm      # noqa: F401
 from .noise_heads import MultiModalNoiseHead           # noqa: F401
 from .sampler import (DenoiseEngine, LinearAdapter, add_sinusoidal_timestep, build_components,   # noqa: F401
-                      latents_to_tokens_audio, latents_to_tokens_video, sample_one_direction, frame_mask,
+                      latents_to_tokens_audio, latents_to_tokens_video, sample_one_direction, frame_mask, canvas_frame_mask,
                       tokens_to_latents_audio)
 from .schedules import ModalitySchedule, build_schedules_from_config   # noqa: F401
 from .vae_video3d import VideoVAE, VideoVAEConfig                      # noqa: F401

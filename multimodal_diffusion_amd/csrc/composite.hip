@@ -81,12 +81,12 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key = nullptr,
                          const int64_t* t_last = nullptr, float* x0_hist = nullptr, const avd_latent_guide* guide = nullptr,
-                         const avd_cfg_control* ctl = nullptr, int canvas_hop = 0);
+                         const avd_cfg_control* ctl = nullptr, int canvas_hop = 0, int guide_hop = 0);
 int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st,
                                const avd_noise_key* key = nullptr, const int64_t* t_last = nullptr, float* x0_hist = nullptr,
-                               const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr, int canvas_hop = 0);
+                               const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr, int canvas_hop = 0, int guide_hop = 0);
 int assemble_cond_f32(float* X1, const float* temb, const float* Xp, int B, int N, int d, int tdim, int Nt, int Np, int target_first,
                       hipStream_t st);
 int assemble_rows_cond_f32(float* X1, const int64_t* t_now, const float* freqs, const float* Xp, float* ss, int B, int N, int d,
@@ -94,12 +94,14 @@ int assemble_rows_cond_f32(float* X1, const int64_t* t_now, const float* freqs, 
 int eps_unpatch_ddim_f32(const float* eps1, const float* z, const int64_t* t_now, const int64_t* t_prev, const float* abar, int T_train,
                          float eta, const float* noise, float* z_out, int B, int C, int T, int H, int W, int t, int h, int w,
                          hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide,
-                         int canvas_hop = 0);
+                         int canvas_hop = 0, int guide_hop = 0);
 int eps_untoken_ddim_audio_f32(const float* eps1, const float* z, const int64_t* t_now, const int64_t* t_prev, const float* abar,
                                int T_train, float eta, const float* noise, float* z_out, int B, int Ca, int F, int len, int stride,
                                hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist,
-                               const avd_latent_guide* guide, int canvas_hop = 0);
+                               const avd_latent_guide* guide, int canvas_hop = 0, int guide_hop = 0);
 int check_canvas_key(const avd_noise_key* key, int N, int64_t outer, int L, int hop, int64_t inner);
+int check_canvas_guide(const avd_latent_guide* g, int N, int64_t outer, int L, int hop, int64_t inner, const float* out,
+                       const float* x0_hist);
 int check_latent_guide(const avd_latent_guide* g, int B, int64_t per, const float* out, const float* x0_hist);
 int check_cfg_control(const avd_cfg_control* ctl, int B, int64_t per, const float* out, const float* x0_hist);
 bool overlaps(const float* a, const float* b, int64_t n);
@@ -799,11 +801,13 @@ extern "C" int64_t avd_step_workspace_bytes(const avd_step_desc* s) {
 // blends the known latent into the update's result (avd_denoise_step_guided_f32); ctl != nullptr applies the CFG control
 // (avd_denoise_step_cfg_f32: its statistics pass runs in the fused update's launcher, on st after the join of the two streams);
 // canvas_hop != 0 keys the seeded draw by canvas position (avd_denoise_step_canvas_f32); key and x0_hist together at eta > 0 end the
-// step with the solver's SDE form (avd_denoise_step_dpmpp_2m_sde_f32)
+// step with the solver's SDE form (avd_denoise_step_dpmpp_2m_sde_f32); guide_hop != 0 keys the guide's known noise by canvas position
+// (avd_denoise_step_canvas_guided_f32)
 static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp, const int64_t* t_now,
                         const int64_t* t_prev, const float* noise, float* z_out, void* workspace, int64_t workspace_bytes,
                         avd_stream_t stream, const int64_t* t_last = nullptr, float* x0_hist = nullptr,
-                        const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr, int canvas_hop = 0) {
+                        const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr, int canvas_hop = 0,
+                        int guide_hop = 0) {
     StepWs ws;
     if (int rc = open_step(s, z, z_out, t_now, t_prev, workspace, workspace_bytes, ws)) return rc;
     auto& [p, X2, tok, core_ws, head_ws, ssx, eps2] = ws;
@@ -846,9 +850,10 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
     }
     if (e.target_kind == 0)
         return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, s->alpha_bar, s->T_train, s->guidance, s->eta, noise, z_out,
-                                    e.B, e.C, e.T, e.H, e.W, e.p0, e.p1, e.p2, st, key, t_last, x0_hist, guide, ctl, canvas_hop);
+                                    e.B, e.C, e.T, e.H, e.W, e.p0, e.p1, e.p2, st, key, t_last, x0_hist, guide, ctl, canvas_hop,
+                                    guide_hop);
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, s->alpha_bar, s->T_train, s->guidance, s->eta, noise, z_out,
-                                      e.B, e.C, e.T, e.p0, e.p1, st, key, t_last, x0_hist, guide, ctl, canvas_hop);
+                                      e.B, e.C, e.T, e.p0, e.p1, st, key, t_last, x0_hist, guide, ctl, canvas_hop, guide_hop);
 }
 
 // The cond-only step of a guidance interval: the conditional branch alone, in the cond half of every workspace region of the CFG step's
@@ -857,7 +862,7 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
 static int denoise_step_cond(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp, const int64_t* t_now,
                              const int64_t* t_prev, const float* noise, float* z_out, void* workspace, int64_t workspace_bytes,
                              avd_stream_t stream, const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide,
-                             int canvas_hop = 0) {
+                             int canvas_hop = 0, int guide_hop = 0) {
     StepWs ws;
     if (int rc = open_step(s, z, z_out, t_now, t_prev, workspace, workspace_bytes, ws)) return rc;
     auto& [p, X1, tok, core_ws, head_ws, ssx, eps1] = ws;
@@ -872,9 +877,9 @@ static int denoise_step_cond(const avd_step_desc* s, const avd_noise_key* key, c
     if (int rc = head_forward(s->head, X1 + (int64_t)row0 * e.d, hm, p.rows / 2, eps1, head_ws, p.head / 2, st)) return rc;
     if (e.target_kind == 0)
         return eps_unpatch_ddim_f32(eps1, z, t_now, t_prev, s->alpha_bar, s->T_train, s->eta, noise, z_out, e.B, e.C, e.T, e.H, e.W, e.p0,
-                                    e.p1, e.p2, st, key, t_last, x0_hist, guide, canvas_hop);
+                                    e.p1, e.p2, st, key, t_last, x0_hist, guide, canvas_hop, guide_hop);
     return eps_untoken_ddim_audio_f32(eps1, z, t_now, t_prev, s->alpha_bar, s->T_train, s->eta, noise, z_out, e.B, e.C, e.T, e.p0, e.p1, st,
-                                      key, t_last, x0_hist, guide, canvas_hop);
+                                      key, t_last, x0_hist, guide, canvas_hop, guide_hop);
 }
 
 // The option checks the step entries share, made here as well as in the fused update's launcher: before the model runs, and for both
@@ -997,6 +1002,35 @@ extern "C" int avd_denoise_step_dpmpp_2m_sde_f32(const avd_step_desc* s, const a
         return denoise_step_cond(s, key, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, g,
                                  canvas_hop);
     return denoise_step(s, key, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, g, ctl, canvas_hop);
+}
+
+// Every kind of step that ends in a canvas-keyed latent guide: DDIM at eta == 0, seeded DDIM at eta > 0, DPM-Solver++(2M) in its ODE
+// and SDE forms (t_last + x0_hist), the CFG step (with an optional control) or, with cond_only, the single-branch step.  At eta > 0
+// the step's own noise is canvas-keyed with the same hop; at eta == 0 nothing is drawn and key is not read.
+extern "C" int avd_denoise_step_canvas_guided_f32(const avd_step_desc* s, const avd_latent_guide* g, int hop, const avd_noise_key* key,
+                                                  const avd_cfg_control* ctl, int cond_only, const int64_t* t_last, float* x0_hist,
+                                                  const float* z, const float* Xp, const int64_t* t_now, const int64_t* t_prev,
+                                                  float* z_out, void* workspace, int64_t workspace_bytes, avd_stream_t stream) {
+    AVD_REQUIRE(s, AVD_EINVAL, "denoise_step_canvas_guided: null descriptor");
+    AVD_REQUIRE(g, AVD_EINVAL, "denoise_step_canvas_guided: null latent guide");
+    AVD_REQUIRE(!(cond_only && ctl), AVD_EINVAL, "denoise_step_canvas_guided: a cond-only step takes no CFG control");
+    AVD_REQUIRE(s->eta >= 0.f, AVD_EINVAL, "denoise_step_canvas_guided: eta must be >= 0");
+    const bool noisy = s->eta > 0.f;
+    AVD_REQUIRE(!noisy || key, AVD_EINVAL,
+                "denoise_step_canvas_guided: eta > 0 under a canvas-keyed guide needs a noise key (the step's noise is canvas-keyed with "
+                "the guide's hop; per-sample or unseeded noise is refused)");
+    const avd_embed_desc& e = s->embed;
+    if (int rc = check_canvas_guide(g, e.B, e.C, e.T, hop, (int64_t)e.H * e.W, z_out, x0_hist)) return rc;
+    if (noisy)
+        if (int rc = check_canvas_key(key, e.B, e.C, e.T, hop, (int64_t)e.H * e.W)) return rc;
+    const avd_noise_key* k = noisy ? key : nullptr;
+    if (int rc = check_step_options("denoise_step_canvas_guided", NEED_GUIDE | TAKES_SDE, s, k, t_last, x0_hist, z, z_out, g, ctl, nullptr))
+        return rc;
+    if (cond_only)
+        return denoise_step_cond(s, k, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, g,
+                                 noisy ? hop : 0, hop);
+    return denoise_step(s, k, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, g, ctl,
+                        noisy ? hop : 0, hop);
 }
 
 extern "C" int avd_prof_enable(int on) {

@@ -316,15 +316,19 @@ struct DpmState {
 struct CondOnly {};
 template <class T, class... X> struct PackHas { static constexpr bool value = (std::is_same<T, X>::value || ...); };
 struct GuideState;
+struct CanvasGuideState;
 struct CfgState;
 // a well-formed pack: optionally one DpmState; one key exactly when SEEDED (a NoiseKey, or a CanvasKey for the canvas-keyed draw: seeded
-// DDIM noise, or with the DpmState the SDE form's noise); then optionally one GuideState, then optionally one CfgState or CondOnly
+// DDIM noise, or with the DpmState the SDE form's noise); then optionally one GuideState or CanvasGuideState (the guide's known noise
+// keyed per sample or by canvas position; a canvas-keyed guide never rides with a NoiseKey), then optionally one CfgState or CondOnly
 struct NoiseKey;
 struct CanvasKey;
 template <bool SEEDED, class... X> struct PackOk {
     template <class T> static constexpr int n = PackHas<T, X...>::value ? 1 : 0;
-    static constexpr bool value = sizeof...(X) == (SEEDED ? 1 : 0) + n<DpmState> + n<GuideState> + n<CfgState> + n<CondOnly> &&
-                                  !(n<CfgState> && n<CondOnly>) &&
+    static constexpr bool value = sizeof...(X) == (SEEDED ? 1 : 0) + n<DpmState> + n<GuideState> + n<CanvasGuideState> + n<CfgState> +
+                                                      n<CondOnly> &&
+                                  !(n<CfgState> && n<CondOnly>) && !(n<GuideState> && n<CanvasGuideState>) &&
+                                  !(n<CanvasGuideState> && n<NoiseKey>) &&
                                   n<NoiseKey> + n<CanvasKey> == (SEEDED ? 1 : 0);
 };
 template <class T, class A, class... R> __device__ __forceinline__ T pack_get(const A& a, const R&... r) {
@@ -413,9 +417,11 @@ struct CanvasKey {
 
 // the Philox call that holds element e' = o * inner + i of canvas position p (window b, position l): e' takes n[e' & 3]; with
 // inner % 4 == 0 and i % 4 == 0 the four values are elements i .. i + 3 of the (o, l) slice
-__device__ __forceinline__ f32x4 canvas_normal4(const CanvasKey& ck, int b, int64_t o, int l, int64_t i, int64_t inner, uint32_t t) {
+// tag: as philox_normal4 (the canvas-keyed latent guide draws with GUIDE_TAG and t = 0)
+__device__ __forceinline__ f32x4 canvas_normal4(const CanvasKey& ck, int b, int64_t o, int l, int64_t i, int64_t inner, uint32_t t,
+                                                uint32_t tag = 0x44444D31u) {
     const uint64_t p = ((uint64_t)ck.w0 + (uint32_t)b) * ck.hop + (uint32_t)l;
-    return philox_normal4(NoiseKey{ck.k0, ck.k1, 0u}, (uint32_t)((o * inner + i) >> 2), (uint32_t)p, t);
+    return philox_normal4(NoiseKey{ck.k0, ck.k1, 0u}, (uint32_t)((o * inner + i) >> 2), (uint32_t)p, t, tag);
 }
 
 // V == 4: inner % 4 == 0 and out 16-byte aligned, a lane's float4 lies inside one (o, l) slice: one Philox call per four values.
@@ -439,16 +445,18 @@ __global__ __launch_bounds__(256) void canvas_noise_kernel(const int64_t* __rest
 
 // the checks of the canvas keying, all before any HIP call: hop >= 1, every canvas position of the batch below 2^32, and one position's
 // slice outer * inner below 2^34 elements
-int make_canvas_key(const avd_noise_key* key, int N, int64_t outer, int L, int hop, int64_t inner, CanvasKey& ck) {
-    AVD_REQUIRE(key, AVD_EINVAL, "canvas noise: null noise key");
-    AVD_REQUIRE(N > 0 && outer > 0 && L > 0 && inner > 0, AVD_EINVAL, "canvas noise: bad dims (N %d, outer %lld, L %d, inner %lld)", N,
+// what: the stream the messages name ("canvas noise", or "canvas guide" for the latent guide's known noise)
+int make_canvas_key(const avd_noise_key* key, int N, int64_t outer, int L, int hop, int64_t inner, CanvasKey& ck,
+                    const char* what = "canvas noise") {
+    AVD_REQUIRE(key, AVD_EINVAL, "%s: null noise key", what);
+    AVD_REQUIRE(N > 0 && outer > 0 && L > 0 && inner > 0, AVD_EINVAL, "%s: bad dims (N %d, outer %lld, L %d, inner %lld)", what, N,
                 (long long)outer, L, (long long)inner);
-    AVD_REQUIRE(hop >= 1, AVD_EINVAL, "canvas noise: hop must be >= 1 (got %d)", hop);
+    AVD_REQUIRE(hop >= 1, AVD_EINVAL, "%s: hop must be >= 1 (got %d)", what, hop);
     const int64_t lim = (int64_t)1 << 32;
     AVD_REQUIRE(key->sample_offset >= 0 && key->sample_offset < lim && key->sample_offset + N - 1 <= (lim - L) / hop, AVD_EINVAL,
-                "canvas noise: (sample_offset %lld + N %d - 1) * hop %d + L %d must lie in [1, 2^32]", (long long)key->sample_offset, N,
+                "%s: (sample_offset %lld + N %d - 1) * hop %d + L %d must lie in [1, 2^32]", what, (long long)key->sample_offset, N,
                 hop, L);
-    AVD_REQUIRE(outer <= (((int64_t)1 << 34) - 1) / inner, AVD_EINVAL, "canvas noise: outer %lld * inner %lld must be < 2^34",
+    AVD_REQUIRE(outer <= (((int64_t)1 << 34) - 1) / inner, AVD_EINVAL, "%s: outer %lld * inner %lld must be < 2^34", what,
                 (long long)outer, (long long)inner);
     ck = CanvasKey{(uint32_t)(key->seed & 0xffffffffu), (uint32_t)(key->seed >> 32), (uint32_t)key->sample_offset, (uint32_t)hop};
     return AVD_OK;
@@ -624,6 +632,36 @@ __device__ __forceinline__ float guide_apply1(const GuideState& gs, const GuideC
     return guide_blend(m, guide_q(gc, gs.known[i], n), z);
 }
 
+// The canvas keying of the guide (include/avdiff_hip.h, "canvas-keyed known noise"): the batch is N consecutive windows of one canvas
+// and n_k of element (o, l, i) of window b is the per-sample guide stream's value for sample p = (w0 + b) * hop + l, element
+// e' = o * inner + i — canvas_normal4 with GUIDE_TAG and no timestep.  q and the blend are guide_q / guide_blend, as above.
+struct CanvasGuideState {
+    const float* known;     // [N, outer, L, inner]
+    const float* mask;      // one window's (mask_bstride 0) or the batch's; nullptr = 1 everywhere
+    int64_t mask_bstride;
+    CanvasKey ck;           // the known-noise stream's seed, the global index of window 0 (guide.key.sample_offset) and the hop
+};
+// the four consecutive elements at lat = b * per + el, elements i .. i + 3 of the (o, l) slice (inner % 4 == 0, i % 4 == 0)
+__device__ __forceinline__ f32x4 canvas_guide_apply4(const CanvasGuideState& gs, const GuideCoef& gc, int b, int64_t lat, int64_t el,
+                                                     int64_t o, int l, int64_t i, int64_t inner, f32x4 z) {
+    const f32x4 m = gs.mask ? *reinterpret_cast<const f32x4*>(gs.mask + b * gs.mask_bstride + el) : f32x4{1.f, 1.f, 1.f, 1.f};
+    const f32x4 xk = *reinterpret_cast<const f32x4*>(gs.known + lat);
+    f32x4 n = {0.f, 0.f, 0.f, 0.f};
+    if (!gc.one) n = canvas_normal4(gs.ck, b, o, l, i, inner, 0u, GUIDE_TAG);
+    f32x4 r;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] = guide_blend(m[k], guide_q(gc, xk[k], n[k]), z[k]);
+    return r;
+}
+// one element at idx = b * per + el, element i of the (o, l) slice
+__device__ __forceinline__ float canvas_guide_apply1(const CanvasGuideState& gs, const GuideCoef& gc, int b, int64_t idx, int64_t el,
+                                                     int64_t o, int l, int64_t i, int64_t inner, float z) {
+    const float m = gs.mask ? gs.mask[b * gs.mask_bstride + el] : 1.f;
+    float n = 0.f;
+    if (!gc.one) n = canvas_normal4(gs.ck, b, o, l, i, inner, 0u, GUIDE_TAG)[(int)((o * inner + i) & 3)];
+    return guide_blend(m, guide_q(gc, gs.known[idx], n), z);
+}
+
 // the checks every guided entry makes before any HIP call; out and x0_hist (either may be nullptr) must not overlap known / mask
 int check_latent_guide(const avd_latent_guide* g, int B, int64_t per, const float* out, const float* x0_hist) {
     AVD_REQUIRE(g, AVD_EINVAL, "latent_guide: null guide");
@@ -651,6 +689,26 @@ static int make_guide(const avd_latent_guide* g, int B, int64_t per, const float
     if (int rc = make_noise_key(&g->key, B, nk)) return rc;
     gs = GuideState{g->known, g->mask, g->mask_batch_stride, nk};
     return AVD_OK;
+}
+
+// the canvas-keyed guide's checks, all before any HIP call: the canvas limits on the guide's key (hop >= 1, every canvas position of
+// the batch below 2^32, one position's slice below 2^34 elements), then check_latent_guide's
+static int make_canvas_guide(const avd_latent_guide* g, int N, int64_t outer, int L, int hop, int64_t inner, const float* out,
+                             const float* x0_hist, CanvasGuideState& gs) {
+    AVD_REQUIRE(g, AVD_EINVAL, "latent_guide: null guide");
+    CanvasKey ck;
+    if (int rc = make_canvas_key(&g->key, N, outer, L, hop, inner, ck, "canvas guide")) return rc;
+    AVD_REQUIRE((double)outer * (double)L * (double)inner < 17179869184.0, AVD_EINVAL,
+                "canvas guide: a window of outer %lld * L %d * inner %lld values must hold < 2^34", (long long)outer, L, (long long)inner);
+    if (int rc = check_latent_guide(g, N, outer * L * inner, out, x0_hist)) return rc;
+    gs = CanvasGuideState{g->known, g->mask, g->mask_batch_stride, ck};
+    return AVD_OK;
+}
+
+int check_canvas_guide(const avd_latent_guide* g, int N, int64_t outer, int L, int hop, int64_t inner, const float* out,
+                       const float* x0_hist) {
+    CanvasGuideState gs;
+    return make_canvas_guide(g, N, outer, L, hop, inner, out, x0_hist, gs);
 }
 
 __global__ __launch_bounds__(256) void latent_guide_kernel(GuideState gs, const int64_t* __restrict__ tau, const float* __restrict__ abar,
@@ -684,6 +742,52 @@ int latent_guide_f32(const avd_latent_guide* g, const int64_t* tau, const float*
     hipLaunchKernelGGL(latent_guide_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, gs, tau, abar, T_train, z, out,
                        per, per4, total4);
     AVD_CHECK_LAUNCH("latent_guide");
+    return AVD_OK;
+}
+
+// The elementwise canvas-keyed guide.  V == 4: inner % 4 == 0 and every base 16-byte aligned, a lane's float4 lies inside one (o, l)
+// slice: one Philox call per four values.  V == 1: one call per element (every audio latent).  n: N * outer * L * inner / V lanes.
+// z == nullptr arrives with gs.mask == nullptr: blend(1, q, .) selects q.
+template <int V>
+__global__ __launch_bounds__(256) void canvas_latent_guide_kernel(CanvasGuideState gs, const int64_t* __restrict__ tau,
+                                                                  const float* __restrict__ abar, int T_train, const float* z, float* out,
+                                                                  int64_t outer, int L, int64_t inner, int64_t n) {      // z may be out
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const int64_t iv = inner / V;
+    const int64_t i = (idx % iv) * V;
+    int64_t r = idx / iv;
+    const int l = (int)(r % L);
+    r /= L;
+    const int64_t o = r % outer;
+    const int b = (int)(r / outer);
+    const int64_t j = idx * V, el = j - (int64_t)b * outer * L * inner;
+    const GuideCoef gc = guide_coef(abar, T_train, tau[b]);
+    if constexpr (V == 4) {
+        const f32x4 zz = z ? *reinterpret_cast<const f32x4*>(z + j) : f32x4{0.f, 0.f, 0.f, 0.f};
+        *reinterpret_cast<f32x4*>(out + j) = canvas_guide_apply4(gs, gc, b, j, el, o, l, i, inner, zz);
+    } else {
+        out[j] = canvas_guide_apply1(gs, gc, b, j, el, o, l, i, inner, z ? z[j] : 0.f);
+    }
+}
+
+int latent_guide_canvas_f32(const avd_latent_guide* g, const int64_t* tau, const float* abar, int T_train, const float* z, float* out,
+                            int N, int64_t outer, int L, int hop, int64_t inner, hipStream_t st) {
+    CanvasGuideState gs;
+    if (int rc = make_canvas_guide(g, N, outer, L, hop, inner, out, nullptr, gs)) return rc;
+    AVD_REQUIRE(tau && abar && out && T_train > 0, AVD_EINVAL, "latent_guide_canvas: null pointer or bad T_train");
+    if (!z) gs.mask = nullptr;      // pure forward noising: the mask reads as 1 everywhere
+    const bool vec = inner % 4 == 0 && aligned16(out) && aligned16(z);
+    AVD_REQUIRE((double)N * (double)outer * (double)L * (double)inner < 9.0e18, AVD_EUNSUPPORTED, "latent_guide_canvas: too many values");
+    const int64_t n = (int64_t)N * outer * L * inner / (vec ? 4 : 1);
+    AVD_REQUIRE((n + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "latent_guide_canvas: %lld lanes are too many for one launch", (long long)n);
+    if (vec)
+        hipLaunchKernelGGL(canvas_latent_guide_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gs, tau, abar, T_train, z,
+                           out, outer, L, inner, n);
+    else
+        hipLaunchKernelGGL(canvas_latent_guide_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gs, tau, abar, T_train, z,
+                           out, outer, L, inner, n);
+    AVD_CHECK_LAUNCH("latent_guide_canvas");
     return AVD_OK;
 }
 
@@ -918,7 +1022,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int64_t total4, Key... nk) {
     constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
     constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
-    constexpr bool CANVAS = PackHas<CanvasKey, Key...>::value;
+    constexpr bool CANVAS = PackHas<CanvasKey, Key...>::value, CGUIDED = PackHas<CanvasGuideState, Key...>::value;
     static_assert(PackOk<SEEDED, Key...>::value, "not a pack of the fused update kernels (see PackOk)");
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total4) return;
@@ -964,6 +1068,11 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
         }
     }
     if constexpr (GUIDED) o = guide_apply4(pack_get<GuideState>(nk...), guide_coef(abar, T_train, t_prev[b]), b, lat, e4 * 4, o);
+    if constexpr (CGUIDED) {      // the canvas-keyed guide: n_k by canvas position, the (c, t) slice of the canvas-keyed draw above
+        const int64_t hw4 = ((int64_t)g.H * g.W) >> 2, r = e4 / hw4;
+        o = canvas_guide_apply4(pack_get<CanvasGuideState>(nk...), guide_coef(abar, T_train, t_prev[b]), b, lat, e4 * 4, r / g.T,
+                                (int)(r % g.T), (e4 % hw4) * 4, hw4 * 4, o);
+    }
     *reinterpret_cast<f32x4*>(z_out + lat) = o;
 }
 
@@ -980,7 +1089,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int groups_per_sample, Key... nk) {
     constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
     constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
-    constexpr bool CANVAS = PackHas<CanvasKey, Key...>::value;
+    constexpr bool CANVAS = PackHas<CanvasKey, Key...>::value, CGUIDED = PackHas<CanvasGuideState, Key...>::value;
     static_assert(PackOk<SEEDED, Key...>::value, "not a pack of the fused update kernels (see PackOk)");
     extern __shared__ __attribute__((aligned(16))) float ebuf[];       // [GT][D + 4]: the pad keeps the transposed 16-byte reads off one bank group
     const int LD = g.D + 4;
@@ -1006,7 +1115,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     [[maybe_unused]] Dpm d{0.f, 0.f, 0.f, 0.f};
     if constexpr (DPM) d = dpm_coef(pack_get<DpmState>(nk...).t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, b);
     [[maybe_unused]] GuideCoef gc{0.f, 0.f, false};
-    if constexpr (GUIDED) gc = guide_coef(abar, T_train, t_prev[b]);
+    if constexpr (GUIDED || CGUIDED) gc = guide_coef(abar, T_train, t_prev[b]);
     // token coordinates of the group: n = (t' Ht + h') Wt + w'
     const int wq = n0 % g.Wt, hq = (n0 / g.Wt) % g.Ht, tq = n0 / (g.Wt * g.Ht);
     const int segs = g.D / g.w;                                          // (c, t, h) combinations of a token
@@ -1046,6 +1155,9 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
             for (int k = 0; k < 4; ++k) o[k] = ddim_apply(c, x[k], e[k], zn[k]);
         }
         if constexpr (GUIDED) o = guide_apply4(pack_get<GuideState>(nk...), gc, b, lat, lat - (int64_t)b * g.per, o);
+        if constexpr (CGUIDED)      // the canvas-keyed guide: the (c, t, h, w) decomposition of the canvas-keyed draw above
+            o = canvas_guide_apply4(pack_get<CanvasGuideState>(nk...), gc, b, lat, lat - (int64_t)b * g.per, cc, tq * g.t + tt,
+                                    (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo, (int64_t)g.H * g.W, o);
         *reinterpret_cast<f32x4*>(z_out + lat) = o;
     }
 }
@@ -1064,11 +1176,12 @@ struct UpdateArgs {
 };
 // what the kernels' trailing pack is made of: filled by check_fused_update, read by with_update_pack
 struct UpdateKeys {
-    bool dpm, seeded, canvas, guide, ctl;
+    bool dpm, seeded, canvas, guide, cguide, ctl;
     DpmState ds;
     NoiseKey nk;
     CanvasKey ck;      // canvas: the seeded draw is keyed by canvas position (ck replaces nk in the pack)
     GuideState gs;
+    CanvasGuideState cgs;      // cguide: the guide's known noise is keyed by canvas position (cgs replaces gs in the pack)
     CfgState cs;
 };
 
@@ -1079,6 +1192,8 @@ struct UpdateKeys {
 // guide != nullptr: the latent guide's blend ends the update (after either solver), right before z_out is stored
 // ctl != nullptr: per-sample guidance and / or rescale (avd_cfg_control); with rescale set the launcher runs the statistics pass first
 // cv != nullptr: the batch is windows of one canvas and the seeded draw is keyed by canvas position (needs key and eta > 0)
+// gcv != nullptr: the guide's known noise is keyed by canvas position (needs guide; a seeded draw must then be canvas-keyed with the
+// same hop: per-sample step noise under a canvas-keyed guide is refused)
 struct CanvasDims {
     int64_t outer;
     int L, hop;
@@ -1086,7 +1201,7 @@ struct CanvasDims {
 };
 static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per, const avd_noise_key* key, const int64_t* t_last,
                               float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl, UpdateKeys& k,
-                              const CanvasDims* cv = nullptr) {
+                              const CanvasDims* cv = nullptr, const CanvasDims* gcv = nullptr) {
     AVD_REQUIRE(a.eps && a.z && a.t_now && a.t_prev && a.abar && a.z_out, AVD_EINVAL, "%s: null pointer", what);
     AVD_REQUIRE(a.eta >= 0.f && (a.eta == 0.f || a.noise || key), AVD_EINVAL, "%s: eta > 0 needs a noise tensor or a noise key", what);
     AVD_REQUIRE(a.z != a.z_out, AVD_EINVAL, "%s: z_out must not alias z", what);
@@ -1109,11 +1224,18 @@ static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per
         if (int rc = make_noise_key(key, a.B, k.nk)) return rc;
         AVD_REQUIRE(per < ((int64_t)1 << 34), AVD_EINVAL, "%s: a seeded sample must hold < 2^34 values", what);
     }
-    k.guide = guide != nullptr;
+    AVD_REQUIRE(guide || !gcv, AVD_EINVAL, "%s: the canvas keying of a latent guide needs the guide", what);
+    k.guide = guide != nullptr && !gcv;
+    k.cguide = guide != nullptr && gcv;
     k.ctl = ctl != nullptr;
     if (guide || ctl)
         AVD_REQUIRE(a.eta == 0.f || k.seeded, AVD_EINVAL, "%s: a guided or controlled step with eta > 0 needs a noise key", what);
-    if (guide)
+    if (k.cguide) {
+        AVD_REQUIRE(!k.seeded || (cv && cv->hop == gcv->hop), AVD_EINVAL,
+                    "%s: under a canvas-keyed latent guide the eta > 0 noise must be canvas-keyed with the guide's hop %d (per-sample "
+                    "step noise is refused)", what, gcv->hop);
+        if (int rc = make_canvas_guide(guide, a.B, gcv->outer, gcv->L, gcv->hop, gcv->inner, a.z_out, x0_hist, k.cgs)) return rc;
+    } else if (guide)
         if (int rc = make_guide(guide, a.B, per, a.z_out, x0_hist, k.gs)) return rc;
     if (ctl)
         if (int rc = make_cfg(ctl, a.B, per, a.z_out, x0_hist, k.cs)) return rc;
@@ -1122,9 +1244,22 @@ static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per
 
 // Calls launch(pack...) with the kernels' whole trailing pack: the solver's state (DpmState, the NoiseKey of a seeded eta > 0 step or
 // the CanvasKey of a canvas-keyed one, DpmState then that key for the SDE form, or nothing), then the guide if there is one, then the
-// CFG control if there is one or, for the single-branch form, the CondOnly tag.
+// CFG control if there is one or, for the single-branch form, the CondOnly tag.  A canvas-keyed guide rides in the guide's place, after
+// the solver states that can reach it: none, DpmState, CanvasKey, DpmState then CanvasKey (never a NoiseKey: check_fused_update).
 template <class F>
 static void with_update_pack(const UpdateKeys& k, bool cond_only, F launch) {
+    if (k.cguide) {
+        auto ctail = [&](auto... state) {
+            if (cond_only) launch(state..., k.cgs, CondOnly{});
+            else if (k.ctl) launch(state..., k.cgs, k.cs);
+            else launch(state..., k.cgs);
+        };
+        if (k.dpm && k.seeded) ctail(k.ds, k.ck);
+        else if (k.dpm) ctail(k.ds);
+        else if (k.seeded) ctail(k.ck);
+        else ctail();
+        return;
+    }
     auto tail = [&](auto... state) {
         if (cond_only && k.guide) launch(state..., k.gs, CondOnly{});
         else if (cond_only) launch(state..., CondOnly{});
@@ -1166,7 +1301,7 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key,
                          const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
-                         int canvas_hop) {
+                         int canvas_hop, int guide_hop) {
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "cfg_unpatch_ddim: bad dims");
     Tube g;
     if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
@@ -1174,7 +1309,9 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
     const UpdateArgs a{eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, B};
     UpdateKeys k;
     const CanvasDims cv{C, T, canvas_hop, (int64_t)H * W};
-    if (int rc = check_fused_update("cfg_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr)) return rc;
+    const CanvasDims gcv{C, T, guide_hop, (int64_t)H * W};
+    if (int rc = check_fused_update("cfg_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
+                                    guide_hop ? &gcv : nullptr)) return rc;
     if (ctl && ctl->rescale) {
         AVD_REQUIRE(aligned16(eps2) && aligned16(eps2 + (int64_t)B * g.per), AVD_EUNSUPPORTED,
                     "cfg_unpatch_ddim: the statistics pass reads 16-byte aligned token rows");
@@ -1192,7 +1329,7 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
 int eps_unpatch_ddim_f32(const float* eps1, const float* z, const int64_t* t_now, const int64_t* t_prev, const float* abar, int T_train,
                          float eta, const float* noise, float* z_out, int B, int C, int T, int H, int W, int t, int h, int w,
                          hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide,
-                         int canvas_hop) {
+                         int canvas_hop, int guide_hop) {
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "eps_unpatch_ddim: bad dims");
     Tube g;
     if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
@@ -1200,7 +1337,9 @@ int eps_unpatch_ddim_f32(const float* eps1, const float* z, const int64_t* t_now
     const UpdateArgs a{eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, B};
     UpdateKeys k;
     const CanvasDims cv{C, T, canvas_hop, (int64_t)H * W};
-    if (int rc = check_fused_update("eps_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, nullptr, k, canvas_hop ? &cv : nullptr)) return rc;
+    const CanvasDims gcv{C, T, guide_hop, (int64_t)H * W};
+    if (int rc = check_fused_update("eps_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, nullptr, k, canvas_hop ? &cv : nullptr,
+                                    guide_hop ? &gcv : nullptr)) return rc;
     static const int tag = prof_tag_id("eps_unpatch_ddim_kernel");
     ProfScope prof(tag, 12.0 * (double)B * g.per, st);
     with_update_pack(k, true, [&](auto... p) { launch_unpatch(a, g, st, p...); });
@@ -1217,7 +1356,7 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
                                               int F, int len, int stride, int Na, Key... nk) {
     constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
     constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
-    constexpr bool CANVAS = PackHas<CanvasKey, Key...>::value;
+    constexpr bool CANVAS = PackHas<CanvasKey, Key...>::value, CGUIDED = PackHas<CanvasGuideState, Key...>::value;
     static_assert(PackOk<SEEDED, Key...>::value, "not a pack of the fused update kernels (see PackOk)");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)B * Ca * F) return;
@@ -1255,6 +1394,9 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
     auto fin = [&](float v) {
         if constexpr (GUIDED)
             return guide_apply1(pack_get<GuideState>(nk...), guide_coef(abar, T_train, t_prev[b]), b, i, i - (int64_t)b * Ca * F, v);
+        else if constexpr (CGUIDED)      // the canvas-keyed guide: canvas position from f, element c of its slice (inner == 1)
+            return canvas_guide_apply1(pack_get<CanvasGuideState>(nk...), guide_coef(abar, T_train, t_prev[b]), b, i,
+                                       i - (int64_t)b * Ca * F, c, f, 0, 1, v);
         else
             return v;
     };
@@ -1295,14 +1437,16 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st, const avd_noise_key* key,
                                const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
-                               int canvas_hop) {
+                               int canvas_hop, int guide_hop) {
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "cfg_untoken_ddim_audio: bad chunking");
     const UpdateArgs a{eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, B};
     const int64_t per = (int64_t)Ca * F;
     UpdateKeys k;
     const CanvasDims cv{Ca, F, canvas_hop, 1};
-    if (int rc = check_fused_update("cfg_untoken_ddim_audio", a, per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr)) return rc;
+    const CanvasDims gcv{Ca, F, guide_hop, 1};
+    if (int rc = check_fused_update("cfg_untoken_ddim_audio", a, per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
+                                    guide_hop ? &gcv : nullptr)) return rc;
     const AudioGeom ag{Ca, F, len, stride, audio_na(F, len, stride)};
     if (ctl && ctl->rescale) {
         const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
@@ -1317,14 +1461,15 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
 int eps_untoken_ddim_audio_f32(const float* eps1, const float* z, const int64_t* t_now, const int64_t* t_prev, const float* abar,
                                int T_train, float eta, const float* noise, float* z_out, int B, int Ca, int F, int len, int stride,
                                hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist,
-                               const avd_latent_guide* guide, int canvas_hop) {
+                               const avd_latent_guide* guide, int canvas_hop, int guide_hop) {
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "eps_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "eps_untoken_ddim_audio: bad chunking");
     const UpdateArgs a{eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, B};
     UpdateKeys k;
     const CanvasDims cv{Ca, F, canvas_hop, 1};
+    const CanvasDims gcv{Ca, F, guide_hop, 1};
     if (int rc = check_fused_update("eps_untoken_ddim_audio", a, (int64_t)Ca * F, key, t_last, x0_hist, guide, nullptr, k,
-                                    canvas_hop ? &cv : nullptr)) return rc;
+                                    canvas_hop ? &cv : nullptr, guide_hop ? &gcv : nullptr)) return rc;
     const AudioGeom ag{Ca, F, len, stride, audio_na(F, len, stride)};
     with_update_pack(k, true, [&](auto... p) { launch_untoken(a, ag, st, p...); });
     AVD_CHECK_LAUNCH("eps_untoken_ddim_audio");
@@ -1606,14 +1751,14 @@ extern "C" int avd_cfg_unpatch_ddim_f32(const float* eps2, const float* z, const
     AVD_REQUIRE(aligned16(eps2) && aligned16(z) && aligned16(z_out) && (!noise || aligned16(noise)), AVD_EUNSUPPORTED,
                 "cfg_unpatch_ddim: pointers must be 16-byte aligned");
     return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, C, T, H, W, t,
-                                h, w, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+                                h, w, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0);
 }
 extern "C" int avd_cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now,
                                               const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance,
                                               float eta, const float* noise, float* z_out, int B, int Ca, int F, int len,
                                               int stride, avd_stream_t stream) {
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, Ca, F,
-                                      len, stride, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+                                      len, stride, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0);
 }
 extern "C" int avd_eps_unpatch_ddim_f32(const float* eps, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                         const float* alpha_bar, int T_train, float eta, const float* noise, float* z_out, int B, int C,
@@ -1622,14 +1767,14 @@ extern "C" int avd_eps_unpatch_ddim_f32(const float* eps, const float* z, const 
     AVD_REQUIRE(aligned16(eps) && aligned16(z) && aligned16(z_out) && (!noise || aligned16(noise)), AVD_EUNSUPPORTED,
                 "eps_unpatch_ddim: pointers must be 16-byte aligned");
     return eps_unpatch_ddim_f32(eps, z, t_now, t_prev, alpha_bar, T_train, eta, noise, z_out, B, C, T, H, W, t, h, w,
-                                static_cast<hipStream_t>(stream), key, t_last, x0_hist, guide, 0);
+                                static_cast<hipStream_t>(stream), key, t_last, x0_hist, guide, 0, 0);
 }
 extern "C" int avd_eps_untoken_ddim_audio_f32(const float* eps, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                               const float* alpha_bar, int T_train, float eta, const float* noise, float* z_out, int B,
                                               int Ca, int F, int len, int stride, const avd_noise_key* key, const int64_t* t_last,
                                               float* x0_hist, const avd_latent_guide* guide, avd_stream_t stream) {
     return eps_untoken_ddim_audio_f32(eps, z, t_now, t_prev, alpha_bar, T_train, eta, noise, z_out, B, Ca, F, len, stride,
-                                      static_cast<hipStream_t>(stream), key, t_last, x0_hist, guide, 0);
+                                      static_cast<hipStream_t>(stream), key, t_last, x0_hist, guide, 0, 0);
 }
 extern "C" int avd_gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int B, int64_t per_sample,
                                       avd_stream_t stream) {
@@ -1675,4 +1820,9 @@ extern "C" int avd_cfg_rescale_f32(const float* e_cond, const float* e_cfg, cons
 extern "C" int avd_latent_guide_f32(const avd_latent_guide* g, const int64_t* tau, const float* alpha_bar, int T_train, const float* z,
                                     float* out, int B, int64_t per_sample, avd_stream_t stream) {
     return latent_guide_f32(g, tau, alpha_bar, T_train, z, out, B, per_sample, static_cast<hipStream_t>(stream));
+}
+extern "C" int avd_latent_guide_canvas_f32(const avd_latent_guide* g, const int64_t* tau, const float* alpha_bar, int T_train,
+                                           const float* z, float* out, int N, int64_t outer, int L, int hop, int64_t inner,
+                                           avd_stream_t stream) {
+    return latent_guide_canvas_f32(g, tau, alpha_bar, T_train, z, out, N, outer, L, hop, inner, static_cast<hipStream_t>(stream));
 }

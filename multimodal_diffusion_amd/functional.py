@@ -284,15 +284,29 @@ def latent_guide_desc(known: Tensor, mask: Optional[Tensor], seed: int, sample_o
 
 
 def latent_guide(known: Tensor, tau: Tensor, alpha_bar: Tensor, z: Optional[Tensor] = None, mask: Optional[Tensor] = None, *,
-                 seed: int = 0, sample_offset: int = 0) -> Tensor:
+                 seed: int = 0, sample_offset: int = 0, canvas_hop: Optional[int] = None, window_offset: int = 0) -> Tensor:
     """The latent guide's blend (avd_latent_guide_f32; contract in include/avdiff_hip.h): out[b] = blend(mask, q(tau[b]), z[b]) with
     q(tau) = sqrt(a) known + sqrt(1 - a) n_k, n_k the known-noise stream of (seed, sample_offset + b).  ``z`` None: out = q (the known
-    latent forward-noised to tau; tau < 0 returns ``known`` itself).  ``mask``: see latent_guide_desc.  ``tau``: int [B]."""
+    latent forward-noised to tau; tau < 0 returns ``known`` itself).  ``mask``: see latent_guide_desc.  ``tau``: int [B].
+    ``canvas_hop`` (default None = the per-sample keying above): ``known`` is a batch of consecutive windows of one canvas
+    ([N,C,T,H,W] video, [N,Ca,F] audio), ``canvas_hop`` positions apart, window 0 at global window index ``window_offset``, and n_k is
+    keyed by canvas position (avd_latent_guide_canvas_f32; "canvas-keyed known noise"): every window over a position holds the same
+    normal there.  ``sample_offset`` belongs to the per-sample keying, ``window_offset`` to the canvas one."""
+    if canvas_hop is None:
+        if window_offset != 0:
+            raise ValueError("window_offset belongs to the canvas keying: pass canvas_hop")
+        offset = sample_offset
+    else:
+        if sample_offset != 0:
+            raise ValueError("sample_offset belongs to the per-sample keying: with canvas_hop pass window_offset")
+        noise_key(seed, window_offset)                       # the offset's type and sign, before it enters the range check
+        canvas_hop = check_canvas_keying(tuple(known.shape), canvas_hop, window_offset)
+        offset = window_offset
     known = L.dev_f32(known, "known").contiguous()
     dev = known.device
     B = known.shape[0]
     m = None if mask is None else L.dev_f32(mask, "mask").contiguous()
-    g = latent_guide_desc(known, m, seed, sample_offset)
+    g = latent_guide_desc(known, m, seed, offset)
     tn = L.dev_i64(tau, dev)
     if tn.numel() != B:
         raise ValueError(f"tau has {tn.numel()} entries, known has {B} samples")
@@ -304,8 +318,13 @@ def latent_guide(known: Tensor, tau: Tensor, alpha_bar: Tensor, z: Optional[Tens
     ab = alpha_bar if (alpha_bar.is_cuda and alpha_bar.dtype == torch.float32) else alpha_bar.to(dev, torch.float32)
     ab = ab.contiguous()
     out = torch.empty_like(known)
-    L.check(L.lib().avd_latent_guide_f32(C.byref(g), tn.data_ptr(), ab.data_ptr(), ab.numel(), L.ptr(zz), out.data_ptr(), B,
-                                         known.numel() // B, _st(out)))
+    if canvas_hop is None:
+        L.check(L.lib().avd_latent_guide_f32(C.byref(g), tn.data_ptr(), ab.data_ptr(), ab.numel(), L.ptr(zz), out.data_ptr(), B,
+                                             known.numel() // B, _st(out)))
+    else:
+        outer, L_, inner = window_dims(known.shape)
+        L.check(L.lib().avd_latent_guide_canvas_f32(C.byref(g), tn.data_ptr(), ab.data_ptr(), ab.numel(), L.ptr(zz), out.data_ptr(), B,
+                                                    outer, L_, canvas_hop, inner, _st(out)))
     return out
 
 

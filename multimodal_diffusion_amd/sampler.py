@@ -186,12 +186,22 @@ class DenoiseEngine:
     avd_denoise_step_canvas_f32): all windows over a canvas position draw the same normal there, so the noise term passes through
     the consensus mean unchanged for any weights, and ``set_window_consensus(hop)`` is allowed at eta > 0 when hop == canvas_hop.
     (sample_offset + N - 1) * canvas_hop + L <= 2**32 replaces the per-sample range check.  Both values are fixed at construction; a
-    captured graph holds them by value.  ``noise=`` is refused as on any seeded engine.  A latent guide's known-noise stream stays
-    keyed per sample; at eta == 0 no noise is drawn and the keying changes nothing.
+    captured graph holds them by value.  ``noise=`` is refused as on any seeded engine.  At eta == 0 no noise is drawn and the keying
+    changes nothing.
+
+    ``set_known(..., keying="canvas", hop=...)`` (extension; default "sample" = the stream above): the same second keying for the
+    latent guide's known noise (include/avdiff_hip.h, "canvas-keyed known noise"): the batch is N consecutive windows of one canvas
+    ``hop`` positions apart and every window draws the same known normal at a shared canvas position, so a held region passes through
+    the consensus mean on its forward path (keyed per sample, the mean over an overlap would shrink its noise term).  Every step of
+    such an engine — either solver, eta == 0 or > 0, CFG, CFG-controlled, cond-only — goes through one entry
+    (avd_denoise_step_canvas_guided_f32), and ``start_latent`` forward-noises with the same keying.  ``hop`` must equal ``canvas_hop``
+    on a canvas-keyed engine and the consensus hop while a consensus is set; eta > 0 needs the canvas-keyed engine (a canvas guide
+    with per-sample step noise is refused).  The known windows must agree on their overlaps (``functional.window_consensus`` once).
     """
 
     SOLVERS = ("ddim", "dpmpp_2m")
     NOISE_KEYINGS = ("sample", "canvas")
+    GUIDE_KEYINGS = ("sample", "canvas")
 
     def __init__(self, *, adapt_v: LinearAdapter, adapt_a: LinearAdapter, core: MMDiT, head: MultiModalNoiseHead,
                  tstep_dim: int, target: str, latent_shape: Tuple[int, ...], prompt_tokens: int, alpha_bar: torch.Tensor,
@@ -305,7 +315,8 @@ class DenoiseEngine:
         self._known: Optional[torch.Tensor] = None
         self._mask: Optional[torch.Tensor] = None
         self._guide: Optional[L.LatentGuide] = None
-        self._guide_sig = None       # what a captured graph holds of the guide by value: pointers, stride, seed
+        self._guide_sig = None       # what a captured graph holds of the guide by value: pointers, stride, seed, offset, keying, hop
+        self._guide_hop: Optional[int] = None      # the hop of a canvas-keyed guide (None: keyed per sample)
         # window consensus (set_window_consensus): the hop (None = off) and the [L] weight table at a fixed address
         self._cons_hop: Optional[int] = None
         self._cons_w: Optional[torch.Tensor] = None
@@ -433,12 +444,36 @@ class DenoiseEngine:
         return Xp
 
     # ---- latent guide: a known clean latent the trajectory is held to (inpainting / outpainting) or starts from (SDEdit) ----
-    def set_known(self, known: torch.Tensor, mask: Optional[torch.Tensor] = None, *, guide_seed: int = 0) -> None:
+    def set_known(self, known: torch.Tensor, mask: Optional[torch.Tensor] = None, *, guide_seed: int = 0, keying: str = "sample",
+                  hop: Optional[int] = None, sample_offset: Optional[int] = None) -> None:
         """Hold the trajectory to ``known`` (the clean latent, the engine's latent shape) where ``mask`` is 1, blend where it is
         fractional, leave it free where it is 0.  ``mask``: None = 1 everywhere, else values in [0, 1] broadcastable to one
-        sample's latent shape (shared by the batch) or to the batch's.  ``guide_seed`` keys the known-noise stream with the
-        engine's sample_offset.  Both are copied into engine-owned buffers: a later call with the same shapes, mask presence and
-        seed keeps every captured graph valid."""
+        sample's latent shape (shared by the batch) or to the batch's.  ``guide_seed`` keys the known-noise stream with
+        ``sample_offset`` (default: the engine's; the global index of this batch's sample — or window — 0 in that stream).
+        ``keying``: "sample" (the stream of (guide_seed, sample_offset + b)) or "canvas" with ``hop`` (class docstring: the batch as
+        windows of one canvas, the known noise keyed by canvas position).  Everything is checked before anything changes.  Known
+        latent and mask are copied into engine-owned buffers: a later call with the same shapes, mask presence, seed, offset, keying
+        and hop keeps every captured graph valid."""
+        if keying not in self.GUIDE_KEYINGS:
+            raise ValueError(f"keying must be one of {self.GUIDE_KEYINGS}, got {keying!r}")
+        offset = self.sample_offset if sample_offset is None else sample_offset
+        Fn.noise_key(guide_seed, offset)                     # validates the seed and the offset
+        if keying == "canvas":
+            if hop is None:
+                raise ValueError("keying='canvas' needs hop: the latent positions from one window of the batch to the next")
+            hop = Fn.check_canvas_keying(self.latent_shape, hop, offset)
+            if self.canvas_hop is not None and hop != self.canvas_hop:
+                raise ValueError(f"a canvas-keyed guide needs hop == canvas_hop (the engine's noise is keyed for windows {self.canvas_hop} "
+                                 f"positions apart), got hop {hop}")
+            if self._cons_hop is not None and hop != self._cons_hop:
+                raise ValueError(f"a canvas-keyed guide needs hop == the window consensus hop {self._cons_hop}, got hop {hop}")
+            if self.eta > 0 and self.canvas_hop is None:
+                raise ValueError("a canvas-keyed guide at eta > 0 needs the step's noise keyed by canvas position as well: build the "
+                                 "engine with noise_keying='canvas', canvas_hop=hop (per-sample step noise is refused)")
+        elif hop is not None:
+            raise ValueError("hop belongs to keying='canvas'")
+        elif offset + self.latent_shape[0] > 2 ** 32:
+            raise ValueError(f"sample_offset {offset} + batch {self.latent_shape[0]} exceeds the stream's 2**32 sample indices")
         known = L.dev_f32(known, "known")
         if tuple(known.shape) != self.latent_shape:
             raise ValueError(f"known latent shape {tuple(known.shape)} != engine shape {self.latent_shape}")
@@ -453,7 +488,6 @@ class DenoiseEngine:
                                  f"{self.latent_shape}") from None
             if not bool(((m >= 0) & (m <= 1)).all()):
                 raise ValueError("mask values must lie in [0, 1]")
-        Fn.noise_key(guide_seed, self.sample_offset)         # validates the seed
         if self._known is None:
             self._known = torch.empty(self.latent_shape, device=self.device, dtype=torch.float32)
         self._known.copy_(known)
@@ -461,7 +495,8 @@ class DenoiseEngine:
             if self._mask is None or tuple(self._mask.shape) != tuple(m.shape):
                 self._mask = torch.empty(tuple(m.shape), device=self.device, dtype=torch.float32)
             self._mask.copy_(m)
-        self._guide = Fn.latent_guide_desc(self._known, self._mask if m is not None else None, guide_seed, self.sample_offset)
+        self._guide = Fn.latent_guide_desc(self._known, self._mask if m is not None else None, guide_seed, offset)
+        self._guide_hop = hop
         self._touch_guide()
 
     def clear_known(self) -> None:
@@ -471,10 +506,11 @@ class DenoiseEngine:
 
     def _touch_guide(self) -> None:
         g = self._guide
-        sig = None if g is None else (g.known, g.mask, g.mask_batch_stride, g.key.seed)
+        sig = None if g is None else (g.known, g.mask, g.mask_batch_stride, g.key.seed, g.key.sample_offset, self._guide_hop)
         if sig != self._guide_sig:
             self._generation += 1
-            self._stale_reason = "the latent guide's buffers, mask presence or seed changed (set_known / clear_known)"
+            self._stale_reason = "the latent guide's buffers, mask presence, seed, sample offset, keying or hop changed (set_known / " \
+                                 "clear_known)"
         self._guide_sig = sig
 
     # ---- CFG control: per-sample guidance scales and guidance rescale ----
@@ -538,6 +574,8 @@ class DenoiseEngine:
         if self.eta > 0 and int(hop) != self.canvas_hop:
             raise ValueError(f"window consensus at eta > 0 needs hop == canvas_hop (the noise is keyed for windows {self.canvas_hop} "
                              f"positions apart), got hop {hop}")
+        if self._guide is not None and self._guide_hop is not None and int(hop) != self._guide_hop:
+            raise ValueError(f"window consensus under a canvas-keyed guide needs hop == the guide's hop {self._guide_hop}, got hop {hop}")
         L_ = Fn.window_dims(self.latent_shape)[1]
         w = Fn.consensus_weights(weights, L_)
         if self._cons_w is None:
@@ -568,7 +606,7 @@ class DenoiseEngine:
         of ``sched`` are run, from t_s = sched_k[0]).  k = n (strength 1): blend(mask, q(t_s), z_init) — the masked region starts on
         the known clip's forward path, the rest is the caller's noise.  k < n: q(t_s) everywhere (SDEdit: the unmasked region becomes
         a variation of the known clip); k = 0 returns the known latent itself.  Without a known latent only strength 1 is allowed and
-        z_start is z_init.  Computed on the device (avd_latent_guide_f32)."""
+        z_start is z_init.  Computed on the device with the guide's keying (avd_latent_guide_f32 / avd_latent_guide_canvas_f32)."""
         sched_k = su.truncate_schedule(sched, strength)
         n = torch.as_tensor(sched).numel() - 1
         z_init = L.dev_f32(z_init, "z_init")
@@ -582,8 +620,12 @@ class DenoiseEngine:
         tau = torch.full((B,), int(sched_k[0]), dtype=torch.long, device=self.device)
         out = torch.empty_like(z_init)
         z = z_init if sched_k.numel() - 1 == n else None
-        L.check(L.lib().avd_latent_guide_f32(C.byref(self._guide), tau.data_ptr(), self.alpha_bar.data_ptr(), self.alpha_bar.numel(),
-                                             L.ptr(z), out.data_ptr(), B, z_init.numel() // B, L.stream_ptr(self.device)))
+        args = (C.byref(self._guide), tau.data_ptr(), self.alpha_bar.data_ptr(), self.alpha_bar.numel(), L.ptr(z), out.data_ptr(), B)
+        if self._guide_hop is None:
+            L.check(L.lib().avd_latent_guide_f32(*args, z_init.numel() // B, L.stream_ptr(self.device)))
+        else:
+            outer, L_, inner = Fn.window_dims(self.latent_shape)
+            L.check(L.lib().avd_latent_guide_canvas_f32(*args, outer, L_, self._guide_hop, inner, L.stream_ptr(self.device)))
         return out, sched_k
 
     def step(self, z: torch.Tensor, t_now: torch.Tensor, t_prev: torch.Tensor,
@@ -639,7 +681,8 @@ class DenoiseEngine:
         return tl, h, noise
 
     def _step_kind(self, z, tn, tp, noise, out, t_last, cond_only) -> torch.Tensor:
-        """the step proper: the SDE form of DPM-Solver++(2M) (one entry for every kind of eta > 0 step of that solver), canvas-keyed
+        """the step proper: under a canvas-keyed latent guide one entry for every kind of step of either solver; else the SDE form
+        of DPM-Solver++(2M) (one entry for every kind of eta > 0 step of that solver), canvas-keyed
         (one entry for every kind of eta > 0 DDIM step of a canvas-keyed engine), cond-only (one entry for every solver state, with
         or without a latent guide; the CFG control does not apply there), CFG-controlled, guided, DPM-Solver++(2M), seeded or plain
         DDIM"""
@@ -650,7 +693,11 @@ class DenoiseEngine:
         guide = None if self._guide is None else C.byref(self._guide)
         zx, ts = (z.data_ptr(), self.Xp.data_ptr()), (tn.data_ptr(), tp.data_ptr())
         tail = (out.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device))
-        if self.solver == "dpmpp_2m" and self.eta > 0:
+        if guide is not None and self._guide_hop is not None:
+            ctl = None if self._ctl is None or cond_only else C.byref(self._ctl)
+            rc = lib.avd_denoise_step_canvas_guided_f32(desc, guide, self._guide_hop, key if self.eta > 0 else None, ctl,
+                                                        1 if cond_only else 0, L.ptr(tl), L.ptr(h), *zx, *ts, *tail)
+        elif self.solver == "dpmpp_2m" and self.eta > 0:
             ctl = None if self._ctl is None or cond_only else C.byref(self._ctl)
             rc = lib.avd_denoise_step_dpmpp_2m_sde_f32(desc, key, self.canvas_hop or 0, ctl, guide, 1 if cond_only else 0, tl.data_ptr(),
                                                        h.data_ptr(), *zx, *ts, *tail)
@@ -822,6 +869,16 @@ def frame_mask(latent_shape, lo: int, hi: int) -> torch.Tensor:
     idx[axis] = slice(lo, hi)
     m[tuple(idx)] = 1.0
     return m
+
+
+def canvas_frame_mask(canvas_shape, lo: int, hi: int) -> torch.Tensor:
+    """``frame_mask`` on a latent canvas (stream_generate ``mask``): float32 ones on canvas positions [lo, hi) and zeros elsewhere — the P
+    axis of a video canvas [C,P,H,W] or of an audio canvas [Ca,P].  "Keep the first positions of the long clip and generate what
+    follows" is canvas_frame_mask(shape, 0, k).  CPU tensor of ``canvas_shape``."""
+    shape = tuple(int(s) for s in canvas_shape)
+    if len(shape) not in (2, 4):
+        raise ValueError(f"canvas_shape {shape} is neither a video ([C,P,H,W]) nor an audio ([Ca,P]) latent canvas")
+    return frame_mask(shape, lo, hi)
 
 
 # ----------------------------------------------------------------------------------------------------------

@@ -171,7 +171,9 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
                     init_noise: Optional[torch.Tensor] = None, max_windows_per_batch: int = 32, shard: bool = False,
                     seed: Optional[int] = None, comm_device: Optional[torch.device] = None,
                     noise_seed: Optional[int] = None, guidance_interval=None, consensus=None,
-                    return_latents: bool = False, noise_keying: Optional[str] = None) -> Optional[Dict[str, np.ndarray]]:
+                    return_latents: bool = False, noise_keying: Optional[str] = None, init_video: Optional[np.ndarray] = None,
+                    init_audio: Optional[np.ndarray] = None, strength: float = 1.0, mask=None,
+                    guide_seed: Optional[int] = None) -> Optional[Dict[str, np.ndarray]]:
     """The body of the reference's ``main()`` (stream_infer.py:146-225) minus file I/O, with all windows batched.
 
     Returns {"audio": wav, "sr"} for a video prompt or {"video": frames uint8, "fps"} for an audio prompt.
@@ -214,7 +216,47 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     ``latent_hop`` and ``sample_offset`` = their first window, so the latents are the same bits for any ``max_windows_per_batch``
     where the engines take the same kernels.  ``shard=True`` stays refused.
     ``return_latents`` adds "latents": the finished [N_windows, *latent] float32 latents (single process only).
+    ``init_video`` (uint8 [T_total,H,W,3], audio->video) / ``init_audio`` (float waveform, video->audio), ``strength``, ``mask``,
+    ``guide_seed`` (the defaults change nothing): the latent guide of ``sample_one_direction`` — inpainting, outpainting, SDEdit —
+    applied to the whole long clip.  The init clip is split into windows like the prompt (it must give the same number of windows)
+    and the windows are encoded as one batch.  ``mask`` lives on the target's latent canvas ([C,P,H,W] / [Ca,P] with P = (N_windows -
+    1)*hop + L latent positions, ``latent_hop``; or anything that broadcasts to it; values in [0, 1], 1 = keep; ``canvas_frame_mask``)
+    and is cut into per-window masks with ``windows_from_canvas``.  ``strength`` < 1 runs the tail of the schedule from the encoded
+    windows noised to that point (``truncate_schedule``; 0 returns the decoded known windows, stitched); without a mask the guide is
+    cleared after the start and the whole latent is free, as in ``sample_one_direction``.  ``guide_seed`` keys the clip's forward
+    noise (default ``noise_seed``, else 0).  Without consensus the windows stay independent: window i is sample i of the per-sample
+    known-noise stream, whatever ``max_windows_per_batch``.  With consensus the encoded windows, which disagree on their overlaps
+    because each was encoded alone, are first made one canvas (one ``window_consensus`` pass with the consensus weights), and the
+    engines hold them with the known noise keyed by canvas position (DenoiseEngine ``set_known(keying="canvas", hop=latent_hop)``;
+    include/avdiff_hip.h, "canvas-keyed known noise"), window offset = the engine's first window: a held region stays on its forward
+    path through every consensus mean and the finished latents equal the known canvas there, for any ``max_windows_per_batch``.
+    ``ddim_eta`` > 0 needs ``noise_seed`` (and under consensus ``noise_keying="canvas"``), as without a guide.  An init clip with
+    ``shard=True`` is refused: the known windows would need a second broadcast, which is not implemented.
     """
+    # the latent guide's argument checks that need no device (the window count and the mask's shape follow the prompt split below)
+    strength = float(strength)
+    if not 0.0 <= strength <= 1.0:
+        raise ValueError(f"strength must lie in [0, 1], got {strength}")
+    init = init_video if init_video is not None else init_audio
+    if init_video is not None and init_audio is not None:
+        raise ValueError("pass init_video or init_audio, not both")
+    if init is None and (mask is not None or strength < 1.0):
+        raise ValueError("a mask or a strength < 1 needs an init clip (init_video for audio->video, init_audio for video->audio)")
+    if init_video is not None and prompt_modality != "audio":
+        raise ValueError("init_video is the target of the audio->video direction (prompt_modality='audio')")
+    if init_audio is not None and prompt_modality != "video":
+        raise ValueError("init_audio is the target of the video->audio direction (prompt_modality='video')")
+    if init is not None and shard:
+        raise ValueError("an init clip with shard=True is not implemented: the known windows would need a second broadcast to the "
+                         "ranks; run the windows in one process")
+    if init_video is not None:
+        init = np.asarray(init_video)
+        if init.ndim != 4 or init.shape[-1] != 3 or init.dtype != np.uint8:
+            raise ValueError(f"init_video must be uint8 [T,H,W,3], got {init.dtype} {init.shape}")
+    elif init_audio is not None:
+        init = np.asarray(init_audio)
+        if init.ndim != 1 or not np.issubdtype(init.dtype, np.floating):
+            raise ValueError(f"init_audio must be a float waveform [N], got {init.dtype} {init.shape}")
     st = cfg.get("streaming", {})
     win_s, hop_s = float(st.get("window_seconds", 3.0)), float(st.get("hop_seconds", 1.0))
     xfade_s = float(st.get("crossfade_seconds", 0.25))
@@ -282,6 +324,28 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         guide = float(cfg["sampling"]["guidance_scale"].get("video", 3.0))
     else:
         raise ValueError("prompt_modality must be 'video' or 'audio'")
+    # the init clip's windows and the mask on the latent canvas, checked before anything is encoded
+    init_chunks = mask_w = None
+    if init is not None:
+        split = split_frames_into_windows if target == "video" else split_audio_into_windows
+        init_chunks = split(init, fps if target == "video" else sr, win_s, hop_s)[0]
+        if init_chunks.shape[0] != zp_shape[0]:
+            raise ValueError(f"the init clip splits into {init_chunks.shape[0]} windows, the prompt into {zp_shape[0]}: they must cover "
+                             "the same long clip")
+    if mask is not None:
+        g_hop, g_L = (cons_hop, cons_L) if consensus else latent_hop(cfg, target)
+        if lat[1] != g_L:
+            raise ValueError(f"mask: the target latent has {lat[1]} positions along its sliding axis (data.clip_seconds), a window of "
+                             f"streaming.window_seconds has {g_L}: they must be equal")
+        mask_canvas_shape = (lat[0], (zp_shape[0] - 1) * g_hop + g_L) + tuple(lat[2:])
+        mc = torch.as_tensor(mask).detach().to("cpu", torch.float32)
+        try:
+            mc = mc.expand(mask_canvas_shape)
+        except RuntimeError:
+            raise ValueError(f"mask shape {tuple(mc.shape)} does not broadcast to the latent canvas {mask_canvas_shape}") from None
+        if not bool(((mc >= 0) & (mc <= 1)).all()):
+            raise ValueError("mask values must lie in [0, 1]")
+        mask_w = windows_from_canvas(mc, g_L, g_hop)                       # [N_windows, *latent]: one mask per window
     z_p, root_error = None, None
     if root:
         try:
@@ -337,6 +401,37 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     if tuple(z0.shape) != (Nw, *lat):
         raise ValueError(f"init_noise has shape {tuple(z0.shape)}, expected {(Nw, *lat)}")
 
+    # the known windows of an init clip: encoded as one batch; under consensus made one canvas first (each window was encoded alone)
+    known = None
+    if init_chunks is not None:
+        if target == "video":
+            fr = torch.from_numpy(np.ascontiguousarray(init_chunks)).to(device).float() / 255.0           # [N,T,H,W,3]
+            known = vid_vae.encode(fr.permute(0, 4, 1, 2, 3).contiguous())
+        else:
+            known = aud_codec.encode(torch.from_numpy(np.ascontiguousarray(init_chunks, dtype=np.float32)).to(device)[:, None, :])
+        known = known.float().contiguous()
+        if tuple(known.shape) != (Nw, *lat):
+            raise ValueError(f"the init clip encodes to windows of shape {tuple(known.shape)}, the target's are {(Nw, *lat)}")
+        if consensus:
+            Fn.window_consensus(known, cons_hop, cons_w)
+        g_seed = guide_seed if guide_seed is not None else (noise_seed if noise_seed is not None else 0)
+
+    def start(eng: DenoiseEngine, lo: int, hi: int):
+        """(z_start, schedule) of the engine of windows [lo, hi): the initial latents and the whole schedule, or with an init clip the
+        guided start (DenoiseEngine.set_known / start_latent; the guide stays set only under a mask)"""
+        z = z0[lo:hi].to(device, torch.float32).contiguous()
+        if known is None:
+            return z, sched
+        m = torch.zeros(lat) if mask_w is None else mask_w[lo:hi]
+        if consensus:
+            eng.set_known(known[lo:hi], m, guide_seed=g_seed, keying="canvas", hop=cons_hop, sample_offset=lo)
+        else:
+            eng.set_known(known[lo:hi], m, guide_seed=g_seed, sample_offset=lo)
+        z, sched_k = eng.start_latent(z, sched, strength)
+        if mask_w is None:
+            eng.clear_known()          # SDEdit without a mask: the whole latent is free, the plain step runs
+        return z, sched_k
+
     def engine(zp_part: torch.Tensor, lo0: int, lo: int, hi: int) -> DenoiseEngine:
         """the engine of windows [lo, hi), its prompt rows set from zp_part (which starts at window lo0)"""
         eng = DenoiseEngine(adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, target=target,
@@ -353,7 +448,11 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         outs = []
         for lo in range(lo0, hi0, max_windows_per_batch):
             hi = min(hi0, lo + max_windows_per_batch)
-            outs.append(engine(zp_part, lo0, lo, hi).run(z0[lo:hi].to(device).contiguous(), sched))
+            if known is None:
+                outs.append(engine(zp_part, lo0, lo, hi).run(z0[lo:hi].to(device).contiguous(), sched))
+                continue
+            eng = engine(zp_part, lo0, lo, hi)
+            outs.append(eng.run(*start(eng, lo, hi)))
         if not outs:
             return torch.empty(0, *lat, device=device)
         return torch.cat(outs, 0) if len(outs) > 1 else outs[0]
@@ -364,17 +463,26 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         if Nw <= max_windows_per_batch:
             eng = engine(zp_all, 0, 0, Nw)
             eng.set_window_consensus(cons_hop, cons_w)
-            return eng.run(z0.to(device).contiguous(), sched)
+            if known is None:
+                return eng.run(z0.to(device).contiguous(), sched)
+            return eng.run(*start(eng, 0, Nw))
         engs = [(lo, min(Nw, lo + max_windows_per_batch)) for lo in range(0, Nw, max_windows_per_batch)]
         engs = [(lo, hi, engine(zp_all, 0, lo, hi)) for lo, hi in engs]
+        if known is None:
+            sched_k, za = sched, z0.to(device, torch.float32).contiguous().clone()
+        else:
+            starts = [start(eng, lo, hi) for lo, hi, eng in engs]
+            sched_k = starts[0][1]                 # one strength: every engine runs the same tail of the schedule
+            za = torch.cat([z for z, _ in starts], 0)
         for _, _, eng in engs:
-            eng.check_schedule(sched)
-            eng.begin(sched)
+            eng.check_schedule(sched_k)
+            eng.begin(sched_k)
         w_dev = cons_w.to(device)
-        za = z0.to(device, torch.float32).contiguous().clone()
         zb = torch.empty_like(za)
-        for start, stop, cfg_step in su.guidance_segments(sched, interval):     # the kind of every step, read on the host as run() does
-            for _ in range(stop - start):
+        if sched_k.numel() < 2:
+            return za                              # strength 0: no steps, the known windows
+        for first, stop, cfg_step in su.guidance_segments(sched_k, interval):     # the kind of every step, read on the host as run() does
+            for _ in range(stop - first):
                 for lo, hi, eng in engs:
                     eng.advance(za[lo:hi], zb[lo:hi], cond_only=not cfg_step)
                 Fn.window_consensus(zb, cons_hop, w_dev)
