@@ -71,6 +71,16 @@ int         avd_device_arch(char* buf, int buflen);
  * bf16x3 path as ONE launch whose hidden activations stay on the CU — d = 512 only; bit-identical to the two launches, and measures
  * 1.5x slower: DESIGN.md 4.9). */
 int         avd_tune_set(const char* key, int64_t value);
+/* The null half of the one-stream CFG step without its duplicate prompt rows (default 1 = on; also the AVD_CFG_DEDUP environment
+ * variable, read when the library loads).  With the target rows first, every prompt row of a null sample is the zero row at the
+ * input and stays one and the same row through every block, so avd_denoise_step_*_f32 carries one of them per null sample and
+ * copies its k / v into the key slots of the others before each attention: the attention sees the keys and values of the full
+ * layout and the step's results are bit-identical to it.  Taken by the stacked one-stream step (split_streams 0) in concat timestep
+ * mode with target_first, Np >= 2, on the folded bf16x3 path (six or nine terms) with the trimmed last block and its residual row map —
+ * today the six-term 16x16x32 kernels have that map, so "bf16x3_strict" still runs the full layout; every other step runs the full
+ * layout whatever the switch says.  Workspace sizes do not depend on it and it may change between calls (not inside a captured
+ * graph's replay: a capture keeps the route it recorded).  Returns the previous value.  Process-wide, single host thread. */
+int         avd_cfg_dedup_set(int on);
 
 /* ---- a6: RMSNorm — avdiff/models/mmdt.py:33-42 (RMSNorm.forward)
  * y = scale * x / (||x||_2 / sqrt(d) + eps), eps OUTSIDE the sqrt. x,y: [rows,d]. */

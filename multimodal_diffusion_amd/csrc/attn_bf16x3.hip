@@ -39,8 +39,8 @@ template <> struct A3Terms<3> { static constexpr int N = 3; static constexpr int
 
 template <bool SPLIT_OUT, int TERMS>   // SPLIT_OUT: the [B*N, H*64] result is written as a split3 image (A operand of out_proj)
 __global__ __launch_bounds__(A3_NW * 64, 2) void attn_bf16x3_kernel(const unsigned char* __restrict__ img, float* __restrict__ out,
-                                                                    int Bt, int N, int Npad, int H, int n_query, int nqb,
-                                                                    float s_inv2, float v_inv, float o_scale, int out_tok) {
+                                                                    int Bt, int N, int Npad, int H, int n_query_max, int nqb,
+                                                                    float s_inv2, float v_inv, float o_scale, RowSegs oseg) {
     // TERMS == 3 (f16x2 image of scale s): s_inv2 = 1 / s^2 takes the scores back to the exp2 domain, the probabilities are split
     // at scale 2^15 (p <= 1), v_inv = 1 / s undoes V's scale, o_scale is the scale of the image written (SPLIT_OUT)
     constexpr int NW = A3_NW, ROWB = QKV3_ROWB;
@@ -59,6 +59,9 @@ __global__ __launch_bounds__(A3_NW * 64, 2) void attn_bf16x3_kernel(const unsign
         h = (w / nqb) % H;
         b = w / (nqb * H);
     }
+    // query rows of this block's sample (block-uniform): the output layout may give the later samples fewer rows (RowSegs)
+    const int seg_tok = oseg.tok[b < oseg.samples[0] ? 0 : 1], n_query = n_query_max < seg_tok ? n_query_max : seg_tok;
+    if (qb * (A3_NW * 32) >= n_query) return;      // no query row of this sample in this block
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
     const int64_t hstride = (int64_t)Npad * ROWB;
@@ -260,12 +263,12 @@ __global__ __launch_bounds__(A3_NW * 64, 2) void attn_bf16x3_kernel(const unsign
                 v[4 + e] = hi ? ch[c + 1][e] : recv;
             }
             if (q_row < n_query) {
-                if constexpr (F16) store_split8_h2(o3, (int64_t)b * out_tok + q_row, h * A3_DH + 8 * (c + hi), d, v, o_scale);
-                else store_split8(o3, (int64_t)b * out_tok + q_row, h * A3_DH + 8 * (c + hi), d, v);
+                if constexpr (F16) store_split8_h2(o3, oseg.row(b, q_row), h * A3_DH + 8 * (c + hi), d, v, o_scale);
+                else store_split8(o3, oseg.row(b, q_row), h * A3_DH + 8 * (c + hi), d, v);
             }
         }
     } else if (q_row < n_query) {
-        float* dst = out + ((int64_t)b * out_tok + q_row) * d + h * A3_DH + 4 * hi;
+        float* dst = out + (oseg.row(b, q_row)) * d + h * A3_DH + 4 * hi;
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
             f32x4 a = {o0[4 * g4] * inv, o0[4 * g4 + 1] * inv, o0[4 * g4 + 2] * inv, o0[4 * g4 + 3] * inv};
@@ -307,8 +310,8 @@ template <bool MORE_, bool KCL_, bool VCL_, bool COPY_> struct A3Flags {
 
 template <bool SPLIT_OUT, int TERMS>
 __global__ __launch_bounds__(A3_NW * 64, 2) void attn_bf16x3_pipe_kernel(const unsigned char* __restrict__ img, float* __restrict__ out,
-                                                                         int Bt, int N, int Npad, int H, int n_query, int nqb,
-                                                                         float s_inv2, float v_inv, float o_scale, int out_tok) {
+                                                                         int Bt, int N, int Npad, int H, int n_query_max, int nqb,
+                                                                         float s_inv2, float v_inv, float o_scale, RowSegs oseg) {
     constexpr int NW = A3_NW, ROWB = QKV3_ROWB;
     constexpr bool F16 = TERMS == 3;
     constexpr int NPL = s3_planes(TERMS);
@@ -325,6 +328,9 @@ __global__ __launch_bounds__(A3_NW * 64, 2) void attn_bf16x3_pipe_kernel(const u
         h = (w / nqb) % H;
         b = w / (nqb * H);
     }
+    // query rows of this block's sample (block-uniform): the output layout may give the later samples fewer rows (RowSegs)
+    const int seg_tok = oseg.tok[b < oseg.samples[0] ? 0 : 1], n_query = n_query_max < seg_tok ? n_query_max : seg_tok;
+    if (qb * (A3_NW * 32) >= n_query) return;      // no query row of this sample in this block
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // provably wave-uniform: what derives from it stays scalar
     const int l31 = lane & 31, hi = lane >> 5;
@@ -637,12 +643,12 @@ __global__ __launch_bounds__(A3_NW * 64, 2) void attn_bf16x3_pipe_kernel(const u
                 v[4 + e] = hi ? ch[c + 1][e] : recv;
             }
             if (q_row < n_query) {
-                if constexpr (F16) store_split8_h2(o3, (int64_t)b * out_tok + q_row, h * A3_DH + 8 * (c + hi), d, v, o_scale);
-                else store_split8(o3, (int64_t)b * out_tok + q_row, h * A3_DH + 8 * (c + hi), d, v);
+                if constexpr (F16) store_split8_h2(o3, oseg.row(b, q_row), h * A3_DH + 8 * (c + hi), d, v, o_scale);
+                else store_split8(o3, oseg.row(b, q_row), h * A3_DH + 8 * (c + hi), d, v);
             }
         }
     } else if (q_row < n_query) {
-        float* dst = out + ((int64_t)b * out_tok + q_row) * d + h * A3_DH + 4 * hi;
+        float* dst = out + (oseg.row(b, q_row)) * d + h * A3_DH + 4 * hi;
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
             f32x4 a = {o0[4 * g4] * inv, o0[4 * g4 + 1] * inv, o0[4 * g4 + 2] * inv, o0[4 * g4 + 3] * inv};
@@ -678,8 +684,8 @@ struct S16 { f32x4t t[4][2]; };       // scores / probabilities of one 64-key ti
 
 template <bool SPLIT_OUT, int TERMS>
 __global__ __launch_bounds__(A3_NW * 64, 2) void attn_bf16x3_p16_kernel(const unsigned char* __restrict__ img, float* __restrict__ out,
-                                                                        int Bt, int N, int Npad, int H, int n_query, int nqb,
-                                                                        float s_inv2, float v_inv, float o_scale, int out_tok) {
+                                                                        int Bt, int N, int Npad, int H, int n_query_max, int nqb,
+                                                                        float s_inv2, float v_inv, float o_scale, RowSegs oseg) {
     constexpr int NW = A3_NW, ROWB = QKV3_ROWB;
     constexpr bool F16 = TERMS == 3;
     constexpr int NPL = s3_planes(TERMS);
@@ -696,6 +702,9 @@ __global__ __launch_bounds__(A3_NW * 64, 2) void attn_bf16x3_p16_kernel(const un
         h = (w / nqb) % H;
         b = w / (nqb * H);
     }
+    // query rows of this block's sample (block-uniform): the output layout may give the later samples fewer rows (RowSegs)
+    const int seg_tok = oseg.tok[b < oseg.samples[0] ? 0 : 1], n_query = n_query_max < seg_tok ? n_query_max : seg_tok;
+    if (qb * (A3_NW * 32) >= n_query) return;      // no query row of this sample in this block
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, kq = lane >> 4;
@@ -1022,10 +1031,10 @@ __global__ __launch_bounds__(A3_NW * 64, 2) void attn_bf16x3_p16_kernel(const un
         const int col = h * A3_DH + 16 * dt + 8 * (kq >> 1);
         if (q_row < n_query) {
             if constexpr (SPLIT_OUT) {
-                if constexpr (F16) store_split8_h2(o3, (int64_t)b * out_tok + q_row, col, d, v, o_scale);
-                else store_split8(o3, (int64_t)b * out_tok + q_row, col, d, v);
+                if constexpr (F16) store_split8_h2(o3, oseg.row(b, q_row), col, d, v, o_scale);
+                else store_split8(o3, oseg.row(b, q_row), col, d, v);
             } else {
-                float* dst = out + ((int64_t)b * out_tok + q_row) * d + col;
+                float* dst = out + (oseg.row(b, q_row)) * d + col;
                 *reinterpret_cast<f32x4*>(dst) = f32x4{v[0], v[1], v[2], v[3]};
                 *reinterpret_cast<f32x4*>(dst + 4) = f32x4{v[4], v[5], v[6], v[7]};
             }
@@ -1038,40 +1047,44 @@ int64_t qkv3_bytes(int B, int N, int H) { return (int64_t)3 * B * H * qkv3_npad(
 // out3 != null: split3 image of the [B*N, H*64] result; otherwise fp32 out [B, N, H*64]
 template <int TERMS>
 static void attn3_launch(const unsigned char* img, float* out, void* out3, int B, int N, int Npad, int H, int n_query, int nqb, hipStream_t st,
-                         float img_scale, float out_scale, int out_tok) {
+                         float img_scale, float out_scale, const RowSegs& oseg) {
     const float s_inv2 = 1.0f / (img_scale * img_scale), v_inv = 1.0f / img_scale;
     // the pipelined kernel pays for the exact three-plane modes (C3: 175 -> 170 us per launch, profiles/r04_attn_pipe.txt); with two fp16
     // planes or one bf16 plane a tile has half / a sixth of the MFMAs to hide the VALU work behind and the plain kernel is as fast or faster
     if (g_attn_m16 && (TERMS == 6 || TERMS == 9 || g_attn_m16 == 2)) {
         if (out3)
             hipLaunchKernelGGL((attn_bf16x3_p16_kernel<true, TERMS>), dim3(nqb * H * B), dim3(A3_NW * 64), 0, st, img, static_cast<float*>(out3),
-                               B, N, Npad, H, n_query, nqb, s_inv2, v_inv, out_scale, out_tok);
+                               B, N, Npad, H, n_query, nqb, s_inv2, v_inv, out_scale, oseg);
         else
             hipLaunchKernelGGL((attn_bf16x3_p16_kernel<false, TERMS>), dim3(nqb * H * B), dim3(A3_NW * 64), 0, st, img, out, B, N, Npad, H,
-                               n_query, nqb, s_inv2, v_inv, out_scale, out_tok);
+                               n_query, nqb, s_inv2, v_inv, out_scale, oseg);
         return;
     }
     if (g_attn_pipe == 2 || (g_attn_pipe == 1 && (TERMS == 6 || TERMS == 9))) {
         if (out3)
             hipLaunchKernelGGL((attn_bf16x3_pipe_kernel<true, TERMS>), dim3(nqb * H * B), dim3(A3_NW * 64), 0, st, img, static_cast<float*>(out3),
-                               B, N, Npad, H, n_query, nqb, s_inv2, v_inv, out_scale, out_tok);
+                               B, N, Npad, H, n_query, nqb, s_inv2, v_inv, out_scale, oseg);
         else
             hipLaunchKernelGGL((attn_bf16x3_pipe_kernel<false, TERMS>), dim3(nqb * H * B), dim3(A3_NW * 64), 0, st, img, out, B, N, Npad, H,
-                               n_query, nqb, s_inv2, v_inv, out_scale, out_tok);
+                               n_query, nqb, s_inv2, v_inv, out_scale, oseg);
         return;
     }
     if (out3)
         hipLaunchKernelGGL((attn_bf16x3_kernel<true, TERMS>), dim3(nqb * H * B), dim3(A3_NW * 64), 0, st, img, static_cast<float*>(out3), B, N,
-                           Npad, H, n_query, nqb, s_inv2, v_inv, out_scale, out_tok);
+                           Npad, H, n_query, nqb, s_inv2, v_inv, out_scale, oseg);
     else
         hipLaunchKernelGGL((attn_bf16x3_kernel<false, TERMS>), dim3(nqb * H * B), dim3(A3_NW * 64), 0, st, img, out, B, N, Npad, H, n_query, nqb,
-                           s_inv2, v_inv, out_scale, out_tok);
+                           s_inv2, v_inv, out_scale, oseg);
 }
 
 int attn_bf16x3(const void* qkv3, float* out, void* out3, int B, int N, int H, int n_query, int terms, hipStream_t st, float img_scale,
-                float out_scale, int out_tokens) {
+                float out_scale, int out_tokens, const RowSegs* out_rows) {
     const int out_tok = out_tokens > 0 ? out_tokens : N;
     AVD_REQUIRE(out_tok >= n_query, AVD_EINVAL, "attn_bf16x3: out_tokens=%d < n_query=%d", out_tok, n_query);
+    AVD_REQUIRE(!out_rows || (out_rows->n_samples() == B && out_rows->samples[0] > 0 && out_rows->tok[0] > 0 && out_rows->tok[1] > 0 &&
+                              out_rows->m0 == (int64_t)out_rows->samples[0] * out_rows->tok[0]), AVD_EINVAL,
+                "attn_bf16x3: the output row layout does not hold the batch's %d samples", B);
+    const RowSegs oseg = out_rows ? *out_rows : RowSegs::uniform(B, out_tok);
     AVD_REQUIRE(terms == 0 || terms == 6 || terms == 9 || terms == 1 || terms == 3, AVD_EINVAL, "attn_bf16x3: terms must be 6, 9, 1 or 3, got %d", terms);
     AVD_REQUIRE(img_scale > 0.f && img_scale < __builtin_inff() && out_scale > 0.f && out_scale < __builtin_inff() &&
                     img_scale * img_scale < __builtin_inff(), AVD_EINVAL, "attn_bf16x3: image scales must be positive and finite");
@@ -1087,10 +1100,10 @@ int attn_bf16x3(const void* qkv3, float* out, void* out3, int B, int N, int H, i
     ProfScope prof(tag, 4.0 * (double)B * H * (double)n_query * N * A3_DH, st);
     const int Npad = qkv3_npad(N);
     const auto* img = static_cast<const unsigned char*>(qkv3);
-    if (terms == 9) attn3_launch<9>(img, out, out3, B, N, Npad, H, n_query, nqb, st, 1.f, 1.f, out_tok);
-    else if (terms == 1) attn3_launch<1>(img, out, out3, B, N, Npad, H, n_query, nqb, st, 1.f, 1.f, out_tok);
-    else if (terms == 3) attn3_launch<3>(img, out, out3, B, N, Npad, H, n_query, nqb, st, img_scale, out_scale, out_tok);
-    else attn3_launch<6>(img, out, out3, B, N, Npad, H, n_query, nqb, st, 1.f, 1.f, out_tok);
+    if (terms == 9) attn3_launch<9>(img, out, out3, B, N, Npad, H, n_query, nqb, st, 1.f, 1.f, oseg);
+    else if (terms == 1) attn3_launch<1>(img, out, out3, B, N, Npad, H, n_query, nqb, st, 1.f, 1.f, oseg);
+    else if (terms == 3) attn3_launch<3>(img, out, out3, B, N, Npad, H, n_query, nqb, st, img_scale, out_scale, oseg);
+    else attn3_launch<6>(img, out, out3, B, N, Npad, H, n_query, nqb, st, 1.f, 1.f, oseg);
     AVD_CHECK_LAUNCH("attn_bf16x3");
     return AVD_OK;
 }

@@ -84,6 +84,28 @@ struct RowMap {
     }
 };
 
+// Row layout of a stacked batch: samples[0] samples of tok[0] rows each (rows 0 .. m0 - 1), then samples[1] samples of tok[1] rows each.
+// Every kernel that turns a row index into (sample, token) — or back — takes this.  One segment (uniform) is the plain [samples, tok]
+// batch; two are the CFG step without the null half's duplicate prompt rows (composite.hip: cond samples of N rows, null samples of
+// Nt + 1).  Rows < 2^31; a row at or past rows() locates to a sample / token nobody stores to.
+struct RowSegs {
+    int64_t m0;
+    int tok[2], samples[2];
+    static RowSegs uniform(int samples, int tok) { return RowSegs{(int64_t)samples * tok, {tok, tok}, {samples, 0}}; }
+    __host__ __device__ __forceinline__ int64_t rows() const { return m0 + (int64_t)samples[1] * tok[1]; }
+    __host__ __device__ __forceinline__ int n_samples() const { return samples[0] + samples[1]; }
+    __host__ __device__ __forceinline__ void locate(int64_t m, int& sample, int& token) const {
+        const bool s1 = m >= m0;
+        const unsigned r = (unsigned)(s1 ? m - m0 : m), t = (unsigned)(s1 ? tok[1] : tok[0]);
+        const unsigned b = r / t;
+        sample = (int)b + (s1 ? samples[0] : 0);
+        token = (int)(r - b * t);
+    }
+    __host__ __device__ __forceinline__ int64_t row(int sample, int token) const {
+        return sample < samples[0] ? (int64_t)sample * tok[0] + token : m0 + (int64_t)(sample - samples[0]) * tok[1] + token;
+    }
+};
+
 // A operand of a GEMM gathered straight from a video latent [B, C, T, H, W] in tube-token order (ops.py:100-127
 // tube_patch_video: token n = ((T/t index) * H/h + H/h index) * W/w + W/w index, element k = ((c * t + dt) * h + dy) * w + dx):
 // logical A[row = b * Nt + n][k] = z[b][c][nt*t + dt][ny*h + dy][nx*w + dx].  w % 4 == 0 and W % 4 == 0 keep every float4 along k
@@ -301,8 +323,10 @@ extern int g_s3_sn, g_s3_super4, g_s3_super8;      // super-tile shape overrides
 extern int g_s3_tile;            // -1 = per epilogue; 0 / 1 = 8-wave 256x256 / 4-wave 256x128 blocks (avd_tune_set "s3_tile")
 extern thread_local bool t_s3_two_streams;
 // terms == 3 (f16x2): ab_scale = (A image scale) x (W image scale), c_scale = scale of the image written (if one is written)
-int gemm_bf16x3_qkv3(const void* A3, const void* W3, const float* bias, void* img, int64_t M, int tokens, int heads, int K, float qscale,
-                     int terms, hipStream_t st, float ab_scale = 1.f, float c_scale = 1.f, const float* ss_in = nullptr, float eps = 0.f);
+// seg: the rows' (sample, token) layout; the image keeps qkv3_npad(longest segment's tokens) slots per (sample, head)
+int gemm_bf16x3_qkv3(const void* A3, const void* W3, const float* bias, void* img, const RowSegs& seg, int heads, int K, float qscale,
+                     int terms, hipStream_t st, float ab_scale = 1.f, float c_scale = 1.f, const float* ss_in = nullptr, float eps = 0.f,
+                     int64_t plan_rows = 0);
 int64_t qkv3_bytes(int B, int N, int H);
 // fp8 attention (attn_fp8.hip): reads the same qkv3 image, needs attn_fp8_ws_bytes(B, N, H) of scratch
 int64_t attn_fp8_ws_bytes(int B, int N, int H);
@@ -311,11 +335,15 @@ int attn_fp8(const void* qkv3, void* ws, int64_t ws_bytes, float* out, void* out
 // terms == 3: img_scale = scale of the qkv image, out_scale = scale of the image written to out3
 // out_tokens (0 = N): rows per sample of the output — n_query <= out_tokens: the last block writes its target rows compactly
 int attn_bf16x3(const void* qkv3, float* out, void* out3, int B, int N, int H, int n_query, int terms, hipStream_t st,
-                float img_scale = 1.f, float out_scale = 1.f, int out_tokens = 0);
+                float img_scale = 1.f, float out_scale = 1.f, int out_tokens = 0, const RowSegs* out_rows = nullptr);
+// out_rows != null: sample b's query q goes to output row out_rows->row(b, q) and the sample runs min(n_query, its segment's tokens)
+// queries — one launch for a batch whose later samples carry fewer rows; all samples attend to their N key slots of the image
 int gemm_bf16x3(const void* A3, const void* W3, const float* bias, const float* R, float* C, void* C3, int64_t M, int N, int K,
                 int act, int terms, hipStream_t st, float ab_scale = 1.f, float c_scale = 1.f, const float* ss_in = nullptr, float eps = 0.f,
-                float* ss_out = nullptr, const float* gamma = nullptr, int r_seg = 0, int r_stride = 0);
-// r_seg > 0 (fp32 + image residual epilogue of the six-term 16x16x32 kernels): output row m adds R row (m / r_seg) * r_stride + m % r_seg
+                float* ss_out = nullptr, const float* gamma = nullptr, int r_seg = 0, const RowSegs* r_map = nullptr, int64_t plan_rows = 0);
+// plan_rows > M: the kernel family, rows per block and ring depth are chosen as for plan_rows rows (a launch on the two-segment layout
+// takes the kernels of the full layout it stands for)
+// r_seg > 0 (fp32 + image residual epilogue of the six-term 16x16x32 kernels): output row m adds R row r_map->row(m / r_seg, m % r_seg)
 bool gemm_bf16x3_resmap_supported(int terms);
 // gamma != null (f16x2 images, N == 512): C = A W^T + bias + R as fp32 AND C3 = image (scale c_scale) of RMSNorm(C; gamma, eps)
 bool gemm_bf16x3_rownorm_supported(int N, int terms);

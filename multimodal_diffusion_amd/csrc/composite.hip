@@ -76,7 +76,8 @@ int audio_tokens_f32(const float* z, float* tok, int B, int Ca, int F, int len, 
 int assemble_f32(float* X2, const float* temb, const float* Xp, int B, int N, int d, int tdim, int Nt, int Np,
                  int target_first, hipStream_t st);
 int assemble_rows_f32(float* X2, const int64_t* t_now, const float* freqs, const float* Xp, float* ss, int B, int N, int d, int tdim,
-                      int Nt, int Np, int target_first, float max_period, hipStream_t st);
+                      int Nt, int Np, int target_first, float max_period, hipStream_t st, const RowSegs* short_null = nullptr);
+int qkv3_replicate(void* img, int img_samples, int H, int n_keys, int first_sample, int n_samples, int src, hipStream_t st);
 int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key = nullptr,
@@ -188,6 +189,18 @@ static bool core_use_fold(const avd_core_weights* w) {
 static int g_core_trim = 1;
 static int64_t core_trim_floats(const avd_core_weights* w, int B, int N) { return (int64_t)B * N * w->d; }
 
+// The null CFG half without its duplicate prompt rows (avd_cfg_dedup_set / AVD_CFG_DEDUP, default on).  With the target rows first the
+// null half of the stacked step is cat([target rows, zero rows]): every prompt row of a null sample is the zero row at the input,
+// RMSNorm, the projections and the MLP act per row, and the rows of one sample attend to the same keys — so the Np prompt rows of a
+// null sample are one and the same row after every block.  The step then carries ONE of them: cond samples of N rows, null samples
+// of Nt + 1 rows (RowSegs), with its k and v copied into the key slots of the other Np - 1 before each attention, which therefore sees
+// the N keys and values of the full layout.  Bit-identical to the full route; what it takes is listed at core_dedup_ok.
+static int g_cfg_dedup = 1;
+[[maybe_unused]] static const bool g_cfg_dedup_env_applied = [] {
+    if (const char* e = getenv("AVD_CFG_DEDUP")) g_cfg_dedup = atoll(e) != 0;
+    return true;
+}();
+
 // the wide scratch of the bf16x3 path holds the qkv3 image, then the fc1 image
 static int64_t core_split_wide_bytes(const avd_core_weights* w, int B, int N) {
     const int64_t qkv3 = qkv3_bytes(B, N, w->n_heads), fc1 = split3_bytes((int64_t)B * N, w->mlp_hidden);
@@ -245,9 +258,22 @@ static int core_norm(const avd_core_weights* w, const float* x, const float* sca
     return layernorm_act_f32(x, scale, bias, y, M, w->d, w->norm_eps, AVD_ACT_NONE, st);
 }
 
+// Can core_forward run a stacked batch of B2 samples whose second half keeps n_out + 1 of its N rows (segs below)?  The folded split
+// path in its six- or nine-term mode with the trimmed last block and its residual row map — which exists on the six-term 16x16x32
+// kernels only (gemm_bf16x3_resmap_supported), so the nine-term mode runs the full layout until it has one; the kernel family is the
+// one the full B2 x N rows take.
+static bool core_dedup_ok(const avd_core_weights* w, int B2, int N, int n_out) {
+    const int terms = w->split_terms;
+    return B2 % 2 == 0 && n_out > 0 && n_out + 2 <= N && w->attn_mode == 0 && (terms == 0 || terms == 6 || terms == 9) && g_core_trim &&
+           !g_mlp_fused && gemm_bf16x3_resmap_supported(terms) && core_use_split(w, (int64_t)B2 * N) && core_use_split_fold(w);
+}
+
+// segs != null (core_dedup_ok holds, out_row0 == 0): x is that two-segment layout — samples 0 .. segs->samples[0] - 1 with N rows, the others
+// with n_out_rows + 1 (the last one stands for the N - n_out_rows equal rows of the full layout) — and y receives the normalised
+// output rows compactly, [B * n_out_rows, d], instead of the [B, N, d] layout.  Kernel families and workspace follow the full B x N.
 static int core_forward(const avd_core_weights* w, const float* x, float* y, int B, int N, int out_row0,
                         int n_out_rows, const unsigned char* kpm, void* ws, int64_t ws_bytes, hipStream_t st,
-                        const float* ss_first = nullptr) {
+                        const float* ss_first = nullptr, const RowSegs* segs = nullptr) {
     if (int rc = check_core(w)) return rc;
     AVD_REQUIRE(x && y && B > 0 && N > 0, AVD_EINVAL, "core: bad input");
     AVD_REQUIRE(out_row0 >= 0 && n_out_rows > 0 && out_row0 + n_out_rows <= N, AVD_EINVAL, "core: bad output row window");
@@ -266,6 +292,10 @@ static int core_forward(const avd_core_weights* w, const float* x, float* y, int
     // explicit reduced-precision request and is refused rather than silently replaced.
     AVD_REQUIRE(!(w->attn_mode == 1 && (kpm || w->norm_kind != 0)), AVD_EUNSUPPORTED,
                 "core: attn_mode 1 (fp8 attention) cannot be combined with a key_padding_mask or norm_kind 1 (LayerNorm)");
+    const int null_from = segs ? segs->samples[0] : 0;
+    AVD_REQUIRE(!segs || (null_from > 0 && segs->n_samples() == B && segs->tok[0] == N && segs->tok[1] == n_out_rows + 1 &&
+                          segs->m0 == (int64_t)null_from * N && out_row0 == 0 && !kpm && core_dedup_ok(w, B, N, n_out_rows)), AVD_EUNSUPPORTED,
+                "core: the two-segment row layout needs the folded six-term split path with the trimmed last block");
     AVD_REQUIRE(!(w->attn_mode == 1 && !core_use_split(w, M)), AVD_EUNSUPPORTED,
                 "core: attn_mode 1 (fp8 attention) reads the q|k|v image of the split-operand projections, which these weights / shapes "
                 "do not take (every block needs its *_weight3 images; 3 d, d and mlp_hidden must be multiples of 256, d of 16)");
@@ -295,18 +325,28 @@ static int core_forward(const avd_core_weights* w, const float* x, float* y, int
             // fc1 -> GELU -> fc2 as one launch (mlp_bf16x3.hip; off by default: it measures slower)
             const bool fused = g_mlp_fused && !ns && mlp_bf16x3_supported(d, hid, terms) && gemm_bf16x3_resmap_supported(terms);
             AVD_REQUIRE(cs.ok, AVD_EWORKSPACE, "core: workspace carve %lld > %lld bytes", (long long)cs.used, (long long)cs.cap);
-            if (int rc = split3_rows_f32(cur, rd, hx, M, d, st, 0.f, ss)) return rc;
+            // rows that run: all B x N, or the caller's two segments
+            const RowSegs seg = segs ? *segs : RowSegs::uniform(B, N);
+            const int64_t Mr = seg.rows();
+            const float qscale = scale * 1.4426950408889634f;
+            // in_proj of block b into the q|k|v image (N key slots per sample in either layout); the short samples' last row is the
+            // k and v of the slots behind it as well
+            auto in_proj = [&](const avd_block_weights& b) {
+                if (int rc = gemm_bf16x3_qkv3(hx, b.in_proj_weight3n, b.in_proj_bias, qkv, seg, H, d, qscale, terms, st, 1.f, 1.f, ss, w->norm_eps, M))
+                    return rc;
+                return null_from ? qkv3_replicate(qkv, B, H, N, null_from, B - null_from, n_out_rows, st) : (int)AVD_OK;
+            };
+            if (int rc = split3_rows_f32(cur, rd, hx, Mr, d, st, 0.f, ss)) return rc;
             for (int l = 0; l < w->n_layers; ++l) {
                 const avd_block_weights& b = w->blocks[l];
                 const bool last = l == w->n_layers - 1;
                 const int nq = (last && out_row0 == 0) ? n_out_rows : N;
                 if (last && trim) {
                     const int64_t Mc = (int64_t)B * nq;
-                    if (int rc = gemm_bf16x3_qkv3(hx, b.in_proj_weight3n, b.in_proj_bias, qkv, M, N, H, d, scale * 1.4426950408889634f, terms, st,
-                                                  1.f, 1.f, ss, w->norm_eps)) return rc;
+                    if (int rc = in_proj(b)) return rc;
                     if (int rc = attn_bf16x3(qkv, nullptr, hs, B, N, H, nq, terms, st, 1.f, 1.f, nq)) return rc;       // rows b * nq + q
                     if (int rc = gemm_bf16x3(hs, b.out_proj_weight3, b.out_proj_bias, cur, yc, hx, Mc, d, d, AVD_ACT_NONE, terms, st, 1.f, 1.f,
-                                             nullptr, 0.f, ss, nullptr, nq, N)) return rc;                                  // residual rows b * N + q
+                                             nullptr, 0.f, ss, nullptr, nq, &seg)) return rc;                               // residual rows seg.row(b, q)
                     if (fused) {
                         if (int rc = mlp_bf16x3(hx, b.fc1_weight3n, b.fc1_bias, b.fc2_weight3, b.fc2_bias, ss, w->norm_eps, yc, yc, nullptr, nullptr, Mc,
                                                 d, hid, st)) return rc;
@@ -320,37 +360,40 @@ static int core_forward(const avd_core_weights* w, const float* x, float* y, int
                             if (int rc = gemm_bf16x3(wide3, b.fc2_weight3, b.fc2_bias, yc, yc, nullptr, Mc, d, hid, AVD_ACT_NONE, terms, st)) return rc;
                         }
                     }
-                    // final norm from the compact rows into the caller's [B, N, d] layout (rows outside the window stay as they were)
-                    return rmsnorm_f32(yc, rd, w->final_norm_scale, y, RowMap{d, nq, (int64_t)N * d}, Mc, d, w->norm_eps, st);
+                    // final norm from the compact rows into the caller's [B, N, d] layout (rows outside the window stay as they were);
+                    // the two-segment layout has no such rows to keep: its caller takes the compact rows
+                    return rmsnorm_f32(yc, rd, w->final_norm_scale, y, null_from ? rd : RowMap{d, nq, (int64_t)N * d}, Mc, d, w->norm_eps, st);
                 }
-                if (int rc = gemm_bf16x3_qkv3(hx, b.in_proj_weight3n, b.in_proj_bias, qkv, M, N, H, d, scale * 1.4426950408889634f, terms, st,
-                                              1.f, 1.f, ss, w->norm_eps)) return rc;
+                if (int rc = in_proj(b)) return rc;
                 if (w->attn_mode == 1) {
                     if (int rc = attn_fp8(qkv, f8w, f8_b, nullptr, hs, B, N, H, nq, st, terms, 1.f, 1.f)) return rc;
+                } else if (null_from) {
+                    // the short samples run their n_out_rows + 1 queries against their N keys and write behind row seg.m0
+                    if (int rc = attn_bf16x3(qkv, nullptr, hs, B, N, H, N, terms, st, 1.f, 1.f, 0, &seg)) return rc;
                 } else {
                     if (int rc = attn_bf16x3(qkv, nullptr, hs, B, N, H, nq, terms, st, 1.f, 1.f)) return rc;
                 }
-                if (int rc = gemm_bf16x3(hs, b.out_proj_weight3, b.out_proj_bias, cur, y, hx, M, d, d, AVD_ACT_NONE, terms, st, 1.f, 1.f, nullptr,
-                                         0.f, ss)) return rc;
+                if (int rc = gemm_bf16x3(hs, b.out_proj_weight3, b.out_proj_bias, cur, y, hx, Mr, d, d, AVD_ACT_NONE, terms, st, 1.f, 1.f, nullptr,
+                                         0.f, ss, nullptr, 0, nullptr, M)) return rc;
                 cur = y;
                 if (fused) {
                     if (int rc = mlp_bf16x3(hx, b.fc1_weight3n, b.fc1_bias, b.fc2_weight3, b.fc2_bias, ss, w->norm_eps, y, y, last ? nullptr : hx,
-                                            last ? nullptr : ss, M, d, hid, st)) return rc;
+                                            last ? nullptr : ss, Mr, d, hid, st)) return rc;
                     continue;
                 }
-                if (int rc = gemm_bf16x3(hx, b.fc1_weight3n, b.fc1_bias, nullptr, nullptr, wide3, M, hid, d, AVD_ACT_GELU, terms, st, 1.f, 1.f, ss,
-                                         w->norm_eps)) return rc;
+                if (int rc = gemm_bf16x3(hx, b.fc1_weight3n, b.fc1_bias, nullptr, nullptr, wide3, Mr, hid, d, AVD_ACT_GELU, terms, st, 1.f, 1.f, ss,
+                                         w->norm_eps, nullptr, nullptr, 0, nullptr, M)) return rc;
                 if (ns) {       // too few blocks for the chip: K slices + a deterministic reduction that writes what the epilogue would
-                    if (int rc = gemm_bf16x3_splitk(wide3, b.fc2_weight3, b.fc2_bias, y, y, last ? nullptr : hx, last ? nullptr : ss, M, d, hid,
+                    if (int rc = gemm_bf16x3_splitk(wide3, b.fc2_weight3, b.fc2_bias, y, y, last ? nullptr : hx, last ? nullptr : ss, Mr, d, hid,
                                                     terms, ns, part, st)) return rc;
                 } else if (last) {     // nothing reads the stream's image after the last block: the final norm takes the fp32 rows
-                    if (int rc = gemm_bf16x3(wide3, b.fc2_weight3, b.fc2_bias, y, y, nullptr, M, d, hid, AVD_ACT_NONE, terms, st)) return rc;
+                    if (int rc = gemm_bf16x3(wide3, b.fc2_weight3, b.fc2_bias, y, y, nullptr, Mr, d, hid, AVD_ACT_NONE, terms, st)) return rc;
                 } else {
-                    if (int rc = gemm_bf16x3(wide3, b.fc2_weight3, b.fc2_bias, y, y, hx, M, d, hid, AVD_ACT_NONE, terms, st, 1.f, 1.f, nullptr, 0.f,
-                                             ss)) return rc;
+                    if (int rc = gemm_bf16x3(wide3, b.fc2_weight3, b.fc2_bias, y, y, hx, Mr, d, hid, AVD_ACT_NONE, terms, st, 1.f, 1.f, nullptr, 0.f,
+                                             ss, nullptr, 0, nullptr, M)) return rc;
                 }
             }
-            return rmsnorm_f32(y, rd, w->final_norm_scale, y, rd, M, d, w->norm_eps, st);
+            return rmsnorm_f32(y, rd, w->final_norm_scale, y, rd, Mr, d, w->norm_eps, st);
         }
         // f16x2 with d = 512: out_proj / fc2 own whole rows and write the NEXT norm's output image themselves (EPI_RES_NORM); the only
         // norm kernel left before the final norm is the first block's norm1
@@ -368,7 +411,7 @@ static int core_forward(const avd_core_weights* w, const float* x, float* y, int
             const float w_in = h2 ? fs[0] : 1.f, w_out = h2 ? fs[1] : 1.f, w_fc1 = h2 ? fs[2] : 1.f, w_fc2 = h2 ? fs[3] : 1.f;
             if (!rown || l == 0)
                 if (int rc = rmsnorm_split3_f32(cur, b.norm1_scale, hn, M, d, w->norm_eps, st, s_n1)) return rc;
-            if (int rc = gemm_bf16x3_qkv3(hn, b.in_proj_weight3, b.in_proj_bias, qkv, M, N, H, d, scale * 1.4426950408889634f, terms, st,
+            if (int rc = gemm_bf16x3_qkv3(hn, b.in_proj_weight3, b.in_proj_bias, qkv, RowSegs::uniform(B, N), H, d, scale * 1.4426950408889634f, terms, st,
                                           h2 ? s_n1 * w_in : 1.f, s_qkv)) return rc;
             if (w->attn_mode == 1) {
                 if (int rc = attn_fp8(qkv, f8w, f8_b, nullptr, hs, B, N, H, nq, st, terms, s_qkv, s_qkv)) return rc;
@@ -559,11 +602,15 @@ static int64_t embed_ws_floats(const avd_embed_desc* e) {
 // ss_out (optional, concat mode): per-row sums of squares of the finished X2, [2B*N] — spares MMDiT's first folded norm its pass
 // cond_only: the single-branch front end of a cond-only step — X2 is [B, N, d] (ss_out [B*N]), the cond half alone, bit-identical to
 // the cond half of the pair; the adapter GEMM is the same launch, only the assembly pass is the B*N-row form
+// short_null (concat mode, target rows first): the null half keeps one prompt row per sample — X2 is that two-segment layout, B samples
+// of N rows and then B samples of Nt + 1 (ss_out alike)
 static int embed_cfg_pair(const avd_embed_desc* e, const float* z, const float* Wt, const float* bt,
                           const int64_t* t_now, const float* Xp, float* tok_ws, float* X2, hipStream_t st, float* ss_out = nullptr,
-                          bool cond_only = false) {
+                          bool cond_only = false, const RowSegs* short_null = nullptr) {
     if (int rc = check_embed(e)) return rc;
     AVD_REQUIRE(z && Wt && t_now && tok_ws && X2 && (e->Np == 0 || Xp), AVD_EINVAL, "embed: null pointer");
+    AVD_REQUIRE(!short_null || (!cond_only && !e->temb_add && e->target_first && e->Np >= 1), AVD_EINVAL,
+                "embed: the short null half is the concat-mode CFG pair with the target rows first");
     const int B = e->B, d = e->d, N = e->Nt + e->Np, D = embed_tok_dim(e);
     float* tok = tok_ws;
     float* temb = tok_ws + align_up((int64_t)B * e->Nt * D * 4) / 4;
@@ -597,7 +644,8 @@ static int embed_cfg_pair(const avd_embed_desc* e, const float* z, const float* 
     // timestep columns, null-half copies, prompt rows and the rows' sums of squares in one pass
     if (cond_only)
         return assemble_rows_cond_f32(X2, t_now, e->temb_freqs, Xp, ss_out, B, N, d, e->tdim, e->Nt, e->Np, e->target_first, 10000.f, st);
-    return assemble_rows_f32(X2, t_now, e->temb_freqs, Xp, ss_out, B, N, d, e->tdim, e->Nt, e->Np, e->target_first, 10000.f, st);
+    return assemble_rows_f32(X2, t_now, e->temb_freqs, Xp, ss_out, B, N, d, e->tdim, e->Nt, e->Np, e->target_first, 10000.f, st,
+                             short_null);
 }
 
 // ---------------------------------------------------------------- one CFG denoising step
@@ -740,6 +788,12 @@ extern "C" int avd_tune_set(const char* key, int64_t value) {
     return set_error(AVD_EINVAL, "tune_set: unknown key '%s'", key);
 }
 
+extern "C" int avd_cfg_dedup_set(int on) {
+    const int prev = g_cfg_dedup;
+    g_cfg_dedup = on != 0;
+    return prev;
+}
+
 extern "C" int avd_device_arch(char* buf, int buflen) {
     AVD_REQUIRE(buf && buflen > 0, AVD_EINVAL, "device_arch: bad buffer");
     hipDeviceProp_t prop;
@@ -815,11 +869,19 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
     const avd_embed_desc& e = s->embed;
     const bool have_ss = !e.temb_add;      // the fused concat front end leaves the rows' sums of squares behind
 
-    if (int rc = embed_cfg_pair(&e, z, s->adapt_w, s->adapt_b, t_now, Xp, tok, X2, st, ssx)) return rc;
+    // the stacked one-stream step in concat mode with the target rows first runs the null half without its Np - 1 duplicate prompt
+    // rows when the core can (g_cfg_dedup); everything else — and every other mode — is the full [2B, N, d] layout
+    const bool dedup = g_cfg_dedup && !s->split_streams && !e.temb_add && e.target_first && e.Np >= 2 && core_dedup_ok(s->core, 2 * e.B, p.N, e.Nt);
+    const RowSegs seg{(int64_t)e.B * p.N, {p.N, e.Nt + 1}, {e.B, e.B}};      // the one definition of the layout: front end and core take it
+    if (int rc = embed_cfg_pair(&e, z, s->adapt_w, s->adapt_b, t_now, Xp, tok, X2, st, ssx, false, dedup ? &seg : nullptr)) return rc;
     const int row0 = e.target_first ? 0 : e.Np;
     // head over the target rows only (per-token independent, so skipping prompt rows is exact)
     const RowMap hm{e.d, e.Nt, (int64_t)p.N * e.d};
-    if (!s->split_streams) {
+    if (dedup) {
+        // the core leaves the 2B x Nt normalised target rows compact at the start of X2
+        if (int rc = core_forward(s->core, X2, X2, 2 * e.B, p.N, 0, e.Nt, nullptr, core_ws, p.core, st, nullptr, &seg)) return rc;
+        if (int rc = head_forward(s->head, X2, RowMap{e.d, 0, 0}, p.rows, eps2, head_ws, p.head, st)) return rc;
+    } else if (!s->split_streams) {
         if (int rc = core_forward(s->core, X2, X2, 2 * e.B, p.N, row0, e.Nt, nullptr, core_ws, p.core, st, have_ss ? ssx : nullptr)) return rc;
         if (int rc = head_forward(s->head, X2 + (int64_t)row0 * e.d, hm, p.rows, eps2, head_ws, p.head, st)) return rc;
     } else {

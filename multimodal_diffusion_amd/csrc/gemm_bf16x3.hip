@@ -271,7 +271,7 @@ __device__ __forceinline__ void s3_epilogue_img_t(const S3Args& g, f32x16 (&acc)
         const int dmodel = g.heads * 64;
         const int part = nbase / dmodel, head = (nbase % dmodel) >> 6;       // a wave's 64 columns are one (part, head)
         mul = part == 0 ? g.qscale : 1.0f;
-        qbase = (((int64_t)part * (g.M / g.tokN)) * g.heads + head) * (int64_t)g.tokNpad * QKV3_ROWB;
+        qbase = (((int64_t)part * g.seg.n_samples()) * g.heads + head) * (int64_t)g.tokNpad * QKV3_ROWB;
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -294,7 +294,8 @@ __device__ __forceinline__ void s3_epilogue_img_t(const S3Args& g, f32x16 (&acc)
         [[maybe_unused]] unsigned char* qrow = nullptr;
         [[maybe_unused]] int qsw = 0;
         if constexpr (EPI == S3_EPI_QKV3) {
-            const unsigned b = (unsigned)m / (unsigned)g.tokN, tok = (unsigned)m - b * (unsigned)g.tokN;      // M < 2^31 (checked by the host)
+            int b, tok;                                   // M < 2^31 (checked by the host)
+            g.seg.locate(m, b, tok);
             const int dmodel = g.heads * 64;
             qrow = g.C3 + qbase + ((int64_t)b * g.heads * g.tokNpad + tok) * QKV3_ROWB;
             qsw = qkv3_swizzle(nbase / dmodel, (int)tok);
@@ -1644,15 +1645,17 @@ static std::optional<int> s3_with_rt(int rt, bool hi_is_default, F&& f) {
 
 template <int EPI, int TERMS>
 static int launch_s3t(const S3Args& a, hipStream_t st) {
+    // the rules below read Mp: a launch that runs fewer rows than the layout it stands for takes that layout's kernels
+    const int64_t Mp = a.M_plan > a.M ? a.M_plan : a.M;
     if constexpr (TERMS == 6 && EPI != S3_EPI_RES_NORM) {
         if (g_s3_m16) {
-            if (s3_tile_for(EPI, a.M, a.N)) {
+            if (s3_tile_for(EPI, Mp, a.N)) {
                 // the noise head's launches (fp32 out with a bias: shared Linears, out_proj; image out: input_proj) when their blocks fit the
                 // CUs once — short blocks, one per CU, on the four-stage ring; EPI_BIAS then runs from the registers (S3_EPI_BIAS_REG)
                 if constexpr (EPI == S3_EPI_BIAS || EPI == S3_EPI_SPLIT || EPI == S3_EPI_RES_IMG) {
                     constexpr int E2 = EPI == S3_EPI_BIAS ? (int)S3_EPI_BIAS_REG : (int)EPI;
-                    const int rt = s3_rt4_for(a.M, a.N, 2);
-                    if ((EPI == S3_EPI_RES_IMG || (a.bias && a.N % 128 == 0)) && s3_deep4_for(a.M, a.N, rt))
+                    const int rt = s3_rt4_for(Mp, a.N, 2);
+                    if ((EPI == S3_EPI_RES_IMG || (a.bias && a.N % 128 == 0)) && s3_deep4_for(Mp, a.N, rt))
                         return *s3_with_rt<2, 8>(rt, true, [&](auto r) { return launch_s3w16<E2, 4, r(), 4>(a, st); });
                     // (in_proj / fc1 on the four-stage ring when their blocks fit the CUs once: measured, no gain — K = 512 is 32 steps, and at
                     // 3,904 rows in_proj's 252 blocks run 62 us two to a CU and 79 us one to a CU; they keep the two-stage ring)
@@ -1661,7 +1664,7 @@ static int launch_s3t(const S3Args& a, hipStream_t st) {
                     }
                 }
                 if constexpr (EPI == S3_EPI_GELU_SPLIT || EPI == S3_EPI_QKV3 || EPI == S3_EPI_RES_IMG) {
-                    const int rt = s3_rt4_for(a.M, a.N, 5);
+                    const int rt = s3_rt4_for(Mp, a.N, 5);
                     if (const auto rc = s3_with_rt<5, 7>(rt, false, [&](auto r) { return launch_s3w16<EPI, 4, r()>(a, st); })) return *rc;
                 }
                 return launch_s3w16<EPI, 4>(a, st);
@@ -1669,7 +1672,7 @@ static int launch_s3t(const S3Args& a, hipStream_t st) {
             // one block per CU: the 128 x 128 wave tile for the image epilogues ("s3_w128"), else 8 waves; 192 / 224-row blocks for the
             // residual + image epilogue (s3_rt8_for; 192 rows exist on the 128 x 128 wave tile only)
             constexpr bool RI = EPI == S3_EPI_RES_IMG;
-            const int rt = RI ? s3_rt8_for(a.M, a.N) : 8;
+            const int rt = RI ? s3_rt8_for(Mp, a.N) : 8;
             if constexpr (RI || EPI == S3_EPI_GELU_SPLIT || EPI == S3_EPI_SPLIT || EPI == S3_EPI_QKV3) {
                 if (g_s3_w128) return *s3_with_rt<RI ? 6 : 7, 8>(rt, true, [&](auto r) { return launch_s3w128<EPI, r()>(a, st); });
             }
@@ -1683,7 +1686,7 @@ static int launch_s3t(const S3Args& a, hipStream_t st) {
         if constexpr (TERMS == 3) return launch_s3w<EPI, 3, 8>(a, st);
         else AVD_REQUIRE(false, AVD_EUNSUPPORTED, "gemm_bf16x3: the residual + RMSNorm epilogue exists for f16x2 images only");
     } else {
-        return s3_tile_for(EPI, a.M, a.N) ? launch_s3w<EPI, TERMS, 4>(a, st) : launch_s3w<EPI, TERMS, 8>(a, st);
+        return s3_tile_for(EPI, Mp, a.N) ? launch_s3w<EPI, TERMS, 4>(a, st) : launch_s3w<EPI, TERMS, 8>(a, st);
     }
 }
 
@@ -1716,8 +1719,9 @@ static S3Args s3_args(const void* A3, const void* W3, int64_t M, int N, int K, i
 
 int gemm_bf16x3(const void* A3, const void* W3, const float* bias, const float* R, float* C, void* C3, int64_t M, int N, int K,
                 int act, int terms, hipStream_t st, float ab_scale, float c_scale, const float* ss_in, float eps, float* ss_out,
-                const float* gamma, int r_seg, int r_stride) {
-    AVD_REQUIRE(r_seg == 0 || (r_seg > 0 && r_stride >= r_seg && ss_out && gemm_bf16x3_resmap_supported(terms) && M < (1ll << 31)), AVD_EUNSUPPORTED,
+                const float* gamma, int r_seg, const RowSegs* r_map, int64_t plan_rows) {
+    AVD_REQUIRE(r_seg == 0 || (r_seg > 0 && r_map && r_map->tok[0] >= r_seg && r_map->tok[1] >= r_seg && M == (int64_t)r_map->n_samples() * r_seg &&
+                               ss_out && gemm_bf16x3_resmap_supported(terms) && r_map->rows() < (1ll << 31)), AVD_EUNSUPPORTED,
                 "gemm_bf16x3: a residual row map needs the fp32 + image residual epilogue of the six-term 16x16x32 kernels");
     AVD_REQUIRE(A3 && W3 && (C || C3), AVD_EINVAL, "gemm_bf16x3: null pointer");
     AVD_REQUIRE(!gamma || (gemm_bf16x3_rownorm_supported(N, terms) && C && C3 && R && bias && !ss_in && !ss_out && act == AVD_ACT_NONE && aligned16(gamma)),
@@ -1734,7 +1738,8 @@ int gemm_bf16x3(const void* A3, const void* W3, const float* bias, const float* 
     a.bias = bias, a.R = R, a.C = C, a.C3 = static_cast<unsigned char*>(C3);
     a.ab_inv = 1.0f / ab_scale, a.c_scale = c_scale;
     a.ss_in = ss_in, a.ss_out = ss_out, a.ss_sqrt_d = (float)sqrt((double)K), a.ss_eps = eps;
-    a.gamma = gamma, a.r_seg = r_seg, a.r_stride = r_stride;
+    a.gamma = gamma, a.r_seg = r_seg, a.M_plan = plan_rows;
+    if (r_seg) a.seg = *r_map;
     if (gamma) {
         a.ss_sqrt_d = (float)sqrt((double)N);
         return launch_s3<S3_EPI_RES_NORM>(a, st);
@@ -1856,20 +1861,23 @@ int gemm_bf16x3_splitk(const void* A3, const void* W3, const float* bias, const 
 }
 
 // in_proj for the bf16x3 attention: qkv = A W^T + bias written as the qkv3 image (q pre-multiplied by qscale)
-int gemm_bf16x3_qkv3(const void* A3, const void* W3, const float* bias, void* img, int64_t M, int tokens, int heads, int K, float qscale,
-                     int terms, hipStream_t st, float ab_scale, float c_scale, const float* ss_in, float eps) {
+int gemm_bf16x3_qkv3(const void* A3, const void* W3, const float* bias, void* img, const RowSegs& seg, int heads, int K, float qscale,
+                     int terms, hipStream_t st, float ab_scale, float c_scale, const float* ss_in, float eps, int64_t plan_rows) {
+    const int64_t M = seg.rows();
+    const int tokens = seg.tok[0] > seg.tok[1] ? seg.tok[0] : seg.tok[1];      // the image keeps the longer segment's slots for every sample
     AVD_REQUIRE(!ss_in || K % 64 == 0, AVD_EUNSUPPORTED, "gemm_bf16x3_qkv3: a folded norm needs K %% 64 == 0");
     AVD_REQUIRE(A3 && W3 && bias && img, AVD_EINVAL, "gemm_bf16x3_qkv3: null pointer");
     AVD_REQUIRE(scale_ok(ab_scale) && scale_ok(c_scale), AVD_EINVAL, "gemm_bf16x3_qkv3: image scales must be positive and finite");
     const int N = 3 * heads * 64;
-    AVD_REQUIRE(tokens > 0 && heads > 0 && M > 0 && M % tokens == 0, AVD_EINVAL, "gemm_bf16x3_qkv3: rows %lld not a multiple of tokens %d",
-                (long long)M, tokens);
+    AVD_REQUIRE(seg.tok[0] > 0 && seg.tok[1] > 0 && seg.samples[0] > 0 && seg.samples[1] >= 0 && heads > 0 &&
+                    seg.m0 == (int64_t)seg.samples[0] * seg.tok[0], AVD_EINVAL, "gemm_bf16x3_qkv3: bad row layout (%d x %d + %d x %d rows)",
+                seg.samples[0], seg.tok[0], seg.samples[1], seg.tok[1]);
     AVD_REQUIRE(M < (1ll << 31) - 256, AVD_EUNSUPPORTED, "gemm_bf16x3_qkv3: more than 2^31 rows");
     AVD_REQUIRE(gemm_bf16x3_supported(M, N, K), AVD_EUNSUPPORTED, "gemm_bf16x3_qkv3: need 3*heads*64 %% 256 == 0 and K %% 16 == 0");
     AVD_REQUIRE(aligned16(A3) && aligned16(W3) && aligned16(bias) && aligned16(img), AVD_EUNSUPPORTED, "gemm_bf16x3_qkv3: alignment");
     S3Args a = s3_args(A3, W3, M, N, K, terms);
     a.bias = bias, a.C3 = static_cast<unsigned char*>(img);
-    a.tokN = tokens, a.tokNpad = qkv3_npad(tokens), a.heads = heads, a.qscale = qscale;
+    a.seg = seg, a.tokNpad = qkv3_npad(tokens), a.heads = heads, a.qscale = qscale, a.M_plan = plan_rows;
     a.ab_inv = 1.0f / ab_scale, a.c_scale = c_scale;
     a.ss_in = ss_in, a.ss_sqrt_d = (float)sqrt((double)K), a.ss_eps = eps;
     return launch_s3<S3_EPI_QKV3>(a, st);
@@ -1896,7 +1904,10 @@ extern "C" int avd_gemm_bf16x3_f32(const void* A3, const void* W3, const float* 
 }
 extern "C" int avd_gemm_bf16x3_qkv3_f32(const void* A3, const void* W3, const float* bias, void* qkv3, int64_t M, int tokens, int heads,
                                         int K, float qscale, int terms, avd_stream_t stream) {
-    return gemm_bf16x3_qkv3(A3, W3, bias, qkv3, M, tokens, heads, K, qscale, terms, static_cast<hipStream_t>(stream));
+    AVD_REQUIRE(tokens > 0 && M > 0 && M % tokens == 0 && M < (1ll << 31), AVD_EINVAL, "gemm_bf16x3_qkv3: rows %lld not a multiple of tokens %d",
+                (long long)M, tokens);
+    return gemm_bf16x3_qkv3(A3, W3, bias, qkv3, RowSegs::uniform((int)(M / tokens), tokens), heads, K, qscale, terms,
+                            static_cast<hipStream_t>(stream));
 }
 
 // f16x2 mode (two fp16 planes, three product terms; avd_common.h): the same images with a caller-chosen power-of-two scale
@@ -1915,5 +1926,8 @@ extern "C" int avd_gemm_f16x2_f32(const void* A2, const void* W2, const float* b
 }
 extern "C" int avd_gemm_f16x2_qkv_f32(const void* A2, const void* W2, const float* bias, void* qkv, int64_t M, int tokens, int heads, int K,
                                       float qscale, float ab_scale, float qkv_scale, avd_stream_t stream) {
-    return gemm_bf16x3_qkv3(A2, W2, bias, qkv, M, tokens, heads, K, qscale, 3, static_cast<hipStream_t>(stream), ab_scale, qkv_scale);
+    AVD_REQUIRE(tokens > 0 && M > 0 && M % tokens == 0 && M < (1ll << 31), AVD_EINVAL, "gemm_f16x2_qkv: rows %lld not a multiple of tokens %d",
+                (long long)M, tokens);
+    return gemm_bf16x3_qkv3(A2, W2, bias, qkv, RowSegs::uniform((int)(M / tokens), tokens), heads, K, qscale, 3,
+                            static_cast<hipStream_t>(stream), ab_scale, qkv_scale);
 }

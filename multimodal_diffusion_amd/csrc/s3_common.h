@@ -24,8 +24,10 @@ struct S3Args {
     float* C;                 // [M][N] fp32 (EPI_BIAS, EPI_RES)
     unsigned char* C3;        // split3 image of [M][N] (EPI_GELU_SPLIT)
     int64_t M;
+    int64_t M_plan;           // host only: the row count the launch rules (tile family, rows per block, ring depth) are decided from; 0 = M
     int N, K, nbn, sm, sn;
-    int tokN, tokNpad, heads;   // EPI_QKV3: tokens per sample, padded tokens per sample, heads (N == 3 * heads * 64)
+    RowSegs seg;                // EPI_QKV3: (sample, token) of the M rows; EPI_RES_IMG with r_seg > 0: rows of the residual operand
+    int tokNpad, heads;         // EPI_QKV3: padded tokens per sample of the image, heads (N == 3 * heads * 64)
     float qscale;               // EPI_QKV3: factor folded into q before it is split (softmax scale * log2 e)
     int stagger;                // 4-wave kernel: the block in the odd wave slots of its SIMDs starts stagger x 1024 cycles late
     int first_gen;              // ... if it belongs to the first generation of blocks (blockIdx < 2 x CUs of the device)
@@ -39,9 +41,9 @@ struct S3Args {
     float* ss_out;
     float ss_sqrt_d, ss_eps;
     const float* gamma;         // EPI_RES_NORM: the norm's scale vector [N]; ss_sqrt_d = sqrt(N), ss_eps as above
-    // EPI_RES_IMG on the 16x16x32 kernels: residual rows in groups — output row m adds R row (m / r_seg) * r_stride + m % r_seg
+    // EPI_RES_IMG on the 16x16x32 kernels: residual rows in groups — output row m adds R row seg.row(m / r_seg, m % r_seg)
     // (r_seg == 0: R row m).  The last block of the core runs on its target rows only: outputs compact, residual stream not.
-    int r_seg, r_stride;
+    int r_seg;
 #ifdef AVD_S3_STAMPS            // diagnostic build only (tools/micro/s3_stamps.py), never in the product library
     unsigned long long* dbg;
 #endif
@@ -131,7 +133,7 @@ __device__ __forceinline__ void s3_epilogue_img16(const S3Args& g, f32x4t (&acc)
         const int dmodel = g.heads * 64;
         const int part = nbase / dmodel, head = (nbase % dmodel) >> 6;
         mul = part == 0 ? g.qscale : 1.0f;
-        qbase = (((int64_t)part * (g.M / g.tokN)) * g.heads + head) * (int64_t)g.tokNpad * QKV3_ROWB;
+        qbase = (((int64_t)part * g.seg.n_samples()) * g.heads + head) * (int64_t)g.tokNpad * QKV3_ROWB;
     }
 #pragma unroll
     for (int ip = 0; ip < 4; ++ip) {         // pairs of row tiles (2 ip, 2 ip + 1): this lane ends up with a row of tile 2 ip + (kq & 1)
@@ -154,7 +156,8 @@ __device__ __forceinline__ void s3_epilogue_img16(const S3Args& g, f32x4t (&acc)
         [[maybe_unused]] unsigned char* qrow = nullptr;
         [[maybe_unused]] int qsw = 0;
         if constexpr (EPI == S3_EPI_QKV3) {
-            const unsigned b = (unsigned)m / (unsigned)g.tokN, tok = (unsigned)m - b * (unsigned)g.tokN;
+            int b, tok;
+            g.seg.locate(m, b, tok);
             qrow = g.C3 + qbase + ((int64_t)b * g.heads * g.tokNpad + tok) * QKV3_ROWB;
             qsw = qkv3_swizzle(nbase / (g.heads * 64), (int)tok);
         }
@@ -163,7 +166,7 @@ __device__ __forceinline__ void s3_epilogue_img16(const S3Args& g, f32x4t (&acc)
         if constexpr (EPI == S3_EPI_RES_IMG) {
             if (g.r_seg > 0 && m < g.M) {
                 const unsigned sgi = (unsigned)m / (unsigned)g.r_seg;
-                rrow = (int64_t)sgi * g.r_stride + ((unsigned)m - sgi * (unsigned)g.r_seg);
+                rrow = g.seg.row((int)sgi, (int)((unsigned)m - sgi * (unsigned)g.r_seg));
             }
         }
 #pragma unroll

@@ -1525,12 +1525,12 @@ int assemble_f32(float* X2, const float* temb, const float* Xp, int B, int N, in
 __global__ __launch_bounds__(256) void assemble_rows_kernel(float* __restrict__ X2, const int64_t* __restrict__ t_now,
                                                             const float* __restrict__ freqs, const float* __restrict__ Xp,
                                                             float* __restrict__ ss, int B, int N, int d, int tdim, int Nt, int Np,
-                                                            int target_first, float neg_log_mp) {
+                                                            int target_first, float neg_log_mp, RowSegs seg) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= (int64_t)2 * B * N) return;
-    const int n = (int)(row % N);
-    const int bb = (int)(row / N);
+    if (row >= seg.rows()) return;
+    int n, bb;
+    seg.locate(row, bb, n);
     const int half = bb >= B, b = half ? bb - B : bb;
     const int t0 = target_first ? 0 : Np;
     const bool is_t = n >= t0 && n < t0 + Nt;
@@ -1569,14 +1569,61 @@ __global__ __launch_bounds__(256) void assemble_rows_kernel(float* __restrict__ 
     if (ss && lane == 0) ss[row] = acc;
 }
 
+// short_null (null = the plain [2B, N, d] layout): the caller's two-segment layout — target rows first, B cond samples of N rows, then B
+// null samples that keep ONE of their Np prompt rows (they are all the zero row): Nt + 1 rows each (composite.hip)
 int assemble_rows_f32(float* X2, const int64_t* t_now, const float* freqs, const float* Xp, float* ss, int B, int N, int d, int tdim,
-                      int Nt, int Np, int target_first, float max_period, hipStream_t st) {
-    const int64_t rows = (int64_t)2 * B * N;
+                      int Nt, int Np, int target_first, float max_period, hipStream_t st, const RowSegs* short_null) {
+    AVD_REQUIRE(!short_null || (target_first && Np >= 1 && short_null->samples[0] == B && short_null->samples[1] == B && short_null->tok[0] == N &&
+                                short_null->tok[1] == Nt + 1 && short_null->m0 == (int64_t)B * N), AVD_EINVAL,
+                "assemble_rows: a short null half is B samples of N rows, then B of the target rows and one prompt row behind them");
+    const RowSegs seg = short_null ? *short_null : RowSegs::uniform(2 * B, N);
+    const int64_t rows = seg.rows();
     static const int tag = prof_tag_id("assemble_rows_kernel");
-    ProfScope prof(tag, 4.0 * (2.0 * B * N * d + (double)B * Nt * (d - tdim) + (double)B * Np * d), st);
+    ProfScope prof(tag, 4.0 * ((double)rows * d + (double)B * Nt * (d - tdim) + (double)B * Np * d), st);
     hipLaunchKernelGGL(assemble_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, X2, t_now, freqs, Xp, ss, B, N, d, tdim,
-                       Nt, Np, target_first, -(float)log((double)max_period));
+                       Nt, Np, target_first, -(float)log((double)max_period), seg);
     AVD_CHECK_LAUNCH("assemble_rows");
+    return AVD_OK;
+}
+
+// The k and v rows of a null CFG sample's one prompt row (token `src` of samples first_sample .. of the qkv3 image), copied into key
+// slots src + 1 .. n_keys - 1 of the same (sample, head): the attention then reads the n_keys keys of the full layout, with the values
+// the in_proj GEMM would have written there (the duplicate rows' inputs are equal, so are their k and v).  A row is three planes of
+// eight 16-byte chunks, chunk c at slot c ^ qkv3_swizzle(part, token): the copy re-applies the swizzle of the slot it fills.
+// One thread per 16-byte chunk.
+__global__ __launch_bounds__(256) void qkv3_replicate_kernel(unsigned char* __restrict__ img, int Bt, int H, int Npad, int first_sample,
+                                                             int n_samples, int src, int n_keys) {
+    const int dup = n_keys - 1 - src;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t total = (int64_t)2 * n_samples * H * dup * 24;
+    if (i >= total) return;
+    const int c = (int)(i % 8), plane = (int)(i / 8 % 3);
+    int64_t r = i / 24;
+    const int j = (int)(r % dup);
+    r /= dup;
+    const int h = (int)(r % H);
+    r /= H;
+    const int b = (int)(r % n_samples), part = 1 + (int)(r / n_samples);
+    unsigned char* base = img + (((int64_t)part * Bt + first_sample + b) * H + h) * (int64_t)Npad * QKV3_ROWB;
+    const int dst = src + 1 + j;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(base + (int64_t)src * QKV3_ROWB + plane * 128 + ((c ^ qkv3_swizzle(part, src)) << 4));
+    *reinterpret_cast<u32x4*>(base + (int64_t)dst * QKV3_ROWB + plane * 128 + ((c ^ qkv3_swizzle(part, dst)) << 4)) = v;
+}
+
+int qkv3_replicate(void* img, int img_samples, int H, int n_keys, int first_sample, int n_samples, int src, hipStream_t st) {
+    AVD_REQUIRE(img && aligned16(img), AVD_EINVAL, "qkv3_replicate: null or misaligned image");
+    AVD_REQUIRE(H > 0 && n_keys > 0 && src >= 0 && src < n_keys && first_sample >= 0 && n_samples > 0 && first_sample + n_samples <= img_samples,
+                AVD_EINVAL, "qkv3_replicate: bad geometry (samples %d + %d of %d, token %d of %d keys)", first_sample, n_samples, img_samples,
+                src, n_keys);
+    const int dup = n_keys - 1 - src;
+    if (dup == 0) return AVD_OK;
+    const int64_t total = (int64_t)2 * n_samples * H * dup * 24;
+    AVD_REQUIRE((total + 255) / 256 < (1ll << 31), AVD_EUNSUPPORTED, "qkv3_replicate: grid too large");
+    static const int tag = prof_tag_id("qkv3_replicate_kernel");
+    ProfScope prof(tag, 32.0 * (double)total, st);
+    hipLaunchKernelGGL(qkv3_replicate_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, static_cast<unsigned char*>(img),
+                       img_samples, H, qkv3_npad(n_keys), first_sample, n_samples, src, n_keys);
+    AVD_CHECK_LAUNCH("qkv3_replicate");
     return AVD_OK;
 }
 
