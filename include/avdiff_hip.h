@@ -299,6 +299,38 @@ int avd_latent_guide_f32(const avd_latent_guide* g, const int64_t* tau, const fl
 int avd_latent_guide_canvas_f32(const avd_latent_guide* g, const int64_t* tau, const float* alpha_bar, int T_train,
                                 const float* z, float* out, int N, int64_t outer, int L, int hop, int64_t inner, avd_stream_t stream);
 
+/* ---- renoise: the forward jump z_t -> z_t' (t' > t) of RePaint resampling (Lugmayr et al. 2022; a public contract).
+ * A resampling schedule (schedule_utils.resample_schedule) sends the trajectory back up the schedule after a stretch of steps and
+ * denoises that stretch again, so that the free and the held region of a latent guide meet at a common noise level more than once.
+ * Per sample b of a call, with a(tau) as in avd_latent_guide, a_f = a(t_from[b]) and a_t = a(t_to[b]):
+ *   1. identity case: if !(a_t < a_f) then out = z bit for bit — no arithmetic and no generator call.  This covers t_to <= t_from
+ *      and a_f == 0;
+ *   2. jump case: otherwise rho = a_t / a_f, A = sqrt(rho), S = sqrt(max(1 - rho, 0)) and out = A z + S n_r, all in fp32, in that
+ *      order, without contraction (q(z_t' | z_t) of the forward process);
+ *   3. renoise stream n_r(s, e): the avd_noise_key construction with counter (e >> 2, (uint32) s, (uint32) visit, 0x52504E31) and
+ *      s = key.sample_offset + b.  `visit` is one uint32 per launch, passed by value: it names the jump, so a jump taken again (with
+ *      another visit) draws fresh normals.  The last word keeps the stream apart from DDIM's (0x44444D31) and the guide's known
+ *      noise (0x4B4E5731);
+ *   4. with a guide (g != NULL) the launch ends in the guide's blend, out <- blend(mask, q(t_to[b]), out), with the guide_coef /
+ *      q / blend of avd_latent_guide, one implementation: a held region leaves the jump on its deterministic forward path, bit for
+ *      bit what avd_latent_guide_f32 gives at t_to; the renoised value there is discarded;
+ *   5. canvas keying (avd_renoise_canvas_f32): the batch is N consecutive windows of one canvas as in "canvas-keyed noise", window b
+ *      at global index w = key.sample_offset + b; element (o, l, i) takes n_r of sample s = p = w*hop + l, element e' = o*inner + i.
+ *      The guide's known noise is canvas-keyed too ("canvas-keyed known noise"), and the guide's key must carry the same
+ *      sample_offset as the renoise key (AVD_EINVAL otherwise).  Windows that agree on an overlap before the call agree after it:
+ *      the same linear map with the same normals.  When inner % 4 == 0 and z / out are 16-byte aligned a lane's four values come
+ *      from one Philox call, otherwise (every audio latent) one call per element; same bits either way.
+ * Arguments, checked before any launch: avd_noise_key's (per-sample) or those of "canvas-keyed noise" / "canvas-keyed known noise"
+ * (canvas), and avd_latent_guide's when g is passed.  out may be z (in place); otherwise they must not overlap; known / mask must
+ * not overlap out.  t_from, t_to: int64 [B]; z, out: fp32 [B, per_sample] / [N, outer, L, inner].
+ * Limit: the step noise of an eta > 0 sampler keeps its own contract (keyed by t_now, not by visit), so a revisited timestep repeats
+ * its step normals; only the renoise normals are fresh per visit. */
+int avd_renoise_f32(const avd_noise_key* key, uint32_t visit, const avd_latent_guide* g, const int64_t* t_from, const int64_t* t_to,
+                    const float* alpha_bar, int T_train, const float* z, float* out, int B, int64_t per_sample, avd_stream_t stream);
+int avd_renoise_canvas_f32(const avd_noise_key* key, uint32_t visit, const avd_latent_guide* g, const int64_t* t_from,
+                           const int64_t* t_to, const float* alpha_bar, int T_train, const float* z, float* out, int N, int64_t outer,
+                           int L, int hop, int64_t inner, avd_stream_t stream);
+
 /* ---- CFG control: per-sample guidance scales and guidance rescale (Lin et al. 2023, diffusers' rescale_noise_cfg; a public
  * contract).  For sample b of a call, with n = per_sample (>= 2):
  *   1. g_b = guidance[b] when that pointer is set, else the scalar guidance (avd_step_desc.guidance); the token-space combine is
@@ -792,8 +824,10 @@ int avd_window_consensus_f32(float* z, const float* w, int N, int64_t outer, int
  * t_now[b] = sched[*cursor], t_prev[b] = sched[*cursor+1] for all b, then (*cursor)++ . */
 int avd_sched_advance(const int64_t* sched, int n_sched, int32_t* cursor, int64_t* t_now, int64_t* t_prev,
                       int B, avd_stream_t stream);
-/* As avd_sched_advance, and t_last[b] = sched[*cursor - 1] when *cursor > 0, else -1 (the multistep solver's history step).
- * A cursor past the end repeats the last step, with its own t_last. */
+/* As avd_sched_advance, and t_last[b] = sched[*cursor - 1] when *cursor > 0 and sched[*cursor - 1] > sched[*cursor], else -1 (the
+ * multistep solver's history step).  An entry before t_now that lies at or below it means the schedule has just jumped up (a
+ * resampling schedule, "renoise"): the history does not belong to this stretch and the step is first order.  On a strictly
+ * decreasing schedule the second condition always holds.  A cursor past the end repeats the last step, with its own t_last. */
 int avd_sched_advance_ms(const int64_t* sched, int n_sched, int32_t* cursor, int64_t* t_last, int64_t* t_now, int64_t* t_prev,
                          int B, avd_stream_t stream);
 

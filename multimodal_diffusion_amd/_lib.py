@@ -151,6 +151,9 @@ SIGNATURES = {
                                                _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "avd_latent_guide_f32": (_I, [C.POINTER(LatentGuide), _P, _P, _I, _P, _P, _I, _L, _P]),
     "avd_latent_guide_canvas_f32": (_I, [C.POINTER(LatentGuide), _P, _P, _I, _P, _P, _I, _L, _I, _I, _L, _P]),
+    "avd_renoise_f32": (_I, [C.POINTER(NoiseKey), C.c_uint32, C.POINTER(LatentGuide), _P, _P, _P, _I, _P, _P, _I, _L, _P]),
+    "avd_renoise_canvas_f32": (_I, [C.POINTER(NoiseKey), C.c_uint32, C.POINTER(LatentGuide), _P, _P, _P, _I, _P, _P, _I, _L, _I, _I, _L,
+                                    _P]),
     "avd_denoise_step_canvas_guided_f32": (_I, [C.POINTER(StepDesc), C.POINTER(LatentGuide), _I, C.POINTER(NoiseKey), C.POINTER(CfgControl),
                                                 _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "avd_denoise_step_guided_f32": (_I, [C.POINTER(StepDesc), C.POINTER(LatentGuide), C.POINTER(NoiseKey), _P, _P, _P, _P, _P, _P, _P,

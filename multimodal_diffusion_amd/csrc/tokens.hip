@@ -739,6 +739,8 @@ int latent_guide_f32(const avd_latent_guide* g, const int64_t* tau, const float*
     const int64_t per4 = (per + 3) >> 2, total4 = (int64_t)B * per4;
     AVD_REQUIRE((total4 + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "latent_guide: %lld values is too many for one launch",
                 (long long)B * per);
+    static const int tag = prof_tag_id("latent_guide_kernel");
+    ProfScope prof(tag, 4.0 * (double)B * per * (z ? 4 : 2), st);
     hipLaunchKernelGGL(latent_guide_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, gs, tau, abar, T_train, z, out,
                        per, per4, total4);
     AVD_CHECK_LAUNCH("latent_guide");
@@ -781,6 +783,8 @@ int latent_guide_canvas_f32(const avd_latent_guide* g, const int64_t* tau, const
     AVD_REQUIRE((double)N * (double)outer * (double)L * (double)inner < 9.0e18, AVD_EUNSUPPORTED, "latent_guide_canvas: too many values");
     const int64_t n = (int64_t)N * outer * L * inner / (vec ? 4 : 1);
     AVD_REQUIRE((n + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "latent_guide_canvas: %lld lanes are too many for one launch", (long long)n);
+    static const int tags[2] = {prof_tag_id("canvas_latent_guide_kernel<1>"), prof_tag_id("canvas_latent_guide_kernel<4>")};
+    ProfScope prof(tags[vec ? 1 : 0], 4.0 * (double)n * (vec ? 4 : 1) * (z ? 4 : 2), st);
     if (vec)
         hipLaunchKernelGGL(canvas_latent_guide_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gs, tau, abar, T_train, z,
                            out, outer, L, inner, n);
@@ -788,6 +792,145 @@ int latent_guide_canvas_f32(const avd_latent_guide* g, const int64_t* tau, const
         hipLaunchKernelGGL(canvas_latent_guide_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gs, tau, abar, T_train, z,
                            out, outer, L, inner, n);
     AVD_CHECK_LAUNCH("latent_guide_canvas");
+    return AVD_OK;
+}
+
+// ------------------------------------------------------------------ renoise (RePaint resampling: the forward jump t_from -> t_to)
+// The contract is written out in include/avdiff_hip.h ("renoise").  Per sample b, with a_f = a(t_from[b]) and a_t = a(t_to[b]):
+//   !(a_t < a_f): out = z, no arithmetic and no generator call;  else rho = a_t / a_f, out = sqrt(rho) z + sqrt(max(1 - rho, 0)) n_r,
+//   n_r = philox_normal4 at counter (e >> 2, s, visit, RENOISE_TAG) — or its canvas keying (canvas_normal4) — fresh per visit;
+//   with a guide the launch ends in blend(mask, q(t_to[b]), out): guide_coef / guide_q / guide_blend, as every guided kernel.
+constexpr uint32_t RENOISE_TAG = 0x52504E31u;   // "RPN1"
+
+struct RenoiseCoef {
+    float A, S;
+    bool same;              // !(a_t < a_f): out = z
+};
+
+__device__ __forceinline__ RenoiseCoef renoise_coef(const float* abar, int T_train, long long t_from, long long t_to) {
+#pragma clang fp contract(off)
+    const float af = dpm_abar(abar, T_train, t_from), at = dpm_abar(abar, T_train, t_to);
+    if (!(at < af)) return RenoiseCoef{1.f, 0.f, true};
+    const float rho = at / af;
+    return RenoiseCoef{sqrtf(rho), sqrtf(fmaxf(1.0f - rho, 0.f)), false};
+}
+__device__ __forceinline__ float renoise_apply(const RenoiseCoef& c, float z, float n) {
+#pragma clang fp contract(off)
+    return c.same ? z : c.A * z + c.S * n;
+}
+
+// gs.known == nullptr: no guide.  Lanes as latent_guide_kernel: four consecutive elements of one sample, the tail lane fewer.
+__global__ __launch_bounds__(256) void renoise_kernel(NoiseKey nk, uint32_t visit, GuideState gs, const int64_t* __restrict__ t_from,
+                                                      const int64_t* __restrict__ t_to, const float* __restrict__ abar, int T_train,
+                                                      const float* z, float* out, int64_t per, int64_t per4,
+                                                      int64_t total4) {      // z may be out (in place)
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total4) return;
+    const int b = (int)(i / per4);
+    const int64_t q4 = i % per4;
+    const RenoiseCoef rc = renoise_coef(abar, T_train, t_from[b], t_to[b]);
+    f32x4 n = {0.f, 0.f, 0.f, 0.f}, nk4 = {0.f, 0.f, 0.f, 0.f};
+    if (!rc.same) n = philox_normal4(nk, (uint32_t)q4, nk.s0 + (uint32_t)b, visit, RENOISE_TAG);
+    GuideCoef gc = {1.f, 0.f, true};
+    if (gs.known) {
+        gc = guide_coef(abar, T_train, t_to[b]);
+        if (!gc.one) nk4 = philox_normal4(gs.nk, (uint32_t)q4, gs.nk.s0 + (uint32_t)b, 0u, GUIDE_TAG);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t el = q4 * 4 + k;
+        if (el >= per) break;
+        const int64_t j = (int64_t)b * per + el;
+        float v = renoise_apply(rc, z[j], n[k]);
+        if (gs.known) v = guide_blend(gs.mask ? gs.mask[b * gs.mask_bstride + el] : 1.f, guide_q(gc, gs.known[j], nk4[k]), v);
+        out[j] = v;
+    }
+}
+
+int renoise_f32(const avd_noise_key* key, uint32_t visit, const avd_latent_guide* g, const int64_t* t_from, const int64_t* t_to,
+                const float* abar, int T_train, const float* z, float* out, int B, int64_t per, hipStream_t st) {
+    NoiseKey nk;
+    if (int rc = make_noise_key(key, B, nk)) return rc;
+    AVD_REQUIRE(t_from && t_to && abar && z && out && T_train > 0, AVD_EINVAL, "renoise: null pointer or bad T_train");
+    AVD_REQUIRE(per > 0 && per < ((int64_t)1 << 34), AVD_EINVAL, "renoise: per_sample %lld must be in [1, 2^34)", (long long)per);
+    AVD_REQUIRE(out == z || !overlaps(out, z, (int64_t)B * per), AVD_EINVAL, "renoise: out must be z or not overlap it");
+    GuideState gs{};
+    if (g)
+        if (int rc = make_guide(g, B, per, out, nullptr, gs)) return rc;
+    const int64_t per4 = (per + 3) >> 2, total4 = (int64_t)B * per4;
+    AVD_REQUIRE((total4 + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "renoise: %lld values is too many for one launch",
+                (long long)B * per);
+    static const int tag = prof_tag_id("renoise_kernel");
+    ProfScope prof(tag, 4.0 * (double)B * per * (g ? 4 : 2), st);
+    hipLaunchKernelGGL(renoise_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, nk, visit, gs, t_from, t_to, abar,
+                       T_train, z, out, per, per4, total4);
+    AVD_CHECK_LAUNCH("renoise");
+    return AVD_OK;
+}
+
+// The canvas-keyed renoise; V lanes as canvas_latent_guide_kernel.  gs.known == nullptr: no guide.
+template <int V>
+__global__ __launch_bounds__(256) void canvas_renoise_kernel(CanvasKey ck, uint32_t visit, CanvasGuideState gs,
+                                                             const int64_t* __restrict__ t_from, const int64_t* __restrict__ t_to,
+                                                             const float* __restrict__ abar, int T_train, const float* z, float* out,
+                                                             int64_t outer, int L, int64_t inner, int64_t n) {      // z may be out
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const int64_t iv = inner / V;
+    const int64_t i = (idx % iv) * V;
+    int64_t r = idx / iv;
+    const int l = (int)(r % L);
+    r /= L;
+    const int64_t o = r % outer;
+    const int b = (int)(r / outer);
+    const int64_t j = idx * V, el = j - (int64_t)b * outer * L * inner;
+    const RenoiseCoef rc = renoise_coef(abar, T_train, t_from[b], t_to[b]);
+    f32x4 nr = {0.f, 0.f, 0.f, 0.f};
+    if (!rc.same) nr = canvas_normal4(ck, b, o, l, i, inner, visit, RENOISE_TAG);
+    if constexpr (V == 4) {
+        const f32x4 zz = *reinterpret_cast<const f32x4*>(z + j);
+        f32x4 v;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = renoise_apply(rc, zz[k], nr[k]);
+        if (gs.known) v = canvas_guide_apply4(gs, guide_coef(abar, T_train, t_to[b]), b, j, el, o, l, i, inner, v);
+        *reinterpret_cast<f32x4*>(out + j) = v;
+    } else {
+        float v = renoise_apply(rc, z[j], nr[(int)((o * inner + i) & 3)]);
+        if (gs.known) v = canvas_guide_apply1(gs, guide_coef(abar, T_train, t_to[b]), b, j, el, o, l, i, inner, v);
+        out[j] = v;
+    }
+}
+
+int renoise_canvas_f32(const avd_noise_key* key, uint32_t visit, const avd_latent_guide* g, const int64_t* t_from, const int64_t* t_to,
+                       const float* abar, int T_train, const float* z, float* out, int N, int64_t outer, int L, int hop, int64_t inner,
+                       hipStream_t st) {
+    CanvasKey ck;
+    if (int rc = make_canvas_key(key, N, outer, L, hop, inner, ck, "canvas renoise")) return rc;
+    AVD_REQUIRE((double)outer * (double)L * (double)inner < 17179869184.0, AVD_EINVAL,
+                "canvas renoise: a window of outer %lld * L %d * inner %lld values must hold < 2^34", (long long)outer, L, (long long)inner);
+    AVD_REQUIRE(t_from && t_to && abar && z && out && T_train > 0, AVD_EINVAL, "renoise_canvas: null pointer or bad T_train");
+    AVD_REQUIRE((double)N * (double)outer * (double)L * (double)inner < 9.0e18, AVD_EUNSUPPORTED, "renoise_canvas: too many values");
+    const int64_t total = (int64_t)N * outer * L * inner;
+    AVD_REQUIRE(out == z || !overlaps(out, z, total), AVD_EINVAL, "renoise_canvas: out must be z or not overlap it");
+    CanvasGuideState gs{};
+    if (g) {
+        AVD_REQUIRE(g->key.sample_offset == key->sample_offset, AVD_EINVAL,
+                    "renoise_canvas: the guide's key and the renoise key must carry the same sample_offset (got %lld and %lld)",
+                    (long long)g->key.sample_offset, (long long)key->sample_offset);
+        if (int rc = make_canvas_guide(g, N, outer, L, hop, inner, out, nullptr, gs)) return rc;
+    }
+    const bool vec = inner % 4 == 0 && aligned16(out) && aligned16(z);
+    const int64_t n = total / (vec ? 4 : 1);
+    AVD_REQUIRE((n + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "renoise_canvas: %lld lanes are too many for one launch", (long long)n);
+    static const int tags[2] = {prof_tag_id("canvas_renoise_kernel<1>"), prof_tag_id("canvas_renoise_kernel<4>")};
+    ProfScope prof(tags[vec ? 1 : 0], 4.0 * (double)total * (g ? 4 : 2), st);
+    if (vec)
+        hipLaunchKernelGGL(canvas_renoise_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ck, visit, gs, t_from, t_to, abar,
+                           T_train, z, out, outer, L, inner, n);
+    else
+        hipLaunchKernelGGL(canvas_renoise_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ck, visit, gs, t_from, t_to, abar,
+                           T_train, z, out, outer, L, inner, n);
+    AVD_CHECK_LAUNCH("renoise_canvas");
     return AVD_OK;
 }
 
@@ -1740,7 +1883,8 @@ __global__ void sched_advance_kernel(const int64_t* __restrict__ sched, int n_sc
     if (threadIdx.x == 0) *cursor = cur + 1;
 }
 
-// as sched_advance_kernel, and t_last[b] = the entry before t_now (-1 at the start of the schedule): the multistep solvers' history
+// as sched_advance_kernel, and t_last[b] = the entry before t_now (-1 at the start of the schedule, and after an up-jump of a
+// resampling schedule, where that entry does not lie above t_now): the multistep solvers' history
 __global__ void sched_advance_ms_kernel(const int64_t* __restrict__ sched, int n_sched, int32_t* cursor, int64_t* __restrict__ t_last,
                                         int64_t* __restrict__ t_now, int64_t* __restrict__ t_prev, int B) {
     __shared__ int cur;
@@ -1749,7 +1893,8 @@ __global__ void sched_advance_ms_kernel(const int64_t* __restrict__ sched, int n
     int i = cur;
     if (i < 0) i = 0;
     if (i > n_sched - 2) i = n_sched - 2;
-    const int64_t l = i > 0 ? sched[i - 1] : -1, a = sched[i], p = sched[i + 1];
+    const int64_t a = sched[i], p = sched[i + 1];
+    const int64_t l = i > 0 && sched[i - 1] > a ? sched[i - 1] : -1;      // an entry at or below t_now: we have just jumped up, no history
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
         t_last[b] = l;
         t_now[b] = a;
@@ -1867,6 +2012,17 @@ extern "C" int avd_cfg_rescale_f32(const float* e_cond, const float* e_cfg, cons
 extern "C" int avd_latent_guide_f32(const avd_latent_guide* g, const int64_t* tau, const float* alpha_bar, int T_train, const float* z,
                                     float* out, int B, int64_t per_sample, avd_stream_t stream) {
     return latent_guide_f32(g, tau, alpha_bar, T_train, z, out, B, per_sample, static_cast<hipStream_t>(stream));
+}
+extern "C" int avd_renoise_f32(const avd_noise_key* key, uint32_t visit, const avd_latent_guide* g, const int64_t* t_from,
+                               const int64_t* t_to, const float* alpha_bar, int T_train, const float* z, float* out, int B,
+                               int64_t per_sample, avd_stream_t stream) {
+    return renoise_f32(key, visit, g, t_from, t_to, alpha_bar, T_train, z, out, B, per_sample, static_cast<hipStream_t>(stream));
+}
+extern "C" int avd_renoise_canvas_f32(const avd_noise_key* key, uint32_t visit, const avd_latent_guide* g, const int64_t* t_from,
+                                      const int64_t* t_to, const float* alpha_bar, int T_train, const float* z, float* out, int N,
+                                      int64_t outer, int L, int hop, int64_t inner, avd_stream_t stream) {
+    return renoise_canvas_f32(key, visit, g, t_from, t_to, alpha_bar, T_train, z, out, N, outer, L, hop, inner,
+                              static_cast<hipStream_t>(stream));
 }
 extern "C" int avd_latent_guide_canvas_f32(const avd_latent_guide* g, const int64_t* tau, const float* alpha_bar, int T_train,
                                            const float* z, float* out, int N, int64_t outer, int L, int hop, int64_t inner,

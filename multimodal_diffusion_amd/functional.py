@@ -328,6 +328,52 @@ def latent_guide(known: Tensor, tau: Tensor, alpha_bar: Tensor, z: Optional[Tens
     return out
 
 
+def check_visit(visit) -> int:
+    """the `visit` word of the renoise stream: an int in [0, 2**32)"""
+    if isinstance(visit, bool) or not isinstance(visit, int) or not 0 <= visit < 2 ** 32:
+        raise ValueError(f"visit must be an int in [0, 2**32), got {visit!r}")
+    return visit
+
+
+def renoise(z: Tensor, t_from: Tensor, t_to: Tensor, alpha_bar: Tensor, seed: int, visit: int, sample_offset: int = 0,
+            guide: Optional["L.LatentGuide"] = None, canvas_hop: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
+    """The forward jump of RePaint resampling (avd_renoise_f32 / avd_renoise_canvas_f32; contract in include/avdiff_hip.h, "renoise"):
+    per sample b with rho = a(t_to[b]) / a(t_from[b]) < 1, out[b] = sqrt(rho) z[b] + sqrt(1 - rho) n_r, n_r the renoise stream of
+    (seed, sample_offset + b, visit); out[b] = z[b] bit for bit where a(t_to[b]) is not below a(t_from[b]).  ``visit`` names the
+    jump: another visit draws fresh normals.  ``guide`` (``latent_guide_desc``): the call ends in blend(mask, q(t_to), out), so a held
+    region stays on its forward path.  ``canvas_hop`` (default None = per-sample keying): ``z`` is a batch of consecutive windows of one
+    canvas ([N,C,T,H,W] video, [N,Ca,F] audio), window 0 at global window index ``sample_offset``, and the renoise stream and the
+    guide's known noise are keyed by canvas position; the guide's key must carry the same offset.  ``out``: a contiguous float32
+    device tensor of z's shape, which may be ``z`` itself (in place)."""
+    z = L.dev_f32(z, "z")
+    dev, B = z.device, z.shape[0]
+    visit = check_visit(visit)
+    key = noise_key(seed, sample_offset)
+    if canvas_hop is not None:
+        canvas_hop = check_canvas_keying(tuple(z.shape), canvas_hop, sample_offset)
+    elif sample_offset + B > 2 ** 32:
+        raise ValueError(f"sample_offset {sample_offset} + batch {B} exceeds the stream's 2**32 sample indices")
+    if guide is not None and not isinstance(guide, L.LatentGuide):
+        raise TypeError("guide must be an avd_latent_guide (functional.latent_guide_desc)")
+    tf, tt = L.dev_i64(t_from, dev), L.dev_i64(t_to, dev)
+    if tf.numel() != B or tt.numel() != B:
+        raise ValueError(f"t_from / t_to have {tf.numel()} / {tt.numel()} entries, z has {B} samples")
+    if out is None:
+        out = torch.empty_like(z)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == z.shape and out.device == dev):
+        raise ValueError(f"out must be a contiguous float32 tensor of shape {tuple(z.shape)} on z's device")
+    ab = alpha_bar if (alpha_bar.is_cuda and alpha_bar.dtype == torch.float32) else alpha_bar.to(dev, torch.float32)
+    ab = ab.contiguous()
+    args = (C.byref(key), visit, None if guide is None else C.byref(guide), tf.data_ptr(), tt.data_ptr(), ab.data_ptr(), ab.numel(),
+            z.data_ptr(), out.data_ptr(), B)
+    if canvas_hop is None:
+        L.check(L.lib().avd_renoise_f32(*args, z.numel() // B, _st(out)))
+    else:
+        outer, L_, inner = window_dims(z.shape)
+        L.check(L.lib().avd_renoise_canvas_f32(*args, outer, L_, canvas_hop, inner, _st(out)))
+    return out
+
+
 def cfg_values(v, B: int, name: str, lo: Optional[float] = None, hi: Optional[float] = None) -> Tensor:
     """A per-sample CFG value (a number for every sample, or B numbers as a sequence / array / tensor) as a CPU float32 [B] tensor,
     after the checks DenoiseEngine, set_cfg and cfg_rescale share: finite, and within [lo, hi] where given (the kernels trust the

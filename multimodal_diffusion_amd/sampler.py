@@ -197,6 +197,14 @@ class DenoiseEngine:
     (avd_denoise_step_canvas_guided_f32), and ``start_latent`` forward-noises with the same keying.  ``hop`` must equal ``canvas_hop``
     on a canvas-keyed engine and the consensus hop while a consensus is set; eta > 0 needs the canvas-keyed engine (a canvas guide
     with per-sample step noise is refused).  The known windows must agree on their overlaps (``functional.window_consensus`` once).
+
+    RePaint resampling (extension; Lugmayr et al. 2022): ``run`` accepts a schedule with up-jumps (schedule_utils.resample_schedule).
+    A pair sched[i] < sched[i + 1] is not a denoising step but a forward jump, ``renoise`` (include/avdiff_hip.h, "renoise"): the
+    latent is noised from sched[i] to sched[i + 1] with fresh seeded normals named by visit = i, and under ``set_known`` the held
+    region lands on its forward path there; the stretch below is then denoised again, so the free and the held region meet at a
+    common noise level more than once.  It needs ``noise_seed`` (also at eta == 0); the keying is the engine's (by canvas position
+    with ``canvas_hop`` or a canvas-keyed guide, which a window consensus requires).  Limit: at eta > 0 the step noise stays keyed by
+    (sample, t_now, element), so a revisited timestep repeats its step normals; only the renoise normals are fresh per visit.
     """
 
     SOLVERS = ("ddim", "dpmpp_2m")
@@ -773,11 +781,70 @@ class DenoiseEngine:
     GRAPH_BELOW_ROWS = 6144      # 2B*N under which a step's ~60-95 launches are host-bound: replay them from a HIP graph
 
     def check_schedule(self, sched: torch.Tensor) -> None:
-        """what ``run`` asks of a schedule before it steps (a caller that drives ``begin`` / ``advance`` itself asks the same)"""
-        if self.solver == "dpmpp_2m":
-            sc = torch.as_tensor(sched).reshape(-1).to("cpu", torch.long)
-            if sc.numel() >= 2 and not bool((sc[1:] < sc[:-1]).all()):
-                raise ValueError("solver 'dpmpp_2m' needs a strictly decreasing schedule (its history step must lie above t_now)")
+        """what ``run`` asks of a schedule before it steps (a caller that drives ``begin`` / ``advance`` itself asks the same).
+        Solver "dpmpp_2m": strictly decreasing runs, joined at most by the up-jumps of a resampling schedule — a jump returns to a
+        timestep the schedule has already passed (schedule_utils.resample_schedule emits nothing else; a climb to a new timestep is
+        refused as a mis-ordered schedule, as before).  Any resampling schedule (schedule_utils.has_jumps: an up-jump back to a
+        timestep already passed): ``noise_seed`` (the renoise key, also at eta == 0), no equal neighbours, and under a window
+        consensus a renoise keyed by canvas position at the consensus hop.  Solver "ddim" takes any other schedule, as before."""
+        sc = torch.as_tensor(sched).reshape(-1).to("cpu", torch.long)
+        jumps = su.has_jumps(sc)
+        if self.solver == "dpmpp_2m" and sc.numel() >= 2:
+            s, seen, ok = sc.tolist(), set(), True
+            for a, b in zip(s[:-1], s[1:]):
+                seen.add(a)
+                ok = ok and (b < a or (b > a and b in seen))
+            if not ok:
+                raise ValueError("solver 'dpmpp_2m' needs a strictly decreasing schedule (its history step must lie above t_now), or "
+                                 "strictly decreasing runs joined by the up-jumps of schedule_utils.resample_schedule, which return to "
+                                 "a timestep already passed")
+        if not jumps:
+            return
+        su.step_segments(sc, None)                  # equal neighbours
+        self._renoise_keying()
+
+    # ---- RePaint resampling: the forward jump of a schedule with up-jumps ----
+    def _renoise_hop(self) -> Optional[int]:
+        """the hop of the canvas keying the renoise takes (the engine's canvas_hop or a canvas-keyed guide's; when both are set they
+        agree: set_known checks it), None = keyed per sample"""
+        if self.canvas_hop is not None:
+            return self.canvas_hop
+        return self._guide_hop if self._guide is not None else None
+
+    def _renoise_keying(self) -> Optional[int]:
+        """the checks every renoise makes (``check_schedule`` makes them before the first step); returns ``_renoise_hop()``"""
+        if self._key is None:
+            raise ValueError("a schedule with up-jumps (resampling) draws its renoise normals from the seeded stream: build the engine "
+                             "with noise_seed (also at eta == 0)")
+        hop = self._renoise_hop()
+        if self._cons_hop is not None and hop != self._cons_hop:
+            raise ValueError("window consensus needs the renoise of a resampling schedule keyed by canvas position at the consensus "
+                             "hop: the mean of the windows' independent renoise draws would shrink their variance (build the engine "
+                             "with noise_keying='canvas', canvas_hop=hop, or set a canvas-keyed guide with that hop)")
+        if self._guide is not None and (self._guide_hop is None) != (hop is None):
+            raise ValueError("a guide keyed per sample cannot end a canvas-keyed renoise: set_known(..., keying='canvas', hop=canvas_hop)")
+        return hop
+
+    def renoise(self, z: torch.Tensor, t_from: torch.Tensor, t_to: torch.Tensor, visit: int,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The forward jump t_from -> t_to of a resampling schedule (include/avdiff_hip.h, "renoise"): out = sqrt(rho) z + sqrt(1 - rho)
+        n_r with rho = a(t_to) / a(t_from), n_r drawn from (noise_seed, sample_offset + b, visit) — or by canvas position when the
+        engine has ``canvas_hop`` or a canvas-keyed guide; a ``set_known`` guide ends the launch in its blend at t_to, so a held region
+        stays on its forward path.  One eager launch; ``out`` may be ``z`` (in place).  No consensus pass follows: on windows that
+        agree, the jump is the same linear map with the same normals."""
+        hop = self._renoise_keying()
+        z = L.dev_f32(z, "z")
+        if tuple(z.shape) != self.latent_shape:
+            raise ValueError(f"latent shape {tuple(z.shape)} != engine shape {self.latent_shape}")
+        return Fn.renoise(z, t_from, t_to, self.alpha_bar, self.noise_seed, visit, self.sample_offset, guide=self._guide,
+                          canvas_hop=hop, out=out)
+
+    def advance_renoise(self, z: torch.Tensor, visit: int) -> None:
+        """``renoise`` in place at the cursor's pair (t_from, t_to) = (sched[i], sched[i + 1]); the cursor moves on, so the steps that
+        follow — eager or replayed from a captured pair — read the right timesteps."""
+        L.check(L.lib().avd_sched_advance(self._sched.data_ptr(), self._sched.numel(), self._cursor.data_ptr(),
+                                          self._tn.data_ptr(), self._tp.data_ptr(), self.embed.B, L.stream_ptr(self.device)))
+        self.renoise(z, self._tn, self._tp, visit, out=z)
 
     def run(self, z: torch.Tensor, sched: torch.Tensor, graph: Optional[bool] = None) -> torch.Tensor:
         """Apply len(sched)-1 steps.  ``graph=True`` replays a captured two-step HIP graph; ``None`` (default) does so when the
@@ -786,9 +853,17 @@ class DenoiseEngine:
         With a ``guidance_interval`` the schedule is read on the host and split into maximal segments of CFG and of cond-only steps
         (schedule_utils.guidance_segments); the device cursor runs on across them.  Each kind follows the rule above with its own
         row count (B*N for cond-only steps), takes its own warm-up step outside capture and keeps its own captured pair for the
-        whole run; capturing one kind leaves the other's pair valid."""
+        whole run; capturing one kind leaves the other's pair valid.
+        A resampling schedule (schedule_utils.resample_schedule: RePaint resampling; recognised by schedule_utils.has_jumps, an
+        up-jump back to a timestep already passed) is split the same way (schedule_utils.step_segments): a pair sched[i] <
+        sched[i + 1] is a renoise — one eager launch, in place in the current
+        latent buffer, visit = i, its timesteps read off the device cursor (``advance_renoise``) — so the captured pairs of the
+        denoising kinds stay valid and aligned.  It needs ``noise_seed``, and under a window consensus the canvas keying
+        (``check_schedule``).  Solver "dpmpp_2m" takes the first step after a jump first order (avd_sched_advance_ms leaves t_last = -1
+        there) and overwrites x0_hist with it.  Limit: at eta > 0 the step noise stays keyed by (sample, t_now, element), so a
+        revisited timestep repeats its step normals; only the renoise normals are fresh per visit."""
         self.check_schedule(sched)
-        if self.guidance_interval is not None:
+        if self.guidance_interval is not None or su.has_jumps(sched):
             return self._run_segments(z, sched, graph)
         if graph is None:
             graph = (self.eta == 0 or self._key is not None) and 2 * self.embed.B * self.N < self.GRAPH_BELOW_ROWS
@@ -812,9 +887,13 @@ class DenoiseEngine:
         return za
 
     def _run_segments(self, z: torch.Tensor, sched: torch.Tensor, graph: Optional[bool]) -> torch.Tensor:
-        """``run`` under a guidance interval.  A captured pair steps cur -> other -> cur between the two latent buffers it was
-        captured on, so it is replayed only while the trajectory sits in its source buffer; a single eager step puts it there."""
-        segs = su.guidance_segments(sched, self.guidance_interval)
+        """``run`` under a guidance interval or over a schedule with up-jumps.  A captured pair steps cur -> other -> cur between the
+        two latent buffers it was captured on, so it is replayed only while the trajectory sits in its source buffer; a single eager
+        step puts it there.  A renoise pair works in place in ``cur`` and swaps nothing."""
+        if su.has_jumps(sched):
+            segs = su.step_segments(sched, self.guidance_interval)
+        else:
+            segs = [(a, b, "cfg" if cfg else "cond") for a, b, cfg in su.guidance_segments(sched, self.guidance_interval)]
         graphable = self.eta == 0 or self._key is not None
         use_graph = {}
         for cfg in (True, False):
@@ -824,7 +903,12 @@ class DenoiseEngine:
         cur = L.dev_f32(z, "z").clone()
         other = torch.empty_like(cur)
         warmed, pairs = set(), {}                   # per kind: warm-up step taken; (captured pair, its source buffer)
-        for start, stop, cfg in segs:
+        for start, stop, kind in segs:
+            if kind == "renoise":
+                for i in range(start, stop):
+                    self.advance_renoise(cur, i)
+                continue
+            cfg = kind == "cfg"
             left, cond = stop - start, not cfg
             while left:
                 replay = False
@@ -871,6 +955,17 @@ def frame_mask(latent_shape, lo: int, hi: int) -> torch.Tensor:
     return m
 
 
+def check_resample_args(rs, has_init: bool, has_mask: bool, noise_seed) -> None:
+    """what RePaint resampling asks of a pipeline call (sample_one_direction, stream_generate): ``rs`` None or (jump, resamples)"""
+    if rs is None:
+        return
+    if not (has_init and has_mask):
+        raise ValueError("resample (RePaint resampling) harmonises a generated region with a held one: it needs an init clip with a "
+                         "mask (init_video / init_audio and mask)")
+    if noise_seed is None:
+        raise ValueError("resample draws its forward jumps from the seeded stream: it needs noise_seed (also at ddim_eta == 0)")
+
+
 def canvas_frame_mask(canvas_shape, lo: int, hi: int) -> torch.Tensor:
     """``frame_mask`` on a latent canvas (stream_generate ``mask``): float32 ones on canvas positions [lo, hi) and zeros elsewhere — the P
     axis of a video canvas [C,P,H,W] or of an audio canvas [Ca,P].  "Keep the first positions of the long clip and generate what
@@ -892,7 +987,7 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
                          device: torch.device, init_noise: Optional[torch.Tensor] = None,
                          noise_seed: Optional[int] = None, init_video: Optional[np.ndarray] = None,
                          init_audio: Optional[np.ndarray] = None, strength: float = 1.0, mask=None,
-                         guide_seed: Optional[int] = None, guidance_interval=None) -> Dict[str, np.ndarray]:
+                         guide_seed: Optional[int] = None, guidance_interval=None, resample=None) -> Dict[str, np.ndarray]:
     """sample_clip.py:220-394 with the loop on the HIP engine.  The V->A branch uses the [1,3,T,H,W] layout the
     reference's comment intends (its own permute at :288 is a bug that crashes in conv3d).
     ``init_noise`` (extension; default None = draw it as the reference does, :297 / :304): the target's initial latent, so that a
@@ -912,7 +1007,13 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
     (DenoiseEngine ``guidance_rescale``); 0 runs the plain step.
     ``guidance_interval`` (extension; default None) or ``sampling.guidance_interval`` (a per-modality dict of [t_lo, t_hi] like
     ``guidance_scale``; the argument wins): apply guidance only on steps with t_lo <= t_now <= t_hi, step on the conditional
-    prediction alone elsewhere (DenoiseEngine ``guidance_interval``)."""
+    prediction alone elsewhere (DenoiseEngine ``guidance_interval``).
+    ``resample`` (extension; default None) = (jump, resamples), or ``sampling.resample: {jump:, resamples:}`` (the argument wins):
+    RePaint resampling of a masked init clip — after every ``jump`` steps the latent is sent back up the schedule by a seeded forward
+    jump and the stretch is denoised again, ``resamples`` passes in all (schedule_utils.resample_schedule, applied after ``strength``
+    has truncated the schedule; DenoiseEngine ``renoise``), so that the generated region harmonises with the held one.  It needs an
+    init clip with a ``mask``, and ``noise_seed`` (the key of the renoise normals, also at ``ddim_eta`` == 0); resamples == 1 is
+    today's run.  At ``ddim_eta`` > 0 a revisited timestep repeats its step normals; only the jumps draw fresh ones."""
     # argument checks that need no device
     strength = float(strength)
     if not 0.0 <= strength <= 1.0:
@@ -927,6 +1028,8 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
     if init_audio is not None and prompt_modality != "video":
         raise ValueError("init_audio is the target of the video->audio direction (prompt_modality='video')")
     dcfg, scfg = cfg["diffusion"], cfg["sampling"]
+    rs = su.check_resample(resample) or su.resample_from_config(scfg)
+    check_resample_args(rs, init is not None, mask is not None, noise_seed)
     eta = float(scfg.get("ddim_eta", 0.0))
     solver = str(scfg.get("solver", "ddim"))
     t_p, p, p_w = tube_from_config(cfg)
@@ -999,6 +1102,8 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
         z, sched = eng.start_latent(z, sched, strength)
         if mask is None:
             eng.clear_known()          # SDEdit without a mask: the whole latent is free, the plain step runs
+        if rs is not None:
+            sched = su.resample_schedule(sched, *rs)
     z = eng.run(z, sched)
     if target == "audio":
         return {"audio": aud_codec.decode(z).squeeze(0).squeeze(0).detach().cpu().numpy(), "sr": sr}

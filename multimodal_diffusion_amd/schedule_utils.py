@@ -97,6 +97,92 @@ def guidance_segments(sched, interval) -> List[Tuple[int, int, bool]]:
     return segs
 
 
+def _whole(v, name: str) -> int:
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1:
+        raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+    return int(v)
+
+
+def check_resample(resample) -> Optional[Tuple[int, int]]:
+    """Validate a RePaint resampling setting: None (off), a pair (jump, resamples) or a dict {"jump":, "resamples":} (the config's
+    ``sampling.resample``), both integers >= 1.  Returns None or the pair as Python ints.  Host-side."""
+    if resample is None:
+        return None
+    if isinstance(resample, dict):
+        if set(resample) != {"jump", "resamples"}:
+            raise ValueError(f"resample as a dict holds exactly 'jump' and 'resamples', got {sorted(resample)}")
+        resample = (resample["jump"], resample["resamples"])
+    if isinstance(resample, (str, bytes)) or not hasattr(resample, "__len__") or len(resample) != 2:
+        raise ValueError(f"resample must be None, a pair (jump, resamples) or a dict with those keys, got {resample!r}")
+    return _whole(resample[0], "resample jump"), _whole(resample[1], "resamples")
+
+
+def resample_schedule(sched, jump: int, resamples: int) -> torch.Tensor:
+    """The RePaint time-travel schedule (Lugmayr et al. 2022; diffusers' ``RePaintScheduler``) of a decreasing sampling schedule
+    s[0..n] that ends in -1.  The n steps are cut into blocks of ``jump`` steps, block k from a_k = k*jump to b_k = min(a_k + jump, n).
+    A block with s[b_k] >= 0 is emitted ``resamples`` times, its passes joined by the up-jump s[b_k] -> s[a_k] (a renoise pair, see
+    ``step_segments``); the block that ends in -1 is emitted once — a finished latent is never sent back.  n = 4, jump = 2,
+    resamples = 2 gives [s0, s1, s2, s0, s1, s2, s3, s4].  ``resamples`` == 1 returns the schedule unchanged.  Host-side (int64 CPU
+    tensor)."""
+    jump, resamples = _whole(jump, "jump"), _whole(resamples, "resamples")
+    sc = torch.as_tensor(sched).reshape(-1).to("cpu", torch.long)
+    s = sc.tolist()
+    if not s or s[-1] != -1:
+        raise ValueError("resample_schedule needs a sampling schedule that ends in -1")
+    if any(b >= a for a, b in zip(s[:-1], s[1:])):
+        raise ValueError("resample_schedule needs a strictly decreasing schedule (resample once, from make_sampling_schedule / "
+                         "truncate_schedule)")
+    n = len(s) - 1
+    if resamples == 1 or n == 0:
+        return sc.clone()
+    out = [s[0]]
+    for a in range(0, n, jump):
+        b = min(a + jump, n)
+        for r in range(resamples if s[b] >= 0 else 1):
+            if r:
+                out.append(s[a])                 # the up-jump s[b] -> s[a]
+            out.extend(s[a + 1:b + 1])
+    return torch.tensor(out, dtype=torch.long)
+
+
+def step_segments(sched, interval) -> List[Tuple[int, int, str]]:
+    """``guidance_segments`` for a schedule that may hold up-jumps: pair i = (sched[i], sched[i + 1]) is a "renoise" when sched[i + 1] >
+    sched[i] (the forward jump of a resampling schedule), else a denoising step — "cfg" when t_lo <= sched[i] <= t_hi (``interval``
+    None: always), else "cond".  Equal neighbours are a ValueError.  Returns the maximal runs of equal kind as [(start, stop, kind)]
+    with pairs start .. stop - 1, in order; together they partition range(len(sched) - 1).  Host-side."""
+    iv = check_guidance_interval(interval)
+    sc = torch.as_tensor(sched).reshape(-1).to("cpu", torch.long).tolist()
+    segs: List[Tuple[int, int, str]] = []
+    for i, (t, nxt) in enumerate(zip(sc[:-1], sc[1:])):
+        if nxt == t:
+            raise ValueError(f"schedule entries {i} and {i + 1} are both {t}: a pair is a denoising step (down) or a renoise (up)")
+        kind = "renoise" if nxt > t else ("cfg" if iv is None or iv[0] <= t <= iv[1] else "cond")
+        if segs and segs[-1][2] == kind:
+            segs[-1] = (segs[-1][0], i + 1, kind)
+        else:
+            segs.append((i, i + 1, kind))
+    return segs
+
+
+def has_jumps(sched) -> bool:
+    """Whether a schedule is a resampling schedule: it holds a time-travel jump, an up-pair that returns to a timestep the schedule
+    has already passed (the only jumps ``resample_schedule`` emits).  ``DenoiseEngine.run`` and ``stream_generate`` read every
+    up-pair of such a schedule as a renoise (``step_segments``).  An up-pair to a timestep not seen before is no time travel: the DDIM
+    engine has always taken any schedule and steps through such a pair as before, the multistep solver refuses it as before."""
+    seen = set()
+    sc = torch.as_tensor(sched).reshape(-1).to("cpu", torch.long).tolist()
+    for a, b in zip(sc[:-1], sc[1:]):
+        seen.add(a)
+        if b > a and b in seen:
+            return True
+    return False
+
+
+def resample_from_config(scfg) -> Optional[Tuple[int, int]]:
+    """``sampling.resample`` of a config: {jump:, resamples:}; a missing key or None means no resampling."""
+    return check_resample(scfg.get("resample"))
+
+
 def guidance_interval_from_config(scfg, modality: str) -> Optional[Tuple[int, int]]:
     """``sampling.guidance_interval`` of a config: a per-modality dict of [t_lo, t_hi] (like ``guidance_scale``); a missing key or
     modality, or None, means guidance on every step."""

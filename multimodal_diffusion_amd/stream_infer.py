@@ -30,7 +30,7 @@ from . import _lib as L
 from . import dist as D
 from . import functional as Fn
 from . import schedule_utils as su
-from .sampler import DenoiseEngine, tube_from_config
+from .sampler import DenoiseEngine, check_resample_args, tube_from_config
 
 
 def split_audio_into_windows(y: np.ndarray, sr: int, win_s: float, hop_s: float) -> Tuple[np.ndarray, int, int]:
@@ -173,7 +173,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
                     noise_seed: Optional[int] = None, guidance_interval=None, consensus=None,
                     return_latents: bool = False, noise_keying: Optional[str] = None, init_video: Optional[np.ndarray] = None,
                     init_audio: Optional[np.ndarray] = None, strength: float = 1.0, mask=None,
-                    guide_seed: Optional[int] = None) -> Optional[Dict[str, np.ndarray]]:
+                    guide_seed: Optional[int] = None, resample=None) -> Optional[Dict[str, np.ndarray]]:
     """The body of the reference's ``main()`` (stream_infer.py:146-225) minus file I/O, with all windows batched.
 
     Returns {"audio": wav, "sr"} for a video prompt or {"video": frames uint8, "fps"} for an audio prompt.
@@ -232,6 +232,13 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     path through every consensus mean and the finished latents equal the known canvas there, for any ``max_windows_per_batch``.
     ``ddim_eta`` > 0 needs ``noise_seed`` (and under consensus ``noise_keying="canvas"``), as without a guide.  An init clip with
     ``shard=True`` is refused: the known windows would need a second broadcast, which is not implemented.
+    ``resample`` (default None) = (jump, resamples), or ``sampling.resample: {jump:, resamples:}`` (the argument wins): RePaint
+    resampling as in ``sample_one_direction`` — the schedule, truncated by ``strength`` first, is expanded with
+    ``schedule_utils.resample_schedule`` and every up-jump is a seeded forward jump of all windows (DenoiseEngine ``renoise``).  It needs
+    an init clip with a ``mask``, and ``noise_seed``.  Without consensus window i draws its renoise normals as sample i; with
+    consensus they are keyed by canvas position like the guide's known noise (window offset = the engine's first window), so every
+    window draws the same normals at a shared position: agreeing windows still agree after a jump, no consensus pass follows it, and
+    the latents are the same bits for any ``max_windows_per_batch`` where the engines take the same kernels.
     """
     # the latent guide's argument checks that need no device (the window count and the mask's shape follow the prompt split below)
     strength = float(strength)
@@ -257,6 +264,8 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         init = np.asarray(init_audio)
         if init.ndim != 1 or not np.issubdtype(init.dtype, np.floating):
             raise ValueError(f"init_audio must be a float waveform [N], got {init.dtype} {init.shape}")
+    rs = su.check_resample(resample) or su.resample_from_config(cfg["sampling"])
+    check_resample_args(rs, init is not None, mask is not None, noise_seed)
     st = cfg.get("streaming", {})
     win_s, hop_s = float(st.get("window_seconds", 3.0)), float(st.get("hop_seconds", 1.0))
     xfade_s = float(st.get("crossfade_seconds", 0.25))
@@ -430,7 +439,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         z, sched_k = eng.start_latent(z, sched, strength)
         if mask_w is None:
             eng.clear_known()          # SDEdit without a mask: the whole latent is free, the plain step runs
-        return z, sched_k
+        return z, (sched_k if rs is None else su.resample_schedule(sched_k, *rs))
 
     def engine(zp_part: torch.Tensor, lo0: int, lo: int, hi: int) -> DenoiseEngine:
         """the engine of windows [lo, hi), its prompt rows set from zp_part (which starts at window lo0)"""
@@ -481,10 +490,18 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         zb = torch.empty_like(za)
         if sched_k.numel() < 2:
             return za                              # strength 0: no steps, the known windows
-        for first, stop, cfg_step in su.guidance_segments(sched_k, interval):     # the kind of every step, read on the host as run() does
-            for _ in range(stop - first):
+        if su.has_jumps(sched_k):
+            segs = su.step_segments(sched_k, interval)
+        else:
+            segs = [(a, b, "cfg" if cfg_step else "cond") for a, b, cfg_step in su.guidance_segments(sched_k, interval)]
+        for first, stop, kind in segs:             # the kind of every pair, read on the host as run() does
+            for i in range(first, stop):
+                if kind == "renoise":              # canvas-keyed: the same linear map with the same normals on agreeing windows
+                    for lo, hi, eng in engs:
+                        eng.advance_renoise(za[lo:hi], i)
+                    continue
                 for lo, hi, eng in engs:
-                    eng.advance(za[lo:hi], zb[lo:hi], cond_only=not cfg_step)
+                    eng.advance(za[lo:hi], zb[lo:hi], cond_only=kind == "cond")
                 Fn.window_consensus(zb, cons_hop, w_dev)
                 za, zb = zb, za
         return za
