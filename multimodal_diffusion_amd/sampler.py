@@ -20,9 +20,11 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import _pipeline as P
 from . import functional as Fn
 from . import ops
 from . import schedule_utils as su
+from ._pipeline import tube_from_config      # noqa: F401  (its home is the pipeline front end)
 from .mmdt import MMDiT
 from .noise_heads import MultiModalNoiseHead
 
@@ -87,12 +89,6 @@ def build_components(cfg: Dict, device: torch.device, vid_vae: Optional[nn.Modul
 
 def latents_to_tokens_video(z_v: torch.Tensor, t_p: int, p: int) -> torch.Tensor:
     return ops.tube_patch_video(z_v, t=t_p, h=p, w=p)
-
-
-def tube_from_config(cfg: Dict) -> Tuple[int, int, int]:
-    """tokenizer.video.tube as (t, h, w); a config without "w" has the reference's square tube (w = h)"""
-    tube = cfg["tokenizer"]["video"]["tube"]
-    return int(tube["t"]), int(tube["h"]), int(tube.get("w", tube["h"]))
 
 
 def latents_to_tokens_audio(z_a: torch.Tensor, l_chunk: int, s_chunk: int) -> torch.Tensor:
@@ -701,21 +697,20 @@ class DenoiseEngine:
         guide = None if self._guide is None else C.byref(self._guide)
         zx, ts = (z.data_ptr(), self.Xp.data_ptr()), (tn.data_ptr(), tp.data_ptr())
         tail = (out.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device))
+        ctl = None if self._ctl is None or cond_only else C.byref(self._ctl)      # the CFG control does not apply to a cond-only step
+        cond = 1 if cond_only else 0
         if guide is not None and self._guide_hop is not None:
-            ctl = None if self._ctl is None or cond_only else C.byref(self._ctl)
-            rc = lib.avd_denoise_step_canvas_guided_f32(desc, guide, self._guide_hop, key if self.eta > 0 else None, ctl,
-                                                        1 if cond_only else 0, L.ptr(tl), L.ptr(h), *zx, *ts, *tail)
+            rc = lib.avd_denoise_step_canvas_guided_f32(desc, guide, self._guide_hop, key if self.eta > 0 else None, ctl, cond,
+                                                        L.ptr(tl), L.ptr(h), *zx, *ts, *tail)
         elif self.solver == "dpmpp_2m" and self.eta > 0:
-            ctl = None if self._ctl is None or cond_only else C.byref(self._ctl)
-            rc = lib.avd_denoise_step_dpmpp_2m_sde_f32(desc, key, self.canvas_hop or 0, ctl, guide, 1 if cond_only else 0, tl.data_ptr(),
-                                                       h.data_ptr(), *zx, *ts, *tail)
+            rc = lib.avd_denoise_step_dpmpp_2m_sde_f32(desc, key, self.canvas_hop or 0, ctl, guide, cond, tl.data_ptr(), h.data_ptr(),
+                                                       *zx, *ts, *tail)
         elif self.canvas_hop is not None and self.eta > 0:
-            ctl = None if self._ctl is None or cond_only else C.byref(self._ctl)
-            rc = lib.avd_denoise_step_canvas_f32(desc, key, self.canvas_hop, ctl, guide, 1 if cond_only else 0, *zx, *ts, *tail)
+            rc = lib.avd_denoise_step_canvas_f32(desc, key, self.canvas_hop, ctl, guide, cond, *zx, *ts, *tail)
         elif cond_only:
             rc = lib.avd_denoise_step_cond_f32(desc, guide, key, L.ptr(tl), L.ptr(h), *zx, *ts, L.ptr(noise), *tail)
-        elif self._ctl is not None:
-            rc = lib.avd_denoise_step_cfg_f32(desc, C.byref(self._ctl), guide, key, L.ptr(tl), L.ptr(h), *zx, *ts, *tail)
+        elif ctl is not None:
+            rc = lib.avd_denoise_step_cfg_f32(desc, ctl, guide, key, L.ptr(tl), L.ptr(h), *zx, *ts, *tail)
         elif guided:
             rc = lib.avd_denoise_step_guided_f32(desc, guide, key, L.ptr(tl), L.ptr(h), *zx, *ts, *tail)
         elif h is not None:
@@ -756,16 +751,18 @@ class DenoiseEngine:
         """dst = one step from src at the cursor's (t_now, t_prev); the cursor moves on, all on the stream.  Solver "dpmpp_2m" also
         reads t_last off the cursor (-1 at the start of the schedule: every trajectory begins first order).  ``cond_only``: as
         ``step`` — the cursor's timesteps stay on the device, the caller names the kind of step."""
-        if self.solver == "dpmpp_2m":
-            L.check(L.lib().avd_sched_advance_ms(self._sched.data_ptr(), self._sched.numel(), self._cursor.data_ptr(),
-                                                 self._tl.data_ptr(), self._tn.data_ptr(), self._tp.data_ptr(), self.embed.B,
-                                                 L.stream_ptr(self.device)))
-            self.step(src, self._tn, self._tp, out=dst, t_last=self._tl, cond_only=cond_only)
-            return
-        L.check(L.lib().avd_sched_advance(self._sched.data_ptr(), self._sched.numel(), self._cursor.data_ptr(),
-                                          self._tn.data_ptr(), self._tp.data_ptr(), self.embed.B,
-                                          L.stream_ptr(self.device)))
-        self.step(src, self._tn, self._tp, out=dst, cond_only=cond_only)
+        multistep = self.solver == "dpmpp_2m"
+        self._advance_cursor(multistep)
+        self.step(src, self._tn, self._tp, out=dst, t_last=self._tl if multistep else None, cond_only=cond_only)
+
+    def _advance_cursor(self, multistep: bool) -> None:
+        """the cursor's pair into (_tn, _tp), with ``multistep`` the entry before it into _tl as well; the cursor moves on"""
+        cursor = (self._sched.data_ptr(), self._sched.numel(), self._cursor.data_ptr())
+        tail = (self._tn.data_ptr(), self._tp.data_ptr(), self.embed.B, L.stream_ptr(self.device))
+        if multistep:
+            L.check(L.lib().avd_sched_advance_ms(*cursor, self._tl.data_ptr(), *tail))
+        else:
+            L.check(L.lib().avd_sched_advance(*cursor, *tail))
 
     def capture_pair(self, za: torch.Tensor, zb: torch.Tensor, cond_only: bool = False) -> "_CapturedPair":
         """Capture two steps (za -> zb -> za) of one kind into one HIP graph; replaying it advances the trajectory by two."""
@@ -842,8 +839,7 @@ class DenoiseEngine:
     def advance_renoise(self, z: torch.Tensor, visit: int) -> None:
         """``renoise`` in place at the cursor's pair (t_from, t_to) = (sched[i], sched[i + 1]); the cursor moves on, so the steps that
         follow — eager or replayed from a captured pair — read the right timesteps."""
-        L.check(L.lib().avd_sched_advance(self._sched.data_ptr(), self._sched.numel(), self._cursor.data_ptr(),
-                                          self._tn.data_ptr(), self._tp.data_ptr(), self.embed.B, L.stream_ptr(self.device)))
+        self._advance_cursor(False)
         self.renoise(z, self._tn, self._tp, visit, out=z)
 
     def run(self, z: torch.Tensor, sched: torch.Tensor, graph: Optional[bool] = None) -> torch.Tensor:
@@ -861,39 +857,12 @@ class DenoiseEngine:
         denoising kinds stay valid and aligned.  It needs ``noise_seed``, and under a window consensus the canvas keying
         (``check_schedule``).  Solver "dpmpp_2m" takes the first step after a jump first order (avd_sched_advance_ms leaves t_last = -1
         there) and overwrites x0_hist with it.  Limit: at eta > 0 the step noise stays keyed by (sample, t_now, element), so a
-        revisited timestep repeats its step normals; only the renoise normals are fresh per visit."""
+        revisited timestep repeats its step normals; only the renoise normals are fresh per visit.
+        One loop runs every schedule (schedule_utils.trajectory_segments; a plain schedule is one CFG segment).  A captured pair steps
+        cur -> other -> cur between the two latent buffers it was captured on, so it is replayed only while the trajectory sits in
+        its source buffer; a single eager step puts it there.  A renoise pair works in place in ``cur`` and swaps nothing."""
         self.check_schedule(sched)
-        if self.guidance_interval is not None or su.has_jumps(sched):
-            return self._run_segments(z, sched, graph)
-        if graph is None:
-            graph = (self.eta == 0 or self._key is not None) and 2 * self.embed.B * self.N < self.GRAPH_BELOW_ROWS
-        self.begin(sched)
-        za = L.dev_f32(z, "z").clone()
-        zb = torch.empty_like(za)
-        n_steps = self._sched.numel() - 1
-        if not graph or n_steps < 3:
-            for _ in range(n_steps):
-                self.advance(za, zb)
-                za, zb = zb, za
-            return za
-        self.advance(za, zb)                        # warm-up step outside capture
-        za, zb = zb, za
-        g = self.capture_pair(za, zb)               # capture enqueues nothing: the cursor still reads 1
-        for _ in range((n_steps - 1) // 2):
-            g.replay()
-        if (n_steps - 1) % 2:
-            self.advance(za, zb)
-            za = zb
-        return za
-
-    def _run_segments(self, z: torch.Tensor, sched: torch.Tensor, graph: Optional[bool]) -> torch.Tensor:
-        """``run`` under a guidance interval or over a schedule with up-jumps.  A captured pair steps cur -> other -> cur between the
-        two latent buffers it was captured on, so it is replayed only while the trajectory sits in its source buffer; a single eager
-        step puts it there.  A renoise pair works in place in ``cur`` and swaps nothing."""
-        if su.has_jumps(sched):
-            segs = su.step_segments(sched, self.guidance_interval)
-        else:
-            segs = [(a, b, "cfg" if cfg else "cond") for a, b, cfg in su.guidance_segments(sched, self.guidance_interval)]
+        segs = su.trajectory_segments(sched, self.guidance_interval)
         graphable = self.eta == 0 or self._key is not None
         use_graph = {}
         for cfg in (True, False):
@@ -955,17 +924,6 @@ def frame_mask(latent_shape, lo: int, hi: int) -> torch.Tensor:
     return m
 
 
-def check_resample_args(rs, has_init: bool, has_mask: bool, noise_seed) -> None:
-    """what RePaint resampling asks of a pipeline call (sample_one_direction, stream_generate): ``rs`` None or (jump, resamples)"""
-    if rs is None:
-        return
-    if not (has_init and has_mask):
-        raise ValueError("resample (RePaint resampling) harmonises a generated region with a held one: it needs an init clip with a "
-                         "mask (init_video / init_audio and mask)")
-    if noise_seed is None:
-        raise ValueError("resample draws its forward jumps from the seeded stream: it needs noise_seed (also at ddim_eta == 0)")
-
-
 def canvas_frame_mask(canvas_shape, lo: int, hi: int) -> torch.Tensor:
     """``frame_mask`` on a latent canvas (stream_generate ``mask``): float32 ones on canvas positions [lo, hi) and zeros elsewhere — the P
     axis of a video canvas [C,P,H,W] or of an audio canvas [Ca,P].  "Keep the first positions of the long clip and generate what
@@ -1014,98 +972,42 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
     has truncated the schedule; DenoiseEngine ``renoise``), so that the generated region harmonises with the held one.  It needs an
     init clip with a ``mask``, and ``noise_seed`` (the key of the renoise normals, also at ``ddim_eta`` == 0); resamples == 1 is
     today's run.  At ``ddim_eta`` > 0 a revisited timestep repeats its step normals; only the jumps draw fresh ones."""
-    # argument checks that need no device
-    strength = float(strength)
-    if not 0.0 <= strength <= 1.0:
-        raise ValueError(f"strength must lie in [0, 1], got {strength}")
-    init = init_video if init_video is not None else init_audio
-    if init_video is not None and init_audio is not None:
-        raise ValueError("pass init_video or init_audio, not both")
-    if init is None and (mask is not None or strength < 1.0):
-        raise ValueError("a mask or a strength < 1 needs an init clip (init_video for audio->video, init_audio for video->audio)")
-    if init_video is not None and prompt_modality != "audio":
-        raise ValueError("init_video is the target of the audio->video direction (prompt_modality='audio')")
-    if init_audio is not None and prompt_modality != "video":
-        raise ValueError("init_audio is the target of the video->audio direction (prompt_modality='video')")
-    dcfg, scfg = cfg["diffusion"], cfg["sampling"]
-    rs = su.check_resample(resample) or su.resample_from_config(scfg)
-    check_resample_args(rs, init is not None, mask is not None, noise_seed)
-    eta = float(scfg.get("ddim_eta", 0.0))
-    solver = str(scfg.get("solver", "ddim"))
-    t_p, p, p_w = tube_from_config(cfg)
-    l_chunk = int(cfg["tokenizer"]["audio"]["chunk"]["length"])
-    s_chunk = int(cfg["tokenizer"]["audio"]["chunk"]["stride"])
-    Cv, t_down, s_down = (int(cfg["video"]["latent"][k]) for k in ("channels", "t_down", "s_down"))
-    Ca, Fa = int(cfg["audio"]["latent"]["channels"]), int(cfg["audio"]["latent"]["frames_per_clip"])
-    fps, sr = int(cfg["video"]["fps"]), int(cfg["audio"]["sr"])
-    H, W = int(cfg["video"]["size"][0]), int(cfg["video"]["size"][1])
-
-    def table(m):
-        c = dcfg[m]
-        betas = su.make_beta_schedule(int(c["steps"]), kind=c["schedule"], min_beta=c["min_beta"], max_beta=c["max_beta"])
-        return su.alphas_cumprod_from_betas(betas)[1], su.make_sampling_schedule(int(c["steps"]), int(c["sampler_steps"]))
-
-    if prompt_modality == "video":
+    strength = P.check_init_args(prompt_modality, init_video, init_audio, strength, mask)
+    init = P.init_clip_array(init_video, init_audio)
+    pc = P.read_config(cfg, prompt_modality, guidance_interval=guidance_interval, resample=resample, has_init=init is not None,
+                       has_mask=mask is not None, noise_seed=noise_seed)
+    if pc.target == "audio":
         if prompt_video is None:
             raise ValueError("prompt_video frames required for prompt_modality=video")
-        frames = torch.from_numpy(prompt_video).to(device).float() / 255.0          # [T,H,W,3]
-        z_p = vid_vae.encode(frames.permute(3, 0, 1, 2).unsqueeze(0).contiguous())   # [1,3,T,H,W] -> [1,Cv,T',H',W']
-        z = torch.randn(1, Ca, Fa, device=device) if init_noise is None else init_noise.to(device).float()
-        if tuple(z.shape) != (1, Ca, Fa):
-            raise ValueError(f"init_noise has shape {tuple(z.shape)}, expected {(1, Ca, Fa)}")
-        target, guide = "audio", float(scfg["guidance_scale"].get("audio", 3.0))
-        n_prompt = (z_p.shape[2] // t_p) * (z_p.shape[3] // p) * (z_p.shape[4] // p_w)
-    elif prompt_modality == "audio":
+        z_p = P.encode_video(vid_vae, prompt_video, device)                          # [1,3,T,H,W] -> [1,Cv,T',H',W']
+        lat_shape = (1, pc.Ca, pc.Fa)
+    else:
         if prompt_audio is None:
             raise ValueError("prompt_audio required for prompt_modality=audio")
-        wav = torch.from_numpy(prompt_audio).to(device).view(1, 1, -1)
-        z_p = aud_codec.encode(wav)                                                  # [1,Ca,Fa]
-        T_in = prompt_video.shape[0] if prompt_video is not None else int(round(cfg["data"]["clip_seconds"] * fps))
-        lat_shape = (1, Cv, max(1, T_in // t_down), H // s_down, W // s_down)
-        z = torch.randn(*lat_shape, device=device) if init_noise is None else init_noise.to(device).float()
-        if tuple(z.shape) != lat_shape:
-            raise ValueError(f"init_noise has shape {tuple(z.shape)}, expected {lat_shape}")
-        target, guide = "video", float(scfg["guidance_scale"].get("video", 3.0))
-        n_prompt = (z_p.shape[-1] - l_chunk) // s_chunk + 1
-    else:
-        raise ValueError("prompt_modality must be 'video' or 'audio'")
-
-    abar, sched = table(target)
-    rescale = float(scfg.get("guidance_rescale", {}).get(target, 0.0))
-    interval = su.check_guidance_interval(guidance_interval) or su.guidance_interval_from_config(scfg, target)
-    eng = DenoiseEngine(adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, target=target,
-                        latent_shape=tuple(z.shape), prompt_tokens=n_prompt, alpha_bar=abar, guidance=guide, eta=eta,
-                        tube=(t_p, p, p_w), chunk=(l_chunk, s_chunk), noise_seed=noise_seed, solver=solver, guidance_rescale=rescale,
-                        guidance_interval=interval)
+        z_p = P.encode_audio(aud_codec, prompt_audio, device, as_float32=False)      # [1,Ca,Fa]
+        T_in = prompt_video.shape[0] if prompt_video is not None else int(round(cfg["data"]["clip_seconds"] * pc.fps))
+        lat_shape = (1, pc.Cv, max(1, T_in // pc.t_down), pc.H // pc.s_down, pc.W // pc.s_down)
+    z = torch.randn(*lat_shape, device=device) if init_noise is None else init_noise.to(device).float()
+    if tuple(z.shape) != lat_shape:
+        raise ValueError(f"init_noise has shape {tuple(z.shape)}, expected {lat_shape}")
+    eng = P.build_engine(pc, adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, latent_shape=lat_shape,
+                         n_prompt=P.prompt_tokens(pc, z_p.shape), noise_seed=noise_seed)
     eng.set_prompt(z_p.float())
+    sched = pc.sched
     if init is not None:
-        if target == "video":
-            iv = np.asarray(init_video)
-            if iv.ndim != 4 or iv.shape[-1] != 3 or iv.dtype != np.uint8:
-                raise ValueError(f"init_video must be uint8 [T,H,W,3], got {iv.dtype} {iv.shape}")
-            fr = torch.from_numpy(iv).to(device).float() / 255.0
-            known = vid_vae.encode(fr.permute(3, 0, 1, 2).unsqueeze(0).contiguous())
-        else:
-            ia = np.asarray(init_audio)
-            if ia.ndim != 1 or not np.issubdtype(ia.dtype, np.floating):
-                raise ValueError(f"init_audio must be a float waveform [N], got {ia.dtype} {ia.shape}")
-            known = aud_codec.encode(torch.from_numpy(ia).to(device).float().view(1, 1, -1))
-        if tuple(known.shape) != tuple(z.shape):
-            raise ValueError(f"the init clip encodes to a latent of shape {tuple(known.shape)}, the target's is {tuple(z.shape)}")
-        m = torch.zeros(tuple(z.shape[1:])) if mask is None else torch.as_tensor(mask, dtype=torch.float32)
-        if m.dim() == len(z.shape):
-            m = m.squeeze(0)
-        if tuple(m.shape) != tuple(z.shape[1:]):
-            raise ValueError(f"mask has shape {tuple(m.shape)}, expected one sample's latent shape {tuple(z.shape[1:])}")
-        gs = guide_seed if guide_seed is not None else (noise_seed if noise_seed is not None else 0)
-        eng.set_known(known, m, guide_seed=gs)
-        z, sched = eng.start_latent(z, sched, strength)
-        if mask is None:
-            eng.clear_known()          # SDEdit without a mask: the whole latent is free, the plain step runs
-        if rs is not None:
-            sched = su.resample_schedule(sched, *rs)
+        known = P.encode_video(vid_vae, init, device) if pc.target == "video" else P.encode_audio(aud_codec, init, device)
+        if tuple(known.shape) != lat_shape:
+            raise ValueError(f"the init clip encodes to a latent of shape {tuple(known.shape)}, the target's is {lat_shape}")
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask, dtype=torch.float32)
+            if m.dim() == len(lat_shape):
+                m = m.squeeze(0)
+            if tuple(m.shape) != lat_shape[1:]:
+                raise ValueError(f"mask has shape {tuple(m.shape)}, expected one sample's latent shape {lat_shape[1:]}")
+        z, sched = P.guided_start(eng, pc, known, m, z, strength, P.default_guide_seed(guide_seed, noise_seed))
     z = eng.run(z, sched)
-    if target == "audio":
-        return {"audio": aud_codec.decode(z).squeeze(0).squeeze(0).detach().cpu().numpy(), "sr": sr}
+    if pc.target == "audio":
+        return {"audio": aud_codec.decode(z).squeeze(0).squeeze(0).detach().cpu().numpy(), "sr": pc.sr}
     x_hat = vid_vae.decode(z).clamp(0, 1)
-    return {"video": (x_hat[0].permute(1, 2, 3, 0).detach().cpu().numpy() * 255.0).astype(np.uint8), "fps": fps}
+    return {"video": (x_hat[0].permute(1, 2, 3, 0).detach().cpu().numpy() * 255.0).astype(np.uint8), "fps": pc.fps}

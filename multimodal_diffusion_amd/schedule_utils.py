@@ -178,6 +178,15 @@ def has_jumps(sched) -> bool:
     return False
 
 
+def trajectory_segments(sched, interval) -> List[Tuple[int, int, str]]:
+    """The pairs of any schedule by kind, [(start, stop, kind)] with kind in {"cfg", "cond", "renoise"}: what ``DenoiseEngine.run`` and
+    ``stream_generate``'s lock-step loop iterate.  A resampling schedule (``has_jumps``) is split by ``step_segments``; any other by
+    ``guidance_segments``, every pair a denoising step — an up-pair to a timestep not seen before and equal neighbours included."""
+    if has_jumps(sched):
+        return step_segments(sched, interval)
+    return [(a, b, "cfg" if cfg else "cond") for a, b, cfg in guidance_segments(sched, interval)]
+
+
 def resample_from_config(scfg) -> Optional[Tuple[int, int]]:
     """``sampling.resample`` of a config: {jump:, resamples:}; a missing key or None means no resampling."""
     return check_resample(scfg.get("resample"))

@@ -27,10 +27,11 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import _pipeline as P
 from . import dist as D
 from . import functional as Fn
 from . import schedule_utils as su
-from .sampler import DenoiseEngine, check_resample_args, tube_from_config
+from .sampler import DenoiseEngine
 
 
 def split_audio_into_windows(y: np.ndarray, sr: int, win_s: float, hop_s: float) -> Tuple[np.ndarray, int, int]:
@@ -241,43 +242,18 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     the latents are the same bits for any ``max_windows_per_batch`` where the engines take the same kernels.
     """
     # the latent guide's argument checks that need no device (the window count and the mask's shape follow the prompt split below)
-    strength = float(strength)
-    if not 0.0 <= strength <= 1.0:
-        raise ValueError(f"strength must lie in [0, 1], got {strength}")
-    init = init_video if init_video is not None else init_audio
-    if init_video is not None and init_audio is not None:
-        raise ValueError("pass init_video or init_audio, not both")
-    if init is None and (mask is not None or strength < 1.0):
-        raise ValueError("a mask or a strength < 1 needs an init clip (init_video for audio->video, init_audio for video->audio)")
-    if init_video is not None and prompt_modality != "audio":
-        raise ValueError("init_video is the target of the audio->video direction (prompt_modality='audio')")
-    if init_audio is not None and prompt_modality != "video":
-        raise ValueError("init_audio is the target of the video->audio direction (prompt_modality='video')")
-    if init is not None and shard:
+    strength = P.check_init_args(prompt_modality, init_video, init_audio, strength, mask)
+    has_init = init_video is not None or init_audio is not None
+    if has_init and shard:
         raise ValueError("an init clip with shard=True is not implemented: the known windows would need a second broadcast to the "
                          "ranks; run the windows in one process")
-    if init_video is not None:
-        init = np.asarray(init_video)
-        if init.ndim != 4 or init.shape[-1] != 3 or init.dtype != np.uint8:
-            raise ValueError(f"init_video must be uint8 [T,H,W,3], got {init.dtype} {init.shape}")
-    elif init_audio is not None:
-        init = np.asarray(init_audio)
-        if init.ndim != 1 or not np.issubdtype(init.dtype, np.floating):
-            raise ValueError(f"init_audio must be a float waveform [N], got {init.dtype} {init.shape}")
-    rs = su.check_resample(resample) or su.resample_from_config(cfg["sampling"])
-    check_resample_args(rs, init is not None, mask is not None, noise_seed)
+    init = P.init_clip_array(init_video, init_audio)
+    pc = P.read_config(cfg, prompt_modality, guidance_interval=guidance_interval, resample=resample, has_init=has_init,
+                       has_mask=mask is not None, noise_seed=noise_seed)
+    target, fps, sr, eta, sched = pc.target, pc.fps, pc.sr, pc.eta, pc.sched
     st = cfg.get("streaming", {})
     win_s, hop_s = float(st.get("window_seconds", 3.0)), float(st.get("hop_seconds", 1.0))
     xfade_s = float(st.get("crossfade_seconds", 0.25))
-    fps, sr = int(cfg["video"]["fps"]), int(cfg["audio"]["sr"])
-    t_p, p, p_w = tube_from_config(cfg)
-    l_chunk, s_chunk = int(cfg["tokenizer"]["audio"]["chunk"]["length"]), int(cfg["tokenizer"]["audio"]["chunk"]["stride"])
-    Cv, t_down, s_down = (int(cfg["video"]["latent"][k]) for k in ("channels", "t_down", "s_down"))
-    Ca, Fa = int(cfg["audio"]["latent"]["channels"]), int(cfg["audio"]["latent"]["frames_per_clip"])
-    H, W = int(cfg["video"]["size"][0]), int(cfg["video"]["size"][1])
-    eta = float(cfg["sampling"].get("ddim_eta", 0.0))
-    solver = str(cfg["sampling"].get("solver", "ddim"))       # "ddim" | "dpmpp_2m" (DenoiseEngine ``solver``)
-    rescale_cfg = cfg["sampling"].get("guidance_rescale", {})  # per modality, like guidance_scale (DenoiseEngine ``guidance_rescale``)
 
     if consensus is None:
         consensus = st.get("latent_consensus")
@@ -299,7 +275,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
             raise ValueError("consensus needs sampling.ddim_eta == 0 with the per-window noise stream: the mean of the windows' "
                              "independent noise draws would shrink their variance (noise_keying='canvas' with noise_seed keys the "
                              "noise by canvas position instead)")
-        cons_hop, cons_L = latent_hop(cfg, "audio" if prompt_modality == "video" else "video")
+        cons_hop, cons_L = latent_hop(cfg, target)
         cons_w = None if isinstance(consensus, str) and consensus == "uniform" else consensus
         if isinstance(cons_w, str):
             raise ValueError(f"consensus must be None, 'uniform' or a table of {cons_L} weights, got {consensus!r}")
@@ -318,21 +294,16 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         if prompt_video is None:
             raise ValueError("prompt_video frames required for prompt_modality=video")
         chunks, win, hop = split_frames_into_windows(prompt_video, fps=fps, win_s=win_s, hop_s=hop_s)
-        zp_shape = (chunks.shape[0], Cv, chunks.shape[1] // t_down, chunks.shape[2] // s_down, chunks.shape[3] // s_down)
-        target, lat = "audio", (Ca, Fa)
-        n_prompt = (zp_shape[2] // t_p) * (zp_shape[3] // p) * (zp_shape[4] // p_w)
-        guide = float(cfg["sampling"]["guidance_scale"].get("audio", 3.0))
-    elif prompt_modality == "audio":
+        zp_shape = (chunks.shape[0], pc.Cv, chunks.shape[1] // pc.t_down, chunks.shape[2] // pc.s_down, chunks.shape[3] // pc.s_down)
+        lat = (pc.Ca, pc.Fa)
+    else:
         if prompt_audio is None:
             raise ValueError("prompt_audio required for prompt_modality=audio")
         chunks, win, hop = split_audio_into_windows(prompt_audio, sr=sr, win_s=win_s, hop_s=hop_s)
-        zp_shape = (chunks.shape[0], Ca, Fa)
+        zp_shape = (chunks.shape[0], pc.Ca, pc.Fa)
         T_in = int(round(cfg["data"]["clip_seconds"] * fps))
-        target, lat = "video", (Cv, max(1, T_in // t_down), H // s_down, W // s_down)
-        n_prompt = (Fa - l_chunk) // s_chunk + 1
-        guide = float(cfg["sampling"]["guidance_scale"].get("video", 3.0))
-    else:
-        raise ValueError("prompt_modality must be 'video' or 'audio'")
+        lat = (pc.Cv, max(1, T_in // pc.t_down), pc.H // pc.s_down, pc.W // pc.s_down)
+    n_prompt = P.prompt_tokens(pc, zp_shape)
     # the init clip's windows and the mask on the latent canvas, checked before anything is encoded
     init_chunks = mask_w = None
     if init is not None:
@@ -358,30 +329,18 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     z_p, root_error = None, None
     if root:
         try:
-            if prompt_modality == "video":
-                frames = torch.from_numpy(np.ascontiguousarray(chunks)).to(device).float() / 255.0      # [N,T,H,W,3]
-                z_p = vid_vae.encode(frames.permute(0, 4, 1, 2, 3).contiguous())
-            else:
-                z_p = aud_codec.encode(torch.from_numpy(np.ascontiguousarray(chunks, dtype=np.float32)).to(device)[:, None, :])
+            z_p = P.encode_video(vid_vae, chunks, device) if prompt_modality == "video" else P.encode_audio(aud_codec, chunks, device)
             if tuple(z_p.shape) != zp_shape:
                 if world > 1:       # the other ranks sized their buffers from the config
                     raise L.AvdError(f"encoded prompt windows have shape {tuple(z_p.shape)}, the config implies {zp_shape}")
                 # single process (e.g. a caller-supplied encoder): the encoder's own output decides, as in the reference
                 zp_shape = tuple(z_p.shape)
-                if prompt_modality == "video":
-                    n_prompt = (zp_shape[2] // t_p) * (zp_shape[3] // p) * (zp_shape[4] // p_w)
-                else:
-                    n_prompt = (zp_shape[-1] - l_chunk) // s_chunk + 1
+                n_prompt = P.prompt_tokens(pc, zp_shape)
         except Exception as exc:            # noqa: BLE001 — re-raised below; a sharded run first tells the other ranks
             if world == 1:
                 raise
             root_error = exc
 
-    c = cfg["diffusion"][target]
-    interval = su.check_guidance_interval(guidance_interval) or su.guidance_interval_from_config(cfg["sampling"], target)
-    abar = su.alphas_cumprod_from_betas(su.make_beta_schedule(int(c["steps"]), kind=c["schedule"], min_beta=c["min_beta"],
-                                                              max_beta=c["max_beta"]))[1]
-    sched = su.make_sampling_schedule(int(c["steps"]), int(c["sampler_steps"]))
     Nw = zp_shape[0]
     if return_latents and world > 1:
         raise ValueError("return_latents needs a single process: a sharded run gathers the decoded windows only")
@@ -413,42 +372,28 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     # the known windows of an init clip: encoded as one batch; under consensus made one canvas first (each window was encoded alone)
     known = None
     if init_chunks is not None:
-        if target == "video":
-            fr = torch.from_numpy(np.ascontiguousarray(init_chunks)).to(device).float() / 255.0           # [N,T,H,W,3]
-            known = vid_vae.encode(fr.permute(0, 4, 1, 2, 3).contiguous())
-        else:
-            known = aud_codec.encode(torch.from_numpy(np.ascontiguousarray(init_chunks, dtype=np.float32)).to(device)[:, None, :])
+        known = P.encode_video(vid_vae, init_chunks, device) if target == "video" else P.encode_audio(aud_codec, init_chunks, device)
         known = known.float().contiguous()
         if tuple(known.shape) != (Nw, *lat):
             raise ValueError(f"the init clip encodes to windows of shape {tuple(known.shape)}, the target's are {(Nw, *lat)}")
         if consensus:
             Fn.window_consensus(known, cons_hop, cons_w)
-        g_seed = guide_seed if guide_seed is not None else (noise_seed if noise_seed is not None else 0)
 
     def start(eng: DenoiseEngine, lo: int, hi: int):
         """(z_start, schedule) of the engine of windows [lo, hi): the initial latents and the whole schedule, or with an init clip the
         guided start (DenoiseEngine.set_known / start_latent; the guide stays set only under a mask)"""
-        z = z0[lo:hi].to(device, torch.float32).contiguous()
+        z = z0[lo:hi].to(device)
         if known is None:
-            return z, sched
-        m = torch.zeros(lat) if mask_w is None else mask_w[lo:hi]
-        if consensus:
-            eng.set_known(known[lo:hi], m, guide_seed=g_seed, keying="canvas", hop=cons_hop, sample_offset=lo)
-        else:
-            eng.set_known(known[lo:hi], m, guide_seed=g_seed, sample_offset=lo)
-        z, sched_k = eng.start_latent(z, sched, strength)
-        if mask_w is None:
-            eng.clear_known()          # SDEdit without a mask: the whole latent is free, the plain step runs
-        return z, (sched_k if rs is None else su.resample_schedule(sched_k, *rs))
+            return z.contiguous(), sched           # in its own dtype: run refuses an init_noise that is not float32
+        keying = dict(keying="canvas", hop=cons_hop) if consensus else {}
+        return P.guided_start(eng, pc, known[lo:hi], None if mask_w is None else mask_w[lo:hi], z.float().contiguous(), strength,
+                              P.default_guide_seed(guide_seed, noise_seed), sample_offset=lo, **keying)
 
     def engine(zp_part: torch.Tensor, lo0: int, lo: int, hi: int) -> DenoiseEngine:
         """the engine of windows [lo, hi), its prompt rows set from zp_part (which starts at window lo0)"""
-        eng = DenoiseEngine(adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, target=target,
-                            latent_shape=(hi - lo, *lat), prompt_tokens=n_prompt, alpha_bar=abar, guidance=guide, eta=eta,
-                            tube=(t_p, p, p_w), chunk=(l_chunk, s_chunk), noise_seed=noise_seed,
-                            sample_offset=lo if noise_seed is not None else 0, solver=solver,
-                            guidance_rescale=float(rescale_cfg.get(target, 0.0)), guidance_interval=interval,
-                            noise_keying=noise_keying, canvas_hop=cons_hop if canvas_keyed else None)
+        eng = P.build_engine(pc, adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, latent_shape=(hi - lo, *lat),
+                             n_prompt=n_prompt, noise_seed=noise_seed, sample_offset=lo if noise_seed is not None else 0,
+                             noise_keying=noise_keying, canvas_hop=cons_hop if canvas_keyed else None)
         eng.set_prompt(zp_part[lo - lo0:hi - lo0].to(device).float().contiguous())
         return eng
 
@@ -457,9 +402,6 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         outs = []
         for lo in range(lo0, hi0, max_windows_per_batch):
             hi = min(hi0, lo + max_windows_per_batch)
-            if known is None:
-                outs.append(engine(zp_part, lo0, lo, hi).run(z0[lo:hi].to(device).contiguous(), sched))
-                continue
             eng = engine(zp_part, lo0, lo, hi)
             outs.append(eng.run(*start(eng, lo, hi)))
         if not outs:
@@ -472,17 +414,12 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         if Nw <= max_windows_per_batch:
             eng = engine(zp_all, 0, 0, Nw)
             eng.set_window_consensus(cons_hop, cons_w)
-            if known is None:
-                return eng.run(z0.to(device).contiguous(), sched)
             return eng.run(*start(eng, 0, Nw))
         engs = [(lo, min(Nw, lo + max_windows_per_batch)) for lo in range(0, Nw, max_windows_per_batch)]
         engs = [(lo, hi, engine(zp_all, 0, lo, hi)) for lo, hi in engs]
-        if known is None:
-            sched_k, za = sched, z0.to(device, torch.float32).contiguous().clone()
-        else:
-            starts = [start(eng, lo, hi) for lo, hi, eng in engs]
-            sched_k = starts[0][1]                 # one strength: every engine runs the same tail of the schedule
-            za = torch.cat([z for z, _ in starts], 0)
+        starts = [start(eng, lo, hi) for lo, hi, eng in engs]
+        sched_k = starts[0][1]                     # one strength: every engine runs the same tail of the schedule
+        za = torch.cat([z for z, _ in starts], 0).float()
         for _, _, eng in engs:
             eng.check_schedule(sched_k)
             eng.begin(sched_k)
@@ -490,11 +427,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         zb = torch.empty_like(za)
         if sched_k.numel() < 2:
             return za                              # strength 0: no steps, the known windows
-        if su.has_jumps(sched_k):
-            segs = su.step_segments(sched_k, interval)
-        else:
-            segs = [(a, b, "cfg" if cfg_step else "cond") for a, b, cfg_step in su.guidance_segments(sched_k, interval)]
-        for first, stop, kind in segs:             # the kind of every pair, read on the host as run() does
+        for first, stop, kind in su.trajectory_segments(sched_k, pc.interval):      # the kind of every pair, read on the host as run() does
             for i in range(first, stop):
                 if kind == "renoise":              # canvas-keyed: the same linear map with the same normals on agreeing windows
                     for lo, hi, eng in engs:
@@ -510,11 +443,11 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         """finished latents of some windows -> what the stitcher takes: waveforms [n, L] float32 or frames [n, T, H, W, 3] uint8"""
         if target == "audio":
             if z.shape[0] == 0:
-                hop_a = int(getattr(aud_codec, "hop", 0)) or int(round(sr * float(cfg["data"]["clip_seconds"]))) // Fa
-                return torch.empty(0, Fa * hop_a, device=device)
+                hop_a = int(getattr(aud_codec, "hop", 0)) or int(round(sr * float(cfg["data"]["clip_seconds"]))) // pc.Fa
+                return torch.empty(0, pc.Fa * hop_a, device=device)
             return aud_codec.decode(z)[:, 0, :].contiguous()
         if z.shape[0] == 0:
-            return torch.empty(0, lat[1] * t_down, lat[2] * s_down, lat[3] * s_down, 3, dtype=torch.uint8, device=device)
+            return torch.empty(0, lat[1] * pc.t_down, lat[2] * pc.s_down, lat[3] * pc.s_down, 3, dtype=torch.uint8, device=device)
         x = vid_vae.decode(z).clamp(0, 1)                                         # [n,3,T,H,W]
         return (x.permute(0, 2, 3, 4, 1) * 255.0).to(torch.uint8).contiguous()    # as the reference's astype(np.uint8)
 
