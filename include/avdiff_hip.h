@@ -252,6 +252,50 @@ int avd_gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float
 int avd_canvas_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int N, int64_t outer, int L, int hop,
                          int64_t inner, avd_stream_t stream);
 
+/* ---- slot timesteps: one (t_now, t_prev) pair per position of the target's sliding axis instead of one per sample (a public contract).
+ * Every other entry reads t_now[b], t_prev[b].  The *_slots entries read int64 tables t_now[B*S], t_prev[B*S], row-major [B, S], where a
+ * slot is one token position along the sliding axis:
+ *   video target: slot s is latent frames s*p0 .. s*p0 + p0 - 1 of a tube (p0, p1, p2); S = T / p0; token n = (t'*Ht + h')*Wt + w' is
+ *     in slot t';
+ *   audio target: non-overlapping chunks only (stride == len, anything else is AVD_EUNSUPPORTED); slot s is chunk s; S = Na; latent
+ *     position f is in slot min(f / len, Na - 1), so the uncovered tail f >= Na*len follows the last slot with eps = 0, as in the
+ *     per-sample update.
+ * Per slot the semantics are the per-sample ones, with t_now[b, s], t_prev[b, s] in the place of t_now[b], t_prev[b]:
+ *   - a target token's timestep columns embed t_now[b, s] (same clamp, frequency table and cos-first order; both CFG halves);
+ *   - every latent element of the slot takes the DDIM update with its slot's coefficients; t_prev < 0 means alpha_bar = 1;
+ *   - the hold: where t_prev[b, s] == t_now[b, s], z_out is z bit for bit on the slot's elements.  A held token is still embedded
+ *     at t_now and still takes part in attention; only its update is skipped (its eps is not read).
+ * A table filled with one pair per sample gives the bits of the per-sample entry; a slot gives the bits the per-sample entry gives
+ * there when its whole sample runs at the slot's pair.  Attention and the GEMMs are the per-sample step's, launch for launch.
+ * Scope, everything else is refused before any launch (AVD_EINVAL): DDIM at eta == 0 (no noise, no key), the CFG step with the
+ * scalar guidance, the concat embedding (temb_add == 0), no solver history, latent guide, CFG control or canvas keying.  Both targets,
+ * every matmul / attention mode, both stream layouts (split_streams) and the null half's short layout are taken as by the plain step.
+ * `slots` must equal the geometry's S.  Samplers whose positions sit at different noise levels (FIFO-Diffusion, rolling diffusion,
+ * continuation from held clean context) are loops over avd_denoise_step_slots_f32. */
+/* The fused updates alone, as avd_cfg_unpatch_ddim_f32 / avd_cfg_untoken_ddim_audio_f32 at eta == 0 with t_now, t_prev: int64 [B*slots]. */
+int avd_cfg_unpatch_ddim_slots_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
+                                   const float* alpha_bar, int T_train, float guidance, int slots, float* z_out,
+                                   int B, int C, int T, int H, int W, int t, int h, int w, avd_stream_t stream);
+int avd_cfg_untoken_ddim_audio_slots_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
+                                         const float* alpha_bar, int T_train, float guidance, int slots, float* z_out,
+                                         int B, int Ca, int F, int len, int stride, avd_stream_t stream);
+
+/* ---- FIFO queue shift: the queue step of diagonal denoising (FIFO-Diffusion, Kim et al. 2024) in one out-of-place launch.
+ * The batch z_in [B, outer, L, inner] ((outer, L, inner) as in "canvas-keyed noise") with L = slots*slot_len is read as a queue of
+ * B*slots slots: queue slot q lives in sample q / slots at positions (q % slots)*slot_len .. + slot_len - 1 of the sliding axis.
+ *   z_out slot q = z_in slot q + 1 for q < B*slots - 1, crossing sample boundaries;
+ *   popped [outer, slot_len, inner] = z_in slot 0 (the finished head);
+ *   z_out's tail slot = fresh noise for slot c of the clip: the canvas-keyed normals of canvas positions c*slot_len + j at timestep t,
+ *     bit for bit avd_canvas_noise_f32(key {seed, sample_offset = c}, t_now = {t}, N = 1, outer, L = slot_len, hop = slot_len, inner).
+ * key->sample_offset is not read: c (by value) is the window index.  A queue initialised with avd_canvas_noise_f32(key {seed, 0}, t,
+ * N = B, outer, L, hop = L, inner) holds clip slots 0 .. B*slots - 1, and the shift number m (c = B*slots + m) appends the next one:
+ * slot c of the clip starts from the same normals however long the clip runs.
+ * Checked before the launch (AVD_EINVAL): 0 <= t < 2^32; c >= 0 and (c + 1)*slot_len <= 2^32; outer*inner < 2^34; z_in, z_out and
+ * popped must not overlap one another.  16-byte lanes when inner % 4 == 0 and the three bases are 16-byte aligned, one element per
+ * lane otherwise (every audio latent); same bits either way. */
+int avd_fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped,
+                       int B, int64_t outer, int slots, int slot_len, int64_t inner, avd_stream_t stream);
+
 /* ---- latent guide: inpainting / outpainting and SDEdit over a known clean latent (a public contract).
  * Per sample b of a call, with x_k = known[b] and m = the mask, both in the latent's natural layout ([C,T,H,W] video, [Ca,F] audio,
  * row-major; element e as in avd_noise_key), and a(tau) = alpha_bar[clamp(tau, 0, T_train-1)] for tau >= 0, 1 for tau < 0:
@@ -433,6 +477,11 @@ int64_t avd_embed_workspace_floats(const avd_embed_desc* desc);
 int avd_embed_cfg_pair_f32(const avd_embed_desc* desc, const float* z_target, const float* Wt, const float* bt,
                            const int64_t* t_now, const float* Xp, float* tok_ws, float* X2,
                            avd_stream_t stream);
+/* As avd_embed_cfg_pair_f32 on slot timesteps (see "slot timesteps"): t_now is int64 [B*slots] and target row n of sample b embeds
+ * t_now[b, slot(n)] in both halves; prompt rows and the adapter columns are unchanged.  Concat mode only. */
+int avd_embed_cfg_pair_slots_f32(const avd_embed_desc* desc, const float* z_target, const float* Wt, const float* bt,
+                                 const int64_t* t_now, int slots, const float* Xp, float* tok_ws, float* X2,
+                                 avd_stream_t stream);
 /* The single-branch front end of a cond-only step: X1[B, Nt+Np, d], bit-identical to the cond half of avd_embed_cfg_pair_f32's X2 on
  * the same inputs; B (Nt+Np) rows are handled, no null rows are written.  ss: NULL, or [B (Nt+Np)] that receives each finished row's
  * sum of squares in concat mode (the table the core's first folded RMSNorm reads; the bits the two-branch front end leaves for its
@@ -627,6 +676,12 @@ int64_t avd_step_workspace_bytes(const avd_step_desc* s);
 int avd_denoise_step_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_now,
                          const int64_t* t_prev, const float* noise, float* z_out,
                          void* workspace, int64_t workspace_bytes, avd_stream_t stream);
+/* The whole step on slot timesteps (see "slot timesteps"): t_now, t_prev int64 [B*slots], slots == the geometry's S.  Requires
+ * s->eta == 0 and the concat embedding; the workspace is avd_step_workspace_bytes'.  Fed a table that repeats one pair per sample it
+ * returns avd_denoise_step_f32's bits.  Graph-capturable: the tables are read at their addresses at every launch. */
+int avd_denoise_step_slots_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_now,
+                               const int64_t* t_prev, int slots, float* z_out,
+                               void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 /* As avd_denoise_step_f32, with the eta > 0 noise drawn inside the fused CFG + DDIM kernel from the seeded stream (avd_noise_key)
  * for samples key->sample_offset .. + B - 1 at t_now: no noise buffer, graph-capturable.  With s->eta == 0 it is the plain step. */
 int avd_denoise_step_seeded_f32(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp,

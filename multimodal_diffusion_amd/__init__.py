@@ -11,6 +11,7 @@ from .noise_heads import MultiModalNoiseHead           # noqa: F401
 from .sampler import (DenoiseEngine, LinearAdapter, add_sinusoidal_timestep, build_components,   # noqa: F401
                       latents_to_tokens_audio, latents_to_tokens_video, sample_one_direction, frame_mask, canvas_frame_mask,
                       tokens_to_latents_audio)
+from .stream_infer import fifo_denoise                                 # noqa: F401
 from .schedules import ModalitySchedule, build_schedules_from_config   # noqa: F401
 from .vae_video3d import VideoVAE, VideoVAEConfig                      # noqa: F401
 from .audio_codec import AudioCodec, AudioCodecConfig                  # noqa: F401

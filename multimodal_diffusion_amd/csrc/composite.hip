@@ -76,18 +76,20 @@ int audio_tokens_f32(const float* z, float* tok, int B, int Ca, int F, int len, 
 int assemble_f32(float* X2, const float* temb, const float* Xp, int B, int N, int d, int tdim, int Nt, int Np,
                  int target_first, hipStream_t st);
 int assemble_rows_f32(float* X2, const int64_t* t_now, const float* freqs, const float* Xp, float* ss, int B, int N, int d, int tdim,
-                      int Nt, int Np, int target_first, float max_period, hipStream_t st, const RowSegs* short_null = nullptr);
+                      int Nt, int Np, int target_first, float max_period, hipStream_t st, const RowSegs* short_null = nullptr, int slots = 0,
+                      int slot_tok = 0);
 int qkv3_replicate(void* img, int img_samples, int H, int n_keys, int first_sample, int n_samples, int src, hipStream_t st);
 int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key = nullptr,
                          const int64_t* t_last = nullptr, float* x0_hist = nullptr, const avd_latent_guide* guide = nullptr,
-                         const avd_cfg_control* ctl = nullptr, int canvas_hop = 0, int guide_hop = 0);
+                         const avd_cfg_control* ctl = nullptr, int canvas_hop = 0, int guide_hop = 0, int slots = 0);
 int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st,
                                const avd_noise_key* key = nullptr, const int64_t* t_last = nullptr, float* x0_hist = nullptr,
-                               const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr, int canvas_hop = 0, int guide_hop = 0);
+                               const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr, int canvas_hop = 0, int guide_hop = 0,
+                               int slots = 0);
 int assemble_cond_f32(float* X1, const float* temb, const float* Xp, int B, int N, int d, int tdim, int Nt, int Np, int target_first,
                       hipStream_t st);
 int assemble_rows_cond_f32(float* X1, const int64_t* t_now, const float* freqs, const float* Xp, float* ss, int B, int N, int d,
@@ -599,6 +601,20 @@ static int64_t embed_ws_floats(const avd_embed_desc* e) {
     return align_up((int64_t)e->B * e->Nt * embed_tok_dim(e) * 4) / 4 + align_up((int64_t)e->B * (e->tdim > 0 ? e->tdim : 1) * 4) / 4;
 }
 
+// The slots of the target's sliding axis ("slot timesteps" in the header): video, the S = T / p0 token frames of Ht * Wt tokens each;
+// audio, the S = Nt chunks, which must not overlap (stride == len)
+static int embed_slots(const avd_embed_desc* e, int& S, int& tok) {
+    if (e->target_kind == 0) {
+        S = e->T / e->p0;
+        tok = (e->H / e->p1) * (e->W / e->p2);
+    } else {
+        AVD_REQUIRE(e->p1 == e->p0, AVD_EUNSUPPORTED, "slot timesteps need non-overlapping audio chunks (stride %d == len %d)", e->p1, e->p0);
+        S = e->Nt;
+        tok = 1;
+    }
+    return AVD_OK;
+}
+
 // ss_out (optional, concat mode): per-row sums of squares of the finished X2, [2B*N] — spares MMDiT's first folded norm its pass
 // cond_only: the single-branch front end of a cond-only step — X2 is [B, N, d] (ss_out [B*N]), the cond half alone, bit-identical to
 // the cond half of the pair; the adapter GEMM is the same launch, only the assembly pass is the B*N-row form
@@ -606,8 +622,15 @@ static int64_t embed_ws_floats(const avd_embed_desc* e) {
 // of N rows and then B samples of Nt + 1 (ss_out alike)
 static int embed_cfg_pair(const avd_embed_desc* e, const float* z, const float* Wt, const float* bt,
                           const int64_t* t_now, const float* Xp, float* tok_ws, float* X2, hipStream_t st, float* ss_out = nullptr,
-                          bool cond_only = false, const RowSegs* short_null = nullptr) {
+                          bool cond_only = false, const RowSegs* short_null = nullptr, int slots = 0) {
     if (int rc = check_embed(e)) return rc;
+    int slot_tok = 0;      // slots != 0: t_now is the [B, S] table of the slot form
+    if (slots) {
+        int S = 0;
+        if (int rc = embed_slots(e, S, slot_tok)) return rc;
+        AVD_REQUIRE(slots == S, AVD_EINVAL, "embed: slots %d must equal the geometry's %d slots along the sliding axis", slots, S);
+        AVD_REQUIRE(!e->temb_add && !cond_only, AVD_EINVAL, "embed: slot timesteps take the concat embedding of the CFG pair (temb_add == 0)");
+    }
     AVD_REQUIRE(z && Wt && t_now && tok_ws && X2 && (e->Np == 0 || Xp), AVD_EINVAL, "embed: null pointer");
     AVD_REQUIRE(!short_null || (!cond_only && !e->temb_add && e->target_first && e->Np >= 1), AVD_EINVAL,
                 "embed: the short null half is the concat-mode CFG pair with the target rows first");
@@ -645,7 +668,7 @@ static int embed_cfg_pair(const avd_embed_desc* e, const float* z, const float* 
     if (cond_only)
         return assemble_rows_cond_f32(X2, t_now, e->temb_freqs, Xp, ss_out, B, N, d, e->tdim, e->Nt, e->Np, e->target_first, 10000.f, st);
     return assemble_rows_f32(X2, t_now, e->temb_freqs, Xp, ss_out, B, N, d, e->tdim, e->Nt, e->Np, e->target_first, 10000.f, st,
-                             short_null);
+                             short_null, slots, slot_tok);
 }
 
 // ---------------------------------------------------------------- one CFG denoising step
@@ -839,6 +862,13 @@ extern "C" int avd_embed_cfg_pair_f32(const avd_embed_desc* desc, const float* z
     return embed_cfg_pair(desc, z_target, Wt, bt, t_now, Xp, tok_ws, X2, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int avd_embed_cfg_pair_slots_f32(const avd_embed_desc* desc, const float* z_target, const float* Wt, const float* bt,
+                                            const int64_t* t_now, int slots, const float* Xp, float* tok_ws, float* X2,
+                                            avd_stream_t stream) {
+    AVD_REQUIRE(slots > 0, AVD_EINVAL, "embed_cfg_pair_slots: slots must be > 0 (got %d)", slots);
+    return embed_cfg_pair(desc, z_target, Wt, bt, t_now, Xp, tok_ws, X2, static_cast<hipStream_t>(stream), nullptr, false, nullptr, slots);
+}
+
 extern "C" int avd_embed_cond_f32(const avd_embed_desc* desc, const float* z_target, const float* Wt, const float* bt,
                                   const int64_t* t_now, const float* Xp, float* tok_ws, float* X1, float* ss, avd_stream_t stream) {
     return embed_cfg_pair(desc, z_target, Wt, bt, t_now, Xp, tok_ws, X1, static_cast<hipStream_t>(stream), ss, true);
@@ -861,7 +891,7 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
                         const int64_t* t_prev, const float* noise, float* z_out, void* workspace, int64_t workspace_bytes,
                         avd_stream_t stream, const int64_t* t_last = nullptr, float* x0_hist = nullptr,
                         const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr, int canvas_hop = 0,
-                        int guide_hop = 0) {
+                        int guide_hop = 0, int slots = 0) {
     StepWs ws;
     if (int rc = open_step(s, z, z_out, t_now, t_prev, workspace, workspace_bytes, ws)) return rc;
     auto& [p, X2, tok, core_ws, head_ws, ssx, eps2] = ws;
@@ -873,7 +903,7 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
     // rows when the core can (g_cfg_dedup); everything else — and every other mode — is the full [2B, N, d] layout
     const bool dedup = g_cfg_dedup && !s->split_streams && !e.temb_add && e.target_first && e.Np >= 2 && core_dedup_ok(s->core, 2 * e.B, p.N, e.Nt);
     const RowSegs seg{(int64_t)e.B * p.N, {p.N, e.Nt + 1}, {e.B, e.B}};      // the one definition of the layout: front end and core take it
-    if (int rc = embed_cfg_pair(&e, z, s->adapt_w, s->adapt_b, t_now, Xp, tok, X2, st, ssx, false, dedup ? &seg : nullptr)) return rc;
+    if (int rc = embed_cfg_pair(&e, z, s->adapt_w, s->adapt_b, t_now, Xp, tok, X2, st, ssx, false, dedup ? &seg : nullptr, slots)) return rc;
     const int row0 = e.target_first ? 0 : e.Np;
     // head over the target rows only (per-token independent, so skipping prompt rows is exact)
     const RowMap hm{e.d, e.Nt, (int64_t)p.N * e.d};
@@ -913,9 +943,9 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
     if (e.target_kind == 0)
         return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, s->alpha_bar, s->T_train, s->guidance, s->eta, noise, z_out,
                                     e.B, e.C, e.T, e.H, e.W, e.p0, e.p1, e.p2, st, key, t_last, x0_hist, guide, ctl, canvas_hop,
-                                    guide_hop);
+                                    guide_hop, slots);
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, s->alpha_bar, s->T_train, s->guidance, s->eta, noise, z_out,
-                                      e.B, e.C, e.T, e.p0, e.p1, st, key, t_last, x0_hist, guide, ctl, canvas_hop, guide_hop);
+                                      e.B, e.C, e.T, e.p0, e.p1, st, key, t_last, x0_hist, guide, ctl, canvas_hop, guide_hop, slots);
 }
 
 // The cond-only step of a guidance interval: the conditional branch alone, in the cond half of every workspace region of the CFG step's
@@ -990,6 +1020,22 @@ extern "C" int avd_denoise_step_f32(const avd_step_desc* s, const float* z, cons
                                     const int64_t* t_prev, const float* noise, float* z_out, void* workspace,
                                     int64_t workspace_bytes, avd_stream_t stream) {
     return denoise_step(s, nullptr, z, Xp, t_now, t_prev, noise, z_out, workspace, workspace_bytes, stream);
+}
+
+// The whole step on slot timesteps ("slot timesteps" in the header): t_now / t_prev are [B, S] tables.  Everything outside the scope is
+// refused here, before the model runs: the fused update's launcher repeats the geometry checks.
+extern "C" int avd_denoise_step_slots_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_now,
+                                          const int64_t* t_prev, int slots, float* z_out, void* workspace, int64_t workspace_bytes,
+                                          avd_stream_t stream) {
+    AVD_REQUIRE(s, AVD_EINVAL, "denoise_step_slots: null descriptor");
+    AVD_REQUIRE(s->eta == 0.f, AVD_EINVAL, "denoise_step_slots: slot timesteps take the DDIM update at eta == 0 (eta is %g)", (double)s->eta);
+    AVD_REQUIRE(!s->embed.temb_add, AVD_EINVAL, "denoise_step_slots: slot timesteps take the concat embedding (temb_add == 0)");
+    if (int rc = check_embed(&s->embed)) return rc;
+    int S = 0, tok = 0;
+    if (int rc = embed_slots(&s->embed, S, tok)) return rc;
+    AVD_REQUIRE(slots == S, AVD_EINVAL, "denoise_step_slots: slots %d must equal the geometry's %d slots along the sliding axis", slots, S);
+    return denoise_step(s, nullptr, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr,
+                        nullptr, 0, 0, slots);
 }
 
 extern "C" int avd_denoise_step_seeded_f32(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp,

@@ -314,6 +314,13 @@ struct DpmState {
 // then eps1 = [B, Nt, D], the conditional prediction alone; the null rows are not loaded, nothing is combined, `guidance` and `B` are
 // not read.  It excludes a CfgState (per-sample guidance and rescale act on the combine: with y = c the rescale is the identity).
 struct CondOnly {};
+// A SlotTimes item, alone in the pack, selects the slot form of the fused kernels (include/avdiff_hip.h, "slot timesteps"): t_now / t_prev
+// are [B, S] tables, one pair per slot of the target's sliding axis (video: the S = T / t token frames; audio: the S = Na chunks, stride
+// == len), every element takes ddim_coef of its slot's pair, and a slot whose pair is equal keeps z bit for bit (the hold).  It is the
+// DDIM update at eta == 0 without a guide or a control: the pack holds nothing else.
+struct SlotTimes {
+    int S;
+};
 template <class T, class... X> struct PackHas { static constexpr bool value = (std::is_same<T, X>::value || ...); };
 struct GuideState;
 struct CanvasGuideState;
@@ -326,7 +333,8 @@ struct CanvasKey;
 template <bool SEEDED, class... X> struct PackOk {
     template <class T> static constexpr int n = PackHas<T, X...>::value ? 1 : 0;
     static constexpr bool value = sizeof...(X) == (SEEDED ? 1 : 0) + n<DpmState> + n<GuideState> + n<CanvasGuideState> + n<CfgState> +
-                                                      n<CondOnly> &&
+                                                      n<CondOnly> + n<SlotTimes> &&
+                                  !(n<SlotTimes> && sizeof...(X) != 1) &&
                                   !(n<CfgState> && n<CondOnly>) && !(n<GuideState> && n<CanvasGuideState>) &&
                                   !(n<CanvasGuideState> && n<NoiseKey>) &&
                                   n<NoiseKey> + n<CanvasKey> == (SEEDED ? 1 : 0);
@@ -481,6 +489,91 @@ int canvas_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out,
     else
         hipLaunchKernelGGL(canvas_noise_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t_now, out, ck, outer, L, inner, n);
     AVD_CHECK_LAUNCH("canvas_noise");
+    return AVD_OK;
+}
+
+bool overlaps(const float* a, const float* b, int64_t n);
+
+// ------------------------------------------------------------------ FIFO queue shift (diagonal denoising)
+// The contract is written out in include/avdiff_hip.h ("FIFO queue shift").  The batch [B, outer, L, inner] with L = S * slot_len is a
+// queue of B * S slots, slot q in sample q / S at positions (q % S) * slot_len ..; one out-of-place launch writes z_out slot q = z_in
+// slot q + 1 (across sample boundaries), popped = z_in slot 0, and fills the tail slot with the canvas-keyed normals of canvas
+// positions c * slot_len + j at timestep `t`: canvas_normal4 with window index c and hop slot_len, the bits of canvas_noise_kernel.
+// V lanes as canvas_noise_kernel.  Lanes [0, n_out) write z_out, lanes [n_out, n_out + n_pop) write popped.
+template <int V>
+__global__ __launch_bounds__(256) void fifo_shift_kernel(const float* __restrict__ z_in, float* __restrict__ z_out,
+                                                         float* __restrict__ popped, CanvasKey ck, uint32_t t, int B, int64_t outer, int S,
+                                                         int slot_len, int64_t inner, int64_t n_out, int64_t n_pop) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n_out + n_pop) return;
+    const int64_t iv = inner / V;
+    const int L = S * slot_len;
+    if (idx >= n_out) {      // popped[o, j, i] = z_in[0, o, j, i]
+        const int64_t k = idx - n_out;
+        const int64_t i = (k % iv) * V;
+        const int64_t r = k / iv;
+        const int j = (int)(r % slot_len);
+        const int64_t o = r / slot_len;
+        const float* src = z_in + (o * L + j) * inner + i;
+        if constexpr (V == 4) *reinterpret_cast<f32x4*>(popped + k * 4) = *reinterpret_cast<const f32x4*>(src);
+        else popped[k] = *src;
+        return;
+    }
+    const int64_t i = (idx % iv) * V;
+    int64_t r = idx / iv;
+    const int l = (int)(r % L);
+    r /= L;
+    const int64_t o = r % outer;
+    const int b = (int)(r / outer);
+    const int j = l % slot_len;
+    const int64_t q1 = (int64_t)b * S + l / slot_len + 1;      // the queue slot this one receives
+    if (q1 < (int64_t)B * S) {
+        const int64_t bs = q1 / S, ls = (q1 % S) * slot_len + j;
+        const float* src = z_in + ((bs * outer + o) * L + ls) * inner + i;
+        if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = *reinterpret_cast<const f32x4*>(src);
+        else z_out[idx] = *src;
+    } else {                 // the tail slot: fresh noise of clip slot c
+        const f32x4 v = canvas_normal4(ck, 0, o, j, i, inner, t);
+        if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = v;
+        else z_out[idx] = v[(int)((o * inner + i) & 3)];
+    }
+}
+
+int fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped, int B, int64_t outer,
+                   int S, int slot_len, int64_t inner, hipStream_t st) {
+    AVD_REQUIRE(key, AVD_EINVAL, "fifo_shift: null noise key");
+    AVD_REQUIRE(z_in && z_out && popped, AVD_EINVAL, "fifo_shift: null pointer");
+    AVD_REQUIRE(B > 0 && outer > 0 && S > 0 && slot_len > 0 && inner > 0, AVD_EINVAL,
+                "fifo_shift: bad dims (B %d, outer %lld, S %d, slot_len %d, inner %lld)", B, (long long)outer, S, slot_len, (long long)inner);
+    AVD_REQUIRE((int64_t)S * slot_len <= 0x7fffffff && (int64_t)B * S <= 0x7fffffff, AVD_EINVAL,
+                "fifo_shift: S %d * slot_len %d and B %d * S must fit an int", S, slot_len, B);
+    AVD_REQUIRE(t >= 0 && t < ((int64_t)1 << 32), AVD_EINVAL, "fifo_shift: the noise timestep %lld must lie in [0, 2^32)", (long long)t);
+    const int64_t lim = (int64_t)1 << 32;
+    AVD_REQUIRE(c >= 0 && c < lim && c + 1 <= lim / slot_len, AVD_EINVAL, "fifo_shift: (c %lld + 1) * slot_len %d must lie in [1, 2^32]",
+                (long long)c, slot_len);
+    AVD_REQUIRE(outer <= (((int64_t)1 << 34) - 1) / inner, AVD_EINVAL, "fifo_shift: outer %lld * inner %lld must be < 2^34", (long long)outer,
+                (long long)inner);
+    AVD_REQUIRE((double)B * (double)outer * (double)S * (double)slot_len * (double)inner < 9.0e18, AVD_EUNSUPPORTED, "fifo_shift: too many values");
+    const int64_t total = (int64_t)B * outer * S * slot_len * inner, pop = outer * slot_len * inner;
+    AVD_REQUIRE(!overlaps(z_in, z_out, total), AVD_EINVAL, "fifo_shift: z_out must not overlap z_in (one out-of-place launch)");
+    AVD_REQUIRE(!(popped < z_in + total && z_in < popped + pop) && !(popped < z_out + total && z_out < popped + pop), AVD_EINVAL,
+                "fifo_shift: popped must not overlap z_in or z_out");
+    const bool vec = inner % 4 == 0 && aligned16(z_in) && aligned16(z_out) && aligned16(popped);
+    const int v = vec ? 4 : 1;
+    const int64_t n_out = total / v, n_pop = pop / v;
+    AVD_REQUIRE((n_out + n_pop + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "fifo_shift: %lld lanes are too many for one launch",
+                (long long)(n_out + n_pop));
+    const CanvasKey ck{(uint32_t)(key->seed & 0xffffffffu), (uint32_t)(key->seed >> 32), (uint32_t)c, (uint32_t)slot_len};
+    static const int tags[2] = {prof_tag_id("fifo_shift_kernel<1>"), prof_tag_id("fifo_shift_kernel<4>")};
+    ProfScope prof(tags[vec ? 1 : 0], 4.0 * (2.0 * (double)total + (double)pop), st);      // read + write of the queue, the popped slot's write
+    const dim3 grid((unsigned)((n_out + n_pop + 255) / 256));
+    if (vec)
+        hipLaunchKernelGGL(fifo_shift_kernel<4>, grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B, outer, S, slot_len, inner,
+                           n_out, n_pop);
+    else
+        hipLaunchKernelGGL(fifo_shift_kernel<1>, grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B, outer, S, slot_len, inner,
+                           n_out, n_pop);
+    AVD_CHECK_LAUNCH("fifo_shift");
     return AVD_OK;
 }
 
@@ -1167,12 +1260,22 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
     constexpr bool CANVAS = PackHas<CanvasKey, Key...>::value, CGUIDED = PackHas<CanvasGuideState, Key...>::value;
     static_assert(PackOk<SEEDED, Key...>::value, "not a pack of the fused update kernels (see PackOk)");
+    constexpr bool SLOT = PackHas<SlotTimes, Key...>::value;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total4) return;
     const int64_t per4 = g.per >> 2;
     const int b = (int)(i / per4);
     const int64_t e4 = i % per4;
     const int64_t lat = (int64_t)b * g.per + e4 * 4;
+    [[maybe_unused]] int tb = b;      // the entry of t_now / t_prev this lane steps with
+    if constexpr (SLOT) {             // per lane: the slot of latent frame tt is tt / t; a held slot keeps z
+        const int tt = (int)((e4 / ((int64_t)(g.W >> 2) * g.H)) % g.T);
+        tb = b * pack_get<SlotTimes>(nk...).S + tt / g.t;
+        if (t_now[tb] == t_prev[tb]) {
+            *reinterpret_cast<f32x4*>(z_out + lat) = *reinterpret_cast<const f32x4*>(z + lat);
+            return;
+        }
+    }
     const int64_t toff = tube_tok_off(g, e4);
     const f32x4 ec = *reinterpret_cast<const f32x4*>(eps2 + (int64_t)b * g.per + toff);
     [[maybe_unused]] f32x4 en = {0.f, 0.f, 0.f, 0.f};
@@ -1190,7 +1293,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
         else k = NoiseKey(nk...);
         zn = philox_normal4(k, (uint32_t)e4, k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
     } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
-    const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, eta, b);
+    const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, eta, SLOT ? tb : b);
     f32x4 o;
     if constexpr (DPM) {
         const DpmState ds = pack_get<DpmState>(nk...);
@@ -1234,13 +1337,20 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
     constexpr bool CANVAS = PackHas<CanvasKey, Key...>::value, CGUIDED = PackHas<CanvasGuideState, Key...>::value;
     static_assert(PackOk<SEEDED, Key...>::value, "not a pack of the fused update kernels (see PackOk)");
+    constexpr bool SLOT = PackHas<SlotTimes, Key...>::value;
     extern __shared__ __attribute__((aligned(16))) float ebuf[];       // [GT][D + 4]: the pad keeps the transposed 16-byte reads off one bank group
     const int LD = g.D + 4;
     const int b = blockIdx.x / groups_per_sample, grp = blockIdx.x % groups_per_sample;
     const int n0 = grp * GT;                                            // first token of the group (GT divides W / w: one (t', h') row)
+    [[maybe_unused]] int tb = b;      // the entry of t_now / t_prev this block steps with
+    [[maybe_unused]] bool hold = false;
+    if constexpr (SLOT) {             // the block's tokens share t': one slot, one pair, and the hold is block-uniform
+        tb = b * pack_get<SlotTimes>(nk...).S + n0 / (g.Wt * g.Ht);
+        hold = t_now[tb] == t_prev[tb];
+    }
     const float* tc = eps2 + ((int64_t)b * (g.per / g.D) + n0) * g.D;
     [[maybe_unused]] const float* tn = eps2 + (((int64_t)B + b) * (g.per / g.D) + n0) * g.D;
-    const int nf4 = GT * g.D / 4;
+    const int nf4 = SLOT && hold ? 0 : GT * g.D / 4;      // a held slot reads no eps
     [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
     if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
     for (int i = threadIdx.x; i < nf4; i += 256) {
@@ -1254,7 +1364,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         *reinterpret_cast<f32x4*>(ebuf + tok * LD + k0) = e;
     }
     __syncthreads();
-    const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, eta, b);
+    const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, eta, SLOT ? tb : b);
     [[maybe_unused]] Dpm d{0.f, 0.f, 0.f, 0.f};
     if constexpr (DPM) d = dpm_coef(pack_get<DpmState>(nk...).t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, b);
     [[maybe_unused]] GuideCoef gc{0.f, 0.f, false};
@@ -1270,6 +1380,12 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         const f32x4 e = *reinterpret_cast<const f32x4*>(ebuf + tok * LD + sg * g.w + wo);
         const int64_t lat = (int64_t)b * g.per + (((int64_t)cc * g.T + (tq * g.t + tt)) * g.H + (hq * g.h + hh)) * g.W + (wq + tok) * g.w + wo;
         const f32x4 x = *reinterpret_cast<const f32x4*>(z + lat);
+        if constexpr (SLOT) {
+            if (hold) {      // z, bit for bit
+                *reinterpret_cast<f32x4*>(z_out + lat) = x;
+                continue;
+            }
+        }
         f32x4 o;
         [[maybe_unused]] f32x4 zn = {0.f, 0.f, 0.f, 0.f};      // the unkeyed DPM update (eta == 0) draws nothing
         if constexpr (CANVAS) {      // element (c, t, h, w) of window b: canvas position from t, element (c, h W + w) of its slice
@@ -1320,6 +1436,8 @@ struct UpdateArgs {
 // what the kernels' trailing pack is made of: filled by check_fused_update, read by with_update_pack
 struct UpdateKeys {
     bool dpm, seeded, canvas, guide, cguide, ctl;
+    bool slots;        // the slot form: sl is the whole pack (set by check_slot_update after check_fused_update)
+    SlotTimes sl;
     DpmState ds;
     NoiseKey nk;
     CanvasKey ck;      // canvas: the seeded draw is keyed by canvas position (ck replaces nk in the pack)
@@ -1385,12 +1503,31 @@ static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per
     return AVD_OK;
 }
 
+// The slot form's checks, before any HIP call: slots == 0 is the per-sample update; otherwise `slots` must be the geometry's S and the
+// update is DDIM at eta == 0 with nothing else in the pack (the scope of "slot timesteps" in include/avdiff_hip.h)
+static int check_slot_update(const char* what, const UpdateArgs& a, int slots, int S, const avd_noise_key* key, const int64_t* t_last,
+                             const avd_latent_guide* guide, const avd_cfg_control* ctl, int canvas_hop, int guide_hop, UpdateKeys& k) {
+    if (!slots) return AVD_OK;
+    AVD_REQUIRE(slots == S, AVD_EINVAL, "%s: slots %d must equal the geometry's %d slots along the sliding axis", what, slots, S);
+    AVD_REQUIRE(a.eta == 0.f && !a.noise && !key, AVD_EINVAL, "%s: slot timesteps take the DDIM update at eta == 0 (no noise, no key)", what);
+    AVD_REQUIRE(!t_last && !guide && !ctl && !canvas_hop && !guide_hop, AVD_EINVAL,
+                "%s: slot timesteps take no solver history, latent guide, CFG control or canvas keying", what);
+    AVD_REQUIRE((int64_t)a.B * S <= 0x7fffffff, AVD_EINVAL, "%s: B %d * slots %d does not fit an int", what, a.B, S);
+    k.slots = true;
+    k.sl = SlotTimes{S};
+    return AVD_OK;
+}
+
 // Calls launch(pack...) with the kernels' whole trailing pack: the solver's state (DpmState, the NoiseKey of a seeded eta > 0 step or
 // the CanvasKey of a canvas-keyed one, DpmState then that key for the SDE form, or nothing), then the guide if there is one, then the
 // CFG control if there is one or, for the single-branch form, the CondOnly tag.  A canvas-keyed guide rides in the guide's place, after
 // the solver states that can reach it: none, DpmState, CanvasKey, DpmState then CanvasKey (never a NoiseKey: check_fused_update).
 template <class F>
 static void with_update_pack(const UpdateKeys& k, bool cond_only, F launch) {
+    if (k.slots) {
+        launch(k.sl);
+        return;
+    }
     if (k.cguide) {
         auto ctail = [&](auto... state) {
             if (cond_only) launch(state..., k.cgs, CondOnly{});
@@ -1444,7 +1581,7 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key,
                          const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
-                         int canvas_hop, int guide_hop) {
+                         int canvas_hop, int guide_hop, int slots) {
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "cfg_unpatch_ddim: bad dims");
     Tube g;
     if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
@@ -1455,6 +1592,7 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
     const CanvasDims gcv{C, T, guide_hop, (int64_t)H * W};
     if (int rc = check_fused_update("cfg_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
                                     guide_hop ? &gcv : nullptr)) return rc;
+    if (int rc = check_slot_update("cfg_unpatch_ddim", a, slots, T / t, key, t_last, guide, ctl, canvas_hop, guide_hop, k)) return rc;
     if (ctl && ctl->rescale) {
         AVD_REQUIRE(aligned16(eps2) && aligned16(eps2 + (int64_t)B * g.per), AVD_EUNSUPPORTED,
                     "cfg_unpatch_ddim: the statistics pass reads 16-byte aligned token rows");
@@ -1508,6 +1646,16 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
     const int b = (int)(i / ((int64_t)F * Ca));
     const int L = (Na - 1) * stride + len;
     const int D = Ca * len;
+    constexpr bool SLOT = PackHas<SlotTimes, Key...>::value;
+    [[maybe_unused]] int tb = b;      // the entry of t_now / t_prev this lane steps with
+    if constexpr (SLOT) {             // per lane (stride == len): chunk f / len, the uncovered tail follows the last chunk; a held slot keeps z
+        const int sl = f / len;
+        tb = b * Na + (sl > Na - 1 ? Na - 1 : sl);
+        if (t_now[tb] == t_prev[tb]) {
+            z_out[i] = z[i];
+            return;
+        }
+    }
     [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
     if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
     float e = 0.f;
@@ -1532,7 +1680,7 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
         e = acc / fmaxf(cnt, 1e-8f);
     }
     if constexpr (CTL) e = cfg_rescale(e, cc.phi, cc.s);      // r(y) on the whole latent, the zero pad included
-    const Ddim cf = ddim_coef(t_now, t_prev, abar, T_train, eta, b);
+    const Ddim cf = ddim_coef(t_now, t_prev, abar, T_train, eta, SLOT ? tb : b);
     // the guide's epilogue on the value about to be stored (the identity for the unguided instantiations)
     auto fin = [&](float v) {
         if constexpr (GUIDED)
@@ -1580,9 +1728,11 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st, const avd_noise_key* key,
                                const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
-                               int canvas_hop, int guide_hop) {
+                               int canvas_hop, int guide_hop, int slots) {
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "cfg_untoken_ddim_audio: bad chunking");
+    AVD_REQUIRE(!slots || stride == len, AVD_EUNSUPPORTED,
+                "cfg_untoken_ddim_audio: slot timesteps need non-overlapping chunks (stride %d == len %d)", stride, len);
     const UpdateArgs a{eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, B};
     const int64_t per = (int64_t)Ca * F;
     UpdateKeys k;
@@ -1591,6 +1741,7 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
     if (int rc = check_fused_update("cfg_untoken_ddim_audio", a, per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
                                     guide_hop ? &gcv : nullptr)) return rc;
     const AudioGeom ag{Ca, F, len, stride, audio_na(F, len, stride)};
+    if (int rc = check_slot_update("cfg_untoken_ddim_audio", a, slots, ag.Na, key, t_last, guide, ctl, canvas_hop, guide_hop, k)) return rc;
     if (ctl && ctl->rescale) {
         const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
         if (int rc = run_cfg_stats<CFG_SRC_AUDIO>(ctl, eps2, eps2 + B * half, half, guidance, B, per, ag, st)) return rc;
@@ -1665,10 +1816,16 @@ int assemble_f32(float* X2, const float* temb, const float* Xp, int B, int N, in
 // adapter GEMM did not write — the sinusoidal timestep columns are computed in place (no [B, tdim] buffer, no separate
 // kernel), the null half's target rows are copied from the cond half, prompt rows come from Xp / zeros — and, while the row
 // is in registers, its sum of squares goes to ss[row] (the table the first folded RMSNorm reads: no rowss pass).
+// A SlotMap ending the arguments (an empty pack otherwise: the per-sample instantiation keeps its argument layout and code) selects the
+// slot form ("slot timesteps"): t_now is [B, S] and target row n embeds t_now[b, (n - first target row) / tok], in both halves.
+struct SlotMap {
+    int S, tok;      // slots per sample, target tokens per slot (video: Ht * Wt, audio: 1)
+};
+template <class... Slot>
 __global__ __launch_bounds__(256) void assemble_rows_kernel(float* __restrict__ X2, const int64_t* __restrict__ t_now,
                                                             const float* __restrict__ freqs, const float* __restrict__ Xp,
                                                             float* __restrict__ ss, int B, int N, int d, int tdim, int Nt, int Np,
-                                                            int target_first, float neg_log_mp, RowSegs seg) {
+                                                            int target_first, float neg_log_mp, RowSegs seg, Slot... sl) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= seg.rows()) return;
@@ -1678,7 +1835,13 @@ __global__ __launch_bounds__(256) void assemble_rows_kernel(float* __restrict__ 
     const int t0 = target_first ? 0 : Np;
     const bool is_t = n >= t0 && n < t0 + Nt;
     const int da = d - tdim, th = tdim >> 1;
-    const float tf = is_t ? (float)t_now[b] : 0.f;
+    float tf = 0.f;
+    if constexpr (sizeof...(Slot) != 0) {
+        const SlotMap sm = SlotMap(sl...);
+        if (is_t) tf = (float)t_now[b * sm.S + (n - t0) / sm.tok];
+    } else {
+        tf = is_t ? (float)t_now[b] : 0.f;
+    }
     float acc = 0.f;
     for (int col = lane * 4; col < d; col += 256) {
         f32x4 v;
@@ -1715,7 +1878,10 @@ __global__ __launch_bounds__(256) void assemble_rows_kernel(float* __restrict__ 
 // short_null (null = the plain [2B, N, d] layout): the caller's two-segment layout — target rows first, B cond samples of N rows, then B
 // null samples that keep ONE of their Np prompt rows (they are all the zero row): Nt + 1 rows each (composite.hip)
 int assemble_rows_f32(float* X2, const int64_t* t_now, const float* freqs, const float* Xp, float* ss, int B, int N, int d, int tdim,
-                      int Nt, int Np, int target_first, float max_period, hipStream_t st, const RowSegs* short_null) {
+                      int Nt, int Np, int target_first, float max_period, hipStream_t st, const RowSegs* short_null, int slots,
+                      int slot_tok) {
+    AVD_REQUIRE(!slots || (slot_tok > 0 && (int64_t)slots * slot_tok == Nt), AVD_EINVAL,
+                "assemble_rows: %d slots of %d tokens are not the %d target rows", slots, slot_tok, Nt);
     AVD_REQUIRE(!short_null || (target_first && Np >= 1 && short_null->samples[0] == B && short_null->samples[1] == B && short_null->tok[0] == N &&
                                 short_null->tok[1] == Nt + 1 && short_null->m0 == (int64_t)B * N), AVD_EINVAL,
                 "assemble_rows: a short null half is B samples of N rows, then B of the target rows and one prompt row behind them");
@@ -1723,8 +1889,12 @@ int assemble_rows_f32(float* X2, const int64_t* t_now, const float* freqs, const
     const int64_t rows = seg.rows();
     static const int tag = prof_tag_id("assemble_rows_kernel");
     ProfScope prof(tag, 4.0 * ((double)rows * d + (double)B * Nt * (d - tdim) + (double)B * Np * d), st);
-    hipLaunchKernelGGL(assemble_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, X2, t_now, freqs, Xp, ss, B, N, d, tdim,
-                       Nt, Np, target_first, -(float)log((double)max_period), seg);
+    if (slots)
+        hipLaunchKernelGGL(assemble_rows_kernel<SlotMap>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, X2, t_now, freqs, Xp, ss, B, N,
+                           d, tdim, Nt, Np, target_first, -(float)log((double)max_period), seg, SlotMap{slots, slot_tok});
+    else
+        hipLaunchKernelGGL(assemble_rows_kernel<>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, X2, t_now, freqs, Xp, ss, B, N, d, tdim,
+                           Nt, Np, target_first, -(float)log((double)max_period), seg);
     AVD_CHECK_LAUNCH("assemble_rows");
     return AVD_OK;
 }
@@ -1943,14 +2113,34 @@ extern "C" int avd_cfg_unpatch_ddim_f32(const float* eps2, const float* z, const
     AVD_REQUIRE(aligned16(eps2) && aligned16(z) && aligned16(z_out) && (!noise || aligned16(noise)), AVD_EUNSUPPORTED,
                 "cfg_unpatch_ddim: pointers must be 16-byte aligned");
     return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, C, T, H, W, t,
-                                h, w, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0);
+                                h, w, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0);
+}
+extern "C" int avd_cfg_unpatch_ddim_slots_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
+                                              const float* alpha_bar, int T_train, float guidance, int slots, float* z_out, int B, int C,
+                                              int T, int H, int W, int t, int h, int w, avd_stream_t stream) {
+    AVD_REQUIRE(aligned16(eps2) && aligned16(z) && aligned16(z_out), AVD_EUNSUPPORTED,
+                "cfg_unpatch_ddim_slots: pointers must be 16-byte aligned");
+    AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_unpatch_ddim_slots: slots must be > 0 (got %d)", slots);
+    return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, 0.f, nullptr, z_out, B, C, T, H, W, t, h, w,
+                                static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, slots);
+}
+extern "C" int avd_cfg_untoken_ddim_audio_slots_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
+                                                    const float* alpha_bar, int T_train, float guidance, int slots, float* z_out, int B,
+                                                    int Ca, int F, int len, int stride, avd_stream_t stream) {
+    AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_untoken_ddim_audio_slots: slots must be > 0 (got %d)", slots);
+    return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, 0.f, nullptr, z_out, B, Ca, F, len, stride,
+                                      static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, slots);
+}
+extern "C" int avd_fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped, int B,
+                                  int64_t outer, int slots, int slot_len, int64_t inner, avd_stream_t stream) {
+    return fifo_shift_f32(key, t, c, z_in, z_out, popped, B, outer, slots, slot_len, inner, static_cast<hipStream_t>(stream));
 }
 extern "C" int avd_cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now,
                                               const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance,
                                               float eta, const float* noise, float* z_out, int B, int Ca, int F, int len,
                                               int stride, avd_stream_t stream) {
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, Ca, F,
-                                      len, stride, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0);
+                                      len, stride, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0);
 }
 extern "C" int avd_eps_unpatch_ddim_f32(const float* eps, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                         const float* alpha_bar, int T_train, float eta, const float* noise, float* z_out, int B, int C,

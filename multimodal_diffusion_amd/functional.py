@@ -522,6 +522,70 @@ def canvas_noise(seed: int, t_now: Tensor, shape, hop: int, window_offset: int =
     return out
 
 
+def slot_tables(t_now: Tensor, t_prev: Tensor, B: int, S: int, device: torch.device):
+    """The [B, S] timestep tables of the slot entries (include/avdiff_hip.h, "slot timesteps") as contiguous int64 device tensors,
+    after the shape check every caller shares."""
+    out = []
+    for name, t in (("t_now", t_now), ("t_prev", t_prev)):
+        t = torch.as_tensor(t)
+        if t.is_floating_point() or t.dtype == torch.bool:
+            raise TypeError(f"{name} must hold integer timesteps, got {t.dtype}")
+        if tuple(t.shape) != (B, S):
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected [B, S] = {(B, S)}: one timestep per sample and slot")
+        out.append(L.dev_i64(t, device))
+    return out
+
+
+def ddim_step_slots(x_t: Tensor, t_now: Tensor, t_prev: Tensor, eps_hat: Tensor, alpha_bar: Tensor, slot_len: int) -> Tensor:
+    """The elementwise mirror of the slot form of the fused update (include/avdiff_hip.h, "slot timesteps") at eta == 0: ``x_t`` and
+    ``eps_hat`` are latents ([B,C,T,H,W] video, [B,Ca,F] audio), ``t_now`` / ``t_prev`` int [B, S]; sliding position l is in slot
+    min(l // slot_len, S - 1).  Every slot takes ``ddim_step`` (avd_ddim_step_f32) with its pair, one launch per distinct pair of the
+    tables; a slot with t_prev == t_now keeps ``x_t`` bit for bit (the hold)."""
+    x_t = L.dev_f32(x_t, "x_t")
+    eps_hat = L.dev_f32(eps_hat, "eps_hat")
+    if eps_hat.shape != x_t.shape:
+        raise RuntimeError("eps_hat must have the shape of x_t")
+    _, L_, _ = window_dims(x_t.shape)
+    B = x_t.shape[0]
+    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or slot_len > L_:
+        raise ValueError(f"slot_len must be an int in [1, {L_}], got {slot_len!r}")
+    S = L_ // slot_len
+    tn, tp = slot_tables(t_now, t_prev, B, S, x_t.device)
+    slot = torch.clamp(torch.arange(L_, device=x_t.device) // slot_len, max=S - 1)
+    view = (B, 1, L_) + (1,) * (x_t.dim() - 3)
+    tn_l, tp_l = tn[:, slot].view(view), tp[:, slot].view(view)      # the pair of every sliding position
+    out = x_t.clone()
+    for a, p in sorted({(int(a), int(p)) for a, p in zip(tn.reshape(-1).tolist(), tp.reshape(-1).tolist())}):
+        if a == p:
+            continue
+        full = ddim_step(x_t, torch.full((B,), a), torch.full((B,), p), eps_hat, alpha_bar)
+        out = torch.where((tn_l == a) & (tp_l == p), full, out)
+    return out
+
+
+def fifo_shift(z: Tensor, c: int, seed: int, t: int, slot_len: int):
+    """The queue step of FIFO diagonal denoising (avd_fifo_shift_f32; contract in include/avdiff_hip.h, "FIFO queue shift"): ``z``
+    ([B,C,T,H,W] video, [B,Ca,F] audio, sliding length L = S * slot_len) is a queue of B * S slots.  Returns (z_out, popped): z_out
+    slot q = z slot q + 1 across sample boundaries, popped = z slot 0 ([C, slot_len, H, W] or [Ca, slot_len]), and the tail slot of
+    z_out holds the seeded normals of clip slot ``c`` at timestep ``t`` — ``canvas_noise(seed, [t], one slot's shape, slot_len,
+    window_offset=c)`` bit for bit."""
+    z = L.dev_f32(z, "z")
+    outer, L_, inner = window_dims(z.shape)
+    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or L_ % slot_len:
+        raise ValueError(f"slot_len must be an int >= 1 that divides the sliding length {L_}, got {slot_len!r}")
+    for name, v in (("c", c), ("t", t)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"{name} must be an int >= 0, got {v!r}")
+    if (c + 1) * slot_len > 2 ** 32:
+        raise ValueError(f"(c {c} + 1) * slot_len {slot_len} exceeds the stream's 2**32 canvas positions")
+    key = noise_key(seed, 0)
+    out = torch.empty_like(z)
+    popped = torch.empty((z.shape[1], slot_len) + tuple(z.shape[3:]), device=z.device, dtype=torch.float32)
+    L.check(L.lib().avd_fifo_shift_f32(C.byref(key), t, c, z.data_ptr(), out.data_ptr(), popped.data_ptr(), z.shape[0], outer,
+                                       L_ // slot_len, slot_len, inner, _st(z)))
+    return out, popped
+
+
 # ---- "bf16x3": fp32-accurate Linear on the bf16 matrix pipe (csrc/gemm_bf16x3.hip) ----
 def split3(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """fp32 [rows, K] -> its split3 image (uint8; three bf16 planes, tiled).  K must be a multiple of 16.

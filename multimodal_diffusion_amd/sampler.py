@@ -201,6 +201,11 @@ class DenoiseEngine:
     common noise level more than once.  It needs ``noise_seed`` (also at eta == 0); the keying is the engine's (by canvas position
     with ``canvas_hop`` or a canvas-keyed guide, which a window consensus requires).  Limit: at eta > 0 the step noise stays keyed by
     (sample, t_now, element), so a revisited timestep repeats its step normals; only the renoise normals are fresh per visit.
+
+    ``step_slots(z, t_now, t_prev)`` (extension: slot timesteps, include/avdiff_hip.h): one (t_now, t_prev) pair per token position
+    of the sliding axis ([B, S] tables, S = ``slots`` of ``slot_len`` latent positions) instead of one per sample; a slot with t_prev ==
+    t_now is held.  The primitive of FIFO diagonal denoising (``stream_infer.fifo_denoise``, ``schedule_utils.fifo_plan``).  Solver
+    "ddim" at eta == 0 with the scalar guidance only; ``step``, ``run`` and ``capture_pair`` do not change.
     """
 
     SOLVERS = ("ddim", "dpmpp_2m")
@@ -720,6 +725,61 @@ class DenoiseEngine:
         else:
             rc = lib.avd_denoise_step_f32(desc, *zx, *ts, L.ptr(noise), *tail)
         L.check(rc)
+        return out
+
+    # ---- slot timesteps: one (t_now, t_prev) pair per position of the sliding axis ----
+    @property
+    def slot_len(self) -> int:
+        """latent positions of one slot along the sliding axis: the tube's t (video target) or the chunk length (audio target)"""
+        return self.tube[0] if self.target == "video" else self.chunk[0]
+
+    @property
+    def slots(self) -> int:
+        """S, the slots of one sample (include/avdiff_hip.h, "slot timesteps"): T // tube t (video) or the Na chunks (audio)"""
+        return self.latent_shape[2] // self.tube[0] if self.target == "video" else self.embed.Nt
+
+    def step_slots(self, z: torch.Tensor, t_now: torch.Tensor, t_prev: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One CFG + DDIM step on slot timesteps (extension; include/avdiff_hip.h, "slot timesteps"; avd_denoise_step_slots_f32):
+        ``t_now`` / ``t_prev`` are int [B, S] tables, S = ``slots``, one pair per slot of ``slot_len`` latent positions along the
+        sliding axis.  Every slot's tokens embed its t_now and its latent takes the DDIM update of its pair; a slot with t_prev ==
+        t_now is held (``out`` equals ``z`` there bit for bit) while its tokens still take part in attention.  A table that repeats
+        one pair per sample gives ``step``'s bits.  The primitive of FIFO diagonal denoising (stream_infer.fifo_denoise) and of
+        continuing from held clean context.  Scope: solver "ddim" at eta == 0 with the scalar guidance; a latent guide, a CFG
+        control, a window consensus, temb_mode "add" and overlapping audio chunks are refused before anything is launched."""
+        if self.Xp is None:
+            raise RuntimeError("call set_prompt() first")
+        if self.eta > 0:
+            raise ValueError("step_slots needs eta == 0: slots at different timesteps have no common noise stream yet (eta > 0 is out "
+                             "of scope)")
+        if self.solver != "ddim":
+            raise ValueError(f"step_slots runs solver 'ddim': the multistep history of solver {self.solver!r} is per sample")
+        if self._guide is not None:
+            raise ValueError("step_slots takes no latent guide (its forward path is keyed by one t_prev per sample): clear_known() first")
+        if self._ctl is not None:
+            raise ValueError("step_slots takes the scalar guidance: per-sample guidance and guidance rescale (the CFG control) are not "
+                             "supported there")
+        if self._cons_hop is not None:
+            raise ValueError("step_slots takes no window consensus (the windows of a canvas share their timesteps): "
+                             "clear_window_consensus() first")
+        if self.temb_mode == "add":
+            raise ValueError("step_slots needs temb_mode='concat': the added embedding is one row per sample")
+        if self.target == "audio" and self.chunk[0] != self.chunk[1]:
+            raise ValueError(f"step_slots needs non-overlapping audio chunks (stride == length), got chunk {self.chunk}")
+        z = L.dev_f32(z, "z")
+        if tuple(z.shape) != self.latent_shape:
+            raise ValueError(f"latent shape {tuple(z.shape)} != engine shape {self.latent_shape}")
+        S = self.slots
+        tn, tp = Fn.slot_tables(t_now, t_prev, self.embed.B, S, self.device)
+        if out is None:
+            out = torch.empty_like(z)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == z.shape and out.device == z.device):
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {tuple(z.shape)} on z's device")
+        if not torch.cuda.is_current_stream_capturing():
+            self._sync_weights()
+        self._last_cond_only = False
+        L.check(L.lib().avd_denoise_step_slots_f32(C.byref(self.desc), z.data_ptr(), self.Xp.data_ptr(), tn.data_ptr(), tp.data_ptr(), S,
+                                                   out.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
+                                                   L.stream_ptr(self.device)))
         return out
 
     def eps_tokens(self) -> torch.Tensor:

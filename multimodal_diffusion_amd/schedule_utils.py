@@ -187,6 +187,41 @@ def trajectory_segments(sched, interval) -> List[Tuple[int, int, str]]:
     return [(a, b, "cfg" if cfg else "cond") for a, b, cfg in guidance_segments(sched, interval)]
 
 
+def fifo_plan(sched, S: int):
+    """The timestep tables of FIFO diagonal denoising (Kim et al. 2024, with its latent partitioning) for ``DenoiseEngine.step_slots``.
+    ``sched`` = s_0 > s_1 > ... > s_n = -1, strictly decreasing, n steps; ``S`` slots per sample, n % S == 0.  The queue has n slots,
+    queue slot q in sample q // S at slot q % S of a batch of B = n // S samples; its head (q = 0) is the cleanest.
+
+    steady state: slot q takes step n-1-q (t_now = s_{n-1-q}, t_prev = s_{n-q}) in every iteration: one model call moves every slot
+      one level, the head leaves finished (t_prev = -1), the queue shifts and noise at s_0 enters at the tail;
+    ramp: all n slots start as noise at s_0.  Ramp iteration r = 0 .. n-2 (no shift): slot q <= r takes step r-q, slot q > r holds at
+      s_0 (t_prev == t_now).  After the ramp slot q stands at s_{n-1-q}: the steady state.
+
+    Returns (ramp_now, ramp_prev, steady_now, steady_prev): int64 CPU tensors [n-1, B, S] x 2 and [B, S] x 2.  Clip slot c leaves in
+    steady iteration c, having taken the pairs (s_i, s_{i+1}), i = 0 .. n-1, in order, and nothing else but holds at s_0.  Host-side."""
+    S = _whole(S, "S")
+    s = torch.as_tensor(sched).reshape(-1).to("cpu", torch.long).tolist()
+    if len(s) < 2 or s[-1] != -1:
+        raise ValueError("fifo_plan needs a sampling schedule of at least one step that ends in -1")
+    if any(b >= a for a, b in zip(s[:-1], s[1:])):
+        raise ValueError("fifo_plan needs a strictly decreasing schedule: every queue slot takes its steps in order (no jumps, no "
+                         "equal neighbours)")
+    n = len(s) - 1
+    if n % S:
+        raise ValueError(f"fifo_plan: the {n} steps of the schedule must be a multiple of the S = {S} slots of a sample (the queue is "
+                         "n slots in n / S samples)")
+    B = n // S
+    q = torch.arange(n)
+    sc = torch.tensor(s, dtype=torch.long)
+    steady_now, steady_prev = sc[n - 1 - q], sc[n - q]
+    r = torch.arange(n - 1)[:, None]
+    live = q[None, :] <= r                                    # slot q steps in ramp iteration r
+    i = (r - q[None, :]).clamp(min=0)
+    hold = torch.full((n - 1, n), s[0], dtype=torch.long)
+    ramp_now, ramp_prev = torch.where(live, sc[i], hold), torch.where(live, sc[i + 1], hold)
+    return ramp_now.view(n - 1, B, S), ramp_prev.view(n - 1, B, S), steady_now.view(B, S).clone(), steady_prev.view(B, S).clone()
+
+
 def resample_from_config(scfg) -> Optional[Tuple[int, int]]:
     """``sampling.resample`` of a config: {jump:, resamples:}; a missing key or None means no resampling."""
     return check_resample(scfg.get("resample"))

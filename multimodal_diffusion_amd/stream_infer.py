@@ -18,6 +18,10 @@ pixel average of up to window / hop unrelated samples.  With consensus the windo
 denoising step each canvas position under several windows is replaced in all of them by their weighted mean (MultiDiffusion, Bar-Tal
 et al. 2023; ``avd_window_consensus_f32``), so they stay one batch and finish as one coherent latent clip.  ``latent_hop``,
 ``windows_from_canvas`` and ``canvas_from_windows`` are its host-side geometry.
+
+Extension (``fifo_denoise``): FIFO diagonal denoising, the other family of long-form samplers.  Instead of windows that share one
+timestep, a queue of latent slots runs from nearly clean to pure noise, one model call moves every slot one level
+(``DenoiseEngine.step_slots``), the head leaves finished and noise enters at the tail (``functional.fifo_shift``).
 """
 from __future__ import annotations
 
@@ -163,6 +167,95 @@ def canvas_from_windows(windows: torch.Tensor, hop: int) -> torch.Tensor:
     canvas = windows.new_empty((windows.shape[1], (N - 1) * hop + L_) + tuple(windows.shape[3:]))
     for k in range(N):
         canvas[:, k * hop:k * hop + L_] = windows[k]
+    return canvas
+
+
+def fifo_prompt_windows(prompt_canvas: torch.Tensor, m: int, B: int, S: int, prompt_hop: int, prompt_len: int) -> torch.Tensor:
+    """The prompt batch of ``fifo_denoise`` before the step of steady iteration ``m``: sample k is prompt positions (m + k*S) *
+    prompt_hop .. + prompt_len - 1 of the canvas's sliding axis ([C, P, H, W] video prompt, [Ca, P] audio prompt), zeros beyond the
+    canvas end.  Returns [B, C, prompt_len, H, W] / [B, Ca, prompt_len] on the canvas's device (any device: pure slicing)."""
+    if prompt_canvas.dim() not in (2, 4):
+        raise ValueError(f"a prompt canvas is [C, P, H, W] (video) or [Ca, P] (audio), got shape {tuple(prompt_canvas.shape)}")
+    if min(B, S, prompt_hop, prompt_len) < 1 or m < 0:
+        raise ValueError(f"fifo_prompt_windows: need B, S, prompt_hop, prompt_len >= 1 and m >= 0 (got {B}, {S}, {prompt_hop}, "
+                         f"{prompt_len}, {m})")
+    P_ = prompt_canvas.shape[1]
+    out = prompt_canvas.new_zeros((B, prompt_canvas.shape[0], prompt_len) + tuple(prompt_canvas.shape[2:]))
+    for k in range(B):
+        p0 = (m + k * S) * prompt_hop
+        n = max(0, min(prompt_len, P_ - p0))
+        if n:
+            out[k, :, :n] = prompt_canvas[:, p0:p0 + n]
+    return out
+
+
+def fifo_prompt_len(engine: DenoiseEngine, prompt_canvas: torch.Tensor) -> int:
+    """The prompt latent's length along its sliding axis that gives the engine's ``prompt_tokens``: an audio prompt (video target)
+    of Np chunks is (Np - 1) * stride + length frames; a video prompt (audio target) [C, P, H, W] of Np tubes is Np / (H/h * W/w)
+    token frames of the tube's t."""
+    Np = engine.embed.Np
+    if engine.target == "video":
+        if prompt_canvas.dim() != 2:
+            raise ValueError(f"a video target takes an audio prompt canvas [Ca, P], got shape {tuple(prompt_canvas.shape)}")
+        ln, st = engine.chunk
+        return (Np - 1) * st + ln
+    if prompt_canvas.dim() != 4:
+        raise ValueError(f"an audio target takes a video prompt canvas [C, P, H, W], got shape {tuple(prompt_canvas.shape)}")
+    t, h, w = engine.tube
+    H, W = prompt_canvas.shape[2:]
+    if H % h or W % w or Np % ((H // h) * (W // w)):
+        raise ValueError(f"a prompt canvas of {H} x {W} does not tile into the engine's {Np} prompt tokens with tube {engine.tube}")
+    return Np // ((H // h) * (W // w)) * t
+
+
+@torch.no_grad()
+def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop: int, sched, n_slots: int, noise_seed: int) -> torch.Tensor:
+    """FIFO diagonal denoising (FIFO-Diffusion, Kim et al. 2024, with latent partitioning): a clip of ``n_slots`` slots of
+    ``engine.slot_len`` latent positions, denoised in a queue whose slots sit at different noise levels.  Returns the finished latent
+    canvas [C, n_slots * slot_len, H, W] (video target) or [Ca, n_slots * slot_len] (audio target).
+
+    ``sched`` = s_0 > ... > s_n = -1 with n = engine batch * ``engine.slots`` (``schedule_utils.fifo_plan``): the engine's batch is
+    the queue, n slots from nearly clean (head) to pure noise (tail).  The queue starts as seeded noise at s_0
+    (``functional.canvas_noise``: clip slot c always starts from the same normals, however long the clip), n - 1 ramp steps bring it
+    to the diagonal, then every steady iteration is one ``step_slots`` — each slot moves one level — and one ``functional.fifo_shift``:
+    the head leaves finished, fresh noise enters at the tail.  Memory is constant in the clip length and a finished slot costs n / S
+    sample-steps, what non-overlapping windows cost; nothing is cross-faded or averaged.
+    ``prompt_canvas`` is the prompt modality's latent along its sliding axis and ``prompt_hop`` its positions per target slot: before
+    the step of steady iteration m (the ramp: m = 0) sample k is conditioned on ``fifo_prompt_windows(prompt_canvas, m, ...)[k]``,
+    the prompt under the clip slots the sample holds (``set_prompt`` into the same buffer).  The loop is eager.  The engine's limits
+    are ``step_slots``'s (solver "ddim", eta == 0, no guide / control / consensus)."""
+    if not isinstance(engine, DenoiseEngine):
+        raise TypeError("fifo_denoise drives a DenoiseEngine")
+    if isinstance(n_slots, bool) or not isinstance(n_slots, int) or n_slots < 1:
+        raise ValueError(f"n_slots must be an int >= 1, got {n_slots!r}")
+    if isinstance(prompt_hop, bool) or not isinstance(prompt_hop, int) or prompt_hop < 1:
+        raise ValueError(f"prompt_hop must be an int >= 1 (prompt positions per target slot), got {prompt_hop!r}")
+    B, S, sl = engine.embed.B, engine.slots, engine.slot_len
+    ramp_now, ramp_prev, steady_now, steady_prev = su.fifo_plan(sched, S)
+    n = ramp_now.shape[0] + 1
+    if n != B * S:
+        raise ValueError(f"the schedule has {n} steps, the engine's queue {B} samples x {S} slots = {B * S}: fifo_denoise needs them equal")
+    outer, L_, _ = Fn.window_dims(engine.latent_shape)
+    if L_ != S * sl:
+        raise ValueError(f"the engine's sliding length {L_} is not {S} slots of {sl} positions (an uncovered audio tail cannot queue)")
+    Fn.noise_key(noise_seed, 0)
+    s0 = int(torch.as_tensor(sched).reshape(-1)[0])
+    dev = engine.device
+    Lp = fifo_prompt_len(engine, prompt_canvas)
+    pc = L.dev_f32(prompt_canvas.to(dev), "prompt canvas")
+    tabs = [t.to(dev) for t in (ramp_now, ramp_prev, steady_now, steady_prev)]
+    z = Fn.canvas_noise(noise_seed, torch.full((B,), s0, dtype=torch.long, device=dev), engine.latent_shape, L_)
+    other = torch.empty_like(z)
+    engine.set_prompt(fifo_prompt_windows(pc, 0, B, S, prompt_hop, Lp))
+    for r in range(n - 1):
+        z, other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other), z
+    canvas = torch.empty((outer, n_slots * sl) + tuple(engine.latent_shape[3:]), device=dev, dtype=torch.float32)
+    for m in range(n_slots):
+        if m:
+            engine.set_prompt(fifo_prompt_windows(pc, m, B, S, prompt_hop, Lp))
+        other = engine.step_slots(z, tabs[2], tabs[3], out=other)
+        z, popped = Fn.fifo_shift(other, n + m, noise_seed, s0, sl)
+        canvas[:, m * sl:(m + 1) * sl] = popped
     return canvas
 
 

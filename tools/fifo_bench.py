@@ -1,0 +1,180 @@
+"""Measurements of slot timesteps and FIFO diagonal denoising at the C3 geometry (256 x 256: latent [B, 8, 12, 32, 32], tube 2 x 4 x 4,
+384 + 37 tokens), on one GPU, in one process:
+
+  --kernels   the slot form of the fused update and of the assembly pass against their per-sample forms (the per-sample form timed
+              twice: its run-to-run spread), and the queue shift kernel with its bytes per microsecond; per-launch times from the
+              library's launch events (avd_prof_enable / avd_prof_report)
+  --e2e       finished latent slots per second of stream_infer.fifo_denoise (n = 48 steps, S = 6, B = 8) next to the window-consensus
+              loop at the same step count, and the share of a steady iteration spent in set_prompt and the shift
+
+Prints plain text: the records are profiles/fifo_kernels.txt and profiles/fifo_e2e.txt."""
+import argparse
+import ctypes as C
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+import multimodal_diffusion_amd as A                       # noqa: E402
+from multimodal_diffusion_amd import _lib as L             # noqa: E402
+from multimodal_diffusion_amd import functional as Fn      # noqa: E402
+from multimodal_diffusion_amd import schedule_utils as su  # noqa: E402
+from multimodal_diffusion_amd.stream_infer import fifo_prompt_len, fifo_prompt_windows  # noqa: E402
+from oracle import ref_cpu as R                            # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--kernels", action="store_true")
+ap.add_argument("--e2e", action="store_true")
+ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--launches", type=int, default=50)
+ap.add_argument("--slots-out", type=int, default=24, help="--e2e: finished slots per timed fifo_denoise call")
+args = ap.parse_args()
+
+dev = torch.device("cuda:0")
+ABAR = R.alpha_bar_table(R.beta_table(1000))
+
+
+def build(n_layers, B, target="video"):
+    ws = R.synth_weights(seed=0, n_layers=n_layers)
+    core = A.MMDiT(d_model=512, n_layers=n_layers, n_heads=8, mlp_ratio=4.0).eval()
+    core.load_state_dict(ws["core"], strict=True)
+    head = A.MultiModalNoiseHead({"video": 512, "audio": 512}, {"video": 256, "audio": 32}, hidden_dim=512).eval()
+    head.load_state_dict(ws["head"], strict=True)
+    av, aa = A.LinearAdapter(256, 256), A.LinearAdapter(32, 256)
+    av.load_state_dict(ws["adapt_v"])
+    aa.load_state_dict(ws["adapt_a"])
+    core, head, av, aa = (m.to(dev) for m in (core, head, av, aa))
+    return A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target=target,
+                           latent_shape=(B, 8, 12, 32, 32), prompt_tokens=37, alpha_bar=ABAR, guidance=3.5, matmul="bf16x3")
+
+
+def per_launch_us(tag, fn, launches):
+    """mean microseconds per launch of the kernels recorded under `tag` while fn() runs `launches` times"""
+    L.prof_enable(True)
+    try:
+        for _ in range(launches):
+            fn()
+        torch.cuda.synchronize()
+    finally:
+        L.prof_enable(False)
+    n, ms, _ = L.prof_report()[tag]
+    assert n == launches, (tag, n, launches)
+    return 1e3 * ms / n
+
+
+if args.kernels:
+    B, S = 32, 6
+    eng = build(2, B)
+    g = torch.Generator().manual_seed(0)
+    z = torch.randn(B, 8, 12, 32, 32, generator=g).to(dev)
+    eng.set_prompt(torch.randn(B, 8, 150, generator=g).to(dev))
+    eps2 = torch.randn(2 * B, 384, 256, generator=g).to(dev)
+    out = torch.empty_like(z)
+    ab, st, lib = ABAR.to(dev), L.stream_ptr(dev), L.lib()
+    sched = su.make_sampling_schedule(1000, 48)
+    tn1, tp1 = (torch.full((B,), int(v), dtype=torch.long, device=dev) for v in (sched[10], sched[11]))
+    # the diagonal of a FIFO queue: every slot of the batch at its own level (6 consecutive pairs per sample, repeated over the batch)
+    i = (torch.arange(B * S) % 47).view(B, S)
+    tnS, tpS = sched[i].to(dev).contiguous(), sched[i + 1].to(dev).contiguous()
+    tnH, tpH = tnS.clone(), tpS.clone()
+    tpH[:, S // 2:] = tnH[:, S // 2:]                     # half of every sample held
+    head = (eps2.data_ptr(), z.data_ptr())
+    dims = (B, 8, 12, 32, 32, 2, 4, 4, st)
+
+    def update(tn, tp, slots):
+        if slots:
+            return lambda: L.check(lib.avd_cfg_unpatch_ddim_slots_f32(*head, tn.data_ptr(), tp.data_ptr(), ab.data_ptr(), 1000, 3.5, slots,
+                                                                      out.data_ptr(), *dims))
+        return lambda: L.check(lib.avd_cfg_unpatch_ddim_f32(*head, tn.data_ptr(), tp.data_ptr(), ab.data_ptr(), 1000, 3.5, 0.0, None,
+                                                            out.data_ptr(), *dims))
+
+    e = eng.embed
+    tok = torch.empty(lib.avd_embed_workspace_floats(C.byref(e)), device=dev)
+    X2 = torch.empty(2 * B, eng.N, eng.d, device=dev)
+    emb = (C.byref(e), z.data_ptr(), eng._aw.data_ptr(), eng._ab.data_ptr())
+
+    def embed(tn, slots):
+        if slots:
+            return lambda: L.check(lib.avd_embed_cfg_pair_slots_f32(*emb, tn.data_ptr(), slots, eng.Xp.data_ptr(), tok.data_ptr(),
+                                                                    X2.data_ptr(), st))
+        return lambda: L.check(lib.avd_embed_cfg_pair_f32(*emb, tn.data_ptr(), eng.Xp.data_ptr(), tok.data_ptr(), X2.data_ptr(), st))
+
+    zq = torch.randn(8, 8, 12, 32, 32, generator=g).to(dev)          # the e2e queue: B = 8
+    rows = [("update per-sample (a)", "cfg_unpatch_ddim_kernel", update(tn1, tp1, 0)),
+            ("update slots, diagonal", "cfg_unpatch_ddim_kernel", update(tnS, tpS, S)),
+            ("update per-sample (b)", "cfg_unpatch_ddim_kernel", update(tn1, tp1, 0)),
+            ("update slots, half held", "cfg_unpatch_ddim_kernel", update(tnH, tpH, S)),
+            ("assembly per-sample (a)", "assemble_rows_kernel", embed(tn1, 0)),
+            ("assembly slots", "assemble_rows_kernel", embed(tnS, S)),
+            ("assembly per-sample (b)", "assemble_rows_kernel", embed(tn1, 0)),
+            ("fifo_shift B=32", "fifo_shift_kernel<4>", lambda: Fn.fifo_shift(z, 192, 7, 999, 2)),
+            ("fifo_shift B=8", "fifo_shift_kernel<4>", lambda: Fn.fifo_shift(zq, 48, 7, 999, 2))]
+    for _, _, fn in rows:
+        for _ in range(5):
+            fn()
+    torch.cuda.synchronize()
+    res = {name: [] for name, _, _ in rows}
+    for _ in range(args.rounds):
+        for name, tag, fn in rows:
+            res[name].append(per_launch_us(tag, fn, args.launches))
+    print(f"C3 geometry, {args.rounds} interleaved rounds of {args.launches} launches, microseconds per launch (launch events)")
+    for name, _, _ in rows:
+        v = res[name]
+        print(f"  {name:28s} " + " ".join(f"{x:8.2f}" for x in v) + f"   median {statistics.median(v):8.2f}")
+    for name, zz in (("fifo_shift B=32", z), ("fifo_shift B=8", zq)):
+        nbytes = 4 * (2 * zz.numel() + zz[0, :, :2].numel())
+        us = statistics.median(res[name])
+        print(f"  {name}: {nbytes / 1e6:.2f} MB read + written, {nbytes / us / 1e6:.2f} TB/s ({nbytes / us:.0f} bytes per microsecond)")
+
+if args.e2e:
+    n, S, B, K = 48, 6, 8, args.slots_out
+    sched = su.make_sampling_schedule(1000, n)
+    eng = build(8, B)
+    g = torch.Generator().manual_seed(1)
+    canvas_p = torch.randn(8, 25 * (n + 2 * K) + 148, generator=g).to(dev)      # 25 audio latent frames per target slot of 2 latent frames
+    hop_p = 25
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, r
+
+    A.fifo_denoise(eng, canvas_p, hop_p, sched, 2, 5)                        # warm-up
+    print(f"fifo_denoise: n = {n} steps, S = {S}, B = {B} (C3 latent, 8 layers, bf16x3, eager), {args.rounds} rounds")
+    for K_ in (K, 2 * K):
+        ts_ = [timed(lambda: A.fifo_denoise(eng, canvas_p, hop_p, sched, K_, 5))[0] for _ in range(args.rounds)]
+        print(f"  {K_:3d} slots out: " + " ".join(f"{t * 1e3:8.1f}" for t in ts_) + f" ms   ({K_ / statistics.median(ts_):6.1f} slots/s whole call, "
+              f"ramp of {n - 1} steps included)")
+    # the parts of a steady iteration, each ended by a synchronise
+    rn, rp, sn, sp = (t.to(dev) for t in su.fifo_plan(sched, S))
+    Lp = fifo_prompt_len(eng, canvas_p)
+    z = Fn.canvas_noise(5, torch.full((B,), int(sched[0])), eng.latent_shape, 12)
+    parts = {"set_prompt": [], "step_slots": [], "fifo_shift": []}
+    for m in range(3 * args.rounds * 4):
+        t, _ = timed(lambda: eng.set_prompt(fifo_prompt_windows(canvas_p, m, B, S, hop_p, Lp)))
+        parts["set_prompt"].append(t)
+        t, zo = timed(lambda: eng.step_slots(z, sn, sp))
+        parts["step_slots"].append(t)
+        t, (z, _) = timed(lambda: Fn.fifo_shift(zo, n + m, 5, int(sched[0]), 2))
+        parts["fifo_shift"].append(t)
+    med = {k: statistics.median(v[4:]) for k, v in parts.items()}
+    tot = sum(med.values())
+    print("  steady iteration (one finished slot), parts timed with a synchronise after each: " +
+          ", ".join(f"{k} {v * 1e3:.3f} ms ({100 * v / tot:.1f} %)" for k, v in med.items()) + f"; {1 / tot:.1f} slots/s steady state")
+    # the window-consensus loop at the same step count: 8 windows of 12 latent frames, hop 4 (the 3 s / 1 s default): a canvas of 40
+    # latent frames = 20 slots of 2 frames
+    engc = build(8, B)
+    engc.set_prompt(torch.randn(B, 8, 150, generator=g).to(dev))
+    engc.set_window_consensus(4)
+    z0 = torch.randn(B, 8, 12, 32, 32, generator=g).to(dev)
+    engc.run(z0, sched[:4])
+    ts_ = [timed(lambda: engc.run(z0, sched))[0] for _ in range(args.rounds)]
+    print(f"window consensus (DenoiseEngine.run, set_window_consensus(4), B = {B} windows of 12 frames: 20 slots of 2 frames), {n} steps: " +
+          " ".join(f"{t * 1e3:8.1f}" for t in ts_) + f" ms   ({20 / statistics.median(ts_):6.1f} slots/s)")
