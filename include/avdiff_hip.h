@@ -790,7 +790,7 @@ typedef struct {
     const float* conv_w_scale;         /* conv_terms 3: HOST array [n_blocks], power-of-two scales of the weight images */
     const float* conv_a_scale;         /* conv_terms 3: HOST array [n_blocks], scales of each block's INPUT image: entry i >= 1 from the bound
                                         * |GroupNorm output| <= sqrt(n - 1) max|gamma| + max|beta| (n = elements of one group of one sample);
-                                        * entry 0 is ignored — the first image's scale is derived on the device from max |from_lat(z)| */
+                                        * entry 0 is ignored — the first image's scale is derived on the device, per sample, from max |from_lat(z)| */
     /* ABI 6 — the first convolution composed with what precedes it (vae_video3d.py:205-209: from_lat -> trilinear upsample -> dec_net.0.0):
      * upsampling is linear, channel-wise and its weights sum to one, so conv(upsample(from_lat(z))) is a convolution of upsample(z) — Cv <= 16
      * input channels instead of 64, a quarter of the matrix work — plus a bias term.  With conv_w3 and conv0_lat_w3 both given the decoder

@@ -575,8 +575,9 @@ struct Conv3Args {
     int64_t x_slab_stride, out_slab_stride;
 };
 
-// scale slot in the workspace: [0] max |x|, [1] (max row norm, unused), [2] s, [3] 1 / s
+// scale slot in the workspace, one per sample (= block): [0] max |x|, [1] (max row norm, unused), [2] s, [3] 1 / s
 __global__ void pow2_scale_kernel(float* ws) {
+    ws += 4 * blockIdx.x;
     const float amax = ws[0] * 1.01f;
     float s = 1.0f;
     if (amax > 0.f) {
@@ -749,7 +750,7 @@ __device__ __forceinline__ void store_act3(unsigned char* X3, int64_t pv, int c8
 }
 
 // trilinear upsample into the interior of the act3 buffer (same arithmetic as upsample_pad_kernel, 8 channels per thread)
-template <bool F16>      // F16: the image scale is read from the device (sc_dev[0], written by pow2_scale_kernel)
+template <bool F16>      // F16: the sample's image scale is read from the device (sc_dev[4 smp], written by pow2_scale_kernel)
 __global__ __launch_bounds__(256) void upsample_pad3_kernel(const float* __restrict__ hlow, unsigned char* __restrict__ X3,
                                                             int Tp, int Hp_, int Wp_, int T, int H, int W, float st,
                                                             float sh, float sw, int64_t total8, const float* __restrict__ sc_dev, int64_t slab_stride) {
@@ -777,7 +778,7 @@ __global__ __launch_bounds__(256) void upsample_pad3_kernel(const float* __restr
         o[4 * q] = r[0]; o[4 * q + 1] = r[1]; o[4 * q + 2] = r[2]; o[4 * q + 3] = r[3];
     }
     const int64_t pv = (((int64_t)smp * (T + 2) + t + 1) * (H + 2) + h + 1) * (W + 2) + w + 1;
-    store_act3<F16>(X3, pv, c8, o, F16 ? sc_dev[0] : 0.f, slab_stride);
+    store_act3<F16>(X3, pv, c8, o, F16 ? sc_dev[4 * smp] : 0.f, slab_stride);
 }
 
 // GroupNorm apply: Y (NDHWC fp32) -> interior of the act3 buffer feeding the next conv.  A block takes 64 consecutive voxels: one thread
@@ -875,7 +876,7 @@ __global__ __launch_bounds__(256) void upsample_lat16_kernel(const float* __rest
     for (int half = 0; half < 2; ++half) {
         if constexpr (F16) {
             u32x4 Hh, Lo;
-            split8_h2(o + 8 * half, sc_dev[0], Hh, Lo);
+            split8_h2(o + 8 * half, sc_dev[4 * smp], Hh, Lo);
             *reinterpret_cast<u32x4*>(dst + half * 16) = Hh;
             *reinterpret_cast<u32x4*>(dst + 32 + half * 16) = Lo;
         } else {
@@ -930,7 +931,7 @@ __global__ __launch_bounds__(256) void upsample_lat8_kernel(const float* __restr
     const u32x4 zero = {0u, 0u, 0u, 0u};
     if constexpr (F16) {
         u32x4 Hh, Lo;
-        split8_h2(o, sc_dev[0], Hh, Lo);
+        split8_h2(o, sc_dev[4 * smp], Hh, Lo);
         *reinterpret_cast<u32x4*>(dst) = Hh;
         *reinterpret_cast<u32x4*>(dst + 16) = zero;
         *reinterpret_cast<u32x4*>(dst + 32) = Lo;
@@ -1263,7 +1264,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_bf16x3_kernel(Conv3Args g) {
     float* slab_f = reinterpret_cast<float*>(smem3) + wave * 64 * CLD;
     const int cr = lane >> 4, cc = (lane & 15) * 4;          // 16 lanes per row (4 channels each), 4 rows per wave instruction
     const f32x4 bv = *reinterpret_cast<const f32x4*>(g.bias + cc);
-    const float ab_inv = F16 ? g.ab_inv * (g.a_inv_dev ? g.a_inv_dev[0] : 1.0f) : 1.0f;
+    const float ab_inv = F16 ? g.ab_inv * (g.a_inv_dev ? g.a_inv_dev[4 * smp] : 1.0f) : 1.0f;
     const int tt = t0 + wave;
     if constexpr (OUT != 0) {
         // 8 lanes per voxel row, 8 channels (one GroupNorm group) each, 8 rows per wave instruction
@@ -1592,7 +1593,7 @@ struct VaePlan {
     int64_t hlow;                   // from_lat(z) on the latent grid | the channel-last copy of z
     int64_t part, fin;              // GroupNorm partials, then gn_finalize's per-chunk fp64 sums
     int64_t consts, wg, wimg, btab1;// {rstd[8], K[4]} per sample, to_img_w . gamma [4][64], folded route: conv 1's per-sample images and bias tables
-    int64_t stats, scale, total;    // GroupNorm mean / rstd, then {max |x|, -, s, 1 / s} of the f16x2 decoder's first image
+    int64_t stats, scale, total;    // GroupNorm mean / rstd, then per sample {max |x|, -, s, 1 / s} of the f16x2 decoder's first image
 };
 
 static int vae_plan(const avd_vae_decode_desc* d, VaePlan& p) {
@@ -1623,7 +1624,7 @@ static int vae_plan(const avd_vae_decode_desc* d, VaePlan& p) {
     p.wimg = p.wg + 4 * VC * 4;
     p.btab1 = p.wimg + (int64_t)d->B * W3_BYTES;
     p.stats = c.take(a256((int64_t)d->B * VG * 2 * 4));
-    p.scale = c.take(256);
+    p.scale = c.take(a256((int64_t)d->B * 16));
     p.total = c.end;
     return AVD_OK;
 }
@@ -1692,10 +1693,12 @@ static int dec_fromlat(const VaeDec& r) {
     return AVD_OK;
 }
 // the f16x2 decoder's first image is an interpolation (a convex combination) of x: its magnitude is bounded by max |x|, which depends on
-// the data — the power-of-two image scale is derived from it on the device
+// the data — the power-of-two image scale is derived from it on the device (x = [B][rows][cols])
 static int dec_first_scale(const VaeDec& r, const float* x, int64_t rows, int cols) {
-    if (int rc = weight_bounds_f32(x, rows, cols, r.at<float>(r.p.scale), r.st)) return rc;
-    hipLaunchKernelGGL(pow2_scale_kernel, dim3(1), dim3(1), 0, r.st, r.at<float>(r.p.scale));
+    // one scale per sample, not per launch: a sample's output must not depend on what else is in the batch
+    for (int smp = 0; smp < r.d->B; ++smp)
+        if (int rc = weight_bounds_f32(x + smp * rows * cols, rows, cols, r.at<float>(r.p.scale) + 4 * smp, r.st)) return rc;
+    hipLaunchKernelGGL(pow2_scale_kernel, dim3(r.d->B), dim3(1), 0, r.st, r.at<float>(r.p.scale));
     AVD_CHECK_LAUNCH("pow2_scale");
     return AVD_OK;
 }
@@ -1774,13 +1777,13 @@ static int vae_dec_split(const VaeDec& r, DecRoute route) {
                     "vae_decode: conv0_lat_w_scale must be positive and finite");
         if (int rc = zero_halo(X3, B, p.T, p.H, p.W, L16_ROWB, r.st)) return rc;
         if (h2)         // |upsample(z)| <= max |z|
-            if (int rc = dec_first_scale(r, r.in, (int64_t)B * d->Cv, d->Tp * d->Hp * d->Wp)) return rc;
+            if (int rc = dec_first_scale(r, r.in, d->Cv, d->Tp * d->Hp * d->Wp)) return rc;
         if (int rc = dec_upsample_lat(r, X3, h2)) return rc;
     } else {
         if (int rc = zero_halo(X3, 4 * B, p.T, p.H, p.W, act_rowb, r.st)) return rc;
         if (int rc = dec_fromlat(r)) return rc;
         if (h2)
-            if (int rc = dec_first_scale(r, hlow, (int64_t)B * d->Tp * d->Hp * d->Wp, VC)) return rc;
+            if (int rc = dec_first_scale(r, hlow, (int64_t)d->Tp * d->Hp * d->Wp, VC)) return rc;
         const int64_t total8 = (int64_t)B * p.THW * 8;
         static const int tag = prof_tag_id("upsample_pad3_kernel");
         ProfScope prof(tag, 6.0 * (double)B * p.THW * VC, r.st);

@@ -2,7 +2,7 @@
 the profiling tags.  Every case is one VideoVAE.decode or .encode call on a tiny input whose tiles are ragged; EXPECT holds the
 (tag, launches, work) triples each case ran, recorded on a5c3b51, the commit before the conv launch ladder and the two route bodies were
 collapsed.  Launches are compared exactly and the work to 1e-9 relative (products of integers and one 14 / 27 factor).  Outputs are not
-checked here (tests/test_gpu_parity.py and tests/test_gpu_f16x2.py do that)."""
+checked here (tests/test_gpu_vae_outputs.py compares every case of this file with the fp64 oracle)."""
 import pytest
 import torch
 
