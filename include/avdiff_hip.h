@@ -267,8 +267,8 @@ int avd_canvas_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* 
  *     at t_now and still takes part in attention; only its update is skipped (its eps is not read).
  * A table filled with one pair per sample gives the bits of the per-sample entry; a slot gives the bits the per-sample entry gives
  * there when its whole sample runs at the slot's pair.  Attention and the GEMMs are the per-sample step's, launch for launch.
- * Scope, everything else is refused before any launch (AVD_EINVAL): DDIM at eta == 0 (no noise, no key), the CFG step with the
- * scalar guidance, the concat embedding (temb_add == 0), no solver history, latent guide, CFG control or canvas keying.  Both targets,
+ * Scope, everything else is refused before any launch (AVD_EINVAL): DDIM or DPM-Solver++(2M) (below) at eta == 0 (no noise, no key), the
+ * CFG step with the scalar guidance, the concat embedding (temb_add == 0), no latent guide, CFG control or canvas keying.  Both targets,
  * every matmul / attention mode, both stream layouts (split_streams) and the null half's short layout are taken as by the plain step.
  * `slots` must equal the geometry's S.  Samplers whose positions sit at different noise levels (FIFO-Diffusion, rolling diffusion,
  * continuation from held clean context) are loops over avd_denoise_step_slots_f32. */
@@ -279,6 +279,25 @@ int avd_cfg_unpatch_ddim_slots_f32(const float* eps2, const float* z, const int6
 int avd_cfg_untoken_ddim_audio_slots_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                          const float* alpha_bar, int T_train, float guidance, int slots, float* z_out,
                                          int B, int Ca, int F, int len, int stride, avd_stream_t stream);
+/* The slot form of the DPM-Solver++(2M) update (ODE, eta == 0): t_last is a third int64 [B*slots] table and x0_hist [B, per_sample]
+ * the history in the latent's natural layout, one value per latent element, so a slot's history is the x0_hist elements of its latent
+ * positions.  Per slot the semantics are avd_dpmpp_2m_step_f32's with the triple (t_last, t_now, t_prev)[b, s] in the place of [b]:
+ *   - t_last[b, s] < 0 (or a t_last that is not above t_now in noise level: the lambda condition) is a first-order step;
+ *   - the slot's x0_hist elements are read only where c_1 != 0, then overwritten with the slot's x0 (DDIM's x0 expression);
+ *   - the hold: where t_prev[b, s] == t_now[b, s], z_out is z bit for bit and the slot's x0_hist elements are neither read nor
+ *     written (t_last[b, s] is not read either): a slot waiting in a queue's ramp picks up no history;
+ *   - audio target: the uncovered tail follows the last slot with eps = 0, its x0_hist elements included.
+ * A table that repeats one triple per sample gives the bits of the per-sample DPM step in z_out and in x0_hist
+ * (avd_dpmpp_2m_step_f32 on the combined eps; the whole step: avd_denoise_step_dpmpp_2m_f32).  x0_hist must not overlap z or z_out (AVD_EINVAL) and, for the video
+ * target and the whole step, must be 16-byte aligned (AVD_EUNSUPPORTED). */
+int avd_cfg_unpatch_dpmpp_2m_slots_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                       const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, int slots,
+                                       float* x0_hist, float* z_out, int B, int C, int T, int H, int W, int t, int h, int w,
+                                       avd_stream_t stream);
+int avd_cfg_untoken_dpmpp_2m_audio_slots_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                             const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, int slots,
+                                             float* x0_hist, float* z_out, int B, int Ca, int F, int len, int stride,
+                                             avd_stream_t stream);
 
 /* ---- FIFO queue shift: the queue step of diagonal denoising (FIFO-Diffusion, Kim et al. 2024) in one out-of-place launch.
  * The batch z_in [B, outer, L, inner] ((outer, L, inner) as in "canvas-keyed noise") with L = slots*slot_len is read as a queue of
@@ -295,6 +314,15 @@ int avd_cfg_untoken_ddim_audio_slots_f32(const float* eps2, const float* z, cons
  * lane otherwise (every audio latent); same bits either way. */
 int avd_fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped,
                        int B, int64_t outer, int slots, int slot_len, int64_t inner, avd_stream_t stream);
+/* FIFO queue shift with history: the same launch carries a multistep solver's per-element history (x0_hist of the slot form of
+ * DPM-Solver++(2M)) along with its slot.  (z_in -> z_out, popped) is avd_fifo_shift_f32's, the same bits and the same tail noise;
+ * hist_out slot q = hist_in slot q + 1 for q < B*slots - 1, and hist_out's tail slot is zero (the entering slot has no history: its
+ * t_last is -1, so the zeros are never read; they keep the buffer defined).  The head's history is dropped.  Out of place for both
+ * pairs; z_in, z_out, popped, hist_in and hist_out must not overlap one another (AVD_EINVAL), the other checks are avd_fifo_shift_f32's.
+ * 16-byte lanes when inner % 4 == 0 and all five bases are 16-byte aligned, one element per lane otherwise; same bits either way. */
+int avd_fifo_shift_hist_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped,
+                            const float* hist_in, float* hist_out, int B, int64_t outer, int slots, int slot_len, int64_t inner,
+                            avd_stream_t stream);
 
 /* ---- latent guide: inpainting / outpainting and SDEdit over a known clean latent (a public contract).
  * Per sample b of a call, with x_k = known[b] and m = the mask, both in the latent's natural layout ([C,T,H,W] video, [Ca,F] audio,
@@ -682,6 +710,13 @@ int avd_denoise_step_f32(const avd_step_desc* s, const float* z, const float* Xp
 int avd_denoise_step_slots_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_now,
                                const int64_t* t_prev, int slots, float* z_out,
                                void* workspace, int64_t workspace_bytes, avd_stream_t stream);
+/* As avd_denoise_step_slots_f32, ending in the slot form of the DPM-Solver++(2M) update (see "slot timesteps"): t_last int64 [B*slots],
+ * x0_hist fp32 [B, per_sample], 16-byte aligned, not overlapping z or z_out.  The front end is avd_denoise_step_slots_f32's, launch for
+ * launch; refusals are its own, plus those of x0_hist.  Uniform tables give avd_denoise_step_dpmpp_2m_f32's bits in z_out and x0_hist.
+ * Graph-capturable: the tables and x0_hist are read at their addresses at every launch. */
+int avd_denoise_step_slots_dpmpp_2m_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_last,
+                                        const int64_t* t_now, const int64_t* t_prev, int slots, float* x0_hist, float* z_out,
+                                        void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 /* As avd_denoise_step_f32, with the eta > 0 noise drawn inside the fused CFG + DDIM kernel from the seeded stream (avd_noise_key)
  * for samples key->sample_offset .. + B - 1 at t_now: no noise buffer, graph-capturable.  With s->eta == 0 it is the plain step. */
 int avd_denoise_step_seeded_f32(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp,

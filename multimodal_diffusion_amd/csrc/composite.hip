@@ -1038,6 +1038,27 @@ extern "C" int avd_denoise_step_slots_f32(const avd_step_desc* s, const float* z
                         nullptr, 0, 0, slots);
 }
 
+// As avd_denoise_step_slots_f32, ending in the slot form of the DPM-Solver++(2M) update: t_last is a [B, S] table as well and x0_hist
+// the per-element history.  The front end is the same slot assembly; only the fused update's pack differs.
+extern "C" int avd_denoise_step_slots_dpmpp_2m_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_last,
+                                                   const int64_t* t_now, const int64_t* t_prev, int slots, float* x0_hist, float* z_out,
+                                                   void* workspace, int64_t workspace_bytes, avd_stream_t stream) {
+    AVD_REQUIRE(s, AVD_EINVAL, "denoise_step_slots_dpmpp_2m: null descriptor");
+    AVD_REQUIRE(s->eta == 0.f, AVD_EINVAL, "denoise_step_slots_dpmpp_2m: slot timesteps take the ODE update at eta == 0 (eta is %g)",
+                (double)s->eta);
+    AVD_REQUIRE(!s->embed.temb_add, AVD_EINVAL, "denoise_step_slots_dpmpp_2m: slot timesteps take the concat embedding (temb_add == 0)");
+    if (int rc = check_embed(&s->embed)) return rc;
+    int S = 0, tok = 0;
+    if (int rc = embed_slots(&s->embed, S, tok)) return rc;
+    AVD_REQUIRE(slots == S, AVD_EINVAL, "denoise_step_slots_dpmpp_2m: slots %d must equal the geometry's %d slots along the sliding axis",
+                slots, S);
+    if (int rc = check_step_options("denoise_step_slots_dpmpp_2m", NEED_HIST, s, nullptr, t_last, x0_hist, z, z_out, nullptr, nullptr, nullptr))
+        return rc;
+    AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "denoise_step_slots_dpmpp_2m: x0_hist must be 16-byte aligned");
+    return denoise_step(s, nullptr, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, nullptr,
+                        nullptr, 0, 0, slots);
+}
+
 extern "C" int avd_denoise_step_seeded_f32(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp,
                                            const int64_t* t_now, const int64_t* t_prev, float* z_out, void* workspace,
                                            int64_t workspace_bytes, avd_stream_t stream) {

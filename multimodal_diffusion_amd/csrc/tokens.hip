@@ -318,6 +318,9 @@ struct CondOnly {};
 // are [B, S] tables, one pair per slot of the target's sliding axis (video: the S = T / t token frames; audio: the S = Na chunks, stride
 // == len), every element takes ddim_coef of its slot's pair, and a slot whose pair is equal keeps z bit for bit (the hold).  It is the
 // DDIM update at eta == 0 without a guide or a control: the pack holds nothing else.
+// Behind a DpmState (the pack `DpmState, SlotTimes`, SEEDED false) it is the slot form of the DPM-Solver++(2M) ODE update: DpmState's
+// t_last is a [B, S] table as well, every element takes ddim_coef / dpm_coef at its slot's entry, and a held slot keeps z and neither
+// reads nor writes its x0_hist elements.
 struct SlotTimes {
     int S;
 };
@@ -334,7 +337,7 @@ template <bool SEEDED, class... X> struct PackOk {
     template <class T> static constexpr int n = PackHas<T, X...>::value ? 1 : 0;
     static constexpr bool value = sizeof...(X) == (SEEDED ? 1 : 0) + n<DpmState> + n<GuideState> + n<CanvasGuideState> + n<CfgState> +
                                                       n<CondOnly> + n<SlotTimes> &&
-                                  !(n<SlotTimes> && sizeof...(X) != 1) &&
+                                  !(n<SlotTimes> && sizeof...(X) != 1 + n<DpmState>) &&
                                   !(n<CfgState> && n<CondOnly>) && !(n<GuideState> && n<CanvasGuideState>) &&
                                   !(n<CanvasGuideState> && n<NoiseKey>) &&
                                   n<NoiseKey> + n<CanvasKey> == (SEEDED ? 1 : 0);
@@ -500,10 +503,17 @@ bool overlaps(const float* a, const float* b, int64_t n);
 // slot q + 1 (across sample boundaries), popped = z_in slot 0, and fills the tail slot with the canvas-keyed normals of canvas
 // positions c * slot_len + j at timestep `t`: canvas_normal4 with window index c and hop slot_len, the bits of canvas_noise_kernel.
 // V lanes as canvas_noise_kernel.  Lanes [0, n_out) write z_out, lanes [n_out, n_out + n_pop) write popped.
-template <int V>
+// A HistShift ending the arguments (an empty pack otherwise: the plain shift keeps its argument layout and code) carries a second
+// buffer of z's layout along ("FIFO queue shift with history"): the lane that writes z_out[idx] writes hist_out[idx] from the same
+// source offset of hist_in, and zeros in the tail slot.  Nothing of the history is popped.
+struct HistShift {
+    const float* in;
+    float* out;
+};
+template <int V, class... Hist>
 __global__ __launch_bounds__(256) void fifo_shift_kernel(const float* __restrict__ z_in, float* __restrict__ z_out,
                                                          float* __restrict__ popped, CanvasKey ck, uint32_t t, int B, int64_t outer, int S,
-                                                         int slot_len, int64_t inner, int64_t n_out, int64_t n_pop) {
+                                                         int slot_len, int64_t inner, int64_t n_out, int64_t n_pop, Hist... hs) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= n_out + n_pop) return;
     const int64_t iv = inner / V;
@@ -529,20 +539,33 @@ __global__ __launch_bounds__(256) void fifo_shift_kernel(const float* __restrict
     const int64_t q1 = (int64_t)b * S + l / slot_len + 1;      // the queue slot this one receives
     if (q1 < (int64_t)B * S) {
         const int64_t bs = q1 / S, ls = (q1 % S) * slot_len + j;
-        const float* src = z_in + ((bs * outer + o) * L + ls) * inner + i;
+        const int64_t so = ((bs * outer + o) * L + ls) * inner + i;
+        const float* src = z_in + so;
         if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = *reinterpret_cast<const f32x4*>(src);
         else z_out[idx] = *src;
+        if constexpr (sizeof...(Hist) != 0) {
+            const HistShift h = HistShift(hs...);
+            if constexpr (V == 4) *reinterpret_cast<f32x4*>(h.out + idx * 4) = *reinterpret_cast<const f32x4*>(h.in + so);
+            else h.out[idx] = h.in[so];
+        }
     } else {                 // the tail slot: fresh noise of clip slot c
         const f32x4 v = canvas_normal4(ck, 0, o, j, i, inner, t);
         if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = v;
         else z_out[idx] = v[(int)((o * inner + i) & 3)];
+        if constexpr (sizeof...(Hist) != 0) {      // no history yet: zeros (never read: the tail's t_last is -1)
+            const HistShift h = HistShift(hs...);
+            if constexpr (V == 4) *reinterpret_cast<f32x4*>(h.out + idx * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+            else h.out[idx] = 0.f;
+        }
     }
 }
 
+// hist_in / hist_out: both null (the plain shift) or both set (the shift with history: hist_out slot q = hist_in slot q + 1, zeros in the tail)
 int fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped, int B, int64_t outer,
-                   int S, int slot_len, int64_t inner, hipStream_t st) {
+                   int S, int slot_len, int64_t inner, hipStream_t st, const float* hist_in = nullptr, float* hist_out = nullptr) {
     AVD_REQUIRE(key, AVD_EINVAL, "fifo_shift: null noise key");
     AVD_REQUIRE(z_in && z_out && popped, AVD_EINVAL, "fifo_shift: null pointer");
+    AVD_REQUIRE(!hist_in == !hist_out, AVD_EINVAL, "fifo_shift: hist_in and hist_out go together");
     AVD_REQUIRE(B > 0 && outer > 0 && S > 0 && slot_len > 0 && inner > 0, AVD_EINVAL,
                 "fifo_shift: bad dims (B %d, outer %lld, S %d, slot_len %d, inner %lld)", B, (long long)outer, S, slot_len, (long long)inner);
     AVD_REQUIRE((int64_t)S * slot_len <= 0x7fffffff && (int64_t)B * S <= 0x7fffffff, AVD_EINVAL,
@@ -558,16 +581,33 @@ int fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* 
     AVD_REQUIRE(!overlaps(z_in, z_out, total), AVD_EINVAL, "fifo_shift: z_out must not overlap z_in (one out-of-place launch)");
     AVD_REQUIRE(!(popped < z_in + total && z_in < popped + pop) && !(popped < z_out + total && z_out < popped + pop), AVD_EINVAL,
                 "fifo_shift: popped must not overlap z_in or z_out");
-    const bool vec = inner % 4 == 0 && aligned16(z_in) && aligned16(z_out) && aligned16(popped);
+    if (hist_in) {      // five buffers, pairwise apart: slot q reads slot q + 1 of both inputs, across block and sample boundaries
+        AVD_REQUIRE(!overlaps(hist_in, hist_out, total), AVD_EINVAL, "fifo_shift: hist_out must not overlap hist_in (one out-of-place launch)");
+        AVD_REQUIRE(!overlaps(hist_out, z_in, total) && !overlaps(hist_out, z_out, total) && !overlaps(hist_in, z_out, total) &&
+                    !overlaps(hist_in, z_in, total), AVD_EINVAL, "fifo_shift: hist_in and hist_out must not overlap z_in or z_out");
+        AVD_REQUIRE(!(popped < hist_in + total && hist_in < popped + pop) && !(popped < hist_out + total && hist_out < popped + pop), AVD_EINVAL,
+                    "fifo_shift: popped must not overlap hist_in or hist_out");
+    }
+    const bool vec = inner % 4 == 0 && aligned16(z_in) && aligned16(z_out) && aligned16(popped) && aligned16(hist_in) && aligned16(hist_out);
     const int v = vec ? 4 : 1;
     const int64_t n_out = total / v, n_pop = pop / v;
     AVD_REQUIRE((n_out + n_pop + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "fifo_shift: %lld lanes are too many for one launch",
                 (long long)(n_out + n_pop));
     const CanvasKey ck{(uint32_t)(key->seed & 0xffffffffu), (uint32_t)(key->seed >> 32), (uint32_t)c, (uint32_t)slot_len};
-    static const int tags[2] = {prof_tag_id("fifo_shift_kernel<1>"), prof_tag_id("fifo_shift_kernel<4>")};
-    ProfScope prof(tags[vec ? 1 : 0], 4.0 * (2.0 * (double)total + (double)pop), st);      // read + write of the queue, the popped slot's write
+    static const int tags[4] = {prof_tag_id("fifo_shift_kernel<1>"), prof_tag_id("fifo_shift_kernel<4>"),
+                                prof_tag_id("fifo_shift_kernel<1, HistShift>"), prof_tag_id("fifo_shift_kernel<4, HistShift>")};
+    // read + write of the queue (and of the history), the popped slot's write
+    ProfScope prof(tags[(hist_in ? 2 : 0) + (vec ? 1 : 0)], 4.0 * ((hist_in ? 4.0 : 2.0) * (double)total + (double)pop), st);
     const dim3 grid((unsigned)((n_out + n_pop + 255) / 256));
-    if (vec)
+    if (hist_in) {
+        const HistShift hs{hist_in, hist_out};
+        if (vec)
+            hipLaunchKernelGGL((fifo_shift_kernel<4, HistShift>), grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B, outer, S,
+                               slot_len, inner, n_out, n_pop, hs);
+        else
+            hipLaunchKernelGGL((fifo_shift_kernel<1, HistShift>), grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B, outer, S,
+                               slot_len, inner, n_out, n_pop, hs);
+    } else if (vec)
         hipLaunchKernelGGL(fifo_shift_kernel<4>, grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B, outer, S, slot_len, inner,
                            n_out, n_pop);
     else
@@ -1297,7 +1337,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     f32x4 o;
     if constexpr (DPM) {
         const DpmState ds = pack_get<DpmState>(nk...);
-        const Dpm d = dpm_coef(ds.t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, b);
+        const Dpm d = dpm_coef(ds.t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, SLOT ? tb : b);
         f32x4 hist = {0.f, 0.f, 0.f, 0.f}, x0;
         if (d.c_1 != 0.f) hist = *reinterpret_cast<const f32x4*>(ds.x0_hist + lat);
 #pragma unroll
@@ -1366,7 +1406,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     __syncthreads();
     const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, eta, SLOT ? tb : b);
     [[maybe_unused]] Dpm d{0.f, 0.f, 0.f, 0.f};
-    if constexpr (DPM) d = dpm_coef(pack_get<DpmState>(nk...).t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, b);
+    if constexpr (DPM) d = dpm_coef(pack_get<DpmState>(nk...).t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, SLOT ? tb : b);
     [[maybe_unused]] GuideCoef gc{0.f, 0.f, false};
     if constexpr (GUIDED || CGUIDED) gc = guide_coef(abar, T_train, t_prev[b]);
     // token coordinates of the group: n = (t' Ht + h') Wt + w'
@@ -1381,7 +1421,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         const int64_t lat = (int64_t)b * g.per + (((int64_t)cc * g.T + (tq * g.t + tt)) * g.H + (hq * g.h + hh)) * g.W + (wq + tok) * g.w + wo;
         const f32x4 x = *reinterpret_cast<const f32x4*>(z + lat);
         if constexpr (SLOT) {
-            if (hold) {      // z, bit for bit
+            if (hold) {      // z, bit for bit; a DpmState's x0_hist is left alone
                 *reinterpret_cast<f32x4*>(z_out + lat) = x;
                 continue;
             }
@@ -1436,7 +1476,7 @@ struct UpdateArgs {
 // what the kernels' trailing pack is made of: filled by check_fused_update, read by with_update_pack
 struct UpdateKeys {
     bool dpm, seeded, canvas, guide, cguide, ctl;
-    bool slots;        // the slot form: sl is the whole pack (set by check_slot_update after check_fused_update)
+    bool slots;        // the slot form: the pack is sl, or ds then sl for DPM-Solver++(2M) (set by check_slot_update after check_fused_update)
     SlotTimes sl;
     DpmState ds;
     NoiseKey nk;
@@ -1504,28 +1544,31 @@ static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per
 }
 
 // The slot form's checks, before any HIP call: slots == 0 is the per-sample update; otherwise `slots` must be the geometry's S and the
-// update is DDIM at eta == 0 with nothing else in the pack (the scope of "slot timesteps" in include/avdiff_hip.h)
-static int check_slot_update(const char* what, const UpdateArgs& a, int slots, int S, const avd_noise_key* key, const int64_t* t_last,
+// update is DDIM or, with t_last / x0_hist (checked as a pair by check_fused_update; t_last is then a [B, S] table too), DPM-Solver++(2M),
+// at eta == 0 with nothing else in the pack (the scope of "slot timesteps" in include/avdiff_hip.h)
+static int check_slot_update(const char* what, const UpdateArgs& a, int slots, int S, const avd_noise_key* key,
                              const avd_latent_guide* guide, const avd_cfg_control* ctl, int canvas_hop, int guide_hop, UpdateKeys& k) {
     if (!slots) return AVD_OK;
     AVD_REQUIRE(slots == S, AVD_EINVAL, "%s: slots %d must equal the geometry's %d slots along the sliding axis", what, slots, S);
-    AVD_REQUIRE(a.eta == 0.f && !a.noise && !key, AVD_EINVAL, "%s: slot timesteps take the DDIM update at eta == 0 (no noise, no key)", what);
-    AVD_REQUIRE(!t_last && !guide && !ctl && !canvas_hop && !guide_hop, AVD_EINVAL,
-                "%s: slot timesteps take no solver history, latent guide, CFG control or canvas keying", what);
+    AVD_REQUIRE(a.eta == 0.f && !a.noise && !key, AVD_EINVAL, "%s: slot timesteps take the update at eta == 0 (no noise, no key)", what);
+    AVD_REQUIRE(!guide && !ctl && !canvas_hop && !guide_hop, AVD_EINVAL,
+                "%s: slot timesteps take no latent guide, CFG control or canvas keying", what);
     AVD_REQUIRE((int64_t)a.B * S <= 0x7fffffff, AVD_EINVAL, "%s: B %d * slots %d does not fit an int", what, a.B, S);
     k.slots = true;
     k.sl = SlotTimes{S};
     return AVD_OK;
 }
 
-// Calls launch(pack...) with the kernels' whole trailing pack: the solver's state (DpmState, the NoiseKey of a seeded eta > 0 step or
+// Calls launch(pack...) with the kernels' whole trailing pack; the slot form's is SlotTimes, behind the DpmState if there is one.
+// Otherwise: the solver's state (DpmState, the NoiseKey of a seeded eta > 0 step or
 // the CanvasKey of a canvas-keyed one, DpmState then that key for the SDE form, or nothing), then the guide if there is one, then the
 // CFG control if there is one or, for the single-branch form, the CondOnly tag.  A canvas-keyed guide rides in the guide's place, after
 // the solver states that can reach it: none, DpmState, CanvasKey, DpmState then CanvasKey (never a NoiseKey: check_fused_update).
 template <class F>
 static void with_update_pack(const UpdateKeys& k, bool cond_only, F launch) {
     if (k.slots) {
-        launch(k.sl);
+        if (k.dpm) launch(k.ds, k.sl);
+        else launch(k.sl);
         return;
     }
     if (k.cguide) {
@@ -1592,7 +1635,7 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
     const CanvasDims gcv{C, T, guide_hop, (int64_t)H * W};
     if (int rc = check_fused_update("cfg_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
                                     guide_hop ? &gcv : nullptr)) return rc;
-    if (int rc = check_slot_update("cfg_unpatch_ddim", a, slots, T / t, key, t_last, guide, ctl, canvas_hop, guide_hop, k)) return rc;
+    if (int rc = check_slot_update("cfg_unpatch_ddim", a, slots, T / t, key, guide, ctl, canvas_hop, guide_hop, k)) return rc;
     if (ctl && ctl->rescale) {
         AVD_REQUIRE(aligned16(eps2) && aligned16(eps2 + (int64_t)B * g.per), AVD_EUNSUPPORTED,
                     "cfg_unpatch_ddim: the statistics pass reads 16-byte aligned token rows");
@@ -1703,7 +1746,7 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
     }
     if constexpr (DPM) {
         const DpmState ds = pack_get<DpmState>(nk...);
-        const Dpm d = dpm_coef(ds.t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, b);
+        const Dpm d = dpm_coef(ds.t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, SLOT ? tb : b);
         const float x = z[i], x0 = ddim_x0(cf, x, e);
         z_out[i] = fin(dpm_apply(d, x, x0, d.c_1 != 0.f ? ds.x0_hist[i] : 0.f, zn, SEEDED));
         ds.x0_hist[i] = x0;
@@ -1741,7 +1784,7 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
     if (int rc = check_fused_update("cfg_untoken_ddim_audio", a, per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
                                     guide_hop ? &gcv : nullptr)) return rc;
     const AudioGeom ag{Ca, F, len, stride, audio_na(F, len, stride)};
-    if (int rc = check_slot_update("cfg_untoken_ddim_audio", a, slots, ag.Na, key, t_last, guide, ctl, canvas_hop, guide_hop, k)) return rc;
+    if (int rc = check_slot_update("cfg_untoken_ddim_audio", a, slots, ag.Na, key, guide, ctl, canvas_hop, guide_hop, k)) return rc;
     if (ctl && ctl->rescale) {
         const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
         if (int rc = run_cfg_stats<CFG_SRC_AUDIO>(ctl, eps2, eps2 + B * half, half, guidance, B, per, ag, st)) return rc;
@@ -2134,6 +2177,33 @@ extern "C" int avd_cfg_untoken_ddim_audio_slots_f32(const float* eps2, const flo
 extern "C" int avd_fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped, int B,
                                   int64_t outer, int slots, int slot_len, int64_t inner, avd_stream_t stream) {
     return fifo_shift_f32(key, t, c, z_in, z_out, popped, B, outer, slots, slot_len, inner, static_cast<hipStream_t>(stream));
+}
+// the slot forms of the DPM-Solver++(2M) update ("slot timesteps" in the header): t_last, t_now, t_prev are [B, slots] tables
+extern "C" int avd_cfg_unpatch_dpmpp_2m_slots_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                                  const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, int slots,
+                                                  float* x0_hist, float* z_out, int B, int C, int T, int H, int W, int t, int h, int w,
+                                                  avd_stream_t stream) {
+    AVD_REQUIRE(aligned16(eps2) && aligned16(z) && aligned16(z_out), AVD_EUNSUPPORTED,
+                "cfg_unpatch_dpmpp_2m_slots: pointers must be 16-byte aligned");
+    AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_unpatch_dpmpp_2m_slots: slots must be > 0 (got %d)", slots);
+    AVD_REQUIRE(t_last && x0_hist, AVD_EINVAL, "cfg_unpatch_dpmpp_2m_slots: null t_last or x0_hist");
+    return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, 0.f, nullptr, z_out, B, C, T, H, W, t, h, w,
+                                static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots);
+}
+extern "C" int avd_cfg_untoken_dpmpp_2m_audio_slots_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                                        const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance,
+                                                        int slots, float* x0_hist, float* z_out, int B, int Ca, int F, int len, int stride,
+                                                        avd_stream_t stream) {
+    AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_untoken_dpmpp_2m_audio_slots: slots must be > 0 (got %d)", slots);
+    AVD_REQUIRE(t_last && x0_hist, AVD_EINVAL, "cfg_untoken_dpmpp_2m_audio_slots: null t_last or x0_hist");
+    return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, 0.f, nullptr, z_out, B, Ca, F, len, stride,
+                                      static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots);
+}
+extern "C" int avd_fifo_shift_hist_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped,
+                                       const float* hist_in, float* hist_out, int B, int64_t outer, int slots, int slot_len, int64_t inner,
+                                       avd_stream_t stream) {
+    AVD_REQUIRE(hist_in && hist_out, AVD_EINVAL, "fifo_shift_hist: null hist_in or hist_out");
+    return fifo_shift_f32(key, t, c, z_in, z_out, popped, B, outer, slots, slot_len, inner, static_cast<hipStream_t>(stream), hist_in, hist_out);
 }
 extern "C" int avd_cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now,
                                               const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance,

@@ -522,11 +522,12 @@ def canvas_noise(seed: int, t_now: Tensor, shape, hop: int, window_offset: int =
     return out
 
 
-def slot_tables(t_now: Tensor, t_prev: Tensor, B: int, S: int, device: torch.device):
+def slot_tables(t_now: Tensor, t_prev: Tensor, B: int, S: int, device: torch.device, t_last: Optional[Tensor] = None):
     """The [B, S] timestep tables of the slot entries (include/avdiff_hip.h, "slot timesteps") as contiguous int64 device tensors,
-    after the shape check every caller shares."""
+    after the shape check every caller shares: [t_now, t_prev], with ``t_last`` (the multistep solver's third table) behind them when
+    it is given."""
     out = []
-    for name, t in (("t_now", t_now), ("t_prev", t_prev)):
+    for name, t in (("t_now", t_now), ("t_prev", t_prev)) + ((("t_last", t_last),) if t_last is not None else ()):
         t = torch.as_tensor(t)
         if t.is_floating_point() or t.dtype == torch.bool:
             raise TypeError(f"{name} must hold integer timesteps, got {t.dtype}")
@@ -547,9 +548,7 @@ def ddim_step_slots(x_t: Tensor, t_now: Tensor, t_prev: Tensor, eps_hat: Tensor,
         raise RuntimeError("eps_hat must have the shape of x_t")
     _, L_, _ = window_dims(x_t.shape)
     B = x_t.shape[0]
-    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or slot_len > L_:
-        raise ValueError(f"slot_len must be an int in [1, {L_}], got {slot_len!r}")
-    S = L_ // slot_len
+    S = _check_slot_len(slot_len, L_)
     tn, tp = slot_tables(t_now, t_prev, B, S, x_t.device)
     slot = torch.clamp(torch.arange(L_, device=x_t.device) // slot_len, max=S - 1)
     view = (B, 1, L_) + (1,) * (x_t.dim() - 3)
@@ -563,13 +562,60 @@ def ddim_step_slots(x_t: Tensor, t_now: Tensor, t_prev: Tensor, eps_hat: Tensor,
     return out
 
 
-def fifo_shift(z: Tensor, c: int, seed: int, t: int, slot_len: int):
+def _check_slot_len(slot_len, L_: int) -> int:
+    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or slot_len > L_:
+        raise ValueError(f"slot_len must be an int in [1, {L_}], got {slot_len!r}")
+    return L_ // slot_len
+
+
+def dpmpp_2m_step_slots(x_t: Tensor, eps_hat: Tensor, x0_hist: Tensor, t_last: Tensor, t_now: Tensor, t_prev: Tensor,
+                        alpha_bar: Tensor, slot_len: int) -> Tensor:
+    """The elementwise mirror of the slot form of the fused DPM-Solver++(2M) update (include/avdiff_hip.h, "slot timesteps"), built as
+    ``ddim_step_slots``: ``t_last`` / ``t_now`` / ``t_prev`` are int [B, S] tables and every slot takes ``dpmpp_2m_step``
+    (avd_dpmpp_2m_step_f32) with its triple, one launch per distinct triple of the tables, kept on that triple's slots in the returned
+    latent and in ``x0_hist`` (updated in place, as by ``dpmpp_2m_step``).  A slot with t_prev == t_now keeps ``x_t`` and its
+    history bit for bit (the hold)."""
+    x_t = L.dev_f32(x_t, "x_t")
+    eps_hat = L.dev_f32(eps_hat, "eps_hat")
+    if eps_hat.shape != x_t.shape:
+        raise RuntimeError("eps_hat must have the shape of x_t")
+    if not (x0_hist.is_cuda and x0_hist.dtype == torch.float32 and x0_hist.is_contiguous() and x0_hist.shape == x_t.shape):
+        raise RuntimeError("x0_hist must be a contiguous float32 device tensor of x_t's shape (it is updated in place)")
+    _, L_, _ = window_dims(x_t.shape)
+    B = x_t.shape[0]
+    S = _check_slot_len(slot_len, L_)
+    tn, tp, tl = slot_tables(t_now, t_prev, B, S, x_t.device, t_last)
+    slot = torch.clamp(torch.arange(L_, device=x_t.device) // slot_len, max=S - 1)
+    view = (B, 1, L_) + (1,) * (x_t.dim() - 3)
+    tl_l, tn_l, tp_l = (t[:, slot].view(view) for t in (tl, tn, tp))      # the triple of every sliding position
+    out, hist = x_t.clone(), x0_hist.clone()
+    for u, a, p in sorted(set(zip(tl.reshape(-1).tolist(), tn.reshape(-1).tolist(), tp.reshape(-1).tolist()))):
+        if a == p:
+            continue
+        h = x0_hist.clone()
+        full = dpmpp_2m_step(x_t, eps_hat, h, torch.full((B,), u), torch.full((B,), a), torch.full((B,), p), alpha_bar)
+        on = (tl_l == u) & (tn_l == a) & (tp_l == p)
+        out, hist = torch.where(on, full, out), torch.where(on, h, hist)
+    x0_hist.copy_(hist)
+    return out
+
+
+def fifo_shift(z: Tensor, c: int, seed: int, t: int, slot_len: int, hist: Optional[Tensor] = None, hist_out: Optional[Tensor] = None):
     """The queue step of FIFO diagonal denoising (avd_fifo_shift_f32; contract in include/avdiff_hip.h, "FIFO queue shift"): ``z``
     ([B,C,T,H,W] video, [B,Ca,F] audio, sliding length L = S * slot_len) is a queue of B * S slots.  Returns (z_out, popped): z_out
     slot q = z slot q + 1 across sample boundaries, popped = z slot 0 ([C, slot_len, H, W] or [Ca, slot_len]), and the tail slot of
     z_out holds the seeded normals of clip slot ``c`` at timestep ``t`` — ``canvas_noise(seed, [t], one slot's shape, slot_len,
-    window_offset=c)`` bit for bit."""
+    window_offset=c)`` bit for bit.
+    With ``hist`` (float32 on z's device, z's shape: a multistep solver's per-element history, ``x0_hist`` of the slot form of
+    DPM-Solver++(2M)) the same launch carries it along with its slot (avd_fifo_shift_hist_f32) and the result is (z_out, popped,
+    hist_out): hist_out slot q = hist slot q + 1, zeros in the tail slot, the head's history dropped.  ``hist_out``: a buffer to
+    write it to (hist's shape, not overlapping it), None allocates one."""
     z = L.dev_f32(z, "z")
+    if hist is None and hist_out is not None:
+        raise ValueError("hist_out goes with hist")
+    if hist is not None and not (hist.is_cuda and hist.dtype == torch.float32 and hist.is_contiguous() and hist.shape == z.shape and
+                                 hist.device == z.device):
+        raise ValueError(f"hist must be a contiguous float32 tensor of z's shape {tuple(z.shape)} on z's device")
     outer, L_, inner = window_dims(z.shape)
     if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or L_ % slot_len:
         raise ValueError(f"slot_len must be an int >= 1 that divides the sliding length {L_}, got {slot_len!r}")
@@ -581,9 +627,18 @@ def fifo_shift(z: Tensor, c: int, seed: int, t: int, slot_len: int):
     key = noise_key(seed, 0)
     out = torch.empty_like(z)
     popped = torch.empty((z.shape[1], slot_len) + tuple(z.shape[3:]), device=z.device, dtype=torch.float32)
-    L.check(L.lib().avd_fifo_shift_f32(C.byref(key), t, c, z.data_ptr(), out.data_ptr(), popped.data_ptr(), z.shape[0], outer,
-                                       L_ // slot_len, slot_len, inner, _st(z)))
-    return out, popped
+    if hist is None:
+        L.check(L.lib().avd_fifo_shift_f32(C.byref(key), t, c, z.data_ptr(), out.data_ptr(), popped.data_ptr(), z.shape[0], outer,
+                                           L_ // slot_len, slot_len, inner, _st(z)))
+        return out, popped
+    if hist_out is None:
+        hist_out = torch.empty_like(hist)
+    elif not (hist_out.is_cuda and hist_out.dtype == torch.float32 and hist_out.is_contiguous() and hist_out.shape == hist.shape and
+              hist_out.device == hist.device):
+        raise ValueError(f"hist_out must be a contiguous float32 tensor of hist's shape {tuple(hist.shape)} on its device")
+    L.check(L.lib().avd_fifo_shift_hist_f32(C.byref(key), t, c, z.data_ptr(), out.data_ptr(), popped.data_ptr(), hist.data_ptr(),
+                                            hist_out.data_ptr(), z.shape[0], outer, L_ // slot_len, slot_len, inner, _st(z)))
+    return out, popped, hist_out
 
 
 # ---- "bf16x3": fp32-accurate Linear on the bf16 matrix pipe (csrc/gemm_bf16x3.hip) ----

@@ -204,8 +204,9 @@ class DenoiseEngine:
 
     ``step_slots(z, t_now, t_prev)`` (extension: slot timesteps, include/avdiff_hip.h): one (t_now, t_prev) pair per token position
     of the sliding axis ([B, S] tables, S = ``slots`` of ``slot_len`` latent positions) instead of one per sample; a slot with t_prev ==
-    t_now is held.  The primitive of FIFO diagonal denoising (``stream_infer.fifo_denoise``, ``schedule_utils.fifo_plan``).  Solver
-    "ddim" at eta == 0 with the scalar guidance only; ``step``, ``run`` and ``capture_pair`` do not change.
+    t_now is held.  The primitive of FIFO diagonal denoising (``stream_infer.fifo_denoise``, ``schedule_utils.fifo_plan``).  Either
+    solver at eta == 0 with the scalar guidance only: solver "dpmpp_2m" takes a third table ``t_last`` and keeps its history per
+    element in ``x0_hist``, which ``fifo_shift`` moves along with the queue.  ``step``, ``run`` and ``capture_pair`` do not change.
     """
 
     SOLVERS = ("ddim", "dpmpp_2m")
@@ -320,6 +321,7 @@ class DenoiseEngine:
         if solver == "dpmpp_2m":
             self.x0_hist = torch.zeros(self.latent_shape, device=self.device, dtype=torch.float32)
             self._no_hist = torch.full((B,), -1, dtype=torch.long, device=self.device)
+        self._hist_other: Optional[torch.Tensor] = None      # fifo_shift's second history buffer: the shift is out of place
         # latent guide (set_known): the known latent and the mask at fixed addresses, and the avd_latent_guide over them
         self._known: Optional[torch.Tensor] = None
         self._mask: Optional[torch.Tensor] = None
@@ -738,21 +740,29 @@ class DenoiseEngine:
         """S, the slots of one sample (include/avdiff_hip.h, "slot timesteps"): T // tube t (video) or the Na chunks (audio)"""
         return self.latent_shape[2] // self.tube[0] if self.target == "video" else self.embed.Nt
 
-    def step_slots(self, z: torch.Tensor, t_now: torch.Tensor, t_prev: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One CFG + DDIM step on slot timesteps (extension; include/avdiff_hip.h, "slot timesteps"; avd_denoise_step_slots_f32):
+    def step_slots(self, z: torch.Tensor, t_now: torch.Tensor, t_prev: torch.Tensor, out: Optional[torch.Tensor] = None,
+                   t_last: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One CFG step on slot timesteps (extension; include/avdiff_hip.h, "slot timesteps"; avd_denoise_step_slots_f32):
         ``t_now`` / ``t_prev`` are int [B, S] tables, S = ``slots``, one pair per slot of ``slot_len`` latent positions along the
         sliding axis.  Every slot's tokens embed its t_now and its latent takes the DDIM update of its pair; a slot with t_prev ==
         t_now is held (``out`` equals ``z`` there bit for bit) while its tokens still take part in attention.  A table that repeats
         one pair per sample gives ``step``'s bits.  The primitive of FIFO diagonal denoising (stream_infer.fifo_denoise) and of
-        continuing from held clean context.  Scope: solver "ddim" at eta == 0 with the scalar guidance; a latent guide, a CFG
-        control, a window consensus, temb_mode "add" and overlapping audio chunks are refused before anything is launched."""
+        continuing from held clean context.
+        Solver "dpmpp_2m" (avd_denoise_step_slots_dpmpp_2m_f32) needs ``t_last``, a third int [B, S] table: the timestep each slot's
+        previous step started from, < 0 for a first-order step.  A slot's history is the elements of ``x0_hist`` under it: read by its
+        second-order steps, overwritten with its x0, and neither read nor written while the slot is held.
+        Scope: eta == 0 with the scalar guidance; a latent guide, a CFG control, a window consensus, temb_mode "add" and overlapping
+        audio chunks are refused before anything is launched, as is ``t_last`` on a "ddim" engine."""
         if self.Xp is None:
             raise RuntimeError("call set_prompt() first")
         if self.eta > 0:
             raise ValueError("step_slots needs eta == 0: slots at different timesteps have no common noise stream yet (eta > 0 is out "
                              "of scope)")
-        if self.solver != "ddim":
-            raise ValueError(f"step_slots runs solver 'ddim': the multistep history of solver {self.solver!r} is per sample")
+        if self.solver == "ddim" and t_last is not None:
+            raise ValueError("t_last is the multistep solver's history: this engine runs solver 'ddim'")
+        if self.solver != "ddim" and t_last is None:
+            raise ValueError(f"step_slots on solver {self.solver!r} needs t_last, the [B, S] table of the timesteps each slot's history "
+                             "comes from (-1: none)")
         if self._guide is not None:
             raise ValueError("step_slots takes no latent guide (its forward path is keyed by one t_prev per sample): clear_known() first")
         if self._ctl is not None:
@@ -769,18 +779,45 @@ class DenoiseEngine:
         if tuple(z.shape) != self.latent_shape:
             raise ValueError(f"latent shape {tuple(z.shape)} != engine shape {self.latent_shape}")
         S = self.slots
-        tn, tp = Fn.slot_tables(t_now, t_prev, self.embed.B, S, self.device)
+        tn, tp, *tl = Fn.slot_tables(t_now, t_prev, self.embed.B, S, self.device, t_last)
         if out is None:
             out = torch.empty_like(z)
         elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == z.shape and out.device == z.device):
             raise ValueError(f"out must be a contiguous float32 tensor of shape {tuple(z.shape)} on z's device")
+        if tl:
+            for name, t in (("z", z), ("out", out)):
+                if t.untyped_storage().data_ptr() == self.x0_hist.untyped_storage().data_ptr():
+                    raise L.AvdError(f"{name} must not alias the engine's x0_hist (the solver history)")
         if not torch.cuda.is_current_stream_capturing():
             self._sync_weights()
         self._last_cond_only = False
-        L.check(L.lib().avd_denoise_step_slots_f32(C.byref(self.desc), z.data_ptr(), self.Xp.data_ptr(), tn.data_ptr(), tp.data_ptr(), S,
-                                                   out.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
-                                                   L.stream_ptr(self.device)))
+        head = (C.byref(self.desc), z.data_ptr(), self.Xp.data_ptr())
+        tail = (out.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device))
+        if tl:
+            L.check(L.lib().avd_denoise_step_slots_dpmpp_2m_f32(*head, tl[0].data_ptr(), tn.data_ptr(), tp.data_ptr(), S,
+                                                                self.x0_hist.data_ptr(), *tail))
+        else:
+            L.check(L.lib().avd_denoise_step_slots_f32(*head, tn.data_ptr(), tp.data_ptr(), S, *tail))
         return out
+
+    def fifo_shift(self, z: torch.Tensor, c: int, t: int, seed: Optional[int] = None):
+        """The queue step of FIFO diagonal denoising on this engine's queue (``functional.fifo_shift`` with the engine's ``slot_len``;
+        ``seed``: the seed of the entering slot's noise, None = the engine's ``noise_seed``): returns (z_out, popped).  Solver "dpmpp_2m": the same launch shifts the history into a
+        second engine-owned buffer, which becomes ``x0_hist`` (the head's history is dropped, the entering slot's is zero): a slot
+        keeps its history as it moves up the queue.  That changes an address a captured graph holds, so it starts a new graph
+        generation."""
+        seed = self.noise_seed if seed is None else seed
+        if seed is None:
+            raise ValueError("fifo_shift draws the entering slot's noise from a seed: pass one, or build the engine with noise_seed")
+        if self.solver != "dpmpp_2m":
+            return Fn.fifo_shift(z, c, seed, t, self.slot_len)
+        if self._hist_other is None:
+            self._hist_other = torch.empty_like(self.x0_hist)
+        z_out, popped, _ = Fn.fifo_shift(z, c, seed, t, self.slot_len, hist=self.x0_hist, hist_out=self._hist_other)
+        self.x0_hist, self._hist_other = self._hist_other, self.x0_hist
+        self._generation += 1
+        self._stale_reason = "fifo_shift moved the solver history into the engine's other history buffer (x0_hist changed its address)"
+        return z_out, popped
 
     def eps_tokens(self) -> torch.Tensor:
         """ε̂ tokens left in the workspace by the last step (debug / parity only): cond / null [2B,Nt,D] after a CFG step; after a

@@ -222,6 +222,25 @@ def fifo_plan(sched, S: int):
     return ramp_now.view(n - 1, B, S), ramp_prev.view(n - 1, B, S), steady_now.view(B, S).clone(), steady_prev.view(B, S).clone()
 
 
+def fifo_plan_last(sched, S: int):
+    """The third table of ``fifo_plan`` for a multistep solver (``DenoiseEngine.step_slots(t_last=)`` on solver "dpmpp_2m"): where a
+    slot takes step i its t_last is s_{i-1}, the timestep its previous step started from and its history's; a slot taking step 0 has
+    -1 (first order), and so has a held slot (it is not read there).  Returns (ramp_last [n-1, B, S], steady_last [B, S]), int64 CPU
+    tensors in ``fifo_plan``'s layout, which also refuses what this refuses.  In the steady state the tail slot (step 0) is first
+    order, so the history of a slot entering the queue is never read."""
+    ramp_now, ramp_prev, steady_now, _ = fifo_plan(sched, S)
+    n = ramp_now.shape[0] + 1
+    s = torch.as_tensor(sched).reshape(-1).to("cpu", torch.long)
+    last = torch.cat([torch.tensor([-1]), s[:n - 1]])                  # last[i] = s_{i-1}
+    q = torch.arange(n)
+    steady_last = last[n - 1 - q].view_as(steady_now).clone()
+    r = torch.arange(n - 1)[:, None]
+    live = q[None, :] <= r
+    i = (r - q[None, :]).clamp(min=0)
+    ramp_last = torch.where(live, last[i], torch.full((n - 1, n), -1, dtype=torch.long))
+    return ramp_last.view_as(ramp_now).clone(), steady_last
+
+
 def resample_from_config(scfg) -> Optional[Tuple[int, int]]:
     """``sampling.resample`` of a config: {jump:, resamples:}; a missing key or None means no resampling."""
     return check_resample(scfg.get("resample"))

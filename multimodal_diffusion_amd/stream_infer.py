@@ -223,7 +223,11 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     ``prompt_canvas`` is the prompt modality's latent along its sliding axis and ``prompt_hop`` its positions per target slot: before
     the step of steady iteration m (the ramp: m = 0) sample k is conditioned on ``fifo_prompt_windows(prompt_canvas, m, ...)[k]``,
     the prompt under the clip slots the sample holds (``set_prompt`` into the same buffer).  The loop is eager.  The engine's limits
-    are ``step_slots``'s (solver "ddim", eta == 0, no guide / control / consensus)."""
+    are ``step_slots``'s (eta == 0, no guide / control / consensus).
+    The driver follows ``engine.solver``.  "dpmpp_2m" adds the ``t_last`` tables (``schedule_utils.fifo_plan_last``) and shifts with
+    ``engine.fifo_shift``, which carries every slot's history along with it; ``x0_hist`` needs no initialisation, every slot's first
+    step being first order.  The queue is as long as the schedule, so the faster solver's shorter schedule also means a shorter
+    queue, a shorter ramp and fewer sample-steps per finished slot."""
     if not isinstance(engine, DenoiseEngine):
         raise TypeError("fifo_denoise drives a DenoiseEngine")
     if isinstance(n_slots, bool) or not isinstance(n_slots, int) or n_slots < 1:
@@ -244,17 +248,19 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     Lp = fifo_prompt_len(engine, prompt_canvas)
     pc = L.dev_f32(prompt_canvas.to(dev), "prompt canvas")
     tabs = [t.to(dev) for t in (ramp_now, ramp_prev, steady_now, steady_prev)]
+    multistep = engine.solver == "dpmpp_2m"
+    ramp_last, steady_last = (t.to(dev) for t in su.fifo_plan_last(sched, S)) if multistep else (None, None)
     z = Fn.canvas_noise(noise_seed, torch.full((B,), s0, dtype=torch.long, device=dev), engine.latent_shape, L_)
     other = torch.empty_like(z)
     engine.set_prompt(fifo_prompt_windows(pc, 0, B, S, prompt_hop, Lp))
     for r in range(n - 1):
-        z, other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other), z
+        z, other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other, t_last=ramp_last[r] if multistep else None), z
     canvas = torch.empty((outer, n_slots * sl) + tuple(engine.latent_shape[3:]), device=dev, dtype=torch.float32)
     for m in range(n_slots):
         if m:
             engine.set_prompt(fifo_prompt_windows(pc, m, B, S, prompt_hop, Lp))
-        other = engine.step_slots(z, tabs[2], tabs[3], out=other)
-        z, popped = Fn.fifo_shift(other, n + m, noise_seed, s0, sl)
+        other = engine.step_slots(z, tabs[2], tabs[3], out=other, t_last=steady_last)
+        z, popped = engine.fifo_shift(other, n + m, s0, seed=noise_seed)
         canvas[:, m * sl:(m + 1) * sl] = popped
     return canvas
 

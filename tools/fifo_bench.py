@@ -7,7 +7,14 @@
   --e2e       finished latent slots per second of stream_infer.fifo_denoise (n = 48 steps, S = 6, B = 8) next to the window-consensus
               loop at the same step count, and the share of a steady iteration spent in set_prompt and the shift
 
-Prints plain text: the records are profiles/fifo_kernels.txt and profiles/fifo_e2e.txt."""
+  --solver    ddim (default) or dpmpp_2m.  With dpmpp_2m, --kernels times the fused DPM-Solver++(2M) update inside whole steps
+              (DenoiseEngine.step against step_slots(t_last=): no entry runs the per-sample CFG form alone) and the queue shift with
+              history against the plain one; --e2e runs fifo_denoise on a dpmpp_2m engine at --steps (default 18: the multiple of S = 6
+              nearest to 20; ddim: 48) and prints the time per finished slot and the ramp time
+  --steps     --e2e: n, the schedule's steps = the queue's slots (a multiple of S = 6)
+
+Prints plain text: the records are profiles/fifo_kernels.txt and profiles/fifo_e2e.txt (ddim), profiles/fifo_dpm_kernels.txt and
+profiles/fifo_dpm_e2e.txt (both solvers in one session)."""
 import argparse
 import ctypes as C
 import statistics
@@ -33,13 +40,16 @@ ap.add_argument("--e2e", action="store_true")
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--launches", type=int, default=50)
 ap.add_argument("--slots-out", type=int, default=24, help="--e2e: finished slots per timed fifo_denoise call")
+ap.add_argument("--solver", choices=("ddim", "dpmpp_2m"), default="ddim")
+ap.add_argument("--steps", type=int, default=None, help="--e2e: steps of the schedule = slots of the queue (default 48, dpmpp_2m: 18)")
 args = ap.parse_args()
+DPM = args.solver == "dpmpp_2m"
 
 dev = torch.device("cuda:0")
 ABAR = R.alpha_bar_table(R.beta_table(1000))
 
 
-def build(n_layers, B, target="video"):
+def build(n_layers, B, target="video", solver="ddim"):
     ws = R.synth_weights(seed=0, n_layers=n_layers)
     core = A.MMDiT(d_model=512, n_layers=n_layers, n_heads=8, mlp_ratio=4.0).eval()
     core.load_state_dict(ws["core"], strict=True)
@@ -50,7 +60,7 @@ def build(n_layers, B, target="video"):
     aa.load_state_dict(ws["adapt_a"])
     core, head, av, aa = (m.to(dev) for m in (core, head, av, aa))
     return A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target=target,
-                           latent_shape=(B, 8, 12, 32, 32), prompt_tokens=37, alpha_bar=ABAR, guidance=3.5, matmul="bf16x3")
+                           latent_shape=(B, 8, 12, 32, 32), prompt_tokens=37, alpha_bar=ABAR, guidance=3.5, matmul="bf16x3", solver=solver)
 
 
 def per_launch_us(tag, fn, launches):
@@ -67,7 +77,55 @@ def per_launch_us(tag, fn, launches):
     return 1e3 * ms / n
 
 
-if args.kernels:
+def report_shift(res, cases):
+    for name, zz, streams in cases:
+        nbytes = 4 * (streams * zz.numel() + zz[0, :, :2].numel())
+        us = statistics.median(res[name])
+        print(f"  {name}: {nbytes / 1e6:.2f} MB read + written, {nbytes / us / 1e3:.1f} GB/s ({nbytes / us:.0f} bytes per microsecond)")
+
+
+if args.kernels and DPM:
+    B, S = 32, 6
+    eng = build(2, B, solver="dpmpp_2m")
+    g = torch.Generator().manual_seed(0)
+    z = torch.randn(B, 8, 12, 32, 32, generator=g).to(dev)
+    eng.set_prompt(torch.randn(B, 8, 150, generator=g).to(dev))
+    eng.x0_hist.copy_(torch.randn(B, 8, 12, 32, 32, generator=g))
+    out = torch.empty_like(z)
+    sched = su.make_sampling_schedule(1000, 18)
+    tl1, tn1, tp1 = (torch.full((B,), int(v), dtype=torch.long, device=dev) for v in (sched[5], sched[6], sched[7]))      # second order
+    i = (torch.arange(B * S) % 16).view(B, S) + 1                              # the diagonal: second-order triples, one per slot
+    tlS, tnS, tpS = (sched[i + d].to(dev).contiguous() for d in (-1, 0, 1))
+    tnH, tpH = tnS.clone(), tpS.clone()
+    tpH[:, S // 2:] = tnH[:, S // 2:]                                          # half of every sample held
+    zq = torch.randn(3, 8, 12, 32, 32, generator=g).to(dev)                    # the e2e queue at n = 18: B = 3
+    hq = torch.randn(3, 8, 12, 32, 32, generator=g).to(dev)
+    hz = eng.x0_hist.clone()
+    TAG = "cfg_unpatch_ddim_kernel"
+    rows = [("DPM update per-sample (a)", TAG, lambda: eng.step(z, tn1, tp1, out=out, t_last=tl1)),
+            ("DPM update slots, diagonal", TAG, lambda: eng.step_slots(z, tnS, tpS, out=out, t_last=tlS)),
+            ("DPM update per-sample (b)", TAG, lambda: eng.step(z, tn1, tp1, out=out, t_last=tl1)),
+            ("DPM update slots, half held", TAG, lambda: eng.step_slots(z, tnH, tpH, out=out, t_last=tlS)),
+            ("fifo_shift B=32", "fifo_shift_kernel<4>", lambda: Fn.fifo_shift(z, 192, 7, 999, 2)),
+            ("fifo_shift+hist B=32", "fifo_shift_kernel<4, HistShift>", lambda: Fn.fifo_shift(z, 192, 7, 999, 2, hist=hz)),
+            ("fifo_shift B=3", "fifo_shift_kernel<4>", lambda: Fn.fifo_shift(zq, 18, 7, 999, 2)),
+            ("fifo_shift+hist B=3", "fifo_shift_kernel<4, HistShift>", lambda: Fn.fifo_shift(zq, 18, 7, 999, 2, hist=hq))]
+    for _, _, fn in rows:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    res = {name: [] for name, _, _ in rows}
+    for _ in range(args.rounds):
+        for name, tag, fn in rows:
+            res[name].append(per_launch_us(tag, fn, args.launches))
+    print(f"C3 geometry, B = {B}, the fused CFG + un-patch + DPM-Solver++(2M) update inside whole steps (2 layers) and the queue shifts: "
+          f"{args.rounds} interleaved rounds of {args.launches} launches, microseconds per launch (launch events)")
+    for name, _, _ in rows:
+        v = res[name]
+        print(f"  {name:28s} " + " ".join(f"{x:8.2f}" for x in v) + f"   median {statistics.median(v):8.2f}")
+    report_shift(res, (("fifo_shift B=32", z, 2), ("fifo_shift+hist B=32", z, 4), ("fifo_shift B=3", zq, 2), ("fifo_shift+hist B=3", zq, 4)))
+
+if args.kernels and not DPM:
     B, S = 32, 6
     eng = build(2, B)
     g = torch.Generator().manual_seed(0)
@@ -126,15 +184,16 @@ if args.kernels:
     for name, _, _ in rows:
         v = res[name]
         print(f"  {name:28s} " + " ".join(f"{x:8.2f}" for x in v) + f"   median {statistics.median(v):8.2f}")
-    for name, zz in (("fifo_shift B=32", z), ("fifo_shift B=8", zq)):
-        nbytes = 4 * (2 * zz.numel() + zz[0, :, :2].numel())
-        us = statistics.median(res[name])
-        print(f"  {name}: {nbytes / 1e6:.2f} MB read + written, {nbytes / us / 1e6:.2f} TB/s ({nbytes / us:.0f} bytes per microsecond)")
+    report_shift(res, (("fifo_shift B=32", z, 2), ("fifo_shift B=8", zq, 2)))
 
 if args.e2e:
-    n, S, B, K = 48, 6, 8, args.slots_out
+    S, K = 6, args.slots_out
+    n = args.steps or (18 if DPM else 48)
+    if n % S:
+        raise SystemExit(f"--steps {n} must be a multiple of S = {S}")
+    B = n // S
     sched = su.make_sampling_schedule(1000, n)
-    eng = build(8, B)
+    eng = build(8, B, solver=args.solver)
     g = torch.Generator().manual_seed(1)
     canvas_p = torch.randn(8, 25 * (n + 2 * K) + 148, generator=g).to(dev)      # 25 audio latent frames per target slot of 2 latent frames
     hop_p = 25
@@ -147,27 +206,36 @@ if args.e2e:
         return time.perf_counter() - t0, r
 
     A.fifo_denoise(eng, canvas_p, hop_p, sched, 2, 5)                        # warm-up
-    print(f"fifo_denoise: n = {n} steps, S = {S}, B = {B} (C3 latent, 8 layers, bf16x3, eager), {args.rounds} rounds")
+    print(f"fifo_denoise: solver {args.solver}, n = {n} steps, S = {S}, B = {B} (C3 latent, 8 layers, bf16x3, eager), {args.rounds} rounds")
+    whole = {}
     for K_ in (K, 2 * K):
         ts_ = [timed(lambda: A.fifo_denoise(eng, canvas_p, hop_p, sched, K_, 5))[0] for _ in range(args.rounds)]
+        whole[K_] = statistics.median(ts_)
         print(f"  {K_:3d} slots out: " + " ".join(f"{t * 1e3:8.1f}" for t in ts_) + f" ms   ({K_ / statistics.median(ts_):6.1f} slots/s whole call, "
               f"ramp of {n - 1} steps included)")
+    # two clip lengths separate the two costs: the difference is K steady iterations, the rest of the shorter call is the ramp
+    per_slot = (whole[2 * K] - whole[K]) / K
+    print(f"  per finished slot (steady state, from the two clip lengths): {per_slot * 1e3:.3f} ms; ramp of {n - 1} steps: "
+          f"{(whole[K] - K * per_slot) * 1e3:.1f} ms")
     # the parts of a steady iteration, each ended by a synchronise
     rn, rp, sn, sp = (t.to(dev) for t in su.fifo_plan(sched, S))
+    sl = su.fifo_plan_last(sched, S)[1].to(dev) if DPM else None
     Lp = fifo_prompt_len(eng, canvas_p)
     z = Fn.canvas_noise(5, torch.full((B,), int(sched[0])), eng.latent_shape, 12)
     parts = {"set_prompt": [], "step_slots": [], "fifo_shift": []}
     for m in range(3 * args.rounds * 4):
         t, _ = timed(lambda: eng.set_prompt(fifo_prompt_windows(canvas_p, m, B, S, hop_p, Lp)))
         parts["set_prompt"].append(t)
-        t, zo = timed(lambda: eng.step_slots(z, sn, sp))
+        t, zo = timed(lambda: eng.step_slots(z, sn, sp, t_last=sl))
         parts["step_slots"].append(t)
-        t, (z, _) = timed(lambda: Fn.fifo_shift(zo, n + m, 5, int(sched[0]), 2))
+        t, (z, _) = timed(lambda: eng.fifo_shift(zo, n + m, int(sched[0]), seed=5))
         parts["fifo_shift"].append(t)
     med = {k: statistics.median(v[4:]) for k, v in parts.items()}
     tot = sum(med.values())
     print("  steady iteration (one finished slot), parts timed with a synchronise after each: " +
           ", ".join(f"{k} {v * 1e3:.3f} ms ({100 * v / tot:.1f} %)" for k, v in med.items()) + f"; {1 / tot:.1f} slots/s steady state")
+    if DPM:
+        sys.exit(0)
     # the window-consensus loop at the same step count: 8 windows of 12 latent frames, hop 4 (the 3 s / 1 s default): a canvas of 40
     # latent frames = 20 slots of 2 frames
     engc = build(8, B)
