@@ -324,6 +324,40 @@ int avd_fifo_shift_hist_f32(const avd_noise_key* key, int64_t t, int64_t c, cons
                             const float* hist_in, float* hist_out, int B, int64_t outer, int slots, int slot_len, int64_t inner,
                             avd_stream_t stream);
 
+/* ---- FIFO device cursors: the three host numbers of a FIFO iteration moved onto the device, so that a whole iteration is a fixed
+ * chain of launches a HIP graph can hold.  A cursor is one int32 in device memory.  No entry below addresses by a cursor without the
+ * clamp or the guard its contract names, so no cursor value makes a kernel leave its buffers; every entry only READS its cursor, and
+ * avd_cursor_add moves it in a launch of its own, behind the last launch of the iteration that reads it. */
+/* *cursor += delta, one launch of one thread on `stream`. */
+int avd_cursor_add(int32_t* cursor, int delta, avd_stream_t stream);
+/* Slot-table select, the slot analogue of avd_sched_advance / avd_sched_advance_ms: tab0, tab1 (and tab2, or null with out2 null) are
+ * [n_rows, n] int64 tables (n = B*slots: the ramp rows of a FIFO plan, t_now / t_prev / t_last); one launch copies row
+ * min(max(*cursor, 0), n_rows - 1) of each into its fixed [n] buffer out0, out1 (, out2).  The clamp is the guard: any cursor reads a
+ * row of the tables.  Checked (AVD_EINVAL): n_rows >= 1, n >= 1, non-null pointers, tab2 and out2 both set or both null. */
+int avd_slot_tables_select(const int64_t* tab0, const int64_t* tab1, const int64_t* tab2, int n_rows, int n, const int32_t* cursor,
+                           int64_t* out0, int64_t* out1, int64_t* out2, avd_stream_t stream);
+/* Prompt gather: out [B, outer, prompt_len, inner] from the prompt canvas [outer, P, inner] (audio [Ca, P]: inner = 1; video
+ * [C, P, H, W]: inner = H*W).  With m = max(*cursor, 0), out[k, o, l, i] = canvas[o, (m + k*slots)*prompt_hop + l, i] where that
+ * position is < P and 0 beyond the canvas end: a position is compared with P before it is read, so any cursor stays inside the canvas.
+ * All index arithmetic is 64-bit.  16-byte lanes when inner % 4 == 0 and both bases are 16-byte aligned, one element per lane otherwise;
+ * same bits either way.  Checked (AVD_EINVAL): positive dims, B*slots and prompt_len fit an int, out does not overlap the canvas. */
+int avd_fifo_prompt_gather_f32(const float* canvas, const int32_t* cursor, float* out, int B, int slots, int prompt_hop, int64_t outer,
+                               int64_t P, int64_t prompt_len, int64_t inner, avd_stream_t stream);
+/* FIFO queue shift off a device cursor: (z_in -> z_out) is avd_fifo_shift_f32's with c = c0 + *cursor, the same kernel body and the
+ * same bits (c only keys the tail's noise draw, modulo 2^32: it addresses nothing).  The finished head is written straight into slot
+ * *cursor of the clip canvas clip [outer, n_out*slot_len, inner] — clip[o, *cursor*slot_len + j, i] = z_in slot 0 [o, j, i], a strided
+ * write, no popped buffer.  The guard: when *cursor is outside [0, n_out) the head is written nowhere; the queue still shifts.
+ * Checked before the launch (AVD_EINVAL): c0 >= 0, n_out >= 1 and (c0 + n_out)*slot_len <= 2^32; z_in, z_out and the clip canvas
+ * must not overlap one another; the other checks are avd_fifo_shift_f32's.  16-byte lanes when inner % 4 == 0 and all bases are
+ * 16-byte aligned, one element per lane otherwise; same bits either way. */
+int avd_fifo_shift_cursor_f32(const avd_noise_key* key, int64_t t, int64_t c0, const int32_t* cursor, int64_t n_out, const float* z_in,
+                              float* z_out, float* clip, int B, int64_t outer, int slots, int slot_len, int64_t inner, avd_stream_t stream);
+/* As avd_fifo_shift_cursor_f32 with the history pair of avd_fifo_shift_hist_f32 (hist_out slot q = hist_in slot q + 1, zeros in the
+ * tail); the five buffers, the clip canvas among them, must not overlap one another. */
+int avd_fifo_shift_cursor_hist_f32(const avd_noise_key* key, int64_t t, int64_t c0, const int32_t* cursor, int64_t n_out,
+                                   const float* z_in, float* z_out, float* clip, const float* hist_in, float* hist_out, int B,
+                                   int64_t outer, int slots, int slot_len, int64_t inner, avd_stream_t stream);
+
 /* ---- latent guide: inpainting / outpainting and SDEdit over a known clean latent (a public contract).
  * Per sample b of a call, with x_k = known[b] and m = the mask, both in the latent's natural layout ([C,T,H,W] video, [Ca,F] audio,
  * row-major; element e as in avd_noise_key), and a(tau) = alpha_bar[clamp(tau, 0, T_train-1)] for tau >= 0, 1 for tau < 0:

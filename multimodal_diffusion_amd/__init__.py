@@ -8,7 +8,7 @@ from . import adapters, ops, schedule_utils, schedules   # noqa: F401
 from .adapters import TimestepCfg, TimestepEmbedder      # noqa: F401
 from .mmdt import MMDiT, Block, MHA, MLP, RMSNorm      # noqa: F401
 from .noise_heads import MultiModalNoiseHead           # noqa: F401
-from .sampler import (DenoiseEngine, LinearAdapter, add_sinusoidal_timestep, build_components,   # noqa: F401
+from .sampler import (DenoiseEngine, FifoQueue, LinearAdapter, add_sinusoidal_timestep, build_components,   # noqa: F401
                       latents_to_tokens_audio, latents_to_tokens_video, sample_one_direction, frame_mask, canvas_frame_mask,
                       tokens_to_latents_audio)
 from .stream_infer import fifo_denoise                                 # noqa: F401

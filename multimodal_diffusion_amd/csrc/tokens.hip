@@ -510,10 +510,19 @@ struct HistShift {
     const float* in;
     float* out;
 };
+// A CursorShift in the pack ("FIFO queue shift off a device cursor") takes the clip slot from the device: c = ck.w0 + *m, and `popped`
+// is the clip canvas [outer, n_slots * slot_len, inner], whose slot *m receives the head (a strided write); *m outside [0, n_slots)
+// writes no head.  The cursor is only read here: it moves in a launch of its own (cursor_add_kernel).
+struct CursorShift {
+    const int32_t* m;
+    int64_t n_slots;
+};
 template <int V, class... Hist>
 __global__ __launch_bounds__(256) void fifo_shift_kernel(const float* __restrict__ z_in, float* __restrict__ z_out,
                                                          float* __restrict__ popped, CanvasKey ck, uint32_t t, int B, int64_t outer, int S,
                                                          int slot_len, int64_t inner, int64_t n_out, int64_t n_pop, Hist... hs) {
+    constexpr bool HIST = PackHas<HistShift, Hist...>::value, CURSOR = PackHas<CursorShift, Hist...>::value;
+    static_assert(sizeof...(Hist) == (HIST ? 1 : 0) + (CURSOR ? 1 : 0), "the pack: optionally one HistShift, then optionally one CursorShift");
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= n_out + n_pop) return;
     const int64_t iv = inner / V;
@@ -525,7 +534,14 @@ __global__ __launch_bounds__(256) void fifo_shift_kernel(const float* __restrict
         const int j = (int)(r % slot_len);
         const int64_t o = r / slot_len;
         const float* src = z_in + (o * L + j) * inner + i;
-        if constexpr (V == 4) *reinterpret_cast<f32x4*>(popped + k * 4) = *reinterpret_cast<const f32x4*>(src);
+        if constexpr (CURSOR) {      // clip[o, m * slot_len + j, i], guarded: a cursor outside the clip writes nothing
+            const CursorShift cs = pack_get<CursorShift>(hs...);
+            const int64_t m = *cs.m;
+            if (m < 0 || m >= cs.n_slots) return;
+            float* dst = popped + ((o * cs.n_slots + m) * slot_len + j) * inner + i;
+            if constexpr (V == 4) *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(src);
+            else *dst = *src;
+        } else if constexpr (V == 4) *reinterpret_cast<f32x4*>(popped + k * 4) = *reinterpret_cast<const f32x4*>(src);
         else popped[k] = *src;
         return;
     }
@@ -543,17 +559,18 @@ __global__ __launch_bounds__(256) void fifo_shift_kernel(const float* __restrict
         const float* src = z_in + so;
         if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = *reinterpret_cast<const f32x4*>(src);
         else z_out[idx] = *src;
-        if constexpr (sizeof...(Hist) != 0) {
-            const HistShift h = HistShift(hs...);
+        if constexpr (HIST) {
+            const HistShift h = pack_get<HistShift>(hs...);
             if constexpr (V == 4) *reinterpret_cast<f32x4*>(h.out + idx * 4) = *reinterpret_cast<const f32x4*>(h.in + so);
             else h.out[idx] = h.in[so];
         }
     } else {                 // the tail slot: fresh noise of clip slot c
+        if constexpr (CURSOR) ck.w0 += (uint32_t)*pack_get<CursorShift>(hs...).m;      // c = c0 + *m: it keys the draw, it addresses nothing
         const f32x4 v = canvas_normal4(ck, 0, o, j, i, inner, t);
         if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = v;
         else z_out[idx] = v[(int)((o * inner + i) & 3)];
-        if constexpr (sizeof...(Hist) != 0) {      // no history yet: zeros (never read: the tail's t_last is -1)
-            const HistShift h = HistShift(hs...);
+        if constexpr (HIST) {      // no history yet: zeros (never read: the tail's t_last is -1)
+            const HistShift h = pack_get<HistShift>(hs...);
             if constexpr (V == 4) *reinterpret_cast<f32x4*>(h.out + idx * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
             else h.out[idx] = 0.f;
         }
@@ -561,8 +578,11 @@ __global__ __launch_bounds__(256) void fifo_shift_kernel(const float* __restrict
 }
 
 // hist_in / hist_out: both null (the plain shift) or both set (the shift with history: hist_out slot q = hist_in slot q + 1, zeros in the tail)
+// cursor: null = the by-value shift (clip slot c, `popped` one slot).  Set = the shift off a device cursor: c is c0, the kernel takes
+// clip slot c0 + *cursor, and `popped` is the clip canvas [outer, n_clip * slot_len, inner]
 int fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped, int B, int64_t outer,
-                   int S, int slot_len, int64_t inner, hipStream_t st, const float* hist_in = nullptr, float* hist_out = nullptr) {
+                   int S, int slot_len, int64_t inner, hipStream_t st, const float* hist_in = nullptr, float* hist_out = nullptr,
+                   const int32_t* cursor = nullptr, int64_t n_clip = 1) {
     AVD_REQUIRE(key, AVD_EINVAL, "fifo_shift: null noise key");
     AVD_REQUIRE(z_in && z_out && popped, AVD_EINVAL, "fifo_shift: null pointer");
     AVD_REQUIRE(!hist_in == !hist_out, AVD_EINVAL, "fifo_shift: hist_in and hist_out go together");
@@ -572,21 +592,28 @@ int fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* 
                 "fifo_shift: S %d * slot_len %d and B %d * S must fit an int", S, slot_len, B);
     AVD_REQUIRE(t >= 0 && t < ((int64_t)1 << 32), AVD_EINVAL, "fifo_shift: the noise timestep %lld must lie in [0, 2^32)", (long long)t);
     const int64_t lim = (int64_t)1 << 32;
-    AVD_REQUIRE(c >= 0 && c < lim && c + 1 <= lim / slot_len, AVD_EINVAL, "fifo_shift: (c %lld + 1) * slot_len %d must lie in [1, 2^32]",
-                (long long)c, slot_len);
+    if (cursor)      // every clip slot the cursor can name inside the clip: c0 .. c0 + n_clip - 1
+        AVD_REQUIRE(c >= 0 && c < lim && n_clip >= 1 && n_clip <= lim && c + n_clip <= lim / slot_len, AVD_EINVAL,
+                    "fifo_shift: (c0 %lld + n_out %lld) * slot_len %d must lie in [1, 2^32]", (long long)c, (long long)n_clip, slot_len);
+    else
+        AVD_REQUIRE(c >= 0 && c < lim && c + 1 <= lim / slot_len, AVD_EINVAL, "fifo_shift: (c %lld + 1) * slot_len %d must lie in [1, 2^32]",
+                    (long long)c, slot_len);
     AVD_REQUIRE(outer <= (((int64_t)1 << 34) - 1) / inner, AVD_EINVAL, "fifo_shift: outer %lld * inner %lld must be < 2^34", (long long)outer,
                 (long long)inner);
     AVD_REQUIRE((double)B * (double)outer * (double)S * (double)slot_len * (double)inner < 9.0e18, AVD_EUNSUPPORTED, "fifo_shift: too many values");
+    AVD_REQUIRE((double)outer * (double)n_clip * (double)slot_len * (double)inner < 9.0e18, AVD_EUNSUPPORTED, "fifo_shift: too large a clip canvas");
     const int64_t total = (int64_t)B * outer * S * slot_len * inner, pop = outer * slot_len * inner;
+    const int64_t dst = pop * n_clip;      // what `popped` spans: one slot, or the clip canvas
+    const char* pname = cursor ? "the clip canvas" : "popped";
     AVD_REQUIRE(!overlaps(z_in, z_out, total), AVD_EINVAL, "fifo_shift: z_out must not overlap z_in (one out-of-place launch)");
-    AVD_REQUIRE(!(popped < z_in + total && z_in < popped + pop) && !(popped < z_out + total && z_out < popped + pop), AVD_EINVAL,
-                "fifo_shift: popped must not overlap z_in or z_out");
+    AVD_REQUIRE(!(popped < z_in + total && z_in < popped + dst) && !(popped < z_out + total && z_out < popped + dst), AVD_EINVAL,
+                "fifo_shift: %s must not overlap z_in or z_out", pname);
     if (hist_in) {      // five buffers, pairwise apart: slot q reads slot q + 1 of both inputs, across block and sample boundaries
         AVD_REQUIRE(!overlaps(hist_in, hist_out, total), AVD_EINVAL, "fifo_shift: hist_out must not overlap hist_in (one out-of-place launch)");
         AVD_REQUIRE(!overlaps(hist_out, z_in, total) && !overlaps(hist_out, z_out, total) && !overlaps(hist_in, z_out, total) &&
                     !overlaps(hist_in, z_in, total), AVD_EINVAL, "fifo_shift: hist_in and hist_out must not overlap z_in or z_out");
-        AVD_REQUIRE(!(popped < hist_in + total && hist_in < popped + pop) && !(popped < hist_out + total && hist_out < popped + pop), AVD_EINVAL,
-                    "fifo_shift: popped must not overlap hist_in or hist_out");
+        AVD_REQUIRE(!(popped < hist_in + total && hist_in < popped + dst) && !(popped < hist_out + total && hist_out < popped + dst), AVD_EINVAL,
+                    "fifo_shift: %s must not overlap hist_in or hist_out", pname);
     }
     const bool vec = inner % 4 == 0 && aligned16(z_in) && aligned16(z_out) && aligned16(popped) && aligned16(hist_in) && aligned16(hist_out);
     const int v = vec ? 4 : 1;
@@ -594,13 +621,31 @@ int fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* 
     AVD_REQUIRE((n_out + n_pop + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "fifo_shift: %lld lanes are too many for one launch",
                 (long long)(n_out + n_pop));
     const CanvasKey ck{(uint32_t)(key->seed & 0xffffffffu), (uint32_t)(key->seed >> 32), (uint32_t)c, (uint32_t)slot_len};
-    static const int tags[4] = {prof_tag_id("fifo_shift_kernel<1>"), prof_tag_id("fifo_shift_kernel<4>"),
-                                prof_tag_id("fifo_shift_kernel<1, HistShift>"), prof_tag_id("fifo_shift_kernel<4, HistShift>")};
+    static const int tags[8] = {prof_tag_id("fifo_shift_kernel<1>"), prof_tag_id("fifo_shift_kernel<4>"),
+                                prof_tag_id("fifo_shift_kernel<1, HistShift>"), prof_tag_id("fifo_shift_kernel<4, HistShift>"),
+                                prof_tag_id("fifo_shift_kernel<1, CursorShift>"), prof_tag_id("fifo_shift_kernel<4, CursorShift>"),
+                                prof_tag_id("fifo_shift_kernel<1, HistShift, CursorShift>"),
+                                prof_tag_id("fifo_shift_kernel<4, HistShift, CursorShift>")};
     // read + write of the queue (and of the history), the popped slot's write
-    ProfScope prof(tags[(hist_in ? 2 : 0) + (vec ? 1 : 0)], 4.0 * ((hist_in ? 4.0 : 2.0) * (double)total + (double)pop), st);
+    ProfScope prof(tags[(cursor ? 4 : 0) + (hist_in ? 2 : 0) + (vec ? 1 : 0)], 4.0 * ((hist_in ? 4.0 : 2.0) * (double)total + (double)pop), st);
     const dim3 grid((unsigned)((n_out + n_pop + 255) / 256));
-    if (hist_in) {
-        const HistShift hs{hist_in, hist_out};
+    const HistShift hs{hist_in, hist_out};
+    const CursorShift cs{cursor, n_clip};
+    if (cursor && hist_in) {
+        if (vec)
+            hipLaunchKernelGGL((fifo_shift_kernel<4, HistShift, CursorShift>), grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B,
+                               outer, S, slot_len, inner, n_out, n_pop, hs, cs);
+        else
+            hipLaunchKernelGGL((fifo_shift_kernel<1, HistShift, CursorShift>), grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B,
+                               outer, S, slot_len, inner, n_out, n_pop, hs, cs);
+    } else if (cursor) {
+        if (vec)
+            hipLaunchKernelGGL((fifo_shift_kernel<4, CursorShift>), grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B, outer, S,
+                               slot_len, inner, n_out, n_pop, cs);
+        else
+            hipLaunchKernelGGL((fifo_shift_kernel<1, CursorShift>), grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B, outer, S,
+                               slot_len, inner, n_out, n_pop, cs);
+    } else if (hist_in) {
         if (vec)
             hipLaunchKernelGGL((fifo_shift_kernel<4, HistShift>), grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B, outer, S,
                                slot_len, inner, n_out, n_pop, hs);
@@ -615,6 +660,53 @@ int fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* 
                            n_out, n_pop);
     AVD_CHECK_LAUNCH("fifo_shift");
     return AVD_OK;
+}
+
+// ------------------------------------------------------------------ device cursors of the FIFO queue
+// The contracts are written out in include/avdiff_hip.h ("FIFO device cursors").  A cursor is one int32 on the device; no kernel below
+// addresses by it without a clamp or a guard, and it moves only in cursor_add_kernel, a launch of its own behind its last reader.
+__global__ void cursor_add_kernel(int32_t* cursor, int delta) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *cursor += delta;
+}
+
+// out_k[j] = tab_k[row, j] for the NT tables, row = clamp(*cursor, 0, n_rows - 1), j < n: the slot analogue of sched_advance_kernel
+struct SlotTabs {
+    const int64_t* tab[3];
+    int64_t* out[3];
+};
+template <int NT>
+__global__ __launch_bounds__(256) void slot_tables_select_kernel(SlotTabs tb, const int32_t* __restrict__ cursor, int n_rows, int n) {
+    int r = *cursor;
+    r = r < 0 ? 0 : (r > n_rows - 1 ? n_rows - 1 : r);
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+#pragma unroll
+    for (int k = 0; k < NT; ++k) tb.out[k][j] = tb.tab[k][(int64_t)r * n + j];
+}
+
+// out[b, o, l, i] = canvas[o, (m + b * S) * hop + l, i] where that position is below P, else 0; m = max(*cursor, 0).  V lanes as
+// canvas_noise_kernel; every index is 64-bit.  n: B * outer * len * inner / V lanes.
+template <int V>
+__global__ __launch_bounds__(256) void fifo_prompt_gather_kernel(const float* __restrict__ canvas, float* __restrict__ out,
+                                                                 const int32_t* __restrict__ cursor, int S, int64_t hop, int64_t outer,
+                                                                 int64_t P, int64_t len, int64_t inner, int64_t n) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    int64_t m = *cursor;
+    if (m < 0) m = 0;
+    const int64_t iv = inner / V;
+    const int64_t i = (idx % iv) * V;
+    int64_t r = idx / iv;
+    const int64_t l = r % len;
+    r /= len;
+    const int64_t o = r % outer, b = r / outer;
+    const int64_t p = (m + b * S) * hop + l;      // m, B * S, hop and len each fit an int (the host checks): below 2^63
+    if constexpr (V == 4) {
+        f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (p < P) v = *reinterpret_cast<const f32x4*>(canvas + (o * P + p) * inner + i);
+        *reinterpret_cast<f32x4*>(out + idx * 4) = v;
+    } else
+        out[idx] = p < P ? canvas[(o * P + p) * inner + i] : 0.f;
 }
 
 __global__ __launch_bounds__(256) void ddim_kernel(const float* __restrict__ x, const float* __restrict__ eps,
@@ -2204,6 +2296,67 @@ extern "C" int avd_fifo_shift_hist_f32(const avd_noise_key* key, int64_t t, int6
                                        avd_stream_t stream) {
     AVD_REQUIRE(hist_in && hist_out, AVD_EINVAL, "fifo_shift_hist: null hist_in or hist_out");
     return fifo_shift_f32(key, t, c, z_in, z_out, popped, B, outer, slots, slot_len, inner, static_cast<hipStream_t>(stream), hist_in, hist_out);
+}
+extern "C" int avd_fifo_shift_cursor_f32(const avd_noise_key* key, int64_t t, int64_t c0, const int32_t* cursor, int64_t n_out,
+                                         const float* z_in, float* z_out, float* clip, int B, int64_t outer, int slots, int slot_len,
+                                         int64_t inner, avd_stream_t stream) {
+    AVD_REQUIRE(cursor, AVD_EINVAL, "fifo_shift_cursor: null cursor");
+    return fifo_shift_f32(key, t, c0, z_in, z_out, clip, B, outer, slots, slot_len, inner, static_cast<hipStream_t>(stream), nullptr, nullptr,
+                          cursor, n_out);
+}
+extern "C" int avd_fifo_shift_cursor_hist_f32(const avd_noise_key* key, int64_t t, int64_t c0, const int32_t* cursor, int64_t n_out,
+                                              const float* z_in, float* z_out, float* clip, const float* hist_in, float* hist_out, int B,
+                                              int64_t outer, int slots, int slot_len, int64_t inner, avd_stream_t stream) {
+    AVD_REQUIRE(cursor, AVD_EINVAL, "fifo_shift_cursor_hist: null cursor");
+    AVD_REQUIRE(hist_in && hist_out, AVD_EINVAL, "fifo_shift_cursor_hist: null hist_in or hist_out");
+    return fifo_shift_f32(key, t, c0, z_in, z_out, clip, B, outer, slots, slot_len, inner, static_cast<hipStream_t>(stream), hist_in, hist_out,
+                          cursor, n_out);
+}
+extern "C" int avd_cursor_add(int32_t* cursor, int delta, avd_stream_t stream) {
+    AVD_REQUIRE(cursor, AVD_EINVAL, "cursor_add: null cursor");
+    hipLaunchKernelGGL(cursor_add_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), cursor, delta);
+    AVD_CHECK_LAUNCH("cursor_add");
+    return AVD_OK;
+}
+extern "C" int avd_slot_tables_select(const int64_t* tab0, const int64_t* tab1, const int64_t* tab2, int n_rows, int n,
+                                      const int32_t* cursor, int64_t* out0, int64_t* out1, int64_t* out2, avd_stream_t stream) {
+    AVD_REQUIRE(tab0 && tab1 && out0 && out1 && cursor, AVD_EINVAL, "slot_tables_select: null pointer");
+    AVD_REQUIRE(!tab2 == !out2, AVD_EINVAL, "slot_tables_select: the third table and its buffer go together");
+    AVD_REQUIRE(n_rows >= 1 && n >= 1, AVD_EINVAL, "slot_tables_select: bad dims (n_rows %d, n %d)", n_rows, n);
+    const SlotTabs tb{{tab0, tab1, tab2}, {out0, out1, out2}};
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (tab2)
+        hipLaunchKernelGGL(slot_tables_select_kernel<3>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), tb, cursor, n_rows, n);
+    else
+        hipLaunchKernelGGL(slot_tables_select_kernel<2>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), tb, cursor, n_rows, n);
+    AVD_CHECK_LAUNCH("slot_tables_select");
+    return AVD_OK;
+}
+extern "C" int avd_fifo_prompt_gather_f32(const float* canvas, const int32_t* cursor, float* out, int B, int slots, int prompt_hop,
+                                          int64_t outer, int64_t P, int64_t prompt_len, int64_t inner, avd_stream_t stream) {
+    AVD_REQUIRE(canvas && cursor && out, AVD_EINVAL, "fifo_prompt_gather: null pointer");
+    AVD_REQUIRE(B > 0 && slots > 0 && prompt_hop > 0 && outer > 0 && P > 0 && prompt_len > 0 && inner > 0, AVD_EINVAL,
+                "fifo_prompt_gather: bad dims (B %d, slots %d, prompt_hop %d, outer %lld, P %lld, prompt_len %lld, inner %lld)", B, slots,
+                prompt_hop, (long long)outer, (long long)P, (long long)prompt_len, (long long)inner);
+    AVD_REQUIRE((int64_t)B * slots <= 0x7fffffff && prompt_len <= 0x7fffffff, AVD_EINVAL,
+                "fifo_prompt_gather: B %d * slots %d and prompt_len %lld must fit an int", B, slots, (long long)prompt_len);
+    AVD_REQUIRE((double)outer * (double)P * (double)inner < 9.0e18 && (double)B * (double)outer * (double)prompt_len * (double)inner < 9.0e18,
+                AVD_EUNSUPPORTED, "fifo_prompt_gather: too many values");
+    const int64_t n_c = outer * P * inner, n_o = (int64_t)B * outer * prompt_len * inner;
+    AVD_REQUIRE(!(out < canvas + n_c && canvas < out + n_o), AVD_EINVAL, "fifo_prompt_gather: out must not overlap the prompt canvas");
+    const bool vec = inner % 4 == 0 && aligned16(canvas) && aligned16(out);
+    const int64_t n = n_o / (vec ? 4 : 1);
+    AVD_REQUIRE((n + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "fifo_prompt_gather: %lld lanes are too many for one launch", (long long)n);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (vec)
+        hipLaunchKernelGGL(fifo_prompt_gather_kernel<4>, grid, dim3(256), 0, st, canvas, out, cursor, slots, (int64_t)prompt_hop, outer, P,
+                           prompt_len, inner, n);
+    else
+        hipLaunchKernelGGL(fifo_prompt_gather_kernel<1>, grid, dim3(256), 0, st, canvas, out, cursor, slots, (int64_t)prompt_hop, outer, P,
+                           prompt_len, inner, n);
+    AVD_CHECK_LAUNCH("fifo_prompt_gather");
+    return AVD_OK;
 }
 extern "C" int avd_cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now,
                                               const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance,

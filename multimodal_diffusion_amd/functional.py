@@ -641,6 +641,109 @@ def fifo_shift(z: Tensor, c: int, seed: int, t: int, slot_len: int, hist: Option
     return out, popped, hist_out
 
 
+# ---- FIFO device cursors (include/avdiff_hip.h, "FIFO device cursors"): the host numbers of a FIFO iteration read off the device ----
+def _cursor(cursor: Tensor, device: torch.device) -> Tensor:
+    if not (isinstance(cursor, Tensor) and cursor.is_cuda and cursor.dtype == torch.int32 and cursor.numel() == 1 and
+            cursor.device == device):
+        raise ValueError("a cursor is one int32 in device memory (a 1-element int32 tensor on the buffers' device)")
+    return cursor
+
+
+def cursor_add(cursor: Tensor, delta: int = 1) -> None:
+    """*cursor += delta on the current stream (avd_cursor_add): how a FIFO cursor moves, in a launch of its own behind its readers."""
+    L.check(L.lib().avd_cursor_add(_cursor(cursor, cursor.device).data_ptr(), int(delta), _st(cursor)))
+
+
+def stack_slot_tables(rows: Tensor) -> Tensor:
+    """[n_rows, B, S] int tables (a ramp table of ``schedule_utils.fifo_plan`` / ``fifo_plan_last``) -> contiguous int64 [n_rows, B*S],
+    the layout ``slot_tables_select`` reads: row r reshaped to [B, S] is ``rows[r]``.  Any device."""
+    rows = torch.as_tensor(rows)
+    if rows.dim() != 3 or rows.is_floating_point() or rows.dtype == torch.bool:
+        raise ValueError(f"slot tables are integer [n_rows, B, S], got {rows.dtype} {tuple(rows.shape)}")
+    return rows.to(torch.long).reshape(rows.shape[0], rows.shape[1] * rows.shape[2]).contiguous()
+
+
+def slot_tables_select(tables, cursor: Tensor, outs) -> None:
+    """One launch (avd_slot_tables_select) copies row min(max(*cursor, 0), n_rows - 1) of each of the two or three ``tables``
+    (contiguous int64 [n_rows, n] on the device, ``stack_slot_tables``) into its buffer of ``outs`` (contiguous int64, n elements: the
+    fixed [B, S] tables ``step_slots`` reads).  The cursor is read, not moved."""
+    tables, outs = list(tables), list(outs)
+    if len(tables) not in (2, 3) or len(outs) != len(tables):
+        raise ValueError("slot_tables_select takes two or three tables and as many buffers")
+    dev = tables[0].device
+    n_rows, n = (int(v) for v in tables[0].shape) if tables[0].dim() == 2 else (0, 0)
+    for t in tables:
+        if not (t.is_cuda and t.dtype == torch.long and t.is_contiguous() and t.dim() == 2 and tuple(t.shape) == (n_rows, n) and t.device == dev):
+            raise ValueError("tables must be contiguous int64 [n_rows, n] device tensors of one shape")
+    for o in outs:
+        if not (o.is_cuda and o.dtype == torch.long and o.is_contiguous() and o.numel() == n and o.device == dev):
+            raise ValueError(f"every buffer must be a contiguous int64 device tensor of {n} elements")
+    p = [t.data_ptr() for t in tables] + [None] * (3 - len(tables))
+    q = [o.data_ptr() for o in outs] + [None] * (3 - len(outs))
+    L.check(L.lib().avd_slot_tables_select(*p, n_rows, n, _cursor(cursor, dev).data_ptr(), *q, L.stream_ptr(dev)))
+
+
+def fifo_prompt_gather(prompt_canvas: Tensor, cursor: Tensor, B: int, S: int, prompt_hop: int, prompt_len: int,
+                       out: Optional[Tensor] = None) -> Tensor:
+    """``stream_infer.fifo_prompt_windows(prompt_canvas, m = max(*cursor, 0), ...)`` in one launch with m read off the device
+    (avd_fifo_prompt_gather_f32): [B, C, prompt_len, H, W] from a video prompt canvas [C, P, H, W], [B, Ca, prompt_len] from an audio
+    one [Ca, P], zeros beyond the canvas end.  ``out``: a contiguous float32 buffer of that shape that does not overlap the canvas."""
+    pc = prompt_canvas
+    if not (isinstance(pc, Tensor) and pc.is_cuda and pc.dtype == torch.float32 and pc.is_contiguous() and pc.dim() in (2, 4)):
+        raise ValueError("a prompt canvas is a contiguous float32 device tensor [C, P, H, W] (video) or [Ca, P] (audio)")
+    for name, v in (("B", B), ("S", S), ("prompt_hop", prompt_hop), ("prompt_len", prompt_len)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v < 2 ** 31:
+            raise ValueError(f"{name} must be an int in [1, 2**31), got {v!r}")
+    shape = (B, pc.shape[0], prompt_len) + tuple(pc.shape[2:])
+    if out is None:
+        out = torch.empty(shape, device=pc.device, dtype=torch.float32)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape and out.device == pc.device):
+        raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on the canvas's device")
+    inner = pc.shape[2] * pc.shape[3] if pc.dim() == 4 else 1
+    L.check(L.lib().avd_fifo_prompt_gather_f32(pc.data_ptr(), _cursor(cursor, pc.device).data_ptr(), out.data_ptr(), B, S, prompt_hop,
+                                               pc.shape[0], pc.shape[1], prompt_len, inner, _st(pc)))
+    return out
+
+
+def fifo_shift_cursor(z: Tensor, c0: int, cursor: Tensor, clip: Tensor, seed: int, t: int, slot_len: int, out: Optional[Tensor] = None,
+                      hist: Optional[Tensor] = None, hist_out: Optional[Tensor] = None):
+    """``fifo_shift`` with the clip slot on the device (avd_fifo_shift_cursor_f32 / _hist_f32; contract in include/avdiff_hip.h, "FIFO
+    queue shift off a device cursor"): with m = *cursor the queue shifts as ``fifo_shift(z, c0 + m, ...)`` and the finished head is
+    written straight into slot m of ``clip``, the clip canvas [C, n_out * slot_len, H, W] / [Ca, n_out * slot_len] — nowhere when m is
+    outside [0, n_out).  Returns z_out, or (z_out, hist_out) with ``hist``.  ``out`` / ``hist_out``: buffers to write to (z's shape).
+    The cursor is read, not moved."""
+    z = L.dev_f32(z, "z")
+    outer, L_, inner = window_dims(z.shape)
+    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or L_ % slot_len:
+        raise ValueError(f"slot_len must be an int >= 1 that divides the sliding length {L_}, got {slot_len!r}")
+    for name, v in (("c0", c0), ("t", t)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"{name} must be an int >= 0, got {v!r}")
+    if not (isinstance(clip, Tensor) and clip.is_cuda and clip.dtype == torch.float32 and clip.is_contiguous() and clip.device == z.device and
+            clip.dim() == z.dim() - 1 and clip.shape[0] == z.shape[1] and tuple(clip.shape[2:]) == tuple(z.shape[3:]) and
+            clip.shape[1] >= slot_len and clip.shape[1] % slot_len == 0):
+        raise ValueError(f"clip must be a contiguous float32 canvas [{z.shape[1]}, n_out * {slot_len}, ...] of z's slice shape on z's device")
+    n_out = clip.shape[1] // slot_len
+    if (c0 + n_out) * slot_len > 2 ** 32:
+        raise ValueError(f"(c0 {c0} + n_out {n_out}) * slot_len {slot_len} exceeds the stream's 2**32 canvas positions")
+    if hist is None and hist_out is not None:
+        raise ValueError("hist_out goes with hist")
+    bufs = [("out", out)] + ([("hist", hist), ("hist_out", hist_out)] if hist is not None else [])
+    for name, b in bufs:
+        if b is not None and not (b.is_cuda and b.dtype == torch.float32 and b.is_contiguous() and b.shape == z.shape and b.device == z.device):
+            raise ValueError(f"{name} must be a contiguous float32 tensor of z's shape {tuple(z.shape)} on z's device")
+    key = noise_key(seed, 0)
+    out = torch.empty_like(z) if out is None else out
+    head = (C.byref(key), t, c0, _cursor(cursor, z.device).data_ptr(), n_out, z.data_ptr(), out.data_ptr(), clip.data_ptr())
+    tail = (z.shape[0], outer, L_ // slot_len, slot_len, inner, _st(z))
+    if hist is None:
+        L.check(L.lib().avd_fifo_shift_cursor_f32(*head, *tail))
+        return out
+    hist_out = torch.empty_like(hist) if hist_out is None else hist_out
+    L.check(L.lib().avd_fifo_shift_cursor_hist_f32(*head, hist.data_ptr(), hist_out.data_ptr(), *tail))
+    return out, hist_out
+
+
 # ---- "bf16x3": fp32-accurate Linear on the bf16 matrix pipe (csrc/gemm_bf16x3.hip) ----
 def split3(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """fp32 [rows, K] -> its split3 image (uint8; three bf16 planes, tiled).  K must be a multiple of 16.

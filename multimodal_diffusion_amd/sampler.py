@@ -104,6 +104,13 @@ def tokens_to_latents_audio(tokens: torch.Tensor, Ca: int, l_chunk: int, Fa: int
 # batched on-device loop
 # ----------------------------------------------------------------------------------------------------------
 
+class FifoQueue:
+    """The state of one open FIFO queue (``DenoiseEngine.fifo_open``): the device cursors ``r`` (ramp iteration) and ``m`` (steady
+    iteration), the uploaded tables (``ramp``: [n - 1, B*S] each; ``steady`` and the selected ``slot`` tables: [B, S] each; two, or
+    three with t_last), the prompt canvas ``canvas_p`` and the prompt-latent buffer ``prompt``, the latent buffers ``z`` / ``other``,
+    the clip canvas ``clip``, and what the launches take by value: ``seed``, ``s0``, ``n`` (= c0), ``n_slots``, ``hop``."""
+
+
 class _CapturedPair:
     """A captured two-step HIP graph of one engine.  ``replay()`` first re-checks the engine's weight tables: parameters updated in
     place behind unchanged pointers are picked up (derived images are refreshed in place).  The graph holds every device pointer
@@ -207,6 +214,10 @@ class DenoiseEngine:
     t_now is held.  The primitive of FIFO diagonal denoising (``stream_infer.fifo_denoise``, ``schedule_utils.fifo_plan``).  Either
     solver at eta == 0 with the scalar guidance only: solver "dpmpp_2m" takes a third table ``t_last`` and keeps its history per
     element in ``x0_hist``, which ``fifo_shift`` moves along with the queue.  ``step``, ``run`` and ``capture_pair`` do not change.
+
+    ``fifo_open`` / ``fifo_ramp`` / ``fifo_steady`` / ``fifo_capture`` (extension: a FIFO queue whose iterations read the ramp row and
+    the clip slot off device cursors, include/avdiff_hip.h, "FIFO device cursors"): what ``fifo_denoise(graph=True)`` replays.  An
+    iteration is the same chain of launches eagerly and under capture; a captured pair belongs to the queue it was captured on.
     """
 
     SOLVERS = ("ddim", "dpmpp_2m")
@@ -424,11 +435,10 @@ class DenoiseEngine:
         B = self.embed.B
         if z.shape[0] != B:
             raise ValueError("prompt batch size must match the engine's")
-        tok = latents_to_tokens_audio(z, *self.chunk) if self.target == "video" else \
-            ops.tube_patch_video(z, *self.tube)
+        tok = self._prompt_tokens(z)
         if tok.shape[1] != self.embed.Np:
             raise ValueError(f"prompt yields {tok.shape[1]} tokens, engine was built for {self.embed.Np}")
-        d, td = self.d, self.tdim
+        d = self.d
         # the prompt rows keep their buffer from call to call (a captured graph holds its address); a first call, or one after the
         # buffer was dropped, starts a new table generation
         Xp = self.Xp
@@ -436,8 +446,20 @@ class DenoiseEngine:
             Xp = torch.empty(B, tok.shape[1], d, device=self.device, dtype=torch.float32)
             self._generation += 1
             self._stale_reason = "the prompt rows were (re-)allocated by set_prompt()"
+        self._prompt_rows(tok, Xp)
+        self.Xp = Xp
+        return Xp
+
+    def _prompt_tokens(self, z: torch.Tensor) -> torch.Tensor:
+        return latents_to_tokens_audio(z, *self.chunk) if self.target == "video" else ops.tube_patch_video(z, *self.tube)
+
+    def _prompt_rows(self, tok: torch.Tensor, Xp: torch.Tensor, temb: bool = True) -> None:
+        """``set_prompt``'s device work behind the tokens: the adapter GEMM into ``Xp`` and, with ``temb``, the timestep-0 embedding.
+        ``temb=False`` (concat mode only) leaves Xp's timestep columns as they are: they are constant, so a FIFO queue writes them once
+        when it is opened and every steady iteration renews the adapter columns alone — launches only, no host synchronisation."""
+        B, d, td = self.embed.B, self.d, self.tdim
         w, b = self.adapt_p.proj.weight.detach(), self.adapt_p.proj.bias.detach()
-        t0 = su.timestep_embedding(torch.zeros(B, dtype=torch.long, device=self.device), td) if td else None
+        t0 = su.timestep_embedding(torch.zeros(B, dtype=torch.long, device=self.device), td) if td and temb else None
         if self.temb_mode == "add":
             # adapter(tok) + temb(0): the broadcast embedding rides in as the GEMM's residual operand
             res = t0[:, None, :].expand(B, tok.shape[1], d).contiguous()
@@ -449,10 +471,8 @@ class DenoiseEngine:
             L.check(L.lib().avd_gemm_bias_act_f32(tok.data_ptr(), tok.shape[2], L.dev_f32(w).data_ptr(), L.dev_f32(b).data_ptr(),
                                                   None, 0, Xp.data_ptr(), d, B * tok.shape[1], d - td, tok.shape[2],
                                                   L.ACT_NONE, L.stream_ptr(self.device)))
-            if td:
+            if t0 is not None:
                 Xp[..., d - td:] = t0[:, None, :]
-        self.Xp = Xp
-        return Xp
 
     # ---- latent guide: a known clean latent the trajectory is held to (inpainting / outpainting) or starts from (SDEdit) ----
     def set_known(self, known: torch.Tensor, mask: Optional[torch.Tensor] = None, *, guide_seed: int = 0, keying: str = "sample",
@@ -755,26 +775,7 @@ class DenoiseEngine:
         audio chunks are refused before anything is launched, as is ``t_last`` on a "ddim" engine."""
         if self.Xp is None:
             raise RuntimeError("call set_prompt() first")
-        if self.eta > 0:
-            raise ValueError("step_slots needs eta == 0: slots at different timesteps have no common noise stream yet (eta > 0 is out "
-                             "of scope)")
-        if self.solver == "ddim" and t_last is not None:
-            raise ValueError("t_last is the multistep solver's history: this engine runs solver 'ddim'")
-        if self.solver != "ddim" and t_last is None:
-            raise ValueError(f"step_slots on solver {self.solver!r} needs t_last, the [B, S] table of the timesteps each slot's history "
-                             "comes from (-1: none)")
-        if self._guide is not None:
-            raise ValueError("step_slots takes no latent guide (its forward path is keyed by one t_prev per sample): clear_known() first")
-        if self._ctl is not None:
-            raise ValueError("step_slots takes the scalar guidance: per-sample guidance and guidance rescale (the CFG control) are not "
-                             "supported there")
-        if self._cons_hop is not None:
-            raise ValueError("step_slots takes no window consensus (the windows of a canvas share their timesteps): "
-                             "clear_window_consensus() first")
-        if self.temb_mode == "add":
-            raise ValueError("step_slots needs temb_mode='concat': the added embedding is one row per sample")
-        if self.target == "audio" and self.chunk[0] != self.chunk[1]:
-            raise ValueError(f"step_slots needs non-overlapping audio chunks (stride == length), got chunk {self.chunk}")
+        self._slot_refusals(t_last is not None)
         z = L.dev_f32(z, "z")
         if tuple(z.shape) != self.latent_shape:
             raise ValueError(f"latent shape {tuple(z.shape)} != engine shape {self.latent_shape}")
@@ -800,6 +801,30 @@ class DenoiseEngine:
             L.check(L.lib().avd_denoise_step_slots_f32(*head, tn.data_ptr(), tp.data_ptr(), S, *tail))
         return out
 
+    def _slot_refusals(self, has_t_last: bool) -> None:
+        """what ``step_slots`` refuses of the engine's state, before anything is launched (``fifo_open`` asks the same before it
+        allocates, so a graph-replayed queue refuses what the eager one does, in the same words, before any capture)"""
+        if self.eta > 0:
+            raise ValueError("step_slots needs eta == 0: slots at different timesteps have no common noise stream yet (eta > 0 is out "
+                             "of scope)")
+        if self.solver == "ddim" and has_t_last:
+            raise ValueError("t_last is the multistep solver's history: this engine runs solver 'ddim'")
+        if self.solver != "ddim" and not has_t_last:
+            raise ValueError(f"step_slots on solver {self.solver!r} needs t_last, the [B, S] table of the timesteps each slot's history "
+                             "comes from (-1: none)")
+        if self._guide is not None:
+            raise ValueError("step_slots takes no latent guide (its forward path is keyed by one t_prev per sample): clear_known() first")
+        if self._ctl is not None:
+            raise ValueError("step_slots takes the scalar guidance: per-sample guidance and guidance rescale (the CFG control) are not "
+                             "supported there")
+        if self._cons_hop is not None:
+            raise ValueError("step_slots takes no window consensus (the windows of a canvas share their timesteps): "
+                             "clear_window_consensus() first")
+        if self.temb_mode == "add":
+            raise ValueError("step_slots needs temb_mode='concat': the added embedding is one row per sample")
+        if self.target == "audio" and self.chunk[0] != self.chunk[1]:
+            raise ValueError(f"step_slots needs non-overlapping audio chunks (stride == length), got chunk {self.chunk}")
+
     def fifo_shift(self, z: torch.Tensor, c: int, t: int, seed: Optional[int] = None):
         """The queue step of FIFO diagonal denoising on this engine's queue (``functional.fifo_shift`` with the engine's ``slot_len``;
         ``seed``: the seed of the entering slot's noise, None = the engine's ``noise_seed``): returns (z_out, popped).  Solver "dpmpp_2m": the same launch shifts the history into a
@@ -818,6 +843,100 @@ class DenoiseEngine:
         self._generation += 1
         self._stale_reason = "fifo_shift moved the solver history into the engine's other history buffer (x0_hist changed its address)"
         return z_out, popped
+
+    # ---- FIFO queue with device cursors: an iteration as a fixed chain of launches (include/avdiff_hip.h, "FIFO device cursors") ----
+    def fifo_open(self, prompt_canvas: torch.Tensor, prompt_hop: int, prompt_len: int, sched, n_slots: int,
+                  noise_seed: int) -> "FifoQueue":
+        """Open a FIFO queue (``stream_infer.fifo_denoise(graph=True)`` drives it) whose iterations read the ramp row r and the steady
+        iteration m off two int32 device cursors, so that ``fifo_ramp`` and ``fifo_steady`` are fixed chains of launches on the
+        current stream, the same eagerly and under ``fifo_capture``.  Uploads the plan's tables (``schedule_utils.fifo_plan``, with
+        ``fifo_plan_last`` on solver "dpmpp_2m"; the ramp rows stacked [n - 1, B*S]) and the prompt canvas; allocates the cursors (both
+        0), the [B, S] table buffers, the prompt-latent buffer, the two latent buffers (``q.z`` holds the seeded start), a clip canvas
+        of ``n_slots`` slots (fresh per call: it is what the driver returns) and, on "dpmpp_2m", the second history buffer; embeds the
+        prompt of m = 0, which also writes Xp's constant timestep columns.  ``prompt_len``: the prompt latent's length along its
+        sliding axis (``stream_infer.fifo_prompt_len``).  Refuses what ``step_slots`` refuses, before it allocates.
+        The queue holds ``noise_seed``, c0 = n, ``n_slots``, the hops and every address: a captured pair is good for this queue only."""
+        B, S, sl = self.embed.B, self.slots, self.slot_len
+        ramp_now, ramp_prev, steady_now, steady_prev = su.fifo_plan(sched, S)
+        n = ramp_now.shape[0] + 1
+        if n != B * S:
+            raise ValueError(f"the schedule has {n} steps, the engine's queue {B} samples x {S} slots = {B * S}: fifo_denoise needs them equal")
+        outer, L_, _ = Fn.window_dims(self.latent_shape)
+        if L_ != S * sl:
+            raise ValueError(f"the engine's sliding length {L_} is not {S} slots of {sl} positions (an uncovered audio tail cannot queue)")
+        Fn.noise_key(noise_seed, 0)
+        for name, v in (("n_slots", n_slots), ("prompt_hop", prompt_hop), ("prompt_len", prompt_len)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"{name} must be an int >= 1, got {v!r}")
+        self._slot_refusals(self.solver == "dpmpp_2m")
+        dev = self.device
+        q = FifoQueue()
+        q.n, q.n_slots, q.seed, q.hop, q.s0 = n, n_slots, noise_seed, prompt_hop, int(torch.as_tensor(sched).reshape(-1)[0])
+        if (n + n_slots) * sl > 2 ** 32:
+            raise ValueError(f"(n {n} + n_slots {n_slots}) * slot_len {sl} exceeds the stream's 2**32 canvas positions")
+        q.canvas_p = L.dev_f32(prompt_canvas.to(dev), "prompt canvas")
+        multistep = self.solver == "dpmpp_2m"
+        ramp = [ramp_now, ramp_prev]
+        steady = [steady_now, steady_prev]
+        if multistep:
+            ramp_last, steady_last = su.fifo_plan_last(sched, S)
+            ramp.append(ramp_last)
+            steady.append(steady_last)
+        q.ramp = [Fn.stack_slot_tables(t).to(dev) for t in ramp] if n > 1 else []
+        q.steady = [L.dev_i64(t, dev) for t in steady]
+        q.slot = [torch.empty(B, S, dtype=torch.long, device=dev) for _ in ramp]
+        q.r = torch.zeros(1, dtype=torch.int32, device=dev)
+        q.m = torch.zeros(1, dtype=torch.int32, device=dev)
+        q.clip = torch.empty((outer, n_slots * sl) + tuple(self.latent_shape[3:]), device=dev, dtype=torch.float32)
+        q.z = Fn.canvas_noise(noise_seed, torch.full((B,), q.s0, dtype=torch.long, device=dev), self.latent_shape, L_)
+        q.other = torch.empty_like(q.z)
+        if multistep and self._hist_other is None:
+            self._hist_other = torch.empty_like(self.x0_hist)
+        q.prompt = Fn.fifo_prompt_gather(q.canvas_p, q.m, B, S, prompt_hop, prompt_len)
+        self.set_prompt(q.prompt)
+        return q
+
+    def fifo_ramp(self, q: "FifoQueue", src: torch.Tensor, dst: torch.Tensor) -> None:
+        """One ramp iteration of an open queue: select row *r of the ramp tables -> ``step_slots`` src -> dst -> r += 1."""
+        Fn.slot_tables_select(q.ramp, q.r, q.slot)
+        self.step_slots(src, q.slot[0], q.slot[1], out=dst, t_last=q.slot[2] if len(q.slot) == 3 else None)
+        Fn.cursor_add(q.r)
+
+    def fifo_steady(self, q: "FifoQueue", z: torch.Tensor, tmp: torch.Tensor) -> None:
+        """One steady iteration of an open queue, with m = *m: gather the prompt of iteration m -> embed it into Xp (same address) ->
+        ``step_slots`` z -> tmp on the constant steady tables -> shift tmp -> z, the finished head into slot m of the clip canvas and
+        clip slot n + m entering at the tail -> m += 1.  The latent is back in ``z``.  On "dpmpp_2m" the shift carries the history
+        into the engine's other history buffer and the two swap, as in ``fifo_shift``: two iterations put ``x0_hist`` back."""
+        B, S = self.embed.B, self.slots
+        Fn.fifo_prompt_gather(q.canvas_p, q.m, B, S, q.hop, q.prompt.shape[2], out=q.prompt)
+        self._prompt_rows(self._prompt_tokens(q.prompt), self.Xp, temb=False)
+        multistep = len(q.steady) == 3
+        self.step_slots(z, q.steady[0], q.steady[1], out=tmp, t_last=q.steady[2] if multistep else None)
+        if not multistep:
+            Fn.fifo_shift_cursor(tmp, q.n, q.m, q.clip, q.seed, q.s0, self.slot_len, out=z)
+        else:
+            Fn.fifo_shift_cursor(tmp, q.n, q.m, q.clip, q.seed, q.s0, self.slot_len, out=z, hist=self.x0_hist, hist_out=self._hist_other)
+            self.x0_hist, self._hist_other = self._hist_other, self.x0_hist
+            if not torch.cuda.is_current_stream_capturing():      # a captured pair swaps twice: the address is back where it was
+                self._generation += 1
+                self._stale_reason = "fifo_steady moved the solver history into the engine's other history buffer (x0_hist changed its address)"
+        Fn.cursor_add(q.m)
+
+    def fifo_capture(self, q: "FifoQueue", steady: bool, za: torch.Tensor, zb: torch.Tensor) -> "torch.cuda.CUDAGraph":
+        """Two iterations of one phase of an open queue in one HIP graph, one chain on one stream: ramp za -> zb -> za, steady twice
+        on (za, zb).  After a replay the latent is back in ``za`` and ``x0_hist`` at its address; the cursors have moved by two.  Every
+        kernel of the phase must have run once before (the driver takes each phase's first iteration eagerly).  The graph is this
+        queue's: it holds the seed, c0, the clip length, the hops and every address by value."""
+        self._sync_weights()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            if steady:
+                self.fifo_steady(q, za, zb)
+                self.fifo_steady(q, za, zb)
+            else:
+                self.fifo_ramp(q, za, zb)
+                self.fifo_ramp(q, zb, za)
+        return g
 
     def eps_tokens(self) -> torch.Tensor:
         """ε̂ tokens left in the workspace by the last step (debug / parity only): cond / null [2B,Nt,D] after a CFG step; after a

@@ -209,7 +209,8 @@ def fifo_prompt_len(engine: DenoiseEngine, prompt_canvas: torch.Tensor) -> int:
 
 
 @torch.no_grad()
-def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop: int, sched, n_slots: int, noise_seed: int) -> torch.Tensor:
+def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop: int, sched, n_slots: int, noise_seed: int,
+                 graph: Optional[bool] = False) -> torch.Tensor:
     """FIFO diagonal denoising (FIFO-Diffusion, Kim et al. 2024, with latent partitioning): a clip of ``n_slots`` slots of
     ``engine.slot_len`` latent positions, denoised in a queue whose slots sit at different noise levels.  Returns the finished latent
     canvas [C, n_slots * slot_len, H, W] (video target) or [Ca, n_slots * slot_len] (audio target).
@@ -222,8 +223,17 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     sample-steps, what non-overlapping windows cost; nothing is cross-faded or averaged.
     ``prompt_canvas`` is the prompt modality's latent along its sliding axis and ``prompt_hop`` its positions per target slot: before
     the step of steady iteration m (the ramp: m = 0) sample k is conditioned on ``fifo_prompt_windows(prompt_canvas, m, ...)[k]``,
-    the prompt under the clip slots the sample holds (``set_prompt`` into the same buffer).  The loop is eager.  The engine's limits
-    are ``step_slots``'s (eta == 0, no guide / control / consensus).
+    the prompt under the clip slots the sample holds (``set_prompt`` into the same buffer).  The engine's limits are ``step_slots``'s
+    (eta == 0, no guide / control / consensus).
+    ``graph`` (False, True or None; default False = the eager loop: per finished slot the host runs one ``set_prompt``, one
+    ``step_slots`` and one ``fifo_shift``): True replays the iterations from captured HIP graphs and returns the same bits.  The ramp
+    row, the prompt positions and the clip slot are then read off two int32 device cursors (``DenoiseEngine.fifo_open``;
+    include/avdiff_hip.h, "FIFO device cursors"), so an iteration is a fixed chain of launches; each phase takes its first iteration
+    eagerly through those kernels, replays a captured pair of iterations while two or more are left, and takes an odd last one
+    eagerly.  The graphs are captured per call and dropped with it: they hold the seed, the clip length, the hops and every address by
+    value.  None follows ``DenoiseEngine.run``'s rule: replay when 2 * B * N < ``GRAPH_BELOW_ROWS``.  ``step_slots``'s refusals are
+    raised before anything is captured.  Either way the returned canvas is a fresh tensor the caller owns (with ``graph`` the queue's
+    clip canvas, which the shift kernel wrote in place; no graph that could write it again outlives the call).
     The driver follows ``engine.solver``.  "dpmpp_2m" adds the ``t_last`` tables (``schedule_utils.fifo_plan_last``) and shifts with
     ``engine.fifo_shift``, which carries every slot's history along with it; ``x0_hist`` needs no initialisation, every slot's first
     step being first order.  The queue is as long as the schedule, so the faster solver's shorter schedule also means a shorter
@@ -234,6 +244,8 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
         raise ValueError(f"n_slots must be an int >= 1, got {n_slots!r}")
     if isinstance(prompt_hop, bool) or not isinstance(prompt_hop, int) or prompt_hop < 1:
         raise ValueError(f"prompt_hop must be an int >= 1 (prompt positions per target slot), got {prompt_hop!r}")
+    if graph is not None and not isinstance(graph, bool):
+        raise TypeError(f"graph must be True, False or None, got {graph!r}")
     B, S, sl = engine.embed.B, engine.slots, engine.slot_len
     ramp_now, ramp_prev, steady_now, steady_prev = su.fifo_plan(sched, S)
     n = ramp_now.shape[0] + 1
@@ -247,6 +259,10 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     dev = engine.device
     Lp = fifo_prompt_len(engine, prompt_canvas)
     pc = L.dev_f32(prompt_canvas.to(dev), "prompt canvas")
+    if graph is None:
+        graph = 2 * B * engine.N < engine.GRAPH_BELOW_ROWS
+    if graph:
+        return _fifo_denoise_graph(engine, engine.fifo_open(pc, prompt_hop, Lp, sched, n_slots, noise_seed))
     tabs = [t.to(dev) for t in (ramp_now, ramp_prev, steady_now, steady_prev)]
     multistep = engine.solver == "dpmpp_2m"
     ramp_last, steady_last = (t.to(dev) for t in su.fifo_plan_last(sched, S)) if multistep else (None, None)
@@ -263,6 +279,34 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
         z, popped = engine.fifo_shift(other, n + m, s0, seed=noise_seed)
         canvas[:, m * sl:(m + 1) * sl] = popped
     return canvas
+
+
+def _fifo_denoise_graph(engine: DenoiseEngine, q) -> torch.Tensor:
+    """``fifo_denoise``'s loop on an open queue (``DenoiseEngine.fifo_open``): per phase one eager iteration, captured pairs while
+    two or more iterations are left, an odd last one eagerly — all through the cursor kernels, so the cursors count every iteration."""
+    z, other = q.z, q.other
+    left = q.n - 1
+    if left:
+        engine.fifo_ramp(q, z, other)
+        z, other, left = other, z, left - 1
+    if left >= 2:
+        pair = engine.fifo_capture(q, False, z, other)
+        for _ in range(left // 2):
+            pair.replay()
+        left %= 2
+    if left:
+        engine.fifo_ramp(q, z, other)
+        z, other = other, z
+    engine.fifo_steady(q, z, other)
+    left = q.n_slots - 1
+    if left >= 2:
+        pair = engine.fifo_capture(q, True, z, other)
+        for _ in range(left // 2):
+            pair.replay()
+        left %= 2
+    if left:
+        engine.fifo_steady(q, z, other)
+    return q.clip
 
 
 @torch.no_grad()

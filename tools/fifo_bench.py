@@ -12,9 +12,11 @@
               history against the plain one; --e2e runs fifo_denoise on a dpmpp_2m engine at --steps (default 18: the multiple of S = 6
               nearest to 20; ddim: 48) and prints the time per finished slot and the ramp time
   --steps     --e2e: n, the schedule's steps = the queue's slots (a multiple of S = 6)
+  --graph     --e2e: fifo_denoise(graph=True) — the iterations replayed from captured HIP graphs, the ramp row, the prompt positions and
+              the clip slot read off device cursors — and the cost of the two captures themselves; without it the eager loop
 
 Prints plain text: the records are profiles/fifo_kernels.txt and profiles/fifo_e2e.txt (ddim), profiles/fifo_dpm_kernels.txt and
-profiles/fifo_dpm_e2e.txt (both solvers in one session)."""
+profiles/fifo_dpm_e2e.txt (both solvers in one session), profiles/fifo_graph_e2e.txt (--e2e with and without --graph)."""
 import argparse
 import ctypes as C
 import statistics
@@ -41,6 +43,7 @@ ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--launches", type=int, default=50)
 ap.add_argument("--slots-out", type=int, default=24, help="--e2e: finished slots per timed fifo_denoise call")
 ap.add_argument("--solver", choices=("ddim", "dpmpp_2m"), default="ddim")
+ap.add_argument("--graph", action="store_true", help="--e2e: replay the iterations from captured HIP graphs")
 ap.add_argument("--steps", type=int, default=None, help="--e2e: steps of the schedule = slots of the queue (default 48, dpmpp_2m: 18)")
 args = ap.parse_args()
 DPM = args.solver == "dpmpp_2m"
@@ -205,11 +208,12 @@ if args.e2e:
         torch.cuda.synchronize()
         return time.perf_counter() - t0, r
 
-    A.fifo_denoise(eng, canvas_p, hop_p, sched, 2, 5)                        # warm-up
-    print(f"fifo_denoise: solver {args.solver}, n = {n} steps, S = {S}, B = {B} (C3 latent, 8 layers, bf16x3, eager), {args.rounds} rounds")
+    A.fifo_denoise(eng, canvas_p, hop_p, sched, 4, 5, graph=args.graph)      # warm-up
+    print(f"fifo_denoise: solver {args.solver}, n = {n} steps, S = {S}, B = {B} (C3 latent, 8 layers, bf16x3, "
+          f"{'graph replay' if args.graph else 'eager'}), {args.rounds} rounds")
     whole = {}
     for K_ in (K, 2 * K):
-        ts_ = [timed(lambda: A.fifo_denoise(eng, canvas_p, hop_p, sched, K_, 5))[0] for _ in range(args.rounds)]
+        ts_ = [timed(lambda: A.fifo_denoise(eng, canvas_p, hop_p, sched, K_, 5, graph=args.graph))[0] for _ in range(args.rounds)]
         whole[K_] = statistics.median(ts_)
         print(f"  {K_:3d} slots out: " + " ".join(f"{t * 1e3:8.1f}" for t in ts_) + f" ms   ({K_ / statistics.median(ts_):6.1f} slots/s whole call, "
               f"ramp of {n - 1} steps included)")
@@ -217,6 +221,18 @@ if args.e2e:
     per_slot = (whole[2 * K] - whole[K]) / K
     print(f"  per finished slot (steady state, from the two clip lengths): {per_slot * 1e3:.3f} ms; ramp of {n - 1} steps: "
           f"{(whole[K] - K * per_slot) * 1e3:.1f} ms")
+    if args.graph:
+        # what the call pays for its two graphs: each capture on an open queue whose phase has run once (no replay: the cursors stay)
+        caps = {"ramp pair": [], "steady pair": []}
+        for _ in range(args.rounds):
+            q = eng.fifo_open(canvas_p, hop_p, fifo_prompt_len(eng, canvas_p), sched, K, 5)
+            eng.fifo_ramp(q, q.z, q.other)
+            eng.fifo_steady(q, q.other, q.z)
+            caps["ramp pair"].append(timed(lambda: eng.fifo_capture(q, False, q.other, q.z))[0])
+            caps["steady pair"].append(timed(lambda: eng.fifo_capture(q, True, q.other, q.z))[0])
+        print("  capture (torch.cuda.graph around two iterations, synchronise included): " +
+              "; ".join(f"{k} " + " ".join(f"{t * 1e3:6.2f}" for t in v) + " ms" for k, v in caps.items()))
+        sys.exit(0)
     # the parts of a steady iteration, each ended by a synchronise
     rn, rp, sn, sp = (t.to(dev) for t in su.fifo_plan(sched, S))
     sl = su.fifo_plan_last(sched, S)[1].to(dev) if DPM else None
