@@ -324,6 +324,40 @@ int avd_fifo_shift_hist_f32(const avd_noise_key* key, int64_t t, int64_t c, cons
                             const float* hist_in, float* hist_out, int B, int64_t outer, int slots, int slot_len, int64_t inner,
                             avd_stream_t stream);
 
+/* ---- FIFO lookahead: overlapping queue windows with held context (lookahead denoising, the second half of FIFO-Diffusion).
+ * With S = slots and a lookahead ctx in 0 .. S - 1, the first ctx slots of every sample are context only and h = S - ctx is the
+ * window stride, the number of slots a sample updates.
+ *   - the logical queue has Q = ctx + B*h slots: slots 0 .. ctx - 1 are the context (the most recently finished slots), slot ctx + a
+ *     is active slot a, a = 0 .. n - 1, n = B*h; active slot 0 is the head, n - 1 the tail (the schedule has n steps);
+ *   - window k is sample k of the batch and holds logical slots k*h .. k*h + S - 1: its first ctx slots are held by the step
+ *     (t_prev == t_now, "slot timesteps"), its last h slots step, and the stepping slots of all windows tile the active queue once;
+ *   - a logical slot lives in up to ceil(S / h) windows.  Its owner copy is the one in a stepping position: active slot a in window
+ *     a / h at slot ctx + a % h; context slot q in window 0 at slot q.  Every other copy is a read-only duplicate.
+ *   - the plan invariant (schedule_utils.fifo_lookahead_plan): a duplicate is held at the timestep its owner takes as t_now in the
+ *     same call, so every copy of a slot embeds the same timestep.
+ * One out-of-place launch keeps the copies coherent, pops the head and draws the tail.  Old[q], q < Q, is the owner copy of logical
+ * slot q in z_in; Old[Q] is the fresh tail, bit for bit the canvas-keyed normals avd_fifo_shift_f32 draws for clip slot c at
+ * timestep t.  With shift in {0, 1}:
+ *   z_out window k slot s = Old[k*h + s + shift];
+ *   shift == 1: popped [outer, slot_len, inner] = Old[ctx], the head the step has just finished, which is also what becomes context
+ *     slot ctx - 1; Old[0] is dropped;
+ *   shift == 0: nothing is popped (popped must be null) and nothing is drawn (key, t and c are not read): the launch only refreshes
+ *     every duplicate from its owner, which a queue's ramp needs after each of its steps.
+ * ctx == 0, shift == 1 gives the bits of avd_fifo_shift_f32.  A finished slot costs B = n/h sample-steps against n/S without
+ * lookahead: a factor S/h, 2 at ctx = S/2.
+ * Checked before the launch (AVD_EINVAL): 0 <= ctx < slots; shift in {0, 1}; popped null exactly when shift == 0; at shift == 1 the
+ * key, t and c as in avd_fifo_shift_f32; outer*inner < 2^34; no two buffers overlap.  All index arithmetic is 64-bit.  16-byte lanes
+ * when inner % 4 == 0 and every base is 16-byte aligned, one element per lane otherwise; same bits either way. */
+int avd_fifo_lookahead_f32(const avd_noise_key* key, int64_t t, int64_t c, int shift, const float* z_in, float* z_out, float* popped,
+                           int B, int64_t outer, int slots, int ctx, int slot_len, int64_t inner, avd_stream_t stream);
+/* FIFO lookahead with history (the x0_hist of the slot form of DPM-Solver++(2M)): (z_in -> z_out, popped) as above; hist_out at the
+ * stepping positions (s >= ctx) follows the same map from hist_in's owner copies, with zeros in the entering tail slot, and every
+ * context position (s < ctx) of hist_out is zero: held slots neither read nor write history, the zeros keep the buffer defined.
+ * ctx == 0, shift == 1 gives the bits of avd_fifo_shift_hist_f32.  The buffers must not overlap one another (AVD_EINVAL). */
+int avd_fifo_lookahead_hist_f32(const avd_noise_key* key, int64_t t, int64_t c, int shift, const float* z_in, float* z_out,
+                                float* popped, const float* hist_in, float* hist_out, int B, int64_t outer, int slots, int ctx,
+                                int slot_len, int64_t inner, avd_stream_t stream);
+
 /* ---- FIFO device cursors: the three host numbers of a FIFO iteration moved onto the device, so that a whole iteration is a fixed
  * chain of launches a HIP graph can hold.  A cursor is one int32 in device memory.  No entry below addresses by a cursor without the
  * clamp or the guard its contract names, so no cursor value makes a kernel leave its buffers; every entry only READS its cursor, and

@@ -151,6 +151,8 @@ SIGNATURES = {
     "avd_cfg_untoken_dpmpp_2m_audio_slots_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _I, _P, _P] + [_I] * 5 + [_P]),
     "avd_denoise_step_slots_dpmpp_2m_f32": (_I, [C.POINTER(StepDesc), _P, _P, _P, _P, _P, _I, _P, _P, _P, _L, _P]),
     "avd_fifo_shift_hist_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _P, _P, _P, _P, _P, _I, _L, _I, _I, _L, _P]),
+    "avd_fifo_lookahead_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _I, _P, _P, _P, _I, _L, _I, _I, _I, _L, _P]),
+    "avd_fifo_lookahead_hist_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _I, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _L, _P]),
     "avd_cursor_add": (_I, [_P, _I, _P]),
     "avd_slot_tables_select": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "avd_fifo_prompt_gather_f32": (_I, [_P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _P]),

@@ -662,6 +662,139 @@ int fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* 
     return AVD_OK;
 }
 
+// ------------------------------------------------------------------ FIFO lookahead (overlapping queue windows, held context)
+// The contract is written out in include/avdiff_hip.h ("FIFO lookahead").  Window b of the batch [B, outer, L, inner] holds logical
+// slots b * h .. b * h + S - 1 of a queue of Q = ctx + B * h slots, h = S - ctx.  Logical slot q is read from its owner copy: window 0
+// slot q for q < ctx, window (q - ctx) / h slot ctx + (q - ctx) % h otherwise.  One out-of-place launch writes z_out window b slot s =
+// Old[b * h + s + shift]; Old[Q] (shift == 1 only) is the fresh tail, fifo_shift_kernel's draw.  Lanes [0, n_out) write z_out (and
+// hist_out: the same source offset of hist_in on the stepping positions s >= ctx, zeros on the context positions and in the tail), lanes
+// [n_out, n_out + n_pop) write popped = Old[ctx] (n_pop == 0 at shift == 0).  V lanes as canvas_noise_kernel.
+template <int V, bool HIST>
+__global__ __launch_bounds__(256) void fifo_lookahead_kernel(const float* __restrict__ z_in, float* __restrict__ z_out,
+                                                             float* __restrict__ popped, const float* __restrict__ hist_in,
+                                                             float* __restrict__ hist_out, CanvasKey ck, uint32_t t, int B, int64_t outer,
+                                                             int S, int ctx, int shift, int slot_len, int64_t inner, int64_t n_out,
+                                                             int64_t n_pop) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n_out + n_pop) return;
+    const int64_t iv = inner / V;
+    const int L = S * slot_len;
+    const int h = S - ctx;
+    if (idx >= n_out) {      // popped[o, j, i] = the head's owner copy: window 0, slot ctx
+        const int64_t k = idx - n_out;
+        const int64_t i = (k % iv) * V;
+        const int64_t r = k / iv;
+        const int j = (int)(r % slot_len);
+        const int64_t o = r / slot_len;
+        const float* src = z_in + (o * L + (int64_t)ctx * slot_len + j) * inner + i;
+        if constexpr (V == 4) *reinterpret_cast<f32x4*>(popped + k * 4) = *reinterpret_cast<const f32x4*>(src);
+        else popped[k] = *src;
+        return;
+    }
+    const int64_t i = (idx % iv) * V;
+    int64_t r = idx / iv;
+    const int l = (int)(r % L);
+    r /= L;
+    const int64_t o = r % outer;
+    const int b = (int)(r / outer);
+    const int s = l / slot_len, j = l % slot_len;
+    const int64_t q = (int64_t)b * h + s + shift;      // the logical slot this position receives; q <= Q, and q == Q only at shift == 1
+    const bool keep = !HIST || s >= ctx;               // a context position carries no history
+    if (q < ctx + (int64_t)B * h) {
+        int64_t bs = 0, ss = q;                        // the owner copy of q
+        if (q >= ctx) {
+            bs = (q - ctx) / h;
+            ss = ctx + (q - ctx) % h;
+        }
+        const int64_t so = ((bs * outer + o) * L + ss * slot_len + j) * inner + i;
+        if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = *reinterpret_cast<const f32x4*>(z_in + so);
+        else z_out[idx] = z_in[so];
+        if constexpr (HIST) {      // s >= ctx gives q >= ctx: the source is a stepping position, where the history lives
+            if constexpr (V == 4)
+                *reinterpret_cast<f32x4*>(hist_out + idx * 4) = keep ? *reinterpret_cast<const f32x4*>(hist_in + so) : f32x4{0.f, 0.f, 0.f, 0.f};
+            else hist_out[idx] = keep ? hist_in[so] : 0.f;
+        }
+    } else {                 // the tail slot: fresh noise of clip slot c, no history yet
+        const f32x4 v = canvas_normal4(ck, 0, o, j, i, inner, t);
+        if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = v;
+        else z_out[idx] = v[(int)((o * inner + i) & 3)];
+        if constexpr (HIST) {
+            if constexpr (V == 4) *reinterpret_cast<f32x4*>(hist_out + idx * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+            else hist_out[idx] = 0.f;
+        }
+    }
+}
+
+// hist_in / hist_out: both null or both set.  shift == 0 refreshes the duplicates only: key, t and c are not read, popped must be null
+int fifo_lookahead_f32(const avd_noise_key* key, int64_t t, int64_t c, int shift, const float* z_in, float* z_out, float* popped, int B,
+                       int64_t outer, int S, int ctx, int slot_len, int64_t inner, hipStream_t st, const float* hist_in = nullptr,
+                       float* hist_out = nullptr) {
+    AVD_REQUIRE(shift == 0 || shift == 1, AVD_EINVAL, "fifo_lookahead: shift must be 0 or 1 (got %d)", shift);
+    AVD_REQUIRE(z_in && z_out, AVD_EINVAL, "fifo_lookahead: null pointer");
+    AVD_REQUIRE(!hist_in == !hist_out, AVD_EINVAL, "fifo_lookahead: hist_in and hist_out go together");
+    AVD_REQUIRE(B > 0 && outer > 0 && S > 0 && slot_len > 0 && inner > 0, AVD_EINVAL,
+                "fifo_lookahead: bad dims (B %d, outer %lld, S %d, slot_len %d, inner %lld)", B, (long long)outer, S, slot_len,
+                (long long)inner);
+    AVD_REQUIRE(ctx >= 0 && ctx < S, AVD_EINVAL, "fifo_lookahead: ctx %d must lie in [0, slots %d)", ctx, S);
+    AVD_REQUIRE((int64_t)S * slot_len <= 0x7fffffff && (int64_t)B * S <= 0x7fffffff, AVD_EINVAL,
+                "fifo_lookahead: S %d * slot_len %d and B %d * S must fit an int", S, slot_len, B);
+    if (shift) {
+        AVD_REQUIRE(key, AVD_EINVAL, "fifo_lookahead: null noise key");
+        AVD_REQUIRE(popped, AVD_EINVAL, "fifo_lookahead: null popped at shift 1");
+        AVD_REQUIRE(t >= 0 && t < ((int64_t)1 << 32), AVD_EINVAL, "fifo_lookahead: the noise timestep %lld must lie in [0, 2^32)",
+                    (long long)t);
+        const int64_t lim = (int64_t)1 << 32;
+        AVD_REQUIRE(c >= 0 && c < lim && c + 1 <= lim / slot_len, AVD_EINVAL,
+                    "fifo_lookahead: (c %lld + 1) * slot_len %d must lie in [1, 2^32]", (long long)c, slot_len);
+    } else
+        AVD_REQUIRE(!popped, AVD_EINVAL, "fifo_lookahead: nothing is popped at shift 0, popped must be null");
+    AVD_REQUIRE(outer <= (((int64_t)1 << 34) - 1) / inner, AVD_EINVAL, "fifo_lookahead: outer %lld * inner %lld must be < 2^34",
+                (long long)outer, (long long)inner);
+    AVD_REQUIRE((double)B * (double)outer * (double)S * (double)slot_len * (double)inner < 9.0e18, AVD_EUNSUPPORTED,
+                "fifo_lookahead: too many values");
+    const int64_t total = (int64_t)B * outer * S * slot_len * inner, pop = shift ? outer * slot_len * inner : 0;
+    AVD_REQUIRE(!overlaps(z_in, z_out, total), AVD_EINVAL, "fifo_lookahead: z_out must not overlap z_in (one out-of-place launch)");
+    if (shift)
+        AVD_REQUIRE(!(popped < z_in + total && z_in < popped + pop) && !(popped < z_out + total && z_out < popped + pop), AVD_EINVAL,
+                    "fifo_lookahead: popped must not overlap z_in or z_out");
+    if (hist_in) {
+        AVD_REQUIRE(!overlaps(hist_in, hist_out, total), AVD_EINVAL, "fifo_lookahead: hist_out must not overlap hist_in (one out-of-place launch)");
+        AVD_REQUIRE(!overlaps(hist_out, z_in, total) && !overlaps(hist_out, z_out, total) && !overlaps(hist_in, z_out, total) &&
+                    !overlaps(hist_in, z_in, total), AVD_EINVAL, "fifo_lookahead: hist_in and hist_out must not overlap z_in or z_out");
+        if (shift)
+            AVD_REQUIRE(!(popped < hist_in + total && hist_in < popped + pop) && !(popped < hist_out + total && hist_out < popped + pop),
+                        AVD_EINVAL, "fifo_lookahead: popped must not overlap hist_in or hist_out");
+    }
+    const bool vec = inner % 4 == 0 && aligned16(z_in) && aligned16(z_out) && aligned16(popped) && aligned16(hist_in) && aligned16(hist_out);
+    const int v = vec ? 4 : 1;
+    const int64_t n_out = total / v, n_pop = pop / v;
+    AVD_REQUIRE((n_out + n_pop + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "fifo_lookahead: %lld lanes are too many for one launch",
+                (long long)(n_out + n_pop));
+    CanvasKey ck{0u, 0u, 0u, (uint32_t)slot_len};
+    if (shift) ck = CanvasKey{(uint32_t)(key->seed & 0xffffffffu), (uint32_t)(key->seed >> 32), (uint32_t)c, (uint32_t)slot_len};
+    static const int tags[4] = {prof_tag_id("fifo_lookahead_kernel<1>"), prof_tag_id("fifo_lookahead_kernel<4>"),
+                                prof_tag_id("fifo_lookahead_kernel<1, hist>"), prof_tag_id("fifo_lookahead_kernel<4, hist>")};
+    // every owner read once (the duplicates' reads hit the cache), B * S slots written; twice that with the history; the popped slot
+    const double slot = (double)outer * slot_len * (double)inner, Q = (double)ctx + (double)B * (S - ctx);
+    ProfScope prof(tags[(hist_in ? 2 : 0) + (vec ? 1 : 0)], 4.0 * ((hist_in ? 2.0 : 1.0) * (Q + (double)B * S) * slot + (double)pop), st);
+    const dim3 grid((unsigned)((n_out + n_pop + 255) / 256));
+    if (hist_in) {
+        if (vec)
+            hipLaunchKernelGGL((fifo_lookahead_kernel<4, true>), grid, dim3(256), 0, st, z_in, z_out, popped, hist_in, hist_out, ck,
+                               (uint32_t)t, B, outer, S, ctx, shift, slot_len, inner, n_out, n_pop);
+        else
+            hipLaunchKernelGGL((fifo_lookahead_kernel<1, true>), grid, dim3(256), 0, st, z_in, z_out, popped, hist_in, hist_out, ck,
+                               (uint32_t)t, B, outer, S, ctx, shift, slot_len, inner, n_out, n_pop);
+    } else if (vec)
+        hipLaunchKernelGGL((fifo_lookahead_kernel<4, false>), grid, dim3(256), 0, st, z_in, z_out, popped, hist_in, hist_out, ck,
+                           (uint32_t)t, B, outer, S, ctx, shift, slot_len, inner, n_out, n_pop);
+    else
+        hipLaunchKernelGGL((fifo_lookahead_kernel<1, false>), grid, dim3(256), 0, st, z_in, z_out, popped, hist_in, hist_out, ck,
+                           (uint32_t)t, B, outer, S, ctx, shift, slot_len, inner, n_out, n_pop);
+    AVD_CHECK_LAUNCH("fifo_lookahead");
+    return AVD_OK;
+}
+
 // ------------------------------------------------------------------ device cursors of the FIFO queue
 // The contracts are written out in include/avdiff_hip.h ("FIFO device cursors").  A cursor is one int32 on the device; no kernel below
 // addresses by it without a clamp or a guard, and it moves only in cursor_add_kernel, a launch of its own behind its last reader.
@@ -2311,6 +2444,18 @@ extern "C" int avd_fifo_shift_cursor_hist_f32(const avd_noise_key* key, int64_t 
     AVD_REQUIRE(hist_in && hist_out, AVD_EINVAL, "fifo_shift_cursor_hist: null hist_in or hist_out");
     return fifo_shift_f32(key, t, c0, z_in, z_out, clip, B, outer, slots, slot_len, inner, static_cast<hipStream_t>(stream), hist_in, hist_out,
                           cursor, n_out);
+}
+extern "C" int avd_fifo_lookahead_f32(const avd_noise_key* key, int64_t t, int64_t c, int shift, const float* z_in, float* z_out,
+                                      float* popped, int B, int64_t outer, int slots, int ctx, int slot_len, int64_t inner,
+                                      avd_stream_t stream) {
+    return fifo_lookahead_f32(key, t, c, shift, z_in, z_out, popped, B, outer, slots, ctx, slot_len, inner, static_cast<hipStream_t>(stream));
+}
+extern "C" int avd_fifo_lookahead_hist_f32(const avd_noise_key* key, int64_t t, int64_t c, int shift, const float* z_in, float* z_out,
+                                           float* popped, const float* hist_in, float* hist_out, int B, int64_t outer, int slots, int ctx,
+                                           int slot_len, int64_t inner, avd_stream_t stream) {
+    AVD_REQUIRE(hist_in && hist_out, AVD_EINVAL, "fifo_lookahead_hist: null hist_in or hist_out");
+    return fifo_lookahead_f32(key, t, c, shift, z_in, z_out, popped, B, outer, slots, ctx, slot_len, inner, static_cast<hipStream_t>(stream),
+                              hist_in, hist_out);
 }
 extern "C" int avd_cursor_add(int32_t* cursor, int delta, avd_stream_t stream) {
     AVD_REQUIRE(cursor, AVD_EINVAL, "cursor_add: null cursor");

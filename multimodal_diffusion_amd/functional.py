@@ -641,6 +641,60 @@ def fifo_shift(z: Tensor, c: int, seed: int, t: int, slot_len: int, hist: Option
     return out, popped, hist_out
 
 
+def fifo_lookahead(z: Tensor, ctx: int, shift: int, slot_len: int, c: Optional[int] = None, seed: Optional[int] = None,
+                   t: Optional[int] = None, hist: Optional[Tensor] = None, hist_out: Optional[Tensor] = None):
+    """The queue step of FIFO lookahead denoising (avd_fifo_lookahead_f32 / _hist_f32; contract in include/avdiff_hip.h, "FIFO
+    lookahead"): ``z`` ([B,C,T,H,W] video, [B,Ca,F] audio, sliding length L = S * slot_len) is B overlapping windows of a logical
+    queue of ctx + B * (S - ctx) slots, window k holding logical slots k * (S - ctx) .. + S - 1, its first ``ctx`` slots context only.
+    Returns (z_out, popped): z_out window k slot s = the owner copy of logical slot k * (S - ctx) + s + shift.
+    ``shift=1``: the queue moves by one slot; popped ([C, slot_len, H, W] or [Ca, slot_len]) is the head, which becomes the last
+    context slot, and the tail holds the seeded normals of clip slot ``c`` at timestep ``t`` (``fifo_shift``'s draw; ``c``, ``seed``
+    and ``t`` are required).  ``shift=0``: only the duplicates are refreshed from their owners; popped is None and ``c``, ``seed``,
+    ``t`` must be left None.  ``ctx=0, shift=1`` gives ``fifo_shift``'s bits.
+    With ``hist`` (as in ``fifo_shift``) the result is (z_out, popped, hist_out): the history follows the same map on the stepping
+    positions, zeros in the entering tail slot and on every context position."""
+    z = L.dev_f32(z, "z")
+    if hist is None and hist_out is not None:
+        raise ValueError("hist_out goes with hist")
+    if hist is not None and not (hist.is_cuda and hist.dtype == torch.float32 and hist.is_contiguous() and hist.shape == z.shape and
+                                 hist.device == z.device):
+        raise ValueError(f"hist must be a contiguous float32 tensor of z's shape {tuple(z.shape)} on z's device")
+    outer, L_, inner = window_dims(z.shape)
+    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or L_ % slot_len:
+        raise ValueError(f"slot_len must be an int >= 1 that divides the sliding length {L_}, got {slot_len!r}")
+    S = L_ // slot_len
+    if isinstance(ctx, bool) or not isinstance(ctx, int) or not 0 <= ctx < S:
+        raise ValueError(f"the lookahead ctx must be an int in [0, S = {S}), got {ctx!r}")
+    if isinstance(shift, bool) or shift not in (0, 1):
+        raise ValueError(f"shift must be 0 or 1, got {shift!r}")
+    popped, key = None, None
+    if shift:
+        for name, v in (("c", c), ("t", t)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"{name} must be an int >= 0 at shift=1, got {v!r}")
+        if (c + 1) * slot_len > 2 ** 32:
+            raise ValueError(f"(c {c} + 1) * slot_len {slot_len} exceeds the stream's 2**32 canvas positions")
+        if seed is None:
+            raise ValueError("shift=1 draws the entering slot's noise from a seed: pass one")
+        key = C.byref(noise_key(seed, 0))
+        popped = torch.empty((z.shape[1], slot_len) + tuple(z.shape[3:]), device=z.device, dtype=torch.float32)
+    elif c is not None or seed is not None or t is not None:
+        raise ValueError("shift=0 draws nothing: leave c, seed and t None")
+    out = torch.empty_like(z)
+    head = (key, t or 0, c or 0, shift, z.data_ptr(), out.data_ptr(), L.ptr(popped))
+    tail = (z.shape[0], outer, S, ctx, slot_len, inner, _st(z))
+    if hist is None:
+        L.check(L.lib().avd_fifo_lookahead_f32(*head, *tail))
+        return out, popped
+    if hist_out is None:
+        hist_out = torch.empty_like(hist)
+    elif not (hist_out.is_cuda and hist_out.dtype == torch.float32 and hist_out.is_contiguous() and hist_out.shape == hist.shape and
+              hist_out.device == hist.device):
+        raise ValueError(f"hist_out must be a contiguous float32 tensor of hist's shape {tuple(hist.shape)} on its device")
+    L.check(L.lib().avd_fifo_lookahead_hist_f32(*head, hist.data_ptr(), hist_out.data_ptr(), *tail))
+    return out, popped, hist_out
+
+
 # ---- FIFO device cursors (include/avdiff_hip.h, "FIFO device cursors"): the host numbers of a FIFO iteration read off the device ----
 def _cursor(cursor: Tensor, device: torch.device) -> Tensor:
     if not (isinstance(cursor, Tensor) and cursor.is_cuda and cursor.dtype == torch.int32 and cursor.numel() == 1 and

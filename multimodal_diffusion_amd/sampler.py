@@ -218,6 +218,9 @@ class DenoiseEngine:
     ``fifo_open`` / ``fifo_ramp`` / ``fifo_steady`` / ``fifo_capture`` (extension: a FIFO queue whose iterations read the ramp row and
     the clip slot off device cursors, include/avdiff_hip.h, "FIFO device cursors"): what ``fifo_denoise(graph=True)`` replays.  An
     iteration is the same chain of launches eagerly and under capture; a captured pair belongs to the queue it was captured on.
+
+    ``fifo_lookahead(z, ctx, shift, ...)`` (extension: overlapping queue windows with held context, include/avdiff_hip.h, "FIFO
+    lookahead"): the queue step of ``fifo_denoise(lookahead=ctx)``; it moves ``x0_hist`` as ``fifo_shift`` does.
     """
 
     SOLVERS = ("ddim", "dpmpp_2m")
@@ -842,6 +845,27 @@ class DenoiseEngine:
         self.x0_hist, self._hist_other = self._hist_other, self.x0_hist
         self._generation += 1
         self._stale_reason = "fifo_shift moved the solver history into the engine's other history buffer (x0_hist changed its address)"
+        return z_out, popped
+
+    def fifo_lookahead(self, z: torch.Tensor, ctx: int, shift: int, c: Optional[int] = None, t: Optional[int] = None,
+                       seed: Optional[int] = None):
+        """The queue step of FIFO lookahead denoising on this engine's queue (``functional.fifo_lookahead`` with the engine's
+        ``slot_len``; include/avdiff_hip.h, "FIFO lookahead"): returns (z_out, popped), popped None at ``shift=0`` (the refresh of the
+        duplicates, which takes no ``c`` / ``t`` / ``seed``).  At ``shift=1`` ``seed`` None is the engine's ``noise_seed``.  Solver
+        "dpmpp_2m": as in ``fifo_shift`` the same launch moves the history into the engine's second buffer, which becomes ``x0_hist``,
+        and a new graph generation starts — at either ``shift``, the launch being out of place."""
+        if shift == 1:
+            seed = self.noise_seed if seed is None else seed
+            if seed is None:
+                raise ValueError("fifo_lookahead draws the entering slot's noise from a seed: pass one, or build the engine with noise_seed")
+        if self.solver != "dpmpp_2m":
+            return Fn.fifo_lookahead(z, ctx, shift, self.slot_len, c=c, seed=seed, t=t)
+        if self._hist_other is None:
+            self._hist_other = torch.empty_like(self.x0_hist)
+        z_out, popped, _ = Fn.fifo_lookahead(z, ctx, shift, self.slot_len, c=c, seed=seed, t=t, hist=self.x0_hist, hist_out=self._hist_other)
+        self.x0_hist, self._hist_other = self._hist_other, self.x0_hist
+        self._generation += 1
+        self._stale_reason = "fifo_lookahead moved the solver history into the engine's other history buffer (x0_hist changed its address)"
         return z_out, popped
 
     # ---- FIFO queue with device cursors: an iteration as a fixed chain of launches (include/avdiff_hip.h, "FIFO device cursors") ----

@@ -241,6 +241,82 @@ def fifo_plan_last(sched, S: int):
     return ramp_last.view_as(ramp_now).clone(), steady_last
 
 
+def _lookahead_tables(sched, S: int, ctx: int, context: str):
+    """(ramp, steady) of the lookahead plan per LOGICAL slot, each a (t_now, t_prev, t_last) triple of int64 tensors [n-1, Q] /
+    [ctx+1, Q] with Q = ctx + n, and the window index map [B, S] of the logical slot every window position holds"""
+    S = _whole(S, "S")
+    if isinstance(ctx, bool) or not isinstance(ctx, int) or not 0 <= ctx < S:
+        raise ValueError(f"fifo_lookahead_plan: the lookahead ctx must be an int in [0, S = {S}), got {ctx!r}")
+    if context not in ("noise", "clean"):
+        raise ValueError(f"fifo_lookahead_plan: context must be 'noise' or 'clean', got {context!r}")
+    h = S - ctx
+    fifo_plan(sched, 1)                                       # the schedule's own refusals
+    s = torch.as_tensor(sched).reshape(-1).to("cpu", torch.long)
+    n = s.numel() - 1
+    if n % h:
+        raise ValueError(f"fifo_lookahead_plan: the {n} steps of the schedule must be a multiple of the h = S - ctx = {h} slots a "
+                         "window updates (the queue is n active slots in n / h windows)")
+    B = n // h
+    s0 = int(s[0])
+    last = torch.cat([torch.tensor([-1]), s[:n - 1]])         # last[i] = s_{i-1}
+    a = torch.arange(n)
+    # ramp, active slots: fifo_plan's rows at one slot per sample, with fifo_plan_last's third table
+    r = torch.arange(n - 1)[:, None]
+    live = a[None, :] <= r
+    i = (r - a[None, :]).clamp(min=0)
+    hold = torch.full((n - 1, n), s0, dtype=torch.long)
+    act = (torch.where(live, s[i], hold), torch.where(live, s[i + 1], hold), torch.where(live, last[i], torch.full_like(hold, -1)))
+    c0 = torch.full((n - 1, ctx), 0 if context == "clean" else s0, dtype=torch.long)
+    ramp = (torch.cat([c0, act[0]], 1), torch.cat([c0, act[1]], 1), torch.cat([torch.full_like(c0, -1), act[2]], 1))
+    # steady, row min(m, ctx): context slot q is a finished slot once q >= ctx - m ("clean": always)
+    m = torch.arange(ctx + 1)[:, None]
+    done = (torch.arange(ctx)[None, :] >= ctx - m) | (context == "clean")
+    cm = torch.where(done, torch.zeros((), dtype=torch.long), torch.full((), s0, dtype=torch.long)).expand(ctx + 1, ctx)
+    rows = lambda t: t[None, :].expand(ctx + 1, n)
+    steady = (torch.cat([cm, rows(s[n - 1 - a])], 1), torch.cat([cm, rows(s[n - a])], 1),
+              torch.cat([torch.full_like(cm, -1), rows(last[n - 1 - a])], 1))
+    q = torch.arange(B)[:, None] * h + torch.arange(S)[None, :]      # window k position s holds logical slot k*h + s
+    return ramp, steady, q, ctx
+
+
+def _lookahead_windows(tabs, q, ctx: int, which: int) -> torch.Tensor:
+    """per-logical-slot triples -> the [rows, B, S] table `which` (0 t_now, 1 t_prev, 2 t_last): a stepping position (s >= ctx) takes
+    its slot's entry, a held one (s < ctx) t_now for t_now and t_prev — the duplicate-label invariant — and -1 for t_last"""
+    held = (torch.arange(q.shape[1]) < ctx)[None, None, :]
+    now, own = tabs[0][:, q], tabs[which][:, q]
+    if which == 2:
+        return torch.where(held, torch.full_like(own, -1), own).contiguous()
+    return torch.where(held, now, own).contiguous()
+
+
+def fifo_lookahead_plan(sched, S: int, ctx: int, context: str = "noise"):
+    """The timestep tables of FIFO lookahead denoising (Kim et al. 2024; layout in include/avdiff_hip.h, "FIFO lookahead") for
+    ``DenoiseEngine.step_slots``.  ``sched`` = s_0 > ... > s_n = -1 as for ``fifo_plan``; ``S`` slots per sample, of which the first
+    ``ctx`` (0 <= ctx < S) are held context and the last h = S - ctx step; n % h == 0 and the batch is B = n // h windows.  Window k
+    holds logical slots k*h .. k*h + S - 1 of a queue of ctx context slots and n active ones (active slot a = logical slot ctx + a).
+
+    The invariant of every row: a duplicate (a window's position s < ctx) is held at the timestep its slot's owner takes as t_now in
+    the same call, so every copy of a slot embeds the same timestep.
+    ramp, row r = 0 .. n-2: active slot a <= r takes step r-a, a > r holds at s_0; the context holds at s_0 (``context="noise"``: the
+      initial context is seeded noise, labelled as noise like any slot waiting in the ramp) or at 0 (``"clean"``: supplied latents);
+    steady, row min(m, ctx) for iteration m: active slot a takes (s_{n-1-a}, s_{n-a}); context slot q holds at 0 once it is a
+      finished slot — "noise": q >= ctx - m, "clean": always — else at s_0.
+
+    Returns (ramp_now, ramp_prev, steady_now, steady_prev): int64 CPU tensors [n-1, B, S] x 2 and [ctx+1, B, S] x 2.  ``ctx = 0`` gives
+    ``fifo_plan``'s tables (the steady ones as one row).  Refuses what ``fifo_plan`` refuses.  Host-side."""
+    ramp, steady, q, ctx = _lookahead_tables(sched, S, ctx, context)
+    return (_lookahead_windows(ramp, q, ctx, 0), _lookahead_windows(ramp, q, ctx, 1), _lookahead_windows(steady, q, ctx, 0),
+            _lookahead_windows(steady, q, ctx, 1))
+
+
+def fifo_lookahead_plan_last(sched, S: int, ctx: int, context: str = "noise"):
+    """The third table of ``fifo_lookahead_plan`` for solver "dpmpp_2m": ``fifo_plan_last``'s values on the stepping positions (s_{i-1}
+    where the slot takes step i, -1 at step 0 and while it waits in the ramp) and -1 on every held position.  Returns (ramp_last
+    [n-1, B, S], steady_last [ctx+1, B, S]), int64 CPU tensors."""
+    ramp, steady, q, ctx = _lookahead_tables(sched, S, ctx, context)
+    return _lookahead_windows(ramp, q, ctx, 2), _lookahead_windows(steady, q, ctx, 2)
+
+
 def resample_from_config(scfg) -> Optional[Tuple[int, int]]:
     """``sampling.resample`` of a config: {jump:, resamples:}; a missing key or None means no resampling."""
     return check_resample(scfg.get("resample"))

@@ -21,7 +21,9 @@ et al. 2023; ``avd_window_consensus_f32``), so they stay one batch and finish as
 
 Extension (``fifo_denoise``): FIFO diagonal denoising, the other family of long-form samplers.  Instead of windows that share one
 timestep, a queue of latent slots runs from nearly clean to pure noise, one model call moves every slot one level
-(``DenoiseEngine.step_slots``), the head leaves finished and noise enters at the tail (``functional.fifo_shift``).
+(``DenoiseEngine.step_slots``), the head leaves finished and noise enters at the tail (``functional.fifo_shift``).  With
+``lookahead=`` the samples are overlapping windows of the queue whose leading slots are held context (``functional.fifo_lookahead``), and
+``context=`` continues an existing clip.
 """
 from __future__ import annotations
 
@@ -170,22 +172,31 @@ def canvas_from_windows(windows: torch.Tensor, hop: int) -> torch.Tensor:
     return canvas
 
 
-def fifo_prompt_windows(prompt_canvas: torch.Tensor, m: int, B: int, S: int, prompt_hop: int, prompt_len: int) -> torch.Tensor:
+def fifo_prompt_windows(prompt_canvas: torch.Tensor, m: int, B: int, S: int, prompt_hop: int, prompt_len: int,
+                        stride: Optional[int] = None, first: Optional[int] = None) -> torch.Tensor:
     """The prompt batch of ``fifo_denoise`` before the step of steady iteration ``m``: sample k is prompt positions (m + k*S) *
     prompt_hop .. + prompt_len - 1 of the canvas's sliding axis ([C, P, H, W] video prompt, [Ca, P] audio prompt), zeros beyond the
-    canvas end.  Returns [B, C, prompt_len, H, W] / [B, Ca, prompt_len] on the canvas's device (any device: pure slicing)."""
+    canvas end.  Returns [B, C, prompt_len, H, W] / [B, Ca, prompt_len] on the canvas's device (any device: pure slicing).
+    ``stride`` (None = S) and ``first`` (None = m; may be negative) generalise it to sample k at positions (first + k*stride) *
+    prompt_hop ..: the overlapping windows of the lookahead queue (stride = S - ctx, first = m - ctx).  Positions before the canvas
+    start are zeros like those past its end."""
     if prompt_canvas.dim() not in (2, 4):
         raise ValueError(f"a prompt canvas is [C, P, H, W] (video) or [Ca, P] (audio), got shape {tuple(prompt_canvas.shape)}")
     if min(B, S, prompt_hop, prompt_len) < 1 or m < 0:
         raise ValueError(f"fifo_prompt_windows: need B, S, prompt_hop, prompt_len >= 1 and m >= 0 (got {B}, {S}, {prompt_hop}, "
                          f"{prompt_len}, {m})")
+    for name, v in (("stride", stride), ("first", first)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or (name == "stride" and v < 1)):
+            raise ValueError(f"fifo_prompt_windows: {name} must be an int{' >= 1' if name == 'stride' else ''} or None, got {v!r}")
+    stride = S if stride is None else stride
+    first = m if first is None else first
     P_ = prompt_canvas.shape[1]
     out = prompt_canvas.new_zeros((B, prompt_canvas.shape[0], prompt_len) + tuple(prompt_canvas.shape[2:]))
     for k in range(B):
-        p0 = (m + k * S) * prompt_hop
-        n = max(0, min(prompt_len, P_ - p0))
-        if n:
-            out[k, :, :n] = prompt_canvas[:, p0:p0 + n]
+        p0 = (first + k * stride) * prompt_hop
+        lo, hi = max(p0, 0), min(p0 + prompt_len, P_)              # the canvas positions the window covers
+        if hi > lo:
+            out[k, :, lo - p0:hi - p0] = prompt_canvas[:, lo:hi]
     return out
 
 
@@ -210,7 +221,7 @@ def fifo_prompt_len(engine: DenoiseEngine, prompt_canvas: torch.Tensor) -> int:
 
 @torch.no_grad()
 def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop: int, sched, n_slots: int, noise_seed: int,
-                 graph: Optional[bool] = False) -> torch.Tensor:
+                 graph: Optional[bool] = False, lookahead: int = 0, context: Optional[torch.Tensor] = None) -> torch.Tensor:
     """FIFO diagonal denoising (FIFO-Diffusion, Kim et al. 2024, with latent partitioning): a clip of ``n_slots`` slots of
     ``engine.slot_len`` latent positions, denoised in a queue whose slots sit at different noise levels.  Returns the finished latent
     canvas [C, n_slots * slot_len, H, W] (video target) or [Ca, n_slots * slot_len] (audio target).
@@ -237,7 +248,21 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     The driver follows ``engine.solver``.  "dpmpp_2m" adds the ``t_last`` tables (``schedule_utils.fifo_plan_last``) and shifts with
     ``engine.fifo_shift``, which carries every slot's history along with it; ``x0_hist`` needs no initialisation, every slot's first
     step being first order.  The queue is as long as the schedule, so the faster solver's shorter schedule also means a shorter
-    queue, a shorter ramp and fewer sample-steps per finished slot."""
+    queue, a shorter ramp and fewer sample-steps per finished slot.
+    ``lookahead`` = ctx > 0 (ctx < S, else ValueError) is FIFO lookahead denoising (the paper's second half; layout and plan in
+    include/avdiff_hip.h, "FIFO lookahead", and ``schedule_utils.fifo_lookahead_plan``): the engine's samples are overlapping windows of
+    the queue, h = S - ctx slots apart; the first ctx slots of every window are held context, the cleaner slots in front of the h slots
+    the window updates, and ctx context slots before the head keep the most recently finished slots in view.  ``sched`` then has n =
+    batch * h steps.  The queue starts as canvas-keyed noise at s_0: clip slot c >= 0 from the normals it starts from without
+    lookahead, context slot q from those of canvas positions (q - ctx) * slot_len + j modulo 2^32, the positions just before the clip.
+    The ramp is n - 1 times ``step_slots`` + ``engine.fifo_lookahead(shift=0)`` (the refresh of the duplicates), every steady iteration
+    ``set_prompt`` -> ``step_slots`` on row min(m, ctx) of the plan -> ``engine.fifo_lookahead(shift=1)``, whose popped head goes into
+    the clip.  Window k at steady iteration m is conditioned on prompt positions (m - ctx + k*h) * prompt_hop .. (the ramp: m = 0),
+    zeros before the canvas start and past its end.  A finished slot costs batch = n / h sample-steps against n / S without lookahead:
+    a factor S / h, 2 at ctx = S / 2.  Eager only: ``graph=True`` is refused before anything is allocated, None runs eagerly.
+    ``context`` (with ``lookahead`` only): the clean latent of the ctx slots before the clip, [C, ctx * slot_len, H, W] (video) or
+    [Ca, ctx * slot_len] (audio).  It fills the context slots at the start, labelled clean (the "clean" plan): the clip continues an
+    existing one.  The prompt under a supplied context is zeros.  ``lookahead=0`` is the queue above, launch for launch."""
     if not isinstance(engine, DenoiseEngine):
         raise TypeError("fifo_denoise drives a DenoiseEngine")
     if isinstance(n_slots, bool) or not isinstance(n_slots, int) or n_slots < 1:
@@ -246,6 +271,14 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
         raise ValueError(f"prompt_hop must be an int >= 1 (prompt positions per target slot), got {prompt_hop!r}")
     if graph is not None and not isinstance(graph, bool):
         raise TypeError(f"graph must be True, False or None, got {graph!r}")
+    if isinstance(lookahead, bool) or not isinstance(lookahead, int) or not 0 <= lookahead < engine.slots:
+        raise ValueError(f"lookahead must be an int in [0, S = {engine.slots}): the context slots of a window of S, got {lookahead!r}")
+    if lookahead:
+        if graph:
+            raise ValueError("fifo_denoise(lookahead > 0) runs eagerly: the lookahead queue has no device cursors, graph=True is refused")
+        return _fifo_denoise_lookahead(engine, prompt_canvas, prompt_hop, sched, n_slots, noise_seed, lookahead, context)
+    if context is not None:
+        raise ValueError("context is the clean latent of the lookahead's context slots: it needs lookahead > 0")
     B, S, sl = engine.embed.B, engine.slots, engine.slot_len
     ramp_now, ramp_prev, steady_now, steady_prev = su.fifo_plan(sched, S)
     n = ramp_now.shape[0] + 1
@@ -277,6 +310,59 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
             engine.set_prompt(fifo_prompt_windows(pc, m, B, S, prompt_hop, Lp))
         other = engine.step_slots(z, tabs[2], tabs[3], out=other, t_last=steady_last)
         z, popped = engine.fifo_shift(other, n + m, s0, seed=noise_seed)
+        canvas[:, m * sl:(m + 1) * sl] = popped
+    return canvas
+
+
+def _fifo_denoise_lookahead(engine: DenoiseEngine, prompt_canvas, prompt_hop: int, sched, n_slots: int, noise_seed: int, ctx: int,
+                            context: Optional[torch.Tensor]) -> torch.Tensor:
+    """``fifo_denoise(lookahead=ctx > 0)``: the eager loop over overlapping windows (the contract is in ``fifo_denoise``)"""
+    B, S, sl = engine.embed.B, engine.slots, engine.slot_len
+    h = S - ctx
+    ramp_now, ramp_prev, steady_now, steady_prev = su.fifo_lookahead_plan(sched, S, ctx, "noise" if context is None else "clean")
+    n = ramp_now.shape[0] + 1
+    if n != B * h:
+        raise ValueError(f"the schedule has {n} steps, the engine's queue {B} windows x {h} stepping slots = {B * h}: fifo_denoise needs "
+                         "them equal")
+    outer, L_, _ = Fn.window_dims(engine.latent_shape)
+    if L_ != S * sl:
+        raise ValueError(f"the engine's sliding length {L_} is not {S} slots of {sl} positions (an uncovered audio tail cannot queue)")
+    Fn.noise_key(noise_seed, 0)
+    if (n + n_slots) * sl > 2 ** 32 - ctx * sl:
+        raise ValueError(f"(n {n} + n_slots {n_slots} + ctx {ctx}) * slot_len {sl} exceeds the stream's 2**32 canvas positions")
+    hw = tuple(engine.latent_shape[3:])
+    if context is not None and not (isinstance(context, torch.Tensor) and tuple(context.shape) == (outer, ctx * sl) + hw):
+        raise ValueError(f"context must be the clean latent of the {ctx} slots before the clip, shape {(outer, ctx * sl) + hw}, got "
+                         f"{tuple(context.shape) if isinstance(context, torch.Tensor) else context!r}")
+    multistep = engine.solver == "dpmpp_2m"
+    engine._slot_refusals(multistep)
+    s0 = int(torch.as_tensor(sched).reshape(-1)[0])
+    dev = engine.device
+    Lp = fifo_prompt_len(engine, prompt_canvas)
+    pc = L.dev_f32(prompt_canvas.to(dev), "prompt canvas")
+    tabs = [t.to(dev) for t in (ramp_now, ramp_prev, steady_now, steady_prev)]
+    ramp_last, steady_last = ((t.to(dev) for t in su.fifo_lookahead_plan_last(sched, S, ctx)) if multistep else (None, None))
+    # the logical queue [outer, (ctx + n) * sl, ...]: the context, then clip slots 0 .. n - 1 keyed by their canvas positions
+    t0 = torch.full((1,), s0, dtype=torch.long, device=dev)
+    if context is None:
+        head = Fn.canvas_noise(noise_seed, t0, (1, outer, ctx * sl) + hw, 1, window_offset=2 ** 32 - ctx * sl)[0]
+    else:
+        head = L.dev_f32(context.to(dev), "context")
+    queue = torch.cat([head, Fn.canvas_noise(noise_seed, t0, (1, outer, n * sl) + hw, n * sl)[0]], 1)
+    z = windows_from_canvas(queue, L_, h * sl)
+    other = torch.empty_like(z)
+    windows = lambda m: fifo_prompt_windows(pc, m, B, S, prompt_hop, Lp, stride=h, first=m - ctx)
+    engine.set_prompt(windows(0))
+    for r in range(n - 1):
+        other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other, t_last=ramp_last[r] if multistep else None)
+        z, _ = engine.fifo_lookahead(other, ctx, 0)
+    canvas = torch.empty((outer, n_slots * sl) + hw, device=dev, dtype=torch.float32)
+    for m in range(n_slots):
+        if m:
+            engine.set_prompt(windows(m))
+        row = min(m, ctx)
+        other = engine.step_slots(z, tabs[2][row], tabs[3][row], out=other, t_last=steady_last[row] if multistep else None)
+        z, popped = engine.fifo_lookahead(other, ctx, 1, c=n + m, t=s0, seed=noise_seed)
         canvas[:, m * sl:(m + 1) * sl] = popped
     return canvas
 

@@ -15,8 +15,14 @@
   --graph     --e2e: fifo_denoise(graph=True) — the iterations replayed from captured HIP graphs, the ramp row, the prompt positions and
               the clip slot read off device cursors — and the cost of the two captures themselves; without it the eager loop
 
+  --lookahead CTX  FIFO lookahead (overlapping windows, CTX held context slots of every window's S = 6).  --kernels: the lookahead
+              launch at shift 0 and 1, with and without history, beside the plain shift in the same session, with the bytes it moves
+              (every owner read once, B * S slots written); --e2e: fifo_denoise(lookahead=CTX) on B = n / (S - CTX) windows beside the
+              plain queue (B = n / S) at the same schedule, time per finished slot and ramp time, on --solver
+
 Prints plain text: the records are profiles/fifo_kernels.txt and profiles/fifo_e2e.txt (ddim), profiles/fifo_dpm_kernels.txt and
-profiles/fifo_dpm_e2e.txt (both solvers in one session), profiles/fifo_graph_e2e.txt (--e2e with and without --graph)."""
+profiles/fifo_dpm_e2e.txt (both solvers in one session), profiles/fifo_graph_e2e.txt (--e2e with and without --graph),
+profiles/fifo_lookahead_kernels.txt and profiles/fifo_lookahead_e2e.txt (--lookahead 3)."""
 import argparse
 import ctypes as C
 import statistics
@@ -45,7 +51,10 @@ ap.add_argument("--slots-out", type=int, default=24, help="--e2e: finished slots
 ap.add_argument("--solver", choices=("ddim", "dpmpp_2m"), default="ddim")
 ap.add_argument("--graph", action="store_true", help="--e2e: replay the iterations from captured HIP graphs")
 ap.add_argument("--steps", type=int, default=None, help="--e2e: steps of the schedule = slots of the queue (default 48, dpmpp_2m: 18)")
+ap.add_argument("--lookahead", type=int, default=0, metavar="CTX", help="FIFO lookahead: CTX context slots per window of S = 6")
 args = ap.parse_args()
+if not 0 <= args.lookahead < 6:
+    raise SystemExit("--lookahead CTX must lie in [0, 6)")
 DPM = args.solver == "dpmpp_2m"
 
 dev = torch.device("cuda:0")
@@ -86,6 +95,52 @@ def report_shift(res, cases):
         us = statistics.median(res[name])
         print(f"  {name}: {nbytes / 1e6:.2f} MB read + written, {nbytes / us / 1e3:.1f} GB/s ({nbytes / us:.0f} bytes per microsecond)")
 
+
+if args.kernels and args.lookahead:
+    S, ctx, sl = 6, args.lookahead, 2
+    h = S - ctx
+    g = torch.Generator().manual_seed(0)
+    # B = 32 as the other kernel records; then the queues of --e2e --lookahead at n = 48 and n = 18 when h divides them
+    sizes = [32] + [n // h for n in (48, 18) if n % h == 0]
+    rows, meta = [], {}
+    for B in sizes:
+        z, hz = torch.randn(B, 8, 12, 32, 32, generator=g).to(dev), torch.randn(B, 8, 12, 32, 32, generator=g).to(dev)
+        slot = z[0, :, :sl].numel()
+        Q = ctx + B * h
+
+        def add(name, tag, fn, nbytes):
+            rows.append((name, tag, fn))
+            meta[name] = nbytes
+
+        add(f"fifo_shift B={B}", "fifo_shift_kernel<4>", lambda z=z, B=B: Fn.fifo_shift(z, B * S, 7, 999, sl), 4 * (2 * z.numel() + slot))
+        add(f"fifo_shift+hist B={B}", "fifo_shift_kernel<4, HistShift>", lambda z=z, hz=hz, B=B: Fn.fifo_shift(z, B * S, 7, 999, sl, hist=hz),
+            4 * (4 * z.numel() + slot))
+        for shift in (0, 1):
+            kw = dict(c=B * h, seed=7, t=999) if shift else {}
+            # every owner read once (Q slots; the tail is drawn, not read), B * S slots written, the popped slot written at shift 1
+            nb = 4 * ((Q - shift + B * S) * slot + shift * slot)
+            add(f"lookahead shift={shift} B={B}", "fifo_lookahead_kernel<4>",
+                lambda z=z, shift=shift, kw=kw: Fn.fifo_lookahead(z, ctx, shift, sl, **kw), nb)
+            # the history: owners of the active slots read, B * h stepping slots and B * ctx zero slots written
+            nbh = nb + 4 * ((B * h - shift) + B * S) * slot
+            add(f"lookahead+hist shift={shift} B={B}", "fifo_lookahead_kernel<4, hist>",
+                lambda z=z, hz=hz, shift=shift, kw=kw: Fn.fifo_lookahead(z, ctx, shift, sl, hist=hz, **kw), nbh)
+    for _, _, fn in rows:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    res = {name: [] for name, _, _ in rows}
+    for _ in range(args.rounds):
+        for name, tag, fn in rows:
+            res[name].append(per_launch_us(tag, fn, args.launches))
+    print(f"C3 geometry (latent [B, 8, 12, 32, 32], S = {S} slots of {sl} latent frames), lookahead ctx = {ctx} (h = {h}): the lookahead "
+          f"launch beside the plain shift, {args.rounds} interleaved rounds of {args.launches} launches, microseconds per launch (launch events)")
+    for name, _, _ in rows:
+        v = res[name]
+        us = statistics.median(v)
+        print(f"  {name:32s} " + " ".join(f"{x:8.2f}" for x in v) + f"   median {us:8.2f}   {meta[name] / 1e6:7.2f} MB, "
+              f"{meta[name] / us:8.0f} bytes per microsecond")
+    sys.exit(0)
 
 if args.kernels and DPM:
     B, S = 32, 6
@@ -188,6 +243,46 @@ if args.kernels and not DPM:
         v = res[name]
         print(f"  {name:28s} " + " ".join(f"{x:8.2f}" for x in v) + f"   median {statistics.median(v):8.2f}")
     report_shift(res, (("fifo_shift B=32", z, 2), ("fifo_shift B=8", zq, 2)))
+
+if args.e2e and args.lookahead:
+    S, K, ctx = 6, args.slots_out, args.lookahead
+    h = S - ctx
+    n = args.steps or (18 if DPM else 48)
+    if n % S or n % h:
+        raise SystemExit(f"--steps {n} must be a multiple of S = {S} and of h = S - ctx = {h}")
+    sched = su.make_sampling_schedule(1000, n)
+    g = torch.Generator().manual_seed(1)
+    canvas_p = torch.randn(8, 25 * (n + 2 * K) + 148, generator=g).to(dev)
+    hop_p = 25
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    print(f"fifo_denoise with and without lookahead: solver {args.solver}, n = {n} steps, S = {S} (C3 latent, 8 layers, bf16x3, eager), "
+          f"{args.rounds} rounds, the two queues' calls interleaved")
+    queues = [("plain queue", 0, build(8, n // S, solver=args.solver)), (f"lookahead ctx = {ctx}", ctx, build(8, n // h, solver=args.solver))]
+    for _, la, eng in queues:
+        A.fifo_denoise(eng, canvas_p, hop_p, sched, 4, 5, lookahead=la)      # warm-up
+    ts_ = {(name, K_): [] for name, _, _ in queues for K_ in (K, 2 * K)}
+    for _ in range(args.rounds):
+        for K_ in (K, 2 * K):
+            for name, la, eng in queues:
+                ts_[name, K_].append(timed(lambda: A.fifo_denoise(eng, canvas_p, hop_p, sched, K_, 5, lookahead=la)))
+    per = {}
+    for name, la, eng in queues:
+        whole = {K_: statistics.median(ts_[name, K_]) for K_ in (K, 2 * K)}
+        per[name] = (whole[2 * K] - whole[K]) / K
+        print(f"  {name:20s} B = {eng.embed.B:2d}: " + "; ".join(f"{K_} slots out " + " ".join(f"{t * 1e3:7.1f}" for t in ts_[name, K_]) + " ms"
+                                                                   for K_ in (K, 2 * K)))
+        print(f"  {'':20s} per finished slot (steady state, from the two clip lengths) {per[name] * 1e3:.3f} ms; ramp of {n - 1} steps and "
+              f"start {(whole[K] - K * per[name]) * 1e3:.1f} ms")
+    a, b = (per[name] for name, _, _ in queues)
+    print(f"  per finished slot, lookahead / plain: x {b / a:.2f} (at most S / h = {S / h:.2f}: one step at B = {n // h} against one at B = {n // S})")
+    sys.exit(0)
 
 if args.e2e:
     S, K = 6, args.slots_out
