@@ -504,6 +504,53 @@ int64_t avd_cfg_stats_bytes(int B, int64_t per_sample);
 int avd_cfg_rescale_f32(const float* e_cond, const float* e_cfg, const float* phi, void* stats, int64_t stats_bytes, float* out,
                         int B, int64_t per_sample, avd_stream_t stream);
 
+/* ---- adaptive projected guidance (APG; Sadat, Hilliges, Weber 2024; diffusers' AdaptiveProjectedGuidance / normalized_guidance; a
+ * public contract).  APG splits the guidance direction cond - null into the part parallel to the conditional prediction, which it
+ * damps, and the orthogonal part, which it keeps; it caps the direction's norm and optionally carries a (negative) momentum across
+ * steps.  For sample b of a call, with U the token -> latent map of avd_cfg_control item 2 and n = per_sample (>= 2) latent elements:
+ *   1. c = U(cond tokens) and u = U(null tokens); for audio two separate overlap-add means, each accumulated in the window order of
+ *      the fused audio step; d0 = c - u in fp32;
+ *   2. momentum, beta = `momentum`: d = d0 + beta m_prev in fp32 without contraction, m_prev the sample's momentum buffer: fp32
+ *      [B, per_sample] in LATENT layout, caller-owned, indexed as x0_hist is; the fused kernel stores d back into it.  beta == 0 means
+ *      no buffer: the pointer must then be NULL, d = d0 and nothing is read or written.  A zeroed buffer gives the first step d = d0;
+ *   3. moments in fp64 over the n latent elements: S_dd = sum d^2, S_dc = sum d c, S_cc = sum c^2, over a partition fixed by n alone:
+ *      chunks of 1024 consecutive LATENT-ORDER elements, for both modalities; each chunk's partial is stored with plain stores and the
+ *      partials are summed in index order, no float atomics.  The coefficients are therefore the same at any B, sample_offset,
+ *      split_streams setting, eager or graph launch;
+ *   4. coefficients, each rounded once to fp32: s_b = (float)min(1, r / sqrt(S_dd)), 1 when r == 0 (no cap), when S_dd == 0 or when
+ *      the result is not finite; r = norm_threshold >= 0 caps the whole-sample L2 norm of d, as in diffusers.
+ *      k_b = (float)((1 - eta_p) S_dc / S_cc), evaluated left to right in fp64, 0 when S_cc == 0 or when the result is not finite;
+ *      eta_p = eta_parallel in [0, 1] is the kept share of the parallel component.  w_b = (g_b - 1.0f) * s_b in fp32, g_b =
+ *      guidance[b] when a per-sample array is set, else the scalar;
+ *   5. the eps the solver consumes is e = c + w_b * (d - k_b * c) in fp32, in that order, without contraction: the paper's form, cond
+ *      + (g - 1) update.  At r = 0, eta_p = 1, beta = 0 it equals plain CFG MATHEMATICALLY BUT NOT IN BITS: plain CFG is evaluated as
+ *      null + g (cond - null);
+ *   6. the step (DDIM, seeded DDIM, DPM-Solver++(2M) or its SDE form) runs on e in place of the combined eps: DPM's x0_hist receives
+ *      the x0 of e; a latent guide's blend (avd_latent_guide) still comes last;
+ *   7. scope: guidance rescale (a control whose rescale is set) together with APG is refused: its statistics would need the APG
+ *      output.  A cond-only step does not apply APG and leaves the momentum buffer untouched.  Slot timesteps refuse it, as they
+ *      refuse every CFG control.  The kernels trust the device values (guidance[b]); the by-value parameters are range-checked here
+ *      (NaN refused) and again by DenoiseEngine / functional.apg_guidance.
+ * Checked before any HIP call: the scratch's size (avd_apg_stats_bytes) and 16-byte alignment; momentum_buf 16-byte aligned, NULL
+ * exactly when momentum == 0, and overlapping none of z, z_out, x0_hist, the scratch and the eps tokens (for the whole step: the
+ * workspace); the scratch likewise.  What the effect on sample quality is at a given guidance scale is not measured here: that
+ * needs trained weights. */
+typedef struct {
+    float norm_threshold;      /* r >= 0; 0: no norm cap */
+    float eta_parallel;        /* eta_p in [0, 1]; 1 keeps the whole parallel component (with r = 0 and no momentum: CFG) */
+    float momentum;            /* beta, finite; 0: no momentum (momentum_buf NULL) */
+    float* momentum_buf;       /* fp32 [B, per_sample], latent layout, read then overwritten with d; NULL exactly when momentum == 0 */
+    void* stats;               /* caller-owned scratch of >= avd_apg_stats_bytes(B, per_sample) bytes, 16-byte aligned */
+    int64_t stats_bytes;       /* its size */
+} avd_apg_control;
+/* Bytes of the APG statistics scratch of B samples of per_sample (>= 2) elements; -1 on bad arguments.  Its last 16 * B bytes hold
+ * (s_b, k_b, w_b, g_b) per sample after a call. */
+int64_t avd_apg_stats_bytes(int B, int64_t per_sample);
+/* The combine alone, on latent-layout tensors (steps 2 to 5 with c = e_cond, u = e_null): out[b] = e.  e_cond, e_null, out: fp32
+ * [B, per_sample]; guidance: fp32 [B] on the device, or NULL for guidance_scalar.  out must not overlap the inputs. */
+int avd_apg_guidance_f32(const float* e_cond, const float* e_null, const float* guidance, float guidance_scalar,
+                         const avd_apg_control* apg, float* out, int B, int64_t per_sample, avd_stream_t stream);
+
 /* ---- a8 fused: CFG combine + tube un-patch + DDIM — avdiff/models/infer/sample_clip.py:381-389.
  * eps2: [2B,Nv,C*t*h*w] (cond batch then null batch); eps = null + g*(cond-null); un-patched on the fly.
  * z, z_out: [B,C,T,H,W]. */
@@ -811,6 +858,18 @@ int avd_denoise_step_guided_f32(const avd_step_desc* s, const avd_latent_guide* 
  * the per-sample arrays and the scratch are read at their addresses at every launch. */
 int avd_denoise_step_cfg_f32(const avd_step_desc* s, const avd_cfg_control* ctl, const avd_latent_guide* g,
                              const avd_noise_key* key, const int64_t* t_last, float* x0_hist, const float* z, const float* Xp,
+                             const int64_t* t_now, const int64_t* t_prev, float* z_out,
+                             void* workspace, int64_t workspace_bytes, avd_stream_t stream);
+/* The whole CFG step on the adaptive projected guidance eps (avd_apg_control; "adaptive projected guidance" above).  It takes what
+ * avd_denoise_step_cfg_f32 takes plus the APG control and the two canvas hops, so that every combination the controlled step has is
+ * one entry: ctl NULL (the scalar guidance) or a control with per-sample guidance (its rescale must be NULL); g, key, t_last + x0_hist
+ * as there, with eta > 0 beside x0_hist being the solver's SDE form; canvas_hop != 0 keys the eta > 0 noise by canvas position
+ * (avd_denoise_step_canvas_f32's rules), guide_hop != 0 the guide's known noise (avd_denoise_step_canvas_guided_f32's rules; at eta
+ * > 0 canvas_hop must equal it).  The statistics pass runs on the stream right before the fused update.  Graph-capturable: the
+ * scratch and the momentum buffer are read and written at their addresses at every launch; the three parameters are held by value. */
+int avd_denoise_step_apg_f32(const avd_step_desc* s, const avd_apg_control* apg, const avd_cfg_control* ctl,
+                             const avd_latent_guide* g, const avd_noise_key* key, int canvas_hop, int guide_hop,
+                             const int64_t* t_last, float* x0_hist, const float* z, const float* Xp,
                              const int64_t* t_now, const int64_t* t_prev, float* z_out,
                              void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 /* The whole cond-only step (see "guidance interval" above): the single-branch front end, the core and the head on B (Nt+Np) resp. B Nt

@@ -79,6 +79,13 @@ class CfgControl(C.Structure):
     _fields_ = [("guidance", C.c_void_p), ("rescale", C.c_void_p), ("stats", C.c_void_p), ("stats_bytes", C.c_int64)]
 
 
+class ApgControl(C.Structure):
+    """avd_apg_control: the parameters of adaptive projected guidance, the momentum buffer (NULL exactly when momentum == 0) and the
+    statistics scratch (contract in include/avdiff_hip.h, "adaptive projected guidance")."""
+    _fields_ = [("norm_threshold", C.c_float), ("eta_parallel", C.c_float), ("momentum", C.c_float), ("momentum_buf", C.c_void_p),
+                ("stats", C.c_void_p), ("stats_bytes", C.c_int64)]
+
+
 class VaeDecodeDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("Cv", C.c_int), ("Tp", C.c_int), ("Hp", C.c_int), ("Wp", C.c_int),
                 ("T", C.c_int), ("H", C.c_int), ("W", C.c_int),
@@ -178,6 +185,10 @@ SIGNATURES = {
     "avd_cfg_rescale_f32": (_I, [_P, _P, _P, _P, _L, _P, _I, _L, _P]),
     "avd_denoise_step_cfg_f32": (_I, [C.POINTER(StepDesc), C.POINTER(CfgControl), C.POINTER(LatentGuide), C.POINTER(NoiseKey), _P, _P, _P,
                                       _P, _P, _P, _P, _P, _L, _P]),
+    "avd_apg_stats_bytes": (_L, [_I, _L]),
+    "avd_apg_guidance_f32": (_I, [_P, _P, _P, _F, C.POINTER(ApgControl), _P, _I, _L, _P]),
+    "avd_denoise_step_apg_f32": (_I, [C.POINTER(StepDesc), C.POINTER(ApgControl), C.POINTER(CfgControl), C.POINTER(LatentGuide),
+                                      C.POINTER(NoiseKey), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "avd_eps_unpatch_ddim_f32": (_I, [_P, _P, _P, _P, _P, _I, _F, _P, _P] + [_I] * 8 + [C.POINTER(NoiseKey), _P, _P, C.POINTER(LatentGuide), _P]),
     "avd_eps_untoken_ddim_audio_f32": (_I, [_P, _P, _P, _P, _P, _I, _F, _P, _P] + [_I] * 5 + [C.POINTER(NoiseKey), _P, _P,
                                                                                                C.POINTER(LatentGuide), _P]),

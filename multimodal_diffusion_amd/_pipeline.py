@@ -83,6 +83,7 @@ class PipelineConfig(NamedTuple):
     rescale: float                    # sampling.guidance_rescale: per modality, like guidance_scale
     interval: Optional[Tuple[int, int]]
     resample: Optional[Tuple[int, int]]
+    apg: Optional[Tuple[float, float, float]] = None      # sampling.apg: per modality; (norm_threshold, eta_parallel, momentum)
 
 
 def read_config(cfg: Dict, prompt_modality: str, *, guidance_interval, resample, has_init: bool, has_mask: bool,
@@ -108,7 +109,23 @@ def read_config(cfg: Dict, prompt_modality: str, *, guidance_interval, resample,
         eta=float(scfg.get("ddim_eta", 0.0)), solver=str(scfg.get("solver", "ddim")),
         alpha_bar=su.alphas_cumprod_from_betas(betas)[1], sched=su.make_sampling_schedule(int(c["steps"]), int(c["sampler_steps"])),
         guidance=float(scfg["guidance_scale"].get(target, 3.0)), rescale=float(scfg.get("guidance_rescale", {}).get(target, 0.0)),
-        interval=su.check_guidance_interval(guidance_interval) or su.guidance_interval_from_config(scfg, target), resample=rs)
+        interval=su.check_guidance_interval(guidance_interval) or su.guidance_interval_from_config(scfg, target), resample=rs,
+        apg=apg_from_config(scfg, target))
+
+
+def apg_from_config(scfg: Dict, target: str) -> Optional[Tuple[float, float, float]]:
+    """``sampling.apg``: a per-modality dict like ``guidance_scale``; the target's entry is a dict with any of norm_threshold /
+    eta_parallel / momentum (functional.apg_params checks them).  None without an entry for the target."""
+    from . import functional as Fn
+    apg = scfg.get("apg")
+    if apg is None:
+        return None
+    if not isinstance(apg, dict) or set(apg) - {"video", "audio"}:
+        raise ValueError(f"sampling.apg must be a dict per modality ('video' / 'audio'), got {apg!r}")
+    vals = Fn.apg_from_dict(apg.get(target))
+    if vals is not None and float(scfg.get("guidance_rescale", {}).get(target, 0.0)) != 0.0:
+        raise ValueError("sampling.apg cannot be combined with sampling.guidance_rescale != 0 for the same target")
+    return vals
 
 
 # ---- clips to latents ----
@@ -152,7 +169,8 @@ def build_engine(pc: PipelineConfig, *, adapt_v, adapt_a, core, head, tstep_dim:
     return DenoiseEngine(adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim, target=pc.target,
                          latent_shape=tuple(latent_shape), prompt_tokens=n_prompt, alpha_bar=pc.alpha_bar, guidance=pc.guidance,
                          eta=pc.eta, tube=pc.tube, chunk=pc.chunk, noise_seed=noise_seed, solver=pc.solver,
-                         guidance_rescale=pc.rescale, guidance_interval=pc.interval, **streaming)
+                         guidance_rescale=pc.rescale, guidance_interval=pc.interval,
+                         apg=None if pc.apg is None else dict(zip(("norm_threshold", "eta_parallel", "momentum"), pc.apg)), **streaming)
 
 
 def guided_start(eng, pc: PipelineConfig, known: torch.Tensor, mask, z: torch.Tensor, strength: float, guide_seed: int, **keying):

@@ -83,13 +83,14 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key = nullptr,
                          const int64_t* t_last = nullptr, float* x0_hist = nullptr, const avd_latent_guide* guide = nullptr,
-                         const avd_cfg_control* ctl = nullptr, int canvas_hop = 0, int guide_hop = 0, int slots = 0);
+                         const avd_cfg_control* ctl = nullptr, int canvas_hop = 0, int guide_hop = 0, int slots = 0,
+                         const avd_apg_control* apg = nullptr);
 int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st,
                                const avd_noise_key* key = nullptr, const int64_t* t_last = nullptr, float* x0_hist = nullptr,
                                const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr, int canvas_hop = 0, int guide_hop = 0,
-                               int slots = 0);
+                               int slots = 0, const avd_apg_control* apg = nullptr);
 int assemble_cond_f32(float* X1, const float* temb, const float* Xp, int B, int N, int d, int tdim, int Nt, int Np, int target_first,
                       hipStream_t st);
 int assemble_rows_cond_f32(float* X1, const int64_t* t_now, const float* freqs, const float* Xp, float* ss, int B, int N, int d,
@@ -107,6 +108,8 @@ int check_canvas_guide(const avd_latent_guide* g, int N, int64_t outer, int L, i
                        const float* x0_hist);
 int check_latent_guide(const avd_latent_guide* g, int B, int64_t per, const float* out, const float* x0_hist);
 int check_cfg_control(const avd_cfg_control* ctl, int B, int64_t per, const float* out, const float* x0_hist);
+int check_apg_control(const avd_apg_control* apg, const avd_cfg_control* ctl, int B, int64_t per, const float* z, const float* out,
+                      const float* x0_hist, const void* eps, int64_t eps_bytes);
 bool overlaps(const float* a, const float* b, int64_t n);
 
 static inline int64_t align_up(int64_t x) { return (x + 255) & ~(int64_t)255; }
@@ -886,12 +889,13 @@ extern "C" int64_t avd_step_workspace_bytes(const avd_step_desc* s) {
 // (avd_denoise_step_cfg_f32: its statistics pass runs in the fused update's launcher, on st after the join of the two streams);
 // canvas_hop != 0 keys the seeded draw by canvas position (avd_denoise_step_canvas_f32); key and x0_hist together at eta > 0 end the
 // step with the solver's SDE form (avd_denoise_step_dpmpp_2m_sde_f32); guide_hop != 0 keys the guide's known noise by canvas position
-// (avd_denoise_step_canvas_guided_f32)
+// (avd_denoise_step_canvas_guided_f32); apg != nullptr steps on the adaptive projected guidance eps (avd_denoise_step_apg_f32: as ctl,
+// its statistics pass runs in the fused update's launcher)
 static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp, const int64_t* t_now,
                         const int64_t* t_prev, const float* noise, float* z_out, void* workspace, int64_t workspace_bytes,
                         avd_stream_t stream, const int64_t* t_last = nullptr, float* x0_hist = nullptr,
                         const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr, int canvas_hop = 0,
-                        int guide_hop = 0, int slots = 0) {
+                        int guide_hop = 0, int slots = 0, const avd_apg_control* apg = nullptr) {
     StepWs ws;
     if (int rc = open_step(s, z, z_out, t_now, t_prev, workspace, workspace_bytes, ws)) return rc;
     auto& [p, X2, tok, core_ws, head_ws, ssx, eps2] = ws;
@@ -943,9 +947,9 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
     if (e.target_kind == 0)
         return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, s->alpha_bar, s->T_train, s->guidance, s->eta, noise, z_out,
                                     e.B, e.C, e.T, e.H, e.W, e.p0, e.p1, e.p2, st, key, t_last, x0_hist, guide, ctl, canvas_hop,
-                                    guide_hop, slots);
+                                    guide_hop, slots, apg);
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, s->alpha_bar, s->T_train, s->guidance, s->eta, noise, z_out,
-                                      e.B, e.C, e.T, e.p0, e.p1, st, key, t_last, x0_hist, guide, ctl, canvas_hop, guide_hop, slots);
+                                      e.B, e.C, e.T, e.p0, e.p1, st, key, t_last, x0_hist, guide, ctl, canvas_hop, guide_hop, slots, apg);
 }
 
 // The cond-only step of a guidance interval: the conditional branch alone, in the cond half of every workspace region of the CFG step's
@@ -1160,6 +1164,40 @@ extern "C" int avd_denoise_step_canvas_guided_f32(const avd_step_desc* s, const 
                                  noisy ? hop : 0, hop);
     return denoise_step(s, k, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, g, ctl,
                         noisy ? hop : 0, hop);
+}
+
+// The CFG step on the adaptive projected guidance eps ("adaptive projected guidance" in the header), for every solver state and keying
+// the CFG-controlled step has: DDIM at eta == 0, seeded DDIM, DPM-Solver++(2M) and its SDE form (t_last + x0_hist), a latent guide keyed
+// per sample or (guide_hop != 0) by canvas position, the step noise keyed per sample or (canvas_hop != 0) by canvas position.  Only the
+// fused update differs from those entries; everything is checked before the model runs.
+extern "C" int avd_denoise_step_apg_f32(const avd_step_desc* s, const avd_apg_control* apg, const avd_cfg_control* ctl,
+                                        const avd_latent_guide* g, const avd_noise_key* key, int canvas_hop, int guide_hop,
+                                        const int64_t* t_last, float* x0_hist, const float* z, const float* Xp, const int64_t* t_now,
+                                        const int64_t* t_prev, float* z_out, void* workspace, int64_t workspace_bytes,
+                                        avd_stream_t stream) {
+    AVD_REQUIRE(s, AVD_EINVAL, "denoise_step_apg: null descriptor");
+    AVD_REQUIRE(apg, AVD_EINVAL, "denoise_step_apg: null APG control");
+    AVD_REQUIRE(canvas_hop >= 0 && guide_hop >= 0, AVD_EINVAL, "denoise_step_apg: canvas_hop %d and guide_hop %d must be >= 0 (0: keyed per sample)",
+                canvas_hop, guide_hop);
+    AVD_REQUIRE(s->eta >= 0.f, AVD_EINVAL, "denoise_step_apg: eta must be >= 0");
+    const bool noisy = s->eta > 0.f;
+    const avd_embed_desc& e = s->embed;
+    AVD_REQUIRE(!canvas_hop || (noisy && key), AVD_EINVAL,
+                "denoise_step_apg: canvas keying of the step noise is a seeded eta > 0 step (needs a noise key and eta > 0)");
+    if (guide_hop) {
+        AVD_REQUIRE(g, AVD_EINVAL, "denoise_step_apg: the canvas keying of a latent guide needs the guide");
+        AVD_REQUIRE(!noisy || canvas_hop == guide_hop, AVD_EINVAL,
+                    "denoise_step_apg: under a canvas-keyed latent guide the eta > 0 noise must be canvas-keyed with the guide's hop %d", guide_hop);
+        if (int rc = check_canvas_guide(g, e.B, e.C, e.T, guide_hop, (int64_t)e.H * e.W, z_out, x0_hist)) return rc;
+    }
+    if (canvas_hop)
+        if (int rc = check_canvas_key(key, e.B, e.C, e.T, canvas_hop, (int64_t)e.H * e.W)) return rc;
+    const avd_noise_key* k = noisy ? key : nullptr;
+    if (int rc = check_step_options("denoise_step_apg", TAKES_SDE, s, k, t_last, x0_hist, z, z_out, g, ctl, nullptr)) return rc;
+    const int64_t per = (int64_t)e.C * e.T * e.H * e.W;
+    if (int rc = check_apg_control(apg, ctl, e.B, per, z, z_out, x0_hist, workspace, workspace_bytes)) return rc;
+    return denoise_step(s, k, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, g, ctl, canvas_hop,
+                        guide_hop, 0, apg);
 }
 
 extern "C" int avd_prof_enable(int on) {

@@ -12,6 +12,8 @@
 
 #include <stdlib.h>
 #include <type_traits>
+#include <cmath>
+#include <initializer_list>
 
 namespace avd {
 
@@ -342,7 +344,7 @@ template <bool SEEDED, class... X> struct PackOk {
                                   !(n<CanvasGuideState> && n<NoiseKey>) &&
                                   n<NoiseKey> + n<CanvasKey> == (SEEDED ? 1 : 0);
 };
-template <class T, class A, class... R> __device__ __forceinline__ T pack_get(const A& a, const R&... r) {
+template <class T, class A, class... R> __host__ __device__ __forceinline__ T pack_get(const A& a, const R&... r) {
     if constexpr (std::is_same<T, A>::value) return a;
     else return pack_get<T>(r...);
 }
@@ -1302,6 +1304,10 @@ struct CfgState {
     const float* guidance;   // [B] or nullptr (the scalar)
     const float* rescale;    // [B] or nullptr (phi = 0)
     const float* scale;      // [B] s_b, written by cfg_stats_finalize_kernel (read only when rescale is set)
+    // adaptive projected guidance (below): nullptr = none, and the kernels take the path they took before it existed
+    const float* apg;        // [B][4] (s_b, k_b, w_b, g_b), written by apg_finalize_kernel
+    float* apg_mom;          // [B, per] the momentum buffer in latent layout, or nullptr (beta == 0)
+    float apg_beta;
 };
 struct CfgCoef {
     float g, phi, s;
@@ -1453,7 +1459,7 @@ static int make_cfg(const avd_cfg_control* ctl, int B, int64_t per, const float*
     AVD_REQUIRE(ctl, AVD_EINVAL, "cfg_control: null control");
     AVD_REQUIRE(B > 0 && B <= 65535 && per >= 2 && per < ((int64_t)1 << 34), AVD_EINVAL,
                 "cfg_control: bad dims (B %d in [1, 65535], per_sample %lld must be >= 2)", B, (long long)per);
-    cs = CfgState{ctl->guidance, ctl->rescale, nullptr};
+    cs = CfgState{ctl->guidance, ctl->rescale, nullptr, nullptr, nullptr, 0.f};
     if (!ctl->rescale) return AVD_OK;
     const int64_t need = cfg_stats_bytes(B, per);
     AVD_REQUIRE(ctl->stats, AVD_EINVAL, "cfg_control: rescale needs the statistics scratch (stats)");
@@ -1504,6 +1510,248 @@ int cfg_rescale_f32(const float* e_cond, const float* e_cfg, const float* phi, v
     if (int rc = run_cfg_stats<CFG_SRC_PAIR>(&ctl, e_cond, e_cfg, per, 0.f, B, per, AudioGeom{}, st)) return rc;
     hipLaunchKernelGGL(cfg_rescale_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, e_cfg, phi, cs.scale, out, per, total);
     AVD_CHECK_LAUNCH("cfg_rescale");
+    return AVD_OK;
+}
+
+// ------------------------------------------------------------------ adaptive projected guidance (APG)
+// The contract is written out in include/avdiff_hip.h ("adaptive projected guidance").  As the CFG control above: a statistics pass
+// writes one fp64 partial of (sum d^2, sum d c, sum c^2) per CFG_CHUNK latent-order elements of a sample, a finalize pass sums them in
+// index order and stores (s_b, k_b, w_b, g_b); the fused kernels read the pair (w_b, k_b) through the CfgState's APG part and step on
+// e = c + w_b (d - k_b c).  d = (c - u) + beta m_prev, and the fused kernel stores d back into the momentum buffer: the statistics pass
+// has read m_prev before that launch starts (same stream), and both evaluate d with the same two functions below.
+__device__ __forceinline__ float apg_d0(float c, float u) {
+#pragma clang fp contract(off)
+    return c - u;
+}
+// d of the contract from d0 and the buffer's value; beta == 0 (no buffer) is d0 itself
+__device__ __forceinline__ float apg_dir(float d0, float beta, float m) {
+#pragma clang fp contract(off)
+    return beta != 0.f ? d0 + beta * m : d0;
+}
+__device__ __forceinline__ float apg_eps(float c, float d, float w, float k) {
+#pragma clang fp contract(off)
+    return c + w * (d - k * c);
+}
+// item 5 of the contract for the four elements at latent address lat of sample b, from c and d0: reads m_prev and stores d when the
+// buffer is set
+__device__ __forceinline__ f32x4 apg_eps4(const CfgState& cs, int b, int64_t lat, const f32x4& c, const f32x4& d0) {
+    const float k = cs.apg[(int64_t)b * 4 + 1], w = cs.apg[(int64_t)b * 4 + 2];
+    f32x4 m = {0.f, 0.f, 0.f, 0.f}, d, e;
+    if (cs.apg_mom) m = *reinterpret_cast<const f32x4*>(cs.apg_mom + lat);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        d[j] = apg_dir(d0[j], cs.apg_beta, m[j]);
+        e[j] = apg_eps(c[j], d[j], w, k);
+    }
+    if (cs.apg_mom) *reinterpret_cast<f32x4*>(cs.apg_mom + lat) = d;
+    return e;
+}
+// the eps an update steps on: the APG value where the launch carries one, else cfg_eps (all a non-CTL instantiation compiles)
+template <bool CTL, bool COND>
+__device__ __forceinline__ float step_eps(bool apg, float ea, float ec, float en, float guidance, const CfgCoef& cc) {
+    if constexpr (CTL) {
+        if (apg) return ea;
+    }
+    return cfg_eps<CTL, COND>(ec, en, guidance, cc);
+}
+
+constexpr int APG_MOMENTS = 3;
+static int64_t apg_coef_off(int B, int64_t per) { return ((int64_t)B * cfg_chunks(per) * APG_MOMENTS * 8 + 15) & ~(int64_t)15; }
+int64_t apg_stats_bytes(int B, int64_t per) {
+    if (B <= 0 || B > 65535 || per < 2 || per >= ((int64_t)1 << 34)) return -1;
+    return apg_coef_off(B, per) + (int64_t)B * 16;
+}
+
+// grid (chunks, B): block (j, b) writes part[(b * chunks + j) * 3 + {0, 1, 2}] = the sums of (d^2, d c, c^2) over latent elements
+// [j * 1024, (j + 1) * 1024) of sample b.  a / u: sample b's source at a + b * sstride and u + b * sstride.  PAIR: latent-layout c and
+// u.  VIDEO: the cond / null token rows, read through the latent -> token offset map, one float4 of latent per lane (the gather form of
+// the fused kernel), so that the partition and the momentum read follow the latent.  AUDIO: the two overlap-add means per element.
+template <int SRC>
+__global__ __launch_bounds__(256) void apg_stats_kernel(const float* __restrict__ a, const float* __restrict__ u, int64_t sstride,
+                                                        const float* __restrict__ mom, float beta, double* __restrict__ part,
+                                                        int64_t per, Tube g, AudioGeom ag) {
+#pragma clang fp contract(off)
+    __shared__ double red[4][APG_MOMENTS];
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const float* sa = a + (int64_t)b * sstride;
+    const float* su = u + (int64_t)b * sstride;
+    const int64_t el0 = (int64_t)blockIdx.x * CFG_CHUNK + threadIdx.x * 4;
+    f32x4 cv = {0.f, 0.f, 0.f, 0.f}, dv = {0.f, 0.f, 0.f, 0.f};
+    int nv = 0;                                        // valid elements of this lane (elements >= per add nothing)
+    if (el0 < per) {
+        nv = per - el0 < 4 ? (int)(per - el0) : 4;
+        const float* sm = mom ? mom + (int64_t)b * per + el0 : nullptr;
+        if constexpr (SRC == CFG_SRC_VIDEO) {          // per % 4 == 0 (w % 4 == 0): a whole float4, 16-byte aligned in all three
+            const int64_t toff = tube_tok_off(g, el0 >> 2);
+            const f32x4 ec = *reinterpret_cast<const f32x4*>(sa + toff), en = *reinterpret_cast<const f32x4*>(su + toff);
+            f32x4 m = {0.f, 0.f, 0.f, 0.f};
+            if (sm) m = *reinterpret_cast<const f32x4*>(sm);
+            cv = ec;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) dv[k] = apg_dir(apg_d0(ec[k], en[k]), beta, m[k]);
+        } else {
+            for (int k = 0; k < nv; ++k) {
+                const int64_t el = el0 + k;
+                float c, n;
+                if constexpr (SRC == CFG_SRC_PAIR) {
+                    c = sa[el];
+                    n = su[el];
+                } else {                                // as cfg_untoken_ddim_audio_kernel's APG branch: the same two means
+                    const int f = (int)(el % ag.F), ch = (int)(el / ag.F);
+                    const int L = (ag.Na - 1) * ag.stride + ag.len, D = ag.Ca * ag.len;
+                    c = f < L ? ola_gather(sa, D, ch, ag.len, ag.stride, ag.Na, f) : 0.f;
+                    n = f < L ? ola_gather(su, D, ch, ag.len, ag.stride, ag.Na, f) : 0.f;
+                }
+                cv[k] = c;
+                dv[k] = apg_dir(apg_d0(c, n), beta, sm ? sm[k] : 0.f);
+            }
+        }
+    }
+    double m[APG_MOMENTS] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < nv; ++k) {
+        const double c = (double)cv[k], d = (double)dv[k];
+        m[0] += d * d;
+        m[1] += d * c;
+        m[2] += c * c;
+    }
+    // fixed-order block sum, as cfg_stats_kernel: a butterfly within each wave, then waves 0..3
+#pragma unroll
+    for (int q = 0; q < APG_MOMENTS; ++q)
+        for (int o = 32; o > 0; o >>= 1) m[q] += __shfl_xor(m[q], o, 64);
+    if (lane == 0)
+        for (int q = 0; q < APG_MOMENTS; ++q) red[wv][q] = m[q];
+    __syncthreads();
+    if (threadIdx.x < APG_MOMENTS) {
+        const int q = threadIdx.x;
+        part[((int64_t)b * gridDim.x + blockIdx.x) * APG_MOMENTS + q] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
+    }
+}
+
+// one lane per sample: the partials summed in index order, then item 4 of the contract; coef[b] = (s_b, k_b, w_b, g_b), one store
+__global__ void apg_finalize_kernel(const double* __restrict__ part, float* __restrict__ coef, const float* __restrict__ gvec,
+                                    float guidance, float r, float eta_p, int B, int chunks) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double s[APG_MOMENTS] = {0.0, 0.0, 0.0};
+    const double* p = part + (int64_t)b * chunks * APG_MOMENTS;
+    for (int j = 0; j < chunks; ++j)
+        for (int q = 0; q < APG_MOMENTS; ++q) s[q] += p[(int64_t)j * APG_MOMENTS + q];
+    float sb = 1.f, kb = 0.f;
+    if (r != 0.f && s[0] != 0.0) {
+        const float v = (float)fmin(1.0, (double)r / sqrt(s[0]));
+        if (isfinite(v)) sb = v;
+    }
+    if (s[2] != 0.0) {
+        const float v = (float)((1.0 - (double)eta_p) * s[1] / s[2]);
+        if (isfinite(v)) kb = v;
+    }
+    const float gb = gvec ? gvec[b] : guidance;
+    *reinterpret_cast<f32x4*>(coef + (int64_t)b * 4) = f32x4{sb, kb, (gb - 1.0f) * sb, gb};
+}
+
+// the combine alone on latent-layout c, u (avd_apg_guidance_f32)
+__global__ __launch_bounds__(256) void apg_combine_kernel(const float* __restrict__ c, const float* __restrict__ u,
+                                                          const float* __restrict__ coef, float* mom, float beta,
+                                                          float* __restrict__ out, int64_t per, int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int64_t b = i / per;
+    const float cv = c[i], d = apg_dir(apg_d0(cv, u[i]), beta, mom ? mom[i] : 0.f);
+    if (mom) mom[i] = d;
+    out[i] = apg_eps(cv, d, coef[b * 4 + 2], coef[b * 4 + 1]);
+}
+
+// The checks of an APG control, all before any HIP call: the parameters' ranges, no rescale beside it, the scratch's size and
+// alignment, the momentum buffer set exactly when beta != 0 and 16-byte aligned, and no overlap of either with the call's latent-sized
+// tensors `lat` (the step: z, z_out, x0_hist; the elementwise entry: e_cond, e_null, out; nullptr entries are skipped), the eps source
+// or each other.  eps: the bytes the statistics pass and the fused kernel read the predictions from (nullptr: they are in `lat`).
+// Fills the CfgState's APG part on top of what make_cfg left.
+static int make_apg(const avd_apg_control* apg, const avd_cfg_control* ctl, int B, int64_t per, std::initializer_list<const float*> lat,
+                    const void* eps, int64_t eps_bytes, CfgState& cs) {
+    AVD_REQUIRE(apg, AVD_EINVAL, "apg_control: null control");
+    AVD_REQUIRE(B > 0 && B <= 65535 && per >= 2 && per < ((int64_t)1 << 34), AVD_EINVAL,
+                "apg_control: bad dims (B %d in [1, 65535], per_sample %lld must be >= 2)", B, (long long)per);
+    AVD_REQUIRE(apg->norm_threshold >= 0.f && std::isfinite(apg->norm_threshold), AVD_EINVAL,
+                "apg_control: norm_threshold must be finite and >= 0 (0: no cap), got %g", (double)apg->norm_threshold);
+    AVD_REQUIRE(apg->eta_parallel >= 0.f && apg->eta_parallel <= 1.f, AVD_EINVAL, "apg_control: eta_parallel must lie in [0, 1], got %g",
+                (double)apg->eta_parallel);
+    AVD_REQUIRE(std::isfinite(apg->momentum), AVD_EINVAL, "apg_control: momentum must be finite, got %g", (double)apg->momentum);
+    AVD_REQUIRE(!(ctl && ctl->rescale), AVD_EINVAL,
+                "apg_control: guidance rescale together with APG is refused (its statistics would need the APG output)");
+    AVD_REQUIRE((apg->momentum != 0.f) == (apg->momentum_buf != nullptr), AVD_EINVAL,
+                "apg_control: momentum_buf must be set exactly when momentum != 0 (momentum %g, buffer %s)", (double)apg->momentum,
+                apg->momentum_buf ? "set" : "NULL");
+    const int64_t need = apg_stats_bytes(B, per), lat_bytes = (int64_t)B * per * 4;
+    AVD_REQUIRE(apg->stats, AVD_EINVAL, "apg_control: APG needs the statistics scratch (stats)");
+    AVD_REQUIRE(aligned16(apg->stats), AVD_EUNSUPPORTED, "apg_control: stats must be 16-byte aligned");
+    AVD_REQUIRE(apg->stats_bytes >= need, AVD_EINVAL, "apg_control: stats holds %lld bytes, %lld needed (avd_apg_stats_bytes)",
+                (long long)apg->stats_bytes, (long long)need);
+    AVD_REQUIRE(aligned16(apg->momentum_buf), AVD_EUNSUPPORTED, "apg_control: momentum_buf must be 16-byte aligned");
+    for (const float* p : lat) {
+        AVD_REQUIRE(!p || !overlaps_bytes(apg->stats, need, p, lat_bytes), AVD_EINVAL,
+                    "apg_control: stats must not overlap the call's latents (z, z_out, x0_hist; e_cond, e_null, out)");
+        AVD_REQUIRE(!p || !apg->momentum_buf || !overlaps_bytes(apg->momentum_buf, lat_bytes, p, lat_bytes), AVD_EINVAL,
+                    "apg_control: momentum_buf must not overlap the call's latents (z, z_out, x0_hist; e_cond, e_null, out)");
+    }
+    AVD_REQUIRE(!apg->momentum_buf || !overlaps_bytes(apg->momentum_buf, lat_bytes, apg->stats, need), AVD_EINVAL,
+                "apg_control: momentum_buf must not overlap the statistics scratch");
+    if (eps) {
+        AVD_REQUIRE(!overlaps_bytes(apg->stats, need, eps, eps_bytes), AVD_EINVAL, "apg_control: stats must not overlap the eps tokens");
+        AVD_REQUIRE(!apg->momentum_buf || !overlaps_bytes(apg->momentum_buf, lat_bytes, eps, eps_bytes), AVD_EINVAL,
+                    "apg_control: momentum_buf must not overlap the eps tokens");
+    }
+    if (!ctl) cs = CfgState{nullptr, nullptr, nullptr, nullptr, nullptr, 0.f};
+    cs.apg = reinterpret_cast<const float*>(static_cast<const char*>(apg->stats) + apg_coef_off(B, per));
+    cs.apg_mom = apg->momentum_buf;
+    cs.apg_beta = apg->momentum;
+    return AVD_OK;
+}
+
+// make_apg's checks alone: the composite step runs them before the model, with the whole workspace as the eps source
+int check_apg_control(const avd_apg_control* apg, const avd_cfg_control* ctl, int B, int64_t per, const float* z, const float* out,
+                      const float* x0_hist, const void* eps, int64_t eps_bytes) {
+    CfgState cs{};
+    return make_apg(apg, ctl, B, per, {z, out, x0_hist}, eps, eps_bytes, cs);
+}
+
+// the statistics pass: partials, then (s_b, k_b, w_b, g_b) into the scratch's coefficient slot
+template <int SRC>
+static int run_apg_stats(const avd_apg_control* apg, const float* gvec, float guidance, const float* a, const float* u, int64_t sstride,
+                         int B, int64_t per, Tube g, AudioGeom ag, hipStream_t st) {
+    const int64_t chunks = cfg_chunks(per);
+    double* part = static_cast<double*>(apg->stats);
+    static const int tag = prof_tag_id("apg_stats_kernel");
+    ProfScope prof(tag, (apg->momentum_buf ? 12.0 : 8.0) * (double)B * per, st);
+    hipLaunchKernelGGL(apg_stats_kernel<SRC>, dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, st, a, u, sstride, apg->momentum_buf,
+                       apg->momentum, part, per, g, ag);
+    hipLaunchKernelGGL(apg_finalize_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, part,
+                       reinterpret_cast<float*>(static_cast<char*>(apg->stats) + apg_coef_off(B, per)), gvec, guidance,
+                       apg->norm_threshold, apg->eta_parallel, B, (int)chunks);
+    AVD_CHECK_LAUNCH("apg_stats");
+    return AVD_OK;
+}
+
+int apg_guidance_f32(const float* e_cond, const float* e_null, const float* gvec, float guidance, const avd_apg_control* apg, float* out,
+                     int B, int64_t per, hipStream_t st) {
+    AVD_REQUIRE(e_cond && e_null && out, AVD_EINVAL, "apg_guidance: null pointer");
+    AVD_REQUIRE(std::isfinite(guidance), AVD_EINVAL, "apg_guidance: the scalar guidance must be finite");
+    CfgState cs{};
+    if (int rc = make_apg(apg, nullptr, B, per, {e_cond, e_null, out}, nullptr, 0, cs)) return rc;
+    const int64_t total = (int64_t)B * per;
+    AVD_REQUIRE(!overlaps(out, e_cond, total) && !overlaps(out, e_null, total), AVD_EINVAL,
+                "apg_guidance: out must not overlap e_cond or e_null");
+    AVD_REQUIRE(!gvec || (!overlaps_bytes(gvec, (int64_t)B * 4, out, total * 4) &&
+                          !overlaps_bytes(gvec, (int64_t)B * 4, apg->stats, apg->stats_bytes) &&
+                          !(apg->momentum_buf && overlaps_bytes(gvec, (int64_t)B * 4, apg->momentum_buf, total * 4))),
+                AVD_EINVAL, "apg_guidance: guidance must not overlap out, the scratch or momentum_buf");
+    AVD_REQUIRE((total + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "apg_guidance: %lld values is too many for one launch", (long long)total);
+    if (int rc = run_apg_stats<CFG_SRC_PAIR>(apg, gvec, guidance, e_cond, e_null, per, B, per, Tube{}, AudioGeom{}, st)) return rc;
+    static const int tag = prof_tag_id("apg_combine_kernel");
+    ProfScope prof(tag, (apg->momentum_buf ? 20.0 : 12.0) * (double)total, st);
+    hipLaunchKernelGGL(apg_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, e_cond, e_null, cs.apg, cs.apg_mom,
+                       cs.apg_beta, out, per, total);
+    AVD_CHECK_LAUNCH("apg_guidance");
     return AVD_OK;
 }
 
@@ -1559,6 +1807,18 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
         zn = philox_normal4(k, (uint32_t)e4, k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
     } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
     const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, eta, SLOT ? tb : b);
+    [[maybe_unused]] bool apg = false;      // a run-time branch of the CTL instantiations: the launch carries an APG part
+    [[maybe_unused]] f32x4 ea = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (CTL) {
+        const CfgState cs = pack_get<CfgState>(nk...);
+        apg = cs.apg != nullptr;
+        if (apg) {
+            f32x4 d0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) d0[k] = apg_d0(ec[k], en[k]);
+            ea = apg_eps4(cs, b, lat, ec, d0);
+        }
+    }
     f32x4 o;
     if constexpr (DPM) {
         const DpmState ds = pack_get<DpmState>(nk...);
@@ -1567,14 +1827,14 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
         if (d.c_1 != 0.f) hist = *reinterpret_cast<const f32x4*>(ds.x0_hist + lat);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            x0[k] = ddim_x0(c, x[k], cfg_eps<CTL, COND>(ec[k], en[k], guidance, cc));
+            x0[k] = ddim_x0(c, x[k], step_eps<CTL, COND>(apg, ea[k], ec[k], en[k], guidance, cc));
             o[k] = dpm_apply(d, x[k], x0[k], hist[k], zn[k], SEEDED);
         }
         *reinterpret_cast<f32x4*>(ds.x0_hist + lat) = x0;
     } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float e = cfg_eps<CTL, COND>(ec[k], en[k], guidance, cc);
+            const float e = step_eps<CTL, COND>(apg, ea[k], ec[k], en[k], guidance, cc);
             o[k] = ddim_apply(c, x[k], e, zn[k]);
         }
     }
@@ -1604,6 +1864,8 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     static_assert(PackOk<SEEDED, Key...>::value, "not a pack of the fused update kernels (see PackOk)");
     constexpr bool SLOT = PackHas<SlotTimes, Key...>::value;
     extern __shared__ __attribute__((aligned(16))) float ebuf[];       // [GT][D + 4]: the pad keeps the transposed 16-byte reads off one bank group
+    // an APG launch parks two values per element, c in ebuf and d0 = c - u in a second [GT][D + 4] behind it: the momentum buffer is in
+    // latent layout, so m_prev is read, d stored and e built after the exchange, by the lane that owns the element's latent address
     const int LD = g.D + 4;
     const int b = blockIdx.x / groups_per_sample, grp = blockIdx.x % groups_per_sample;
     const int n0 = grp * GT;                                            // first token of the group (GT divides W / w: one (t', h') row)
@@ -1618,14 +1880,26 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     const int nf4 = SLOT && hold ? 0 : GT * g.D / 4;      // a held slot reads no eps
     [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
     if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
+    [[maybe_unused]] bool apg = false;      // block-uniform: the launch carries an APG part
+    if constexpr (CTL) apg = pack_get<CfgState>(nk...).apg != nullptr;
     for (int i = threadIdx.x; i < nf4; i += 256) {
         const f32x4 ec = *reinterpret_cast<const f32x4*>(tc + (int64_t)i * 4);
         [[maybe_unused]] f32x4 en = {0.f, 0.f, 0.f, 0.f};
         if constexpr (!COND) en = *reinterpret_cast<const f32x4*>(tn + (int64_t)i * 4);
+        const int tok = (i * 4) / g.D, k0 = (i * 4) % g.D;
+        if constexpr (CTL) {
+            if (apg) {
+                f32x4 d0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) d0[k] = apg_d0(ec[k], en[k]);
+                *reinterpret_cast<f32x4*>(ebuf + tok * LD + k0) = ec;
+                *reinterpret_cast<f32x4*>(ebuf + (GT + tok) * LD + k0) = d0;
+                continue;
+            }
+        }
         f32x4 e;
 #pragma unroll
         for (int k = 0; k < 4; ++k) e[k] = cfg_eps<CTL, COND>(ec[k], en[k], guidance, cc);
-        const int tok = (i * 4) / g.D, k0 = (i * 4) % g.D;
         *reinterpret_cast<f32x4*>(ebuf + tok * LD + k0) = e;
     }
     __syncthreads();
@@ -1642,8 +1916,12 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         const int sg = i / per_seg4, j = i % per_seg4;                   // piece j of line sg: token j * 4 / w, offset (j * 4) % w
         const int tok = (j * 4) / g.w, wo = (j * 4) % g.w;
         const int hh = sg % g.h, tt = (sg / g.h) % g.t, cc = sg / (g.h * g.t);
-        const f32x4 e = *reinterpret_cast<const f32x4*>(ebuf + tok * LD + sg * g.w + wo);
+        f32x4 e = *reinterpret_cast<const f32x4*>(ebuf + tok * LD + sg * g.w + wo);
         const int64_t lat = (int64_t)b * g.per + (((int64_t)cc * g.T + (tq * g.t + tt)) * g.H + (hq * g.h + hh)) * g.W + (wq + tok) * g.w + wo;
+        if constexpr (CTL) {
+            if (apg)      // e holds c: this lane owns the latent address of the four elements, on this side of the exchange
+                e = apg_eps4(pack_get<CfgState>(nk...), b, lat, e, *reinterpret_cast<const f32x4*>(ebuf + (GT + tok) * LD + sg * g.w + wo));
+        }
         const f32x4 x = *reinterpret_cast<const f32x4*>(z + lat);
         if constexpr (SLOT) {
             if (hold) {      // z, bit for bit; a DpmState's x0_hist is left alone
@@ -1720,6 +1998,8 @@ struct UpdateKeys {
 // cv != nullptr: the batch is windows of one canvas and the seeded draw is keyed by canvas position (needs key and eta > 0)
 // gcv != nullptr: the guide's known noise is keyed by canvas position (needs guide; a seeded draw must then be canvas-keyed with the
 // same hop: per-sample step noise under a canvas-keyed guide is refused)
+// apg != nullptr: adaptive projected guidance rides in the CfgState (with or without ctl, whose rescale it excludes); the launcher runs
+// its statistics pass first; eps_bytes: the bytes of a.eps, which the scratch and the momentum buffer must not overlap
 struct CanvasDims {
     int64_t outer;
     int L, hop;
@@ -1727,7 +2007,8 @@ struct CanvasDims {
 };
 static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per, const avd_noise_key* key, const int64_t* t_last,
                               float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl, UpdateKeys& k,
-                              const CanvasDims* cv = nullptr, const CanvasDims* gcv = nullptr) {
+                              const CanvasDims* cv = nullptr, const CanvasDims* gcv = nullptr, const avd_apg_control* apg = nullptr,
+                              int64_t eps_bytes = 0) {
     AVD_REQUIRE(a.eps && a.z && a.t_now && a.t_prev && a.abar && a.z_out, AVD_EINVAL, "%s: null pointer", what);
     AVD_REQUIRE(a.eta >= 0.f && (a.eta == 0.f || a.noise || key), AVD_EINVAL, "%s: eta > 0 needs a noise tensor or a noise key", what);
     AVD_REQUIRE(a.z != a.z_out, AVD_EINVAL, "%s: z_out must not alias z", what);
@@ -1753,8 +2034,8 @@ static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per
     AVD_REQUIRE(guide || !gcv, AVD_EINVAL, "%s: the canvas keying of a latent guide needs the guide", what);
     k.guide = guide != nullptr && !gcv;
     k.cguide = guide != nullptr && gcv;
-    k.ctl = ctl != nullptr;
-    if (guide || ctl)
+    k.ctl = ctl != nullptr || apg != nullptr;
+    if (guide || ctl || apg)
         AVD_REQUIRE(a.eta == 0.f || k.seeded, AVD_EINVAL, "%s: a guided or controlled step with eta > 0 needs a noise key", what);
     if (k.cguide) {
         AVD_REQUIRE(!k.seeded || (cv && cv->hop == gcv->hop), AVD_EINVAL,
@@ -1765,6 +2046,8 @@ static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per
         if (int rc = make_guide(guide, a.B, per, a.z_out, x0_hist, k.gs)) return rc;
     if (ctl)
         if (int rc = make_cfg(ctl, a.B, per, a.z_out, x0_hist, k.cs)) return rc;
+    if (apg)
+        if (int rc = make_apg(apg, ctl, a.B, per, {a.z, a.z_out, x0_hist}, a.eps, eps_bytes, k.cs)) return rc;
     return AVD_OK;
 }
 
@@ -1830,10 +2113,13 @@ static void launch_unpatch(const UpdateArgs& a, const Tube& g, hipStream_t st, P
     constexpr bool SEEDED = PackHas<NoiseKey, P...>::value || PackHas<CanvasKey, P...>::value;
     // whole-line form: groups of tokens along w' that make up 128 bytes (or the whole row when W is shorter) of latent per (c, t, h)
     const int gt = (g.W < 32 ? g.W : 32) / g.w;
-    if (g_cfg_rows && (gt == 8 || gt == 4) && g.Wt % gt == 0 && g.D % 4 == 0 && (int64_t)gt * (g.D + 4) * 4 <= 64 * 1024) {
+    int planes = 1;      // an APG launch parks c and d0: twice the LDS (the gather form where that does not fit)
+    if constexpr (PackHas<CfgState, P...>::value) planes = pack_get<CfgState>(p...).apg ? 2 : 1;
+    const int64_t lds = (int64_t)planes * gt * (g.D + 4) * 4;
+    if (g_cfg_rows && (gt == 8 || gt == 4) && g.Wt % gt == 0 && g.D % 4 == 0 && lds <= 64 * 1024) {
         const int groups = (int)(g.per / g.D) / gt;
         hipLaunchKernelGGL((gt == 8 ? cfg_unpatch_ddim_rows_kernel<8, SEEDED, P...> : cfg_unpatch_ddim_rows_kernel<4, SEEDED, P...>),
-                           dim3((unsigned)(a.B * groups)), dim3(256), (size_t)gt * (g.D + 4) * 4, st, a.eps, a.z, a.t_now, a.t_prev, a.abar,
+                           dim3((unsigned)(a.B * groups)), dim3(256), (size_t)lds, st, a.eps, a.z, a.t_now, a.t_prev, a.abar,
                            a.T_train, a.guidance, a.eta, a.noise, a.z_out, g, a.B, groups, p...);
     } else {
         const int64_t total4 = (int64_t)a.B * (g.per >> 2);
@@ -1849,7 +2135,7 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key,
                          const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
-                         int canvas_hop, int guide_hop, int slots) {
+                         int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg) {
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "cfg_unpatch_ddim: bad dims");
     Tube g;
     if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
@@ -1859,15 +2145,22 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
     const CanvasDims cv{C, T, canvas_hop, (int64_t)H * W};
     const CanvasDims gcv{C, T, guide_hop, (int64_t)H * W};
     if (int rc = check_fused_update("cfg_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
-                                    guide_hop ? &gcv : nullptr)) return rc;
+                                    guide_hop ? &gcv : nullptr, apg, (int64_t)2 * B * g.per * 4)) return rc;
     if (int rc = check_slot_update("cfg_unpatch_ddim", a, slots, T / t, key, guide, ctl, canvas_hop, guide_hop, k)) return rc;
+    if (apg) {
+        AVD_REQUIRE(aligned16(eps2) && aligned16(eps2 + (int64_t)B * g.per) && aligned16(z) && aligned16(z_out), AVD_EUNSUPPORTED,
+                    "cfg_unpatch_ddim: the APG statistics pass reads 16-byte aligned token rows");
+        if (int rc = run_apg_stats<CFG_SRC_VIDEO>(apg, ctl ? ctl->guidance : nullptr, guidance, eps2, eps2 + (int64_t)B * g.per, g.per, B,
+                                                  g.per, g, AudioGeom{}, st)) return rc;
+    }
     if (ctl && ctl->rescale) {
         AVD_REQUIRE(aligned16(eps2) && aligned16(eps2 + (int64_t)B * g.per), AVD_EUNSUPPORTED,
                     "cfg_unpatch_ddim: the statistics pass reads 16-byte aligned token rows");
         if (int rc = run_cfg_stats<CFG_SRC_VIDEO>(ctl, eps2, eps2 + (int64_t)B * g.per, g.per, guidance, B, g.per, AudioGeom{}, st)) return rc;
     }
     static const int tag = prof_tag_id("cfg_unpatch_ddim_kernel");
-    ProfScope prof(tag, 16.0 * (double)B * g.per, st);
+    static const int tag_apg = prof_tag_id("cfg_unpatch_ddim_kernel<apg>");      // the fused launch of an APG step, timed apart
+    ProfScope prof(apg ? tag_apg : tag, (apg && apg->momentum_buf ? 24.0 : 16.0) * (double)B * g.per, st);
     with_update_pack(k, false, [&](auto... p) { launch_unpatch(a, g, st, p...); });
     AVD_CHECK_LAUNCH("cfg_unpatch_ddim");
     return AVD_OK;
@@ -1927,10 +2220,22 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
     [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
     if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
     float e = 0.f;
+    [[maybe_unused]] bool apg = false;      // a run-time branch of the CTL instantiations: the launch carries an APG part
+    if constexpr (CTL) {
+        const CfgState cs = pack_get<CfgState>(nk...);
+        apg = cs.apg != nullptr;
+        if (apg) {      // two separate overlap-add means (zero on the uncovered tail), then items 2 and 5 of the contract
+            const float cv = f < L ? ola_gather(eps2 + (int64_t)b * Na * D, D, c, len, stride, Na, f) : 0.f;
+            const float uv = f < L ? ola_gather(eps2 + ((int64_t)B + b) * Na * D, D, c, len, stride, Na, f) : 0.f;
+            const float dv = apg_dir(apg_d0(cv, uv), cs.apg_beta, cs.apg_mom ? cs.apg_mom[i] : 0.f);
+            if (cs.apg_mom) cs.apg_mom[i] = dv;
+            e = apg_eps(cv, dv, cs.apg[(int64_t)b * 4 + 2], cs.apg[(int64_t)b * 4 + 1]);
+        }
+    }
     if constexpr (COND) {
         // the single-branch form: the overlap-add mean of the cond tokens, the arithmetic of audio_untok_kernel
         if (f < L) e = ola_gather(eps2 + (int64_t)b * Na * D, D, c, len, stride, Na, f);
-    } else if (f < L) {
+    } else if (!(CTL && apg) && f < L) {
         // CFG combine is linear, but the reference combines per token first and overlap-adds after:
         // gather both halves with the same window order, combine per window
         int n_hi = f / stride;
@@ -1996,7 +2301,7 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st, const avd_noise_key* key,
                                const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
-                               int canvas_hop, int guide_hop, int slots) {
+                               int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg) {
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "cfg_untoken_ddim_audio: bad chunking");
     AVD_REQUIRE(!slots || stride == len, AVD_EUNSUPPORTED,
@@ -2006,10 +2311,15 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
     UpdateKeys k;
     const CanvasDims cv{Ca, F, canvas_hop, 1};
     const CanvasDims gcv{Ca, F, guide_hop, 1};
-    if (int rc = check_fused_update("cfg_untoken_ddim_audio", a, per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
-                                    guide_hop ? &gcv : nullptr)) return rc;
     const AudioGeom ag{Ca, F, len, stride, audio_na(F, len, stride)};
+    if (int rc = check_fused_update("cfg_untoken_ddim_audio", a, per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
+                                    guide_hop ? &gcv : nullptr, apg, (int64_t)2 * B * ag.Na * Ca * len * 4)) return rc;
     if (int rc = check_slot_update("cfg_untoken_ddim_audio", a, slots, ag.Na, key, guide, ctl, canvas_hop, guide_hop, k)) return rc;
+    if (apg) {
+        const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
+        if (int rc = run_apg_stats<CFG_SRC_AUDIO>(apg, ctl ? ctl->guidance : nullptr, guidance, eps2, eps2 + B * half, half, B, per,
+                                                  Tube{}, ag, st)) return rc;
+    }
     if (ctl && ctl->rescale) {
         const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
         if (int rc = run_cfg_stats<CFG_SRC_AUDIO>(ctl, eps2, eps2 + B * half, half, guidance, B, per, ag, st)) return rc;
@@ -2381,7 +2691,7 @@ extern "C" int avd_cfg_unpatch_ddim_f32(const float* eps2, const float* z, const
     AVD_REQUIRE(aligned16(eps2) && aligned16(z) && aligned16(z_out) && (!noise || aligned16(noise)), AVD_EUNSUPPORTED,
                 "cfg_unpatch_ddim: pointers must be 16-byte aligned");
     return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, C, T, H, W, t,
-                                h, w, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0);
+                                h, w, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, nullptr);
 }
 extern "C" int avd_cfg_unpatch_ddim_slots_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                               const float* alpha_bar, int T_train, float guidance, int slots, float* z_out, int B, int C,
@@ -2390,14 +2700,14 @@ extern "C" int avd_cfg_unpatch_ddim_slots_f32(const float* eps2, const float* z,
                 "cfg_unpatch_ddim_slots: pointers must be 16-byte aligned");
     AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_unpatch_ddim_slots: slots must be > 0 (got %d)", slots);
     return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, 0.f, nullptr, z_out, B, C, T, H, W, t, h, w,
-                                static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, slots);
+                                static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, slots, nullptr);
 }
 extern "C" int avd_cfg_untoken_ddim_audio_slots_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                                     const float* alpha_bar, int T_train, float guidance, int slots, float* z_out, int B,
                                                     int Ca, int F, int len, int stride, avd_stream_t stream) {
     AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_untoken_ddim_audio_slots: slots must be > 0 (got %d)", slots);
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, 0.f, nullptr, z_out, B, Ca, F, len, stride,
-                                      static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, slots);
+                                      static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, slots, nullptr);
 }
 extern "C" int avd_fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped, int B,
                                   int64_t outer, int slots, int slot_len, int64_t inner, avd_stream_t stream) {
@@ -2413,7 +2723,7 @@ extern "C" int avd_cfg_unpatch_dpmpp_2m_slots_f32(const float* eps2, const float
     AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_unpatch_dpmpp_2m_slots: slots must be > 0 (got %d)", slots);
     AVD_REQUIRE(t_last && x0_hist, AVD_EINVAL, "cfg_unpatch_dpmpp_2m_slots: null t_last or x0_hist");
     return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, 0.f, nullptr, z_out, B, C, T, H, W, t, h, w,
-                                static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots);
+                                static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots, nullptr);
 }
 extern "C" int avd_cfg_untoken_dpmpp_2m_audio_slots_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
                                                         const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance,
@@ -2422,7 +2732,7 @@ extern "C" int avd_cfg_untoken_dpmpp_2m_audio_slots_f32(const float* eps2, const
     AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_untoken_dpmpp_2m_audio_slots: slots must be > 0 (got %d)", slots);
     AVD_REQUIRE(t_last && x0_hist, AVD_EINVAL, "cfg_untoken_dpmpp_2m_audio_slots: null t_last or x0_hist");
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, 0.f, nullptr, z_out, B, Ca, F, len, stride,
-                                      static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots);
+                                      static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots, nullptr);
 }
 extern "C" int avd_fifo_shift_hist_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped,
                                        const float* hist_in, float* hist_out, int B, int64_t outer, int slots, int slot_len, int64_t inner,
@@ -2508,7 +2818,7 @@ extern "C" int avd_cfg_untoken_ddim_audio_f32(const float* eps2, const float* z,
                                               float eta, const float* noise, float* z_out, int B, int Ca, int F, int len,
                                               int stride, avd_stream_t stream) {
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, noise, z_out, B, Ca, F,
-                                      len, stride, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0);
+                                      len, stride, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, nullptr);
 }
 extern "C" int avd_eps_unpatch_ddim_f32(const float* eps, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                         const float* alpha_bar, int T_train, float eta, const float* noise, float* z_out, int B, int C,
@@ -2563,6 +2873,11 @@ extern "C" int avd_dpmpp_2m_sde_step_f32(const float* x_t, const float* eps_hat,
                                  static_cast<hipStream_t>(stream));
 }
 extern "C" int64_t avd_cfg_stats_bytes(int B, int64_t per_sample) { return cfg_stats_bytes(B, per_sample); }
+extern "C" int64_t avd_apg_stats_bytes(int B, int64_t per_sample) { return apg_stats_bytes(B, per_sample); }
+extern "C" int avd_apg_guidance_f32(const float* e_cond, const float* e_null, const float* guidance, float guidance_scalar,
+                                    const avd_apg_control* apg, float* out, int B, int64_t per_sample, avd_stream_t stream) {
+    return apg_guidance_f32(e_cond, e_null, guidance, guidance_scalar, apg, out, B, per_sample, static_cast<hipStream_t>(stream));
+}
 extern "C" int avd_cfg_rescale_f32(const float* e_cond, const float* e_cfg, const float* phi, void* stats, int64_t stats_bytes, float* out,
                                    int B, int64_t per_sample, avd_stream_t stream) {
     return cfg_rescale_f32(e_cond, e_cfg, phi, stats, stats_bytes, out, B, per_sample, static_cast<hipStream_t>(stream));

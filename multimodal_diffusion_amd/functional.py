@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import numbers
 from typing import Optional
 
 import torch
@@ -411,6 +412,69 @@ def cfg_rescale(e_cond: Tensor, e_cfg: Tensor, phi, *, return_scale: bool = Fals
     if return_scale:
         off = nb - ((4 * B + 15) // 16) * 16           # the scale slot ends the scratch
         return out, stats[off:off + 4 * B].view(torch.float32).clone()
+    return out
+
+
+def apg_params(norm_threshold=0.0, eta_parallel=0.0, momentum=0.0) -> tuple:
+    """(norm_threshold, eta_parallel, momentum) of adaptive projected guidance as floats, after the checks DenoiseEngine, set_apg,
+    ``sampling.apg`` and apg_guidance share: numbers (not bools), finite, norm_threshold >= 0 (0: no norm cap), eta_parallel in [0, 1]."""
+    vals = []
+    for name, v in (("norm_threshold", norm_threshold), ("eta_parallel", eta_parallel), ("momentum", momentum)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real):
+            raise ValueError(f"apg {name} must be a number, got {v!r}")
+        v = float(v)
+        if not math.isfinite(v):
+            raise ValueError(f"apg {name} must be finite, got {v}")
+        vals.append(v)
+    if vals[0] < 0:
+        raise ValueError(f"apg norm_threshold must be >= 0 (0: no norm cap), got {vals[0]}")
+    if not 0.0 <= vals[1] <= 1.0:
+        raise ValueError(f"apg eta_parallel must lie in [0, 1], got {vals[1]}")
+    return tuple(vals)
+
+
+def apg_from_dict(apg) -> Optional[tuple]:
+    """``apg``: None, or a mapping with any of norm_threshold / eta_parallel / momentum (nothing else) -> None or ``apg_params``"""
+    if apg is None:
+        return None
+    if not isinstance(apg, dict):
+        raise ValueError(f"apg must be None or a dict of norm_threshold / eta_parallel / momentum, got {apg!r}")
+    extra = set(apg) - {"norm_threshold", "eta_parallel", "momentum"}
+    if extra:
+        raise ValueError(f"apg takes norm_threshold, eta_parallel and momentum, not {sorted(extra)}")
+    return apg_params(**apg)
+
+
+def apg_guidance(e_cond: Tensor, e_null: Tensor, guidance, *, norm_threshold: float = 0.0, eta_parallel: float = 0.0,
+                 momentum: float = 0.0, momentum_buf: Optional[Tensor] = None, return_coef: bool = False):
+    """Adaptive projected guidance on latent-layout tensors (avd_apg_guidance_f32; contract in include/avdiff_hip.h, "adaptive
+    projected guidance"): per sample b, d = (e_cond - e_null) + momentum * momentum_buf, and out = e_cond + (g_b - 1) s_b (d - k_b
+    e_cond) with s_b = min(1, norm_threshold / |d|) (1 at norm_threshold 0) and k_b = (1 - eta_parallel) <d, e_cond> / <e_cond,
+    e_cond>: the component of d parallel to e_cond is scaled by eta_parallel, the orthogonal one kept.  ``guidance``: a number or B
+    numbers.  ``momentum_buf``: a contiguous float32 device tensor of e_cond's shape, required exactly when momentum != 0; it is
+    read, then overwritten in place with d.  ``return_coef``: also return (s, k, w), float32 [B] each on the device, w = (g - 1) s."""
+    ec, en = L.dev_f32(e_cond, "e_cond"), L.dev_f32(e_null, "e_null")
+    if ec.shape != en.shape or ec.device != en.device:
+        raise ValueError(f"e_cond {tuple(ec.shape)} and e_null {tuple(en.shape)} must have one shape on one device")
+    r, eta_p, beta = apg_params(norm_threshold, eta_parallel, momentum)
+    B = ec.shape[0]
+    per = ec.numel() // B
+    g = cfg_values(guidance, B, "guidance").to(ec.device)
+    if (beta != 0.0) != (momentum_buf is not None):
+        raise ValueError("momentum_buf goes with momentum != 0: pass both or neither")
+    if momentum_buf is not None and not (momentum_buf.is_cuda and momentum_buf.dtype == torch.float32 and momentum_buf.is_contiguous()
+                                         and momentum_buf.shape == ec.shape and momentum_buf.device == ec.device):
+        raise ValueError(f"momentum_buf must be a contiguous float32 tensor of shape {tuple(ec.shape)} on e_cond's device")
+    nb = L.lib().avd_apg_stats_bytes(B, per)
+    if nb < 0:
+        raise ValueError(f"apg_guidance needs >= 2 elements per sample (got {per}) and 1 <= B <= 65535")
+    stats = torch.empty(nb, dtype=torch.uint8, device=ec.device)
+    ctl = L.ApgControl(r, eta_p, beta, L.ptr(momentum_buf), stats.data_ptr(), nb)
+    out = torch.empty_like(ec)
+    L.check(L.lib().avd_apg_guidance_f32(ec.data_ptr(), en.data_ptr(), g.data_ptr(), 0.0, C.byref(ctl), out.data_ptr(), B, per, _st(out)))
+    if return_coef:
+        coef = stats[nb - 16 * B:].view(torch.float32).view(B, 4)      # the coefficient slot ends the scratch: (s, k, w, g)
+        return out, (coef[:, 0].clone(), coef[:, 1].clone(), coef[:, 2].clone())
     return out
 
 

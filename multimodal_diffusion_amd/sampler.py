@@ -163,6 +163,19 @@ class DenoiseEngine:
     engine-owned buffers (a captured graph follows them); switching between the plain and the controlled step starts a new graph
     generation.
 
+    ``apg`` (extension: adaptive projected guidance, Sadat et al. 2024, diffusers' ``AdaptiveProjectedGuidance``; include/avdiff_hip.h,
+    "adaptive projected guidance"; default None = off): a dict with any of ``norm_threshold`` (r >= 0, 0 = no cap on the norm of the
+    guidance direction), ``eta_parallel`` (in [0, 1]: the kept share of the direction's component parallel to the conditional
+    prediction) and ``momentum`` (beta, negative in the paper; 0 = none).  Every CFG step then runs a statistics pass over the eps and
+    steps, inside the same fused kernel, on cond + (g - 1) s (d - k cond) instead of the CFG combine; per-sample ``guidance`` applies,
+    ``guidance_rescale`` != 0 beside it is refused.  The engine owns the statistics scratch and, with momentum, the per-element
+    momentum buffer (``apg_momentum``; zeroed by ``begin`` — so by every ``run`` — and by ``start_latent``; updated in place, so a
+    captured pair leaves it at its address).  Cond-only steps of a guidance interval do not apply it and leave the buffer untouched;
+    ``rewind`` and ``renoise`` (RePaint resampling) carry the buffer as it is: the direction's running average goes on across a jump.
+    ``set_apg`` / ``clear_apg`` change it and start a new graph generation (the parameters are held by value).  ``step_slots`` and the
+    FIFO queue refuse it, as they refuse every CFG control.  What it does to sample quality at a given guidance scale is not measured
+    here: that needs trained weights.
+
     ``guidance_interval`` (extension: guidance in a limited interval, Kynkaanniemi et al. 2024; default None = every step is a CFG
     step): (t_lo, t_hi) in training timesteps, both ends inclusive.  ``run`` takes a CFG step — today's step, whichever form the
     engine runs — where t_lo <= t_now <= t_hi, and a cond-only step elsewhere (include/avdiff_hip.h, "guidance interval"): eps =
@@ -232,7 +245,7 @@ class DenoiseEngine:
                  guidance: float, eta: float = 0.0, tube=(2, 4, 4), chunk=(4, 4), split_streams: Optional[bool] = None,
                  temb_mode: str = "concat", matmul: Optional[str] = None, attn: Optional[str] = None,
                  noise_seed: Optional[int] = None, sample_offset: int = 0, solver: str = "ddim", guidance_rescale=0.0,
-                 guidance_interval=None, noise_keying: str = "sample", canvas_hop: Optional[int] = None):
+                 guidance_interval=None, noise_keying: str = "sample", canvas_hop: Optional[int] = None, apg=None):
         if target not in ("video", "audio"):
             raise ValueError("target must be 'video' or 'audio'")
         if eta < 0:
@@ -268,6 +281,12 @@ class DenoiseEngine:
         self._cfg_g = self._cfg_phi = self._cfg_stats = None
         self._ctl: Optional[L.CfgControl] = None
         self._cfg_sig = None          # what a captured graph holds of the control by value: its pointers
+        # adaptive projected guidance (set_apg): the parameters on the host, the scratch and the momentum buffer once a step needs them
+        self._apg_vals = self._check_apg(Fn.apg_from_dict(apg), self._phi_vals)
+        self._apg: Optional[L.ApgControl] = None
+        self._apg_stats: Optional[torch.Tensor] = None
+        self.apg_momentum: Optional[torch.Tensor] = None
+        self._apg_sig = None          # what a captured graph holds of it by value: the parameters and the two pointers
         self.noise_seed, self.sample_offset = noise_seed, int(sample_offset)
         self._key = None if noise_seed is None else Fn.noise_key(noise_seed, sample_offset)
         if self._key is None and sample_offset != 0:
@@ -347,6 +366,7 @@ class DenoiseEngine:
         self._cons_w: Optional[torch.Tensor] = None
         self._bind_weights()
         self._apply_cfg()
+        self._apply_apg()
 
     # ---- pointer tables.  They hold derived copies (norm-folded / split3 weights), so they are re-derived whenever a
     # parameter's (address, version) changes: load_state_dict, EMA copy_to, an optimiser step or .to(device) after the
@@ -557,6 +577,8 @@ class DenoiseEngine:
         B = self.embed.B
         g = None if guidance is None else Fn.cfg_values(guidance, B, "guidance")
         phi = None if rescale is None else Fn.cfg_values(rescale, B, "guidance_rescale", 0.0, 1.0)
+        if phi is not None:
+            self._check_apg(self._apg_vals, phi)
         if g is not None:
             self._g_vals, self._g_per_sample = g, not _scalar_like(guidance)
         if phi is not None:
@@ -592,6 +614,52 @@ class DenoiseEngine:
         if reason:
             self._generation += 1
             self._stale_reason = reason
+
+    # ---- adaptive projected guidance ----
+    @staticmethod
+    def _check_apg(vals, phi):
+        """APG beside guidance rescale is refused: the rescale's statistics would need the APG output"""
+        if vals is not None and bool((phi != 0).any()):
+            raise ValueError("adaptive projected guidance (apg) cannot be combined with guidance_rescale != 0: the rescale's statistics "
+                             "would need the APG output")
+        return vals
+
+    def set_apg(self, norm_threshold: float = 0.0, eta_parallel: float = 0.0, momentum: float = 0.0) -> None:
+        """Switch adaptive projected guidance on, or change its parameters (class docstring).  Checked before anything changes.  The
+        parameters ride in the launches by value, so a change starts a new graph generation; the momentum buffer keeps its contents
+        (``begin`` / ``start_latent`` zero it)."""
+        self._apg_vals = self._check_apg(Fn.apg_params(norm_threshold, eta_parallel, momentum), self._phi_vals)
+        self._apply_apg()
+
+    def clear_apg(self) -> None:
+        """Back to the CFG combine (the buffers are kept for a later set_apg)."""
+        self._apg_vals = None
+        self._apply_apg()
+
+    def _apply_apg(self) -> None:
+        if self._apg_vals is None:
+            self._apg, sig = None, None
+        else:
+            r, eta_p, beta = self._apg_vals
+            if self._apg_stats is None:
+                nb = L.lib().avd_apg_stats_bytes(self.embed.B, int(np.prod(self.latent_shape[1:])))
+                if nb < 0:
+                    raise ValueError(f"apg needs >= 2 latent elements per sample and B <= 65535 (latent {self.latent_shape})")
+                self._apg_stats = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            if beta != 0.0 and self.apg_momentum is None:
+                self.apg_momentum = torch.zeros(self.latent_shape, device=self.device, dtype=torch.float32)
+            mom = self.apg_momentum if beta != 0.0 else None
+            self._apg = L.ApgControl(r, eta_p, beta, L.ptr(mom), self._apg_stats.data_ptr(), self._apg_stats.numel())
+            sig = (r, eta_p, beta, L.ptr(mom), self._apg_stats.data_ptr())
+        if sig != self._apg_sig:
+            self._generation += 1
+            self._stale_reason = "adaptive projected guidance was switched on or off, or its parameters changed (set_apg / clear_apg)"
+        self._apg_sig = sig
+
+    def _zero_apg_momentum(self) -> None:
+        """a trajectory starts without momentum"""
+        if self.apg_momentum is not None:
+            self.apg_momentum.zero_()
 
     # ---- window consensus: the batch as N consecutive windows of one latent canvas ----
     def set_window_consensus(self, hop: int, weights=None) -> None:
@@ -643,6 +711,7 @@ class DenoiseEngine:
         z_start is z_init.  Computed on the device with the guide's keying (avd_latent_guide_f32 / avd_latent_guide_canvas_f32)."""
         sched_k = su.truncate_schedule(sched, strength)
         n = torch.as_tensor(sched).numel() - 1
+        self._zero_apg_momentum()
         z_init = L.dev_f32(z_init, "z_init")
         if tuple(z_init.shape) != self.latent_shape:
             raise ValueError(f"latent shape {tuple(z_init.shape)} != engine shape {self.latent_shape}")
@@ -720,7 +789,8 @@ class DenoiseEngine:
         (one entry for every kind of eta > 0 DDIM step of a canvas-keyed engine), cond-only (one entry for every solver state, with
         or without a latent guide; the CFG control does not apply there), CFG-controlled, guided, DPM-Solver++(2M), seeded or plain
         DDIM"""
-        guided = self._guide is not None or (self._ctl is not None and not cond_only)
+        apg = None if self._apg is None or cond_only else C.byref(self._apg)      # as the CFG control: not on a cond-only step
+        guided = self._guide is not None or ((self._ctl is not None or apg is not None) and not cond_only)
         tl, h, noise = self._step_args(z, out, noise, t_last, guided)
         lib, desc = L.lib(), C.byref(self.desc)
         key = None if self._key is None else C.byref(self._key)
@@ -729,7 +799,11 @@ class DenoiseEngine:
         tail = (out.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device))
         ctl = None if self._ctl is None or cond_only else C.byref(self._ctl)      # the CFG control does not apply to a cond-only step
         cond = 1 if cond_only else 0
-        if guide is not None and self._guide_hop is not None:
+        if apg is not None:      # one entry for every solver state and keying of the APG step
+            hop = (self.canvas_hop or 0) if self.eta > 0 else 0
+            rc = lib.avd_denoise_step_apg_f32(desc, apg, ctl, guide, key if self.eta > 0 else None, hop,
+                                              (self._guide_hop or 0) if guide is not None else 0, L.ptr(tl), L.ptr(h), *zx, *ts, *tail)
+        elif guide is not None and self._guide_hop is not None:
             rc = lib.avd_denoise_step_canvas_guided_f32(desc, guide, self._guide_hop, key if self.eta > 0 else None, ctl, cond,
                                                         L.ptr(tl), L.ptr(h), *zx, *ts, *tail)
         elif self.solver == "dpmpp_2m" and self.eta > 0:
@@ -820,6 +894,9 @@ class DenoiseEngine:
         if self._ctl is not None:
             raise ValueError("step_slots takes the scalar guidance: per-sample guidance and guidance rescale (the CFG control) are not "
                              "supported there")
+        if self._apg is not None:
+            raise ValueError("step_slots takes the plain CFG combine: adaptive projected guidance (a CFG control) is not supported "
+                             "there: clear_apg() first")
         if self._cons_hop is not None:
             raise ValueError("step_slots takes no window consensus (the windows of a canvas share their timesteps): "
                              "clear_window_consensus() first")
@@ -983,8 +1060,10 @@ class DenoiseEngine:
         self._tn = torch.empty(B, dtype=torch.long, device=dev)
         self._tp = torch.empty(B, dtype=torch.long, device=dev)
         self._tl = torch.empty(B, dtype=torch.long, device=dev)
+        self._zero_apg_momentum()
 
     def rewind(self) -> None:
+        """the cursor back to the schedule's start; an APG momentum buffer is carried as it is (``begin`` zeroes it)"""
         self._cursor.zero_()
 
     def advance(self, src: torch.Tensor, dst: torch.Tensor, cond_only: bool = False) -> None:
@@ -1203,6 +1282,8 @@ def sample_one_direction(*, cfg: Dict, vid_vae, aud_codec, adapt_v: LinearAdapte
     a mask the whole latent is free.  ``guide_seed`` keys the clip's forward noise (default ``noise_seed``, else 0).
     ``sampling.guidance_rescale`` (extension; a per-modality dict like ``guidance_scale``, default 0): CFG rescale phi of the target
     (DenoiseEngine ``guidance_rescale``); 0 runs the plain step.
+    ``sampling.apg`` (extension; a per-modality dict like ``guidance_scale``, each entry a dict of norm_threshold / eta_parallel /
+    momentum; default none): adaptive projected guidance for the target (DenoiseEngine ``apg``) in place of the CFG combine.
     ``guidance_interval`` (extension; default None) or ``sampling.guidance_interval`` (a per-modality dict of [t_lo, t_hi] like
     ``guidance_scale``; the argument wins): apply guidance only on steps with t_lo <= t_now <= t_hi, step on the conditional
     prediction alone elsewhere (DenoiseEngine ``guidance_interval``).

@@ -427,6 +427,10 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     without it every rank draws from its own device generator.
     ``guidance_interval`` (default None) or ``sampling.guidance_interval`` (per modality, [t_lo, t_hi]; the argument wins): guidance
     on the steps with t_lo <= t_now <= t_hi only, cond-only steps elsewhere (DenoiseEngine ``guidance_interval``).
+    ``sampling.apg`` (per modality, a dict of norm_threshold / eta_parallel / momentum; default none): adaptive projected guidance in
+    place of the CFG combine on every window's engine (DenoiseEngine ``apg``).  Every window is its own sample — its coefficients and
+    its momentum buffer depend on that window alone, also under a consensus — so any ``max_windows_per_batch`` and ``shard`` give the
+    same windows.
     ``consensus`` (default None = independent windows, today's output; else ``streaming.latent_consensus``, the argument wins):
     "uniform" or a table of L weights > 0 (L latent positions per window, ``latent_hop``) switches latent window consensus on: the
     windows are views of one latent canvas and after every step each canvas position under several windows becomes their weighted

@@ -40,6 +40,9 @@ ap.add_argument("--keep-frames", type=int, default=None,
 ap.add_argument("--guidance-rescale", type=float, default=None,
                 help="time only the sampler loop, both directions, plain CFG against DenoiseEngine(guidance_rescale=PHI) (statistics "
                      "pass + controlled fused step), interleaved in one process")
+ap.add_argument("--apg", action="store_true",
+                help="with --guidance-rescale: also time DenoiseEngine(apg=...) (adaptive projected guidance: statistics pass + APG fused "
+                     "step) without and with momentum, in the same interleaved rounds")
 ap.add_argument("--guidance-interval", type=int, nargs=2, default=None, metavar=("LO", "HI"),
                 help="time only the sampler loop, both directions, the plain trajectory against DenoiseEngine(guidance_interval=(LO, HI)) "
                      "(cond-only steps outside the interval), interleaved in one process")
@@ -133,13 +136,16 @@ if args.guidance_rescale is not None:
     # CFG rescale cost: the plain engine against one with guidance_rescale = PHI, interleaved; ms/step medians
     import statistics
     zv_prompt = torch.randn(B, 8, 12, size // 8, size // 8, generator=torch.Generator().manual_seed(3)).to(dev)
-    variants = (("plain", 0.0), (f"rescale={args.guidance_rescale:g}", args.guidance_rescale))
+    variants = (("plain", {}), (f"rescale={args.guidance_rescale:g}", dict(guidance_rescale=args.guidance_rescale)))
+    if args.apg:
+        apg = dict(norm_threshold=15.0, eta_parallel=0.0)
+        variants += (("apg", dict(apg=dict(apg, momentum=0.0))), ("apg momentum", dict(apg=dict(apg, momentum=-0.5))))
     for target, z_init, prompt, n_prompt in (("video", z0, za, 37), ("audio", za, zv_prompt, (12 // 2) * (size // 8 // 4) ** 2)):
         engs = []
-        for name, phi in variants:
+        for name, ctl in variants:
             eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=tdim, target=target,
                                   latent_shape=tuple(z_init.shape), prompt_tokens=n_prompt, alpha_bar=abar, guidance=3.5,
-                                  guidance_rescale=phi, matmul=args.matmul, solver=args.solver)
+                                  matmul=args.matmul, solver=args.solver, **ctl)
             eng.set_prompt(prompt)
             eng.run(z_init, sched[:4])                  # warm-up
             engs.append(eng)
