@@ -267,7 +267,8 @@ int avd_canvas_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* 
  *     at t_now and still takes part in attention; only its update is skipped (its eps is not read).
  * A table filled with one pair per sample gives the bits of the per-sample entry; a slot gives the bits the per-sample entry gives
  * there when its whole sample runs at the slot's pair.  Attention and the GEMMs are the per-sample step's, launch for launch.
- * Scope, everything else is refused before any launch (AVD_EINVAL): DDIM or DPM-Solver++(2M) (below) at eta == 0 (no noise, no key), the
+ * Scope, everything else is refused before any launch (AVD_EINVAL): DDIM or DPM-Solver++(2M) (below) at eta == 0 (no noise, no key) or,
+ * through the *_slots_seeded entries, at eta > 0 with a slot key ("clip-keyed slot noise" below; no unseeded or explicit noise), the
  * CFG step with the scalar guidance, the concat embedding (temb_add == 0), no latent guide, CFG control or canvas keying.  Both targets,
  * every matmul / attention mode, both stream layouts (split_streams) and the null half's short layout are taken as by the plain step.
  * `slots` must equal the geometry's S.  Samplers whose positions sit at different noise levels (FIFO-Diffusion, rolling diffusion,
@@ -298,6 +299,49 @@ int avd_cfg_untoken_dpmpp_2m_audio_slots_f32(const float* eps2, const float* z, 
                                              const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, int slots,
                                              float* x0_hist, float* z_out, int B, int Ca, int F, int len, int stride,
                                              avd_stream_t stream);
+
+/* ---- clip-keyed slot noise: the slot entries at eta > 0 (a public contract).  Slots of one call sit at different timesteps and move
+ * through a queue, so a slot's step noise follows the CLIP POSITION the slot holds, not its place in the batch: the same clip slot
+ * draws the same normals in a plain queue or a lookahead queue, eagerly or replayed, whichever sample holds it and whenever.
+ * For a batch [B, outer, L, inner] ((outer, L, inner) as in "canvas-keyed noise"), slot_len the tube's p0 (video) or the chunk length
+ * (audio) and s = min(l / slot_len, S - 1) the slot of sliding position l (the audio tail follows the last slot, as in "slot
+ * timesteps"), element (b, o, l, i) sits on clip position
+ *     p = ((first + max(*cursor, 0) + b*stride)*slot_len + l)  mod 2^32       (the sum in 64 bits, then truncated: negative slots wrap,
+ *                                                                              as the lookahead's context positions do)
+ * and its normal is the per-sample stream's construction (avd_noise_key: the same Philox4x32-10, Box-Muller, rounding, "element takes
+ * n[e' & 3]") with counter (e' >> 2, (uint32) p, (uint32) t_now[b, s], 0x534C4F54), e' = o*inner + i.  The last word ("SLOT") is a
+ * domain word of its own, and it has to be: a FIFO queue starts, and its tail is filled, with canvas-keyed normals of tag 0x44444D31
+ * at positions c*slot_len + j and timestep s_0, and a slot's first step has t_now = s_0 — under the old tag the first step's noise
+ * term would be the very normals the slot was initialised with.
+ *   - a held slot (t_prev == t_now) draws nothing and stays bit for bit (its x0_hist elements too);
+ *   - at eta == 0 nothing is drawn and the key's fields are not read: the bits of the eta == 0 slot entries;
+ *   - the final step to t_prev = -1 has DDIM's sigma = 0 and the SDE form's c_n = 0, as in the per-sample contracts;
+ *   - the key addresses nothing: whatever the cursor holds no kernel leaves its buffers, and the kernels only read the cursor.
+ * Checked before any launch (AVD_EINVAL): a non-null key; at eta > 0 stride >= 1, |first| < 2^32, outer*inner < 2^34.
+ * A uniform table (one pair per sample) with explicit noise = avd_slot_noise_f32's output gives the bits of the per-sample entries. */
+typedef struct {
+    uint64_t seed;
+    int64_t  first;          /* clip slot held by slot 0 of sample 0 of the call; may be negative */
+    int32_t  stride;         /* clip slots from one sample to the next: S for a queue of samples, S - ctx for lookahead windows; >= 1 */
+    const int32_t* cursor;   /* optional device int32 (a "FIFO device cursor"): max(*cursor, 0) is added to first; NULL: 0 */
+} avd_slot_key;
+/* out[b, o, l, i] = the clip-keyed normal above; out: fp32 [B, outer, L, inner]; t_now: int64 [B*slots]; slots*slot_len <= L (positions
+ * past the last slot follow it).  16-byte lanes (one Philox call per four values) when inner % 4 == 0 and out is 16-byte aligned, one
+ * element per lane otherwise; same bits either way, and the same bits as the fused draw.  The key is read whatever eta a step has. */
+int avd_slot_noise_f32(const avd_slot_key* key, const int64_t* t_now, float* out, int B, int64_t outer, int L, int slots, int slot_len,
+                       int64_t inner, avd_stream_t stream);
+/* The fused updates alone at eta >= 0: the seeded twins of avd_cfg_unpatch_ddim_slots_f32 / avd_cfg_untoken_ddim_audio_slots_f32.
+ * t_last and x0_hist both NULL: the DDIM slot update with sigma(eta) at each slot's pair.  Both set: the slot form of the
+ * DPM-Solver++(2M) update in its SDE form (avd_dpmpp_2m_sde_step_f32's coefficients at each slot's triple; x0_hist as in the ODE slot
+ * form).  Everything else as those entries. */
+int avd_cfg_unpatch_ddim_slots_seeded_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                          const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, float eta,
+                                          const avd_slot_key* key, int slots, float* x0_hist, float* z_out, int B, int C, int T, int H,
+                                          int W, int t, int h, int w, avd_stream_t stream);
+int avd_cfg_untoken_ddim_audio_slots_seeded_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                                const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, float eta,
+                                                const avd_slot_key* key, int slots, float* x0_hist, float* z_out, int B, int Ca, int F,
+                                                int len, int stride, avd_stream_t stream);
 
 /* ---- FIFO queue shift: the queue step of diagonal denoising (FIFO-Diffusion, Kim et al. 2024) in one out-of-place launch.
  * The batch z_in [B, outer, L, inner] ((outer, L, inner) as in "canvas-keyed noise") with L = slots*slot_len is read as a queue of
@@ -832,6 +876,15 @@ int avd_denoise_step_slots_f32(const avd_step_desc* s, const float* z, const flo
 int avd_denoise_step_slots_dpmpp_2m_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_last,
                                         const int64_t* t_now, const int64_t* t_prev, int slots, float* x0_hist, float* z_out,
                                         void* workspace, int64_t workspace_bytes, avd_stream_t stream);
+/* The whole step on slot timesteps at s->eta >= 0, both solvers (see "clip-keyed slot noise"): t_last and x0_hist both NULL end it in
+ * the DDIM slot update, both set in the slot form of DPM-Solver++(2M) (its SDE form at eta > 0), the noise of every stepping slot
+ * drawn inside the fused kernel by clip position.  The front end is avd_denoise_step_slots_f32's, launch for launch; the key is
+ * checked before the model runs.  At s->eta == 0 the key is not read and the result has the bits of the two entries above.
+ * Graph-capturable: the tables, x0_hist and key->cursor are read at their addresses at every launch; seed, first and stride are held
+ * by value. */
+int avd_denoise_step_slots_seeded_f32(const avd_step_desc* s, const avd_slot_key* key, const int64_t* t_last, float* x0_hist,
+                                      const float* z, const float* Xp, const int64_t* t_now, const int64_t* t_prev, int slots,
+                                      float* z_out, void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 /* As avd_denoise_step_f32, with the eta > 0 noise drawn inside the fused CFG + DDIM kernel from the seeded stream (avd_noise_key)
  * for samples key->sample_offset .. + B - 1 at t_now: no noise buffer, graph-capturable.  With s->eta == 0 it is the plain step. */
 int avd_denoise_step_seeded_f32(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp,

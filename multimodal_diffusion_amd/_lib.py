@@ -68,6 +68,12 @@ class NoiseKey(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("sample_offset", C.c_int64)]
 
 
+class SlotKey(C.Structure):
+    """avd_slot_key: the clip keying of the slot entries' eta > 0 noise (contract in include/avdiff_hip.h, "clip-keyed slot noise").
+    ``cursor`` is a raw device pointer or None: keep its tensor alive."""
+    _fields_ = [("seed", C.c_uint64), ("first", C.c_int64), ("stride", C.c_int32), ("cursor", C.c_void_p)]
+
+
 class LatentGuide(C.Structure):
     """avd_latent_guide: a known clean latent, its mask and the key of its known-noise stream (contract in include/avdiff_hip.h)."""
     _fields_ = [("known", C.c_void_p), ("mask", C.c_void_p), ("mask_batch_stride", C.c_int64), ("key", NoiseKey)]
@@ -157,6 +163,11 @@ SIGNATURES = {
     "avd_cfg_unpatch_dpmpp_2m_slots_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _I, _P, _P] + [_I] * 8 + [_P]),
     "avd_cfg_untoken_dpmpp_2m_audio_slots_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _I, _P, _P] + [_I] * 5 + [_P]),
     "avd_denoise_step_slots_dpmpp_2m_f32": (_I, [C.POINTER(StepDesc), _P, _P, _P, _P, _P, _I, _P, _P, _P, _L, _P]),
+    "avd_slot_noise_f32": (_I, [C.POINTER(SlotKey), _P, _P, _I, _L, _I, _I, _I, _L, _P]),
+    "avd_cfg_unpatch_ddim_slots_seeded_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _F, C.POINTER(SlotKey), _I, _P, _P] + [_I] * 8 + [_P]),
+    "avd_cfg_untoken_ddim_audio_slots_seeded_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _F, C.POINTER(SlotKey), _I, _P, _P] + [_I] * 5 +
+                                                    [_P]),
+    "avd_denoise_step_slots_seeded_f32": (_I, [C.POINTER(StepDesc), C.POINTER(SlotKey), _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P]),
     "avd_fifo_shift_hist_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _P, _P, _P, _P, _P, _I, _L, _I, _I, _L, _P]),
     "avd_fifo_lookahead_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _I, _P, _P, _P, _I, _L, _I, _I, _I, _L, _P]),
     "avd_fifo_lookahead_hist_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _I, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _L, _P]),

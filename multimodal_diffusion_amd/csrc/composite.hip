@@ -84,13 +84,13 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key = nullptr,
                          const int64_t* t_last = nullptr, float* x0_hist = nullptr, const avd_latent_guide* guide = nullptr,
                          const avd_cfg_control* ctl = nullptr, int canvas_hop = 0, int guide_hop = 0, int slots = 0,
-                         const avd_apg_control* apg = nullptr);
+                         const avd_apg_control* apg = nullptr, const avd_slot_key* skey = nullptr);
 int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st,
                                const avd_noise_key* key = nullptr, const int64_t* t_last = nullptr, float* x0_hist = nullptr,
                                const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr, int canvas_hop = 0, int guide_hop = 0,
-                               int slots = 0, const avd_apg_control* apg = nullptr);
+                               int slots = 0, const avd_apg_control* apg = nullptr, const avd_slot_key* skey = nullptr);
 int assemble_cond_f32(float* X1, const float* temb, const float* Xp, int B, int N, int d, int tdim, int Nt, int Np, int target_first,
                       hipStream_t st);
 int assemble_rows_cond_f32(float* X1, const int64_t* t_now, const float* freqs, const float* Xp, float* ss, int B, int N, int d,
@@ -104,6 +104,7 @@ int eps_untoken_ddim_audio_f32(const float* eps1, const float* z, const int64_t*
                                hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist,
                                const avd_latent_guide* guide, int canvas_hop = 0, int guide_hop = 0);
 int check_canvas_key(const avd_noise_key* key, int N, int64_t outer, int L, int hop, int64_t inner);
+int check_slot_key(const avd_slot_key* key, int B, int64_t outer, int slot_len, int64_t inner);
 int check_canvas_guide(const avd_latent_guide* g, int N, int64_t outer, int L, int hop, int64_t inner, const float* out,
                        const float* x0_hist);
 int check_latent_guide(const avd_latent_guide* g, int B, int64_t per, const float* out, const float* x0_hist);
@@ -895,7 +896,7 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
                         const int64_t* t_prev, const float* noise, float* z_out, void* workspace, int64_t workspace_bytes,
                         avd_stream_t stream, const int64_t* t_last = nullptr, float* x0_hist = nullptr,
                         const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr, int canvas_hop = 0,
-                        int guide_hop = 0, int slots = 0, const avd_apg_control* apg = nullptr) {
+                        int guide_hop = 0, int slots = 0, const avd_apg_control* apg = nullptr, const avd_slot_key* skey = nullptr) {
     StepWs ws;
     if (int rc = open_step(s, z, z_out, t_now, t_prev, workspace, workspace_bytes, ws)) return rc;
     auto& [p, X2, tok, core_ws, head_ws, ssx, eps2] = ws;
@@ -947,9 +948,10 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
     if (e.target_kind == 0)
         return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, s->alpha_bar, s->T_train, s->guidance, s->eta, noise, z_out,
                                     e.B, e.C, e.T, e.H, e.W, e.p0, e.p1, e.p2, st, key, t_last, x0_hist, guide, ctl, canvas_hop,
-                                    guide_hop, slots, apg);
+                                    guide_hop, slots, apg, skey);
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, s->alpha_bar, s->T_train, s->guidance, s->eta, noise, z_out,
-                                      e.B, e.C, e.T, e.p0, e.p1, st, key, t_last, x0_hist, guide, ctl, canvas_hop, guide_hop, slots, apg);
+                                      e.B, e.C, e.T, e.p0, e.p1, st, key, t_last, x0_hist, guide, ctl, canvas_hop, guide_hop, slots, apg,
+                                      skey);
 }
 
 // The cond-only step of a guidance interval: the conditional branch alone, in the cond half of every workspace region of the CFG step's
@@ -1061,6 +1063,34 @@ extern "C" int avd_denoise_step_slots_dpmpp_2m_f32(const avd_step_desc* s, const
     AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "denoise_step_slots_dpmpp_2m: x0_hist must be 16-byte aligned");
     return denoise_step(s, nullptr, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, nullptr,
                         nullptr, 0, 0, slots);
+}
+
+// The whole step on slot timesteps at eta > 0 ("clip-keyed slot noise" in the header), both solvers: t_last / x0_hist both null = DDIM,
+// both set = the SDE form of the DPM-Solver++(2M) slot update.  The front end is avd_denoise_step_slots_f32's; the key is checked here,
+// before the model runs, as the fused update's launcher checks it again.  At eta == 0 the key is not read: the plain slot step.
+extern "C" int avd_denoise_step_slots_seeded_f32(const avd_step_desc* s, const avd_slot_key* key, const int64_t* t_last, float* x0_hist,
+                                                 const float* z, const float* Xp, const int64_t* t_now, const int64_t* t_prev, int slots,
+                                                 float* z_out, void* workspace, int64_t workspace_bytes, avd_stream_t stream) {
+    AVD_REQUIRE(s, AVD_EINVAL, "denoise_step_slots_seeded: null descriptor");
+    AVD_REQUIRE(key, AVD_EINVAL, "denoise_step_slots_seeded: null slot key");
+    AVD_REQUIRE(!s->embed.temb_add, AVD_EINVAL, "denoise_step_slots_seeded: slot timesteps take the concat embedding (temb_add == 0)");
+    if (int rc = check_embed(&s->embed)) return rc;
+    int S = 0, tok = 0;
+    if (int rc = embed_slots(&s->embed, S, tok)) return rc;
+    AVD_REQUIRE(slots == S, AVD_EINVAL, "denoise_step_slots_seeded: slots %d must equal the geometry's %d slots along the sliding axis", slots,
+                S);
+    const avd_embed_desc& e = s->embed;
+    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "denoise_step_slots_seeded: t_last and x0_hist go together (the DPM-Solver++(2M) update)");
+    if (x0_hist) {
+        const int64_t n = (int64_t)e.B * e.C * e.T * e.H * e.W;
+        AVD_REQUIRE(!(z && overlaps(x0_hist, z, n)) && !(z_out && overlaps(x0_hist, z_out, n)), AVD_EINVAL,
+                    "denoise_step_slots_seeded: x0_hist must not alias z or z_out");
+        AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "denoise_step_slots_seeded: x0_hist must be 16-byte aligned");
+    }
+    if (s->eta > 0.f)
+        if (int rc = check_slot_key(key, e.B, e.C, e.p0, (int64_t)e.H * e.W)) return rc;
+    return denoise_step(s, nullptr, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, nullptr,
+                        nullptr, 0, 0, slots, nullptr, key);
 }
 
 extern "C" int avd_denoise_step_seeded_f32(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp,

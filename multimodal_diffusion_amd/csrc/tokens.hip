@@ -323,6 +323,9 @@ struct CondOnly {};
 // Behind a DpmState (the pack `DpmState, SlotTimes`, SEEDED false) it is the slot form of the DPM-Solver++(2M) ODE update: DpmState's
 // t_last is a [B, S] table as well, every element takes ddim_coef / dpm_coef at its slot's entry, and a held slot keeps z and neither
 // reads nor writes its x0_hist elements.
+// A SlotKey behind the SlotTimes (SEEDED true: `SlotTimes, SlotKey` and `DpmState, SlotTimes, SlotKey`) is the slot form at eta > 0
+// ("clip-keyed slot noise"): a stepping slot's noise term is drawn by the clip position the slot holds (slot_normal4), DDIM's sigma or
+// the SDE form's c_n taken at the slot's entry.  A held slot draws nothing.
 struct SlotTimes {
     int S;
 };
@@ -332,17 +335,19 @@ struct CanvasGuideState;
 struct CfgState;
 // a well-formed pack: optionally one DpmState; one key exactly when SEEDED (a NoiseKey, or a CanvasKey for the canvas-keyed draw: seeded
 // DDIM noise, or with the DpmState the SDE form's noise); then optionally one GuideState or CanvasGuideState (the guide's known noise
-// keyed per sample or by canvas position; a canvas-keyed guide never rides with a NoiseKey), then optionally one CfgState or CondOnly
+// keyed per sample or by canvas position; a canvas-keyed guide never rides with a NoiseKey), then optionally one CfgState or CondOnly.
+// The slot form's packs are SlotTimes, behind the DpmState if there is one, and its key is a SlotKey, which rides nowhere else.
 struct NoiseKey;
 struct CanvasKey;
+struct SlotKey;
 template <bool SEEDED, class... X> struct PackOk {
     template <class T> static constexpr int n = PackHas<T, X...>::value ? 1 : 0;
     static constexpr bool value = sizeof...(X) == (SEEDED ? 1 : 0) + n<DpmState> + n<GuideState> + n<CanvasGuideState> + n<CfgState> +
                                                       n<CondOnly> + n<SlotTimes> &&
-                                  !(n<SlotTimes> && sizeof...(X) != 1 + n<DpmState>) &&
+                                  !(n<SlotTimes> && sizeof...(X) != 1 + n<DpmState> + n<SlotKey>) && n<SlotKey> <= n<SlotTimes> &&
                                   !(n<CfgState> && n<CondOnly>) && !(n<GuideState> && n<CanvasGuideState>) &&
                                   !(n<CanvasGuideState> && n<NoiseKey>) &&
-                                  n<NoiseKey> + n<CanvasKey> == (SEEDED ? 1 : 0);
+                                  n<NoiseKey> + n<CanvasKey> + n<SlotKey> == (SEEDED ? 1 : 0);
 };
 template <class T, class A, class... R> __host__ __device__ __forceinline__ T pack_get(const A& a, const R&... r) {
     if constexpr (std::is_same<T, A>::value) return a;
@@ -494,6 +499,86 @@ int canvas_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out,
     else
         hipLaunchKernelGGL(canvas_noise_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t_now, out, ck, outer, L, inner, n);
     AVD_CHECK_LAUNCH("canvas_noise");
+    return AVD_OK;
+}
+
+// ------------------------------------------------------------------ clip keying of the seeded stream (slot timesteps at eta > 0)
+// The contract is written out in include/avdiff_hip.h ("clip-keyed slot noise").  Sample b of a batch [B, outer, L, inner] holds clip
+// slots first + max(*cursor, 0) + b * stride ..; element (o, l, i) sits on clip position p = that slot * slot_len + l (mod 2^32) and
+// takes the per-sample stream's value for sample p, its slot's timestep and element e' = o * inner + i under the domain word SLOT_TAG:
+// the draw follows the clip slot through the queue, whichever sample holds it.  The cursor is only read, and it addresses nothing.
+constexpr uint32_t SLOT_TAG = 0x534C4F54u;      // "SLOT": apart from the stream a slot was initialised from (same positions, t = s_0)
+struct SlotKey {
+    uint32_t k0, k1;          // seed & 0xffffffff, seed >> 32
+    int64_t first;            // clip slot of slot 0 of sample 0, before the cursor
+    int32_t stride, slot_len; // clip slots from one sample to the next; positions of one slot
+    const int32_t* cursor;    // device int32 or null
+};
+
+// as canvas_normal4; t: the timestep of the slot of position l.  The sum wraps in 64 bits, so its low word is the contract's p
+__device__ __forceinline__ f32x4 slot_normal4(const SlotKey& sk, int b, int64_t o, int l, int64_t i, int64_t inner, uint32_t t) {
+    int32_t m = sk.cursor ? *sk.cursor : 0;
+    if (m < 0) m = 0;
+    const uint64_t p = ((uint64_t)sk.first + (uint64_t)m + (uint64_t)b * (uint64_t)sk.stride) * (uint64_t)sk.slot_len + (uint64_t)l;
+    return philox_normal4(NoiseKey{sk.k0, sk.k1, 0u}, (uint32_t)((o * inner + i) >> 2), (uint32_t)p, t, SLOT_TAG);
+}
+
+// V lanes as canvas_noise_kernel; t_now is the [B, S] table, position l in slot min(l / slot_len, S - 1)
+template <int V>
+__global__ __launch_bounds__(256) void slot_noise_kernel(const int64_t* __restrict__ t_now, float* __restrict__ out, SlotKey sk,
+                                                         int64_t outer, int L, int S, int64_t inner, int64_t n) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const int64_t iv = inner / V;
+    const int64_t i = (idx % iv) * V;
+    int64_t r = idx / iv;
+    const int l = (int)(r % L);
+    r /= L;
+    const int64_t o = r % outer;
+    const int b = (int)(r / outer);
+    int s = l / sk.slot_len;
+    if (s > S - 1) s = S - 1;
+    const f32x4 v = slot_normal4(sk, b, o, l, i, inner, (uint32_t)t_now[(int64_t)b * S + s]);
+    if constexpr (V == 4) *reinterpret_cast<f32x4*>(out + idx * 4) = v;
+    else out[idx] = v[(int)((o * inner + i) & 3)];
+}
+
+// the checks of the clip keying, all before any HIP call: stride >= 1, |first| < 2^32 and one position's slice below 2^34 elements
+int make_slot_key(const avd_slot_key* key, int B, int64_t outer, int slot_len, int64_t inner, SlotKey& sk, const char* what = "slot noise") {
+    AVD_REQUIRE(key, AVD_EINVAL, "%s: null slot key", what);
+    AVD_REQUIRE(B > 0 && outer > 0 && slot_len > 0 && inner > 0, AVD_EINVAL, "%s: bad dims (B %d, outer %lld, slot_len %d, inner %lld)", what,
+                B, (long long)outer, slot_len, (long long)inner);
+    AVD_REQUIRE(key->stride >= 1, AVD_EINVAL, "%s: the slot key's stride must be >= 1 (got %d)", what, key->stride);
+    const int64_t lim = (int64_t)1 << 32;
+    AVD_REQUIRE(key->first > -lim && key->first < lim, AVD_EINVAL, "%s: the slot key's first %lld must lie in (-2^32, 2^32)", what,
+                (long long)key->first);
+    AVD_REQUIRE(outer <= (((int64_t)1 << 34) - 1) / inner, AVD_EINVAL, "%s: outer %lld * inner %lld must be < 2^34", what,
+                (long long)outer, (long long)inner);
+    sk = SlotKey{(uint32_t)(key->seed & 0xffffffffu), (uint32_t)(key->seed >> 32), key->first, key->stride, slot_len, key->cursor};
+    return AVD_OK;
+}
+
+int check_slot_key(const avd_slot_key* key, int B, int64_t outer, int slot_len, int64_t inner) {
+    SlotKey sk;
+    return make_slot_key(key, B, outer, slot_len, inner, sk);
+}
+
+int slot_noise_f32(const avd_slot_key* key, const int64_t* t_now, float* out, int B, int64_t outer, int L, int slots, int slot_len,
+                   int64_t inner, hipStream_t st) {
+    SlotKey sk;
+    if (int rc = make_slot_key(key, B, outer, slot_len, inner, sk)) return rc;
+    AVD_REQUIRE(t_now && out, AVD_EINVAL, "slot_noise: null pointer");
+    AVD_REQUIRE(slots > 0 && (int64_t)slots * slot_len <= L && (int64_t)B * slots <= 0x7fffffff, AVD_EINVAL,
+                "slot_noise: slots %d * slot_len %d must lie in [1, L %d] and B %d * slots fit an int", slots, slot_len, L, B);
+    const bool vec = inner % 4 == 0 && aligned16(out);
+    AVD_REQUIRE((double)B * (double)outer * (double)L * (double)inner < 9.0e18, AVD_EUNSUPPORTED, "slot_noise: too many values");
+    const int64_t n = (int64_t)B * outer * L * inner / (vec ? 4 : 1);
+    AVD_REQUIRE((n + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "slot_noise: %lld lanes are too many for one launch", (long long)n);
+    if (vec)
+        hipLaunchKernelGGL(slot_noise_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t_now, out, sk, outer, L, slots, inner, n);
+    else
+        hipLaunchKernelGGL(slot_noise_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t_now, out, sk, outer, L, slots, inner, n);
+    AVD_CHECK_LAUNCH("slot_noise");
     return AVD_OK;
 }
 
@@ -1797,7 +1882,10 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
     if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
     f32x4 zn = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (CANVAS) {      // the canvas-keyed draw: this lane's float4 lies inside one (c, t) slice (W % 4 == 0)
+    if constexpr (PackHas<SlotKey, Key...>::value) {      // the clip-keyed draw of a stepping slot: the (c, t) slice of the canvas-keyed draw
+        const int64_t hw4 = ((int64_t)g.H * g.W) >> 2, r = e4 / hw4;
+        zn = slot_normal4(pack_get<SlotKey>(nk...), b, r / g.T, (int)(r % g.T), (e4 % hw4) * 4, hw4 * 4, (uint32_t)t_now[tb]);
+    } else if constexpr (CANVAS) {      // the canvas-keyed draw: this lane's float4 lies inside one (c, t) slice (W % 4 == 0)
         const int64_t hw4 = ((int64_t)g.H * g.W) >> 2, r = e4 / hw4;
         zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, r / g.T, (int)(r % g.T), (e4 % hw4) * 4, hw4 * 4, (uint32_t)t_now[b]);
     } else if constexpr (SEEDED) {
@@ -1931,7 +2019,10 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         }
         f32x4 o;
         [[maybe_unused]] f32x4 zn = {0.f, 0.f, 0.f, 0.f};      // the unkeyed DPM update (eta == 0) draws nothing
-        if constexpr (CANVAS) {      // element (c, t, h, w) of window b: canvas position from t, element (c, h W + w) of its slice
+        if constexpr (PackHas<SlotKey, Key...>::value) {      // the clip-keyed draw: the canvas-keyed decomposition, the block's slot timestep
+            zn = slot_normal4(pack_get<SlotKey>(nk...), b, cc, tq * g.t + tt, (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo,
+                              (int64_t)g.H * g.W, (uint32_t)t_now[tb]);
+        } else if constexpr (CANVAS) {      // element (c, t, h, w) of window b: canvas position from t, element (c, h W + w) of its slice
             zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, cc, tq * g.t + tt, (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo,
                                 (int64_t)g.H * g.W, (uint32_t)t_now[b]);
         } else if constexpr (SEEDED) {
@@ -1981,6 +2072,8 @@ struct UpdateKeys {
     bool dpm, seeded, canvas, guide, cguide, ctl;
     bool slots;        // the slot form: the pack is sl, or ds then sl for DPM-Solver++(2M) (set by check_slot_update after check_fused_update)
     SlotTimes sl;
+    bool skey;         // the slot form at eta > 0: sk ends the slot pack (clip-keyed slot noise)
+    SlotKey sk;
     DpmState ds;
     NoiseKey nk;
     CanvasKey ck;      // canvas: the seeded draw is keyed by canvas position (ck replaces nk in the pack)
@@ -2008,16 +2101,16 @@ struct CanvasDims {
 static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per, const avd_noise_key* key, const int64_t* t_last,
                               float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl, UpdateKeys& k,
                               const CanvasDims* cv = nullptr, const CanvasDims* gcv = nullptr, const avd_apg_control* apg = nullptr,
-                              int64_t eps_bytes = 0) {
+                              int64_t eps_bytes = 0, const avd_slot_key* skey = nullptr) {
     AVD_REQUIRE(a.eps && a.z && a.t_now && a.t_prev && a.abar && a.z_out, AVD_EINVAL, "%s: null pointer", what);
-    AVD_REQUIRE(a.eta >= 0.f && (a.eta == 0.f || a.noise || key), AVD_EINVAL, "%s: eta > 0 needs a noise tensor or a noise key", what);
+    AVD_REQUIRE(a.eta >= 0.f && (a.eta == 0.f || a.noise || key || skey), AVD_EINVAL, "%s: eta > 0 needs a noise tensor or a noise key", what);
     AVD_REQUIRE(a.z != a.z_out, AVD_EINVAL, "%s: z_out must not alias z", what);
     AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "%s: t_last and x0_hist go together (the DPM-Solver++(2M) update)", what);
     k = UpdateKeys{};
     k.dpm = x0_hist != nullptr;
     k.ds = DpmState{t_last, x0_hist};
     if (k.dpm) {
-        AVD_REQUIRE(a.eta == 0.f || (key && !a.noise), AVD_EINVAL,
+        AVD_REQUIRE(a.eta == 0.f || ((key || skey) && !a.noise), AVD_EINVAL,
                     "%s: the DPM-Solver++(2M) update with eta > 0 draws its noise from a noise key (no unseeded or explicit noise)", what);
         AVD_REQUIRE(!overlaps(x0_hist, a.z, a.B * per) && !overlaps(x0_hist, a.z_out, a.B * per), AVD_EINVAL,
                     "%s: x0_hist must not overlap z or z_out", what);
@@ -2053,21 +2146,34 @@ static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per
 
 // The slot form's checks, before any HIP call: slots == 0 is the per-sample update; otherwise `slots` must be the geometry's S and the
 // update is DDIM or, with t_last / x0_hist (checked as a pair by check_fused_update; t_last is then a [B, S] table too), DPM-Solver++(2M),
-// at eta == 0 with nothing else in the pack (the scope of "slot timesteps" in include/avdiff_hip.h)
+// at eta == 0 with nothing else in the pack (the scope of "slot timesteps" in include/avdiff_hip.h), or at eta > 0 with a slot key
+// ("clip-keyed slot noise"; skd: the key's (outer, slot_len, inner)), which at eta == 0 is not read
+struct SlotKeyDims {
+    int64_t outer;
+    int slot_len;
+    int64_t inner;
+};
 static int check_slot_update(const char* what, const UpdateArgs& a, int slots, int S, const avd_noise_key* key,
-                             const avd_latent_guide* guide, const avd_cfg_control* ctl, int canvas_hop, int guide_hop, UpdateKeys& k) {
+                             const avd_latent_guide* guide, const avd_cfg_control* ctl, int canvas_hop, int guide_hop, UpdateKeys& k,
+                             const avd_slot_key* skey, const SlotKeyDims& skd) {
+    AVD_REQUIRE(slots || !skey, AVD_EINVAL, "%s: a slot key rides with slot timesteps (slots > 0)", what);
     if (!slots) return AVD_OK;
     AVD_REQUIRE(slots == S, AVD_EINVAL, "%s: slots %d must equal the geometry's %d slots along the sliding axis", what, slots, S);
-    AVD_REQUIRE(a.eta == 0.f && !a.noise && !key, AVD_EINVAL, "%s: slot timesteps take the update at eta == 0 (no noise, no key)", what);
+    AVD_REQUIRE((a.eta == 0.f || skey) && !a.noise && !key, AVD_EINVAL,
+                "%s: slot timesteps take the update at eta == 0 (no noise, no key), or at eta > 0 with a slot key", what);
     AVD_REQUIRE(!guide && !ctl && !canvas_hop && !guide_hop, AVD_EINVAL,
                 "%s: slot timesteps take no latent guide, CFG control or canvas keying", what);
     AVD_REQUIRE((int64_t)a.B * S <= 0x7fffffff, AVD_EINVAL, "%s: B %d * slots %d does not fit an int", what, a.B, S);
     k.slots = true;
     k.sl = SlotTimes{S};
+    k.skey = skey && a.eta > 0.f;
+    if (k.skey)
+        if (int rc = make_slot_key(skey, a.B, skd.outer, skd.slot_len, skd.inner, k.sk, what)) return rc;
     return AVD_OK;
 }
 
-// Calls launch(pack...) with the kernels' whole trailing pack; the slot form's is SlotTimes, behind the DpmState if there is one.
+// Calls launch(pack...) with the kernels' whole trailing pack; the slot form's is SlotTimes, behind the DpmState if there is one and
+// before the SlotKey of an eta > 0 step.
 // Otherwise: the solver's state (DpmState, the NoiseKey of a seeded eta > 0 step or
 // the CanvasKey of a canvas-keyed one, DpmState then that key for the SDE form, or nothing), then the guide if there is one, then the
 // CFG control if there is one or, for the single-branch form, the CondOnly tag.  A canvas-keyed guide rides in the guide's place, after
@@ -2075,7 +2181,9 @@ static int check_slot_update(const char* what, const UpdateArgs& a, int slots, i
 template <class F>
 static void with_update_pack(const UpdateKeys& k, bool cond_only, F launch) {
     if (k.slots) {
-        if (k.dpm) launch(k.ds, k.sl);
+        if (k.dpm && k.skey) launch(k.ds, k.sl, k.sk);
+        else if (k.dpm) launch(k.ds, k.sl);
+        else if (k.skey) launch(k.sl, k.sk);
         else launch(k.sl);
         return;
     }
@@ -2110,7 +2218,7 @@ static void with_update_pack(const UpdateKeys& k, bool cond_only, F launch) {
 // the video launch for one pack: the whole-line kernel where the geometry allows it, the gather form otherwise
 template <class... P>
 static void launch_unpatch(const UpdateArgs& a, const Tube& g, hipStream_t st, P... p) {
-    constexpr bool SEEDED = PackHas<NoiseKey, P...>::value || PackHas<CanvasKey, P...>::value;
+    constexpr bool SEEDED = PackHas<NoiseKey, P...>::value || PackHas<CanvasKey, P...>::value || PackHas<SlotKey, P...>::value;
     // whole-line form: groups of tokens along w' that make up 128 bytes (or the whole row when W is shorter) of latent per (c, t, h)
     const int gt = (g.W < 32 ? g.W : 32) / g.w;
     int planes = 1;      // an APG launch parks c and d0: twice the LDS (the gather form where that does not fit)
@@ -2135,7 +2243,7 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key,
                          const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
-                         int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg) {
+                         int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg, const avd_slot_key* skey = nullptr) {
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "cfg_unpatch_ddim: bad dims");
     Tube g;
     if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
@@ -2145,8 +2253,9 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
     const CanvasDims cv{C, T, canvas_hop, (int64_t)H * W};
     const CanvasDims gcv{C, T, guide_hop, (int64_t)H * W};
     if (int rc = check_fused_update("cfg_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
-                                    guide_hop ? &gcv : nullptr, apg, (int64_t)2 * B * g.per * 4)) return rc;
-    if (int rc = check_slot_update("cfg_unpatch_ddim", a, slots, T / t, key, guide, ctl, canvas_hop, guide_hop, k)) return rc;
+                                    guide_hop ? &gcv : nullptr, apg, (int64_t)2 * B * g.per * 4, skey)) return rc;
+    if (int rc = check_slot_update("cfg_unpatch_ddim", a, slots, T / t, key, guide, ctl, canvas_hop, guide_hop, k, skey,
+                                   SlotKeyDims{C, t, (int64_t)H * W})) return rc;
     if (apg) {
         AVD_REQUIRE(aligned16(eps2) && aligned16(eps2 + (int64_t)B * g.per) && aligned16(z) && aligned16(z_out), AVD_EUNSUPPORTED,
                     "cfg_unpatch_ddim: the APG statistics pass reads 16-byte aligned token rows");
@@ -2265,7 +2374,9 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
             return v;
     };
     [[maybe_unused]] float zn = 0.f;      // the unkeyed DPM update (eta == 0) draws nothing
-    if constexpr (CANVAS) {      // element (c, f) of window b: canvas position from f, element c of its slice (inner == 1)
+    if constexpr (PackHas<SlotKey, Key...>::value) {      // the clip-keyed draw: clip position from f, element c of its slice, the slot's timestep
+        zn = slot_normal4(pack_get<SlotKey>(nk...), b, c, f, 0, 1, (uint32_t)t_now[tb])[c & 3];
+    } else if constexpr (CANVAS) {      // element (c, f) of window b: canvas position from f, element c of its slice (inner == 1)
         zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, c, f, 0, 1, (uint32_t)t_now[b])[c & 3];
     } else if constexpr (SEEDED) {
         NoiseKey k;      // as in cfg_unpatch_ddim_kernel
@@ -2289,7 +2400,7 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
 
 template <class... P>
 static void launch_untoken(const UpdateArgs& a, const AudioGeom& ag, hipStream_t st, P... p) {
-    constexpr bool SEEDED = PackHas<NoiseKey, P...>::value || PackHas<CanvasKey, P...>::value;
+    constexpr bool SEEDED = PackHas<NoiseKey, P...>::value || PackHas<CanvasKey, P...>::value || PackHas<SlotKey, P...>::value;
     const int64_t n = (int64_t)a.B * ag.Ca * ag.F;
     hipLaunchKernelGGL((cfg_untoken_ddim_audio_kernel<SEEDED, P...>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.eps, a.z,
                        a.t_now, a.t_prev, a.abar, a.T_train, a.guidance, a.eta, a.noise, a.z_out, a.B, ag.Ca, ag.F, ag.len, ag.stride,
@@ -2301,7 +2412,7 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st, const avd_noise_key* key,
                                const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
-                               int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg) {
+                               int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg, const avd_slot_key* skey = nullptr) {
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "cfg_untoken_ddim_audio: bad chunking");
     AVD_REQUIRE(!slots || stride == len, AVD_EUNSUPPORTED,
@@ -2313,8 +2424,9 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
     const CanvasDims gcv{Ca, F, guide_hop, 1};
     const AudioGeom ag{Ca, F, len, stride, audio_na(F, len, stride)};
     if (int rc = check_fused_update("cfg_untoken_ddim_audio", a, per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
-                                    guide_hop ? &gcv : nullptr, apg, (int64_t)2 * B * ag.Na * Ca * len * 4)) return rc;
-    if (int rc = check_slot_update("cfg_untoken_ddim_audio", a, slots, ag.Na, key, guide, ctl, canvas_hop, guide_hop, k)) return rc;
+                                    guide_hop ? &gcv : nullptr, apg, (int64_t)2 * B * ag.Na * Ca * len * 4, skey)) return rc;
+    if (int rc = check_slot_update("cfg_untoken_ddim_audio", a, slots, ag.Na, key, guide, ctl, canvas_hop, guide_hop, k, skey,
+                                   SlotKeyDims{Ca, len, 1})) return rc;
     if (apg) {
         const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
         if (int rc = run_apg_stats<CFG_SRC_AUDIO>(apg, ctl ? ctl->guidance : nullptr, guidance, eps2, eps2 + B * half, half, B, per,
@@ -2733,6 +2845,32 @@ extern "C" int avd_cfg_untoken_dpmpp_2m_audio_slots_f32(const float* eps2, const
     AVD_REQUIRE(t_last && x0_hist, AVD_EINVAL, "cfg_untoken_dpmpp_2m_audio_slots: null t_last or x0_hist");
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, 0.f, nullptr, z_out, B, Ca, F, len, stride,
                                       static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots, nullptr);
+}
+// the slot forms at eta > 0 ("clip-keyed slot noise" in the header): the key is required, and read only when eta > 0; t_last / x0_hist
+// both null = DDIM, both set = the SDE form of the DPM-Solver++(2M) slot update
+extern "C" int avd_cfg_unpatch_ddim_slots_seeded_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                                     const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, float eta,
+                                                     const avd_slot_key* key, int slots, float* x0_hist, float* z_out, int B, int C, int T,
+                                                     int H, int W, int t, int h, int w, avd_stream_t stream) {
+    AVD_REQUIRE(aligned16(eps2) && aligned16(z) && aligned16(z_out), AVD_EUNSUPPORTED,
+                "cfg_unpatch_ddim_slots_seeded: pointers must be 16-byte aligned");
+    AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_unpatch_ddim_slots_seeded: slots must be > 0 (got %d)", slots);
+    AVD_REQUIRE(key, AVD_EINVAL, "cfg_unpatch_ddim_slots_seeded: null slot key");
+    return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, nullptr, z_out, B, C, T, H, W, t, h, w,
+                                static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots, nullptr, key);
+}
+extern "C" int avd_cfg_untoken_ddim_audio_slots_seeded_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                                           const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance,
+                                                           float eta, const avd_slot_key* key, int slots, float* x0_hist, float* z_out,
+                                                           int B, int Ca, int F, int len, int stride, avd_stream_t stream) {
+    AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_untoken_ddim_audio_slots_seeded: slots must be > 0 (got %d)", slots);
+    AVD_REQUIRE(key, AVD_EINVAL, "cfg_untoken_ddim_audio_slots_seeded: null slot key");
+    return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, nullptr, z_out, B, Ca, F, len, stride,
+                                      static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots, nullptr, key);
+}
+extern "C" int avd_slot_noise_f32(const avd_slot_key* key, const int64_t* t_now, float* out, int B, int64_t outer, int L, int slots,
+                                  int slot_len, int64_t inner, avd_stream_t stream) {
+    return slot_noise_f32(key, t_now, out, B, outer, L, slots, slot_len, inner, static_cast<hipStream_t>(stream));
 }
 extern "C" int avd_fifo_shift_hist_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped,
                                        const float* hist_in, float* hist_out, int B, int64_t outer, int slots, int slot_len, int64_t inner,

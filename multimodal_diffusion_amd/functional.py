@@ -601,15 +601,83 @@ def slot_tables(t_now: Tensor, t_prev: Tensor, B: int, S: int, device: torch.dev
     return out
 
 
-def ddim_step_slots(x_t: Tensor, t_now: Tensor, t_prev: Tensor, eps_hat: Tensor, alpha_bar: Tensor, slot_len: int) -> Tensor:
-    """The elementwise mirror of the slot form of the fused update (include/avdiff_hip.h, "slot timesteps") at eta == 0: ``x_t`` and
+def slot_key(seed: int, first: int = 0, stride: int = 1, cursor: Optional[Tensor] = None,
+             device: Optional[torch.device] = None) -> "L.SlotKey":
+    """avd_slot_key (include/avdiff_hip.h, "clip-keyed slot noise") after the checks its users share: 0 <= seed < 2**64, an int
+    ``first`` with |first| < 2**32 (the clip slot of slot 0 of sample 0; negative slots wrap), an int ``stride`` in [1, 2**31) (clip
+    slots from one sample to the next) and ``cursor`` None or one int32 in device memory (on ``device`` when that is given), whose
+    value, read at each launch and clamped at 0, is added to ``first``.  The struct holds the cursor's raw pointer: keep it alive."""
+    noise_key(seed, 0)
+    if isinstance(first, bool) or not isinstance(first, int) or abs(first) >= 2 ** 32:
+        raise ValueError(f"clip_first must be an int with |first| < 2**32 (the clip slot of slot 0 of sample 0), got {first!r}")
+    if isinstance(stride, bool) or not isinstance(stride, int) or not 1 <= stride < 2 ** 31:
+        raise ValueError(f"clip_stride must be an int in [1, 2**31) (clip slots from one sample to the next), got {stride!r}")
+    if cursor is not None:
+        if not isinstance(cursor, Tensor):
+            raise ValueError("a cursor is one int32 in device memory (a 1-element int32 tensor on the buffers' device)")
+        _cursor(cursor, cursor.device if device is None else device)
+    return L.SlotKey(seed, first, stride, L.ptr(cursor))
+
+
+def slot_noise(seed: int, t_now: Tensor, shape, slot_len: int, first: int = 0, stride: Optional[int] = None,
+               cursor: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """The clip-keyed normals of the slot entries' eta > 0 noise (avd_slot_noise_f32; contract in include/avdiff_hip.h, "clip-keyed
+    slot noise"): a float32 tensor of ``shape`` ([B,C,T,H,W] video, [B,Ca,F] audio).  ``t_now``: int [B, S]; sliding position l is in
+    slot min(l // slot_len, S - 1) and sits on clip position ((first + max(*cursor, 0) + b*stride) * slot_len + l) mod 2**32, whose
+    normal at the slot's timestep it holds: the values ``DenoiseEngine.step_slots(clip_first=...)`` draws inside its step, so the
+    result can be passed as ``noise`` to ``ddim_step_slots`` / ``dpmpp_2m_sde_step_slots`` or, with a uniform table, to an unseeded
+    engine's ``step``.  ``stride`` None = S; ``cursor``: see ``slot_key``; ``out``: a contiguous float32 device tensor of ``shape``
+    to fill instead of a new one."""
+    shape = tuple(int(s) for s in shape)
+    outer, L_, inner = window_dims(shape)
+    if any(s < 1 for s in shape):
+        raise ValueError(f"shape must have positive sizes, got {shape}")
+    t_now = torch.as_tensor(t_now)
+    if t_now.dim() != 2 or t_now.shape[0] != shape[0] or t_now.is_floating_point() or t_now.dtype == torch.bool:
+        raise ValueError(f"t_now must be an int [B, S] table with B = {shape[0]}, got {t_now.dtype} {tuple(t_now.shape)}")
+    S = int(t_now.shape[1])
+    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or S < 1 or S * slot_len > L_:
+        raise ValueError(f"S = {S} slots of slot_len {slot_len!r} must fit the sliding length {L_}")
+    if outer * inner >= 2 ** 34:
+        raise ValueError(f"one clip position holds outer * inner = {outer * inner} elements, the stream keys < 2**34")
+    if out is not None and not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+        raise ValueError(f"out must be a contiguous float32 device tensor of shape {shape}")
+    dev = out.device if out is not None else (t_now.device if t_now.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    key = slot_key(seed, first, S if stride is None else stride, cursor, dev)
+    tn = L.dev_i64(t_now, dev)
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=torch.float32)
+    L.check(L.lib().avd_slot_noise_f32(C.byref(key), tn.data_ptr(), out.data_ptr(), shape[0], outer, L_, S, slot_len, inner, _st(out)))
+    return out
+
+
+def _slot_step_noise(eta: float, noise: Optional[Tensor], x_t: Tensor, what: str) -> Optional[Tensor]:
+    """the explicit noise of the slot mirrors: required when eta > 0 (``slot_noise`` gives the fused step's normals), not read at 0"""
+    if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not eta >= 0:
+        raise ValueError(f"eta must be a number >= 0, got {eta!r}")
+    if eta == 0:
+        return None
+    if noise is None:
+        raise ValueError(f"{what}: eta > 0 needs `noise` (slot_noise gives the clip-keyed normals the fused step draws)")
+    nz = L.dev_f32(noise, "noise")
+    if nz.shape != x_t.shape:
+        raise RuntimeError("noise must have the shape of x_t")
+    return nz
+
+
+def ddim_step_slots(x_t: Tensor, t_now: Tensor, t_prev: Tensor, eps_hat: Tensor, alpha_bar: Tensor, slot_len: int, eta: float = 0.0,
+                    noise: Optional[Tensor] = None) -> Tensor:
+    """The elementwise mirror of the slot form of the fused update (include/avdiff_hip.h, "slot timesteps"): ``x_t`` and
     ``eps_hat`` are latents ([B,C,T,H,W] video, [B,Ca,F] audio), ``t_now`` / ``t_prev`` int [B, S]; sliding position l is in slot
     min(l // slot_len, S - 1).  Every slot takes ``ddim_step`` (avd_ddim_step_f32) with its pair, one launch per distinct pair of the
-    tables; a slot with t_prev == t_now keeps ``x_t`` bit for bit (the hold)."""
+    tables; a slot with t_prev == t_now keeps ``x_t`` bit for bit (the hold).
+    ``eta`` > 0 ("clip-keyed slot noise") needs ``noise``, a float32 tensor of x_t's shape — ``slot_noise`` gives the normals the
+    fused step draws — and every stepping slot takes its pair's sigma(eta) times it; at the default 0 ``noise`` is not read."""
     x_t = L.dev_f32(x_t, "x_t")
     eps_hat = L.dev_f32(eps_hat, "eps_hat")
     if eps_hat.shape != x_t.shape:
         raise RuntimeError("eps_hat must have the shape of x_t")
+    nz = _slot_step_noise(eta, noise, x_t, "ddim_step_slots")
     _, L_, _ = window_dims(x_t.shape)
     B = x_t.shape[0]
     S = _check_slot_len(slot_len, L_)
@@ -621,7 +689,7 @@ def ddim_step_slots(x_t: Tensor, t_now: Tensor, t_prev: Tensor, eps_hat: Tensor,
     for a, p in sorted({(int(a), int(p)) for a, p in zip(tn.reshape(-1).tolist(), tp.reshape(-1).tolist())}):
         if a == p:
             continue
-        full = ddim_step(x_t, torch.full((B,), a), torch.full((B,), p), eps_hat, alpha_bar)
+        full = ddim_step(x_t, torch.full((B,), a), torch.full((B,), p), eps_hat, alpha_bar, float(eta) if nz is not None else 0.0, nz)
         out = torch.where((tn_l == a) & (tp_l == p), full, out)
     return out
 
@@ -658,6 +726,39 @@ def dpmpp_2m_step_slots(x_t: Tensor, eps_hat: Tensor, x0_hist: Tensor, t_last: T
             continue
         h = x0_hist.clone()
         full = dpmpp_2m_step(x_t, eps_hat, h, torch.full((B,), u), torch.full((B,), a), torch.full((B,), p), alpha_bar)
+        on = (tl_l == u) & (tn_l == a) & (tp_l == p)
+        out, hist = torch.where(on, full, out), torch.where(on, h, hist)
+    x0_hist.copy_(hist)
+    return out
+
+
+def dpmpp_2m_sde_step_slots(x_t: Tensor, eps_hat: Tensor, x0_hist: Tensor, t_last: Tensor, t_now: Tensor, t_prev: Tensor,
+                            alpha_bar: Tensor, slot_len: int, eta: float, noise: Optional[Tensor] = None) -> Tensor:
+    """``dpmpp_2m_step_slots`` for the solver's SDE form (include/avdiff_hip.h, "clip-keyed slot noise"): every slot takes
+    ``dpmpp_2m_sde_step`` (avd_dpmpp_2m_sde_step_f32) with its triple, ``eta`` and the explicit ``noise`` (float32, x_t's shape;
+    ``slot_noise`` gives the normals the fused step draws; required when eta > 0).  A held slot keeps ``x_t`` and its history bit for
+    bit; at eta == 0 ``noise`` is not read and the result has ``dpmpp_2m_step_slots``'s bits."""
+    x_t = L.dev_f32(x_t, "x_t")
+    eps_hat = L.dev_f32(eps_hat, "eps_hat")
+    if eps_hat.shape != x_t.shape:
+        raise RuntimeError("eps_hat must have the shape of x_t")
+    if not (x0_hist.is_cuda and x0_hist.dtype == torch.float32 and x0_hist.is_contiguous() and x0_hist.shape == x_t.shape):
+        raise RuntimeError("x0_hist must be a contiguous float32 device tensor of x_t's shape (it is updated in place)")
+    nz = _slot_step_noise(eta, noise, x_t, "dpmpp_2m_sde_step_slots")
+    _, L_, _ = window_dims(x_t.shape)
+    B = x_t.shape[0]
+    S = _check_slot_len(slot_len, L_)
+    tn, tp, tl = slot_tables(t_now, t_prev, B, S, x_t.device, t_last)
+    slot = torch.clamp(torch.arange(L_, device=x_t.device) // slot_len, max=S - 1)
+    view = (B, 1, L_) + (1,) * (x_t.dim() - 3)
+    tl_l, tn_l, tp_l = (t[:, slot].view(view) for t in (tl, tn, tp))      # the triple of every sliding position
+    out, hist = x_t.clone(), x0_hist.clone()
+    for u, a, p in sorted(set(zip(tl.reshape(-1).tolist(), tn.reshape(-1).tolist(), tp.reshape(-1).tolist()))):
+        if a == p:
+            continue
+        h = x0_hist.clone()
+        full = dpmpp_2m_sde_step(x_t, eps_hat, h, torch.full((B,), u), torch.full((B,), a), torch.full((B,), p), alpha_bar,
+                                 float(eta) if nz is not None else 0.0, nz)
         on = (tl_l == u) & (tn_l == a) & (tp_l == p)
         out, hist = torch.where(on, full, out), torch.where(on, h, hist)
     x0_hist.copy_(hist)

@@ -108,7 +108,8 @@ class FifoQueue:
     """The state of one open FIFO queue (``DenoiseEngine.fifo_open``): the device cursors ``r`` (ramp iteration) and ``m`` (steady
     iteration), the uploaded tables (``ramp``: [n - 1, B*S] each; ``steady`` and the selected ``slot`` tables: [B, S] each; two, or
     three with t_last), the prompt canvas ``canvas_p`` and the prompt-latent buffer ``prompt``, the latent buffers ``z`` / ``other``,
-    the clip canvas ``clip``, and what the launches take by value: ``seed``, ``s0``, ``n`` (= c0), ``n_slots``, ``hop``."""
+    the clip canvas ``clip``, and what the launches take by value: ``seed``, ``s0``, ``n`` (= c0), ``n_slots``, ``hop`` and
+    ``clip_first`` (0 on an eta > 0 engine with a noise_seed, whose steps key their noise by clip slot off ``m``; else None)."""
 
 
 class _CapturedPair:
@@ -225,8 +226,12 @@ class DenoiseEngine:
     ``step_slots(z, t_now, t_prev)`` (extension: slot timesteps, include/avdiff_hip.h): one (t_now, t_prev) pair per token position
     of the sliding axis ([B, S] tables, S = ``slots`` of ``slot_len`` latent positions) instead of one per sample; a slot with t_prev ==
     t_now is held.  The primitive of FIFO diagonal denoising (``stream_infer.fifo_denoise``, ``schedule_utils.fifo_plan``).  Either
-    solver at eta == 0 with the scalar guidance only: solver "dpmpp_2m" takes a third table ``t_last`` and keeps its history per
-    element in ``x0_hist``, which ``fifo_shift`` moves along with the queue.  ``step``, ``run`` and ``capture_pair`` do not change.
+    solver with the scalar guidance only: solver "dpmpp_2m" takes a third table ``t_last`` and keeps its history per
+    element in ``x0_hist``, which ``fifo_shift`` moves along with the queue.  At eta > 0 it needs ``noise_seed`` and ``clip_first``,
+    the clip slot the batch starts at: every stepping slot draws its noise keyed by (noise_seed, the clip position it holds, its
+    t_now, element) under a domain tag of its own (include/avdiff_hip.h, "clip-keyed slot noise"), so a clip slot's draws do not
+    depend on the queue layout, on which sample holds it or on eager / replayed launches.  ``step``, ``run`` and ``capture_pair`` do
+    not change.
 
     ``fifo_open`` / ``fifo_ramp`` / ``fifo_steady`` / ``fifo_capture`` (extension: a FIFO queue whose iterations read the ramp row and
     the clip slot off device cursors, include/avdiff_hip.h, "FIFO device cursors"): what ``fifo_denoise(graph=True)`` replays.  An
@@ -838,7 +843,8 @@ class DenoiseEngine:
         return self.latent_shape[2] // self.tube[0] if self.target == "video" else self.embed.Nt
 
     def step_slots(self, z: torch.Tensor, t_now: torch.Tensor, t_prev: torch.Tensor, out: Optional[torch.Tensor] = None,
-                   t_last: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   t_last: Optional[torch.Tensor] = None, clip_first: Optional[int] = None, clip_stride: Optional[int] = None,
+                   clip_cursor: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One CFG step on slot timesteps (extension; include/avdiff_hip.h, "slot timesteps"; avd_denoise_step_slots_f32):
         ``t_now`` / ``t_prev`` are int [B, S] tables, S = ``slots``, one pair per slot of ``slot_len`` latent positions along the
         sliding axis.  Every slot's tokens embed its t_now and its latent takes the DDIM update of its pair; a slot with t_prev ==
@@ -848,15 +854,25 @@ class DenoiseEngine:
         Solver "dpmpp_2m" (avd_denoise_step_slots_dpmpp_2m_f32) needs ``t_last``, a third int [B, S] table: the timestep each slot's
         previous step started from, < 0 for a first-order step.  A slot's history is the elements of ``x0_hist`` under it: read by its
         second-order steps, overwritten with its x0, and neither read nor written while the slot is held.
-        Scope: eta == 0 with the scalar guidance; a latent guide, a CFG control, a window consensus, temb_mode "add" and overlapping
-        audio chunks are refused before anything is launched, as is ``t_last`` on a "ddim" engine."""
+        On an eta > 0 engine ``clip_first`` selects the stochastic step (avd_denoise_step_slots_seeded_f32; include/avdiff_hip.h,
+        "clip-keyed slot noise"): an int, the clip slot that slot 0 of sample 0 holds (negative slots wrap).  Every stepping slot then
+        draws its noise term — DDIM's sigma(eta), or the SDE form of "dpmpp_2m" — by the clip position it holds, keyed by the engine's
+        ``noise_seed`` (required): sample k holds clip slots clip_first + k * ``clip_stride`` .. (``clip_stride`` None = S), and
+        ``clip_cursor`` (one int32 in device memory, or None) is read at every launch and added, clamped at 0, to ``clip_first``, so a
+        captured step follows a moving queue.  A held slot draws nothing.  Without ``clip_first`` an eta > 0 engine is refused, and
+        on an eta == 0 engine the three arguments change nothing: the same launches, the same bits.
+        Scope: the scalar guidance; a latent guide, a CFG control, a window consensus, temb_mode "add" and overlapping audio chunks
+        are refused before anything is launched, as is ``t_last`` on a "ddim" engine; no unseeded or explicit noise."""
         if self.Xp is None:
             raise RuntimeError("call set_prompt() first")
-        self._slot_refusals(t_last is not None)
+        self._slot_refusals(t_last is not None, clip_first)
+        S = self.slots
+        key = None
+        if self.eta > 0:      # _slot_refusals has asked for clip_first and noise_seed
+            key = Fn.slot_key(self.noise_seed, clip_first, S if clip_stride is None else clip_stride, clip_cursor, self.device)
         z = L.dev_f32(z, "z")
         if tuple(z.shape) != self.latent_shape:
             raise ValueError(f"latent shape {tuple(z.shape)} != engine shape {self.latent_shape}")
-        S = self.slots
         tn, tp, *tl = Fn.slot_tables(t_now, t_prev, self.embed.B, S, self.device, t_last)
         if out is None:
             out = torch.empty_like(z)
@@ -871,19 +887,27 @@ class DenoiseEngine:
         self._last_cond_only = False
         head = (C.byref(self.desc), z.data_ptr(), self.Xp.data_ptr())
         tail = (out.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device))
-        if tl:
+        if key is not None:
+            L.check(L.lib().avd_denoise_step_slots_seeded_f32(head[0], C.byref(key), tl[0].data_ptr() if tl else None,
+                                                              self.x0_hist.data_ptr() if tl else None, *head[1:], tn.data_ptr(),
+                                                              tp.data_ptr(), S, *tail))
+        elif tl:
             L.check(L.lib().avd_denoise_step_slots_dpmpp_2m_f32(*head, tl[0].data_ptr(), tn.data_ptr(), tp.data_ptr(), S,
                                                                 self.x0_hist.data_ptr(), *tail))
         else:
             L.check(L.lib().avd_denoise_step_slots_f32(*head, tn.data_ptr(), tp.data_ptr(), S, *tail))
         return out
 
-    def _slot_refusals(self, has_t_last: bool) -> None:
+    def _slot_refusals(self, has_t_last: bool, clip_first: Optional[int] = None) -> None:
         """what ``step_slots`` refuses of the engine's state, before anything is launched (``fifo_open`` asks the same before it
-        allocates, so a graph-replayed queue refuses what the eager one does, in the same words, before any capture)"""
-        if self.eta > 0:
-            raise ValueError("step_slots needs eta == 0: slots at different timesteps have no common noise stream yet (eta > 0 is out "
-                             "of scope)")
+        allocates, so a graph-replayed queue refuses what the eager one does, in the same words, before any capture).
+        ``clip_first``: as ``step_slots`` takes it; an eta > 0 engine steps only with it and a ``noise_seed``"""
+        if self.eta > 0 and clip_first is None:
+            raise ValueError("step_slots needs eta == 0, or clip_first on an engine with noise_seed: slots at different timesteps draw "
+                             "their eta > 0 noise by the clip position they hold (unkeyed noise is out of scope)")
+        if self.eta > 0 and self.noise_seed is None:
+            raise ValueError("step_slots(clip_first=...) at eta > 0 draws its noise from the engine's noise_seed: build the engine with "
+                             "one (unseeded and explicit noise are not supported there)")
         if self.solver == "ddim" and has_t_last:
             raise ValueError("t_last is the multistep solver's history: this engine runs solver 'ddim'")
         if self.solver != "ddim" and not has_t_last:
@@ -956,6 +980,8 @@ class DenoiseEngine:
         of ``n_slots`` slots (fresh per call: it is what the driver returns) and, on "dpmpp_2m", the second history buffer; embeds the
         prompt of m = 0, which also writes Xp's constant timestep columns.  ``prompt_len``: the prompt latent's length along its
         sliding axis (``stream_infer.fifo_prompt_len``).  Refuses what ``step_slots`` refuses, before it allocates.
+        On an eta > 0 engine with a ``noise_seed`` the queue is stochastic: its steps pass ``clip_first=0, clip_cursor=q.m`` (m is 0
+        through the ramp), the step noise keyed by ``engine.noise_seed``; ``noise_seed`` here seeds the start and the entering noise.
         The queue holds ``noise_seed``, c0 = n, ``n_slots``, the hops and every address: a captured pair is good for this queue only."""
         B, S, sl = self.embed.B, self.slots, self.slot_len
         ramp_now, ramp_prev, steady_now, steady_prev = su.fifo_plan(sched, S)
@@ -969,9 +995,11 @@ class DenoiseEngine:
         for name, v in (("n_slots", n_slots), ("prompt_hop", prompt_hop), ("prompt_len", prompt_len)):
             if isinstance(v, bool) or not isinstance(v, int) or v < 1:
                 raise ValueError(f"{name} must be an int >= 1, got {v!r}")
-        self._slot_refusals(self.solver == "dpmpp_2m")
+        stochastic = self.eta > 0 and self.noise_seed is not None
+        self._slot_refusals(self.solver == "dpmpp_2m", 0 if stochastic else None)
         dev = self.device
         q = FifoQueue()
+        q.clip_first = 0 if stochastic else None      # eta > 0: the steps key their noise by clip slot, read off the cursor m
         q.n, q.n_slots, q.seed, q.hop, q.s0 = n, n_slots, noise_seed, prompt_hop, int(torch.as_tensor(sched).reshape(-1)[0])
         if (n + n_slots) * sl > 2 ** 32:
             raise ValueError(f"(n {n} + n_slots {n_slots}) * slot_len {sl} exceeds the stream's 2**32 canvas positions")
@@ -998,21 +1026,25 @@ class DenoiseEngine:
         return q
 
     def fifo_ramp(self, q: "FifoQueue", src: torch.Tensor, dst: torch.Tensor) -> None:
-        """One ramp iteration of an open queue: select row *r of the ramp tables -> ``step_slots`` src -> dst -> r += 1."""
+        """One ramp iteration of an open queue: select row *r of the ramp tables -> ``step_slots`` src -> dst (on a stochastic queue
+        keyed by the clip slots the queue holds at m = 0) -> r += 1."""
         Fn.slot_tables_select(q.ramp, q.r, q.slot)
-        self.step_slots(src, q.slot[0], q.slot[1], out=dst, t_last=q.slot[2] if len(q.slot) == 3 else None)
+        self.step_slots(src, q.slot[0], q.slot[1], out=dst, t_last=q.slot[2] if len(q.slot) == 3 else None, clip_first=q.clip_first,
+                        clip_cursor=q.m)
         Fn.cursor_add(q.r)
 
     def fifo_steady(self, q: "FifoQueue", z: torch.Tensor, tmp: torch.Tensor) -> None:
         """One steady iteration of an open queue, with m = *m: gather the prompt of iteration m -> embed it into Xp (same address) ->
         ``step_slots`` z -> tmp on the constant steady tables -> shift tmp -> z, the finished head into slot m of the clip canvas and
-        clip slot n + m entering at the tail -> m += 1.  The latent is back in ``z``.  On "dpmpp_2m" the shift carries the history
+        clip slot n + m entering at the tail -> m += 1.  The latent is back in ``z``.  On a stochastic queue the step draws its noise
+        for clip slots m .., read off the same cursor.  On "dpmpp_2m" the shift carries the history
         into the engine's other history buffer and the two swap, as in ``fifo_shift``: two iterations put ``x0_hist`` back."""
         B, S = self.embed.B, self.slots
         Fn.fifo_prompt_gather(q.canvas_p, q.m, B, S, q.hop, q.prompt.shape[2], out=q.prompt)
         self._prompt_rows(self._prompt_tokens(q.prompt), self.Xp, temb=False)
         multistep = len(q.steady) == 3
-        self.step_slots(z, q.steady[0], q.steady[1], out=tmp, t_last=q.steady[2] if multistep else None)
+        self.step_slots(z, q.steady[0], q.steady[1], out=tmp, t_last=q.steady[2] if multistep else None, clip_first=q.clip_first,
+                        clip_cursor=q.m)
         if not multistep:
             Fn.fifo_shift_cursor(tmp, q.n, q.m, q.clip, q.seed, q.s0, self.slot_len, out=z)
         else:

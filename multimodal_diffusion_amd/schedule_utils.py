@@ -317,6 +317,18 @@ def fifo_lookahead_plan_last(sched, S: int, ctx: int, context: str = "noise"):
     return _lookahead_windows(ramp, q, ctx, 2), _lookahead_windows(steady, q, ctx, 2)
 
 
+def fifo_slot_keying(S: int, ctx: int = 0) -> Tuple[int, int]:
+    """(first_offset, stride) = (-ctx, S - ctx): how a FIFO queue keys the step noise of an eta > 0 engine by clip position
+    (include/avdiff_hip.h, "clip-keyed slot noise").  Before the step of steady iteration m (the ramp: m = 0) position s of sample k
+    holds clip slot m + first_offset + k*stride + s, so the drivers pass ``step_slots(clip_first=m + first_offset,
+    clip_stride=stride)``: a queue of samples (``ctx`` = 0) is S slots apart, lookahead windows h = S - ctx, their first ctx positions
+    being the slots before the window's own.  Clip slot c then draws at the keys (c, s_i), i = 0 .. n-1, once each, in either queue."""
+    S = _whole(S, "S")
+    if isinstance(ctx, bool) or not isinstance(ctx, int) or not 0 <= ctx < S:
+        raise ValueError(f"fifo_slot_keying: the lookahead ctx must be an int in [0, S = {S}), got {ctx!r}")
+    return -ctx, S - ctx
+
+
 def resample_from_config(scfg) -> Optional[Tuple[int, int]]:
     """``sampling.resample`` of a config: {jump:, resamples:}; a missing key or None means no resampling."""
     return check_resample(scfg.get("resample"))

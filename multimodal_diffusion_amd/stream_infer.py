@@ -235,7 +235,13 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     ``prompt_canvas`` is the prompt modality's latent along its sliding axis and ``prompt_hop`` its positions per target slot: before
     the step of steady iteration m (the ramp: m = 0) sample k is conditioned on ``fifo_prompt_windows(prompt_canvas, m, ...)[k]``,
     the prompt under the clip slots the sample holds (``set_prompt`` into the same buffer).  The engine's limits are ``step_slots``'s
-    (eta == 0, no guide / control / consensus).
+    (no guide / control / consensus).
+    An engine with eta > 0 and a ``noise_seed`` samples stochastically, in every driver below: each ``step_slots`` is keyed by the clip
+    slots the batch holds (``schedule_utils.fifo_slot_keying``; include/avdiff_hip.h, "clip-keyed slot noise"), so clip slot c draws
+    the same step normals at each of its n steps in the eager loop, the replayed one and the lookahead queue, whatever the clip
+    length.  The step noise is seeded by ``engine.noise_seed``; the ``noise_seed`` argument keeps seeding the start and the entering
+    noise, and the two may be equal: the step noise has a domain tag of its own.  An eta > 0 engine without a ``noise_seed`` is
+    refused, as ``step_slots`` refuses it.
     ``graph`` (False, True or None; default False = the eager loop: per finished slot the host runs one ``set_prompt``, one
     ``step_slots`` and one ``fifo_shift``): True replays the iterations from captured HIP graphs and returns the same bits.  The ramp
     row, the prompt positions and the clip slot are then read off two int32 device cursors (``DenoiseEngine.fifo_open``;
@@ -302,16 +308,28 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     z = Fn.canvas_noise(noise_seed, torch.full((B,), s0, dtype=torch.long, device=dev), engine.latent_shape, L_)
     other = torch.empty_like(z)
     engine.set_prompt(fifo_prompt_windows(pc, 0, B, S, prompt_hop, Lp))
+    first, stride = _fifo_clip_keying(engine, S, 0)
     for r in range(n - 1):
-        z, other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other, t_last=ramp_last[r] if multistep else None), z
+        z, other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other, t_last=ramp_last[r] if multistep else None, clip_first=first(0),
+                                     clip_stride=stride), z
     canvas = torch.empty((outer, n_slots * sl) + tuple(engine.latent_shape[3:]), device=dev, dtype=torch.float32)
     for m in range(n_slots):
         if m:
             engine.set_prompt(fifo_prompt_windows(pc, m, B, S, prompt_hop, Lp))
-        other = engine.step_slots(z, tabs[2], tabs[3], out=other, t_last=steady_last)
+        other = engine.step_slots(z, tabs[2], tabs[3], out=other, t_last=steady_last, clip_first=first(m), clip_stride=stride)
         z, popped = engine.fifo_shift(other, n + m, s0, seed=noise_seed)
         canvas[:, m * sl:(m + 1) * sl] = popped
     return canvas
+
+
+def _fifo_clip_keying(engine: DenoiseEngine, S: int, ctx: int):
+    """(first, stride) of the eager drivers' ``step_slots`` calls: on an eta > 0 engine with a noise_seed ``first(m)`` is the clip slot
+    at slot 0 of sample 0 before the step of steady iteration m (``schedule_utils.fifo_slot_keying``); otherwise it is None, which an
+    eta == 0 engine ignores and with which an unseeded eta > 0 engine is refused by ``step_slots``"""
+    off, stride = su.fifo_slot_keying(S, ctx)
+    if engine.eta > 0 and engine.noise_seed is not None:
+        return (lambda m: m + off), stride
+    return (lambda m: None), None
 
 
 def _fifo_denoise_lookahead(engine: DenoiseEngine, prompt_canvas, prompt_hop: int, sched, n_slots: int, noise_seed: int, ctx: int,
@@ -335,7 +353,8 @@ def _fifo_denoise_lookahead(engine: DenoiseEngine, prompt_canvas, prompt_hop: in
         raise ValueError(f"context must be the clean latent of the {ctx} slots before the clip, shape {(outer, ctx * sl) + hw}, got "
                          f"{tuple(context.shape) if isinstance(context, torch.Tensor) else context!r}")
     multistep = engine.solver == "dpmpp_2m"
-    engine._slot_refusals(multistep)
+    first, stride = _fifo_clip_keying(engine, S, ctx)
+    engine._slot_refusals(multistep, first(0))
     s0 = int(torch.as_tensor(sched).reshape(-1)[0])
     dev = engine.device
     Lp = fifo_prompt_len(engine, prompt_canvas)
@@ -354,14 +373,16 @@ def _fifo_denoise_lookahead(engine: DenoiseEngine, prompt_canvas, prompt_hop: in
     windows = lambda m: fifo_prompt_windows(pc, m, B, S, prompt_hop, Lp, stride=h, first=m - ctx)
     engine.set_prompt(windows(0))
     for r in range(n - 1):
-        other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other, t_last=ramp_last[r] if multistep else None)
+        other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other, t_last=ramp_last[r] if multistep else None, clip_first=first(0),
+                                  clip_stride=stride)
         z, _ = engine.fifo_lookahead(other, ctx, 0)
     canvas = torch.empty((outer, n_slots * sl) + hw, device=dev, dtype=torch.float32)
     for m in range(n_slots):
         if m:
             engine.set_prompt(windows(m))
         row = min(m, ctx)
-        other = engine.step_slots(z, tabs[2][row], tabs[3][row], out=other, t_last=steady_last[row] if multistep else None)
+        other = engine.step_slots(z, tabs[2][row], tabs[3][row], out=other, t_last=steady_last[row] if multistep else None,
+                                  clip_first=first(m), clip_stride=stride)
         z, popped = engine.fifo_lookahead(other, ctx, 1, c=n + m, t=s0, seed=noise_seed)
         canvas[:, m * sl:(m + 1) * sl] = popped
     return canvas

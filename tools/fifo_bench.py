@@ -20,9 +20,15 @@
               (every owner read once, B * S slots written); --e2e: fifo_denoise(lookahead=CTX) on B = n / (S - CTX) windows beside the
               plain queue (B = n / S) at the same schedule, time per finished slot and ramp time, on --solver
 
+  --stochastic  eta > 0 on a seeded engine, the step noise keyed by clip position ("clip-keyed slot noise"), both solvers in one session
+              (DDIM eta 0.5 at n = 48, dpmpp_2m eta 1.0 at n = 18).  --kernels: the fused update of the seeded slot step inside whole
+              2-layer steps, between two runs of the eta = 0 slot step, beside the canvas-keyed and the eta = 0 per-sample steps;
+              --e2e: fifo_denoise per finished slot, eager and replayed, the eta = 0 and the eta > 0 engine's calls interleaved
+
 Prints plain text: the records are profiles/fifo_kernels.txt and profiles/fifo_e2e.txt (ddim), profiles/fifo_dpm_kernels.txt and
 profiles/fifo_dpm_e2e.txt (both solvers in one session), profiles/fifo_graph_e2e.txt (--e2e with and without --graph),
-profiles/fifo_lookahead_kernels.txt and profiles/fifo_lookahead_e2e.txt (--lookahead 3)."""
+profiles/fifo_lookahead_kernels.txt and profiles/fifo_lookahead_e2e.txt (--lookahead 3), profiles/fifo_stochastic_kernels.txt and
+profiles/fifo_stochastic_e2e.txt (--stochastic)."""
 import argparse
 import ctypes as C
 import statistics
@@ -52,6 +58,7 @@ ap.add_argument("--solver", choices=("ddim", "dpmpp_2m"), default="ddim")
 ap.add_argument("--graph", action="store_true", help="--e2e: replay the iterations from captured HIP graphs")
 ap.add_argument("--steps", type=int, default=None, help="--e2e: steps of the schedule = slots of the queue (default 48, dpmpp_2m: 18)")
 ap.add_argument("--lookahead", type=int, default=0, metavar="CTX", help="FIFO lookahead: CTX context slots per window of S = 6")
+ap.add_argument("--stochastic", action="store_true", help="eta > 0 with clip-keyed slot noise beside eta = 0, both solvers")
 args = ap.parse_args()
 if not 0 <= args.lookahead < 6:
     raise SystemExit("--lookahead CTX must lie in [0, 6)")
@@ -61,7 +68,7 @@ dev = torch.device("cuda:0")
 ABAR = R.alpha_bar_table(R.beta_table(1000))
 
 
-def build(n_layers, B, target="video", solver="ddim"):
+def build(n_layers, B, target="video", solver="ddim", **kw):
     ws = R.synth_weights(seed=0, n_layers=n_layers)
     core = A.MMDiT(d_model=512, n_layers=n_layers, n_heads=8, mlp_ratio=4.0).eval()
     core.load_state_dict(ws["core"], strict=True)
@@ -72,7 +79,7 @@ def build(n_layers, B, target="video", solver="ddim"):
     aa.load_state_dict(ws["adapt_a"])
     core, head, av, aa = (m.to(dev) for m in (core, head, av, aa))
     return A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=256, target=target,
-                           latent_shape=(B, 8, 12, 32, 32), prompt_tokens=37, alpha_bar=ABAR, guidance=3.5, matmul="bf16x3", solver=solver)
+                           latent_shape=(B, 8, 12, 32, 32), prompt_tokens=37, alpha_bar=ABAR, guidance=3.5, matmul="bf16x3", solver=solver, **kw)
 
 
 def per_launch_us(tag, fn, launches):
@@ -95,6 +102,90 @@ def report_shift(res, cases):
         us = statistics.median(res[name])
         print(f"  {name}: {nbytes / 1e6:.2f} MB read + written, {nbytes / us / 1e3:.1f} GB/s ({nbytes / us:.0f} bytes per microsecond)")
 
+
+STOCHASTIC = (("ddim", 0.5, 48), ("dpmpp_2m", 1.0, 18))      # solver, eta, steps: the two queues of profiles/fifo_dpm_e2e.txt
+
+if args.stochastic and args.kernels:
+    B, S = 32, 6
+    g = torch.Generator().manual_seed(0)
+    z = torch.randn(B, 8, 12, 32, 32, generator=g).to(dev)
+    prompt = torch.randn(B, 8, 150, generator=g).to(dev)
+    out = torch.empty_like(z)
+    TAG = "cfg_unpatch_ddim_kernel"
+    rows = []
+    for solver, eta, n in STOCHASTIC:
+        dpm = solver == "dpmpp_2m"
+        sched = su.make_sampling_schedule(1000, n)
+        det = build(2, B, solver=solver)
+        sto = build(2, B, solver=solver, eta=eta, noise_seed=11)
+        can = build(2, B, solver=solver, eta=eta, noise_seed=11, noise_keying="canvas", canvas_hop=12)
+        for e in (det, sto, can):
+            e.set_prompt(prompt)
+            if dpm:
+                e.x0_hist.copy_(torch.randn(B, 8, 12, 32, 32, generator=g))
+        # the diagonal: every slot at its own level (second-order triples for dpmpp_2m), none held, none final
+        i = (torch.arange(B * S) % (n - 2)).view(B, S) + 1
+        tlS, tnS, tpS = (sched[i + d].to(dev).contiguous() for d in (-1, 0, 1))
+        tl1, tn1, tp1 = (torch.full((B,), int(sched[5 + d]), dtype=torch.long, device=dev) for d in (-1, 0, 1))
+        last = dict(t_last=tlS) if dpm else {}
+        last1 = dict(t_last=tl1) if dpm else {}
+        rows += [(f"{solver} slots, eta = 0 (a)", lambda det=det, last=last, tnS=tnS, tpS=tpS: det.step_slots(z, tnS, tpS, out=out, **last)),
+                 (f"{solver} slots, eta = {eta}, clip-keyed", lambda sto=sto, last=last, tnS=tnS, tpS=tpS:
+                  sto.step_slots(z, tnS, tpS, out=out, clip_first=0, **last)),
+                 (f"{solver} slots, eta = 0 (b)", lambda det=det, last=last, tnS=tnS, tpS=tpS: det.step_slots(z, tnS, tpS, out=out, **last)),
+                 (f"{solver} per-sample, eta = {eta}, canvas-keyed", lambda can=can, last1=last1, tn1=tn1, tp1=tp1:
+                  can.step(z, tn1, tp1, out=out, **last1)),
+                 (f"{solver} per-sample, eta = 0", lambda det=det, last1=last1, tn1=tn1, tp1=tp1: det.step(z, tn1, tp1, out=out, **last1))]
+    for _, fn in rows:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    res = {name: [] for name, _ in rows}
+    for _ in range(args.rounds):
+        for name, fn in rows:
+            res[name].append(per_launch_us(TAG, fn, args.launches))
+    print(f"C3 geometry, B = {B}, the fused CFG + un-patch + solver update inside whole steps (2 layers), tag {TAG}: {args.rounds} interleaved "
+          f"rounds of {args.launches} launches, microseconds per launch (launch events)")
+    for name, _ in rows:
+        v = res[name]
+        print(f"  {name:46s} " + " ".join(f"{x:8.2f}" for x in v) + f"   median {statistics.median(v):8.2f}")
+    sys.exit(0)
+
+if args.stochastic and args.e2e:
+    S, K = 6, args.slots_out
+    g = torch.Generator().manual_seed(1)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    print(f"fifo_denoise at eta = 0 and at eta > 0 (clip-keyed slot noise), S = {S} (C3 latent, 8 layers, bf16x3), {args.rounds} rounds, the two "
+          f"engines' calls interleaved, {K} and {2 * K} slots out; milliseconds")
+    for solver, eta, n in STOCHASTIC:
+        sched = su.make_sampling_schedule(1000, n)
+        canvas_p = torch.randn(8, 25 * (n + 2 * K) + 148, generator=g).to(dev)
+        engines = [("eta = 0", build(8, n // S, solver=solver)), (f"eta = {eta}", build(8, n // S, solver=solver, eta=eta, noise_seed=11))]
+        for graph in (False, True):
+            for _, eng in engines:
+                A.fifo_denoise(eng, canvas_p, 25, sched, 4, 5, graph=graph)      # warm-up
+            ts_ = {(name, K_): [] for name, _ in engines for K_ in (K, 2 * K)}
+            for _ in range(args.rounds):
+                for K_ in (K, 2 * K):
+                    for name, eng in engines:
+                        ts_[name, K_].append(timed(lambda: A.fifo_denoise(eng, canvas_p, 25, sched, K_, 5, graph=graph)))
+            per = {}
+            for name, eng in engines:
+                whole = {K_: statistics.median(ts_[name, K_]) for K_ in (K, 2 * K)}
+                per[name] = (whole[2 * K] - whole[K]) / K
+                print(f"  {solver:8s} n = {n}, B = {n // S}, {'replayed' if graph else 'eager':8s} {name:9s}: " +
+                      "; ".join(f"{K_} out " + " ".join(f"{t * 1e3:7.1f}" for t in ts_[name, K_]) for K_ in (K, 2 * K)) +
+                      f"; per finished slot {per[name] * 1e3:.3f}, ramp and start {(whole[K] - K * per[name]) * 1e3:.1f}")
+            a, b = (per[name] for name, _ in engines)
+            print(f"  {'':8s} per finished slot, eta > 0 against eta = 0: {(b - a) * 1e3:+.3f} ms (x {b / a:.3f})")
+    sys.exit(0)
 
 if args.kernels and args.lookahead:
     S, ctx, sl = 6, args.lookahead, 2
