@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from _attn_kit import h2_decode as _h2_decode
 from _kit import components, dev, engine, full, modules, pipeline  # noqa: F401  (dev / full are fixtures)
 from _tune import tuned
 from conftest import rel_err
@@ -14,17 +15,6 @@ from oracle import ref_cpu as R
 from test_gpu_parity import TOL
 
 pytestmark = pytest.mark.gpu
-
-
-def _h2_decode(img: np.ndarray, rows: int, K: int) -> np.ndarray:
-    """Independent reading of the f16x2 image (split3 geometry, planes 0 and 1 hold fp16): -> [2, rows, K] float64."""
-    r = np.arange(rows)[:, None]
-    k = np.arange(K)[None, :]
-    f = ((r & 127) >> 4) & 1
-    half = (k >> 3) & 1
-    base = ((r >> 7) * (K // 16) + (k >> 4)) * (128 * 96) + (r & 127) * 32 + ((half ^ f) * 16) + (k & 7) * 2
-    f16 = img.view(np.float16)
-    return np.stack([f16[(base + p * 4096) // 2].astype(np.float64) for p in range(2)])
 
 
 def _gemm(dev, x, w, b=None, r=None, sx=None, sw=None):

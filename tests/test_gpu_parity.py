@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from _attn_kit import split3_decode as _split3_decode
 from _kit import STREAM_HALF_SECOND, components, dev, engine, full, grp, modules, pipeline  # noqa: F401  (dev / full are fixtures)
 from _tune import tune, tuned
 from conftest import load_golden, rel_err, split_weights
@@ -685,21 +686,6 @@ def test_stream_generate_equals_per_window_sampling(dev, full):
 
 
 # ------------------------------------------------------------------------------------------------- bf16x3 matmul path
-def _split3_decode(img: np.ndarray, rows: int, K: int) -> np.ndarray:
-    """Independent reading of the split3 image layout (include/avdiff_hip.h, csrc/gemm_bf16x3.hip): -> planes [3, rows, K]."""
-    r = np.arange(rows)[:, None]
-    k = np.arange(K)[None, :]
-    f = ((r & 127) >> 4) & 1
-    half = (k >> 3) & 1
-    base = ((r >> 7) * (K // 16) + (k >> 4)) * (128 * 96) + (r & 127) * 32 + ((half ^ f) * 16) + (k & 7) * 2
-    u16 = img.view(np.uint16)
-    planes = []
-    for p in range(3):
-        bits = u16[(base + p * 4096) // 2].astype(np.uint32) << 16
-        planes.append(bits.view(np.float32))
-    return np.stack(planes)
-
-
 @pytest.mark.parametrize("rows,K", [(5, 16), (300, 512), (1000, 2048)])
 def test_split3_is_exact(dev, rows, K):
     """x == h + m + l exactly (each plane 8 significant bits), including huge and tiny magnitudes."""

@@ -263,3 +263,54 @@ def test_agpr_hazard_lint_on_synthetic_listings(tmp_path):
         r = subprocess.run([sys.executable, tool, str(f)], capture_output=True, text=True)
         assert r.returncode == rc, (name, r.stdout, r.stderr)
         assert word in r.stdout, (name, r.stdout)
+
+
+def _s3_supertile(tile, nbn, s3_sn=0, super4=0, super8=0):
+    """mirror of s3_supertile (csrc/gemm_bf16x3.hip): (sn, sm) of the two-per-CU (tile) / one-per-CU kernels"""
+    sn = 8
+    while nbn % sn:
+        sn >>= 1
+    if tile and nbn <= 16:
+        sn = nbn
+    total = 32 if tile else 16
+    if tile and nbn >= 8 and nbn % 4 == 0:
+        sn, total = 4, 64
+    if s3_sn > 0:
+        sn = min(s3_sn, nbn)
+        while nbn % sn:
+            sn -= 1
+    override = super4 if tile else super8
+    if override > 0:
+        total = override
+    return sn, max(total // sn, 1)
+
+
+def _s3_block_of(b, nwg, nbm, nbn, sm, sn):
+    """mirror of s3_block_of (csrc/s3_common.h): block id -> (block row, block column)"""
+    q, r, x = nwg >> 3, nwg & 7, b & 7
+    wg = (x * (q + 1) if x < r else r * (q + 1) + (x - r) * q) + (b >> 3)
+    per_row = sm * nbn
+    srow, rem = divmod(wg, per_row)
+    h = min(nbm - srow * sm, sm)
+    sc, rem2 = divmod(rem, h * sn)
+    return srow * sm + rem2 // sn, sc * sn + rem2 % sn
+
+
+def test_s3_block_map_is_a_bijection():
+    """The split GEMMs' block-to-tile map (XCD remap, then super-tiles with a ragged last super-row) sends the nbm x nbn block ids onto
+    the block grid one to one — for the default super-tile shapes and for the "s3_sn" / "s3_super4" / "s3_super8" values that
+    tests/test_gpu_kernel_variants.py sets, on both kernel families.  Host arithmetic only."""
+    keys = [(0, 0), (2, 8), (3, 6), (4, 4), (1, 3), (2, 1)]          # (s3_sn, s3_super4 resp. s3_super8)
+    for tile in (False, True):
+        for s3_sn, total in keys:
+            for nbn in range(1, 17):
+                sn, sm = _s3_supertile(tile, nbn, s3_sn, total, total)
+                assert sn >= 1 and sm >= 1 and nbn % sn == 0, (tile, s3_sn, total, nbn)
+                for nbm in (1, 2, 3, 5, 11, 17, 33):
+                    nwg = nbm * nbn
+                    seen = {_s3_block_of(b, nwg, nbm, nbn, sm, sn) for b in range(nwg)}
+                    assert seen == {(i, j) for i in range(nbm) for j in range(nbn)}, (tile, s3_sn, total, nbn, nbm)
+    # the five settings of the GPU test give the super-tiles its table names (11 block rows)
+    assert _s3_supertile(True, 4, 2, super4=8) == (2, 4) and _s3_supertile(True, 12, 3, super4=6) == (3, 2)
+    assert _s3_supertile(True, 12, 4, super4=4) == (4, 1) and _s3_supertile(False, 2, 1, super8=3) == (1, 3)
+    assert _s3_supertile(False, 6, 2, super8=1) == (2, 1)
