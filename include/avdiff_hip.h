@@ -343,6 +343,60 @@ int avd_cfg_untoken_ddim_audio_slots_seeded_f32(const float* eps2, const float* 
                                                 const avd_slot_key* key, int slots, float* x0_hist, float* z_out, int B, int Ca, int F,
                                                 int len, int stride, avd_stream_t stream);
 
+/* ---- clip-keyed latent guide: inpainting / SDEdit for the slot entries (a public contract).  A latent guide needs q(t_prev) at the
+ * slot's own noise level, and its known noise has to follow the CLIP POSITION a slot holds while the slot moves through the queue:
+ * the shape "clip-keyed slot noise" gives the step noise, applied to the guide.
+ * A clip guide is the clean clip canvas known [outer, P, inner] (video [C, P, H, W], inner = H*W; audio [Ca, P], inner = 1), an
+ * optional mask canvas of the same layout with values in [0, 1] (NULL: 1 everywhere), a seed, and the slot geometry of avd_slot_key.
+ * For a batch [B, outer, L, inner], slot_len and s = min(l / slot_len, S - 1) as above, element (b, o, l, i) sits on clip position
+ *     p = (first + max(*cursor, 0) + b*stride)*slot_len + l           in SIGNED 64 bits, NOT wrapped
+ *   - p < 0 or p >= P: the element is unguided.  The mask reads as 0 there and known / mask are not read: the comparison comes before
+ *     the read, so no cursor value makes a kernel leave the canvases;
+ *   - 0 <= p < P: x_k = known[o, p, i], m = mask[o, p, i], and n_k is the per-sample guide stream's value for sample p, element
+ *     e' = o*inner + i: counter (e' >> 2, (uint32) p, 0, 0x4B4E5731), the element takes n[e' & 3].  Bit for bit the normal that
+ *     "canvas-keyed known noise" puts on canvas position p: a clip guided through the queue and one guided through the consensus loop
+ *     share their forward paths.
+ * q(tau) = A x_k + S n_k and blend(m, q, z) are avd_latent_guide's, including the a == 1 shortcut and "no contraction".
+ * The guided slot step: a stepping slot takes the (seeded) slot update of "slot timesteps" / "clip-keyed slot noise" giving z_out,
+ * then, in the same kernel, z_out <- blend(m, q(t_prev[b, s]), z_out).
+ *   - a held slot (t_prev == t_now) is z bit for bit: it reads neither the canvases nor the generator, its x0_hist elements are untouched;
+ *   - DPM-Solver++(2M)'s x0_hist receives the model's x0_s, not a blended value;
+ *   - the final step (t_prev = -1) returns x_k bit for bit where m == 1;
+ *   - an all-zero mask, or a canvas every position of the batch misses, gives the bits of the unguided entry;
+ *   - when a slot key rides along (eta > 0) its first / stride / cursor must equal the guide's (AVD_EINVAL before any launch).
+ * Checked before any launch (AVD_EINVAL): non-null guide and known; 1 <= P <= 2^32; outer*inner < 2^34; stride >= 1; |first| < 2^32;
+ * slot_len >= 1 with slots*slot_len <= L; known / mask must not overlap out / z_out / x0_hist.
+ * 16-byte lanes (one Philox call per four values) when inner % 4 == 0 and every base is 16-byte aligned, known and mask included; one
+ * element per lane otherwise (every audio latent); the same bits either way.
+ * Quality is not measured here (no trained weights): the contract is the arithmetic. */
+typedef struct {
+    const float* known;      /* fp32 [outer, P, inner]: the clean clip canvas */
+    const float* mask;       /* fp32 [outer, P, inner] in [0, 1], or NULL = 1 everywhere */
+    int64_t  P;              /* clip positions of the canvases */
+    uint64_t seed;           /* of the guide's known-noise stream */
+    int64_t  first;          /* as avd_slot_key */
+    int32_t  stride;
+    const int32_t* cursor;
+} avd_clip_guide;
+#define AVD_SLOT_LEAVE INT64_MIN
+/* The stand-alone pass: out = blend(m(p), q_p(tau[b, s]), z) per slot; tau: int64 [B*slots].  tau[b, s] == AVD_SLOT_LEAVE leaves that
+ * slot's elements as z, bit for bit.  everywhere != 0 reads the mask as 1 on every in-canvas position (SDEdit's start: q everywhere).
+ * out may be z; an in-place call with one slot set touches that slot's bytes alone (a block whose slot is left returns before it
+ * loads anything): it is what puts a queue's start, and each entering tail slot, on the forward path at s_0. */
+int avd_clip_guide_slots_f32(const avd_clip_guide* g, const int64_t* tau, const float* alpha_bar, int T_train, int everywhere,
+                             const float* z, float* out, int B, int64_t outer, int L, int slots, int slot_len, int64_t inner,
+                             avd_stream_t stream);
+/* The fused updates alone: avd_cfg_unpatch_ddim_slots_seeded_f32 / avd_cfg_untoken_ddim_audio_slots_seeded_f32 ending in the clip
+ * guide's blend.  key may be NULL at eta == 0; t_last / x0_hist both NULL or both set, as there. */
+int avd_cfg_unpatch_ddim_slots_guided_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                          const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, float eta,
+                                          const avd_slot_key* key, const avd_clip_guide* guide, int slots, float* x0_hist, float* z_out,
+                                          int B, int C, int T, int H, int W, int t, int h, int w, avd_stream_t stream);
+int avd_cfg_untoken_ddim_audio_slots_guided_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                                const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, float eta,
+                                                const avd_slot_key* key, const avd_clip_guide* guide, int slots, float* x0_hist,
+                                                float* z_out, int B, int Ca, int F, int len, int stride, avd_stream_t stream);
+
 /* ---- FIFO queue shift: the queue step of diagonal denoising (FIFO-Diffusion, Kim et al. 2024) in one out-of-place launch.
  * The batch z_in [B, outer, L, inner] ((outer, L, inner) as in "canvas-keyed noise") with L = slots*slot_len is read as a queue of
  * B*slots slots: queue slot q lives in sample q / slots at positions (q % slots)*slot_len .. + slot_len - 1 of the sliding axis.
@@ -885,6 +939,12 @@ int avd_denoise_step_slots_dpmpp_2m_f32(const avd_step_desc* s, const float* z, 
 int avd_denoise_step_slots_seeded_f32(const avd_step_desc* s, const avd_slot_key* key, const int64_t* t_last, float* x0_hist,
                                       const float* z, const float* Xp, const int64_t* t_now, const int64_t* t_prev, int slots,
                                       float* z_out, void* workspace, int64_t workspace_bytes, avd_stream_t stream);
+/* The whole step on slot timesteps ending in the clip guide's blend (see "clip-keyed latent guide"): avd_denoise_step_slots_seeded_f32
+ * with the guide added; key may be NULL at s->eta == 0.  The front end is avd_denoise_step_slots_f32's, launch for launch; the guide
+ * and the key are checked before the model runs.  Graph-capturable: the cursor is read at every launch. */
+int avd_denoise_step_slots_guided_f32(const avd_step_desc* s, const avd_slot_key* key, const avd_clip_guide* guide, const int64_t* t_last,
+                                      float* x0_hist, const float* z, const float* Xp, const int64_t* t_now, const int64_t* t_prev,
+                                      int slots, float* z_out, void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 /* As avd_denoise_step_f32, with the eta > 0 noise drawn inside the fused CFG + DDIM kernel from the seeded stream (avd_noise_key)
  * for samples key->sample_offset .. + B - 1 at t_now: no noise buffer, graph-capturable.  With s->eta == 0 it is the plain step. */
 int avd_denoise_step_seeded_f32(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp,

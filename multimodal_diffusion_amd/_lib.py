@@ -74,6 +74,16 @@ class SlotKey(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first", C.c_int64), ("stride", C.c_int32), ("cursor", C.c_void_p)]
 
 
+class ClipGuide(C.Structure):
+    """avd_clip_guide: the clean clip canvas, its mask canvas, the seed of the known-noise stream and the slot geometry of avd_slot_key
+    (contract in include/avdiff_hip.h, "clip-keyed latent guide").  Raw device pointers: keep the tensors alive."""
+    _fields_ = [("known", C.c_void_p), ("mask", C.c_void_p), ("P", C.c_int64), ("seed", C.c_uint64), ("first", C.c_int64),
+                ("stride", C.c_int32), ("cursor", C.c_void_p)]
+
+
+SLOT_LEAVE = -2 ** 63      # AVD_SLOT_LEAVE: a tau entry that leaves its slot as z
+
+
 class LatentGuide(C.Structure):
     """avd_latent_guide: a known clean latent, its mask and the key of its known-noise stream (contract in include/avdiff_hip.h)."""
     _fields_ = [("known", C.c_void_p), ("mask", C.c_void_p), ("mask_batch_stride", C.c_int64), ("key", NoiseKey)]
@@ -168,6 +178,13 @@ SIGNATURES = {
     "avd_cfg_untoken_ddim_audio_slots_seeded_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _F, C.POINTER(SlotKey), _I, _P, _P] + [_I] * 5 +
                                                     [_P]),
     "avd_denoise_step_slots_seeded_f32": (_I, [C.POINTER(StepDesc), C.POINTER(SlotKey), _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P]),
+    "avd_clip_guide_slots_f32": (_I, [C.POINTER(ClipGuide), _P, _P, _I, _I, _P, _P, _I, _L, _I, _I, _I, _L, _P]),
+    "avd_cfg_unpatch_ddim_slots_guided_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _F, C.POINTER(SlotKey), C.POINTER(ClipGuide), _I, _P, _P] +
+                                              [_I] * 8 + [_P]),
+    "avd_cfg_untoken_ddim_audio_slots_guided_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _F, C.POINTER(SlotKey), C.POINTER(ClipGuide), _I, _P,
+                                                         _P] + [_I] * 5 + [_P]),
+    "avd_denoise_step_slots_guided_f32": (_I, [C.POINTER(StepDesc), C.POINTER(SlotKey), C.POINTER(ClipGuide), _P, _P, _P, _P, _P, _P, _I, _P,
+                                               _P, _L, _P]),
     "avd_fifo_shift_hist_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _P, _P, _P, _P, _P, _I, _L, _I, _I, _L, _P]),
     "avd_fifo_lookahead_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _I, _P, _P, _P, _I, _L, _I, _I, _I, _L, _P]),
     "avd_fifo_lookahead_hist_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _I, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _L, _P]),

@@ -340,11 +340,14 @@ struct CfgState;
 struct NoiseKey;
 struct CanvasKey;
 struct SlotKey;
+// A ClipGuideState ends a slot pack ("clip-keyed latent guide"): behind the SlotTimes, and behind the SlotKey when there is one.
+struct ClipGuideState;
 template <bool SEEDED, class... X> struct PackOk {
     template <class T> static constexpr int n = PackHas<T, X...>::value ? 1 : 0;
     static constexpr bool value = sizeof...(X) == (SEEDED ? 1 : 0) + n<DpmState> + n<GuideState> + n<CanvasGuideState> + n<CfgState> +
-                                                      n<CondOnly> + n<SlotTimes> &&
-                                  !(n<SlotTimes> && sizeof...(X) != 1 + n<DpmState> + n<SlotKey>) && n<SlotKey> <= n<SlotTimes> &&
+                                                      n<CondOnly> + n<SlotTimes> + n<ClipGuideState> &&
+                                  !(n<SlotTimes> && sizeof...(X) != 1 + n<DpmState> + n<SlotKey> + n<ClipGuideState>) &&
+                                  n<SlotKey> <= n<SlotTimes> && n<ClipGuideState> <= n<SlotTimes> &&
                                   !(n<CfgState> && n<CondOnly>) && !(n<GuideState> && n<CanvasGuideState>) &&
                                   !(n<CanvasGuideState> && n<NoiseKey>) &&
                                   n<NoiseKey> + n<CanvasKey> + n<SlotKey> == (SEEDED ? 1 : 0);
@@ -1105,6 +1108,164 @@ __device__ __forceinline__ float canvas_guide_apply1(const CanvasGuideState& gs,
     float n = 0.f;
     if (!gc.one) n = canvas_normal4(gs.ck, b, o, l, i, inner, 0u, GUIDE_TAG)[(int)((o * inner + i) & 3)];
     return guide_blend(m, guide_q(gc, gs.known[idx], n), z);
+}
+
+// The clip keying of the guide (include/avdiff_hip.h, "clip-keyed latent guide"): known / mask are canvases [outer, P, inner] of the
+// whole clip, and element (o, l, i) of sample b sits on clip position p = (first + max(*cursor, 0) + b * stride) * slot_len + l, signed
+// and unwrapped.  Outside [0, P) the element is unguided and nothing is read; inside, x_k and m are gathered at (o, p, i) and n_k is
+// canvas_normal4's value for canvas position p (GUIDE_TAG, no timestep).  q and the blend are guide_q / guide_blend, as above.
+struct ClipGuideState {
+    const float* known;       // [outer, P, inner]
+    const float* mask;        // [outer, P, inner]; nullptr = 1 everywhere
+    int64_t P;
+    uint32_t k0, k1;          // seed & 0xffffffff, seed >> 32
+    int64_t first;            // as SlotKey
+    int32_t stride, slot_len;
+    const int32_t* cursor;    // device int32 or null: it selects the position, which is compared with [0, P) before it addresses
+    int vec;                  // inner % 4 == 0 and known / mask 16-byte aligned: the canvases are read as f32x4
+};
+__device__ __forceinline__ int64_t clip_guide_pos(const ClipGuideState& cg, int b, int l) {
+    int64_t m = cg.cursor ? *cg.cursor : 0;
+    if (m < 0) m = 0;
+    return (cg.first + m + (int64_t)b * cg.stride) * cg.slot_len + l;      // the host bounds every term: no overflow
+}
+__device__ __forceinline__ f32x4 clip_canvas4(const float* c, int64_t at, bool vec) {
+    if (vec) return *reinterpret_cast<const f32x4*>(c + at);
+    return f32x4{c[at], c[at + 1], c[at + 2], c[at + 3]};
+}
+// elements i .. i + 3 of the (o, l) slice (inner % 4 == 0, i % 4 == 0); a lane whose four mask values are 0 skips the generator: the
+// blend would not read q
+__device__ __forceinline__ f32x4 clip_guide_apply4(const ClipGuideState& cg, const GuideCoef& gc, int b, int64_t o, int l, int64_t i,
+                                                   int64_t inner, f32x4 z) {
+    const int64_t p = clip_guide_pos(cg, b, l);
+    if (p < 0 || p >= cg.P) return z;
+    const int64_t at = (o * cg.P + p) * inner + i;
+    f32x4 m = {1.f, 1.f, 1.f, 1.f};
+    if (cg.mask) {
+        m = clip_canvas4(cg.mask, at, cg.vec);
+        if (m[0] == 0.f && m[1] == 0.f && m[2] == 0.f && m[3] == 0.f) return z;
+    }
+    const f32x4 xk = clip_canvas4(cg.known, at, cg.vec);
+    f32x4 n = {0.f, 0.f, 0.f, 0.f};
+    if (!gc.one) n = philox_normal4(NoiseKey{cg.k0, cg.k1, 0u}, (uint32_t)((o * inner + i) >> 2), (uint32_t)p, 0u, GUIDE_TAG);
+    f32x4 r;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] = guide_blend(m[k], guide_q(gc, xk[k], n[k]), z[k]);
+    return r;
+}
+// one element i of the (o, l) slice
+__device__ __forceinline__ float clip_guide_apply1(const ClipGuideState& cg, const GuideCoef& gc, int b, int64_t o, int l, int64_t i,
+                                                   int64_t inner, float z) {
+    const int64_t p = clip_guide_pos(cg, b, l);
+    if (p < 0 || p >= cg.P) return z;
+    const int64_t at = (o * cg.P + p) * inner + i;
+    const float m = cg.mask ? cg.mask[at] : 1.f;
+    if (m == 0.f) return z;
+    float n = 0.f;
+    if (!gc.one) n = philox_normal4(NoiseKey{cg.k0, cg.k1, 0u}, (uint32_t)((o * inner + i) >> 2), (uint32_t)p, 0u, GUIDE_TAG)[(int)((o * inner + i) & 3)];
+    return guide_blend(m, guide_q(gc, cg.known[at], n), z);
+}
+
+// the clip guide's checks, all before any HIP call (the list is in the header); outs: buffers known / mask must not overlap, each of
+// B * outer * L * inner floats, nullptr skipped
+int make_clip_guide(const avd_clip_guide* g, int B, int64_t outer, int L, int slots, int slot_len, int64_t inner,
+                    std::initializer_list<const float*> outs, ClipGuideState& cg, const char* what = "clip_guide") {
+    AVD_REQUIRE(g, AVD_EINVAL, "%s: null clip guide", what);
+    AVD_REQUIRE(g->known, AVD_EINVAL, "%s: null known canvas", what);
+    AVD_REQUIRE(B > 0 && outer > 0 && L > 0 && inner > 0, AVD_EINVAL, "%s: bad dims (B %d, outer %lld, L %d, inner %lld)", what, B,
+                (long long)outer, L, (long long)inner);
+    const int64_t lim = (int64_t)1 << 32;
+    AVD_REQUIRE(g->P >= 1 && g->P <= lim, AVD_EINVAL, "%s: the clip guide's P %lld must lie in [1, 2^32]", what, (long long)g->P);
+    AVD_REQUIRE(outer <= (((int64_t)1 << 34) - 1) / inner, AVD_EINVAL, "%s: outer %lld * inner %lld must be < 2^34", what, (long long)outer,
+                (long long)inner);
+    AVD_REQUIRE(g->stride >= 1, AVD_EINVAL, "%s: the clip guide's stride must be >= 1 (got %d)", what, g->stride);
+    AVD_REQUIRE(g->first > -lim && g->first < lim, AVD_EINVAL, "%s: the clip guide's first %lld must lie in (-2^32, 2^32)", what,
+                (long long)g->first);
+    AVD_REQUIRE(slot_len >= 1 && slots >= 1 && (int64_t)slots * slot_len <= L && (int64_t)B * slots <= 0x7fffffff, AVD_EINVAL,
+                "%s: slots %d * slot_len %d must lie in [1, L %d] and B %d * slots fit an int", what, slots, slot_len, L, B);
+    // every term of the position: |first| < 2^32, the cursor < 2^31, B * stride < 2^62, so the slot index stays below 2^62.1 only
+    // when B * stride does; times slot_len plus l it must stay inside int64
+    AVD_REQUIRE(((double)B * g->stride + 8.6e9) * (double)slot_len + (double)L < 9.0e18, AVD_EINVAL,
+                "%s: B %d * stride %d * slot_len %d leaves the signed 64-bit positions", what, B, g->stride, slot_len);
+    AVD_REQUIRE((double)outer * (double)g->P * (double)inner < 9.0e18 && (double)B * (double)outer * (double)L * (double)inner < 9.0e18,
+                AVD_EUNSUPPORTED, "%s: too many values", what);
+    const int64_t nc = outer * g->P * inner, n = (int64_t)B * outer * L * inner;
+    for (const float* p : outs) {
+        if (!p) continue;
+        AVD_REQUIRE(!(p < g->known + nc && g->known < p + n) && !(g->mask && p < g->mask + nc && g->mask < p + n), AVD_EINVAL,
+                    "%s: known / mask must not overlap out, z_out or x0_hist", what);
+    }
+    cg = ClipGuideState{g->known, g->mask, g->P, (uint32_t)(g->seed & 0xffffffffu), (uint32_t)(g->seed >> 32), g->first, g->stride,
+                        slot_len, g->cursor, inner % 4 == 0 && aligned16(g->known) && aligned16(g->mask) ? 1 : 0};
+    return AVD_OK;
+}
+
+int check_clip_guide(const avd_clip_guide* g, int B, int64_t outer, int L, int slots, int slot_len, int64_t inner, const float* out,
+                     const float* x0_hist) {
+    ClipGuideState cg;
+    return make_clip_guide(g, B, outer, L, slots, slot_len, inner, {out, x0_hist}, cg);
+}
+
+// The stand-alone pass (avd_clip_guide_slots_f32): out = blend(m(p), q_p(tau[b, s]), z) per slot.  A block lies inside one slot of one
+// (b, o) row — bpr blocks cover the longest row, the last slot's with the uncovered tail — so the slot's tau is block-uniform, and a
+// block whose slot is left (AVD_SLOT_LEAVE) returns before it loads anything when the call is in place, and copies z otherwise.
+// V lanes as canvas_noise_kernel.
+template <int V>
+__global__ __launch_bounds__(256) void clip_guide_slots_kernel(ClipGuideState cg, const int64_t* __restrict__ tau,
+                                                               const float* __restrict__ abar, int T_train, const float* z, float* out,
+                                                               int64_t outer, int L, int S, int64_t inner, int bpr) {      // z may be out
+    int64_t r = blockIdx.x;
+    const int chunk = (int)(r % bpr);
+    r /= bpr;
+    const int s = (int)(r % S);
+    r /= S;
+    const int64_t o = r % outer;
+    const int b = (int)(r / outer);
+    const int64_t t = tau[(int64_t)b * S + s];
+    const bool leave = t == INT64_MIN;
+    if (leave && out == z) return;
+    const int l0 = s * cg.slot_len;
+    const int nl = s == S - 1 ? L - l0 : cg.slot_len;      // the uncovered tail follows the last slot
+    const int64_t j = ((int64_t)chunk * 256 + threadIdx.x) * V;      // the lane's first element of the slot's [nl, inner] piece
+    if (j >= (int64_t)nl * inner) return;
+    const int l = l0 + (int)(j / inner);
+    const int64_t i = j % inner;
+    const int64_t at = (((int64_t)b * outer + o) * L + l) * inner + i;
+    if constexpr (V == 4) {
+        f32x4 v = *reinterpret_cast<const f32x4*>(z + at);
+        if (!leave) v = clip_guide_apply4(cg, guide_coef(abar, T_train, t), b, o, l, i, inner, v);
+        *reinterpret_cast<f32x4*>(out + at) = v;
+    } else {
+        float v = z[at];
+        if (!leave) v = clip_guide_apply1(cg, guide_coef(abar, T_train, t), b, o, l, i, inner, v);
+        out[at] = v;
+    }
+}
+
+int clip_guide_slots_f32(const avd_clip_guide* g, const int64_t* tau, const float* abar, int T_train, int everywhere, const float* z,
+                         float* out, int B, int64_t outer, int L, int slots, int slot_len, int64_t inner, hipStream_t st) {
+    ClipGuideState cg;
+    if (int rc = make_clip_guide(g, B, outer, L, slots, slot_len, inner, {out}, cg, "clip_guide_slots")) return rc;
+    AVD_REQUIRE(tau && abar && z && out && T_train > 0, AVD_EINVAL, "clip_guide_slots: null pointer or bad T_train");
+    const int64_t total = (int64_t)B * outer * L * inner;
+    AVD_REQUIRE(out == z || !overlaps(out, z, total), AVD_EINVAL, "clip_guide_slots: out must be z or not overlap it");
+    if (everywhere) cg.mask = nullptr;      // the mask reads as 1 on every in-canvas position
+    cg.vec = inner % 4 == 0 && aligned16(cg.known) && aligned16(cg.mask);
+    const bool vec = cg.vec && aligned16(z) && aligned16(out);
+    const int64_t row = (int64_t)(L - (slots - 1) * slot_len) * inner / (vec ? 4 : 1);      // lanes of the longest slot piece
+    const int64_t bpr = (row + 255) / 256, blocks = (int64_t)B * outer * slots * bpr;
+    AVD_REQUIRE(bpr <= 0x7fffffff && blocks <= 0x7fffffff, AVD_EUNSUPPORTED, "clip_guide_slots: %lld blocks are too many for one launch",
+                (long long)blocks);
+    static const int tags[2] = {prof_tag_id("clip_guide_slots_kernel<1>"), prof_tag_id("clip_guide_slots_kernel<4>")};
+    ProfScope prof(tags[vec ? 1 : 0], 4.0 * (double)total * 4, st);      // an upper bound: left slots move nothing
+    if (vec)
+        hipLaunchKernelGGL(clip_guide_slots_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, st, cg, tau, abar, T_train, z, out, outer, L,
+                           slots, inner, (int)bpr);
+    else
+        hipLaunchKernelGGL(clip_guide_slots_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, cg, tau, abar, T_train, z, out, outer, L,
+                           slots, inner, (int)bpr);
+    AVD_CHECK_LAUNCH("clip_guide_slots");
+    return AVD_OK;
 }
 
 // the checks every guided entry makes before any HIP call; out and x0_hist (either may be nullptr) must not overlap known / mask
@@ -1932,6 +2093,11 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
         o = canvas_guide_apply4(pack_get<CanvasGuideState>(nk...), guide_coef(abar, T_train, t_prev[b]), b, lat, e4 * 4, r / g.T,
                                 (int)(r % g.T), (e4 % hw4) * 4, hw4 * 4, o);
     }
+    if constexpr (PackHas<ClipGuideState, Key...>::value) {      // the clip-keyed guide of a stepping slot: q at the slot's own t_prev
+        const int64_t hw4 = ((int64_t)g.H * g.W) >> 2, r = e4 / hw4;
+        o = clip_guide_apply4(pack_get<ClipGuideState>(nk...), guide_coef(abar, T_train, t_prev[tb]), b, r / g.T, (int)(r % g.T),
+                              (e4 % hw4) * 4, hw4 * 4, o);
+    }
     *reinterpret_cast<f32x4*>(z_out + lat) = o;
 }
 
@@ -2051,6 +2217,9 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         if constexpr (CGUIDED)      // the canvas-keyed guide: the (c, t, h, w) decomposition of the canvas-keyed draw above
             o = canvas_guide_apply4(pack_get<CanvasGuideState>(nk...), gc, b, lat, lat - (int64_t)b * g.per, cc, tq * g.t + tt,
                                     (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo, (int64_t)g.H * g.W, o);
+        if constexpr (PackHas<ClipGuideState, Key...>::value)      // the clip-keyed guide: the same decomposition, q at the block's slot t_prev
+            o = clip_guide_apply4(pack_get<ClipGuideState>(nk...), guide_coef(abar, T_train, t_prev[tb]), b, cc, tq * g.t + tt,
+                                  (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo, (int64_t)g.H * g.W, o);
         *reinterpret_cast<f32x4*>(z_out + lat) = o;
     }
 }
@@ -2074,6 +2243,8 @@ struct UpdateKeys {
     SlotTimes sl;
     bool skey;         // the slot form at eta > 0: sk ends the slot pack (clip-keyed slot noise)
     SlotKey sk;
+    bool clip;         // the slot form under a clip-keyed latent guide: cg ends the slot pack
+    ClipGuideState cg;
     DpmState ds;
     NoiseKey nk;
     CanvasKey ck;      // canvas: the seeded draw is keyed by canvas position (ck replaces nk in the pack)
@@ -2147,7 +2318,9 @@ static int check_fused_update(const char* what, const UpdateArgs& a, int64_t per
 // The slot form's checks, before any HIP call: slots == 0 is the per-sample update; otherwise `slots` must be the geometry's S and the
 // update is DDIM or, with t_last / x0_hist (checked as a pair by check_fused_update; t_last is then a [B, S] table too), DPM-Solver++(2M),
 // at eta == 0 with nothing else in the pack (the scope of "slot timesteps" in include/avdiff_hip.h), or at eta > 0 with a slot key
-// ("clip-keyed slot noise"; skd: the key's (outer, slot_len, inner)), which at eta == 0 is not read
+// ("clip-keyed slot noise"; skd: the key's (outer, slot_len, inner)), which at eta == 0 is not read.  cguide != nullptr ends the slot
+// update in the clip-keyed latent guide's blend, at any eta (L: the sliding length its positions run over); a slot key riding along
+// must carry the guide's geometry
 struct SlotKeyDims {
     int64_t outer;
     int slot_len;
@@ -2155,8 +2328,9 @@ struct SlotKeyDims {
 };
 static int check_slot_update(const char* what, const UpdateArgs& a, int slots, int S, const avd_noise_key* key,
                              const avd_latent_guide* guide, const avd_cfg_control* ctl, int canvas_hop, int guide_hop, UpdateKeys& k,
-                             const avd_slot_key* skey, const SlotKeyDims& skd) {
+                             const avd_slot_key* skey, const SlotKeyDims& skd, const avd_clip_guide* cguide = nullptr, int L = 0) {
     AVD_REQUIRE(slots || !skey, AVD_EINVAL, "%s: a slot key rides with slot timesteps (slots > 0)", what);
+    AVD_REQUIRE(slots || !cguide, AVD_EINVAL, "%s: a clip guide rides with slot timesteps (slots > 0)", what);
     if (!slots) return AVD_OK;
     AVD_REQUIRE(slots == S, AVD_EINVAL, "%s: slots %d must equal the geometry's %d slots along the sliding axis", what, slots, S);
     AVD_REQUIRE((a.eta == 0.f || skey) && !a.noise && !key, AVD_EINVAL,
@@ -2169,6 +2343,12 @@ static int check_slot_update(const char* what, const UpdateArgs& a, int slots, i
     k.skey = skey && a.eta > 0.f;
     if (k.skey)
         if (int rc = make_slot_key(skey, a.B, skd.outer, skd.slot_len, skd.inner, k.sk, what)) return rc;
+    k.clip = cguide != nullptr;
+    if (cguide) {      // L: the sliding length the positions run over (the guide's checks: include/avdiff_hip.h, "clip-keyed latent guide")
+        if (int rc = make_clip_guide(cguide, a.B, skd.outer, L, S, skd.slot_len, skd.inner, {a.z_out, k.ds.x0_hist}, k.cg, what)) return rc;
+        AVD_REQUIRE(!k.skey || (skey->first == cguide->first && skey->stride == cguide->stride && skey->cursor == cguide->cursor), AVD_EINVAL,
+                    "%s: the slot key's first / stride / cursor must equal the clip guide's (one clip position per element)", what);
+    }
     return AVD_OK;
 }
 
@@ -2180,11 +2360,15 @@ static int check_slot_update(const char* what, const UpdateArgs& a, int slots, i
 // the solver states that can reach it: none, DpmState, CanvasKey, DpmState then CanvasKey (never a NoiseKey: check_fused_update).
 template <class F>
 static void with_update_pack(const UpdateKeys& k, bool cond_only, F launch) {
-    if (k.slots) {
-        if (k.dpm && k.skey) launch(k.ds, k.sl, k.sk);
-        else if (k.dpm) launch(k.ds, k.sl);
-        else if (k.skey) launch(k.sl, k.sk);
-        else launch(k.sl);
+    if (k.slots) {      // a clip-keyed guide ends the slot pack
+        auto stail = [&](auto... state) {
+            if (k.clip) launch(state..., k.cg);
+            else launch(state...);
+        };
+        if (k.dpm && k.skey) stail(k.ds, k.sl, k.sk);
+        else if (k.dpm) stail(k.ds, k.sl);
+        else if (k.skey) stail(k.sl, k.sk);
+        else stail(k.sl);
         return;
     }
     if (k.cguide) {
@@ -2243,7 +2427,8 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key,
                          const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
-                         int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg, const avd_slot_key* skey = nullptr) {
+                         int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg, const avd_slot_key* skey = nullptr,
+                         const avd_clip_guide* cguide = nullptr) {
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "cfg_unpatch_ddim: bad dims");
     Tube g;
     if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
@@ -2255,7 +2440,7 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
     if (int rc = check_fused_update("cfg_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
                                     guide_hop ? &gcv : nullptr, apg, (int64_t)2 * B * g.per * 4, skey)) return rc;
     if (int rc = check_slot_update("cfg_unpatch_ddim", a, slots, T / t, key, guide, ctl, canvas_hop, guide_hop, k, skey,
-                                   SlotKeyDims{C, t, (int64_t)H * W})) return rc;
+                                   SlotKeyDims{C, t, (int64_t)H * W}, cguide, T)) return rc;
     if (apg) {
         AVD_REQUIRE(aligned16(eps2) && aligned16(eps2 + (int64_t)B * g.per) && aligned16(z) && aligned16(z_out), AVD_EUNSUPPORTED,
                     "cfg_unpatch_ddim: the APG statistics pass reads 16-byte aligned token rows");
@@ -2269,7 +2454,9 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
     }
     static const int tag = prof_tag_id("cfg_unpatch_ddim_kernel");
     static const int tag_apg = prof_tag_id("cfg_unpatch_ddim_kernel<apg>");      // the fused launch of an APG step, timed apart
-    ProfScope prof(apg ? tag_apg : tag, (apg && apg->momentum_buf ? 24.0 : 16.0) * (double)B * g.per, st);
+    static const int tag_clip = prof_tag_id("cfg_unpatch_ddim_kernel<clip guide>");      // as is the clip-guided slot update
+    ProfScope prof(apg ? tag_apg : cguide ? tag_clip : tag,
+                   (apg && apg->momentum_buf ? 24.0 : cguide ? (cguide->mask ? 24.0 : 20.0) : 16.0) * (double)B * g.per, st);
     with_update_pack(k, false, [&](auto... p) { launch_unpatch(a, g, st, p...); });
     AVD_CHECK_LAUNCH("cfg_unpatch_ddim");
     return AVD_OK;
@@ -2370,6 +2557,8 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
         else if constexpr (CGUIDED)      // the canvas-keyed guide: canvas position from f, element c of its slice (inner == 1)
             return canvas_guide_apply1(pack_get<CanvasGuideState>(nk...), guide_coef(abar, T_train, t_prev[b]), b, i,
                                        i - (int64_t)b * Ca * F, c, f, 0, 1, v);
+        else if constexpr (PackHas<ClipGuideState, Key...>::value)      // the clip-keyed guide: clip position from f, q at the slot's t_prev
+            return clip_guide_apply1(pack_get<ClipGuideState>(nk...), guide_coef(abar, T_train, t_prev[tb]), b, c, f, 0, 1, v);
         else
             return v;
     };
@@ -2412,7 +2601,8 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st, const avd_noise_key* key,
                                const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
-                               int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg, const avd_slot_key* skey = nullptr) {
+                               int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg, const avd_slot_key* skey = nullptr,
+                               const avd_clip_guide* cguide = nullptr) {
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "cfg_untoken_ddim_audio: bad chunking");
     AVD_REQUIRE(!slots || stride == len, AVD_EUNSUPPORTED,
@@ -2426,7 +2616,7 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
     if (int rc = check_fused_update("cfg_untoken_ddim_audio", a, per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
                                     guide_hop ? &gcv : nullptr, apg, (int64_t)2 * B * ag.Na * Ca * len * 4, skey)) return rc;
     if (int rc = check_slot_update("cfg_untoken_ddim_audio", a, slots, ag.Na, key, guide, ctl, canvas_hop, guide_hop, k, skey,
-                                   SlotKeyDims{Ca, len, 1})) return rc;
+                                   SlotKeyDims{Ca, len, 1}, cguide, F)) return rc;
     if (apg) {
         const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
         if (int rc = run_apg_stats<CFG_SRC_AUDIO>(apg, ctl ? ctl->guidance : nullptr, guidance, eps2, eps2 + B * half, half, B, per,
@@ -2867,6 +3057,39 @@ extern "C" int avd_cfg_untoken_ddim_audio_slots_seeded_f32(const float* eps2, co
     AVD_REQUIRE(key, AVD_EINVAL, "cfg_untoken_ddim_audio_slots_seeded: null slot key");
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, nullptr, z_out, B, Ca, F, len, stride,
                                       static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots, nullptr, key);
+}
+// the slot forms under a clip-keyed latent guide ("clip-keyed latent guide" in the header): the seeded entries' arguments and the guide;
+// the key is read at eta > 0 only and may be null at eta == 0
+extern "C" int avd_cfg_unpatch_ddim_slots_guided_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                                     const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, float eta,
+                                                     const avd_slot_key* key, const avd_clip_guide* guide, int slots, float* x0_hist,
+                                                     float* z_out, int B, int C, int T, int H, int W, int t, int h, int w,
+                                                     avd_stream_t stream) {
+    AVD_REQUIRE(aligned16(eps2) && aligned16(z) && aligned16(z_out), AVD_EUNSUPPORTED,
+                "cfg_unpatch_ddim_slots_guided: pointers must be 16-byte aligned");
+    AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_unpatch_ddim_slots_guided: slots must be > 0 (got %d)", slots);
+    AVD_REQUIRE(guide, AVD_EINVAL, "cfg_unpatch_ddim_slots_guided: null clip guide");
+    AVD_REQUIRE(key || !(eta > 0.f), AVD_EINVAL, "cfg_unpatch_ddim_slots_guided: eta > 0 needs a slot key");
+    return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, nullptr, z_out, B, C, T, H, W, t, h, w,
+                                static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots, nullptr, key, guide);
+}
+extern "C" int avd_cfg_untoken_ddim_audio_slots_guided_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                                           const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance,
+                                                           float eta, const avd_slot_key* key, const avd_clip_guide* guide, int slots,
+                                                           float* x0_hist, float* z_out, int B, int Ca, int F, int len, int stride,
+                                                           avd_stream_t stream) {
+    AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_untoken_ddim_audio_slots_guided: slots must be > 0 (got %d)", slots);
+    AVD_REQUIRE(guide, AVD_EINVAL, "cfg_untoken_ddim_audio_slots_guided: null clip guide");
+    AVD_REQUIRE(key || !(eta > 0.f), AVD_EINVAL, "cfg_untoken_ddim_audio_slots_guided: eta > 0 needs a slot key");
+    return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, nullptr, z_out, B, Ca, F, len, stride,
+                                      static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots, nullptr, key,
+                                      guide);
+}
+extern "C" int avd_clip_guide_slots_f32(const avd_clip_guide* g, const int64_t* tau, const float* alpha_bar, int T_train, int everywhere,
+                                        const float* z, float* out, int B, int64_t outer, int L, int slots, int slot_len, int64_t inner,
+                                        avd_stream_t stream) {
+    return clip_guide_slots_f32(g, tau, alpha_bar, T_train, everywhere, z, out, B, outer, L, slots, slot_len, inner,
+                                static_cast<hipStream_t>(stream));
 }
 extern "C" int avd_slot_noise_f32(const avd_slot_key* key, const int64_t* t_now, float* out, int B, int64_t outer, int L, int slots,
                                   int slot_len, int64_t inner, avd_stream_t stream) {

@@ -651,6 +651,73 @@ def slot_noise(seed: int, t_now: Tensor, shape, slot_len: int, first: int = 0, s
     return out
 
 
+SLOT_LEAVE = L.SLOT_LEAVE      # a tau entry of clip_guide_slots that leaves its slot as z (AVD_SLOT_LEAVE)
+
+
+def _clip_canvas(t: Tensor, name: str, like: Optional[Tensor] = None) -> Tensor:
+    if not (isinstance(t, Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() in (2, 4)):
+        raise ValueError(f"{name} must be a contiguous float32 device canvas [C, P, H, W] (video) or [Ca, P] (audio)")
+    if like is not None and (tuple(t.shape) != tuple(like.shape) or t.device != like.device):
+        raise ValueError(f"{name} shape {tuple(t.shape)} must be the known canvas's {tuple(like.shape)}, on its device")
+    return t
+
+
+def clip_guide(known: Tensor, mask: Optional[Tensor], seed: int, first: int = 0, stride: int = 1, cursor: Optional[Tensor] = None,
+               shape=None) -> "L.ClipGuide":
+    """avd_clip_guide (include/avdiff_hip.h, "clip-keyed latent guide") after the checks its users share: ``known`` the clean clip
+    canvas, contiguous float32 on the device, [C, P, H, W] (video) or [Ca, P] (audio); ``mask`` None (1 everywhere) or a canvas of the
+    same shape with values in [0, 1] (what ``sampler.canvas_frame_mask`` returns); ``seed`` / ``first`` / ``stride`` / ``cursor`` as
+    ``slot_key``.  ``shape``: the batch the guide will ride with ([B,C,T,H,W] / [B,Ca,F]), whose channel and spatial sizes must be the
+    canvas's.  The struct holds raw pointers: keep the tensors alive."""
+    known = _clip_canvas(known, "known")
+    if mask is not None:
+        _clip_canvas(mask, "mask", known)
+    if known.shape[1] < 1 or known.shape[1] > 2 ** 32:
+        raise ValueError(f"the known canvas holds {known.shape[1]} clip positions, a clip guide takes 1 .. 2**32")
+    if shape is not None:
+        shape = tuple(int(s) for s in shape)
+        if len(shape) != known.dim() + 1 or shape[1] != known.shape[0] or tuple(shape[3:]) != tuple(known.shape[2:]):
+            raise ValueError(f"a known canvas of shape {tuple(known.shape)} does not guide a batch of shape {shape}: the channels and "
+                             "the spatial sizes must agree")
+    k = slot_key(seed, first, stride, cursor, known.device)
+    return L.ClipGuide(known.data_ptr(), L.ptr(mask), known.shape[1], k.seed, k.first, k.stride, k.cursor)
+
+
+def clip_guide_slots(known: Tensor, tau: Tensor, alpha_bar: Tensor, z: Tensor, mask: Optional[Tensor] = None, *, slot_len: int,
+                     seed: int, first: int = 0, stride: Optional[int] = None, cursor: Optional[Tensor] = None,
+                     everywhere: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """The clip-keyed latent guide's blend per slot (avd_clip_guide_slots_f32; contract in include/avdiff_hip.h, "clip-keyed latent
+    guide"): ``z`` is a batch [B,C,T,H,W] (video) or [B,Ca,F] (audio), ``tau`` int [B, S]; sliding position l of sample b is in slot
+    min(l // slot_len, S - 1) and sits on clip position p = (first + max(*cursor, 0) + b*stride) * slot_len + l (signed, not wrapped).
+    Where 0 <= p < P the result is blend(mask[:, p], q_p(tau[b, s]), z) with q_p = sqrt(a) known[:, p] + sqrt(1 - a) n_k(p), n_k the
+    canvas-keyed known noise of ``seed`` at position p; elsewhere, and in every slot whose tau is ``SLOT_LEAVE``, it is ``z`` bit for
+    bit.  ``mask`` None = 1 everywhere; ``everywhere`` reads the mask as 1 on every in-canvas position (SDEdit's start).  ``stride``
+    None = S.  ``out``: a contiguous float32 tensor of z's shape to write — ``z`` itself for an in-place call, which touches only the
+    slots that are not left — None allocates one."""
+    known = _clip_canvas(known, "known")
+    z = L.dev_f32(z, "z")
+    shape = tuple(z.shape)
+    outer, L_, inner = window_dims(shape)
+    tau = torch.as_tensor(tau)
+    if tau.dim() != 2 or tau.shape[0] != shape[0] or tau.is_floating_point() or tau.dtype == torch.bool:
+        raise ValueError(f"tau must be an int [B, S] table with B = {shape[0]}, got {tau.dtype} {tuple(tau.shape)}")
+    S = int(tau.shape[1])
+    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or S < 1 or S * slot_len > L_:
+        raise ValueError(f"S = {S} slots of slot_len {slot_len!r} must fit the sliding length {L_}")
+    m = None if mask is None else L.dev_f32(mask, "mask")
+    g = clip_guide(known, m, seed, first, S if stride is None else stride, cursor, shape)
+    if out is None:
+        out = torch.empty_like(z)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape and out.device == z.device):
+        raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on z's device")
+    tn = L.dev_i64(tau, z.device)
+    ab = alpha_bar if (alpha_bar.is_cuda and alpha_bar.dtype == torch.float32) else alpha_bar.to(z.device, torch.float32)
+    ab = ab.contiguous()
+    L.check(L.lib().avd_clip_guide_slots_f32(C.byref(g), tn.data_ptr(), ab.data_ptr(), ab.numel(), 1 if everywhere else 0, z.data_ptr(),
+                                             out.data_ptr(), shape[0], outer, L_, S, slot_len, inner, _st(z)))
+    return out
+
+
 def _slot_step_noise(eta: float, noise: Optional[Tensor], x_t: Tensor, what: str) -> Optional[Tensor]:
     """the explicit noise of the slot mirrors: required when eta > 0 (``slot_noise`` gives the fused step's normals), not read at 0"""
     if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not eta >= 0:

@@ -366,6 +366,8 @@ class DenoiseEngine:
         self._guide: Optional[L.LatentGuide] = None
         self._guide_sig = None       # what a captured graph holds of the guide by value: pointers, stride, seed, offset, keying, hop
         self._guide_hop: Optional[int] = None      # the hop of a canvas-keyed guide (None: keyed per sample)
+        # clip-keyed latent guide (set_clip_guide): (known canvas, mask canvas or None, seed), a state of its own beside set_known's
+        self._clip = None
         # window consensus (set_window_consensus): the hop (None = off) and the [L] weight table at a fixed address
         self._cons_hop: Optional[int] = None
         self._cons_w: Optional[torch.Tensor] = None
@@ -563,6 +565,44 @@ class DenoiseEngine:
         self._guide = None
         self._touch_guide()
 
+    # ---- clip-keyed latent guide: a known clean clip canvas that ``step_slots`` holds every slot to, by the clip position it holds ----
+    def set_clip_guide(self, known_canvas: torch.Tensor, mask: Optional[torch.Tensor] = None, *, guide_seed: int = 0) -> None:
+        """Guide ``step_slots`` by a clean clip canvas (extension; include/avdiff_hip.h, "clip-keyed latent guide"):
+        ``known_canvas`` [C, P, H, W] (video target) or [Ca, P] (audio target) is the whole clip along the sliding axis, ``mask`` None
+        (1 everywhere) or values in [0, 1] broadcastable to the canvas (``canvas_frame_mask`` gives one): after every stepping slot's
+        update the slot is blended, by the clip positions it holds (``step_slots``'s ``clip_first``, required while the guide is set),
+        with the known canvas forward-noised to the slot's own t_prev — 1 keeps the clip, 0 leaves the trajectory free, positions
+        outside the canvas are unguided.  The known noise is keyed by ``guide_seed`` and clip position (the stream of
+        ``set_known(keying="canvas")``).  Both canvases are copied into engine-owned buffers.  It is a state of its own: ``set_known``
+        stays the guide of ``step`` / ``run``, which refuse a clip guide, as do ``fifo_open`` and ``fifo_lookahead``."""
+        Fn.noise_key(guide_seed, 0)
+        want = self.latent_shape[1:2] + self.latent_shape[3:]
+        k = torch.as_tensor(known_canvas)
+        if k.dim() != len(self.latent_shape) - 1 or tuple(k.shape[:1]) + tuple(k.shape[2:]) != want or k.shape[1] < 1:
+            raise ValueError(f"known canvas shape {tuple(k.shape)} must be {want[:1] + ('P',) + want[1:]}: the engine's latent without "
+                             "its batch axis, any P >= 1 along the sliding axis")
+        if not k.is_floating_point():
+            raise TypeError(f"known canvas must be a float tensor, got {k.dtype}")
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask).to(torch.float32)
+            try:
+                m = m.expand(tuple(k.shape))
+            except RuntimeError:
+                raise ValueError(f"mask shape {tuple(m.shape)} does not broadcast to the known canvas's {tuple(k.shape)}") from None
+            if not bool(((m >= 0) & (m <= 1)).all()):
+                raise ValueError("mask values must lie in [0, 1]")
+            m = m.to(self.device).contiguous()
+        self._clip = (k.to(self.device, torch.float32).contiguous().clone(), m, guide_seed)
+
+    def clear_clip_guide(self) -> None:
+        """Back to the unguided ``step_slots``."""
+        self._clip = None
+
+    def _clip_refusal(self, what: str, why: str) -> None:
+        if self._clip is not None:
+            raise ValueError(f"{what} takes no clip guide ({why}): clear_clip_guide() first")
+
     def _touch_guide(self) -> None:
         g = self._guide
         sig = None if g is None else (g.known, g.mask, g.mask_batch_stride, g.key.seed, g.key.sample_offset, self._guide_hop)
@@ -746,6 +786,7 @@ class DenoiseEngine:
         says which kind it wants (``run`` does, from the host copy of the schedule)."""
         if self.Xp is None:
             raise RuntimeError("call set_prompt() first")
+        self._clip_refusal("step", "a clip guide is keyed by the clip positions of step_slots' slots; a per-sample step is guided by set_known")
         z = L.dev_f32(z, "z")
         if tuple(z.shape) != self.latent_shape:
             raise ValueError(f"latent shape {tuple(z.shape)} != engine shape {self.latent_shape}")
@@ -861,15 +902,21 @@ class DenoiseEngine:
         ``clip_cursor`` (one int32 in device memory, or None) is read at every launch and added, clamped at 0, to ``clip_first``, so a
         captured step follows a moving queue.  A held slot draws nothing.  Without ``clip_first`` an eta > 0 engine is refused, and
         on an eta == 0 engine the three arguments change nothing: the same launches, the same bits.
-        Scope: the scalar guidance; a latent guide, a CFG control, a window consensus, temb_mode "add" and overlapping audio chunks
+        Under ``set_clip_guide`` (avd_denoise_step_slots_guided_f32; "clip-keyed latent guide") ``clip_first`` is required at any eta:
+        every stepping slot ends in the blend with the known clip canvas at the clip positions it holds, forward-noised to the slot's
+        own t_prev; a held slot stays ``z`` and ``x0_hist`` keeps the model's x0.
+        Scope: the scalar guidance; a per-sample latent guide (``set_known``), a CFG control, a window consensus, temb_mode "add" and overlapping audio chunks
         are refused before anything is launched, as is ``t_last`` on a "ddim" engine; no unseeded or explicit noise."""
         if self.Xp is None:
             raise RuntimeError("call set_prompt() first")
         self._slot_refusals(t_last is not None, clip_first)
         S = self.slots
-        key = None
+        key = guide = None
         if self.eta > 0:      # _slot_refusals has asked for clip_first and noise_seed
             key = Fn.slot_key(self.noise_seed, clip_first, S if clip_stride is None else clip_stride, clip_cursor, self.device)
+        if self._clip is not None:      # _slot_refusals has asked for clip_first; the guide shares the key's geometry
+            guide = Fn.clip_guide(self._clip[0], self._clip[1], self._clip[2], clip_first, S if clip_stride is None else clip_stride,
+                                  clip_cursor, self.latent_shape)
         z = L.dev_f32(z, "z")
         if tuple(z.shape) != self.latent_shape:
             raise ValueError(f"latent shape {tuple(z.shape)} != engine shape {self.latent_shape}")
@@ -887,7 +934,11 @@ class DenoiseEngine:
         self._last_cond_only = False
         head = (C.byref(self.desc), z.data_ptr(), self.Xp.data_ptr())
         tail = (out.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device))
-        if key is not None:
+        if guide is not None:
+            L.check(L.lib().avd_denoise_step_slots_guided_f32(head[0], None if key is None else C.byref(key), C.byref(guide),
+                                                              tl[0].data_ptr() if tl else None, self.x0_hist.data_ptr() if tl else None,
+                                                              *head[1:], tn.data_ptr(), tp.data_ptr(), S, *tail))
+        elif key is not None:
             L.check(L.lib().avd_denoise_step_slots_seeded_f32(head[0], C.byref(key), tl[0].data_ptr() if tl else None,
                                                               self.x0_hist.data_ptr() if tl else None, *head[1:], tn.data_ptr(),
                                                               tp.data_ptr(), S, *tail))
@@ -902,6 +953,9 @@ class DenoiseEngine:
         """what ``step_slots`` refuses of the engine's state, before anything is launched (``fifo_open`` asks the same before it
         allocates, so a graph-replayed queue refuses what the eager one does, in the same words, before any capture).
         ``clip_first``: as ``step_slots`` takes it; an eta > 0 engine steps only with it and a ``noise_seed``"""
+        if self._clip is not None and clip_first is None:
+            raise ValueError("step_slots under a clip guide needs clip_first, at any eta: the guide reads the clip canvas at the clip "
+                             "positions the slots hold")
         if self.eta > 0 and clip_first is None:
             raise ValueError("step_slots needs eta == 0, or clip_first on an engine with noise_seed: slots at different timesteps draw "
                              "their eta > 0 noise by the clip position they hold (unkeyed noise is out of scope)")
@@ -955,6 +1009,8 @@ class DenoiseEngine:
         duplicates, which takes no ``c`` / ``t`` / ``seed``).  At ``shift=1`` ``seed`` None is the engine's ``noise_seed``.  Solver
         "dpmpp_2m": as in ``fifo_shift`` the same launch moves the history into the engine's second buffer, which becomes ``x0_hist``,
         and a new graph generation starts — at either ``shift``, the launch being out of place."""
+        self._clip_refusal("fifo_lookahead", "the duplicated slots of overlapping windows are refreshed from their owner copies, and the guide's "
+                           "tail pass has no lookahead form yet")
         if shift == 1:
             seed = self.noise_seed if seed is None else seed
             if seed is None:
@@ -983,6 +1039,7 @@ class DenoiseEngine:
         On an eta > 0 engine with a ``noise_seed`` the queue is stochastic: its steps pass ``clip_first=0, clip_cursor=q.m`` (m is 0
         through the ramp), the step noise keyed by ``engine.noise_seed``; ``noise_seed`` here seeds the start and the entering noise.
         The queue holds ``noise_seed``, c0 = n, ``n_slots``, the hops and every address: a captured pair is good for this queue only."""
+        self._clip_refusal("fifo_open", "the replayed queue's chain of launches has no guided tail pass: the guided queue runs eagerly")
         B, S, sl = self.embed.B, self.slots, self.slot_len
         ramp_now, ramp_prev, steady_now, steady_prev = su.fifo_plan(sched, S)
         n = ramp_now.shape[0] + 1
@@ -1212,6 +1269,7 @@ class DenoiseEngine:
         One loop runs every schedule (schedule_utils.trajectory_segments; a plain schedule is one CFG segment).  A captured pair steps
         cur -> other -> cur between the two latent buffers it was captured on, so it is replayed only while the trajectory sits in
         its source buffer; a single eager step puts it there.  A renoise pair works in place in ``cur`` and swaps nothing."""
+        self._clip_refusal("run", "a clip guide is keyed by the clip positions of step_slots' slots; a trajectory is guided by set_known")
         self.check_schedule(sched)
         segs = su.trajectory_segments(sched, self.guidance_interval)
         graphable = self.eta == 0 or self._key is not None

@@ -221,7 +221,9 @@ def fifo_prompt_len(engine: DenoiseEngine, prompt_canvas: torch.Tensor) -> int:
 
 @torch.no_grad()
 def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop: int, sched, n_slots: int, noise_seed: int,
-                 graph: Optional[bool] = False, lookahead: int = 0, context: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 graph: Optional[bool] = False, lookahead: int = 0, context: Optional[torch.Tensor] = None,
+                 init_canvas: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, guide_seed: int = 0,
+                 guide_start: str = "noise") -> torch.Tensor:
     """FIFO diagonal denoising (FIFO-Diffusion, Kim et al. 2024, with latent partitioning): a clip of ``n_slots`` slots of
     ``engine.slot_len`` latent positions, denoised in a queue whose slots sit at different noise levels.  Returns the finished latent
     canvas [C, n_slots * slot_len, H, W] (video target) or [Ca, n_slots * slot_len] (audio target).
@@ -268,7 +270,18 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     a factor S / h, 2 at ctx = S / 2.  Eager only: ``graph=True`` is refused before anything is allocated, None runs eagerly.
     ``context`` (with ``lookahead`` only): the clean latent of the ctx slots before the clip, [C, ctx * slot_len, H, W] (video) or
     [Ca, ctx * slot_len] (audio).  It fills the context slots at the start, labelled clean (the "clean" plan): the clip continues an
-    existing one.  The prompt under a supplied context is zeros.  ``lookahead=0`` is the queue above, launch for launch."""
+    existing one.  The prompt under a supplied context is zeros.  ``lookahead=0`` is the queue above, launch for launch.
+    ``init_canvas`` (the plain eager queue, both solvers, eta == 0 and eta > 0) guides the clip by a clean latent canvas [C, P, H, W]
+    / [Ca, P] (include/avdiff_hip.h, "clip-keyed latent guide"): long-form inpainting, outpainting and SDEdit.  ``mask``: None = 1
+    everywhere, or values in [0, 1] broadcastable to the canvas (``sampler.canvas_frame_mask`` gives one): 1 keeps the canvas, 0 is
+    generated, clip positions past P are unguided.  After the start noise is drawn one ``functional.clip_guide_slots`` call puts every
+    slot on the forward path q(s_0) of its clip positions, after every shift one in-place call does so for the entering tail slot
+    alone, and every ``step_slots`` runs under ``engine.set_clip_guide`` at the clip slot then at queue slot 0 — so a held region
+    leaves the queue equal to the canvas bit for bit.  The known noise is keyed by ``guide_seed`` and clip position, the stream of
+    ``stream_generate``'s canvas-keyed guide.  ``guide_start``: "noise" starts the unmasked positions from noise; "init" (SDEdit)
+    starts every in-canvas position from q(s_0) of the canvas — pass the truncated schedule
+    (``schedule_utils.truncate_schedule``), whose length sets the queue.  The engine's clip guide is set for the call and cleared
+    after it.  ``graph=True`` or ``lookahead > 0`` with ``init_canvas`` raises ValueError before anything is allocated."""
     if not isinstance(engine, DenoiseEngine):
         raise TypeError("fifo_denoise drives a DenoiseEngine")
     if isinstance(n_slots, bool) or not isinstance(n_slots, int) or n_slots < 1:
@@ -279,6 +292,18 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
         raise TypeError(f"graph must be True, False or None, got {graph!r}")
     if isinstance(lookahead, bool) or not isinstance(lookahead, int) or not 0 <= lookahead < engine.slots:
         raise ValueError(f"lookahead must be an int in [0, S = {engine.slots}): the context slots of a window of S, got {lookahead!r}")
+    if guide_start not in ("noise", "init"):
+        raise ValueError(f"guide_start must be 'noise' or 'init', got {guide_start!r}")
+    if init_canvas is None and (mask is not None or guide_start != "noise"):
+        raise ValueError("mask and guide_start belong to the clip guide: pass init_canvas")
+    if init_canvas is not None:
+        if graph:
+            raise ValueError("fifo_denoise(init_canvas=...) runs eagerly: the replayed queue has no guided tail pass, graph=True is refused")
+        if lookahead:
+            raise ValueError("fifo_denoise(init_canvas=...) drives the plain queue: the lookahead queue takes no clip guide, lookahead > 0 "
+                             "is refused")
+        Fn.noise_key(guide_seed, 0)
+        graph = False      # None follows the row rule only without a guide
     if lookahead:
         if graph:
             raise ValueError("fifo_denoise(lookahead > 0) runs eagerly: the lookahead queue has no device cursors, graph=True is refused")
@@ -302,6 +327,26 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
         graph = 2 * B * engine.N < engine.GRAPH_BELOW_ROWS
     if graph:
         return _fifo_denoise_graph(engine, engine.fifo_open(pc, prompt_hop, Lp, sched, n_slots, noise_seed))
+    if init_canvas is not None:
+        engine.set_clip_guide(init_canvas, mask, guide_seed=guide_seed)
+    try:
+        return _fifo_denoise_eager(engine, pc, prompt_hop, Lp, sched, n_slots, noise_seed, guide_start == "init")
+    finally:
+        if init_canvas is not None:
+            engine.clear_clip_guide()
+
+
+def _fifo_denoise_eager(engine: DenoiseEngine, pc: torch.Tensor, prompt_hop: int, Lp: int, sched, n_slots: int, noise_seed: int,
+                        everywhere: bool) -> torch.Tensor:
+    """``fifo_denoise``'s eager loop over the plain queue; under ``engine.set_clip_guide`` the guided one (the contract is in
+    ``fifo_denoise``): the start and every entering tail slot go through ``functional.clip_guide_slots`` at s_0, the steps are keyed by
+    the clip slot at queue slot 0 at any eta."""
+    B, S, sl = engine.embed.B, engine.slots, engine.slot_len
+    ramp_now, ramp_prev, steady_now, steady_prev = su.fifo_plan(sched, S)
+    n = ramp_now.shape[0] + 1
+    outer, L_, _ = Fn.window_dims(engine.latent_shape)
+    s0 = int(torch.as_tensor(sched).reshape(-1)[0])
+    dev = engine.device
     tabs = [t.to(dev) for t in (ramp_now, ramp_prev, steady_now, steady_prev)]
     multistep = engine.solver == "dpmpp_2m"
     ramp_last, steady_last = (t.to(dev) for t in su.fifo_plan_last(sched, S)) if multistep else (None, None)
@@ -309,6 +354,14 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     other = torch.empty_like(z)
     engine.set_prompt(fifo_prompt_windows(pc, 0, B, S, prompt_hop, Lp))
     first, stride = _fifo_clip_keying(engine, S, 0)
+    clip = engine._clip
+    if clip is not None:      # the guide reads clip positions at any eta: slot 0 of sample 0 holds clip slot m
+        first, stride = (lambda m: m), S
+        ab = engine.alpha_bar.to(dev, torch.float32)
+        guide = dict(slot_len=sl, seed=clip[2], everywhere=everywhere)
+        tail = torch.full((B, S), Fn.SLOT_LEAVE, dtype=torch.long, device=dev)
+        tail[B - 1, S - 1] = s0
+        Fn.clip_guide_slots(clip[0], torch.full((B, S), s0, dtype=torch.long, device=dev), ab, z, clip[1], first=0, out=z, **guide)
     for r in range(n - 1):
         z, other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other, t_last=ramp_last[r] if multistep else None, clip_first=first(0),
                                      clip_stride=stride), z
@@ -318,6 +371,8 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
             engine.set_prompt(fifo_prompt_windows(pc, m, B, S, prompt_hop, Lp))
         other = engine.step_slots(z, tabs[2], tabs[3], out=other, t_last=steady_last, clip_first=first(m), clip_stride=stride)
         z, popped = engine.fifo_shift(other, n + m, s0, seed=noise_seed)
+        if clip is not None:      # the entering tail slot alone: clip slot n + m, now that clip slot m + 1 is at queue slot 0
+            Fn.clip_guide_slots(clip[0], tail, ab, z, clip[1], first=m + 1, out=z, **guide)
         canvas[:, m * sl:(m + 1) * sl] = popped
     return canvas
 

@@ -25,10 +25,15 @@
               2-layer steps, between two runs of the eta = 0 slot step, beside the canvas-keyed and the eta = 0 per-sample steps;
               --e2e: fifo_denoise per finished slot, eager and replayed, the eta = 0 and the eta > 0 engine's calls interleaved
 
+  --guide     the clip-keyed latent guide ("clip-keyed latent guide"), both solvers at eta 0 and eta > 0 in one session.  --kernels: the
+              guided fused slot update inside whole 2-layer steps between two runs of the unguided slot update of the same engine, and
+              the stand-alone pass (all slots, and the entering tail slot alone, in place) beside the queue shift; --e2e:
+              fifo_denoise(init_canvas=) per finished slot beside the unguided queue, eager, the calls interleaved
+
 Prints plain text: the records are profiles/fifo_kernels.txt and profiles/fifo_e2e.txt (ddim), profiles/fifo_dpm_kernels.txt and
 profiles/fifo_dpm_e2e.txt (both solvers in one session), profiles/fifo_graph_e2e.txt (--e2e with and without --graph),
 profiles/fifo_lookahead_kernels.txt and profiles/fifo_lookahead_e2e.txt (--lookahead 3), profiles/fifo_stochastic_kernels.txt and
-profiles/fifo_stochastic_e2e.txt (--stochastic)."""
+profiles/fifo_stochastic_e2e.txt (--stochastic), profiles/fifo_guide_kernels.txt (--guide)."""
 import argparse
 import ctypes as C
 import statistics
@@ -59,6 +64,7 @@ ap.add_argument("--graph", action="store_true", help="--e2e: replay the iteratio
 ap.add_argument("--steps", type=int, default=None, help="--e2e: steps of the schedule = slots of the queue (default 48, dpmpp_2m: 18)")
 ap.add_argument("--lookahead", type=int, default=0, metavar="CTX", help="FIFO lookahead: CTX context slots per window of S = 6")
 ap.add_argument("--stochastic", action="store_true", help="eta > 0 with clip-keyed slot noise beside eta = 0, both solvers")
+ap.add_argument("--guide", action="store_true", help="the clip-keyed latent guide beside the unguided slot update and queue")
 args = ap.parse_args()
 if not 0 <= args.lookahead < 6:
     raise SystemExit("--lookahead CTX must lie in [0, 6)")
@@ -104,6 +110,107 @@ def report_shift(res, cases):
 
 
 STOCHASTIC = (("ddim", 0.5, 48), ("dpmpp_2m", 1.0, 18))      # solver, eta, steps: the two queues of profiles/fifo_dpm_e2e.txt
+
+if args.guide and args.kernels:
+    B, S, sl = 32, 6, 2
+    g = torch.Generator().manual_seed(0)
+    z = torch.randn(B, 8, 12, 32, 32, generator=g).to(dev)
+    prompt = torch.randn(B, 8, 150, generator=g).to(dev)
+    out = torch.empty_like(z)
+    known = torch.randn(8, B * 12, 32, 32, generator=g).to(dev)      # the clip under the whole batch: two more 25 MB streams
+    mask = torch.rand(8, B * 12, 32, 32, generator=g).to(dev)
+    PLAIN, GUIDED = "cfg_unpatch_ddim_kernel", "cfg_unpatch_ddim_kernel<clip guide>"
+    rows = []
+    for solver, eta, n in (("ddim", 0.0, 48), ("ddim", 0.5, 48), ("dpmpp_2m", 0.0, 18), ("dpmpp_2m", 1.0, 18)):
+        dpm = solver == "dpmpp_2m"
+        sched = su.make_sampling_schedule(1000, n)
+        eng = build(2, B, solver=solver, eta=eta, **({"noise_seed": 11} if eta else {}))
+        eng.set_prompt(prompt)
+        if dpm:
+            eng.x0_hist.copy_(torch.randn(B, 8, 12, 32, 32, generator=g))
+        i = (torch.arange(B * S) % (n - 2)).view(B, S) + 1      # the diagonal: none held, none final
+        tlS, tnS, tpS = (sched[i + d].to(dev).contiguous() for d in (-1, 0, 1))
+        last = dict(t_last=tlS) if dpm else {}
+
+        def step(guided, eng=eng, last=last, tnS=tnS, tpS=tpS):
+            if guided:      # "mask": a fractional mask canvas, one more stream than "no mask" (1 everywhere)
+                eng.set_clip_guide(known, mask if guided == "mask" else None, guide_seed=3)
+            else:
+                eng.clear_clip_guide()
+            return lambda: eng.step_slots(z, tnS, tpS, out=out, clip_first=0, **last)
+
+        name = f"{solver} eta = {eta}"
+        rows += [(f"{name}, unguided (a)", PLAIN, step, False), (f"{name}, clip guide", GUIDED, step, "mask"),
+                 (f"{name}, clip guide, no mask", GUIDED, step, "no mask"), (f"{name}, unguided (b)", PLAIN, step, False)]
+    zq = torch.randn(8, 8, 12, 32, 32, generator=g).to(dev)          # the e2e queue at n = 48: B = 8
+    every = {b: torch.full((b, S), 999, dtype=torch.long, device=dev) for b in (B, 8)}
+    tail = {b: torch.full((b, S), Fn.SLOT_LEAVE, dtype=torch.long, device=dev) for b in (B, 8)}
+    for b in (B, 8):
+        tail[b][b - 1, S - 1] = 999
+    kw = dict(slot_len=sl, seed=3)
+    PASS = "clip_guide_slots_kernel<4>"
+    for zz in (z, zq):
+        b = zz.shape[0]
+        rows += [(f"fifo_shift B={b}", "fifo_shift_kernel<4>", lambda g_, zz=zz, b=b: (lambda: Fn.fifo_shift(zz, b * S, 7, 999, sl)), None),
+                 (f"guide pass, all slots B={b}", PASS, lambda g_, zz=zz, b=b: (lambda: Fn.clip_guide_slots(known, every[b], ABAR_D, zz, mask,
+                                                                                                          out=out[:b], **kw)), None),
+                 (f"guide pass, tail slot in place B={b}", PASS, lambda g_, zz=zz, b=b: (lambda: Fn.clip_guide_slots(
+                     known, tail[b], ABAR_D, zz, mask, first=1, out=zz, **kw)), None)]
+    ABAR_D = ABAR.to(dev)
+    for _, _, mk, guided in rows:
+        fn = mk(guided)
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    res = {name: [] for name, _, _, _ in rows}
+    for _ in range(args.rounds):
+        for name, tag, mk, guided in rows:
+            res[name].append(per_launch_us(tag, mk(guided), args.launches))
+    print(f"C3 geometry, B = {B}: the fused CFG + un-patch + solver slot update inside whole steps (2 layers), unguided (tag {PLAIN}) and "
+          f"under a clip-keyed latent guide with a fractional mask (tag {GUIDED}); the stand-alone guide pass beside the queue shift: "
+          f"{args.rounds} interleaved rounds of {args.launches} launches, microseconds per launch (launch events)")
+    for name, _, _, _ in rows:
+        v = res[name]
+        print(f"  {name:40s} " + " ".join(f"{x:8.2f}" for x in v) + f"   median {statistics.median(v):8.2f}")
+    sys.exit(0)
+
+if args.guide and args.e2e:
+    S, K = 6, args.slots_out
+    g = torch.Generator().manual_seed(1)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    print(f"fifo_denoise unguided and with init_canvas (clip-keyed latent guide, frames kept on a third of the clip), S = {S} (C3 latent, "
+          f"8 layers, bf16x3, eager), {args.rounds} rounds, the calls interleaved, {K} and {2 * K} slots out; milliseconds")
+    for solver, eta, n in (("ddim", 0.0, 48), ("dpmpp_2m", 0.0, 18)):
+        sched = su.make_sampling_schedule(1000, n)
+        canvas_p = torch.randn(8, 25 * (n + 2 * K) + 148, generator=g).to(dev)
+        eng = build(8, n // S, solver=solver)
+        known = torch.randn(8, 2 * K * 2, 32, 32, generator=g).to(dev)
+        mask = A.sampler.canvas_frame_mask(known.shape, 0, known.shape[1] // 3)
+        kinds = [("unguided", {}), ("init_canvas", dict(init_canvas=known, mask=mask, guide_seed=3))]
+        for _, kw in kinds:
+            A.fifo_denoise(eng, canvas_p, 25, sched, 4, 5, **kw)      # warm-up
+        ts_ = {(name, K_): [] for name, _ in kinds for K_ in (K, 2 * K)}
+        for _ in range(args.rounds):
+            for K_ in (K, 2 * K):
+                for name, kw in kinds:
+                    ts_[name, K_].append(timed(lambda: A.fifo_denoise(eng, canvas_p, 25, sched, K_, 5, **kw)))
+        per = {}
+        for name, _ in kinds:
+            whole = {K_: statistics.median(ts_[name, K_]) for K_ in (K, 2 * K)}
+            per[name] = (whole[2 * K] - whole[K]) / K
+            print(f"  {solver:8s} n = {n}, B = {n // S}, {name:11s}: " +
+                  "; ".join(f"{K_} out " + " ".join(f"{t * 1e3:7.1f}" for t in ts_[name, K_]) for K_ in (K, 2 * K)) +
+                  f"; per finished slot {per[name] * 1e3:.3f}, ramp and start {(whole[K] - K * per[name]) * 1e3:.1f}")
+        a, b = (per[name] for name, _ in kinds)
+        print(f"  {'':8s} per finished slot, guided against unguided: {(b - a) * 1e3:+.3f} ms (x {b / a:.3f})")
+    sys.exit(0)
 
 if args.stochastic and args.kernels:
     B, S = 32, 6
