@@ -269,7 +269,8 @@ int avd_canvas_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* 
  * there when its whole sample runs at the slot's pair.  Attention and the GEMMs are the per-sample step's, launch for launch.
  * Scope, everything else is refused before any launch (AVD_EINVAL): DDIM or DPM-Solver++(2M) (below) at eta == 0 (no noise, no key) or,
  * through the *_slots_seeded entries, at eta > 0 with a slot key ("clip-keyed slot noise" below; no unseeded or explicit noise), the
- * CFG step with the scalar guidance, the concat embedding (temb_add == 0), no latent guide, CFG control or canvas keying.  Both targets,
+ * CFG step with the scalar guidance (or, through the *_slots_cfg entries, a "slot CFG control" below), the concat embedding (temb_add ==
+ * 0), no latent guide, per-sample CFG control or canvas keying.  Both targets,
  * every matmul / attention mode, both stream layouts (split_streams) and the null half's short layout are taken as by the plain step.
  * `slots` must equal the geometry's S.  Samplers whose positions sit at different noise levels (FIFO-Diffusion, rolling diffusion,
  * continuation from held clean context) are loops over avd_denoise_step_slots_f32. */
@@ -396,6 +397,72 @@ int avd_cfg_untoken_ddim_audio_slots_guided_f32(const float* eps2, const float* 
                                                 const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, float eta,
                                                 const avd_slot_key* key, const avd_clip_guide* guide, int slots, float* x0_hist,
                                                 float* z_out, int B, int Ca, int F, int len, int stride, avd_stream_t stream);
+
+/* ---- slot CFG control: guidance by noise level, per-slot guidance rescale and per-slot APG for the slot entries (a public contract).
+ * The per-sample controls (avd_cfg_control, "adaptive projected guidance") do not carry over to slots: a sample of a queue holds S
+ * slots at S noise levels, so a std ratio or a norm cap over the sample mixes nearly clean and pure-noise positions, and what a user
+ * varies along a queue is the guidance along the NOISE LEVEL (Kynkaanniemi et al. 2024), which in a queue is the slot's t_now.  Here
+ * every coefficient belongs to one slot, and g and phi are looked up by the slot's level inside the kernels: no host tables per
+ * iteration, so the ramp, the replayed driver (rows chosen by a device cursor) and the lookahead queue (held duplicates) need nothing.
+ * Levels and coefficients.  For slot (b, s), tb = b*S + s, the level is i = min(max(t_now[tb], 0), T_train - 1);
+ *     g = guidance_t ? guidance_t[i] : the scalar guidance;        phi = rescale_t ? rescale_t[i] : 0.
+ * The combine is cfg_combine(cond, null, g) = null + g (cond - null) in fp32 without contraction, as today: a table whose entries all
+ * equal the scalar, with no rescale and no APG, gives the bits of the existing slot entries (eta == 0, seeded or guided).  A level
+ * table that is 1 outside an interval is the slot form of the guidance interval (a queue has no cond-only steps: some slot is always
+ * inside the interval).
+ * The elements of a slot.  Video: the tokens with t' = s, Ht*Wt*D contiguous values of the token layout; per_slot = C*p0*H*W.  Audio
+ * (stride == len only, as in "slot timesteps"): token s, per_slot = Ca*len; the uncovered tail f >= Na*len takes no part in the
+ * moments and its eps stays 0.  per_slot >= 2.
+ * Rescale (rescale_t set).  Steps 3 and 4 of avd_cfg_control with n = per_slot, c the slot's cond values and y its combined values:
+ * the fp64 moments run over chunks of 1024 elements in TOKEN order counted from the slot's first element, each chunk's partial is
+ * written with plain stores and the partials are summed in index order; s is rounded once to fp32 and is 1 when sigma_y == 0 or the
+ * result is not finite; r(e) is avd_cfg_control's, unchanged.
+ * APG (apg != 0; excludes rescale_t).  Items 1 and 3 to 5 of "adaptive projected guidance" per slot with beta = 0: d = c - u, the
+ * chunks are 1024 elements in the LATENT order of the slot alone ((c, t in slot, h, w) for video, (ch, j) for audio), r caps the
+ * SLOT's L2 norm of d: a threshold chosen for a whole sample of S slots corresponds to r / sqrt(S) per slot.  There is no momentum
+ * and no buffer: a slot's momentum would have to travel with it through the queue's shift as x0_hist does, which is not built.
+ * Partition rule.  At S == 1 the slot is the sample: both partitions, and therefore every coefficient and every output bit, are
+ * those of the per-sample controlled entries (avd_denoise_step_cfg_f32 / avd_denoise_step_apg_f32) with g_b = guidance_t[t_now[b]]
+ * and phi_b = rescale_t[t_now[b]] (audio: where the chunk covers the whole latent, F == len).
+ * Invariance.  A slot's coefficients are a pure function of the slot's eps tokens, its g and the slot geometry: the same whatever B
+ * and S are, whichever (b, s) holds the slot, whatever the other slots do, eager or replayed, under either split_streams setting.
+ * Held slots (t_prev == t_now) are z bit for bit: their statistics blocks return before they load anything, the finalize pass
+ * stores the neutral (1, 0, 0, 0) for them, and their tables and x0_hist elements are not read.
+ * Order within a stepping slot: combine -> rescale or APG -> the solver update (DDIM, seeded DDIM with the slot key, DPM-Solver++(2M)
+ * or its SDE form; x0_hist receives the x0 of the controlled eps) -> the clip guide's blend last.
+ * Scratch.  Needed when rescale_t or apg is set (a guidance table alone launches no statistics pass): avd_slot_cfg_stats_bytes(B, S,
+ * per_slot) bytes, 16-byte aligned; its last 16*B*S bytes hold per slot (s, g, phi, 0) after a rescale call, (s, k, w, g) after an
+ * APG call.
+ * Checked before any HIP call, in this order: AVD_EINVAL for a null cfg, apg together with rescale_t, r < 0 or NaN, eta_p outside
+ * [0, 1] or NaN, a missing or short scratch (B*S > 65535 and per_slot < 2 count as short); AVD_EUNSUPPORTED for a misaligned
+ * scratch; AVD_EINVAL for a scratch overlapping z, z_out, x0_hist or the eps tokens (the whole step: the workspace), and for
+ * everything the slot entries already check.  The kernels trust the device values: table entries that are NaN or outside their range
+ * are not detected there (DenoiseEngine.set_slot_cfg / schedule_utils.level_table check them before upload).
+ * Limits: no slot momentum; the per-sample avd_cfg_control / avd_apg_control stay refused under slot timesteps; overlapping audio
+ * chunks stay refused.  Quality is not measured here (no trained weights): the contract is the arithmetic. */
+typedef struct {
+    const float* guidance_t;   /* fp32 [T_train] on the device, or NULL = the scalar guidance */
+    const float* rescale_t;    /* fp32 [T_train] phi in [0, 1], or NULL = no rescale */
+    int32_t apg;               /* 1: adaptive projected guidance per slot (excludes rescale_t) */
+    float norm_threshold;      /* r >= 0, as avd_apg_control; read when apg */
+    float eta_parallel;        /* in [0, 1], as avd_apg_control; read when apg */
+    void* stats;               /* caller-owned scratch, needed when rescale_t or apg is set */
+    int64_t stats_bytes;       /* its size */
+} avd_slot_cfg;
+/* Bytes of the statistics scratch of B*slots slots of per_slot (>= 2) elements; -1 on bad arguments (B*slots outside [1, 65535]). */
+int64_t avd_slot_cfg_stats_bytes(int B, int slots, int64_t per_slot);
+/* The fused updates alone: avd_cfg_unpatch_ddim_slots_guided_f32 / avd_cfg_untoken_ddim_audio_slots_guided_f32 under the control.  key
+ * may be NULL at eta == 0, guide may be NULL (no clip guide); t_last / x0_hist both NULL or both set, as there. */
+int avd_cfg_unpatch_ddim_slots_cfg_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                       const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, float eta,
+                                       const avd_slot_key* key, const avd_clip_guide* guide, int slots, float* x0_hist, float* z_out,
+                                       int B, int C, int T, int H, int W, int t, int h, int w, const avd_slot_cfg* cfg,
+                                       avd_stream_t stream);
+int avd_cfg_untoken_ddim_audio_slots_cfg_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                             const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, float eta,
+                                             const avd_slot_key* key, const avd_clip_guide* guide, int slots, float* x0_hist,
+                                             float* z_out, int B, int Ca, int F, int len, int stride, const avd_slot_cfg* cfg,
+                                             avd_stream_t stream);
 
 /* ---- FIFO queue shift: the queue step of diagonal denoising (FIFO-Diffusion, Kim et al. 2024) in one out-of-place launch.
  * The batch z_in [B, outer, L, inner] ((outer, L, inner) as in "canvas-keyed noise") with L = slots*slot_len is read as a queue of
@@ -627,8 +694,8 @@ int avd_cfg_rescale_f32(const float* e_cond, const float* e_cfg, const float* ph
  *      the x0 of e; a latent guide's blend (avd_latent_guide) still comes last;
  *   7. scope: guidance rescale (a control whose rescale is set) together with APG is refused: its statistics would need the APG
  *      output.  A cond-only step does not apply APG and leaves the momentum buffer untouched.  Slot timesteps refuse it, as they
- *      refuse every CFG control.  The kernels trust the device values (guidance[b]); the by-value parameters are range-checked here
- *      (NaN refused) and again by DenoiseEngine / functional.apg_guidance.
+ *      refuse every per-sample CFG control: their form is "slot CFG control".  The kernels trust the device values (guidance[b]);
+ *      the by-value parameters are range-checked here (NaN refused) and again by DenoiseEngine / functional.apg_guidance.
  * Checked before any HIP call: the scratch's size (avd_apg_stats_bytes) and 16-byte alignment; momentum_buf 16-byte aligned, NULL
  * exactly when momentum == 0, and overlapping none of z, z_out, x0_hist, the scratch and the eps tokens (for the whole step: the
  * workspace); the scratch likewise.  What the effect on sample quality is at a given guidance scale is not measured here: that
@@ -945,6 +1012,15 @@ int avd_denoise_step_slots_seeded_f32(const avd_step_desc* s, const avd_slot_key
 int avd_denoise_step_slots_guided_f32(const avd_step_desc* s, const avd_slot_key* key, const avd_clip_guide* guide, const int64_t* t_last,
                                       float* x0_hist, const float* z, const float* Xp, const int64_t* t_now, const int64_t* t_prev,
                                       int slots, float* z_out, void* workspace, int64_t workspace_bytes, avd_stream_t stream);
+/* The whole step on slot timesteps under a slot CFG control (see "slot CFG control"): avd_denoise_step_slots_guided_f32 with the control
+ * added; key may be NULL at s->eta == 0, guide may be NULL.  The front end is avd_denoise_step_slots_f32's, launch for launch; the
+ * control (the workspace standing for the eps tokens in its overlap check), the guide and the key are checked before the model runs;
+ * the statistics pass of a rescale or APG control runs on the caller's stream right before the fused update.  Graph-capturable: the
+ * tables are read at their addresses at every launch. */
+int avd_denoise_step_slots_cfg_f32(const avd_step_desc* s, const avd_slot_cfg* cfg, const avd_slot_key* key, const avd_clip_guide* guide,
+                                   const int64_t* t_last, float* x0_hist, const float* z, const float* Xp, const int64_t* t_now,
+                                   const int64_t* t_prev, int slots, float* z_out, void* workspace, int64_t workspace_bytes,
+                                   avd_stream_t stream);
 /* As avd_denoise_step_f32, with the eta > 0 noise drawn inside the fused CFG + DDIM kernel from the seeded stream (avd_noise_key)
  * for samples key->sample_offset .. + B - 1 at t_now: no noise buffer, graph-capturable.  With s->eta == 0 it is the plain step. */
 int avd_denoise_step_seeded_f32(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp,

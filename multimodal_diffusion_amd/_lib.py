@@ -102,6 +102,13 @@ class ApgControl(C.Structure):
                 ("stats", C.c_void_p), ("stats_bytes", C.c_int64)]
 
 
+class SlotCfg(C.Structure):
+    """avd_slot_cfg: guidance and rescale tables by noise level (device [T_train] arrays, either may be NULL), per-slot APG and the
+    statistics scratch (contract in include/avdiff_hip.h, "slot CFG control").  Raw device pointers: keep the tensors alive."""
+    _fields_ = [("guidance_t", C.c_void_p), ("rescale_t", C.c_void_p), ("apg", C.c_int32), ("norm_threshold", C.c_float),
+                ("eta_parallel", C.c_float), ("stats", C.c_void_p), ("stats_bytes", C.c_int64)]
+
+
 class VaeDecodeDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("Cv", C.c_int), ("Tp", C.c_int), ("Hp", C.c_int), ("Wp", C.c_int),
                 ("T", C.c_int), ("H", C.c_int), ("W", C.c_int),
@@ -185,6 +192,13 @@ SIGNATURES = {
                                                          _P] + [_I] * 5 + [_P]),
     "avd_denoise_step_slots_guided_f32": (_I, [C.POINTER(StepDesc), C.POINTER(SlotKey), C.POINTER(ClipGuide), _P, _P, _P, _P, _P, _P, _I, _P,
                                                _P, _L, _P]),
+    "avd_slot_cfg_stats_bytes": (_L, [_I, _I, _L]),
+    "avd_cfg_unpatch_ddim_slots_cfg_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _F, C.POINTER(SlotKey), C.POINTER(ClipGuide), _I, _P, _P] +
+                                           [_I] * 8 + [C.POINTER(SlotCfg), _P]),
+    "avd_cfg_untoken_ddim_audio_slots_cfg_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _F, C.POINTER(SlotKey), C.POINTER(ClipGuide), _I, _P,
+                                                      _P] + [_I] * 5 + [C.POINTER(SlotCfg), _P]),
+    "avd_denoise_step_slots_cfg_f32": (_I, [C.POINTER(StepDesc), C.POINTER(SlotCfg), C.POINTER(SlotKey), C.POINTER(ClipGuide), _P, _P, _P,
+                                            _P, _P, _P, _I, _P, _P, _L, _P]),
     "avd_fifo_shift_hist_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _P, _P, _P, _P, _P, _I, _L, _I, _I, _L, _P]),
     "avd_fifo_lookahead_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _I, _P, _P, _P, _I, _L, _I, _I, _I, _L, _P]),
     "avd_fifo_lookahead_hist_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _I, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _L, _P]),

@@ -342,12 +342,14 @@ struct CanvasKey;
 struct SlotKey;
 // A ClipGuideState ends a slot pack ("clip-keyed latent guide"): behind the SlotTimes, and behind the SlotKey when there is one.
 struct ClipGuideState;
+// A SlotCfgState rides behind the SlotTimes alone ("slot CFG control"): after the SlotKey when there is one, before the ClipGuideState.
+struct SlotCfgState;
 template <bool SEEDED, class... X> struct PackOk {
     template <class T> static constexpr int n = PackHas<T, X...>::value ? 1 : 0;
     static constexpr bool value = sizeof...(X) == (SEEDED ? 1 : 0) + n<DpmState> + n<GuideState> + n<CanvasGuideState> + n<CfgState> +
-                                                      n<CondOnly> + n<SlotTimes> + n<ClipGuideState> &&
-                                  !(n<SlotTimes> && sizeof...(X) != 1 + n<DpmState> + n<SlotKey> + n<ClipGuideState>) &&
-                                  n<SlotKey> <= n<SlotTimes> && n<ClipGuideState> <= n<SlotTimes> &&
+                                                      n<CondOnly> + n<SlotTimes> + n<ClipGuideState> + n<SlotCfgState> &&
+                                  !(n<SlotTimes> && sizeof...(X) != 1 + n<DpmState> + n<SlotKey> + n<ClipGuideState> + n<SlotCfgState>) &&
+                                  n<SlotKey> <= n<SlotTimes> && n<ClipGuideState> <= n<SlotTimes> && n<SlotCfgState> <= n<SlotTimes> &&
                                   !(n<CfgState> && n<CondOnly>) && !(n<GuideState> && n<CanvasGuideState>) &&
                                   !(n<CanvasGuideState> && n<NoiseKey>) &&
                                   n<NoiseKey> + n<CanvasKey> + n<SlotKey> == (SEEDED ? 1 : 0);
@@ -2001,8 +2003,244 @@ int apg_guidance_f32(const float* e_cond, const float* e_null, const float* gvec
     return AVD_OK;
 }
 
+// ------------------------------------------------------------------ slot CFG control: guidance by noise level, per-slot rescale and APG
+// The contract is written out in include/avdiff_hip.h ("slot CFG control").  The slot forms of the two controls above: g and phi are
+// looked up by the slot's noise level t_now[b, s] in device tables, and the rescale / APG moments run over ONE slot's elements, not the
+// sample's (a sample of a queue holds S slots at S noise levels).  The statistics pass writes fp64 partials per CFG_CHUNK elements of a
+// slot, the finalize pass sums them in index order and stores four floats per slot; the fused kernels read them by tb = b * S + s
+// through a SlotCfgState in their trailing pack.  The arithmetic is cfg_combine / cfg_rescale / apg_d0 / apg_eps, as per sample.
+enum { SLOT_CFG_TABLE = 0, SLOT_CFG_RESCALE = 1, SLOT_CFG_APG = 2 };
+struct SlotCfgState {
+    const float* guidance_t;   // [T_train] or nullptr (the scalar); read by the TABLE mode and the statistics passes
+    const float* rescale_t;    // [T_train], set in the RESCALE mode
+    const float* coef;         // [B * S][4]: RESCALE (s, g, phi, 0), APG (s, k, w, g); nullptr in the TABLE mode
+    int mode;
+};
+struct SlotCfgCoef {
+    float g, phi, s, k, w;
+    bool apg;
+};
+// the level of the contract: the clamp of ddim_coef
+__device__ __forceinline__ int slot_level(const int64_t* t_now, int T_train, int tb) {
+    long long tn = t_now[tb];
+    if (tn < 0) tn = 0;
+    if (tn > T_train - 1) tn = T_train - 1;
+    return (int)tn;
+}
+// a stepping slot's coefficients (a held slot never gets here)
+__device__ __forceinline__ SlotCfgCoef slot_cfg_coef(const SlotCfgState& sc, const int64_t* t_now, int T_train, float guidance, int tb) {
+    SlotCfgCoef c{guidance, 0.f, 1.f, 0.f, 0.f, false};
+    if (sc.mode == SLOT_CFG_TABLE) {
+        if (sc.guidance_t) c.g = sc.guidance_t[slot_level(t_now, T_train, tb)];
+        return c;
+    }
+    const f32x4 v = *reinterpret_cast<const f32x4*>(sc.coef + (int64_t)tb * 4);
+    if (sc.mode == SLOT_CFG_APG) c = SlotCfgCoef{v[3], 0.f, v[0], v[1], v[2], true};
+    else c = SlotCfgCoef{v[1], v[2], v[0], 0.f, 0.f, false};
+    return c;
+}
+// the eps a slot steps on, per element: r(combine with g) or the APG value at beta == 0 (d = d0: no momentum, so it needs no exchange)
+__device__ __forceinline__ float slot_cfg_eps(const SlotCfgCoef& c, float ec, float en) {
+    if (c.apg) return apg_eps(ec, apg_d0(ec, en), c.w, c.k);
+    return cfg_rescale(cfg_combine(ec, en, c.g), c.phi, c.s);
+}
+
+static int64_t slot_cfg_coef_off(int64_t BS, int64_t per_slot) { return (BS * cfg_chunks(per_slot) * 32 + 15) & ~(int64_t)15; }
+int64_t slot_cfg_stats_bytes(int B, int slots, int64_t per_slot) {
+    if (B <= 0 || slots <= 0 || (int64_t)B * slots > 65535 || per_slot < 2 || per_slot >= ((int64_t)1 << 34)) return -1;
+    return slot_cfg_coef_off((int64_t)B * slots, per_slot) + (int64_t)B * slots * 16;
+}
+
+// the geometry of one slot inside its sample's token rows and latent
+struct SlotGeom {
+    int S;
+    int64_t per_slot;      // video C p0 H W, audio Ca len
+    int64_t tok_slot;      // floats of a slot's token rows: video Ht Wt D (contiguous), audio D (token s)
+    int64_t lat_slice;     // video: p0 H W, the slot's latent elements per channel (audio: unused)
+};
+
+// grid (chunks per slot, B * S): block (j, tb) writes part[(tb * chunks + j) * 4 + q], the sums over elements [j * 1024, (j + 1) * 1024)
+// of slot tb.  RESCALE: (sum c, sum c^2, sum y, sum y^2) in token order from the slot's first token element, y = cfg_combine(c, u, g).
+// APG: (sum d^2, sum d c, sum c^2, 0) in the slot's own latent order ((c, t in slot, h, w); audio (ch, j), which is its token order).
+// A held slot's blocks return before they load anything: its partials are never read.
+template <int SRC, bool APG>
+__global__ __launch_bounds__(256) void slot_cfg_stats_kernel(const float* __restrict__ a, const float* __restrict__ u, int64_t sstride,
+                                                             const int64_t* __restrict__ t_now, const int64_t* __restrict__ t_prev,
+                                                             const float* __restrict__ gtab, float guidance, int T_train,
+                                                             double* __restrict__ part, SlotGeom sg, Tube g) {
+#pragma clang fp contract(off)
+    __shared__ double red[4][4];
+    const int tb = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (t_now[tb] == t_prev[tb]) return;
+    const int b = tb / sg.S, s = tb % sg.S;
+    [[maybe_unused]] float gb = guidance;
+    if constexpr (!APG)
+        if (gtab) gb = gtab[slot_level(t_now, T_train, tb)];
+    const float* sa = a + (int64_t)b * sstride;
+    const float* su = u + (int64_t)b * sstride;
+    const int64_t el0 = (int64_t)blockIdx.x * CFG_CHUNK + threadIdx.x * 4;
+    f32x4 cv = {0.f, 0.f, 0.f, 0.f}, uv = {0.f, 0.f, 0.f, 0.f};
+    int nv = 0;                                        // valid elements of this lane (elements >= per_slot add nothing)
+    if (el0 < sg.per_slot) {
+        nv = sg.per_slot - el0 < 4 ? (int)(sg.per_slot - el0) : 4;
+        if constexpr (SRC == CFG_SRC_VIDEO) {          // per_slot % 4 == 0 (w % 4 == 0): a whole float4, 16-byte aligned
+            int64_t off = (int64_t)s * sg.tok_slot + el0;      // RESCALE: token order
+            if constexpr (APG) {                       // the slot's latent order -> the sample's latent float4 -> its token offset
+                const int64_t c = el0 / sg.lat_slice, r = el0 % sg.lat_slice;
+                off = tube_tok_off(g, ((c * g.T + (int64_t)s * g.t) * ((int64_t)g.H * g.W) + r) >> 2);
+            }
+            cv = *reinterpret_cast<const f32x4*>(sa + off);
+            uv = *reinterpret_cast<const f32x4*>(su + off);
+        } else {                                       // audio token s: (ch, j) in either order
+            for (int k = 0; k < nv; ++k) {
+                cv[k] = sa[(int64_t)s * sg.tok_slot + el0 + k];
+                uv[k] = su[(int64_t)s * sg.tok_slot + el0 + k];
+            }
+        }
+    }
+    double m[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < nv; ++k) {
+        const double c = (double)cv[k];
+        if constexpr (APG) {
+            const double d = (double)apg_d0(cv[k], uv[k]);
+            m[0] += d * d;
+            m[1] += d * c;
+            m[2] += c * c;
+        } else {
+            const double e = (double)cfg_combine(cv[k], uv[k], gb);
+            m[0] += c;
+            m[1] += c * c;
+            m[2] += e;
+            m[3] += e * e;
+        }
+    }
+    // fixed-order block sum, as cfg_stats_kernel: a butterfly within each wave, then waves 0..3
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        for (int o = 32; o > 0; o >>= 1) m[q] += __shfl_xor(m[q], o, 64);
+    if (lane == 0)
+        for (int q = 0; q < 4; ++q) red[wv][q] = m[q];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int q = threadIdx.x;
+        part[((int64_t)tb * gridDim.x + blockIdx.x) * 4 + q] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
+    }
+}
+
+// one lane per slot: the partials summed in index order, then the coefficients of the contract in one store.  A held slot gets the
+// neutral (1, 0, 0, 0) and reads neither its partials nor the tables.
+template <bool APG>
+__global__ void slot_cfg_finalize_kernel(const double* __restrict__ part, float* __restrict__ coef, const int64_t* __restrict__ t_now,
+                                         const int64_t* __restrict__ t_prev, const float* __restrict__ gtab,
+                                         const float* __restrict__ ptab, float guidance, int T_train, float r, float eta_p, int BS,
+                                         int chunks, int64_t per_slot) {
+#pragma clang fp contract(off)
+    const int tb = blockIdx.x * blockDim.x + threadIdx.x;
+    if (tb >= BS) return;
+    if (t_now[tb] == t_prev[tb]) {
+        *reinterpret_cast<f32x4*>(coef + (int64_t)tb * 4) = f32x4{1.f, 0.f, 0.f, 0.f};
+        return;
+    }
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    const double* p = part + (int64_t)tb * chunks * 4;
+    for (int j = 0; j < chunks; ++j)
+        for (int q = 0; q < 4; ++q) s[q] += p[(int64_t)j * 4 + q];
+    const int lv = slot_level(t_now, T_train, tb);
+    const float gb = gtab ? gtab[lv] : guidance;
+    if constexpr (APG) {      // item 4 of "adaptive projected guidance", the expressions of apg_finalize_kernel
+        float sb = 1.f, kb = 0.f;
+        if (r != 0.f && s[0] != 0.0) {
+            const float v = (float)fmin(1.0, (double)r / sqrt(s[0]));
+            if (isfinite(v)) sb = v;
+        }
+        if (s[2] != 0.0) {
+            const float v = (float)((1.0 - (double)eta_p) * s[1] / s[2]);
+            if (isfinite(v)) kb = v;
+        }
+        *reinterpret_cast<f32x4*>(coef + (int64_t)tb * 4) = f32x4{sb, kb, (gb - 1.0f) * sb, gb};
+    } else {                  // step 3 of avd_cfg_control, the expressions of cfg_stats_finalize_kernel
+        const double n = (double)per_slot;
+        const double sig_c = sqrt((s[1] - s[0] * s[0] / n) / (n - 1.0));
+        const double sig_y = sqrt((s[3] - s[2] * s[2] / n) / (n - 1.0));
+        float sc = (float)(sig_c / sig_y);
+        if (sig_y == 0.0 || !isfinite(sc)) sc = 1.f;
+        *reinterpret_cast<f32x4*>(coef + (int64_t)tb * 4) = f32x4{sc, gb, ptab ? ptab[lv] : 0.f, 0.f};
+    }
+}
+
+// The checks of a slot control, all before any HIP call, in the contract's order; fills the pack's state.  lat: the call's latent-sized
+// tensors (z, z_out, x0_hist; nullptr entries are skipped); eps: the bytes the predictions are read from.
+static int make_slot_cfg(const avd_slot_cfg* cfg, int B, int S, int64_t per_slot, int64_t per, std::initializer_list<const float*> lat,
+                         const void* eps, int64_t eps_bytes, SlotCfgState& sc) {
+    AVD_REQUIRE(cfg, AVD_EINVAL, "slot_cfg: null control");
+    AVD_REQUIRE(!(cfg->apg && cfg->rescale_t), AVD_EINVAL,
+                "slot_cfg: guidance rescale together with APG is refused (its statistics would need the APG output)");
+    if (cfg->apg) {
+        AVD_REQUIRE(cfg->norm_threshold >= 0.f && std::isfinite(cfg->norm_threshold), AVD_EINVAL,
+                    "slot_cfg: norm_threshold must be finite and >= 0 (0: no cap), got %g", (double)cfg->norm_threshold);
+        AVD_REQUIRE(cfg->eta_parallel >= 0.f && cfg->eta_parallel <= 1.f, AVD_EINVAL, "slot_cfg: eta_parallel must lie in [0, 1], got %g",
+                    (double)cfg->eta_parallel);
+    }
+    sc = SlotCfgState{cfg->guidance_t, cfg->rescale_t, nullptr, cfg->apg ? SLOT_CFG_APG : cfg->rescale_t ? SLOT_CFG_RESCALE : SLOT_CFG_TABLE};
+    if (sc.mode == SLOT_CFG_TABLE) return AVD_OK;
+    const int64_t need = slot_cfg_stats_bytes(B, S, per_slot);
+    AVD_REQUIRE(need > 0, AVD_EINVAL, "slot_cfg: bad dims (B %d * slots %d in [1, 65535], per_slot %lld must be >= 2)", B, S,
+                (long long)per_slot);
+    AVD_REQUIRE(cfg->stats, AVD_EINVAL, "slot_cfg: rescale and APG need the statistics scratch (stats)");
+    AVD_REQUIRE(cfg->stats_bytes >= need, AVD_EINVAL, "slot_cfg: stats holds %lld bytes, %lld needed (avd_slot_cfg_stats_bytes)",
+                (long long)cfg->stats_bytes, (long long)need);
+    AVD_REQUIRE(aligned16(cfg->stats), AVD_EUNSUPPORTED, "slot_cfg: stats must be 16-byte aligned");
+    for (const float* p : lat)
+        AVD_REQUIRE(!p || !overlaps_bytes(cfg->stats, need, p, (int64_t)B * per * 4), AVD_EINVAL,
+                    "slot_cfg: stats must not overlap z, z_out or x0_hist");
+    AVD_REQUIRE(!eps || !overlaps_bytes(cfg->stats, need, eps, eps_bytes), AVD_EINVAL, "slot_cfg: stats must not overlap the eps tokens");
+    sc.coef = reinterpret_cast<const float*>(static_cast<const char*>(cfg->stats) + slot_cfg_coef_off((int64_t)B * S, per_slot));
+    return AVD_OK;
+}
+
+// make_slot_cfg's checks alone: the composite step runs them before the model, with the whole workspace as the eps source
+int check_slot_cfg(const avd_slot_cfg* cfg, int B, int S, int64_t per_slot, int64_t per, const float* z, const float* out,
+                   const float* x0_hist, const void* eps, int64_t eps_bytes) {
+    SlotCfgState sc;
+    return make_slot_cfg(cfg, B, S, per_slot, per, {z, out, x0_hist}, eps, eps_bytes, sc);
+}
+
+// the statistics pass of a RESCALE or APG control: partials, then four floats per slot into the scratch's tail
+template <int SRC>
+static int run_slot_cfg_stats(const avd_slot_cfg* cfg, const SlotCfgState& sc, const float* a, const float* u, int64_t sstride,
+                              const int64_t* t_now, const int64_t* t_prev, float guidance, int T_train, int B, const SlotGeom& sg, Tube g,
+                              hipStream_t st) {
+    const int64_t chunks = cfg_chunks(sg.per_slot);
+    const int BS = B * sg.S;
+    double* part = static_cast<double*>(cfg->stats);
+    float* coef = const_cast<float*>(sc.coef);
+    static const int tag = prof_tag_id("slot_cfg_stats_kernel");
+    static const int tag_fin = prof_tag_id("slot_cfg_finalize_kernel");
+    const dim3 grid((unsigned)chunks, (unsigned)BS), fgrid((unsigned)((BS + 63) / 64));
+    {
+        ProfScope prof(tag, 8.0 * (double)BS * sg.per_slot, st);
+        if (sc.mode == SLOT_CFG_APG)
+            hipLaunchKernelGGL((slot_cfg_stats_kernel<SRC, true>), grid, dim3(256), 0, st, a, u, sstride, t_now, t_prev, sc.guidance_t,
+                               guidance, T_train, part, sg, g);
+        else
+            hipLaunchKernelGGL((slot_cfg_stats_kernel<SRC, false>), grid, dim3(256), 0, st, a, u, sstride, t_now, t_prev, sc.guidance_t,
+                               guidance, T_train, part, sg, g);
+    }
+    {
+        ProfScope prof(tag_fin, 32.0 * (double)BS * chunks, st);
+        if (sc.mode == SLOT_CFG_APG)
+            hipLaunchKernelGGL(slot_cfg_finalize_kernel<true>, fgrid, dim3(64), 0, st, part, coef, t_now, t_prev, sc.guidance_t,
+                               sc.rescale_t, guidance, T_train, cfg->norm_threshold, cfg->eta_parallel, BS, (int)chunks, sg.per_slot);
+        else
+            hipLaunchKernelGGL(slot_cfg_finalize_kernel<false>, fgrid, dim3(64), 0, st, part, coef, t_now, t_prev, sc.guidance_t,
+                               sc.rescale_t, guidance, T_train, 0.f, 0.f, BS, (int)chunks, sg.per_slot);
+    }
+    AVD_CHECK_LAUNCH("slot_cfg_stats");
+    return AVD_OK;
+}
+
 // ------------------------------------------------------------------ fused CFG + unpatch + DDIM (video target)
-int g_cfg_rows = 1;      // avd_tune_set "cfg_rows": 0 = the 16-bytes-per-lane gather form
+int g_cfg_rows = 1;     // avd_tune_set "cfg_rows": 0 = the 16-bytes-per-lane gather form
 // SEEDED: zn comes from the seeded normal stream (philox_normal4: one call is exactly this lane's float4) instead of `noise`.  The key
 // rides as a trailing parameter pack that is empty when !SEEDED, so the unseeded instantiations keep the kernel-argument layout (the
 // hidden arguments such as blockDim sit right behind the explicit ones) and compile to the same code as before the stream existed.
@@ -2042,6 +2280,13 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const f32x4 x = *reinterpret_cast<const f32x4*>(z + lat);
     [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
     if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
+    constexpr bool SCFG = PackHas<SlotCfgState, Key...>::value;
+    [[maybe_unused]] f32x4 es = {0.f, 0.f, 0.f, 0.f};      // the slot control's eps: coefficients by tb, not by b
+    if constexpr (SCFG) {
+        const SlotCfgCoef sf = slot_cfg_coef(pack_get<SlotCfgState>(nk...), t_now, T_train, guidance, tb);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) es[k] = slot_cfg_eps(sf, ec[k], en[k]);
+    }
     f32x4 zn = {0.f, 0.f, 0.f, 0.f};
     if constexpr (PackHas<SlotKey, Key...>::value) {      // the clip-keyed draw of a stepping slot: the (c, t) slice of the canvas-keyed draw
         const int64_t hw4 = ((int64_t)g.H * g.W) >> 2, r = e4 / hw4;
@@ -2076,14 +2321,17 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
         if (d.c_1 != 0.f) hist = *reinterpret_cast<const f32x4*>(ds.x0_hist + lat);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            x0[k] = ddim_x0(c, x[k], step_eps<CTL, COND>(apg, ea[k], ec[k], en[k], guidance, cc));
+            if constexpr (SCFG) x0[k] = ddim_x0(c, x[k], es[k]);
+            else x0[k] = ddim_x0(c, x[k], step_eps<CTL, COND>(apg, ea[k], ec[k], en[k], guidance, cc));
             o[k] = dpm_apply(d, x[k], x0[k], hist[k], zn[k], SEEDED);
         }
         *reinterpret_cast<f32x4*>(ds.x0_hist + lat) = x0;
     } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float e = step_eps<CTL, COND>(apg, ea[k], ec[k], en[k], guidance, cc);
+            float e;
+            if constexpr (SCFG) e = es[k];
+            else e = step_eps<CTL, COND>(apg, ea[k], ec[k], en[k], guidance, cc);
             o[k] = ddim_apply(c, x[k], e, zn[k]);
         }
     }
@@ -2136,6 +2384,10 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
     [[maybe_unused]] bool apg = false;      // block-uniform: the launch carries an APG part
     if constexpr (CTL) apg = pack_get<CfgState>(nk...).apg != nullptr;
+    constexpr bool SCFG = PackHas<SlotCfgState, Key...>::value;
+    [[maybe_unused]] SlotCfgCoef sf{guidance, 0.f, 1.f, 0.f, 0.f, false};      // the slot control: block-uniform, by tb (a held slot reads nothing)
+    if constexpr (SCFG)
+        if (!hold) sf = slot_cfg_coef(pack_get<SlotCfgState>(nk...), t_now, T_train, guidance, tb);
     for (int i = threadIdx.x; i < nf4; i += 256) {
         const f32x4 ec = *reinterpret_cast<const f32x4*>(tc + (int64_t)i * 4);
         [[maybe_unused]] f32x4 en = {0.f, 0.f, 0.f, 0.f};
@@ -2153,7 +2405,10 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         }
         f32x4 e;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) e[k] = cfg_eps<CTL, COND>(ec[k], en[k], guidance, cc);
+        for (int k = 0; k < 4; ++k) {
+            if constexpr (SCFG) e[k] = slot_cfg_eps(sf, ec[k], en[k]);      // beta == 0: the APG value needs no second plane
+            else e[k] = cfg_eps<CTL, COND>(ec[k], en[k], guidance, cc);
+        }
         *reinterpret_cast<f32x4*>(ebuf + tok * LD + k0) = e;
     }
     __syncthreads();
@@ -2245,6 +2500,8 @@ struct UpdateKeys {
     SlotKey sk;
     bool clip;         // the slot form under a clip-keyed latent guide: cg ends the slot pack
     ClipGuideState cg;
+    bool scfg;         // the slot form under a slot CFG control: sc rides behind the slot key, before the clip guide
+    SlotCfgState sc;
     DpmState ds;
     NoiseKey nk;
     CanvasKey ck;      // canvas: the seeded draw is keyed by canvas position (ck replaces nk in the pack)
@@ -2361,9 +2618,13 @@ static int check_slot_update(const char* what, const UpdateArgs& a, int slots, i
 template <class F>
 static void with_update_pack(const UpdateKeys& k, bool cond_only, F launch) {
     if (k.slots) {      // a clip-keyed guide ends the slot pack
-        auto stail = [&](auto... state) {
+        auto gtail = [&](auto... state) {
             if (k.clip) launch(state..., k.cg);
             else launch(state...);
+        };
+        auto stail = [&](auto... state) {      // a slot CFG control rides behind the key, before the guide
+            if (k.scfg) gtail(state..., k.sc);
+            else gtail(state...);
         };
         if (k.dpm && k.skey) stail(k.ds, k.sl, k.sk);
         else if (k.dpm) stail(k.ds, k.sl);
@@ -2428,10 +2689,17 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key,
                          const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
                          int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg, const avd_slot_key* skey = nullptr,
-                         const avd_clip_guide* cguide = nullptr) {
+                         const avd_clip_guide* cguide = nullptr, const avd_slot_cfg* scfg = nullptr) {
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "cfg_unpatch_ddim: bad dims");
     Tube g;
     if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
+    // scfg != nullptr: the call came through a *_slots_cfg entry; the control is checked first
+    SlotCfgState sc{};
+    const SlotGeom sg{T / t, (int64_t)C * t * H * W, (int64_t)g.Ht * g.Wt * g.D, (int64_t)t * H * W};
+    if (scfg) {
+        AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_unpatch_ddim: a slot CFG control rides with slot timesteps (slots > 0)");
+        if (int rc = make_slot_cfg(scfg, B, sg.S, sg.per_slot, g.per, {z, z_out, x0_hist}, eps2, (int64_t)2 * B * g.per * 4, sc)) return rc;
+    }
     AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "cfg_unpatch_ddim: x0_hist must be 16-byte aligned");
     const UpdateArgs a{eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, B};
     UpdateKeys k;
@@ -2441,6 +2709,11 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
                                     guide_hop ? &gcv : nullptr, apg, (int64_t)2 * B * g.per * 4, skey)) return rc;
     if (int rc = check_slot_update("cfg_unpatch_ddim", a, slots, T / t, key, guide, ctl, canvas_hop, guide_hop, k, skey,
                                    SlotKeyDims{C, t, (int64_t)H * W}, cguide, T)) return rc;
+    k.scfg = scfg != nullptr;
+    k.sc = sc;
+    if (scfg && sc.mode != SLOT_CFG_TABLE)      // 16-byte aligned token rows: the entry has checked eps2, and per % 4 == 0
+        if (int rc = run_slot_cfg_stats<CFG_SRC_VIDEO>(scfg, sc, eps2, eps2 + (int64_t)B * g.per, g.per, t_now, t_prev, guidance, T_train, B,
+                                                       sg, g, st)) return rc;
     if (apg) {
         AVD_REQUIRE(aligned16(eps2) && aligned16(eps2 + (int64_t)B * g.per) && aligned16(z) && aligned16(z_out), AVD_EUNSUPPORTED,
                     "cfg_unpatch_ddim: the APG statistics pass reads 16-byte aligned token rows");
@@ -2455,7 +2728,8 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
     static const int tag = prof_tag_id("cfg_unpatch_ddim_kernel");
     static const int tag_apg = prof_tag_id("cfg_unpatch_ddim_kernel<apg>");      // the fused launch of an APG step, timed apart
     static const int tag_clip = prof_tag_id("cfg_unpatch_ddim_kernel<clip guide>");      // as is the clip-guided slot update
-    ProfScope prof(apg ? tag_apg : cguide ? tag_clip : tag,
+    static const int tag_scfg = prof_tag_id("cfg_unpatch_ddim_kernel<slot cfg>");        // and the slot update under a slot CFG control
+    ProfScope prof(scfg ? tag_scfg : apg ? tag_apg : cguide ? tag_clip : tag,
                    (apg && apg->momentum_buf ? 24.0 : cguide ? (cguide->mask ? 24.0 : 20.0) : 16.0) * (double)B * g.per, st);
     with_update_pack(k, false, [&](auto... p) { launch_unpatch(a, g, st, p...); });
     AVD_CHECK_LAUNCH("cfg_unpatch_ddim");
@@ -2515,6 +2789,9 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
     }
     [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
     if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
+    constexpr bool SCFG = PackHas<SlotCfgState, Key...>::value;
+    [[maybe_unused]] SlotCfgCoef sf{guidance, 0.f, 1.f, 0.f, 0.f, false};      // the slot control's coefficients, by tb
+    if constexpr (SCFG) sf = slot_cfg_coef(pack_get<SlotCfgState>(nk...), t_now, T_train, guidance, tb);
     float e = 0.f;
     [[maybe_unused]] bool apg = false;      // a run-time branch of the CTL instantiations: the launch carries an APG part
     if constexpr (CTL) {
@@ -2543,10 +2820,16 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
         for (int n = n_lo; n <= n_hi; ++n) {
             const int64_t o = (int64_t)n * D + c * len + (f - n * stride);
             const float vn = tn[o];
-            acc += cfg_combine(tc[o], vn, CTL ? cc.g : guidance);
+            acc += cfg_combine(tc[o], vn, SCFG ? sf.g : CTL ? cc.g : guidance);
             cnt += 1.f;
         }
         e = acc / fmaxf(cnt, 1e-8f);
+        if constexpr (SCFG) {      // the slot's token alone (stride == len: one window); the uncovered tail keeps eps = 0
+            if (sf.apg) {          // the two means of the per-sample APG branch
+                const float cv = ola_gather(tc, D, c, len, stride, Na, f), uv = ola_gather(tn, D, c, len, stride, Na, f);
+                e = apg_eps(cv, apg_d0(cv, uv), sf.w, sf.k);
+            } else e = cfg_rescale(e, sf.phi, sf.s);
+        }
     }
     if constexpr (CTL) e = cfg_rescale(e, cc.phi, cc.s);      // r(y) on the whole latent, the zero pad included
     const Ddim cf = ddim_coef(t_now, t_prev, abar, T_train, eta, SLOT ? tb : b);
@@ -2602,7 +2885,7 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st, const avd_noise_key* key,
                                const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
                                int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg, const avd_slot_key* skey = nullptr,
-                               const avd_clip_guide* cguide = nullptr) {
+                               const avd_clip_guide* cguide = nullptr, const avd_slot_cfg* scfg = nullptr) {
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "cfg_untoken_ddim_audio: bad chunking");
     AVD_REQUIRE(!slots || stride == len, AVD_EUNSUPPORTED,
@@ -2613,10 +2896,24 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
     const CanvasDims cv{Ca, F, canvas_hop, 1};
     const CanvasDims gcv{Ca, F, guide_hop, 1};
     const AudioGeom ag{Ca, F, len, stride, audio_na(F, len, stride)};
+    SlotCfgState sc{};      // as cfg_unpatch_ddim_f32: the control of a *_slots_cfg entry is checked first
+    const SlotGeom sg{ag.Na, (int64_t)Ca * len, (int64_t)Ca * len, 0};
+    if (scfg) {
+        AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: a slot CFG control rides with slot timesteps (slots > 0)");
+        if (int rc = make_slot_cfg(scfg, B, sg.S, sg.per_slot, per, {z, z_out, x0_hist}, eps2, (int64_t)2 * B * ag.Na * Ca * len * 4, sc))
+            return rc;
+    }
     if (int rc = check_fused_update("cfg_untoken_ddim_audio", a, per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
                                     guide_hop ? &gcv : nullptr, apg, (int64_t)2 * B * ag.Na * Ca * len * 4, skey)) return rc;
     if (int rc = check_slot_update("cfg_untoken_ddim_audio", a, slots, ag.Na, key, guide, ctl, canvas_hop, guide_hop, k, skey,
                                    SlotKeyDims{Ca, len, 1}, cguide, F)) return rc;
+    k.scfg = scfg != nullptr;
+    k.sc = sc;
+    if (scfg && sc.mode != SLOT_CFG_TABLE) {
+        const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
+        if (int rc = run_slot_cfg_stats<CFG_SRC_AUDIO>(scfg, sc, eps2, eps2 + B * half, half, t_now, t_prev, guidance, T_train, B, sg, Tube{},
+                                                       st)) return rc;
+    }
     if (apg) {
         const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
         if (int rc = run_apg_stats<CFG_SRC_AUDIO>(apg, ctl ? ctl->guidance : nullptr, guidance, eps2, eps2 + B * half, half, B, per,
@@ -3085,6 +3382,35 @@ extern "C" int avd_cfg_untoken_ddim_audio_slots_guided_f32(const float* eps2, co
                                       static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots, nullptr, key,
                                       guide);
 }
+// the slot forms under a slot CFG control ("slot CFG control" in the header): the guided entries' arguments and the control; key and
+// guide may be null
+extern "C" int avd_cfg_unpatch_ddim_slots_cfg_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                                  const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, float eta,
+                                                  const avd_slot_key* key, const avd_clip_guide* guide, int slots, float* x0_hist,
+                                                  float* z_out, int B, int C, int T, int H, int W, int t, int h, int w,
+                                                  const avd_slot_cfg* cfg, avd_stream_t stream) {
+    AVD_REQUIRE(cfg, AVD_EINVAL, "cfg_unpatch_ddim_slots_cfg: null slot CFG control");
+    AVD_REQUIRE(aligned16(eps2) && aligned16(z) && aligned16(z_out), AVD_EUNSUPPORTED,
+                "cfg_unpatch_ddim_slots_cfg: pointers must be 16-byte aligned");
+    AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_unpatch_ddim_slots_cfg: slots must be > 0 (got %d)", slots);
+    AVD_REQUIRE(key || !(eta > 0.f), AVD_EINVAL, "cfg_unpatch_ddim_slots_cfg: eta > 0 needs a slot key");
+    return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, nullptr, z_out, B, C, T, H, W, t, h, w,
+                                static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots, nullptr,
+                                eta > 0.f ? key : nullptr, guide, cfg);
+}
+extern "C" int avd_cfg_untoken_ddim_audio_slots_cfg_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                                        const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance,
+                                                        float eta, const avd_slot_key* key, const avd_clip_guide* guide, int slots,
+                                                        float* x0_hist, float* z_out, int B, int Ca, int F, int len, int stride,
+                                                        const avd_slot_cfg* cfg, avd_stream_t stream) {
+    AVD_REQUIRE(cfg, AVD_EINVAL, "cfg_untoken_ddim_audio_slots_cfg: null slot CFG control");
+    AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_untoken_ddim_audio_slots_cfg: slots must be > 0 (got %d)", slots);
+    AVD_REQUIRE(key || !(eta > 0.f), AVD_EINVAL, "cfg_untoken_ddim_audio_slots_cfg: eta > 0 needs a slot key");
+    return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, nullptr, z_out, B, Ca, F, len, stride,
+                                      static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots, nullptr,
+                                      eta > 0.f ? key : nullptr, guide, cfg);
+}
+extern "C" int64_t avd_slot_cfg_stats_bytes(int B, int slots, int64_t per_slot) { return slot_cfg_stats_bytes(B, slots, per_slot); }
 extern "C" int avd_clip_guide_slots_f32(const avd_clip_guide* g, const int64_t* tau, const float* alpha_bar, int T_train, int everywhere,
                                         const float* z, float* out, int B, int64_t outer, int L, int slots, int slot_len, int64_t inner,
                                         avd_stream_t stream) {

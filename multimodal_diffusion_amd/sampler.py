@@ -174,8 +174,9 @@ class DenoiseEngine:
     captured pair leaves it at its address).  Cond-only steps of a guidance interval do not apply it and leave the buffer untouched;
     ``rewind`` and ``renoise`` (RePaint resampling) carry the buffer as it is: the direction's running average goes on across a jump.
     ``set_apg`` / ``clear_apg`` change it and start a new graph generation (the parameters are held by value).  ``step_slots`` and the
-    FIFO queue refuse it, as they refuse every CFG control.  What it does to sample quality at a given guidance scale is not measured
-    here: that needs trained weights.
+    FIFO queue refuse it, as they refuse every per-sample CFG control: their form is ``set_slot_cfg`` (guidance by noise level, per-slot
+    rescale and APG without momentum; include/avdiff_hip.h, "slot CFG control").  What it does to sample quality at a given guidance
+    scale is not measured here: that needs trained weights.
 
     ``guidance_interval`` (extension: guidance in a limited interval, Kynkaanniemi et al. 2024; default None = every step is a CFG
     step): (t_lo, t_hi) in training timesteps, both ends inclusive.  ``run`` takes a CFG step — today's step, whichever form the
@@ -368,6 +369,9 @@ class DenoiseEngine:
         self._guide_hop: Optional[int] = None      # the hop of a canvas-keyed guide (None: keyed per sample)
         # clip-keyed latent guide (set_clip_guide): (known canvas, mask canvas or None, seed), a state of its own beside set_known's
         self._clip = None
+        # slot CFG control (set_slot_cfg): the avd_slot_cfg over engine-owned level tables and scratch, None = off
+        self._scfg: Optional[L.SlotCfg] = None
+        self._scfg_g = self._scfg_phi = self._scfg_stats = None
         # window consensus (set_window_consensus): the hop (None = off) and the [L] weight table at a fixed address
         self._cons_hop: Optional[int] = None
         self._cons_w: Optional[torch.Tensor] = None
@@ -603,6 +607,71 @@ class DenoiseEngine:
         if self._clip is not None:
             raise ValueError(f"{what} takes no clip guide ({why}): clear_clip_guide() first")
 
+    # ---- slot CFG control: guidance by noise level, per-slot guidance rescale and per-slot APG for ``step_slots`` ----
+    def set_slot_cfg(self, guidance=None, rescale=None, apg=None) -> None:
+        """Control the CFG combine of ``step_slots`` per slot (extension; include/avdiff_hip.h, "slot CFG control"): ``guidance`` and
+        ``rescale`` are ``schedule_utils.level_table`` specs — a number, T_train values or a callable t -> value — looked up inside the
+        kernels at each slot's own t_now (``schedule_utils.guidance_interval_table`` gives the slot form of a guidance interval);
+        ``rescale`` phi in [0, 1] rescales every stepping slot's combined eps to the std of its conditional eps, over the slot's own
+        elements; ``apg`` {"norm_threshold":, "eta_parallel":} steps every slot on the adaptive projected guidance eps, its moments
+        and its norm cap taken per slot (a threshold chosen for a whole sample of S slots corresponds to r / sqrt(S)).  None leaves a
+        part off: the scalar guidance, no rescale, the plain combine.  Everything is checked before anything changes; the tables and
+        the scratch are engine-owned, so a later call with new values reaches a captured step.  A ``rescale`` that is zero at every
+        level launches no statistics pass.  It is a state of its own: ``set_cfg`` / ``set_apg`` stay the controls of ``step`` /
+        ``run``, which refuse a slot control, as ``step_slots`` refuses theirs."""
+        self._apply_slot_cfg(*self._check_slot_cfg(guidance, rescale, apg))
+
+    def _check_slot_cfg(self, guidance, rescale, apg):
+        """set_slot_cfg's checks alone, on the host: (guidance table or None, rescale table or None, (r, eta_p) or None, scratch bytes)"""
+        if guidance is None and rescale is None and apg is None:
+            raise ValueError("set_slot_cfg needs guidance, rescale or apg (clear_slot_cfg() switches the control off)")
+        T = int(self.alpha_bar.numel())
+        g = None if guidance is None else su.level_table(guidance, T, "guidance")
+        phi = None if rescale is None else su.level_table(rescale, T, "guidance_rescale", 0.0, 1.0)
+        vals = Fn.apg_from_dict(apg)
+        if vals is not None and vals[2] != 0.0:
+            raise ValueError("the slot APG takes no momentum: a slot's momentum would have to travel with it through the queue's shift "
+                             "as x0_hist does, which is not built (momentum must be 0)")
+        self._check_apg(vals, torch.zeros(1) if phi is None else phi)
+        rescale_on = phi is not None and bool((phi != 0).any())      # phi = 0 at every level: no statistics pass (rescale_t NULL)
+        nb = 0
+        if rescale_on or vals is not None:
+            per_slot = int(np.prod(self.latent_shape[1:])) // self.latent_shape[2] * self.slot_len
+            nb = L.lib().avd_slot_cfg_stats_bytes(self.latent_shape[0], self.slots, per_slot)
+            if nb < 0:
+                raise ValueError(f"the slot CFG control needs >= 2 latent elements per slot and B * S <= 65535 (latent "
+                                 f"{self.latent_shape}, {self.slots} slots)")
+        return g, phi if rescale_on else None, None if vals is None else vals[:2], nb
+
+    def _apply_slot_cfg(self, g, phi, apg, nb) -> None:
+        dev, rescale_on, vals = self.device, phi is not None, apg
+        if g is not None:
+            self._scfg_g = g.to(dev) if self._scfg_g is None else self._scfg_g.copy_(g)
+        if rescale_on:
+            self._scfg_phi = phi.to(dev) if self._scfg_phi is None else self._scfg_phi.copy_(phi)
+        if nb and (self._scfg_stats is None or self._scfg_stats.numel() < nb):
+            self._scfg_stats = torch.empty(nb, dtype=torch.uint8, device=dev)
+        r, eta_p = (0.0, 0.0) if vals is None else vals
+        self._scfg = L.SlotCfg(None if g is None else self._scfg_g.data_ptr(), self._scfg_phi.data_ptr() if rescale_on else None,
+                               0 if vals is None else 1, r, eta_p, self._scfg_stats.data_ptr() if nb else None, nb)
+
+    def clear_slot_cfg(self) -> None:
+        """Back to the scalar guidance and the plain combine in ``step_slots`` (the buffers are kept for a later set_slot_cfg)."""
+        self._scfg = None
+
+    def slot_cfg_coef(self) -> torch.Tensor:
+        """The per-slot coefficients the last controlled ``step_slots`` left in the scratch, float32 [B, S, 4] on the device:
+        (s, g, phi, 0) under a rescale, (s, k, w, g) under APG (held slots: (1, 0, 0, 0)).  A view, overwritten by the next step."""
+        if self._scfg is None or not self._scfg.stats:
+            raise ValueError("no statistics pass is set: set_slot_cfg(rescale=...) or set_slot_cfg(apg=...) first")
+        n = self.latent_shape[0] * self.slots
+        return self._scfg_stats[self._scfg.stats_bytes - 16 * n:self._scfg.stats_bytes].view(torch.float32).view(-1, self.slots, 4)
+
+    def _slot_cfg_refusal(self, what: str) -> None:
+        if self._scfg is not None:
+            raise ValueError(f"{what} takes no slot CFG control (its guidance and statistics are per slot of step_slots; a per-sample "
+                             "step is controlled by set_cfg / set_apg): clear_slot_cfg() first")
+
     def _touch_guide(self) -> None:
         g = self._guide
         sig = None if g is None else (g.known, g.mask, g.mask_batch_stride, g.key.seed, g.key.sample_offset, self._guide_hop)
@@ -787,6 +856,7 @@ class DenoiseEngine:
         if self.Xp is None:
             raise RuntimeError("call set_prompt() first")
         self._clip_refusal("step", "a clip guide is keyed by the clip positions of step_slots' slots; a per-sample step is guided by set_known")
+        self._slot_cfg_refusal("step")
         z = L.dev_f32(z, "z")
         if tuple(z.shape) != self.latent_shape:
             raise ValueError(f"latent shape {tuple(z.shape)} != engine shape {self.latent_shape}")
@@ -905,8 +975,12 @@ class DenoiseEngine:
         Under ``set_clip_guide`` (avd_denoise_step_slots_guided_f32; "clip-keyed latent guide") ``clip_first`` is required at any eta:
         every stepping slot ends in the blend with the known clip canvas at the clip positions it holds, forward-noised to the slot's
         own t_prev; a held slot stays ``z`` and ``x0_hist`` keeps the model's x0.
-        Scope: the scalar guidance; a per-sample latent guide (``set_known``), a CFG control, a window consensus, temb_mode "add" and overlapping audio chunks
-        are refused before anything is launched, as is ``t_last`` on a "ddim" engine; no unseeded or explicit noise."""
+        Under ``set_slot_cfg`` (avd_denoise_step_slots_cfg_f32; "slot CFG control") every stepping slot's eps is combined with the
+        guidance of its own noise level and rescaled, or projected (APG), with statistics over the slot's own elements, before the
+        solver update; any solver, any eta, with or without the clip guide.
+        Scope: the scalar guidance or a slot CFG control; a per-sample latent guide (``set_known``), a per-sample CFG control, a window
+        consensus, temb_mode "add" and overlapping audio chunks are refused before anything is launched, as is ``t_last`` on a "ddim"
+        engine; no unseeded or explicit noise."""
         if self.Xp is None:
             raise RuntimeError("call set_prompt() first")
         self._slot_refusals(t_last is not None, clip_first)
@@ -934,7 +1008,12 @@ class DenoiseEngine:
         self._last_cond_only = False
         head = (C.byref(self.desc), z.data_ptr(), self.Xp.data_ptr())
         tail = (out.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device))
-        if guide is not None:
+        if self._scfg is not None:      # any solver, any eta, with or without the clip guide
+            L.check(L.lib().avd_denoise_step_slots_cfg_f32(head[0], C.byref(self._scfg), None if key is None else C.byref(key),
+                                                           None if guide is None else C.byref(guide),
+                                                           tl[0].data_ptr() if tl else None, self.x0_hist.data_ptr() if tl else None,
+                                                           *head[1:], tn.data_ptr(), tp.data_ptr(), S, *tail))
+        elif guide is not None:
             L.check(L.lib().avd_denoise_step_slots_guided_f32(head[0], None if key is None else C.byref(key), C.byref(guide),
                                                               tl[0].data_ptr() if tl else None, self.x0_hist.data_ptr() if tl else None,
                                                               *head[1:], tn.data_ptr(), tp.data_ptr(), S, *tail))
@@ -1270,6 +1349,7 @@ class DenoiseEngine:
         cur -> other -> cur between the two latent buffers it was captured on, so it is replayed only while the trajectory sits in
         its source buffer; a single eager step puts it there.  A renoise pair works in place in ``cur`` and swaps nothing."""
         self._clip_refusal("run", "a clip guide is keyed by the clip positions of step_slots' slots; a trajectory is guided by set_known")
+        self._slot_cfg_refusal("run")
         self.check_schedule(sched)
         segs = su.trajectory_segments(sched, self.guidance_interval)
         graphable = self.eta == 0 or self._key is not None

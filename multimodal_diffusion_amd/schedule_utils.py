@@ -81,6 +81,54 @@ def check_guidance_interval(interval) -> Optional[Tuple[int, int]]:
     return lo, hi
 
 
+def level_table(spec, T_train: int, name: str, lo: Optional[float] = None, hi: Optional[float] = None) -> torch.Tensor:
+    """A value per noise level as a CPU float32 [T_train] tensor (include/avdiff_hip.h, "slot CFG control": the kernels look a slot's
+    guidance and rescale up at its t_now).  ``spec``: a number (every level), a sequence / array / tensor of T_train values, or a
+    callable t -> value, evaluated here for t = 0 .. T_train - 1.  Refuses NaN, infinities and, where given, values outside
+    [lo, hi]: the kernels trust the device values.  Host-side."""
+    T_train = _whole(T_train, "T_train")
+    if callable(spec):
+        vals = [spec(t) for t in range(T_train)]
+        for t, v in enumerate(vals):
+            if isinstance(v, torch.Tensor) and v.numel() == 1:
+                vals[t] = v = v.item()
+            if isinstance(v, bool) or not isinstance(v, numbers.Real):
+                raise ValueError(f"{name}: the callable must return a number per level, got {v!r} at t = {t}")
+        t_ = torch.tensor(vals, dtype=torch.float32)
+    elif isinstance(spec, (bool, str, bytes)) or spec is None:
+        raise ValueError(f"{name} must be a number, {T_train} values or a callable t -> value, got {spec!r}")
+    else:
+        try:
+            t_ = torch.as_tensor(spec.detach().cpu() if isinstance(spec, torch.Tensor) else spec, dtype=torch.float32)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"{name} must be a number, {T_train} values or a callable t -> value, got {spec!r}") from None
+        if t_.dim() == 0:
+            t_ = t_.reshape(1).expand(T_train)
+        elif t_.dim() != 1 or t_.numel() != T_train:
+            raise ValueError(f"{name} has shape {tuple(t_.shape)}, expected a number or {T_train} values (one per training timestep)")
+    if not bool(torch.isfinite(t_).all()):
+        raise ValueError(f"{name} must be finite at every level")
+    if lo is not None and not bool(((t_ >= lo) & (t_ <= hi)).all()):
+        raise ValueError(f"{name} must lie in [{lo:g}, {hi:g}] at every level, got [{float(t_.min()):g}, {float(t_.max()):g}]")
+    return t_.contiguous().clone()
+
+
+def guidance_interval_table(g: float, interval, T_train: int) -> torch.Tensor:
+    """The slot form of a guidance interval as a ``level_table``: ``g`` at the levels t_lo <= t <= t_hi (``check_guidance_interval``;
+    None: every level), 1.0 outside, where the CFG combine returns the conditional prediction.  A queue has no cond-only steps (some
+    slot is always inside the interval), so the interval acts through the table.  Host-side."""
+    if isinstance(g, bool) or not isinstance(g, numbers.Real) or not math.isfinite(g):
+        raise ValueError(f"guidance must be a finite number, got {g!r}")
+    iv = check_guidance_interval(interval)
+    T_train = _whole(T_train, "T_train")
+    tab = torch.ones(T_train, dtype=torch.float32)
+    if iv is None:
+        tab.fill_(float(g))
+    else:
+        tab[iv[0]:iv[1] + 1] = float(g)
+    return tab
+
+
 def guidance_segments(sched, interval) -> List[Tuple[int, int, bool]]:
     """Split the steps of a sampling schedule by kind: step i goes from sched[i] to sched[i + 1] and is a CFG step when
     t_lo <= sched[i] <= t_hi (``interval`` None: always), else a cond-only step.  Returns the maximal runs of equal kind as

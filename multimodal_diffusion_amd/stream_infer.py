@@ -27,6 +27,7 @@ timestep, a queue of latent slots runs from nearly clean to pure noise, one mode
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -223,7 +224,7 @@ def fifo_prompt_len(engine: DenoiseEngine, prompt_canvas: torch.Tensor) -> int:
 def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop: int, sched, n_slots: int, noise_seed: int,
                  graph: Optional[bool] = False, lookahead: int = 0, context: Optional[torch.Tensor] = None,
                  init_canvas: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, guide_seed: int = 0,
-                 guide_start: str = "noise") -> torch.Tensor:
+                 guide_start: str = "noise", guidance_by_level=None, rescale_by_level=None, apg: Optional[dict] = None) -> torch.Tensor:
     """FIFO diagonal denoising (FIFO-Diffusion, Kim et al. 2024, with latent partitioning): a clip of ``n_slots`` slots of
     ``engine.slot_len`` latent positions, denoised in a queue whose slots sit at different noise levels.  Returns the finished latent
     canvas [C, n_slots * slot_len, H, W] (video target) or [Ca, n_slots * slot_len] (audio target).
@@ -281,9 +282,17 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     ``stream_generate``'s canvas-keyed guide.  ``guide_start``: "noise" starts the unmasked positions from noise; "init" (SDEdit)
     starts every in-canvas position from q(s_0) of the canvas — pass the truncated schedule
     (``schedule_utils.truncate_schedule``), whose length sets the queue.  The engine's clip guide is set for the call and cleared
-    after it.  ``graph=True`` or ``lookahead > 0`` with ``init_canvas`` raises ValueError before anything is allocated."""
+    after it.  ``graph=True`` or ``lookahead > 0`` with ``init_canvas`` raises ValueError before anything is allocated.
+    ``guidance_by_level`` / ``rescale_by_level`` / ``apg`` (every driver: eager, ``graph=True``, ``lookahead``, and the eager one under
+    ``init_canvas``) control the CFG combine per slot (``DenoiseEngine.set_slot_cfg``; include/avdiff_hip.h, "slot CFG control"): the
+    first two are ``schedule_utils.level_table`` specs looked up at each slot's own noise level (``guidance_interval_table`` gives a
+    guidance interval), ``apg`` {"norm_threshold":, "eta_parallel":} is per-slot adaptive projected guidance (no momentum).  They are
+    checked before anything is allocated; the engine's slot control is set for the call and cleared after it, also when it raises."""
     if not isinstance(engine, DenoiseEngine):
         raise TypeError("fifo_denoise drives a DenoiseEngine")
+    scfg = None
+    if guidance_by_level is not None or rescale_by_level is not None or apg is not None:
+        scfg = engine._check_slot_cfg(guidance_by_level, rescale_by_level, apg)
     if isinstance(n_slots, bool) or not isinstance(n_slots, int) or n_slots < 1:
         raise ValueError(f"n_slots must be an int >= 1, got {n_slots!r}")
     if isinstance(prompt_hop, bool) or not isinstance(prompt_hop, int) or prompt_hop < 1:
@@ -307,7 +316,8 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     if lookahead:
         if graph:
             raise ValueError("fifo_denoise(lookahead > 0) runs eagerly: the lookahead queue has no device cursors, graph=True is refused")
-        return _fifo_denoise_lookahead(engine, prompt_canvas, prompt_hop, sched, n_slots, noise_seed, lookahead, context)
+        with _slot_cfg_scope(engine, scfg):
+            return _fifo_denoise_lookahead(engine, prompt_canvas, prompt_hop, sched, n_slots, noise_seed, lookahead, context)
     if context is not None:
         raise ValueError("context is the clean latent of the lookahead's context slots: it needs lookahead > 0")
     B, S, sl = engine.embed.B, engine.slots, engine.slot_len
@@ -326,14 +336,29 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     if graph is None:
         graph = 2 * B * engine.N < engine.GRAPH_BELOW_ROWS
     if graph:
-        return _fifo_denoise_graph(engine, engine.fifo_open(pc, prompt_hop, Lp, sched, n_slots, noise_seed))
+        with _slot_cfg_scope(engine, scfg):
+            return _fifo_denoise_graph(engine, engine.fifo_open(pc, prompt_hop, Lp, sched, n_slots, noise_seed))
     if init_canvas is not None:
         engine.set_clip_guide(init_canvas, mask, guide_seed=guide_seed)
     try:
-        return _fifo_denoise_eager(engine, pc, prompt_hop, Lp, sched, n_slots, noise_seed, guide_start == "init")
+        with _slot_cfg_scope(engine, scfg):
+            return _fifo_denoise_eager(engine, pc, prompt_hop, Lp, sched, n_slots, noise_seed, guide_start == "init")
     finally:
         if init_canvas is not None:
             engine.clear_clip_guide()
+
+
+@contextlib.contextmanager
+def _slot_cfg_scope(engine: DenoiseEngine, checked):
+    """the engine's slot CFG control for one fifo_denoise call: ``checked`` is ``_check_slot_cfg``'s result, None = leave the engine as
+    it is"""
+    if checked is not None:
+        engine._apply_slot_cfg(*checked)
+    try:
+        yield
+    finally:
+        if checked is not None:
+            engine.clear_slot_cfg()
 
 
 def _fifo_denoise_eager(engine: DenoiseEngine, pc: torch.Tensor, prompt_hop: int, Lp: int, sched, n_slots: int, noise_seed: int,

@@ -30,10 +30,17 @@
               the stand-alone pass (all slots, and the entering tail slot alone, in place) beside the queue shift; --e2e:
               fifo_denoise(init_canvas=) per finished slot beside the unguided queue, eager, the calls interleaved
 
+  --slot-cfg  the slot CFG control ("slot CFG control"), both solvers at eta 0 and eta > 0 in one session.  --kernels: the fused slot
+              update inside whole 2-layer steps, plain, under a guidance table alone, under a per-slot rescale (its statistics and
+              finalize launches on lines of their own) and under per-slot APG (likewise), between two runs of the plain update;
+              --e2e: fifo_denoise per finished slot with and without the control (table + rescale, table + APG), eager, the calls
+              interleaved
+
 Prints plain text: the records are profiles/fifo_kernels.txt and profiles/fifo_e2e.txt (ddim), profiles/fifo_dpm_kernels.txt and
 profiles/fifo_dpm_e2e.txt (both solvers in one session), profiles/fifo_graph_e2e.txt (--e2e with and without --graph),
 profiles/fifo_lookahead_kernels.txt and profiles/fifo_lookahead_e2e.txt (--lookahead 3), profiles/fifo_stochastic_kernels.txt and
-profiles/fifo_stochastic_e2e.txt (--stochastic), profiles/fifo_guide_kernels.txt (--guide)."""
+profiles/fifo_stochastic_e2e.txt (--stochastic), profiles/fifo_guide_kernels.txt (--guide), profiles/slot_cfg_kernels.txt and
+profiles/slot_cfg_e2e.txt (--slot-cfg)."""
 import argparse
 import ctypes as C
 import statistics
@@ -65,6 +72,7 @@ ap.add_argument("--steps", type=int, default=None, help="--e2e: steps of the sch
 ap.add_argument("--lookahead", type=int, default=0, metavar="CTX", help="FIFO lookahead: CTX context slots per window of S = 6")
 ap.add_argument("--stochastic", action="store_true", help="eta > 0 with clip-keyed slot noise beside eta = 0, both solvers")
 ap.add_argument("--guide", action="store_true", help="the clip-keyed latent guide beside the unguided slot update and queue")
+ap.add_argument("--slot-cfg", action="store_true", help="the slot CFG control beside the plain slot update and queue")
 args = ap.parse_args()
 if not 0 <= args.lookahead < 6:
     raise SystemExit("--lookahead CTX must lie in [0, 6)")
@@ -110,6 +118,98 @@ def report_shift(res, cases):
 
 
 STOCHASTIC = (("ddim", 0.5, 48), ("dpmpp_2m", 1.0, 18))      # solver, eta, steps: the two queues of profiles/fifo_dpm_e2e.txt
+
+if args.slot_cfg and args.kernels:
+    B, S = 32, 6
+    g = torch.Generator().manual_seed(0)
+    z = torch.randn(B, 8, 12, 32, 32, generator=g).to(dev)
+    prompt = torch.randn(B, 8, 150, generator=g).to(dev)
+    out = torch.empty_like(z)
+    gtab = su.guidance_interval_table(5.0, (200, 800), 1000)
+    PLAIN, CTL = "cfg_unpatch_ddim_kernel", "cfg_unpatch_ddim_kernel<slot cfg>"
+    STATS, FIN = "slot_cfg_stats_kernel", "slot_cfg_finalize_kernel"
+    KINDS = {"plain": None, "table": dict(guidance=gtab), "rescale": dict(guidance=gtab, rescale=0.7),
+             "apg": dict(guidance=gtab, apg={"norm_threshold": 20.0, "eta_parallel": 0.5})}
+    rows = []
+    for solver, eta, n in (("ddim", 0.0, 48), ("ddim", 0.5, 48), ("dpmpp_2m", 0.0, 18), ("dpmpp_2m", 1.0, 18)):
+        dpm = solver == "dpmpp_2m"
+        sched = su.make_sampling_schedule(1000, n)
+        eng = build(2, B, solver=solver, eta=eta, **({"noise_seed": 11} if eta else {}))
+        eng.set_prompt(prompt)
+        if dpm:
+            eng.x0_hist.copy_(torch.randn(B, 8, 12, 32, 32, generator=g))
+        i = (torch.arange(B * S) % (n - 2)).view(B, S) + 1      # the diagonal: none held, none final
+        tlS, tnS, tpS = (sched[i + d].to(dev).contiguous() for d in (-1, 0, 1))
+        last = dict(t_last=tlS) if dpm else {}
+
+        def step(kind, eng=eng, last=last, tnS=tnS, tpS=tpS):
+            if KINDS[kind] is None:
+                eng.clear_slot_cfg()
+            else:
+                eng.set_slot_cfg(**KINDS[kind])
+            return lambda: eng.step_slots(z, tnS, tpS, out=out, clip_first=0, **last)
+
+        name = f"{solver} eta = {eta}"
+        rows += [(f"{name}, plain (a)", PLAIN, step, "plain"), (f"{name}, guidance table", CTL, step, "table"),
+                 (f"{name}, rescale: update", CTL, step, "rescale"), (f"{name}, rescale: statistics", STATS, step, "rescale"),
+                 (f"{name}, rescale: finalize", FIN, step, "rescale"), (f"{name}, APG: update", CTL, step, "apg"),
+                 (f"{name}, APG: statistics", STATS, step, "apg"), (f"{name}, APG: finalize", FIN, step, "apg"),
+                 (f"{name}, plain (b)", PLAIN, step, "plain")]
+    for _, _, mk, kind in rows:
+        fn = mk(kind)
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    res = {name: [] for name, _, _, _ in rows}
+    for _ in range(args.rounds):
+        for name, tag, mk, kind in rows:
+            res[name].append(per_launch_us(tag, mk(kind), args.launches))
+    print(f"C3 geometry, B = {B} (S = {S} slots of 16384 elements: 16 chunks per slot): the fused CFG + un-patch + solver slot update inside "
+          f"whole steps (2 layers), plain (tag {PLAIN}) and under a slot CFG control (tag {CTL}: a guidance table by level; the table and "
+          f"a per-slot rescale phi = 0.7; the table and per-slot APG), with the statistics and finalize launches of the rescale and of APG "
+          f"(tags {STATS}, {FIN}): {args.rounds} interleaved rounds of {args.launches} launches, microseconds per launch (launch events)")
+    for name, _, _, _ in rows:
+        v = res[name]
+        print(f"  {name:40s} " + " ".join(f"{x:8.2f}" for x in v) + f"   median {statistics.median(v):8.2f}")
+    sys.exit(0)
+
+if args.slot_cfg and args.e2e:
+    S, K = 6, args.slots_out
+    g = torch.Generator().manual_seed(1)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    gtab = su.guidance_interval_table(5.0, (200, 800), 1000)
+    print(f"fifo_denoise plain and under a slot CFG control (guidance by level with a per-slot rescale phi = 0.7, and with per-slot APG), "
+          f"S = {S} (C3 latent, 8 layers, bf16x3, eager), {args.rounds} rounds, the calls interleaved, {K} and {2 * K} slots out; milliseconds")
+    for solver, eta, n in (("ddim", 0.0, 48), ("dpmpp_2m", 0.0, 18)):
+        sched = su.make_sampling_schedule(1000, n)
+        canvas_p = torch.randn(8, 25 * (n + 2 * K) + 148, generator=g).to(dev)
+        eng = build(8, n // S, solver=solver)
+        kinds = [("plain", {}), ("rescale", dict(guidance_by_level=gtab, rescale_by_level=0.7)),
+                 ("apg", dict(guidance_by_level=gtab, apg={"norm_threshold": 20.0, "eta_parallel": 0.5}))]
+        for _, kw in kinds:
+            A.fifo_denoise(eng, canvas_p, 25, sched, 4, 5, **kw)      # warm-up
+        ts_ = {(name, K_): [] for name, _ in kinds for K_ in (K, 2 * K)}
+        for _ in range(args.rounds):
+            for K_ in (K, 2 * K):
+                for name, kw in kinds:
+                    ts_[name, K_].append(timed(lambda: A.fifo_denoise(eng, canvas_p, 25, sched, K_, 5, **kw)))
+        per = {}
+        for name, _ in kinds:
+            whole = {K_: statistics.median(ts_[name, K_]) for K_ in (K, 2 * K)}
+            per[name] = (whole[2 * K] - whole[K]) / K
+            print(f"  {solver:8s} n = {n}, B = {n // S}, {name:8s}: " +
+                  "; ".join(f"{K_} out " + " ".join(f"{t * 1e3:7.1f}" for t in ts_[name, K_]) for K_ in (K, 2 * K)) +
+                  f"; per finished slot {per[name] * 1e3:.3f}, ramp and start {(whole[K] - K * per[name]) * 1e3:.1f}")
+        for name in ("rescale", "apg"):
+            print(f"  {'':8s} per finished slot, {name} against plain: {(per[name] - per['plain']) * 1e3:+.3f} ms (x {per[name] / per['plain']:.3f})")
+    sys.exit(0)
 
 if args.guide and args.kernels:
     B, S, sl = 32, 6, 2
