@@ -924,6 +924,11 @@ int avd_attn_fwd_fp8_f16x2_f32(const void* qkv, void* workspace, int64_t workspa
  * no residual). */
 int avd_gemm_bf16x3_f32(const void* A3, const void* W3, const float* bias, const float* residual, float* C, void* C3,
                         int64_t M, int N, int K, int act, int terms, avd_stream_t stream);
+/* The residual epilogue the MMDiT composite runs for out_proj / fc2 (six terms), stand-alone: C = (A W^T + bias) + residual as fp32
+ * [M,N] (residual may alias C), the split3 image of C into C3, and the sums of squares of every row's 64-column chunks into
+ * ss_out [M, N / 64] — the producer side of a folded RMSNorm.  N % 256 == 0, K % 16 == 0; every pointer required. */
+int avd_gemm_bf16x3_res_img_f32(const void* A3, const void* W3, const float* bias, const float* residual, float* C, void* C3,
+                                float* ss_out, int64_t M, int N, int K, avd_stream_t stream);
 
 /* ---- "f16x2": the same Linear / attention (mmdt.py:51-61,77-83) with every operand held as TWO fp16 planes, x ~ (h + l) / s
  * with h = rn_f16(s x), l = rn_f16(s x - h), and three product terms hh + hl + lh accumulated in fp32 on

@@ -1146,7 +1146,9 @@ __global__ __launch_bounds__(WAVES * 64, 2) void gemm_bf16x3_m16_kernel(S3Args g
     int lane_e = lane;
     asm volatile("" : "+v"(lane_e));
     if constexpr (TR) {
-        s3_epilogue_img16<EPI, RT>(g, acc, (int64_t)bm * BM + wm * WM, bn * BN + wn * WN, lane_e);
+        const int64_t m0 = (int64_t)bm * BM + wm * WM;
+        if constexpr (EPI == S3_EPI_RES_IMG) s3_epilogue_res<RT, 1>(g, acc, acc, m0, bn * BN + wn * WN, lane_e);
+        else s3_epilogue_img16<EPI, RT>(g, acc, m0, bn * BN + wn * WN, lane_e);
     } else {
         __syncthreads();
         constexpr int CLD = WN + 4;
@@ -1370,8 +1372,13 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16x3_w128_kernel(S3Args g) {
                    "+a"(acc[1][RT - 1][2]), "+a"(acc[1][RT - 1][3]));
     // (the other row tiles were last written >= 16 MFMAs = 256 issue cycles before the loop's final sched_barrier, above which nothing of the
     // epilogue can be scheduled: they need no wait states.  Naming all 64 tiles here as well made the register allocator spill.)
-    s3_epilogue_img16<EPI, RT>(g, acc[0], (int64_t)bm * BM + wm * WM, bn * BN + wn * 128, lane_e);
-    s3_epilogue_img16<EPI, RT>(g, acc[1], (int64_t)bm * BM + wm * WM, bn * BN + wn * 128 + 64, lane_e);
+    const int64_t m0 = (int64_t)bm * BM + wm * WM;
+    if constexpr (EPI == S3_EPI_RES_IMG) {
+        s3_epilogue_res<RT, 2>(g, acc[0], acc[1], m0, bn * BN + wn * 128, lane_e);      // one routine over both halves: the residual prefetch carries across
+    } else {
+        s3_epilogue_img16<EPI, RT>(g, acc[0], m0, bn * BN + wn * 128, lane_e);
+        s3_epilogue_img16<EPI, RT>(g, acc[1], m0, bn * BN + wn * 128 + 64, lane_e);
+    }
 #ifdef AVD_S3_STAMPS
     const unsigned long long t_issued = S3_T();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1901,6 +1908,11 @@ extern "C" int avd_rmsnorm_split3_f32(const float* x, const float* scale, void* 
 extern "C" int avd_gemm_bf16x3_f32(const void* A3, const void* W3, const float* bias, const float* residual, float* C, void* C3,
                                    int64_t M, int N, int K, int act, int terms, avd_stream_t stream) {
     return gemm_bf16x3(A3, W3, bias, residual, C, C3, M, N, K, act, terms, static_cast<hipStream_t>(stream));
+}
+extern "C" int avd_gemm_bf16x3_res_img_f32(const void* A3, const void* W3, const float* bias, const float* residual, float* C, void* C3,
+                                           float* ss_out, int64_t M, int N, int K, avd_stream_t stream) {
+    AVD_REQUIRE(bias && residual && C && C3 && ss_out, AVD_EINVAL, "gemm_bf16x3_res_img: null pointer");
+    return gemm_bf16x3(A3, W3, bias, residual, C, C3, M, N, K, AVD_ACT_NONE, 6, static_cast<hipStream_t>(stream), 1.f, 1.f, nullptr, 0.f, ss_out);
 }
 extern "C" int avd_gemm_bf16x3_qkv3_f32(const void* A3, const void* W3, const float* bias, void* qkv3, int64_t M, int tokens, int heads,
                                         int K, float qscale, int terms, avd_stream_t stream) {
