@@ -397,6 +397,24 @@ int avd_cfg_untoken_ddim_audio_slots_guided_f32(const float* eps2, const float* 
                                                 const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, float eta,
                                                 const avd_slot_key* key, const avd_clip_guide* guide, int slots, float* x0_hist,
                                                 float* z_out, int B, int Ca, int F, int len, int stride, avd_stream_t stream);
+/* Guided FIFO queue shift (a public contract): the queue step of a guided queue in one launch, the entering slot put on the guide's
+ * forward path where it is drawn.  (z_in -> z_out, popped) is avd_fifo_shift_f32's, and with hist_in / hist_out (both NULL or both
+ * set) avd_fifo_shift_hist_f32's, except z_out's tail slot, which is
+ *     blend(m(p), q_p(t), fresh),   p = c*slot_len + j   in SIGNED 64 bits, compared with [0, P) before anything is read,
+ * where fresh is the shift's own canvas-keyed normal for clip slot c at timestep t, and q_p, m and the known-noise stream are
+ * avd_clip_guide_slots_f32's (tau = t; alpha_bar [T_train]); everywhere != 0 reads the mask as 1 on every in-canvas position, a NULL
+ * mask is 1 everywhere.  Bit for bit the shift followed by the in-place avd_clip_guide_slots_f32 call that leaves every slot but the
+ * tail, with `first` chosen so that the tail holds clip slot c: the same "no contraction" rule and a == 1 shortcut, and a lane whose
+ * mask values are all 0 skips the generator call.  An all-zero mask, or a tail past the canvas end (c*slot_len >= P), gives the plain
+ * shift's bits; a tail that straddles the end is guided on its positions below P only.  popped, every other slot and the history
+ * are the plain shift's (the tail's history is zero).
+ * guide->first, stride and cursor are NOT read: c names the clip slot.  Checked before the launch (AVD_EINVAL): everything
+ * avd_fifo_shift_f32 / _hist_f32 check, then a non-null guide, known and alpha_bar, T_train > 0, 1 <= P <= 2^32, and known / mask
+ * must not overlap z_out, hist_out or popped.  16-byte lanes under the shift's rule (known / mask are read as 16-byte values when they
+ * are aligned too); one element per lane otherwise; the same bits either way. */
+int avd_fifo_shift_guided_f32(const avd_noise_key* key, int64_t t, int64_t c, const avd_clip_guide* guide, const float* alpha_bar,
+                              int T_train, int everywhere, const float* z_in, float* z_out, float* popped, const float* hist_in,
+                              float* hist_out, int B, int64_t outer, int slots, int slot_len, int64_t inner, avd_stream_t stream);
 
 /* ---- slot CFG control: guidance by noise level, per-slot guidance rescale and per-slot APG for the slot entries (a public contract).
  * The per-sample controls (avd_cfg_control, "adaptive projected guidance") do not carry over to slots: a sample of a queue holds S

@@ -200,6 +200,8 @@ SIGNATURES = {
     "avd_denoise_step_slots_cfg_f32": (_I, [C.POINTER(StepDesc), C.POINTER(SlotCfg), C.POINTER(SlotKey), C.POINTER(ClipGuide), _P, _P, _P,
                                             _P, _P, _P, _I, _P, _P, _L, _P]),
     "avd_fifo_shift_hist_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _P, _P, _P, _P, _P, _I, _L, _I, _I, _L, _P]),
+    "avd_fifo_shift_guided_f32": (_I, [C.POINTER(NoiseKey), _L, _L, C.POINTER(ClipGuide), _P, _I, _I, _P, _P, _P, _P, _P, _I, _L, _I, _I, _L,
+                                       _P]),
     "avd_fifo_lookahead_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _I, _P, _P, _P, _I, _L, _I, _I, _I, _L, _P]),
     "avd_fifo_lookahead_hist_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _I, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _L, _P]),
     "avd_cursor_add": (_I, [_P, _I, _P]),

@@ -609,12 +609,18 @@ struct CursorShift {
     const int32_t* m;
     int64_t n_slots;
 };
+// A GuideShift ending the pack ("guided FIFO queue shift"; with or without a HistShift before it, never with a CursorShift) puts the
+// entering tail slot on the clip guide's forward path inside this launch: the lane that drew the tail's normals blends them with
+// q_p(t) of clip positions c * slot_len + j.  It is defined with the clip guide below, whose gather and blend it calls.
+struct GuideShift;
 template <int V, class... Hist>
 __global__ __launch_bounds__(256) void fifo_shift_kernel(const float* __restrict__ z_in, float* __restrict__ z_out,
                                                          float* __restrict__ popped, CanvasKey ck, uint32_t t, int B, int64_t outer, int S,
                                                          int slot_len, int64_t inner, int64_t n_out, int64_t n_pop, Hist... hs) {
     constexpr bool HIST = PackHas<HistShift, Hist...>::value, CURSOR = PackHas<CursorShift, Hist...>::value;
-    static_assert(sizeof...(Hist) == (HIST ? 1 : 0) + (CURSOR ? 1 : 0), "the pack: optionally one HistShift, then optionally one CursorShift");
+    constexpr bool GUIDE = PackHas<GuideShift, Hist...>::value;
+    static_assert(sizeof...(Hist) == (HIST ? 1 : 0) + (CURSOR ? 1 : 0) + (GUIDE ? 1 : 0) && !(CURSOR && GUIDE),
+                  "the pack: optionally one HistShift, then optionally one CursorShift or one GuideShift");
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= n_out + n_pop) return;
     const int64_t iv = inner / V;
@@ -659,7 +665,10 @@ __global__ __launch_bounds__(256) void fifo_shift_kernel(const float* __restrict
     } else {                 // the tail slot: fresh noise of clip slot c
         if constexpr (CURSOR) ck.w0 += (uint32_t)*pack_get<CursorShift>(hs...).m;      // c = c0 + *m: it keys the draw, it addresses nothing
         const f32x4 v = canvas_normal4(ck, 0, o, j, i, inner, t);
-        if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = v;
+        if constexpr (GUIDE) {     // blend(m(p), q_p(t), fresh): the bits of the stand-alone pass on this slot
+            if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = pack_get<GuideShift>(hs...).tail4(o, j, i, inner, t, v);
+            else z_out[idx] = pack_get<GuideShift>(hs...).tail1(o, j, i, inner, t, v[(int)((o * inner + i) & 3)]);
+        } else if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = v;
         else z_out[idx] = v[(int)((o * inner + i) & 3)];
         if constexpr (HIST) {      // no history yet: zeros (never read: the tail's t_last is -1)
             const HistShift h = pack_get<HistShift>(hs...);
@@ -672,9 +681,15 @@ __global__ __launch_bounds__(256) void fifo_shift_kernel(const float* __restrict
 // hist_in / hist_out: both null (the plain shift) or both set (the shift with history: hist_out slot q = hist_in slot q + 1, zeros in the tail)
 // cursor: null = the by-value shift (clip slot c, `popped` one slot).  Set = the shift off a device cursor: c is c0, the kernel takes
 // clip slot c0 + *cursor, and `popped` is the clip canvas [outer, n_clip * slot_len, inner]
-int fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped, int B, int64_t outer,
-                   int S, int slot_len, int64_t inner, hipStream_t st, const float* hist_in = nullptr, float* hist_out = nullptr,
-                   const int32_t* cursor = nullptr, int64_t n_clip = 1) {
+// what the shift's checks leave for its launch; the guided shift (below the clip guide) makes the same checks
+struct ShiftPlan {
+    bool vec;
+    int64_t total, pop, n_out, n_pop;
+    CanvasKey ck;
+};
+int fifo_shift_plan(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped, int B, int64_t outer,
+                    int S, int slot_len, int64_t inner, const float* hist_in, float* hist_out, const int32_t* cursor, int64_t n_clip,
+                    ShiftPlan& plan) {
     AVD_REQUIRE(key, AVD_EINVAL, "fifo_shift: null noise key");
     AVD_REQUIRE(z_in && z_out && popped, AVD_EINVAL, "fifo_shift: null pointer");
     AVD_REQUIRE(!hist_in == !hist_out, AVD_EINVAL, "fifo_shift: hist_in and hist_out go together");
@@ -712,7 +727,19 @@ int fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* 
     const int64_t n_out = total / v, n_pop = pop / v;
     AVD_REQUIRE((n_out + n_pop + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "fifo_shift: %lld lanes are too many for one launch",
                 (long long)(n_out + n_pop));
-    const CanvasKey ck{(uint32_t)(key->seed & 0xffffffffu), (uint32_t)(key->seed >> 32), (uint32_t)c, (uint32_t)slot_len};
+    plan = ShiftPlan{vec, total, pop, n_out, n_pop,
+                     CanvasKey{(uint32_t)(key->seed & 0xffffffffu), (uint32_t)(key->seed >> 32), (uint32_t)c, (uint32_t)slot_len}};
+    return AVD_OK;
+}
+
+int fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped, int B, int64_t outer,
+                   int S, int slot_len, int64_t inner, hipStream_t st, const float* hist_in = nullptr, float* hist_out = nullptr,
+                   const int32_t* cursor = nullptr, int64_t n_clip = 1) {
+    ShiftPlan plan;
+    if (int rc = fifo_shift_plan(key, t, c, z_in, z_out, popped, B, outer, S, slot_len, inner, hist_in, hist_out, cursor, n_clip, plan)) return rc;
+    const bool vec = plan.vec;
+    const int64_t total = plan.total, pop = plan.pop, n_out = plan.n_out, n_pop = plan.n_pop;
+    const CanvasKey ck = plan.ck;
     static const int tags[8] = {prof_tag_id("fifo_shift_kernel<1>"), prof_tag_id("fifo_shift_kernel<4>"),
                                 prof_tag_id("fifo_shift_kernel<1, HistShift>"), prof_tag_id("fifo_shift_kernel<4, HistShift>"),
                                 prof_tag_id("fifo_shift_kernel<1, CursorShift>"), prof_tag_id("fifo_shift_kernel<4, CursorShift>"),
@@ -1267,6 +1294,64 @@ int clip_guide_slots_f32(const avd_clip_guide* g, const int64_t* tau, const floa
         hipLaunchKernelGGL(clip_guide_slots_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, cg, tau, abar, T_train, z, out, outer, L,
                            slots, inner, (int)bpr);
     AVD_CHECK_LAUNCH("clip_guide_slots");
+    return AVD_OK;
+}
+
+// The guided FIFO queue shift (avd_fifo_shift_guided_f32; contract in include/avdiff_hip.h, "clip-keyed latent guide"):
+// fifo_shift_kernel's GuideShift.  cg has first = c, stride unused and no cursor, so with sample 0 and position j clip_guide_pos gives
+// p = c * slot_len + j, what the stand-alone pass computes for the tail slot; the coefficients, the gather and the blend are its own.
+struct GuideShift {
+    ClipGuideState cg;
+    const float* abar;
+    int T_train;
+    __device__ __forceinline__ f32x4 tail4(int64_t o, int j, int64_t i, int64_t inner, uint32_t t, f32x4 v) const {
+        return clip_guide_apply4(cg, guide_coef(abar, T_train, (long long)t), 0, o, j, i, inner, v);
+    }
+    __device__ __forceinline__ float tail1(int64_t o, int j, int64_t i, int64_t inner, uint32_t t, float v) const {
+        return clip_guide_apply1(cg, guide_coef(abar, T_train, (long long)t), 0, o, j, i, inner, v);
+    }
+};
+
+int fifo_shift_guided_f32(const avd_noise_key* key, int64_t t, int64_t c, const avd_clip_guide* guide, const float* abar, int T_train,
+                          int everywhere, const float* z_in, float* z_out, float* popped, const float* hist_in, float* hist_out, int B,
+                          int64_t outer, int S, int slot_len, int64_t inner, hipStream_t st) {
+    ShiftPlan plan;
+    if (int rc = fifo_shift_plan(key, t, c, z_in, z_out, popped, B, outer, S, slot_len, inner, hist_in, hist_out, nullptr, 1, plan)) return rc;
+    AVD_REQUIRE(guide, AVD_EINVAL, "fifo_shift_guided: null clip guide");
+    AVD_REQUIRE(abar && T_train > 0, AVD_EINVAL, "fifo_shift_guided: null alpha_bar or bad T_train");
+    avd_clip_guide g = *guide;      // c names the clip slot: first / stride / cursor are not read
+    g.first = c;
+    g.stride = 1;
+    g.cursor = nullptr;
+    GuideShift gs{ClipGuideState{}, abar, T_train};
+    if (int rc = make_clip_guide(&g, B, outer, S * slot_len, S, slot_len, inner, {z_out, hist_out}, gs.cg, "fifo_shift_guided")) return rc;
+    const int64_t nc = outer * g.P * inner;
+    AVD_REQUIRE(!(popped < g.known + nc && g.known < popped + plan.pop) && !(g.mask && popped < g.mask + nc && g.mask < popped + plan.pop),
+                AVD_EINVAL, "fifo_shift_guided: known / mask must not overlap popped");
+    if (everywhere) gs.cg.mask = nullptr;      // the mask reads as 1 on every in-canvas position
+    gs.cg.vec = inner % 4 == 0 && aligned16(gs.cg.known) && aligned16(gs.cg.mask);
+    static const int tags[4] = {prof_tag_id("fifo_shift_kernel<1, GuideShift>"), prof_tag_id("fifo_shift_kernel<4, GuideShift>"),
+                                prof_tag_id("fifo_shift_kernel<1, HistShift, GuideShift>"),
+                                prof_tag_id("fifo_shift_kernel<4, HistShift, GuideShift>")};
+    // the shift's traffic and the tail slot's known / mask reads
+    ProfScope prof(tags[(hist_in ? 2 : 0) + (plan.vec ? 1 : 0)],
+                   4.0 * ((hist_in ? 4.0 : 2.0) * (double)plan.total + 3.0 * (double)plan.pop), st);
+    const dim3 grid((unsigned)((plan.n_out + plan.n_pop + 255) / 256));
+    const HistShift hs{hist_in, hist_out};
+    if (hist_in) {
+        if (plan.vec)
+            hipLaunchKernelGGL((fifo_shift_kernel<4, HistShift, GuideShift>), grid, dim3(256), 0, st, z_in, z_out, popped, plan.ck, (uint32_t)t,
+                               B, outer, S, slot_len, inner, plan.n_out, plan.n_pop, hs, gs);
+        else
+            hipLaunchKernelGGL((fifo_shift_kernel<1, HistShift, GuideShift>), grid, dim3(256), 0, st, z_in, z_out, popped, plan.ck, (uint32_t)t,
+                               B, outer, S, slot_len, inner, plan.n_out, plan.n_pop, hs, gs);
+    } else if (plan.vec)
+        hipLaunchKernelGGL((fifo_shift_kernel<4, GuideShift>), grid, dim3(256), 0, st, z_in, z_out, popped, plan.ck, (uint32_t)t, B, outer, S,
+                           slot_len, inner, plan.n_out, plan.n_pop, gs);
+    else
+        hipLaunchKernelGGL((fifo_shift_kernel<1, GuideShift>), grid, dim3(256), 0, st, z_in, z_out, popped, plan.ck, (uint32_t)t, B, outer, S,
+                           slot_len, inner, plan.n_out, plan.n_pop, gs);
+    AVD_CHECK_LAUNCH("fifo_shift_guided");
     return AVD_OK;
 }
 
@@ -3426,6 +3511,13 @@ extern "C" int avd_fifo_shift_hist_f32(const avd_noise_key* key, int64_t t, int6
                                        avd_stream_t stream) {
     AVD_REQUIRE(hist_in && hist_out, AVD_EINVAL, "fifo_shift_hist: null hist_in or hist_out");
     return fifo_shift_f32(key, t, c, z_in, z_out, popped, B, outer, slots, slot_len, inner, static_cast<hipStream_t>(stream), hist_in, hist_out);
+}
+extern "C" int avd_fifo_shift_guided_f32(const avd_noise_key* key, int64_t t, int64_t c, const avd_clip_guide* guide,
+                                         const float* alpha_bar, int T_train, int everywhere, const float* z_in, float* z_out,
+                                         float* popped, const float* hist_in, float* hist_out, int B, int64_t outer, int slots,
+                                         int slot_len, int64_t inner, avd_stream_t stream) {
+    return fifo_shift_guided_f32(key, t, c, guide, alpha_bar, T_train, everywhere, z_in, z_out, popped, hist_in, hist_out, B, outer, slots,
+                                 slot_len, inner, static_cast<hipStream_t>(stream));
 }
 extern "C" int avd_fifo_shift_cursor_f32(const avd_noise_key* key, int64_t t, int64_t c0, const int32_t* cursor, int64_t n_out,
                                          const float* z_in, float* z_out, float* clip, int B, int64_t outer, int slots, int slot_len,

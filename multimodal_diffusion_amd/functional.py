@@ -832,7 +832,8 @@ def dpmpp_2m_sde_step_slots(x_t: Tensor, eps_hat: Tensor, x0_hist: Tensor, t_las
     return out
 
 
-def fifo_shift(z: Tensor, c: int, seed: int, t: int, slot_len: int, hist: Optional[Tensor] = None, hist_out: Optional[Tensor] = None):
+def fifo_shift(z: Tensor, c: int, seed: int, t: int, slot_len: int, hist: Optional[Tensor] = None, hist_out: Optional[Tensor] = None,
+               guide: Optional[dict] = None):
     """The queue step of FIFO diagonal denoising (avd_fifo_shift_f32; contract in include/avdiff_hip.h, "FIFO queue shift"): ``z``
     ([B,C,T,H,W] video, [B,Ca,F] audio, sliding length L = S * slot_len) is a queue of B * S slots.  Returns (z_out, popped): z_out
     slot q = z slot q + 1 across sample boundaries, popped = z slot 0 ([C, slot_len, H, W] or [Ca, slot_len]), and the tail slot of
@@ -841,7 +842,11 @@ def fifo_shift(z: Tensor, c: int, seed: int, t: int, slot_len: int, hist: Option
     With ``hist`` (float32 on z's device, z's shape: a multistep solver's per-element history, ``x0_hist`` of the slot form of
     DPM-Solver++(2M)) the same launch carries it along with its slot (avd_fifo_shift_hist_f32) and the result is (z_out, popped,
     hist_out): hist_out slot q = hist slot q + 1, zeros in the tail slot, the head's history dropped.  ``hist_out``: a buffer to
-    write it to (hist's shape, not overlapping it), None allocates one."""
+    write it to (hist's shape, not overlapping it), None allocates one.
+    ``guide`` (avd_fifo_shift_guided_f32; "clip-keyed latent guide") = {"known":, "alpha_bar":, "seed":, "mask": None, "everywhere":
+    False}, the arguments of ``clip_guide_slots``: the same launch blends the entering tail slot with the known canvas forward-noised
+    to ``t`` at clip positions c * slot_len + j — bit for bit this shift followed by the in-place ``clip_guide_slots`` call on the
+    tail slot alone.  Everything else is the plain shift's."""
     z = L.dev_f32(z, "z")
     if hist is None and hist_out is not None:
         raise ValueError("hist_out goes with hist")
@@ -859,15 +864,27 @@ def fifo_shift(z: Tensor, c: int, seed: int, t: int, slot_len: int, hist: Option
     key = noise_key(seed, 0)
     out = torch.empty_like(z)
     popped = torch.empty((z.shape[1], slot_len) + tuple(z.shape[3:]), device=z.device, dtype=torch.float32)
-    if hist is None:
+    if hist is None and guide is None:
         L.check(L.lib().avd_fifo_shift_f32(C.byref(key), t, c, z.data_ptr(), out.data_ptr(), popped.data_ptr(), z.shape[0], outer,
                                            L_ // slot_len, slot_len, inner, _st(z)))
         return out, popped
-    if hist_out is None:
+    if hist is not None and hist_out is None:
         hist_out = torch.empty_like(hist)
-    elif not (hist_out.is_cuda and hist_out.dtype == torch.float32 and hist_out.is_contiguous() and hist_out.shape == hist.shape and
-              hist_out.device == hist.device):
+    elif hist is not None and not (hist_out.is_cuda and hist_out.dtype == torch.float32 and hist_out.is_contiguous() and
+                                   hist_out.shape == hist.shape and hist_out.device == hist.device):
         raise ValueError(f"hist_out must be a contiguous float32 tensor of hist's shape {tuple(hist.shape)} on its device")
+    if guide is not None:
+        if not isinstance(guide, dict) or set(guide) - {"known", "alpha_bar", "seed", "mask", "everywhere"} or \
+                not {"known", "alpha_bar", "seed"} <= set(guide):
+            raise ValueError(f"guide must be a dict with known, alpha_bar, seed and optionally mask, everywhere, got {guide!r}")
+        m = None if guide.get("mask") is None else L.dev_f32(guide["mask"], "mask")
+        g = clip_guide(guide["known"], m, guide["seed"], shape=tuple(z.shape))
+        ab = guide["alpha_bar"]
+        ab = (ab if (ab.is_cuda and ab.dtype == torch.float32) else ab.to(z.device, torch.float32)).contiguous()
+        L.check(L.lib().avd_fifo_shift_guided_f32(C.byref(key), t, c, C.byref(g), ab.data_ptr(), ab.numel(),
+                                                  1 if guide.get("everywhere") else 0, z.data_ptr(), out.data_ptr(), popped.data_ptr(),
+                                                  L.ptr(hist), L.ptr(hist_out), z.shape[0], outer, L_ // slot_len, slot_len, inner, _st(z)))
+        return (out, popped) if hist is None else (out, popped, hist_out)
     L.check(L.lib().avd_fifo_shift_hist_f32(C.byref(key), t, c, z.data_ptr(), out.data_ptr(), popped.data_ptr(), hist.data_ptr(),
                                             hist_out.data_ptr(), z.shape[0], outer, L_ // slot_len, slot_len, inner, _st(z)))
     return out, popped, hist_out

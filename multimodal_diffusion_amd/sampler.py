@@ -1062,20 +1062,31 @@ class DenoiseEngine:
         if self.target == "audio" and self.chunk[0] != self.chunk[1]:
             raise ValueError(f"step_slots needs non-overlapping audio chunks (stride == length), got chunk {self.chunk}")
 
-    def fifo_shift(self, z: torch.Tensor, c: int, t: int, seed: Optional[int] = None):
+    def fifo_shift(self, z: torch.Tensor, c: int, t: int, seed: Optional[int] = None, guided: Optional[str] = None):
         """The queue step of FIFO diagonal denoising on this engine's queue (``functional.fifo_shift`` with the engine's ``slot_len``;
         ``seed``: the seed of the entering slot's noise, None = the engine's ``noise_seed``): returns (z_out, popped).  Solver "dpmpp_2m": the same launch shifts the history into a
         second engine-owned buffer, which becomes ``x0_hist`` (the head's history is dropped, the entering slot's is zero): a slot
         keeps its history as it moves up the queue.  That changes an address a captured graph holds, so it starts a new graph
-        generation."""
+        generation.
+        ``guided`` (None = the plain shift, also under a clip guide): "mask" or "everywhere" needs ``set_clip_guide`` and puts the
+        entering slot, clip slot ``c``, on the guide's forward path at ``t`` inside the same launch (avd_fifo_shift_guided_f32) —
+        through the guide's mask, or with the mask read as 1 on every in-canvas position (SDEdit's start)."""
         seed = self.noise_seed if seed is None else seed
         if seed is None:
             raise ValueError("fifo_shift draws the entering slot's noise from a seed: pass one, or build the engine with noise_seed")
+        guide = None
+        if guided is not None:
+            if guided not in ("mask", "everywhere"):
+                raise ValueError(f"guided must be None, 'mask' or 'everywhere', got {guided!r}")
+            if self._clip is None:
+                raise ValueError("fifo_shift(guided=...) guides the entering slot by the clip guide: set_clip_guide() first")
+            guide = dict(known=self._clip[0], mask=self._clip[1], seed=self._clip[2], alpha_bar=self.alpha_bar,
+                         everywhere=guided == "everywhere")
         if self.solver != "dpmpp_2m":
-            return Fn.fifo_shift(z, c, seed, t, self.slot_len)
+            return Fn.fifo_shift(z, c, seed, t, self.slot_len, guide=guide)
         if self._hist_other is None:
             self._hist_other = torch.empty_like(self.x0_hist)
-        z_out, popped, _ = Fn.fifo_shift(z, c, seed, t, self.slot_len, hist=self.x0_hist, hist_out=self._hist_other)
+        z_out, popped, _ = Fn.fifo_shift(z, c, seed, t, self.slot_len, hist=self.x0_hist, hist_out=self._hist_other, guide=guide)
         self.x0_hist, self._hist_other = self._hist_other, self.x0_hist
         self._generation += 1
         self._stale_reason = "fifo_shift moved the solver history into the engine's other history buffer (x0_hist changed its address)"

@@ -23,12 +23,12 @@ Extension (``fifo_denoise``): FIFO diagonal denoising, the other family of long-
 timestep, a queue of latent slots runs from nearly clean to pure noise, one model call moves every slot one level
 (``DenoiseEngine.step_slots``), the head leaves finished and noise enters at the tail (``functional.fifo_shift``).  With
 ``lookahead=`` the samples are overlapping windows of the queue whose leading slots are held context (``functional.fifo_lookahead``), and
-``context=`` continues an existing clip.
+``context=`` continues an existing clip.  ``stream_generate(sampler="fifo")`` runs it from a config, a VAE, a codec and a prompt clip.
 """
 from __future__ import annotations
 
 import contextlib
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -224,7 +224,8 @@ def fifo_prompt_len(engine: DenoiseEngine, prompt_canvas: torch.Tensor) -> int:
 def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop: int, sched, n_slots: int, noise_seed: int,
                  graph: Optional[bool] = False, lookahead: int = 0, context: Optional[torch.Tensor] = None,
                  init_canvas: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, guide_seed: int = 0,
-                 guide_start: str = "noise", guidance_by_level=None, rescale_by_level=None, apg: Optional[dict] = None) -> torch.Tensor:
+                 guide_start: str = "noise", guidance_by_level=None, rescale_by_level=None, apg: Optional[dict] = None,
+                 guided_shift: bool = False) -> torch.Tensor:
     """FIFO diagonal denoising (FIFO-Diffusion, Kim et al. 2024, with latent partitioning): a clip of ``n_slots`` slots of
     ``engine.slot_len`` latent positions, denoised in a queue whose slots sit at different noise levels.  Returns the finished latent
     canvas [C, n_slots * slot_len, H, W] (video target) or [Ca, n_slots * slot_len] (audio target).
@@ -283,6 +284,9 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     starts every in-canvas position from q(s_0) of the canvas — pass the truncated schedule
     (``schedule_utils.truncate_schedule``), whose length sets the queue.  The engine's clip guide is set for the call and cleared
     after it.  ``graph=True`` or ``lookahead > 0`` with ``init_canvas`` raises ValueError before anything is allocated.
+    ``guided_shift=True`` (with ``init_canvas``; default False: the launches above) folds the tail slot's pass into the shift's own
+    launch (``functional.fifo_shift(guide=)``; include/avdiff_hip.h, "Guided FIFO queue shift"): one launch fewer per finished slot,
+    the same bits.  ``stream_generate(sampler="fifo")`` runs its init clips this way.
     ``guidance_by_level`` / ``rescale_by_level`` / ``apg`` (every driver: eager, ``graph=True``, ``lookahead``, and the eager one under
     ``init_canvas``) control the CFG combine per slot (``DenoiseEngine.set_slot_cfg``; include/avdiff_hip.h, "slot CFG control"): the
     first two are ``schedule_utils.level_table`` specs looked up at each slot's own noise level (``guidance_interval_table`` gives a
@@ -305,6 +309,8 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
         raise ValueError(f"guide_start must be 'noise' or 'init', got {guide_start!r}")
     if init_canvas is None and (mask is not None or guide_start != "noise"):
         raise ValueError("mask and guide_start belong to the clip guide: pass init_canvas")
+    if not isinstance(guided_shift, bool) or (guided_shift and init_canvas is None):
+        raise ValueError(f"guided_shift must be a bool, and True only with init_canvas (it guides the entering slot), got {guided_shift!r}")
     if init_canvas is not None:
         if graph:
             raise ValueError("fifo_denoise(init_canvas=...) runs eagerly: the replayed queue has no guided tail pass, graph=True is refused")
@@ -342,7 +348,7 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
         engine.set_clip_guide(init_canvas, mask, guide_seed=guide_seed)
     try:
         with _slot_cfg_scope(engine, scfg):
-            return _fifo_denoise_eager(engine, pc, prompt_hop, Lp, sched, n_slots, noise_seed, guide_start == "init")
+            return _fifo_denoise_eager(engine, pc, prompt_hop, Lp, sched, n_slots, noise_seed, guide_start == "init", guided_shift)
     finally:
         if init_canvas is not None:
             engine.clear_clip_guide()
@@ -362,10 +368,11 @@ def _slot_cfg_scope(engine: DenoiseEngine, checked):
 
 
 def _fifo_denoise_eager(engine: DenoiseEngine, pc: torch.Tensor, prompt_hop: int, Lp: int, sched, n_slots: int, noise_seed: int,
-                        everywhere: bool) -> torch.Tensor:
+                        everywhere: bool, guided_shift: bool = False) -> torch.Tensor:
     """``fifo_denoise``'s eager loop over the plain queue; under ``engine.set_clip_guide`` the guided one (the contract is in
-    ``fifo_denoise``): the start and every entering tail slot go through ``functional.clip_guide_slots`` at s_0, the steps are keyed by
-    the clip slot at queue slot 0 at any eta."""
+    ``fifo_denoise``): the start and every entering tail slot go through ``functional.clip_guide_slots`` at s_0 — with ``guided_shift``
+    the tail slot inside the shift's own launch (``engine.fifo_shift(guided=)``) — and the steps are keyed by the clip slot at queue
+    slot 0 at any eta."""
     B, S, sl = engine.embed.B, engine.slots, engine.slot_len
     ramp_now, ramp_prev, steady_now, steady_prev = su.fifo_plan(sched, S)
     n = ramp_now.shape[0] + 1
@@ -387,6 +394,7 @@ def _fifo_denoise_eager(engine: DenoiseEngine, pc: torch.Tensor, prompt_hop: int
         tail = torch.full((B, S), Fn.SLOT_LEAVE, dtype=torch.long, device=dev)
         tail[B - 1, S - 1] = s0
         Fn.clip_guide_slots(clip[0], torch.full((B, S), s0, dtype=torch.long, device=dev), ab, z, clip[1], first=0, out=z, **guide)
+    guided = None if clip is None or not guided_shift else ("everywhere" if everywhere else "mask")
     for r in range(n - 1):
         z, other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other, t_last=ramp_last[r] if multistep else None, clip_first=first(0),
                                      clip_stride=stride), z
@@ -395,8 +403,8 @@ def _fifo_denoise_eager(engine: DenoiseEngine, pc: torch.Tensor, prompt_hop: int
         if m:
             engine.set_prompt(fifo_prompt_windows(pc, m, B, S, prompt_hop, Lp))
         other = engine.step_slots(z, tabs[2], tabs[3], out=other, t_last=steady_last, clip_first=first(m), clip_stride=stride)
-        z, popped = engine.fifo_shift(other, n + m, s0, seed=noise_seed)
-        if clip is not None:      # the entering tail slot alone: clip slot n + m, now that clip slot m + 1 is at queue slot 0
+        z, popped = engine.fifo_shift(other, n + m, s0, seed=noise_seed, guided=guided)      # guided: clip slot n + m enters at q(s_0)
+        if clip is not None and guided is None:      # the entering tail slot alone: clip slot n + m, now that clip slot m + 1 is at queue slot 0
             Fn.clip_guide_slots(clip[0], tail, ab, z, clip[1], first=m + 1, out=z, **guide)
         canvas[:, m * sl:(m + 1) * sl] = popped
     return canvas
@@ -496,6 +504,249 @@ def _fifo_denoise_graph(engine: DenoiseEngine, q) -> torch.Tensor:
     return q.clip
 
 
+SAMPLERS = ("windows", "fifo")      # stream_generate(sampler=): independent / consensus windows, or the FIFO queue
+
+
+# ---- what both samplers of stream_generate do around their denoising: split, encode, the mask on the canvas, decode, stitch ----
+def _window_seconds(cfg: Dict) -> Tuple[float, float, float]:
+    """(window, hop, crossfade) seconds of ``streaming``"""
+    st = cfg.get("streaming", {})
+    return float(st.get("window_seconds", 3.0)), float(st.get("hop_seconds", 1.0)), float(st.get("crossfade_seconds", 0.25))
+
+
+def _prompt_windows(cfg: Dict, pc, prompt_modality: str, prompt_video, prompt_audio):
+    """(chunks, zp_shape, lat): the prompt clip split into windows, the shape its encoded form has by the config, and the target's
+    latent shape without the batch axis"""
+    win_s, hop_s, _ = _window_seconds(cfg)
+    if prompt_modality == "video":
+        if prompt_video is None:
+            raise ValueError("prompt_video frames required for prompt_modality=video")
+        chunks = split_frames_into_windows(prompt_video, fps=pc.fps, win_s=win_s, hop_s=hop_s)[0]
+        zp_shape = (chunks.shape[0], pc.Cv, chunks.shape[1] // pc.t_down, chunks.shape[2] // pc.s_down, chunks.shape[3] // pc.s_down)
+        return chunks, zp_shape, (pc.Ca, pc.Fa)
+    if prompt_audio is None:
+        raise ValueError("prompt_audio required for prompt_modality=audio")
+    chunks = split_audio_into_windows(prompt_audio, sr=pc.sr, win_s=win_s, hop_s=hop_s)[0]
+    T_in = int(round(cfg["data"]["clip_seconds"] * pc.fps))
+    return chunks, (chunks.shape[0], pc.Ca, pc.Fa), (pc.Cv, max(1, T_in // pc.t_down), pc.H // pc.s_down, pc.W // pc.s_down)
+
+
+def _init_windows(cfg: Dict, pc, init: Optional[np.ndarray], n_windows: int) -> Optional[np.ndarray]:
+    """the init clip split into windows like the prompt (None without one); it must give the prompt's number of windows"""
+    if init is None:
+        return None
+    win_s, hop_s, _ = _window_seconds(cfg)
+    split = split_frames_into_windows if pc.target == "video" else split_audio_into_windows
+    init_chunks = split(init, pc.fps if pc.target == "video" else pc.sr, win_s, hop_s)[0]
+    if init_chunks.shape[0] != n_windows:
+        raise ValueError(f"the init clip splits into {init_chunks.shape[0]} windows, the prompt into {n_windows}: they must cover "
+                         "the same long clip")
+    return init_chunks
+
+
+def _canvas_mask(mask, lat, n_windows: int, hop: int, L_: int) -> torch.Tensor:
+    """``mask`` checked and expanded to the target's latent canvas [C, P, H, W] / [Ca, P], P = (n_windows - 1) * hop + L (CPU float32)"""
+    if lat[1] != L_:
+        raise ValueError(f"mask: the target latent has {lat[1]} positions along its sliding axis (data.clip_seconds), a window of "
+                         f"streaming.window_seconds has {L_}: they must be equal")
+    mask_canvas_shape = (lat[0], (n_windows - 1) * hop + L_) + tuple(lat[2:])
+    mc = torch.as_tensor(mask).detach().to("cpu", torch.float32)
+    try:
+        mc = mc.expand(mask_canvas_shape)
+    except RuntimeError:
+        raise ValueError(f"mask shape {tuple(mc.shape)} does not broadcast to the latent canvas {mask_canvas_shape}") from None
+    if not bool(((mc >= 0) & (mc <= 1)).all()):
+        raise ValueError("mask values must lie in [0, 1]")
+    return mc
+
+
+def _encode_windows(modality: str, vid_vae, aud_codec, chunks: np.ndarray, device) -> torch.Tensor:
+    return P.encode_video(vid_vae, chunks, device) if modality == "video" else P.encode_audio(aud_codec, chunks, device)
+
+
+def _encode_init(target: str, vid_vae, aud_codec, init_chunks: np.ndarray, device, want) -> torch.Tensor:
+    """the init clip's windows encoded as one batch: contiguous float32 of the target's window shape ``want``"""
+    known = _encode_windows(target, vid_vae, aud_codec, init_chunks, device).float().contiguous()
+    if tuple(known.shape) != tuple(want):
+        raise ValueError(f"the init clip encodes to windows of shape {tuple(known.shape)}, the target's are {tuple(want)}")
+    return known
+
+
+def _decode_windows(cfg: Dict, pc, vid_vae, aud_codec, lat, z: torch.Tensor, device) -> torch.Tensor:
+    """finished latents of some windows -> what the stitcher takes: waveforms [n, L] float32 or frames [n, T, H, W, 3] uint8"""
+    if pc.target == "audio":
+        if z.shape[0] == 0:
+            hop_a = int(getattr(aud_codec, "hop", 0)) or int(round(pc.sr * float(cfg["data"]["clip_seconds"]))) // pc.Fa
+            return torch.empty(0, pc.Fa * hop_a, device=device)
+        return aud_codec.decode(z)[:, 0, :].contiguous()
+    if z.shape[0] == 0:
+        return torch.empty(0, lat[1] * pc.t_down, lat[2] * pc.s_down, lat[3] * pc.s_down, 3, dtype=torch.uint8, device=device)
+    x = vid_vae.decode(z).clamp(0, 1)                                         # [n,3,T,H,W]
+    return (x.permute(0, 2, 3, 4, 1) * 255.0).to(torch.uint8).contiguous()    # as the reference's astype(np.uint8)
+
+
+def _stitch(cfg: Dict, pc, out: torch.Tensor) -> Dict:
+    """the decoded windows cross-faded into the result dict"""
+    _, hop_s, xfade_s = _window_seconds(cfg)
+    if pc.target == "audio":
+        w = torch.from_numpy(audio_fade_window(out.shape[1], int(round(pc.sr * xfade_s))))
+        return {"audio": crossfade_tensor(out, w, int(round(pc.sr * hop_s))).cpu().numpy(), "sr": pc.sr}
+    w = torch.from_numpy(video_fade_window(out.shape[1], int(round(xfade_s * pc.fps))))
+    return {"video": crossfade_tensor(out, w, int(round(pc.fps * hop_s))).cpu().numpy(), "fps": pc.fps}
+
+
+# ---- stream_generate(sampler="fifo"): the FIFO queue behind the pipeline's front end ----
+class FifoGeometry(NamedTuple):
+    """``fifo_geometry``'s result: latent positions and slots of a long clip run through the FIFO queue"""
+    hop_t: int          # the target's hop and window length in latent positions (``latent_hop``)
+    L_t: int
+    hop_p: int          # the prompt's
+    L_p: int
+    slot_len: int       # latent positions per slot: the tube's t (video target) or the chunk length (audio target)
+    S: int              # slots per sample; the engine's sliding length is S * slot_len <= L_t
+    prompt_hop: int     # prompt positions per target slot
+    h: int              # stepping slots per sample, S - lookahead
+    B: int              # the engine's batch, steps // h
+    P: int              # the target canvas' positions, (n_windows - 1) * hop_t + L_t
+    n_slots: int        # ceil(P / slot_len): the queue runs whole slots, the canvas is cropped to P
+    P_p: int            # the prompt canvas' positions
+
+
+def fifo_geometry(cfg: Dict, prompt_modality: str, n_windows: int, steps: int, lookahead: int = 0) -> FifoGeometry:
+    """The geometry of ``stream_generate(sampler="fifo")`` from the config alone (no device): how ``n_windows`` windows of
+    ``streaming.window_seconds`` / ``hop_seconds`` become a target canvas of P latent positions, a queue of samples of S slots and a
+    prompt canvas the queue's prompt gather walks by whole positions.  ``steps`` is the length of the schedule the queue will run (after
+    any truncation by ``strength``).  ValueError, naming the numbers, where the config does not fit the queue."""
+    if prompt_modality not in ("video", "audio"):
+        raise ValueError("prompt_modality must be 'video' or 'audio'")
+    target = "audio" if prompt_modality == "video" else "video"
+    for name, v, lo in (("n_windows", n_windows, 1), ("steps", steps, 1), ("lookahead", lookahead, 0)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+            raise ValueError(f"{name} must be an int >= {lo}, got {v!r}")
+    hop_t, L_t = latent_hop(cfg, target)
+    hop_p, L_p = latent_hop(cfg, prompt_modality)
+    if target == "video":
+        slot_len = P.tube_from_config(cfg)[0]
+    else:
+        chunk = cfg["tokenizer"]["audio"]["chunk"]
+        slot_len, stride = int(chunk["length"]), int(chunk["stride"])
+        if stride != slot_len:
+            raise ValueError(f"the audio chunk has length {slot_len} and stride {stride}: a queue slot is one chunk, so the FIFO sampler "
+                             "needs non-overlapping chunks (stride == length)")
+    S = L_t // slot_len
+    if S < 1:
+        raise ValueError(f"a window of {L_t} latent positions holds no slot of {slot_len}: the FIFO sampler needs at least one")
+    if (L_p * slot_len) % L_t:
+        raise ValueError(f"the prompt has {L_p * slot_len / L_t:g} latent positions per target slot ({L_p} per window of {L_t} target "
+                         f"positions, slots of {slot_len}); the queue's prompt gather moves by whole positions")
+    prompt_hop = L_p * slot_len // L_t
+    if not lookahead < S:
+        raise ValueError(f"lookahead {lookahead} must be below the S = {S} slots of a sample")
+    h = S - lookahead
+    if steps % h:
+        raise ValueError(f"{steps} steps do not fill a queue of samples with {h} stepping slots (S = {S}, lookahead {lookahead}): the "
+                         f"nearest step counts are {steps // h * h} and {(steps // h + 1) * h}")
+    P_ = (n_windows - 1) * hop_t + L_t
+    return FifoGeometry(hop_t, L_t, hop_p, L_p, slot_len, S, prompt_hop, h, steps // h, P_, -(-P_ // slot_len),
+                        (n_windows - 1) * hop_p + L_p)
+
+
+def _fifo_options(cfg: Dict, *, shard, consensus, noise_keying, resample, init_noise, fifo) -> dict:
+    """What ``stream_generate(sampler="fifo")`` refuses, before anything is read or encoded, and its ``fifo`` options ({"steps":
+    None = the target's sampler_steps, "lookahead": 0, "graph": False}; the argument wins over ``streaming.fifo``)."""
+    st = cfg.get("streaming", {})
+    if shard:
+        raise ValueError("sampler='fifo' with shard=True is not implemented: the queue is one chain of steps on one device")
+    if (consensus if consensus is not None else st.get("latent_consensus")) not in (None, False):
+        raise ValueError("sampler='fifo' takes no consensus: the queue generates one latent canvas, there are no windows to average")
+    if (noise_keying if noise_keying is not None else st.get("noise_keying", "sample")) == "canvas":
+        raise ValueError("sampler='fifo' takes no noise_keying='canvas': that keys the windows' step noise, the queue keys its own by "
+                         "clip slot")
+    if su.check_resample(resample) or su.resample_from_config(cfg["sampling"]):
+        raise ValueError("sampler='fifo' takes no resample: a queue slot moves down the schedule one level per step and cannot jump back")
+    if init_noise is not None:
+        raise ValueError("sampler='fifo' takes no init_noise: the queue starts from the canvas-keyed noise stream of seed")
+    opts = fifo if fifo is not None else st.get("fifo")
+    opts = {} if opts is None else opts
+    if not isinstance(opts, dict) or set(opts) - {"steps", "lookahead", "graph"}:
+        raise ValueError(f"fifo takes a dict with any of steps, lookahead and graph, got {opts!r}")
+    opts = dict({"steps": None, "lookahead": 0, "graph": False}, **opts)
+    if opts["steps"] is not None and (isinstance(opts["steps"], bool) or not isinstance(opts["steps"], int) or opts["steps"] < 1):
+        raise ValueError(f"fifo['steps'] must be an int >= 1 or None, got {opts['steps']!r}")
+    if isinstance(opts["lookahead"], bool) or not isinstance(opts["lookahead"], int) or opts["lookahead"] < 0:
+        raise ValueError(f"fifo['lookahead'] must be an int >= 0, got {opts['lookahead']!r}")
+    if opts["graph"] is not None and not isinstance(opts["graph"], bool):
+        raise ValueError(f"fifo['graph'] must be True, False or None, got {opts['graph']!r}")
+    return opts
+
+
+def _stream_generate_fifo(cfg: Dict, pc, mods: Dict, device, prompt_modality: str, chunks: np.ndarray, zp_shape, lat, init_chunks,
+                          mask, strength: float, opts: dict, *, seed, noise_seed, guide_seed, return_latents: bool,
+                          max_windows_per_batch: int) -> Dict:
+    """``stream_generate(sampler="fifo")`` after the common checks and splits (the contract is in ``stream_generate``): the prompt
+    windows become one prompt canvas, ``fifo_denoise`` generates the target canvas, and its windows are decoded and cross-faded as the
+    windows sampler's are."""
+    vid_vae, aud_codec = mods["vid_vae"], mods["aud_codec"]
+    target, Nw, T_train = pc.target, zp_shape[0], int(pc.alpha_bar.numel())
+    whole = su.make_sampling_schedule(T_train, opts["steps"]) if opts["steps"] is not None else pc.sched
+    sched = su.truncate_schedule(whole, strength) if init_chunks is not None and strength < 1.0 else whole
+    n = int(sched.numel()) - 1
+    # strength 0 runs no step: the geometry is then checked for the whole schedule
+    geo = fifo_geometry(cfg, prompt_modality, Nw, n or int(whole.numel()) - 1, opts["lookahead"])
+    if lat[1] != geo.L_t:
+        raise ValueError(f"the target latent has {lat[1]} positions along its sliding axis (data.clip_seconds), a window of "
+                         f"streaming.window_seconds has {geo.L_t}: they must be equal")
+    ctl = {}
+    if pc.interval is not None:
+        ctl["guidance_by_level"] = su.guidance_interval_table(pc.guidance, pc.interval, T_train)
+    if pc.rescale != 0.0:
+        ctl["rescale_by_level"] = pc.rescale
+    if pc.apg is not None:
+        if pc.apg[2] != 0.0:
+            raise ValueError(f"sampling.apg momentum {pc.apg[2]:g}: the FIFO queue has no slot momentum (a slot's buffer would have to "
+                             "travel with it through the shift); set momentum to 0")
+        ctl["apg"] = {"norm_threshold": pc.apg[0], "eta_parallel": pc.apg[1]}
+    mc = None if mask is None else _canvas_mask(mask, lat, Nw, geo.hop_t, geo.L_t)
+
+    def one_canvas(windows: torch.Tensor, hop: int) -> torch.Tensor:
+        """windows encoded alone disagree on their overlaps: one uniform consensus pass, then the canvas"""
+        return canvas_from_windows(Fn.window_consensus(windows, hop), hop)
+
+    init_canvas = None
+    if init_chunks is not None:
+        init_canvas = one_canvas(_encode_init(target, vid_vae, aud_codec, init_chunks, device, (Nw, *lat)), geo.hop_t)
+    if n == 0:                                     # strength 0: no steps, the known canvas
+        canvas = init_canvas
+    else:
+        z_p = _encode_windows(prompt_modality, vid_vae, aud_codec, chunks, device)
+        n_prompt = P.prompt_tokens(pc, tuple(z_p.shape))      # the encoder's own output decides, as in the windows sampler
+        if z_p.shape[2] != geo.L_p:
+            raise ValueError(f"encoded prompt windows have {z_p.shape[2]} latent positions, the config implies {geo.L_p}: the prompt "
+                             "canvas cannot be laid out")
+        prompt_canvas = one_canvas(z_p.float().contiguous(), geo.hop_p)
+        # the per-sample CFG controls stay off the engine: a queue sample holds S noise levels, ``ctl`` is their slot form
+        eng = P.build_engine(pc._replace(rescale=0.0, interval=None, apg=None), adapt_v=mods["adapt_v"], adapt_a=mods["adapt_a"],
+                             core=mods["core"], head=mods["head"], tstep_dim=mods["tstep_dim"],
+                             latent_shape=(geo.B, lat[0], geo.S * geo.slot_len) + tuple(lat[2:]), n_prompt=n_prompt, noise_seed=noise_seed)
+        if seed is None:                           # once, from torch's global CPU generator: torch.manual_seed governs it
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        guide = {}
+        if init_canvas is not None:
+            sdedit = strength < 1.0
+            guide = dict(init_canvas=init_canvas, mask=mc if mc is not None else (torch.zeros(1) if sdedit else None),
+                         guide_seed=P.default_guide_seed(guide_seed, noise_seed), guide_start="init" if sdedit else "noise",
+                         guided_shift=True)
+        canvas = fifo_denoise(eng, prompt_canvas, geo.prompt_hop, sched, geo.n_slots, int(seed), graph=opts["graph"],
+                              lookahead=opts["lookahead"], **guide, **ctl)[:, :geo.P].contiguous()
+    windows = windows_from_canvas(canvas, geo.L_t, geo.hop_t)
+    out = torch.cat([_decode_windows(cfg, pc, vid_vae, aud_codec, lat, windows[lo:lo + max_windows_per_batch], device)
+                     for lo in range(0, Nw, max_windows_per_batch)], 0)
+    res = _stitch(cfg, pc, out)
+    if return_latents:
+        res["latents"], res["latent_canvas"] = windows.cpu().numpy(), canvas.cpu().numpy()
+    return res
+
+
 @torch.no_grad()
 def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, head, tstep_dim: int, prompt_modality: str,
                     prompt_video: Optional[np.ndarray], prompt_audio: Optional[np.ndarray], device: torch.device,
@@ -504,7 +755,8 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
                     noise_seed: Optional[int] = None, guidance_interval=None, consensus=None,
                     return_latents: bool = False, noise_keying: Optional[str] = None, init_video: Optional[np.ndarray] = None,
                     init_audio: Optional[np.ndarray] = None, strength: float = 1.0, mask=None,
-                    guide_seed: Optional[int] = None, resample=None) -> Optional[Dict[str, np.ndarray]]:
+                    guide_seed: Optional[int] = None, resample=None, sampler: Optional[str] = None,
+                    fifo: Optional[dict] = None) -> Optional[Dict[str, np.ndarray]]:
     """The body of the reference's ``main()`` (stream_infer.py:146-225) minus file I/O, with all windows batched.
 
     Returns {"audio": wav, "sr"} for a video prompt or {"video": frames uint8, "fps"} for an audio prompt.
@@ -574,9 +826,37 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     consensus they are keyed by canvas position like the guide's known noise (window offset = the engine's first window), so every
     window draws the same normals at a shared position: agreeing windows still agree after a jump, no consensus pass follows it, and
     the latents are the same bits for any ``max_windows_per_batch`` where the engines take the same kernels.
+    ``sampler`` (default None = ``streaming.sampler``, else "windows"; the argument wins): "windows" is everything above; "fifo"
+    generates the clip with FIFO diagonal denoising (``fifo_denoise``) behind the same front end.  The prompt windows are split and
+    encoded as above and made ONE prompt canvas (a uniform ``window_consensus`` pass, since each window was encoded alone, then
+    ``canvas_from_windows``); one engine of batch B runs the queue over the target canvas of P = (N_windows - 1)*hop + L latent
+    positions (``fifo_geometry`` gives every number and refuses a config that does not fit: the audio chunks must not overlap, the
+    prompt must have a whole number of latent positions per target slot, and the step count must be a multiple of the S - lookahead
+    stepping slots of a sample); the canvas is cut into the windows' latents (``windows_from_canvas``), which are decoded in batches of
+    ``max_windows_per_batch`` and cross-faded as above, so the output has the windows sampler's length and dtype.
+    ``fifo`` (or ``streaming.fifo``; the argument wins) = {"steps": the target's ``sampler_steps``, "lookahead": 0, "graph": False},
+    ``fifo_denoise``'s arguments; unknown keys are refused.  ``seed`` seeds the queue's start and entering noise (None: drawn once from
+    torch's global CPU generator), ``noise_seed`` the engine's step noise (``ddim_eta`` > 0 needs it).  The config's solver, eta and
+    guidance go to the engine; its per-sample CFG controls become ``fifo_denoise``'s slot controls: the guidance interval a
+    ``guidance_interval_table``, ``guidance_rescale`` a constant ``rescale_by_level``, ``sampling.apg`` the per-slot APG (a momentum
+    != 0 is refused: the queue has none).  An init clip is made one canvas like the prompt and guides the queue (``init_canvas``):
+    ``mask`` is passed whole, ``strength`` < 1 truncates the schedule (the truncated length must still divide) and starts every
+    position from the clip (``guide_start="init"``; without a mask everything is free afterwards), ``strength`` 0 returns the decoded
+    known canvas.  The entering slots are guided inside the shift's launch (``guided_shift=True``).  It runs eagerly on the plain queue:
+    ``fifo_denoise`` refuses it with ``graph`` True or a ``lookahead``.  Refused, before anything is encoded: ``shard=True``,
+    ``consensus``, ``noise_keying="canvas"``, ``resample`` and ``init_noise``.
+    ``return_latents`` adds "latents", the [N_windows, *latent] windows of the canvas, and "latent_canvas" [C, P, H, W] / [Ca, P].
     """
     # the latent guide's argument checks that need no device (the window count and the mask's shape follow the prompt split below)
     strength = P.check_init_args(prompt_modality, init_video, init_audio, strength, mask)
+    st = cfg.get("streaming", {})
+    if sampler is None:
+        sampler = st.get("sampler", "windows")
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
+    if sampler == "fifo":
+        fifo = _fifo_options(cfg, shard=shard, consensus=consensus, noise_keying=noise_keying, resample=resample, init_noise=init_noise,
+                             fifo=fifo)
     has_init = init_video is not None or init_audio is not None
     if has_init and shard:
         raise ValueError("an init clip with shard=True is not implemented: the known windows would need a second broadcast to the "
@@ -584,11 +864,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     init = P.init_clip_array(init_video, init_audio)
     pc = P.read_config(cfg, prompt_modality, guidance_interval=guidance_interval, resample=resample, has_init=has_init,
                        has_mask=mask is not None, noise_seed=noise_seed)
-    target, fps, sr, eta, sched = pc.target, pc.fps, pc.sr, pc.eta, pc.sched
-    st = cfg.get("streaming", {})
-    win_s, hop_s = float(st.get("window_seconds", 3.0)), float(st.get("hop_seconds", 1.0))
-    xfade_s = float(st.get("crossfade_seconds", 0.25))
-
+    target, eta, sched = pc.target, pc.eta, pc.sched
     if consensus is None:
         consensus = st.get("latent_consensus")
     if noise_keying is None:
@@ -624,46 +900,23 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     root = rank == 0
 
     # the prompt windows and the shape of their encoded form (known on every rank without encoding: only rank 0 runs the encoder)
-    if prompt_modality == "video":
-        if prompt_video is None:
-            raise ValueError("prompt_video frames required for prompt_modality=video")
-        chunks, win, hop = split_frames_into_windows(prompt_video, fps=fps, win_s=win_s, hop_s=hop_s)
-        zp_shape = (chunks.shape[0], pc.Cv, chunks.shape[1] // pc.t_down, chunks.shape[2] // pc.s_down, chunks.shape[3] // pc.s_down)
-        lat = (pc.Ca, pc.Fa)
-    else:
-        if prompt_audio is None:
-            raise ValueError("prompt_audio required for prompt_modality=audio")
-        chunks, win, hop = split_audio_into_windows(prompt_audio, sr=sr, win_s=win_s, hop_s=hop_s)
-        zp_shape = (chunks.shape[0], pc.Ca, pc.Fa)
-        T_in = int(round(cfg["data"]["clip_seconds"] * fps))
-        lat = (pc.Cv, max(1, T_in // pc.t_down), pc.H // pc.s_down, pc.W // pc.s_down)
+    chunks, zp_shape, lat = _prompt_windows(cfg, pc, prompt_modality, prompt_video, prompt_audio)
     n_prompt = P.prompt_tokens(pc, zp_shape)
     # the init clip's windows and the mask on the latent canvas, checked before anything is encoded
-    init_chunks = mask_w = None
-    if init is not None:
-        split = split_frames_into_windows if target == "video" else split_audio_into_windows
-        init_chunks = split(init, fps if target == "video" else sr, win_s, hop_s)[0]
-        if init_chunks.shape[0] != zp_shape[0]:
-            raise ValueError(f"the init clip splits into {init_chunks.shape[0]} windows, the prompt into {zp_shape[0]}: they must cover "
-                             "the same long clip")
+    init_chunks = _init_windows(cfg, pc, init, zp_shape[0])
+    if sampler == "fifo":
+        mods = dict(vid_vae=vid_vae, aud_codec=aud_codec, adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim)
+        return _stream_generate_fifo(cfg, pc, mods, device, prompt_modality, chunks, zp_shape, lat, init_chunks, mask, strength, fifo,
+                                     seed=seed, noise_seed=noise_seed, guide_seed=guide_seed, return_latents=return_latents,
+                                     max_windows_per_batch=max_windows_per_batch)
+    mask_w = None
     if mask is not None:
         g_hop, g_L = (cons_hop, cons_L) if consensus else latent_hop(cfg, target)
-        if lat[1] != g_L:
-            raise ValueError(f"mask: the target latent has {lat[1]} positions along its sliding axis (data.clip_seconds), a window of "
-                             f"streaming.window_seconds has {g_L}: they must be equal")
-        mask_canvas_shape = (lat[0], (zp_shape[0] - 1) * g_hop + g_L) + tuple(lat[2:])
-        mc = torch.as_tensor(mask).detach().to("cpu", torch.float32)
-        try:
-            mc = mc.expand(mask_canvas_shape)
-        except RuntimeError:
-            raise ValueError(f"mask shape {tuple(mc.shape)} does not broadcast to the latent canvas {mask_canvas_shape}") from None
-        if not bool(((mc >= 0) & (mc <= 1)).all()):
-            raise ValueError("mask values must lie in [0, 1]")
-        mask_w = windows_from_canvas(mc, g_L, g_hop)                       # [N_windows, *latent]: one mask per window
+        mask_w = windows_from_canvas(_canvas_mask(mask, lat, zp_shape[0], g_hop, g_L), g_L, g_hop)      # [N_windows, *latent]
     z_p, root_error = None, None
     if root:
         try:
-            z_p = P.encode_video(vid_vae, chunks, device) if prompt_modality == "video" else P.encode_audio(aud_codec, chunks, device)
+            z_p = _encode_windows(prompt_modality, vid_vae, aud_codec, chunks, device)
             if tuple(z_p.shape) != zp_shape:
                 if world > 1:       # the other ranks sized their buffers from the config
                     raise L.AvdError(f"encoded prompt windows have shape {tuple(z_p.shape)}, the config implies {zp_shape}")
@@ -706,10 +959,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     # the known windows of an init clip: encoded as one batch; under consensus made one canvas first (each window was encoded alone)
     known = None
     if init_chunks is not None:
-        known = P.encode_video(vid_vae, init_chunks, device) if target == "video" else P.encode_audio(aud_codec, init_chunks, device)
-        known = known.float().contiguous()
-        if tuple(known.shape) != (Nw, *lat):
-            raise ValueError(f"the init clip encodes to windows of shape {tuple(known.shape)}, the target's are {(Nw, *lat)}")
+        known = _encode_init(target, vid_vae, aud_codec, init_chunks, device, (Nw, *lat))
         if consensus:
             Fn.window_consensus(known, cons_hop, cons_w)
 
@@ -774,16 +1024,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         return za
 
     def decode_windows(z: torch.Tensor) -> torch.Tensor:
-        """finished latents of some windows -> what the stitcher takes: waveforms [n, L] float32 or frames [n, T, H, W, 3] uint8"""
-        if target == "audio":
-            if z.shape[0] == 0:
-                hop_a = int(getattr(aud_codec, "hop", 0)) or int(round(sr * float(cfg["data"]["clip_seconds"]))) // pc.Fa
-                return torch.empty(0, pc.Fa * hop_a, device=device)
-            return aud_codec.decode(z)[:, 0, :].contiguous()
-        if z.shape[0] == 0:
-            return torch.empty(0, lat[1] * pc.t_down, lat[2] * pc.s_down, lat[3] * pc.s_down, 3, dtype=torch.uint8, device=device)
-        x = vid_vae.decode(z).clamp(0, 1)                                         # [n,3,T,H,W]
-        return (x.permute(0, 2, 3, 4, 1) * 255.0).to(torch.uint8).contiguous()    # as the reference's astype(np.uint8)
+        return _decode_windows(cfg, pc, vid_vae, aud_codec, lat, z, device)
 
     if world > 1:
         if comm_device is None:
@@ -797,12 +1038,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         z_fin = denoise_consensus(z_p) if consensus else denoise(z_p, 0, Nw)
         out = decode_windows(z_fin)
 
-    if target == "audio":
-        w = torch.from_numpy(audio_fade_window(out.shape[1], int(round(sr * xfade_s))))
-        res = {"audio": crossfade_tensor(out, w, int(round(sr * hop_s))).cpu().numpy(), "sr": sr}
-    else:
-        w = torch.from_numpy(video_fade_window(out.shape[1], int(round(xfade_s * fps))))
-        res = {"video": crossfade_tensor(out, w, int(round(fps * hop_s))).cpu().numpy(), "fps": fps}
+    res = _stitch(cfg, pc, out)
     if return_latents:
         res["latents"] = z_fin.cpu().numpy()
     return res

@@ -36,11 +36,16 @@
               --e2e: fifo_denoise per finished slot with and without the control (table + rescale, table + APG), eager, the calls
               interleaved
 
+  --guided-shift  the guided FIFO queue shift ("Guided FIFO queue shift").  --kernels: the guided shift against the plain shift plus the
+              in-place guide pass on the tail slot, with and without history, at B = 8 and B = 32, beside the plain shift alone;
+              --e2e: fifo_denoise(init_canvas=) per finished slot with guided_shift off (a stand-alone tail pass per shift) and on,
+              beside the unguided queue, both solvers, eager, the calls interleaved
+
 Prints plain text: the records are profiles/fifo_kernels.txt and profiles/fifo_e2e.txt (ddim), profiles/fifo_dpm_kernels.txt and
 profiles/fifo_dpm_e2e.txt (both solvers in one session), profiles/fifo_graph_e2e.txt (--e2e with and without --graph),
 profiles/fifo_lookahead_kernels.txt and profiles/fifo_lookahead_e2e.txt (--lookahead 3), profiles/fifo_stochastic_kernels.txt and
 profiles/fifo_stochastic_e2e.txt (--stochastic), profiles/fifo_guide_kernels.txt (--guide), profiles/slot_cfg_kernels.txt and
-profiles/slot_cfg_e2e.txt (--slot-cfg)."""
+profiles/slot_cfg_e2e.txt (--slot-cfg), profiles/fifo_guided_shift_kernels.txt and profiles/fifo_guided_shift_e2e.txt (--guided-shift)."""
 import argparse
 import ctypes as C
 import statistics
@@ -73,6 +78,7 @@ ap.add_argument("--lookahead", type=int, default=0, metavar="CTX", help="FIFO lo
 ap.add_argument("--stochastic", action="store_true", help="eta > 0 with clip-keyed slot noise beside eta = 0, both solvers")
 ap.add_argument("--guide", action="store_true", help="the clip-keyed latent guide beside the unguided slot update and queue")
 ap.add_argument("--slot-cfg", action="store_true", help="the slot CFG control beside the plain slot update and queue")
+ap.add_argument("--guided-shift", action="store_true", help="the guided queue shift beside the plain shift followed by the tail slot's pass")
 args = ap.parse_args()
 if not 0 <= args.lookahead < 6:
     raise SystemExit("--lookahead CTX must lie in [0, 6)")
@@ -209,6 +215,91 @@ if args.slot_cfg and args.e2e:
                   f"; per finished slot {per[name] * 1e3:.3f}, ramp and start {(whole[K] - K * per[name]) * 1e3:.1f}")
         for name in ("rescale", "apg"):
             print(f"  {'':8s} per finished slot, {name} against plain: {(per[name] - per['plain']) * 1e3:+.3f} ms (x {per[name] / per['plain']:.3f})")
+    sys.exit(0)
+
+if args.guided_shift and args.kernels:
+    S, sl = 6, 2
+    g = torch.Generator().manual_seed(0)
+    ABAR_D = ABAR.to(dev)
+    known = torch.randn(8, 32 * 12 + 2 * sl, 32, 32, generator=g).to(dev)      # the clip under the largest queue and its entering slot
+    mask = torch.rand(known.shape, generator=g).to(dev)
+    guide = dict(known=known, mask=mask, seed=3, alpha_bar=ABAR_D)
+    SHIFT, HIST, PASS = "fifo_shift_kernel<4>", "fifo_shift_kernel<4, HistShift>", "clip_guide_slots_kernel<4>"
+    rows = []
+    for b in (8, 32):
+        zz, hh, ho = (torch.randn(b, 8, 12, 32, 32, generator=g).to(dev) for _ in range(3))
+        tail = torch.full((b, S), Fn.SLOT_LEAVE, dtype=torch.long, device=dev)
+        tail[b - 1, S - 1] = 999
+        c = b * S                                               # the entering clip slot of a queue that holds slots 0 .. b * S - 1
+        shift = lambda zz=zz, c=c: Fn.fifo_shift(zz, c, 7, 999, sl)
+        shift_h = lambda zz=zz, hh=hh, ho=ho, c=c: Fn.fifo_shift(zz, c, 7, 999, sl, hist=hh, hist_out=ho)
+        tail_pass = lambda zz=zz, tail=tail: Fn.clip_guide_slots(known, tail, ABAR_D, zz, mask, first=1, out=zz, slot_len=sl, seed=3)
+        rows += [(f"B={b}: plain shift (a)", SHIFT, shift), (f"B={b}: tail slot's guide pass, in place", PASS, tail_pass),
+                 (f"B={b}: guided shift", "fifo_shift_kernel<4, GuideShift>", lambda zz=zz, c=c: Fn.fifo_shift(zz, c, 7, 999, sl, guide=guide)),
+                 (f"B={b}: plain shift (b)", SHIFT, shift), (f"B={b}: shift with history (a)", HIST, shift_h),
+                 (f"B={b}: guided shift with history", "fifo_shift_kernel<4, HistShift, GuideShift>",
+                  lambda zz=zz, hh=hh, ho=ho, c=c: Fn.fifo_shift(zz, c, 7, 999, sl, hist=hh, hist_out=ho, guide=guide)),
+                 (f"B={b}: shift with history (b)", HIST, shift_h)]
+    for _, _, fn in rows:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    res = {name: [] for name, _, _ in rows}
+    for _ in range(args.rounds):
+        for name, tag, fn in rows:
+            res[name].append(per_launch_us(tag, fn, args.launches))
+    print(f"C3 geometry (latent [B, 8, 12, 32, 32], S = {S} slots of {sl}), a fractional mask canvas: the guided queue shift against the "
+          f"plain shift and the stand-alone guide pass on the entering tail slot (in place), with and without the solver history: "
+          f"{args.rounds} interleaved rounds of {args.launches} launches, microseconds per launch (launch events)")
+    for name, _, _ in rows:
+        v = res[name]
+        print(f"  {name:44s} " + " ".join(f"{x:8.2f}" for x in v) + f"   median {statistics.median(v):8.2f}")
+    med = {name: statistics.median(v) for name, v in res.items()}
+    for b in (8, 32):
+        two = med[f"B={b}: plain shift (a)"] + med[f"B={b}: tail slot's guide pass, in place"]
+        twoh = med[f"B={b}: shift with history (a)"] + med[f"B={b}: tail slot's guide pass, in place"]
+        print(f"  B={b}: shift + tail pass {two:.2f} -> guided shift {med[f'B={b}: guided shift']:.2f}; with history {twoh:.2f} -> "
+              f"{med[f'B={b}: guided shift with history']:.2f} (kernel time; the saved launch itself is host time, see --e2e)")
+    sys.exit(0)
+
+if args.guided_shift and args.e2e:
+    S, K = 6, args.slots_out
+    g = torch.Generator().manual_seed(1)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    print(f"fifo_denoise with init_canvas (frames kept on a third of the clip): the entering slot guided by a stand-alone pass after every "
+          f"shift (guided_shift=False) and inside the shift's launch (guided_shift=True), beside the unguided queue; S = {S} (C3 latent, "
+          f"8 layers, bf16x3, eager), {args.rounds} rounds, the calls interleaved, {K} and {2 * K} slots out; milliseconds")
+    for solver, eta, n in (("ddim", 0.0, 48), ("dpmpp_2m", 0.0, 18)):
+        sched = su.make_sampling_schedule(1000, n)
+        canvas_p = torch.randn(8, 25 * (n + 2 * K) + 148, generator=g).to(dev)
+        eng = build(8, n // S, solver=solver)
+        known = torch.randn(8, 2 * K * 2, 32, 32, generator=g).to(dev)
+        mask = A.sampler.canvas_frame_mask(known.shape, 0, known.shape[1] // 3)
+        init = dict(init_canvas=known, mask=mask, guide_seed=3)
+        kinds = [("unguided", {}), ("tail pass", dict(init, guided_shift=False)), ("guided shift", dict(init, guided_shift=True))]
+        outs = [A.fifo_denoise(eng, canvas_p, 25, sched, 4, 5, **kw) for _, kw in kinds]      # warm-up
+        assert torch.equal(outs[1], outs[2])
+        ts_ = {(name, K_): [] for name, _ in kinds for K_ in (K, 2 * K)}
+        for _ in range(args.rounds):
+            for K_ in (K, 2 * K):
+                for name, kw in kinds:
+                    ts_[name, K_].append(timed(lambda: A.fifo_denoise(eng, canvas_p, 25, sched, K_, 5, **kw)))
+        per = {}
+        for name, _ in kinds:
+            whole = {K_: statistics.median(ts_[name, K_]) for K_ in (K, 2 * K)}
+            per[name] = (whole[2 * K] - whole[K]) / K
+            print(f"  {solver:8s} n = {n}, B = {n // S}, {name:12s}: " +
+                  "; ".join(f"{K_} out " + " ".join(f"{t * 1e3:7.1f}" for t in ts_[name, K_]) for K_ in (K, 2 * K)) +
+                  f"; per finished slot {per[name] * 1e3:.3f}, ramp and start {(whole[K] - K * per[name]) * 1e3:.1f}")
+        print(f"  {'':8s} per finished slot, guided shift against tail pass: {(per['guided shift'] - per['tail pass']) * 1e6:+.1f} us "
+              f"(x {per['guided shift'] / per['tail pass']:.4f})")
     sys.exit(0)
 
 if args.guide and args.kernels:
