@@ -560,6 +560,34 @@ int avd_slot_tables_select(const int64_t* tab0, const int64_t* tab1, const int64
  * same bits either way.  Checked (AVD_EINVAL): positive dims, B*slots and prompt_len fit an int, out does not overlap the canvas. */
 int avd_fifo_prompt_gather_f32(const float* canvas, const int32_t* cursor, float* out, int B, int slots, int prompt_hop, int64_t outer,
                                int64_t P, int64_t prompt_len, int64_t inner, avd_stream_t stream);
+/* ---- fractional prompt hop (a public contract): the prompt gather for a prompt that has a rational number of positions per target
+ * slot (a video prompt under an audio target: 12 * 4 / 150 = 8 / 25 at the shipped geometry).  The hop is a reduced fraction num / den
+ * of prompt positions per target slot, 1 <= num, den < 2^31.  For the target slot with clip index q (any int64 with |q| < 2^31;
+ * negative in the lookahead queue), in 64-bit integers:
+ *     i0  = floor(q * num / den)      (a floor division, also for q < 0)
+ *     rem = q * num - i0 * den        (in [0, den))
+ * Row l (0 <= l < prompt_len) of the slot's prompt window is then, by `interp`:
+ *   0, "nearest":  canvas position i0 + l + (2 * rem >= den ? 1 : 0): real latents only, the window lags or leads the slot by at most
+ *                  half a position; a tie (2 * rem == den) rounds up.
+ *   1, "linear":   with a = canvas[i0 + l] and b = canvas[i0 + l + 1] the value a + f * (b - a), evaluated in fp32 in that order
+ *                  without contraction, f = (float)rem / (float)den (one correctly rounded fp32 division).  When rem == 0 the value
+ *                  is a itself and b is not read (an inf or NaN neighbour does not leak).
+ * In both modes a position < 0 or >= P reads as 0, in either operand, and is compared before it is loaded: no q makes the kernel leave
+ * the canvas, and the last in-canvas row of a linear window blends toward 0.  den == 1 gives, in both modes, the bits of
+ * avd_fifo_prompt_gather_f32.  Which mode serves a trained model better is the user's choice; it cannot be measured on synthetic
+ * weights.  The pure-torch restatement is stream_infer.fifo_prompt_windows(prompt_den=, prompt_interp=).
+ * avd_fifo_prompt_gather_frac_f32: out [B, outer, prompt_len, inner] from the canvas [outer, P, inner]; sample k holds clip slot
+ * q = first + max(*cursor, 0) + k*stride.  `cursor` may be null and then reads as 0 (the eager drivers pass m by value in `first`);
+ * `first` may be negative and `stride` below the slots of a sample, so one entry serves the plain queue (first = 0, stride = slots,
+ * m off the cursor), the eager loop (first = m) and the lookahead's overlapping windows (first = m - ctx, stride = slots - ctx).  A
+ * cursor from which sample 0 starts at or past P gives zeros everywhere, as every larger one does: the kernel clamps the cursor there,
+ * which changes no value and keeps q * num in range whatever the cursor holds.  q, i0 and rem are computed once per lane.  16-byte
+ * lanes when inner % 4 == 0 and both bases are 16-byte aligned, one element per lane otherwise (every audio prompt: inner = 1); same
+ * bits either way.  Checked before the launch (AVD_EINVAL): non-null canvas and out, positive dims, num >= 1, den >= 1, interp 0 or 1,
+ * |first|, B*stride and prompt_len below 2^31, the largest |q| of the call times num below 2^62, out does not overlap the canvas. */
+int avd_fifo_prompt_gather_frac_f32(const float* canvas, const int32_t* cursor, float* out, int B, int64_t first, int stride, int num,
+                                    int den, int interp, int64_t outer, int64_t P, int64_t prompt_len, int64_t inner,
+                                    avd_stream_t stream);
 /* FIFO queue shift off a device cursor: (z_in -> z_out) is avd_fifo_shift_f32's with c = c0 + *cursor, the same kernel body and the
  * same bits (c only keys the tail's noise draw, modulo 2^32: it addresses nothing).  The finished head is written straight into slot
  * *cursor of the clip canvas clip [outer, n_out*slot_len, inner] — clip[o, *cursor*slot_len + j, i] = z_in slot 0 [o, j, i], a strided

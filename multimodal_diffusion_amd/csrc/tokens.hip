@@ -961,6 +961,66 @@ __global__ __launch_bounds__(256) void fifo_prompt_gather_kernel(const float* __
         out[idx] = p < P ? canvas[(o * P + p) * inner + i] : 0.f;
 }
 
+// The gather above on a rational hop num / den (include/avdiff_hip.h, "fractional prompt hop"): sample b holds clip slot q = first +
+// clamp(*cursor, 0, m_cap) + b * stride (no cursor: q = first + b * stride), i0 = floor(q * num / den), rem = q * num - i0 * den.
+// m_cap is the host's: from it on every window of the call lies past the canvas end, so the clamp changes no value and keeps q * num
+// below 2^63 whatever the cursor holds.  q, i0 and rem are per sample: once per lane, from b.  A position is compared with [0, P)
+// before it is loaded, in either operand.
+constexpr int kPromptNearest = 0, kPromptLinear = 1;
+
+__device__ __forceinline__ float prompt_lerp(float a, float b, float f) {
+#pragma clang fp contract(off)
+    return a + f * (b - a);
+}
+
+template <int V, int INTERP>
+__global__ __launch_bounds__(256) void fifo_prompt_gather_frac_kernel(const float* __restrict__ canvas, float* __restrict__ out,
+                                                                      const int32_t* __restrict__ cursor, int64_t m_cap, int64_t first,
+                                                                      int64_t stride, int64_t num, int64_t den, int64_t outer, int64_t P,
+                                                                      int64_t len, int64_t inner, int64_t n) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    int64_t m = 0;
+    if (cursor) {
+        m = *cursor;
+        m = m < 0 ? 0 : (m > m_cap ? m_cap : m);
+    }
+    const int64_t iv = inner / V;
+    const int64_t i = (idx % iv) * V;
+    int64_t r = idx / iv;
+    const int64_t l = r % len;
+    r /= len;
+    const int64_t o = r % outer, b = r / outer;
+    const int64_t t = (first + m + b * stride) * num;      // |q| * num < 2^62 (the host checks)
+    int64_t i0 = t / den, rem = t - i0 * den;
+    if (rem < 0) {      // C++ division truncates: make it a floor
+        rem += den;
+        --i0;
+    }
+    int64_t pa = i0 + l;
+    if constexpr (INTERP == kPromptNearest) pa += 2 * rem >= den ? 1 : 0;
+    const bool in_a = pa >= 0 && pa < P;
+    const bool blend = INTERP == kPromptLinear && rem != 0;      // rem == 0: a itself, b is not read
+    const bool in_b = blend && pa + 1 >= 0 && pa + 1 < P;
+    const float f = blend ? (float)rem / (float)den : 0.f;
+    const float* row = canvas + o * P * inner + i;      // position p of this lane is row + p * inner, formed under in_a / in_b only
+    if constexpr (V == 4) {
+        f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (in_a) a = *reinterpret_cast<const f32x4*>(row + pa * inner);
+        if (blend) {
+            f32x4 nb = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (in_b) nb = *reinterpret_cast<const f32x4*>(row + (pa + 1) * inner);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] = prompt_lerp(a[j], nb[j], f);
+        }
+        *reinterpret_cast<f32x4*>(out + idx * 4) = a;
+    } else {
+        float a = in_a ? row[pa * inner] : 0.f;
+        if (blend) a = prompt_lerp(a, in_b ? row[(pa + 1) * inner] : 0.f, f);
+        out[idx] = a;
+    }
+}
+
 __global__ __launch_bounds__(256) void ddim_kernel(const float* __restrict__ x, const float* __restrict__ eps,
                                                    const int64_t* __restrict__ t_now, const int64_t* __restrict__ t_prev,
                                                    const float* __restrict__ abar, int T_train, float eta,
@@ -3590,6 +3650,55 @@ extern "C" int avd_fifo_prompt_gather_f32(const float* canvas, const int32_t* cu
         hipLaunchKernelGGL(fifo_prompt_gather_kernel<1>, grid, dim3(256), 0, st, canvas, out, cursor, slots, (int64_t)prompt_hop, outer, P,
                            prompt_len, inner, n);
     AVD_CHECK_LAUNCH("fifo_prompt_gather");
+    return AVD_OK;
+}
+extern "C" int avd_fifo_prompt_gather_frac_f32(const float* canvas, const int32_t* cursor, float* out, int B, int64_t first, int stride,
+                                               int num, int den, int interp, int64_t outer, int64_t P, int64_t prompt_len, int64_t inner,
+                                               avd_stream_t stream) {
+    AVD_REQUIRE(canvas && out, AVD_EINVAL, "fifo_prompt_gather_frac: null pointer");
+    AVD_REQUIRE(B > 0 && stride > 0 && outer > 0 && P > 0 && prompt_len > 0 && inner > 0, AVD_EINVAL,
+                "fifo_prompt_gather_frac: bad dims (B %d, stride %d, outer %lld, P %lld, prompt_len %lld, inner %lld)", B, stride,
+                (long long)outer, (long long)P, (long long)prompt_len, (long long)inner);
+    AVD_REQUIRE(num >= 1 && den >= 1, AVD_EINVAL, "fifo_prompt_gather_frac: the hop num / den needs num >= 1 and den >= 1 (got %d / %d)", num,
+                den);
+    AVD_REQUIRE(interp == kPromptNearest || interp == kPromptLinear, AVD_EINVAL,
+                "fifo_prompt_gather_frac: interp must be 0 (nearest) or 1 (linear), got %d", interp);
+    AVD_REQUIRE(first > -(1ll << 31) && first < (1ll << 31) && (int64_t)B * stride <= 0x7fffffff && prompt_len <= 0x7fffffff, AVD_EINVAL,
+                "fifo_prompt_gather_frac: |first| %lld, B %d * stride %d and prompt_len %lld must be below 2^31", (long long)first, B, stride,
+                (long long)prompt_len);
+    AVD_REQUIRE((double)outer * (double)P * (double)inner < 9.0e18 && (double)B * (double)outer * (double)prompt_len * (double)inner < 9.0e18,
+                AVD_EUNSUPPORTED, "fifo_prompt_gather_frac: too many values");
+    // the cursor's clamp: from m_cap on sample 0, the first of the call, starts at or past P, so every larger cursor gives the same zeros
+    __int128 cap = ((__int128)P * den + num - 1) / num - first;
+    cap = cap < 0 ? 0 : (cap > 0x7fffffff ? 0x7fffffff : cap);
+    const int64_t m_cap = cursor ? (int64_t)cap : 0;
+    const __int128 q_hi = (__int128)first + m_cap + (__int128)(B - 1) * stride, q_lo = first;
+    const __int128 q_abs = (q_hi < 0 ? -q_hi : q_hi) > (q_lo < 0 ? -q_lo : q_lo) ? (q_hi < 0 ? -q_hi : q_hi) : (q_lo < 0 ? -q_lo : q_lo);
+    AVD_REQUIRE(q_abs * num < ((__int128)1 << 62), AVD_EINVAL,
+                "fifo_prompt_gather_frac: the largest clip slot %lld times num %d leaves the 64-bit range of the walk", (long long)q_abs, num);
+    const int64_t n_c = outer * P * inner, n_o = (int64_t)B * outer * prompt_len * inner;
+    AVD_REQUIRE(!(out < canvas + n_c && canvas < out + n_o), AVD_EINVAL, "fifo_prompt_gather_frac: out must not overlap the prompt canvas");
+    const bool vec = inner % 4 == 0 && aligned16(canvas) && aligned16(out);
+    const int64_t n = n_o / (vec ? 4 : 1);
+    AVD_REQUIRE((n + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "fifo_prompt_gather_frac: %lld lanes are too many for one launch",
+                (long long)n);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    static const int tags[4] = {prof_tag_id("fifo_prompt_gather_frac_kernel<1, nearest>"), prof_tag_id("fifo_prompt_gather_frac_kernel<4, nearest>"),
+                                prof_tag_id("fifo_prompt_gather_frac_kernel<1, linear>"), prof_tag_id("fifo_prompt_gather_frac_kernel<4, linear>")};
+    ProfScope prof(tags[(interp == kPromptLinear ? 2 : 0) + (vec ? 1 : 0)], 4.0 * (interp == kPromptLinear ? 3.0 : 2.0) * (double)n_o, st);
+#define AVD_PROMPT_FRAC(V, I)                                                                                                         \
+    hipLaunchKernelGGL((fifo_prompt_gather_frac_kernel<V, I>), grid, dim3(256), 0, st, canvas, out, cursor, m_cap, first, (int64_t)stride, \
+                       (int64_t)num, (int64_t)den, outer, P, prompt_len, inner, n)
+    if (interp == kPromptLinear) {
+        if (vec) AVD_PROMPT_FRAC(4, kPromptLinear);
+        else AVD_PROMPT_FRAC(1, kPromptLinear);
+    } else {
+        if (vec) AVD_PROMPT_FRAC(4, kPromptNearest);
+        else AVD_PROMPT_FRAC(1, kPromptNearest);
+    }
+#undef AVD_PROMPT_FRAC
+    AVD_CHECK_LAUNCH("fifo_prompt_gather_frac");
     return AVD_OK;
 }
 extern "C" int avd_cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now,

@@ -1008,6 +1008,52 @@ def fifo_prompt_gather(prompt_canvas: Tensor, cursor: Tensor, B: int, S: int, pr
     return out
 
 
+PROMPT_INTERPS = ("nearest", "linear")      # avd_fifo_prompt_gather_frac_f32's `interp`, by index
+
+
+def check_prompt_frac(num: int, den: int, interp: Optional[str], what: str = "prompt_hop") -> None:
+    """the hop num / den and the mode of a fractional prompt walk (include/avdiff_hip.h, "fractional prompt hop"): ValueError unless
+    both are ints in [1, 2**31), ``interp`` is None or one of ``PROMPT_INTERPS``, and a den > 1 comes with a mode"""
+    for name, v in ((what, num), ("prompt_den", den)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v < 2 ** 31:
+            raise ValueError(f"{name} must be an int in [1, 2**31), got {v!r}")
+    if interp is not None and interp not in PROMPT_INTERPS:
+        raise ValueError(f"prompt_interp must be None or one of {PROMPT_INTERPS}, got {interp!r}")
+    if den > 1 and interp is None:
+        raise ValueError(f"prompt_den {den} > 1 is a fractional prompt hop: it needs prompt_interp, one of {PROMPT_INTERPS}, to say how a "
+                         "window that starts between two prompt positions is read")
+
+
+def fifo_prompt_gather_frac(prompt_canvas: Tensor, cursor: Optional[Tensor], B: int, first: int, stride: int, num: int, den: int,
+                            interp: str, prompt_len: int, out: Optional[Tensor] = None) -> Tensor:
+    """``stream_infer.fifo_prompt_windows`` on a rational hop ``num / den`` in one launch (avd_fifo_prompt_gather_frac_f32;
+    include/avdiff_hip.h, "fractional prompt hop"): sample k is the prompt window of clip slot q = first + max(*cursor, 0) + k*stride,
+    read by ``interp`` ("nearest" or "linear"); zeros before the canvas start and past its end.  ``cursor``: one int32 on the device,
+    or None (reads as 0: pass m in ``first``).  ``first`` may be negative.  Shapes and ``out`` as ``fifo_prompt_gather``; ``den == 1``
+    gives its bits in either mode."""
+    pc = prompt_canvas
+    if not (isinstance(pc, Tensor) and pc.is_cuda and pc.dtype == torch.float32 and pc.is_contiguous() and pc.dim() in (2, 4)):
+        raise ValueError("a prompt canvas is a contiguous float32 device tensor [C, P, H, W] (video) or [Ca, P] (audio)")
+    for name, v in (("B", B), ("stride", stride), ("prompt_len", prompt_len)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v < 2 ** 31:
+            raise ValueError(f"{name} must be an int in [1, 2**31), got {v!r}")
+    if isinstance(first, bool) or not isinstance(first, int) or not -2 ** 31 < first < 2 ** 31:
+        raise ValueError(f"first must be an int with |first| < 2**31, got {first!r}")
+    check_prompt_frac(num, den, interp, "num")
+    if interp is None:
+        raise ValueError(f"interp must be one of {PROMPT_INTERPS}, got None")
+    shape = (B, pc.shape[0], prompt_len) + tuple(pc.shape[2:])
+    if out is None:
+        out = torch.empty(shape, device=pc.device, dtype=torch.float32)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape and out.device == pc.device):
+        raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on the canvas's device")
+    inner = pc.shape[2] * pc.shape[3] if pc.dim() == 4 else 1
+    cur = None if cursor is None else _cursor(cursor, pc.device).data_ptr()
+    L.check(L.lib().avd_fifo_prompt_gather_frac_f32(pc.data_ptr(), cur, out.data_ptr(), B, first, stride, num, den,
+                                                    PROMPT_INTERPS.index(interp), pc.shape[0], pc.shape[1], prompt_len, inner, _st(pc)))
+    return out
+
+
 def fifo_shift_cursor(z: Tensor, c0: int, cursor: Tensor, clip: Tensor, seed: int, t: int, slot_len: int, out: Optional[Tensor] = None,
                       hist: Optional[Tensor] = None, hist_out: Optional[Tensor] = None):
     """``fifo_shift`` with the clip slot on the device (avd_fifo_shift_cursor_f32 / _hist_f32; contract in include/avdiff_hip.h, "FIFO

@@ -108,8 +108,8 @@ class FifoQueue:
     """The state of one open FIFO queue (``DenoiseEngine.fifo_open``): the device cursors ``r`` (ramp iteration) and ``m`` (steady
     iteration), the uploaded tables (``ramp``: [n - 1, B*S] each; ``steady`` and the selected ``slot`` tables: [B, S] each; two, or
     three with t_last), the prompt canvas ``canvas_p`` and the prompt-latent buffer ``prompt``, the latent buffers ``z`` / ``other``,
-    the clip canvas ``clip``, and what the launches take by value: ``seed``, ``s0``, ``n`` (= c0), ``n_slots``, ``hop`` and
-    ``clip_first`` (0 on an eta > 0 engine with a noise_seed, whose steps key their noise by clip slot off ``m``; else None)."""
+    the clip canvas ``clip``, and what the launches take by value: ``seed``, ``s0``, ``n`` (= c0), ``n_slots``, ``hop``, ``frac``
+    ((prompt_den, prompt_interp) of a fractional prompt hop ``hop / prompt_den``, None on a whole one) and ``clip_first`` (0 on an eta > 0 engine with a noise_seed, whose steps key their noise by clip slot off ``m``; else None)."""
 
 
 class _CapturedPair:
@@ -1117,7 +1117,7 @@ class DenoiseEngine:
 
     # ---- FIFO queue with device cursors: an iteration as a fixed chain of launches (include/avdiff_hip.h, "FIFO device cursors") ----
     def fifo_open(self, prompt_canvas: torch.Tensor, prompt_hop: int, prompt_len: int, sched, n_slots: int,
-                  noise_seed: int) -> "FifoQueue":
+                  noise_seed: int, prompt_den: int = 1, prompt_interp: Optional[str] = None) -> "FifoQueue":
         """Open a FIFO queue (``stream_infer.fifo_denoise(graph=True)`` drives it) whose iterations read the ramp row r and the steady
         iteration m off two int32 device cursors, so that ``fifo_ramp`` and ``fifo_steady`` are fixed chains of launches on the
         current stream, the same eagerly and under ``fifo_capture``.  Uploads the plan's tables (``schedule_utils.fifo_plan``, with
@@ -1128,7 +1128,10 @@ class DenoiseEngine:
         sliding axis (``stream_infer.fifo_prompt_len``).  Refuses what ``step_slots`` refuses, before it allocates.
         On an eta > 0 engine with a ``noise_seed`` the queue is stochastic: its steps pass ``clip_first=0, clip_cursor=q.m`` (m is 0
         through the ramp), the step noise keyed by ``engine.noise_seed``; ``noise_seed`` here seeds the start and the entering noise.
-        The queue holds ``noise_seed``, c0 = n, ``n_slots``, the hops and every address: a captured pair is good for this queue only."""
+        The queue holds ``noise_seed``, c0 = n, ``n_slots``, the hops and every address: a captured pair is good for this queue only.
+        ``prompt_den`` > 1 with a ``prompt_interp`` (include/avdiff_hip.h, "fractional prompt hop") makes the hop ``prompt_hop /
+        prompt_den``: the prompt of m = 0 and ``fifo_steady``'s come from ``functional.fifo_prompt_gather_frac`` off the same cursor
+        (first = 0, stride = S).  ``prompt_den`` == 1 is the integer gather, launch for launch."""
         self._clip_refusal("fifo_open", "the replayed queue's chain of launches has no guided tail pass: the guided queue runs eagerly")
         B, S, sl = self.embed.B, self.slots, self.slot_len
         ramp_now, ramp_prev, steady_now, steady_prev = su.fifo_plan(sched, S)
@@ -1142,12 +1145,14 @@ class DenoiseEngine:
         for name, v in (("n_slots", n_slots), ("prompt_hop", prompt_hop), ("prompt_len", prompt_len)):
             if isinstance(v, bool) or not isinstance(v, int) or v < 1:
                 raise ValueError(f"{name} must be an int >= 1, got {v!r}")
+        Fn.check_prompt_frac(prompt_hop, prompt_den, prompt_interp)
         stochastic = self.eta > 0 and self.noise_seed is not None
         self._slot_refusals(self.solver == "dpmpp_2m", 0 if stochastic else None)
         dev = self.device
         q = FifoQueue()
         q.clip_first = 0 if stochastic else None      # eta > 0: the steps key their noise by clip slot, read off the cursor m
         q.n, q.n_slots, q.seed, q.hop, q.s0 = n, n_slots, noise_seed, prompt_hop, int(torch.as_tensor(sched).reshape(-1)[0])
+        q.frac = (prompt_den, prompt_interp) if prompt_den > 1 else None      # None: the integer gather
         if (n + n_slots) * sl > 2 ** 32:
             raise ValueError(f"(n {n} + n_slots {n_slots}) * slot_len {sl} exceeds the stream's 2**32 canvas positions")
         q.canvas_p = L.dev_f32(prompt_canvas.to(dev), "prompt canvas")
@@ -1168,9 +1173,17 @@ class DenoiseEngine:
         q.other = torch.empty_like(q.z)
         if multistep and self._hist_other is None:
             self._hist_other = torch.empty_like(self.x0_hist)
-        q.prompt = Fn.fifo_prompt_gather(q.canvas_p, q.m, B, S, prompt_hop, prompt_len)
+        q.prompt = self._fifo_gather(q, torch.empty((B, q.canvas_p.shape[0], prompt_len) + tuple(q.canvas_p.shape[2:]), device=dev,
+                                                    dtype=torch.float32))
         self.set_prompt(q.prompt)
         return q
+
+    def _fifo_gather(self, q: "FifoQueue", out: torch.Tensor) -> torch.Tensor:
+        """the prompt batch of the open queue's iteration *m into ``out``: one launch, the integer gather or the fractional one"""
+        B, S = self.embed.B, self.slots
+        if q.frac is None:
+            return Fn.fifo_prompt_gather(q.canvas_p, q.m, B, S, q.hop, out.shape[2], out=out)
+        return Fn.fifo_prompt_gather_frac(q.canvas_p, q.m, B, 0, S, q.hop, q.frac[0], q.frac[1], out.shape[2], out=out)
 
     def fifo_ramp(self, q: "FifoQueue", src: torch.Tensor, dst: torch.Tensor) -> None:
         """One ramp iteration of an open queue: select row *r of the ramp tables -> ``step_slots`` src -> dst (on a stochastic queue
@@ -1187,7 +1200,7 @@ class DenoiseEngine:
         for clip slots m .., read off the same cursor.  On "dpmpp_2m" the shift carries the history
         into the engine's other history buffer and the two swap, as in ``fifo_shift``: two iterations put ``x0_hist`` back."""
         B, S = self.embed.B, self.slots
-        Fn.fifo_prompt_gather(q.canvas_p, q.m, B, S, q.hop, q.prompt.shape[2], out=q.prompt)
+        self._fifo_gather(q, q.prompt)
         self._prompt_rows(self._prompt_tokens(q.prompt), self.Xp, temb=False)
         multistep = len(q.steady) == 3
         self.step_slots(z, q.steady[0], q.steady[1], out=tmp, t_last=q.steady[2] if multistep else None, clip_first=q.clip_first,

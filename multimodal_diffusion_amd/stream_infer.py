@@ -28,6 +28,7 @@ timestep, a queue of latent slots runs from nearly clean to pure noise, one mode
 from __future__ import annotations
 
 import contextlib
+import math
 from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
@@ -174,13 +175,20 @@ def canvas_from_windows(windows: torch.Tensor, hop: int) -> torch.Tensor:
 
 
 def fifo_prompt_windows(prompt_canvas: torch.Tensor, m: int, B: int, S: int, prompt_hop: int, prompt_len: int,
-                        stride: Optional[int] = None, first: Optional[int] = None) -> torch.Tensor:
+                        stride: Optional[int] = None, first: Optional[int] = None, prompt_den: int = 1,
+                        prompt_interp: Optional[str] = None) -> torch.Tensor:
     """The prompt batch of ``fifo_denoise`` before the step of steady iteration ``m``: sample k is prompt positions (m + k*S) *
     prompt_hop .. + prompt_len - 1 of the canvas's sliding axis ([C, P, H, W] video prompt, [Ca, P] audio prompt), zeros beyond the
     canvas end.  Returns [B, C, prompt_len, H, W] / [B, Ca, prompt_len] on the canvas's device (any device: pure slicing).
     ``stride`` (None = S) and ``first`` (None = m; may be negative) generalise it to sample k at positions (first + k*stride) *
     prompt_hop ..: the overlapping windows of the lookahead queue (stride = S - ctx, first = m - ctx).  Positions before the canvas
-    start are zeros like those past its end."""
+    start are zeros like those past its end.
+    ``prompt_den`` / ``prompt_interp`` (defaults 1 / None: everything above, call for call) walk the canvas by the rational hop
+    ``prompt_hop / prompt_den`` (include/avdiff_hip.h, "fractional prompt hop"; this function is its pure-torch statement and the CPU
+    reference of ``functional.fifo_prompt_gather_frac``): for the clip slot q = first + k*stride of sample k, i0 = floor(q * prompt_hop /
+    prompt_den) and rem = q * prompt_hop - i0 * prompt_den; "nearest" reads positions i0 + (2*rem >= prompt_den) .., "linear" the fp32
+    value a + f * (b - a) of positions i0 + l and i0 + l + 1 with f = float32(rem) / float32(prompt_den), a itself when rem == 0.  A
+    ``prompt_den`` > 1 without a mode is a ValueError."""
     if prompt_canvas.dim() not in (2, 4):
         raise ValueError(f"a prompt canvas is [C, P, H, W] (video) or [Ca, P] (audio), got shape {tuple(prompt_canvas.shape)}")
     if min(B, S, prompt_hop, prompt_len) < 1 or m < 0:
@@ -189,15 +197,37 @@ def fifo_prompt_windows(prompt_canvas: torch.Tensor, m: int, B: int, S: int, pro
     for name, v in (("stride", stride), ("first", first)):
         if v is not None and (isinstance(v, bool) or not isinstance(v, int) or (name == "stride" and v < 1)):
             raise ValueError(f"fifo_prompt_windows: {name} must be an int{' >= 1' if name == 'stride' else ''} or None, got {v!r}")
+    if prompt_den != 1 or prompt_interp is not None:
+        Fn.check_prompt_frac(prompt_hop, prompt_den, prompt_interp)
+        if prompt_interp == "linear" and prompt_canvas.dtype != torch.float32:
+            raise ValueError(f"prompt_interp='linear' blends in float32: the prompt canvas is {prompt_canvas.dtype}")
     stride = S if stride is None else stride
     first = m if first is None else first
     P_ = prompt_canvas.shape[1]
     out = prompt_canvas.new_zeros((B, prompt_canvas.shape[0], prompt_len) + tuple(prompt_canvas.shape[2:]))
-    for k in range(B):
-        p0 = (first + k * stride) * prompt_hop
-        lo, hi = max(p0, 0), min(p0 + prompt_len, P_)              # the canvas positions the window covers
+
+    def rows(dst: torch.Tensor, p0: int) -> torch.Tensor:
+        """canvas positions p0 .. p0 + prompt_len - 1 into ``dst`` (zeros to start with), where they lie on the canvas"""
+        lo, hi = max(p0, 0), min(p0 + prompt_len, P_)
         if hi > lo:
-            out[k, :, lo - p0:hi - p0] = prompt_canvas[:, lo:hi]
+            dst[:, lo - p0:hi - p0] = prompt_canvas[:, lo:hi]
+        return dst
+
+    for k in range(B):
+        if prompt_interp is None:
+            rows(out[k], (first + k * stride) * prompt_hop)
+            continue
+        t = (first + k * stride) * prompt_hop                      # Python ints: exact, and // is a floor for negative slots too
+        i0 = t // prompt_den
+        rem = t - i0 * prompt_den
+        if prompt_interp == "nearest":
+            rows(out[k], i0 + (1 if 2 * rem >= prompt_den else 0))
+        else:
+            a = rows(out[k], i0)
+            if rem:                                                # rem == 0: a itself, the neighbour is not read
+                b = rows(torch.zeros_like(a), i0 + 1)
+                f = (torch.tensor(rem, dtype=torch.float32) / prompt_den).to(a.device)      # divided on the CPU: one IEEE division
+                out[k] = a + f * (b - a)
     return out
 
 
@@ -225,7 +255,7 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
                  graph: Optional[bool] = False, lookahead: int = 0, context: Optional[torch.Tensor] = None,
                  init_canvas: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, guide_seed: int = 0,
                  guide_start: str = "noise", guidance_by_level=None, rescale_by_level=None, apg: Optional[dict] = None,
-                 guided_shift: bool = False) -> torch.Tensor:
+                 guided_shift: bool = False, prompt_den: int = 1, prompt_interp: Optional[str] = None) -> torch.Tensor:
     """FIFO diagonal denoising (FIFO-Diffusion, Kim et al. 2024, with latent partitioning): a clip of ``n_slots`` slots of
     ``engine.slot_len`` latent positions, denoised in a queue whose slots sit at different noise levels.  Returns the finished latent
     canvas [C, n_slots * slot_len, H, W] (video target) or [Ca, n_slots * slot_len] (audio target).
@@ -291,7 +321,16 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     ``init_canvas``) control the CFG combine per slot (``DenoiseEngine.set_slot_cfg``; include/avdiff_hip.h, "slot CFG control"): the
     first two are ``schedule_utils.level_table`` specs looked up at each slot's own noise level (``guidance_interval_table`` gives a
     guidance interval), ``apg`` {"norm_threshold":, "eta_parallel":} is per-slot adaptive projected guidance (no momentum).  They are
-    checked before anything is allocated; the engine's slot control is set for the call and cleared after it, also when it raises."""
+    checked before anything is allocated; the engine's slot control is set for the call and cleared after it, also when it raises.
+    ``prompt_den`` / ``prompt_interp`` (every driver; defaults 1 / None) make the prompt hop the fraction ``prompt_hop / prompt_den`` of
+    prompt positions per target slot (include/avdiff_hip.h, "fractional prompt hop"): a video prompt under an audio target, 8 / 25 at
+    the shipped geometry.  ``prompt_hop`` keeps its meaning and its check: it is the numerator.  ``prompt_interp`` "nearest" reads the
+    real latent rows nearest to where a slot's window starts, "linear" blends the two neighbouring rows in fp32; which serves a trained
+    model better cannot be measured on synthetic weights.  With ``prompt_den`` > 1 (which needs a mode: ValueError without) the eager
+    loops take each iteration's prompt from ``functional.fifo_prompt_gather_frac`` (the lookahead one with stride = h, first = m - ctx)
+    and ``set_prompt`` it, and ``graph=True`` launches the same gather off the cursor m (``DenoiseEngine.fifo_open(prompt_den=,
+    prompt_interp=)``).  Sample k is then conditioned on ``fifo_prompt_windows(..., prompt_den=, prompt_interp=)[k]``, bit for bit.
+    With ``prompt_den`` == 1 every driver is the one above, launch for launch, whatever the mode."""
     if not isinstance(engine, DenoiseEngine):
         raise TypeError("fifo_denoise drives a DenoiseEngine")
     scfg = None
@@ -301,6 +340,8 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
         raise ValueError(f"n_slots must be an int >= 1, got {n_slots!r}")
     if isinstance(prompt_hop, bool) or not isinstance(prompt_hop, int) or prompt_hop < 1:
         raise ValueError(f"prompt_hop must be an int >= 1 (prompt positions per target slot), got {prompt_hop!r}")
+    Fn.check_prompt_frac(prompt_hop, prompt_den, prompt_interp)
+    frac = (prompt_den, prompt_interp) if prompt_den > 1 else None      # None: today's integer walk
     if graph is not None and not isinstance(graph, bool):
         raise TypeError(f"graph must be True, False or None, got {graph!r}")
     if isinstance(lookahead, bool) or not isinstance(lookahead, int) or not 0 <= lookahead < engine.slots:
@@ -323,7 +364,7 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
         if graph:
             raise ValueError("fifo_denoise(lookahead > 0) runs eagerly: the lookahead queue has no device cursors, graph=True is refused")
         with _slot_cfg_scope(engine, scfg):
-            return _fifo_denoise_lookahead(engine, prompt_canvas, prompt_hop, sched, n_slots, noise_seed, lookahead, context)
+            return _fifo_denoise_lookahead(engine, prompt_canvas, prompt_hop, sched, n_slots, noise_seed, lookahead, context, frac)
     if context is not None:
         raise ValueError("context is the clean latent of the lookahead's context slots: it needs lookahead > 0")
     B, S, sl = engine.embed.B, engine.slots, engine.slot_len
@@ -343,12 +384,13 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
         graph = 2 * B * engine.N < engine.GRAPH_BELOW_ROWS
     if graph:
         with _slot_cfg_scope(engine, scfg):
-            return _fifo_denoise_graph(engine, engine.fifo_open(pc, prompt_hop, Lp, sched, n_slots, noise_seed))
+            return _fifo_denoise_graph(engine, engine.fifo_open(pc, prompt_hop, Lp, sched, n_slots, noise_seed, prompt_den=prompt_den,
+                                                                        prompt_interp=prompt_interp))
     if init_canvas is not None:
         engine.set_clip_guide(init_canvas, mask, guide_seed=guide_seed)
     try:
         with _slot_cfg_scope(engine, scfg):
-            return _fifo_denoise_eager(engine, pc, prompt_hop, Lp, sched, n_slots, noise_seed, guide_start == "init", guided_shift)
+            return _fifo_denoise_eager(engine, pc, prompt_hop, Lp, sched, n_slots, noise_seed, guide_start == "init", guided_shift, frac)
     finally:
         if init_canvas is not None:
             engine.clear_clip_guide()
@@ -368,11 +410,11 @@ def _slot_cfg_scope(engine: DenoiseEngine, checked):
 
 
 def _fifo_denoise_eager(engine: DenoiseEngine, pc: torch.Tensor, prompt_hop: int, Lp: int, sched, n_slots: int, noise_seed: int,
-                        everywhere: bool, guided_shift: bool = False) -> torch.Tensor:
+                        everywhere: bool, guided_shift: bool = False, frac=None) -> torch.Tensor:
     """``fifo_denoise``'s eager loop over the plain queue; under ``engine.set_clip_guide`` the guided one (the contract is in
     ``fifo_denoise``): the start and every entering tail slot go through ``functional.clip_guide_slots`` at s_0 — with ``guided_shift``
     the tail slot inside the shift's own launch (``engine.fifo_shift(guided=)``) — and the steps are keyed by the clip slot at queue
-    slot 0 at any eta."""
+    slot 0 at any eta.  ``frac`` = (prompt_den, prompt_interp) takes the prompt from the fractional gather instead of the slices."""
     B, S, sl = engine.embed.B, engine.slots, engine.slot_len
     ramp_now, ramp_prev, steady_now, steady_prev = su.fifo_plan(sched, S)
     n = ramp_now.shape[0] + 1
@@ -384,7 +426,8 @@ def _fifo_denoise_eager(engine: DenoiseEngine, pc: torch.Tensor, prompt_hop: int
     ramp_last, steady_last = (t.to(dev) for t in su.fifo_plan_last(sched, S)) if multistep else (None, None)
     z = Fn.canvas_noise(noise_seed, torch.full((B,), s0, dtype=torch.long, device=dev), engine.latent_shape, L_)
     other = torch.empty_like(z)
-    engine.set_prompt(fifo_prompt_windows(pc, 0, B, S, prompt_hop, Lp))
+    windows = _fifo_prompt_source(pc, B, S, prompt_hop, Lp, S, 0, frac)
+    engine.set_prompt(windows(0))
     first, stride = _fifo_clip_keying(engine, S, 0)
     clip = engine._clip
     if clip is not None:      # the guide reads clip positions at any eta: slot 0 of sample 0 holds clip slot m
@@ -401,13 +444,22 @@ def _fifo_denoise_eager(engine: DenoiseEngine, pc: torch.Tensor, prompt_hop: int
     canvas = torch.empty((outer, n_slots * sl) + tuple(engine.latent_shape[3:]), device=dev, dtype=torch.float32)
     for m in range(n_slots):
         if m:
-            engine.set_prompt(fifo_prompt_windows(pc, m, B, S, prompt_hop, Lp))
+            engine.set_prompt(windows(m))
         other = engine.step_slots(z, tabs[2], tabs[3], out=other, t_last=steady_last, clip_first=first(m), clip_stride=stride)
         z, popped = engine.fifo_shift(other, n + m, s0, seed=noise_seed, guided=guided)      # guided: clip slot n + m enters at q(s_0)
         if clip is not None and guided is None:      # the entering tail slot alone: clip slot n + m, now that clip slot m + 1 is at queue slot 0
             Fn.clip_guide_slots(clip[0], tail, ab, z, clip[1], first=m + 1, out=z, **guide)
         canvas[:, m * sl:(m + 1) * sl] = popped
     return canvas
+
+
+def _fifo_prompt_source(pc: torch.Tensor, B: int, S: int, prompt_hop: int, Lp: int, stride: int, ctx: int, frac):
+    """m -> the prompt batch of the eager drivers' steady iteration m, sample k under clip slot m - ctx + k * stride: slices of the canvas
+    (``fifo_prompt_windows``) on a whole hop, one ``functional.fifo_prompt_gather_frac`` launch with ``frac`` = (prompt_den,
+    prompt_interp)"""
+    if frac is None:
+        return lambda m: fifo_prompt_windows(pc, m, B, S, prompt_hop, Lp, stride=stride, first=m - ctx)
+    return lambda m: Fn.fifo_prompt_gather_frac(pc, None, B, m - ctx, stride, prompt_hop, frac[0], frac[1], Lp)
 
 
 def _fifo_clip_keying(engine: DenoiseEngine, S: int, ctx: int):
@@ -421,7 +473,7 @@ def _fifo_clip_keying(engine: DenoiseEngine, S: int, ctx: int):
 
 
 def _fifo_denoise_lookahead(engine: DenoiseEngine, prompt_canvas, prompt_hop: int, sched, n_slots: int, noise_seed: int, ctx: int,
-                            context: Optional[torch.Tensor]) -> torch.Tensor:
+                            context: Optional[torch.Tensor], frac=None) -> torch.Tensor:
     """``fifo_denoise(lookahead=ctx > 0)``: the eager loop over overlapping windows (the contract is in ``fifo_denoise``)"""
     B, S, sl = engine.embed.B, engine.slots, engine.slot_len
     h = S - ctx
@@ -458,7 +510,7 @@ def _fifo_denoise_lookahead(engine: DenoiseEngine, prompt_canvas, prompt_hop: in
     queue = torch.cat([head, Fn.canvas_noise(noise_seed, t0, (1, outer, n * sl) + hw, n * sl)[0]], 1)
     z = windows_from_canvas(queue, L_, h * sl)
     other = torch.empty_like(z)
-    windows = lambda m: fifo_prompt_windows(pc, m, B, S, prompt_hop, Lp, stride=h, first=m - ctx)
+    windows = _fifo_prompt_source(pc, B, S, prompt_hop, Lp, h, ctx, frac)
     engine.set_prompt(windows(0))
     for r in range(n - 1):
         other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other, t_last=ramp_last[r] if multistep else None, clip_first=first(0),
@@ -604,21 +656,29 @@ class FifoGeometry(NamedTuple):
     L_p: int
     slot_len: int       # latent positions per slot: the tube's t (video target) or the chunk length (audio target)
     S: int              # slots per sample; the engine's sliding length is S * slot_len <= L_t
-    prompt_hop: int     # prompt positions per target slot
+    prompt_hop: int     # prompt positions per target slot; with ``prompt_den`` > 1 the numerator of the reduced fraction
     h: int              # stepping slots per sample, S - lookahead
     B: int              # the engine's batch, steps // h
     P: int              # the target canvas' positions, (n_windows - 1) * hop_t + L_t
     n_slots: int        # ceil(P / slot_len): the queue runs whole slots, the canvas is cropped to P
     P_p: int            # the prompt canvas' positions
+    prompt_den: int = 1 # the denominator of the prompt hop (> 1 only under ``fifo_geometry(prompt_interp=)``)
 
 
-def fifo_geometry(cfg: Dict, prompt_modality: str, n_windows: int, steps: int, lookahead: int = 0) -> FifoGeometry:
+def fifo_geometry(cfg: Dict, prompt_modality: str, n_windows: int, steps: int, lookahead: int = 0,
+                  prompt_interp: Optional[str] = None) -> FifoGeometry:
     """The geometry of ``stream_generate(sampler="fifo")`` from the config alone (no device): how ``n_windows`` windows of
     ``streaming.window_seconds`` / ``hop_seconds`` become a target canvas of P latent positions, a queue of samples of S slots and a
     prompt canvas the queue's prompt gather walks by whole positions.  ``steps`` is the length of the schedule the queue will run (after
-    any truncation by ``strength``).  ValueError, naming the numbers, where the config does not fit the queue."""
+    any truncation by ``strength``).  ValueError, naming the numbers, where the config does not fit the queue.
+    ``prompt_interp`` ("nearest" or "linear"; default None) admits a prompt with a fractional number of positions per target slot
+    (include/avdiff_hip.h, "fractional prompt hop"): the hop L_p * slot_len / L_t comes back reduced, ``prompt_hop`` its numerator and
+    ``prompt_den`` its denominator — a video prompt at the shipped geometry is 12 * 4 / 150 = 8 / 25.  Without a mode such a prompt
+    is refused."""
     if prompt_modality not in ("video", "audio"):
         raise ValueError("prompt_modality must be 'video' or 'audio'")
+    if prompt_interp is not None and prompt_interp not in Fn.PROMPT_INTERPS:
+        raise ValueError(f"prompt_interp must be None or one of {Fn.PROMPT_INTERPS}, got {prompt_interp!r}")
     target = "audio" if prompt_modality == "video" else "video"
     for name, v, lo in (("n_windows", n_windows, 1), ("steps", steps, 1), ("lookahead", lookahead, 0)):
         if isinstance(v, bool) or not isinstance(v, int) or v < lo:
@@ -636,10 +696,11 @@ def fifo_geometry(cfg: Dict, prompt_modality: str, n_windows: int, steps: int, l
     S = L_t // slot_len
     if S < 1:
         raise ValueError(f"a window of {L_t} latent positions holds no slot of {slot_len}: the FIFO sampler needs at least one")
-    if (L_p * slot_len) % L_t:
+    if (L_p * slot_len) % L_t and prompt_interp is None:
         raise ValueError(f"the prompt has {L_p * slot_len / L_t:g} latent positions per target slot ({L_p} per window of {L_t} target "
                          f"positions, slots of {slot_len}); the queue's prompt gather moves by whole positions")
-    prompt_hop = L_p * slot_len // L_t
+    g = math.gcd(L_p * slot_len, L_t)
+    prompt_hop, prompt_den = L_p * slot_len // g, L_t // g
     if not lookahead < S:
         raise ValueError(f"lookahead {lookahead} must be below the S = {S} slots of a sample")
     h = S - lookahead
@@ -648,12 +709,13 @@ def fifo_geometry(cfg: Dict, prompt_modality: str, n_windows: int, steps: int, l
                          f"nearest step counts are {steps // h * h} and {(steps // h + 1) * h}")
     P_ = (n_windows - 1) * hop_t + L_t
     return FifoGeometry(hop_t, L_t, hop_p, L_p, slot_len, S, prompt_hop, h, steps // h, P_, -(-P_ // slot_len),
-                        (n_windows - 1) * hop_p + L_p)
+                        (n_windows - 1) * hop_p + L_p, prompt_den)
 
 
 def _fifo_options(cfg: Dict, *, shard, consensus, noise_keying, resample, init_noise, fifo) -> dict:
     """What ``stream_generate(sampler="fifo")`` refuses, before anything is read or encoded, and its ``fifo`` options ({"steps":
-    None = the target's sampler_steps, "lookahead": 0, "graph": False}; the argument wins over ``streaming.fifo``)."""
+    None = the target's sampler_steps, "lookahead": 0, "graph": False, "prompt_interp": None}; the argument wins over
+    ``streaming.fifo``)."""
     st = cfg.get("streaming", {})
     if shard:
         raise ValueError("sampler='fifo' with shard=True is not implemented: the queue is one chain of steps on one device")
@@ -668,15 +730,17 @@ def _fifo_options(cfg: Dict, *, shard, consensus, noise_keying, resample, init_n
         raise ValueError("sampler='fifo' takes no init_noise: the queue starts from the canvas-keyed noise stream of seed")
     opts = fifo if fifo is not None else st.get("fifo")
     opts = {} if opts is None else opts
-    if not isinstance(opts, dict) or set(opts) - {"steps", "lookahead", "graph"}:
-        raise ValueError(f"fifo takes a dict with any of steps, lookahead and graph, got {opts!r}")
-    opts = dict({"steps": None, "lookahead": 0, "graph": False}, **opts)
+    if not isinstance(opts, dict) or set(opts) - {"steps", "lookahead", "graph", "prompt_interp"}:
+        raise ValueError(f"fifo takes a dict with any of steps, lookahead and graph, or prompt_interp, got {opts!r}")
+    opts = dict({"steps": None, "lookahead": 0, "graph": False, "prompt_interp": None}, **opts)
     if opts["steps"] is not None and (isinstance(opts["steps"], bool) or not isinstance(opts["steps"], int) or opts["steps"] < 1):
         raise ValueError(f"fifo['steps'] must be an int >= 1 or None, got {opts['steps']!r}")
     if isinstance(opts["lookahead"], bool) or not isinstance(opts["lookahead"], int) or opts["lookahead"] < 0:
         raise ValueError(f"fifo['lookahead'] must be an int >= 0, got {opts['lookahead']!r}")
     if opts["graph"] is not None and not isinstance(opts["graph"], bool):
         raise ValueError(f"fifo['graph'] must be True, False or None, got {opts['graph']!r}")
+    if opts["prompt_interp"] is not None and not (isinstance(opts["prompt_interp"], str) and opts["prompt_interp"] in Fn.PROMPT_INTERPS):
+        raise ValueError(f"fifo['prompt_interp'] must be None or one of {Fn.PROMPT_INTERPS}, got {opts['prompt_interp']!r}")
     return opts
 
 
@@ -692,7 +756,7 @@ def _stream_generate_fifo(cfg: Dict, pc, mods: Dict, device, prompt_modality: st
     sched = su.truncate_schedule(whole, strength) if init_chunks is not None and strength < 1.0 else whole
     n = int(sched.numel()) - 1
     # strength 0 runs no step: the geometry is then checked for the whole schedule
-    geo = fifo_geometry(cfg, prompt_modality, Nw, n or int(whole.numel()) - 1, opts["lookahead"])
+    geo = fifo_geometry(cfg, prompt_modality, Nw, n or int(whole.numel()) - 1, opts["lookahead"], opts["prompt_interp"])
     if lat[1] != geo.L_t:
         raise ValueError(f"the target latent has {lat[1]} positions along its sliding axis (data.clip_seconds), a window of "
                          f"streaming.window_seconds has {geo.L_t}: they must be equal")
@@ -737,7 +801,8 @@ def _stream_generate_fifo(cfg: Dict, pc, mods: Dict, device, prompt_modality: st
                          guide_seed=P.default_guide_seed(guide_seed, noise_seed), guide_start="init" if sdedit else "noise",
                          guided_shift=True)
         canvas = fifo_denoise(eng, prompt_canvas, geo.prompt_hop, sched, geo.n_slots, int(seed), graph=opts["graph"],
-                              lookahead=opts["lookahead"], **guide, **ctl)[:, :geo.P].contiguous()
+                              lookahead=opts["lookahead"], prompt_den=geo.prompt_den, prompt_interp=opts["prompt_interp"], **guide,
+                              **ctl)[:, :geo.P].contiguous()
     windows = windows_from_canvas(canvas, geo.L_t, geo.hop_t)
     out = torch.cat([_decode_windows(cfg, pc, vid_vae, aud_codec, lat, windows[lo:lo + max_windows_per_batch], device)
                      for lo in range(0, Nw, max_windows_per_batch)], 0)
@@ -831,12 +896,16 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     encoded as above and made ONE prompt canvas (a uniform ``window_consensus`` pass, since each window was encoded alone, then
     ``canvas_from_windows``); one engine of batch B runs the queue over the target canvas of P = (N_windows - 1)*hop + L latent
     positions (``fifo_geometry`` gives every number and refuses a config that does not fit: the audio chunks must not overlap, the
-    prompt must have a whole number of latent positions per target slot, and the step count must be a multiple of the S - lookahead
-    stepping slots of a sample); the canvas is cut into the windows' latents (``windows_from_canvas``), which are decoded in batches of
+    prompt must have a whole number of latent positions per target slot unless ``fifo["prompt_interp"]`` is set, and the step count
+    must be a multiple of the S - lookahead stepping slots of a sample); the canvas is cut into the windows' latents (``windows_from_canvas``), which are decoded in batches of
     ``max_windows_per_batch`` and cross-faded as above, so the output has the windows sampler's length and dtype.
-    ``fifo`` (or ``streaming.fifo``; the argument wins) = {"steps": the target's ``sampler_steps``, "lookahead": 0, "graph": False},
-    ``fifo_denoise``'s arguments; unknown keys are refused.  ``seed`` seeds the queue's start and entering noise (None: drawn once from
-    torch's global CPU generator), ``noise_seed`` the engine's step noise (``ddim_eta`` > 0 needs it).  The config's solver, eta and
+    ``fifo`` (or ``streaming.fifo``; the argument wins) = {"steps": the target's ``sampler_steps``, "lookahead": 0, "graph": False,
+    "prompt_interp": None}, ``fifo_denoise``'s arguments; unknown keys are refused.  ``prompt_interp`` "nearest" or "linear" admits a
+    prompt with a fractional number of latent positions per target slot (include/avdiff_hip.h, "fractional prompt hop"; a video prompt
+    at the shipped geometry: 8 / 25): ``fifo_geometry`` reduces the hop and ``fifo_denoise`` walks it, reading between two prompt
+    positions by the nearest row or by an fp32 blend of the two.  The choice is the user's: which conditions a trained model better
+    cannot be measured on synthetic weights.  None keeps the refusal of such a prompt.
+    ``seed`` seeds the queue's start and entering noise (None: drawn once from torch's global CPU generator), ``noise_seed`` the engine's step noise (``ddim_eta`` > 0 needs it).  The config's solver, eta and
     guidance go to the engine; its per-sample CFG controls become ``fifo_denoise``'s slot controls: the guidance interval a
     ``guidance_interval_table``, ``guidance_rescale`` a constant ``rescale_by_level``, ``sampling.apg`` the per-slot APG (a momentum
     != 0 is refused: the queue has none).  An init clip is made one canvas like the prompt and guides the queue (``init_canvas``):
