@@ -437,8 +437,8 @@ int avd_fifo_shift_guided_f32(const avd_noise_key* key, int64_t t, int64_t c, co
  * result is not finite; r(e) is avd_cfg_control's, unchanged.
  * APG (apg != 0; excludes rescale_t).  Items 1 and 3 to 5 of "adaptive projected guidance" per slot with beta = 0: d = c - u, the
  * chunks are 1024 elements in the LATENT order of the slot alone ((c, t in slot, h, w) for video, (ch, j) for audio), r caps the
- * SLOT's L2 norm of d: a threshold chosen for a whole sample of S slots corresponds to r / sqrt(S) per slot.  There is no momentum
- * and no buffer: a slot's momentum would have to travel with it through the queue's shift as x0_hist does, which is not built.
+ * SLOT's L2 norm of d: a threshold chosen for a whole sample of S slots corresponds to r / sqrt(S) per slot.  With momentum == 0
+ * there is no buffer and nothing of item 2; a momentum is "slot APG momentum" below.
  * Partition rule.  At S == 1 the slot is the sample: both partitions, and therefore every coefficient and every output bit, are
  * those of the per-sample controlled entries (avd_denoise_step_cfg_f32 / avd_denoise_step_apg_f32) with g_b = guidance_t[t_now[b]]
  * and phi_b = rescale_t[t_now[b]] (audio: where the chunk covers the whole latent, F == len).
@@ -456,8 +456,8 @@ int avd_fifo_shift_guided_f32(const avd_noise_key* key, int64_t t, int64_t c, co
  * scratch; AVD_EINVAL for a scratch overlapping z, z_out, x0_hist or the eps tokens (the whole step: the workspace), and for
  * everything the slot entries already check.  The kernels trust the device values: table entries that are NaN or outside their range
  * are not detected there (DenoiseEngine.set_slot_cfg / schedule_utils.level_table check them before upload).
- * Limits: no slot momentum; the per-sample avd_cfg_control / avd_apg_control stay refused under slot timesteps; overlapping audio
- * chunks stay refused.  Quality is not measured here (no trained weights): the contract is the arithmetic. */
+ * Limits: the per-sample avd_cfg_control / avd_apg_control stay refused under slot timesteps; overlapping audio chunks stay
+ * refused.  Quality is not measured here (no trained weights): the contract is the arithmetic. */
 typedef struct {
     const float* guidance_t;   /* fp32 [T_train] on the device, or NULL = the scalar guidance */
     const float* rescale_t;    /* fp32 [T_train] phi in [0, 1], or NULL = no rescale */
@@ -467,6 +467,15 @@ typedef struct {
     void* stats;               /* caller-owned scratch, needed when rescale_t or apg is set */
     int64_t stats_bytes;       /* its size */
 } avd_slot_cfg;
+/* The control with the two trailing fields of "slot APG momentum" (below).  avd_slot_cfg keeps its 48 bytes, so callers built against
+ * it stay valid; a caller that wants the momentum passes &m.cfg of this struct to the same entries with cfg.apg ==
+ * AVD_SLOT_APG_MOMENTUM, which tells them that the two fields follow.  Never set that value on a plain avd_slot_cfg. */
+#define AVD_SLOT_APG_MOMENTUM 2
+typedef struct {
+    avd_slot_cfg cfg;          /* apg == AVD_SLOT_APG_MOMENTUM: per-slot APG, and the fields below are read */
+    float momentum;            /* beta, finite; 0: none (momentum_buf NULL) */
+    float* momentum_buf;       /* fp32 [B, per_sample], latent layout: a stepping slot's elements are read, then overwritten with d */
+} avd_slot_cfg_momentum;
 /* Bytes of the statistics scratch of B*slots slots of per_slot (>= 2) elements; -1 on bad arguments (B*slots outside [1, 65535]). */
 int64_t avd_slot_cfg_stats_bytes(int B, int slots, int64_t per_slot);
 /* The fused updates alone: avd_cfg_unpatch_ddim_slots_guided_f32 / avd_cfg_untoken_ddim_audio_slots_guided_f32 under the control.  key
@@ -481,6 +490,43 @@ int avd_cfg_untoken_ddim_audio_slots_cfg_f32(const float* eps2, const float* z, 
                                              const avd_slot_key* key, const avd_clip_guide* guide, int slots, float* x0_hist,
                                              float* z_out, int B, int Ca, int F, int len, int stride, const avd_slot_cfg* cfg,
                                              avd_stream_t stream);
+
+/* ---- slot APG momentum: APG's momentum per slot, in a buffer that travels with its slot through the queue (a public contract).
+ * The third part of "adaptive projected guidance" for the slot entries: momentum (beta) and momentum_buf (M), the two fields that
+ * trail the control in avd_slot_cfg_momentum.  The entries take that struct through its first member, with cfg.apg ==
+ * AVD_SLOT_APG_MOMENTUM; avd_slot_cfg itself is unchanged (any other non-zero apg is the momentum-free APG, and nothing behind the 48
+ * bytes is read), so momentum without apg cannot be stated.
+ * The buffer.  M is fp32 [B, per_sample] in LATENT layout, caller-owned, indexed as x0_hist is: slot (b, s) owns the elements of its
+ * slot_len positions of the sliding axis.  Audio: stride == len only, as everywhere under slot timesteps; the uncovered tail f >=
+ * Na*len is never read or written.
+ * A stepping slot, beta != 0.  Item 2 of "adaptive projected guidance" per slot: d = d0 + beta m_prev in fp32 without contraction,
+ * d0 = c - u, m_prev the slot's elements of M.  The moments S_dd, S_dc, S_cc of "slot CFG control" run over this d (the slot's
+ * latent order, chunks of 1024, fp64 partials summed in index order) and give (s, k, w, g) by the same expressions.  The fused update
+ * stores d back into the slot's elements of M and steps on e = c + w (d - k c).  The order within the slot is unchanged: combine ->
+ * APG -> the solver update (DDIM, seeded DDIM with the slot key, DPM-Solver++(2M) or its SDE form; x0_hist receives the x0 of e) ->
+ * the clip guide's blend last.  The statistics launch reads m_prev before the fused launch that overwrites it starts (one stream).
+ * A held slot (t_prev == t_now) neither reads nor writes M, and is z bit for bit.
+ * An entering slot's momentum is zero (avd_fifo_carry_f32 below), so a slot's first step has d = d0 + beta*0: the bits of the
+ * momentum-free slot APG except where d0 is -0.0 (-0.0 + 0.0 = +0.0).
+ * Invariance.  A slot's coefficients and output are a pure function of its eps tokens, its g, the slot geometry and its own elements
+ * of M: the same wherever the slot sits in the batch, eager or replayed, under either split_streams setting.
+ * Partition rule.  At S == 1 the step equals avd_denoise_step_apg_f32 with momentum = beta and g_b = guidance_t[t_now[b]], bit for
+ * bit, output and buffer (audio: where F == len).
+ * Checked before any HIP call, after the control's parameter ranges: AVD_EINVAL for a beta that is not finite and for a buffer that
+ * is not set exactly when beta != 0; then, behind the scratch's checks, AVD_EUNSUPPORTED for a
+ * buffer that is not 16-byte aligned and AVD_EINVAL for one that overlaps z, z_out, x0_hist, the scratch or the eps tokens (the whole
+ * step: the workspace).  momentum == 0 and momentum_buf == NULL is "slot CFG control" as it was, launch for launch.
+ * The carry.  avd_fifo_carry_f32 takes a slot-attached buffer of the batch's layout [B, outer, slots*slot_len, inner] through the
+ * queue move, out of place (in and out must not overlap: AVD_EINVAL).  It applies exactly the map avd_fifo_lookahead_hist_f32
+ * applies to its history: with h = slots - ctx, out window b position s >= ctx = the owner copy of logical slot b*h + s + shift of
+ * `in` (window (q - ctx) / h, position ctx + (q - ctx) % h); the entering tail slot (shift == 1) and every context position s < ctx
+ * are zero.  ctx == 0, shift == 1 is the history map of avd_fifo_shift_hist_f32; shift == 0 moves nothing and copies the stepping
+ * positions.  The map reads neither a clip slot nor a cursor, so the same launch follows the eager shift, the lookahead move and the
+ * cursor shift of a captured graph.  16-byte lanes when inner % 4 == 0 and both bases are 16-byte aligned, one element per lane
+ * otherwise: the same bits.  It is a launch of its own beside the four shift kernels on purpose: one launch is below the loop's
+ * resolution (profiles/fifo_guided_shift_e2e.txt). */
+int avd_fifo_carry_f32(const float* in, float* out, int B, int64_t outer, int slots, int ctx, int shift, int slot_len, int64_t inner,
+                       avd_stream_t stream);
 
 /* ---- FIFO queue shift: the queue step of diagonal denoising (FIFO-Diffusion, Kim et al. 2024) in one out-of-place launch.
  * The batch z_in [B, outer, L, inner] ((outer, L, inner) as in "canvas-keyed noise") with L = slots*slot_len is read as a queue of

@@ -109,6 +109,16 @@ class SlotCfg(C.Structure):
                 ("eta_parallel", C.c_float), ("stats", C.c_void_p), ("stats_bytes", C.c_int64)]
 
 
+SLOT_APG_MOMENTUM = 2      # AVD_SLOT_APG_MOMENTUM: the value of SlotCfg.apg that says the two fields of SlotCfgMomentum follow
+
+
+class SlotCfgMomentum(SlotCfg):
+    """avd_slot_cfg_momentum: the control (the base's fields, where they were) followed by APG's momentum and its latent-layout buffer
+    ("slot APG momentum").  The slot entries take it where they take a SlotCfg; they read the two fields when ``apg`` ==
+    SLOT_APG_MOMENTUM, which must never be set on a plain SlotCfg."""
+    _fields_ = [("momentum", C.c_float), ("momentum_buf", C.c_void_p)]
+
+
 class VaeDecodeDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("Cv", C.c_int), ("Tp", C.c_int), ("Hp", C.c_int), ("Wp", C.c_int),
                 ("T", C.c_int), ("H", C.c_int), ("W", C.c_int),
@@ -204,6 +214,7 @@ SIGNATURES = {
                                        _P]),
     "avd_fifo_lookahead_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _I, _P, _P, _P, _I, _L, _I, _I, _I, _L, _P]),
     "avd_fifo_lookahead_hist_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _I, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _L, _P]),
+    "avd_fifo_carry_f32": (_I, [_P, _P, _I, _L, _I, _I, _I, _I, _L, _P]),
     "avd_cursor_add": (_I, [_P, _I, _P]),
     "avd_slot_tables_select": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "avd_fifo_prompt_gather_f32": (_I, [_P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _P]),

@@ -344,12 +344,16 @@ struct SlotKey;
 struct ClipGuideState;
 // A SlotCfgState rides behind the SlotTimes alone ("slot CFG control"): after the SlotKey when there is one, before the ClipGuideState.
 struct SlotCfgState;
+// A SlotMomentum rides right behind a SlotCfgState in its APG mode ("slot APG momentum"): before the ClipGuideState.
+struct SlotMomentum;
 template <bool SEEDED, class... X> struct PackOk {
     template <class T> static constexpr int n = PackHas<T, X...>::value ? 1 : 0;
     static constexpr bool value = sizeof...(X) == (SEEDED ? 1 : 0) + n<DpmState> + n<GuideState> + n<CanvasGuideState> + n<CfgState> +
-                                                      n<CondOnly> + n<SlotTimes> + n<ClipGuideState> + n<SlotCfgState> &&
-                                  !(n<SlotTimes> && sizeof...(X) != 1 + n<DpmState> + n<SlotKey> + n<ClipGuideState> + n<SlotCfgState>) &&
+                                                      n<CondOnly> + n<SlotTimes> + n<ClipGuideState> + n<SlotCfgState> + n<SlotMomentum> &&
+                                  !(n<SlotTimes> &&
+                                    sizeof...(X) != 1 + n<DpmState> + n<SlotKey> + n<ClipGuideState> + n<SlotCfgState> + n<SlotMomentum>) &&
                                   n<SlotKey> <= n<SlotTimes> && n<ClipGuideState> <= n<SlotTimes> && n<SlotCfgState> <= n<SlotTimes> &&
+                                  n<SlotMomentum> <= n<SlotCfgState> &&
                                   !(n<CfgState> && n<CondOnly>) && !(n<GuideState> && n<CanvasGuideState>) &&
                                   !(n<CanvasGuideState> && n<NoiseKey>) &&
                                   n<NoiseKey> + n<CanvasKey> + n<SlotKey> == (SEEDED ? 1 : 0);
@@ -911,6 +915,66 @@ int fifo_lookahead_f32(const avd_noise_key* key, int64_t t, int64_t c, int shift
         hipLaunchKernelGGL((fifo_lookahead_kernel<1, false>), grid, dim3(256), 0, st, z_in, z_out, popped, hist_in, hist_out, ck,
                            (uint32_t)t, B, outer, S, ctx, shift, slot_len, inner, n_out, n_pop);
     AVD_CHECK_LAUNCH("fifo_lookahead");
+    return AVD_OK;
+}
+
+// ------------------------------------------------------------------ FIFO carry (a slot-attached buffer through the queue move)
+// The contract is written out in include/avdiff_hip.h ("slot APG momentum").  fifo_lookahead_kernel's history map alone, on a buffer of
+// z's layout: out window b slot s = the owner copy of logical slot b * h + s + shift of `in` on the stepping positions s >= ctx, zeros
+// on the context positions and in the entering tail slot (q == Q, shift == 1 only).  ctx == 0, shift == 1 is fifo_shift_kernel's
+// HistShift map.  Neither a clip slot nor a cursor enters: one launch serves the eager loops and a captured graph.  V lanes as
+// canvas_noise_kernel.
+template <int V>
+__global__ __launch_bounds__(256) void fifo_carry_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int64_t outer, int S,
+                                                         int ctx, int shift, int slot_len, int64_t inner, int64_t n_out) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n_out) return;
+    const int64_t iv = inner / V;
+    const int L = S * slot_len;
+    const int h = S - ctx;
+    const int64_t i = (idx % iv) * V;
+    int64_t r = idx / iv;
+    const int l = (int)(r % L);
+    r /= L;
+    const int64_t o = r % outer;
+    const int b = (int)(r / outer);
+    const int s = l / slot_len, j = l % slot_len;
+    const int64_t q = (int64_t)b * h + s + shift;      // the logical slot this position receives; q == Q only at shift == 1
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (s >= ctx && q < ctx + (int64_t)B * h) {        // s >= ctx gives q >= ctx: the owner copy is a stepping position
+        const int64_t bs = (q - ctx) / h, ss = ctx + (q - ctx) % h;
+        const float* src = in + ((bs * outer + o) * L + ss * slot_len + j) * inner + i;
+        if constexpr (V == 4) v = *reinterpret_cast<const f32x4*>(src);
+        else v[0] = *src;
+    }
+    if constexpr (V == 4) *reinterpret_cast<f32x4*>(out + idx * 4) = v;
+    else out[idx] = v[0];
+}
+
+int fifo_carry_f32(const float* in, float* out, int B, int64_t outer, int S, int ctx, int shift, int slot_len, int64_t inner,
+                   hipStream_t st) {
+    AVD_REQUIRE(in && out, AVD_EINVAL, "fifo_carry: null pointer");
+    AVD_REQUIRE(shift == 0 || shift == 1, AVD_EINVAL, "fifo_carry: shift must be 0 or 1 (got %d)", shift);
+    AVD_REQUIRE(B > 0 && outer > 0 && S > 0 && slot_len > 0 && inner > 0, AVD_EINVAL,
+                "fifo_carry: bad dims (B %d, outer %lld, S %d, slot_len %d, inner %lld)", B, (long long)outer, S, slot_len, (long long)inner);
+    AVD_REQUIRE(ctx >= 0 && ctx < S, AVD_EINVAL, "fifo_carry: ctx %d must lie in [0, slots %d)", ctx, S);
+    AVD_REQUIRE((int64_t)S * slot_len <= 0x7fffffff && (int64_t)B * S <= 0x7fffffff, AVD_EINVAL,
+                "fifo_carry: S %d * slot_len %d and B %d * S must fit an int", S, slot_len, B);
+    AVD_REQUIRE((double)B * (double)outer * (double)S * (double)slot_len * (double)inner < 9.0e18, AVD_EUNSUPPORTED,
+                "fifo_carry: too many values");
+    const int64_t total = (int64_t)B * outer * S * slot_len * inner;
+    AVD_REQUIRE(!overlaps(in, out, total), AVD_EINVAL, "fifo_carry: out must not overlap in (one out-of-place launch)");
+    const bool vec = inner % 4 == 0 && aligned16(in) && aligned16(out);
+    const int64_t n_out = total / (vec ? 4 : 1);
+    AVD_REQUIRE((n_out + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "fifo_carry: %lld lanes are too many for one launch", (long long)n_out);
+    static const int tags[2] = {prof_tag_id("fifo_carry_kernel<1>"), prof_tag_id("fifo_carry_kernel<4>")};
+    // every stepping owner but the head read once, B * S slots written
+    const double slot = (double)outer * slot_len * (double)inner;
+    ProfScope prof(tags[vec ? 1 : 0], 4.0 * ((double)B * (S - ctx) - shift + (double)B * S) * slot, st);
+    const dim3 grid((unsigned)((n_out + 255) / 256));
+    if (vec) hipLaunchKernelGGL(fifo_carry_kernel<4>, grid, dim3(256), 0, st, in, out, B, outer, S, ctx, shift, slot_len, inner, n_out);
+    else hipLaunchKernelGGL(fifo_carry_kernel<1>, grid, dim3(256), 0, st, in, out, B, outer, S, ctx, shift, slot_len, inner, n_out);
+    AVD_CHECK_LAUNCH("fifo_carry");
     return AVD_OK;
 }
 
@@ -2165,6 +2229,20 @@ struct SlotCfgCoef {
     float g, phi, s, k, w;
     bool apg;
 };
+// "slot APG momentum": behind a SlotCfgState in its APG mode, a pack element of its own, so that the packs without it keep their code.
+// buf is the [B, per] latent-layout buffer whose elements travel with their slot (avd_fifo_carry_f32); a stepping slot's lanes read
+// m_prev at their latent address and store d there, a held slot's lanes touch nothing.
+struct SlotMomentum {
+    float* buf;
+    float beta;      // != 0
+};
+// the statistics pass's view of it: the buffer read-only, and what turns a slot's element index into its latent address
+struct SlotMomentumAt {
+    const float* buf;
+    float beta;
+    int64_t per;     // one sample's latent elements
+    int len, F;      // audio: the chunk length and the latent's frames (video: unused, the Tube has the geometry)
+};
 // the level of the contract: the clamp of ddim_coef
 __device__ __forceinline__ int slot_level(const int64_t* t_now, int T_train, int tb) {
     long long tn = t_now[tb];
@@ -2189,6 +2267,19 @@ __device__ __forceinline__ float slot_cfg_eps(const SlotCfgCoef& c, float ec, fl
     if (c.apg) return apg_eps(ec, apg_d0(ec, en), c.w, c.k);
     return cfg_rescale(cfg_combine(ec, en, c.g), c.phi, c.s);
 }
+// the momentum form for the four elements at latent address lat (the lane owns it), from c and d0 = c - u: reads m_prev, stores d and
+// returns e = c + w (d - k c); apg_eps4 with the slot's coefficients
+__device__ __forceinline__ f32x4 slot_mom_eps4(const SlotMomentum& sm, const SlotCfgCoef& sf, int64_t lat, const f32x4& c, const f32x4& d0) {
+    const f32x4 m = *reinterpret_cast<const f32x4*>(sm.buf + lat);
+    f32x4 d, e;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        d[j] = apg_dir(d0[j], sm.beta, m[j]);
+        e[j] = apg_eps(c[j], d[j], sf.w, sf.k);
+    }
+    *reinterpret_cast<f32x4*>(sm.buf + lat) = d;
+    return e;
+}
 
 static int64_t slot_cfg_coef_off(int64_t BS, int64_t per_slot) { return (BS * cfg_chunks(per_slot) * 32 + 15) & ~(int64_t)15; }
 int64_t slot_cfg_stats_bytes(int B, int slots, int64_t per_slot) {
@@ -2208,12 +2299,17 @@ struct SlotGeom {
 // of slot tb.  RESCALE: (sum c, sum c^2, sum y, sum y^2) in token order from the slot's first token element, y = cfg_combine(c, u, g).
 // APG: (sum d^2, sum d c, sum c^2, 0) in the slot's own latent order ((c, t in slot, h, w); audio (ch, j), which is its token order).
 // A held slot's blocks return before they load anything: its partials are never read.
-template <int SRC, bool APG>
+// A SlotMomentumAt ending the arguments (APG only; an empty pack otherwise, which keeps the argument layout and the code) makes d =
+// d0 + beta m_prev, m_prev read at the element's latent address as apg_stats_kernel reads it: the fused update that stores d starts
+// after this launch (same stream) and evaluates d with the same two functions.
+template <int SRC, bool APG, class... Mom>
 __global__ __launch_bounds__(256) void slot_cfg_stats_kernel(const float* __restrict__ a, const float* __restrict__ u, int64_t sstride,
                                                              const int64_t* __restrict__ t_now, const int64_t* __restrict__ t_prev,
                                                              const float* __restrict__ gtab, float guidance, int T_train,
-                                                             double* __restrict__ part, SlotGeom sg, Tube g) {
+                                                             double* __restrict__ part, SlotGeom sg, Tube g, Mom... mm) {
 #pragma clang fp contract(off)
+    constexpr bool MOM = sizeof...(Mom) == 1;
+    static_assert(sizeof...(Mom) <= 1 && (!MOM || APG), "the pack: empty, or one SlotMomentumAt behind an APG pass");
     __shared__ double red[4][4];
     const int tb = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (t_now[tb] == t_prev[tb]) return;
@@ -2225,6 +2321,7 @@ __global__ __launch_bounds__(256) void slot_cfg_stats_kernel(const float* __rest
     const float* su = u + (int64_t)b * sstride;
     const int64_t el0 = (int64_t)blockIdx.x * CFG_CHUNK + threadIdx.x * 4;
     f32x4 cv = {0.f, 0.f, 0.f, 0.f}, uv = {0.f, 0.f, 0.f, 0.f};
+    [[maybe_unused]] f32x4 mv = {0.f, 0.f, 0.f, 0.f};  // m_prev of the lane's elements (MOM)
     int nv = 0;                                        // valid elements of this lane (elements >= per_slot add nothing)
     if (el0 < sg.per_slot) {
         nv = sg.per_slot - el0 < 4 ? (int)(sg.per_slot - el0) : 4;
@@ -2233,6 +2330,10 @@ __global__ __launch_bounds__(256) void slot_cfg_stats_kernel(const float* __rest
             if constexpr (APG) {                       // the slot's latent order -> the sample's latent float4 -> its token offset
                 const int64_t c = el0 / sg.lat_slice, r = el0 % sg.lat_slice;
                 off = tube_tok_off(g, ((c * g.T + (int64_t)s * g.t) * ((int64_t)g.H * g.W) + r) >> 2);
+                if constexpr (MOM) {                   // the same latent float4 of the buffer
+                    const SlotMomentumAt ma = pack_get<SlotMomentumAt>(mm...);
+                    mv = *reinterpret_cast<const f32x4*>(ma.buf + (int64_t)b * ma.per + (c * g.T + (int64_t)s * g.t) * ((int64_t)g.H * g.W) + r);
+                }
             }
             cv = *reinterpret_cast<const f32x4*>(sa + off);
             uv = *reinterpret_cast<const f32x4*>(su + off);
@@ -2240,13 +2341,23 @@ __global__ __launch_bounds__(256) void slot_cfg_stats_kernel(const float* __rest
             for (int k = 0; k < nv; ++k) {
                 cv[k] = sa[(int64_t)s * sg.tok_slot + el0 + k];
                 uv[k] = su[(int64_t)s * sg.tok_slot + el0 + k];
+                if constexpr (MOM) {                   // element (ch, j) of chunk s is latent (ch, s len + j)
+                    const SlotMomentumAt ma = pack_get<SlotMomentumAt>(mm...);
+                    const int64_t el = el0 + k;
+                    mv[k] = ma.buf[(int64_t)b * ma.per + (el / ma.len) * ma.F + (int64_t)s * ma.len + el % ma.len];
+                }
             }
         }
     }
     double m[4] = {0.0, 0.0, 0.0, 0.0};
     for (int k = 0; k < nv; ++k) {
         const double c = (double)cv[k];
-        if constexpr (APG) {
+        if constexpr (MOM) {
+            const double d = (double)apg_dir(apg_d0(cv[k], uv[k]), pack_get<SlotMomentumAt>(mm...).beta, mv[k]);
+            m[0] += d * d;
+            m[1] += d * c;
+            m[2] += c * c;
+        } else if constexpr (APG) {
             const double d = (double)apg_d0(cv[k], uv[k]);
             m[0] += d * d;
             m[1] += d * c;
@@ -2315,8 +2426,10 @@ __global__ void slot_cfg_finalize_kernel(const double* __restrict__ part, float*
 
 // The checks of a slot control, all before any HIP call, in the contract's order; fills the pack's state.  lat: the call's latent-sized
 // tensors (z, z_out, x0_hist; nullptr entries are skipped); eps: the bytes the predictions are read from.
+// sm: the momentum element of the pack ("slot APG momentum"), buf == nullptr when the control carries none; its checks mirror
+// make_apg's for avd_apg_control's buffer.
 static int make_slot_cfg(const avd_slot_cfg* cfg, int B, int S, int64_t per_slot, int64_t per, std::initializer_list<const float*> lat,
-                         const void* eps, int64_t eps_bytes, SlotCfgState& sc) {
+                         const void* eps, int64_t eps_bytes, SlotCfgState& sc, SlotMomentum& sm) {
     AVD_REQUIRE(cfg, AVD_EINVAL, "slot_cfg: null control");
     AVD_REQUIRE(!(cfg->apg && cfg->rescale_t), AVD_EINVAL,
                 "slot_cfg: guidance rescale together with APG is refused (its statistics would need the APG output)");
@@ -2325,6 +2438,15 @@ static int make_slot_cfg(const avd_slot_cfg* cfg, int B, int S, int64_t per_slot
                     "slot_cfg: norm_threshold must be finite and >= 0 (0: no cap), got %g", (double)cfg->norm_threshold);
         AVD_REQUIRE(cfg->eta_parallel >= 0.f && cfg->eta_parallel <= 1.f, AVD_EINVAL, "slot_cfg: eta_parallel must lie in [0, 1], got %g",
                     (double)cfg->eta_parallel);
+    }
+    sm = SlotMomentum{nullptr, 0.f};
+    if (cfg->apg == AVD_SLOT_APG_MOMENTUM) {      // the control is the first member of an avd_slot_cfg_momentum: its two fields follow
+        const avd_slot_cfg_momentum* m = reinterpret_cast<const avd_slot_cfg_momentum*>(cfg);
+        AVD_REQUIRE(std::isfinite(m->momentum), AVD_EINVAL, "slot_cfg: momentum must be finite, got %g", (double)m->momentum);
+        AVD_REQUIRE((m->momentum != 0.f) == (m->momentum_buf != nullptr), AVD_EINVAL,
+                    "slot_cfg: momentum_buf must be set exactly when momentum != 0 (momentum %g, buffer %s)", (double)m->momentum,
+                    m->momentum_buf ? "set" : "NULL");
+        sm = SlotMomentum{m->momentum_buf, m->momentum};
     }
     sc = SlotCfgState{cfg->guidance_t, cfg->rescale_t, nullptr, cfg->apg ? SLOT_CFG_APG : cfg->rescale_t ? SLOT_CFG_RESCALE : SLOT_CFG_TABLE};
     if (sc.mode == SLOT_CFG_TABLE) return AVD_OK;
@@ -2339,6 +2461,17 @@ static int make_slot_cfg(const avd_slot_cfg* cfg, int B, int S, int64_t per_slot
         AVD_REQUIRE(!p || !overlaps_bytes(cfg->stats, need, p, (int64_t)B * per * 4), AVD_EINVAL,
                     "slot_cfg: stats must not overlap z, z_out or x0_hist");
     AVD_REQUIRE(!eps || !overlaps_bytes(cfg->stats, need, eps, eps_bytes), AVD_EINVAL, "slot_cfg: stats must not overlap the eps tokens");
+    if (sm.buf) {
+        const int64_t lat_bytes = (int64_t)B * per * 4;
+        AVD_REQUIRE(aligned16(sm.buf), AVD_EUNSUPPORTED, "slot_cfg: momentum_buf must be 16-byte aligned");
+        for (const float* p : lat)
+            AVD_REQUIRE(!p || !overlaps_bytes(sm.buf, lat_bytes, p, lat_bytes), AVD_EINVAL,
+                        "slot_cfg: momentum_buf must not overlap z, z_out or x0_hist");
+        AVD_REQUIRE(!overlaps_bytes(sm.buf, lat_bytes, cfg->stats, need), AVD_EINVAL,
+                    "slot_cfg: momentum_buf must not overlap the statistics scratch");
+        AVD_REQUIRE(!eps || !overlaps_bytes(sm.buf, lat_bytes, eps, eps_bytes), AVD_EINVAL,
+                    "slot_cfg: momentum_buf must not overlap the eps tokens");
+    }
     sc.coef = reinterpret_cast<const float*>(static_cast<const char*>(cfg->stats) + slot_cfg_coef_off((int64_t)B * S, per_slot));
     return AVD_OK;
 }
@@ -2347,24 +2480,29 @@ static int make_slot_cfg(const avd_slot_cfg* cfg, int B, int S, int64_t per_slot
 int check_slot_cfg(const avd_slot_cfg* cfg, int B, int S, int64_t per_slot, int64_t per, const float* z, const float* out,
                    const float* x0_hist, const void* eps, int64_t eps_bytes) {
     SlotCfgState sc;
-    return make_slot_cfg(cfg, B, S, per_slot, per, {z, out, x0_hist}, eps, eps_bytes, sc);
+    SlotMomentum sm;
+    return make_slot_cfg(cfg, B, S, per_slot, per, {z, out, x0_hist}, eps, eps_bytes, sc, sm);
 }
 
 // the statistics pass of a RESCALE or APG control: partials, then four floats per slot into the scratch's tail
 template <int SRC>
 static int run_slot_cfg_stats(const avd_slot_cfg* cfg, const SlotCfgState& sc, const float* a, const float* u, int64_t sstride,
                               const int64_t* t_now, const int64_t* t_prev, float guidance, int T_train, int B, const SlotGeom& sg, Tube g,
-                              hipStream_t st) {
+                              hipStream_t st, const SlotMomentumAt& ma = SlotMomentumAt{}) {
     const int64_t chunks = cfg_chunks(sg.per_slot);
     const int BS = B * sg.S;
     double* part = static_cast<double*>(cfg->stats);
     float* coef = const_cast<float*>(sc.coef);
     static const int tag = prof_tag_id("slot_cfg_stats_kernel");
+    static const int tag_mom = prof_tag_id("slot_cfg_stats_kernel<momentum>");
     static const int tag_fin = prof_tag_id("slot_cfg_finalize_kernel");
     const dim3 grid((unsigned)chunks, (unsigned)BS), fgrid((unsigned)((BS + 63) / 64));
     {
-        ProfScope prof(tag, 8.0 * (double)BS * sg.per_slot, st);
-        if (sc.mode == SLOT_CFG_APG)
+        ProfScope prof(ma.buf ? tag_mom : tag, (ma.buf ? 12.0 : 8.0) * (double)BS * sg.per_slot, st);
+        if (ma.buf)      // make_slot_cfg: a momentum rides with the APG mode alone
+            hipLaunchKernelGGL((slot_cfg_stats_kernel<SRC, true, SlotMomentumAt>), grid, dim3(256), 0, st, a, u, sstride, t_now, t_prev,
+                               sc.guidance_t, guidance, T_train, part, sg, g, ma);
+        else if (sc.mode == SLOT_CFG_APG)
             hipLaunchKernelGGL((slot_cfg_stats_kernel<SRC, true>), grid, dim3(256), 0, st, a, u, sstride, t_now, t_prev, sc.guidance_t,
                                guidance, T_train, part, sg, g);
         else
@@ -2427,7 +2565,13 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
     constexpr bool SCFG = PackHas<SlotCfgState, Key...>::value;
     [[maybe_unused]] f32x4 es = {0.f, 0.f, 0.f, 0.f};      // the slot control's eps: coefficients by tb, not by b
-    if constexpr (SCFG) {
+    if constexpr (PackHas<SlotMomentum, Key...>::value) {      // "slot APG momentum": this lane owns the latent address (APG mode)
+        const SlotCfgCoef sf = slot_cfg_coef(pack_get<SlotCfgState>(nk...), t_now, T_train, guidance, tb);
+        f32x4 d0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) d0[k] = apg_d0(ec[k], en[k]);
+        es = slot_mom_eps4(pack_get<SlotMomentum>(nk...), sf, lat, ec, d0);
+    } else if constexpr (SCFG) {
         const SlotCfgCoef sf = slot_cfg_coef(pack_get<SlotCfgState>(nk...), t_now, T_train, guidance, tb);
 #pragma unroll
         for (int k = 0; k < 4; ++k) es[k] = slot_cfg_eps(sf, ec[k], en[k]);
@@ -2530,6 +2674,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     [[maybe_unused]] bool apg = false;      // block-uniform: the launch carries an APG part
     if constexpr (CTL) apg = pack_get<CfgState>(nk...).apg != nullptr;
     constexpr bool SCFG = PackHas<SlotCfgState, Key...>::value;
+    constexpr bool SMOM = PackHas<SlotMomentum, Key...>::value;      // "slot APG momentum": two planes, as the APG part
     [[maybe_unused]] SlotCfgCoef sf{guidance, 0.f, 1.f, 0.f, 0.f, false};      // the slot control: block-uniform, by tb (a held slot reads nothing)
     if constexpr (SCFG)
         if (!hold) sf = slot_cfg_coef(pack_get<SlotCfgState>(nk...), t_now, T_train, guidance, tb);
@@ -2547,6 +2692,14 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
                 *reinterpret_cast<f32x4*>(ebuf + (GT + tok) * LD + k0) = d0;
                 continue;
             }
+        }
+        if constexpr (SMOM) {      // as the APG part: c and d0 parked, d and e built by the owner of the latent address below
+            f32x4 d0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) d0[k] = apg_d0(ec[k], en[k]);
+            *reinterpret_cast<f32x4*>(ebuf + tok * LD + k0) = ec;
+            *reinterpret_cast<f32x4*>(ebuf + (GT + tok) * LD + k0) = d0;
+            continue;
         }
         f32x4 e;
 #pragma unroll
@@ -2583,6 +2736,8 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
                 continue;
             }
         }
+        if constexpr (SMOM)      // e holds c: a stepping slot's lane on this side of the exchange reads m_prev, stores d and builds e
+            e = slot_mom_eps4(pack_get<SlotMomentum>(nk...), sf, lat, e, *reinterpret_cast<const f32x4*>(ebuf + (GT + tok) * LD + sg * g.w + wo));
         f32x4 o;
         [[maybe_unused]] f32x4 zn = {0.f, 0.f, 0.f, 0.f};      // the unkeyed DPM update (eta == 0) draws nothing
         if constexpr (PackHas<SlotKey, Key...>::value) {      // the clip-keyed draw: the canvas-keyed decomposition, the block's slot timestep
@@ -2647,6 +2802,8 @@ struct UpdateKeys {
     ClipGuideState cg;
     bool scfg;         // the slot form under a slot CFG control: sc rides behind the slot key, before the clip guide
     SlotCfgState sc;
+    bool smom;         // the slot CFG control carries a momentum buffer: sm rides right behind sc
+    SlotMomentum sm;
     DpmState ds;
     NoiseKey nk;
     CanvasKey ck;      // canvas: the seeded draw is keyed by canvas position (ck replaces nk in the pack)
@@ -2767,8 +2924,9 @@ static void with_update_pack(const UpdateKeys& k, bool cond_only, F launch) {
             if (k.clip) launch(state..., k.cg);
             else launch(state...);
         };
-        auto stail = [&](auto... state) {      // a slot CFG control rides behind the key, before the guide
-            if (k.scfg) gtail(state..., k.sc);
+        auto stail = [&](auto... state) {      // a slot CFG control rides behind the key, before the guide; its momentum behind it
+            if (k.scfg && k.smom) gtail(state..., k.sc, k.sm);
+            else if (k.scfg) gtail(state..., k.sc);
             else gtail(state...);
         };
         if (k.dpm && k.skey) stail(k.ds, k.sl, k.sk);
@@ -2813,6 +2971,7 @@ static void launch_unpatch(const UpdateArgs& a, const Tube& g, hipStream_t st, P
     const int gt = (g.W < 32 ? g.W : 32) / g.w;
     int planes = 1;      // an APG launch parks c and d0: twice the LDS (the gather form where that does not fit)
     if constexpr (PackHas<CfgState, P...>::value) planes = pack_get<CfgState>(p...).apg ? 2 : 1;
+    if constexpr (PackHas<SlotMomentum, P...>::value) planes = 2;      // a slot momentum launch likewise
     const int64_t lds = (int64_t)planes * gt * (g.D + 4) * 4;
     if (g_cfg_rows && (gt == 8 || gt == 4) && g.Wt % gt == 0 && g.D % 4 == 0 && lds <= 64 * 1024) {
         const int groups = (int)(g.per / g.D) / gt;
@@ -2840,10 +2999,12 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
     if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
     // scfg != nullptr: the call came through a *_slots_cfg entry; the control is checked first
     SlotCfgState sc{};
+    SlotMomentum sm{};
     const SlotGeom sg{T / t, (int64_t)C * t * H * W, (int64_t)g.Ht * g.Wt * g.D, (int64_t)t * H * W};
     if (scfg) {
         AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_unpatch_ddim: a slot CFG control rides with slot timesteps (slots > 0)");
-        if (int rc = make_slot_cfg(scfg, B, sg.S, sg.per_slot, g.per, {z, z_out, x0_hist}, eps2, (int64_t)2 * B * g.per * 4, sc)) return rc;
+        if (int rc = make_slot_cfg(scfg, B, sg.S, sg.per_slot, g.per, {z, z_out, x0_hist}, eps2, (int64_t)2 * B * g.per * 4, sc, sm))
+            return rc;
     }
     AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "cfg_unpatch_ddim: x0_hist must be 16-byte aligned");
     const UpdateArgs a{eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, B};
@@ -2856,9 +3017,11 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
                                    SlotKeyDims{C, t, (int64_t)H * W}, cguide, T)) return rc;
     k.scfg = scfg != nullptr;
     k.sc = sc;
+    k.smom = sm.buf != nullptr;
+    k.sm = sm;
     if (scfg && sc.mode != SLOT_CFG_TABLE)      // 16-byte aligned token rows: the entry has checked eps2, and per % 4 == 0
         if (int rc = run_slot_cfg_stats<CFG_SRC_VIDEO>(scfg, sc, eps2, eps2 + (int64_t)B * g.per, g.per, t_now, t_prev, guidance, T_train, B,
-                                                       sg, g, st)) return rc;
+                                                       sg, g, st, SlotMomentumAt{sm.buf, sm.beta, g.per, 0, 0})) return rc;
     if (apg) {
         AVD_REQUIRE(aligned16(eps2) && aligned16(eps2 + (int64_t)B * g.per) && aligned16(z) && aligned16(z_out), AVD_EUNSUPPORTED,
                     "cfg_unpatch_ddim: the APG statistics pass reads 16-byte aligned token rows");
@@ -2874,8 +3037,9 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
     static const int tag_apg = prof_tag_id("cfg_unpatch_ddim_kernel<apg>");      // the fused launch of an APG step, timed apart
     static const int tag_clip = prof_tag_id("cfg_unpatch_ddim_kernel<clip guide>");      // as is the clip-guided slot update
     static const int tag_scfg = prof_tag_id("cfg_unpatch_ddim_kernel<slot cfg>");        // and the slot update under a slot CFG control
-    ProfScope prof(scfg ? tag_scfg : apg ? tag_apg : cguide ? tag_clip : tag,
-                   (apg && apg->momentum_buf ? 24.0 : cguide ? (cguide->mask ? 24.0 : 20.0) : 16.0) * (double)B * g.per, st);
+    static const int tag_smom = prof_tag_id("cfg_unpatch_ddim_kernel<slot momentum>");   // and under its momentum
+    ProfScope prof(k.smom ? tag_smom : scfg ? tag_scfg : apg ? tag_apg : cguide ? tag_clip : tag,
+                   ((apg && apg->momentum_buf) || k.smom ? 24.0 : cguide ? (cguide->mask ? 24.0 : 20.0) : 16.0) * (double)B * g.per, st);
     with_update_pack(k, false, [&](auto... p) { launch_unpatch(a, g, st, p...); });
     AVD_CHECK_LAUNCH("cfg_unpatch_ddim");
     return AVD_OK;
@@ -2972,7 +3136,12 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
         if constexpr (SCFG) {      // the slot's token alone (stride == len: one window); the uncovered tail keeps eps = 0
             if (sf.apg) {          // the two means of the per-sample APG branch
                 const float cv = ola_gather(tc, D, c, len, stride, Na, f), uv = ola_gather(tn, D, c, len, stride, Na, f);
-                e = apg_eps(cv, apg_d0(cv, uv), sf.w, sf.k);
+                if constexpr (PackHas<SlotMomentum, Key...>::value) {      // "slot APG momentum": element i is this lane's latent address
+                    const SlotMomentum sm = pack_get<SlotMomentum>(nk...);
+                    const float dv = apg_dir(apg_d0(cv, uv), sm.beta, sm.buf[i]);
+                    sm.buf[i] = dv;
+                    e = apg_eps(cv, dv, sf.w, sf.k);
+                } else e = apg_eps(cv, apg_d0(cv, uv), sf.w, sf.k);
             } else e = cfg_rescale(e, sf.phi, sf.s);
         }
     }
@@ -3042,11 +3211,12 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
     const CanvasDims gcv{Ca, F, guide_hop, 1};
     const AudioGeom ag{Ca, F, len, stride, audio_na(F, len, stride)};
     SlotCfgState sc{};      // as cfg_unpatch_ddim_f32: the control of a *_slots_cfg entry is checked first
+    SlotMomentum sm{};
     const SlotGeom sg{ag.Na, (int64_t)Ca * len, (int64_t)Ca * len, 0};
     if (scfg) {
         AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: a slot CFG control rides with slot timesteps (slots > 0)");
-        if (int rc = make_slot_cfg(scfg, B, sg.S, sg.per_slot, per, {z, z_out, x0_hist}, eps2, (int64_t)2 * B * ag.Na * Ca * len * 4, sc))
-            return rc;
+        if (int rc = make_slot_cfg(scfg, B, sg.S, sg.per_slot, per, {z, z_out, x0_hist}, eps2, (int64_t)2 * B * ag.Na * Ca * len * 4, sc,
+                                   sm)) return rc;
     }
     if (int rc = check_fused_update("cfg_untoken_ddim_audio", a, per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
                                     guide_hop ? &gcv : nullptr, apg, (int64_t)2 * B * ag.Na * Ca * len * 4, skey)) return rc;
@@ -3054,10 +3224,12 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
                                    SlotKeyDims{Ca, len, 1}, cguide, F)) return rc;
     k.scfg = scfg != nullptr;
     k.sc = sc;
+    k.smom = sm.buf != nullptr;
+    k.sm = sm;
     if (scfg && sc.mode != SLOT_CFG_TABLE) {
         const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
         if (int rc = run_slot_cfg_stats<CFG_SRC_AUDIO>(scfg, sc, eps2, eps2 + B * half, half, t_now, t_prev, guidance, T_train, B, sg, Tube{},
-                                                       st)) return rc;
+                                                       st, SlotMomentumAt{sm.buf, sm.beta, per, len, F})) return rc;
     }
     if (apg) {
         const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
@@ -3605,6 +3777,10 @@ extern "C" int avd_fifo_lookahead_hist_f32(const avd_noise_key* key, int64_t t, 
     AVD_REQUIRE(hist_in && hist_out, AVD_EINVAL, "fifo_lookahead_hist: null hist_in or hist_out");
     return fifo_lookahead_f32(key, t, c, shift, z_in, z_out, popped, B, outer, slots, ctx, slot_len, inner, static_cast<hipStream_t>(stream),
                               hist_in, hist_out);
+}
+extern "C" int avd_fifo_carry_f32(const float* in, float* out, int B, int64_t outer, int slots, int ctx, int shift, int slot_len,
+                                  int64_t inner, avd_stream_t stream) {
+    return fifo_carry_f32(in, out, B, outer, slots, ctx, shift, slot_len, inner, static_cast<hipStream_t>(stream));
 }
 extern "C" int avd_cursor_add(int32_t* cursor, int delta, avd_stream_t stream) {
     AVD_REQUIRE(cursor, AVD_EINVAL, "cursor_add: null cursor");

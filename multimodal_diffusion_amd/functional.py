@@ -944,6 +944,81 @@ def fifo_lookahead(z: Tensor, ctx: int, shift: int, slot_len: int, c: Optional[i
     return out, popped, hist_out
 
 
+def fifo_carry(buf: Tensor, slots: int, slot_len: int, ctx: int = 0, shift: int = 1, out: Optional[Tensor] = None) -> Tensor:
+    """A slot-attached buffer through the queue move (avd_fifo_carry_f32; contract in include/avdiff_hip.h, "slot APG momentum"):
+    ``buf`` has the queue's layout ([B,C,T,H,W] video, [B,Ca,F] audio, sliding length ``slots`` * ``slot_len``) and holds per-element
+    state of the slots, the slot APG momentum.  The result follows ``fifo_lookahead``'s history map: with h = slots - ctx, window b
+    position s >= ctx receives the owner copy of logical slot b*h + s + shift; the entering tail slot (``shift=1``) and every context
+    position s < ctx are zero.  ``ctx=0, shift=1`` is ``fifo_shift``'s history map, ``shift=0`` copies the stepping positions.
+    A CPU tensor takes the torch statement below, which is the reference; a device tensor one out-of-place launch (``out``: a buffer
+    of buf's shape that does not overlap it, None allocates one)."""
+    if not (isinstance(buf, Tensor) and buf.dtype == torch.float32 and buf.dim() in (3, 5)):
+        raise ValueError("buf must be a float32 tensor of the queue's layout, [B,C,T,H,W] or [B,Ca,F]")
+    outer, L_, inner = window_dims(buf.shape)
+    for name, v in (("slots", slots), ("slot_len", slot_len)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{name} must be an int >= 1, got {v!r}")
+    if slots * slot_len != L_:
+        raise ValueError(f"slots {slots} * slot_len {slot_len} must be the sliding length {L_}")
+    if isinstance(ctx, bool) or not isinstance(ctx, int) or not 0 <= ctx < slots:
+        raise ValueError(f"ctx must be an int in [0, slots = {slots}), got {ctx!r}")
+    if isinstance(shift, bool) or shift not in (0, 1):
+        raise ValueError(f"shift must be 0 or 1, got {shift!r}")
+    B = buf.shape[0]
+    if out is not None and not (out.dtype == torch.float32 and out.is_contiguous() and out.shape == buf.shape and out.device == buf.device):
+        raise ValueError(f"out must be a contiguous float32 tensor of buf's shape {tuple(buf.shape)} on its device")
+    if buf.is_cuda:
+        buf = buf.contiguous()
+        out = torch.empty_like(buf) if out is None else out
+        L.check(L.lib().avd_fifo_carry_f32(buf.data_ptr(), out.data_ptr(), B, outer, slots, ctx, shift, slot_len, inner, _st(buf)))
+        return out
+    h = slots - ctx
+    v = buf.reshape(B, outer, slots, slot_len, inner)
+    queue = v[:, :, ctx:].permute(0, 2, 1, 3, 4).reshape(B * h, outer, slot_len, inner)      # the stepping owners: logical slots ctx ..
+    moved = torch.zeros_like(queue)
+    moved[:B * h - shift] = queue[shift:]                                                     # the entering tail slot stays zero
+    res = torch.zeros_like(v)
+    res[:, :, ctx:] = moved.reshape(B, h, outer, slot_len, inner).permute(0, 2, 1, 3, 4)
+    res = res.reshape(buf.shape)
+    return res if out is None else out.copy_(res)
+
+
+def slot_apg_reference(cond: Tensor, null: Tensor, guidance, norm_threshold: float = 0.0, eta_parallel: float = 0.0,
+                       momentum: float = 0.0, m_prev: Optional[Tensor] = None):
+    """The slot APG of "slot CFG control" / "slot APG momentum" for stepping slots given as rows, in torch on the host: ``cond`` /
+    ``null`` [n, per_slot] (any trailing shape), one slot per row in the slot's own order; ``guidance`` a number or n numbers;
+    ``m_prev`` the slots' momentum elements (required exactly when ``momentum`` != 0).  Returns (e, d), float32: d = (cond - null) +
+    momentum * m_prev with one fp32 rounding per operation — what the fused update stores back — and e = cond + w (d - k cond) with
+    the coefficients from fp64 moments over the row, each rounded once to fp32.  The device sums its moments in 1024-element chunks,
+    so its coefficients may differ from these in the last places."""
+    r, eta_p, beta = apg_params(norm_threshold, eta_parallel, momentum)
+    c, u = cond.detach().cpu().to(torch.float32), null.detach().cpu().to(torch.float32)
+    if c.shape != u.shape or c.dim() < 2:
+        raise ValueError(f"cond {tuple(c.shape)} and null {tuple(u.shape)} must have one shape [n, per_slot, ...]")
+    if (beta != 0.0) != (m_prev is not None):
+        raise ValueError("m_prev goes with momentum != 0: pass both or neither")
+    n = c.shape[0]
+    d = c - u
+    if beta != 0.0:
+        m = m_prev.detach().cpu().to(torch.float32)
+        if m.shape != c.shape:
+            raise ValueError(f"m_prev must have cond's shape {tuple(c.shape)}")
+        d = d + torch.tensor(beta, dtype=torch.float32) * m
+    c64, d64 = c.reshape(n, -1).double(), d.reshape(n, -1).double()
+    sdd, sdc, scc = (d64 * d64).sum(1), (d64 * c64).sum(1), (c64 * c64).sum(1)
+    r64 = float(torch.tensor(r, dtype=torch.float32))
+    eta64 = float(torch.tensor(eta_p, dtype=torch.float32))
+    s = torch.minimum(torch.ones_like(sdd), r64 / sdd.sqrt()).to(torch.float32)
+    s = torch.where((sdd == 0) | ~torch.isfinite(s) | torch.tensor(r64 == 0.0), torch.ones_like(s), s)
+    k = ((1.0 - eta64) * sdc / scc).to(torch.float32)
+    k = torch.where((scc == 0) | ~torch.isfinite(k), torch.zeros_like(k), k)
+    g = torch.as_tensor(guidance, dtype=torch.float32).reshape(-1).expand(n)
+    w = (g - 1.0) * s
+    shape = (n,) + (1,) * (c.dim() - 1)
+    e = c + w.reshape(shape) * (d - k.reshape(shape) * c)
+    return e, d
+
+
 # ---- FIFO device cursors (include/avdiff_hip.h, "FIFO device cursors"): the host numbers of a FIFO iteration read off the device ----
 def _cursor(cursor: Tensor, device: torch.device) -> Tensor:
     if not (isinstance(cursor, Tensor) and cursor.is_cuda and cursor.dtype == torch.int32 and cursor.numel() == 1 and

@@ -175,7 +175,8 @@ class DenoiseEngine:
     ``rewind`` and ``renoise`` (RePaint resampling) carry the buffer as it is: the direction's running average goes on across a jump.
     ``set_apg`` / ``clear_apg`` change it and start a new graph generation (the parameters are held by value).  ``step_slots`` and the
     FIFO queue refuse it, as they refuse every per-sample CFG control: their form is ``set_slot_cfg`` (guidance by noise level, per-slot
-    rescale and APG without momentum; include/avdiff_hip.h, "slot CFG control").  What it does to sample quality at a given guidance
+    rescale and APG, whose momentum is a per-slot buffer that travels with the slot; include/avdiff_hip.h, "slot CFG control" and
+    "slot APG momentum").  What it does to sample quality at a given guidance
     scale is not measured here: that needs trained weights.
 
     ``guidance_interval`` (extension: guidance in a limited interval, Kynkaanniemi et al. 2024; default None = every step is a CFG
@@ -608,7 +609,13 @@ class DenoiseEngine:
             raise ValueError(f"{what} takes no clip guide ({why}): clear_clip_guide() first")
 
     # ---- slot CFG control: guidance by noise level, per-slot guidance rescale and per-slot APG for ``step_slots`` ----
-    def set_slot_cfg(self, guidance=None, rescale=None, apg=None) -> None:
+    # slot APG momentum (set_slot_cfg(apg_momentum=)): beta and the two engine-owned [B, per] buffers; class-level, so that an engine
+    # that never sets one (or a shell built without __init__) reads "none"
+    _smom_beta = 0.0
+    _smom: Optional[torch.Tensor] = None
+    _smom_other: Optional[torch.Tensor] = None
+
+    def set_slot_cfg(self, guidance=None, rescale=None, apg=None, apg_momentum=None) -> None:
         """Control the CFG combine of ``step_slots`` per slot (extension; include/avdiff_hip.h, "slot CFG control"): ``guidance`` and
         ``rescale`` are ``schedule_utils.level_table`` specs — a number, T_train values or a callable t -> value — looked up inside the
         kernels at each slot's own t_now (``schedule_utils.guidance_interval_table`` gives the slot form of a guidance interval);
@@ -618,11 +625,20 @@ class DenoiseEngine:
         part off: the scalar guidance, no rescale, the plain combine.  Everything is checked before anything changes; the tables and
         the scratch are engine-owned, so a later call with new values reaches a captured step.  A ``rescale`` that is zero at every
         level launches no statistics pass.  It is a state of its own: ``set_cfg`` / ``set_apg`` stay the controls of ``step`` /
-        ``run``, which refuse a slot control, as ``step_slots`` refuses theirs."""
-        self._apply_slot_cfg(*self._check_slot_cfg(guidance, rescale, apg))
+        ``run``, which refuse a slot control, as ``step_slots`` refuses theirs.
+        ``apg_momentum`` (a finite number; needs ``apg``; None or 0 = none) is APG's momentum per slot (include/avdiff_hip.h, "slot APG
+        momentum"): every stepping slot's direction becomes d = (cond - null) + apg_momentum * m_prev and is stored back, in two
+        engine-owned zeroed [B, per] buffers in latent layout.  ``fifo_shift`` / ``fifo_lookahead`` / ``fifo_steady`` carry the live
+        one into the other behind their move and the two swap, as the solver histories do, so a slot's momentum travels with it up
+        the queue and an entering slot starts from zero; ``slot_momentum`` is the live buffer.  A call with a momentum keeps the
+        buffers' contents when one was already set (zero them with ``slot_momentum.zero_()``)."""
+        self._apply_slot_cfg(*self._check_slot_cfg(guidance, rescale, apg, apg_momentum))
 
-    def _check_slot_cfg(self, guidance, rescale, apg):
-        """set_slot_cfg's checks alone, on the host: (guidance table or None, rescale table or None, (r, eta_p) or None, scratch bytes)"""
+    def _check_slot_cfg(self, guidance, rescale, apg, apg_momentum=None):
+        """set_slot_cfg's checks alone, on the host: (guidance table or None, rescale table or None, (r, eta_p) or None, scratch bytes,
+        the slot momentum beta)"""
+        if apg_momentum is not None and apg is None:
+            raise ValueError(f"apg_momentum {apg_momentum!r} needs apg: the momentum is adaptive projected guidance's")
         if guidance is None and rescale is None and apg is None:
             raise ValueError("set_slot_cfg needs guidance, rescale or apg (clear_slot_cfg() switches the control off)")
         T = int(self.alpha_bar.numel())
@@ -630,8 +646,12 @@ class DenoiseEngine:
         phi = None if rescale is None else su.level_table(rescale, T, "guidance_rescale", 0.0, 1.0)
         vals = Fn.apg_from_dict(apg)
         if vals is not None and vals[2] != 0.0:
-            raise ValueError("the slot APG takes no momentum: a slot's momentum would have to travel with it through the queue's shift "
-                             "as x0_hist does, which is not built (momentum must be 0)")
+            raise ValueError("the slot APG's dict takes no momentum: that key is the per-sample buffer of set_apg, which does not travel "
+                             "with it through the queue's shift; a slot's momentum is set_slot_cfg(apg_momentum=) / "
+                             "fifo_denoise(apg_momentum=) (the dict's momentum must be 0)")
+        beta = 0.0
+        if apg_momentum is not None:
+            beta = Fn.apg_params(momentum=apg_momentum)[2]      # a number (not a bool), finite
         self._check_apg(vals, torch.zeros(1) if phi is None else phi)
         rescale_on = phi is not None and bool((phi != 0).any())      # phi = 0 at every level: no statistics pass (rescale_t NULL)
         nb = 0
@@ -641,10 +661,14 @@ class DenoiseEngine:
             if nb < 0:
                 raise ValueError(f"the slot CFG control needs >= 2 latent elements per slot and B * S <= 65535 (latent "
                                  f"{self.latent_shape}, {self.slots} slots)")
-        return g, phi if rescale_on else None, None if vals is None else vals[:2], nb
+        return g, phi if rescale_on else None, None if vals is None else vals[:2], nb, beta
 
-    def _apply_slot_cfg(self, g, phi, apg, nb) -> None:
+    def _apply_slot_cfg(self, g, phi, apg, nb, beta=0.0) -> None:
         dev, rescale_on, vals = self.device, phi is not None, apg
+        if beta != 0.0 and self._smom is None:      # zeroed once: a slot that has not stepped has no momentum
+            self._smom = torch.zeros(self.latent_shape, device=dev, dtype=torch.float32)
+            self._smom_other = torch.zeros(self.latent_shape, device=dev, dtype=torch.float32)
+        self._smom_beta = beta
         if g is not None:
             self._scfg_g = g.to(dev) if self._scfg_g is None else self._scfg_g.copy_(g)
         if rescale_on:
@@ -652,12 +676,33 @@ class DenoiseEngine:
         if nb and (self._scfg_stats is None or self._scfg_stats.numel() < nb):
             self._scfg_stats = torch.empty(nb, dtype=torch.uint8, device=dev)
         r, eta_p = (0.0, 0.0) if vals is None else vals
-        self._scfg = L.SlotCfg(None if g is None else self._scfg_g.data_ptr(), self._scfg_phi.data_ptr() if rescale_on else None,
-                               0 if vals is None else 1, r, eta_p, self._scfg_stats.data_ptr() if nb else None, nb)
+        base = (None if g is None else self._scfg_g.data_ptr(), self._scfg_phi.data_ptr() if rescale_on else None,
+                0 if vals is None else 1, r, eta_p, self._scfg_stats.data_ptr() if nb else None, nb)
+        if beta != 0.0:      # the control with its two trailing fields: apg says that they follow
+            self._scfg = L.SlotCfgMomentum(*base[:2], L.SLOT_APG_MOMENTUM, *base[3:], beta, self._smom.data_ptr())
+        else:
+            self._scfg = L.SlotCfg(*base)
 
     def clear_slot_cfg(self) -> None:
-        """Back to the scalar guidance and the plain combine in ``step_slots`` (the buffers are kept for a later set_slot_cfg)."""
+        """Back to the scalar guidance and the plain combine in ``step_slots`` (the tables and the scratch are kept for a later
+        set_slot_cfg; a slot momentum's state is dropped: its beta and both buffers)."""
         self._scfg = None
+        self._smom_beta, self._smom, self._smom_other = 0.0, None, None
+
+    @property
+    def slot_momentum(self) -> Optional[torch.Tensor]:
+        """the live slot APG momentum buffer, float32 of the latent's shape (None without ``set_slot_cfg(apg_momentum=)``): what the
+        next ``step_slots`` reads and overwrites under its stepping slots"""
+        return self._smom if self._smom_beta != 0.0 else None
+
+    def _carry_slot_momentum(self, ctx: int, shift: int) -> None:
+        """behind a queue move: the live momentum buffer through the same move into the other one (``functional.fifo_carry``), and the
+        two swap; the control follows the live address.  Nothing without a slot momentum."""
+        if self._smom_beta == 0.0:
+            return
+        Fn.fifo_carry(self._smom, self.slots, self.slot_len, ctx=ctx, shift=shift, out=self._smom_other)
+        self._smom, self._smom_other = self._smom_other, self._smom
+        self._scfg.momentum_buf = self._smom.data_ptr()
 
     def slot_cfg_coef(self) -> torch.Tensor:
         """The per-slot coefficients the last controlled ``step_slots`` left in the scratch, float32 [B, S, 4] on the device:
@@ -1067,7 +1112,8 @@ class DenoiseEngine:
         ``seed``: the seed of the entering slot's noise, None = the engine's ``noise_seed``): returns (z_out, popped).  Solver "dpmpp_2m": the same launch shifts the history into a
         second engine-owned buffer, which becomes ``x0_hist`` (the head's history is dropped, the entering slot's is zero): a slot
         keeps its history as it moves up the queue.  That changes an address a captured graph holds, so it starts a new graph
-        generation.
+        generation.  Under ``set_slot_cfg(apg_momentum=)`` one more launch (``functional.fifo_carry``) carries the slot momentum into
+        the engine's other momentum buffer in the same way, on either solver, and the two swap.
         ``guided`` (None = the plain shift, also under a clip guide): "mask" or "everywhere" needs ``set_clip_guide`` and puts the
         entering slot, clip slot ``c``, on the guide's forward path at ``t`` inside the same launch (avd_fifo_shift_guided_f32) —
         through the guide's mask, or with the mask read as 1 on every in-canvas position (SDEdit's start)."""
@@ -1083,10 +1129,13 @@ class DenoiseEngine:
             guide = dict(known=self._clip[0], mask=self._clip[1], seed=self._clip[2], alpha_bar=self.alpha_bar,
                          everywhere=guided == "everywhere")
         if self.solver != "dpmpp_2m":
-            return Fn.fifo_shift(z, c, seed, t, self.slot_len, guide=guide)
+            out = Fn.fifo_shift(z, c, seed, t, self.slot_len, guide=guide)
+            self._carry_slot_momentum(0, 1)      # a slot momentum follows its slot: a launch of its own behind the move
+            return out
         if self._hist_other is None:
             self._hist_other = torch.empty_like(self.x0_hist)
         z_out, popped, _ = Fn.fifo_shift(z, c, seed, t, self.slot_len, hist=self.x0_hist, hist_out=self._hist_other, guide=guide)
+        self._carry_slot_momentum(0, 1)
         self.x0_hist, self._hist_other = self._hist_other, self.x0_hist
         self._generation += 1
         self._stale_reason = "fifo_shift moved the solver history into the engine's other history buffer (x0_hist changed its address)"
@@ -1098,7 +1147,8 @@ class DenoiseEngine:
         ``slot_len``; include/avdiff_hip.h, "FIFO lookahead"): returns (z_out, popped), popped None at ``shift=0`` (the refresh of the
         duplicates, which takes no ``c`` / ``t`` / ``seed``).  At ``shift=1`` ``seed`` None is the engine's ``noise_seed``.  Solver
         "dpmpp_2m": as in ``fifo_shift`` the same launch moves the history into the engine's second buffer, which becomes ``x0_hist``,
-        and a new graph generation starts — at either ``shift``, the launch being out of place."""
+        and a new graph generation starts — at either ``shift``, the launch being out of place.  A slot momentum
+        (``set_slot_cfg(apg_momentum=)``) follows the history's map in a ``functional.fifo_carry`` launch behind it, at either ``shift``."""
         self._clip_refusal("fifo_lookahead", "the duplicated slots of overlapping windows are refreshed from their owner copies, and the guide's "
                            "tail pass has no lookahead form yet")
         if shift == 1:
@@ -1106,10 +1156,13 @@ class DenoiseEngine:
             if seed is None:
                 raise ValueError("fifo_lookahead draws the entering slot's noise from a seed: pass one, or build the engine with noise_seed")
         if self.solver != "dpmpp_2m":
-            return Fn.fifo_lookahead(z, ctx, shift, self.slot_len, c=c, seed=seed, t=t)
+            out = Fn.fifo_lookahead(z, ctx, shift, self.slot_len, c=c, seed=seed, t=t)
+            self._carry_slot_momentum(ctx, shift)
+            return out
         if self._hist_other is None:
             self._hist_other = torch.empty_like(self.x0_hist)
         z_out, popped, _ = Fn.fifo_lookahead(z, ctx, shift, self.slot_len, c=c, seed=seed, t=t, hist=self.x0_hist, hist_out=self._hist_other)
+        self._carry_slot_momentum(ctx, shift)
         self.x0_hist, self._hist_other = self._hist_other, self.x0_hist
         self._generation += 1
         self._stale_reason = "fifo_lookahead moved the solver history into the engine's other history buffer (x0_hist changed its address)"
@@ -1198,7 +1251,8 @@ class DenoiseEngine:
         ``step_slots`` z -> tmp on the constant steady tables -> shift tmp -> z, the finished head into slot m of the clip canvas and
         clip slot n + m entering at the tail -> m += 1.  The latent is back in ``z``.  On a stochastic queue the step draws its noise
         for clip slots m .., read off the same cursor.  On "dpmpp_2m" the shift carries the history
-        into the engine's other history buffer and the two swap, as in ``fifo_shift``: two iterations put ``x0_hist`` back."""
+        into the engine's other history buffer and the two swap, as in ``fifo_shift``: two iterations put ``x0_hist`` back.  A slot
+        momentum is carried by one more launch behind the shift and its two buffers swap likewise (``fifo_ramp`` moves nothing)."""
         B, S = self.embed.B, self.slots
         self._fifo_gather(q, q.prompt)
         self._prompt_rows(self._prompt_tokens(q.prompt), self.Xp, temb=False)
@@ -1213,7 +1267,8 @@ class DenoiseEngine:
             if not torch.cuda.is_current_stream_capturing():      # a captured pair swaps twice: the address is back where it was
                 self._generation += 1
                 self._stale_reason = "fifo_steady moved the solver history into the engine's other history buffer (x0_hist changed its address)"
-        Fn.cursor_add(q.m)
+        self._carry_slot_momentum(0, 1)      # the carry's map reads no cursor: the same launch eagerly and in a captured pair, whose two
+        Fn.cursor_add(q.m)                   # iterations put the live buffer back at its address, as the histories
 
     def fifo_capture(self, q: "FifoQueue", steady: bool, za: torch.Tensor, zb: torch.Tensor) -> "torch.cuda.CUDAGraph":
         """Two iterations of one phase of an open queue in one HIP graph, one chain on one stream: ramp za -> zb -> za, steady twice

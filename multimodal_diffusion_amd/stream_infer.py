@@ -255,7 +255,8 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
                  graph: Optional[bool] = False, lookahead: int = 0, context: Optional[torch.Tensor] = None,
                  init_canvas: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, guide_seed: int = 0,
                  guide_start: str = "noise", guidance_by_level=None, rescale_by_level=None, apg: Optional[dict] = None,
-                 guided_shift: bool = False, prompt_den: int = 1, prompt_interp: Optional[str] = None) -> torch.Tensor:
+                 guided_shift: bool = False, prompt_den: int = 1, prompt_interp: Optional[str] = None,
+                 apg_momentum: Optional[float] = None) -> torch.Tensor:
     """FIFO diagonal denoising (FIFO-Diffusion, Kim et al. 2024, with latent partitioning): a clip of ``n_slots`` slots of
     ``engine.slot_len`` latent positions, denoised in a queue whose slots sit at different noise levels.  Returns the finished latent
     canvas [C, n_slots * slot_len, H, W] (video target) or [Ca, n_slots * slot_len] (audio target).
@@ -320,8 +321,13 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     ``guidance_by_level`` / ``rescale_by_level`` / ``apg`` (every driver: eager, ``graph=True``, ``lookahead``, and the eager one under
     ``init_canvas``) control the CFG combine per slot (``DenoiseEngine.set_slot_cfg``; include/avdiff_hip.h, "slot CFG control"): the
     first two are ``schedule_utils.level_table`` specs looked up at each slot's own noise level (``guidance_interval_table`` gives a
-    guidance interval), ``apg`` {"norm_threshold":, "eta_parallel":} is per-slot adaptive projected guidance (no momentum).  They are
+    guidance interval), ``apg`` {"norm_threshold":, "eta_parallel":} is per-slot adaptive projected guidance.  They are
     checked before anything is allocated; the engine's slot control is set for the call and cleared after it, also when it raises.
+    ``apg_momentum`` (with ``apg``; every driver; a finite number, negative in the APG paper; None or 0 = none) adds APG's momentum per
+    slot (include/avdiff_hip.h, "slot APG momentum"): every slot's direction accumulates over the steps it takes, in an engine-owned
+    buffer that each queue move carries along with the slot (one ``functional.fifo_carry`` launch behind the shift); the call starts
+    from a zeroed buffer and an entering slot from zero.  The ``apg`` dict's own "momentum" key stays refused: it names the
+    per-sample buffer of ``DenoiseEngine.set_apg``.
     ``prompt_den`` / ``prompt_interp`` (every driver; defaults 1 / None) make the prompt hop the fraction ``prompt_hop / prompt_den`` of
     prompt positions per target slot (include/avdiff_hip.h, "fractional prompt hop"): a video prompt under an audio target, 8 / 25 at
     the shipped geometry.  ``prompt_hop`` keeps its meaning and its check: it is the numerator.  ``prompt_interp`` "nearest" reads the
@@ -334,8 +340,8 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     if not isinstance(engine, DenoiseEngine):
         raise TypeError("fifo_denoise drives a DenoiseEngine")
     scfg = None
-    if guidance_by_level is not None or rescale_by_level is not None or apg is not None:
-        scfg = engine._check_slot_cfg(guidance_by_level, rescale_by_level, apg)
+    if guidance_by_level is not None or rescale_by_level is not None or apg is not None or apg_momentum is not None:
+        scfg = engine._check_slot_cfg(guidance_by_level, rescale_by_level, apg, apg_momentum)
     if isinstance(n_slots, bool) or not isinstance(n_slots, int) or n_slots < 1:
         raise ValueError(f"n_slots must be an int >= 1, got {n_slots!r}")
     if isinstance(prompt_hop, bool) or not isinstance(prompt_hop, int) or prompt_hop < 1:
@@ -399,9 +405,11 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
 @contextlib.contextmanager
 def _slot_cfg_scope(engine: DenoiseEngine, checked):
     """the engine's slot CFG control for one fifo_denoise call: ``checked`` is ``_check_slot_cfg``'s result, None = leave the engine as
-    it is"""
+    it is.  Either way a slot momentum starts the call from zero."""
     if checked is not None:
         engine._apply_slot_cfg(*checked)
+    if engine.slot_momentum is not None:
+        engine.slot_momentum.zero_()
     try:
         yield
     finally:
@@ -714,8 +722,8 @@ def fifo_geometry(cfg: Dict, prompt_modality: str, n_windows: int, steps: int, l
 
 def _fifo_options(cfg: Dict, *, shard, consensus, noise_keying, resample, init_noise, fifo) -> dict:
     """What ``stream_generate(sampler="fifo")`` refuses, before anything is read or encoded, and its ``fifo`` options ({"steps":
-    None = the target's sampler_steps, "lookahead": 0, "graph": False, "prompt_interp": None}; the argument wins over
-    ``streaming.fifo``)."""
+    None = the target's sampler_steps, "lookahead": 0, "graph": False, "prompt_interp": None, "apg_momentum": None}; the argument
+    wins over ``streaming.fifo``)."""
     st = cfg.get("streaming", {})
     if shard:
         raise ValueError("sampler='fifo' with shard=True is not implemented: the queue is one chain of steps on one device")
@@ -730,9 +738,11 @@ def _fifo_options(cfg: Dict, *, shard, consensus, noise_keying, resample, init_n
         raise ValueError("sampler='fifo' takes no init_noise: the queue starts from the canvas-keyed noise stream of seed")
     opts = fifo if fifo is not None else st.get("fifo")
     opts = {} if opts is None else opts
-    if not isinstance(opts, dict) or set(opts) - {"steps", "lookahead", "graph", "prompt_interp"}:
-        raise ValueError(f"fifo takes a dict with any of steps, lookahead and graph, or prompt_interp, got {opts!r}")
-    opts = dict({"steps": None, "lookahead": 0, "graph": False, "prompt_interp": None}, **opts)
+    if not isinstance(opts, dict) or set(opts) - {"steps", "lookahead", "graph", "prompt_interp", "apg_momentum"}:
+        raise ValueError(f"fifo takes a dict with any of steps, lookahead and graph, or prompt_interp, or apg_momentum, got {opts!r}")
+    opts = dict({"steps": None, "lookahead": 0, "graph": False, "prompt_interp": None, "apg_momentum": None}, **opts)
+    if opts["apg_momentum"] is not None:      # the slot APG momentum (fifo_denoise(apg_momentum=)): a finite number, not a bool
+        opts["apg_momentum"] = Fn.apg_params(momentum=opts["apg_momentum"])[2]
     if opts["steps"] is not None and (isinstance(opts["steps"], bool) or not isinstance(opts["steps"], int) or opts["steps"] < 1):
         raise ValueError(f"fifo['steps'] must be an int >= 1 or None, got {opts['steps']!r}")
     if isinstance(opts["lookahead"], bool) or not isinstance(opts["lookahead"], int) or opts["lookahead"] < 0:
@@ -767,9 +777,15 @@ def _stream_generate_fifo(cfg: Dict, pc, mods: Dict, device, prompt_modality: st
         ctl["rescale_by_level"] = pc.rescale
     if pc.apg is not None:
         if pc.apg[2] != 0.0:
-            raise ValueError(f"sampling.apg momentum {pc.apg[2]:g}: the FIFO queue has no slot momentum (a slot's buffer would have to "
-                             "travel with it through the shift); set momentum to 0")
+            raise ValueError(f"sampling.apg momentum {pc.apg[2]:g} is the per-sample buffer's and gives the FIFO queue no slot momentum "
+                             "(that buffer does not travel with a slot through the shift): set it to 0 and use "
+                             "streaming.fifo.apg_momentum (fifo={'apg_momentum': beta})")
         ctl["apg"] = {"norm_threshold": pc.apg[0], "eta_parallel": pc.apg[1]}
+    if opts["apg_momentum"] is not None:
+        if pc.apg is None:
+            raise ValueError(f"fifo['apg_momentum'] {opts['apg_momentum']:g} needs sampling.apg for the target: the momentum is adaptive "
+                             "projected guidance's")
+        ctl["apg_momentum"] = opts["apg_momentum"]
     mc = None if mask is None else _canvas_mask(mask, lat, Nw, geo.hop_t, geo.L_t)
 
     def one_canvas(windows: torch.Tensor, hop: int) -> torch.Tensor:
@@ -900,15 +916,17 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     must be a multiple of the S - lookahead stepping slots of a sample); the canvas is cut into the windows' latents (``windows_from_canvas``), which are decoded in batches of
     ``max_windows_per_batch`` and cross-faded as above, so the output has the windows sampler's length and dtype.
     ``fifo`` (or ``streaming.fifo``; the argument wins) = {"steps": the target's ``sampler_steps``, "lookahead": 0, "graph": False,
-    "prompt_interp": None}, ``fifo_denoise``'s arguments; unknown keys are refused.  ``prompt_interp`` "nearest" or "linear" admits a
+    "prompt_interp": None, "apg_momentum": None}, ``fifo_denoise``'s arguments; unknown keys are refused.  ``apg_momentum`` (a finite
+    number; needs ``sampling.apg`` for the target) is APG's momentum per slot, carried with the slot through the queue
+    (include/avdiff_hip.h, "slot APG momentum").  ``prompt_interp`` "nearest" or "linear" admits a
     prompt with a fractional number of latent positions per target slot (include/avdiff_hip.h, "fractional prompt hop"; a video prompt
     at the shipped geometry: 8 / 25): ``fifo_geometry`` reduces the hop and ``fifo_denoise`` walks it, reading between two prompt
     positions by the nearest row or by an fp32 blend of the two.  The choice is the user's: which conditions a trained model better
     cannot be measured on synthetic weights.  None keeps the refusal of such a prompt.
     ``seed`` seeds the queue's start and entering noise (None: drawn once from torch's global CPU generator), ``noise_seed`` the engine's step noise (``ddim_eta`` > 0 needs it).  The config's solver, eta and
     guidance go to the engine; its per-sample CFG controls become ``fifo_denoise``'s slot controls: the guidance interval a
-    ``guidance_interval_table``, ``guidance_rescale`` a constant ``rescale_by_level``, ``sampling.apg`` the per-slot APG (a momentum
-    != 0 is refused: the queue has none).  An init clip is made one canvas like the prompt and guides the queue (``init_canvas``):
+    ``guidance_interval_table``, ``guidance_rescale`` a constant ``rescale_by_level``, ``sampling.apg`` the per-slot APG (its own momentum
+    key != 0 is refused: that is the per-sample buffer; the queue's is ``fifo["apg_momentum"]``).  An init clip is made one canvas like the prompt and guides the queue (``init_canvas``):
     ``mask`` is passed whole, ``strength`` < 1 truncates the schedule (the truncated length must still divide) and starts every
     position from the clip (``guide_start="init"``; without a mask everything is free afterwards), ``strength`` 0 returns the decoded
     known canvas.  The entering slots are guided inside the shift's launch (``guided_shift=True``).  It runs eagerly on the plain queue:

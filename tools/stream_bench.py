@@ -16,7 +16,18 @@ no trained weights.  The record is profiles/stream_fifo_e2e.txt.
             rows alone are timed, so the same command on the parent commit gives the figures to compare.
   e2e       one video -> audio clip through the windows sampler and through sampler="fifo" with prompt_interp "linear" and "nearest"
             (eager, and "linear" replayed from HIP graphs), --steps steps (74 = 2 x the S = 37 slots of an audio sample).
-The records are profiles/fifo_prompt_frac_kernels.txt and profiles/fifo_prompt_frac_e2e.txt."""
+The records are profiles/fifo_prompt_frac_kernels.txt and profiles/fifo_prompt_frac_e2e.txt.
+
+--slot-momentum kernels | e2e times the slot APG momentum (include/avdiff_hip.h, "slot APG momentum") instead:
+  kernels   at the C3 latent [B, 8, 12, 32, 32] (S = 6), B = 32 and 8, through the C entries of the fused slot update alone: the plain
+            slot update, the slot APG update at beta = 0 and with a momentum buffer, with their statistics launches, for DDIM and
+            DPM-Solver++(2M) at eta 0; the plain queue shift and the carry launch.  Kernel time under the library's launch events,
+            --launches launches per window, the variants interleaved over --rounds rounds, all rounds printed.  On a checkout without
+            the momentum the unchanged entries alone are timed (the plain update, the beta = 0 slot APG, the plain shift), so the
+            same command on the parent commit gives the figures to compare.
+  e2e       fifo_denoise under the slot APG with and without apg_momentum, DDIM at n = 48 and DPM-Solver++(2M) at n = 18 (8 layers),
+            --slots-out and twice as many finished slots: the time per finished slot is the difference.
+The records are profiles/slot_momentum_kernels.txt, profiles/slot_momentum_e2e.txt and profiles/slot_momentum_parent.txt."""
 import argparse
 import statistics
 import sys
@@ -37,7 +48,9 @@ ap.add_argument("--steps", type=int, default=48, help="sampler steps of all thre
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--matmul", default="bf16x3", help="matrix-pipe mode (default: bench.py's headline mode)")
 ap.add_argument("--prompt-frac", choices=("kernels", "e2e"), default=None, help="time the fractional prompt hop instead (see above)")
-ap.add_argument("--launches", type=int, default=200, help="--prompt-frac kernels: launches per timed window")
+ap.add_argument("--launches", type=int, default=200, help="--prompt-frac / --slot-momentum kernels: launches per timed window")
+ap.add_argument("--slot-momentum", choices=("kernels", "e2e"), default=None, help="time the slot APG momentum instead (see above)")
+ap.add_argument("--slots-out", type=int, default=12, help="--slot-momentum e2e: finished slots per timed fifo_denoise call")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
@@ -56,7 +69,7 @@ cfg = {"tokenizer": {"width": 512, "video": {"tube": {"t": 2, "h": 4, "w": 4}}, 
        "streaming": {"window_seconds": 3.0, "hop_seconds": 1.0, "crossfade_seconds": 0.25}}
 wav = (0.1 * torch.randn(int(args.seconds * 16000), generator=torch.Generator().manual_seed(9))).numpy()
 n_windows = S.split_audio_into_windows(wav, 16000, 3.0, 1.0)[0].shape[0]
-geo = S.fifo_geometry(cfg, "audio", n_windows, args.steps) if args.prompt_frac is None else None
+geo = S.fifo_geometry(cfg, "audio", n_windows, args.steps) if args.prompt_frac is None and args.slot_momentum is None else None
 kw = dict(cfg=cfg, vid_vae=vae, aud_codec=codec, adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=tdim, device=dev,
           prompt_modality="audio", prompt_video=None, prompt_audio=wav, seed=1, max_windows_per_batch=32)
 kinds = [("windows", {}), ("consensus", dict(consensus="uniform")), ("fifo", dict(sampler="fifo"))]
@@ -146,8 +159,132 @@ def prompt_frac_e2e():
     print("  quality is not measured: there are no trained weights, so neither sampler nor prompt_interp mode can be ranked by ear or metric")
 
 
+def slot_momentum_kernels():
+    import ctypes as C
+    from multimodal_diffusion_amd import _lib as L, functional as Fn, schedule_utils as su
+    from oracle import ref_cpu as R
+    lib = L.lib()
+    has_mom = hasattr(Fn, "fifo_carry")
+    abar = R.alpha_bar_table(R.beta_table(1000)).to(dev)
+    S_, sl, T_ = 6, 2, 1000
+    g = torch.Generator().manual_seed(0)
+    PLAIN, CTL, MOM = "cfg_unpatch_ddim_kernel", "cfg_unpatch_ddim_kernel<slot cfg>", "cfg_unpatch_ddim_kernel<slot momentum>"
+    STATS, STATS_M = "slot_cfg_stats_kernel", "slot_cfg_stats_kernel<momentum>"
+    rows = []
+    for B in (32, 8):
+        shape = (B, 8, 12, 32, 32)
+        z, hist, mom, out = (torch.randn(shape, generator=g).to(dev) for _ in range(4))
+        eps2 = torch.randn(2 * B, 6 * 8 * 8, 256, generator=g).to(dev)
+        nb = lib.avd_slot_cfg_stats_bytes(B, S_, 8 * sl * 32 * 32)
+        stats = torch.empty(nb, dtype=torch.uint8, device=dev)
+        key = L.SlotKey(0, 0, 1, None)
+        for solver, n in (("ddim", 48), ("dpmpp_2m", 18)):
+            dpm = solver == "dpmpp_2m"
+            sched = su.make_sampling_schedule(T_, n)
+            i = (torch.arange(B * S_) % (n - 2)).view(B, S_) + 1      # the diagonal: none held, none final
+            tl, tn, tp = (sched[i + d].to(dev).contiguous() for d in (-1, 0, 1))
+            head = (eps2.data_ptr(), z.data_ptr(), tl.data_ptr() if dpm else None, tn.data_ptr(), tp.data_ptr(), abar.data_ptr(), T_, 3.5, 0.0)
+            tail = (S_, hist.data_ptr() if dpm else None, out.data_ptr(), *shape, 2, 4, 4)
+
+            def plain(head=head, tail=tail):
+                L.check(lib.avd_cfg_unpatch_ddim_slots_seeded_f32(*head, C.byref(key), *tail, L.stream_ptr(dev)))
+
+            def ctl(beta, head=head, tail=tail):
+                cfg_ = L.SlotCfg(None, None, 1, 20.0, 0.5, stats.data_ptr(), nb)
+                if beta:      # the control with its two trailing fields
+                    cfg_ = L.SlotCfgMomentum(None, None, L.SLOT_APG_MOMENTUM, 20.0, 0.5, stats.data_ptr(), nb, beta, mom.data_ptr())
+                return lambda: L.check(lib.avd_cfg_unpatch_ddim_slots_cfg_f32(*head, None, None, *tail, C.byref(cfg_), L.stream_ptr(dev)))
+
+            name = f"B={B} {solver}"
+            rows += [(f"{name}: plain slot update (a)", PLAIN, plain), (f"{name}: slot APG beta = 0, update", CTL, ctl(0.0)),
+                     (f"{name}: slot APG beta = 0, statistics", STATS, ctl(0.0))]
+            if has_mom:
+                rows += [(f"{name}: slot APG momentum, update", MOM, ctl(-0.5)), (f"{name}: slot APG momentum, statistics", STATS_M, ctl(-0.5))]
+            rows += [(f"{name}: plain slot update (b)", PLAIN, plain)]
+        shift = lambda z=z, B=B: Fn.fifo_shift(z, B * S_, 7, 999, sl)      # noqa: E731
+        rows += [(f"B={B}: plain shift (a)", "fifo_shift_kernel<4>", shift)]
+        if has_mom:
+            rows += [(f"B={B}: carry", "fifo_carry_kernel<4>", lambda mom=mom, out=out: Fn.fifo_carry(mom, S_, sl, out=out))]
+        rows += [(f"B={B}: plain shift (b)", "fifo_shift_kernel<4>", shift)]
+
+    def per_launch_us(tag, fn):
+        L.prof_enable(True)
+        try:
+            for _ in range(args.launches):
+                fn()
+            torch.cuda.synchronize()
+        finally:
+            L.prof_enable(False)
+        n, ms, _ = L.prof_report()[tag]
+        assert n == args.launches, (tag, n)
+        return 1e3 * ms / n
+
+    for _, _, fn in rows:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    res = {name: [] for name, _, _ in rows}
+    for _ in range(args.rounds):
+        for name, tag, fn in rows:
+            res[name].append(per_launch_us(tag, fn))
+    print(f"C3 latent [B, 8, 12, 32, 32] (S = {S_} slots of 16384 elements: 16 chunks per slot), the fused CFG + un-patch + solver slot "
+          f"update through its C entries (random eps tokens, the diagonal's tables: no slot held), eta 0: plain, under the slot APG at beta "
+          f"= 0 and with a momentum buffer (beta -0.5), with the statistics launch of each; the plain queue shift and the carry launch.  "
+          f"{args.rounds} interleaved rounds of {args.launches} launches, microseconds per launch (launch events)")
+    if not has_mom:
+        print("  this checkout has no slot momentum: the unchanged entries alone")
+    for name, _, _ in rows:
+        v = res[name]
+        print(f"  {name:46s} " + " ".join(f"{x:8.2f}" for x in v) + f"   median {statistics.median(v):8.2f}")
+    for B in (32, 8):                                      # the spread of the entries timed twice: what a difference has to exceed
+        for what in ("ddim: plain slot update", "dpmpp_2m: plain slot update", "plain shift"):
+            sep = " " if "shift" not in what else ": "
+            v = res[f"B={B}{sep}{what} (a)"] + res[f"B={B}{sep}{what} (b)"]
+            print(f"  B={B} {what}: run-to-run spread {min(v):.2f} .. {max(v):.2f}")
+
+
+def slot_momentum_e2e():
+    from multimodal_diffusion_amd import schedule_utils as su
+    from oracle import ref_cpu as R
+    abar = R.alpha_bar_table(R.beta_table(1000))
+    S_, K = 6, args.slots_out
+    g = torch.Generator().manual_seed(1)
+    apg = {"norm_threshold": 20.0, "eta_parallel": 0.5}
+    has_mom = "apg_momentum" in __import__("inspect").signature(A.fifo_denoise).parameters
+    print(f"fifo_denoise under the slot APG without and with apg_momentum = -0.5 (one carry launch behind every shift), S = {S_} (C3 latent, "
+          f"8 layers, {args.matmul}, eager), {args.rounds} rounds, the calls interleaved, {K} and {2 * K} slots out; milliseconds")
+    for solver, n in (("ddim", 48), ("dpmpp_2m", 18)):
+        sched = su.make_sampling_schedule(1000, n)
+        canvas_p = torch.randn(8, 25 * (n + 2 * K) + 148, generator=g).to(dev)
+        eng = A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=tdim, target="video",
+                              latent_shape=(n // S_, 8, 12, 32, 32), prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul=args.matmul,
+                              solver=solver)
+        kinds = [("apg", dict(apg=apg))] + ([("momentum", dict(apg=apg, apg_momentum=-0.5))] if has_mom else [])
+        for _, kw_ in kinds:
+            A.fifo_denoise(eng, canvas_p, 25, sched, 4, 5, **kw_)      # warm-up
+        ts_ = {(name, K_): [] for name, _ in kinds for K_ in (K, 2 * K)}
+        for _ in range(args.rounds):
+            for K_ in (K, 2 * K):
+                for name, kw_ in kinds:
+                    ts_[name, K_].append(timed(lambda: A.fifo_denoise(eng, canvas_p, 25, sched, K_, 5, **kw_))[0])
+        per = {}
+        for name, _ in kinds:
+            whole = {K_: statistics.median(ts_[name, K_]) for K_ in (K, 2 * K)}
+            per[name] = (whole[2 * K] - whole[K]) / K
+            print(f"  {solver:8s} n = {n}, B = {n // S_}, {name:8s}: " +
+                  "; ".join(f"{K_} out " + " ".join(f"{t * 1e3:7.1f}" for t in ts_[name, K_]) for K_ in (K, 2 * K)) +
+                  f"; per finished slot {per[name] * 1e3:.3f}")
+        if has_mom:
+            print(f"  {'':8s} per finished slot, momentum against none: {(per['momentum'] - per['apg']) * 1e3:+.3f} ms "
+                  f"(x {per['momentum'] / per['apg']:.3f})")
+    print("  quality is not measured: there are no trained weights")
+
+
 if args.prompt_frac is not None:
     prompt_frac_kernels() if args.prompt_frac == "kernels" else prompt_frac_e2e()
+    sys.exit(0)
+if args.slot_momentum is not None:
+    slot_momentum_kernels() if args.slot_momentum == "kernels" else slot_momentum_e2e()
     sys.exit(0)
 
 frames = None
