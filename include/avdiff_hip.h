@@ -75,7 +75,8 @@ int         avd_tune_set(const char* key, int64_t value);
  * variable, read when the library loads).  With the target rows first, every prompt row of a null sample is the zero row at the
  * input and stays one and the same row through every block, so avd_denoise_step_*_f32 carries one of them per null sample and
  * copies its k / v into the key slots of the others before each attention: the attention sees the keys and values of the full
- * layout and the step's results are bit-identical to it.  Taken by the stacked one-stream step (split_streams 0) in concat timestep
+ * layout and the step's results are bit-identical to it.  Taken by the stacked one-stream step (split_streams 0) and by the
+ * two-chain step that asks for it (split_streams 2, at avd_step_desc below; split_streams 1 keeps the full layout) in concat timestep
  * mode with target_first, Np >= 2, on the folded bf16x3 path (six or nine terms) with the trimmed last block and its residual row map —
  * today the six-term 16x16x32 kernels have that map, so "bf16x3_strict" still runs the full layout; every other step runs the full
  * layout whatever the switch says.  Workspace sizes do not depend on it and it may change between calls (not inside a captured
@@ -1074,7 +1075,14 @@ typedef struct {                       /* one whole CFG denoising step (sample_c
     const float* alpha_bar; int T_train;
     float guidance, eta;
     int split_streams;   /* !=0: run the cond and null CFG halves as two kernel chains on two streams (fork/join by events;
-                            graph-capturable); results are bit-identical to the single-stream order */
+                            graph-capturable); results are bit-identical to the single-stream order.  1: both chains on the full
+                            layout.  2: the null half's short layout (avd_cfg_dedup_set above) as two chains — the cond half, B
+                            samples of N rows, on `stream`, the null half, B samples of Nt + 1 rows, on the second stream, both on
+                            the kernels the stacked 2B x N batch takes — and the one-stream step (0) wherever that layout does not
+                            apply.  The null chain starts at the fork, or, with the tune key cfg_offset (AVD_CFG_OFFSET; 0 default,
+                            1 .. 3) set to k > 0, behind the cond chain's k-th launch of block 0 (in_proj, attention, out_proj): an
+                            event recorded there, no waiting in kernels; measured slower than 0 at every k
+                            (profiles/two_stream_dedup_e2e.txt) */
 } avd_step_desc;
 int64_t avd_step_workspace_bytes(const avd_step_desc* s);
 /* z_out = DDIM(z, eps_cfg(z, Xp, t_now), t_now -> t_prev).  z_out must not alias z. */

@@ -1081,7 +1081,7 @@ int attn_bf16x3(const void* qkv3, float* out, void* out3, int B, int N, int H, i
                 float out_scale, int out_tokens, const RowSegs* out_rows) {
     const int out_tok = out_tokens > 0 ? out_tokens : N;
     AVD_REQUIRE(out_tok >= n_query, AVD_EINVAL, "attn_bf16x3: out_tokens=%d < n_query=%d", out_tok, n_query);
-    AVD_REQUIRE(!out_rows || (out_rows->n_samples() == B && out_rows->samples[0] > 0 && out_rows->tok[0] > 0 && out_rows->tok[1] > 0 &&
+    AVD_REQUIRE(!out_rows || (out_rows->n_samples() == B && out_rows->samples[0] >= 0 && out_rows->samples[1] >= 0 && out_rows->tok[0] > 0 && out_rows->tok[1] > 0 &&
                               out_rows->m0 == (int64_t)out_rows->samples[0] * out_rows->tok[0]), AVD_EINVAL,
                 "attn_bf16x3: the output row layout does not hold the batch's %d samples", B);
     const RowSegs oseg = out_rows ? *out_rows : RowSegs::uniform(B, out_tok);

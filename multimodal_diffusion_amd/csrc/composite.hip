@@ -197,9 +197,18 @@ static bool core_use_fold(const avd_core_weights* w) {
     return true;
 }
 
+#define AVD_HIP(call)                                                                        \
+    do {                                                                                     \
+        hipError_t e__ = (call);                                                             \
+        if (e__ != hipSuccess) return set_error(AVD_ELAUNCH, "%s: %s", #call, hipGetErrorString(e__)); \
+    } while (0)
+
 // last-block dead-row elimination (avd_tune_set "core_trim" 0 switches it off: measurement aid / A-B in tests)
 static int g_core_trim = 1;
 static int64_t core_trim_floats(const avd_core_weights* w, int B, int N) { return (int64_t)B * N * w->d; }
+// launches of block 0 by which the null chain of the two-chain short-layout step trails the cond chain (avd_tune_set "cfg_offset", 0 .. 3;
+// 0, both chains start at the fork, measured fastest: profiles/two_stream_dedup_e2e.txt)
+static int g_cfg_offset = 0;
 
 // The null CFG half without its duplicate prompt rows (avd_cfg_dedup_set / AVD_CFG_DEDUP, default on).  With the target rows first the
 // null half of the stacked step is cat([target rows, zero rows]): every prompt row of a null sample is the zero row at the input,
@@ -283,9 +292,15 @@ static bool core_dedup_ok(const avd_core_weights* w, int B2, int N, int n_out) {
 // segs != null (core_dedup_ok holds, out_row0 == 0): x is that two-segment layout — samples 0 .. segs->samples[0] - 1 with N rows, the others
 // with n_out_rows + 1 (the last one stands for the N - n_out_rows equal rows of the full layout) — and y receives the normalised
 // output rows compactly, [B * n_out_rows, d], instead of the [B, N, d] layout.  Kernel families and workspace follow the full B x N.
+// segs->samples[0] == 0 (m0 == 0) is the batch whose samples are ALL short: the null half of a step that runs its halves as two calls.
+// plan_samples > B (the folded split path): this call is one part of a stacked batch of plan_samples samples — the split GEMMs choose
+// their kernel family, rows per block and ring depth as for the whole batch, as the one call over it would.
+// lead (the folded split path): recorded on st behind block 0's in_proj (lead_after 1), attention (2) or out_proj (3) — what a second
+// chain waits on to trail this one by that many launches.
 static int core_forward(const avd_core_weights* w, const float* x, float* y, int B, int N, int out_row0,
                         int n_out_rows, const unsigned char* kpm, void* ws, int64_t ws_bytes, hipStream_t st,
-                        const float* ss_first = nullptr, const RowSegs* segs = nullptr) {
+                        const float* ss_first = nullptr, const RowSegs* segs = nullptr, int plan_samples = 0,
+                        hipEvent_t lead = nullptr, int lead_after = 0) {
     if (int rc = check_core(w)) return rc;
     AVD_REQUIRE(x && y && B > 0 && N > 0, AVD_EINVAL, "core: bad input");
     AVD_REQUIRE(out_row0 >= 0 && n_out_rows > 0 && out_row0 + n_out_rows <= N, AVD_EINVAL, "core: bad output row window");
@@ -305,8 +320,10 @@ static int core_forward(const avd_core_weights* w, const float* x, float* y, int
     AVD_REQUIRE(!(w->attn_mode == 1 && (kpm || w->norm_kind != 0)), AVD_EUNSUPPORTED,
                 "core: attn_mode 1 (fp8 attention) cannot be combined with a key_padding_mask or norm_kind 1 (LayerNorm)");
     const int null_from = segs ? segs->samples[0] : 0;
-    AVD_REQUIRE(!segs || (null_from > 0 && segs->n_samples() == B && segs->tok[0] == N && segs->tok[1] == n_out_rows + 1 &&
-                          segs->m0 == (int64_t)null_from * N && out_row0 == 0 && !kpm && core_dedup_ok(w, B, N, n_out_rows)), AVD_EUNSUPPORTED,
+    const int Bp = plan_samples > B ? plan_samples : B;              // samples of the stacked batch this call belongs to
+    AVD_REQUIRE(!segs || (null_from >= 0 && segs->samples[1] > 0 && segs->n_samples() == B && segs->tok[0] == N &&
+                          segs->tok[1] == n_out_rows + 1 && segs->m0 == (int64_t)null_from * N && out_row0 == 0 && !kpm &&
+                          core_dedup_ok(w, null_from ? B : Bp, N, n_out_rows)), AVD_EUNSUPPORTED,
                 "core: the two-segment row layout needs the folded six-term split path with the trimmed last block");
     AVD_REQUIRE(!(w->attn_mode == 1 && !core_use_split(w, M)), AVD_EUNSUPPORTED,
                 "core: attn_mode 1 (fp8 attention) reads the q|k|v image of the split-operand projections, which these weights / shapes "
@@ -327,7 +344,8 @@ static int core_forward(const avd_core_weights* w, const float* x, float* y, int
             // scale and multiply their rows by 1 / (rms + eps) before the bias.  No norm kernel between the first split and the final norm.
             void* hx = cs.take((split3_bytes(M, d) + 3) / 4);           // image of the residual stream
             float* ss = cs.take(M * (d / 64));                           // its rows' sums of squares, [M][d / 64]
-            const int ns = gemm_bf16x3_splitk_slices(M, d, hid, terms);
+            const int64_t Mp = (int64_t)Bp * N;                          // rows the GEMMs plan for (plan_samples)
+            const int ns = gemm_bf16x3_splitk_slices(Mp, d, hid, terms);
             float* part = ns ? cs.take(gemm_bf16x3_splitk_ws_floats(M, d, ns)) : nullptr;
             // dead-row elimination in the LAST block (sample_clip.py:375,379 consume the target rows only): its attention already
             // computes only the caller's row window; when that window starts at row 0 the attention writes those rows compactly and
@@ -344,9 +362,13 @@ static int core_forward(const avd_core_weights* w, const float* x, float* y, int
             // in_proj of block b into the q|k|v image (N key slots per sample in either layout); the short samples' last row is the
             // k and v of the slots behind it as well
             auto in_proj = [&](const avd_block_weights& b) {
-                if (int rc = gemm_bf16x3_qkv3(hx, b.in_proj_weight3n, b.in_proj_bias, qkv, seg, H, d, qscale, terms, st, 1.f, 1.f, ss, w->norm_eps, M))
+                if (int rc = gemm_bf16x3_qkv3(hx, b.in_proj_weight3n, b.in_proj_bias, qkv, seg, H, d, qscale, terms, st, 1.f, 1.f, ss, w->norm_eps, Mp))
                     return rc;
-                return null_from ? qkv3_replicate(qkv, B, H, N, null_from, B - null_from, n_out_rows, st) : (int)AVD_OK;
+                return segs ? qkv3_replicate(qkv, B, H, N, null_from, B - null_from, n_out_rows, st) : (int)AVD_OK;
+            };
+            auto mark = [&](int l, int n) {      // the launch of block 0 a trailing chain waits for
+                if (lead && l == 0 && n == lead_after) AVD_HIP(hipEventRecord(lead, st));
+                return (int)AVD_OK;
             };
             if (int rc = split3_rows_f32(cur, rd, hx, Mr, d, st, 0.f, ss)) return rc;
             for (int l = 0; l < w->n_layers; ++l) {
@@ -354,39 +376,46 @@ static int core_forward(const avd_core_weights* w, const float* x, float* y, int
                 const bool last = l == w->n_layers - 1;
                 const int nq = (last && out_row0 == 0) ? n_out_rows : N;
                 if (last && trim) {
-                    const int64_t Mc = (int64_t)B * nq;
+                    const int64_t Mc = (int64_t)B * nq, Mcp = (int64_t)Bp * nq;
                     if (int rc = in_proj(b)) return rc;
+                    if (int rc = mark(l, 1)) return rc;
                     if (int rc = attn_bf16x3(qkv, nullptr, hs, B, N, H, nq, terms, st, 1.f, 1.f, nq)) return rc;       // rows b * nq + q
+                    if (int rc = mark(l, 2)) return rc;
                     if (int rc = gemm_bf16x3(hs, b.out_proj_weight3, b.out_proj_bias, cur, yc, hx, Mc, d, d, AVD_ACT_NONE, terms, st, 1.f, 1.f,
-                                             nullptr, 0.f, ss, nullptr, nq, &seg)) return rc;                               // residual rows seg.row(b, q)
+                                             nullptr, 0.f, ss, nullptr, nq, &seg, Mcp)) return rc;                          // residual rows seg.row(b, q)
+                    if (int rc = mark(l, 3)) return rc;
                     if (fused) {
                         if (int rc = mlp_bf16x3(hx, b.fc1_weight3n, b.fc1_bias, b.fc2_weight3, b.fc2_bias, ss, w->norm_eps, yc, yc, nullptr, nullptr, Mc,
                                                 d, hid, st)) return rc;
                     } else {
                         if (int rc = gemm_bf16x3(hx, b.fc1_weight3n, b.fc1_bias, nullptr, nullptr, wide3, Mc, hid, d, AVD_ACT_GELU, terms, st, 1.f, 1.f,
-                                                 ss, w->norm_eps)) return rc;
+                                                 ss, w->norm_eps, nullptr, nullptr, 0, nullptr, Mcp)) return rc;
                         if (ns) {       // the same K slices as every other block: the window's rows keep their summation order
                             if (int rc = gemm_bf16x3_splitk(wide3, b.fc2_weight3, b.fc2_bias, yc, yc, nullptr, nullptr, Mc, d, hid, terms, ns, part,
                                                             st)) return rc;
                         } else {
-                            if (int rc = gemm_bf16x3(wide3, b.fc2_weight3, b.fc2_bias, yc, yc, nullptr, Mc, d, hid, AVD_ACT_NONE, terms, st)) return rc;
+                            if (int rc = gemm_bf16x3(wide3, b.fc2_weight3, b.fc2_bias, yc, yc, nullptr, Mc, d, hid, AVD_ACT_NONE, terms, st, 1.f, 1.f,
+                                                     nullptr, 0.f, nullptr, nullptr, 0, nullptr, Mcp)) return rc;
                         }
                     }
                     // final norm from the compact rows into the caller's [B, N, d] layout (rows outside the window stay as they were);
                     // the two-segment layout has no such rows to keep: its caller takes the compact rows
-                    return rmsnorm_f32(yc, rd, w->final_norm_scale, y, null_from ? rd : RowMap{d, nq, (int64_t)N * d}, Mc, d, w->norm_eps, st);
+                    return rmsnorm_f32(yc, rd, w->final_norm_scale, y, segs ? rd : RowMap{d, nq, (int64_t)N * d}, Mc, d, w->norm_eps, st);
                 }
                 if (int rc = in_proj(b)) return rc;
+                if (int rc = mark(l, 1)) return rc;
                 if (w->attn_mode == 1) {
                     if (int rc = attn_fp8(qkv, f8w, f8_b, nullptr, hs, B, N, H, nq, st, terms, 1.f, 1.f)) return rc;
-                } else if (null_from) {
+                } else if (segs) {
                     // the short samples run their n_out_rows + 1 queries against their N keys and write behind row seg.m0
                     if (int rc = attn_bf16x3(qkv, nullptr, hs, B, N, H, N, terms, st, 1.f, 1.f, 0, &seg)) return rc;
                 } else {
                     if (int rc = attn_bf16x3(qkv, nullptr, hs, B, N, H, nq, terms, st, 1.f, 1.f)) return rc;
                 }
+                if (int rc = mark(l, 2)) return rc;
                 if (int rc = gemm_bf16x3(hs, b.out_proj_weight3, b.out_proj_bias, cur, y, hx, Mr, d, d, AVD_ACT_NONE, terms, st, 1.f, 1.f, nullptr,
-                                         0.f, ss, nullptr, 0, nullptr, M)) return rc;
+                                         0.f, ss, nullptr, 0, nullptr, Mp)) return rc;
+                if (int rc = mark(l, 3)) return rc;
                 cur = y;
                 if (fused) {
                     if (int rc = mlp_bf16x3(hx, b.fc1_weight3n, b.fc1_bias, b.fc2_weight3, b.fc2_bias, ss, w->norm_eps, y, y, last ? nullptr : hx,
@@ -394,7 +423,7 @@ static int core_forward(const avd_core_weights* w, const float* x, float* y, int
                     continue;
                 }
                 if (int rc = gemm_bf16x3(hx, b.fc1_weight3n, b.fc1_bias, nullptr, nullptr, wide3, Mr, hid, d, AVD_ACT_GELU, terms, st, 1.f, 1.f, ss,
-                                         w->norm_eps, nullptr, nullptr, 0, nullptr, M)) return rc;
+                                         w->norm_eps, nullptr, nullptr, 0, nullptr, Mp)) return rc;
                 if (ns) {       // too few blocks for the chip: K slices + a deterministic reduction that writes what the epilogue would
                     if (int rc = gemm_bf16x3_splitk(wide3, b.fc2_weight3, b.fc2_bias, y, y, last ? nullptr : hx, last ? nullptr : ss, Mr, d, hid,
                                                     terms, ns, part, st)) return rc;
@@ -402,7 +431,7 @@ static int core_forward(const avd_core_weights* w, const float* x, float* y, int
                     if (int rc = gemm_bf16x3(wide3, b.fc2_weight3, b.fc2_bias, y, y, nullptr, Mr, d, hid, AVD_ACT_NONE, terms, st)) return rc;
                 } else {
                     if (int rc = gemm_bf16x3(wide3, b.fc2_weight3, b.fc2_bias, y, y, hx, Mr, d, hid, AVD_ACT_NONE, terms, st, 1.f, 1.f, nullptr, 0.f,
-                                             ss, nullptr, 0, nullptr, M)) return rc;
+                                             ss, nullptr, 0, nullptr, Mp)) return rc;
                 }
             }
             return rmsnorm_f32(y, rd, w->final_norm_scale, y, rd, Mr, d, w->norm_eps, st);
@@ -533,8 +562,9 @@ static int64_t head_ws_bytes(const avd_head_weights* w, int64_t rows) {
     return split_path > fp32_path ? split_path : fp32_path;
 }
 
+// plan_rows > rows (split-operand mode): the GEMMs choose their kernels as for plan_rows rows — one half of a step's head on its own call
 static int head_forward(const avd_head_weights* w, const float* h, RowMap hm, int64_t rows, float* out, void* ws,
-                        int64_t ws_bytes, hipStream_t st) {
+                        int64_t ws_bytes, hipStream_t st, int64_t plan_rows = 0) {
     AVD_REQUIRE(w && h && out, AVD_EINVAL, "head: null pointer");
     AVD_REQUIRE(w->d_in > 0 && w->hidden > 0 && w->d_out > 0 && w->n_shared >= 0, AVD_EINVAL, "head: bad dims");
     AVD_REQUIRE(w->input_proj_weight && w->out_proj_weight, AVD_EINVAL, "head: null weights");
@@ -561,18 +591,18 @@ static int head_forward(const avd_head_weights* w, const float* h, RowMap hm, in
         float* t2 = cv.take(rows * w->hidden);
         if (int rc = split3_rows_f32(h, hm, imgA, rows, w->d_in, st, asc(0))) return rc;
         if (int rc = gemm_bf16x3(imgA, w->input_proj_weight3, w->input_proj_bias, nullptr, nullptr, imgB, rows, w->hidden, w->d_in, AVD_ACT_NONE,
-                                 terms, st, h2 ? asc(0) * wsc(0) : 1.f, h2 ? asc(1) : 1.f)) return rc;
+                                 terms, st, h2 ? asc(0) * wsc(0) : 1.f, h2 ? asc(1) : 1.f, nullptr, 0.f, nullptr, nullptr, 0, nullptr, plan_rows)) return rc;
         void* cur = imgB;
         void* nxt = imgA;
         for (int j = 0; j < n; ++j) {
             if (int rc = gemm_bf16x3(cur, w->shared_lin_weight3[j], w->shared_lin_bias[j], nullptr, t2, nullptr, rows, w->hidden, w->hidden,
-                                     AVD_ACT_NONE, terms, st, h2 ? asc(1 + j) * wsc(1 + j) : 1.f, 1.f)) return rc;
+                                     AVD_ACT_NONE, terms, st, h2 ? asc(1 + j) * wsc(1 + j) : 1.f, 1.f, nullptr, 0.f, nullptr, nullptr, 0, nullptr, plan_rows)) return rc;
             if (int rc = layernorm_act_split3_f32(t2, w->shared_ln_weight[j], w->shared_ln_bias[j], nxt, rows, w->hidden, w->ln_eps, w->act, st,
                                                   asc(2 + j))) return rc;
             void* t = cur; cur = nxt; nxt = t;
         }
         return gemm_bf16x3(cur, w->out_proj_weight3, w->out_proj_bias, nullptr, out, nullptr, rows, w->d_out, w->hidden, AVD_ACT_NONE, terms, st,
-                           h2 ? asc(1 + n) * wsc(1 + n) : 1.f, 1.f);
+                           h2 ? asc(1 + n) * wsc(1 + n) : 1.f, 1.f, nullptr, 0.f, nullptr, nullptr, 0, nullptr, plan_rows);
     }
     float* t1 = cv.take(rows * w->hidden);
     float* t2 = cv.take(rows * w->hidden);
@@ -682,15 +712,9 @@ static int embed_cfg_pair(const avd_embed_desc* e, const float* z, const float* 
 }
 
 // ---------------------------------------------------------------- one CFG denoising step
-#define AVD_HIP(call)                                                                        \
-    do {                                                                                     \
-        hipError_t e__ = (call);                                                             \
-        if (e__ != hipSuccess) return set_error(AVD_ELAUNCH, "%s: %s", #call, hipGetErrorString(e__)); \
-    } while (0)
-
 // second stream + fork/join events of the split-stream step, one set per (device, caller stream): created on first use (the one
 // place the library allocates, outside any capture), never shared between two caller streams
-struct AuxState { hipStream_t aux = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
+struct AuxState { hipStream_t aux = nullptr; hipEvent_t fork = nullptr, join = nullptr, lead = nullptr; };
 static std::mutex g_aux_mu;
 static std::map<std::pair<int, hipStream_t>, AuxState> g_aux_map;
 static int ensure_aux(hipStream_t st, AuxState& out) {
@@ -702,6 +726,7 @@ static int ensure_aux(hipStream_t st, AuxState& out) {
         AVD_HIP(hipStreamCreateWithFlags(&a.aux, hipStreamNonBlocking));
         AVD_HIP(hipEventCreateWithFlags(&a.fork, hipEventDisableTiming));
         AVD_HIP(hipEventCreateWithFlags(&a.join, hipEventDisableTiming));
+        AVD_HIP(hipEventCreateWithFlags(&a.lead, hipEventDisableTiming));
     }
     out = a;
     return AVD_OK;
@@ -791,6 +816,7 @@ static const TuneKey kTuneKeys[] = {
     {"attn_pipe", "AVD_ATTN_PIPE", &g_attn_pipe, INT_MIN, INT_MAX, false},
     {"attn_m16", "AVD_ATTN_M16", &g_attn_m16, INT_MIN, INT_MAX, false},
     {"core_trim", "AVD_CORE_TRIM", &g_core_trim, INT_MIN, INT_MAX, true},
+    {"cfg_offset", "AVD_CFG_OFFSET", &g_cfg_offset, 0, 3, false},        // 0 no offset, 1 .. 3 launches of block 0
     {"mlp_fused", "AVD_MLP_FUSED", &g_mlp_fused, INT_MIN, INT_MAX, false},
     {"gemm_tile", "AVD_GEMM_TILE", &g_gemm_force_tile, INT_MIN, INT_MAX, false},
     {"gemm_stages", "AVD_GEMM_STAGES", &g_gemm_stages, INT_MIN, INT_MAX, false},
@@ -912,18 +938,21 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
     const bool have_ss = !e.temb_add;      // the fused concat front end leaves the rows' sums of squares behind
 
     // the stacked one-stream step in concat mode with the target rows first runs the null half without its Np - 1 duplicate prompt
-    // rows when the core can (g_cfg_dedup); everything else — and every other mode — is the full [2B, N, d] layout
-    const bool dedup = g_cfg_dedup && !s->split_streams && !e.temb_add && e.target_first && e.Np >= 2 && core_dedup_ok(s->core, 2 * e.B, p.N, e.Nt);
+    // rows when the core can (g_cfg_dedup); split_streams 2 runs that layout as two chains on two streams, and is the one-stream step
+    // where the layout does not apply; everything else — and every other mode — is the full [2B, N, d] layout
+    const bool dedup = g_cfg_dedup && (!s->split_streams || s->split_streams == 2) && !e.temb_add && e.target_first && e.Np >= 2 &&
+                       core_dedup_ok(s->core, 2 * e.B, p.N, e.Nt);
+    const bool two = s->split_streams == 2 ? dedup : s->split_streams != 0;
     const RowSegs seg{(int64_t)e.B * p.N, {p.N, e.Nt + 1}, {e.B, e.B}};      // the one definition of the layout: front end and core take it
     if (int rc = embed_cfg_pair(&e, z, s->adapt_w, s->adapt_b, t_now, Xp, tok, X2, st, ssx, false, dedup ? &seg : nullptr, slots)) return rc;
     const int row0 = e.target_first ? 0 : e.Np;
     // head over the target rows only (per-token independent, so skipping prompt rows is exact)
     const RowMap hm{e.d, e.Nt, (int64_t)p.N * e.d};
-    if (dedup) {
+    if (dedup && !two) {
         // the core leaves the 2B x Nt normalised target rows compact at the start of X2
         if (int rc = core_forward(s->core, X2, X2, 2 * e.B, p.N, 0, e.Nt, nullptr, core_ws, p.core, st, nullptr, &seg)) return rc;
         if (int rc = head_forward(s->head, X2, RowMap{e.d, 0, 0}, p.rows, eps2, head_ws, p.head, st)) return rc;
-    } else if (!s->split_streams) {
+    } else if (!two) {
         if (int rc = core_forward(s->core, X2, X2, 2 * e.B, p.N, row0, e.Nt, nullptr, core_ws, p.core, st, have_ss ? ssx : nullptr)) return rc;
         if (int rc = head_forward(s->head, X2 + (int64_t)row0 * e.d, hm, p.rows, eps2, head_ws, p.head, st)) return rc;
     } else {
@@ -941,7 +970,24 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
             TwoStreams(int64_t rows, int64_t head_rows) { t_s3_two_streams = true; t_step_rows = rows; t_step_head_rows = head_rows; }
             ~TwoStreams() { t_s3_two_streams = false; t_step_rows = 0; t_step_head_rows = 0; }
         } two_streams_scope((int64_t)2 * e.B * p.N, p.rows);
-        for (int half = 0; half < 2; ++half) {
+        if (dedup) {
+            // the short null layout as two chains: the cond half is B samples of N rows, output window 0 .. Nt, in place; the null half
+            // is the all-short batch behind row seg.m0 and leaves its B x Nt normalised target rows compact there.  Both take the
+            // kernels of the stacked 2B x N plan.  "cfg_offset" k > 0: the null chain starts behind the cond chain's k-th launch of
+            // block 0 instead of at the fork, so that equal launches of the two chains do not run side by side (measured slower).
+            const RowSegs null_seg{0, {p.N, e.Nt + 1}, {0, e.B}};
+            float* xn = X2 + seg.m0 * e.d;
+            float* eps_n = eps2 + (p.rows / 2) * p.D;
+            if (int rc = core_forward(s->core, X2, X2, e.B, p.N, 0, e.Nt, nullptr, core_ws, hc, st, nullptr, nullptr, 2 * e.B,
+                                      g_cfg_offset ? ax.lead : nullptr, g_cfg_offset)) return rc;
+            if (int rc = head_forward(s->head, X2, hm, p.rows / 2, eps2, head_ws, hh, st, p.rows)) return rc;
+            if (g_cfg_offset) AVD_HIP(hipStreamWaitEvent(g_aux, ax.lead, 0));
+            if (int rc = core_forward(s->core, xn, xn, e.B, p.N, 0, e.Nt, nullptr, static_cast<char*>(core_ws) + hc, hc, g_aux, nullptr,
+                                      &null_seg, 2 * e.B)) return rc;
+            if (int rc = head_forward(s->head, xn, RowMap{e.d, 0, 0}, p.rows / 2, eps_n, static_cast<char*>(head_ws) + hh, hh,
+                                      g_aux, p.rows)) return rc;
+        }
+        for (int half = 0; half < 2 && !dedup; ++half) {
             hipStream_t hs = half ? g_aux : st;
             float* xh = X2 + half * half_rows;
             if (int rc = core_forward(s->core, xh, xh, e.B, p.N, row0, e.Nt, nullptr, static_cast<char*>(core_ws) + half * hc, hc, hs,

@@ -1876,7 +1876,7 @@ int gemm_bf16x3_qkv3(const void* A3, const void* W3, const float* bias, void* im
     AVD_REQUIRE(A3 && W3 && bias && img, AVD_EINVAL, "gemm_bf16x3_qkv3: null pointer");
     AVD_REQUIRE(scale_ok(ab_scale) && scale_ok(c_scale), AVD_EINVAL, "gemm_bf16x3_qkv3: image scales must be positive and finite");
     const int N = 3 * heads * 64;
-    AVD_REQUIRE(seg.tok[0] > 0 && seg.tok[1] > 0 && seg.samples[0] > 0 && seg.samples[1] >= 0 && heads > 0 &&
+    AVD_REQUIRE(seg.tok[0] > 0 && seg.tok[1] > 0 && seg.samples[0] >= 0 && seg.samples[1] >= 0 && seg.n_samples() > 0 && heads > 0 &&
                     seg.m0 == (int64_t)seg.samples[0] * seg.tok[0], AVD_EINVAL, "gemm_bf16x3_qkv3: bad row layout (%d x %d + %d x %d rows)",
                 seg.samples[0], seg.tok[0], seg.samples[1], seg.tok[1]);
     AVD_REQUIRE(M < (1ll << 31) - 256, AVD_EUNSUPPORTED, "gemm_bf16x3_qkv3: more than 2^31 rows");

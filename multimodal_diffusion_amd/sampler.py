@@ -345,10 +345,26 @@ class DenoiseEngine:
         self.attn = core.attn if attn is None else attn
         # cond / null halves as two kernel chains on two HIP streams (bit-identical results).  Default: on where it was measured to
         # pay — the f16x2 mode, whose kernels alternate matrix-bound loops with memory-bound epilogues, with >= 6144 rows per half
-        # (C3: 166 -> 174 steps/s, 512x512: 137 -> 144); the fp32 and bf16x3 modes are matrix-bound throughout and gain nothing
+        # (C3: 166 -> 174 steps/s, 512x512: 137 -> 144) — and the bf16x3 mode where the null half's short layout applies (audio ->
+        # video in concat mode with two or more prompt tokens), as split_streams="short": the cond half on the caller's stream, the
+        # null half with one prompt row per sample on the second (C3: 122.5 -> 128.9 steps/s, profiles/two_stream_dedup_e2e.txt), from
+        # 24,321 stacked rows 2 B N: the size from which out_proj / fc2 run as one generation of one-block-per-CU launches, whose
+        # launch, fill and epilogue phases the other chain covers, and the regime of the six-run record.  Smaller batches gained in
+        # three-run sweeps too (same file); they keep the one-stream default, which tests/test_gpu_f16x2.py pins at 6,736 rows per half.
+        # "short" where that layout does not apply is the one-stream step.  True keeps the full layout in both chains, which bf16x3
+        # and the fp32 mode lose by.
+        short_applies = (self.matmul == "bf16x3" and self.attn != "fp8" and temb_mode == "concat" and target == "video" and e.Np >= 2)
         if split_streams is None:
-            split_streams = self.matmul == "f16x2" and B * self.N >= 6144
-        self._split_streams = bool(split_streams)
+            if self.matmul == "f16x2":
+                split_streams = B * self.N >= 6144
+            else:
+                split_streams = "short" if short_applies and 2 * B * self.N >= 24321 else False
+        if isinstance(split_streams, str):
+            if split_streams != "short":
+                raise ValueError(f"split_streams must be None, a bool or 'short', got {split_streams!r}")
+            self._split_short = self._split_streams = short_applies
+        else:
+            self._split_short, self._split_streams = False, bool(split_streams)
         # generation of the pointer / scalar tables: bumped whenever something a captured HIP graph holds by value changes
         # (see _CapturedPair); _stale_reason says what changed last
         self._generation = 0
@@ -418,7 +434,7 @@ class DenoiseEngine:
         s.adapt_w, s.adapt_b = self._aw.data_ptr(), self._ab.data_ptr()
         s.alpha_bar, s.T_train = self.alpha_bar.data_ptr(), self.alpha_bar.numel()
         s.guidance, s.eta = self.guidance, self.eta
-        s.split_streams = 1 if self._split_streams else 0
+        s.split_streams = 2 if self._split_short else 1 if self._split_streams else 0
         self.desc = s
         need = L.lib().avd_step_workspace_bytes(C.byref(s))
         if need < 0:
