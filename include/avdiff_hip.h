@@ -650,6 +650,35 @@ int avd_fifo_shift_cursor_hist_f32(const avd_noise_key* key, int64_t t, int64_t 
                                    const float* z_in, float* z_out, float* clip, const float* hist_in, float* hist_out, int B,
                                    int64_t outer, int slots, int slot_len, int64_t inner, avd_stream_t stream);
 
+/* ---- FIFO clip batch (a public contract): K independent clips denoised as K queues in lockstep inside one batch, so that one model
+ * call finishes one slot of every clip.  The slot entries allow it as they are (samples never attend to one another, the slot tables
+ * are per sample, the slot CFG control is per slot); this entry is the queue step of such a batch in one out-of-place launch.
+ * Layout.  The batch [B, outer, L, inner] with B = K*B_q and L = slots*slot_len is K queues: queue k is samples k*B_q .. (k+1)*B_q - 1
+ * and has B_q*slots slots, slot q of it in sample k*B_q + q / slots at positions (q % slots)*slot_len ...
+ *   z_out slot q of queue k = z_in slot q + 1 of queue k for q < B_q*slots - 1, crossing the sample boundaries inside the queue and
+ *     never the boundary between two queues;
+ *   z_out's tail slot of queue k = the canvas-keyed normals of clip slot c at timestep t under seeds[k], bit for bit what
+ *     avd_fifo_shift_f32 draws with avd_noise_key{seeds[k]}.  seeds: K uint64 values in device memory (8-byte aligned); c and t are
+ *     shared by the queues, which run in lockstep;
+ *   the head (slot 0) of queue k is written straight into slot m of clip canvas k, clips [K, outer, n_clip*slot_len, inner]:
+ *     clips[k, o, m*slot_len + j, i] = z_in[k*B_q, o, j, i], a strided write as avd_fifo_shift_cursor_f32's, with m by value.  m outside
+ *     [0, n_clip) writes no head (the queues still shift): m is compared before the address is formed;
+ *   riders: (hist_in, hist_out) and (carry_in, carry_out), each both NULL or both set, are buffers of z's layout that take the same
+ *     map with zeros in every entering tail slot: the map of avd_fifo_shift_hist_f32's history, which avd_fifo_carry_f32 applies at
+ *     ctx == 0, shift == 1.  The first carries DPM-Solver++(2M)'s x0_hist, the second the slot APG momentum; either may ride alone.
+ * Equivalence.  The launch is bit for bit K calls of avd_fifo_shift_f32 (avd_fifo_shift_hist_f32 with a history) on the K slices with
+ * keys {seeds[k]}, K copies of `popped` into the canvases and, with a carry pair, K avd_fifo_carry_f32 calls on its slices.  K == 1
+ * gives the existing entries' bits.
+ * Checked before the launch (AVD_EINVAL): everything avd_fifo_shift_f32 checks (the dims, 0 <= t < 2^32, c >= 0 and (c + 1)*slot_len
+ * <= 2^32, outer*inner < 2^34); K >= 1 and K divides B; non-null seeds and clips; 1 <= n_clip and n_clip*slot_len <= 2^32; each rider
+ * pair both NULL or both set; no two buffers overlap, the canvases and the seeds included.  All index arithmetic is 64-bit.  16-byte
+ * lanes when inner % 4 == 0 and every base is 16-byte aligned, one element per lane otherwise (every audio latent); the same bits
+ * either way.  Limits of the drivers built on it (stream_infer.fifo_denoise_clips): eta == 0 only (the clip-keyed slot noise has one
+ * seed per call), the plain eager queue only, no clip guide, and the clips share n_clip. */
+int avd_fifo_shift_clips_f32(const uint64_t* seeds, int64_t t, int64_t c, const float* z_in, float* z_out, float* clips, int64_t n_clip,
+                             int64_t m, const float* hist_in, float* hist_out, const float* carry_in, float* carry_out, int B, int K,
+                             int64_t outer, int slots, int slot_len, int64_t inner, avd_stream_t stream);
+
 /* ---- latent guide: inpainting / outpainting and SDEdit over a known clean latent (a public contract).
  * Per sample b of a call, with x_k = known[b] and m = the mask, both in the latent's natural layout ([C,T,H,W] video, [Ca,F] audio,
  * row-major; element e as in avd_noise_key), and a(tau) = alpha_bar[clamp(tau, 0, T_train-1)] for tau >= 0, 1 for tau < 0:

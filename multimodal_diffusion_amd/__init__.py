@@ -12,6 +12,7 @@ from .sampler import (DenoiseEngine, FifoQueue, LinearAdapter, add_sinusoidal_ti
                       latents_to_tokens_audio, latents_to_tokens_video, sample_one_direction, frame_mask, canvas_frame_mask,
                       tokens_to_latents_audio)
 from .stream_infer import fifo_denoise                                 # noqa: F401
+from .stream_infer import fifo_denoise_clips                           # noqa: F401
 from .schedules import ModalitySchedule, build_schedules_from_config   # noqa: F401
 from .vae_video3d import VideoVAE, VideoVAEConfig                      # noqa: F401
 from .audio_codec import AudioCodec, AudioCodecConfig                  # noqa: F401

@@ -221,6 +221,7 @@ SIGNATURES = {
     "avd_fifo_prompt_gather_frac_f32": (_I, [_P, _P, _P, _I, _L, _I, _I, _I, _I, _L, _L, _L, _L, _P]),
     "avd_fifo_shift_cursor_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _P, _L, _P, _P, _P, _I, _L, _I, _I, _L, _P]),
     "avd_fifo_shift_cursor_hist_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _P, _L, _P, _P, _P, _P, _P, _I, _L, _I, _I, _L, _P]),
+    "avd_fifo_shift_clips_f32": (_I, [_P, _L, _L, _P, _P, _P, _L, _L, _P, _P, _P, _P, _I, _I, _L, _I, _I, _L, _P]),
     "avd_sched_advance": (_I, [_P, _I, _P, _P, _P, _I, _P]),
     "avd_sched_advance_ms": (_I, [_P, _I, _P, _P, _P, _P, _I, _P]),
     "avd_dpmpp_2m_step_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _L, _P]),

@@ -978,6 +978,131 @@ int fifo_carry_f32(const float* in, float* out, int B, int64_t outer, int S, int
     return AVD_OK;
 }
 
+// ------------------------------------------------------------------ FIFO clip batch (K queues in lockstep in one batch)
+// The contract is written out in include/avdiff_hip.h ("FIFO clip batch").  The batch [K * Bq, outer, L, inner] is K queues of Bq * S
+// slots, queue k in samples k * Bq .. (k + 1) * Bq - 1.  A sibling of fifo_shift_kernel, which keeps its code: the same lane split
+// (lanes [0, n_out) write z_out, lanes [n_out, n_out + K * n_pop) write the K heads), the same source arithmetic inside a queue and
+// the same tail draw, with the seed of the lane's queue read from `seeds` and the head written into slot m of the queue's own clip
+// canvas (CursorShift's strided write, m by value; m is compared with [0, n_clip) before the address is formed).  R rider pairs of
+// z's layout take the move with zeros in every entering tail slot: HistShift's map, which is fifo_carry_kernel's at ctx = 0, shift = 1.
+struct ClipRiders {
+    const float* in[2];
+    float* out[2];
+};
+template <int V, int R>
+__global__ __launch_bounds__(256) void fifo_shift_clips_kernel(const float* __restrict__ z_in, float* __restrict__ z_out,
+                                                               float* __restrict__ clips, const uint64_t* __restrict__ seeds, uint32_t c,
+                                                               uint32_t t, int Bq, int64_t outer, int S, int slot_len, int64_t inner,
+                                                               int64_t n_out, int64_t n_pop, int64_t n_heads, int64_t n_clip, int64_t m,
+                                                               ClipRiders rd) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n_out + n_heads) return;
+    const int64_t iv = inner / V;
+    const int L = S * slot_len;
+    if (idx >= n_out) {      // clips[k, o, m * slot_len + j, i] = z_in[k * Bq, o, j, i]: the head of queue k
+        if (m < 0 || m >= n_clip) return;
+        int64_t r = idx - n_out;
+        const int64_t kq = r / n_pop;
+        r %= n_pop;
+        const int64_t i = (r % iv) * V;
+        r /= iv;
+        const int j = (int)(r % slot_len);
+        const int64_t o = r / slot_len;
+        const float* src = z_in + ((kq * Bq * outer + o) * L + j) * inner + i;
+        float* dst = clips + (((kq * outer + o) * n_clip + m) * slot_len + j) * inner + i;
+        if constexpr (V == 4) *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(src);
+        else *dst = *src;
+        return;
+    }
+    const int64_t i = (idx % iv) * V;
+    int64_t r = idx / iv;
+    const int l = (int)(r % L);
+    r /= L;
+    const int64_t o = r % outer;
+    const int64_t b = r / outer;
+    const int64_t kq = b / Bq;
+    const int j = l % slot_len;
+    const int64_t q1 = (b % Bq) * S + l / slot_len + 1;      // the slot of queue kq this one receives
+    if (q1 < (int64_t)Bq * S) {
+        const int64_t bs = kq * Bq + q1 / S, ls = (q1 % S) * slot_len + j;
+        const int64_t so = ((bs * outer + o) * L + ls) * inner + i;
+        if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = *reinterpret_cast<const f32x4*>(z_in + so);
+        else z_out[idx] = z_in[so];
+#pragma unroll
+        for (int a = 0; a < R; ++a) {
+            if constexpr (V == 4) *reinterpret_cast<f32x4*>(rd.out[a] + idx * 4) = *reinterpret_cast<const f32x4*>(rd.in[a] + so);
+            else rd.out[a][idx] = rd.in[a][so];
+        }
+    } else {                 // the tail slot of queue kq: fresh noise of clip slot c under the queue's own seed
+        const uint64_t seed = seeds[kq];
+        const CanvasKey ck{(uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), c, (uint32_t)slot_len};
+        const f32x4 v = canvas_normal4(ck, 0, o, j, i, inner, t);
+        if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = v;
+        else z_out[idx] = v[(int)((o * inner + i) & 3)];
+#pragma unroll
+        for (int a = 0; a < R; ++a) {      // an entering slot has no history and no momentum
+            if constexpr (V == 4) *reinterpret_cast<f32x4*>(rd.out[a] + idx * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+            else rd.out[a][idx] = 0.f;
+        }
+    }
+}
+
+// r1_in / r1_out and r2_in / r2_out: the rider pairs, each both null or both set (the history, the slot momentum: either alone or both)
+int fifo_shift_clips_f32(const uint64_t* seeds, int64_t t, int64_t c, const float* z_in, float* z_out, float* clips, int64_t n_clip,
+                         int64_t m, const float* r1_in, float* r1_out, const float* r2_in, float* r2_out, int B, int K, int64_t outer, int S,
+                         int slot_len, int64_t inner, hipStream_t st) {
+    AVD_REQUIRE(seeds && clips, AVD_EINVAL, "fifo_shift_clips: null seeds or clip canvases");
+    AVD_REQUIRE((reinterpret_cast<uintptr_t>(seeds) & 7u) == 0, AVD_EINVAL, "fifo_shift_clips: seeds must be 8-byte aligned");
+    AVD_REQUIRE(!r2_in == !r2_out, AVD_EINVAL, "fifo_shift_clips: carry_in and carry_out go together");
+    // the shift's own checks on everything the two share (a by-value c, the dims, t, the lane limit of one queue's head)
+    const avd_noise_key probe{0, 0};
+    ShiftPlan plan;
+    if (int rc = fifo_shift_plan(&probe, t, c, z_in, z_out, clips, B, outer, S, slot_len, inner, r1_in, r1_out, nullptr, 1, plan)) return rc;
+    AVD_REQUIRE(K >= 1 && B % K == 0, AVD_EINVAL, "fifo_shift_clips: the %d queues must divide the batch %d", K, B);
+    const int64_t lim = (int64_t)1 << 32;
+    AVD_REQUIRE(n_clip >= 1 && n_clip <= lim / slot_len, AVD_EINVAL, "fifo_shift_clips: n_clip %lld * slot_len %d must lie in [1, 2^32]",
+                (long long)n_clip, slot_len);
+    AVD_REQUIRE((double)K * (double)outer * (double)n_clip * (double)slot_len * (double)inner < 9.0e18, AVD_EUNSUPPORTED,
+                "fifo_shift_clips: too large a set of clip canvases");
+    const int64_t total = plan.total, pop = plan.pop;
+    // every buffer apart from every other, the canvases and the seeds among them (byte spans)
+    const struct { const void* p; int64_t bytes; const char* name; } bufs[8] = {
+        {z_in, 4 * total, "z_in"}, {z_out, 4 * total, "z_out"}, {clips, 4 * pop * n_clip * K, "the clip canvases"},
+        {seeds, 8 * (int64_t)K, "seeds"}, {r1_in, 4 * total, "hist_in"}, {r1_out, 4 * total, "hist_out"},
+        {r2_in, 4 * total, "carry_in"}, {r2_out, 4 * total, "carry_out"}};
+    for (int a = 0; a < 8; ++a)
+        for (int b = a + 1; b < 8; ++b) {
+            if (!bufs[a].p || !bufs[b].p) continue;
+            const char *pa = static_cast<const char*>(bufs[a].p), *pb = static_cast<const char*>(bufs[b].p);
+            AVD_REQUIRE(!(pa < pb + bufs[b].bytes && pb < pa + bufs[a].bytes), AVD_EINVAL, "fifo_shift_clips: %s must not overlap %s",
+                        bufs[a].name, bufs[b].name);
+        }
+    ClipRiders rd{{nullptr, nullptr}, {nullptr, nullptr}};
+    int R = 0;
+    if (r1_in) { rd.in[R] = r1_in; rd.out[R++] = r1_out; }
+    if (r2_in) { rd.in[R] = r2_in; rd.out[R++] = r2_out; }
+    const bool vec = plan.vec && aligned16(r2_in) && aligned16(r2_out);      // plan.vec: inner % 4 == 0, z_in, z_out, clips and rider one
+    const int v = vec ? 4 : 1;
+    const int64_t n_out = total / v, n_pop = pop / v, n_heads = n_pop * K;
+    AVD_REQUIRE((n_out + n_heads + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "fifo_shift_clips: %lld lanes are too many for one launch",
+                (long long)(n_out + n_heads));
+    static const int tags[6] = {prof_tag_id("fifo_shift_clips_kernel<1, 0>"), prof_tag_id("fifo_shift_clips_kernel<4, 0>"),
+                                prof_tag_id("fifo_shift_clips_kernel<1, 1>"), prof_tag_id("fifo_shift_clips_kernel<4, 1>"),
+                                prof_tag_id("fifo_shift_clips_kernel<1, 2>"), prof_tag_id("fifo_shift_clips_kernel<4, 2>")};
+    // read + write of the queues and of every rider, the K heads' writes
+    ProfScope prof(tags[2 * R + (vec ? 1 : 0)], 4.0 * (2.0 * (1 + R) * (double)total + (double)K * (double)pop), st);
+    const dim3 grid((unsigned)((n_out + n_heads + 255) / 256));
+#define AVD_CLIPS(V_, R_)                                                                                                              \
+    hipLaunchKernelGGL((fifo_shift_clips_kernel<V_, R_>), grid, dim3(256), 0, st, z_in, z_out, clips, seeds, (uint32_t)c, (uint32_t)t, \
+                       B / K, outer, S, slot_len, inner, n_out, n_pop, n_heads, n_clip, m, rd)
+    if (R == 2) { if (vec) AVD_CLIPS(4, 2); else AVD_CLIPS(1, 2); }
+    else if (R == 1) { if (vec) AVD_CLIPS(4, 1); else AVD_CLIPS(1, 1); }
+    else { if (vec) AVD_CLIPS(4, 0); else AVD_CLIPS(1, 0); }
+#undef AVD_CLIPS
+    AVD_CHECK_LAUNCH("fifo_shift_clips");
+    return AVD_OK;
+}
+
 // ------------------------------------------------------------------ device cursors of the FIFO queue
 // The contracts are written out in include/avdiff_hip.h ("FIFO device cursors").  A cursor is one int32 on the device; no kernel below
 // addresses by it without a clamp or a guard, and it moves only in cursor_add_kernel, a launch of its own behind its last reader.
@@ -3781,6 +3906,13 @@ extern "C" int avd_fifo_lookahead_hist_f32(const avd_noise_key* key, int64_t t, 
 extern "C" int avd_fifo_carry_f32(const float* in, float* out, int B, int64_t outer, int slots, int ctx, int shift, int slot_len,
                                   int64_t inner, avd_stream_t stream) {
     return fifo_carry_f32(in, out, B, outer, slots, ctx, shift, slot_len, inner, static_cast<hipStream_t>(stream));
+}
+extern "C" int avd_fifo_shift_clips_f32(const uint64_t* seeds, int64_t t, int64_t c, const float* z_in, float* z_out, float* clips,
+                                        int64_t n_clip, int64_t m, const float* hist_in, float* hist_out, const float* carry_in,
+                                        float* carry_out, int B, int K, int64_t outer, int slots, int slot_len, int64_t inner,
+                                        avd_stream_t stream) {
+    return fifo_shift_clips_f32(seeds, t, c, z_in, z_out, clips, n_clip, m, hist_in, hist_out, carry_in, carry_out, B, K, outer, slots,
+                                slot_len, inner, static_cast<hipStream_t>(stream));
 }
 extern "C" int avd_cursor_add(int32_t* cursor, int delta, avd_stream_t stream) {
     AVD_REQUIRE(cursor, AVD_EINVAL, "cursor_add: null cursor");

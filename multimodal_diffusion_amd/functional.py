@@ -1168,6 +1168,109 @@ def fifo_shift_cursor(z: Tensor, c0: int, cursor: Tensor, clip: Tensor, seed: in
     return out, hist_out
 
 
+def clip_seeds(seeds, queues: int, device=None) -> Tensor:
+    """The K seeds of a FIFO clip batch as the int64 tensor ``fifo_shift_clips`` passes to its launch (the kernel reads the same 64
+    bits unsigned): ``seeds`` is a sequence of ``queues`` ints, each checked as ``noise_key`` checks a seed.  ``device`` None keeps it
+    on the CPU."""
+    if isinstance(seeds, Tensor) or isinstance(seeds, (str, bytes)) or not hasattr(seeds, "__len__"):
+        raise ValueError(f"seeds must be a sequence of {queues} ints, got {seeds!r}")
+    if len(seeds) != queues:
+        raise ValueError(f"{len(seeds)} seeds for {queues} queues: fifo_shift_clips needs one seed per queue")
+    for s in seeds:
+        noise_key(s, 0)
+    t = torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64)
+    return t if device is None else t.to(device)
+
+
+def fifo_shift_clips(z: Tensor, queues: int, c: int, seeds, t: int, slot_len: int, clips: Tensor, m: int, hist: Optional[Tensor] = None,
+                     hist_out: Optional[Tensor] = None, carry: Optional[Tensor] = None, carry_out: Optional[Tensor] = None, *,
+                     tails: Optional[Tensor] = None):
+    """The queue step of a FIFO clip batch (avd_fifo_shift_clips_f32; contract in include/avdiff_hip.h, "FIFO clip batch"): ``z``
+    ([B,C,T,H,W] video, [B,Ca,F] audio, sliding length L = S * slot_len) is ``queues`` = K independent queues in lockstep, queue k the
+    samples k * B/K .. (k + 1) * B/K - 1.  Every queue shifts as ``fifo_shift`` shifts its batch, never into its neighbour: the tail
+    slot of queue k holds the seeded normals of clip slot ``c`` at timestep ``t`` under ``seeds[k]``, and its head is written into slot
+    ``m`` of ``clips[k]`` (``clips``: [K, C, n_clip * slot_len, H, W] / [K, Ca, n_clip * slot_len], written in place; ``m`` outside
+    [0, n_clip) writes no head).  ``seeds``: K ints, or the int64 device tensor ``clip_seeds`` makes of them (a loop uploads it once).
+    ``hist`` / ``carry`` (z's shape) are riders that take the same map with zeros in every entering slot — the DPM-Solver++(2M)
+    history and the slot APG momentum; ``hist_out`` / ``carry_out``: buffers to write them to, None allocates.  Returns z_out, or the
+    tuple (z_out, hist_out and / or carry_out) with riders.
+    A device tensor takes the one launch.  A CPU tensor takes the torch statement below, which is the reference: per queue a roll by one
+    slot and the tail; ``tails`` ([K, C, slot_len, H, W] / [K, Ca, slot_len]) hands the entering slots in, None draws them with
+    ``canvas_noise`` (which needs a device: a CPU-only caller passes ``tails``).  ``tails`` is refused with a device tensor."""
+    if not (isinstance(z, Tensor) and z.dtype == torch.float32 and z.dim() in (3, 5)):
+        raise ValueError("z must be a float32 tensor of the queue's layout, [B,C,T,H,W] or [B,Ca,F]")
+    outer, L_, inner = window_dims(z.shape)
+    B = z.shape[0]
+    if isinstance(queues, bool) or not isinstance(queues, int) or queues < 1 or B % queues:
+        raise ValueError(f"queues {queues!r} must be an int >= 1 that divides the batch {B}")
+    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or L_ % slot_len:
+        raise ValueError(f"slot_len must be an int >= 1 that divides the sliding length {L_}, got {slot_len!r}")
+    for name, v in (("c", c), ("t", t)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"{name} must be an int >= 0, got {v!r}")
+    if (c + 1) * slot_len > 2 ** 32:
+        raise ValueError(f"(c {c} + 1) * slot_len {slot_len} exceeds the stream's 2**32 canvas positions")
+    if isinstance(m, bool) or not isinstance(m, int):
+        raise ValueError(f"m must be an int (the clip slot the heads go to), got {m!r}")
+    if isinstance(seeds, Tensor):
+        if not (seeds.dtype == torch.int64 and seeds.is_contiguous() and tuple(seeds.shape) == (queues,) and seeds.device == z.device):
+            raise ValueError(f"a seeds tensor must be clip_seeds' int64 [{queues}] on z's device, got {seeds.dtype} "
+                             f"{tuple(seeds.shape)} on {seeds.device}")
+    else:
+        seeds = clip_seeds(seeds, queues, z.device)
+    slice_shape = (z.shape[1],) + tuple(z.shape[3:])
+    if not (isinstance(clips, Tensor) and clips.dtype == torch.float32 and clips.is_contiguous() and clips.device == z.device and
+            clips.dim() == z.dim() and clips.shape[0] == queues and (clips.shape[1],) + tuple(clips.shape[3:]) == slice_shape and
+            clips.shape[2] >= slot_len and clips.shape[2] % slot_len == 0):
+        raise ValueError(f"clips must be a contiguous float32 [{queues}, {z.shape[1]}, n_clip * {slot_len}, ...] of z's slice shape on "
+                         f"z's device, got {tuple(clips.shape) if isinstance(clips, Tensor) else clips!r}")
+    n_clip = clips.shape[2] // slot_len
+    riders = []
+    for name, a, b in (("hist", hist, hist_out), ("carry", carry, carry_out)):
+        if a is None and b is not None:
+            raise ValueError(f"{name}_out goes with {name}")
+        for nm, x in ((name, a), (f"{name}_out", b)):
+            if x is not None and not (isinstance(x, Tensor) and x.dtype == torch.float32 and x.is_contiguous() and x.shape == z.shape and
+                                      x.device == z.device):
+                raise ValueError(f"{nm} must be a contiguous float32 tensor of z's shape {tuple(z.shape)} on z's device")
+        if a is not None:
+            riders.append([a, torch.empty_like(a) if b is None else b])
+    if z.is_cuda:
+        if tails is not None:
+            raise ValueError("tails belongs to the CPU statement: the launch draws the entering slots itself")
+        z = z.contiguous()
+        out = torch.empty_like(z)
+        h, k = ((hist, riders[0][1]) if hist is not None else (None, None)), ((carry, riders[-1][1]) if carry is not None else (None, None))
+        L.check(L.lib().avd_fifo_shift_clips_f32(seeds.data_ptr(), t, c, z.data_ptr(), out.data_ptr(), clips.data_ptr(), n_clip, m,
+                                                 L.ptr(h[0]), L.ptr(h[1]), L.ptr(k[0]), L.ptr(k[1]), B, queues, outer,
+                                                 L_ // slot_len, slot_len, inner, _st(z)))
+        return out if not riders else (out,) + tuple(r[1] for r in riders)
+    Bq = B // queues
+    if tails is None:
+        vals = [s + 2 ** 64 if s < 0 else s for s in seeds.tolist()]
+        tails = torch.stack([canvas_noise(s, torch.tensor([t]), (1,) + slice_shape[:1] + (slot_len,) + slice_shape[1:], slot_len,
+                                          window_offset=c)[0].cpu() for s in vals])
+    elif not (isinstance(tails, Tensor) and tuple(tails.shape) == (queues, z.shape[1], slot_len) + tuple(z.shape[3:])):
+        raise ValueError(f"tails must be the entering slots, shape {(queues, z.shape[1], slot_len) + tuple(z.shape[3:])}")
+
+    def roll(x: Tensor, tail: Tensor) -> Tensor:
+        """one queue [Bq, C, L, ...] rolled by one slot towards its head, ``tail`` [C, slot_len, ...] in its last slot"""
+        q = x.movedim(2, 1).reshape((Bq * (L_ // slot_len), slot_len) + slice_shape)      # [queue slot, j, C, ...]
+        q = torch.roll(q, -1, 0)
+        q[-1] = tail.movedim(1, 0)
+        return q.reshape((Bq, L_) + slice_shape).movedim(1, 2)
+
+    out = torch.empty_like(z)
+    for k in range(queues):
+        sl = slice(k * Bq, (k + 1) * Bq)
+        if 0 <= m < n_clip:
+            clips[k, :, m * slot_len:(m + 1) * slot_len] = z[k * Bq, :, :slot_len]
+        out[sl] = roll(z[sl], tails[k].to(torch.float32))
+        for a, b in riders:
+            b[sl] = roll(a[sl], torch.zeros_like(tails[k], dtype=torch.float32))
+    return out if not riders else (out,) + tuple(r[1] for r in riders)
+
+
 # ---- "bf16x3": fp32-accurate Linear on the bf16 matrix pipe (csrc/gemm_bf16x3.hip) ----
 def split3(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """fp32 [rows, K] -> its split3 image (uint8; three bf16 planes, tiled).  K must be a multiple of 16.

@@ -241,6 +241,9 @@ class DenoiseEngine:
 
     ``fifo_lookahead(z, ctx, shift, ...)`` (extension: overlapping queue windows with held context, include/avdiff_hip.h, "FIFO
     lookahead"): the queue step of ``fifo_denoise(lookahead=ctx)``; it moves ``x0_hist`` as ``fifo_shift`` does.
+
+    ``fifo_shift_clips(z, queues, c, t, seeds, clips, m)`` (extension: K queues in lockstep in one batch, include/avdiff_hip.h, "FIFO
+    clip batch"): the queue step of ``stream_infer.fifo_denoise_clips``; one launch moves every queue, ``x0_hist`` and the slot momentum.
     """
 
     SOLVERS = ("ddim", "dpmpp_2m")
@@ -1156,6 +1159,30 @@ class DenoiseEngine:
         self._generation += 1
         self._stale_reason = "fifo_shift moved the solver history into the engine's other history buffer (x0_hist changed its address)"
         return z_out, popped
+
+    def fifo_shift_clips(self, z: torch.Tensor, queues: int, c: int, t: int, seeds, clips: torch.Tensor, m: int) -> torch.Tensor:
+        """The multi-queue form of ``fifo_shift`` (``functional.fifo_shift_clips`` with the engine's ``slot_len``; include/avdiff_hip.h,
+        "FIFO clip batch"): the batch is ``queues`` independent queues in lockstep, queue k under ``seeds[k]``; every queue shifts, its
+        head goes into slot ``m`` of ``clips[k]`` and noise of clip slot ``c`` at ``t`` enters its tail.  Returns z_out.  Solver
+        "dpmpp_2m": the same launch moves ``x0_hist`` into the engine's second buffer and the two swap, which starts a new graph
+        generation, exactly as ``fifo_shift`` does.  Under ``set_slot_cfg(apg_momentum=)`` the same launch carries the slot momentum into
+        the other momentum buffer too: no ``functional.fifo_carry`` launch.  A clip guide refuses the call."""
+        self._clip_refusal("fifo_shift_clips", "a clip guide is one canvas walked by one queue, and a clip batch holds several")
+        multistep, mom = self.solver == "dpmpp_2m", self._smom_beta != 0.0
+        if multistep and self._hist_other is None:
+            self._hist_other = torch.empty_like(self.x0_hist)
+        out = Fn.fifo_shift_clips(z, queues, c, seeds, t, self.slot_len, clips, m,
+                                  hist=self.x0_hist if multistep else None, hist_out=self._hist_other if multistep else None,
+                                  carry=self._smom if mom else None, carry_out=self._smom_other if mom else None)
+        if mom:
+            self._smom, self._smom_other = self._smom_other, self._smom
+            self._scfg.momentum_buf = self._smom.data_ptr()
+        if multistep:
+            self.x0_hist, self._hist_other = self._hist_other, self.x0_hist
+            self._generation += 1
+            self._stale_reason = ("fifo_shift_clips moved the solver history into the engine's other history buffer (x0_hist changed its "
+                                  "address)")
+        return out[0] if isinstance(out, tuple) else out
 
     def fifo_lookahead(self, z: torch.Tensor, ctx: int, shift: int, c: Optional[int] = None, t: Optional[int] = None,
                        seed: Optional[int] = None):

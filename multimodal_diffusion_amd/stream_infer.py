@@ -24,6 +24,8 @@ timestep, a queue of latent slots runs from nearly clean to pure noise, one mode
 (``DenoiseEngine.step_slots``), the head leaves finished and noise enters at the tail (``functional.fifo_shift``).  With
 ``lookahead=`` the samples are overlapping windows of the queue whose leading slots are held context (``functional.fifo_lookahead``), and
 ``context=`` continues an existing clip.  ``stream_generate(sampler="fifo")`` runs it from a config, a VAE, a codec and a prompt clip.
+``fifo_denoise_clips`` runs K independent clips as K queues in lockstep in one engine (``functional.fifo_shift_clips``), which fills
+the batch a short schedule leaves small; ``stream_generate(sampler="fifo")`` takes a list of prompt clips for it.
 """
 from __future__ import annotations
 
@@ -461,6 +463,92 @@ def _fifo_denoise_eager(engine: DenoiseEngine, pc: torch.Tensor, prompt_hop: int
     return canvas
 
 
+@torch.no_grad()
+def fifo_denoise_clips(engine: DenoiseEngine, prompt_canvases, prompt_hop: int, sched, n_slots: int, noise_seeds, prompt_den: int = 1,
+                       prompt_interp: Optional[str] = None, guidance_by_level=None, rescale_by_level=None, apg: Optional[dict] = None,
+                       apg_momentum: Optional[float] = None) -> torch.Tensor:
+    """``fifo_denoise`` for K independent clips at once (include/avdiff_hip.h, "FIFO clip batch"): the engine's batch B = K * B_q is K
+    queues in lockstep, queue k the samples k * B_q .. (k + 1) * B_q - 1 under prompt ``prompt_canvases[k]`` and seed
+    ``noise_seeds[k]``, and every model call finishes one slot of every clip.  The queue's own batch is pinned to the schedule (B_q * S
+    = n steps), so this is how a short schedule fills the machine.  Returns the K finished canvases [K, C, n_slots * slot_len, H, W]
+    (video target) or [K, Ca, n_slots * slot_len] (audio target).
+    ``prompt_canvases``: a sequence of K prompt canvases of one shape, or one stacked tensor [K, ...].  ``noise_seeds``: K ints; equal
+    seeds are allowed and give correlated starts (the same start and entering noise under different prompts).  ``prompt_hop``,
+    ``sched``, ``n_slots``, ``prompt_den`` / ``prompt_interp`` and the slot CFG control (``guidance_by_level``, ``rescale_by_level``,
+    ``apg``, ``apg_momentum``: one control for all clips, the momentum buffer starting from zero) are ``fifo_denoise``'s.  The engine's
+    batch must be K * B_q with B_q * S = n, else ValueError.
+    It is the plain eager loop: queue k starts from ``canvas_noise(noise_seeds[k], ...)``, the ramp and steady tables are
+    ``fifo_plan``'s (``fifo_plan_last``'s on solver "dpmpp_2m") tiled K times, and a steady iteration is one ``set_prompt`` of the K
+    clips' prompt batches concatenated, one ``step_slots`` and one ``engine.fifo_shift_clips``, which moves every queue, its history
+    and its slot momentum and writes the K heads into the result in one launch.  Nothing else on the host depends on K, and the loop
+    never synchronises.  Clip k's samples see only their own prompt, tables and seed, so its canvas does not depend on the other clips
+    of the batch; equal bits across different batch sizes are not promised (the GEMMs may pick a kernel by row count).
+    Limits, refused before anything is allocated: an engine with eta > 0 (the clip-keyed slot noise has one seed and one clip-position
+    walk per call, so the K clips would draw the same step normals; per-clip step-noise keys are a later change), an engine with a
+    clip guide (one canvas, one queue), K = 0, canvases of differing shapes, a seed count other than K.  The replayed queue, the
+    lookahead queue, a context and an init canvas are ``fifo_denoise``'s alone; the clips run in lockstep and so share ``n_slots``."""
+    if not isinstance(engine, DenoiseEngine):
+        raise TypeError("fifo_denoise_clips drives a DenoiseEngine")
+    scfg = None
+    if guidance_by_level is not None or rescale_by_level is not None or apg is not None or apg_momentum is not None:
+        scfg = engine._check_slot_cfg(guidance_by_level, rescale_by_level, apg, apg_momentum)
+    if isinstance(n_slots, bool) or not isinstance(n_slots, int) or n_slots < 1:
+        raise ValueError(f"n_slots must be an int >= 1, got {n_slots!r}")
+    if isinstance(prompt_hop, bool) or not isinstance(prompt_hop, int) or prompt_hop < 1:
+        raise ValueError(f"prompt_hop must be an int >= 1 (prompt positions per target slot), got {prompt_hop!r}")
+    Fn.check_prompt_frac(prompt_hop, prompt_den, prompt_interp)
+    frac = (prompt_den, prompt_interp) if prompt_den > 1 else None
+    pcs = list(prompt_canvases.unbind(0)) if isinstance(prompt_canvases, torch.Tensor) else list(prompt_canvases)
+    K = len(pcs)
+    if K == 0:
+        raise ValueError("fifo_denoise_clips needs at least one clip: K = 0 prompt canvases were passed")
+    if any(not isinstance(p, torch.Tensor) or p.shape != pcs[0].shape for p in pcs):
+        raise ValueError(f"the {K} prompt canvases must be tensors of one shape (the clips run in lockstep), got "
+                         f"{[tuple(p.shape) if isinstance(p, torch.Tensor) else p for p in pcs]}")
+    seeds = Fn.clip_seeds(noise_seeds, K)
+    if engine.eta > 0:
+        raise ValueError(f"fifo_denoise_clips needs eta == 0 (the engine has eta = {engine.eta}): the clip-keyed slot noise has one seed "
+                         "and one clip-position walk per call, so the K clips would draw the same step normals")
+    engine._clip_refusal("fifo_denoise_clips", "a clip guide is one canvas walked by one queue, and a clip batch holds several")
+    B, S, sl = engine.embed.B, engine.slots, engine.slot_len
+    n = su.fifo_plan(sched, 1)[0].shape[0] + 1      # the schedule's own refusals, and its steps
+    if B % K or (B // K) * S != n:
+        raise ValueError(f"K = {K} clips in an engine of batch B = {B} with S = {S} slots per sample against a schedule of n = {n} "
+                         "steps: fifo_denoise_clips needs B = K * B_q and B_q * S = n")
+    Bq = B // K
+    outer, L_, _ = Fn.window_dims(engine.latent_shape)
+    if L_ != S * sl:
+        raise ValueError(f"the engine's sliding length {L_} is not {S} slots of {sl} positions (an uncovered audio tail cannot queue)")
+    if (n + n_slots) * sl > 2 ** 32:
+        raise ValueError(f"(n {n} + n_slots {n_slots}) * slot_len {sl} exceeds the stream's 2**32 canvas positions")
+    dev = engine.device
+    multistep = engine.solver == "dpmpp_2m"
+    engine._slot_refusals(multistep, None)
+    Lp = fifo_prompt_len(engine, pcs[0])
+    pcs = [L.dev_f32(p.to(dev), "prompt canvas") for p in pcs]
+    s0 = int(torch.as_tensor(sched).reshape(-1)[0])
+    tile = (lambda t: t.repeat((1,) * (t.dim() - 2) + (K, 1)).to(dev))      # one queue's [.., B_q, S] rows, K times along the batch
+    tabs = [tile(t) for t in su.fifo_plan(sched, S)]
+    ramp_last, steady_last = (tile(t) for t in su.fifo_plan_last(sched, S)) if multistep else (None, None)
+    seeds_dev = seeds.to(dev)
+    t0 = torch.full((Bq,), s0, dtype=torch.long, device=dev)
+    z = torch.cat([Fn.canvas_noise(s, t0, (Bq,) + tuple(engine.latent_shape[1:]), L_) for s in noise_seeds], 0)
+    other = torch.empty_like(z)
+    sources = [_fifo_prompt_source(p, Bq, S, prompt_hop, Lp, S, 0, frac) for p in pcs]
+    windows = (lambda m: torch.cat([w(m) for w in sources], 0))
+    canvases = torch.empty((K, outer, n_slots * sl) + tuple(engine.latent_shape[3:]), device=dev, dtype=torch.float32)
+    with _slot_cfg_scope(engine, scfg):
+        engine.set_prompt(windows(0))
+        for r in range(n - 1):
+            z, other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other, t_last=ramp_last[r] if multistep else None), z
+        for m in range(n_slots):
+            if m:
+                engine.set_prompt(windows(m))
+            other = engine.step_slots(z, tabs[2], tabs[3], out=other, t_last=steady_last)
+            z = engine.fifo_shift_clips(other, K, n + m, s0, seeds_dev, canvases, m)
+    return canvases
+
+
 def _fifo_prompt_source(pc: torch.Tensor, B: int, S: int, prompt_hop: int, Lp: int, stride: int, ctx: int, frac):
     """m -> the prompt batch of the eager drivers' steady iteration m, sample k under clip slot m - ctx + k * stride: slices of the canvas
     (``fifo_prompt_windows``) on a whole hop, one ``functional.fifo_prompt_gather_frac`` launch with ``frac`` = (prompt_den,
@@ -672,9 +760,25 @@ class FifoGeometry(NamedTuple):
     P_p: int            # the prompt canvas' positions
     prompt_den: int = 1 # the denominator of the prompt hop (> 1 only under ``fifo_geometry(prompt_interp=)``)
 
+    @property
+    def clips(self) -> int:
+        """K, the clips queued in lockstep in one engine: 1 here, K on the ``FifoClipsGeometry`` of ``fifo_geometry(clips=K)``"""
+        return 1
+
+
+class FifoClipsGeometry(FifoGeometry):
+    """``fifo_geometry(clips=K)``'s result for K > 1: one clip's ``FifoGeometry`` with ``B`` the whole engine's batch, K times one
+    queue's, and ``clips`` = K (an attribute beside the tuple's fields, which keep their order and number)."""
+    clips = 1
+
+    def __new__(cls, geo: FifoGeometry, clips: int):
+        self = super().__new__(cls, *geo._replace(B=clips * geo.B))
+        self.clips = clips
+        return self
+
 
 def fifo_geometry(cfg: Dict, prompt_modality: str, n_windows: int, steps: int, lookahead: int = 0,
-                  prompt_interp: Optional[str] = None) -> FifoGeometry:
+                  prompt_interp: Optional[str] = None, clips: int = 1) -> FifoGeometry:
     """The geometry of ``stream_generate(sampler="fifo")`` from the config alone (no device): how ``n_windows`` windows of
     ``streaming.window_seconds`` / ``hop_seconds`` become a target canvas of P latent positions, a queue of samples of S slots and a
     prompt canvas the queue's prompt gather walks by whole positions.  ``steps`` is the length of the schedule the queue will run (after
@@ -682,13 +786,15 @@ def fifo_geometry(cfg: Dict, prompt_modality: str, n_windows: int, steps: int, l
     ``prompt_interp`` ("nearest" or "linear"; default None) admits a prompt with a fractional number of positions per target slot
     (include/avdiff_hip.h, "fractional prompt hop"): the hop L_p * slot_len / L_t comes back reduced, ``prompt_hop`` its numerator and
     ``prompt_den`` its denominator — a video prompt at the shipped geometry is 12 * 4 / 150 = 8 / 25.  Without a mode such a prompt
-    is refused."""
+    is refused.
+    ``clips`` = K >= 1 (default 1) is the number of equally long clips queued in lockstep in one engine (``fifo_denoise_clips``): the
+    result carries it and ``B`` is K times one queue's batch; every other number is one clip's."""
     if prompt_modality not in ("video", "audio"):
         raise ValueError("prompt_modality must be 'video' or 'audio'")
     if prompt_interp is not None and prompt_interp not in Fn.PROMPT_INTERPS:
         raise ValueError(f"prompt_interp must be None or one of {Fn.PROMPT_INTERPS}, got {prompt_interp!r}")
     target = "audio" if prompt_modality == "video" else "video"
-    for name, v, lo in (("n_windows", n_windows, 1), ("steps", steps, 1), ("lookahead", lookahead, 0)):
+    for name, v, lo in (("n_windows", n_windows, 1), ("steps", steps, 1), ("lookahead", lookahead, 0), ("clips", clips, 1)):
         if isinstance(v, bool) or not isinstance(v, int) or v < lo:
             raise ValueError(f"{name} must be an int >= {lo}, got {v!r}")
     hop_t, L_t = latent_hop(cfg, target)
@@ -716,8 +822,9 @@ def fifo_geometry(cfg: Dict, prompt_modality: str, n_windows: int, steps: int, l
         raise ValueError(f"{steps} steps do not fill a queue of samples with {h} stepping slots (S = {S}, lookahead {lookahead}): the "
                          f"nearest step counts are {steps // h * h} and {(steps // h + 1) * h}")
     P_ = (n_windows - 1) * hop_t + L_t
-    return FifoGeometry(hop_t, L_t, hop_p, L_p, slot_len, S, prompt_hop, h, steps // h, P_, -(-P_ // slot_len),
-                        (n_windows - 1) * hop_p + L_p, prompt_den)
+    geo = FifoGeometry(hop_t, L_t, hop_p, L_p, slot_len, S, prompt_hop, h, steps // h, P_, -(-P_ // slot_len),
+                       (n_windows - 1) * hop_p + L_p, prompt_den)
+    return geo if clips == 1 else FifoClipsGeometry(geo, clips)
 
 
 def _fifo_options(cfg: Dict, *, shard, consensus, noise_keying, resample, init_noise, fifo) -> dict:
@@ -754,22 +861,8 @@ def _fifo_options(cfg: Dict, *, shard, consensus, noise_keying, resample, init_n
     return opts
 
 
-def _stream_generate_fifo(cfg: Dict, pc, mods: Dict, device, prompt_modality: str, chunks: np.ndarray, zp_shape, lat, init_chunks,
-                          mask, strength: float, opts: dict, *, seed, noise_seed, guide_seed, return_latents: bool,
-                          max_windows_per_batch: int) -> Dict:
-    """``stream_generate(sampler="fifo")`` after the common checks and splits (the contract is in ``stream_generate``): the prompt
-    windows become one prompt canvas, ``fifo_denoise`` generates the target canvas, and its windows are decoded and cross-faded as the
-    windows sampler's are."""
-    vid_vae, aud_codec = mods["vid_vae"], mods["aud_codec"]
-    target, Nw, T_train = pc.target, zp_shape[0], int(pc.alpha_bar.numel())
-    whole = su.make_sampling_schedule(T_train, opts["steps"]) if opts["steps"] is not None else pc.sched
-    sched = su.truncate_schedule(whole, strength) if init_chunks is not None and strength < 1.0 else whole
-    n = int(sched.numel()) - 1
-    # strength 0 runs no step: the geometry is then checked for the whole schedule
-    geo = fifo_geometry(cfg, prompt_modality, Nw, n or int(whole.numel()) - 1, opts["lookahead"], opts["prompt_interp"])
-    if lat[1] != geo.L_t:
-        raise ValueError(f"the target latent has {lat[1]} positions along its sliding axis (data.clip_seconds), a window of "
-                         f"streaming.window_seconds has {geo.L_t}: they must be equal")
+def _fifo_slot_controls(pc, opts: dict, T_train: int) -> dict:
+    """the config's per-sample CFG controls as ``fifo_denoise``'s slot controls (a queue sample holds S noise levels)"""
     ctl = {}
     if pc.interval is not None:
         ctl["guidance_by_level"] = su.guidance_interval_table(pc.guidance, pc.interval, T_train)
@@ -786,6 +879,26 @@ def _stream_generate_fifo(cfg: Dict, pc, mods: Dict, device, prompt_modality: st
             raise ValueError(f"fifo['apg_momentum'] {opts['apg_momentum']:g} needs sampling.apg for the target: the momentum is adaptive "
                              "projected guidance's")
         ctl["apg_momentum"] = opts["apg_momentum"]
+    return ctl
+
+
+def _stream_generate_fifo(cfg: Dict, pc, mods: Dict, device, prompt_modality: str, chunks: np.ndarray, zp_shape, lat, init_chunks,
+                          mask, strength: float, opts: dict, *, seed, noise_seed, guide_seed, return_latents: bool,
+                          max_windows_per_batch: int) -> Dict:
+    """``stream_generate(sampler="fifo")`` after the common checks and splits (the contract is in ``stream_generate``): the prompt
+    windows become one prompt canvas, ``fifo_denoise`` generates the target canvas, and its windows are decoded and cross-faded as the
+    windows sampler's are."""
+    vid_vae, aud_codec = mods["vid_vae"], mods["aud_codec"]
+    target, Nw, T_train = pc.target, zp_shape[0], int(pc.alpha_bar.numel())
+    whole = su.make_sampling_schedule(T_train, opts["steps"]) if opts["steps"] is not None else pc.sched
+    sched = su.truncate_schedule(whole, strength) if init_chunks is not None and strength < 1.0 else whole
+    n = int(sched.numel()) - 1
+    # strength 0 runs no step: the geometry is then checked for the whole schedule
+    geo = fifo_geometry(cfg, prompt_modality, Nw, n or int(whole.numel()) - 1, opts["lookahead"], opts["prompt_interp"])
+    if lat[1] != geo.L_t:
+        raise ValueError(f"the target latent has {lat[1]} positions along its sliding axis (data.clip_seconds), a window of "
+                         f"streaming.window_seconds has {geo.L_t}: they must be equal")
+    ctl = _fifo_slot_controls(pc, opts, T_train)
     mc = None if mask is None else _canvas_mask(mask, lat, Nw, geo.hop_t, geo.L_t)
 
     def one_canvas(windows: torch.Tensor, hop: int) -> torch.Tensor:
@@ -826,6 +939,84 @@ def _stream_generate_fifo(cfg: Dict, pc, mods: Dict, device, prompt_modality: st
     if return_latents:
         res["latents"], res["latent_canvas"] = windows.cpu().numpy(), canvas.cpu().numpy()
     return res
+
+
+def _fifo_clips_refusals(cfg: Dict, opts: dict, K: int, has_init: bool, has_mask: bool) -> None:
+    """What ``stream_generate(sampler="fifo")`` refuses of a LIST of prompt clips, before anything is read or encoded: the limits of
+    ``fifo_denoise_clips`` (``opts``: ``_fifo_options``' result)"""
+    if K < 1:
+        raise ValueError("a list of prompt clips needs at least one clip, got an empty one")
+    if has_init or has_mask:
+        raise ValueError("a list of prompt clips takes no init clip or mask: the clip guide is one canvas walked by one queue, and the "
+                         "clips share an engine (run a guided clip on its own)")
+    eta = float(cfg["sampling"].get("ddim_eta", 0.0))
+    if eta > 0:
+        raise ValueError(f"a list of prompt clips needs sampling.ddim_eta == 0 (got {eta:g}): the queue's step noise has one seed and one "
+                         "clip-position walk per call, so the clips would draw the same step normals")
+    if opts["graph"]:
+        raise ValueError("a list of prompt clips runs the plain eager queue: fifo['graph'] True is refused (the replayed queue's device "
+                         "cursors and clip canvas serve one clip)")
+    if opts["lookahead"]:
+        raise ValueError(f"a list of prompt clips runs the plain eager queue: fifo['lookahead'] {opts['lookahead']} is refused (the "
+                         "lookahead move has no multi-queue form)")
+
+
+def _stream_generate_fifo_clips(cfg: Dict, pc, mods: Dict, device, prompt_modality: str, clips, opts: dict, *, seed, noise_seed,
+                                return_latents: bool, max_windows_per_batch: int) -> list:
+    """``stream_generate(sampler="fifo")`` with a list of K prompt clips (the contract is in ``stream_generate``): every clip is split,
+    encoded and made a prompt canvas as a single clip is, one engine of batch K * B runs ``fifo_denoise_clips``, and every canvas is
+    decoded and cross-faded as a single clip's is.  Returns the K result dicts."""
+    vid_vae, aud_codec = mods["vid_vae"], mods["aud_codec"]
+    K, T_train = len(clips), int(pc.alpha_bar.numel())
+    shapes = [tuple(np.shape(c)) for c in clips]
+    if any(s != shapes[0] for s in shapes):
+        raise ValueError(f"the prompt clips of a list must have equal length (the queues run in lockstep), got shapes {shapes}")
+    if isinstance(seed, (list, tuple)):
+        if len(seed) != K:
+            raise ValueError(f"seed lists {len(seed)} seeds for {K} prompt clips: one per clip, or one int (clip k then takes seed + k)")
+        seeds = [s for s in seed]
+    else:
+        if seed is None:                               # once, from torch's global CPU generator: torch.manual_seed governs it
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError(f"seed must be an int, a list of {K} ints or None, got {seed!r}")
+        seeds = [seed + k for k in range(K)]
+    Fn.clip_seeds(seeds, K)
+    split = [_prompt_windows(cfg, pc, prompt_modality, c if prompt_modality == "video" else None,
+                             c if prompt_modality == "audio" else None) for c in clips]
+    chunks0, zp_shape, lat = split[0]
+    Nw = zp_shape[0]
+    sched = su.make_sampling_schedule(T_train, opts["steps"]) if opts["steps"] is not None else pc.sched
+    geo = fifo_geometry(cfg, prompt_modality, Nw, int(sched.numel()) - 1, 0, opts["prompt_interp"], clips=K)
+    if lat[1] != geo.L_t:
+        raise ValueError(f"the target latent has {lat[1]} positions along its sliding axis (data.clip_seconds), a window of "
+                         f"streaming.window_seconds has {geo.L_t}: they must be equal")
+    ctl = _fifo_slot_controls(pc, opts, T_train)
+    prompt_canvases, n_prompt = [], None
+    for chunks, _, _ in split:
+        z_p = _encode_windows(prompt_modality, vid_vae, aud_codec, chunks, device)
+        n_prompt = P.prompt_tokens(pc, tuple(z_p.shape))
+        if z_p.shape[2] != geo.L_p:
+            raise ValueError(f"encoded prompt windows have {z_p.shape[2]} latent positions, the config implies {geo.L_p}: the prompt "
+                             "canvas cannot be laid out")
+        z_p = z_p.float().contiguous()
+        prompt_canvases.append(canvas_from_windows(Fn.window_consensus(z_p, geo.hop_p), geo.hop_p))
+    eng = P.build_engine(pc._replace(rescale=0.0, interval=None, apg=None), adapt_v=mods["adapt_v"], adapt_a=mods["adapt_a"],
+                         core=mods["core"], head=mods["head"], tstep_dim=mods["tstep_dim"],
+                         latent_shape=(geo.B, lat[0], geo.S * geo.slot_len) + tuple(lat[2:]), n_prompt=n_prompt, noise_seed=noise_seed)
+    canvases = fifo_denoise_clips(eng, prompt_canvases, geo.prompt_hop, sched, geo.n_slots, seeds, prompt_den=geo.prompt_den,
+                                  prompt_interp=opts["prompt_interp"], **ctl)
+    results = []
+    for k in range(K):
+        canvas = canvases[k, :, :geo.P].contiguous()
+        windows = windows_from_canvas(canvas, geo.L_t, geo.hop_t)
+        out = torch.cat([_decode_windows(cfg, pc, vid_vae, aud_codec, lat, windows[lo:lo + max_windows_per_batch], device)
+                         for lo in range(0, Nw, max_windows_per_batch)], 0)
+        res = _stitch(cfg, pc, out)
+        if return_latents:
+            res["latents"], res["latent_canvas"] = windows.cpu().numpy(), canvas.cpu().numpy()
+        results.append(res)
+    return results
 
 
 @torch.no_grad()
@@ -933,6 +1124,15 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     ``fifo_denoise`` refuses it with ``graph`` True or a ``lookahead``.  Refused, before anything is encoded: ``shard=True``,
     ``consensus``, ``noise_keying="canvas"``, ``resample`` and ``init_noise``.
     ``return_latents`` adds "latents", the [N_windows, *latent] windows of the canvas, and "latent_canvas" [C, P, H, W] / [Ca, P].
+    A LIST or tuple of K prompt clips of equal length in ``prompt_video`` / ``prompt_audio`` (``sampler="fifo"`` only) generates K clips
+    at once (``fifo_denoise_clips``; include/avdiff_hip.h, "FIFO clip batch"): every clip is split, encoded and made a prompt canvas as
+    above, one engine of batch K * B (``fifo_geometry(clips=K)``) runs the K queues in lockstep, one model call finishing one slot of
+    every clip, and every canvas is decoded and cross-faded as above.  The result is a list of K dicts of the single clip's kind
+    (``return_latents`` adds each clip's "latents" and "latent_canvas").  ``seed`` is then a list of K ints, one per clip, or one int
+    (or None, drawn as above) from which clip k takes seed + k; equal seeds give correlated starts.  Refused with a list, before
+    anything is encoded: an init clip or mask (the clip guide is one canvas walked by one queue), ``sampling.ddim_eta`` > 0 (the step
+    noise has one seed and one clip-position walk per call), ``fifo["graph"]`` True and a nonzero ``fifo["lookahead"]`` (the clip
+    batch is the plain eager queue).  A single clip that is not in a list runs exactly as before.
     """
     # the latent guide's argument checks that need no device (the window count and the mask's shape follow the prompt split below)
     strength = P.check_init_args(prompt_modality, init_video, init_audio, strength, mask)
@@ -945,6 +1145,14 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
         fifo = _fifo_options(cfg, shard=shard, consensus=consensus, noise_keying=noise_keying, resample=resample, init_noise=init_noise,
                              fifo=fifo)
     has_init = init_video is not None or init_audio is not None
+    clip_list = prompt_video if prompt_modality == "video" else prompt_audio
+    if sampler == "fifo" and isinstance(clip_list, (list, tuple)):      # K clips as K queues in one engine
+        _fifo_clips_refusals(cfg, fifo, len(clip_list), has_init, mask is not None)
+        pc = P.read_config(cfg, prompt_modality, guidance_interval=guidance_interval, resample=resample, has_init=False, has_mask=False,
+                           noise_seed=noise_seed)
+        mods = dict(vid_vae=vid_vae, aud_codec=aud_codec, adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim)
+        return _stream_generate_fifo_clips(cfg, pc, mods, device, prompt_modality, list(clip_list), fifo, seed=seed, noise_seed=noise_seed,
+                                           return_latents=return_latents, max_windows_per_batch=max_windows_per_batch)
     if has_init and shard:
         raise ValueError("an init clip with shard=True is not implemented: the known windows would need a second broadcast to the "
                          "ranks; run the windows in one process")

@@ -27,7 +27,20 @@ The records are profiles/fifo_prompt_frac_kernels.txt and profiles/fifo_prompt_f
             same command on the parent commit gives the figures to compare.
   e2e       fifo_denoise under the slot APG with and without apg_momentum, DDIM at n = 48 and DPM-Solver++(2M) at n = 18 (8 layers),
             --slots-out and twice as many finished slots: the time per finished slot is the difference.
-The records are profiles/slot_momentum_kernels.txt, profiles/slot_momentum_e2e.txt and profiles/slot_momentum_parent.txt."""
+The records are profiles/slot_momentum_kernels.txt, profiles/slot_momentum_e2e.txt and profiles/slot_momentum_parent.txt.
+
+--clips kernels | e2e times the FIFO clip batch (include/avdiff_hip.h, "FIFO clip batch") instead:
+  kernels   at the C3 latent [K * B_q, 8, 12, 32, 32] (S = 6), K = 2, 4, 8 queues of B_q = 3 and K = 2, 4 of B_q = 8, without and with
+            the history rider: the one multi-queue launch (functional.fifo_shift_clips) against what it replaces, K one-queue shifts
+            on slices plus K copies of the popped heads into the canvases; beside them the unchanged one-queue plain and history shift
+            at B = 3, 8 and 32, each timed twice per round.  Device events around --launches back-to-back iterations (launch overhead
+            included: the two sides differ in their number of launches), the variants interleaved over --rounds rounds, all rounds
+            printed.  On a checkout without the clip batch the unchanged shifts alone are timed, so the same command on the parent
+            commit gives the figures to compare.
+  e2e       fifo_denoise_clips (8 layers), DPM-Solver++(2M) at n = 18 with K = 1, 2, 4, 8, 10 clips and DDIM at n = 48 with K = 1, 2, 4:
+            --slots-out and twice as many finished slots per clip, the time per finished slot per clip is the difference over K; one
+            fifo_denoise line per solver beside them (the only line on a checkout without the clip batch).
+The records are profiles/fifo_clips_kernels.txt, profiles/fifo_clips_e2e.txt and profiles/fifo_clips_parent.txt."""
 import argparse
 import statistics
 import sys
@@ -50,7 +63,8 @@ ap.add_argument("--matmul", default="bf16x3", help="matrix-pipe mode (default: b
 ap.add_argument("--prompt-frac", choices=("kernels", "e2e"), default=None, help="time the fractional prompt hop instead (see above)")
 ap.add_argument("--launches", type=int, default=200, help="--prompt-frac / --slot-momentum kernels: launches per timed window")
 ap.add_argument("--slot-momentum", choices=("kernels", "e2e"), default=None, help="time the slot APG momentum instead (see above)")
-ap.add_argument("--slots-out", type=int, default=12, help="--slot-momentum e2e: finished slots per timed fifo_denoise call")
+ap.add_argument("--slots-out", type=int, default=12, help="--slot-momentum / --clips e2e: finished slots per timed fifo_denoise call")
+ap.add_argument("--clips", choices=("kernels", "e2e"), default=None, help="time the FIFO clip batch instead (see above)")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
@@ -69,7 +83,7 @@ cfg = {"tokenizer": {"width": 512, "video": {"tube": {"t": 2, "h": 4, "w": 4}}, 
        "streaming": {"window_seconds": 3.0, "hop_seconds": 1.0, "crossfade_seconds": 0.25}}
 wav = (0.1 * torch.randn(int(args.seconds * 16000), generator=torch.Generator().manual_seed(9))).numpy()
 n_windows = S.split_audio_into_windows(wav, 16000, 3.0, 1.0)[0].shape[0]
-geo = S.fifo_geometry(cfg, "audio", n_windows, args.steps) if args.prompt_frac is None and args.slot_momentum is None else None
+geo = S.fifo_geometry(cfg, "audio", n_windows, args.steps) if args.prompt_frac is None and args.slot_momentum is None and args.clips is None else None
 kw = dict(cfg=cfg, vid_vae=vae, aud_codec=codec, adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=tdim, device=dev,
           prompt_modality="audio", prompt_video=None, prompt_audio=wav, seed=1, max_windows_per_batch=32)
 kinds = [("windows", {}), ("consensus", dict(consensus="uniform")), ("fifo", dict(sampler="fifo"))]
@@ -280,6 +294,159 @@ def slot_momentum_e2e():
     print("  quality is not measured: there are no trained weights")
 
 
+def clips_kernels():
+    from multimodal_diffusion_amd import _lib as L, functional as Fn
+    has_clips = hasattr(Fn, "fifo_shift_clips")
+    S_, sl, n_clip, c, t = 6, 2, 64, 48, 999
+    g = torch.Generator().manual_seed(0)
+    rows, pairs = [], []      # (name, fn, launches per iteration, bytes moved, the kernel's prof tag); (clip batch, its row of parts)
+    slot = 8 * sl * 32 * 32 * 4
+
+    def single(z, hist, hout):
+        if hist is None:
+            return lambda: Fn.fifo_shift(z, c, 7, t, sl)
+        return lambda: Fn.fifo_shift(z, c, 7, t, sl, hist=hist, hist_out=hout)
+
+    def measure(rows):
+        """{name: [us per iteration of every round]} by device events, and {name: kernel us} under the library's launch events"""
+        for _, fn, _, _, _ in rows:
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        us = {r[0]: [] for r in rows}
+        for _ in range(args.rounds):
+            for name, fn, _, _, _ in rows:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(args.launches):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                us[name].append(1e3 * e0.elapsed_time(e1) / args.launches)
+        kern = {}
+        for name, fn, _, _, tag in rows:
+            if tag is None:
+                continue
+            L.prof_enable(True)
+            try:
+                for _ in range(args.launches):
+                    fn()
+                torch.cuda.synchronize()
+            finally:
+                L.prof_enable(False)
+            n, ms, _ = L.prof_report()[tag]
+            assert n == args.launches, (tag, n)
+            kern[name] = 1e3 * ms / n
+        return us, kern
+
+    def report(rows, us, kern):
+        for name, _, launches, moved, _ in rows:
+            v = us[name]
+            med = statistics.median(v)
+            k = f"   kernel alone {kern[name]:6.2f} = {moved / kern[name] / 1e3:7.1f} GB/s" if name in kern else ""
+            print(f"  {name:44s} " + " ".join(f"{x:8.2f}" for x in v) + f"   median {med:8.2f}   {launches:2d} launch(es){k}")
+        for B in (3, 8, 32):                               # the spread of the entries timed twice: what a difference has to exceed
+            for what in ("plain shift", "history shift"):
+                v = us[f"B={B}: {what} (a)"] + us[f"B={B}: {what} (b)"]
+                print(f"  B={B} {what}: run-to-run spread {min(v):.2f} .. {max(v):.2f}")
+
+    for B in (3, 8, 32):                                   # the unchanged one-queue entries, each twice per round
+        z, hist, hout = (torch.randn((B, 8, 12, 32, 32), generator=g).to(dev) for _ in range(3))
+        for tag in ("(a)", "(b)"):
+            rows.append((f"B={B}: plain shift {tag}", single(z, None, None), 1, 2 * z.numel() * 4 + slot, "fifo_shift_kernel<4>"))
+            rows.append((f"B={B}: history shift {tag}", single(z, hist, hout), 1, 4 * z.numel() * 4 + slot, "fifo_shift_kernel<4, HistShift>"))
+    print(f"FIFO queue shifts at the C3 latent [B, 8, 12, 32, 32] (S = {S_} slots of {sl} frames, 16-byte lanes), through functional.* "
+          f"(every call allocates its outputs, as the drivers' calls do): microseconds per iteration, device events around {args.launches} "
+          f"back-to-back iterations (the host's launch work included: at these sizes it is what the loop waits for), {args.rounds} "
+          f"interleaved rounds after a warm-up, then the median; kernel alone = the library's launch events around {args.launches} launches "
+          "in a pass of their own, and the bytes the launch has to move over that time")
+    print(" the unchanged one-queue shifts alone, before anything of the clip batch is allocated (the same pass on any checkout):")
+    report(rows, *measure(rows))
+    if not has_clips:
+        print("  this checkout has no clip batch: nothing else to time")
+        return
+    for Bq, Ks in ((3, (2, 4, 8)), (8, (2, 4))):
+        for K in Ks:
+            z, hist, hout = (torch.randn((K * Bq, 8, 12, 32, 32), generator=g).to(dev) for _ in range(3))
+            clips = torch.zeros(K, 8, n_clip * sl, 32, 32, device=dev)
+            seeds = Fn.clip_seeds(list(range(1, K + 1)), K, dev)
+            for rider in (False, True):
+                moved = (4 if rider else 2) * z.numel() * 4 + K * slot
+
+                def multi(z=z, hist=hist, hout=hout, clips=clips, seeds=seeds, K=K, rider=rider):
+                    Fn.fifo_shift_clips(z, K, c, seeds, t, sl, clips, 5, hist=hist if rider else None, hist_out=hout if rider else None)
+
+                def parts(z=z, hist=hist, hout=hout, clips=clips, K=K, Bq=Bq, rider=rider):
+                    for k in range(K):
+                        q = slice(k * Bq, (k + 1) * Bq)
+                        res = Fn.fifo_shift(z[q], c, k + 1, t, sl, hist=hist[q] if rider else None, hist_out=hout[q] if rider else None)
+                        clips[k, :, 5 * sl:6 * sl] = res[1]
+
+                name = f"K={K} x B_q={Bq}{', history' if rider else ''}"
+                rows += [(f"{name}: one launch", multi, 1, moved, f"fifo_shift_clips_kernel<4, {1 if rider else 0}>"),
+                         (f"{name}: {K} shifts + {K} copies", parts, 2 * K, moved + K * slot, None)]
+                pairs.append((name, rows[-1][0]))
+    print(" every variant interleaved: the clip batch's one launch against the K one-queue shifts + K copies it replaces:")
+    us, kern = measure(rows)
+    report(rows, us, kern)
+    for name, parts_name in pairs:
+        a, b = statistics.median(us[f"{name}: one launch"]), statistics.median(us[parts_name])
+        print(f"  {name:28s} one launch {a:8.2f} against {b:8.2f}: x {b / a:.2f}")
+
+
+def clips_e2e():
+    from multimodal_diffusion_amd import schedule_utils as su
+    from oracle import ref_cpu as R
+    abar = R.alpha_bar_table(R.beta_table(1000))
+    S_, N = 6, args.slots_out
+    has_clips = hasattr(A, "fifo_denoise_clips")
+    g = torch.Generator().manual_seed(1)
+    print(f"fifo_denoise_clips: K clips as K queues in one engine of batch K * B_q, S = {S_} (C3 latent [8, 12, 32, 32] per sample, 384 + 37 "
+          f"tokens, 8 layers, {args.matmul}, eager, eta 0), audio prompt canvases with 25 latent frames per target slot; host clock around "
+          f"calls that end in a device synchronise, {args.rounds} rounds, the calls interleaved, {N} and {2 * N} slots out per clip; "
+          "milliseconds.  Per finished slot = the difference of the two clip lengths over the slots; per clip = that over K")
+    if not has_clips:
+        print("  this checkout has no clip batch: the fifo_denoise lines alone")
+    for solver, n, Ks in (("dpmpp_2m", 18, (1, 2, 4, 8, 10)), ("ddim", 48, (1, 2, 4))):
+        sched = su.make_sampling_schedule(1000, n)
+        Bq = n // S_
+        pcs = [torch.randn(8, 25 * (n + 2 * N) + 148, generator=g).to(dev) for _ in range(max(Ks))]
+
+        def eng(B):
+            return A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=tdim, target="video",
+                                   latent_shape=(B, 8, 12, 32, 32), prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul=args.matmul,
+                                   solver=solver)
+
+        e1 = eng(Bq)
+        runs = [("fifo_denoise", 1, lambda n_out, e1=e1: A.fifo_denoise(e1, pcs[0], 25, sched, n_out, 5))]
+        if has_clips:
+            for K in Ks:
+                eK = e1 if K == 1 else eng(K * Bq)
+                runs.append((f"clips K = {K}", K, lambda n_out, eK=eK, K=K: A.fifo_denoise_clips(eK, pcs[:K], 25, sched, n_out,
+                                                                                               list(range(5, 5 + K)))))
+        for _, _, fn in runs:
+            fn(4)                                          # warm-up
+        ts_ = {(name, n_out): [] for name, _, _ in runs for n_out in (N, 2 * N)}
+        for _ in range(args.rounds):
+            for n_out in (N, 2 * N):
+                for name, _, fn in runs:
+                    ts_[name, n_out].append(timed(lambda: fn(n_out))[0])
+        per1 = None
+        for name, K, _ in runs:
+            whole = {n_out: statistics.median(ts_[name, n_out]) for n_out in (N, 2 * N)}
+            per = (whole[2 * N] - whole[N]) / N
+            if name == "clips K = 1":
+                per1 = per
+            ratio = f"   x {per1 / (per / K):.2f} per clip against K = 1" if per1 is not None and K > 1 else ""
+            print(f"  {solver:8s} n = {n}, B = {K * Bq:2d}, {name:13s}: " +
+                  "; ".join(f"{n_out} out " + " ".join(f"{x * 1e3:7.1f}" for x in ts_[name, n_out]) for n_out in (N, 2 * N)) +
+                  f"; per finished slot {per * 1e3:.3f}, per clip {per / K * 1e3:.3f}; ramp and start {(whole[N] - N * per) * 1e3:.1f}{ratio}")
+    print("  quality is not measured: there are no trained weights")
+
+
+if args.clips is not None:
+    clips_kernels() if args.clips == "kernels" else clips_e2e()
+    sys.exit(0)
 if args.prompt_frac is not None:
     prompt_frac_kernels() if args.prompt_frac == "kernels" else prompt_frac_e2e()
     sys.exit(0)
