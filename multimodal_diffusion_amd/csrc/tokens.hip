@@ -14,6 +14,7 @@
 #include <type_traits>
 #include <cmath>
 #include <initializer_list>
+#include <string>
 
 namespace avd {
 
@@ -591,516 +592,344 @@ int slot_noise_f32(const avd_slot_key* key, const int64_t* t_now, float* out, in
     return AVD_OK;
 }
 
-bool overlaps(const float* a, const float* b, int64_t n);
-
-// ------------------------------------------------------------------ FIFO queue shift (diagonal denoising)
-// The contract is written out in include/avdiff_hip.h ("FIFO queue shift").  The batch [B, outer, L, inner] with L = S * slot_len is a
-// queue of B * S slots, slot q in sample q / S at positions (q % S) * slot_len ..; one out-of-place launch writes z_out slot q = z_in
-// slot q + 1 (across sample boundaries), popped = z_in slot 0, and fills the tail slot with the canvas-keyed normals of canvas
-// positions c * slot_len + j at timestep `t`: canvas_normal4 with window index c and hop slot_len, the bits of canvas_noise_kernel.
-// V lanes as canvas_noise_kernel.  Lanes [0, n_out) write z_out, lanes [n_out, n_out + n_pop) write popped.
-// A HistShift ending the arguments (an empty pack otherwise: the plain shift keeps its argument layout and code) carries a second
-// buffer of z's layout along ("FIFO queue shift with history"): the lane that writes z_out[idx] writes hist_out[idx] from the same
-// source offset of hist_in, and zeros in the tail slot.  Nothing of the history is popped.
-struct HistShift {
-    const float* in;
-    float* out;
+// ------------------------------------------------------------------ FIFO queue moves (diagonal denoising)
+// The contracts are written out in include/avdiff_hip.h ("FIFO queue shift", "... with history", "... off a device cursor", "Guided FIFO
+// queue shift", "FIFO lookahead", "slot APG momentum", "FIFO clip batch").  Every one of them is one move of one slot map.
+// The batch [B, outer, L, inner] with L = S * slot_len holds K queues of Bq = B / K windows, queue k in samples k * Bq ..  Window b of
+// a queue holds logical slots b * h .. b * h + S - 1 of its Q = ctx + Bq * h slots, h = S - ctx: the first ctx slots of a window are
+// held context (duplicates of the window before), the others step.  Logical slot q is read from its owner copy: window 0 slot q for
+// q < ctx, window (q - ctx) / h slot ctx + (q - ctx) % h otherwise.  A move writes window b slot s = Old[b * h + s + shift]; Old[Q]
+// (shift == 1 only) is the entering tail.  The plain shift and the clip batch are ctx = 0, shift = 1; the one-queue entries are K = 1.
+struct QueueGeom {
+    int Bq, S, ctx, shift, slot_len;
+    int64_t outer, inner;
 };
-// A CursorShift in the pack ("FIFO queue shift off a device cursor") takes the clip slot from the device: c = ck.w0 + *m, and `popped`
-// is the clip canvas [outer, n_slots * slot_len, inner], whose slot *m receives the head (a strided write); *m outside [0, n_slots)
-// writes no head.  The cursor is only read here: it moves in a launch of its own (cursor_add_kernel).
-struct CursorShift {
-    const int32_t* m;
-    int64_t n_slots;
+struct QueueSrc {
+    int64_t off;      // the source's element offset in a buffer of z's layout; < 0: the entering tail
+    bool step;        // s >= ctx: a stepping position, where a rider lives
 };
-// A GuideShift ending the pack ("guided FIFO queue shift"; with or without a HistShift before it, never with a CursorShift) puts the
-// entering tail slot on the clip guide's forward path inside this launch: the lane that drew the tail's normals blends them with
-// q_p(t) of clip positions c * slot_len + j.  It is defined with the clip guide below, whose gather and blend it calls.
-struct GuideShift;
-template <int V, class... Hist>
-__global__ __launch_bounds__(256) void fifo_shift_kernel(const float* __restrict__ z_in, float* __restrict__ z_out,
-                                                         float* __restrict__ popped, CanvasKey ck, uint32_t t, int B, int64_t outer, int S,
-                                                         int slot_len, int64_t inner, int64_t n_out, int64_t n_pop, Hist... hs) {
-    constexpr bool HIST = PackHas<HistShift, Hist...>::value, CURSOR = PackHas<CursorShift, Hist...>::value;
-    constexpr bool GUIDE = PackHas<GuideShift, Hist...>::value;
-    static_assert(sizeof...(Hist) == (HIST ? 1 : 0) + (CURSOR ? 1 : 0) + (GUIDE ? 1 : 0) && !(CURSOR && GUIDE),
-                  "the pack: optionally one HistShift, then optionally one CursorShift or one GuideShift");
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n_out + n_pop) return;
-    const int64_t iv = inner / V;
-    const int L = S * slot_len;
-    if (idx >= n_out) {      // popped[o, j, i] = z_in[0, o, j, i]
-        const int64_t k = idx - n_out;
-        const int64_t i = (k % iv) * V;
-        const int64_t r = k / iv;
-        const int j = (int)(r % slot_len);
-        const int64_t o = r / slot_len;
-        const float* src = z_in + (o * L + j) * inner + i;
-        if constexpr (CURSOR) {      // clip[o, m * slot_len + j, i], guarded: a cursor outside the clip writes nothing
-            const CursorShift cs = pack_get<CursorShift>(hs...);
-            const int64_t m = *cs.m;
-            if (m < 0 || m >= cs.n_slots) return;
-            float* dst = popped + ((o * cs.n_slots + m) * slot_len + j) * inner + i;
-            if constexpr (V == 4) *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(src);
-            else *dst = *src;
-        } else if constexpr (V == 4) *reinterpret_cast<f32x4*>(popped + k * 4) = *reinterpret_cast<const f32x4*>(src);
-        else popped[k] = *src;
-        return;
+// the source of element (o, j, i) of slot s of window b of queue kq.  q <= Q <= B * S fits an int (the host checks), so the two
+// divisions are 32-bit.  This is the one place a queue source is computed: the head, logical slot ctx, is (b, s) = (0, ctx - shift).
+__device__ __forceinline__ QueueSrc queue_source(const QueueGeom& g, int kq, int b, int s, int64_t o, int j, int64_t i) {
+    const uint32_t h = (uint32_t)(g.S - g.ctx);
+    const int q = b * (int)h + s + g.shift;
+    const bool step = s >= g.ctx;
+    if (q >= g.ctx + g.Bq * (int)h) return QueueSrc{-1, step};
+    int bs = 0, ss = q;
+    if (q >= g.ctx) {
+        bs = (int)((uint32_t)(q - g.ctx) / h);
+        ss = g.ctx + (int)((uint32_t)(q - g.ctx) % h);
     }
-    const int64_t i = (idx % iv) * V;
-    int64_t r = idx / iv;
-    const int l = (int)(r % L);
-    r /= L;
-    const int64_t o = r % outer;
-    const int b = (int)(r / outer);
-    const int j = l % slot_len;
-    const int64_t q1 = (int64_t)b * S + l / slot_len + 1;      // the queue slot this one receives
-    if (q1 < (int64_t)B * S) {
-        const int64_t bs = q1 / S, ls = (q1 % S) * slot_len + j;
-        const int64_t so = ((bs * outer + o) * L + ls) * inner + i;
-        const float* src = z_in + so;
-        if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = *reinterpret_cast<const f32x4*>(src);
-        else z_out[idx] = *src;
-        if constexpr (HIST) {
-            const HistShift h = pack_get<HistShift>(hs...);
-            if constexpr (V == 4) *reinterpret_cast<f32x4*>(h.out + idx * 4) = *reinterpret_cast<const f32x4*>(h.in + so);
-            else h.out[idx] = h.in[so];
-        }
-    } else {                 // the tail slot: fresh noise of clip slot c
-        if constexpr (CURSOR) ck.w0 += (uint32_t)*pack_get<CursorShift>(hs...).m;      // c = c0 + *m: it keys the draw, it addresses nothing
-        const f32x4 v = canvas_normal4(ck, 0, o, j, i, inner, t);
-        if constexpr (GUIDE) {     // blend(m(p), q_p(t), fresh): the bits of the stand-alone pass on this slot
-            if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = pack_get<GuideShift>(hs...).tail4(o, j, i, inner, t, v);
-            else z_out[idx] = pack_get<GuideShift>(hs...).tail1(o, j, i, inner, t, v[(int)((o * inner + i) & 3)]);
-        } else if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = v;
-        else z_out[idx] = v[(int)((o * inner + i) & 3)];
-        if constexpr (HIST) {      // no history yet: zeros (never read: the tail's t_last is -1)
-            const HistShift h = pack_get<HistShift>(hs...);
-            if constexpr (V == 4) *reinterpret_cast<f32x4*>(h.out + idx * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
-            else h.out[idx] = 0.f;
-        }
-    }
+    const int64_t L = (int64_t)g.S * g.slot_len;
+    return QueueSrc{((((int64_t)kq * g.Bq + bs) * g.outer + o) * L + (int64_t)ss * g.slot_len + j) * g.inner + i, step};
 }
 
-// hist_in / hist_out: both null (the plain shift) or both set (the shift with history: hist_out slot q = hist_in slot q + 1, zeros in the tail)
-// cursor: null = the by-value shift (clip slot c, `popped` one slot).  Set = the shift off a device cursor: c is c0, the kernel takes
-// clip slot c0 + *cursor, and `popped` is the clip canvas [outer, n_clip * slot_len, inner]
-// what the shift's checks leave for its launch; the guided shift (below the clip guide) makes the same checks
-struct ShiftPlan {
-    bool vec;
-    int64_t total, pop, n_out, n_pop;
-    CanvasKey ck;
+// The tracks of a move.  The latent track copies every position and draws the tail: the canvas-keyed normals of canvas positions
+// c * slot_len + j at timestep t (canvas_normal4 with window index c and hop slot_len, the bits of canvas_noise_kernel), under `seed`
+// or the queue's own seeds[k], at clip slot c or c + *cursor (the cursor keys the draw, it addresses nothing).  The head of queue k
+// (window 0, slot ctx) goes to slot m of canvas k of `heads`, [K, outer, n_clip * slot_len, inner]; m by value or *cursor, compared with
+// [0, n_clip) before any address is formed.  The dense one-slot `popped` is n_clip = 1, m = 0, K = 1.  The cursor is only read here.
+struct QueueLatent {
+    const float* in;
+    float *out, *heads;
+    int64_t n_clip, m;
+    const int32_t* cursor;      // device int32 or null
+    const uint64_t* seeds;      // K device seeds or null
+    uint64_t seed;
+    uint32_t c, t;
 };
-int fifo_shift_plan(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped, int B, int64_t outer,
-                    int S, int slot_len, int64_t inner, const float* hist_in, float* hist_out, const int32_t* cursor, int64_t n_clip,
-                    ShiftPlan& plan) {
-    AVD_REQUIRE(key, AVD_EINVAL, "fifo_shift: null noise key");
-    AVD_REQUIRE(z_in && z_out && popped, AVD_EINVAL, "fifo_shift: null pointer");
-    AVD_REQUIRE(!hist_in == !hist_out, AVD_EINVAL, "fifo_shift: hist_in and hist_out go together");
-    AVD_REQUIRE(B > 0 && outer > 0 && S > 0 && slot_len > 0 && inner > 0, AVD_EINVAL,
-                "fifo_shift: bad dims (B %d, outer %lld, S %d, slot_len %d, inner %lld)", B, (long long)outer, S, slot_len, (long long)inner);
-    AVD_REQUIRE((int64_t)S * slot_len <= 0x7fffffff && (int64_t)B * S <= 0x7fffffff, AVD_EINVAL,
-                "fifo_shift: S %d * slot_len %d and B %d * S must fit an int", S, slot_len, B);
-    AVD_REQUIRE(t >= 0 && t < ((int64_t)1 << 32), AVD_EINVAL, "fifo_shift: the noise timestep %lld must lie in [0, 2^32)", (long long)t);
-    const int64_t lim = (int64_t)1 << 32;
-    if (cursor)      // every clip slot the cursor can name inside the clip: c0 .. c0 + n_clip - 1
-        AVD_REQUIRE(c >= 0 && c < lim && n_clip >= 1 && n_clip <= lim && c + n_clip <= lim / slot_len, AVD_EINVAL,
-                    "fifo_shift: (c0 %lld + n_out %lld) * slot_len %d must lie in [1, 2^32]", (long long)c, (long long)n_clip, slot_len);
-    else
-        AVD_REQUIRE(c >= 0 && c < lim && c + 1 <= lim / slot_len, AVD_EINVAL, "fifo_shift: (c %lld + 1) * slot_len %d must lie in [1, 2^32]",
-                    (long long)c, slot_len);
-    AVD_REQUIRE(outer <= (((int64_t)1 << 34) - 1) / inner, AVD_EINVAL, "fifo_shift: outer %lld * inner %lld must be < 2^34", (long long)outer,
-                (long long)inner);
-    AVD_REQUIRE((double)B * (double)outer * (double)S * (double)slot_len * (double)inner < 9.0e18, AVD_EUNSUPPORTED, "fifo_shift: too many values");
-    AVD_REQUIRE((double)outer * (double)n_clip * (double)slot_len * (double)inner < 9.0e18, AVD_EUNSUPPORTED, "fifo_shift: too large a clip canvas");
-    const int64_t total = (int64_t)B * outer * S * slot_len * inner, pop = outer * slot_len * inner;
-    const int64_t dst = pop * n_clip;      // what `popped` spans: one slot, or the clip canvas
-    const char* pname = cursor ? "the clip canvas" : "popped";
-    AVD_REQUIRE(!overlaps(z_in, z_out, total), AVD_EINVAL, "fifo_shift: z_out must not overlap z_in (one out-of-place launch)");
-    AVD_REQUIRE(!(popped < z_in + total && z_in < popped + dst) && !(popped < z_out + total && z_out < popped + dst), AVD_EINVAL,
-                "fifo_shift: %s must not overlap z_in or z_out", pname);
-    if (hist_in) {      // five buffers, pairwise apart: slot q reads slot q + 1 of both inputs, across block and sample boundaries
-        AVD_REQUIRE(!overlaps(hist_in, hist_out, total), AVD_EINVAL, "fifo_shift: hist_out must not overlap hist_in (one out-of-place launch)");
-        AVD_REQUIRE(!overlaps(hist_out, z_in, total) && !overlaps(hist_out, z_out, total) && !overlaps(hist_in, z_out, total) &&
-                    !overlaps(hist_in, z_in, total), AVD_EINVAL, "fifo_shift: hist_in and hist_out must not overlap z_in or z_out");
-        AVD_REQUIRE(!(popped < hist_in + total && hist_in < popped + dst) && !(popped < hist_out + total && hist_out < popped + dst), AVD_EINVAL,
-                    "fifo_shift: %s must not overlap hist_in or hist_out", pname);
+// A rider (the x0 history, the slot momentum) is a buffer of z's layout that travels with its slot: the latent's source offset on a
+// stepping position whose source is not the tail, zeros elsewhere (never read: the tail's t_last is -1).  Nothing of a rider is popped.
+struct QueueRiders {
+    const float* in[2];
+    float* out[2];
+};
+// A GuideShift ending the arguments ("guided FIFO queue shift") puts the entering tail slot on the clip guide's forward path inside
+// this launch: the lane that drew the tail's normals blends them with q_p(t) of clip positions c * slot_len + j.  It is defined with
+// the clip guide below, whose gather and blend it calls; a launch without a guide carries none of its state.
+struct GuideShift;
+
+template <int V> __device__ __forceinline__ f32x4 load_v(const float* p) {
+    if constexpr (V == 4) return *reinterpret_cast<const f32x4*>(p);
+    else return f32x4{*p, 0.f, 0.f, 0.f};
+}
+template <int V> __device__ __forceinline__ void store_v(float* p, f32x4 v) {
+    if constexpr (V == 4) *reinterpret_cast<f32x4*>(p) = v;
+    else *p = v[0];
+}
+
+// lane idx -> (b, o, l, i) of [B, outer, L, inner / V].  At the queues' sizes the move is paced by this arithmetic more than by memory
+// (profiles/fifo_move_kernels.txt, table 2: with 64-bit divisions in every lane the one kernel ran 0.3 - 0.7 us behind the parent's
+// at B = 32), so a launch of fewer than 2^32 lanes (a uniform test) divides in 32 bits
+struct QueueLane {
+    int b, l;
+    int64_t o, i;
+};
+template <class T, int V> __device__ __forceinline__ QueueLane queue_lane(T idx, T iv, T L, T outer) {
+    const T r = idx / iv, row = r / L;
+    return QueueLane{(int)(row / outer), (int)(r % L), (int64_t)(row % outer), (int64_t)(idx % iv) * V};
+}
+
+// V lanes as canvas_noise_kernel, in the order idx -> (b, o, l, i).  Lanes [0, n_out) write the tracks, lanes [n_out, n_out + n_heads)
+// the K heads of n_pop lanes each (n_heads == 0 at shift == 0 and without the latent track).  R riders; LATENT false is the carry:
+// the rider map alone.
+template <int V, int R, bool LATENT, class... Guide>
+__global__ __launch_bounds__(256) void fifo_move_kernel(QueueGeom g, QueueLatent z, QueueRiders rd, int64_t n_out, int64_t n_pop,
+                                                        int64_t n_heads, Guide... guide) {
+    static_assert(sizeof...(Guide) == (PackHas<GuideShift, Guide...>::value ? 1 : 0) && (LATENT || sizeof...(Guide) == 0),
+                  "the pack: optionally one GuideShift, on a latent track");
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n_out + n_heads) return;
+    const int64_t iv = g.inner / V;
+    if (idx >= n_out) {      // heads[kq, o, m * slot_len + j, i] = the head's owner copy
+        if constexpr (LATENT) {
+            const int64_t m = z.cursor ? (int64_t)*z.cursor : z.m;
+            if (m < 0 || m >= z.n_clip) return;      // a head outside the clip is written nowhere
+            int64_t r = idx - n_out;
+            const int kq = (int)(r / n_pop);
+            r %= n_pop;
+            const int64_t i = (r % iv) * V;
+            r /= iv;
+            const int j = (int)(r % g.slot_len);
+            const int64_t o = r / g.slot_len;
+            float* dst = z.heads + (((kq * g.outer + o) * z.n_clip + m) * g.slot_len + j) * g.inner + i;
+            store_v<V>(dst, load_v<V>(z.in + queue_source(g, kq, 0, g.ctx - g.shift, o, j, i).off));
+        }
+        return;
     }
-    const bool vec = inner % 4 == 0 && aligned16(z_in) && aligned16(z_out) && aligned16(popped) && aligned16(hist_in) && aligned16(hist_out);
+    const int L = g.S * g.slot_len;
+    const QueueLane ln = n_out + n_heads <= 0xffffffffll ? queue_lane<uint32_t, V>((uint32_t)idx, (uint32_t)iv, (uint32_t)L, (uint32_t)g.outer)
+                                                         : queue_lane<int64_t, V>(idx, iv, (int64_t)L, g.outer);
+    const int b = ln.b, l = ln.l;
+    const int64_t o = ln.o, i = ln.i;
+    const int kq = b < g.Bq ? 0 : (int)((uint32_t)b / (uint32_t)g.Bq);      // one queue: no lane divides
+    const int s = (int)((uint32_t)l / (uint32_t)g.slot_len), j = l - s * g.slot_len;
+    // a rider alone reads nothing on a context position: its source is not looked up
+    const QueueSrc src = LATENT || s >= g.ctx ? queue_source(g, kq, b - kq * g.Bq, s, o, j, i) : QueueSrc{-1, false};
+    f32x4 v = {0.f, 0.f, 0.f, 0.f}, rv[R > 0 ? R : 1];
+#pragma unroll
+    for (int a = 0; a < R; ++a) rv[a] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (src.off >= 0) {      // every load ahead of the stores
+        if constexpr (LATENT) v = load_v<V>(z.in + src.off);
+        if (src.step) {
+#pragma unroll
+            for (int a = 0; a < R; ++a) rv[a] = load_v<V>(rd.in[a] + src.off);
+        }
+    } else if constexpr (LATENT) {      // the tail slot of queue kq: fresh noise of its clip slot
+        const uint64_t seed = z.seeds ? z.seeds[kq] : z.seed;
+        const CanvasKey ck{(uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), z.c + (z.cursor ? (uint32_t)*z.cursor : 0u),
+                           (uint32_t)g.slot_len};
+        v = canvas_normal4(ck, 0, o, j, i, g.inner, z.t);
+        if constexpr (V == 1) v[0] = v[(int)((o * g.inner + i) & 3)];
+        if constexpr (sizeof...(Guide) > 0) {      // blend(m(p), q_p(t), fresh): the bits of the stand-alone pass on this slot
+            if constexpr (V == 4) v = pack_get<GuideShift>(guide...).tail4(o, j, i, g.inner, z.t, v);
+            else v[0] = pack_get<GuideShift>(guide...).tail1(o, j, i, g.inner, z.t, v[0]);
+        }
+    }
+    if constexpr (LATENT) store_v<V>(z.out + idx * V, v);
+#pragma unroll
+    for (int a = 0; a < R; ++a) store_v<V>(rd.out[a] + idx * V, rv[a]);
+}
+
+// What an entry asks of fifo_move.  Every check is made in fifo_move_check, before any HIP call.
+struct MoveTrack {
+    const float* in;
+    float* out;
+    const char *in_name, *out_name;
+};
+struct QueueMove {
+    const char* what;                 // the entry's prefix in messages
+    const char *family, *opts;        // the profile label: "<family><V<opts>>"
+    double bytes;                     // what the entry tells the profile it moves
+    int B, K, S, ctx, shift, slot_len;
+    int64_t outer, inner;
+    bool latent;                      // false: the carry, riders[0] alone
+    MoveTrack z, riders[2];           // a rider pair both null or both set
+    float* heads;                     // null exactly at shift == 0 (and without the latent track)
+    const char* heads_name;
+    int64_t n_clip, m;
+    const int32_t* cursor;
+    const avd_noise_key* key;         // the seed by value, or
+    const uint64_t* seeds;            // one device seed per queue
+    int64_t t, c;
+};
+
+template <int... N, class F> void with_int(int n, F&& f) { (void)((n == N ? (f(std::integral_constant<int, N>{}), true) : false) || ...); }
+
+// what the checks leave for the launch
+struct MovePlan {
+    QueueGeom g;
+    QueueLatent z;
+    QueueRiders rd;
+    int R, v;
+    int64_t n_out, n_pop, n_heads;
+};
+
+int fifo_move_check(const QueueMove& d, MovePlan& plan) {
+    const char* w = d.what;
+    const bool draws = d.latent && d.shift == 1;
+    const int64_t lim = (int64_t)1 << 32;
+    AVD_REQUIRE(d.shift == 0 || d.shift == 1, AVD_EINVAL, "%s: shift must be 0 or 1 (got %d)", w, d.shift);
+    AVD_REQUIRE(d.latent ? d.z.in && d.z.out : d.riders[0].in && d.riders[0].out, AVD_EINVAL, "%s: null pointer", w);
+    for (const MoveTrack& r : d.riders)
+        AVD_REQUIRE(!r.in == !r.out, AVD_EINVAL, "%s: %s and %s go together", w, r.in_name, r.out_name);
+    AVD_REQUIRE(d.B > 0 && d.outer > 0 && d.S > 0 && d.slot_len > 0 && d.inner > 0, AVD_EINVAL,
+                "%s: bad dims (B %d, outer %lld, S %d, slot_len %d, inner %lld)", w, d.B, (long long)d.outer, d.S, d.slot_len, (long long)d.inner);
+    AVD_REQUIRE(d.ctx >= 0 && d.ctx < d.S, AVD_EINVAL, "%s: ctx %d must lie in [0, slots %d)", w, d.ctx, d.S);
+    AVD_REQUIRE((int64_t)d.S * d.slot_len <= 0x7fffffff && (int64_t)d.B * d.S <= 0x7fffffff, AVD_EINVAL,
+                "%s: S %d * slot_len %d and B %d * S must fit an int", w, d.S, d.slot_len, d.B);
+    AVD_REQUIRE(d.K >= 1 && d.B % d.K == 0, AVD_EINVAL, "%s: the %d queues must divide the batch %d", w, d.K, d.B);
+    if (draws) {
+        AVD_REQUIRE(d.key || d.seeds, AVD_EINVAL, "%s: null noise key or seeds", w);
+        AVD_REQUIRE((reinterpret_cast<uintptr_t>(d.seeds) & 7u) == 0, AVD_EINVAL, "%s: seeds must be 8-byte aligned", w);
+        AVD_REQUIRE(d.heads, AVD_EINVAL, "%s: null %s at shift 1", w, d.heads_name);
+        AVD_REQUIRE(d.t >= 0 && d.t < lim, AVD_EINVAL, "%s: the noise timestep %lld must lie in [0, 2^32)", w, (long long)d.t);
+        // every clip slot the draw can name inside the clip: c alone, or c0 .. c0 + n_clip - 1 off a cursor
+        const int64_t nc = d.cursor ? d.n_clip : 1;
+        AVD_REQUIRE(d.c >= 0 && d.c < lim && nc >= 1 && nc <= lim && d.c + nc <= lim / d.slot_len, AVD_EINVAL,
+                    d.cursor ? "%s: (c0 %lld + n_out %lld) * slot_len %d must lie in [1, 2^32]" : "%s: (c %lld + %lld) * slot_len %d must lie in [1, 2^32]",
+                    w, (long long)d.c, (long long)nc, d.slot_len);
+        AVD_REQUIRE(d.n_clip >= 1 && d.n_clip <= lim / d.slot_len, AVD_EINVAL, "%s: n_clip %lld * slot_len %d must lie in [1, 2^32]", w,
+                    (long long)d.n_clip, d.slot_len);
+        AVD_REQUIRE((double)d.K * (double)d.outer * (double)d.n_clip * (double)d.slot_len * (double)d.inner < 9.0e18, AVD_EUNSUPPORTED,
+                    "%s: too large a clip canvas", w);
+    } else
+        AVD_REQUIRE(!d.heads, AVD_EINVAL, "%s: nothing is popped at shift 0, %s must be null", w, d.heads_name);
+    AVD_REQUIRE(!d.latent || d.outer <= (((int64_t)1 << 34) - 1) / d.inner, AVD_EINVAL, "%s: outer %lld * inner %lld must be < 2^34", w,
+                (long long)d.outer, (long long)d.inner);
+    AVD_REQUIRE((double)d.B * (double)d.outer * (double)d.S * (double)d.slot_len * (double)d.inner < 9.0e18, AVD_EUNSUPPORTED,
+                "%s: too many values", w);
+    const int64_t total = (int64_t)d.B * d.outer * d.S * d.slot_len * d.inner, pop = draws ? d.outer * d.slot_len * d.inner : 0;
+    // every buffer apart from every other, by byte spans (null: absent): slot q reads slot q + 1 of every input, across block and sample
+    // boundaries.  pair > 0: an in / out pair, adjacent in the list
+    struct { const void* p; int64_t bytes; const char* name; int pair; } sp[9];
+    int n_sp = 0, R = 0;
+    if (d.latent) {
+        sp[n_sp++] = {d.z.in, 4 * total, d.z.in_name, 1};
+        sp[n_sp++] = {d.z.out, 4 * total, d.z.out_name, 1};
+    }
+    QueueRiders rd{{nullptr, nullptr}, {nullptr, nullptr}};
+    for (const MoveTrack& r : d.riders)
+        if (r.in) {
+            rd.in[R] = r.in;
+            rd.out[R++] = r.out;
+            sp[n_sp++] = {r.in, 4 * total, r.in_name, 1 + R};
+            sp[n_sp++] = {r.out, 4 * total, r.out_name, 1 + R};
+        }
+    if (draws) {
+        sp[n_sp++] = {d.heads, 4 * pop * d.n_clip * d.K, d.heads_name, 0};
+        sp[n_sp++] = {d.seeds, 8 * (int64_t)d.K, "seeds", 0};
+        sp[n_sp++] = {d.cursor, 4, "the cursor", 0};
+    }
+    auto phrase = [&](int k, const char* joint) {      // a buffer alone by its name, a pair's by both: "x_in <joint> x_out"
+        if (!sp[k].pair) return std::string(sp[k].name);
+        const int first = k > 0 && sp[k - 1].pair == sp[k].pair ? k - 1 : k;
+        return std::string(sp[first].name) + joint + sp[first + 1].name;
+    };
+    for (int b = 1; b < n_sp; ++b)
+        for (int a = 0; a < b; ++a) {
+            const char *pa = static_cast<const char*>(sp[a].p), *pb = static_cast<const char*>(sp[b].p);
+            if (!pa || !pb || !(pa < pb + sp[b].bytes && pb < pa + sp[a].bytes)) continue;
+            if (sp[a].pair && sp[a].pair == sp[b].pair)
+                return avd::set_error(AVD_EINVAL, "%s: %s must not overlap %s (one out-of-place launch)", w, sp[b].name, sp[a].name);
+            return avd::set_error(AVD_EINVAL, "%s: %s must not overlap %s", w, phrase(b, " and ").c_str(), phrase(a, " or ").c_str());
+        }
+    bool vec = d.inner % 4 == 0 && aligned16(d.heads);
+    for (int k = 0; k < n_sp; ++k)
+        if (sp[k].pair) vec = vec && aligned16(sp[k].p);
     const int v = vec ? 4 : 1;
-    const int64_t n_out = total / v, n_pop = pop / v;
-    AVD_REQUIRE((n_out + n_pop + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "fifo_shift: %lld lanes are too many for one launch",
-                (long long)(n_out + n_pop));
-    plan = ShiftPlan{vec, total, pop, n_out, n_pop,
-                     CanvasKey{(uint32_t)(key->seed & 0xffffffffu), (uint32_t)(key->seed >> 32), (uint32_t)c, (uint32_t)slot_len}};
+    const int64_t n_out = total / v, n_pop = pop / v, n_heads = n_pop * d.K;
+    AVD_REQUIRE((n_out + n_heads + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "%s: %lld lanes are too many for one launch", w,
+                (long long)(n_out + n_heads));
+    plan = MovePlan{QueueGeom{d.B / d.K, d.S, d.ctx, d.shift, d.slot_len, d.outer, d.inner},
+                    QueueLatent{d.z.in, d.z.out, d.heads, d.n_clip, d.m, d.cursor, d.seeds, d.key ? d.key->seed : 0, (uint32_t)d.c, (uint32_t)d.t},
+                    rd, R, v, n_out, n_pop, n_heads};
     return AVD_OK;
 }
 
+template <class... Guide> int fifo_move_launch(const QueueMove& d, const MovePlan& p, hipStream_t st, Guide... guide) {
+    // a label names a launch family (the entry and its options), not a symbol: the profiles and the bench tools key on it
+    ProfScope prof(g_prof_on ? prof_tag_id("%s<%d%s>", d.family, p.v, d.opts) : 0, d.bytes, st);
+    const dim3 grid((unsigned)((p.n_out + p.n_heads + 255) / 256));
+    auto launch = [&](auto V, auto Rc, auto Lat) {
+        hipLaunchKernelGGL((fifo_move_kernel<decltype(V)::value, decltype(Rc)::value, decltype(Lat)::value, Guide...>), grid, dim3(256), 0, st,
+                           p.g, p.z, p.rd, p.n_out, p.n_pop, p.n_heads, guide...);
+    };
+    with_int<1, 4>(p.v, [&](auto V) {
+        if constexpr (sizeof...(Guide) > 0) with_int<0, 1>(p.R, [&](auto Rc) { launch(V, Rc, std::true_type{}); });      // the history at most
+        else if (d.latent) with_int<0, 1, 2>(p.R, [&](auto Rc) { launch(V, Rc, std::true_type{}); });
+        else launch(V, std::integral_constant<int, 1>{}, std::false_type{});
+    });
+    AVD_CHECK_LAUNCH(d.what);
+    return AVD_OK;
+}
+
+int fifo_move(const QueueMove& d, hipStream_t st) {
+    MovePlan plan;
+    if (int rc = fifo_move_check(d, plan)) return rc;
+    return fifo_move_launch(d, plan, st);
+}
+
+// the profile's byte counts below: one slot's and the batch's floats, in double (they are formed before the checks)
+static double slot_floats(int64_t outer, int slot_len, int64_t inner) { return (double)outer * slot_len * (double)inner; }
+
+// hist_in / hist_out: both null (the plain shift) or both set (the shift with history).  cursor: null = the by-value shift (clip slot c,
+// `popped` one slot).  Set = the shift off a device cursor: c is c0, the kernel takes clip slot c0 + *cursor, and `popped` is the clip
+// canvas [outer, n_clip * slot_len, inner].  what / guided: fifo_shift_guided_f32's (below the clip guide), which adds the tail's reads
+QueueMove fifo_shift_move(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped, int B,
+                          int64_t outer, int S, int slot_len, int64_t inner, const float* hist_in, float* hist_out,
+                          const int32_t* cursor = nullptr, int64_t n_clip = 1, bool guided = false) {
+    const double slot = slot_floats(outer, slot_len, inner), total = (double)B * S * slot;
+    const char* opts = guided ? (hist_in ? ", HistShift, GuideShift" : ", GuideShift")
+                     : cursor ? (hist_in ? ", HistShift, CursorShift" : ", CursorShift") : (hist_in ? ", HistShift" : "");
+    // read + write of the queue (and of the history), the popped slot's write (and the guide's known / mask reads of the tail slot)
+    return QueueMove{guided ? "fifo_shift_guided" : "fifo_shift", "fifo_shift_kernel", opts,
+                     4.0 * ((hist_in ? 4.0 : 2.0) * total + (guided ? 3.0 : 1.0) * slot), B, 1, S, 0, 1, slot_len, outer, inner, true,
+                     {z_in, z_out, "z_in", "z_out"}, {{hist_in, hist_out, "hist_in", "hist_out"}, {nullptr, nullptr, "", ""}}, popped,
+                     cursor ? "the clip canvas" : "popped", n_clip, 0, cursor, key, nullptr, t, c};
+}
 int fifo_shift_f32(const avd_noise_key* key, int64_t t, int64_t c, const float* z_in, float* z_out, float* popped, int B, int64_t outer,
                    int S, int slot_len, int64_t inner, hipStream_t st, const float* hist_in = nullptr, float* hist_out = nullptr,
                    const int32_t* cursor = nullptr, int64_t n_clip = 1) {
-    ShiftPlan plan;
-    if (int rc = fifo_shift_plan(key, t, c, z_in, z_out, popped, B, outer, S, slot_len, inner, hist_in, hist_out, cursor, n_clip, plan)) return rc;
-    const bool vec = plan.vec;
-    const int64_t total = plan.total, pop = plan.pop, n_out = plan.n_out, n_pop = plan.n_pop;
-    const CanvasKey ck = plan.ck;
-    static const int tags[8] = {prof_tag_id("fifo_shift_kernel<1>"), prof_tag_id("fifo_shift_kernel<4>"),
-                                prof_tag_id("fifo_shift_kernel<1, HistShift>"), prof_tag_id("fifo_shift_kernel<4, HistShift>"),
-                                prof_tag_id("fifo_shift_kernel<1, CursorShift>"), prof_tag_id("fifo_shift_kernel<4, CursorShift>"),
-                                prof_tag_id("fifo_shift_kernel<1, HistShift, CursorShift>"),
-                                prof_tag_id("fifo_shift_kernel<4, HistShift, CursorShift>")};
-    // read + write of the queue (and of the history), the popped slot's write
-    ProfScope prof(tags[(cursor ? 4 : 0) + (hist_in ? 2 : 0) + (vec ? 1 : 0)], 4.0 * ((hist_in ? 4.0 : 2.0) * (double)total + (double)pop), st);
-    const dim3 grid((unsigned)((n_out + n_pop + 255) / 256));
-    const HistShift hs{hist_in, hist_out};
-    const CursorShift cs{cursor, n_clip};
-    if (cursor && hist_in) {
-        if (vec)
-            hipLaunchKernelGGL((fifo_shift_kernel<4, HistShift, CursorShift>), grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B,
-                               outer, S, slot_len, inner, n_out, n_pop, hs, cs);
-        else
-            hipLaunchKernelGGL((fifo_shift_kernel<1, HistShift, CursorShift>), grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B,
-                               outer, S, slot_len, inner, n_out, n_pop, hs, cs);
-    } else if (cursor) {
-        if (vec)
-            hipLaunchKernelGGL((fifo_shift_kernel<4, CursorShift>), grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B, outer, S,
-                               slot_len, inner, n_out, n_pop, cs);
-        else
-            hipLaunchKernelGGL((fifo_shift_kernel<1, CursorShift>), grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B, outer, S,
-                               slot_len, inner, n_out, n_pop, cs);
-    } else if (hist_in) {
-        if (vec)
-            hipLaunchKernelGGL((fifo_shift_kernel<4, HistShift>), grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B, outer, S,
-                               slot_len, inner, n_out, n_pop, hs);
-        else
-            hipLaunchKernelGGL((fifo_shift_kernel<1, HistShift>), grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B, outer, S,
-                               slot_len, inner, n_out, n_pop, hs);
-    } else if (vec)
-        hipLaunchKernelGGL(fifo_shift_kernel<4>, grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B, outer, S, slot_len, inner,
-                           n_out, n_pop);
-    else
-        hipLaunchKernelGGL(fifo_shift_kernel<1>, grid, dim3(256), 0, st, z_in, z_out, popped, ck, (uint32_t)t, B, outer, S, slot_len, inner,
-                           n_out, n_pop);
-    AVD_CHECK_LAUNCH("fifo_shift");
-    return AVD_OK;
-}
-
-// ------------------------------------------------------------------ FIFO lookahead (overlapping queue windows, held context)
-// The contract is written out in include/avdiff_hip.h ("FIFO lookahead").  Window b of the batch [B, outer, L, inner] holds logical
-// slots b * h .. b * h + S - 1 of a queue of Q = ctx + B * h slots, h = S - ctx.  Logical slot q is read from its owner copy: window 0
-// slot q for q < ctx, window (q - ctx) / h slot ctx + (q - ctx) % h otherwise.  One out-of-place launch writes z_out window b slot s =
-// Old[b * h + s + shift]; Old[Q] (shift == 1 only) is the fresh tail, fifo_shift_kernel's draw.  Lanes [0, n_out) write z_out (and
-// hist_out: the same source offset of hist_in on the stepping positions s >= ctx, zeros on the context positions and in the tail), lanes
-// [n_out, n_out + n_pop) write popped = Old[ctx] (n_pop == 0 at shift == 0).  V lanes as canvas_noise_kernel.
-template <int V, bool HIST>
-__global__ __launch_bounds__(256) void fifo_lookahead_kernel(const float* __restrict__ z_in, float* __restrict__ z_out,
-                                                             float* __restrict__ popped, const float* __restrict__ hist_in,
-                                                             float* __restrict__ hist_out, CanvasKey ck, uint32_t t, int B, int64_t outer,
-                                                             int S, int ctx, int shift, int slot_len, int64_t inner, int64_t n_out,
-                                                             int64_t n_pop) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n_out + n_pop) return;
-    const int64_t iv = inner / V;
-    const int L = S * slot_len;
-    const int h = S - ctx;
-    if (idx >= n_out) {      // popped[o, j, i] = the head's owner copy: window 0, slot ctx
-        const int64_t k = idx - n_out;
-        const int64_t i = (k % iv) * V;
-        const int64_t r = k / iv;
-        const int j = (int)(r % slot_len);
-        const int64_t o = r / slot_len;
-        const float* src = z_in + (o * L + (int64_t)ctx * slot_len + j) * inner + i;
-        if constexpr (V == 4) *reinterpret_cast<f32x4*>(popped + k * 4) = *reinterpret_cast<const f32x4*>(src);
-        else popped[k] = *src;
-        return;
-    }
-    const int64_t i = (idx % iv) * V;
-    int64_t r = idx / iv;
-    const int l = (int)(r % L);
-    r /= L;
-    const int64_t o = r % outer;
-    const int b = (int)(r / outer);
-    const int s = l / slot_len, j = l % slot_len;
-    const int64_t q = (int64_t)b * h + s + shift;      // the logical slot this position receives; q <= Q, and q == Q only at shift == 1
-    const bool keep = !HIST || s >= ctx;               // a context position carries no history
-    if (q < ctx + (int64_t)B * h) {
-        int64_t bs = 0, ss = q;                        // the owner copy of q
-        if (q >= ctx) {
-            bs = (q - ctx) / h;
-            ss = ctx + (q - ctx) % h;
-        }
-        const int64_t so = ((bs * outer + o) * L + ss * slot_len + j) * inner + i;
-        if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = *reinterpret_cast<const f32x4*>(z_in + so);
-        else z_out[idx] = z_in[so];
-        if constexpr (HIST) {      // s >= ctx gives q >= ctx: the source is a stepping position, where the history lives
-            if constexpr (V == 4)
-                *reinterpret_cast<f32x4*>(hist_out + idx * 4) = keep ? *reinterpret_cast<const f32x4*>(hist_in + so) : f32x4{0.f, 0.f, 0.f, 0.f};
-            else hist_out[idx] = keep ? hist_in[so] : 0.f;
-        }
-    } else {                 // the tail slot: fresh noise of clip slot c, no history yet
-        const f32x4 v = canvas_normal4(ck, 0, o, j, i, inner, t);
-        if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = v;
-        else z_out[idx] = v[(int)((o * inner + i) & 3)];
-        if constexpr (HIST) {
-            if constexpr (V == 4) *reinterpret_cast<f32x4*>(hist_out + idx * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
-            else hist_out[idx] = 0.f;
-        }
-    }
+    return fifo_move(fifo_shift_move(key, t, c, z_in, z_out, popped, B, outer, S, slot_len, inner, hist_in, hist_out, cursor, n_clip), st);
 }
 
 // hist_in / hist_out: both null or both set.  shift == 0 refreshes the duplicates only: key, t and c are not read, popped must be null
 int fifo_lookahead_f32(const avd_noise_key* key, int64_t t, int64_t c, int shift, const float* z_in, float* z_out, float* popped, int B,
                        int64_t outer, int S, int ctx, int slot_len, int64_t inner, hipStream_t st, const float* hist_in = nullptr,
                        float* hist_out = nullptr) {
-    AVD_REQUIRE(shift == 0 || shift == 1, AVD_EINVAL, "fifo_lookahead: shift must be 0 or 1 (got %d)", shift);
-    AVD_REQUIRE(z_in && z_out, AVD_EINVAL, "fifo_lookahead: null pointer");
-    AVD_REQUIRE(!hist_in == !hist_out, AVD_EINVAL, "fifo_lookahead: hist_in and hist_out go together");
-    AVD_REQUIRE(B > 0 && outer > 0 && S > 0 && slot_len > 0 && inner > 0, AVD_EINVAL,
-                "fifo_lookahead: bad dims (B %d, outer %lld, S %d, slot_len %d, inner %lld)", B, (long long)outer, S, slot_len,
-                (long long)inner);
-    AVD_REQUIRE(ctx >= 0 && ctx < S, AVD_EINVAL, "fifo_lookahead: ctx %d must lie in [0, slots %d)", ctx, S);
-    AVD_REQUIRE((int64_t)S * slot_len <= 0x7fffffff && (int64_t)B * S <= 0x7fffffff, AVD_EINVAL,
-                "fifo_lookahead: S %d * slot_len %d and B %d * S must fit an int", S, slot_len, B);
-    if (shift) {
-        AVD_REQUIRE(key, AVD_EINVAL, "fifo_lookahead: null noise key");
-        AVD_REQUIRE(popped, AVD_EINVAL, "fifo_lookahead: null popped at shift 1");
-        AVD_REQUIRE(t >= 0 && t < ((int64_t)1 << 32), AVD_EINVAL, "fifo_lookahead: the noise timestep %lld must lie in [0, 2^32)",
-                    (long long)t);
-        const int64_t lim = (int64_t)1 << 32;
-        AVD_REQUIRE(c >= 0 && c < lim && c + 1 <= lim / slot_len, AVD_EINVAL,
-                    "fifo_lookahead: (c %lld + 1) * slot_len %d must lie in [1, 2^32]", (long long)c, slot_len);
-    } else
-        AVD_REQUIRE(!popped, AVD_EINVAL, "fifo_lookahead: nothing is popped at shift 0, popped must be null");
-    AVD_REQUIRE(outer <= (((int64_t)1 << 34) - 1) / inner, AVD_EINVAL, "fifo_lookahead: outer %lld * inner %lld must be < 2^34",
-                (long long)outer, (long long)inner);
-    AVD_REQUIRE((double)B * (double)outer * (double)S * (double)slot_len * (double)inner < 9.0e18, AVD_EUNSUPPORTED,
-                "fifo_lookahead: too many values");
-    const int64_t total = (int64_t)B * outer * S * slot_len * inner, pop = shift ? outer * slot_len * inner : 0;
-    AVD_REQUIRE(!overlaps(z_in, z_out, total), AVD_EINVAL, "fifo_lookahead: z_out must not overlap z_in (one out-of-place launch)");
-    if (shift)
-        AVD_REQUIRE(!(popped < z_in + total && z_in < popped + pop) && !(popped < z_out + total && z_out < popped + pop), AVD_EINVAL,
-                    "fifo_lookahead: popped must not overlap z_in or z_out");
-    if (hist_in) {
-        AVD_REQUIRE(!overlaps(hist_in, hist_out, total), AVD_EINVAL, "fifo_lookahead: hist_out must not overlap hist_in (one out-of-place launch)");
-        AVD_REQUIRE(!overlaps(hist_out, z_in, total) && !overlaps(hist_out, z_out, total) && !overlaps(hist_in, z_out, total) &&
-                    !overlaps(hist_in, z_in, total), AVD_EINVAL, "fifo_lookahead: hist_in and hist_out must not overlap z_in or z_out");
-        if (shift)
-            AVD_REQUIRE(!(popped < hist_in + total && hist_in < popped + pop) && !(popped < hist_out + total && hist_out < popped + pop),
-                        AVD_EINVAL, "fifo_lookahead: popped must not overlap hist_in or hist_out");
-    }
-    const bool vec = inner % 4 == 0 && aligned16(z_in) && aligned16(z_out) && aligned16(popped) && aligned16(hist_in) && aligned16(hist_out);
-    const int v = vec ? 4 : 1;
-    const int64_t n_out = total / v, n_pop = pop / v;
-    AVD_REQUIRE((n_out + n_pop + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "fifo_lookahead: %lld lanes are too many for one launch",
-                (long long)(n_out + n_pop));
-    CanvasKey ck{0u, 0u, 0u, (uint32_t)slot_len};
-    if (shift) ck = CanvasKey{(uint32_t)(key->seed & 0xffffffffu), (uint32_t)(key->seed >> 32), (uint32_t)c, (uint32_t)slot_len};
-    static const int tags[4] = {prof_tag_id("fifo_lookahead_kernel<1>"), prof_tag_id("fifo_lookahead_kernel<4>"),
-                                prof_tag_id("fifo_lookahead_kernel<1, hist>"), prof_tag_id("fifo_lookahead_kernel<4, hist>")};
     // every owner read once (the duplicates' reads hit the cache), B * S slots written; twice that with the history; the popped slot
-    const double slot = (double)outer * slot_len * (double)inner, Q = (double)ctx + (double)B * (S - ctx);
-    ProfScope prof(tags[(hist_in ? 2 : 0) + (vec ? 1 : 0)], 4.0 * ((hist_in ? 2.0 : 1.0) * (Q + (double)B * S) * slot + (double)pop), st);
-    const dim3 grid((unsigned)((n_out + n_pop + 255) / 256));
-    if (hist_in) {
-        if (vec)
-            hipLaunchKernelGGL((fifo_lookahead_kernel<4, true>), grid, dim3(256), 0, st, z_in, z_out, popped, hist_in, hist_out, ck,
-                               (uint32_t)t, B, outer, S, ctx, shift, slot_len, inner, n_out, n_pop);
-        else
-            hipLaunchKernelGGL((fifo_lookahead_kernel<1, true>), grid, dim3(256), 0, st, z_in, z_out, popped, hist_in, hist_out, ck,
-                               (uint32_t)t, B, outer, S, ctx, shift, slot_len, inner, n_out, n_pop);
-    } else if (vec)
-        hipLaunchKernelGGL((fifo_lookahead_kernel<4, false>), grid, dim3(256), 0, st, z_in, z_out, popped, hist_in, hist_out, ck,
-                           (uint32_t)t, B, outer, S, ctx, shift, slot_len, inner, n_out, n_pop);
-    else
-        hipLaunchKernelGGL((fifo_lookahead_kernel<1, false>), grid, dim3(256), 0, st, z_in, z_out, popped, hist_in, hist_out, ck,
-                           (uint32_t)t, B, outer, S, ctx, shift, slot_len, inner, n_out, n_pop);
-    AVD_CHECK_LAUNCH("fifo_lookahead");
-    return AVD_OK;
+    const double slot = slot_floats(outer, slot_len, inner), Q = (double)ctx + (double)B * (S - ctx);
+    return fifo_move(QueueMove{"fifo_lookahead", "fifo_lookahead_kernel", hist_in ? ", hist" : "",
+                               4.0 * ((hist_in ? 2.0 : 1.0) * (Q + (double)B * S) * slot + (shift ? slot : 0.0)), B, 1, S, ctx, shift, slot_len,
+                               outer, inner, true, {z_in, z_out, "z_in", "z_out"},
+                               {{hist_in, hist_out, "hist_in", "hist_out"}, {nullptr, nullptr, "", ""}}, popped, "popped", 1, 0, nullptr, key,
+                               nullptr, t, c}, st);
 }
 
-// ------------------------------------------------------------------ FIFO carry (a slot-attached buffer through the queue move)
-// The contract is written out in include/avdiff_hip.h ("slot APG momentum").  fifo_lookahead_kernel's history map alone, on a buffer of
-// z's layout: out window b slot s = the owner copy of logical slot b * h + s + shift of `in` on the stepping positions s >= ctx, zeros
-// on the context positions and in the entering tail slot (q == Q, shift == 1 only).  ctx == 0, shift == 1 is fifo_shift_kernel's
-// HistShift map.  Neither a clip slot nor a cursor enters: one launch serves the eager loops and a captured graph.  V lanes as
-// canvas_noise_kernel.
-template <int V>
-__global__ __launch_bounds__(256) void fifo_carry_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int64_t outer, int S,
-                                                         int ctx, int shift, int slot_len, int64_t inner, int64_t n_out) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n_out) return;
-    const int64_t iv = inner / V;
-    const int L = S * slot_len;
-    const int h = S - ctx;
-    const int64_t i = (idx % iv) * V;
-    int64_t r = idx / iv;
-    const int l = (int)(r % L);
-    r /= L;
-    const int64_t o = r % outer;
-    const int b = (int)(r / outer);
-    const int s = l / slot_len, j = l % slot_len;
-    const int64_t q = (int64_t)b * h + s + shift;      // the logical slot this position receives; q == Q only at shift == 1
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (s >= ctx && q < ctx + (int64_t)B * h) {        // s >= ctx gives q >= ctx: the owner copy is a stepping position
-        const int64_t bs = (q - ctx) / h, ss = ctx + (q - ctx) % h;
-        const float* src = in + ((bs * outer + o) * L + ss * slot_len + j) * inner + i;
-        if constexpr (V == 4) v = *reinterpret_cast<const f32x4*>(src);
-        else v[0] = *src;
-    }
-    if constexpr (V == 4) *reinterpret_cast<f32x4*>(out + idx * 4) = v;
-    else out[idx] = v[0];
-}
-
+// the rider map alone ("slot APG momentum").  Neither a clip slot nor a cursor enters: one launch serves the eager loops and a graph
 int fifo_carry_f32(const float* in, float* out, int B, int64_t outer, int S, int ctx, int shift, int slot_len, int64_t inner,
                    hipStream_t st) {
-    AVD_REQUIRE(in && out, AVD_EINVAL, "fifo_carry: null pointer");
-    AVD_REQUIRE(shift == 0 || shift == 1, AVD_EINVAL, "fifo_carry: shift must be 0 or 1 (got %d)", shift);
-    AVD_REQUIRE(B > 0 && outer > 0 && S > 0 && slot_len > 0 && inner > 0, AVD_EINVAL,
-                "fifo_carry: bad dims (B %d, outer %lld, S %d, slot_len %d, inner %lld)", B, (long long)outer, S, slot_len, (long long)inner);
-    AVD_REQUIRE(ctx >= 0 && ctx < S, AVD_EINVAL, "fifo_carry: ctx %d must lie in [0, slots %d)", ctx, S);
-    AVD_REQUIRE((int64_t)S * slot_len <= 0x7fffffff && (int64_t)B * S <= 0x7fffffff, AVD_EINVAL,
-                "fifo_carry: S %d * slot_len %d and B %d * S must fit an int", S, slot_len, B);
-    AVD_REQUIRE((double)B * (double)outer * (double)S * (double)slot_len * (double)inner < 9.0e18, AVD_EUNSUPPORTED,
-                "fifo_carry: too many values");
-    const int64_t total = (int64_t)B * outer * S * slot_len * inner;
-    AVD_REQUIRE(!overlaps(in, out, total), AVD_EINVAL, "fifo_carry: out must not overlap in (one out-of-place launch)");
-    const bool vec = inner % 4 == 0 && aligned16(in) && aligned16(out);
-    const int64_t n_out = total / (vec ? 4 : 1);
-    AVD_REQUIRE((n_out + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "fifo_carry: %lld lanes are too many for one launch", (long long)n_out);
-    static const int tags[2] = {prof_tag_id("fifo_carry_kernel<1>"), prof_tag_id("fifo_carry_kernel<4>")};
     // every stepping owner but the head read once, B * S slots written
-    const double slot = (double)outer * slot_len * (double)inner;
-    ProfScope prof(tags[vec ? 1 : 0], 4.0 * ((double)B * (S - ctx) - shift + (double)B * S) * slot, st);
-    const dim3 grid((unsigned)((n_out + 255) / 256));
-    if (vec) hipLaunchKernelGGL(fifo_carry_kernel<4>, grid, dim3(256), 0, st, in, out, B, outer, S, ctx, shift, slot_len, inner, n_out);
-    else hipLaunchKernelGGL(fifo_carry_kernel<1>, grid, dim3(256), 0, st, in, out, B, outer, S, ctx, shift, slot_len, inner, n_out);
-    AVD_CHECK_LAUNCH("fifo_carry");
-    return AVD_OK;
+    return fifo_move(QueueMove{"fifo_carry", "fifo_carry_kernel", "",
+                               4.0 * ((double)B * (S - ctx) - shift + (double)B * S) * slot_floats(outer, slot_len, inner), B, 1, S, ctx, shift,
+                               slot_len, outer, inner, false, {nullptr, nullptr, "", ""},
+                               {{in, out, "in", "out"}, {nullptr, nullptr, "", ""}}, nullptr, "popped", 1, 0, nullptr, nullptr, nullptr, 0, 0}, st);
 }
 
-// ------------------------------------------------------------------ FIFO clip batch (K queues in lockstep in one batch)
-// The contract is written out in include/avdiff_hip.h ("FIFO clip batch").  The batch [K * Bq, outer, L, inner] is K queues of Bq * S
-// slots, queue k in samples k * Bq .. (k + 1) * Bq - 1.  A sibling of fifo_shift_kernel, which keeps its code: the same lane split
-// (lanes [0, n_out) write z_out, lanes [n_out, n_out + K * n_pop) write the K heads), the same source arithmetic inside a queue and
-// the same tail draw, with the seed of the lane's queue read from `seeds` and the head written into slot m of the queue's own clip
-// canvas (CursorShift's strided write, m by value; m is compared with [0, n_clip) before the address is formed).  R rider pairs of
-// z's layout take the move with zeros in every entering tail slot: HistShift's map, which is fifo_carry_kernel's at ctx = 0, shift = 1.
-struct ClipRiders {
-    const float* in[2];
-    float* out[2];
-};
-template <int V, int R>
-__global__ __launch_bounds__(256) void fifo_shift_clips_kernel(const float* __restrict__ z_in, float* __restrict__ z_out,
-                                                               float* __restrict__ clips, const uint64_t* __restrict__ seeds, uint32_t c,
-                                                               uint32_t t, int Bq, int64_t outer, int S, int slot_len, int64_t inner,
-                                                               int64_t n_out, int64_t n_pop, int64_t n_heads, int64_t n_clip, int64_t m,
-                                                               ClipRiders rd) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n_out + n_heads) return;
-    const int64_t iv = inner / V;
-    const int L = S * slot_len;
-    if (idx >= n_out) {      // clips[k, o, m * slot_len + j, i] = z_in[k * Bq, o, j, i]: the head of queue k
-        if (m < 0 || m >= n_clip) return;
-        int64_t r = idx - n_out;
-        const int64_t kq = r / n_pop;
-        r %= n_pop;
-        const int64_t i = (r % iv) * V;
-        r /= iv;
-        const int j = (int)(r % slot_len);
-        const int64_t o = r / slot_len;
-        const float* src = z_in + ((kq * Bq * outer + o) * L + j) * inner + i;
-        float* dst = clips + (((kq * outer + o) * n_clip + m) * slot_len + j) * inner + i;
-        if constexpr (V == 4) *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(src);
-        else *dst = *src;
-        return;
-    }
-    const int64_t i = (idx % iv) * V;
-    int64_t r = idx / iv;
-    const int l = (int)(r % L);
-    r /= L;
-    const int64_t o = r % outer;
-    const int64_t b = r / outer;
-    const int64_t kq = b / Bq;
-    const int j = l % slot_len;
-    const int64_t q1 = (b % Bq) * S + l / slot_len + 1;      // the slot of queue kq this one receives
-    if (q1 < (int64_t)Bq * S) {
-        const int64_t bs = kq * Bq + q1 / S, ls = (q1 % S) * slot_len + j;
-        const int64_t so = ((bs * outer + o) * L + ls) * inner + i;
-        if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = *reinterpret_cast<const f32x4*>(z_in + so);
-        else z_out[idx] = z_in[so];
-#pragma unroll
-        for (int a = 0; a < R; ++a) {
-            if constexpr (V == 4) *reinterpret_cast<f32x4*>(rd.out[a] + idx * 4) = *reinterpret_cast<const f32x4*>(rd.in[a] + so);
-            else rd.out[a][idx] = rd.in[a][so];
-        }
-    } else {                 // the tail slot of queue kq: fresh noise of clip slot c under the queue's own seed
-        const uint64_t seed = seeds[kq];
-        const CanvasKey ck{(uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), c, (uint32_t)slot_len};
-        const f32x4 v = canvas_normal4(ck, 0, o, j, i, inner, t);
-        if constexpr (V == 4) *reinterpret_cast<f32x4*>(z_out + idx * 4) = v;
-        else z_out[idx] = v[(int)((o * inner + i) & 3)];
-#pragma unroll
-        for (int a = 0; a < R; ++a) {      // an entering slot has no history and no momentum
-            if constexpr (V == 4) *reinterpret_cast<f32x4*>(rd.out[a] + idx * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
-            else rd.out[a][idx] = 0.f;
-        }
-    }
-}
-
+// K queues in lockstep: the seed of a lane's queue is read from `seeds`, the head goes into slot m of the queue's own clip canvas.
 // r1_in / r1_out and r2_in / r2_out: the rider pairs, each both null or both set (the history, the slot momentum: either alone or both)
 int fifo_shift_clips_f32(const uint64_t* seeds, int64_t t, int64_t c, const float* z_in, float* z_out, float* clips, int64_t n_clip,
                          int64_t m, const float* r1_in, float* r1_out, const float* r2_in, float* r2_out, int B, int K, int64_t outer, int S,
                          int slot_len, int64_t inner, hipStream_t st) {
-    AVD_REQUIRE(seeds && clips, AVD_EINVAL, "fifo_shift_clips: null seeds or clip canvases");
-    AVD_REQUIRE((reinterpret_cast<uintptr_t>(seeds) & 7u) == 0, AVD_EINVAL, "fifo_shift_clips: seeds must be 8-byte aligned");
-    AVD_REQUIRE(!r2_in == !r2_out, AVD_EINVAL, "fifo_shift_clips: carry_in and carry_out go together");
-    // the shift's own checks on everything the two share (a by-value c, the dims, t, the lane limit of one queue's head)
-    const avd_noise_key probe{0, 0};
-    ShiftPlan plan;
-    if (int rc = fifo_shift_plan(&probe, t, c, z_in, z_out, clips, B, outer, S, slot_len, inner, r1_in, r1_out, nullptr, 1, plan)) return rc;
-    AVD_REQUIRE(K >= 1 && B % K == 0, AVD_EINVAL, "fifo_shift_clips: the %d queues must divide the batch %d", K, B);
-    const int64_t lim = (int64_t)1 << 32;
-    AVD_REQUIRE(n_clip >= 1 && n_clip <= lim / slot_len, AVD_EINVAL, "fifo_shift_clips: n_clip %lld * slot_len %d must lie in [1, 2^32]",
-                (long long)n_clip, slot_len);
-    AVD_REQUIRE((double)K * (double)outer * (double)n_clip * (double)slot_len * (double)inner < 9.0e18, AVD_EUNSUPPORTED,
-                "fifo_shift_clips: too large a set of clip canvases");
-    const int64_t total = plan.total, pop = plan.pop;
-    // every buffer apart from every other, the canvases and the seeds among them (byte spans)
-    const struct { const void* p; int64_t bytes; const char* name; } bufs[8] = {
-        {z_in, 4 * total, "z_in"}, {z_out, 4 * total, "z_out"}, {clips, 4 * pop * n_clip * K, "the clip canvases"},
-        {seeds, 8 * (int64_t)K, "seeds"}, {r1_in, 4 * total, "hist_in"}, {r1_out, 4 * total, "hist_out"},
-        {r2_in, 4 * total, "carry_in"}, {r2_out, 4 * total, "carry_out"}};
-    for (int a = 0; a < 8; ++a)
-        for (int b = a + 1; b < 8; ++b) {
-            if (!bufs[a].p || !bufs[b].p) continue;
-            const char *pa = static_cast<const char*>(bufs[a].p), *pb = static_cast<const char*>(bufs[b].p);
-            AVD_REQUIRE(!(pa < pb + bufs[b].bytes && pb < pa + bufs[a].bytes), AVD_EINVAL, "fifo_shift_clips: %s must not overlap %s",
-                        bufs[a].name, bufs[b].name);
-        }
-    ClipRiders rd{{nullptr, nullptr}, {nullptr, nullptr}};
-    int R = 0;
-    if (r1_in) { rd.in[R] = r1_in; rd.out[R++] = r1_out; }
-    if (r2_in) { rd.in[R] = r2_in; rd.out[R++] = r2_out; }
-    const bool vec = plan.vec && aligned16(r2_in) && aligned16(r2_out);      // plan.vec: inner % 4 == 0, z_in, z_out, clips and rider one
-    const int v = vec ? 4 : 1;
-    const int64_t n_out = total / v, n_pop = pop / v, n_heads = n_pop * K;
-    AVD_REQUIRE((n_out + n_heads + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "fifo_shift_clips: %lld lanes are too many for one launch",
-                (long long)(n_out + n_heads));
-    static const int tags[6] = {prof_tag_id("fifo_shift_clips_kernel<1, 0>"), prof_tag_id("fifo_shift_clips_kernel<4, 0>"),
-                                prof_tag_id("fifo_shift_clips_kernel<1, 1>"), prof_tag_id("fifo_shift_clips_kernel<4, 1>"),
-                                prof_tag_id("fifo_shift_clips_kernel<1, 2>"), prof_tag_id("fifo_shift_clips_kernel<4, 2>")};
+    const int R = (r1_in ? 1 : 0) + (r2_in ? 1 : 0);
+    static const char* const opts[3] = {", 0", ", 1", ", 2"};
     // read + write of the queues and of every rider, the K heads' writes
-    ProfScope prof(tags[2 * R + (vec ? 1 : 0)], 4.0 * (2.0 * (1 + R) * (double)total + (double)K * (double)pop), st);
-    const dim3 grid((unsigned)((n_out + n_heads + 255) / 256));
-#define AVD_CLIPS(V_, R_)                                                                                                              \
-    hipLaunchKernelGGL((fifo_shift_clips_kernel<V_, R_>), grid, dim3(256), 0, st, z_in, z_out, clips, seeds, (uint32_t)c, (uint32_t)t, \
-                       B / K, outer, S, slot_len, inner, n_out, n_pop, n_heads, n_clip, m, rd)
-    if (R == 2) { if (vec) AVD_CLIPS(4, 2); else AVD_CLIPS(1, 2); }
-    else if (R == 1) { if (vec) AVD_CLIPS(4, 1); else AVD_CLIPS(1, 1); }
-    else { if (vec) AVD_CLIPS(4, 0); else AVD_CLIPS(1, 0); }
-#undef AVD_CLIPS
-    AVD_CHECK_LAUNCH("fifo_shift_clips");
-    return AVD_OK;
+    const double slot = slot_floats(outer, slot_len, inner);
+    return fifo_move(QueueMove{"fifo_shift_clips", "fifo_shift_clips_kernel", opts[R], 4.0 * (2.0 * (1 + R) * (double)B * S + (double)K) * slot,
+                               B, K, S, 0, 1, slot_len, outer, inner, true, {z_in, z_out, "z_in", "z_out"},
+                               {{r1_in, r1_out, "hist_in", "hist_out"}, {r2_in, r2_out, "carry_in", "carry_out"}}, clips,
+                               "the clip canvases", n_clip, m, nullptr, nullptr, seeds, t, c}, st);
 }
 
 // ------------------------------------------------------------------ device cursors of the FIFO queue
@@ -1547,7 +1376,7 @@ int clip_guide_slots_f32(const avd_clip_guide* g, const int64_t* tau, const floa
 }
 
 // The guided FIFO queue shift (avd_fifo_shift_guided_f32; contract in include/avdiff_hip.h, "clip-keyed latent guide"):
-// fifo_shift_kernel's GuideShift.  cg has first = c, stride unused and no cursor, so with sample 0 and position j clip_guide_pos gives
+// fifo_move_kernel's GuideShift.  cg has first = c, stride unused and no cursor, so with sample 0 and position j clip_guide_pos gives
 // p = c * slot_len + j, what the stand-alone pass computes for the tail slot; the coefficients, the gather and the blend are its own.
 struct GuideShift {
     ClipGuideState cg;
@@ -1564,8 +1393,9 @@ struct GuideShift {
 int fifo_shift_guided_f32(const avd_noise_key* key, int64_t t, int64_t c, const avd_clip_guide* guide, const float* abar, int T_train,
                           int everywhere, const float* z_in, float* z_out, float* popped, const float* hist_in, float* hist_out, int B,
                           int64_t outer, int S, int slot_len, int64_t inner, hipStream_t st) {
-    ShiftPlan plan;
-    if (int rc = fifo_shift_plan(key, t, c, z_in, z_out, popped, B, outer, S, slot_len, inner, hist_in, hist_out, nullptr, 1, plan)) return rc;
+    const QueueMove d = fifo_shift_move(key, t, c, z_in, z_out, popped, B, outer, S, slot_len, inner, hist_in, hist_out, nullptr, 1, true);
+    MovePlan plan;
+    if (int rc = fifo_move_check(d, plan)) return rc;      // the shift's own checks first, then the guide's
     AVD_REQUIRE(guide, AVD_EINVAL, "fifo_shift_guided: null clip guide");
     AVD_REQUIRE(abar && T_train > 0, AVD_EINVAL, "fifo_shift_guided: null alpha_bar or bad T_train");
     avd_clip_guide g = *guide;      // c names the clip slot: first / stride / cursor are not read
@@ -1574,34 +1404,12 @@ int fifo_shift_guided_f32(const avd_noise_key* key, int64_t t, int64_t c, const 
     g.cursor = nullptr;
     GuideShift gs{ClipGuideState{}, abar, T_train};
     if (int rc = make_clip_guide(&g, B, outer, S * slot_len, S, slot_len, inner, {z_out, hist_out}, gs.cg, "fifo_shift_guided")) return rc;
-    const int64_t nc = outer * g.P * inner;
-    AVD_REQUIRE(!(popped < g.known + nc && g.known < popped + plan.pop) && !(g.mask && popped < g.mask + nc && g.mask < popped + plan.pop),
-                AVD_EINVAL, "fifo_shift_guided: known / mask must not overlap popped");
+    const int64_t nc = outer * g.P * inner, pop = outer * slot_len * inner;
+    AVD_REQUIRE(!(popped < g.known + nc && g.known < popped + pop) && !(g.mask && popped < g.mask + nc && g.mask < popped + pop), AVD_EINVAL,
+                "fifo_shift_guided: known / mask must not overlap popped");
     if (everywhere) gs.cg.mask = nullptr;      // the mask reads as 1 on every in-canvas position
     gs.cg.vec = inner % 4 == 0 && aligned16(gs.cg.known) && aligned16(gs.cg.mask);
-    static const int tags[4] = {prof_tag_id("fifo_shift_kernel<1, GuideShift>"), prof_tag_id("fifo_shift_kernel<4, GuideShift>"),
-                                prof_tag_id("fifo_shift_kernel<1, HistShift, GuideShift>"),
-                                prof_tag_id("fifo_shift_kernel<4, HistShift, GuideShift>")};
-    // the shift's traffic and the tail slot's known / mask reads
-    ProfScope prof(tags[(hist_in ? 2 : 0) + (plan.vec ? 1 : 0)],
-                   4.0 * ((hist_in ? 4.0 : 2.0) * (double)plan.total + 3.0 * (double)plan.pop), st);
-    const dim3 grid((unsigned)((plan.n_out + plan.n_pop + 255) / 256));
-    const HistShift hs{hist_in, hist_out};
-    if (hist_in) {
-        if (plan.vec)
-            hipLaunchKernelGGL((fifo_shift_kernel<4, HistShift, GuideShift>), grid, dim3(256), 0, st, z_in, z_out, popped, plan.ck, (uint32_t)t,
-                               B, outer, S, slot_len, inner, plan.n_out, plan.n_pop, hs, gs);
-        else
-            hipLaunchKernelGGL((fifo_shift_kernel<1, HistShift, GuideShift>), grid, dim3(256), 0, st, z_in, z_out, popped, plan.ck, (uint32_t)t,
-                               B, outer, S, slot_len, inner, plan.n_out, plan.n_pop, hs, gs);
-    } else if (plan.vec)
-        hipLaunchKernelGGL((fifo_shift_kernel<4, GuideShift>), grid, dim3(256), 0, st, z_in, z_out, popped, plan.ck, (uint32_t)t, B, outer, S,
-                           slot_len, inner, plan.n_out, plan.n_pop, gs);
-    else
-        hipLaunchKernelGGL((fifo_shift_kernel<1, GuideShift>), grid, dim3(256), 0, st, z_in, z_out, popped, plan.ck, (uint32_t)t, B, outer, S,
-                           slot_len, inner, plan.n_out, plan.n_pop, gs);
-    AVD_CHECK_LAUNCH("fifo_shift_guided");
-    return AVD_OK;
+    return fifo_move_launch(d, plan, st, gs);
 }
 
 // the checks every guided entry makes before any HIP call; out and x0_hist (either may be nullptr) must not overlap known / mask

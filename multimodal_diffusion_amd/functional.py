@@ -832,6 +832,41 @@ def dpmpp_2m_sde_step_slots(x_t: Tensor, eps_hat: Tensor, x0_hist: Tensor, t_las
     return out
 
 
+def _queue_dims(shape, slot_len) -> tuple:
+    """(outer, S, inner) of a queue of layout ``shape`` whose sliding length is S slots of ``slot_len`` positions"""
+    outer, L_, inner = window_dims(shape)
+    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or L_ % slot_len:
+        raise ValueError(f"slot_len must be an int >= 1 that divides the sliding length {L_}, got {slot_len!r}")
+    return outer, L_ // slot_len, inner
+
+
+def _check_clip_slot(c, t, slot_len: int, n_out: Optional[int] = None, at: str = "") -> None:
+    """the clip slot and timestep of a tail draw: ints >= 0, every slot the draw can name (``c`` alone, or ``c0`` .. ``c0 + n_out - 1``
+    off a cursor) inside the stream's 2**32 canvas positions"""
+    for name, v in (("c" if n_out is None else "c0", c), ("t", t)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"{name} must be an int >= 0{at}, got {v!r}")
+    if n_out is None and (c + 1) * slot_len > 2 ** 32:
+        raise ValueError(f"(c {c} + 1) * slot_len {slot_len} exceeds the stream's 2**32 canvas positions")
+    if n_out is not None and (c + n_out) * slot_len > 2 ** 32:
+        raise ValueError(f"(c0 {c} + n_out {n_out}) * slot_len {slot_len} exceeds the stream's 2**32 canvas positions")
+
+
+def _check_like(x, name: str, ref: Tensor, of: str = "z's", on: str = "z's device") -> None:
+    if not (isinstance(x, Tensor) and x.dtype == torch.float32 and x.is_contiguous() and x.shape == ref.shape and x.device == ref.device):
+        raise ValueError(f"{name} must be a contiguous float32 tensor of {of} shape {tuple(ref.shape)} on {on}")
+
+
+def _check_rider(z: Tensor, name: str, x: Optional[Tensor], x_out: Optional[Tensor], out_like_z: bool = True) -> None:
+    """a rider pair of a queue move: ``x_out`` goes with ``x``, and both are contiguous float32 tensors of z's shape on z's device"""
+    if x is None and x_out is not None:
+        raise ValueError(f"{name}_out goes with {name}")
+    if x is not None:
+        _check_like(x, name, z)
+    if x_out is not None:
+        _check_like(x_out, f"{name}_out", *((z,) if out_like_z else (x, f"{name}'s", "its device")))
+
+
 def fifo_shift(z: Tensor, c: int, seed: int, t: int, slot_len: int, hist: Optional[Tensor] = None, hist_out: Optional[Tensor] = None,
                guide: Optional[dict] = None):
     """The queue step of FIFO diagonal denoising (avd_fifo_shift_f32; contract in include/avdiff_hip.h, "FIFO queue shift"): ``z``
@@ -848,31 +883,18 @@ def fifo_shift(z: Tensor, c: int, seed: int, t: int, slot_len: int, hist: Option
     to ``t`` at clip positions c * slot_len + j — bit for bit this shift followed by the in-place ``clip_guide_slots`` call on the
     tail slot alone.  Everything else is the plain shift's."""
     z = L.dev_f32(z, "z")
-    if hist is None and hist_out is not None:
-        raise ValueError("hist_out goes with hist")
-    if hist is not None and not (hist.is_cuda and hist.dtype == torch.float32 and hist.is_contiguous() and hist.shape == z.shape and
-                                 hist.device == z.device):
-        raise ValueError(f"hist must be a contiguous float32 tensor of z's shape {tuple(z.shape)} on z's device")
-    outer, L_, inner = window_dims(z.shape)
-    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or L_ % slot_len:
-        raise ValueError(f"slot_len must be an int >= 1 that divides the sliding length {L_}, got {slot_len!r}")
-    for name, v in (("c", c), ("t", t)):
-        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
-            raise ValueError(f"{name} must be an int >= 0, got {v!r}")
-    if (c + 1) * slot_len > 2 ** 32:
-        raise ValueError(f"(c {c} + 1) * slot_len {slot_len} exceeds the stream's 2**32 canvas positions")
+    _check_rider(z, "hist", hist, hist_out, out_like_z=False)
+    outer, S, inner = _queue_dims(z.shape, slot_len)
+    _check_clip_slot(c, t, slot_len)
     key = noise_key(seed, 0)
     out = torch.empty_like(z)
     popped = torch.empty((z.shape[1], slot_len) + tuple(z.shape[3:]), device=z.device, dtype=torch.float32)
     if hist is None and guide is None:
         L.check(L.lib().avd_fifo_shift_f32(C.byref(key), t, c, z.data_ptr(), out.data_ptr(), popped.data_ptr(), z.shape[0], outer,
-                                           L_ // slot_len, slot_len, inner, _st(z)))
+                                           S, slot_len, inner, _st(z)))
         return out, popped
     if hist is not None and hist_out is None:
         hist_out = torch.empty_like(hist)
-    elif hist is not None and not (hist_out.is_cuda and hist_out.dtype == torch.float32 and hist_out.is_contiguous() and
-                                   hist_out.shape == hist.shape and hist_out.device == hist.device):
-        raise ValueError(f"hist_out must be a contiguous float32 tensor of hist's shape {tuple(hist.shape)} on its device")
     if guide is not None:
         if not isinstance(guide, dict) or set(guide) - {"known", "alpha_bar", "seed", "mask", "everywhere"} or \
                 not {"known", "alpha_bar", "seed"} <= set(guide):
@@ -883,10 +905,10 @@ def fifo_shift(z: Tensor, c: int, seed: int, t: int, slot_len: int, hist: Option
         ab = (ab if (ab.is_cuda and ab.dtype == torch.float32) else ab.to(z.device, torch.float32)).contiguous()
         L.check(L.lib().avd_fifo_shift_guided_f32(C.byref(key), t, c, C.byref(g), ab.data_ptr(), ab.numel(),
                                                   1 if guide.get("everywhere") else 0, z.data_ptr(), out.data_ptr(), popped.data_ptr(),
-                                                  L.ptr(hist), L.ptr(hist_out), z.shape[0], outer, L_ // slot_len, slot_len, inner, _st(z)))
+                                                  L.ptr(hist), L.ptr(hist_out), z.shape[0], outer, S, slot_len, inner, _st(z)))
         return (out, popped) if hist is None else (out, popped, hist_out)
     L.check(L.lib().avd_fifo_shift_hist_f32(C.byref(key), t, c, z.data_ptr(), out.data_ptr(), popped.data_ptr(), hist.data_ptr(),
-                                            hist_out.data_ptr(), z.shape[0], outer, L_ // slot_len, slot_len, inner, _st(z)))
+                                            hist_out.data_ptr(), z.shape[0], outer, S, slot_len, inner, _st(z)))
     return out, popped, hist_out
 
 
@@ -903,26 +925,15 @@ def fifo_lookahead(z: Tensor, ctx: int, shift: int, slot_len: int, c: Optional[i
     With ``hist`` (as in ``fifo_shift``) the result is (z_out, popped, hist_out): the history follows the same map on the stepping
     positions, zeros in the entering tail slot and on every context position."""
     z = L.dev_f32(z, "z")
-    if hist is None and hist_out is not None:
-        raise ValueError("hist_out goes with hist")
-    if hist is not None and not (hist.is_cuda and hist.dtype == torch.float32 and hist.is_contiguous() and hist.shape == z.shape and
-                                 hist.device == z.device):
-        raise ValueError(f"hist must be a contiguous float32 tensor of z's shape {tuple(z.shape)} on z's device")
-    outer, L_, inner = window_dims(z.shape)
-    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or L_ % slot_len:
-        raise ValueError(f"slot_len must be an int >= 1 that divides the sliding length {L_}, got {slot_len!r}")
-    S = L_ // slot_len
+    _check_rider(z, "hist", hist, hist_out, out_like_z=False)
+    outer, S, inner = _queue_dims(z.shape, slot_len)
     if isinstance(ctx, bool) or not isinstance(ctx, int) or not 0 <= ctx < S:
         raise ValueError(f"the lookahead ctx must be an int in [0, S = {S}), got {ctx!r}")
     if isinstance(shift, bool) or shift not in (0, 1):
         raise ValueError(f"shift must be 0 or 1, got {shift!r}")
     popped, key = None, None
     if shift:
-        for name, v in (("c", c), ("t", t)):
-            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
-                raise ValueError(f"{name} must be an int >= 0 at shift=1, got {v!r}")
-        if (c + 1) * slot_len > 2 ** 32:
-            raise ValueError(f"(c {c} + 1) * slot_len {slot_len} exceeds the stream's 2**32 canvas positions")
+        _check_clip_slot(c, t, slot_len, at=" at shift=1")
         if seed is None:
             raise ValueError("shift=1 draws the entering slot's noise from a seed: pass one")
         key = C.byref(noise_key(seed, 0))
@@ -935,11 +946,7 @@ def fifo_lookahead(z: Tensor, ctx: int, shift: int, slot_len: int, c: Optional[i
     if hist is None:
         L.check(L.lib().avd_fifo_lookahead_f32(*head, *tail))
         return out, popped
-    if hist_out is None:
-        hist_out = torch.empty_like(hist)
-    elif not (hist_out.is_cuda and hist_out.dtype == torch.float32 and hist_out.is_contiguous() and hist_out.shape == hist.shape and
-              hist_out.device == hist.device):
-        raise ValueError(f"hist_out must be a contiguous float32 tensor of hist's shape {tuple(hist.shape)} on its device")
+    hist_out = torch.empty_like(hist) if hist_out is None else hist_out
     L.check(L.lib().avd_fifo_lookahead_hist_f32(*head, hist.data_ptr(), hist_out.data_ptr(), *tail))
     return out, popped, hist_out
 
@@ -965,8 +972,8 @@ def fifo_carry(buf: Tensor, slots: int, slot_len: int, ctx: int = 0, shift: int 
     if isinstance(shift, bool) or shift not in (0, 1):
         raise ValueError(f"shift must be 0 or 1, got {shift!r}")
     B = buf.shape[0]
-    if out is not None and not (out.dtype == torch.float32 and out.is_contiguous() and out.shape == buf.shape and out.device == buf.device):
-        raise ValueError(f"out must be a contiguous float32 tensor of buf's shape {tuple(buf.shape)} on its device")
+    if out is not None:
+        _check_like(out, "out", buf, "buf's", "its device")
     if buf.is_cuda:
         buf = buf.contiguous()
         out = torch.empty_like(buf) if out is None else out
@@ -1137,29 +1144,20 @@ def fifo_shift_cursor(z: Tensor, c0: int, cursor: Tensor, clip: Tensor, seed: in
     outside [0, n_out).  Returns z_out, or (z_out, hist_out) with ``hist``.  ``out`` / ``hist_out``: buffers to write to (z's shape).
     The cursor is read, not moved."""
     z = L.dev_f32(z, "z")
-    outer, L_, inner = window_dims(z.shape)
-    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or L_ % slot_len:
-        raise ValueError(f"slot_len must be an int >= 1 that divides the sliding length {L_}, got {slot_len!r}")
-    for name, v in (("c0", c0), ("t", t)):
-        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
-            raise ValueError(f"{name} must be an int >= 0, got {v!r}")
+    outer, S, inner = _queue_dims(z.shape, slot_len)
     if not (isinstance(clip, Tensor) and clip.is_cuda and clip.dtype == torch.float32 and clip.is_contiguous() and clip.device == z.device and
             clip.dim() == z.dim() - 1 and clip.shape[0] == z.shape[1] and tuple(clip.shape[2:]) == tuple(z.shape[3:]) and
             clip.shape[1] >= slot_len and clip.shape[1] % slot_len == 0):
         raise ValueError(f"clip must be a contiguous float32 canvas [{z.shape[1]}, n_out * {slot_len}, ...] of z's slice shape on z's device")
     n_out = clip.shape[1] // slot_len
-    if (c0 + n_out) * slot_len > 2 ** 32:
-        raise ValueError(f"(c0 {c0} + n_out {n_out}) * slot_len {slot_len} exceeds the stream's 2**32 canvas positions")
-    if hist is None and hist_out is not None:
-        raise ValueError("hist_out goes with hist")
-    bufs = [("out", out)] + ([("hist", hist), ("hist_out", hist_out)] if hist is not None else [])
-    for name, b in bufs:
-        if b is not None and not (b.is_cuda and b.dtype == torch.float32 and b.is_contiguous() and b.shape == z.shape and b.device == z.device):
-            raise ValueError(f"{name} must be a contiguous float32 tensor of z's shape {tuple(z.shape)} on z's device")
+    _check_clip_slot(c0, t, slot_len, n_out)
+    if out is not None:
+        _check_like(out, "out", z)
+    _check_rider(z, "hist", hist, hist_out)
     key = noise_key(seed, 0)
     out = torch.empty_like(z) if out is None else out
     head = (C.byref(key), t, c0, _cursor(cursor, z.device).data_ptr(), n_out, z.data_ptr(), out.data_ptr(), clip.data_ptr())
-    tail = (z.shape[0], outer, L_ // slot_len, slot_len, inner, _st(z))
+    tail = (z.shape[0], outer, S, slot_len, inner, _st(z))
     if hist is None:
         L.check(L.lib().avd_fifo_shift_cursor_f32(*head, *tail))
         return out
@@ -1199,17 +1197,11 @@ def fifo_shift_clips(z: Tensor, queues: int, c: int, seeds, t: int, slot_len: in
     ``canvas_noise`` (which needs a device: a CPU-only caller passes ``tails``).  ``tails`` is refused with a device tensor."""
     if not (isinstance(z, Tensor) and z.dtype == torch.float32 and z.dim() in (3, 5)):
         raise ValueError("z must be a float32 tensor of the queue's layout, [B,C,T,H,W] or [B,Ca,F]")
-    outer, L_, inner = window_dims(z.shape)
-    B = z.shape[0]
+    B, L_ = z.shape[0], z.shape[2]
     if isinstance(queues, bool) or not isinstance(queues, int) or queues < 1 or B % queues:
         raise ValueError(f"queues {queues!r} must be an int >= 1 that divides the batch {B}")
-    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or L_ % slot_len:
-        raise ValueError(f"slot_len must be an int >= 1 that divides the sliding length {L_}, got {slot_len!r}")
-    for name, v in (("c", c), ("t", t)):
-        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
-            raise ValueError(f"{name} must be an int >= 0, got {v!r}")
-    if (c + 1) * slot_len > 2 ** 32:
-        raise ValueError(f"(c {c} + 1) * slot_len {slot_len} exceeds the stream's 2**32 canvas positions")
+    outer, S, inner = _queue_dims(z.shape, slot_len)
+    _check_clip_slot(c, t, slot_len)
     if isinstance(m, bool) or not isinstance(m, int):
         raise ValueError(f"m must be an int (the clip slot the heads go to), got {m!r}")
     if isinstance(seeds, Tensor):
@@ -1227,12 +1219,7 @@ def fifo_shift_clips(z: Tensor, queues: int, c: int, seeds, t: int, slot_len: in
     n_clip = clips.shape[2] // slot_len
     riders = []
     for name, a, b in (("hist", hist, hist_out), ("carry", carry, carry_out)):
-        if a is None and b is not None:
-            raise ValueError(f"{name}_out goes with {name}")
-        for nm, x in ((name, a), (f"{name}_out", b)):
-            if x is not None and not (isinstance(x, Tensor) and x.dtype == torch.float32 and x.is_contiguous() and x.shape == z.shape and
-                                      x.device == z.device):
-                raise ValueError(f"{nm} must be a contiguous float32 tensor of z's shape {tuple(z.shape)} on z's device")
+        _check_rider(z, name, a, b)
         if a is not None:
             riders.append([a, torch.empty_like(a) if b is None else b])
     if z.is_cuda:
@@ -1243,7 +1230,7 @@ def fifo_shift_clips(z: Tensor, queues: int, c: int, seeds, t: int, slot_len: in
         h, k = ((hist, riders[0][1]) if hist is not None else (None, None)), ((carry, riders[-1][1]) if carry is not None else (None, None))
         L.check(L.lib().avd_fifo_shift_clips_f32(seeds.data_ptr(), t, c, z.data_ptr(), out.data_ptr(), clips.data_ptr(), n_clip, m,
                                                  L.ptr(h[0]), L.ptr(h[1]), L.ptr(k[0]), L.ptr(k[1]), B, queues, outer,
-                                                 L_ // slot_len, slot_len, inner, _st(z)))
+                                                 S, slot_len, inner, _st(z)))
         return out if not riders else (out,) + tuple(r[1] for r in riders)
     Bq = B // queues
     if tails is None:

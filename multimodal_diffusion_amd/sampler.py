@@ -720,8 +720,25 @@ class DenoiseEngine:
         if self._smom_beta == 0.0:
             return
         Fn.fifo_carry(self._smom, self.slots, self.slot_len, ctx=ctx, shift=shift, out=self._smom_other)
+        self._swap_slot_momentum()
+
+    def _swap_slot_momentum(self) -> None:
+        """behind a launch that moved the live momentum buffer into the other one: the two swap, the control follows the live address"""
         self._smom, self._smom_other = self._smom_other, self._smom
         self._scfg.momentum_buf = self._smom.data_ptr()
+
+    def _move_hist(self, what: str, move, bump: bool = True):
+        """An out-of-place queue move of the solver history: ``move(hist, hist_out)`` launches it from ``x0_hist`` into the engine's
+        other history buffer (allocated on first use), then the two swap.  That changes an address a captured graph holds, so a new
+        graph generation starts (``bump`` False inside a captured pair, whose two swaps put the address back).  Returns move's result."""
+        if self._hist_other is None:
+            self._hist_other = torch.empty_like(self.x0_hist)
+        res = move(self.x0_hist, self._hist_other)
+        self.x0_hist, self._hist_other = self._hist_other, self.x0_hist
+        if bump:
+            self._generation += 1
+            self._stale_reason = f"{what} moved the solver history into the engine's other history buffer (x0_hist changed its address)"
+        return res
 
     def slot_cfg_coef(self) -> torch.Tensor:
         """The per-slot coefficients the last controlled ``step_slots`` left in the scratch, float32 [B, S, 4] on the device:
@@ -1151,13 +1168,9 @@ class DenoiseEngine:
             out = Fn.fifo_shift(z, c, seed, t, self.slot_len, guide=guide)
             self._carry_slot_momentum(0, 1)      # a slot momentum follows its slot: a launch of its own behind the move
             return out
-        if self._hist_other is None:
-            self._hist_other = torch.empty_like(self.x0_hist)
-        z_out, popped, _ = Fn.fifo_shift(z, c, seed, t, self.slot_len, hist=self.x0_hist, hist_out=self._hist_other, guide=guide)
+        z_out, popped, _ = self._move_hist("fifo_shift", lambda h, h_out: Fn.fifo_shift(z, c, seed, t, self.slot_len, hist=h, hist_out=h_out,
+                                                                                        guide=guide))
         self._carry_slot_momentum(0, 1)
-        self.x0_hist, self._hist_other = self._hist_other, self.x0_hist
-        self._generation += 1
-        self._stale_reason = "fifo_shift moved the solver history into the engine's other history buffer (x0_hist changed its address)"
         return z_out, popped
 
     def fifo_shift_clips(self, z: torch.Tensor, queues: int, c: int, t: int, seeds, clips: torch.Tensor, m: int) -> torch.Tensor:
@@ -1169,19 +1182,14 @@ class DenoiseEngine:
         the other momentum buffer too: no ``functional.fifo_carry`` launch.  A clip guide refuses the call."""
         self._clip_refusal("fifo_shift_clips", "a clip guide is one canvas walked by one queue, and a clip batch holds several")
         multistep, mom = self.solver == "dpmpp_2m", self._smom_beta != 0.0
-        if multistep and self._hist_other is None:
-            self._hist_other = torch.empty_like(self.x0_hist)
-        out = Fn.fifo_shift_clips(z, queues, c, seeds, t, self.slot_len, clips, m,
-                                  hist=self.x0_hist if multistep else None, hist_out=self._hist_other if multistep else None,
-                                  carry=self._smom if mom else None, carry_out=self._smom_other if mom else None)
+
+        def move(h, h_out):
+            return Fn.fifo_shift_clips(z, queues, c, seeds, t, self.slot_len, clips, m, hist=h, hist_out=h_out,
+                                       carry=self._smom if mom else None, carry_out=self._smom_other if mom else None)
+
+        out = self._move_hist("fifo_shift_clips", move) if multistep else move(None, None)
         if mom:
-            self._smom, self._smom_other = self._smom_other, self._smom
-            self._scfg.momentum_buf = self._smom.data_ptr()
-        if multistep:
-            self.x0_hist, self._hist_other = self._hist_other, self.x0_hist
-            self._generation += 1
-            self._stale_reason = ("fifo_shift_clips moved the solver history into the engine's other history buffer (x0_hist changed its "
-                                  "address)")
+            self._swap_slot_momentum()
         return out[0] if isinstance(out, tuple) else out
 
     def fifo_lookahead(self, z: torch.Tensor, ctx: int, shift: int, c: Optional[int] = None, t: Optional[int] = None,
@@ -1202,13 +1210,9 @@ class DenoiseEngine:
             out = Fn.fifo_lookahead(z, ctx, shift, self.slot_len, c=c, seed=seed, t=t)
             self._carry_slot_momentum(ctx, shift)
             return out
-        if self._hist_other is None:
-            self._hist_other = torch.empty_like(self.x0_hist)
-        z_out, popped, _ = Fn.fifo_lookahead(z, ctx, shift, self.slot_len, c=c, seed=seed, t=t, hist=self.x0_hist, hist_out=self._hist_other)
+        z_out, popped, _ = self._move_hist("fifo_lookahead", lambda h, h_out: Fn.fifo_lookahead(z, ctx, shift, self.slot_len, c=c, seed=seed,
+                                                                                                t=t, hist=h, hist_out=h_out))
         self._carry_slot_momentum(ctx, shift)
-        self.x0_hist, self._hist_other = self._hist_other, self.x0_hist
-        self._generation += 1
-        self._stale_reason = "fifo_lookahead moved the solver history into the engine's other history buffer (x0_hist changed its address)"
         return z_out, popped
 
     # ---- FIFO queue with device cursors: an iteration as a fixed chain of launches (include/avdiff_hip.h, "FIFO device cursors") ----
@@ -1305,11 +1309,9 @@ class DenoiseEngine:
         if not multistep:
             Fn.fifo_shift_cursor(tmp, q.n, q.m, q.clip, q.seed, q.s0, self.slot_len, out=z)
         else:
-            Fn.fifo_shift_cursor(tmp, q.n, q.m, q.clip, q.seed, q.s0, self.slot_len, out=z, hist=self.x0_hist, hist_out=self._hist_other)
-            self.x0_hist, self._hist_other = self._hist_other, self.x0_hist
-            if not torch.cuda.is_current_stream_capturing():      # a captured pair swaps twice: the address is back where it was
-                self._generation += 1
-                self._stale_reason = "fifo_steady moved the solver history into the engine's other history buffer (x0_hist changed its address)"
+            self._move_hist("fifo_steady", lambda h, h_out: Fn.fifo_shift_cursor(tmp, q.n, q.m, q.clip, q.seed, q.s0, self.slot_len, out=z,
+                                                                                 hist=h, hist_out=h_out),
+                            bump=not torch.cuda.is_current_stream_capturing())      # a captured pair swaps twice: the address is back
         self._carry_slot_momentum(0, 1)      # the carry's map reads no cursor: the same launch eagerly and in a captured pair, whose two
         Fn.cursor_add(q.m)                   # iterations put the live buffer back at its address, as the histories
 

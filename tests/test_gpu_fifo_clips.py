@@ -37,7 +37,9 @@ def _reference(z, K, c, seeds, t, slot_len, clips, m, hist, carry):
 
 
 @pytest.mark.parametrize("riders", [0, 1, 2])
-@pytest.mark.parametrize("shape,slot_len,K", [((4, 8, 4, 16, 16), 2, 2), ((6, 8, 40), 4, 3), ((3, 8, 4, 16, 16), 1, 3)])
+# the last two are K queues of one window of one slot each (Bq = 1, S = 1): every queue's only slot is its head and its tail
+@pytest.mark.parametrize("shape,slot_len,K", [((4, 8, 4, 16, 16), 2, 2), ((6, 8, 40), 4, 3), ((3, 8, 4, 16, 16), 1, 3),
+                                              ((2, 1, 1, 2, 2), 1, 2), ((2, 2, 4), 4, 2)])
 def test_kernel_equals_the_one_queue_entries_on_slices(dev, shape, slot_len, K, riders):
     from multimodal_diffusion_amd import _lib as L
     from multimodal_diffusion_amd import functional as Fn

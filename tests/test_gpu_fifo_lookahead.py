@@ -22,14 +22,17 @@ def _tail(Fn, shape, slot_len, c):
 
 # ------------------------------------------------------------------------------------------------- the kernel
 # B = 3: the smallest batch with a window whose slots are duplicated on both sides; ctx = 3 (h = 1): one slot lives in every window;
-# the audio latent (inner = 1) takes the one-element lanes
+# the audio latent (inner = 1) takes the one-element lanes.  The last four are the smallest queues with h = 1, where the owner's window
+# is the division's quotient alone: one window (no duplicates, every stepping position is the tail at shift 1), two, and inner = 3 (the
+# one-element lanes on a video shape)
 @pytest.mark.parametrize("shape,slot_len,ctx", [((3, 8, 8, 16, 16), 2, 1), ((3, 8, 8, 16, 16), 2, 2), ((3, 8, 8, 16, 16), 2, 3),
-                                                ((3, 8, 16), 4, 2), ((2, 8, 4, 16, 16), 2, 1)])
+                                                ((3, 8, 16), 4, 2), ((2, 8, 4, 16, 16), 2, 1), ((1, 1, 2, 2, 2), 1, 1),
+                                                ((2, 1, 2, 2, 2), 1, 1), ((2, 1, 3, 1, 3), 1, 2), ((2, 2, 8), 4, 1)])
 def test_lookahead_equals_the_torch_map(dev, shape, slot_len, ctx):
     from multimodal_diffusion_amd import _lib as L, functional as Fn
     g = torch.Generator().manual_seed(len(shape) + ctx)
     z, hist = torch.randn(shape, generator=g).to(dev), torch.randn(shape, generator=g).to(dev)      # no copy equals its owner yet
-    assert ctx == 0 or not LR.coherent(z, ctx, slot_len)
+    assert ctx == 0 or shape[0] == 1 or not LR.coherent(z, ctx, slot_len)      # one window holds no duplicate
     c = 11
     tail = _tail(Fn, shape, slot_len, c)
     B, S = shape[0], shape[2] // slot_len
@@ -52,10 +55,10 @@ def test_lookahead_equals_the_torch_map(dev, shape, slot_len, ctx):
         assert (hist_out[:, :, :ctx * slot_len] == 0).all()                         # zeros on the context positions ...
         if shift:
             assert (LR.slot(hist_out, B - 1, S - 1, slot_len) == 0).all()           # ... and in the tail
-        assert (hist_out[:, :, ctx * slot_len:] != 0).any()
+        if B * (S - ctx) > shift:                                                   # a stepping position whose source is not the tail
+            assert (hist_out[:, :, ctx * slot_len:] != 0).any()
         if len(shape) == 5:      # misaligned views take the one-element lanes: same bits
-            buf = torch.empty(2, z.numel() + 1, device=dev)
-            zu, hu = buf[0, 1:].view(shape).copy_(z), buf[1, 1:].view(shape).copy_(hist)
+            zu, hu = (torch.empty(x.numel() + 1, device=dev)[1:].view(shape).copy_(x) for x in (z, hist))      # one float past an allocation
             assert zu.data_ptr() % 16 != 0 and hu.data_ptr() % 16 != 0
             o2, h2 = torch.empty_like(z), torch.empty_like(z)
             p2 = torch.empty_like(popped) if shift else None
@@ -69,7 +72,9 @@ def test_lookahead_equals_the_torch_map(dev, shape, slot_len, ctx):
             assert torch.equal(o2, ref) and torch.equal(h2, ref_hist)
 
 
-@pytest.mark.parametrize("shape,slot_len", [((2, 8, 4, 16, 16), 2), ((2, 8, 40), 4), ((3, 8, 4, 16, 16), 1)])
+# the last two are queues of one slot: every output lane is the tail and the only slot is the head
+@pytest.mark.parametrize("shape,slot_len", [((2, 8, 4, 16, 16), 2), ((2, 8, 40), 4), ((3, 8, 4, 16, 16), 1), ((1, 1, 1, 2, 2), 1),
+                                            ((1, 2, 4), 4)])
 def test_ctx_0_is_the_plain_shift(dev, shape, slot_len):
     from multimodal_diffusion_amd import functional as Fn
     g = torch.Generator().manual_seed(5)
@@ -82,6 +87,53 @@ def test_ctx_0_is_the_plain_shift(dev, shape, slot_len):
     assert torch.equal(out, ref) and torch.equal(popped, ref_popped) and torch.equal(hist_out, ref_hist)
     out0, none = Fn.fifo_lookahead(z, 0, 0, slot_len)                     # no duplicates at ctx = 0: the refresh is a copy
     assert none is None and torch.equal(out0, z)
+
+
+@pytest.mark.parametrize("shape,slot_len", [((3, 2, 4, 2, 2), 1), ((2, 2, 8), 4)])
+def test_every_entry_is_the_one_map(dev, shape, slot_len):
+    """Every queue-move entry is one slot map: at ctx = 0, shift = 1 and one queue the shift, the lookahead, the cursor shift (the
+    cursor holding m, c0 = c - m) and the clip batch give the torch map's bits, their histories fifo_carry's; at ctx > 0 fifo_carry is
+    the lookahead's history output at either shift.  Once more on a view misaligned by one float (the one-element lanes)."""
+    from multimodal_diffusion_amd import functional as Fn
+    g = torch.Generator().manual_seed(23)
+    z, hist = torch.randn(shape, generator=g).to(dev), torch.randn(shape, generator=g).to(dev)
+    S, c, m, n_clip = shape[2] // slot_len, 11, 2, 4
+    ref, ref_popped = LR.lookahead(z, 0, 1, slot_len, _tail(Fn, shape, slot_len, c))
+    ref_hist = Fn.fifo_carry(hist, S, slot_len)
+    assert torch.equal(ref_hist, LR.lookahead_hist(hist, 0, 1, slot_len))
+    canvas = (shape[1], n_clip * slot_len) + tuple(shape[3:])
+    head = (slice(None), slice(m * slot_len, (m + 1) * slot_len))
+
+    def entries(z_, h_):
+        """(z_out, head, hist_out or None) of every entry"""
+        kw = {} if h_ is None else dict(hist=h_)
+        yield Fn.fifo_shift(z_, c, SEED, T0, slot_len, **kw) + (() if kw else (None,))
+        yield Fn.fifo_lookahead(z_, 0, 1, slot_len, c=c, seed=SEED, t=T0, **kw) + (() if kw else (None,))
+        clip = torch.full(canvas, 7.0, device=dev)
+        res = Fn.fifo_shift_cursor(z_, c - m, torch.tensor([m], dtype=torch.int32, device=dev), clip, SEED, T0, slot_len, **kw)
+        yield (res[0], clip[head], res[1]) if kw else (res, clip[head], None)
+        clips = torch.full((1,) + canvas, 7.0, device=dev)
+        res = Fn.fifo_shift_clips(z_, 1, c, [SEED], T0, slot_len, clips, m, **kw)
+        yield (res[0], clips[0][head], res[1]) if kw else (res, clips[0][head], None)
+
+    views = [(z, hist)]
+    if len(shape) == 5:
+        zu, hu = (torch.empty(x.numel() + 1, device=dev)[1:].view(shape).copy_(x) for x in (z, hist))
+        assert zu.data_ptr() % 16 != 0 and hu.data_ptr() % 16 != 0
+        views.append((zu, hu))
+    for z_, h_ in views:
+        for with_hist in (False, True):
+            got = list(entries(z_, h_ if with_hist else None))
+            assert len(got) == 4
+            for out, popped, hist_out in got:
+                assert torch.equal(out, ref) and torch.equal(popped, ref_popped)
+                assert (hist_out is None) if not with_hist else torch.equal(hist_out, ref_hist)
+        for ctx in sorted({1, S - 1}):
+            for shift in (0, 1):
+                kw = dict(c=c, seed=SEED, t=T0) if shift else {}
+                want = LR.lookahead_hist(hist, ctx, shift, slot_len)
+                assert torch.equal(Fn.fifo_carry(h_, S, slot_len, ctx=ctx, shift=shift), want)
+                assert torch.equal(Fn.fifo_lookahead(z_, ctx, shift, slot_len, hist=h_, **kw)[2], want)
 
 
 def test_functional_refusals(dev):
