@@ -398,18 +398,27 @@ __device__ __forceinline__ f32x4 philox_normal4(const NoiseKey& nk, uint32_t e4,
     return f32x4{r0 * co0, r0 * s0, r1 * co1, r1 * s1};
 }
 
-__global__ __launch_bounds__(256) void gaussian_noise_kernel(const int64_t* __restrict__ t_now, float* __restrict__ out, NoiseKey nk,
-                                                             int64_t per, int64_t per4, int64_t total4) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total4) return;
-    const int b = (int)(i / per4);
-    const int64_t q = i % per4;
-    const f32x4 n = philox_normal4(nk, (uint32_t)q, nk.s0 + (uint32_t)b, (uint32_t)t_now[b]);
-    float* o = out + (int64_t)b * per + q * 4;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (q * 4 + k < per) o[k] = n[k];
+// One position map serves the three keyings of the stream (per sample, by canvas position, by clip position) in the stand-alone passes
+// ("the stream's stand-alone passes" below).  Element (o, l, i) of sample b of a batch [B, outer, L, inner] draws at stream position
+//   p = base + max(*cursor, 0) * cstep + b * bstep + l
+// with element e' = o * inner + i.  The sum wraps in 64 bits and its low word is the contract's p: a negative clip origin arrives as
+// its two's complement in base.  The keyings differ in the coefficients alone (stream_map below) and in the time word the caller passes.
+struct StreamMap {
+    uint32_t k0, k1;            // seed & 0xffffffff, seed >> 32
+    uint64_t base, bstep, cstep;
+    const int32_t* cursor;      // device int32 or null: only read, it addresses nothing
+};
+// the Philox call that holds element e' = o * inner + i: e' takes n[e' & 3]; where o * inner and i are multiples of 4 the four values are
+// elements i .. i + 3 of the (o, l) slice
+__device__ __forceinline__ f32x4 stream_normal4(const StreamMap& m, int b, int64_t o, int l, int64_t i, int64_t inner, uint32_t t,
+                                                uint32_t tag) {
+    int32_t c = m.cursor ? *m.cursor : 0;
+    if (c < 0) c = 0;
+    const uint64_t p = m.base + (uint64_t)c * m.cstep + (uint64_t)b * m.bstep + (uint64_t)l;
+    return philox_normal4(NoiseKey{m.k0, m.k1, 0u}, (uint32_t)((o * inner + i) >> 2), (uint32_t)p, t, tag);
 }
+// per sample: the batch is [B, 1, 1, per], sample b at position s0 + b
+static StreamMap stream_map(const NoiseKey& k) { return StreamMap{k.k0, k.k1, k.s0, 1, 0, nullptr}; }
 
 static int make_noise_key(const avd_noise_key* key, int B, NoiseKey& nk) {
     AVD_REQUIRE(key, AVD_EINVAL, "noise key: null pointer");
@@ -420,16 +429,27 @@ static int make_noise_key(const avd_noise_key* key, int B, NoiseKey& nk) {
     return AVD_OK;
 }
 
-int gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int B, int64_t per, hipStream_t st) {
-    NoiseKey nk;
-    if (int rc = make_noise_key(key, B, nk)) return rc;
-    AVD_REQUIRE(t_now && out, AVD_EINVAL, "gaussian_noise: null pointer");
-    AVD_REQUIRE(per > 0 && per < ((int64_t)1 << 34), AVD_EINVAL, "gaussian_noise: per_sample %lld must be in [1, 2^34)", (long long)per);
-    const int64_t per4 = (per + 3) >> 2, total4 = (int64_t)B * per4;
-    AVD_REQUIRE((total4 + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "gaussian_noise: %lld values is too many for one launch",
-                (long long)B * per);
-    hipLaunchKernelGGL(gaussian_noise_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, t_now, out, nk, per, per4, total4);
-    AVD_CHECK_LAUNCH("gaussian_noise");
+// The checks the canvas key, the slot key and the clip guide share; `what` is the prefix of their messages.
+// the batch's dims, named as the caller's contract names them (bn: "N" or "B"; ln: "L" or "slot_len"), and one position's slice below
+// 2^34 elements: e' >> 2 fits the counter's word
+static int check_keyed_dims(const char* what, const char* bn, int B, int64_t outer, const char* ln, int L, int64_t inner) {
+    AVD_REQUIRE(B > 0 && outer > 0 && L > 0 && inner > 0, AVD_EINVAL, "%s: bad dims (%s %d, outer %lld, %s %d, inner %lld)", what, bn, B,
+                (long long)outer, ln, L, (long long)inner);
+    AVD_REQUIRE(outer <= (((int64_t)1 << 34) - 1) / inner, AVD_EINVAL, "%s: outer %lld * inner %lld must be < 2^34", what,
+                (long long)outer, (long long)inner);
+    return AVD_OK;
+}
+// a clip origin (whose: "slot key" or "clip guide"): stride >= 1 and |first| < 2^32
+static int check_clip_origin(const char* what, const char* whose, int stride, int64_t first) {
+    const int64_t lim = (int64_t)1 << 32;
+    AVD_REQUIRE(stride >= 1, AVD_EINVAL, "%s: the %s's stride must be >= 1 (got %d)", what, whose, stride);
+    AVD_REQUIRE(first > -lim && first < lim, AVD_EINVAL, "%s: the %s's first %lld must lie in (-2^32, 2^32)", what, whose, (long long)first);
+    return AVD_OK;
+}
+// a slot table [B, slots] over L positions
+static int check_slots(const char* what, int B, int L, int slots, int slot_len) {
+    AVD_REQUIRE(slot_len >= 1 && slots >= 1 && (int64_t)slots * slot_len <= L && (int64_t)B * slots <= 0x7fffffff, AVD_EINVAL,
+                "%s: slots %d * slot_len %d must lie in [1, L %d] and B %d * slots fit an int", what, slots, slot_len, L, B);
     return AVD_OK;
 }
 
@@ -452,40 +472,18 @@ __device__ __forceinline__ f32x4 canvas_normal4(const CanvasKey& ck, int b, int6
     return philox_normal4(NoiseKey{ck.k0, ck.k1, 0u}, (uint32_t)((o * inner + i) >> 2), (uint32_t)p, t, tag);
 }
 
-// V == 4: inner % 4 == 0 and out 16-byte aligned, a lane's float4 lies inside one (o, l) slice: one Philox call per four values.
-// V == 1: one Philox call per element (every audio latent: inner == 1).  n: N * outer * L * inner / V lanes.
-template <int V>
-__global__ __launch_bounds__(256) void canvas_noise_kernel(const int64_t* __restrict__ t_now, float* __restrict__ out, CanvasKey ck,
-                                                           int64_t outer, int L, int64_t inner, int64_t n) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n) return;
-    const int64_t iv = inner / V;
-    const int64_t i = (idx % iv) * V;
-    int64_t r = idx / iv;
-    const int l = (int)(r % L);
-    r /= L;
-    const int64_t o = r % outer;
-    const int b = (int)(r / outer);
-    const f32x4 v = canvas_normal4(ck, b, o, l, i, inner, (uint32_t)t_now[b]);
-    if constexpr (V == 4) *reinterpret_cast<f32x4*>(out + idx * 4) = v;
-    else out[idx] = v[(int)((o * inner + i) & 3)];
-}
-
 // the checks of the canvas keying, all before any HIP call: hop >= 1, every canvas position of the batch below 2^32, and one position's
 // slice outer * inner below 2^34 elements
 // what: the stream the messages name ("canvas noise", or "canvas guide" for the latent guide's known noise)
 int make_canvas_key(const avd_noise_key* key, int N, int64_t outer, int L, int hop, int64_t inner, CanvasKey& ck,
                     const char* what = "canvas noise") {
     AVD_REQUIRE(key, AVD_EINVAL, "%s: null noise key", what);
-    AVD_REQUIRE(N > 0 && outer > 0 && L > 0 && inner > 0, AVD_EINVAL, "%s: bad dims (N %d, outer %lld, L %d, inner %lld)", what, N,
-                (long long)outer, L, (long long)inner);
+    if (int rc = check_keyed_dims(what, "N", N, outer, "L", L, inner)) return rc;
     AVD_REQUIRE(hop >= 1, AVD_EINVAL, "%s: hop must be >= 1 (got %d)", what, hop);
     const int64_t lim = (int64_t)1 << 32;
     AVD_REQUIRE(key->sample_offset >= 0 && key->sample_offset < lim && key->sample_offset + N - 1 <= (lim - L) / hop, AVD_EINVAL,
                 "%s: (sample_offset %lld + N %d - 1) * hop %d + L %d must lie in [1, 2^32]", what, (long long)key->sample_offset, N,
                 hop, L);
-    AVD_REQUIRE(outer <= (((int64_t)1 << 34) - 1) / inner, AVD_EINVAL, "%s: outer %lld * inner %lld must be < 2^34", what,
-                (long long)outer, (long long)inner);
     ck = CanvasKey{(uint32_t)(key->seed & 0xffffffffu), (uint32_t)(key->seed >> 32), (uint32_t)key->sample_offset, (uint32_t)hop};
     return AVD_OK;
 }
@@ -495,22 +493,8 @@ int check_canvas_key(const avd_noise_key* key, int N, int64_t outer, int L, int 
     return make_canvas_key(key, N, outer, L, hop, inner, ck);
 }
 
-int canvas_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int N, int64_t outer, int L, int hop, int64_t inner,
-                     hipStream_t st) {
-    CanvasKey ck;
-    if (int rc = make_canvas_key(key, N, outer, L, hop, inner, ck)) return rc;
-    AVD_REQUIRE(t_now && out, AVD_EINVAL, "canvas_noise: null pointer");
-    const bool vec = inner % 4 == 0 && aligned16(out);
-    AVD_REQUIRE((double)N * (double)outer * (double)L * (double)inner < 9.0e18, AVD_EUNSUPPORTED, "canvas_noise: too many values");
-    const int64_t n = (int64_t)N * outer * L * inner / (vec ? 4 : 1);
-    AVD_REQUIRE((n + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "canvas_noise: %lld lanes are too many for one launch", (long long)n);
-    if (vec)
-        hipLaunchKernelGGL(canvas_noise_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t_now, out, ck, outer, L, inner, n);
-    else
-        hipLaunchKernelGGL(canvas_noise_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t_now, out, ck, outer, L, inner, n);
-    AVD_CHECK_LAUNCH("canvas_noise");
-    return AVD_OK;
-}
+// window b at position (w0 + b) * hop
+static StreamMap stream_map(const CanvasKey& k) { return StreamMap{k.k0, k.k1, (uint64_t)k.w0 * k.hop, k.hop, 0, nullptr}; }
 
 // ------------------------------------------------------------------ clip keying of the seeded stream (slot timesteps at eta > 0)
 // The contract is written out in include/avdiff_hip.h ("clip-keyed slot noise").  Sample b of a batch [B, outer, L, inner] holds clip
@@ -533,37 +517,11 @@ __device__ __forceinline__ f32x4 slot_normal4(const SlotKey& sk, int b, int64_t 
     return philox_normal4(NoiseKey{sk.k0, sk.k1, 0u}, (uint32_t)((o * inner + i) >> 2), (uint32_t)p, t, SLOT_TAG);
 }
 
-// V lanes as canvas_noise_kernel; t_now is the [B, S] table, position l in slot min(l / slot_len, S - 1)
-template <int V>
-__global__ __launch_bounds__(256) void slot_noise_kernel(const int64_t* __restrict__ t_now, float* __restrict__ out, SlotKey sk,
-                                                         int64_t outer, int L, int S, int64_t inner, int64_t n) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n) return;
-    const int64_t iv = inner / V;
-    const int64_t i = (idx % iv) * V;
-    int64_t r = idx / iv;
-    const int l = (int)(r % L);
-    r /= L;
-    const int64_t o = r % outer;
-    const int b = (int)(r / outer);
-    int s = l / sk.slot_len;
-    if (s > S - 1) s = S - 1;
-    const f32x4 v = slot_normal4(sk, b, o, l, i, inner, (uint32_t)t_now[(int64_t)b * S + s]);
-    if constexpr (V == 4) *reinterpret_cast<f32x4*>(out + idx * 4) = v;
-    else out[idx] = v[(int)((o * inner + i) & 3)];
-}
-
 // the checks of the clip keying, all before any HIP call: stride >= 1, |first| < 2^32 and one position's slice below 2^34 elements
 int make_slot_key(const avd_slot_key* key, int B, int64_t outer, int slot_len, int64_t inner, SlotKey& sk, const char* what = "slot noise") {
     AVD_REQUIRE(key, AVD_EINVAL, "%s: null slot key", what);
-    AVD_REQUIRE(B > 0 && outer > 0 && slot_len > 0 && inner > 0, AVD_EINVAL, "%s: bad dims (B %d, outer %lld, slot_len %d, inner %lld)", what,
-                B, (long long)outer, slot_len, (long long)inner);
-    AVD_REQUIRE(key->stride >= 1, AVD_EINVAL, "%s: the slot key's stride must be >= 1 (got %d)", what, key->stride);
-    const int64_t lim = (int64_t)1 << 32;
-    AVD_REQUIRE(key->first > -lim && key->first < lim, AVD_EINVAL, "%s: the slot key's first %lld must lie in (-2^32, 2^32)", what,
-                (long long)key->first);
-    AVD_REQUIRE(outer <= (((int64_t)1 << 34) - 1) / inner, AVD_EINVAL, "%s: outer %lld * inner %lld must be < 2^34", what,
-                (long long)outer, (long long)inner);
+    if (int rc = check_keyed_dims(what, "B", B, outer, "slot_len", slot_len, inner)) return rc;
+    if (int rc = check_clip_origin(what, "slot key", key->stride, key->first)) return rc;
     sk = SlotKey{(uint32_t)(key->seed & 0xffffffffu), (uint32_t)(key->seed >> 32), key->first, key->stride, slot_len, key->cursor};
     return AVD_OK;
 }
@@ -573,23 +531,9 @@ int check_slot_key(const avd_slot_key* key, int B, int64_t outer, int slot_len, 
     return make_slot_key(key, B, outer, slot_len, inner, sk);
 }
 
-int slot_noise_f32(const avd_slot_key* key, const int64_t* t_now, float* out, int B, int64_t outer, int L, int slots, int slot_len,
-                   int64_t inner, hipStream_t st) {
-    SlotKey sk;
-    if (int rc = make_slot_key(key, B, outer, slot_len, inner, sk)) return rc;
-    AVD_REQUIRE(t_now && out, AVD_EINVAL, "slot_noise: null pointer");
-    AVD_REQUIRE(slots > 0 && (int64_t)slots * slot_len <= L && (int64_t)B * slots <= 0x7fffffff, AVD_EINVAL,
-                "slot_noise: slots %d * slot_len %d must lie in [1, L %d] and B %d * slots fit an int", slots, slot_len, L, B);
-    const bool vec = inner % 4 == 0 && aligned16(out);
-    AVD_REQUIRE((double)B * (double)outer * (double)L * (double)inner < 9.0e18, AVD_EUNSUPPORTED, "slot_noise: too many values");
-    const int64_t n = (int64_t)B * outer * L * inner / (vec ? 4 : 1);
-    AVD_REQUIRE((n + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "slot_noise: %lld lanes are too many for one launch", (long long)n);
-    if (vec)
-        hipLaunchKernelGGL(slot_noise_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t_now, out, sk, outer, L, slots, inner, n);
-    else
-        hipLaunchKernelGGL(slot_noise_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t_now, out, sk, outer, L, slots, inner, n);
-    AVD_CHECK_LAUNCH("slot_noise");
-    return AVD_OK;
+// sample b at position (first + max(*cursor, 0) + b * stride) * slot_len, multiplied out
+static StreamMap stream_map(const SlotKey& k) {
+    return StreamMap{k.k0, k.k1, (uint64_t)k.first * (uint64_t)k.slot_len, (uint64_t)k.stride * (uint64_t)k.slot_len, (uint64_t)k.slot_len, k.cursor};
 }
 
 // ------------------------------------------------------------------ FIFO queue moves (diagonal denoising)
@@ -625,7 +569,7 @@ __device__ __forceinline__ QueueSrc queue_source(const QueueGeom& g, int kq, int
 }
 
 // The tracks of a move.  The latent track copies every position and draws the tail: the canvas-keyed normals of canvas positions
-// c * slot_len + j at timestep t (canvas_normal4 with window index c and hop slot_len, the bits of canvas_noise_kernel), under `seed`
+// c * slot_len + j at timestep t (canvas_normal4 with window index c and hop slot_len, the bits of avd_canvas_noise_f32), under `seed`
 // or the queue's own seeds[k], at clip slot c or c + *cursor (the cursor keys the draw, it addresses nothing).  The head of queue k
 // (window 0, slot ctx) goes to slot m of canvas k of `heads`, [K, outer, n_clip * slot_len, inner]; m by value or *cursor, compared with
 // [0, n_clip) before any address is formed.  The dense one-slot `popped` is n_clip = 1, m = 0, K = 1.  The cursor is only read here.
@@ -670,7 +614,8 @@ template <class T, int V> __device__ __forceinline__ QueueLane queue_lane(T idx,
     return QueueLane{(int)(row / outer), (int)(r % L), (int64_t)(row % outer), (int64_t)(idx % iv) * V};
 }
 
-// V lanes as canvas_noise_kernel, in the order idx -> (b, o, l, i).  Lanes [0, n_out) write the tracks, lanes [n_out, n_out + n_heads)
+// V == 4: inner % 4 == 0 and every base 16-byte aligned, a lane's float4 lies inside one (o, l) slice; V == 1: one element per lane.
+// Lanes in the order idx -> (b, o, l, i).  Lanes [0, n_out) write the tracks, lanes [n_out, n_out + n_heads)
 // the K heads of n_pop lanes each (n_heads == 0 at shift == 0 and without the latent track).  R riders; LATENT false is the carry:
 // the rider map alone.
 template <int V, int R, bool LATENT, class... Guide>
@@ -955,7 +900,7 @@ __global__ __launch_bounds__(256) void slot_tables_select_kernel(SlotTabs tb, co
 }
 
 // out[b, o, l, i] = canvas[o, (m + b * S) * hop + l, i] where that position is below P, else 0; m = max(*cursor, 0).  V lanes as
-// canvas_noise_kernel; every index is 64-bit.  n: B * outer * len * inner / V lanes.
+// fifo_move_kernel; every index is 64-bit.  n: B * outer * len * inner / V lanes.
 template <int V>
 __global__ __launch_bounds__(256) void fifo_prompt_gather_kernel(const float* __restrict__ canvas, float* __restrict__ out,
                                                                  const int32_t* __restrict__ cursor, int S, int64_t hop, int64_t outer,
@@ -1279,17 +1224,10 @@ int make_clip_guide(const avd_clip_guide* g, int B, int64_t outer, int L, int sl
                     std::initializer_list<const float*> outs, ClipGuideState& cg, const char* what = "clip_guide") {
     AVD_REQUIRE(g, AVD_EINVAL, "%s: null clip guide", what);
     AVD_REQUIRE(g->known, AVD_EINVAL, "%s: null known canvas", what);
-    AVD_REQUIRE(B > 0 && outer > 0 && L > 0 && inner > 0, AVD_EINVAL, "%s: bad dims (B %d, outer %lld, L %d, inner %lld)", what, B,
-                (long long)outer, L, (long long)inner);
-    const int64_t lim = (int64_t)1 << 32;
-    AVD_REQUIRE(g->P >= 1 && g->P <= lim, AVD_EINVAL, "%s: the clip guide's P %lld must lie in [1, 2^32]", what, (long long)g->P);
-    AVD_REQUIRE(outer <= (((int64_t)1 << 34) - 1) / inner, AVD_EINVAL, "%s: outer %lld * inner %lld must be < 2^34", what, (long long)outer,
-                (long long)inner);
-    AVD_REQUIRE(g->stride >= 1, AVD_EINVAL, "%s: the clip guide's stride must be >= 1 (got %d)", what, g->stride);
-    AVD_REQUIRE(g->first > -lim && g->first < lim, AVD_EINVAL, "%s: the clip guide's first %lld must lie in (-2^32, 2^32)", what,
-                (long long)g->first);
-    AVD_REQUIRE(slot_len >= 1 && slots >= 1 && (int64_t)slots * slot_len <= L && (int64_t)B * slots <= 0x7fffffff, AVD_EINVAL,
-                "%s: slots %d * slot_len %d must lie in [1, L %d] and B %d * slots fit an int", what, slots, slot_len, L, B);
+    if (int rc = check_keyed_dims(what, "B", B, outer, "L", L, inner)) return rc;
+    AVD_REQUIRE(g->P >= 1 && g->P <= (int64_t)1 << 32, AVD_EINVAL, "%s: the clip guide's P %lld must lie in [1, 2^32]", what, (long long)g->P);
+    if (int rc = check_clip_origin(what, "clip guide", g->stride, g->first)) return rc;
+    if (int rc = check_slots(what, B, L, slots, slot_len)) return rc;
     // every term of the position: |first| < 2^32, the cursor < 2^31, B * stride < 2^62, so the slot index stays below 2^62.1 only
     // when B * stride does; times slot_len plus l it must stay inside int64
     AVD_REQUIRE(((double)B * g->stride + 8.6e9) * (double)slot_len + (double)L < 9.0e18, AVD_EINVAL,
@@ -1316,7 +1254,7 @@ int check_clip_guide(const avd_clip_guide* g, int B, int64_t outer, int L, int s
 // The stand-alone pass (avd_clip_guide_slots_f32): out = blend(m(p), q_p(tau[b, s]), z) per slot.  A block lies inside one slot of one
 // (b, o) row — bpr blocks cover the longest row, the last slot's with the uncovered tail — so the slot's tau is block-uniform, and a
 // block whose slot is left (AVD_SLOT_LEAVE) returns before it loads anything when the call is in place, and copies z otherwise.
-// V lanes as canvas_noise_kernel.
+// V lanes as fifo_move_kernel.
 template <int V>
 __global__ __launch_bounds__(256) void clip_guide_slots_kernel(ClipGuideState cg, const int64_t* __restrict__ tau,
                                                                const float* __restrict__ abar, int T_train, const float* z, float* out,
@@ -1347,32 +1285,6 @@ __global__ __launch_bounds__(256) void clip_guide_slots_kernel(ClipGuideState cg
         if (!leave) v = clip_guide_apply1(cg, guide_coef(abar, T_train, t), b, o, l, i, inner, v);
         out[at] = v;
     }
-}
-
-int clip_guide_slots_f32(const avd_clip_guide* g, const int64_t* tau, const float* abar, int T_train, int everywhere, const float* z,
-                         float* out, int B, int64_t outer, int L, int slots, int slot_len, int64_t inner, hipStream_t st) {
-    ClipGuideState cg;
-    if (int rc = make_clip_guide(g, B, outer, L, slots, slot_len, inner, {out}, cg, "clip_guide_slots")) return rc;
-    AVD_REQUIRE(tau && abar && z && out && T_train > 0, AVD_EINVAL, "clip_guide_slots: null pointer or bad T_train");
-    const int64_t total = (int64_t)B * outer * L * inner;
-    AVD_REQUIRE(out == z || !overlaps(out, z, total), AVD_EINVAL, "clip_guide_slots: out must be z or not overlap it");
-    if (everywhere) cg.mask = nullptr;      // the mask reads as 1 on every in-canvas position
-    cg.vec = inner % 4 == 0 && aligned16(cg.known) && aligned16(cg.mask);
-    const bool vec = cg.vec && aligned16(z) && aligned16(out);
-    const int64_t row = (int64_t)(L - (slots - 1) * slot_len) * inner / (vec ? 4 : 1);      // lanes of the longest slot piece
-    const int64_t bpr = (row + 255) / 256, blocks = (int64_t)B * outer * slots * bpr;
-    AVD_REQUIRE(bpr <= 0x7fffffff && blocks <= 0x7fffffff, AVD_EUNSUPPORTED, "clip_guide_slots: %lld blocks are too many for one launch",
-                (long long)blocks);
-    static const int tags[2] = {prof_tag_id("clip_guide_slots_kernel<1>"), prof_tag_id("clip_guide_slots_kernel<4>")};
-    ProfScope prof(tags[vec ? 1 : 0], 4.0 * (double)total * 4, st);      // an upper bound: left slots move nothing
-    if (vec)
-        hipLaunchKernelGGL(clip_guide_slots_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, st, cg, tau, abar, T_train, z, out, outer, L,
-                           slots, inner, (int)bpr);
-    else
-        hipLaunchKernelGGL(clip_guide_slots_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, cg, tau, abar, T_train, z, out, outer, L,
-                           slots, inner, (int)bpr);
-    AVD_CHECK_LAUNCH("clip_guide_slots");
-    return AVD_OK;
 }
 
 // The guided FIFO queue shift (avd_fifo_shift_guided_f32; contract in include/avdiff_hip.h, "clip-keyed latent guide"):
@@ -1461,94 +1373,10 @@ int check_canvas_guide(const avd_latent_guide* g, int N, int64_t outer, int L, i
     return make_canvas_guide(g, N, outer, L, hop, inner, out, x0_hist, gs);
 }
 
-__global__ __launch_bounds__(256) void latent_guide_kernel(GuideState gs, const int64_t* __restrict__ tau, const float* __restrict__ abar,
-                                                           int T_train, const float* z, float* out, int64_t per, int64_t per4,
-                                                           int64_t total4) {      // z may be out (in place)
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total4) return;
-    const int b = (int)(i / per4);
-    const int64_t q4 = i % per4;
-    const GuideCoef gc = guide_coef(abar, T_train, tau[b]);
-    f32x4 n = {0.f, 0.f, 0.f, 0.f};
-    if (!gc.one) n = philox_normal4(gs.nk, (uint32_t)q4, gs.nk.s0 + (uint32_t)b, 0u, GUIDE_TAG);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int64_t el = q4 * 4 + k;
-        if (el >= per) break;
-        const int64_t j = (int64_t)b * per + el;
-        const float q = guide_q(gc, gs.known[j], n[k]);
-        out[j] = z ? guide_blend(gs.mask ? gs.mask[b * gs.mask_bstride + el] : 1.f, q, z[j]) : q;
-    }
-}
-
-int latent_guide_f32(const avd_latent_guide* g, const int64_t* tau, const float* abar, int T_train, const float* z, float* out, int B,
-                     int64_t per, hipStream_t st) {
-    GuideState gs;
-    if (int rc = make_guide(g, B, per, out, nullptr, gs)) return rc;
-    AVD_REQUIRE(tau && abar && out && T_train > 0, AVD_EINVAL, "latent_guide: null pointer or bad T_train");
-    const int64_t per4 = (per + 3) >> 2, total4 = (int64_t)B * per4;
-    AVD_REQUIRE((total4 + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "latent_guide: %lld values is too many for one launch",
-                (long long)B * per);
-    static const int tag = prof_tag_id("latent_guide_kernel");
-    ProfScope prof(tag, 4.0 * (double)B * per * (z ? 4 : 2), st);
-    hipLaunchKernelGGL(latent_guide_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, gs, tau, abar, T_train, z, out,
-                       per, per4, total4);
-    AVD_CHECK_LAUNCH("latent_guide");
-    return AVD_OK;
-}
-
-// The elementwise canvas-keyed guide.  V == 4: inner % 4 == 0 and every base 16-byte aligned, a lane's float4 lies inside one (o, l)
-// slice: one Philox call per four values.  V == 1: one call per element (every audio latent).  n: N * outer * L * inner / V lanes.
-// z == nullptr arrives with gs.mask == nullptr: blend(1, q, .) selects q.
-template <int V>
-__global__ __launch_bounds__(256) void canvas_latent_guide_kernel(CanvasGuideState gs, const int64_t* __restrict__ tau,
-                                                                  const float* __restrict__ abar, int T_train, const float* z, float* out,
-                                                                  int64_t outer, int L, int64_t inner, int64_t n) {      // z may be out
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n) return;
-    const int64_t iv = inner / V;
-    const int64_t i = (idx % iv) * V;
-    int64_t r = idx / iv;
-    const int l = (int)(r % L);
-    r /= L;
-    const int64_t o = r % outer;
-    const int b = (int)(r / outer);
-    const int64_t j = idx * V, el = j - (int64_t)b * outer * L * inner;
-    const GuideCoef gc = guide_coef(abar, T_train, tau[b]);
-    if constexpr (V == 4) {
-        const f32x4 zz = z ? *reinterpret_cast<const f32x4*>(z + j) : f32x4{0.f, 0.f, 0.f, 0.f};
-        *reinterpret_cast<f32x4*>(out + j) = canvas_guide_apply4(gs, gc, b, j, el, o, l, i, inner, zz);
-    } else {
-        out[j] = canvas_guide_apply1(gs, gc, b, j, el, o, l, i, inner, z ? z[j] : 0.f);
-    }
-}
-
-int latent_guide_canvas_f32(const avd_latent_guide* g, const int64_t* tau, const float* abar, int T_train, const float* z, float* out,
-                            int N, int64_t outer, int L, int hop, int64_t inner, hipStream_t st) {
-    CanvasGuideState gs;
-    if (int rc = make_canvas_guide(g, N, outer, L, hop, inner, out, nullptr, gs)) return rc;
-    AVD_REQUIRE(tau && abar && out && T_train > 0, AVD_EINVAL, "latent_guide_canvas: null pointer or bad T_train");
-    if (!z) gs.mask = nullptr;      // pure forward noising: the mask reads as 1 everywhere
-    const bool vec = inner % 4 == 0 && aligned16(out) && aligned16(z);
-    AVD_REQUIRE((double)N * (double)outer * (double)L * (double)inner < 9.0e18, AVD_EUNSUPPORTED, "latent_guide_canvas: too many values");
-    const int64_t n = (int64_t)N * outer * L * inner / (vec ? 4 : 1);
-    AVD_REQUIRE((n + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "latent_guide_canvas: %lld lanes are too many for one launch", (long long)n);
-    static const int tags[2] = {prof_tag_id("canvas_latent_guide_kernel<1>"), prof_tag_id("canvas_latent_guide_kernel<4>")};
-    ProfScope prof(tags[vec ? 1 : 0], 4.0 * (double)n * (vec ? 4 : 1) * (z ? 4 : 2), st);
-    if (vec)
-        hipLaunchKernelGGL(canvas_latent_guide_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gs, tau, abar, T_train, z,
-                           out, outer, L, inner, n);
-    else
-        hipLaunchKernelGGL(canvas_latent_guide_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gs, tau, abar, T_train, z,
-                           out, outer, L, inner, n);
-    AVD_CHECK_LAUNCH("latent_guide_canvas");
-    return AVD_OK;
-}
-
 // ------------------------------------------------------------------ renoise (RePaint resampling: the forward jump t_from -> t_to)
 // The contract is written out in include/avdiff_hip.h ("renoise").  Per sample b, with a_f = a(t_from[b]) and a_t = a(t_to[b]):
 //   !(a_t < a_f): out = z, no arithmetic and no generator call;  else rho = a_t / a_f, out = sqrt(rho) z + sqrt(max(1 - rho, 0)) n_r,
-//   n_r = philox_normal4 at counter (e >> 2, s, visit, RENOISE_TAG) — or its canvas keying (canvas_normal4) — fresh per visit;
+//   n_r = philox_normal4 at counter (e >> 2, s, visit, RENOISE_TAG) — or its canvas keying (the StreamMap's) — fresh per visit;
 //   with a guide the launch ends in blend(mask, q(t_to[b]), out): guide_coef / guide_q / guide_blend, as every guided kernel.
 constexpr uint32_t RENOISE_TAG = 0x52504E31u;   // "RPN1"
 
@@ -1569,119 +1397,315 @@ __device__ __forceinline__ float renoise_apply(const RenoiseCoef& c, float z, fl
     return c.same ? z : c.A * z + c.S * n;
 }
 
-// gs.known == nullptr: no guide.  Lanes as latent_guide_kernel: four consecutive elements of one sample, the tail lane fewer.
-__global__ __launch_bounds__(256) void renoise_kernel(NoiseKey nk, uint32_t visit, GuideState gs, const int64_t* __restrict__ t_from,
-                                                      const int64_t* __restrict__ t_to, const float* __restrict__ abar, int T_train,
-                                                      const float* z, float* out, int64_t per, int64_t per4,
-                                                      int64_t total4) {      // z may be out (in place)
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total4) return;
-    const int b = (int)(i / per4);
-    const int64_t q4 = i % per4;
-    const RenoiseCoef rc = renoise_coef(abar, T_train, t_from[b], t_to[b]);
-    f32x4 n = {0.f, 0.f, 0.f, 0.f}, nk4 = {0.f, 0.f, 0.f, 0.f};
-    if (!rc.same) n = philox_normal4(nk, (uint32_t)q4, nk.s0 + (uint32_t)b, visit, RENOISE_TAG);
-    GuideCoef gc = {1.f, 0.f, true};
-    if (gs.known) {
-        gc = guide_coef(abar, T_train, t_to[b]);
-        if (!gc.one) nk4 = philox_normal4(gs.nk, (uint32_t)q4, gs.nk.s0 + (uint32_t)b, 0u, GUIDE_TAG);
-    }
+// ------------------------------------------------------------------ the stream's stand-alone passes
+// The eight elementwise entries of the stream (avd_gaussian_noise_f32, avd_canvas_noise_f32, avd_slot_noise_f32, avd_latent_guide_f32 /
+// _canvas_f32, avd_renoise_f32 / _canvas_f32, avd_clip_guide_slots_f32; contracts in include/avdiff_hip.h) are one descriptor, one check
+// function and one launch function.  All but the last run on one lane loop over [B, outer, L, inner] with a StreamMap per stream; the
+// per-sample entries are the batch [B, 1, 1, per] under stream_map(NoiseKey).  A lane takes one of three forms:
+//   Float4    inner % 4 == 0 and every base 16-byte aligned: the lane's float4 lies inside one (o, l) slice, one Philox call per four;
+//   Guarded4  four elements of one slice by scalar access, the slice's last lane fewer: where inner % 4 == 0 but a base is unaligned,
+//             and where outer == 1 (so e' = i and a lane's four elements share a call whatever inner is);
+//   One       one Philox call per element: everything else, which is every audio latent (inner == 1).
+enum class Lanes { One, Guarded4, Float4 };
+template <Lanes F> constexpr int lane_width = F == Lanes::One ? 1 : 4;
+
+// n: the lane's elements (lane_width, or fewer on a Guarded4 tail)
+template <Lanes F> __device__ __forceinline__ f32x4 lane_load(const float* p, int n) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (F == Lanes::Float4) v = *reinterpret_cast<const f32x4*>(p);
+    else
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int64_t el = q4 * 4 + k;
-        if (el >= per) break;
-        const int64_t j = (int64_t)b * per + el;
-        float v = renoise_apply(rc, z[j], n[k]);
-        if (gs.known) v = guide_blend(gs.mask ? gs.mask[b * gs.mask_bstride + el] : 1.f, guide_q(gc, gs.known[j], nk4[k]), v);
-        out[j] = v;
-    }
+        for (int k = 0; k < lane_width<F>; ++k)
+            if (k < n) v[k] = p[k];
+    return v;
+}
+template <Lanes F> __device__ __forceinline__ void lane_store(float* p, f32x4 v, int n) {
+    if constexpr (F == Lanes::Float4) *reinterpret_cast<f32x4*>(p) = v;
+    else
+#pragma unroll
+        for (int k = 0; k < lane_width<F>; ++k)
+            if (k < n) p[k] = v[k];
 }
 
-int renoise_f32(const avd_noise_key* key, uint32_t visit, const avd_latent_guide* g, const int64_t* t_from, const int64_t* t_to,
-                const float* abar, int T_train, const float* z, float* out, int B, int64_t per, hipStream_t st) {
-    NoiseKey nk;
-    if (int rc = make_noise_key(key, B, nk)) return rc;
-    AVD_REQUIRE(t_from && t_to && abar && z && out && T_train > 0, AVD_EINVAL, "renoise: null pointer or bad T_train");
-    AVD_REQUIRE(per > 0 && per < ((int64_t)1 << 34), AVD_EINVAL, "renoise: per_sample %lld must be in [1, 2^34)", (long long)per);
-    AVD_REQUIRE(out == z || !overlaps(out, z, (int64_t)B * per), AVD_EINVAL, "renoise: out must be z or not overlap it");
-    GuideState gs{};
-    if (g)
-        if (int rc = make_guide(g, B, per, out, nullptr, gs)) return rc;
-    const int64_t per4 = (per + 3) >> 2, total4 = (int64_t)B * per4;
-    AVD_REQUIRE((total4 + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "renoise: %lld values is too many for one launch",
-                (long long)B * per);
-    static const int tag = prof_tag_id("renoise_kernel");
-    ProfScope prof(tag, 4.0 * (double)B * per * (g ? 4 : 2), st);
-    hipLaunchKernelGGL(renoise_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, nk, visit, gs, t_from, t_to, abar,
-                       T_train, z, out, per, per4, total4);
-    AVD_CHECK_LAUNCH("renoise");
+struct PassDims {
+    int64_t outer, inner, per;      // per = outer * L * inner
+    int L, S, slot_len;             // the time tables are [B, S], position l in slot min(l / slot_len, S - 1)
+};
+struct PassLane {
+    int b, l, n;                    // n: as lane_load
+    int64_t o, i, at;               // at: the element offset of (b, o, l, i)
+};
+// the lane's four normals in element order; a One lane keeps the one its element takes
+template <Lanes F>
+__device__ __forceinline__ f32x4 lane_normal4(const StreamMap& m, const PassDims& d, const PassLane& ln, uint32_t t, uint32_t tag) {
+    f32x4 v = stream_normal4(m, ln.b, ln.o, ln.l, ln.i, d.inner, t, tag);
+    if constexpr (F == Lanes::One) v[0] = v[(int)((ln.o * d.inner + ln.i) & 3)];
+    return v;
+}
+
+// the draw: out = n at the time word of the position's slot
+struct DrawBody {
+    const int64_t* t_now;           // [B, S]
+    float* out;
+    StreamMap map;
+    uint32_t tag;
+    template <Lanes F, bool> __device__ __forceinline__ void lane(const PassDims& d, const PassLane& ln) const {
+        int s = 0;
+        if (d.S > 1) {
+            s = ln.l / d.slot_len;
+            if (s > d.S - 1) s = d.S - 1;
+        }
+        lane_store<F>(out + ln.at, lane_normal4<F>(map, d, ln, (uint32_t)t_now[(int64_t)ln.b * d.S + s], tag), ln.n);
+    }
+};
+
+// the blend: v = renoise_apply(renoise_coef(t_from, t_to), z, n_r), then under a guide (known != nullptr) blend(m, q(t_to), v).  The
+// latent guide is the jump t_from == t_to, where renoise_coef gives `same`, v = z and nothing is drawn: RENOISE false says so at
+// compile time, which keeps the guide's launches at their cost (profiles/stream_pass_kernels.txt).  z == nullptr (the guide's pure
+// forward noising) arrives with mask == nullptr: v = 0 and blend(1, q, .) selects q.  z may be out (in place).
+struct BlendBody {
+    const int64_t *t_from, *t_to;   // [B]; RENOISE false: t_to alone, the guide's tau
+    const float* abar;
+    int T_train;
+    const float* z;
+    float* out;
+    StreamMap rmap;                 // the renoise stream
+    uint32_t visit;
+    const float *known, *mask;      // mask: [per] (mask_bstride 0) or the batch's; nullptr = 1 everywhere
+    int64_t mask_bstride;
+    StreamMap gmap;                 // the guide's known noise
+    template <Lanes F, bool RENOISE> __device__ __forceinline__ void lane(const PassDims& d, const PassLane& ln) const {
+        f32x4 v = z ? lane_load<F>(z + ln.at, ln.n) : f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (RENOISE) {
+            const RenoiseCoef rc = renoise_coef(abar, T_train, t_from[ln.b], t_to[ln.b]);
+            f32x4 nr = {0.f, 0.f, 0.f, 0.f};
+            if (!rc.same) nr = lane_normal4<F>(rmap, d, ln, visit, RENOISE_TAG);
+#pragma unroll
+            for (int k = 0; k < lane_width<F>; ++k) v[k] = renoise_apply(rc, v[k], nr[k]);
+        }
+        if (known) {
+            const GuideCoef gc = guide_coef(abar, T_train, t_to[ln.b]);
+            f32x4 nk = {0.f, 0.f, 0.f, 0.f}, m = {1.f, 1.f, 1.f, 1.f};
+            if (!gc.one) nk = lane_normal4<F>(gmap, d, ln, 0u, GUIDE_TAG);
+            if (mask) m = lane_load<F>(mask + ln.b * mask_bstride + (ln.at - ln.b * d.per), ln.n);
+            const f32x4 xk = lane_load<F>(known + ln.at, ln.n);
+#pragma unroll
+            for (int k = 0; k < lane_width<F>; ++k) v[k] = guide_blend(m[k], guide_q(gc, xk[k], nk[k]), v[k]);
+        }
+        lane_store<F>(out + ln.at, v, ln.n);
+    }
+};
+
+// The lane loop: lane idx -> (b, o, l, i) of [B, outer, L, ceil(inner / width)], queue_lane's arithmetic (32-bit below 2^32 lanes).
+// n: the launch's lanes.  RENOISE: the blend's renoise half (false: the guide alone).
+template <Lanes F, class Body, bool RENOISE = true>
+__global__ __launch_bounds__(256) void stream_pass_kernel(Body body, PassDims d, int64_t n) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    constexpr int V = lane_width<F>;
+    const int64_t iv = (d.inner + V - 1) / V;
+    const bool narrow = n <= 0xffffffffll;
+    const QueueLane q = narrow ? queue_lane<uint32_t, V>((uint32_t)idx, (uint32_t)iv, (uint32_t)d.L, (uint32_t)d.outer)
+                               : queue_lane<int64_t, V>(idx, iv, (int64_t)d.L, d.outer);
+    PassLane ln{q.b, q.l, V, q.o, q.i, idx * V};
+    if constexpr (F == Lanes::Guarded4) {
+        const int64_t slice = narrow ? (int64_t)((uint32_t)idx / (uint32_t)iv) : idx / iv;
+        ln.at = slice * d.inner + q.i;
+        if (d.inner - q.i < 4) ln.n = (int)(d.inner - q.i);
+    }
+    body.template lane<F, RENOISE>(d, ln);
+}
+
+// What an entry asks of stream_pass.  Every check is made in stream_pass_check, before any HIP call.
+enum class Keying { Sample, Canvas, Clip };
+enum class Pass { Draw, Guide, Renoise, ClipSlots };      // Guide and Renoise are the blend, without and with a stream of its own
+struct StreamPass {
+    const char *what, *key_what;      // the entry's prefix in messages; its keying's (make_canvas_key, make_slot_key)
+    const char* label;                // the profile label, which names the entry's form; label_lanes: "<4>" (Float4) or "<1>" follows
+    bool label_lanes;
+    Keying keying;
+    Pass kind;
+    int B, L;                         // the batch [B, outer, L, inner]; the per-sample entries are [B, 1, 1, per]
+    int64_t outer, inner;
+    int hop, slots, slot_len;         // Canvas: hop.  Clip: the [B, slots] tables
+    const void* key;                  // Draw, Renoise: the pass's own stream, an avd_noise_key or (Clip) an avd_slot_key
+    uint32_t word;                    // Draw: the domain word.  Renoise: the visit
+    const void* guide;                // an avd_latent_guide (Guide; Renoise: or null) or (ClipSlots) an avd_clip_guide
+    int everywhere, T_train;
+    const int64_t *t_from, *t_to;     // the draw's t_now is t_to; a guide's tau is both
+    const float *abar, *z;            // z: may be null under Guide
+    float* out;
+};
+// what the checks leave for the launch
+struct PassPlan {
+    PassDims d;
+    DrawBody draw;
+    BlendBody blend;
+    ClipGuideState cg;
+    Lanes lanes;
+    int64_t n;                        // lanes; ClipSlots: blocks
+    int bpr;
+    double bytes;                     // what the entry tells the profile it moves
+};
+
+int stream_pass_check(const StreamPass& d, PassPlan& p) {
+    const char* w = d.what;
+    const bool draw = d.kind == Pass::Draw, clip = d.kind == Pass::ClipSlots;
+    const bool keyed = draw || d.kind == Pass::Renoise;      // the pass draws a stream of its own
+    const avd_latent_guide* g = clip ? nullptr : static_cast<const avd_latent_guide*>(d.guide);
+    p = PassPlan{};
+    StreamMap map{}, gmap{};
+    const float *known = nullptr, *mask = nullptr;
+    if (keyed && d.keying == Keying::Sample) {
+        NoiseKey nk;
+        if (int rc = make_noise_key(static_cast<const avd_noise_key*>(d.key), d.B, nk)) return rc;
+        map = stream_map(nk);
+    } else if (keyed && d.keying == Keying::Canvas) {
+        CanvasKey ck;
+        if (int rc = make_canvas_key(static_cast<const avd_noise_key*>(d.key), d.B, d.outer, d.L, d.hop, d.inner, ck, d.key_what)) return rc;
+        AVD_REQUIRE(draw || (double)d.outer * (double)d.L * (double)d.inner < 17179869184.0, AVD_EINVAL,
+                    "%s: a window of outer %lld * L %d * inner %lld values must hold < 2^34", d.key_what, (long long)d.outer, d.L,
+                    (long long)d.inner);
+        map = stream_map(ck);
+    } else if (keyed) {
+        SlotKey sk;
+        if (int rc = make_slot_key(static_cast<const avd_slot_key*>(d.key), d.B, d.outer, d.slot_len, d.inner, sk, d.key_what)) return rc;
+        map = stream_map(sk);
+    }
+    // the guide's checks come first in a pass of the guide alone, and behind the pass's own otherwise
+    auto guide = [&]() -> int {
+        if (clip)
+            return make_clip_guide(static_cast<const avd_clip_guide*>(d.guide), d.B, d.outer, d.L, d.slots, d.slot_len, d.inner, {d.out}, p.cg, w);
+        if (keyed && !g) return AVD_OK;
+        if (d.keying == Keying::Sample) {
+            if (int rc = check_latent_guide(g, d.B, d.inner, d.out, nullptr)) return rc;
+            NoiseKey nk;
+            if (int rc = make_noise_key(&g->key, d.B, nk)) return rc;
+            gmap = stream_map(nk);
+        } else {
+            CanvasGuideState gs;
+            if (int rc = make_canvas_guide(g, d.B, d.outer, d.L, d.hop, d.inner, d.out, nullptr, gs)) return rc;
+            gmap = stream_map(gs.ck);
+        }
+        known = g->known;
+        mask = d.z ? g->mask : nullptr;      // pure forward noising: the mask reads as 1 everywhere
+        return AVD_OK;
+    };
+    if (!keyed)
+        if (int rc = guide()) return rc;
+    if (draw)
+        AVD_REQUIRE(d.t_to && d.out, AVD_EINVAL, "%s: null pointer", w);
+    else
+        AVD_REQUIRE(d.t_from && d.t_to && d.abar && d.out && (d.z || d.kind == Pass::Guide) && d.T_train > 0, AVD_EINVAL,
+                    "%s: null pointer or bad T_train", w);
+    if (keyed && d.keying == Keying::Sample)
+        AVD_REQUIRE(d.inner > 0 && d.inner < ((int64_t)1 << 34), AVD_EINVAL, "%s: per_sample %lld must be in [1, 2^34)", w, (long long)d.inner);
+    if (draw && d.keying == Keying::Clip)
+        if (int rc = check_slots(w, d.B, d.L, d.slots, d.slot_len)) return rc;
+    AVD_REQUIRE((double)d.B * (double)d.outer * (double)d.L * (double)d.inner < 9.0e18, AVD_EUNSUPPORTED, "%s: too many values", w);
+    const int64_t total = (int64_t)d.B * d.outer * d.L * d.inner;
+    AVD_REQUIRE(draw || d.kind == Pass::Guide || d.out == d.z || !overlaps(d.out, d.z, total), AVD_EINVAL,
+                "%s: out must be z or not overlap it", w);      // the guide entries' contract asks it of known / mask alone
+    if (keyed)
+        if (int rc = guide()) return rc;
+    const bool tables = d.keying == Keying::Clip;
+    p.d = PassDims{d.outer, d.inner, d.outer * d.L * d.inner, d.L, tables ? d.slots : 1, tables ? d.slot_len : 1};
+    if (clip) {
+        if (d.everywhere) p.cg.mask = nullptr;      // the mask reads as 1 on every in-canvas position
+        p.cg.vec = d.inner % 4 == 0 && aligned16(p.cg.known) && aligned16(p.cg.mask);
+        const bool vec = p.cg.vec && aligned16(d.z) && aligned16(d.out);
+        p.lanes = vec ? Lanes::Float4 : Lanes::One;
+        const int64_t row = (int64_t)(d.L - (d.slots - 1) * d.slot_len) * d.inner / (vec ? 4 : 1);      // lanes of the longest slot piece
+        const int64_t bpr = (row + 255) / 256;
+        p.n = (int64_t)d.B * d.outer * d.slots * bpr;
+        AVD_REQUIRE(bpr <= 0x7fffffff && p.n <= 0x7fffffff, AVD_EUNSUPPORTED, "%s: %lld blocks are too many for one launch", w, (long long)p.n);
+        p.bpr = (int)bpr;
+        p.bytes = 4.0 * (double)total * 4;      // an upper bound: left slots move nothing
+        return AVD_OK;
+    }
+    const bool aligned = aligned16(d.out) && aligned16(d.z) && aligned16(known) && aligned16(mask);
+    p.lanes = d.inner % 4 == 0 ? (aligned ? Lanes::Float4 : Lanes::Guarded4) : (d.outer == 1 && d.inner > 1 ? Lanes::Guarded4 : Lanes::One);
+    const int v = p.lanes == Lanes::One ? 1 : 4;
+    p.n = total / d.inner * ((d.inner + v - 1) / v);
+    AVD_REQUIRE((p.n + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "%s: %lld lanes are too many for one launch", w, (long long)p.n);
+    p.draw = DrawBody{d.t_to, d.out, map, d.word};
+    p.blend = BlendBody{d.t_from, d.t_to, d.abar, d.T_train, d.z, d.out, map, d.word, known, mask, known ? g->mask_batch_stride : 0, gmap};
+    p.bytes = 4.0 * (double)total * (draw ? 1 : (keyed ? g != nullptr : d.z != nullptr) ? 4 : 2);
     return AVD_OK;
 }
 
-// The canvas-keyed renoise; V lanes as canvas_latent_guide_kernel.  gs.known == nullptr: no guide.
-template <int V>
-__global__ __launch_bounds__(256) void canvas_renoise_kernel(CanvasKey ck, uint32_t visit, CanvasGuideState gs,
-                                                             const int64_t* __restrict__ t_from, const int64_t* __restrict__ t_to,
-                                                             const float* __restrict__ abar, int T_train, const float* z, float* out,
-                                                             int64_t outer, int L, int64_t inner, int64_t n) {      // z may be out
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n) return;
-    const int64_t iv = inner / V;
-    const int64_t i = (idx % iv) * V;
-    int64_t r = idx / iv;
-    const int l = (int)(r % L);
-    r /= L;
-    const int64_t o = r % outer;
-    const int b = (int)(r / outer);
-    const int64_t j = idx * V, el = j - (int64_t)b * outer * L * inner;
-    const RenoiseCoef rc = renoise_coef(abar, T_train, t_from[b], t_to[b]);
-    f32x4 nr = {0.f, 0.f, 0.f, 0.f};
-    if (!rc.same) nr = canvas_normal4(ck, b, o, l, i, inner, visit, RENOISE_TAG);
-    if constexpr (V == 4) {
-        const f32x4 zz = *reinterpret_cast<const f32x4*>(z + j);
-        f32x4 v;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = renoise_apply(rc, zz[k], nr[k]);
-        if (gs.known) v = canvas_guide_apply4(gs, guide_coef(abar, T_train, t_to[b]), b, j, el, o, l, i, inner, v);
-        *reinterpret_cast<f32x4*>(out + j) = v;
-    } else {
-        float v = renoise_apply(rc, z[j], nr[(int)((o * inner + i) & 3)]);
-        if (gs.known) v = canvas_guide_apply1(gs, guide_coef(abar, T_train, t_to[b]), b, j, el, o, l, i, inner, v);
-        out[j] = v;
-    }
+int stream_pass_launch(const StreamPass& d, const PassPlan& p, hipStream_t st) {
+    const int v = p.lanes == Lanes::Float4 ? 4 : 1;
+    ProfScope prof(g_prof_on ? (d.label_lanes ? prof_tag_id("%s<%d>", d.label, v) : prof_tag_id("%s", d.label)) : 0, p.bytes, st);
+    const dim3 grid((unsigned)((p.n + 255) / 256));
+    if (d.kind == Pass::ClipSlots)
+        with_int<1, 4>(v, [&](auto V) {
+            hipLaunchKernelGGL(clip_guide_slots_kernel<decltype(V)::value>, dim3((unsigned)p.n), dim3(256), 0, st, p.cg, d.t_to, d.abar,
+                               d.T_train, d.z, d.out, d.outer, d.L, d.slots, d.inner, p.bpr);
+        });
+    else
+        with_int<(int)Lanes::One, (int)Lanes::Guarded4, (int)Lanes::Float4>((int)p.lanes, [&](auto F) {
+            constexpr Lanes f = (Lanes) decltype(F)::value;
+            if (d.kind == Pass::Draw)
+                hipLaunchKernelGGL((stream_pass_kernel<f, DrawBody>), grid, dim3(256), 0, st, p.draw, p.d, p.n);
+            else if (d.kind == Pass::Renoise)
+                hipLaunchKernelGGL((stream_pass_kernel<f, BlendBody>), grid, dim3(256), 0, st, p.blend, p.d, p.n);
+            else
+                hipLaunchKernelGGL((stream_pass_kernel<f, BlendBody, false>), grid, dim3(256), 0, st, p.blend, p.d, p.n);
+        });
+    AVD_CHECK_LAUNCH(d.what);
+    return AVD_OK;
 }
 
+int stream_pass(const StreamPass& d, hipStream_t st) {
+    PassPlan plan;
+    if (int rc = stream_pass_check(d, plan)) return rc;
+    return stream_pass_launch(d, plan, st);
+}
+
+int gaussian_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int B, int64_t per, hipStream_t st) {
+    return stream_pass(StreamPass{"gaussian_noise", "", "gaussian_noise_kernel", false, Keying::Sample, Pass::Draw, B, 1, 1, per, 0, 0, 0, key,
+                                  0x44444D31u, nullptr, 0, 0, nullptr, t_now, nullptr, nullptr, out}, st);
+}
+int canvas_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out, int N, int64_t outer, int L, int hop, int64_t inner,
+                     hipStream_t st) {
+    return stream_pass(StreamPass{"canvas_noise", "canvas noise", "canvas_noise_kernel", true, Keying::Canvas, Pass::Draw, N, L, outer, inner,
+                                  hop, 0, 0, key, 0x44444D31u, nullptr, 0, 0, nullptr, t_now, nullptr, nullptr, out}, st);
+}
+int slot_noise_f32(const avd_slot_key* key, const int64_t* t_now, float* out, int B, int64_t outer, int L, int slots, int slot_len,
+                   int64_t inner, hipStream_t st) {
+    return stream_pass(StreamPass{"slot_noise", "slot noise", "slot_noise_kernel", true, Keying::Clip, Pass::Draw, B, L, outer, inner, 0, slots,
+                                  slot_len, key, SLOT_TAG, nullptr, 0, 0, nullptr, t_now, nullptr, nullptr, out}, st);
+}
+int latent_guide_f32(const avd_latent_guide* g, const int64_t* tau, const float* abar, int T_train, const float* z, float* out, int B,
+                     int64_t per, hipStream_t st) {
+    return stream_pass(StreamPass{"latent_guide", "", "latent_guide_kernel", false, Keying::Sample, Pass::Guide, B, 1, 1, per, 0, 0, 0, nullptr,
+                                  0, g, 0, T_train, tau, tau, abar, z, out}, st);
+}
+int latent_guide_canvas_f32(const avd_latent_guide* g, const int64_t* tau, const float* abar, int T_train, const float* z, float* out,
+                            int N, int64_t outer, int L, int hop, int64_t inner, hipStream_t st) {
+    return stream_pass(StreamPass{"latent_guide_canvas", "canvas guide", "canvas_latent_guide_kernel", true, Keying::Canvas, Pass::Guide, N,
+                                  L, outer, inner, hop, 0, 0, nullptr, 0, g, 0, T_train, tau, tau, abar, z, out}, st);
+}
+int renoise_f32(const avd_noise_key* key, uint32_t visit, const avd_latent_guide* g, const int64_t* t_from, const int64_t* t_to,
+                const float* abar, int T_train, const float* z, float* out, int B, int64_t per, hipStream_t st) {
+    return stream_pass(StreamPass{"renoise", "", "renoise_kernel", false, Keying::Sample, Pass::Renoise, B, 1, 1, per, 0, 0, 0, key, visit, g, 0,
+                                  T_train, t_from, t_to, abar, z, out}, st);
+}
 int renoise_canvas_f32(const avd_noise_key* key, uint32_t visit, const avd_latent_guide* g, const int64_t* t_from, const int64_t* t_to,
                        const float* abar, int T_train, const float* z, float* out, int N, int64_t outer, int L, int hop, int64_t inner,
                        hipStream_t st) {
-    CanvasKey ck;
-    if (int rc = make_canvas_key(key, N, outer, L, hop, inner, ck, "canvas renoise")) return rc;
-    AVD_REQUIRE((double)outer * (double)L * (double)inner < 17179869184.0, AVD_EINVAL,
-                "canvas renoise: a window of outer %lld * L %d * inner %lld values must hold < 2^34", (long long)outer, L, (long long)inner);
-    AVD_REQUIRE(t_from && t_to && abar && z && out && T_train > 0, AVD_EINVAL, "renoise_canvas: null pointer or bad T_train");
-    AVD_REQUIRE((double)N * (double)outer * (double)L * (double)inner < 9.0e18, AVD_EUNSUPPORTED, "renoise_canvas: too many values");
-    const int64_t total = (int64_t)N * outer * L * inner;
-    AVD_REQUIRE(out == z || !overlaps(out, z, total), AVD_EINVAL, "renoise_canvas: out must be z or not overlap it");
-    CanvasGuideState gs{};
-    if (g) {
-        AVD_REQUIRE(g->key.sample_offset == key->sample_offset, AVD_EINVAL,
-                    "renoise_canvas: the guide's key and the renoise key must carry the same sample_offset (got %lld and %lld)",
-                    (long long)g->key.sample_offset, (long long)key->sample_offset);
-        if (int rc = make_canvas_guide(g, N, outer, L, hop, inner, out, nullptr, gs)) return rc;
-    }
-    const bool vec = inner % 4 == 0 && aligned16(out) && aligned16(z);
-    const int64_t n = total / (vec ? 4 : 1);
-    AVD_REQUIRE((n + 255) / 256 <= 0x7fffffff, AVD_EUNSUPPORTED, "renoise_canvas: %lld lanes are too many for one launch", (long long)n);
-    static const int tags[2] = {prof_tag_id("canvas_renoise_kernel<1>"), prof_tag_id("canvas_renoise_kernel<4>")};
-    ProfScope prof(tags[vec ? 1 : 0], 4.0 * (double)total * (g ? 4 : 2), st);
-    if (vec)
-        hipLaunchKernelGGL(canvas_renoise_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ck, visit, gs, t_from, t_to, abar,
-                           T_train, z, out, outer, L, inner, n);
-    else
-        hipLaunchKernelGGL(canvas_renoise_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ck, visit, gs, t_from, t_to, abar,
-                           T_train, z, out, outer, L, inner, n);
-    AVD_CHECK_LAUNCH("renoise_canvas");
-    return AVD_OK;
+    // the two maps of this entry share their base: its own check (a null key is stream_pass_check's to report)
+    AVD_REQUIRE(!g || !key || g->key.sample_offset == key->sample_offset, AVD_EINVAL,
+                "renoise_canvas: the guide's key and the renoise key must carry the same sample_offset (got %lld and %lld)",
+                g ? (long long)g->key.sample_offset : 0ll, key ? (long long)key->sample_offset : 0ll);
+    return stream_pass(StreamPass{"renoise_canvas", "canvas renoise", "canvas_renoise_kernel", true, Keying::Canvas, Pass::Renoise, N, L, outer,
+                                  inner, hop, 0, 0, key, visit, g, 0, T_train, t_from, t_to, abar, z, out}, st);
+}
+int clip_guide_slots_f32(const avd_clip_guide* g, const int64_t* tau, const float* abar, int T_train, int everywhere, const float* z,
+                         float* out, int B, int64_t outer, int L, int slots, int slot_len, int64_t inner, hipStream_t st) {
+    return stream_pass(StreamPass{"clip_guide_slots", "", "clip_guide_slots_kernel", true, Keying::Clip, Pass::ClipSlots, B, L, outer, inner, 0,
+                                  slots, slot_len, nullptr, 0, g, everywhere, T_train, tau, tau, abar, z, out}, st);
 }
 
 // ------------------------------------------------------------------ CFG control: per-sample guidance, guidance rescale

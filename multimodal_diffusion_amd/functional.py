@@ -256,6 +256,39 @@ def dpmpp_2m_sde_step(x_t: Tensor, eps_hat: Tensor, x0_hist: Tensor, t_last: Ten
     return out
 
 
+def _alpha_bar(alpha_bar: Tensor, dev: torch.device) -> Tensor:
+    """the alpha_bar table as a contiguous float32 tensor on ``dev``"""
+    ab = alpha_bar if (alpha_bar.is_cuda and alpha_bar.dtype == torch.float32) else alpha_bar.to(dev, torch.float32)
+    return ab.contiguous()
+
+
+def _positive_shape(shape, what: str = "shape must have positive sizes") -> tuple:
+    shape = tuple(int(s) for s in shape)
+    if len(shape) < 1 or any(s < 1 for s in shape):
+        raise ValueError(f"{what}, got {shape}")
+    return shape
+
+
+def _check_out(out: Optional[Tensor], shape: tuple, z: Optional[Tensor] = None) -> None:
+    """an ``out`` to fill: None, or a contiguous float32 device tensor of ``shape``, on z's device where the pass reads a ``z``"""
+    ok = out is None or (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == tuple(shape))
+    if z is not None and not (ok and (out is None or out.device == z.device)):
+        raise ValueError(f"out must be a contiguous float32 tensor of shape {tuple(shape)} on z's device")
+    if not ok:
+        raise ValueError(f"out must be a contiguous float32 device tensor of shape {tuple(shape)}")
+
+
+def _slot_table(t: Tensor, name: str, B: int, L_: int, slot_len) -> tuple:
+    """(table, S): an int [B, S] table whose S slots of ``slot_len`` positions fit the sliding length ``L_``"""
+    t = torch.as_tensor(t)
+    if t.dim() != 2 or t.shape[0] != B or t.is_floating_point() or t.dtype == torch.bool:
+        raise ValueError(f"{name} must be an int [B, S] table with B = {B}, got {t.dtype} {tuple(t.shape)}")
+    S = int(t.shape[1])
+    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or S < 1 or S * slot_len > L_:
+        raise ValueError(f"S = {S} slots of slot_len {slot_len!r} must fit the sliding length {L_}")
+    return t, S
+
+
 def noise_key(seed: int, sample_offset: int = 0) -> "L.NoiseKey":
     """avd_noise_key after the checks the engine and gaussian_noise share: 0 <= seed < 2**64, sample_offset >= 0."""
     if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
@@ -316,16 +349,19 @@ def latent_guide(known: Tensor, tau: Tensor, alpha_bar: Tensor, z: Optional[Tens
         zz = L.dev_f32(z, "z").contiguous()
         if zz.shape != known.shape:
             raise ValueError(f"z shape {tuple(zz.shape)} != known shape {tuple(known.shape)}")
-    ab = alpha_bar if (alpha_bar.is_cuda and alpha_bar.dtype == torch.float32) else alpha_bar.to(dev, torch.float32)
-    ab = ab.contiguous()
-    out = torch.empty_like(known)
+    return latent_guide_launch(g, canvas_hop, tn, _alpha_bar(alpha_bar, dev), zz, torch.empty_like(known))
+
+
+def latent_guide_launch(g: "L.LatentGuide", canvas_hop: Optional[int], tau: Tensor, ab: Tensor, z: Optional[Tensor], out: Tensor) -> Tensor:
+    """avd_latent_guide_f32 (``canvas_hop`` None) or avd_latent_guide_canvas_f32 on checked device tensors: ``tau`` int64 [B], ``ab``
+    the float32 alpha_bar table, ``z`` None or of out's shape.  Fills and returns ``out``."""
+    B = out.shape[0]
+    args = (C.byref(g), tau.data_ptr(), ab.data_ptr(), ab.numel(), L.ptr(z), out.data_ptr(), B)
     if canvas_hop is None:
-        L.check(L.lib().avd_latent_guide_f32(C.byref(g), tn.data_ptr(), ab.data_ptr(), ab.numel(), L.ptr(zz), out.data_ptr(), B,
-                                             known.numel() // B, _st(out)))
+        L.check(L.lib().avd_latent_guide_f32(*args, out.numel() // B, _st(out)))
     else:
-        outer, L_, inner = window_dims(known.shape)
-        L.check(L.lib().avd_latent_guide_canvas_f32(C.byref(g), tn.data_ptr(), ab.data_ptr(), ab.numel(), L.ptr(zz), out.data_ptr(), B,
-                                                    outer, L_, canvas_hop, inner, _st(out)))
+        outer, L_, inner = window_dims(out.shape)
+        L.check(L.lib().avd_latent_guide_canvas_f32(*args, outer, L_, canvas_hop, inner, _st(out)))
     return out
 
 
@@ -359,12 +395,10 @@ def renoise(z: Tensor, t_from: Tensor, t_to: Tensor, alpha_bar: Tensor, seed: in
     tf, tt = L.dev_i64(t_from, dev), L.dev_i64(t_to, dev)
     if tf.numel() != B or tt.numel() != B:
         raise ValueError(f"t_from / t_to have {tf.numel()} / {tt.numel()} entries, z has {B} samples")
+    _check_out(out, z.shape, z)
     if out is None:
         out = torch.empty_like(z)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == z.shape and out.device == dev):
-        raise ValueError(f"out must be a contiguous float32 tensor of shape {tuple(z.shape)} on z's device")
-    ab = alpha_bar if (alpha_bar.is_cuda and alpha_bar.dtype == torch.float32) else alpha_bar.to(dev, torch.float32)
-    ab = ab.contiguous()
+    ab = _alpha_bar(alpha_bar, dev)
     args = (C.byref(key), visit, None if guide is None else C.byref(guide), tf.data_ptr(), tt.data_ptr(), ab.data_ptr(), ab.numel(),
             z.data_ptr(), out.data_ptr(), B)
     if canvas_hop is None:
@@ -529,9 +563,7 @@ def gaussian_noise(seed: int, sample_offset: int, t_now: Tensor, shape) -> Tenso
     element e of the row in row-major order of shape[1:].  The same values the seeded DenoiseEngine draws inside its step, so the
     result can be passed as ``noise`` to ``schedule_utils.ddim_step`` / ``DenoiseEngine.step``.  ``t_now``: int [B] (moved to the
     current ROCm device if it is not on one)."""
-    shape = tuple(int(s) for s in shape)
-    if len(shape) < 1 or shape[0] < 1 or any(s < 1 for s in shape):
-        raise ValueError(f"shape must be (B, ...) with positive sizes, got {shape}")
+    shape = _positive_shape(shape, "shape must be (B, ...) with positive sizes")
     key = noise_key(seed, sample_offset)
     dev = t_now.device if t_now.is_cuda else torch.device("cuda", torch.cuda.current_device())
     tn = L.dev_i64(t_now, dev)
@@ -568,14 +600,11 @@ def canvas_noise(seed: int, t_now: Tensor, shape, hop: int, window_offset: int =
     [p, o, i] — every window covering p gets the same bits.  The values a canvas-keyed DenoiseEngine draws inside its step, so the
     result can be passed as ``noise`` to an unseeded engine's ``step``.  ``t_now``: int [N] (moved to the current ROCm device if it
     is not on one).  ``out``: a contiguous float32 device tensor of ``shape`` to fill instead of a new one."""
-    shape = tuple(int(s) for s in shape)
     outer, L_, inner = window_dims(shape)
-    if any(s < 1 for s in shape):
-        raise ValueError(f"shape must have positive sizes, got {shape}")
+    shape = _positive_shape(shape)
     key = noise_key(seed, window_offset)
     hop = check_canvas_keying(shape, hop, window_offset)
-    if out is not None and not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
-        raise ValueError(f"out must be a contiguous float32 device tensor of shape {shape}")
+    _check_out(out, shape)
     dev = out.device if out is not None else (t_now.device if t_now.is_cuda else torch.device("cuda", torch.cuda.current_device()))
     tn = L.dev_i64(t_now, dev)
     if tn.numel() != shape[0]:
@@ -628,20 +657,12 @@ def slot_noise(seed: int, t_now: Tensor, shape, slot_len: int, first: int = 0, s
     result can be passed as ``noise`` to ``ddim_step_slots`` / ``dpmpp_2m_sde_step_slots`` or, with a uniform table, to an unseeded
     engine's ``step``.  ``stride`` None = S; ``cursor``: see ``slot_key``; ``out``: a contiguous float32 device tensor of ``shape``
     to fill instead of a new one."""
-    shape = tuple(int(s) for s in shape)
     outer, L_, inner = window_dims(shape)
-    if any(s < 1 for s in shape):
-        raise ValueError(f"shape must have positive sizes, got {shape}")
-    t_now = torch.as_tensor(t_now)
-    if t_now.dim() != 2 or t_now.shape[0] != shape[0] or t_now.is_floating_point() or t_now.dtype == torch.bool:
-        raise ValueError(f"t_now must be an int [B, S] table with B = {shape[0]}, got {t_now.dtype} {tuple(t_now.shape)}")
-    S = int(t_now.shape[1])
-    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or S < 1 or S * slot_len > L_:
-        raise ValueError(f"S = {S} slots of slot_len {slot_len!r} must fit the sliding length {L_}")
+    shape = _positive_shape(shape)
+    t_now, S = _slot_table(t_now, "t_now", shape[0], L_, slot_len)
     if outer * inner >= 2 ** 34:
         raise ValueError(f"one clip position holds outer * inner = {outer * inner} elements, the stream keys < 2**34")
-    if out is not None and not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
-        raise ValueError(f"out must be a contiguous float32 device tensor of shape {shape}")
+    _check_out(out, shape)
     dev = out.device if out is not None else (t_now.device if t_now.is_cuda else torch.device("cuda", torch.cuda.current_device()))
     key = slot_key(seed, first, S if stride is None else stride, cursor, dev)
     tn = L.dev_i64(t_now, dev)
@@ -698,21 +719,14 @@ def clip_guide_slots(known: Tensor, tau: Tensor, alpha_bar: Tensor, z: Tensor, m
     z = L.dev_f32(z, "z")
     shape = tuple(z.shape)
     outer, L_, inner = window_dims(shape)
-    tau = torch.as_tensor(tau)
-    if tau.dim() != 2 or tau.shape[0] != shape[0] or tau.is_floating_point() or tau.dtype == torch.bool:
-        raise ValueError(f"tau must be an int [B, S] table with B = {shape[0]}, got {tau.dtype} {tuple(tau.shape)}")
-    S = int(tau.shape[1])
-    if isinstance(slot_len, bool) or not isinstance(slot_len, int) or slot_len < 1 or S < 1 or S * slot_len > L_:
-        raise ValueError(f"S = {S} slots of slot_len {slot_len!r} must fit the sliding length {L_}")
+    tau, S = _slot_table(tau, "tau", shape[0], L_, slot_len)
     m = None if mask is None else L.dev_f32(mask, "mask")
     g = clip_guide(known, m, seed, first, S if stride is None else stride, cursor, shape)
+    _check_out(out, shape, z)
     if out is None:
         out = torch.empty_like(z)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape and out.device == z.device):
-        raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on z's device")
     tn = L.dev_i64(tau, z.device)
-    ab = alpha_bar if (alpha_bar.is_cuda and alpha_bar.dtype == torch.float32) else alpha_bar.to(z.device, torch.float32)
-    ab = ab.contiguous()
+    ab = _alpha_bar(alpha_bar, z.device)
     L.check(L.lib().avd_clip_guide_slots_f32(C.byref(g), tn.data_ptr(), ab.data_ptr(), ab.numel(), 1 if everywhere else 0, z.data_ptr(),
                                              out.data_ptr(), shape[0], outer, L_, S, slot_len, inner, _st(z)))
     return out

@@ -916,15 +916,8 @@ class DenoiseEngine:
             return z_init, sched_k
         B = self.embed.B
         tau = torch.full((B,), int(sched_k[0]), dtype=torch.long, device=self.device)
-        out = torch.empty_like(z_init)
         z = z_init if sched_k.numel() - 1 == n else None
-        args = (C.byref(self._guide), tau.data_ptr(), self.alpha_bar.data_ptr(), self.alpha_bar.numel(), L.ptr(z), out.data_ptr(), B)
-        if self._guide_hop is None:
-            L.check(L.lib().avd_latent_guide_f32(*args, z_init.numel() // B, L.stream_ptr(self.device)))
-        else:
-            outer, L_, inner = Fn.window_dims(self.latent_shape)
-            L.check(L.lib().avd_latent_guide_canvas_f32(*args, outer, L_, self._guide_hop, inner, L.stream_ptr(self.device)))
-        return out, sched_k
+        return Fn.latent_guide_launch(self._guide, self._guide_hop, tau, self.alpha_bar, z, torch.empty_like(z_init)), sched_k
 
     def step(self, z: torch.Tensor, t_now: torch.Tensor, t_prev: torch.Tensor,
              noise: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,

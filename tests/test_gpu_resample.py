@@ -13,6 +13,8 @@ import torch
 
 import _canvas_noise_ref as CN
 import _consensus_ref as W
+import _guide_ref as G
+import _noise_ref as NR
 import _renoise_ref as RR
 from _kit import (ABAR, STREAM_HALF_SECOND, Recorder, audio_case, audio_prompt, components, dev, engine, matmul_f32, model,  # noqa: F401  (dev / model are fixtures)
                   pipeline, soft_mask, ts, video_case)
@@ -44,6 +46,13 @@ def _latents(dev, kind):
     return z, known
 
 
+def _unaligned(x, copy=False):
+    """a contiguous view of x's shape that starts one float into a larger buffer"""
+    v = torch.empty(x.numel() + 1, device=x.device)[1:].view(x.shape)
+    assert v.data_ptr() % 16 != 0
+    return v.copy_(x) if copy else v
+
+
 # per-sample timesteps that differ across the batch: a jump from the clean end (t_from = -1), an identity sample (t_to <= t_from)
 T_PAIRS = [([-1, 500], [300, 200]), ([100, 700], [600, 999]), ([250, 250], [250, 750])]
 
@@ -72,6 +81,9 @@ def test_kernel_vs_reference(dev, kind):
         # in place = out of place, and an explicit out
         zi = z.clone()
         assert Fn.renoise(zi, ts(tf, dev), ts(tt, dev), ABAR, SEED, visit + 7, sample_offset=4, out=zi) is zi and torch.equal(zi, out)
+        # an out one float into a larger buffer takes the guarded lanes: the same bits
+        ou = _unaligned(z)
+        assert torch.equal(Fn.renoise(z, ts(tf, dev), ts(tt, dev), ABAR, SEED, visit + 7, sample_offset=4, out=ou), out)
         # a soft mask: the blend of the contract
         got = Fn.renoise(z, ts(tf, dev), ts(tt, dev), ABAR, SEED, visit + 7, sample_offset=4, guide=guide_soft)
         m = md.cpu().numpy()
@@ -196,6 +208,7 @@ def test_canvas_entry(dev, name, shape, hop, off):
     zu.copy_(z)
     assert zu.data_ptr() % 16 != 0
     assert torch.equal(Fn.renoise(zu, ts(tf, dev), ts(tt, dev), ABAR, SEED, visit, guide=guide, **kw), held)
+    assert torch.equal(Fn.renoise(z, ts(tf, dev), ts(tt, dev), ABAR, SEED, visit, guide=guide, out=_unaligned(z), **kw), held)
     parts = []
     for lo, hi in ((0, 2), (2, 3)):
         gp = Fn.latent_guide_desc(known[lo:hi], mask[lo:hi], GSEED, off + lo)                     # views of known / mask
@@ -206,12 +219,52 @@ def test_canvas_entry(dev, name, shape, hop, off):
     mixed_f, mixed_t = [-1, 500, 100], [300, 200, 600]
     mixed = Fn.renoise(z, ts(mixed_f, dev), ts(mixed_t, dev), ABAR, SEED, visit, **kw)
     assert torch.equal(mixed[1], z[1]) and not torch.equal(mixed[0], z[0])
+    for zm in (z.clone(), _unaligned(z, copy=True)):          # the identity window in place, on this shape's lanes and the unaligned ones
+        Fn.renoise(zm, ts(mixed_f, dev), ts(mixed_t, dev), ABAR, SEED, visit, out=zm, **kw)
+        assert torch.equal(zm, mixed)
     assert _err(mixed, RR.renoise_canvas_f64(z.cpu().numpy(), mixed_f, mixed_t, ABAR.numpy(), SEED, visit, hop, off)) <= TOL
     # keyed per sample the windows part
     per_sample = Fn.renoise(z, ts(tf, dev), ts(tt, dev), ABAR, SEED, visit, sample_offset=off)
     assert not W.overlaps_agree(per_sample.cpu().numpy(), hop)
     with pytest.raises(ValueError, match="same sample_offset"):
         Fn.renoise(z, ts(tf, dev), ts(tt, dev), ABAR, SEED, visit, guide=Fn.latent_guide_desc(known, mask, GSEED, off + 1), **kw)
+
+
+# ------------------------------------------------------------------------------------------------- one map for the keyings
+@pytest.mark.parametrize("per", [1, 3, 5, 8])                 # a lone partial lane (1, 3), a full lane and a tail of one, no tail
+def test_per_sample_entries_are_the_canvas_entries_at_hop_1(dev, per):
+    """the batch [B, 1, 1, per] at hop 1 puts window b on canvas position off + b, element e' = i: the per-sample stream's counters"""
+    from multimodal_diffusion_amd import functional as Fn
+    B, off, shape = 2, 11, (2, 1, 1, 1, per)
+    g = torch.Generator().manual_seed(per)
+    z, known = torch.randn(shape, generator=g).to(dev), torch.randn(shape, generator=g).to(dev)
+    md = torch.tensor([0.0, 1.0, 0.4, 0.75] * 4)[:B * per].view(shape).to(dev)      # both selects, and fractions from per = 3 on
+    zn, kn, mn = (x.cpu().numpy().reshape(B, per) for x in (z, known, md))
+    # the draw
+    tn = [731, 17]
+    draw = Fn.gaussian_noise(SEED, off, ts(tn, dev), shape)
+    assert torch.equal(draw, Fn.canvas_noise(SEED, ts(tn, dev), shape, 1, window_offset=off))
+    assert np.abs(draw.cpu().double().numpy().reshape(B, per) - NR.normals(SEED, off, tn, per)).max() < 1e-5
+    # the guide: the blend, and z = None; an unaligned z takes the guarded lanes
+    tau = [700, 300]
+    q_ref = G.q_f64(kn, tau, ABAR.numpy(), GSEED, off)
+    for zz, ref in ((z, G.blend_f64(mn, q_ref, zn)), (None, q_ref)):
+        m = md if zz is not None else None
+        per_sample = Fn.latent_guide(known, ts(tau, dev), ABAR, z=zz, mask=m, seed=GSEED, sample_offset=off)
+        assert torch.equal(per_sample, Fn.latent_guide(known, ts(tau, dev), ABAR, z=zz, mask=m, seed=GSEED, canvas_hop=1, window_offset=off))
+        assert _err(per_sample.reshape(B, per), ref) <= TOL
+        if zz is not None:
+            assert torch.equal(Fn.latent_guide(known, ts(tau, dev), ABAR, z=_unaligned(z, copy=True), mask=m, seed=GSEED, sample_offset=off),
+                               per_sample)
+    # the renoise, free and guided; sample 1 is the identity
+    tf, tt, visit = [249, 500], [749, 200], 4
+    guide = Fn.latent_guide_desc(known, md, GSEED, off)
+    for gd, kwr in ((None, {}), (guide, dict(known=kn, mask=mn, guide_seed=GSEED))):
+        per_sample = Fn.renoise(z, ts(tf, dev), ts(tt, dev), ABAR, SEED, visit, sample_offset=off, guide=gd)
+        assert torch.equal(per_sample, Fn.renoise(z, ts(tf, dev), ts(tt, dev), ABAR, SEED, visit, sample_offset=off, guide=gd, canvas_hop=1))
+        assert _err(per_sample.reshape(B, per), RR.renoise_f64(zn, tf, tt, ABAR.numpy(), SEED, visit, sample_offset=off, **kwr)) <= TOL
+        if gd is None:
+            assert torch.equal(per_sample[1], z[1]) and not torch.equal(per_sample[0], z[0])
 
 
 # ------------------------------------------------------------------------------------------------- the engine
