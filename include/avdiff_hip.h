@@ -673,11 +673,55 @@ int avd_fifo_shift_cursor_hist_f32(const avd_noise_key* key, int64_t t, int64_t 
  * <= 2^32, outer*inner < 2^34); K >= 1 and K divides B; non-null seeds and clips; 1 <= n_clip and n_clip*slot_len <= 2^32; each rider
  * pair both NULL or both set; no two buffers overlap, the canvases and the seeds included.  All index arithmetic is 64-bit.  16-byte
  * lanes when inner % 4 == 0 and every base is 16-byte aligned, one element per lane otherwise (every audio latent); the same bits
- * either way.  Limits of the drivers built on it (stream_infer.fifo_denoise_clips): eta == 0 only (the clip-keyed slot noise has one
- * seed per call), the plain eager queue only, no clip guide, and the clips share n_clip. */
+ * either way.  Limits of the drivers built on it (stream_infer.fifo_denoise_clips): the plain eager queue only, and the clips share
+ * n_clip; eta > 0 and a latent guide per clip ride on "clip batch keying" below. */
 int avd_fifo_shift_clips_f32(const uint64_t* seeds, int64_t t, int64_t c, const float* z_in, float* z_out, float* clips, int64_t n_clip,
                              int64_t m, const float* hist_in, float* hist_out, const float* carry_in, float* carry_out, int B, int K,
                              int64_t outer, int slots, int slot_len, int64_t inner, avd_stream_t stream);
+
+/* ---- clip batch keying (a public contract): the step noise and the latent guide of a FIFO clip batch, one seed and one canvas per
+ * queue.  avd_slot_key and avd_clip_guide carry one seed, one canvas and one clip-position walk first + b*stride over the whole batch;
+ * in a clip batch the K queues restart that walk and own their seeds and canvases.  A batch [B, outer, L, inner] with B = K*B_q is K
+ * queues; sample b is sample b' = b mod B_q of queue k = b / B_q.  With a descriptor present the keying of "clip-keyed slot noise" and
+ * "clip-keyed latent guide" changes as follows, and nothing else does.
+ *   Step noise.  Element (b, o, l, i) sits on clip position p = ((first + max(*cursor, 0) + b'*stride)*slot_len + l) mod 2^32 and draws
+ *     that contract's normal under seed step_seeds[k]: same counter words, same SLOT domain word, same lane rules.  key->seed is not read.
+ *   Clip guide.  guide->known and guide->mask are [K, outer, P, inner] (the mask may be NULL: 1 everywhere).  Queue k reads canvas k at
+ *     p = (first + max(*cursor, 0) + b'*stride)*slot_len + l, signed and unwrapped, compared with [0, P) before anything is read; its
+ *     known noise is the guide stream under guide_seeds[k].  guide->seed is not read.
+ * Equivalence.  A call with a descriptor is bit for bit K calls of the existing entry on the K sample slices, with
+ * avd_slot_key{step_seeds[k], first, stride, cursor} and avd_clip_guide{known[k], mask[k], P, guide_seeds[k], first, stride, cursor}.
+ * K == 1 gives the existing entries' bits.  A held slot, eta == 0, the final step, the all-zero mask and the "no contraction" rule are
+ * unchanged.  The seeds are read on the device at every launch, so a graph driver can swap them; K is held by value.
+ * Checked before any launch (AVD_EINVAL): everything the existing entries check; K >= 1 and K divides B; non-null, 8-byte aligned
+ * step_seeds at eta > 0 (with a slot key) and guide_seeds with a guide; the K canvases together must not overlap z_out (out), x0_hist
+ * or the seeds, and the seeds must not overlap z_out (out) or x0_hist.  All index arithmetic is 64-bit. */
+typedef struct {
+    int32_t K;                    /* queues; K >= 1 and K divides B */
+    const uint64_t* step_seeds;   /* K uint64 on the device, 8-byte aligned; read only at eta > 0 (may be NULL at eta == 0) */
+    const uint64_t* guide_seeds;  /* K uint64 on the device; read only with a clip guide (NULL without one) */
+} avd_clip_queues;
+/* avd_slot_noise_f32 with the descriptor: t_now int64 [B*slots]. */
+int avd_slot_noise_clips_f32(const avd_slot_key* key, const avd_clip_queues* queues, const int64_t* t_now, float* out, int B,
+                             int64_t outer, int L, int slots, int slot_len, int64_t inner, avd_stream_t stream);
+/* avd_clip_guide_slots_f32 with the descriptor.  One in-place launch with AVD_SLOT_LEAVE everywhere except each queue's tail slot puts
+ * all K entering slots on their forward paths. */
+int avd_clip_guide_slots_clips_f32(const avd_clip_guide* g, const avd_clip_queues* queues, const int64_t* tau, const float* alpha_bar,
+                                   int T_train, int everywhere, const float* z, float* out, int B, int64_t outer, int L, int slots,
+                                   int slot_len, int64_t inner, avd_stream_t stream);
+/* The fused updates alone: avd_cfg_unpatch_ddim_slots_cfg_f32 / avd_cfg_untoken_ddim_audio_slots_cfg_f32 with the descriptor.  cfg may
+ * be NULL here (the scalar guidance), key may be NULL at eta == 0, guide may be NULL; a descriptor with neither an eta > 0 key nor a
+ * guide changes nothing. */
+int avd_cfg_unpatch_ddim_slots_clips_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                         const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, float eta,
+                                         const avd_slot_key* key, const avd_clip_guide* guide, const avd_clip_queues* queues, int slots,
+                                         float* x0_hist, float* z_out, int B, int C, int T, int H, int W, int t, int h, int w,
+                                         const avd_slot_cfg* cfg, avd_stream_t stream);
+int avd_cfg_untoken_ddim_audio_slots_clips_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                               const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, float eta,
+                                               const avd_slot_key* key, const avd_clip_guide* guide, const avd_clip_queues* queues,
+                                               int slots, float* x0_hist, float* z_out, int B, int Ca, int F, int len, int stride,
+                                               const avd_slot_cfg* cfg, avd_stream_t stream);
 
 /* ---- latent guide: inpainting / outpainting and SDEdit over a known clean latent (a public contract).
  * Per sample b of a call, with x_k = known[b] and m = the mask, both in the latent's natural layout ([C,T,H,W] video, [Ca,F] audio,
@@ -1155,6 +1199,14 @@ int avd_denoise_step_slots_cfg_f32(const avd_step_desc* s, const avd_slot_cfg* c
                                    const int64_t* t_last, float* x0_hist, const float* z, const float* Xp, const int64_t* t_now,
                                    const int64_t* t_prev, int slots, float* z_out, void* workspace, int64_t workspace_bytes,
                                    avd_stream_t stream);
+/* The whole step of a FIFO clip batch under per-queue keys and guides (see "clip batch keying"): avd_denoise_step_slots_cfg_f32 with the
+ * descriptor, both solvers.  cfg may be NULL here (the scalar guidance); the slot CFG control and the slot momentum are per slot already
+ * and unchanged.  The descriptor is checked before the model runs, as the fused update's launcher checks it again.  Graph-capturable:
+ * the seeds are read at their addresses at every launch. */
+int avd_denoise_step_slots_clips_f32(const avd_step_desc* s, const avd_slot_cfg* cfg, const avd_slot_key* key, const avd_clip_guide* guide,
+                                     const avd_clip_queues* queues, const int64_t* t_last, float* x0_hist, const float* z,
+                                     const float* Xp, const int64_t* t_now, const int64_t* t_prev, int slots, float* z_out,
+                                     void* workspace, int64_t workspace_bytes, avd_stream_t stream);
 /* As avd_denoise_step_f32, with the eta > 0 noise drawn inside the fused CFG + DDIM kernel from the seeded stream (avd_noise_key)
  * for samples key->sample_offset .. + B - 1 at t_now: no noise buffer, graph-capturable.  With s->eta == 0 it is the plain step. */
 int avd_denoise_step_seeded_f32(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp,

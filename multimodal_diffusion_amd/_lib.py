@@ -81,6 +81,12 @@ class ClipGuide(C.Structure):
                 ("stride", C.c_int32), ("cursor", C.c_void_p)]
 
 
+class ClipQueues(C.Structure):
+    """avd_clip_queues: the K queues of a FIFO clip batch and their seeds, K uint64 each in device memory (contract in
+    include/avdiff_hip.h, "clip batch keying").  Raw device pointers, either may be None: keep the tensors alive."""
+    _fields_ = [("K", C.c_int32), ("step_seeds", C.c_void_p), ("guide_seeds", C.c_void_p)]
+
+
 SLOT_LEAVE = -2 ** 63      # AVD_SLOT_LEAVE: a tau entry that leaves its slot as z
 
 
@@ -209,6 +215,14 @@ SIGNATURES = {
                                                       _P] + [_I] * 5 + [C.POINTER(SlotCfg), _P]),
     "avd_denoise_step_slots_cfg_f32": (_I, [C.POINTER(StepDesc), C.POINTER(SlotCfg), C.POINTER(SlotKey), C.POINTER(ClipGuide), _P, _P, _P,
                                             _P, _P, _P, _I, _P, _P, _L, _P]),
+    "avd_slot_noise_clips_f32": (_I, [C.POINTER(SlotKey), C.POINTER(ClipQueues), _P, _P, _I, _L, _I, _I, _I, _L, _P]),
+    "avd_clip_guide_slots_clips_f32": (_I, [C.POINTER(ClipGuide), C.POINTER(ClipQueues), _P, _P, _I, _I, _P, _P, _I, _L, _I, _I, _I, _L, _P]),
+    "avd_cfg_unpatch_ddim_slots_clips_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _F, C.POINTER(SlotKey), C.POINTER(ClipGuide),
+                                                  C.POINTER(ClipQueues), _I, _P, _P] + [_I] * 8 + [C.POINTER(SlotCfg), _P]),
+    "avd_cfg_untoken_ddim_audio_slots_clips_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _F, C.POINTER(SlotKey), C.POINTER(ClipGuide),
+                                                        C.POINTER(ClipQueues), _I, _P, _P] + [_I] * 5 + [C.POINTER(SlotCfg), _P]),
+    "avd_denoise_step_slots_clips_f32": (_I, [C.POINTER(StepDesc), C.POINTER(SlotCfg), C.POINTER(SlotKey), C.POINTER(ClipGuide),
+                                              C.POINTER(ClipQueues), _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P]),
     "avd_fifo_shift_hist_f32": (_I, [C.POINTER(NoiseKey), _L, _L, _P, _P, _P, _P, _P, _I, _L, _I, _I, _L, _P]),
     "avd_fifo_shift_guided_f32": (_I, [C.POINTER(NoiseKey), _L, _L, C.POINTER(ClipGuide), _P, _I, _I, _P, _P, _P, _P, _P, _I, _L, _I, _I, _L,
                                        _P]),

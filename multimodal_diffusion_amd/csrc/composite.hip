@@ -85,14 +85,16 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
                          const int64_t* t_last = nullptr, float* x0_hist = nullptr, const avd_latent_guide* guide = nullptr,
                          const avd_cfg_control* ctl = nullptr, int canvas_hop = 0, int guide_hop = 0, int slots = 0,
                          const avd_apg_control* apg = nullptr, const avd_slot_key* skey = nullptr,
-                         const avd_clip_guide* cguide = nullptr, const avd_slot_cfg* scfg = nullptr);
+                         const avd_clip_guide* cguide = nullptr, const avd_slot_cfg* scfg = nullptr,
+                         const avd_clip_queues* cq = nullptr);
 int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st,
                                const avd_noise_key* key = nullptr, const int64_t* t_last = nullptr, float* x0_hist = nullptr,
                                const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr, int canvas_hop = 0, int guide_hop = 0,
                                int slots = 0, const avd_apg_control* apg = nullptr, const avd_slot_key* skey = nullptr,
-                               const avd_clip_guide* cguide = nullptr, const avd_slot_cfg* scfg = nullptr);
+                               const avd_clip_guide* cguide = nullptr, const avd_slot_cfg* scfg = nullptr,
+                               const avd_clip_queues* cq = nullptr);
 int assemble_cond_f32(float* X1, const float* temb, const float* Xp, int B, int N, int d, int tdim, int Nt, int Np, int target_first,
                       hipStream_t st);
 int assemble_rows_cond_f32(float* X1, const int64_t* t_now, const float* freqs, const float* Xp, float* ss, int B, int N, int d,
@@ -108,7 +110,9 @@ int eps_untoken_ddim_audio_f32(const float* eps1, const float* z, const int64_t*
 int check_canvas_key(const avd_noise_key* key, int N, int64_t outer, int L, int hop, int64_t inner);
 int check_slot_key(const avd_slot_key* key, int B, int64_t outer, int slot_len, int64_t inner);
 int check_clip_guide(const avd_clip_guide* g, int B, int64_t outer, int L, int slots, int slot_len, int64_t inner, const float* out,
-                     const float* x0_hist);
+                     const float* x0_hist, int K = 1);
+int check_clip_queues(const avd_clip_queues* cq, const avd_clip_guide* g, bool step, int B, int64_t outer, int L, int64_t inner,
+                      const float* out, const float* x0_hist);
 int check_canvas_guide(const avd_latent_guide* g, int N, int64_t outer, int L, int hop, int64_t inner, const float* out,
                        const float* x0_hist);
 int check_latent_guide(const avd_latent_guide* g, int B, int64_t per, const float* out, const float* x0_hist);
@@ -929,7 +933,7 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
                         avd_stream_t stream, const int64_t* t_last = nullptr, float* x0_hist = nullptr,
                         const avd_latent_guide* guide = nullptr, const avd_cfg_control* ctl = nullptr, int canvas_hop = 0,
                         int guide_hop = 0, int slots = 0, const avd_apg_control* apg = nullptr, const avd_slot_key* skey = nullptr,
-                        const avd_clip_guide* cguide = nullptr, const avd_slot_cfg* scfg = nullptr) {
+                        const avd_clip_guide* cguide = nullptr, const avd_slot_cfg* scfg = nullptr, const avd_clip_queues* cq = nullptr) {
     StepWs ws;
     if (int rc = open_step(s, z, z_out, t_now, t_prev, workspace, workspace_bytes, ws)) return rc;
     auto& [p, X2, tok, core_ws, head_ws, ssx, eps2] = ws;
@@ -1001,10 +1005,10 @@ static int denoise_step(const avd_step_desc* s, const avd_noise_key* key, const 
     if (e.target_kind == 0)
         return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, s->alpha_bar, s->T_train, s->guidance, s->eta, noise, z_out,
                                     e.B, e.C, e.T, e.H, e.W, e.p0, e.p1, e.p2, st, key, t_last, x0_hist, guide, ctl, canvas_hop,
-                                    guide_hop, slots, apg, skey, cguide, scfg);
+                                    guide_hop, slots, apg, skey, cguide, scfg, cq);
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, s->alpha_bar, s->T_train, s->guidance, s->eta, noise, z_out,
                                       e.B, e.C, e.T, e.p0, e.p1, st, key, t_last, x0_hist, guide, ctl, canvas_hop, guide_hop, slots, apg,
-                                      skey, cguide, scfg);
+                                      skey, cguide, scfg, cq);
 }
 
 // The cond-only step of a guidance interval: the conditional branch alone, in the cond half of every workspace region of the CFG step's
@@ -1214,6 +1218,44 @@ extern "C" int avd_denoise_step_slots_cfg_f32(const avd_step_desc* s, const avd_
     }
     return denoise_step(s, nullptr, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, nullptr,
                         nullptr, 0, 0, slots, nullptr, s->eta > 0.f ? key : nullptr, guide, cfg);
+}
+
+// The whole step of a FIFO clip batch under per-queue keys and guides ("clip batch keying" in the header): avd_denoise_step_slots_cfg_f32
+// with the descriptor and the control optional.  The descriptor is checked here, before the model runs, with the guide and the key.
+extern "C" int avd_denoise_step_slots_clips_f32(const avd_step_desc* s, const avd_slot_cfg* cfg, const avd_slot_key* key,
+                                                const avd_clip_guide* guide, const avd_clip_queues* queues, const int64_t* t_last,
+                                                float* x0_hist, const float* z, const float* Xp, const int64_t* t_now,
+                                                const int64_t* t_prev, int slots, float* z_out, void* workspace, int64_t workspace_bytes,
+                                                avd_stream_t stream) {
+    AVD_REQUIRE(s, AVD_EINVAL, "denoise_step_slots_clips: null descriptor");
+    AVD_REQUIRE(queues, AVD_EINVAL, "denoise_step_slots_clips: null clip queues");
+    AVD_REQUIRE(key || !(s->eta > 0.f), AVD_EINVAL, "denoise_step_slots_clips: eta > 0 needs a slot key");
+    AVD_REQUIRE(!s->embed.temb_add, AVD_EINVAL, "denoise_step_slots_clips: slot timesteps take the concat embedding (temb_add == 0)");
+    if (int rc = check_embed(&s->embed)) return rc;
+    int S = 0, tok = 0;
+    if (int rc = embed_slots(&s->embed, S, tok)) return rc;
+    AVD_REQUIRE(slots == S, AVD_EINVAL, "denoise_step_slots_clips: slots %d must equal the geometry's %d slots along the sliding axis", slots, S);
+    const avd_embed_desc& e = s->embed;
+    const int64_t per = (int64_t)e.C * e.T * e.H * e.W;
+    const int64_t per_slot = e.target_kind == 0 ? (int64_t)e.C * e.p0 * e.H * e.W : (int64_t)e.C * e.p0;
+    if (cfg)
+        if (int rc = check_slot_cfg(cfg, e.B, S, per_slot, per, z, z_out, x0_hist, workspace, workspace_bytes)) return rc;
+    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "denoise_step_slots_clips: t_last and x0_hist go together (the DPM-Solver++(2M) update)");
+    if (x0_hist) {
+        AVD_REQUIRE(!(z && overlaps(x0_hist, z, e.B * per)) && !(z_out && overlaps(x0_hist, z_out, e.B * per)), AVD_EINVAL,
+                    "denoise_step_slots_clips: x0_hist must not alias z or z_out");
+        AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "denoise_step_slots_clips: x0_hist must be 16-byte aligned");
+    }
+    if (guide)
+        if (int rc = check_clip_guide(guide, e.B, e.C, e.T, S, e.p0, (int64_t)e.H * e.W, z_out, x0_hist, queues->K)) return rc;
+    if (s->eta > 0.f) {
+        if (int rc = check_slot_key(key, e.B, e.C, e.p0, (int64_t)e.H * e.W)) return rc;
+        AVD_REQUIRE(!guide || (key->first == guide->first && key->stride == guide->stride && key->cursor == guide->cursor), AVD_EINVAL,
+                    "denoise_step_slots_clips: the slot key's first / stride / cursor must equal the clip guide's");
+    }
+    if (int rc = check_clip_queues(queues, guide, s->eta > 0.f, e.B, e.C, e.T, (int64_t)e.H * e.W, z_out, x0_hist)) return rc;
+    return denoise_step(s, nullptr, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, nullptr,
+                        nullptr, 0, 0, slots, nullptr, s->eta > 0.f ? key : nullptr, guide, cfg, queues);
 }
 
 extern "C" int avd_denoise_step_seeded_f32(const avd_step_desc* s, const avd_noise_key* key, const float* z, const float* Xp,

@@ -347,14 +347,18 @@ struct ClipGuideState;
 struct SlotCfgState;
 // A SlotMomentum rides right behind a SlotCfgState in its APG mode ("slot APG momentum"): before the ClipGuideState.
 struct SlotMomentum;
+// A ClipQueues ends a slot pack that holds a SlotKey or a ClipGuideState ("clip batch keying"): the batch is K queues, each under its own
+// seeds and canvases.  A pack without it carries none of its state: no divide, no seed load.
+struct ClipQueues;
 template <bool SEEDED, class... X> struct PackOk {
     template <class T> static constexpr int n = PackHas<T, X...>::value ? 1 : 0;
     static constexpr bool value = sizeof...(X) == (SEEDED ? 1 : 0) + n<DpmState> + n<GuideState> + n<CanvasGuideState> + n<CfgState> +
-                                                      n<CondOnly> + n<SlotTimes> + n<ClipGuideState> + n<SlotCfgState> + n<SlotMomentum> &&
-                                  !(n<SlotTimes> &&
-                                    sizeof...(X) != 1 + n<DpmState> + n<SlotKey> + n<ClipGuideState> + n<SlotCfgState> + n<SlotMomentum>) &&
+                                                      n<CondOnly> + n<SlotTimes> + n<ClipGuideState> + n<SlotCfgState> + n<SlotMomentum> +
+                                                      n<ClipQueues> &&
+                                  !(n<SlotTimes> && sizeof...(X) != 1 + n<DpmState> + n<SlotKey> + n<ClipGuideState> + n<SlotCfgState> +
+                                                                        n<SlotMomentum> + n<ClipQueues>) &&
                                   n<SlotKey> <= n<SlotTimes> && n<ClipGuideState> <= n<SlotTimes> && n<SlotCfgState> <= n<SlotTimes> &&
-                                  n<SlotMomentum> <= n<SlotCfgState> &&
+                                  n<SlotMomentum> <= n<SlotCfgState> && n<ClipQueues> <= (n<SlotKey> || n<ClipGuideState> ? 1 : 0) &&
                                   !(n<CfgState> && n<CondOnly>) && !(n<GuideState> && n<CanvasGuideState>) &&
                                   !(n<CanvasGuideState> && n<NoiseKey>) &&
                                   n<NoiseKey> + n<CanvasKey> + n<SlotKey> == (SEEDED ? 1 : 0);
@@ -534,6 +538,69 @@ int check_slot_key(const avd_slot_key* key, int B, int64_t outer, int slot_len, 
 // sample b at position (first + max(*cursor, 0) + b * stride) * slot_len, multiplied out
 static StreamMap stream_map(const SlotKey& k) {
     return StreamMap{k.k0, k.k1, (uint64_t)k.first * (uint64_t)k.slot_len, (uint64_t)k.stride * (uint64_t)k.slot_len, (uint64_t)k.slot_len, k.cursor};
+}
+
+// ------------------------------------------------------------------ clip batch keying (K queues in one batch)
+// The contract is written out in include/avdiff_hip.h ("clip batch keying").  The batch is K queues of Bq samples: sample b is sample
+// b' = b % Bq of queue k = b / Bq, the clip-position walk restarts in every queue (b' takes b's place in slot_normal4 / clip_guide_pos)
+// and queue k draws under its own seeds and reads its own canvases.  This is the one per-queue map: every keyed kernel resolves its
+// SlotKey, StreamMap or ClipGuideState through it and then calls the one-queue function, so the bits are the one-queue bits.
+struct ClipQueues {
+    int Bq;                        // samples of one queue
+    const uint64_t* step_seeds;    // K device seeds of the step noise; read only where a SlotKey (a draw's StreamMap) rides along
+    const uint64_t* guide_seeds;   // K device seeds of the guide's known noise; read only where a ClipGuideState rides along
+    int64_t canvas;                // outer * P * inner: floats from one queue's known / mask canvas to the next
+};
+struct QueueOf {
+    int k, b;                      // the queue, and the sample's index inside it
+};
+__device__ __forceinline__ QueueOf queue_of(const ClipQueues& q, int b) {
+    const int k = (int)((uint32_t)b / (uint32_t)q.Bq);
+    return QueueOf{k, b - k * q.Bq};
+}
+__device__ __forceinline__ SlotKey queue_slot_key(const ClipQueues& q, SlotKey sk, int k) {
+    const uint64_t seed = q.step_seeds[k];
+    sk.k0 = (uint32_t)(seed & 0xffffffffu);
+    sk.k1 = (uint32_t)(seed >> 32);
+    return sk;
+}
+__device__ __forceinline__ StreamMap queue_stream_map(const ClipQueues& q, StreamMap m, int k) {
+    const uint64_t seed = q.step_seeds[k];
+    m.k0 = (uint32_t)(seed & 0xffffffffu);
+    m.k1 = (uint32_t)(seed >> 32);
+    return m;
+}
+// the SlotKey a lane of the fused kernels draws with: the pack's own, or under a ClipQueues its queue's (qo: queue_of the lane's sample)
+template <class... Key> __device__ __forceinline__ SlotKey lane_slot_key(const QueueOf& qo, const Key&... nk) {
+    if constexpr (PackHas<ClipQueues, Key...>::value) return queue_slot_key(pack_get<ClipQueues>(nk...), pack_get<SlotKey>(nk...), qo.k);
+    else return pack_get<SlotKey>(nk...);
+}
+// The host side: the descriptor's checks, all before any HIP call.  step / guide: the launch reads the step seeds / the guide seeds;
+// outs: the buffers the launch writes (n floats each, nullptr skipped); known / mask: the K canvases together (nc floats each, null: none)
+static int make_clip_queues(const char* what, const avd_clip_queues* cq, int B, bool step, bool guide,
+                            std::initializer_list<const float*> outs, int64_t n, const float* known, const float* mask, int64_t nc,
+                            int64_t canvas, ClipQueues& q) {
+    AVD_REQUIRE(cq, AVD_EINVAL, "%s: null clip queues", what);
+    AVD_REQUIRE(cq->K >= 1 && B > 0 && B % cq->K == 0, AVD_EINVAL, "%s: the %d queues must divide the batch %d", what, cq->K, B);
+    AVD_REQUIRE(!step || cq->step_seeds, AVD_EINVAL, "%s: eta > 0 in a clip batch needs step_seeds, one per queue", what);
+    AVD_REQUIRE(!guide || cq->guide_seeds, AVD_EINVAL, "%s: a clip guide in a clip batch needs guide_seeds, one per queue", what);
+    const struct { const uint64_t* p; const char* name; } seeds[2] = {{step ? cq->step_seeds : nullptr, "step_seeds"},
+                                                                      {guide ? cq->guide_seeds : nullptr, "guide_seeds"}};
+    for (const auto& s : seeds) {
+        if (!s.p) continue;
+        AVD_REQUIRE((reinterpret_cast<uintptr_t>(s.p) & 7u) == 0, AVD_EINVAL, "%s: %s must be 8-byte aligned", what, s.name);
+        const char *sb = reinterpret_cast<const char*>(s.p), *se = sb + 8 * (int64_t)cq->K;
+        for (const float* o : outs) {
+            const char* ob = reinterpret_cast<const char*>(o);
+            AVD_REQUIRE(!o || !(sb < ob + 4 * n && ob < se), AVD_EINVAL, "%s: %s must not overlap out, z_out or x0_hist", what, s.name);
+        }
+        for (const float* c : {known, mask}) {
+            const char* cb = reinterpret_cast<const char*>(c);
+            AVD_REQUIRE(!c || !(sb < cb + 4 * nc && cb < se), AVD_EINVAL, "%s: known / mask must not overlap %s", what, s.name);
+        }
+    }
+    q = ClipQueues{B / cq->K, step ? cq->step_seeds : nullptr, guide ? cq->guide_seeds : nullptr, canvas};
+    return AVD_OK;
 }
 
 // ------------------------------------------------------------------ FIFO queue moves (diagonal denoising)
@@ -1217,11 +1284,26 @@ __device__ __forceinline__ float clip_guide_apply1(const ClipGuideState& cg, con
     if (!gc.one) n = philox_normal4(NoiseKey{cg.k0, cg.k1, 0u}, (uint32_t)((o * inner + i) >> 2), (uint32_t)p, 0u, GUIDE_TAG)[(int)((o * inner + i) & 3)];
     return guide_blend(m, guide_q(gc, cg.known[at], n), z);
 }
+// queue k's guide ("clip batch keying"): canvas k of known / mask and the known-noise stream under guide_seeds[k].  The canvas stride is
+// a multiple of 4 floats wherever vec is set, so canvas k is as aligned as canvas 0
+__device__ __forceinline__ ClipGuideState queue_clip_guide(const ClipQueues& q, ClipGuideState cg, int k) {
+    const uint64_t seed = q.guide_seeds[k];
+    cg.k0 = (uint32_t)(seed & 0xffffffffu);
+    cg.k1 = (uint32_t)(seed >> 32);
+    cg.known += (int64_t)k * q.canvas;
+    if (cg.mask) cg.mask += (int64_t)k * q.canvas;
+    return cg;
+}
+// as lane_slot_key: the ClipGuideState a lane of the fused kernels blends with
+template <class... Key> __device__ __forceinline__ ClipGuideState lane_clip_guide(const QueueOf& qo, const Key&... nk) {
+    if constexpr (PackHas<ClipQueues, Key...>::value) return queue_clip_guide(pack_get<ClipQueues>(nk...), pack_get<ClipGuideState>(nk...), qo.k);
+    else return pack_get<ClipGuideState>(nk...);
+}
 
 // the clip guide's checks, all before any HIP call (the list is in the header); outs: buffers known / mask must not overlap, each of
-// B * outer * L * inner floats, nullptr skipped
+// B * outer * L * inner floats, nullptr skipped.  K > 1 ("clip batch keying"): known / mask hold K canvases, walked by B / K samples each
 int make_clip_guide(const avd_clip_guide* g, int B, int64_t outer, int L, int slots, int slot_len, int64_t inner,
-                    std::initializer_list<const float*> outs, ClipGuideState& cg, const char* what = "clip_guide") {
+                    std::initializer_list<const float*> outs, ClipGuideState& cg, const char* what = "clip_guide", int K = 1) {
     AVD_REQUIRE(g, AVD_EINVAL, "%s: null clip guide", what);
     AVD_REQUIRE(g->known, AVD_EINVAL, "%s: null known canvas", what);
     if (int rc = check_keyed_dims(what, "B", B, outer, "L", L, inner)) return rc;
@@ -1230,11 +1312,13 @@ int make_clip_guide(const avd_clip_guide* g, int B, int64_t outer, int L, int sl
     if (int rc = check_slots(what, B, L, slots, slot_len)) return rc;
     // every term of the position: |first| < 2^32, the cursor < 2^31, B * stride < 2^62, so the slot index stays below 2^62.1 only
     // when B * stride does; times slot_len plus l it must stay inside int64
-    AVD_REQUIRE(((double)B * g->stride + 8.6e9) * (double)slot_len + (double)L < 9.0e18, AVD_EINVAL,
-                "%s: B %d * stride %d * slot_len %d leaves the signed 64-bit positions", what, B, g->stride, slot_len);
-    AVD_REQUIRE((double)outer * (double)g->P * (double)inner < 9.0e18 && (double)B * (double)outer * (double)L * (double)inner < 9.0e18,
+    AVD_REQUIRE(K >= 1 && B % K == 0, AVD_EINVAL, "%s: the %d queues must divide the batch %d", what, K, B);
+    AVD_REQUIRE(((double)(B / K) * g->stride + 8.6e9) * (double)slot_len + (double)L < 9.0e18, AVD_EINVAL,
+                "%s: B %d * stride %d * slot_len %d leaves the signed 64-bit positions", what, B / K, g->stride, slot_len);
+    AVD_REQUIRE((double)K * (double)outer * (double)g->P * (double)inner < 9.0e18 &&
+                    (double)B * (double)outer * (double)L * (double)inner < 9.0e18,
                 AVD_EUNSUPPORTED, "%s: too many values", what);
-    const int64_t nc = outer * g->P * inner, n = (int64_t)B * outer * L * inner;
+    const int64_t nc = K * outer * g->P * inner, n = (int64_t)B * outer * L * inner;
     for (const float* p : outs) {
         if (!p) continue;
         AVD_REQUIRE(!(p < g->known + nc && g->known < p + n) && !(g->mask && p < g->mask + nc && g->mask < p + n), AVD_EINVAL,
@@ -1246,19 +1330,30 @@ int make_clip_guide(const avd_clip_guide* g, int B, int64_t outer, int L, int sl
 }
 
 int check_clip_guide(const avd_clip_guide* g, int B, int64_t outer, int L, int slots, int slot_len, int64_t inner, const float* out,
-                     const float* x0_hist) {
+                     const float* x0_hist, int K = 1) {
     ClipGuideState cg;
-    return make_clip_guide(g, B, outer, L, slots, slot_len, inner, {out, x0_hist}, cg);
+    return make_clip_guide(g, B, outer, L, slots, slot_len, inner, {out, x0_hist}, cg, "clip_guide", K);
+}
+// the descriptor's checks for the whole step, before the model runs: g (null: no guide) has passed check_clip_guide with cq->K;
+// step: the update reads the step seeds (eta > 0)
+int check_clip_queues(const avd_clip_queues* cq, const avd_clip_guide* g, bool step, int B, int64_t outer, int L, int64_t inner,
+                      const float* out, const float* x0_hist) {
+    ClipQueues q;
+    const int64_t canvas = g ? outer * g->P * inner : 0;
+    return make_clip_queues("clip_queues", cq, B, step, g != nullptr, {out, x0_hist}, (int64_t)B * outer * L * inner, g ? g->known : nullptr,
+                            g ? g->mask : nullptr, (cq ? cq->K : 0) * canvas, canvas, q);
 }
 
 // The stand-alone pass (avd_clip_guide_slots_f32): out = blend(m(p), q_p(tau[b, s]), z) per slot.  A block lies inside one slot of one
 // (b, o) row — bpr blocks cover the longest row, the last slot's with the uncovered tail — so the slot's tau is block-uniform, and a
 // block whose slot is left (AVD_SLOT_LEAVE) returns before it loads anything when the call is in place, and copies z otherwise.
-// V lanes as fifo_move_kernel.
-template <int V>
+// V lanes as fifo_move_kernel.  Q: empty, or one ClipQueues ("clip batch keying"): b is block-uniform, so the queue's guide is resolved
+// once per block, behind the left block's return, and the positions walk by the sample's index inside its queue.
+template <int V, class... Q>
 __global__ __launch_bounds__(256) void clip_guide_slots_kernel(ClipGuideState cg, const int64_t* __restrict__ tau,
                                                                const float* __restrict__ abar, int T_train, const float* z, float* out,
-                                                               int64_t outer, int L, int S, int64_t inner, int bpr) {      // z may be out
+                                                               int64_t outer, int L, int S, int64_t inner, int bpr, Q... q) {      // z may be out
+    static_assert(sizeof...(Q) == (PackHas<ClipQueues, Q...>::value ? 1 : 0), "the pack: optionally one ClipQueues");
     int64_t r = blockIdx.x;
     const int chunk = (int)(r % bpr);
     r /= bpr;
@@ -1269,6 +1364,12 @@ __global__ __launch_bounds__(256) void clip_guide_slots_kernel(ClipGuideState cg
     const int64_t t = tau[(int64_t)b * S + s];
     const bool leave = t == INT64_MIN;
     if (leave && out == z) return;
+    [[maybe_unused]] int bq = b;      // the sample index the positions walk by
+    if constexpr (sizeof...(Q) > 0) {
+        const QueueOf qo = queue_of(q..., b);
+        cg = queue_clip_guide(q..., cg, qo.k);
+        bq = qo.b;
+    }
     const int l0 = s * cg.slot_len;
     const int nl = s == S - 1 ? L - l0 : cg.slot_len;      // the uncovered tail follows the last slot
     const int64_t j = ((int64_t)chunk * 256 + threadIdx.x) * V;      // the lane's first element of the slot's [nl, inner] piece
@@ -1278,11 +1379,11 @@ __global__ __launch_bounds__(256) void clip_guide_slots_kernel(ClipGuideState cg
     const int64_t at = (((int64_t)b * outer + o) * L + l) * inner + i;
     if constexpr (V == 4) {
         f32x4 v = *reinterpret_cast<const f32x4*>(z + at);
-        if (!leave) v = clip_guide_apply4(cg, guide_coef(abar, T_train, t), b, o, l, i, inner, v);
+        if (!leave) v = clip_guide_apply4(cg, guide_coef(abar, T_train, t), bq, o, l, i, inner, v);
         *reinterpret_cast<f32x4*>(out + at) = v;
     } else {
         float v = z[at];
-        if (!leave) v = clip_guide_apply1(cg, guide_coef(abar, T_train, t), b, o, l, i, inner, v);
+        if (!leave) v = clip_guide_apply1(cg, guide_coef(abar, T_train, t), bq, o, l, i, inner, v);
         out[at] = v;
     }
 }
@@ -1449,13 +1550,26 @@ struct DrawBody {
     float* out;
     StreamMap map;
     uint32_t tag;
-    template <Lanes F, bool> __device__ __forceinline__ void lane(const PassDims& d, const PassLane& ln) const {
+    template <Lanes F, bool> __device__ __forceinline__ void lane(const PassDims& d, const PassLane& ln) const { draw<F>(d, ln, map, ln.b); }
+    // m, bm: the stream and the sample index the position walks by (the lane's own, or its queue's); the time word is the sample's
+    template <Lanes F> __device__ __forceinline__ void draw(const PassDims& d, const PassLane& ln, const StreamMap& m, int bm) const {
         int s = 0;
         if (d.S > 1) {
             s = ln.l / d.slot_len;
             if (s > d.S - 1) s = d.S - 1;
         }
-        lane_store<F>(out + ln.at, lane_normal4<F>(map, d, ln, (uint32_t)t_now[(int64_t)ln.b * d.S + s], tag), ln.n);
+        PassLane lm = ln;
+        lm.b = bm;
+        lane_store<F>(out + ln.at, lane_normal4<F>(m, d, lm, (uint32_t)t_now[(int64_t)ln.b * d.S + s], tag), ln.n);
+    }
+};
+// the draw of a clip batch ("clip batch keying"): queue k's seed in the map, the sample's index inside its queue in b's place
+struct QueueDrawBody {
+    DrawBody d;
+    ClipQueues q;
+    template <Lanes F, bool> __device__ __forceinline__ void lane(const PassDims& pd, const PassLane& ln) const {
+        const QueueOf qo = queue_of(q, ln.b);
+        d.template draw<F>(pd, ln, queue_stream_map(q, d.map, qo.k), qo.b);
     }
 };
 
@@ -1535,6 +1649,7 @@ struct StreamPass {
     const int64_t *t_from, *t_to;     // the draw's t_now is t_to; a guide's tau is both
     const float *abar, *z;            // z: may be null under Guide
     float* out;
+    const avd_clip_queues* queues;    // Clip keying alone, or null: the batch is K queues ("clip batch keying")
 };
 // what the checks leave for the launch
 struct PassPlan {
@@ -1542,6 +1657,8 @@ struct PassPlan {
     DrawBody draw;
     BlendBody blend;
     ClipGuideState cg;
+    bool queues;                      // cq rides along: the draw's QueueDrawBody, the clip guide's pack
+    ClipQueues cq;
     Lanes lanes;
     int64_t n;                        // lanes; ClipSlots: blocks
     int bpr;
@@ -1575,7 +1692,8 @@ int stream_pass_check(const StreamPass& d, PassPlan& p) {
     // the guide's checks come first in a pass of the guide alone, and behind the pass's own otherwise
     auto guide = [&]() -> int {
         if (clip)
-            return make_clip_guide(static_cast<const avd_clip_guide*>(d.guide), d.B, d.outer, d.L, d.slots, d.slot_len, d.inner, {d.out}, p.cg, w);
+            return make_clip_guide(static_cast<const avd_clip_guide*>(d.guide), d.B, d.outer, d.L, d.slots, d.slot_len, d.inner, {d.out}, p.cg, w,
+                                   d.queues ? d.queues->K : 1);
         if (keyed && !g) return AVD_OK;
         if (d.keying == Keying::Sample) {
             if (int rc = check_latent_guide(g, d.B, d.inner, d.out, nullptr)) return rc;
@@ -1608,6 +1726,12 @@ int stream_pass_check(const StreamPass& d, PassPlan& p) {
                 "%s: out must be z or not overlap it", w);      // the guide entries' contract asks it of known / mask alone
     if (keyed)
         if (int rc = guide()) return rc;
+    if (d.queues) {      // the entries that take a descriptor require it; the canvases as the guide holds them, before `everywhere`
+        const int64_t canvas = clip ? d.outer * p.cg.P * d.inner : 0;
+        if (int rc = make_clip_queues(w, d.queues, d.B, draw, clip, {d.out}, total, clip ? p.cg.known : nullptr, clip ? p.cg.mask : nullptr,
+                                      d.queues->K * canvas, canvas, p.cq)) return rc;
+        p.queues = true;
+    }
     const bool tables = d.keying == Keying::Clip;
     p.d = PassDims{d.outer, d.inner, d.outer * d.L * d.inner, d.L, tables ? d.slots : 1, tables ? d.slot_len : 1};
     if (clip) {
@@ -1640,13 +1764,19 @@ int stream_pass_launch(const StreamPass& d, const PassPlan& p, hipStream_t st) {
     const dim3 grid((unsigned)((p.n + 255) / 256));
     if (d.kind == Pass::ClipSlots)
         with_int<1, 4>(v, [&](auto V) {
-            hipLaunchKernelGGL(clip_guide_slots_kernel<decltype(V)::value>, dim3((unsigned)p.n), dim3(256), 0, st, p.cg, d.t_to, d.abar,
-                               d.T_train, d.z, d.out, d.outer, d.L, d.slots, d.inner, p.bpr);
+            if (p.queues)
+                hipLaunchKernelGGL((clip_guide_slots_kernel<decltype(V)::value, ClipQueues>), dim3((unsigned)p.n), dim3(256), 0, st, p.cg,
+                                   d.t_to, d.abar, d.T_train, d.z, d.out, d.outer, d.L, d.slots, d.inner, p.bpr, p.cq);
+            else
+                hipLaunchKernelGGL(clip_guide_slots_kernel<decltype(V)::value>, dim3((unsigned)p.n), dim3(256), 0, st, p.cg, d.t_to, d.abar,
+                                   d.T_train, d.z, d.out, d.outer, d.L, d.slots, d.inner, p.bpr);
         });
     else
         with_int<(int)Lanes::One, (int)Lanes::Guarded4, (int)Lanes::Float4>((int)p.lanes, [&](auto F) {
             constexpr Lanes f = (Lanes) decltype(F)::value;
-            if (d.kind == Pass::Draw)
+            if (d.kind == Pass::Draw && p.queues)
+                hipLaunchKernelGGL((stream_pass_kernel<f, QueueDrawBody>), grid, dim3(256), 0, st, QueueDrawBody{p.draw, p.cq}, p.d, p.n);
+            else if (d.kind == Pass::Draw)
                 hipLaunchKernelGGL((stream_pass_kernel<f, DrawBody>), grid, dim3(256), 0, st, p.draw, p.d, p.n);
             else if (d.kind == Pass::Renoise)
                 hipLaunchKernelGGL((stream_pass_kernel<f, BlendBody>), grid, dim3(256), 0, st, p.blend, p.d, p.n);
@@ -1672,10 +1802,12 @@ int canvas_noise_f32(const avd_noise_key* key, const int64_t* t_now, float* out,
     return stream_pass(StreamPass{"canvas_noise", "canvas noise", "canvas_noise_kernel", true, Keying::Canvas, Pass::Draw, N, L, outer, inner,
                                   hop, 0, 0, key, 0x44444D31u, nullptr, 0, 0, nullptr, t_now, nullptr, nullptr, out}, st);
 }
+// cq != nullptr: the batch is K queues ("clip batch keying"), the entry avd_slot_noise_clips_f32
 int slot_noise_f32(const avd_slot_key* key, const int64_t* t_now, float* out, int B, int64_t outer, int L, int slots, int slot_len,
-                   int64_t inner, hipStream_t st) {
-    return stream_pass(StreamPass{"slot_noise", "slot noise", "slot_noise_kernel", true, Keying::Clip, Pass::Draw, B, L, outer, inner, 0, slots,
-                                  slot_len, key, SLOT_TAG, nullptr, 0, 0, nullptr, t_now, nullptr, nullptr, out}, st);
+                   int64_t inner, hipStream_t st, const avd_clip_queues* cq = nullptr) {
+    return stream_pass(StreamPass{cq ? "slot_noise_clips" : "slot_noise", "slot noise", cq ? "slot_noise_clips_kernel" : "slot_noise_kernel",
+                                  true, Keying::Clip, Pass::Draw, B, L, outer, inner, 0, slots, slot_len, key, SLOT_TAG, nullptr, 0, 0,
+                                  nullptr, t_now, nullptr, nullptr, out, cq}, st);
 }
 int latent_guide_f32(const avd_latent_guide* g, const int64_t* tau, const float* abar, int T_train, const float* z, float* out, int B,
                      int64_t per, hipStream_t st) {
@@ -1703,9 +1835,11 @@ int renoise_canvas_f32(const avd_noise_key* key, uint32_t visit, const avd_laten
                                   inner, hop, 0, 0, key, visit, g, 0, T_train, t_from, t_to, abar, z, out}, st);
 }
 int clip_guide_slots_f32(const avd_clip_guide* g, const int64_t* tau, const float* abar, int T_train, int everywhere, const float* z,
-                         float* out, int B, int64_t outer, int L, int slots, int slot_len, int64_t inner, hipStream_t st) {
-    return stream_pass(StreamPass{"clip_guide_slots", "", "clip_guide_slots_kernel", true, Keying::Clip, Pass::ClipSlots, B, L, outer, inner, 0,
-                                  slots, slot_len, nullptr, 0, g, everywhere, T_train, tau, tau, abar, z, out}, st);
+                         float* out, int B, int64_t outer, int L, int slots, int slot_len, int64_t inner, hipStream_t st,
+                         const avd_clip_queues* cq = nullptr) {      // cq: as slot_noise_f32, the entry avd_clip_guide_slots_clips_f32
+    return stream_pass(StreamPass{cq ? "clip_guide_slots_clips" : "clip_guide_slots", "", cq ? "clip_guide_slots_clips_kernel" : "clip_guide_slots_kernel",
+                                  true, Keying::Clip, Pass::ClipSlots, B, L, outer, inner, 0, slots, slot_len, nullptr, 0, g, everywhere,
+                                  T_train, tau, tau, abar, z, out, cq}, st);
 }
 
 // ------------------------------------------------------------------ CFG control: per-sample guidance, guidance rescale
@@ -2505,6 +2639,8 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const int64_t e4 = i % per4;
     const int64_t lat = (int64_t)b * g.per + e4 * 4;
     [[maybe_unused]] int tb = b;      // the entry of t_now / t_prev this lane steps with
+    [[maybe_unused]] QueueOf qo{0, b};      // "clip batch keying": the lane's queue; a pack without a ClipQueues is not touched
+    if constexpr (PackHas<ClipQueues, Key...>::value) qo = queue_of(pack_get<ClipQueues>(nk...), b);
     if constexpr (SLOT) {             // per lane: the slot of latent frame tt is tt / t; a held slot keeps z
         const int tt = (int)((e4 / ((int64_t)(g.W >> 2) * g.H)) % g.T);
         tb = b * pack_get<SlotTimes>(nk...).S + tt / g.t;
@@ -2536,7 +2672,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     f32x4 zn = {0.f, 0.f, 0.f, 0.f};
     if constexpr (PackHas<SlotKey, Key...>::value) {      // the clip-keyed draw of a stepping slot: the (c, t) slice of the canvas-keyed draw
         const int64_t hw4 = ((int64_t)g.H * g.W) >> 2, r = e4 / hw4;
-        zn = slot_normal4(pack_get<SlotKey>(nk...), b, r / g.T, (int)(r % g.T), (e4 % hw4) * 4, hw4 * 4, (uint32_t)t_now[tb]);
+        zn = slot_normal4(lane_slot_key(qo, nk...), qo.b, r / g.T, (int)(r % g.T), (e4 % hw4) * 4, hw4 * 4, (uint32_t)t_now[tb]);
     } else if constexpr (CANVAS) {      // the canvas-keyed draw: this lane's float4 lies inside one (c, t) slice (W % 4 == 0)
         const int64_t hw4 = ((int64_t)g.H * g.W) >> 2, r = e4 / hw4;
         zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, r / g.T, (int)(r % g.T), (e4 % hw4) * 4, hw4 * 4, (uint32_t)t_now[b]);
@@ -2589,7 +2725,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     }
     if constexpr (PackHas<ClipGuideState, Key...>::value) {      // the clip-keyed guide of a stepping slot: q at the slot's own t_prev
         const int64_t hw4 = ((int64_t)g.H * g.W) >> 2, r = e4 / hw4;
-        o = clip_guide_apply4(pack_get<ClipGuideState>(nk...), guide_coef(abar, T_train, t_prev[tb]), b, r / g.T, (int)(r % g.T),
+        o = clip_guide_apply4(lane_clip_guide(qo, nk...), guide_coef(abar, T_train, t_prev[tb]), qo.b, r / g.T, (int)(r % g.T),
                               (e4 % hw4) * 4, hw4 * 4, o);
     }
     *reinterpret_cast<f32x4*>(z_out + lat) = o;
@@ -2618,6 +2754,8 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     const int b = blockIdx.x / groups_per_sample, grp = blockIdx.x % groups_per_sample;
     const int n0 = grp * GT;                                            // first token of the group (GT divides W / w: one (t', h') row)
     [[maybe_unused]] int tb = b;      // the entry of t_now / t_prev this block steps with
+    [[maybe_unused]] QueueOf qo{0, b};      // "clip batch keying": block-uniform, so the seeds are uniform loads; a pack without a ClipQueues is not touched
+    if constexpr (PackHas<ClipQueues, Key...>::value) qo = queue_of(pack_get<ClipQueues>(nk...), b);
     [[maybe_unused]] bool hold = false;
     if constexpr (SLOT) {             // the block's tokens share t': one slot, one pair, and the hold is block-uniform
         tb = b * pack_get<SlotTimes>(nk...).S + n0 / (g.Wt * g.Ht);
@@ -2698,7 +2836,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         f32x4 o;
         [[maybe_unused]] f32x4 zn = {0.f, 0.f, 0.f, 0.f};      // the unkeyed DPM update (eta == 0) draws nothing
         if constexpr (PackHas<SlotKey, Key...>::value) {      // the clip-keyed draw: the canvas-keyed decomposition, the block's slot timestep
-            zn = slot_normal4(pack_get<SlotKey>(nk...), b, cc, tq * g.t + tt, (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo,
+            zn = slot_normal4(lane_slot_key(qo, nk...), qo.b, cc, tq * g.t + tt, (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo,
                               (int64_t)g.H * g.W, (uint32_t)t_now[tb]);
         } else if constexpr (CANVAS) {      // element (c, t, h, w) of window b: canvas position from t, element (c, h W + w) of its slice
             zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, cc, tq * g.t + tt, (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo,
@@ -2730,7 +2868,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
             o = canvas_guide_apply4(pack_get<CanvasGuideState>(nk...), gc, b, lat, lat - (int64_t)b * g.per, cc, tq * g.t + tt,
                                     (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo, (int64_t)g.H * g.W, o);
         if constexpr (PackHas<ClipGuideState, Key...>::value)      // the clip-keyed guide: the same decomposition, q at the block's slot t_prev
-            o = clip_guide_apply4(pack_get<ClipGuideState>(nk...), guide_coef(abar, T_train, t_prev[tb]), b, cc, tq * g.t + tt,
+            o = clip_guide_apply4(lane_clip_guide(qo, nk...), guide_coef(abar, T_train, t_prev[tb]), qo.b, cc, tq * g.t + tt,
                                   (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo, (int64_t)g.H * g.W, o);
         *reinterpret_cast<f32x4*>(z_out + lat) = o;
     }
@@ -2761,6 +2899,8 @@ struct UpdateKeys {
     SlotCfgState sc;
     bool smom;         // the slot CFG control carries a momentum buffer: sm rides right behind sc
     SlotMomentum sm;
+    bool queues;       // the slot form of a clip batch whose pack holds sk or cg: cq ends the slot pack (clip batch keying)
+    ClipQueues cq;
     DpmState ds;
     NoiseKey nk;
     CanvasKey ck;      // canvas: the seeded draw is keyed by canvas position (ck replaces nk in the pack)
@@ -2844,9 +2984,11 @@ struct SlotKeyDims {
 };
 static int check_slot_update(const char* what, const UpdateArgs& a, int slots, int S, const avd_noise_key* key,
                              const avd_latent_guide* guide, const avd_cfg_control* ctl, int canvas_hop, int guide_hop, UpdateKeys& k,
-                             const avd_slot_key* skey, const SlotKeyDims& skd, const avd_clip_guide* cguide = nullptr, int L = 0) {
+                             const avd_slot_key* skey, const SlotKeyDims& skd, const avd_clip_guide* cguide = nullptr, int L = 0,
+                             const avd_clip_queues* cq = nullptr) {
     AVD_REQUIRE(slots || !skey, AVD_EINVAL, "%s: a slot key rides with slot timesteps (slots > 0)", what);
     AVD_REQUIRE(slots || !cguide, AVD_EINVAL, "%s: a clip guide rides with slot timesteps (slots > 0)", what);
+    AVD_REQUIRE(slots || !cq, AVD_EINVAL, "%s: clip queues ride with slot timesteps (slots > 0)", what);
     if (!slots) return AVD_OK;
     AVD_REQUIRE(slots == S, AVD_EINVAL, "%s: slots %d must equal the geometry's %d slots along the sliding axis", what, slots, S);
     AVD_REQUIRE((a.eta == 0.f || skey) && !a.noise && !key, AVD_EINVAL,
@@ -2861,9 +3003,16 @@ static int check_slot_update(const char* what, const UpdateArgs& a, int slots, i
         if (int rc = make_slot_key(skey, a.B, skd.outer, skd.slot_len, skd.inner, k.sk, what)) return rc;
     k.clip = cguide != nullptr;
     if (cguide) {      // L: the sliding length the positions run over (the guide's checks: include/avdiff_hip.h, "clip-keyed latent guide")
-        if (int rc = make_clip_guide(cguide, a.B, skd.outer, L, S, skd.slot_len, skd.inner, {a.z_out, k.ds.x0_hist}, k.cg, what)) return rc;
+        if (int rc = make_clip_guide(cguide, a.B, skd.outer, L, S, skd.slot_len, skd.inner, {a.z_out, k.ds.x0_hist}, k.cg, what,
+                                     cq ? cq->K : 1)) return rc;
         AVD_REQUIRE(!k.skey || (skey->first == cguide->first && skey->stride == cguide->stride && skey->cursor == cguide->cursor), AVD_EINVAL,
                     "%s: the slot key's first / stride / cursor must equal the clip guide's (one clip position per element)", what);
+    }
+    if (cq) {      // L: as the guide's; a descriptor beside neither a key that is read nor a guide is checked and changes nothing
+        const int64_t canvas = k.clip ? skd.outer * k.cg.P * skd.inner : 0;
+        if (int rc = make_clip_queues(what, cq, a.B, k.skey, k.clip, {a.z_out, k.ds.x0_hist}, (int64_t)a.B * skd.outer * L * skd.inner,
+                                      k.clip ? k.cg.known : nullptr, k.clip ? k.cg.mask : nullptr, cq->K * canvas, canvas, k.cq)) return rc;
+        k.queues = k.skey || k.clip;
     }
     return AVD_OK;
 }
@@ -2877,9 +3026,15 @@ static int check_slot_update(const char* what, const UpdateArgs& a, int slots, i
 template <class F>
 static void with_update_pack(const UpdateKeys& k, bool cond_only, F launch) {
     if (k.slots) {      // a clip-keyed guide ends the slot pack
+        auto qtail = [&](auto... state) {      // the clip queues end a pack that holds a slot key or a clip guide
+            if constexpr (PackHas<SlotKey, decltype(state)...>::value || PackHas<ClipGuideState, decltype(state)...>::value) {
+                if (k.queues) return launch(state..., k.cq);
+            }
+            launch(state...);
+        };
         auto gtail = [&](auto... state) {
-            if (k.clip) launch(state..., k.cg);
-            else launch(state...);
+            if (k.clip) qtail(state..., k.cg);
+            else qtail(state...);
         };
         auto stail = [&](auto... state) {      // a slot CFG control rides behind the key, before the guide; its momentum behind it
             if (k.scfg && k.smom) gtail(state..., k.sc, k.sm);
@@ -2950,7 +3105,7 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key,
                          const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
                          int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg, const avd_slot_key* skey = nullptr,
-                         const avd_clip_guide* cguide = nullptr, const avd_slot_cfg* scfg = nullptr) {
+                         const avd_clip_guide* cguide = nullptr, const avd_slot_cfg* scfg = nullptr, const avd_clip_queues* cq = nullptr) {
     AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "cfg_unpatch_ddim: bad dims");
     Tube g;
     if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
@@ -2971,7 +3126,7 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
     if (int rc = check_fused_update("cfg_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
                                     guide_hop ? &gcv : nullptr, apg, (int64_t)2 * B * g.per * 4, skey)) return rc;
     if (int rc = check_slot_update("cfg_unpatch_ddim", a, slots, T / t, key, guide, ctl, canvas_hop, guide_hop, k, skey,
-                                   SlotKeyDims{C, t, (int64_t)H * W}, cguide, T)) return rc;
+                                   SlotKeyDims{C, t, (int64_t)H * W}, cguide, T, cq)) return rc;
     k.scfg = scfg != nullptr;
     k.sc = sc;
     k.smom = sm.buf != nullptr;
@@ -2995,7 +3150,8 @@ int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now
     static const int tag_clip = prof_tag_id("cfg_unpatch_ddim_kernel<clip guide>");      // as is the clip-guided slot update
     static const int tag_scfg = prof_tag_id("cfg_unpatch_ddim_kernel<slot cfg>");        // and the slot update under a slot CFG control
     static const int tag_smom = prof_tag_id("cfg_unpatch_ddim_kernel<slot momentum>");   // and under its momentum
-    ProfScope prof(k.smom ? tag_smom : scfg ? tag_scfg : apg ? tag_apg : cguide ? tag_clip : tag,
+    static const int tag_queues = prof_tag_id("cfg_unpatch_ddim_kernel<clip queues>");   // and the keyed or guided update of a clip batch
+    ProfScope prof(k.queues ? tag_queues : k.smom ? tag_smom : scfg ? tag_scfg : apg ? tag_apg : cguide ? tag_clip : tag,
                    ((apg && apg->momentum_buf) || k.smom ? 24.0 : cguide ? (cguide->mask ? 24.0 : 20.0) : 16.0) * (double)B * g.per, st);
     with_update_pack(k, false, [&](auto... p) { launch_unpatch(a, g, st, p...); });
     AVD_CHECK_LAUNCH("cfg_unpatch_ddim");
@@ -3045,6 +3201,8 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
     const int D = Ca * len;
     constexpr bool SLOT = PackHas<SlotTimes, Key...>::value;
     [[maybe_unused]] int tb = b;      // the entry of t_now / t_prev this lane steps with
+    [[maybe_unused]] QueueOf qo{0, b};      // "clip batch keying": the lane's queue; a pack without a ClipQueues is not touched
+    if constexpr (PackHas<ClipQueues, Key...>::value) qo = queue_of(pack_get<ClipQueues>(nk...), b);
     if constexpr (SLOT) {             // per lane (stride == len): chunk f / len, the uncovered tail follows the last chunk; a held slot keeps z
         const int sl = f / len;
         tb = b * Na + (sl > Na - 1 ? Na - 1 : sl);
@@ -3112,13 +3270,13 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
             return canvas_guide_apply1(pack_get<CanvasGuideState>(nk...), guide_coef(abar, T_train, t_prev[b]), b, i,
                                        i - (int64_t)b * Ca * F, c, f, 0, 1, v);
         else if constexpr (PackHas<ClipGuideState, Key...>::value)      // the clip-keyed guide: clip position from f, q at the slot's t_prev
-            return clip_guide_apply1(pack_get<ClipGuideState>(nk...), guide_coef(abar, T_train, t_prev[tb]), b, c, f, 0, 1, v);
+            return clip_guide_apply1(lane_clip_guide(qo, nk...), guide_coef(abar, T_train, t_prev[tb]), qo.b, c, f, 0, 1, v);
         else
             return v;
     };
     [[maybe_unused]] float zn = 0.f;      // the unkeyed DPM update (eta == 0) draws nothing
     if constexpr (PackHas<SlotKey, Key...>::value) {      // the clip-keyed draw: clip position from f, element c of its slice, the slot's timestep
-        zn = slot_normal4(pack_get<SlotKey>(nk...), b, c, f, 0, 1, (uint32_t)t_now[tb])[c & 3];
+        zn = slot_normal4(lane_slot_key(qo, nk...), qo.b, c, f, 0, 1, (uint32_t)t_now[tb])[c & 3];
     } else if constexpr (CANVAS) {      // element (c, f) of window b: canvas position from f, element c of its slice (inner == 1)
         zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, c, f, 0, 1, (uint32_t)t_now[b])[c & 3];
     } else if constexpr (SEEDED) {
@@ -3156,7 +3314,8 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
                                float* z_out, int B, int Ca, int F, int len, int stride, hipStream_t st, const avd_noise_key* key,
                                const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
                                int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg, const avd_slot_key* skey = nullptr,
-                               const avd_clip_guide* cguide = nullptr, const avd_slot_cfg* scfg = nullptr) {
+                               const avd_clip_guide* cguide = nullptr, const avd_slot_cfg* scfg = nullptr,
+                               const avd_clip_queues* cq = nullptr) {
     AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: bad dims");
     AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "cfg_untoken_ddim_audio: bad chunking");
     AVD_REQUIRE(!slots || stride == len, AVD_EUNSUPPORTED,
@@ -3178,7 +3337,7 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
     if (int rc = check_fused_update("cfg_untoken_ddim_audio", a, per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
                                     guide_hop ? &gcv : nullptr, apg, (int64_t)2 * B * ag.Na * Ca * len * 4, skey)) return rc;
     if (int rc = check_slot_update("cfg_untoken_ddim_audio", a, slots, ag.Na, key, guide, ctl, canvas_hop, guide_hop, k, skey,
-                                   SlotKeyDims{Ca, len, 1}, cguide, F)) return rc;
+                                   SlotKeyDims{Ca, len, 1}, cguide, F, cq)) return rc;
     k.scfg = scfg != nullptr;
     k.sc = sc;
     k.smom = sm.buf != nullptr;
@@ -3683,6 +3842,47 @@ extern "C" int avd_cfg_untoken_ddim_audio_slots_cfg_f32(const float* eps2, const
     return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, nullptr, z_out, B, Ca, F, len, stride,
                                       static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots, nullptr,
                                       eta > 0.f ? key : nullptr, guide, cfg);
+}
+// the slot forms of a clip batch ("clip batch keying" in the header): the controlled entries' arguments and the descriptor; cfg, key and
+// guide may be null
+extern "C" int avd_cfg_unpatch_ddim_slots_clips_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                                    const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance, float eta,
+                                                    const avd_slot_key* key, const avd_clip_guide* guide, const avd_clip_queues* queues,
+                                                    int slots, float* x0_hist, float* z_out, int B, int C, int T, int H, int W, int t, int h,
+                                                    int w, const avd_slot_cfg* cfg, avd_stream_t stream) {
+    AVD_REQUIRE(queues, AVD_EINVAL, "cfg_unpatch_ddim_slots_clips: null clip queues");
+    AVD_REQUIRE(aligned16(eps2) && aligned16(z) && aligned16(z_out), AVD_EUNSUPPORTED,
+                "cfg_unpatch_ddim_slots_clips: pointers must be 16-byte aligned");
+    AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_unpatch_ddim_slots_clips: slots must be > 0 (got %d)", slots);
+    AVD_REQUIRE(key || !(eta > 0.f), AVD_EINVAL, "cfg_unpatch_ddim_slots_clips: eta > 0 needs a slot key");
+    return cfg_unpatch_ddim_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, nullptr, z_out, B, C, T, H, W, t, h, w,
+                                static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots, nullptr,
+                                eta > 0.f ? key : nullptr, guide, cfg, queues);
+}
+extern "C" int avd_cfg_untoken_ddim_audio_slots_clips_f32(const float* eps2, const float* z, const int64_t* t_last, const int64_t* t_now,
+                                                          const int64_t* t_prev, const float* alpha_bar, int T_train, float guidance,
+                                                          float eta, const avd_slot_key* key, const avd_clip_guide* guide,
+                                                          const avd_clip_queues* queues, int slots, float* x0_hist, float* z_out, int B,
+                                                          int Ca, int F, int len, int stride, const avd_slot_cfg* cfg,
+                                                          avd_stream_t stream) {
+    AVD_REQUIRE(queues, AVD_EINVAL, "cfg_untoken_ddim_audio_slots_clips: null clip queues");
+    AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_untoken_ddim_audio_slots_clips: slots must be > 0 (got %d)", slots);
+    AVD_REQUIRE(key || !(eta > 0.f), AVD_EINVAL, "cfg_untoken_ddim_audio_slots_clips: eta > 0 needs a slot key");
+    return cfg_untoken_ddim_audio_f32(eps2, z, t_now, t_prev, alpha_bar, T_train, guidance, eta, nullptr, z_out, B, Ca, F, len, stride,
+                                      static_cast<hipStream_t>(stream), nullptr, t_last, x0_hist, nullptr, nullptr, 0, 0, slots, nullptr,
+                                      eta > 0.f ? key : nullptr, guide, cfg, queues);
+}
+extern "C" int avd_clip_guide_slots_clips_f32(const avd_clip_guide* g, const avd_clip_queues* queues, const int64_t* tau,
+                                              const float* alpha_bar, int T_train, int everywhere, const float* z, float* out, int B,
+                                              int64_t outer, int L, int slots, int slot_len, int64_t inner, avd_stream_t stream) {
+    AVD_REQUIRE(queues, AVD_EINVAL, "clip_guide_slots_clips: null clip queues");
+    return clip_guide_slots_f32(g, tau, alpha_bar, T_train, everywhere, z, out, B, outer, L, slots, slot_len, inner,
+                                static_cast<hipStream_t>(stream), queues);
+}
+extern "C" int avd_slot_noise_clips_f32(const avd_slot_key* key, const avd_clip_queues* queues, const int64_t* t_now, float* out, int B,
+                                        int64_t outer, int L, int slots, int slot_len, int64_t inner, avd_stream_t stream) {
+    AVD_REQUIRE(queues, AVD_EINVAL, "slot_noise_clips: null clip queues");
+    return slot_noise_f32(key, t_now, out, B, outer, L, slots, slot_len, inner, static_cast<hipStream_t>(stream), queues);
 }
 extern "C" int64_t avd_slot_cfg_stats_bytes(int B, int slots, int64_t per_slot) { return slot_cfg_stats_bytes(B, slots, per_slot); }
 extern "C" int avd_clip_guide_slots_f32(const avd_clip_guide* g, const int64_t* tau, const float* alpha_bar, int T_train, int everywhere,

@@ -732,6 +732,151 @@ def clip_guide_slots(known: Tensor, tau: Tensor, alpha_bar: Tensor, z: Tensor, m
     return out
 
 
+# ---- clip batch keying (include/avdiff_hip.h, "clip batch keying"): the batch is K queues, each under its own seeds and canvases ----
+def queue_seeds(seeds, queues: Optional[int] = None, device=None) -> Tensor:
+    """The K per-queue seeds of a clip batch as ``clip_seeds``' int64 tensor on ``device`` (None: the CPU): K ints, or that tensor
+    already made (a loop uploads it once), which must then be int64 [K] on ``device``.  ``queues`` None takes K from ``seeds``."""
+    if isinstance(seeds, Tensor):
+        d = None if device is None else torch.device(device)      # an index-free device names the current one
+        if not (seeds.dtype == torch.int64 and seeds.is_contiguous() and seeds.dim() == 1 and seeds.numel() >= 1 and
+                (queues is None or seeds.numel() == queues) and
+                (d is None or (seeds.device.type == d.type and (d.index is None or seeds.device.index == d.index)))):
+            raise ValueError(f"a seeds tensor must be clip_seeds' int64 [{'K' if queues is None else queues}] on {device or 'the CPU'}, got "
+                             f"{seeds.dtype} {tuple(seeds.shape)} on {seeds.device}")
+        return seeds
+    if isinstance(seeds, (str, bytes)) or not hasattr(seeds, "__len__"):
+        raise ValueError(f"seeds must be a sequence of ints, one per queue, got {seeds!r}")
+    return clip_seeds(seeds, len(seeds) if queues is None else queues, device)
+
+
+def _seed_ints(seeds: Tensor):
+    """the unsigned values of a ``clip_seeds`` tensor"""
+    return [s + 2 ** 64 if s < 0 else s for s in seeds.tolist()]
+
+
+def clip_queues(queues: int, B: int, step_seeds: Optional[Tensor] = None, guide_seeds: Optional[Tensor] = None) -> "L.ClipQueues":
+    """avd_clip_queues for a batch of ``B`` samples: ``queues`` = K >= 1 must divide B; the seeds are ``queue_seeds`` tensors on the
+    buffers' device, or None where the call does not read them.  The struct holds raw pointers: keep the tensors alive."""
+    if isinstance(queues, bool) or not isinstance(queues, int) or queues < 1 or B % queues:
+        raise ValueError(f"queues {queues!r} must be an int >= 1 that divides the batch {B}")
+    for name, s in (("step_seeds", step_seeds), ("guide_seeds", guide_seeds)):
+        if s is not None and not (isinstance(s, Tensor) and s.is_cuda and s.dtype == torch.int64 and s.is_contiguous() and
+                                  tuple(s.shape) == (queues,)):
+            raise ValueError(f"{name} must be queue_seeds' int64 [{queues}] on the device")
+    return L.ClipQueues(queues, L.ptr(step_seeds), L.ptr(guide_seeds))
+
+
+def slot_noise_clips(seeds, t_now: Tensor, shape, slot_len: int, first: int = 0, stride: Optional[int] = None,
+                     cursor: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """``slot_noise`` for a FIFO clip batch (avd_slot_noise_clips_f32; contract in include/avdiff_hip.h, "clip batch keying"): ``shape``
+    is K = len(seeds) queues of B / K samples; sample b is sample b' = b % (B / K) of queue k = b // (B / K), sits on clip position
+    ((first + max(*cursor, 0) + b'*stride) * slot_len + l) mod 2**32 and draws under ``seeds[k]``.  ``seeds``: K ints, or the int64
+    device tensor ``queue_seeds`` makes of them.  Everything else as ``slot_noise``; the values
+    ``DenoiseEngine.step_slots(clip_queues=K, clip_seeds=seeds)`` draws inside its step.
+    A device ``out`` (or none) takes the one launch.  A CPU ``out`` takes the torch statement below, which is the reference: per queue
+    ``slot_noise`` under the queue's seed on the queue's slice of ``t_now``."""
+    shape = _positive_shape(shape)
+    statement = out is not None and isinstance(out, Tensor) and not out.is_cuda
+    dev = None if statement else (out.device if out is not None else
+                                  (t_now.device if isinstance(t_now, Tensor) and t_now.is_cuda else torch.device("cuda", torch.cuda.current_device())))
+    seeds = queue_seeds(seeds, None, dev)
+    K, B = seeds.numel(), shape[0]
+    if B % K:
+        raise ValueError(f"{K} seeds for a batch of {B}: the queues must divide the batch")
+    Bq = B // K
+    if statement:
+        if tuple(out.shape) != shape or out.dtype != torch.float32:
+            raise ValueError(f"out must be a float32 tensor of shape {shape}")
+        t_now = torch.as_tensor(t_now)
+        for k, s in enumerate(_seed_ints(seeds)):
+            sl = slice(k * Bq, (k + 1) * Bq)
+            out[sl] = slot_noise(s, t_now[sl], (Bq,) + shape[1:], slot_len, first, stride, cursor).to(out.device)
+        return out
+    outer, L_, inner = window_dims(shape)
+    t_now, S = _slot_table(t_now, "t_now", B, L_, slot_len)
+    if outer * inner >= 2 ** 34:
+        raise ValueError(f"one clip position holds outer * inner = {outer * inner} elements, the stream keys < 2**34")
+    _check_out(out, shape)
+    key = slot_key(0, first, S if stride is None else stride, cursor, dev)      # the seed is not read: the queues' are
+    cq = clip_queues(K, B, step_seeds=seeds)
+    tn = L.dev_i64(t_now, dev)
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=torch.float32)
+    L.check(L.lib().avd_slot_noise_clips_f32(C.byref(key), C.byref(cq), tn.data_ptr(), out.data_ptr(), B, outer, L_, S, slot_len, inner,
+                                             _st(out)))
+    return out
+
+
+def stack_clip_canvases(canvases, name: str = "known") -> Tensor:
+    """K clip canvases of one shape — a sequence of tensors, or one stacked tensor [K, C, P, H, W] (video) / [K, Ca, P] (audio) — as
+    the stacked tensor; ValueError for none, for differing shapes and for a wrong rank"""
+    if isinstance(canvases, Tensor):
+        t = canvases
+    else:
+        cs = list(canvases)
+        if not cs or any(not isinstance(c, Tensor) or c.shape != cs[0].shape for c in cs):
+            raise ValueError(f"the {name} canvases must be K >= 1 tensors of one shape (the clips run in lockstep), got "
+                             f"{[tuple(c.shape) if isinstance(c, Tensor) else c for c in cs]}")
+        t = torch.stack(cs)
+    if t.dim() not in (3, 5) or t.shape[0] < 1:
+        raise ValueError(f"the {name} canvases must stack to [K, C, P, H, W] (video) or [K, Ca, P] (audio), got {tuple(t.shape)}")
+    return t
+
+
+def clip_guide_slots_clips(known: Tensor, tau: Tensor, alpha_bar: Tensor, z: Tensor, masks: Optional[Tensor] = None, *, slot_len: int,
+                           seeds, first: int = 0, stride: Optional[int] = None, cursor: Optional[Tensor] = None,
+                           everywhere: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """``clip_guide_slots`` for a FIFO clip batch (avd_clip_guide_slots_clips_f32; contract in include/avdiff_hip.h, "clip batch
+    keying"): ``known`` holds K canvases, [K, C, P, H, W] / [K, Ca, P] (``masks`` None or the same shape), ``z`` is K queues of B / K
+    samples; sample b' of queue k sits on clip position (first + max(*cursor, 0) + b'*stride) * slot_len + l, reads canvas k there
+    and takes the known noise of ``seeds[k]``.  ``seeds``: K ints or ``queue_seeds``' device tensor.  Everything else as
+    ``clip_guide_slots``: one in-place call (``out=z``) with ``SLOT_LEAVE`` everywhere but each queue's tail slot puts all K entering
+    slots on their forward paths.
+    A device ``z`` takes the one launch.  A CPU ``z`` takes the torch statement below, which is the reference: per queue
+    ``clip_guide_slots`` with the queue's canvas, mask and seed on the queue's slices of ``tau`` and ``z``.  ``clip_guide_slots``
+    launches on a device, so where there is one the slices go to the current device and the result comes back to ``z``'s."""
+    known = stack_clip_canvases(known)
+    if masks is not None:
+        masks = stack_clip_canvases(masks, "mask")
+        if masks.shape != known.shape:
+            raise ValueError(f"masks shape {tuple(masks.shape)} must be the known canvases' {tuple(known.shape)}")
+    if not isinstance(z, Tensor) or z.dim() != known.dim():
+        raise ValueError("z must be a batch [B,C,T,H,W] (video) or [B,Ca,F] (audio) of the canvases' rank")
+    K, B = known.shape[0], z.shape[0]
+    seeds = queue_seeds(seeds, K, z.device if z.is_cuda else None)
+    if B % K:
+        raise ValueError(f"{K} canvases for a batch of {B}: the queues must divide the batch")
+    Bq = B // K
+    if not z.is_cuda:
+        tau = torch.as_tensor(tau)
+        res = torch.empty_like(z) if out is None else out
+        on = (lambda t: t.cuda().contiguous()) if torch.cuda.is_available() else (lambda t: t)
+        for k, s in enumerate(_seed_ints(seeds)):
+            sl = slice(k * Bq, (k + 1) * Bq)
+            r = clip_guide_slots(on(known[k]), tau[sl], alpha_bar, on(z[sl]), None if masks is None else on(masks[k]), slot_len=slot_len,
+                                 seed=s, first=first, stride=stride, cursor=cursor, everywhere=everywhere)
+            res[sl] = r.to(res.device)
+        return res
+    z = L.dev_f32(z, "z")
+    shape = tuple(z.shape)
+    outer, L_, inner = window_dims(shape)
+    tau, S = _slot_table(tau, "tau", B, L_, slot_len)
+    if not (known.is_cuda and known.dtype == torch.float32 and known.is_contiguous() and known.device == z.device):
+        raise ValueError("known must be contiguous float32 device canvases [K, C, P, H, W] (video) or [K, Ca, P] (audio) on z's device")
+    if masks is not None and not (masks.is_cuda and masks.dtype == torch.float32 and masks.is_contiguous() and masks.device == z.device):
+        raise ValueError("masks must be contiguous float32 device canvases of the known canvases' shape, on z's device")
+    g = clip_guide(known[0], None if masks is None else masks[0], 0, first, S if stride is None else stride, cursor, shape)
+    cq = clip_queues(K, B, guide_seeds=seeds)
+    _check_out(out, shape, z)
+    if out is None:
+        out = torch.empty_like(z)
+    tn = L.dev_i64(tau, z.device)
+    ab = _alpha_bar(alpha_bar, z.device)
+    L.check(L.lib().avd_clip_guide_slots_clips_f32(C.byref(g), C.byref(cq), tn.data_ptr(), ab.data_ptr(), ab.numel(), 1 if everywhere else 0,
+                                                   z.data_ptr(), out.data_ptr(), B, outer, L_, S, slot_len, inner, _st(z)))
+    return out
+
+
 def _slot_step_noise(eta: float, noise: Optional[Tensor], x_t: Tensor, what: str) -> Optional[Tensor]:
     """the explicit noise of the slot mirrors: required when eta > 0 (``slot_noise`` gives the fused step's normals), not read at 0"""
     if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not eta >= 0:

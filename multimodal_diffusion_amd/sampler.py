@@ -627,6 +627,50 @@ class DenoiseEngine:
         if self._clip is not None:
             raise ValueError(f"{what} takes no clip guide ({why}): clear_clip_guide() first")
 
+    # ---- the K clip guides of a FIFO clip batch: one canvas, mask and seed per queue ("clip batch keying"); class-level None, so that
+    # an engine that never sets them (or a shell built without __init__) reads "none"
+    _clips: Optional[tuple] = None
+
+    def set_clip_guides(self, known_canvases, masks=None, *, guide_seeds) -> None:
+        """Guide ``step_slots(clip_queues=K)`` by K clean clip canvases, one per queue of a FIFO clip batch (extension;
+        include/avdiff_hip.h, "clip batch keying"): ``known_canvases`` is K canvases of one shape as ``set_clip_guide`` takes one — a
+        sequence, or a stacked tensor [K, C, P, H, W] / [K, Ca, P]; ``masks`` None (1 everywhere) or K masks, each broadcastable to a
+        canvas (a stacked tensor broadcastable to the stack); ``guide_seeds`` K ints, the seeds of the queues' known-noise streams.
+        Queue k's stepping slots end in the blend with canvas k at the clip positions they hold inside their own queue.  A state of its
+        own: ``set_clip_guide`` stays one canvas for one queue, and ``step``, ``run``, ``fifo_open`` and ``fifo_lookahead`` refuse
+        this one as they refuse that."""
+        k = Fn.stack_clip_canvases(known_canvases)
+        K = k.shape[0]
+        want = self.latent_shape[1:2] + self.latent_shape[3:]
+        if k.dim() != len(self.latent_shape) or tuple(k.shape[1:2]) + tuple(k.shape[3:]) != want or k.shape[2] < 1:
+            raise ValueError(f"known canvases shape {tuple(k.shape)} must be {('K',) + want[:1] + ('P',) + want[1:]}: K times the engine's "
+                             "latent without its batch axis, any P >= 1 along the sliding axis")
+        if not k.is_floating_point():
+            raise TypeError(f"known canvases must be float tensors, got {k.dtype}")
+        if self.embed.B % K:
+            raise ValueError(f"{K} canvases for an engine of batch {self.embed.B}: the queues must divide the batch")
+        seeds = Fn.queue_seeds(guide_seeds, K)
+        m = None
+        if masks is not None:
+            m = masks if isinstance(masks, torch.Tensor) else torch.stack([torch.as_tensor(x).to(torch.float32).expand(tuple(k.shape[1:]))
+                                                                          for x in masks])
+            try:
+                m = m.to(torch.float32).expand(tuple(k.shape))
+            except RuntimeError:
+                raise ValueError(f"masks shape {tuple(m.shape)} does not broadcast to the known canvases' {tuple(k.shape)}") from None
+            if not bool(((m >= 0) & (m <= 1)).all()):
+                raise ValueError("mask values must lie in [0, 1]")
+            m = m.to(self.device).contiguous()
+        self._clips = (k.to(self.device, torch.float32).contiguous().clone(), m, seeds.to(self.device))
+
+    def clear_clip_guides(self) -> None:
+        """Back to the unguided ``step_slots(clip_queues=K)``."""
+        self._clips = None
+
+    def _clips_refusal(self, what: str) -> None:
+        if self._clips is not None:
+            raise ValueError(f"{what} takes no clip guides (they are the K canvases of step_slots(clip_queues=K)): clear_clip_guides() first")
+
     # ---- slot CFG control: guidance by noise level, per-slot guidance rescale and per-slot APG for ``step_slots`` ----
     # slot APG momentum (set_slot_cfg(apg_momentum=)): beta and the two engine-owned [B, per] buffers; class-level, so that an engine
     # that never sets one (or a shell built without __init__) reads "none"
@@ -930,6 +974,7 @@ class DenoiseEngine:
         if self.Xp is None:
             raise RuntimeError("call set_prompt() first")
         self._clip_refusal("step", "a clip guide is keyed by the clip positions of step_slots' slots; a per-sample step is guided by set_known")
+        self._clips_refusal("step")
         self._slot_cfg_refusal("step")
         z = L.dev_f32(z, "z")
         if tuple(z.shape) != self.latent_shape:
@@ -1029,7 +1074,7 @@ class DenoiseEngine:
 
     def step_slots(self, z: torch.Tensor, t_now: torch.Tensor, t_prev: torch.Tensor, out: Optional[torch.Tensor] = None,
                    t_last: Optional[torch.Tensor] = None, clip_first: Optional[int] = None, clip_stride: Optional[int] = None,
-                   clip_cursor: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   clip_cursor: Optional[torch.Tensor] = None, clip_queues: Optional[int] = None, clip_seeds=None) -> torch.Tensor:
         """One CFG step on slot timesteps (extension; include/avdiff_hip.h, "slot timesteps"; avd_denoise_step_slots_f32):
         ``t_now`` / ``t_prev`` are int [B, S] tables, S = ``slots``, one pair per slot of ``slot_len`` latent positions along the
         sliding axis.  Every slot's tokens embed its t_now and its latent takes the DDIM update of its pair; a slot with t_prev ==
@@ -1052,16 +1097,42 @@ class DenoiseEngine:
         Under ``set_slot_cfg`` (avd_denoise_step_slots_cfg_f32; "slot CFG control") every stepping slot's eps is combined with the
         guidance of its own noise level and rescaled, or projected (APG), with statistics over the slot's own elements, before the
         solver update; any solver, any eta, with or without the clip guide.
+        ``clip_queues`` = K (avd_denoise_step_slots_clips_f32; "clip batch keying") steps a FIFO clip batch: the batch is K queues of
+        B / K samples, the walk ``clip_first + k * clip_stride`` restarts in every queue, and at eta > 0 queue k draws its step noise
+        under ``clip_seeds[k]`` — K ints, or the int64 device tensor ``functional.queue_seeds`` makes of them — which stand in for the
+        engine's ``noise_seed`` (not read, and not required); an eta > 0 engine without ``clip_seeds`` is refused.  Under
+        ``set_clip_guides`` (which requires ``clip_queues``, with its K) queue k is guided by its own canvas, mask and seed.  The bits
+        are those of K separate calls on the K slices; ``set_clip_guide``'s one canvas is refused here, and ``clip_seeds`` without
+        ``clip_queues`` is.
         Scope: the scalar guidance or a slot CFG control; a per-sample latent guide (``set_known``), a per-sample CFG control, a window
         consensus, temb_mode "add" and overlapping audio chunks are refused before anything is launched, as is ``t_last`` on a "ddim"
         engine; no unseeded or explicit noise."""
         if self.Xp is None:
             raise RuntimeError("call set_prompt() first")
-        self._slot_refusals(t_last is not None, clip_first)
+        if clip_queues is None:
+            if clip_seeds is not None:
+                raise ValueError("clip_seeds are the step seeds of a clip batch's queues: they need clip_queues")
+            if self._clips is not None:
+                raise ValueError("step_slots under set_clip_guides needs clip_queues: the K canvases guide the K queues of a clip batch")
+        else:
+            if isinstance(clip_queues, bool) or not isinstance(clip_queues, int) or clip_queues < 1 or self.embed.B % clip_queues:
+                raise ValueError(f"clip_queues {clip_queues!r} must be an int >= 1 that divides the batch {self.embed.B}")
+            self._clip_refusal("step_slots(clip_queues=)", "a clip guide is one canvas walked by one queue, and a clip batch holds several: "
+                               "set_clip_guides")
+            if self._clips is not None and self._clips[0].shape[0] != clip_queues:
+                raise ValueError(f"clip_queues {clip_queues} against the {self._clips[0].shape[0]} canvases of set_clip_guides")
+            if self.eta > 0 and clip_seeds is None:
+                raise ValueError("step_slots(clip_queues=K) at eta > 0 draws every queue's step noise under its own seed: pass clip_seeds, "
+                                 "one per queue")
+        self._slot_refusals(t_last is not None, clip_first, seeded=clip_seeds is not None, guided=self._clips is not None)
         S = self.slots
         key = guide = None
-        if self.eta > 0:      # _slot_refusals has asked for clip_first and noise_seed
-            key = Fn.slot_key(self.noise_seed, clip_first, S if clip_stride is None else clip_stride, clip_cursor, self.device)
+        if self.eta > 0:      # _slot_refusals has asked for clip_first and noise_seed (a clip batch: the queues' seeds stand in for it)
+            key = Fn.slot_key(0 if clip_queues is not None else self.noise_seed, clip_first, S if clip_stride is None else clip_stride,
+                              clip_cursor, self.device)
+        if self._clips is not None:      # canvas 0 carries the checks and the addresses; the queues' seeds ride in the descriptor
+            guide = Fn.clip_guide(self._clips[0][0], None if self._clips[1] is None else self._clips[1][0], 0, clip_first,
+                                  S if clip_stride is None else clip_stride, clip_cursor, self.latent_shape)
         if self._clip is not None:      # _slot_refusals has asked for clip_first; the guide shares the key's geometry
             guide = Fn.clip_guide(self._clip[0], self._clip[1], self._clip[2], clip_first, S if clip_stride is None else clip_stride,
                                   clip_cursor, self.latent_shape)
@@ -1082,7 +1153,15 @@ class DenoiseEngine:
         self._last_cond_only = False
         head = (C.byref(self.desc), z.data_ptr(), self.Xp.data_ptr())
         tail = (out.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), L.stream_ptr(self.device))
-        if self._scfg is not None:      # any solver, any eta, with or without the clip guide
+        if clip_queues is not None:      # a clip batch: any solver, any eta, with or without the control and the guides
+            seeds = Fn.queue_seeds(clip_seeds, clip_queues, self.device) if key is not None else None
+            cq = Fn.clip_queues(clip_queues, self.embed.B, seeds, None if guide is None else self._clips[2])
+            L.check(L.lib().avd_denoise_step_slots_clips_f32(head[0], None if self._scfg is None else C.byref(self._scfg),
+                                                             None if key is None else C.byref(key),
+                                                             None if guide is None else C.byref(guide), C.byref(cq),
+                                                             tl[0].data_ptr() if tl else None, self.x0_hist.data_ptr() if tl else None,
+                                                             *head[1:], tn.data_ptr(), tp.data_ptr(), S, *tail))
+        elif self._scfg is not None:      # any solver, any eta, with or without the clip guide
             L.check(L.lib().avd_denoise_step_slots_cfg_f32(head[0], C.byref(self._scfg), None if key is None else C.byref(key),
                                                            None if guide is None else C.byref(guide),
                                                            tl[0].data_ptr() if tl else None, self.x0_hist.data_ptr() if tl else None,
@@ -1102,17 +1181,18 @@ class DenoiseEngine:
             L.check(L.lib().avd_denoise_step_slots_f32(*head, tn.data_ptr(), tp.data_ptr(), S, *tail))
         return out
 
-    def _slot_refusals(self, has_t_last: bool, clip_first: Optional[int] = None) -> None:
+    def _slot_refusals(self, has_t_last: bool, clip_first: Optional[int] = None, seeded: bool = False, guided: bool = False) -> None:
         """what ``step_slots`` refuses of the engine's state, before anything is launched (``fifo_open`` asks the same before it
         allocates, so a graph-replayed queue refuses what the eager one does, in the same words, before any capture).
-        ``clip_first``: as ``step_slots`` takes it; an eta > 0 engine steps only with it and a ``noise_seed``"""
-        if self._clip is not None and clip_first is None:
+        ``clip_first``: as ``step_slots`` takes it; an eta > 0 engine steps only with it and a ``noise_seed``.  ``seeded``: the step of
+        a clip batch, whose queues' ``clip_seeds`` stand in for the ``noise_seed``; ``guided``: it runs under ``set_clip_guides``"""
+        if (self._clip is not None or guided) and clip_first is None:
             raise ValueError("step_slots under a clip guide needs clip_first, at any eta: the guide reads the clip canvas at the clip "
                              "positions the slots hold")
         if self.eta > 0 and clip_first is None:
             raise ValueError("step_slots needs eta == 0, or clip_first on an engine with noise_seed: slots at different timesteps draw "
                              "their eta > 0 noise by the clip position they hold (unkeyed noise is out of scope)")
-        if self.eta > 0 and self.noise_seed is None:
+        if self.eta > 0 and self.noise_seed is None and not seeded:
             raise ValueError("step_slots(clip_first=...) at eta > 0 draws its noise from the engine's noise_seed: build the engine with "
                              "one (unseeded and explicit noise are not supported there)")
         if self.solver == "ddim" and has_t_last:
@@ -1195,6 +1275,7 @@ class DenoiseEngine:
         (``set_slot_cfg(apg_momentum=)``) follows the history's map in a ``functional.fifo_carry`` launch behind it, at either ``shift``."""
         self._clip_refusal("fifo_lookahead", "the duplicated slots of overlapping windows are refreshed from their owner copies, and the guide's "
                            "tail pass has no lookahead form yet")
+        self._clips_refusal("fifo_lookahead")
         if shift == 1:
             seed = self.noise_seed if seed is None else seed
             if seed is None:
@@ -1226,6 +1307,7 @@ class DenoiseEngine:
         prompt_den``: the prompt of m = 0 and ``fifo_steady``'s come from ``functional.fifo_prompt_gather_frac`` off the same cursor
         (first = 0, stride = S).  ``prompt_den`` == 1 is the integer gather, launch for launch."""
         self._clip_refusal("fifo_open", "the replayed queue's chain of launches has no guided tail pass: the guided queue runs eagerly")
+        self._clips_refusal("fifo_open")
         B, S, sl = self.embed.B, self.slots, self.slot_len
         ramp_now, ramp_prev, steady_now, steady_prev = su.fifo_plan(sched, S)
         n = ramp_now.shape[0] + 1
@@ -1466,6 +1548,7 @@ class DenoiseEngine:
         cur -> other -> cur between the two latent buffers it was captured on, so it is replayed only while the trajectory sits in
         its source buffer; a single eager step puts it there.  A renoise pair works in place in ``cur`` and swaps nothing."""
         self._clip_refusal("run", "a clip guide is keyed by the clip positions of step_slots' slots; a trajectory is guided by set_known")
+        self._clips_refusal("run")
         self._slot_cfg_refusal("run")
         self.check_schedule(sched)
         segs = su.trajectory_segments(sched, self.guidance_interval)

@@ -466,7 +466,8 @@ def _fifo_denoise_eager(engine: DenoiseEngine, pc: torch.Tensor, prompt_hop: int
 @torch.no_grad()
 def fifo_denoise_clips(engine: DenoiseEngine, prompt_canvases, prompt_hop: int, sched, n_slots: int, noise_seeds, prompt_den: int = 1,
                        prompt_interp: Optional[str] = None, guidance_by_level=None, rescale_by_level=None, apg: Optional[dict] = None,
-                       apg_momentum: Optional[float] = None) -> torch.Tensor:
+                       apg_momentum: Optional[float] = None, step_seeds=None, init_canvases=None, masks=None, guide_seeds=None,
+                       guide_start: str = "noise") -> torch.Tensor:
     """``fifo_denoise`` for K independent clips at once (include/avdiff_hip.h, "FIFO clip batch"): the engine's batch B = K * B_q is K
     queues in lockstep, queue k the samples k * B_q .. (k + 1) * B_q - 1 under prompt ``prompt_canvases[k]`` and seed
     ``noise_seeds[k]``, and every model call finishes one slot of every clip.  The queue's own batch is pinned to the schedule (B_q * S
@@ -483,10 +484,23 @@ def fifo_denoise_clips(engine: DenoiseEngine, prompt_canvases, prompt_hop: int, 
     and its slot momentum and writes the K heads into the result in one launch.  Nothing else on the host depends on K, and the loop
     never synchronises.  Clip k's samples see only their own prompt, tables and seed, so its canvas does not depend on the other clips
     of the batch; equal bits across different batch sizes are not promised (the GEMMs may pick a kernel by row count).
-    Limits, refused before anything is allocated: an engine with eta > 0 (the clip-keyed slot noise has one seed and one clip-position
-    walk per call, so the K clips would draw the same step normals; per-clip step-noise keys are a later change), an engine with a
-    clip guide (one canvas, one queue), K = 0, canvases of differing shapes, a seed count other than K.  The replayed queue, the
-    lookahead queue, a context and an init canvas are ``fifo_denoise``'s alone; the clips run in lockstep and so share ``n_slots``."""
+    ``step_seeds`` (K ints; include/avdiff_hip.h, "clip batch keying") admits an eta > 0 engine: it runs ``fifo_denoise``'s stochastic
+    loop per queue, every ``step_slots`` under ``clip_queues=K, clip_seeds=step_seeds`` and keyed by the clip slot at slot 0 of each
+    queue (``schedule_utils.fifo_slot_keying``, stride S inside a queue), so clip k draws the step normals ``fifo_denoise`` draws on an
+    engine with ``noise_seed=step_seeds[k]``.  The engine's own ``noise_seed`` is not read.  On an eta == 0 engine ``step_seeds`` is
+    checked (count and types) and otherwise ignored: nothing is drawn, the same launches, the same bits.
+    ``init_canvases`` (K clean latent canvases of one shape, or a stacked tensor [K, C, P, H, W] / [K, Ca, P]) runs the guided queue
+    per clip, ``fifo_denoise(init_canvas=)`` K times over: ``masks`` None or K masks (each broadcastable to a canvas), ``guide_seeds``
+    K ints (None = K zeros, as ``guide_seed`` defaults to 0), ``guide_start`` "noise" or "init" with the truncated schedule, as
+    there.  The start goes through one ``functional.clip_guide_slots_clips`` call at s_0, each ``fifo_shift_clips`` is followed by one
+    in-place call for the K entering tails, and every step runs under ``engine.set_clip_guides`` (set for the call, cleared after
+    it): a held region leaves queue k equal to canvas k bit for bit.  The guided shift inside the clip batch's own launch is not
+    built; ``masks`` or a ``guide_start`` other than "noise" without ``init_canvases`` is refused.
+    Limits, refused before anything is allocated: an engine with eta > 0 and no ``step_seeds`` (the clip-keyed slot noise would have one
+    seed and one clip-position walk per call, so the K clips would draw the same step normals), an engine with a clip guide or clip
+    guides of its own (``set_clip_guide`` is one canvas, one queue; pass ``init_canvases``), K = 0, canvases of differing shapes, a
+    seed or canvas count other than K.  The replayed queue, the lookahead queue and a context are ``fifo_denoise``'s alone; the clips
+    run in lockstep and so share ``n_slots``."""
     if not isinstance(engine, DenoiseEngine):
         raise TypeError("fifo_denoise_clips drives a DenoiseEngine")
     scfg = None
@@ -506,10 +520,26 @@ def fifo_denoise_clips(engine: DenoiseEngine, prompt_canvases, prompt_hop: int, 
         raise ValueError(f"the {K} prompt canvases must be tensors of one shape (the clips run in lockstep), got "
                          f"{[tuple(p.shape) if isinstance(p, torch.Tensor) else p for p in pcs]}")
     seeds = Fn.clip_seeds(noise_seeds, K)
-    if engine.eta > 0:
+    if step_seeds is not None:
+        step_seeds = Fn.clip_seeds(step_seeds, K)
+    if engine.eta > 0 and step_seeds is None:
         raise ValueError(f"fifo_denoise_clips needs eta == 0 (the engine has eta = {engine.eta}): the clip-keyed slot noise has one seed "
-                         "and one clip-position walk per call, so the K clips would draw the same step normals")
+                         "and one clip-position walk per call, so the K clips would draw the same step normals; pass step_seeds, one "
+                         "per clip, for per-clip step noise")
     engine._clip_refusal("fifo_denoise_clips", "a clip guide is one canvas walked by one queue, and a clip batch holds several")
+    if engine._clips is not None:
+        raise ValueError("fifo_denoise_clips sets the engine's clip guides for the call: clear_clip_guides() first and pass init_canvases")
+    if guide_start not in ("noise", "init"):
+        raise ValueError(f"guide_start must be 'noise' or 'init', got {guide_start!r}")
+    if init_canvases is None and (masks is not None or guide_seeds is not None or guide_start != "noise"):
+        raise ValueError("masks, guide_seeds and guide_start belong to the clip guides: pass init_canvases")
+    if init_canvases is not None:
+        init_canvases = Fn.stack_clip_canvases(init_canvases, "init")
+        if init_canvases.shape[0] != K:
+            raise ValueError(f"{init_canvases.shape[0]} init canvases for {K} clips: fifo_denoise_clips needs one canvas per clip")
+        if masks is not None and not isinstance(masks, torch.Tensor) and len(masks) != K:
+            raise ValueError(f"{len(masks)} masks for {K} clips: fifo_denoise_clips needs one mask per clip, or None")
+        guide_seeds = Fn.clip_seeds([0] * K if guide_seeds is None else guide_seeds, K)
     B, S, sl = engine.embed.B, engine.slots, engine.slot_len
     n = su.fifo_plan(sched, 1)[0].shape[0] + 1      # the schedule's own refusals, and its steps
     if B % K or (B // K) * S != n:
@@ -523,7 +553,11 @@ def fifo_denoise_clips(engine: DenoiseEngine, prompt_canvases, prompt_hop: int, 
         raise ValueError(f"(n {n} + n_slots {n_slots}) * slot_len {sl} exceeds the stream's 2**32 canvas positions")
     dev = engine.device
     multistep = engine.solver == "dpmpp_2m"
-    engine._slot_refusals(multistep, None)
+    keyed, guided = engine.eta > 0, init_canvases is not None
+    off, stride = su.fifo_slot_keying(S, 0)
+    # the clip slot at slot 0 of sample 0 of every queue before the step of steady iteration m: read by the step noise and by the guides
+    first = (lambda m: m + off) if keyed or guided else (lambda m: None)
+    engine._slot_refusals(multistep, first(0), seeded=keyed, guided=guided)
     Lp = fifo_prompt_len(engine, pcs[0])
     pcs = [L.dev_f32(p.to(dev), "prompt canvas") for p in pcs]
     s0 = int(torch.as_tensor(sched).reshape(-1)[0])
@@ -537,15 +571,33 @@ def fifo_denoise_clips(engine: DenoiseEngine, prompt_canvases, prompt_hop: int, 
     sources = [_fifo_prompt_source(p, Bq, S, prompt_hop, Lp, S, 0, frac) for p in pcs]
     windows = (lambda m: torch.cat([w(m) for w in sources], 0))
     canvases = torch.empty((K, outer, n_slots * sl) + tuple(engine.latent_shape[3:]), device=dev, dtype=torch.float32)
-    with _slot_cfg_scope(engine, scfg):
-        engine.set_prompt(windows(0))
-        for r in range(n - 1):
-            z, other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other, t_last=ramp_last[r] if multistep else None), z
-        for m in range(n_slots):
-            if m:
-                engine.set_prompt(windows(m))
-            other = engine.step_slots(z, tabs[2], tabs[3], out=other, t_last=steady_last)
-            z = engine.fifo_shift_clips(other, K, n + m, s0, seeds_dev, canvases, m)
+    # the plain deterministic batch steps as it always has; per-clip keys or guides ride on step_slots(clip_queues=K)
+    kw = dict(clip_stride=stride, clip_queues=K, clip_seeds=step_seeds.to(dev) if keyed else None) if keyed or guided else {}
+    if guided:
+        engine.set_clip_guides(init_canvases, masks, guide_seeds=guide_seeds)
+    try:
+        with _slot_cfg_scope(engine, scfg):
+            if guided:      # the start, and after every shift the K entering tails, on their forward paths at s_0
+                known, gmask, gseeds = engine._clips
+                ab = engine.alpha_bar.to(dev, torch.float32)
+                guide = dict(slot_len=sl, seeds=gseeds, everywhere=guide_start == "init")
+                tails = torch.full((B, S), Fn.SLOT_LEAVE, dtype=torch.long, device=dev)
+                tails[Bq - 1::Bq, S - 1] = s0
+                Fn.clip_guide_slots_clips(known, torch.full((B, S), s0, dtype=torch.long, device=dev), ab, z, gmask, first=0, out=z, **guide)
+            engine.set_prompt(windows(0))
+            for r in range(n - 1):
+                z, other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other, t_last=ramp_last[r] if multistep else None,
+                                             clip_first=first(0), **kw), z
+            for m in range(n_slots):
+                if m:
+                    engine.set_prompt(windows(m))
+                other = engine.step_slots(z, tabs[2], tabs[3], out=other, t_last=steady_last, clip_first=first(m), **kw)
+                z = engine.fifo_shift_clips(other, K, n + m, s0, seeds_dev, canvases, m)
+                if guided:      # clip slot n + m entered every queue, now that clip slot m + 1 is at its slot 0
+                    Fn.clip_guide_slots_clips(known, tails, ab, z, gmask, first=m + 1, out=z, **guide)
+    finally:
+        if guided:
+            engine.clear_clip_guides()
     return canvases
 
 
@@ -941,18 +993,22 @@ def _stream_generate_fifo(cfg: Dict, pc, mods: Dict, device, prompt_modality: st
     return res
 
 
-def _fifo_clips_refusals(cfg: Dict, opts: dict, K: int, has_init: bool, has_mask: bool) -> None:
+def _fifo_clips_refusals(cfg: Dict, opts: dict, K: int, has_init: bool, has_mask: bool, noise_seed=None) -> None:
     """What ``stream_generate(sampler="fifo")`` refuses of a LIST of prompt clips, before anything is read or encoded: the limits of
-    ``fifo_denoise_clips`` (``opts``: ``_fifo_options``' result)"""
+    ``fifo_denoise_clips`` (``opts``: ``_fifo_options``' result).  ``noise_seed``: a list of K ints keys the step noise per clip
+    (``fifo_denoise_clips(step_seeds=)``) and admits ``sampling.ddim_eta`` > 0; an int or None does not"""
     if K < 1:
         raise ValueError("a list of prompt clips needs at least one clip, got an empty one")
     if has_init or has_mask:
         raise ValueError("a list of prompt clips takes no init clip or mask: the clip guide is one canvas walked by one queue, and the "
                          "clips share an engine (run a guided clip on its own)")
     eta = float(cfg["sampling"].get("ddim_eta", 0.0))
-    if eta > 0:
+    if isinstance(noise_seed, (list, tuple)):
+        Fn.clip_seeds(noise_seed, K)      # one step seed per clip, each a seed of the stream
+    elif eta > 0:
         raise ValueError(f"a list of prompt clips needs sampling.ddim_eta == 0 (got {eta:g}): the queue's step noise has one seed and one "
-                         "clip-position walk per call, so the clips would draw the same step normals")
+                         "clip-position walk per call, so the clips would draw the same step normals; a noise_seed list of one int per "
+                         "clip keys the step noise per clip")
     if opts["graph"]:
         raise ValueError("a list of prompt clips runs the plain eager queue: fifo['graph'] True is refused (the replayed queue's device "
                          "cursors and clip canvas serve one clip)")
@@ -1003,9 +1059,12 @@ def _stream_generate_fifo_clips(cfg: Dict, pc, mods: Dict, device, prompt_modali
         prompt_canvases.append(canvas_from_windows(Fn.window_consensus(z_p, geo.hop_p), geo.hop_p))
     eng = P.build_engine(pc._replace(rescale=0.0, interval=None, apg=None), adapt_v=mods["adapt_v"], adapt_a=mods["adapt_a"],
                          core=mods["core"], head=mods["head"], tstep_dim=mods["tstep_dim"],
-                         latent_shape=(geo.B, lat[0], geo.S * geo.slot_len) + tuple(lat[2:]), n_prompt=n_prompt, noise_seed=noise_seed)
+                         latent_shape=(geo.B, lat[0], geo.S * geo.slot_len) + tuple(lat[2:]), n_prompt=n_prompt,
+                         noise_seed=noise_seed[0] if isinstance(noise_seed, (list, tuple)) else noise_seed)
+    # a noise_seed list is the K clips' step seeds: the engine's own seed (which the SDE solver asks for at construction) is not read
     canvases = fifo_denoise_clips(eng, prompt_canvases, geo.prompt_hop, sched, geo.n_slots, seeds, prompt_den=geo.prompt_den,
-                                  prompt_interp=opts["prompt_interp"], **ctl)
+                                  prompt_interp=opts["prompt_interp"], step_seeds=list(noise_seed) if isinstance(noise_seed, (list, tuple)) else None,
+                                  **ctl)
     results = []
     for k in range(K):
         canvas = canvases[k, :, :geo.P].contiguous()
@@ -1130,9 +1189,12 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     every clip, and every canvas is decoded and cross-faded as above.  The result is a list of K dicts of the single clip's kind
     (``return_latents`` adds each clip's "latents" and "latent_canvas").  ``seed`` is then a list of K ints, one per clip, or one int
     (or None, drawn as above) from which clip k takes seed + k; equal seeds give correlated starts.  Refused with a list, before
-    anything is encoded: an init clip or mask (the clip guide is one canvas walked by one queue), ``sampling.ddim_eta`` > 0 (the step
-    noise has one seed and one clip-position walk per call), ``fifo["graph"]`` True and a nonzero ``fifo["lookahead"]`` (the clip
-    batch is the plain eager queue).  A single clip that is not in a list runs exactly as before.
+    anything is encoded: an init clip or mask (the pipeline encodes one init clip; ``fifo_denoise_clips(init_canvases=)`` guides K
+    clips from K latent canvases), ``sampling.ddim_eta`` > 0 under an int ``noise_seed`` or none (the step noise would have one seed
+    and one clip-position walk per call), ``fifo["graph"]`` True and a nonzero ``fifo["lookahead"]`` (the clip batch is the plain
+    eager queue).  ``noise_seed`` may be a LIST of K ints with a list of clips: clip k then draws its ``ddim_eta`` > 0 step noise under
+    ``noise_seed[k]`` (``fifo_denoise_clips(step_seeds=)``; include/avdiff_hip.h, "clip batch keying").  A single clip that is not in
+    a list runs exactly as before.
     """
     # the latent guide's argument checks that need no device (the window count and the mask's shape follow the prompt split below)
     strength = P.check_init_args(prompt_modality, init_video, init_audio, strength, mask)
@@ -1147,7 +1209,7 @@ def stream_generate(*, cfg: Dict, vid_vae, aud_codec, adapt_v, adapt_a, core, he
     has_init = init_video is not None or init_audio is not None
     clip_list = prompt_video if prompt_modality == "video" else prompt_audio
     if sampler == "fifo" and isinstance(clip_list, (list, tuple)):      # K clips as K queues in one engine
-        _fifo_clips_refusals(cfg, fifo, len(clip_list), has_init, mask is not None)
+        _fifo_clips_refusals(cfg, fifo, len(clip_list), has_init, mask is not None, noise_seed)
         pc = P.read_config(cfg, prompt_modality, guidance_interval=guidance_interval, resample=resample, has_init=False, has_mask=False,
                            noise_seed=noise_seed)
         mods = dict(vid_vae=vid_vae, aud_codec=aud_codec, adapt_v=adapt_v, adapt_a=adapt_a, core=core, head=head, tstep_dim=tstep_dim)

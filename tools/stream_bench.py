@@ -40,7 +40,20 @@ The records are profiles/slot_momentum_kernels.txt, profiles/slot_momentum_e2e.t
   e2e       fifo_denoise_clips (8 layers), DPM-Solver++(2M) at n = 18 with K = 1, 2, 4, 8, 10 clips and DDIM at n = 48 with K = 1, 2, 4:
             --slots-out and twice as many finished slots per clip, the time per finished slot per clip is the difference over K; one
             fifo_denoise line per solver beside them (the only line on a checkout without the clip batch).
-The records are profiles/fifo_clips_kernels.txt, profiles/fifo_clips_e2e.txt and profiles/fifo_clips_parent.txt."""
+The records are profiles/fifo_clips_kernels.txt, profiles/fifo_clips_e2e.txt and profiles/fifo_clips_parent.txt.
+
+--clips keyed-kernels | keyed-e2e times the clip batch keying (include/avdiff_hip.h, "clip batch keying"):
+  keyed-kernels  at the C3 latent [B, 8, 12, 32, 32] (S = 6), B = 30 as K = 10 queues of 3 and B = 32 as K = 4 queues of 8, the fused DDIM
+                 and DPM-Solver++(2M) slot updates through their C entries at eta 0.5: with per-clip keys, with the per-clip guide, with
+                 both, each beside the existing single-key and single-guide entry at the same B; the plain slot update and the existing
+                 seeded update timed twice per round (their run-to-run spread), avd_fifo_shift_clips_f32, and the K-tail guide pass
+                 against K single passes.  Kernel time under the library's launch events; device events where the sides differ in
+                 their number of launches.  On a checkout without the keying the unchanged entries alone are timed, so the same
+                 command on the parent commit gives the figures to compare.
+  keyed-e2e      fifo_denoise_clips per finished slot per clip: DPM-Solver++(2M) at n = 18 with eta 0.5 at K = 1, 4, 10 and DDIM at n =
+                 48 at K = 4, each beside the eta = 0 clip batch of the same build and beside fifo_denoise at eta 0.5 alone; the same
+                 for a guided run (init_canvases against init_canvas).
+The records are profiles/fifo_clips_keyed_kernels.txt, profiles/fifo_clips_keyed_parent.txt and profiles/fifo_clips_keyed_e2e.txt."""
 import argparse
 import statistics
 import sys
@@ -64,7 +77,8 @@ ap.add_argument("--prompt-frac", choices=("kernels", "e2e"), default=None, help=
 ap.add_argument("--launches", type=int, default=200, help="--prompt-frac / --slot-momentum kernels: launches per timed window")
 ap.add_argument("--slot-momentum", choices=("kernels", "e2e"), default=None, help="time the slot APG momentum instead (see above)")
 ap.add_argument("--slots-out", type=int, default=12, help="--slot-momentum / --clips e2e: finished slots per timed fifo_denoise call")
-ap.add_argument("--clips", choices=("kernels", "e2e"), default=None, help="time the FIFO clip batch instead (see above)")
+ap.add_argument("--clips", choices=("kernels", "e2e", "keyed-kernels", "keyed-e2e"), default=None,
+                help="time the FIFO clip batch, or its per-clip keying, instead (see above)")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
@@ -444,8 +458,182 @@ def clips_e2e():
     print("  quality is not measured: there are no trained weights")
 
 
+def keyed_kernels():
+    import ctypes as C
+    from multimodal_diffusion_amd import _lib as L, functional as Fn, schedule_utils as su
+    from oracle import ref_cpu as R
+    lib = L.lib()
+    has_keyed = hasattr(Fn, "slot_noise_clips")
+    abar = R.alpha_bar_table(R.beta_table(1000)).to(dev)
+    S_, sl, T_, P_ = 6, 2, 1000, 480      # every position of either walk inside the canvases
+    g = torch.Generator().manual_seed(0)
+    PLAIN, GUIDE, QUEUES = "cfg_unpatch_ddim_kernel", "cfg_unpatch_ddim_kernel<clip guide>", "cfg_unpatch_ddim_kernel<clip queues>"
+    rows, passes, keep = [], [], []      # (name, prof tag, fn); (name, fn, launches) timed by device events; what the raw addresses need
+    for B, K in ((30, 10), (32, 4)):
+        shape = (B, 8, 12, 32, 32)
+        z, hist, out = (torch.randn(shape, generator=g).to(dev) for _ in range(3))
+        eps2 = torch.randn(2 * B, 6 * 8 * 8, 256, generator=g).to(dev)
+        known = torch.randn(K, 8, P_, 32, 32, generator=g).to(dev)
+        masks = (torch.rand(K, 8, P_, 32, 32, generator=g) < 0.5).float().to(dev)
+        seeds = Fn.clip_seeds(list(range(1, K + 1)), K, dev)
+        key = L.SlotKey(7, 40, S_, None)
+        guide1 = L.ClipGuide(known.data_ptr(), masks.data_ptr(), P_, 9, 40, S_, None)      # K canvases: the single guide reads the first
+        cq = L.ClipQueues(K, seeds.data_ptr(), seeds.data_ptr()) if has_keyed else None
+        keep += [z, hist, out, eps2, known, masks, seeds]
+        for solver, n in (("ddim", 48), ("dpmpp_2m", 18)):
+            dpm = solver == "dpmpp_2m"
+            sched = su.make_sampling_schedule(T_, n)
+            i = (torch.arange(B * S_) % (n - 2)).view(B, S_) + 1      # the diagonal: none held, none final
+            tl, tn, tp = (sched[i + d].to(dev).contiguous() for d in (-1, 0, 1))
+            tail = (S_, hist.data_ptr() if dpm else None, out.data_ptr(), *shape, 2, 4, 4)
+
+            keep += [tl, tn, tp]      # the closures below hold raw addresses: every tensor and struct of this pass stays alive, and
+            #                           every name is bound here, not when the closure runs (the loop rebinds them all)
+            head = {eta: (eps2.data_ptr(), z.data_ptr(), tl.data_ptr() if dpm else None, tn.data_ptr(), tp.data_ptr(), abar.data_ptr(), T_,
+                          3.5, eta) for eta in (0.0, 0.5)}
+
+            def seeded(eta, head=head, tail=tail, key=key):
+                return lambda: L.check(lib.avd_cfg_unpatch_ddim_slots_seeded_f32(*head[eta], C.byref(key), *tail, L.stream_ptr(dev)))
+
+            def guided(eta, head=head, tail=tail, key=key, guide1=guide1):
+                return lambda: L.check(lib.avd_cfg_unpatch_ddim_slots_guided_f32(*head[eta], C.byref(key), C.byref(guide1), *tail,
+                                                                                 L.stream_ptr(dev)))
+
+            def clips(eta, with_guide, head=head, tail=tail, key=key, guide1=guide1, cq=cq):
+                return lambda: L.check(lib.avd_cfg_unpatch_ddim_slots_clips_f32(*head[eta], C.byref(key), C.byref(guide1) if with_guide else None,
+                                                                                C.byref(cq), *tail, None, L.stream_ptr(dev)))
+
+            name = f"B={B} K={K} {solver}"
+            rows += [(f"{name}: plain slot update, eta 0 (a)", PLAIN, seeded(0.0)), (f"{name}: single key, eta 0.5 (a)", PLAIN, seeded(0.5))]
+            if has_keyed:
+                rows += [(f"{name}: per-clip keys, eta 0.5", QUEUES, clips(0.5, False))]
+            rows += [(f"{name}: single guide, eta 0", GUIDE, guided(0.0))]
+            if has_keyed:
+                rows += [(f"{name}: per-clip guide, eta 0", QUEUES, clips(0.0, True))]
+            rows += [(f"{name}: single key + guide, eta 0.5", GUIDE, guided(0.5))]
+            if has_keyed:
+                rows += [(f"{name}: per-clip keys + guide, eta 0.5", QUEUES, clips(0.5, True))]
+            rows += [(f"{name}: plain slot update, eta 0 (b)", PLAIN, seeded(0.0)), (f"{name}: single key, eta 0.5 (b)", PLAIN, seeded(0.5))]
+        canv = torch.zeros(K, 8, 64 * sl, 32, 32, device=dev)
+        rows += [(f"B={B} K={K}: fifo_shift_clips ({tag})", "fifo_shift_clips_kernel<4, 0>",
+                  lambda z=z, K=K, canv=canv, seeds=seeds: Fn.fifo_shift_clips(z, K, 48, seeds, 999, sl, canv, 5)) for tag in ("a", "b")]
+        # the K entering tails: one launch of the clip batch's pass against K one-queue passes on slices, in place
+        Bq = B // K
+        tails = torch.full((B, S_), Fn.SLOT_LEAVE, dtype=torch.long, device=dev)
+        tails[Bq - 1::Bq, S_ - 1] = 999
+
+        def single_passes(z=z, K=K, Bq=Bq, known=known, masks=masks, tails=tails):
+            for k in range(K):
+                q = slice(k * Bq, (k + 1) * Bq)
+                Fn.clip_guide_slots(known[k], tails[q], abar, z[q], masks[k], slot_len=sl, seed=k + 1, first=40, out=z[q])
+
+        passes.append((f"B={B} K={K}: {K} single tail passes", single_passes, K))
+        if has_keyed:
+            passes.append((f"B={B} K={K}: one K-tail pass", lambda z=z, known=known, masks=masks, tails=tails, seeds=seeds:
+                           Fn.clip_guide_slots_clips(known, tails, abar, z, masks, slot_len=sl, seeds=seeds, first=40, out=z), 1))
+
+    def per_launch_us(tag, fn):
+        L.prof_enable(True)
+        try:
+            for _ in range(args.launches):
+                fn()
+            torch.cuda.synchronize()
+        finally:
+            L.prof_enable(False)
+        n, ms, _ = L.prof_report()[tag]
+        assert n == args.launches, (tag, n)
+        return 1e3 * ms / n
+
+    for _, _, fn in rows:
+        for _ in range(3):
+            fn()
+    for _, fn, _ in passes:
+        fn()
+    torch.cuda.synchronize()
+    res = {name: [] for name, _, _ in rows}
+    ev = {name: [] for name, _, _ in passes}
+    for _ in range(args.rounds):
+        for name, tag, fn in rows:
+            res[name].append(per_launch_us(tag, fn))
+        for name, fn, _ in passes:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.launches):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ev[name].append(1e3 * e0.elapsed_time(e1) / args.launches)
+    print(f"C3 latent [B, 8, 12, 32, 32] (S = {S_} slots of {sl} frames), the fused CFG + un-patch + solver slot update through its C entries "
+          f"(random eps tokens, the diagonal's tables: no slot held), the rows form: one key / one guide for the batch (the existing entries) "
+          f"against one per queue (avd_cfg_unpatch_ddim_slots_clips_f32), canvases of P = {P_} positions with a half-open mask; and "
+          f"avd_fifo_shift_clips_f32.  {args.rounds} interleaved rounds of {args.launches} launches, microseconds per launch (launch events)")
+    if not has_keyed:
+        print("  this checkout has no clip batch keying: the unchanged entries alone")
+    for name, _, _ in rows:
+        v = res[name]
+        print(f"  {name:52s} " + " ".join(f"{x:8.2f}" for x in v) + f"   median {statistics.median(v):8.2f}")
+    for name in sorted({n[:-4] for n in res if n.endswith("(a)")}):      # the spread of the entries timed twice: what a difference has to exceed
+        v = res[name + " (a)"] + res[name + " (b)"]
+        print(f"  {name}: run-to-run spread {min(v):.2f} .. {max(v):.2f}")
+    print(f" the entering tails' guide pass, in place, through functional.* (device events around {args.launches} back-to-back iterations, "
+          "the host's launch work included), microseconds per iteration:")
+    for name, _, launches in passes:
+        v = ev[name]
+        print(f"  {name:52s} " + " ".join(f"{x:8.2f}" for x in v) + f"   median {statistics.median(v):8.2f}   {launches:2d} launch(es)")
+
+
+def keyed_e2e():
+    from multimodal_diffusion_amd import schedule_utils as su
+    from oracle import ref_cpu as R
+    abar = R.alpha_bar_table(R.beta_table(1000))
+    S_, N = 6, args.slots_out
+    g = torch.Generator().manual_seed(1)
+    print(f"fifo_denoise_clips with per-clip step seeds (eta 0.5) and per-clip init canvases, S = {S_} (C3 latent [8, 12, 32, 32] per sample, "
+          f"8 layers, {args.matmul}, eager), beside the eta = 0 clip batch of the same build and fifo_denoise alone; host clock around calls "
+          f"that end in a device synchronise, {args.rounds} rounds, the calls interleaved, {N} and {2 * N} slots out per clip; milliseconds.  "
+          "Per finished slot = the difference of the two clip lengths over the slots; per clip = that over K")
+    for solver, n, Ks in (("dpmpp_2m", 18, (1, 4, 10)), ("ddim", 48, (4,))):
+        sched = su.make_sampling_schedule(1000, n)
+        Bq = n // S_
+        pcs = [torch.randn(8, 25 * (n + 2 * N) + 148, generator=g).to(dev) for _ in range(max(Ks))]
+        canv = [torch.randn(8, 2 * (n + 2 * N), 32, 32, generator=g).to(dev) for _ in range(max(Ks))]
+        mask = torch.zeros(8, 2 * (n + 2 * N), 32, 32, device=dev)
+        mask[:, ::4] = 1.0
+
+        def eng(B, eta):
+            return A.DenoiseEngine(adapt_v=av, adapt_a=aa, core=core, head=head, tstep_dim=tdim, target="video",
+                                   latent_shape=(B, 8, 12, 32, 32), prompt_tokens=37, alpha_bar=abar, guidance=3.5, matmul=args.matmul,
+                                   solver=solver, eta=eta, noise_seed=3)
+
+        e1 = eng(Bq, 0.5)
+        runs = [("fifo_denoise eta .5", 1, lambda n_out, e1=e1: A.fifo_denoise(e1, pcs[0], 25, sched, n_out, 5)),
+                ("fifo_denoise guided", 1, lambda n_out, e1=e1: A.fifo_denoise(e1, pcs[0], 25, sched, n_out, 5, init_canvas=canv[0], mask=mask))]
+        for K in Ks:
+            e0, eK = eng(K * Bq, 0.0), (e1 if K == 1 else eng(K * Bq, 0.5))
+            seeds = list(range(5, 5 + K))
+            runs += [(f"K = {K:2d} eta 0", K, lambda n_out, e0=e0, K=K, seeds=seeds: A.fifo_denoise_clips(e0, pcs[:K], 25, sched, n_out, seeds)),
+                     (f"K = {K:2d} eta .5 keyed", K, lambda n_out, eK=eK, K=K, seeds=seeds:
+                      A.fifo_denoise_clips(eK, pcs[:K], 25, sched, n_out, seeds, step_seeds=seeds)),
+                     (f"K = {K:2d} eta .5 guided", K, lambda n_out, eK=eK, K=K, seeds=seeds:
+                      A.fifo_denoise_clips(eK, pcs[:K], 25, sched, n_out, seeds, step_seeds=seeds, init_canvases=canv[:K], masks=[mask] * K))]
+        for _, _, fn in runs:
+            fn(4)                                          # warm-up
+        ts_ = {(name, n_out): [] for name, _, _ in runs for n_out in (N, 2 * N)}
+        for _ in range(args.rounds):
+            for n_out in (N, 2 * N):
+                for name, _, fn in runs:
+                    ts_[name, n_out].append(timed(lambda: fn(n_out))[0])
+        for name, K, _ in runs:
+            whole = {n_out: statistics.median(ts_[name, n_out]) for n_out in (N, 2 * N)}
+            per = (whole[2 * N] - whole[N]) / N
+            print(f"  {solver:8s} n = {n}, B = {K * Bq:2d}, {name:20s}: " +
+                  "; ".join(f"{n_out} out " + " ".join(f"{x * 1e3:7.1f}" for x in ts_[name, n_out]) for n_out in (N, 2 * N)) +
+                  f"; per finished slot {per * 1e3:.3f}, per clip {per / K * 1e3:.3f}")
+    print("  quality is not measured: there are no trained weights")
+
+
 if args.clips is not None:
-    clips_kernels() if args.clips == "kernels" else clips_e2e()
+    {"kernels": clips_kernels, "e2e": clips_e2e, "keyed-kernels": keyed_kernels, "keyed-e2e": keyed_e2e}[args.clips]()
     sys.exit(0)
 if args.prompt_frac is not None:
     prompt_frac_kernels() if args.prompt_frac == "kernels" else prompt_frac_e2e()
