@@ -1060,6 +1060,11 @@ int avd_split3_f32(const float* x, void* out, int64_t rows, int K, avd_stream_t 
 /* RMSNorm (mmdt.py:39-42) whose output is written as a split3 image (the A operand of the next Linear) */
 int avd_rmsnorm_split3_f32(const float* x, const float* scale, void* out, int64_t rows, int d, float eps,
                            avd_stream_t stream);
+/* LayerNorm + activation (avd_layernorm_act_f32's arithmetic; noise_heads.py:141-147) whose output is written as a split3 image: the
+ * producer avd_head_forward_f32 runs between the trunk Linears in the split-operand modes.  d % 16 == 0, d <= 2048, rows > 0;
+ * image rows >= rows are left untouched. */
+int avd_layernorm_act_split3_f32(const float* x, const float* gamma, const float* beta, void* out, int64_t rows, int d, float eps,
+                                 int act, avd_stream_t stream);
 /* avd_attn_fwd_f32 whose [B*N, H*Dh] result is written as a split3 image (rows >= n_query of a sample are left untouched) */
 int avd_attn_fwd_split3_f32(const float* qkv, void* out3, int B, int N, int H, int Dh, float scale, int n_query,
                             avd_stream_t stream);
@@ -1112,6 +1117,9 @@ int avd_weight_bounds_f32(const float* w, int64_t rows, int cols, float* out2, a
 int avd_split_f16x2_f32(const float* x, void* out, int64_t rows, int K, float scale, avd_stream_t stream);
 int avd_rmsnorm_split_f16x2_f32(const float* x, const float* gamma, void* out, int64_t rows, int d, float eps, float scale,
                                 avd_stream_t stream);
+/* avd_layernorm_act_split3_f32 writing an f16x2 image at `scale` (> 0; the head bounds the output by sqrt(d) |gamma| + |beta|) */
+int avd_layernorm_act_split_f16x2_f32(const float* x, const float* gamma, const float* beta, void* out, int64_t rows, int d,
+                                      float eps, int act, float scale, avd_stream_t stream);
 int avd_gemm_f16x2_f32(const void* A2, const void* W2, const float* bias, const float* residual, float* C, void* C2,
                        int64_t M, int N, int K, int act, float ab_scale, float c_scale, avd_stream_t stream);
 int avd_gemm_f16x2_qkv_f32(const void* A2, const void* W2, const float* bias, void* qkv, int64_t M, int tokens, int heads,

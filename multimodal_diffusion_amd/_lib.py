@@ -269,6 +269,7 @@ SIGNATURES = {
     "avd_split3_bytes": (_L, [_L, _I]),
     "avd_split3_f32": (_I, [_P, _P, _L, _I, _P]),
     "avd_rmsnorm_split3_f32": (_I, [_P, _P, _P, _L, _I, _F, _P]),
+    "avd_layernorm_act_split3_f32": (_I, [_P, _P, _P, _P, _L, _I, _F, _I, _P]),
     "avd_attn_fwd_split3_f32": (_I, [_P, _P, _I, _I, _I, _I, _F, _I, _P]),
     "avd_qkv3_bytes": (_L, [_I, _I, _I]),
     "avd_gemm_bf16x3_qkv3_f32": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _F, _I, _P]),
@@ -281,6 +282,7 @@ SIGNATURES = {
     "avd_weight_bounds_f32": (_I, [_P, _L, _I, _P, _P]),
     "avd_split_f16x2_f32": (_I, [_P, _P, _L, _I, _F, _P]),
     "avd_rmsnorm_split_f16x2_f32": (_I, [_P, _P, _P, _L, _I, _F, _F, _P]),
+    "avd_layernorm_act_split_f16x2_f32": (_I, [_P, _P, _P, _P, _L, _I, _F, _I, _F, _P]),
     "avd_gemm_f16x2_f32": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _F, _F, _P]),
     "avd_gemm_f16x2_qkv_f32": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _F, _F, _F, _P]),
     "avd_attn_fwd_qkv_f16x2_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _F, _P]),

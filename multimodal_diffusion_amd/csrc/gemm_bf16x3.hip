@@ -1905,6 +1905,10 @@ extern "C" int avd_rmsnorm_split3_f32(const float* x, const float* scale, void* 
                                       avd_stream_t stream) {
     return rmsnorm_split3_f32(x, scale, out, rows, d, eps, static_cast<hipStream_t>(stream));
 }
+extern "C" int avd_layernorm_act_split3_f32(const float* x, const float* gamma, const float* beta, void* out, int64_t rows, int d,
+                                            float eps, int act, avd_stream_t stream) {
+    return layernorm_act_split3_f32(x, gamma, beta, out, rows, d, eps, act, static_cast<hipStream_t>(stream));
+}
 extern "C" int avd_gemm_bf16x3_f32(const void* A3, const void* W3, const float* bias, const float* residual, float* C, void* C3,
                                    int64_t M, int N, int K, int act, int terms, avd_stream_t stream) {
     return gemm_bf16x3(A3, W3, bias, residual, C, C3, M, N, K, act, terms, static_cast<hipStream_t>(stream));
@@ -1931,6 +1935,11 @@ extern "C" int avd_rmsnorm_split_f16x2_f32(const float* x, const float* gamma, v
                                            avd_stream_t stream) {
     AVD_REQUIRE(scale > 0.f, AVD_EINVAL, "avd_rmsnorm_split_f16x2_f32: scale must be positive");
     return rmsnorm_split3_f32(x, gamma, out, rows, d, eps, static_cast<hipStream_t>(stream), scale);
+}
+extern "C" int avd_layernorm_act_split_f16x2_f32(const float* x, const float* gamma, const float* beta, void* out, int64_t rows, int d,
+                                                 float eps, int act, float scale, avd_stream_t stream) {
+    AVD_REQUIRE(scale > 0.f, AVD_EINVAL, "avd_layernorm_act_split_f16x2_f32: scale must be positive");
+    return layernorm_act_split3_f32(x, gamma, beta, out, rows, d, eps, act, static_cast<hipStream_t>(stream), scale);
 }
 extern "C" int avd_gemm_f16x2_f32(const void* A2, const void* W2, const float* bias, const float* residual, float* C, void* C2, int64_t M,
                                   int N, int K, int act, float ab_scale, float c_scale, avd_stream_t stream) {

@@ -1418,6 +1418,22 @@ def fifo_shift_clips(z: Tensor, queues: int, c: int, seeds, t: int, slot_len: in
 
 
 # ---- "bf16x3": fp32-accurate Linear on the bf16 matrix pipe (csrc/gemm_bf16x3.hip) ----
+def _image_like(rows: int, d: int, device: torch.device, who: str) -> Tensor:
+    """an uninitialised operand image for a [rows, d] matrix; a width the image geometry does not cover is refused here"""
+    nbytes = L.lib().avd_split3_bytes(rows, d)
+    if nbytes < 0:
+        raise L.AvdError(f"{who}: need rows > 0 and d % 16 == 0 (rows={rows} d={d})")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _image_scale(scale: float, who: str) -> float:
+    """a caller's f16x2 image scale: positive and finite, or refused before anything is allocated or launched"""
+    scale = float(scale)
+    if not (0.0 < scale < math.inf):
+        raise L.AvdError(f"{who}: the f16x2 image scale must be positive and finite, got {scale}")
+    return scale
+
+
 def split3(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """fp32 [rows, K] -> its split3 image (uint8; three bf16 planes, tiled).  K must be a multiple of 16.
     ``out``: an existing image of the same size to overwrite (keeps its address)."""
@@ -1439,8 +1455,21 @@ def rmsnorm_split3(x: Tensor, scale: Tensor, eps: float = 1e-6) -> Tensor:
     scale = L.dev_f32(scale, "scale")
     d = x.shape[-1]
     rows = x.numel() // d
-    out = torch.empty(L.lib().avd_split3_bytes(rows, d), dtype=torch.uint8, device=x.device)
+    out = _image_like(rows, d, x.device, "rmsnorm_split3")
     L.check(L.lib().avd_rmsnorm_split3_f32(x.data_ptr(), scale.data_ptr(), out.data_ptr(), rows, d, eps, _st(x)))
+    return out
+
+
+def layernorm_act_split3(x: Tensor, weight: Tensor, bias: Tensor, eps: float = 1e-5, act: int = L.ACT_NONE) -> Tensor:
+    """act(LayerNorm(x)) written as a split3 image (what the noise head's trunk hands its next bf16x3 Linear)."""
+    x = L.dev_f32(x, "x")
+    weight = L.dev_f32(weight, "weight")
+    bias = L.dev_f32(bias, "bias")
+    d = x.shape[-1]
+    rows = x.numel() // d
+    out = _image_like(rows, d, x.device, "layernorm_act_split3")
+    L.check(L.lib().avd_layernorm_act_split3_f32(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), out.data_ptr(), rows, d, eps, act,
+                                                 _st(x)))
     return out
 
 
@@ -1512,8 +1541,28 @@ def rmsnorm_split_f16x2(x: Tensor, gamma: Tensor, eps: float = 1e-6, scale: Opti
     rows = x.numel() // d
     if scale is None:
         scale = f16x2_scale(weight_bounds([gamma])[0][0] * d ** 0.5)
-    out = torch.empty(L.lib().avd_split3_bytes(rows, d), dtype=torch.uint8, device=x.device)
+    scale = _image_scale(scale, "rmsnorm_split_f16x2")
+    out = _image_like(rows, d, x.device, "rmsnorm_split_f16x2")
     L.check(L.lib().avd_rmsnorm_split_f16x2_f32(x.data_ptr(), gamma.data_ptr(), out.data_ptr(), rows, d, eps, scale, _st(x)))
+    return out, scale
+
+
+def layernorm_act_split_f16x2(x: Tensor, weight: Tensor, bias: Tensor, eps: float = 1e-5, act: int = L.ACT_NONE,
+                              scale: Optional[float] = None):
+    """act(LayerNorm(x)) written as an f16x2 image; the default scale uses the noise head's bound
+    |y_i| <= sqrt(d) max|gamma| + max|beta| (every activation here satisfies |act(y)| <= |y|)."""
+    x = L.dev_f32(x, "x")
+    weight = L.dev_f32(weight, "weight")
+    bias = L.dev_f32(bias, "bias")
+    d = x.shape[-1]
+    rows = x.numel() // d
+    if scale is None:
+        (gmax, _), (bmax, _) = weight_bounds([weight, bias])
+        scale = f16x2_scale(gmax * d ** 0.5 + bmax)
+    scale = _image_scale(scale, "layernorm_act_split_f16x2")
+    out = _image_like(rows, d, x.device, "layernorm_act_split_f16x2")
+    L.check(L.lib().avd_layernorm_act_split_f16x2_f32(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), out.data_ptr(), rows, d, eps,
+                                                      act, scale, _st(x)))
     return out, scale
 
 
