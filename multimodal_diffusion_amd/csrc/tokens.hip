@@ -734,8 +734,7 @@ __global__ __launch_bounds__(256) void fifo_move_kernel(QueueGeom g, QueueLatent
         v = canvas_normal4(ck, 0, o, j, i, g.inner, z.t);
         if constexpr (V == 1) v[0] = v[(int)((o * g.inner + i) & 3)];
         if constexpr (sizeof...(Guide) > 0) {      // blend(m(p), q_p(t), fresh): the bits of the stand-alone pass on this slot
-            if constexpr (V == 4) v = pack_get<GuideShift>(guide...).tail4(o, j, i, g.inner, z.t, v);
-            else v[0] = pack_get<GuideShift>(guide...).tail1(o, j, i, g.inner, z.t, v[0]);
+            v = pack_get<GuideShift>(guide...).template tail<V>(o, j, i, g.inner, z.t, v);
         }
     }
     if constexpr (LATENT) store_v<V>(z.out + idx * V, v);
@@ -1180,23 +1179,22 @@ __device__ __forceinline__ float guide_blend(float m, float q, float z) {
 #pragma clang fp contract(off)
     return m == 0.f ? z : (m == 1.f ? q : (1.0f - m) * z + m * q);
 }
-// the four consecutive elements el .. el + 3 (el % 4 == 0) of sample b at lat = b * per + el: known / mask read as f32x4
-__device__ __forceinline__ f32x4 guide_apply4(const GuideState& gs, const GuideCoef& gc, int b, int64_t lat, int64_t el, f32x4 z) {
-    const f32x4 m = gs.mask ? *reinterpret_cast<const f32x4*>(gs.mask + b * gs.mask_bstride + el) : f32x4{1.f, 1.f, 1.f, 1.f};
-    const f32x4 xk = *reinterpret_cast<const f32x4*>(gs.known + lat);
-    f32x4 n = {0.f, 0.f, 0.f, 0.f};
-    if (!gc.one) n = philox_normal4(gs.nk, (uint32_t)(el >> 2), gs.nk.s0 + (uint32_t)b, 0u, GUIDE_TAG);
-    f32x4 o;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = guide_blend(m[k], guide_q(gc, xk[k], n[k]), z[k]);
-    return o;
+// A lane of V values (4 or 1) rides in an f32x4 (load_v / store_v); a one-value lane keeps of a generator call the normal its element
+// e takes
+template <int V> __device__ __forceinline__ f32x4 lane_pick(f32x4 n, int64_t e) {
+    if constexpr (V == 1) n[0] = n[(int)(e & 3)];
+    return n;
 }
-// one element el of sample b at i = b * per + el
-__device__ __forceinline__ float guide_apply1(const GuideState& gs, const GuideCoef& gc, int b, int64_t i, int64_t el, float z) {
-    const float m = gs.mask ? gs.mask[b * gs.mask_bstride + el] : 1.f;
-    float n = 0.f;
-    if (!gc.one) n = philox_normal4(gs.nk, (uint32_t)(el >> 2), gs.nk.s0 + (uint32_t)b, 0u, GUIDE_TAG)[(int)(el & 3)];
-    return guide_blend(m, guide_q(gc, gs.known[i], n), z);
+// the V consecutive elements el .. el + V - 1 (V == 4: el % 4 == 0) of sample b at lat = b * per + el
+template <int V>
+__device__ __forceinline__ f32x4 guide_apply(const GuideState& gs, const GuideCoef& gc, int b, int64_t lat, int64_t el, f32x4 z) {
+    const f32x4 m = gs.mask ? load_v<V>(gs.mask + b * gs.mask_bstride + el) : f32x4{1.f, 1.f, 1.f, 1.f};
+    const f32x4 xk = load_v<V>(gs.known + lat);
+    f32x4 n = {0.f, 0.f, 0.f, 0.f};
+    if (!gc.one) n = lane_pick<V>(philox_normal4(gs.nk, (uint32_t)(el >> 2), gs.nk.s0 + (uint32_t)b, 0u, GUIDE_TAG), el);
+#pragma unroll
+    for (int k = 0; k < V; ++k) z[k] = guide_blend(m[k], guide_q(gc, xk[k], n[k]), z[k]);
+    return z;
 }
 
 // The canvas keying of the guide (include/avdiff_hip.h, "canvas-keyed known noise"): the batch is N consecutive windows of one canvas
@@ -1208,25 +1206,17 @@ struct CanvasGuideState {
     int64_t mask_bstride;
     CanvasKey ck;           // the known-noise stream's seed, the global index of window 0 (guide.key.sample_offset) and the hop
 };
-// the four consecutive elements at lat = b * per + el, elements i .. i + 3 of the (o, l) slice (inner % 4 == 0, i % 4 == 0)
-__device__ __forceinline__ f32x4 canvas_guide_apply4(const CanvasGuideState& gs, const GuideCoef& gc, int b, int64_t lat, int64_t el,
-                                                     int64_t o, int l, int64_t i, int64_t inner, f32x4 z) {
-    const f32x4 m = gs.mask ? *reinterpret_cast<const f32x4*>(gs.mask + b * gs.mask_bstride + el) : f32x4{1.f, 1.f, 1.f, 1.f};
-    const f32x4 xk = *reinterpret_cast<const f32x4*>(gs.known + lat);
+// the V consecutive elements at lat = b * per + el, elements i .. i + V - 1 of the (o, l) slice (V == 4: inner % 4 == 0, i % 4 == 0)
+template <int V>
+__device__ __forceinline__ f32x4 canvas_guide_apply(const CanvasGuideState& gs, const GuideCoef& gc, int b, int64_t lat, int64_t el,
+                                                    int64_t o, int l, int64_t i, int64_t inner, f32x4 z) {
+    const f32x4 m = gs.mask ? load_v<V>(gs.mask + b * gs.mask_bstride + el) : f32x4{1.f, 1.f, 1.f, 1.f};
+    const f32x4 xk = load_v<V>(gs.known + lat);
     f32x4 n = {0.f, 0.f, 0.f, 0.f};
-    if (!gc.one) n = canvas_normal4(gs.ck, b, o, l, i, inner, 0u, GUIDE_TAG);
-    f32x4 r;
+    if (!gc.one) n = lane_pick<V>(canvas_normal4(gs.ck, b, o, l, i, inner, 0u, GUIDE_TAG), o * inner + i);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) r[k] = guide_blend(m[k], guide_q(gc, xk[k], n[k]), z[k]);
-    return r;
-}
-// one element at idx = b * per + el, element i of the (o, l) slice
-__device__ __forceinline__ float canvas_guide_apply1(const CanvasGuideState& gs, const GuideCoef& gc, int b, int64_t idx, int64_t el,
-                                                     int64_t o, int l, int64_t i, int64_t inner, float z) {
-    const float m = gs.mask ? gs.mask[b * gs.mask_bstride + el] : 1.f;
-    float n = 0.f;
-    if (!gc.one) n = canvas_normal4(gs.ck, b, o, l, i, inner, 0u, GUIDE_TAG)[(int)((o * inner + i) & 3)];
-    return guide_blend(m, guide_q(gc, gs.known[idx], n), z);
+    for (int k = 0; k < V; ++k) z[k] = guide_blend(m[k], guide_q(gc, xk[k], n[k]), z[k]);
+    return z;
 }
 
 // The clip keying of the guide (include/avdiff_hip.h, "clip-keyed latent guide"): known / mask are canvases [outer, P, inner] of the
@@ -1248,41 +1238,37 @@ __device__ __forceinline__ int64_t clip_guide_pos(const ClipGuideState& cg, int 
     if (m < 0) m = 0;
     return (cg.first + m + (int64_t)b * cg.stride) * cg.slot_len + l;      // the host bounds every term: no overflow
 }
-__device__ __forceinline__ f32x4 clip_canvas4(const float* c, int64_t at, bool vec) {
-    if (vec) return *reinterpret_cast<const f32x4*>(c + at);
+template <int V> __device__ __forceinline__ f32x4 clip_canvas(const float* c, int64_t at, bool vec) {
+    if (V == 1 || vec) return load_v<V>(c + at);
     return f32x4{c[at], c[at + 1], c[at + 2], c[at + 3]};
 }
-// elements i .. i + 3 of the (o, l) slice (inner % 4 == 0, i % 4 == 0); a lane whose four mask values are 0 skips the generator: the
-// blend would not read q
-__device__ __forceinline__ f32x4 clip_guide_apply4(const ClipGuideState& cg, const GuideCoef& gc, int b, int64_t o, int l, int64_t i,
-                                                   int64_t inner, f32x4 z) {
+// elements i .. i + V - 1 of the (o, l) slice (V == 4: inner % 4 == 0, i % 4 == 0); a lane whose mask values are all 0 skips the
+// generator: the blend would not read q
+template <int V>
+__device__ __forceinline__ f32x4 clip_guide_apply(const ClipGuideState& cg, const GuideCoef& gc, int b, int64_t o, int l, int64_t i,
+                                                  int64_t inner, f32x4 z) {
     const int64_t p = clip_guide_pos(cg, b, l);
     if (p < 0 || p >= cg.P) return z;
     const int64_t at = (o * cg.P + p) * inner + i;
     f32x4 m = {1.f, 1.f, 1.f, 1.f};
-    if (cg.mask) {
-        m = clip_canvas4(cg.mask, at, cg.vec);
-        if (m[0] == 0.f && m[1] == 0.f && m[2] == 0.f && m[3] == 0.f) return z;
+    if constexpr (V == 4) {
+        if (cg.mask) {
+            m = clip_canvas<V>(cg.mask, at, cg.vec);
+            if (m[0] == 0.f && m[1] == 0.f && m[2] == 0.f && m[3] == 0.f) return z;
+        }
+    } else {
+        if (cg.mask) m = clip_canvas<V>(cg.mask, at, cg.vec);
+        if (m[0] == 0.f) return z;
     }
-    const f32x4 xk = clip_canvas4(cg.known, at, cg.vec);
+    f32x4 xk = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (V == 4) xk = clip_canvas<V>(cg.known, at, cg.vec);
     f32x4 n = {0.f, 0.f, 0.f, 0.f};
-    if (!gc.one) n = philox_normal4(NoiseKey{cg.k0, cg.k1, 0u}, (uint32_t)((o * inner + i) >> 2), (uint32_t)p, 0u, GUIDE_TAG);
-    f32x4 r;
+    if (!gc.one)
+        n = lane_pick<V>(philox_normal4(NoiseKey{cg.k0, cg.k1, 0u}, (uint32_t)((o * inner + i) >> 2), (uint32_t)p, 0u, GUIDE_TAG), o * inner + i);
+    if constexpr (V == 1) xk = clip_canvas<V>(cg.known, at, cg.vec);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) r[k] = guide_blend(m[k], guide_q(gc, xk[k], n[k]), z[k]);
-    return r;
-}
-// one element i of the (o, l) slice
-__device__ __forceinline__ float clip_guide_apply1(const ClipGuideState& cg, const GuideCoef& gc, int b, int64_t o, int l, int64_t i,
-                                                   int64_t inner, float z) {
-    const int64_t p = clip_guide_pos(cg, b, l);
-    if (p < 0 || p >= cg.P) return z;
-    const int64_t at = (o * cg.P + p) * inner + i;
-    const float m = cg.mask ? cg.mask[at] : 1.f;
-    if (m == 0.f) return z;
-    float n = 0.f;
-    if (!gc.one) n = philox_normal4(NoiseKey{cg.k0, cg.k1, 0u}, (uint32_t)((o * inner + i) >> 2), (uint32_t)p, 0u, GUIDE_TAG)[(int)((o * inner + i) & 3)];
-    return guide_blend(m, guide_q(gc, cg.known[at], n), z);
+    for (int k = 0; k < V; ++k) z[k] = guide_blend(m[k], guide_q(gc, xk[k], n[k]), z[k]);
+    return z;
 }
 // queue k's guide ("clip batch keying"): canvas k of known / mask and the known-noise stream under guide_seeds[k].  The canvas stride is
 // a multiple of 4 floats wherever vec is set, so canvas k is as aligned as canvas 0
@@ -1377,15 +1363,9 @@ __global__ __launch_bounds__(256) void clip_guide_slots_kernel(ClipGuideState cg
     const int l = l0 + (int)(j / inner);
     const int64_t i = j % inner;
     const int64_t at = (((int64_t)b * outer + o) * L + l) * inner + i;
-    if constexpr (V == 4) {
-        f32x4 v = *reinterpret_cast<const f32x4*>(z + at);
-        if (!leave) v = clip_guide_apply4(cg, guide_coef(abar, T_train, t), bq, o, l, i, inner, v);
-        *reinterpret_cast<f32x4*>(out + at) = v;
-    } else {
-        float v = z[at];
-        if (!leave) v = clip_guide_apply1(cg, guide_coef(abar, T_train, t), bq, o, l, i, inner, v);
-        out[at] = v;
-    }
+    f32x4 v = load_v<V>(z + at);
+    if (!leave) v = clip_guide_apply<V>(cg, guide_coef(abar, T_train, t), bq, o, l, i, inner, v);
+    store_v<V>(out + at, v);
 }
 
 // The guided FIFO queue shift (avd_fifo_shift_guided_f32; contract in include/avdiff_hip.h, "clip-keyed latent guide"):
@@ -1395,11 +1375,8 @@ struct GuideShift {
     ClipGuideState cg;
     const float* abar;
     int T_train;
-    __device__ __forceinline__ f32x4 tail4(int64_t o, int j, int64_t i, int64_t inner, uint32_t t, f32x4 v) const {
-        return clip_guide_apply4(cg, guide_coef(abar, T_train, (long long)t), 0, o, j, i, inner, v);
-    }
-    __device__ __forceinline__ float tail1(int64_t o, int j, int64_t i, int64_t inner, uint32_t t, float v) const {
-        return clip_guide_apply1(cg, guide_coef(abar, T_train, (long long)t), 0, o, j, i, inner, v);
+    template <int V> __device__ __forceinline__ f32x4 tail(int64_t o, int j, int64_t i, int64_t inner, uint32_t t, f32x4 v) const {
+        return clip_guide_apply<V>(cg, guide_coef(abar, T_train, (long long)t), 0, o, j, i, inner, v);
     }
 };
 
@@ -2622,14 +2599,87 @@ int g_cfg_rows = 1;     // avd_tune_set "cfg_rows": 0 = the 16-bytes-per-lane ga
 // instantiations with a NoiseKey are untouched.
 // A DpmState in the pack replaces the DDIM update by the DPM-Solver++(2M) one (dpm_coef / dpm_apply) on the same x0: alone (SEEDED false)
 // the ODE update; followed by a key (SEEDED true, eta > 0) the SDE form, whose noise term is the same zn the DDIM step would draw.
+// The three kernels below differ in their fronts alone: how a lane gets its combined eps and where its elements sit in the latent.
+// Each builds an UpdateLane once per lane from its own indices and hands it, x and eps to update_tail, the one copy of the draw, the
+// solver, the guide blends and the store.
+struct UpdateLane {
+    int b, tb;            // the sample; the entry of t_now / t_prev the lane steps with (the slot's in the slot form, else b)
+    int64_t lat, el;      // the lane's first element: its latent offset, and its offset inside the sample
+    int64_t o;            // the slice coordinates of the keyed draws and guides (canvas_normal4): elements i .. of the (o, l) slice
+    int l;
+    int64_t i, inner;
+};
+// "clip batch keying": the lane's queue, taken where a keyed call needs it; {0, b} in a pack without a ClipQueues, which is not touched
+template <class... Key> __device__ __forceinline__ QueueOf lane_queue(int b, const Key&... nk) {
+    if constexpr (PackHas<ClipQueues, Key...>::value) return queue_of(pack_get<ClipQueues>(nk...), b);
+    else return QueueOf{0, b};
+}
+// the coefficients of DDIM (entry tb), of a DpmState's update (entry tb) and of a per-sample or canvas-keyed guide (at t_prev[b])
+struct UpdateCoef {
+    Ddim c;
+    Dpm d;
+    GuideCoef gc;
+};
+// V: the lane's values (4 or 1), in an f32x4.  x: z at the lane; e: the combined eps.  blk: the coefficients a block computed once
+// (the rows form), or nullptr: each is then computed per lane where it is first read, which keeps it out of the registers until then
+// (the call is inlined, so the choice costs nothing at run time).  The clip guide's, at the slot's own t_prev, are per lane everywhere.
+template <int V, bool SEEDED, class... Key>
+__device__ __forceinline__ void update_tail(const UpdateLane& ln, f32x4 x, f32x4 e, const UpdateCoef* blk, const int64_t* t_now,
+                                            const int64_t* t_prev, const float* abar, int T_train, float eta, const float* noise,
+                                            float* z_out, const Key&... nk) {
+    constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
+    constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
+    [[maybe_unused]] f32x4 zn = {0.f, 0.f, 0.f, 0.f};      // the unkeyed DPM update (eta == 0) draws nothing
+    if constexpr (PackHas<SlotKey, Key...>::value) {      // the clip-keyed draw of a stepping slot: by clip position, at the slot's timestep
+        const QueueOf qo = lane_queue(ln.b, nk...);
+        zn = lane_pick<V>(slot_normal4(lane_slot_key(qo, nk...), qo.b, ln.o, ln.l, ln.i, ln.inner, (uint32_t)t_now[ln.tb]),
+                          ln.o * ln.inner + ln.i);
+    } else if constexpr (PackHas<CanvasKey, Key...>::value) {      // the canvas-keyed draw: canvas position from l, element (o, i) of its slice
+        zn = lane_pick<V>(canvas_normal4(pack_get<CanvasKey>(nk...), ln.b, ln.o, ln.l, ln.i, ln.inner, (uint32_t)t_now[ln.b]),
+                          ln.o * ln.inner + ln.i);
+    } else if constexpr (SEEDED) {
+        NoiseKey k;      // a one-item pack is copied as before the guide existed: through pack_get its argument loads reorder
+        if constexpr (GUIDED || CTL || COND || DPM) k = pack_get<NoiseKey>(nk...);
+        else k = NoiseKey(nk...);
+        zn = lane_pick<V>(philox_normal4(k, (uint32_t)(ln.el >> 2), k.s0 + (uint32_t)ln.b, (uint32_t)t_now[ln.b]), ln.el);
+    } else if constexpr (!DPM) {
+        if (eta > 0.f) zn = load_v<V>(noise + ln.lat);
+    }
+    const Ddim c = blk ? blk->c : ddim_coef(t_now, t_prev, abar, T_train, eta, ln.tb);
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (DPM) {
+        const DpmState ds = pack_get<DpmState>(nk...);
+        const Dpm d = blk ? blk->d : dpm_coef(ds.t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, ln.tb);
+        f32x4 hist = {0.f, 0.f, 0.f, 0.f}, x0 = {0.f, 0.f, 0.f, 0.f};
+        if (d.c_1 != 0.f) hist = load_v<V>(ds.x0_hist + ln.lat);
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            x0[k] = ddim_x0(c, x[k], e[k]);
+            o[k] = dpm_apply(d, x[k], x0[k], hist[k], zn[k], SEEDED);
+        }
+        store_v<V>(ds.x0_hist + ln.lat, x0);
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k) o[k] = ddim_apply(c, x[k], e[k], zn[k]);
+    }
+    [[maybe_unused]] GuideCoef gc{0.f, 0.f, false};
+    if constexpr (GUIDED || PackHas<CanvasGuideState, Key...>::value) gc = blk ? blk->gc : guide_coef(abar, T_train, t_prev[ln.b]);
+    if constexpr (GUIDED) o = guide_apply<V>(pack_get<GuideState>(nk...), gc, ln.b, ln.lat, ln.el, o);
+    if constexpr (PackHas<CanvasGuideState, Key...>::value)      // n_k by canvas position: the slice of the canvas-keyed draw above
+        o = canvas_guide_apply<V>(pack_get<CanvasGuideState>(nk...), gc, ln.b, ln.lat, ln.el, ln.o, ln.l, ln.i, ln.inner, o);
+    if constexpr (PackHas<ClipGuideState, Key...>::value) {      // the clip-keyed guide of a stepping slot: q at the slot's own t_prev
+        const QueueOf qo = lane_queue(ln.b, nk...);
+        o = clip_guide_apply<V>(lane_clip_guide(qo, nk...), guide_coef(abar, T_train, t_prev[ln.tb]), qo.b, ln.o, ln.l, ln.i, ln.inner, o);
+    }
+    store_v<V>(z_out + ln.lat, o);
+}
+
 template <bool SEEDED, class... Key>
 __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const float* __restrict__ eps2, const float* __restrict__ z, const int64_t* __restrict__ t_now,
     const int64_t* __restrict__ t_prev, const float* __restrict__ abar, int T_train, float guidance, float eta,
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int64_t total4, Key... nk) {
-    constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
     constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
-    constexpr bool CANVAS = PackHas<CanvasKey, Key...>::value, CGUIDED = PackHas<CanvasGuideState, Key...>::value;
     static_assert(PackOk<SEEDED, Key...>::value, "not a pack of the fused update kernels (see PackOk)");
     constexpr bool SLOT = PackHas<SlotTimes, Key...>::value;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -2639,9 +2689,9 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     const int64_t e4 = i % per4;
     const int64_t lat = (int64_t)b * g.per + e4 * 4;
     [[maybe_unused]] int tb = b;      // the entry of t_now / t_prev this lane steps with
-    [[maybe_unused]] QueueOf qo{0, b};      // "clip batch keying": the lane's queue; a pack without a ClipQueues is not touched
-    if constexpr (PackHas<ClipQueues, Key...>::value) qo = queue_of(pack_get<ClipQueues>(nk...), b);
     if constexpr (SLOT) {             // per lane: the slot of latent frame tt is tt / t; a held slot keeps z
+        // tt is divided out here on its own, not shared with the lane's position below: the shared quotient would stay in registers
+        // across the front, which costs the DPM slot packs a wave per SIMD (profiles/update_tail_kernels.txt, item 3)
         const int tt = (int)((e4 / ((int64_t)(g.W >> 2) * g.H)) % g.T);
         tb = b * pack_get<SlotTimes>(nk...).S + tt / g.t;
         if (t_now[tb] == t_prev[tb]) {
@@ -2654,81 +2704,38 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_kernel(
     [[maybe_unused]] f32x4 en = {0.f, 0.f, 0.f, 0.f};
     if constexpr (!COND) en = *reinterpret_cast<const f32x4*>(eps2 + ((int64_t)B + b) * g.per + toff);
     const f32x4 x = *reinterpret_cast<const f32x4*>(z + lat);
-    [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
-    if constexpr (CTL) cc = cfg_coef(pack_get<CfgState>(nk...), guidance, b);
-    constexpr bool SCFG = PackHas<SlotCfgState, Key...>::value;
-    [[maybe_unused]] f32x4 es = {0.f, 0.f, 0.f, 0.f};      // the slot control's eps: coefficients by tb, not by b
+    f32x4 e = {0.f, 0.f, 0.f, 0.f};
     if constexpr (PackHas<SlotMomentum, Key...>::value) {      // "slot APG momentum": this lane owns the latent address (APG mode)
         const SlotCfgCoef sf = slot_cfg_coef(pack_get<SlotCfgState>(nk...), t_now, T_train, guidance, tb);
         f32x4 d0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) d0[k] = apg_d0(ec[k], en[k]);
-        es = slot_mom_eps4(pack_get<SlotMomentum>(nk...), sf, lat, ec, d0);
-    } else if constexpr (SCFG) {
+        e = slot_mom_eps4(pack_get<SlotMomentum>(nk...), sf, lat, ec, d0);
+    } else if constexpr (PackHas<SlotCfgState, Key...>::value) {      // the slot control's eps: coefficients by tb, not by b
         const SlotCfgCoef sf = slot_cfg_coef(pack_get<SlotCfgState>(nk...), t_now, T_train, guidance, tb);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) es[k] = slot_cfg_eps(sf, ec[k], en[k]);
-    }
-    f32x4 zn = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (PackHas<SlotKey, Key...>::value) {      // the clip-keyed draw of a stepping slot: the (c, t) slice of the canvas-keyed draw
-        const int64_t hw4 = ((int64_t)g.H * g.W) >> 2, r = e4 / hw4;
-        zn = slot_normal4(lane_slot_key(qo, nk...), qo.b, r / g.T, (int)(r % g.T), (e4 % hw4) * 4, hw4 * 4, (uint32_t)t_now[tb]);
-    } else if constexpr (CANVAS) {      // the canvas-keyed draw: this lane's float4 lies inside one (c, t) slice (W % 4 == 0)
-        const int64_t hw4 = ((int64_t)g.H * g.W) >> 2, r = e4 / hw4;
-        zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, r / g.T, (int)(r % g.T), (e4 % hw4) * 4, hw4 * 4, (uint32_t)t_now[b]);
-    } else if constexpr (SEEDED) {
-        NoiseKey k;      // a one-item pack is copied as before the guide existed: through pack_get its argument loads reorder
-        if constexpr (GUIDED || CTL || COND || DPM) k = pack_get<NoiseKey>(nk...);
-        else k = NoiseKey(nk...);
-        zn = philox_normal4(k, (uint32_t)e4, k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
-    } else if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
-    const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, eta, SLOT ? tb : b);
-    [[maybe_unused]] bool apg = false;      // a run-time branch of the CTL instantiations: the launch carries an APG part
-    [[maybe_unused]] f32x4 ea = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (CTL) {
-        const CfgState cs = pack_get<CfgState>(nk...);
-        apg = cs.apg != nullptr;
-        if (apg) {
-            f32x4 d0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) d0[k] = apg_d0(ec[k], en[k]);
-            ea = apg_eps4(cs, b, lat, ec, d0);
-        }
-    }
-    f32x4 o;
-    if constexpr (DPM) {
-        const DpmState ds = pack_get<DpmState>(nk...);
-        const Dpm d = dpm_coef(ds.t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, SLOT ? tb : b);
-        f32x4 hist = {0.f, 0.f, 0.f, 0.f}, x0;
-        if (d.c_1 != 0.f) hist = *reinterpret_cast<const f32x4*>(ds.x0_hist + lat);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if constexpr (SCFG) x0[k] = ddim_x0(c, x[k], es[k]);
-            else x0[k] = ddim_x0(c, x[k], step_eps<CTL, COND>(apg, ea[k], ec[k], en[k], guidance, cc));
-            o[k] = dpm_apply(d, x[k], x0[k], hist[k], zn[k], SEEDED);
-        }
-        *reinterpret_cast<f32x4*>(ds.x0_hist + lat) = x0;
+        for (int k = 0; k < 4; ++k) e[k] = slot_cfg_eps(sf, ec[k], en[k]);
     } else {
+        [[maybe_unused]] CfgCoef cc{guidance, 0.f, 1.f};
+        [[maybe_unused]] bool apg = false;      // a run-time branch of the CTL instantiations: the launch carries an APG part
+        [[maybe_unused]] f32x4 ea = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (CTL) {
+            const CfgState cs = pack_get<CfgState>(nk...);
+            cc = cfg_coef(cs, guidance, b);
+            apg = cs.apg != nullptr;
+            if (apg) {
+                f32x4 d0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float e;
-            if constexpr (SCFG) e = es[k];
-            else e = step_eps<CTL, COND>(apg, ea[k], ec[k], en[k], guidance, cc);
-            o[k] = ddim_apply(c, x[k], e, zn[k]);
+                for (int k = 0; k < 4; ++k) d0[k] = apg_d0(ec[k], en[k]);
+                ea = apg_eps4(cs, b, lat, ec, d0);
+            }
         }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) e[k] = step_eps<CTL, COND>(apg, ea[k], ec[k], en[k], guidance, cc);
     }
-    if constexpr (GUIDED) o = guide_apply4(pack_get<GuideState>(nk...), guide_coef(abar, T_train, t_prev[b]), b, lat, e4 * 4, o);
-    if constexpr (CGUIDED) {      // the canvas-keyed guide: n_k by canvas position, the (c, t) slice of the canvas-keyed draw above
-        const int64_t hw4 = ((int64_t)g.H * g.W) >> 2, r = e4 / hw4;
-        o = canvas_guide_apply4(pack_get<CanvasGuideState>(nk...), guide_coef(abar, T_train, t_prev[b]), b, lat, e4 * 4, r / g.T,
-                                (int)(r % g.T), (e4 % hw4) * 4, hw4 * 4, o);
-    }
-    if constexpr (PackHas<ClipGuideState, Key...>::value) {      // the clip-keyed guide of a stepping slot: q at the slot's own t_prev
-        const int64_t hw4 = ((int64_t)g.H * g.W) >> 2, r = e4 / hw4;
-        o = clip_guide_apply4(lane_clip_guide(qo, nk...), guide_coef(abar, T_train, t_prev[tb]), qo.b, r / g.T, (int)(r % g.T),
-                              (e4 % hw4) * 4, hw4 * 4, o);
-    }
-    *reinterpret_cast<f32x4*>(z_out + lat) = o;
+    const int64_t hw4 = ((int64_t)g.H * g.W) >> 2, r = e4 / hw4;      // the lane's float4 lies inside one (c, t) slice (W % 4 == 0)
+    const UpdateLane ln{b, tb, lat, e4 * 4, r / g.T, (int)(r % g.T), (e4 % hw4) * 4, hw4 * 4};
+    update_tail<4, SEEDED>(ln, x, e, nullptr, t_now, t_prev, abar, T_train, eta, noise, z_out, nk...);
 }
 
 // Coalesced form (round 5).  In the kernel above a lane's 16 bytes of latent (4 consecutive w) are one 16-byte piece of a token row, and
@@ -2742,9 +2749,8 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     const float* __restrict__ eps2, const float* __restrict__ z, const int64_t* __restrict__ t_now,
     const int64_t* __restrict__ t_prev, const float* __restrict__ abar, int T_train, float guidance, float eta,
     const float* __restrict__ noise, float* __restrict__ z_out, Tube g, int B, int groups_per_sample, Key... nk) {
-    constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
+    constexpr bool DPM = PackHas<DpmState, Key...>::value;
     constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
-    constexpr bool CANVAS = PackHas<CanvasKey, Key...>::value, CGUIDED = PackHas<CanvasGuideState, Key...>::value;
     static_assert(PackOk<SEEDED, Key...>::value, "not a pack of the fused update kernels (see PackOk)");
     constexpr bool SLOT = PackHas<SlotTimes, Key...>::value;
     extern __shared__ __attribute__((aligned(16))) float ebuf[];       // [GT][D + 4]: the pad keeps the transposed 16-byte reads off one bank group
@@ -2754,8 +2760,6 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     const int b = blockIdx.x / groups_per_sample, grp = blockIdx.x % groups_per_sample;
     const int n0 = grp * GT;                                            // first token of the group (GT divides W / w: one (t', h') row)
     [[maybe_unused]] int tb = b;      // the entry of t_now / t_prev this block steps with
-    [[maybe_unused]] QueueOf qo{0, b};      // "clip batch keying": block-uniform, so the seeds are uniform loads; a pack without a ClipQueues is not touched
-    if constexpr (PackHas<ClipQueues, Key...>::value) qo = queue_of(pack_get<ClipQueues>(nk...), b);
     [[maybe_unused]] bool hold = false;
     if constexpr (SLOT) {             // the block's tokens share t': one slot, one pair, and the hold is block-uniform
         tb = b * pack_get<SlotTimes>(nk...).S + n0 / (g.Wt * g.Ht);
@@ -2778,17 +2782,7 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         [[maybe_unused]] f32x4 en = {0.f, 0.f, 0.f, 0.f};
         if constexpr (!COND) en = *reinterpret_cast<const f32x4*>(tn + (int64_t)i * 4);
         const int tok = (i * 4) / g.D, k0 = (i * 4) % g.D;
-        if constexpr (CTL) {
-            if (apg) {
-                f32x4 d0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) d0[k] = apg_d0(ec[k], en[k]);
-                *reinterpret_cast<f32x4*>(ebuf + tok * LD + k0) = ec;
-                *reinterpret_cast<f32x4*>(ebuf + (GT + tok) * LD + k0) = d0;
-                continue;
-            }
-        }
-        if constexpr (SMOM) {      // as the APG part: c and d0 parked, d and e built by the owner of the latent address below
+        if (SMOM || (CTL && apg)) {      // c and d0 parked: d and e are built by the owner of the latent address below
             f32x4 d0;
 #pragma unroll
             for (int k = 0; k < 4; ++k) d0[k] = apg_d0(ec[k], en[k]);
@@ -2805,11 +2799,9 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         *reinterpret_cast<f32x4*>(ebuf + tok * LD + k0) = e;
     }
     __syncthreads();
-    const Ddim c = ddim_coef(t_now, t_prev, abar, T_train, eta, SLOT ? tb : b);
-    [[maybe_unused]] Dpm d{0.f, 0.f, 0.f, 0.f};
-    if constexpr (DPM) d = dpm_coef(pack_get<DpmState>(nk...).t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, SLOT ? tb : b);
-    [[maybe_unused]] GuideCoef gc{0.f, 0.f, false};
-    if constexpr (GUIDED || CGUIDED) gc = guide_coef(abar, T_train, t_prev[b]);
+    UpdateCoef uc{ddim_coef(t_now, t_prev, abar, T_train, eta, tb), Dpm{0.f, 0.f, 0.f, 0.f}, GuideCoef{0.f, 0.f, false}};      // once per block
+    if constexpr (DPM) uc.d = dpm_coef(pack_get<DpmState>(nk...).t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, tb);
+    if constexpr (PackHas<GuideState, Key...>::value || PackHas<CanvasGuideState, Key...>::value) uc.gc = guide_coef(abar, T_train, t_prev[b]);
     // token coordinates of the group: n = (t' Ht + h') Wt + w'
     const int wq = n0 % g.Wt, hq = (n0 / g.Wt) % g.Ht, tq = n0 / (g.Wt * g.Ht);
     const int segs = g.D / g.w;                                          // (c, t, h) combinations of a token
@@ -2817,9 +2809,9 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
     for (int i = threadIdx.x; i < segs * per_seg4; i += 256) {
         const int sg = i / per_seg4, j = i % per_seg4;                   // piece j of line sg: token j * 4 / w, offset (j * 4) % w
         const int tok = (j * 4) / g.w, wo = (j * 4) % g.w;
-        const int hh = sg % g.h, tt = (sg / g.h) % g.t, cc = sg / (g.h * g.t);
+        const int hh = sg % g.h, tt = (sg / g.h) % g.t, co = sg / (g.h * g.t);
         f32x4 e = *reinterpret_cast<const f32x4*>(ebuf + tok * LD + sg * g.w + wo);
-        const int64_t lat = (int64_t)b * g.per + (((int64_t)cc * g.T + (tq * g.t + tt)) * g.H + (hq * g.h + hh)) * g.W + (wq + tok) * g.w + wo;
+        const int64_t lat = (int64_t)b * g.per + (((int64_t)co * g.T + (tq * g.t + tt)) * g.H + (hq * g.h + hh)) * g.W + (wq + tok) * g.w + wo;
         if constexpr (CTL) {
             if (apg)      // e holds c: this lane owns the latent address of the four elements, on this side of the exchange
                 e = apg_eps4(pack_get<CfgState>(nk...), b, lat, e, *reinterpret_cast<const f32x4*>(ebuf + (GT + tok) * LD + sg * g.w + wo));
@@ -2833,44 +2825,10 @@ __global__ __launch_bounds__(256) void cfg_unpatch_ddim_rows_kernel(
         }
         if constexpr (SMOM)      // e holds c: a stepping slot's lane on this side of the exchange reads m_prev, stores d and builds e
             e = slot_mom_eps4(pack_get<SlotMomentum>(nk...), sf, lat, e, *reinterpret_cast<const f32x4*>(ebuf + (GT + tok) * LD + sg * g.w + wo));
-        f32x4 o;
-        [[maybe_unused]] f32x4 zn = {0.f, 0.f, 0.f, 0.f};      // the unkeyed DPM update (eta == 0) draws nothing
-        if constexpr (PackHas<SlotKey, Key...>::value) {      // the clip-keyed draw: the canvas-keyed decomposition, the block's slot timestep
-            zn = slot_normal4(lane_slot_key(qo, nk...), qo.b, cc, tq * g.t + tt, (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo,
-                              (int64_t)g.H * g.W, (uint32_t)t_now[tb]);
-        } else if constexpr (CANVAS) {      // element (c, t, h, w) of window b: canvas position from t, element (c, h W + w) of its slice
-            zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, cc, tq * g.t + tt, (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo,
-                                (int64_t)g.H * g.W, (uint32_t)t_now[b]);
-        } else if constexpr (SEEDED) {
-            NoiseKey k;      // as in cfg_unpatch_ddim_kernel
-            if constexpr (GUIDED || CTL || COND || DPM) k = pack_get<NoiseKey>(nk...);
-            else k = NoiseKey(nk...);
-            zn = philox_normal4(k, (uint32_t)((lat - (int64_t)b * g.per) >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b]);
-        } else if constexpr (!DPM) {
-            if (eta > 0.f) zn = *reinterpret_cast<const f32x4*>(noise + lat);
-        }
-        if constexpr (DPM) {
-            const DpmState ds = pack_get<DpmState>(nk...);
-            f32x4 hist = {0.f, 0.f, 0.f, 0.f}, x0;
-            if (d.c_1 != 0.f) hist = *reinterpret_cast<const f32x4*>(ds.x0_hist + lat);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                x0[k] = ddim_x0(c, x[k], e[k]);
-                o[k] = dpm_apply(d, x[k], x0[k], hist[k], zn[k], SEEDED);
-            }
-            *reinterpret_cast<f32x4*>(ds.x0_hist + lat) = x0;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) o[k] = ddim_apply(c, x[k], e[k], zn[k]);
-        }
-        if constexpr (GUIDED) o = guide_apply4(pack_get<GuideState>(nk...), gc, b, lat, lat - (int64_t)b * g.per, o);
-        if constexpr (CGUIDED)      // the canvas-keyed guide: the (c, t, h, w) decomposition of the canvas-keyed draw above
-            o = canvas_guide_apply4(pack_get<CanvasGuideState>(nk...), gc, b, lat, lat - (int64_t)b * g.per, cc, tq * g.t + tt,
-                                    (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo, (int64_t)g.H * g.W, o);
-        if constexpr (PackHas<ClipGuideState, Key...>::value)      // the clip-keyed guide: the same decomposition, q at the block's slot t_prev
-            o = clip_guide_apply4(lane_clip_guide(qo, nk...), guide_coef(abar, T_train, t_prev[tb]), qo.b, cc, tq * g.t + tt,
-                                  (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo, (int64_t)g.H * g.W, o);
-        *reinterpret_cast<f32x4*>(z_out + lat) = o;
+        // element (c, t, h, w) of sample b: position t of the sliding axis, element h W + w of the (c, t) slice
+        const UpdateLane ln{b, tb, lat, lat - (int64_t)b * g.per, co, tq * g.t + tt,
+                            (int64_t)(hq * g.h + hh) * g.W + (wq + tok) * g.w + wo, (int64_t)g.H * g.W};
+        update_tail<4, SEEDED>(ln, x, e, &uc, t_now, t_prev, abar, T_train, eta, noise, z_out, nk...);
     }
 }
 
@@ -3097,88 +3055,125 @@ static void launch_unpatch(const UpdateArgs& a, const Tube& g, hipStream_t st, P
     }
 }
 
-// key, t_last / x0_hist, guide, ctl: see check_fused_update; with ctl->rescale set the statistics pass runs first, on st
-// canvas_hop != 0: the B samples are consecutive windows of one canvas, canvas_hop positions apart along T (F for audio), and the seeded
-// draw is keyed by canvas position (CanvasDims); 0: per-sample keying
+// what may ride with an update: key, t_last / x0_hist, guide, ctl, apg: see check_fused_update; slots, skey, cguide, cq: see
+// check_slot_update; scfg != nullptr: the call came through a *_slots_cfg entry
+struct UpdateRiders {
+    const avd_noise_key* key;
+    const int64_t* t_last;
+    float* x0_hist;
+    const avd_latent_guide* guide;
+    const avd_cfg_control* ctl;
+    int slots;
+    const avd_apg_control* apg;
+    const avd_slot_key* skey;
+    const avd_clip_guide* cguide;
+    const avd_slot_cfg* scfg;
+    const avd_clip_queues* cq;
+};
+// what the host body needs of a target (the statistics source rides as fused_update's SRC)
+struct UpdateTarget {
+    const char* what;          // the message prefix: the entry's name
+    const int* tags;           // the profile labels (update_tags)
+    int64_t per, half;         // one sample's latent values, and the floats of its eps rows
+    int64_t eps_bytes;         // the bytes of the CFG form's eps, which scratch and momentum buffers must not overlap
+    CanvasDims cv, gcv;        // the canvas keying of the draw and of the guide; hop 0: per-sample keying (the B samples are not windows)
+    SlotKeyDims skd;
+    int S, L;                  // the slots of the sliding axis, and its length
+    SlotGeom sg;
+    Tube g;                    // the video target's geometry (audio: empty)
+    AudioGeom ag;              // the audio target's (video: empty)
+};
+// the labels of a target's launches: the CFG form's six, then the single-branch form's
+enum { TAG_PLAIN, TAG_APG, TAG_CLIP, TAG_SCFG, TAG_SMOM, TAG_QUEUES, TAG_EPS, UPDATE_TAGS };
+struct UpdateTags {
+    int id[UPDATE_TAGS];
+    UpdateTags(const char* cfg, const char* eps) {
+        const char* const form[] = {"", "<apg>", "<clip guide>", "<slot cfg>", "<slot momentum>", "<clip queues>"};
+        for (int i = 0; i < TAG_EPS; ++i) id[i] = prof_tag_id("%s_kernel%s", cfg, form[i]);
+        id[TAG_EPS] = prof_tag_id("%s_kernel", eps);
+    }
+};
+
+// The one host body of the fused updates: the checks, all before any HIP call (a slot CFG control first, then check_fused_update, then
+// check_slot_update), the statistics passes a control asks for, on st, and the launch of the pack.  cond_only: the single-branch form
+// (a.eps holds the cond rows alone, and no control rides).  launch(pack...) is the target's launch_unpatch / launch_untoken.
+template <int SRC, class Launch>
+static int fused_update(const UpdateTarget& tg, const UpdateArgs& a, const UpdateRiders& r, bool cond_only, hipStream_t st, Launch launch) {
+    constexpr bool VIDEO = SRC == CFG_SRC_VIDEO;      // its kernels read float4: the alignment checks are the video target's
+    SlotCfgState sc{};
+    SlotMomentum sm{};
+    if (r.scfg) {
+        AVD_REQUIRE(r.slots > 0, AVD_EINVAL, "%s: a slot CFG control rides with slot timesteps (slots > 0)", tg.what);
+        if (int rc = make_slot_cfg(r.scfg, a.B, tg.sg.S, tg.sg.per_slot, tg.per, {a.z, a.z_out, r.x0_hist}, a.eps, tg.eps_bytes, sc, sm))
+            return rc;
+    }
+    AVD_REQUIRE(!VIDEO || aligned16(r.x0_hist), AVD_EUNSUPPORTED, "%s: x0_hist must be 16-byte aligned", tg.what);
+    UpdateKeys k;
+    if (int rc = check_fused_update(tg.what, a, tg.per, r.key, r.t_last, r.x0_hist, r.guide, r.ctl, k, tg.cv.hop ? &tg.cv : nullptr,
+                                    tg.gcv.hop ? &tg.gcv : nullptr, r.apg, tg.eps_bytes, r.skey)) return rc;
+    if (int rc = check_slot_update(tg.what, a, r.slots, tg.S, r.key, r.guide, r.ctl, tg.cv.hop, tg.gcv.hop, k, r.skey, tg.skd, r.cguide,
+                                   tg.L, r.cq)) return rc;
+    k.scfg = r.scfg != nullptr;
+    k.sc = sc;
+    k.smom = sm.buf != nullptr;
+    k.sm = sm;
+    const float* null_rows = a.eps + (int64_t)a.B * tg.half;
+    if (r.scfg && sc.mode != SLOT_CFG_TABLE)      // video: 16-byte aligned token rows (the entry has checked eps, and per % 4 == 0)
+        if (int rc = run_slot_cfg_stats<SRC>(r.scfg, sc, a.eps, null_rows, tg.half, a.t_now, a.t_prev, a.guidance, a.T_train, a.B, tg.sg,
+                                             tg.g, st, SlotMomentumAt{sm.buf, sm.beta, tg.per, tg.ag.len, tg.ag.F})) return rc;
+    if (r.apg) {
+        AVD_REQUIRE(!VIDEO || (aligned16(a.eps) && aligned16(null_rows) && aligned16(a.z) && aligned16(a.z_out)), AVD_EUNSUPPORTED,
+                    "%s: the APG statistics pass reads 16-byte aligned token rows", tg.what);
+        if (int rc = run_apg_stats<SRC>(r.apg, r.ctl ? r.ctl->guidance : nullptr, a.guidance, a.eps, null_rows, tg.half, a.B, tg.per, tg.g,
+                                        tg.ag, st)) return rc;
+    }
+    if (r.ctl && r.ctl->rescale) {
+        AVD_REQUIRE(!VIDEO || (aligned16(a.eps) && aligned16(null_rows)), AVD_EUNSUPPORTED,
+                    "%s: the statistics pass reads 16-byte aligned token rows", tg.what);
+        if (int rc = run_cfg_stats<SRC>(r.ctl, a.eps, null_rows, tg.half, a.guidance, a.B, tg.per, tg.ag, st)) return rc;
+    }
+    // the fused launch of an APG step is timed apart, as are the clip-guided slot update, the slot update under a slot CFG control and
+    // under its momentum, and the keyed or guided update of a clip batch; the work: bytes per latent element
+    const int tag = cond_only ? TAG_EPS : k.queues ? TAG_QUEUES : k.smom ? TAG_SMOM : r.scfg ? TAG_SCFG : r.apg ? TAG_APG
+                                                                                             : r.cguide ? TAG_CLIP : TAG_PLAIN;
+    const double bytes = cond_only ? 12.0 : (r.apg && r.apg->momentum_buf) || k.smom ? 24.0 : r.cguide ? (r.cguide->mask ? 24.0 : 20.0) : 16.0;
+    ProfScope prof(tg.tags[tag], bytes * (double)a.B * tg.per, st);
+    with_update_pack(k, cond_only, launch);
+    AVD_CHECK_LAUNCH(tg.what);
+    return AVD_OK;
+}
+
+// The video target's geometry.  canvas_hop != 0: the B samples are consecutive windows of one canvas, canvas_hop positions apart along
+// T (F for audio), and the seeded draw is keyed by canvas position (CanvasDims); guide_hop likewise for the guide's known noise
+static int unpatch_update(const char* what, bool cond_only, const UpdateArgs& a, int C, int T, int H, int W, int t, int h, int w,
+                          hipStream_t st, const UpdateRiders& r, int canvas_hop, int guide_hop) {
+    AVD_REQUIRE(a.B > 0 && a.T_train > 0, AVD_EINVAL, "%s: bad dims", what);
+    Tube g;
+    if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
+    static const UpdateTags tags("cfg_unpatch_ddim", "eps_unpatch_ddim");
+    const UpdateTarget tg{what, tags.id, g.per, g.per, (int64_t)2 * a.B * g.per * 4, CanvasDims{C, T, canvas_hop, (int64_t)H * W},
+                          CanvasDims{C, T, guide_hop, (int64_t)H * W}, SlotKeyDims{C, t, (int64_t)H * W}, T / t, T,
+                          SlotGeom{T / t, (int64_t)C * t * H * W, (int64_t)g.Ht * g.Wt * g.D, (int64_t)t * H * W}, g, AudioGeom{}};
+    return fused_update<CFG_SRC_VIDEO>(tg, a, r, cond_only, st, [&](auto... p) { launch_unpatch(a, g, st, p...); });
+}
 int cfg_unpatch_ddim_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                          const float* abar, int T_train, float guidance, float eta, const float* noise, float* z_out,
                          int B, int C, int T, int H, int W, int t, int h, int w, hipStream_t st, const avd_noise_key* key,
                          const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide, const avd_cfg_control* ctl,
                          int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg, const avd_slot_key* skey = nullptr,
                          const avd_clip_guide* cguide = nullptr, const avd_slot_cfg* scfg = nullptr, const avd_clip_queues* cq = nullptr) {
-    AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "cfg_unpatch_ddim: bad dims");
-    Tube g;
-    if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
-    // scfg != nullptr: the call came through a *_slots_cfg entry; the control is checked first
-    SlotCfgState sc{};
-    SlotMomentum sm{};
-    const SlotGeom sg{T / t, (int64_t)C * t * H * W, (int64_t)g.Ht * g.Wt * g.D, (int64_t)t * H * W};
-    if (scfg) {
-        AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_unpatch_ddim: a slot CFG control rides with slot timesteps (slots > 0)");
-        if (int rc = make_slot_cfg(scfg, B, sg.S, sg.per_slot, g.per, {z, z_out, x0_hist}, eps2, (int64_t)2 * B * g.per * 4, sc, sm))
-            return rc;
-    }
-    AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "cfg_unpatch_ddim: x0_hist must be 16-byte aligned");
-    const UpdateArgs a{eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, B};
-    UpdateKeys k;
-    const CanvasDims cv{C, T, canvas_hop, (int64_t)H * W};
-    const CanvasDims gcv{C, T, guide_hop, (int64_t)H * W};
-    if (int rc = check_fused_update("cfg_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
-                                    guide_hop ? &gcv : nullptr, apg, (int64_t)2 * B * g.per * 4, skey)) return rc;
-    if (int rc = check_slot_update("cfg_unpatch_ddim", a, slots, T / t, key, guide, ctl, canvas_hop, guide_hop, k, skey,
-                                   SlotKeyDims{C, t, (int64_t)H * W}, cguide, T, cq)) return rc;
-    k.scfg = scfg != nullptr;
-    k.sc = sc;
-    k.smom = sm.buf != nullptr;
-    k.sm = sm;
-    if (scfg && sc.mode != SLOT_CFG_TABLE)      // 16-byte aligned token rows: the entry has checked eps2, and per % 4 == 0
-        if (int rc = run_slot_cfg_stats<CFG_SRC_VIDEO>(scfg, sc, eps2, eps2 + (int64_t)B * g.per, g.per, t_now, t_prev, guidance, T_train, B,
-                                                       sg, g, st, SlotMomentumAt{sm.buf, sm.beta, g.per, 0, 0})) return rc;
-    if (apg) {
-        AVD_REQUIRE(aligned16(eps2) && aligned16(eps2 + (int64_t)B * g.per) && aligned16(z) && aligned16(z_out), AVD_EUNSUPPORTED,
-                    "cfg_unpatch_ddim: the APG statistics pass reads 16-byte aligned token rows");
-        if (int rc = run_apg_stats<CFG_SRC_VIDEO>(apg, ctl ? ctl->guidance : nullptr, guidance, eps2, eps2 + (int64_t)B * g.per, g.per, B,
-                                                  g.per, g, AudioGeom{}, st)) return rc;
-    }
-    if (ctl && ctl->rescale) {
-        AVD_REQUIRE(aligned16(eps2) && aligned16(eps2 + (int64_t)B * g.per), AVD_EUNSUPPORTED,
-                    "cfg_unpatch_ddim: the statistics pass reads 16-byte aligned token rows");
-        if (int rc = run_cfg_stats<CFG_SRC_VIDEO>(ctl, eps2, eps2 + (int64_t)B * g.per, g.per, guidance, B, g.per, AudioGeom{}, st)) return rc;
-    }
-    static const int tag = prof_tag_id("cfg_unpatch_ddim_kernel");
-    static const int tag_apg = prof_tag_id("cfg_unpatch_ddim_kernel<apg>");      // the fused launch of an APG step, timed apart
-    static const int tag_clip = prof_tag_id("cfg_unpatch_ddim_kernel<clip guide>");      // as is the clip-guided slot update
-    static const int tag_scfg = prof_tag_id("cfg_unpatch_ddim_kernel<slot cfg>");        // and the slot update under a slot CFG control
-    static const int tag_smom = prof_tag_id("cfg_unpatch_ddim_kernel<slot momentum>");   // and under its momentum
-    static const int tag_queues = prof_tag_id("cfg_unpatch_ddim_kernel<clip queues>");   // and the keyed or guided update of a clip batch
-    ProfScope prof(k.queues ? tag_queues : k.smom ? tag_smom : scfg ? tag_scfg : apg ? tag_apg : cguide ? tag_clip : tag,
-                   ((apg && apg->momentum_buf) || k.smom ? 24.0 : cguide ? (cguide->mask ? 24.0 : 20.0) : 16.0) * (double)B * g.per, st);
-    with_update_pack(k, false, [&](auto... p) { launch_unpatch(a, g, st, p...); });
-    AVD_CHECK_LAUNCH("cfg_unpatch_ddim");
-    return AVD_OK;
+    return unpatch_update("cfg_unpatch_ddim", false, UpdateArgs{eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, B}, C, T,
+                          H, W, t, h, w, st, UpdateRiders{key, t_last, x0_hist, guide, ctl, slots, apg, skey, cguide, scfg, cq}, canvas_hop,
+                          guide_hop);
 }
-
 // The single-branch fused update of a cond-only step: eps1 = [B, Nv, D], the conditional prediction alone (12 B per latent element:
 // one eps stream less than the CFG form).  key, t_last / x0_hist and guide as in cfg_unpatch_ddim_f32; the same rows / gather choice.
 int eps_unpatch_ddim_f32(const float* eps1, const float* z, const int64_t* t_now, const int64_t* t_prev, const float* abar, int T_train,
                          float eta, const float* noise, float* z_out, int B, int C, int T, int H, int W, int t, int h, int w,
                          hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist, const avd_latent_guide* guide,
                          int canvas_hop, int guide_hop) {
-    AVD_REQUIRE(B > 0 && T_train > 0, AVD_EINVAL, "eps_unpatch_ddim: bad dims");
-    Tube g;
-    if (int rc = make_tube(g, C, T, H, W, t, h, w)) return rc;
-    AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "eps_unpatch_ddim: x0_hist must be 16-byte aligned");
-    const UpdateArgs a{eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, B};
-    UpdateKeys k;
-    const CanvasDims cv{C, T, canvas_hop, (int64_t)H * W};
-    const CanvasDims gcv{C, T, guide_hop, (int64_t)H * W};
-    if (int rc = check_fused_update("eps_unpatch_ddim", a, g.per, key, t_last, x0_hist, guide, nullptr, k, canvas_hop ? &cv : nullptr,
-                                    guide_hop ? &gcv : nullptr)) return rc;
-    static const int tag = prof_tag_id("eps_unpatch_ddim_kernel");
-    ProfScope prof(tag, 12.0 * (double)B * g.per, st);
-    with_update_pack(k, true, [&](auto... p) { launch_unpatch(a, g, st, p...); });
-    AVD_CHECK_LAUNCH("eps_unpatch_ddim");
-    return AVD_OK;
+    return unpatch_update("eps_unpatch_ddim", true, UpdateArgs{eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, B}, C, T, H, W,
+                          t, h, w, st, UpdateRiders{key, t_last, x0_hist, guide}, canvas_hop, guide_hop);
 }
 
 // ------------------------------------------------------------------ fused CFG + overlap-add + DDIM (audio target)
@@ -3188,9 +3183,7 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
                                               const float* __restrict__ abar, int T_train, float guidance, float eta,
                                               const float* __restrict__ noise, float* __restrict__ z_out, int B, int Ca,
                                               int F, int len, int stride, int Na, Key... nk) {
-    constexpr bool DPM = PackHas<DpmState, Key...>::value, GUIDED = PackHas<GuideState, Key...>::value;
     constexpr bool CTL = PackHas<CfgState, Key...>::value, COND = PackHas<CondOnly, Key...>::value;
-    constexpr bool CANVAS = PackHas<CanvasKey, Key...>::value, CGUIDED = PackHas<CanvasGuideState, Key...>::value;
     static_assert(PackOk<SEEDED, Key...>::value, "not a pack of the fused update kernels (see PackOk)");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)B * Ca * F) return;
@@ -3201,8 +3194,6 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
     const int D = Ca * len;
     constexpr bool SLOT = PackHas<SlotTimes, Key...>::value;
     [[maybe_unused]] int tb = b;      // the entry of t_now / t_prev this lane steps with
-    [[maybe_unused]] QueueOf qo{0, b};      // "clip batch keying": the lane's queue; a pack without a ClipQueues is not touched
-    if constexpr (PackHas<ClipQueues, Key...>::value) qo = queue_of(pack_get<ClipQueues>(nk...), b);
     if constexpr (SLOT) {             // per lane (stride == len): chunk f / len, the uncovered tail follows the last chunk; a held slot keeps z
         const int sl = f / len;
         tb = b * Na + (sl > Na - 1 ? Na - 1 : sl);
@@ -3261,42 +3252,10 @@ __global__ void cfg_untoken_ddim_audio_kernel(const float* __restrict__ eps2, co
         }
     }
     if constexpr (CTL) e = cfg_rescale(e, cc.phi, cc.s);      // r(y) on the whole latent, the zero pad included
-    const Ddim cf = ddim_coef(t_now, t_prev, abar, T_train, eta, SLOT ? tb : b);
-    // the guide's epilogue on the value about to be stored (the identity for the unguided instantiations)
-    auto fin = [&](float v) {
-        if constexpr (GUIDED)
-            return guide_apply1(pack_get<GuideState>(nk...), guide_coef(abar, T_train, t_prev[b]), b, i, i - (int64_t)b * Ca * F, v);
-        else if constexpr (CGUIDED)      // the canvas-keyed guide: canvas position from f, element c of its slice (inner == 1)
-            return canvas_guide_apply1(pack_get<CanvasGuideState>(nk...), guide_coef(abar, T_train, t_prev[b]), b, i,
-                                       i - (int64_t)b * Ca * F, c, f, 0, 1, v);
-        else if constexpr (PackHas<ClipGuideState, Key...>::value)      // the clip-keyed guide: clip position from f, q at the slot's t_prev
-            return clip_guide_apply1(lane_clip_guide(qo, nk...), guide_coef(abar, T_train, t_prev[tb]), qo.b, c, f, 0, 1, v);
-        else
-            return v;
-    };
-    [[maybe_unused]] float zn = 0.f;      // the unkeyed DPM update (eta == 0) draws nothing
-    if constexpr (PackHas<SlotKey, Key...>::value) {      // the clip-keyed draw: clip position from f, element c of its slice, the slot's timestep
-        zn = slot_normal4(lane_slot_key(qo, nk...), qo.b, c, f, 0, 1, (uint32_t)t_now[tb])[c & 3];
-    } else if constexpr (CANVAS) {      // element (c, f) of window b: canvas position from f, element c of its slice (inner == 1)
-        zn = canvas_normal4(pack_get<CanvasKey>(nk...), b, c, f, 0, 1, (uint32_t)t_now[b])[c & 3];
-    } else if constexpr (SEEDED) {
-        NoiseKey k;      // as in cfg_unpatch_ddim_kernel
-        if constexpr (GUIDED || CTL || COND || DPM) k = pack_get<NoiseKey>(nk...);
-        else k = NoiseKey(nk...);
-        const int64_t el = i - (int64_t)b * Ca * F;
-        zn = philox_normal4(k, (uint32_t)(el >> 2), k.s0 + (uint32_t)b, (uint32_t)t_now[b])[(int)(el & 3)];
-    }
-    if constexpr (DPM) {
-        const DpmState ds = pack_get<DpmState>(nk...);
-        const Dpm d = dpm_coef(ds.t_last, t_now, t_prev, abar, T_train, SEEDED ? eta : 0.f, SLOT ? tb : b);
-        const float x = z[i], x0 = ddim_x0(cf, x, e);
-        z_out[i] = fin(dpm_apply(d, x, x0, d.c_1 != 0.f ? ds.x0_hist[i] : 0.f, zn, SEEDED));
-        ds.x0_hist[i] = x0;
-    } else if constexpr (SEEDED) {
-        z_out[i] = fin(ddim_apply(cf, z[i], e, zn));
-    } else {
-        z_out[i] = fin(ddim_apply(cf, z[i], e, eta > 0.f ? noise[i] : 0.f));
-    }
+    // element (c, f) of sample b: position f of the sliding axis, element c of its slice (inner == 1)
+    const UpdateLane ln{b, tb, i, i - (int64_t)b * Ca * F, c, f, 0, 1};
+    update_tail<1, SEEDED>(ln, f32x4{z[i], 0.f, 0.f, 0.f}, f32x4{e, 0.f, 0.f, 0.f}, nullptr, t_now, t_prev, abar, T_train, eta, noise, z_out,
+                           nk...);
 }
 
 template <class... P>
@@ -3308,6 +3267,21 @@ static void launch_untoken(const UpdateArgs& a, const AudioGeom& ag, hipStream_t
                        ag.Na, p...);
 }
 
+// the audio target's geometry; canvas_hop, guide_hop: as unpatch_update
+static int untoken_update(const char* what, bool cond_only, const UpdateArgs& a, int Ca, int F, int len, int stride, hipStream_t st,
+                          const UpdateRiders& r, int canvas_hop, int guide_hop) {
+    AVD_REQUIRE(a.B > 0 && Ca > 0 && a.T_train > 0, AVD_EINVAL, "%s: bad dims", what);
+    AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "%s: bad chunking", what);
+    AVD_REQUIRE(!r.slots || stride == len, AVD_EUNSUPPORTED, "%s: slot timesteps need non-overlapping chunks (stride %d == len %d)", what,
+                stride, len);
+    const AudioGeom ag{Ca, F, len, stride, audio_na(F, len, stride)};
+    const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
+    static const UpdateTags tags("cfg_untoken_ddim_audio", "eps_untoken_ddim_audio");
+    const UpdateTarget tg{what, tags.id, (int64_t)Ca * F, half, 2 * a.B * half * 4, CanvasDims{Ca, F, canvas_hop, 1},
+                          CanvasDims{Ca, F, guide_hop, 1}, SlotKeyDims{Ca, len, 1}, ag.Na, F,
+                          SlotGeom{ag.Na, (int64_t)Ca * len, (int64_t)Ca * len, 0}, Tube{}, ag};
+    return fused_update<CFG_SRC_AUDIO>(tg, a, r, cond_only, st, [&](auto... p) { launch_untoken(a, ag, st, p...); });
+}
 // key, t_last, x0_hist, guide, ctl: as cfg_unpatch_ddim_f32
 int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t* t_now, const int64_t* t_prev,
                                const float* abar, int T_train, float guidance, float eta, const float* noise,
@@ -3316,68 +3290,17 @@ int cfg_untoken_ddim_audio_f32(const float* eps2, const float* z, const int64_t*
                                int canvas_hop, int guide_hop, int slots, const avd_apg_control* apg, const avd_slot_key* skey = nullptr,
                                const avd_clip_guide* cguide = nullptr, const avd_slot_cfg* scfg = nullptr,
                                const avd_clip_queues* cq = nullptr) {
-    AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: bad dims");
-    AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "cfg_untoken_ddim_audio: bad chunking");
-    AVD_REQUIRE(!slots || stride == len, AVD_EUNSUPPORTED,
-                "cfg_untoken_ddim_audio: slot timesteps need non-overlapping chunks (stride %d == len %d)", stride, len);
-    const UpdateArgs a{eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, B};
-    const int64_t per = (int64_t)Ca * F;
-    UpdateKeys k;
-    const CanvasDims cv{Ca, F, canvas_hop, 1};
-    const CanvasDims gcv{Ca, F, guide_hop, 1};
-    const AudioGeom ag{Ca, F, len, stride, audio_na(F, len, stride)};
-    SlotCfgState sc{};      // as cfg_unpatch_ddim_f32: the control of a *_slots_cfg entry is checked first
-    SlotMomentum sm{};
-    const SlotGeom sg{ag.Na, (int64_t)Ca * len, (int64_t)Ca * len, 0};
-    if (scfg) {
-        AVD_REQUIRE(slots > 0, AVD_EINVAL, "cfg_untoken_ddim_audio: a slot CFG control rides with slot timesteps (slots > 0)");
-        if (int rc = make_slot_cfg(scfg, B, sg.S, sg.per_slot, per, {z, z_out, x0_hist}, eps2, (int64_t)2 * B * ag.Na * Ca * len * 4, sc,
-                                   sm)) return rc;
-    }
-    if (int rc = check_fused_update("cfg_untoken_ddim_audio", a, per, key, t_last, x0_hist, guide, ctl, k, canvas_hop ? &cv : nullptr,
-                                    guide_hop ? &gcv : nullptr, apg, (int64_t)2 * B * ag.Na * Ca * len * 4, skey)) return rc;
-    if (int rc = check_slot_update("cfg_untoken_ddim_audio", a, slots, ag.Na, key, guide, ctl, canvas_hop, guide_hop, k, skey,
-                                   SlotKeyDims{Ca, len, 1}, cguide, F, cq)) return rc;
-    k.scfg = scfg != nullptr;
-    k.sc = sc;
-    k.smom = sm.buf != nullptr;
-    k.sm = sm;
-    if (scfg && sc.mode != SLOT_CFG_TABLE) {
-        const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
-        if (int rc = run_slot_cfg_stats<CFG_SRC_AUDIO>(scfg, sc, eps2, eps2 + B * half, half, t_now, t_prev, guidance, T_train, B, sg, Tube{},
-                                                       st, SlotMomentumAt{sm.buf, sm.beta, per, len, F})) return rc;
-    }
-    if (apg) {
-        const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
-        if (int rc = run_apg_stats<CFG_SRC_AUDIO>(apg, ctl ? ctl->guidance : nullptr, guidance, eps2, eps2 + B * half, half, B, per,
-                                                  Tube{}, ag, st)) return rc;
-    }
-    if (ctl && ctl->rescale) {
-        const int64_t half = (int64_t)ag.Na * Ca * len;      // one sample's token rows
-        if (int rc = run_cfg_stats<CFG_SRC_AUDIO>(ctl, eps2, eps2 + B * half, half, guidance, B, per, ag, st)) return rc;
-    }
-    with_update_pack(k, false, [&](auto... p) { launch_untoken(a, ag, st, p...); });
-    AVD_CHECK_LAUNCH("cfg_untoken_ddim_audio");
-    return AVD_OK;
+    return untoken_update("cfg_untoken_ddim_audio", false, UpdateArgs{eps2, z, t_now, t_prev, abar, T_train, guidance, eta, noise, z_out, B},
+                          Ca, F, len, stride, st, UpdateRiders{key, t_last, x0_hist, guide, ctl, slots, apg, skey, cguide, scfg, cq},
+                          canvas_hop, guide_hop);
 }
-
 // the single-branch form (eps1 = [B, Na, Ca * len]): as eps_unpatch_ddim_f32
 int eps_untoken_ddim_audio_f32(const float* eps1, const float* z, const int64_t* t_now, const int64_t* t_prev, const float* abar,
                                int T_train, float eta, const float* noise, float* z_out, int B, int Ca, int F, int len, int stride,
                                hipStream_t st, const avd_noise_key* key, const int64_t* t_last, float* x0_hist,
                                const avd_latent_guide* guide, int canvas_hop, int guide_hop) {
-    AVD_REQUIRE(B > 0 && Ca > 0 && T_train > 0, AVD_EINVAL, "eps_untoken_ddim_audio: bad dims");
-    AVD_REQUIRE(len > 0 && stride > 0 && F >= len, AVD_EUNSUPPORTED, "eps_untoken_ddim_audio: bad chunking");
-    const UpdateArgs a{eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, B};
-    UpdateKeys k;
-    const CanvasDims cv{Ca, F, canvas_hop, 1};
-    const CanvasDims gcv{Ca, F, guide_hop, 1};
-    if (int rc = check_fused_update("eps_untoken_ddim_audio", a, (int64_t)Ca * F, key, t_last, x0_hist, guide, nullptr, k,
-                                    canvas_hop ? &cv : nullptr, guide_hop ? &gcv : nullptr)) return rc;
-    const AudioGeom ag{Ca, F, len, stride, audio_na(F, len, stride)};
-    with_update_pack(k, true, [&](auto... p) { launch_untoken(a, ag, st, p...); });
-    AVD_CHECK_LAUNCH("eps_untoken_ddim_audio");
-    return AVD_OK;
+    return untoken_update("eps_untoken_ddim_audio", true, UpdateArgs{eps1, z, t_now, t_prev, abar, T_train, 0.f, eta, noise, z_out, B}, Ca, F,
+                          len, stride, st, UpdateRiders{key, t_last, x0_hist, guide}, canvas_hop, guide_hop);
 }
 
 // ------------------------------------------------------------------ CFG-stacked sequence assembly

@@ -74,8 +74,9 @@ def _canvases(geom, dev, P=None, seed=1, offset=0):
     return outs
 
 
-def _run(dev, geom, z, eps2, tn, tp, tl, hist, eta, key, guide, cq=None):
-    """one fused update through a C entry: the clips entry with ``cq``, else the existing guided or seeded entry"""
+def _run(dev, geom, z, eps2, tn, tp, tl, hist, eta, key, guide, cq=None, ctl=None):
+    """one fused update through a C entry: the clips entry with ``cq``, else the existing controlled (``ctl``: an avd_slot_cfg), guided
+    or seeded entry"""
     L, _ = _fn()
     video, sl, S, Nt, D = _dims(geom)
     out = torch.empty_like(z)
@@ -84,9 +85,12 @@ def _run(dev, geom, z, eps2, tn, tp, tl, hist, eta, key, guide, cq=None):
     head = (eps2.data_ptr(), z.data_ptr(), L.ptr(tl), tn.data_ptr(), tp.data_ptr(), ab.data_ptr(), T_TRAIN, GS, eta)
     dims = (z.shape[0],) + tuple(geom[1][1:]) + tuple(geom[2])
     kp, gp = (None if key is None else C.byref(key)), (None if guide is None else C.byref(guide))
+    cp = None if ctl is None else C.byref(ctl)
     st = L.stream_ptr(dev)
     if cq is not None:
-        rc = getattr(L.lib(), name + "_slots_clips_f32")(*head, kp, gp, C.byref(cq), S, L.ptr(hist), out.data_ptr(), *dims, None, st)
+        rc = getattr(L.lib(), name + "_slots_clips_f32")(*head, kp, gp, C.byref(cq), S, L.ptr(hist), out.data_ptr(), *dims, cp, st)
+    elif ctl is not None:
+        rc = getattr(L.lib(), name + "_slots_cfg_f32")(*head, kp, gp, S, L.ptr(hist), out.data_ptr(), *dims, cp, st)
     elif guide is not None:
         rc = getattr(L.lib(), name + "_slots_guided_f32")(*head, kp, gp, S, L.ptr(hist), out.data_ptr(), *dims, st)
     else:
@@ -103,8 +107,8 @@ def _queues(dev, K, B, step=None, guide=None):
     return Fn.clip_queues(K, B, s, g), (s, g)
 
 
-def _clips(dev, geom, z, eps2, tn, tp, tl, hist, eta, first, cursor, step=None, known=None, masks=None, gseeds=None, K=None):
-    """the clips entry on the whole batch: (z_out, x0_hist after)"""
+def _clips(dev, geom, z, eps2, tn, tp, tl, hist, eta, first, cursor, step=None, known=None, masks=None, gseeds=None, K=None, ctl=None):
+    """the clips entry on the whole batch: (z_out, x0_hist after); ``ctl``: samples -> the batch's avd_slot_cfg"""
     _, Fn = _fn()
     _, sl, S, _, _ = _dims(geom)
     K = geom[3] if K is None else K
@@ -112,12 +116,13 @@ def _clips(dev, geom, z, eps2, tn, tp, tl, hist, eta, first, cursor, step=None, 
     guide = None if known is None else Fn.clip_guide(known[0], None if masks is None else masks[0], 0, first, S, cursor, tuple(z.shape))
     cq, keep = _queues(dev, K, z.shape[0], step if eta > 0 else None, gseeds if known is not None else None)
     h = None if hist is None else hist.clone()
-    out, _ = _run(dev, geom, z, eps2, tn, tp, tl if h is not None else None, h, eta, key, guide, cq)
+    out, _ = _run(dev, geom, z, eps2, tn, tp, tl if h is not None else None, h, eta, key, guide, cq,
+                  None if ctl is None else ctl(slice(0, z.shape[0])))
     return out, h
 
 
-def _slices(dev, geom, z, eps2, tn, tp, tl, hist, eta, first, cursor, step, known=None, masks=None, gseeds=None, K=None):
-    """the reference: K calls of the existing seeded / guided entry on the K sample slices"""
+def _slices(dev, geom, z, eps2, tn, tp, tl, hist, eta, first, cursor, step, known=None, masks=None, gseeds=None, K=None, ctl=None):
+    """the reference: K calls of the existing seeded / guided / controlled entry on the K sample slices"""
     _, Fn = _fn()
     _, sl, S, _, _ = _dims(geom)
     K = geom[3] if K is None else K
@@ -134,7 +139,7 @@ def _slices(dev, geom, z, eps2, tn, tp, tl, hist, eta, first, cursor, step, know
         e = torch.cat([eps2[:B][q], eps2[B:][q]]).contiguous()
         h = None if hist is None else hist[q].clone()
         out[q], _ = _run(dev, geom, z[q].contiguous(), e, tn[q].contiguous(), tp[q].contiguous(),
-                         tl[q].contiguous() if h is not None else None, h, eta, key, guide)
+                         tl[q].contiguous() if h is not None else None, h, eta, key, guide, ctl=None if ctl is None else ctl(q))
         if h is not None:
             h_out[q] = h
     return out, h_out
@@ -188,6 +193,57 @@ def test_canvases_off_a_16_byte_boundary_take_the_scalar_reads(dev):
             b = _clips(dev, geom, z, eps2, tn, tp, tl, hist, 0.5, 0, cursor, step=SEEDS[:2], known=ku, masks=mu, gseeds=GSEEDS[:2])
             _same(a, b)
             _same(b, _slices(dev, geom, z, eps2, tn, tp, tl, hist, 0.5, 0, cursor, SEEDS[:2], ku, mu, GSEEDS[:2]))
+
+
+WIDEST = [("video", (2, 8, 4, 16, 16), (2, 4, 4), 2), ("audio", (2, 6, 10), (4, 4), 2)]
+
+
+@pytest.mark.parametrize("geom", WIDEST, ids=["video", "audio"])
+def test_the_widest_slot_pack_equals_its_one_queue_slices(dev, geom):
+    """DPM-Solver++(2M) at eta > 0 under a slot key, the slot APG with a momentum buffer, a masked clip guide and K = 2 queues: every
+    item a slot pack can hold, in one launch of each form.  Slot 1 of sample 0 is held; with first + cursor = 4 and P = 5.5 slots the
+    canvas ends inside every sample's second slot."""
+    L, _ = _fn()
+    video, sl, S, _, _ = _dims(geom)
+    shape = geom[1]
+    B, K = shape[0], geom[3]
+    per_slot = shape[1] * sl * (shape[3] * shape[4] if video else 1)
+    z, eps2, hist = _inputs(geom, dev, seed=5)
+    tn, tp, tl = _tables(B, S, dev)
+    held = (tn == tp).cpu()
+    assert S == 2 and held.tolist() == [[False, True], [False, False]]
+    cursor = torch.tensor([2], dtype=torch.int32, device=dev)
+    known, masks = _canvases(geom, dev)
+    assert (2 + 2) * sl < known.shape[2] < (2 + 2 + S) * sl
+    M0 = torch.randn(shape, generator=torch.Generator().manual_seed(17)).to(dev)
+    gtab = torch.linspace(1.0, 6.0, T_TRAIN).to(dev)
+    keep = []
+
+    def control(M):
+        def of(q):
+            n = q.stop - q.start
+            nb = L.lib().avd_slot_cfg_stats_bytes(n, S, per_slot)
+            stats = torch.zeros(nb, dtype=torch.uint8, device=dev)
+            keep.append(stats)
+            return L.SlotCfgMomentum(gtab.data_ptr(), None, L.SLOT_APG_MOMENTUM, 2.0, 0.25, stats.data_ptr(), nb, -0.5, M[q].data_ptr())
+        return of
+
+    got = {}
+    for rows in ((1, 0) if video else (1,)):
+        with tuned(cfg_rows=rows):
+            Mk, Ms = M0.clone(), M0.clone()
+            a = _clips(dev, geom, z, eps2, tn, tp, tl, hist, 0.5, 2, cursor, step=SEEDS[:K], known=known, masks=masks, gseeds=GSEEDS[:K],
+                       ctl=control(Mk))
+            _same(a, _slices(dev, geom, z, eps2, tn, tp, tl, hist, 0.5, 2, cursor, SEEDS[:K], known, masks, GSEEDS[:K], ctl=control(Ms)))
+            assert torch.equal(Mk, Ms) and not torch.equal(Mk, M0)
+            got[rows] = a + (Mk,)
+    if video:
+        assert all(torch.equal(x, y) for x, y in zip(got[1], got[0]))
+    out, h, M = got[1]
+    for b, s in held.nonzero().tolist():      # a held slot keeps z, and its history and momentum stay as they were
+        for after, before in ((out, z), (h, hist), (M, M0)):
+            assert torch.equal(after[b, :, s * sl:(s + 1) * sl], before[b, :, s * sl:(s + 1) * sl])
+    assert not torch.equal(out[0, :, :sl], z[0, :, :sl])
 
 
 # ------------------------------------------------------------------------------------------------- 2. the guide's properties
