@@ -1085,18 +1085,62 @@ extern "C" int avd_denoise_step_f32(const avd_step_desc* s, const float* z, cons
     return denoise_step(s, nullptr, z, Xp, t_now, t_prev, noise, z_out, workspace, workspace_bytes, stream);
 }
 
-// The whole step on slot timesteps ("slot timesteps" in the header): t_now / t_prev are [B, S] tables.  Everything outside the scope is
-// refused here, before the model runs: the fused update's launcher repeats the geometry checks.
+// The checks the six whole-step slot entries share ("slot timesteps" in the header), made here, before the model runs, as the fused
+// update's launcher makes the geometry, key, guide and control checks again.  need: the riders this entry cannot do without; a control,
+// a key, a guide or a history it merely accepts is checked when present (the key: when eta > 0 reads it).  SLOT_ETA0: the entry has no
+// key, so it takes eta == 0 alone; every other entry asks for the key at eta > 0.  One sequence serves all six: the nulls, the eta
+// rule, the embedding and its slots, the control, the history's pairing / aliasing / alignment, the guide, the key, the geometry the
+// key and the guide must share, the queues.
+enum { SLOT_ETA0 = 1, SLOT_HIST = 2, SLOT_KEY = 4, SLOT_GUIDE = 8, SLOT_CFG = 16, SLOT_QUEUES = 32 };
+static int check_slot_step(const char* what, int need, const avd_step_desc* s, const avd_slot_cfg* cfg, const avd_slot_key* key,
+                           const avd_clip_guide* guide, const avd_clip_queues* queues, const int64_t* t_last, const float* x0_hist,
+                           const float* z, const float* z_out, const void* workspace, int64_t workspace_bytes, int slots) {
+    AVD_REQUIRE(s, AVD_EINVAL, "%s: null descriptor", what);
+    AVD_REQUIRE(cfg || !(need & SLOT_CFG), AVD_EINVAL, "%s: null slot CFG control", what);
+    AVD_REQUIRE(key || !(need & SLOT_KEY), AVD_EINVAL, "%s: null slot key", what);
+    AVD_REQUIRE(guide || !(need & SLOT_GUIDE), AVD_EINVAL, "%s: null clip guide", what);
+    AVD_REQUIRE(queues || !(need & SLOT_QUEUES), AVD_EINVAL, "%s: null clip queues", what);
+    const bool keyed = s->eta > 0.f;
+    if (need & SLOT_ETA0)
+        AVD_REQUIRE(s->eta == 0.f, AVD_EINVAL, "%s: slot timesteps take the %s update at eta == 0 (eta is %g)", what,
+                    (need & SLOT_HIST) ? "ODE" : "DDIM", (double)s->eta);
+    AVD_REQUIRE(key || !keyed, AVD_EINVAL, "%s: eta > 0 needs a slot key", what);
+    const avd_embed_desc& e = s->embed;
+    AVD_REQUIRE(!e.temb_add, AVD_EINVAL, "%s: slot timesteps take the concat embedding (temb_add == 0)", what);
+    if (int rc = check_embed(&e)) return rc;
+    int S = 0, tok = 0;
+    if (int rc = embed_slots(&e, S, tok)) return rc;
+    AVD_REQUIRE(slots == S, AVD_EINVAL, "%s: slots %d must equal the geometry's %d slots along the sliding axis", what, slots, S);
+    const int64_t inner = (int64_t)e.H * e.W, per = (int64_t)e.C * e.T * inner;
+    const int64_t per_slot = (int64_t)e.C * e.p0 * (e.target_kind == 0 ? inner : 1);
+    if (cfg)
+        if (int rc = check_slot_cfg(cfg, e.B, S, per_slot, per, z, z_out, x0_hist, workspace, workspace_bytes)) return rc;
+    AVD_REQUIRE(!(need & SLOT_HIST) || (t_last && x0_hist), AVD_EINVAL, "%s: null t_last or x0_hist", what);
+    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "%s: t_last and x0_hist go together (the DPM-Solver++(2M) update)", what);
+    if (x0_hist) {
+        AVD_REQUIRE(!(z && overlaps(x0_hist, z, e.B * per)) && !(z_out && overlaps(x0_hist, z_out, e.B * per)), AVD_EINVAL,
+                    "%s: x0_hist must not alias z or z_out", what);
+        AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "%s: x0_hist must be 16-byte aligned", what);
+    }
+    if (guide)
+        if (int rc = check_clip_guide(guide, e.B, e.C, e.T, S, e.p0, inner, z_out, x0_hist, queues ? queues->K : 1)) return rc;
+    if (keyed) {
+        if (int rc = check_slot_key(key, e.B, e.C, e.p0, inner)) return rc;
+        AVD_REQUIRE(!guide || (key->first == guide->first && key->stride == guide->stride && key->cursor == guide->cursor), AVD_EINVAL,
+                    "%s: the slot key's first / stride / cursor must equal the clip guide's", what);
+    }
+    if (queues)
+        if (int rc = check_clip_queues(queues, guide, keyed, e.B, e.C, e.T, inner, z_out, x0_hist)) return rc;
+    return AVD_OK;
+}
+
+// The whole step on slot timesteps: t_now / t_prev are [B, S] tables, the DDIM update at eta == 0.
 extern "C" int avd_denoise_step_slots_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_now,
                                           const int64_t* t_prev, int slots, float* z_out, void* workspace, int64_t workspace_bytes,
                                           avd_stream_t stream) {
-    AVD_REQUIRE(s, AVD_EINVAL, "denoise_step_slots: null descriptor");
-    AVD_REQUIRE(s->eta == 0.f, AVD_EINVAL, "denoise_step_slots: slot timesteps take the DDIM update at eta == 0 (eta is %g)", (double)s->eta);
-    AVD_REQUIRE(!s->embed.temb_add, AVD_EINVAL, "denoise_step_slots: slot timesteps take the concat embedding (temb_add == 0)");
-    if (int rc = check_embed(&s->embed)) return rc;
-    int S = 0, tok = 0;
-    if (int rc = embed_slots(&s->embed, S, tok)) return rc;
-    AVD_REQUIRE(slots == S, AVD_EINVAL, "denoise_step_slots: slots %d must equal the geometry's %d slots along the sliding axis", slots, S);
+    if (int rc = check_slot_step("denoise_step_slots", SLOT_ETA0, s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, z, z_out,
+                                 workspace, workspace_bytes, slots))
+        return rc;
     return denoise_step(s, nullptr, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr,
                         nullptr, 0, 0, slots);
 }
@@ -1106,154 +1150,62 @@ extern "C" int avd_denoise_step_slots_f32(const avd_step_desc* s, const float* z
 extern "C" int avd_denoise_step_slots_dpmpp_2m_f32(const avd_step_desc* s, const float* z, const float* Xp, const int64_t* t_last,
                                                    const int64_t* t_now, const int64_t* t_prev, int slots, float* x0_hist, float* z_out,
                                                    void* workspace, int64_t workspace_bytes, avd_stream_t stream) {
-    AVD_REQUIRE(s, AVD_EINVAL, "denoise_step_slots_dpmpp_2m: null descriptor");
-    AVD_REQUIRE(s->eta == 0.f, AVD_EINVAL, "denoise_step_slots_dpmpp_2m: slot timesteps take the ODE update at eta == 0 (eta is %g)",
-                (double)s->eta);
-    AVD_REQUIRE(!s->embed.temb_add, AVD_EINVAL, "denoise_step_slots_dpmpp_2m: slot timesteps take the concat embedding (temb_add == 0)");
-    if (int rc = check_embed(&s->embed)) return rc;
-    int S = 0, tok = 0;
-    if (int rc = embed_slots(&s->embed, S, tok)) return rc;
-    AVD_REQUIRE(slots == S, AVD_EINVAL, "denoise_step_slots_dpmpp_2m: slots %d must equal the geometry's %d slots along the sliding axis",
-                slots, S);
-    if (int rc = check_step_options("denoise_step_slots_dpmpp_2m", NEED_HIST, s, nullptr, t_last, x0_hist, z, z_out, nullptr, nullptr, nullptr))
+    if (int rc = check_slot_step("denoise_step_slots_dpmpp_2m", SLOT_ETA0 | SLOT_HIST, s, nullptr, nullptr, nullptr, nullptr, t_last,
+                                 x0_hist, z, z_out, workspace, workspace_bytes, slots))
         return rc;
-    AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "denoise_step_slots_dpmpp_2m: x0_hist must be 16-byte aligned");
     return denoise_step(s, nullptr, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, nullptr,
                         nullptr, 0, 0, slots);
 }
 
 // The whole step on slot timesteps at eta > 0 ("clip-keyed slot noise" in the header), both solvers: t_last / x0_hist both null = DDIM,
-// both set = the SDE form of the DPM-Solver++(2M) slot update.  The front end is avd_denoise_step_slots_f32's; the key is checked here,
-// before the model runs, as the fused update's launcher checks it again.  At eta == 0 the key is not read: the plain slot step.
+// both set = the SDE form of the DPM-Solver++(2M) slot update.  At eta == 0 the key is not read: the plain slot step.
 extern "C" int avd_denoise_step_slots_seeded_f32(const avd_step_desc* s, const avd_slot_key* key, const int64_t* t_last, float* x0_hist,
                                                  const float* z, const float* Xp, const int64_t* t_now, const int64_t* t_prev, int slots,
                                                  float* z_out, void* workspace, int64_t workspace_bytes, avd_stream_t stream) {
-    AVD_REQUIRE(s, AVD_EINVAL, "denoise_step_slots_seeded: null descriptor");
-    AVD_REQUIRE(key, AVD_EINVAL, "denoise_step_slots_seeded: null slot key");
-    AVD_REQUIRE(!s->embed.temb_add, AVD_EINVAL, "denoise_step_slots_seeded: slot timesteps take the concat embedding (temb_add == 0)");
-    if (int rc = check_embed(&s->embed)) return rc;
-    int S = 0, tok = 0;
-    if (int rc = embed_slots(&s->embed, S, tok)) return rc;
-    AVD_REQUIRE(slots == S, AVD_EINVAL, "denoise_step_slots_seeded: slots %d must equal the geometry's %d slots along the sliding axis", slots,
-                S);
-    const avd_embed_desc& e = s->embed;
-    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "denoise_step_slots_seeded: t_last and x0_hist go together (the DPM-Solver++(2M) update)");
-    if (x0_hist) {
-        const int64_t n = (int64_t)e.B * e.C * e.T * e.H * e.W;
-        AVD_REQUIRE(!(z && overlaps(x0_hist, z, n)) && !(z_out && overlaps(x0_hist, z_out, n)), AVD_EINVAL,
-                    "denoise_step_slots_seeded: x0_hist must not alias z or z_out");
-        AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "denoise_step_slots_seeded: x0_hist must be 16-byte aligned");
-    }
-    if (s->eta > 0.f)
-        if (int rc = check_slot_key(key, e.B, e.C, e.p0, (int64_t)e.H * e.W)) return rc;
+    if (int rc = check_slot_step("denoise_step_slots_seeded", SLOT_KEY, s, nullptr, key, nullptr, nullptr, t_last, x0_hist, z, z_out,
+                                 workspace, workspace_bytes, slots))
+        return rc;
     return denoise_step(s, nullptr, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, nullptr,
                         nullptr, 0, 0, slots, nullptr, key);
 }
 
 // The whole step on slot timesteps under a clip-keyed latent guide ("clip-keyed latent guide" in the header), both solvers, eta >= 0:
-// avd_denoise_step_slots_seeded_f32 with the guide added.  The guide, and the key where eta > 0 reads it, are checked here, before the
-// model runs, as the fused update's launcher checks them again.
+// avd_denoise_step_slots_seeded_f32 with the guide added, and the key needed only where eta > 0 reads it.
 extern "C" int avd_denoise_step_slots_guided_f32(const avd_step_desc* s, const avd_slot_key* key, const avd_clip_guide* guide,
                                                  const int64_t* t_last, float* x0_hist, const float* z, const float* Xp,
                                                  const int64_t* t_now, const int64_t* t_prev, int slots, float* z_out, void* workspace,
                                                  int64_t workspace_bytes, avd_stream_t stream) {
-    AVD_REQUIRE(s, AVD_EINVAL, "denoise_step_slots_guided: null descriptor");
-    AVD_REQUIRE(guide, AVD_EINVAL, "denoise_step_slots_guided: null clip guide");
-    AVD_REQUIRE(key || !(s->eta > 0.f), AVD_EINVAL, "denoise_step_slots_guided: eta > 0 needs a slot key");
-    AVD_REQUIRE(!s->embed.temb_add, AVD_EINVAL, "denoise_step_slots_guided: slot timesteps take the concat embedding (temb_add == 0)");
-    if (int rc = check_embed(&s->embed)) return rc;
-    int S = 0, tok = 0;
-    if (int rc = embed_slots(&s->embed, S, tok)) return rc;
-    AVD_REQUIRE(slots == S, AVD_EINVAL, "denoise_step_slots_guided: slots %d must equal the geometry's %d slots along the sliding axis", slots,
-                S);
-    const avd_embed_desc& e = s->embed;
-    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "denoise_step_slots_guided: t_last and x0_hist go together (the DPM-Solver++(2M) update)");
-    if (x0_hist) {
-        const int64_t n = (int64_t)e.B * e.C * e.T * e.H * e.W;
-        AVD_REQUIRE(!(z && overlaps(x0_hist, z, n)) && !(z_out && overlaps(x0_hist, z_out, n)), AVD_EINVAL,
-                    "denoise_step_slots_guided: x0_hist must not alias z or z_out");
-        AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "denoise_step_slots_guided: x0_hist must be 16-byte aligned");
-    }
-    if (int rc = check_clip_guide(guide, e.B, e.C, e.T, S, e.p0, (int64_t)e.H * e.W, z_out, x0_hist)) return rc;
-    if (s->eta > 0.f) {
-        if (int rc = check_slot_key(key, e.B, e.C, e.p0, (int64_t)e.H * e.W)) return rc;
-        AVD_REQUIRE(key->first == guide->first && key->stride == guide->stride && key->cursor == guide->cursor, AVD_EINVAL,
-                    "denoise_step_slots_guided: the slot key's first / stride / cursor must equal the clip guide's");
-    }
+    if (int rc = check_slot_step("denoise_step_slots_guided", SLOT_GUIDE, s, nullptr, key, guide, nullptr, t_last, x0_hist, z, z_out,
+                                 workspace, workspace_bytes, slots))
+        return rc;
     return denoise_step(s, nullptr, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, nullptr,
                         nullptr, 0, 0, slots, nullptr, s->eta > 0.f ? key : nullptr, guide);
 }
 
 // The whole step on slot timesteps under a slot CFG control ("slot CFG control" in the header): avd_denoise_step_slots_guided_f32 with
-// the control added and the guide optional.  The control is checked first, with the whole workspace as the eps source; its statistics
-// pass runs in the fused update's launcher, on the caller's stream after the join of the two streams.
+// the control added and the guide optional.  The control is checked with the whole workspace as the eps source; its statistics pass
+// runs in the fused update's launcher, on the caller's stream after the join of the two streams.
 extern "C" int avd_denoise_step_slots_cfg_f32(const avd_step_desc* s, const avd_slot_cfg* cfg, const avd_slot_key* key,
                                               const avd_clip_guide* guide, const int64_t* t_last, float* x0_hist, const float* z,
                                               const float* Xp, const int64_t* t_now, const int64_t* t_prev, int slots, float* z_out,
                                               void* workspace, int64_t workspace_bytes, avd_stream_t stream) {
-    AVD_REQUIRE(s, AVD_EINVAL, "denoise_step_slots_cfg: null descriptor");
-    AVD_REQUIRE(cfg, AVD_EINVAL, "denoise_step_slots_cfg: null slot CFG control");
-    AVD_REQUIRE(key || !(s->eta > 0.f), AVD_EINVAL, "denoise_step_slots_cfg: eta > 0 needs a slot key");
-    AVD_REQUIRE(!s->embed.temb_add, AVD_EINVAL, "denoise_step_slots_cfg: slot timesteps take the concat embedding (temb_add == 0)");
-    if (int rc = check_embed(&s->embed)) return rc;
-    int S = 0, tok = 0;
-    if (int rc = embed_slots(&s->embed, S, tok)) return rc;
-    AVD_REQUIRE(slots == S, AVD_EINVAL, "denoise_step_slots_cfg: slots %d must equal the geometry's %d slots along the sliding axis", slots, S);
-    const avd_embed_desc& e = s->embed;
-    const int64_t per = (int64_t)e.C * e.T * e.H * e.W;
-    const int64_t per_slot = e.target_kind == 0 ? (int64_t)e.C * e.p0 * e.H * e.W : (int64_t)e.C * e.p0;
-    if (int rc = check_slot_cfg(cfg, e.B, S, per_slot, per, z, z_out, x0_hist, workspace, workspace_bytes)) return rc;
-    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "denoise_step_slots_cfg: t_last and x0_hist go together (the DPM-Solver++(2M) update)");
-    if (x0_hist) {
-        AVD_REQUIRE(!(z && overlaps(x0_hist, z, e.B * per)) && !(z_out && overlaps(x0_hist, z_out, e.B * per)), AVD_EINVAL,
-                    "denoise_step_slots_cfg: x0_hist must not alias z or z_out");
-        AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "denoise_step_slots_cfg: x0_hist must be 16-byte aligned");
-    }
-    if (guide)
-        if (int rc = check_clip_guide(guide, e.B, e.C, e.T, S, e.p0, (int64_t)e.H * e.W, z_out, x0_hist)) return rc;
-    if (s->eta > 0.f) {
-        if (int rc = check_slot_key(key, e.B, e.C, e.p0, (int64_t)e.H * e.W)) return rc;
-        AVD_REQUIRE(!guide || (key->first == guide->first && key->stride == guide->stride && key->cursor == guide->cursor), AVD_EINVAL,
-                    "denoise_step_slots_cfg: the slot key's first / stride / cursor must equal the clip guide's");
-    }
+    if (int rc = check_slot_step("denoise_step_slots_cfg", SLOT_CFG, s, cfg, key, guide, nullptr, t_last, x0_hist, z, z_out, workspace,
+                                 workspace_bytes, slots))
+        return rc;
     return denoise_step(s, nullptr, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, nullptr,
                         nullptr, 0, 0, slots, nullptr, s->eta > 0.f ? key : nullptr, guide, cfg);
 }
 
 // The whole step of a FIFO clip batch under per-queue keys and guides ("clip batch keying" in the header): avd_denoise_step_slots_cfg_f32
-// with the descriptor and the control optional.  The descriptor is checked here, before the model runs, with the guide and the key.
+// with the queue descriptor added and the control optional.
 extern "C" int avd_denoise_step_slots_clips_f32(const avd_step_desc* s, const avd_slot_cfg* cfg, const avd_slot_key* key,
                                                 const avd_clip_guide* guide, const avd_clip_queues* queues, const int64_t* t_last,
                                                 float* x0_hist, const float* z, const float* Xp, const int64_t* t_now,
                                                 const int64_t* t_prev, int slots, float* z_out, void* workspace, int64_t workspace_bytes,
                                                 avd_stream_t stream) {
-    AVD_REQUIRE(s, AVD_EINVAL, "denoise_step_slots_clips: null descriptor");
-    AVD_REQUIRE(queues, AVD_EINVAL, "denoise_step_slots_clips: null clip queues");
-    AVD_REQUIRE(key || !(s->eta > 0.f), AVD_EINVAL, "denoise_step_slots_clips: eta > 0 needs a slot key");
-    AVD_REQUIRE(!s->embed.temb_add, AVD_EINVAL, "denoise_step_slots_clips: slot timesteps take the concat embedding (temb_add == 0)");
-    if (int rc = check_embed(&s->embed)) return rc;
-    int S = 0, tok = 0;
-    if (int rc = embed_slots(&s->embed, S, tok)) return rc;
-    AVD_REQUIRE(slots == S, AVD_EINVAL, "denoise_step_slots_clips: slots %d must equal the geometry's %d slots along the sliding axis", slots, S);
-    const avd_embed_desc& e = s->embed;
-    const int64_t per = (int64_t)e.C * e.T * e.H * e.W;
-    const int64_t per_slot = e.target_kind == 0 ? (int64_t)e.C * e.p0 * e.H * e.W : (int64_t)e.C * e.p0;
-    if (cfg)
-        if (int rc = check_slot_cfg(cfg, e.B, S, per_slot, per, z, z_out, x0_hist, workspace, workspace_bytes)) return rc;
-    AVD_REQUIRE(!t_last == !x0_hist, AVD_EINVAL, "denoise_step_slots_clips: t_last and x0_hist go together (the DPM-Solver++(2M) update)");
-    if (x0_hist) {
-        AVD_REQUIRE(!(z && overlaps(x0_hist, z, e.B * per)) && !(z_out && overlaps(x0_hist, z_out, e.B * per)), AVD_EINVAL,
-                    "denoise_step_slots_clips: x0_hist must not alias z or z_out");
-        AVD_REQUIRE(aligned16(x0_hist), AVD_EUNSUPPORTED, "denoise_step_slots_clips: x0_hist must be 16-byte aligned");
-    }
-    if (guide)
-        if (int rc = check_clip_guide(guide, e.B, e.C, e.T, S, e.p0, (int64_t)e.H * e.W, z_out, x0_hist, queues->K)) return rc;
-    if (s->eta > 0.f) {
-        if (int rc = check_slot_key(key, e.B, e.C, e.p0, (int64_t)e.H * e.W)) return rc;
-        AVD_REQUIRE(!guide || (key->first == guide->first && key->stride == guide->stride && key->cursor == guide->cursor), AVD_EINVAL,
-                    "denoise_step_slots_clips: the slot key's first / stride / cursor must equal the clip guide's");
-    }
-    if (int rc = check_clip_queues(queues, guide, s->eta > 0.f, e.B, e.C, e.T, (int64_t)e.H * e.W, z_out, x0_hist)) return rc;
+    if (int rc = check_slot_step("denoise_step_slots_clips", SLOT_QUEUES, s, cfg, key, guide, queues, t_last, x0_hist, z, z_out, workspace,
+                                 workspace_bytes, slots))
+        return rc;
     return denoise_step(s, nullptr, z, Xp, t_now, t_prev, nullptr, z_out, workspace, workspace_bytes, stream, t_last, x0_hist, nullptr,
                         nullptr, 0, 0, slots, nullptr, s->eta > 0.f ? key : nullptr, guide, cfg, queues);
 }

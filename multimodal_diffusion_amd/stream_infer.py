@@ -268,7 +268,9 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     (``functional.canvas_noise``: clip slot c always starts from the same normals, however long the clip), n - 1 ramp steps bring it
     to the diagonal, then every steady iteration is one ``step_slots`` — each slot moves one level — and one ``functional.fifo_shift``:
     the head leaves finished, fresh noise enters at the tail.  Memory is constant in the clip length and a finished slot costs n / S
-    sample-steps, what non-overlapping windows cost; nothing is cross-faded or averaged.
+    sample-steps, what non-overlapping windows cost; nothing is cross-faded or averaged.  Every driver below takes its checked plan from
+    ``DenoiseEngine.fifo_plan`` before anything is allocated or launched: a schedule that does not fit the queue, a clip whose
+    (n + n_slots) * slot_len leaves the stream's 2**32 canvas positions and what ``step_slots`` refuses are ValueErrors raised there.
     ``prompt_canvas`` is the prompt modality's latent along its sliding axis and ``prompt_hop`` its positions per target slot: before
     the step of steady iteration m (the ramp: m = 0) sample k is conditioned on ``fifo_prompt_windows(prompt_canvas, m, ...)[k]``,
     the prompt under the clip slots the sample holds (``set_prompt`` into the same buffer).  The engine's limits are ``step_slots``'s
@@ -339,23 +341,12 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
     and ``set_prompt`` it, and ``graph=True`` launches the same gather off the cursor m (``DenoiseEngine.fifo_open(prompt_den=,
     prompt_interp=)``).  Sample k is then conditioned on ``fifo_prompt_windows(..., prompt_den=, prompt_interp=)[k]``, bit for bit.
     With ``prompt_den`` == 1 every driver is the one above, launch for launch, whatever the mode."""
-    if not isinstance(engine, DenoiseEngine):
-        raise TypeError("fifo_denoise drives a DenoiseEngine")
-    scfg = None
-    if guidance_by_level is not None or rescale_by_level is not None or apg is not None or apg_momentum is not None:
-        scfg = engine._check_slot_cfg(guidance_by_level, rescale_by_level, apg, apg_momentum)
-    if isinstance(n_slots, bool) or not isinstance(n_slots, int) or n_slots < 1:
-        raise ValueError(f"n_slots must be an int >= 1, got {n_slots!r}")
-    if isinstance(prompt_hop, bool) or not isinstance(prompt_hop, int) or prompt_hop < 1:
-        raise ValueError(f"prompt_hop must be an int >= 1 (prompt positions per target slot), got {prompt_hop!r}")
-    Fn.check_prompt_frac(prompt_hop, prompt_den, prompt_interp)
-    frac = (prompt_den, prompt_interp) if prompt_den > 1 else None      # None: today's integer walk
+    scfg, frac = _fifo_scalar_checks("fifo_denoise", engine, n_slots, prompt_hop, prompt_den, prompt_interp, guide_start,
+                                     (guidance_by_level, rescale_by_level, apg, apg_momentum))
     if graph is not None and not isinstance(graph, bool):
         raise TypeError(f"graph must be True, False or None, got {graph!r}")
     if isinstance(lookahead, bool) or not isinstance(lookahead, int) or not 0 <= lookahead < engine.slots:
         raise ValueError(f"lookahead must be an int in [0, S = {engine.slots}): the context slots of a window of S, got {lookahead!r}")
-    if guide_start not in ("noise", "init"):
-        raise ValueError(f"guide_start must be 'noise' or 'init', got {guide_start!r}")
     if init_canvas is None and (mask is not None or guide_start != "noise"):
         raise ValueError("mask and guide_start belong to the clip guide: pass init_canvas")
     if not isinstance(guided_shift, bool) or (guided_shift and init_canvas is None):
@@ -375,33 +366,43 @@ def fifo_denoise(engine: DenoiseEngine, prompt_canvas: torch.Tensor, prompt_hop:
             return _fifo_denoise_lookahead(engine, prompt_canvas, prompt_hop, sched, n_slots, noise_seed, lookahead, context, frac)
     if context is not None:
         raise ValueError("context is the clean latent of the lookahead's context slots: it needs lookahead > 0")
-    B, S, sl = engine.embed.B, engine.slots, engine.slot_len
-    ramp_now, ramp_prev, steady_now, steady_prev = su.fifo_plan(sched, S)
-    n = ramp_now.shape[0] + 1
-    if n != B * S:
-        raise ValueError(f"the schedule has {n} steps, the engine's queue {B} samples x {S} slots = {B * S}: fifo_denoise needs them equal")
-    outer, L_, _ = Fn.window_dims(engine.latent_shape)
-    if L_ != S * sl:
-        raise ValueError(f"the engine's sliding length {L_} is not {S} slots of {sl} positions (an uncovered audio tail cannot queue)")
-    Fn.noise_key(noise_seed, 0)
-    s0 = int(torch.as_tensor(sched).reshape(-1)[0])
-    dev = engine.device
     Lp = fifo_prompt_len(engine, prompt_canvas)
-    pc = L.dev_f32(prompt_canvas.to(dev), "prompt canvas")
     if graph is None:
-        graph = 2 * B * engine.N < engine.GRAPH_BELOW_ROWS
-    if graph:
+        graph = 2 * engine.embed.B * engine.N < engine.GRAPH_BELOW_ROWS
+    if graph:      # fifo_open makes the plan's checks itself
         with _slot_cfg_scope(engine, scfg):
-            return _fifo_denoise_graph(engine, engine.fifo_open(pc, prompt_hop, Lp, sched, n_slots, noise_seed, prompt_den=prompt_den,
-                                                                        prompt_interp=prompt_interp))
+            return _fifo_denoise_graph(engine, engine.fifo_open(prompt_canvas, prompt_hop, Lp, sched, n_slots, noise_seed,
+                                                                prompt_den=prompt_den, prompt_interp=prompt_interp))
+    # under a clip guide, the call's or the engine's own, the steps are keyed by the clip slot at queue slot 0 at any eta
+    keying = _fifo_clip_keying(engine, engine.slots, 0, guided=init_canvas is not None or engine._clip is not None)
+    plan = engine.fifo_plan(sched, n_slots, clip_first=keying[0](0))
+    Fn.noise_key(noise_seed, 0)
+    pc = L.dev_f32(prompt_canvas.to(engine.device), "prompt canvas")
     if init_canvas is not None:
         engine.set_clip_guide(init_canvas, mask, guide_seed=guide_seed)
     try:
         with _slot_cfg_scope(engine, scfg):
-            return _fifo_denoise_eager(engine, pc, prompt_hop, Lp, sched, n_slots, noise_seed, guide_start == "init", guided_shift, frac)
+            return _fifo_denoise_eager(engine, pc, prompt_hop, Lp, plan, keying, n_slots, noise_seed, guide_start == "init", guided_shift,
+                                       frac)
     finally:
         if init_canvas is not None:
             engine.clear_clip_guide()
+
+
+def _fifo_scalar_checks(what: str, engine, n_slots, prompt_hop, prompt_den, prompt_interp, guide_start, slot_cfg):
+    """the argument checks ``fifo_denoise`` and ``fifo_denoise_clips`` share, the slot CFG arguments (``slot_cfg``: guidance, rescale,
+    apg, apg_momentum) first: returns (``_check_slot_cfg``'s result or None, (prompt_den, prompt_interp) or None on a whole hop)"""
+    if not isinstance(engine, DenoiseEngine):
+        raise TypeError(f"{what} drives a DenoiseEngine")
+    scfg = None if all(a is None for a in slot_cfg) else engine._check_slot_cfg(*slot_cfg)
+    if isinstance(n_slots, bool) or not isinstance(n_slots, int) or n_slots < 1:
+        raise ValueError(f"n_slots must be an int >= 1, got {n_slots!r}")
+    if isinstance(prompt_hop, bool) or not isinstance(prompt_hop, int) or prompt_hop < 1:
+        raise ValueError(f"prompt_hop must be an int >= 1 (prompt positions per target slot), got {prompt_hop!r}")
+    Fn.check_prompt_frac(prompt_hop, prompt_den, prompt_interp)
+    if guide_start not in ("noise", "init"):
+        raise ValueError(f"guide_start must be 'noise' or 'init', got {guide_start!r}")
+    return scfg, (prompt_den, prompt_interp) if prompt_den > 1 else None
 
 
 @contextlib.contextmanager
@@ -419,47 +420,62 @@ def _slot_cfg_scope(engine: DenoiseEngine, checked):
             engine.clear_slot_cfg()
 
 
-def _fifo_denoise_eager(engine: DenoiseEngine, pc: torch.Tensor, prompt_hop: int, Lp: int, sched, n_slots: int, noise_seed: int,
-                        everywhere: bool, guided_shift: bool = False, frac=None) -> torch.Tensor:
-    """``fifo_denoise``'s eager loop over the plain queue; under ``engine.set_clip_guide`` the guided one (the contract is in
-    ``fifo_denoise``): the start and every entering tail slot go through ``functional.clip_guide_slots`` at s_0 — with ``guided_shift``
-    the tail slot inside the shift's own launch (``engine.fifo_shift(guided=)``) — and the steps are keyed by the clip slot at queue
-    slot 0 at any eta.  ``frac`` = (prompt_den, prompt_interp) takes the prompt from the fractional gather instead of the slices."""
-    B, S, sl = engine.embed.B, engine.slots, engine.slot_len
-    ramp_now, ramp_prev, steady_now, steady_prev = su.fifo_plan(sched, S)
-    n = ramp_now.shape[0] + 1
-    outer, L_, _ = Fn.window_dims(engine.latent_shape)
-    s0 = int(torch.as_tensor(sched).reshape(-1)[0])
-    dev = engine.device
-    tabs = [t.to(dev) for t in (ramp_now, ramp_prev, steady_now, steady_prev)]
-    multistep = engine.solver == "dpmpp_2m"
-    ramp_last, steady_last = (t.to(dev) for t in su.fifo_plan_last(sched, S)) if multistep else (None, None)
-    z = Fn.canvas_noise(noise_seed, torch.full((B,), s0, dtype=torch.long, device=dev), engine.latent_shape, L_)
+def _fifo_queue_loop(engine: DenoiseEngine, z: torch.Tensor, plan, tabs, n_slots: int, windows, first, step_kw: dict, ramp_move,
+                     steady_move) -> None:
+    """The loop every eager FIFO driver runs on a queue ``z`` whose prompt of m = 0 is set: n - 1 ramp iterations of ``step_slots`` on
+    row r of the ramp tables and ``ramp_move``, then per finished slot m ``set_prompt(windows(m))`` (m > 0), ``step_slots`` on the
+    plan's steady tables of m, and ``steady_move``.  The driver supplies what differs:
+    ``tabs`` = (ramp, steady), the plan's tables where and how the driver laid them out; ``windows``: m -> the prompt batch; ``first``:
+    m -> ``clip_first`` and ``step_kw`` the other keywords of every ``step_slots``; ``ramp_move(new, old)`` -> (the queue after a ramp
+    step, the buffer the next step writes); ``steady_move(new, m)`` -> the queue after the move, which also puts the finished head
+    where it belongs and runs the driver's pass over the entering tail, if it has one."""
+    ramp, steady = tabs
     other = torch.empty_like(z)
-    windows = _fifo_prompt_source(pc, B, S, prompt_hop, Lp, S, 0, frac)
-    engine.set_prompt(windows(0))
-    first, stride = _fifo_clip_keying(engine, S, 0)
-    clip = engine._clip
-    if clip is not None:      # the guide reads clip positions at any eta: slot 0 of sample 0 holds clip slot m
-        first, stride = (lambda m: m), S
-        ab = engine.alpha_bar.to(dev, torch.float32)
-        guide = dict(slot_len=sl, seed=clip[2], everywhere=everywhere)
-        tail = torch.full((B, S), Fn.SLOT_LEAVE, dtype=torch.long, device=dev)
-        tail[B - 1, S - 1] = s0
-        Fn.clip_guide_slots(clip[0], torch.full((B, S), s0, dtype=torch.long, device=dev), ab, z, clip[1], first=0, out=z, **guide)
-    guided = None if clip is None or not guided_shift else ("everywhere" if everywhere else "mask")
-    for r in range(n - 1):
-        z, other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other, t_last=ramp_last[r] if multistep else None, clip_first=first(0),
-                                     clip_stride=stride), z
-    canvas = torch.empty((outer, n_slots * sl) + tuple(engine.latent_shape[3:]), device=dev, dtype=torch.float32)
+    for r in range(plan.n - 1):
+        other = engine.step_slots(z, ramp[0][r], ramp[1][r], out=other, t_last=ramp[2][r] if len(ramp) == 3 else None,
+                                  clip_first=first(0), **step_kw)
+        z, other = ramp_move(other, z)
     for m in range(n_slots):
         if m:
             engine.set_prompt(windows(m))
-        other = engine.step_slots(z, tabs[2], tabs[3], out=other, t_last=steady_last, clip_first=first(m), clip_stride=stride)
-        z, popped = engine.fifo_shift(other, n + m, s0, seed=noise_seed, guided=guided)      # guided: clip slot n + m enters at q(s_0)
-        if clip is not None and guided is None:      # the entering tail slot alone: clip slot n + m, now that clip slot m + 1 is at queue slot 0
-            Fn.clip_guide_slots(clip[0], tail, ab, z, clip[1], first=m + 1, out=z, **guide)
+        now, prev, *last = plan.steady_tables(steady, m)
+        other = engine.step_slots(z, now, prev, out=other, t_last=last[0] if last else None, clip_first=first(m), **step_kw)
+        z = steady_move(other, m)
+
+
+def _fifo_denoise_eager(engine: DenoiseEngine, pc: torch.Tensor, prompt_hop: int, Lp: int, plan, keying, n_slots: int, noise_seed: int,
+                        everywhere: bool, guided_shift: bool = False, frac=None) -> torch.Tensor:
+    """``fifo_denoise``'s plain queue for ``_fifo_queue_loop``; under ``engine.set_clip_guide`` the guided one (the contract is in
+    ``fifo_denoise``): the start and every entering tail slot go through ``functional.clip_guide_slots`` at s_0 — with ``guided_shift``
+    the tail slot inside the shift's own launch (``engine.fifo_shift(guided=)``).  ``keying``: ``_fifo_clip_keying``'s result, which
+    the plan was checked with; ``frac`` = (prompt_den, prompt_interp) takes the prompt from the fractional gather, not the slices."""
+    B, S, sl = engine.embed.B, engine.slots, engine.slot_len
+    n, s0, dev = plan.n, plan.s0, engine.device
+    z = Fn.canvas_noise(noise_seed, torch.full((B,), s0, dtype=torch.long, device=dev), engine.latent_shape, plan.L)
+    windows = _fifo_prompt_source(pc, B, S, prompt_hop, Lp, S, 0, frac)
+    engine.set_prompt(windows(0))
+    clip, guided, tail_pass = engine._clip, None, None
+    if clip is not None:
+        ab = engine.alpha_bar.to(dev, torch.float32)
+        guide = dict(slot_len=sl, seed=clip[2], everywhere=everywhere)
+        Fn.clip_guide_slots(clip[0], torch.full((B, S), s0, dtype=torch.long, device=dev), ab, z, clip[1], first=0, out=z, **guide)
+        if guided_shift:      # clip slot n + m enters at q(s_0) inside the shift
+            guided = "everywhere" if everywhere else "mask"
+        else:      # the entering tail slot alone: clip slot n + m, now that clip slot m + 1 is at queue slot 0
+            tail = torch.full((B, S), Fn.SLOT_LEAVE, dtype=torch.long, device=dev)
+            tail[B - 1, S - 1] = s0
+            tail_pass = (lambda z, m: Fn.clip_guide_slots(clip[0], tail, ab, z, clip[1], first=m + 1, out=z, **guide))
+    canvas = torch.empty((plan.outer, n_slots * sl) + plan.trailing, device=dev, dtype=torch.float32)
+
+    def shift(new, m):
+        z, popped = engine.fifo_shift(new, n + m, s0, seed=noise_seed, guided=guided)
+        if tail_pass is not None:
+            tail_pass(z, m)
         canvas[:, m * sl:(m + 1) * sl] = popped
+        return z
+
+    _fifo_queue_loop(engine, z, plan, ([t.to(dev) for t in plan.ramp], [t.to(dev) for t in plan.steady]), n_slots, windows, keying[0],
+                     dict(clip_stride=keying[1]), lambda new, old: (new, old), shift)
     return canvas
 
 
@@ -501,17 +517,8 @@ def fifo_denoise_clips(engine: DenoiseEngine, prompt_canvases, prompt_hop: int, 
     guides of its own (``set_clip_guide`` is one canvas, one queue; pass ``init_canvases``), K = 0, canvases of differing shapes, a
     seed or canvas count other than K.  The replayed queue, the lookahead queue and a context are ``fifo_denoise``'s alone; the clips
     run in lockstep and so share ``n_slots``."""
-    if not isinstance(engine, DenoiseEngine):
-        raise TypeError("fifo_denoise_clips drives a DenoiseEngine")
-    scfg = None
-    if guidance_by_level is not None or rescale_by_level is not None or apg is not None or apg_momentum is not None:
-        scfg = engine._check_slot_cfg(guidance_by_level, rescale_by_level, apg, apg_momentum)
-    if isinstance(n_slots, bool) or not isinstance(n_slots, int) or n_slots < 1:
-        raise ValueError(f"n_slots must be an int >= 1, got {n_slots!r}")
-    if isinstance(prompt_hop, bool) or not isinstance(prompt_hop, int) or prompt_hop < 1:
-        raise ValueError(f"prompt_hop must be an int >= 1 (prompt positions per target slot), got {prompt_hop!r}")
-    Fn.check_prompt_frac(prompt_hop, prompt_den, prompt_interp)
-    frac = (prompt_den, prompt_interp) if prompt_den > 1 else None
+    scfg, frac = _fifo_scalar_checks("fifo_denoise_clips", engine, n_slots, prompt_hop, prompt_den, prompt_interp, guide_start,
+                                     (guidance_by_level, rescale_by_level, apg, apg_momentum))
     pcs = list(prompt_canvases.unbind(0)) if isinstance(prompt_canvases, torch.Tensor) else list(prompt_canvases)
     K = len(pcs)
     if K == 0:
@@ -529,8 +536,6 @@ def fifo_denoise_clips(engine: DenoiseEngine, prompt_canvases, prompt_hop: int, 
     engine._clip_refusal("fifo_denoise_clips", "a clip guide is one canvas walked by one queue, and a clip batch holds several")
     if engine._clips is not None:
         raise ValueError("fifo_denoise_clips sets the engine's clip guides for the call: clear_clip_guides() first and pass init_canvases")
-    if guide_start not in ("noise", "init"):
-        raise ValueError(f"guide_start must be 'noise' or 'init', got {guide_start!r}")
     if init_canvases is None and (masks is not None or guide_seeds is not None or guide_start != "noise"):
         raise ValueError("masks, guide_seeds and guide_start belong to the clip guides: pass init_canvases")
     if init_canvases is not None:
@@ -541,42 +546,29 @@ def fifo_denoise_clips(engine: DenoiseEngine, prompt_canvases, prompt_hop: int, 
             raise ValueError(f"{len(masks)} masks for {K} clips: fifo_denoise_clips needs one mask per clip, or None")
         guide_seeds = Fn.clip_seeds([0] * K if guide_seeds is None else guide_seeds, K)
     B, S, sl = engine.embed.B, engine.slots, engine.slot_len
-    n = su.fifo_plan(sched, 1)[0].shape[0] + 1      # the schedule's own refusals, and its steps
-    if B % K or (B // K) * S != n:
-        raise ValueError(f"K = {K} clips in an engine of batch B = {B} with S = {S} slots per sample against a schedule of n = {n} "
-                         "steps: fifo_denoise_clips needs B = K * B_q and B_q * S = n")
-    Bq = B // K
-    outer, L_, _ = Fn.window_dims(engine.latent_shape)
-    if L_ != S * sl:
-        raise ValueError(f"the engine's sliding length {L_} is not {S} slots of {sl} positions (an uncovered audio tail cannot queue)")
-    if (n + n_slots) * sl > 2 ** 32:
-        raise ValueError(f"(n {n} + n_slots {n_slots}) * slot_len {sl} exceeds the stream's 2**32 canvas positions")
-    dev = engine.device
-    multistep = engine.solver == "dpmpp_2m"
     keyed, guided = engine.eta > 0, init_canvases is not None
     off, stride = su.fifo_slot_keying(S, 0)
     # the clip slot at slot 0 of sample 0 of every queue before the step of steady iteration m: read by the step noise and by the guides
     first = (lambda m: m + off) if keyed or guided else (lambda m: None)
-    engine._slot_refusals(multistep, first(0), seeded=keyed, guided=guided)
+    plan = engine.fifo_plan(sched, n_slots, queues=K, clip_first=first(0), seeded=keyed, guided=guided)
+    n, s0, Bq, dev = plan.n, plan.s0, B // K, engine.device
     Lp = fifo_prompt_len(engine, pcs[0])
     pcs = [L.dev_f32(p.to(dev), "prompt canvas") for p in pcs]
-    s0 = int(torch.as_tensor(sched).reshape(-1)[0])
     tile = (lambda t: t.repeat((1,) * (t.dim() - 2) + (K, 1)).to(dev))      # one queue's [.., B_q, S] rows, K times along the batch
-    tabs = [tile(t) for t in su.fifo_plan(sched, S)]
-    ramp_last, steady_last = (tile(t) for t in su.fifo_plan_last(sched, S)) if multistep else (None, None)
     seeds_dev = seeds.to(dev)
     t0 = torch.full((Bq,), s0, dtype=torch.long, device=dev)
-    z = torch.cat([Fn.canvas_noise(s, t0, (Bq,) + tuple(engine.latent_shape[1:]), L_) for s in noise_seeds], 0)
-    other = torch.empty_like(z)
+    z = torch.cat([Fn.canvas_noise(s, t0, (Bq,) + tuple(engine.latent_shape[1:]), plan.L) for s in noise_seeds], 0)
     sources = [_fifo_prompt_source(p, Bq, S, prompt_hop, Lp, S, 0, frac) for p in pcs]
     windows = (lambda m: torch.cat([w(m) for w in sources], 0))
-    canvases = torch.empty((K, outer, n_slots * sl) + tuple(engine.latent_shape[3:]), device=dev, dtype=torch.float32)
+    canvases = torch.empty((K, plan.outer, n_slots * sl) + plan.trailing, device=dev, dtype=torch.float32)
     # the plain deterministic batch steps as it always has; per-clip keys or guides ride on step_slots(clip_queues=K)
     kw = dict(clip_stride=stride, clip_queues=K, clip_seeds=step_seeds.to(dev) if keyed else None) if keyed or guided else {}
     if guided:
         engine.set_clip_guides(init_canvases, masks, guide_seeds=guide_seeds)
     try:
         with _slot_cfg_scope(engine, scfg):
+            engine.set_prompt(windows(0))
+            tail_pass = None
             if guided:      # the start, and after every shift the K entering tails, on their forward paths at s_0
                 known, gmask, gseeds = engine._clips
                 ab = engine.alpha_bar.to(dev, torch.float32)
@@ -584,17 +576,17 @@ def fifo_denoise_clips(engine: DenoiseEngine, prompt_canvases, prompt_hop: int, 
                 tails = torch.full((B, S), Fn.SLOT_LEAVE, dtype=torch.long, device=dev)
                 tails[Bq - 1::Bq, S - 1] = s0
                 Fn.clip_guide_slots_clips(known, torch.full((B, S), s0, dtype=torch.long, device=dev), ab, z, gmask, first=0, out=z, **guide)
-            engine.set_prompt(windows(0))
-            for r in range(n - 1):
-                z, other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other, t_last=ramp_last[r] if multistep else None,
-                                             clip_first=first(0), **kw), z
-            for m in range(n_slots):
-                if m:
-                    engine.set_prompt(windows(m))
-                other = engine.step_slots(z, tabs[2], tabs[3], out=other, t_last=steady_last, clip_first=first(m), **kw)
-                z = engine.fifo_shift_clips(other, K, n + m, s0, seeds_dev, canvases, m)
-                if guided:      # clip slot n + m entered every queue, now that clip slot m + 1 is at its slot 0
-                    Fn.clip_guide_slots_clips(known, tails, ab, z, gmask, first=m + 1, out=z, **guide)
+                # clip slot n + m entered every queue, now that clip slot m + 1 is at its slot 0
+                tail_pass = (lambda z, m: Fn.clip_guide_slots_clips(known, tails, ab, z, gmask, first=m + 1, out=z, **guide))
+
+            def shift(new, m):
+                z = engine.fifo_shift_clips(new, K, n + m, s0, seeds_dev, canvases, m)
+                if tail_pass is not None:
+                    tail_pass(z, m)
+                return z
+
+            _fifo_queue_loop(engine, z, plan, ([tile(t) for t in plan.ramp], [tile(t) for t in plan.steady]), n_slots, windows, first, kw,
+                             lambda new, old: (new, old), shift)
     finally:
         if guided:
             engine.clear_clip_guides()
@@ -610,12 +602,13 @@ def _fifo_prompt_source(pc: torch.Tensor, B: int, S: int, prompt_hop: int, Lp: i
     return lambda m: Fn.fifo_prompt_gather_frac(pc, None, B, m - ctx, stride, prompt_hop, frac[0], frac[1], Lp)
 
 
-def _fifo_clip_keying(engine: DenoiseEngine, S: int, ctx: int):
-    """(first, stride) of the eager drivers' ``step_slots`` calls: on an eta > 0 engine with a noise_seed ``first(m)`` is the clip slot
-    at slot 0 of sample 0 before the step of steady iteration m (``schedule_utils.fifo_slot_keying``); otherwise it is None, which an
-    eta == 0 engine ignores and with which an unseeded eta > 0 engine is refused by ``step_slots``"""
+def _fifo_clip_keying(engine: DenoiseEngine, S: int, ctx: int, guided: bool = False):
+    """(first, stride) of the eager drivers' ``step_slots`` calls: on an eta > 0 engine with a noise_seed, and at any eta on a
+    ``guided`` queue (the clip guide reads clip positions), ``first(m)`` is the clip slot at slot 0 of sample 0 before the step of
+    steady iteration m (``schedule_utils.fifo_slot_keying``); otherwise it is None, which an eta == 0 engine ignores and with which an
+    unseeded eta > 0 engine is refused by ``step_slots``"""
     off, stride = su.fifo_slot_keying(S, ctx)
-    if engine.eta > 0 and engine.noise_seed is not None:
+    if guided or (engine.eta > 0 and engine.noise_seed is not None):
         return (lambda m: m + off), stride
     return (lambda m: None), None
 
@@ -625,30 +618,15 @@ def _fifo_denoise_lookahead(engine: DenoiseEngine, prompt_canvas, prompt_hop: in
     """``fifo_denoise(lookahead=ctx > 0)``: the eager loop over overlapping windows (the contract is in ``fifo_denoise``)"""
     B, S, sl = engine.embed.B, engine.slots, engine.slot_len
     h = S - ctx
-    ramp_now, ramp_prev, steady_now, steady_prev = su.fifo_lookahead_plan(sched, S, ctx, "noise" if context is None else "clean")
-    n = ramp_now.shape[0] + 1
-    if n != B * h:
-        raise ValueError(f"the schedule has {n} steps, the engine's queue {B} windows x {h} stepping slots = {B * h}: fifo_denoise needs "
-                         "them equal")
-    outer, L_, _ = Fn.window_dims(engine.latent_shape)
-    if L_ != S * sl:
-        raise ValueError(f"the engine's sliding length {L_} is not {S} slots of {sl} positions (an uncovered audio tail cannot queue)")
+    first, stride = _fifo_clip_keying(engine, S, ctx)
+    plan = engine.fifo_plan(sched, n_slots, ctx, context="noise" if context is None else "clean", clip_first=first(0))
+    n, s0, outer, hw, dev = plan.n, plan.s0, plan.outer, plan.trailing, engine.device
     Fn.noise_key(noise_seed, 0)
-    if (n + n_slots) * sl > 2 ** 32 - ctx * sl:
-        raise ValueError(f"(n {n} + n_slots {n_slots} + ctx {ctx}) * slot_len {sl} exceeds the stream's 2**32 canvas positions")
-    hw = tuple(engine.latent_shape[3:])
     if context is not None and not (isinstance(context, torch.Tensor) and tuple(context.shape) == (outer, ctx * sl) + hw):
         raise ValueError(f"context must be the clean latent of the {ctx} slots before the clip, shape {(outer, ctx * sl) + hw}, got "
                          f"{tuple(context.shape) if isinstance(context, torch.Tensor) else context!r}")
-    multistep = engine.solver == "dpmpp_2m"
-    first, stride = _fifo_clip_keying(engine, S, ctx)
-    engine._slot_refusals(multistep, first(0))
-    s0 = int(torch.as_tensor(sched).reshape(-1)[0])
-    dev = engine.device
     Lp = fifo_prompt_len(engine, prompt_canvas)
     pc = L.dev_f32(prompt_canvas.to(dev), "prompt canvas")
-    tabs = [t.to(dev) for t in (ramp_now, ramp_prev, steady_now, steady_prev)]
-    ramp_last, steady_last = ((t.to(dev) for t in su.fifo_lookahead_plan_last(sched, S, ctx)) if multistep else (None, None))
     # the logical queue [outer, (ctx + n) * sl, ...]: the context, then clip slots 0 .. n - 1 keyed by their canvas positions
     t0 = torch.full((1,), s0, dtype=torch.long, device=dev)
     if context is None:
@@ -656,51 +634,42 @@ def _fifo_denoise_lookahead(engine: DenoiseEngine, prompt_canvas, prompt_hop: in
     else:
         head = L.dev_f32(context.to(dev), "context")
     queue = torch.cat([head, Fn.canvas_noise(noise_seed, t0, (1, outer, n * sl) + hw, n * sl)[0]], 1)
-    z = windows_from_canvas(queue, L_, h * sl)
-    other = torch.empty_like(z)
+    z = windows_from_canvas(queue, plan.L, h * sl)
     windows = _fifo_prompt_source(pc, B, S, prompt_hop, Lp, h, ctx, frac)
     engine.set_prompt(windows(0))
-    for r in range(n - 1):
-        other = engine.step_slots(z, tabs[0][r], tabs[1][r], out=other, t_last=ramp_last[r] if multistep else None, clip_first=first(0),
-                                  clip_stride=stride)
-        z, _ = engine.fifo_lookahead(other, ctx, 0)
     canvas = torch.empty((outer, n_slots * sl) + hw, device=dev, dtype=torch.float32)
-    for m in range(n_slots):
-        if m:
-            engine.set_prompt(windows(m))
-        row = min(m, ctx)
-        other = engine.step_slots(z, tabs[2][row], tabs[3][row], out=other, t_last=steady_last[row] if multistep else None,
-                                  clip_first=first(m), clip_stride=stride)
-        z, popped = engine.fifo_lookahead(other, ctx, 1, c=n + m, t=s0, seed=noise_seed)
-        canvas[:, m * sl:(m + 1) * sl] = popped
+
+    def shift(new, m):      # the popped head goes into the clip
+        z, canvas[:, m * sl:(m + 1) * sl] = engine.fifo_lookahead(new, ctx, 1, c=n + m, t=s0, seed=noise_seed)
+        return z
+
+    # a ramp step ends in the refresh of the duplicates, out of place: the stepped buffer is the next step's to write
+    _fifo_queue_loop(engine, z, plan, ([t.to(dev) for t in plan.ramp], [t.to(dev) for t in plan.steady]), n_slots, windows, first,
+                     dict(clip_stride=stride), lambda new, old: (engine.fifo_lookahead(new, ctx, 0)[0], new), shift)
     return canvas
 
 
 def _fifo_denoise_graph(engine: DenoiseEngine, q) -> torch.Tensor:
     """``fifo_denoise``'s loop on an open queue (``DenoiseEngine.fifo_open``): per phase one eager iteration, captured pairs while
     two or more iterations are left, an odd last one eagerly — all through the cursor kernels, so the cursors count every iteration."""
-    z, other = q.z, q.other
-    left = q.n - 1
-    if left:
-        engine.fifo_ramp(q, z, other)
-        z, other, left = other, z, left - 1
-    if left >= 2:
-        pair = engine.fifo_capture(q, False, z, other)
-        for _ in range(left // 2):
-            pair.replay()
-        left %= 2
-    if left:
-        engine.fifo_ramp(q, z, other)
-        z, other = other, z
-    engine.fifo_steady(q, z, other)
-    left = q.n_slots - 1
-    if left >= 2:
-        pair = engine.fifo_capture(q, True, z, other)
-        for _ in range(left // 2):
-            pair.replay()
-        left %= 2
-    if left:
-        engine.fifo_steady(q, z, other)
+    def phase(steady: bool, left: int, z, other):
+        """``left`` iterations of one phase on (z, other); returns the pair with the latent first.  A ramp iteration steps z -> other,
+        so the two swap; a steady one leaves the latent in z, and a replayed pair puts it back where it was either way."""
+        def eager(z, other):
+            (engine.fifo_steady if steady else engine.fifo_ramp)(q, z, other)
+            return (z, other) if steady else (other, z)
+
+        if left:      # every kernel of the phase runs once before it is captured
+            z, other, left = *eager(z, other), left - 1
+        if left >= 2:
+            pair = engine.fifo_capture(q, steady, z, other)
+            for _ in range(left // 2):
+                pair.replay()
+            left %= 2
+        return eager(z, other) if left else (z, other)
+
+    z, other = phase(False, q.n - 1, q.z, q.other)
+    phase(True, q.n_slots, z, other)
     return q.clip
 
 
@@ -934,14 +903,49 @@ def _fifo_slot_controls(pc, opts: dict, T_train: int) -> dict:
     return ctl
 
 
+def _one_canvas(windows: torch.Tensor, hop: int) -> torch.Tensor:
+    """windows encoded alone disagree on their overlaps: one uniform consensus pass, then the canvas"""
+    return canvas_from_windows(Fn.window_consensus(windows, hop), hop)
+
+
+def _fifo_prompt_canvas(pc, mods: Dict, device, prompt_modality: str, chunks: np.ndarray, geo: FifoGeometry):
+    """(the prompt canvas of one clip's chunks, its prompt token count): the encoder's own output decides the count, as in the windows
+    sampler"""
+    z_p = _encode_windows(prompt_modality, mods["vid_vae"], mods["aud_codec"], chunks, device)
+    n_prompt = P.prompt_tokens(pc, tuple(z_p.shape))
+    if z_p.shape[2] != geo.L_p:
+        raise ValueError(f"encoded prompt windows have {z_p.shape[2]} latent positions, the config implies {geo.L_p}: the prompt "
+                         "canvas cannot be laid out")
+    return _one_canvas(z_p.float().contiguous(), geo.hop_p), n_prompt
+
+
+def _fifo_engine(pc, mods: Dict, geo: FifoGeometry, lat, n_prompt: int, noise_seed) -> DenoiseEngine:
+    """the engine of a queue geometry.  The per-sample CFG controls stay off it: a queue sample holds S noise levels, and
+    ``_fifo_slot_controls`` gives their slot form"""
+    return P.build_engine(pc._replace(rescale=0.0, interval=None, apg=None), adapt_v=mods["adapt_v"], adapt_a=mods["adapt_a"],
+                          core=mods["core"], head=mods["head"], tstep_dim=mods["tstep_dim"],
+                          latent_shape=(geo.B, lat[0], geo.S * geo.slot_len) + tuple(lat[2:]), n_prompt=n_prompt, noise_seed=noise_seed)
+
+
+def _fifo_result(cfg: Dict, pc, mods: Dict, device, lat, geo: FifoGeometry, canvas: torch.Tensor, return_latents: bool,
+                 max_windows_per_batch: int) -> Dict:
+    """the result dict of one finished latent canvas: its windows decoded in batches and cross-faded as the windows sampler's are"""
+    windows = windows_from_canvas(canvas, geo.L_t, geo.hop_t)
+    out = torch.cat([_decode_windows(cfg, pc, mods["vid_vae"], mods["aud_codec"], lat, windows[lo:lo + max_windows_per_batch], device)
+                     for lo in range(0, windows.shape[0], max_windows_per_batch)], 0)
+    res = _stitch(cfg, pc, out)
+    if return_latents:
+        res["latents"], res["latent_canvas"] = windows.cpu().numpy(), canvas.cpu().numpy()
+    return res
+
+
 def _stream_generate_fifo(cfg: Dict, pc, mods: Dict, device, prompt_modality: str, chunks: np.ndarray, zp_shape, lat, init_chunks,
                           mask, strength: float, opts: dict, *, seed, noise_seed, guide_seed, return_latents: bool,
                           max_windows_per_batch: int) -> Dict:
     """``stream_generate(sampler="fifo")`` after the common checks and splits (the contract is in ``stream_generate``): the prompt
     windows become one prompt canvas, ``fifo_denoise`` generates the target canvas, and its windows are decoded and cross-faded as the
     windows sampler's are."""
-    vid_vae, aud_codec = mods["vid_vae"], mods["aud_codec"]
-    target, Nw, T_train = pc.target, zp_shape[0], int(pc.alpha_bar.numel())
+    Nw, T_train = zp_shape[0], int(pc.alpha_bar.numel())
     whole = su.make_sampling_schedule(T_train, opts["steps"]) if opts["steps"] is not None else pc.sched
     sched = su.truncate_schedule(whole, strength) if init_chunks is not None and strength < 1.0 else whole
     n = int(sched.numel()) - 1
@@ -952,27 +956,14 @@ def _stream_generate_fifo(cfg: Dict, pc, mods: Dict, device, prompt_modality: st
                          f"streaming.window_seconds has {geo.L_t}: they must be equal")
     ctl = _fifo_slot_controls(pc, opts, T_train)
     mc = None if mask is None else _canvas_mask(mask, lat, Nw, geo.hop_t, geo.L_t)
-
-    def one_canvas(windows: torch.Tensor, hop: int) -> torch.Tensor:
-        """windows encoded alone disagree on their overlaps: one uniform consensus pass, then the canvas"""
-        return canvas_from_windows(Fn.window_consensus(windows, hop), hop)
-
     init_canvas = None
     if init_chunks is not None:
-        init_canvas = one_canvas(_encode_init(target, vid_vae, aud_codec, init_chunks, device, (Nw, *lat)), geo.hop_t)
+        init_canvas = _one_canvas(_encode_init(pc.target, mods["vid_vae"], mods["aud_codec"], init_chunks, device, (Nw, *lat)), geo.hop_t)
     if n == 0:                                     # strength 0: no steps, the known canvas
         canvas = init_canvas
     else:
-        z_p = _encode_windows(prompt_modality, vid_vae, aud_codec, chunks, device)
-        n_prompt = P.prompt_tokens(pc, tuple(z_p.shape))      # the encoder's own output decides, as in the windows sampler
-        if z_p.shape[2] != geo.L_p:
-            raise ValueError(f"encoded prompt windows have {z_p.shape[2]} latent positions, the config implies {geo.L_p}: the prompt "
-                             "canvas cannot be laid out")
-        prompt_canvas = one_canvas(z_p.float().contiguous(), geo.hop_p)
-        # the per-sample CFG controls stay off the engine: a queue sample holds S noise levels, ``ctl`` is their slot form
-        eng = P.build_engine(pc._replace(rescale=0.0, interval=None, apg=None), adapt_v=mods["adapt_v"], adapt_a=mods["adapt_a"],
-                             core=mods["core"], head=mods["head"], tstep_dim=mods["tstep_dim"],
-                             latent_shape=(geo.B, lat[0], geo.S * geo.slot_len) + tuple(lat[2:]), n_prompt=n_prompt, noise_seed=noise_seed)
+        prompt_canvas, n_prompt = _fifo_prompt_canvas(pc, mods, device, prompt_modality, chunks, geo)
+        eng = _fifo_engine(pc, mods, geo, lat, n_prompt, noise_seed)
         if seed is None:                           # once, from torch's global CPU generator: torch.manual_seed governs it
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         guide = {}
@@ -984,13 +975,7 @@ def _stream_generate_fifo(cfg: Dict, pc, mods: Dict, device, prompt_modality: st
         canvas = fifo_denoise(eng, prompt_canvas, geo.prompt_hop, sched, geo.n_slots, int(seed), graph=opts["graph"],
                               lookahead=opts["lookahead"], prompt_den=geo.prompt_den, prompt_interp=opts["prompt_interp"], **guide,
                               **ctl)[:, :geo.P].contiguous()
-    windows = windows_from_canvas(canvas, geo.L_t, geo.hop_t)
-    out = torch.cat([_decode_windows(cfg, pc, vid_vae, aud_codec, lat, windows[lo:lo + max_windows_per_batch], device)
-                     for lo in range(0, Nw, max_windows_per_batch)], 0)
-    res = _stitch(cfg, pc, out)
-    if return_latents:
-        res["latents"], res["latent_canvas"] = windows.cpu().numpy(), canvas.cpu().numpy()
-    return res
+    return _fifo_result(cfg, pc, mods, device, lat, geo, canvas, return_latents, max_windows_per_batch)
 
 
 def _fifo_clips_refusals(cfg: Dict, opts: dict, K: int, has_init: bool, has_mask: bool, noise_seed=None) -> None:
@@ -1022,7 +1007,6 @@ def _stream_generate_fifo_clips(cfg: Dict, pc, mods: Dict, device, prompt_modali
     """``stream_generate(sampler="fifo")`` with a list of K prompt clips (the contract is in ``stream_generate``): every clip is split,
     encoded and made a prompt canvas as a single clip is, one engine of batch K * B runs ``fifo_denoise_clips``, and every canvas is
     decoded and cross-faded as a single clip's is.  Returns the K result dicts."""
-    vid_vae, aud_codec = mods["vid_vae"], mods["aud_codec"]
     K, T_train = len(clips), int(pc.alpha_bar.numel())
     shapes = [tuple(np.shape(c)) for c in clips]
     if any(s != shapes[0] for s in shapes):
@@ -1048,34 +1032,14 @@ def _stream_generate_fifo_clips(cfg: Dict, pc, mods: Dict, device, prompt_modali
         raise ValueError(f"the target latent has {lat[1]} positions along its sliding axis (data.clip_seconds), a window of "
                          f"streaming.window_seconds has {geo.L_t}: they must be equal")
     ctl = _fifo_slot_controls(pc, opts, T_train)
-    prompt_canvases, n_prompt = [], None
-    for chunks, _, _ in split:
-        z_p = _encode_windows(prompt_modality, vid_vae, aud_codec, chunks, device)
-        n_prompt = P.prompt_tokens(pc, tuple(z_p.shape))
-        if z_p.shape[2] != geo.L_p:
-            raise ValueError(f"encoded prompt windows have {z_p.shape[2]} latent positions, the config implies {geo.L_p}: the prompt "
-                             "canvas cannot be laid out")
-        z_p = z_p.float().contiguous()
-        prompt_canvases.append(canvas_from_windows(Fn.window_consensus(z_p, geo.hop_p), geo.hop_p))
-    eng = P.build_engine(pc._replace(rescale=0.0, interval=None, apg=None), adapt_v=mods["adapt_v"], adapt_a=mods["adapt_a"],
-                         core=mods["core"], head=mods["head"], tstep_dim=mods["tstep_dim"],
-                         latent_shape=(geo.B, lat[0], geo.S * geo.slot_len) + tuple(lat[2:]), n_prompt=n_prompt,
-                         noise_seed=noise_seed[0] if isinstance(noise_seed, (list, tuple)) else noise_seed)
+    prompts = [_fifo_prompt_canvas(pc, mods, device, prompt_modality, chunks, geo) for chunks, _, _ in split]
     # a noise_seed list is the K clips' step seeds: the engine's own seed (which the SDE solver asks for at construction) is not read
-    canvases = fifo_denoise_clips(eng, prompt_canvases, geo.prompt_hop, sched, geo.n_slots, seeds, prompt_den=geo.prompt_den,
-                                  prompt_interp=opts["prompt_interp"], step_seeds=list(noise_seed) if isinstance(noise_seed, (list, tuple)) else None,
-                                  **ctl)
-    results = []
-    for k in range(K):
-        canvas = canvases[k, :, :geo.P].contiguous()
-        windows = windows_from_canvas(canvas, geo.L_t, geo.hop_t)
-        out = torch.cat([_decode_windows(cfg, pc, vid_vae, aud_codec, lat, windows[lo:lo + max_windows_per_batch], device)
-                         for lo in range(0, Nw, max_windows_per_batch)], 0)
-        res = _stitch(cfg, pc, out)
-        if return_latents:
-            res["latents"], res["latent_canvas"] = windows.cpu().numpy(), canvas.cpu().numpy()
-        results.append(res)
-    return results
+    step_seeds = list(noise_seed) if isinstance(noise_seed, (list, tuple)) else None
+    eng = _fifo_engine(pc, mods, geo, lat, prompts[-1][1], noise_seed if step_seeds is None else step_seeds[0])
+    canvases = fifo_denoise_clips(eng, [c for c, _ in prompts], geo.prompt_hop, sched, geo.n_slots, seeds, prompt_den=geo.prompt_den,
+                                  prompt_interp=opts["prompt_interp"], step_seeds=step_seeds, **ctl)
+    return [_fifo_result(cfg, pc, mods, device, lat, geo, canvases[k, :, :geo.P].contiguous(), return_latents, max_windows_per_batch)
+            for k in range(K)]
 
 
 @torch.no_grad()

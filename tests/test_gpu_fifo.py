@@ -119,3 +119,39 @@ def test_fifo_denoise_refuses_a_mismatched_queue(dev, model):
         A.fifo_denoise(eng, canvas_p, hop, torch.tensor([999, 749, 499, 249, -1]), 0, SEED)
     with pytest.raises(ValueError, match="audio prompt canvas"):
         A.fifo_denoise(eng, torch.zeros(8, 14, 8, 8, device=dev), hop, torch.tensor([999, 749, 499, 249, -1]), 1, SEED)
+
+
+@pytest.mark.parametrize("target", ["video", "audio"])
+def test_every_driver_refuses_a_bad_queue_before_anything_runs(dev, model, target, monkeypatch):
+    """the argument and geometry faults every driver checks — eager, graph=True, lookahead=1 and the clip batch of K = 2 — are
+    ValueErrors raised before the first set_prompt or step_slots, and leave no control or guide on the engine"""
+    import re
+    import multimodal_diffusion_amd as A
+    sched = torch.tensor([999, 749, 499, 249, -1])
+    eng2, canvas_p, hop = _setup(dev, model[1], target)                                   # B = 2: n = B * S = 4
+    eng4 = engine(model[1], target, (4,) + tuple(eng2.latent_shape[1:]), eng2.embed.Np, guidance=GS)      # lookahead 1: n = B * (S - 1);
+    sl = eng2.slot_len                                                                    # clips: n = (B / 2) * S
+    drivers = {"eager": (eng2, lambda e, hop, sched, K, **kw: A.fifo_denoise(e, canvas_p, hop, sched, K, SEED, graph=False, **kw)),
+               "graph": (eng2, lambda e, hop, sched, K, **kw: A.fifo_denoise(e, canvas_p, hop, sched, K, SEED, graph=True, **kw)),
+               "lookahead": (eng4, lambda e, hop, sched, K, **kw: A.fifo_denoise(e, canvas_p, hop, sched, K, SEED, lookahead=1, **kw)),
+               "clips": (eng4, lambda e, hop, sched, K, **kw: A.fifo_denoise_clips(e, [canvas_p, canvas_p + 1.0], hop, sched, K,
+                                                                                   [SEED, SEED + 1], **kw))}
+    faults = [(dict(K=0), "n_slots"), (dict(K=True), "n_slots"), (dict(hop=0), "prompt_hop"), (dict(prompt_den=2), "prompt_interp"),
+              (dict(sched=torch.tensor([999, 749, 499, -1])), None), (dict(K=2 ** 32 // sl), re.escape("2**32 canvas positions"))]
+    calls = []
+    for eng in (eng2, eng4):
+        assert eng.slots == 2
+        for name in ("step_slots", "set_prompt"):
+            def spy(*a, _name=name, _real=getattr(eng, name), **kw):
+                calls.append(_name)
+                return _real(*a, **kw)
+            monkeypatch.setattr(eng, name, spy)
+    for name, (eng, run) in drivers.items():
+        for fault, match in faults:
+            for ctl in (dict(), dict(guidance_by_level=3.0)):
+                args = dict(dict(hop=hop, sched=sched, K=2), **fault)
+                with pytest.raises(ValueError, match=match):
+                    run(eng, args.pop("hop"), args.pop("sched"), args.pop("K"), **args, **ctl)
+                assert calls == [], (name, fault)
+                assert eng._scfg is None and eng._clip is None and eng._clips is None, (name, fault)
+    assert not torch.cuda.is_current_stream_capturing()
