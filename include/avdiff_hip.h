@@ -115,7 +115,7 @@ int avd_gemm_rmsfold_f32(const float* A, const float* W, const float* bias, cons
  * `out` are left untouched); pass N for the reference behaviour.
  * key_padding_mask: NULL, or bytes [B,N] with non-zero = this key is padding and gets no attention weight
  * (MMDiT.forward's key_padding_mask, mmdt.py:57-60,134-149).  A sample whose keys are ALL padded is undefined in the reference
- * (NaN); here it attends uniformly. */
+ * (NaN); here it attends uniformly: every query row of it is the mean of its N value rows, for any N. */
 int avd_attn_fwd_f32(const float* qkv, float* out, int B, int N, int H, int Dh, float scale,
                      int n_query, const uint8_t* key_padding_mask, avd_stream_t stream);
 

@@ -24,7 +24,9 @@ namespace avd {
 
 constexpr int ATT_DH = 64;
 constexpr int ATT_KT = 64;            // keys per tile
-constexpr float ATT_NEG = -1.0e30f;
+constexpr float ATT_NEG = -1.0e30f;   // score of a key the key_padding_mask hides
+constexpr float ATT_PAD = -2.0e30f;   // score of a filler key >= N: below ATT_NEG, so exp2(ATT_PAD - m) is 0 even when a sample's
+                                      // keys are all masked and its row maximum m is ATT_NEG (such a sample attends uniformly)
 constexpr float LOG2E = 1.4426950408889634f;
 
 #define AVD_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
@@ -150,8 +152,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_f32_kernel(const float* __res
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int key = kbase + mfma32_row(r, hi);
-                if (key >= N) s0[r] = ATT_NEG;
-                if (key + 32 >= N) s1[r] = ATT_NEG;
+                if (key >= N) s0[r] = ATT_PAD;
+                if (key + 32 >= N) s1[r] = ATT_PAD;
             }
         }
         if (kpm) {                           // key_padding_mask (mmdt.py:57-60): padded keys get no weight (wave-uniform branch)
