@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void layernorm_act_split3_kernel(const float* 
                 float t = (v[i][e] - mean) * rstd * gm[e] + bt[e];
                 if (GELU || act == AVD_ACT_GELU) t = gelu_erf(t);
                 else if (act == AVD_ACT_SILU) t = silu(t);
-                else if (act == AVD_ACT_RELU) t = fmaxf(t, 0.f);
+                else if (act == AVD_ACT_RELU) t = t != t ? t : fmaxf(t, 0.f);      // as layernorm_act_kernel: a NaN row stays NaN
                 else if (act == AVD_ACT_LEAKY_RELU) t = t > 0.f ? t : 0.1f * t;
                 o[e] = t;
             }

@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void layernorm_act_kernel(const float* x,     
                 float t = (v[i][e] - mean) * rstd * gm[e] + bt[e];
                 if (act == AVD_ACT_GELU) t = gelu_erf(t);
                 else if (act == AVD_ACT_SILU) t = silu(t);
-                else if (act == AVD_ACT_RELU) t = fmaxf(t, 0.f);
+                else if (act == AVD_ACT_RELU) t = t != t ? t : fmaxf(t, 0.f);       // nn.ReLU keeps NaN; fmaxf alone returns 0 for it
                 else if (act == AVD_ACT_LEAKY_RELU) t = t > 0.f ? t : 0.1f * t;       // nn.LeakyReLU(0.1), noise_heads.py:34
                 o[e] = t;
             }

@@ -184,6 +184,9 @@ class MultiModalNoiseHead(nn.Module):
             if d_in != self.input_dims[m]:
                 raise RuntimeError(f"{m}: expected last dim {self.input_dims[m]}, got {d_in}")
             rows = x.numel() // d_in
+            if rows == 0:      # an empty batch: nothing to launch, and no storage behind x or the output to hand to the library
+                outputs[m] = torch.empty(*x.shape[:-1], self.output_dims[m], device=x.device, dtype=torch.float32)
+                continue
             if self.matmul == "f16x2":      # standalone call: bound the rows from the data (one device sync)
                 from . import functional as Fn
                 amax = Fn.weight_bounds([x.reshape(rows, d_in)])[0][0]
